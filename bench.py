@@ -7,8 +7,11 @@ Contract (one JSON line on rank 0):
             graph already in HBM when the timed region starts (reset of the estimates included);
   value   = outer LM iterations executed by ALL ranks / max-over-ranks wall time  (weak scaling: each
             rank owns `--windows-per-gpu` independent windows, no data-path collective).
-Also reported: `roofline` of the dominant kernel (HIP-event durations measured in the timed region on
-the library's own stream) and `cpu_baseline` = the CPU oracle timed on this box (rank 0, N=1 only).
+A plain run sets up, warms up, times `--steps` steps and prints the line.  `--full` adds what takes runs
+of its own: `roofline` of the dominant kernel (HIP-event durations measured right behind the timed region
+on the library's own stream), the per-kernel calibration, the result gather check, `config5`, the per-frame
+call and `cpu_baseline` = the CPU oracle timed on this box with parity against it (rank 0, N=1 only).
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy.
 """
 import argparse
 import ctypes as C
@@ -87,10 +90,16 @@ def main():
     ap.add_argument("--tuning", choices=("auto", "latency", "throughput"), default="auto",
                     help="visfs_ba_set_tuning of the handles: auto = throughput for handles that hold a batch of resident windows (BASELINE config 5: the PCG "
                          "of a window in one workgroup), latency for a window on its own (the headline)")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beside the headline: per-kernel calibration and roofline, the result gather check, config 5, "
+                         "the per-frame call, the CPU baseline and parity against the oracle")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps write what the last timed step computed (rank 0's windows: poses, landmarks, outlier flags, "
+                         "per-edge chi2, solve statistics) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--config5", choices=("auto", "on", "off"), default="auto",
                     help="also measure BASELINE config 5's per-GPU share in the same run (8 resident C2-size windows per GPU sharing every launch, "
-                         "results all_gather'ed and checked): 'auto' = on, so every driver-run line (N = 1 included) carries a config-5 number")
+                         "results all_gather'ed and checked): 'auto' = on with --full, off otherwise")
     args = ap.parse_args()
 
     from visfs_amd import dist as vdist
@@ -158,67 +167,71 @@ def main():
         s.reset()
         rc, st = s.optimize()
         assert rc == abi.OK, rc
-        return st.iterations_run[0] + st.iterations_run[1], st
+        return st.iterations_run[0] + st.iterations_run[1], [st]
+
+    def run_batch(s):
+        s.batch_reset()
+        rc, stats = s.batch_optimize()
+        assert rc == abi.OK, rc
+        return sum(st.iterations_run[0] + st.iterations_run[1] for st in stats), stats
 
     def step():
+        """One timed step: (outer iterations of every resident window, their visfs_ba_stats in window order)."""
         if B == 1:
             return solve_one(solvers[0])
         if batched and H == 1:
-            solvers[0].batch_reset()
-            rc, stats = solvers[0].batch_optimize()
-            assert rc == abi.OK, rc
-            return sum(st.iterations_run[0] + st.iterations_run[1] for st in stats), stats[0]
-        if batched:
-            def run(s):
-                s.batch_reset()
-                rc, stats = s.batch_optimize()
-                assert rc == abi.OK, rc
-                return sum(st.iterations_run[0] + st.iterations_run[1] for st in stats), stats[0]
-            res = list(pool.map(run, solvers[:H]))
-            return sum(r[0] for r in res), res[0][1]
-        res = list(pool.map(solve_one, solvers))
-        return sum(r[0] for r in res), res[0][1]
+            return run_batch(solvers[0])
+        res = list(pool.map(run_batch if batched else solve_one, solvers[:H] if batched else solvers))
+        return sum(r[0] for r in res), [st for r in res for st in r[1]]
 
     for _ in range(args.warmup):
         step()
-    # untimed calibration pass: a HIP-event pair on every kernel launch → per-kernel breakdown + the dominant kernel
-    data_kernels = ("k_linearize", "k_schur_partial", "k_backsub", "k_pcg", "k_direct")
-    solvers[0].profile_enable(True)
-    for _ in range(3):
-        step()
-    calib = solvers[0].profile_read()
-    null_us = 1e3 * getattr(solvers[0], "null_pair_ms", 0.0)     # an empty event pair: the mechanism's own share of every duration
-    cand = [k for k in data_kernels if calib.get(k, {}).get("active_launches", 0) > 0]
-    dom = max(cand, key=lambda k: calib[k]["active_ms"]) if cand else None
-    # timed region: no instrumentation at all (event bookkeeping is host work between launches)
-    solvers[0].profile_enable(False)
+    dom, calib, cand, null_us = None, {}, [], 0.0
+    if args.full:
+        # untimed calibration pass: a HIP-event pair on every kernel launch → per-kernel breakdown + the dominant kernel
+        data_kernels = ("k_linearize", "k_schur_partial", "k_backsub", "k_pcg", "k_direct")
+        solvers[0].profile_enable(True)
+        for _ in range(3):
+            step()
+        calib = solvers[0].profile_read()
+        null_us = 1e3 * getattr(solvers[0], "null_pair_ms", 0.0)     # an empty event pair: the mechanism's own share of every duration
+        cand = [k for k in data_kernels if calib.get(k, {}).get("active_launches", 0) > 0]
+        dom = max(cand, key=lambda k: calib[k]["active_ms"]) if cand else None
+        # timed region: no instrumentation at all (event bookkeeping is host work between launches)
+        solvers[0].profile_enable(False)
     vdist.barrier(world, bar_dev)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     iters = 0
-    last = None
+    stats = None
     for k in range(args.steps):
-        n, last = step()
+        n, stats = step()
         iters += n
     torch.cuda.synchronize()
     vdist.barrier(world, bar_dev)
     t1 = time.perf_counter()
     elapsed = vdist.reduce_max(t1 - t0, world, red_dev)
     total_iters = vdist.reduce_sum(iters, world, red_dev)
+    last = stats[0] if stats else None
     graph_replay = bool(solvers[0].describe().get("graph_replayed", 0)) if B == 1 else False    # how the LAST timed solve was launched
-    # the dominant kernel's launch durations: the SAME steps once more, right behind the timed region, with a HIP-event pair
-    # attached to every launch of that kernel on the library's own stream (max(3, steps / 8) steps)
-    if dom:
-        solvers[0].profile_enable([dom])
-        for _ in range(max(3, args.steps // 8)):
-            step()
-        solvers[0].profile_enable(False)
-    # config 5 as north_star words it: after the timed region every rank's window results travel to every rank in ONE
-    # all_gather (RCCL over xGMI when the backend is nccl); rank 0 checks them against its own single-rank solves of the same windows
-    gathered = gather_and_check(args, prm, lib, solvers, batched, B, rank, world, dev, red_dev, vdist, abi, synth, backend, torch)
-    c5 = None
-    # 'auto' = always (round 4): the driver's plain `bench.py --gpus 1` line then carries a driver-timed config-5 number too
-    if args.config5 in ("on", "auto"):
+    # what the last timed step left in HBM, fetched before anything else runs on the resident windows
+    results = download_all(args, solvers, batched, B) if (args.full or args.dump_outputs) else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, results, stats)
+    gathered, c5 = None, None
+    if args.full:
+        # the dominant kernel's launch durations: the SAME steps once more, right behind the timed region, with a HIP-event pair
+        # attached to every launch of that kernel on the library's own stream (max(3, steps / 8) steps)
+        if dom:
+            solvers[0].profile_enable([dom])
+            for _ in range(max(3, args.steps // 8)):
+                step()
+            solvers[0].profile_enable(False)
+        # config 5 as north_star words it: after the timed region every rank's window results travel to every rank in ONE
+        # all_gather (RCCL over xGMI when the backend is nccl); rank 0 checks them against its own single-rank solves of the same windows
+        gathered = gather_and_check(args, prm, lib, [r[0] for r in results], batched, B, rank, world, dev, red_dev, vdist, abi, synth, backend, torch)
+    # 'auto' = on in a --full run: its line then carries a config-5 number too
+    if args.config5 == "on" or (args.config5 == "auto" and args.full):
         # (the headline line must survive whatever happens in this extra leg: every rank takes the same path through its collectives
         # unless its own solve fails, and a failure is reported instead of raised)
         try:
@@ -229,7 +242,7 @@ def main():
 
     if rank != 0:
         return
-    prof = solvers[0].profile_read()
+    prof = solvers[0].profile_read() if args.full else {}
     d = descs[0]
     roofline = None
     d["pcg_iters_per_launch"] = (last.pcg_iterations / max(1, last.trials_run[0] + last.trials_run[1])) if last is not None else 0
@@ -270,15 +283,15 @@ def main():
                    "parallelism": f"{world} rank(s) x {B} independent window(s), no data-path collective"
                                   + (f"; windows of a rank share every launch (blockIdx.y = window)" if batched else "")
                                   + (f"; {H} handles (streams / host threads) of {(B + H - 1) // H} windows each" if batched and H > 1 else "")},
-        "roofline": roofline,
-        "roofline_other_kernels": roofline_kernels,
         # the headline re-optimises ONE resident graph: from its second solve on the library replays the launch sequence as a hipGraph
         # (C2 +2 %, PROD +9 %); a per-frame visfs_ba_solve_window never gets that — its rate is in profiles/*e2e_breakdown.log
         "graph_replay": graph_replay,
-        "result_gather": gathered,
-        "config5": c5,
-        "kernel_us_per_step_calibration": {k: round(1e3 * v["total_ms"] / 3, 2) for k, v in calib.items()},
     }
+    if args.full:
+        out.update({"roofline": roofline, "roofline_other_kernels": roofline_kernels, "result_gather": gathered,
+                    "kernel_us_per_step_calibration": {k: round(1e3 * v["total_ms"] / 3, 2) for k, v in calib.items()}})
+    if c5 is not None:
+        out["config5"] = c5
     if last is not None and args.solver == 2:
         # whole-iteration view: bytes of one solve = sum over its two phases of (iterations x linearise bytes + damped
         # solves x (Schur + back-substitution + PCG bytes)), each phase with ITS active edge count (phase 2 runs without the edges the
@@ -299,14 +312,14 @@ def main():
                                      "frac": round(rate / 8000.0, 4), "floor_us_per_iteration": round(byts / 8e6, 2),
                                      "window_us_per_iteration": round(1e6 * elapsed * world * B / total_iters, 2),
                                      "aggregate_us_per_iteration_per_gpu": round(1e6 * elapsed * world / total_iters, 2)}
-    if world == 1 and B == 1:
+    if args.full and world == 1 and B == 1:
         # the drop-in's real call (Estimator.cpp:254): host buffers in, results out, one handle across frames — reported beside the
         # resident headline, never as `value` (it crosses PCIe both ways)
         try:
             out["per_frame_call"] = per_frame_call(args, prm)
         except Exception as e:
             out["per_frame_call"] = {"error": str(e)[:120]}
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args, prm)
         # parity of the timed configuration against the oracle (max pose error metric of BASELINE.json)
         out["max_pose_err_vs_oracle"] = parity_vs_oracle(args, prm, solvers[0])
@@ -384,18 +397,52 @@ def config5_record(args, lib, rank, world, dev, red_dev, bar_dev, vdist, abi, sy
     return rec if rank == 0 else None
 
 
-def gather_and_check(args, prm, lib, solvers, batched, B, rank, world, dev, red_dev, vdist, abi, synth, backend, torch):
-    """One all_gather of every window's optimised poses ([B, Np, 7] fp64 per rank) over the bench's process group; rank 0 re-solves
-    the FIRST window of every rank itself (same chunking: as a batch member when the ranks ran batches) and compares bit for bit —
-    the kernels are run-to-run and device-to-device deterministic (fixed-order reductions, no floating-point atomics)."""
-    poses = []
+def download_all(args, solvers, batched, B):
+    """(poses, landmarks, outlier flags, per-edge chi2) of every resident window of this rank, in window order."""
+    out = []
     for b in range(B):
         if batched:
             per = (B + max(1, min(args.handles, B)) - 1) // max(1, min(args.handles, B))     # windows per handle (--handles)
-            pose = solvers[b // per].batch_download(b % per)[0]
+            out.append(solvers[b // per].batch_download(b % per))
         else:
-            pose = solvers[b].download()[0]
-        poses.append(pose)
+            out.append(solvers[b].download())
+    return out
+
+
+STATS_FIELDS = ("status", "iterations_run", "trials_run", "pcg_iterations", "n_outliers", "chi2_initial", "chi2_phase1", "chi2_final",
+                "n_active_edges", "pcg_iterations_phase", "solver_fallback")
+
+
+def dump_outputs(path, results, stats, budget=60 * 10**6):
+    """--dump-outputs: window<b>_{poses,points,outliers,edge_chi2,stats}.npy of rank 0's windows as the last timed step left them
+    (float64; the uint8 outlier flags as float32; stats = STATS_FIELDS flattened).  Above `budget` bytes in all (64 MB with the file
+    headers), every array but the stats keeps a fixed, seeded sample of its rows."""
+    arrays = {}
+    for b, ((pose, pt, outl, chi2), st) in enumerate(zip(results, stats)):
+        flat = []
+        for f in STATS_FIELDS:
+            v = getattr(st, f)
+            flat += list(v) if hasattr(v, "__len__") else [v]
+        arrays.update({f"window{b}_poses": pose.astype(np.float64), f"window{b}_points": pt.astype(np.float64),
+                       f"window{b}_outliers": outl.astype(np.float32), f"window{b}_edge_chi2": chi2.astype(np.float64),
+                       f"window{b}_stats": np.array(flat, np.float64)})
+    fixed = sum(a.nbytes for name, a in arrays.items() if name.endswith("_stats"))
+    total = sum(a.nbytes for a in arrays.values())
+    if total > budget:
+        keep = (budget - fixed) / (total - fixed)
+        for name, a in arrays.items():
+            if not name.endswith("_stats"):
+                rows = np.random.default_rng(12345).permutation(len(a))[:max(1, int(len(a) * keep))]
+                arrays[name] = a[np.sort(rows)]
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def gather_and_check(args, prm, lib, poses, batched, B, rank, world, dev, red_dev, vdist, abi, synth, backend, torch):
+    """One all_gather of every window's optimised poses ([B, Np, 7] fp64 per rank) over the bench's process group; rank 0 re-solves
+    the FIRST window of every rank itself (same chunking: as a batch member when the ranks ran batches) and compares bit for bit —
+    the kernels are run-to-run and device-to-device deterministic (fixed-order reductions, no floating-point atomics)."""
     local = torch.from_numpy(np.stack(poses, 0))
     if world == 1:
         return {"backend": None, "ranks_seen": [0], "windows": B, "bytes": int(local.numel() * 8), "checked_windows": 0, "bit_identical": None}

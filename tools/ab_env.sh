@@ -4,13 +4,13 @@
 O=gpurun_out; TAG=$1; shift
 mkdir -p $O
 run_all() {
-  python bench.py --steps 60 --warmup 10 --no-cpu-baseline >> $O/${TAG}_ab.log 2>&1
-  python bench.py --config C3 --steps 40 --warmup 5 --no-cpu-baseline >> $O/${TAG}_ab.log 2>&1
-  python bench.py --config C4 --steps 10 --warmup 2 --no-cpu-baseline >> $O/${TAG}_ab.log 2>&1
-  python bench.py --config C4R --steps 10 --warmup 2 --no-cpu-baseline >> $O/${TAG}_ab.log 2>&1
-  python bench.py --config C5 --windows-per-gpu 8 --steps 10 --warmup 2 --no-cpu-baseline >> $O/${TAG}_ab.log 2>&1
-  python bench.py --config C5 --windows-per-gpu 16 --steps 10 --warmup 2 --no-cpu-baseline >> $O/${TAG}_ab.log 2>&1
-  python bench.py --config PROD --iterations 10 --steps 100 --warmup 10 --no-cpu-baseline >> $O/${TAG}_ab.log 2>&1
+  python bench.py --steps 60 --warmup 10 --no-cpu-baseline --full >> $O/${TAG}_ab.log 2>&1
+  python bench.py --config C3 --steps 40 --warmup 5 --no-cpu-baseline --full >> $O/${TAG}_ab.log 2>&1
+  python bench.py --config C4 --steps 10 --warmup 2 --no-cpu-baseline --full >> $O/${TAG}_ab.log 2>&1
+  python bench.py --config C4R --steps 10 --warmup 2 --no-cpu-baseline --full >> $O/${TAG}_ab.log 2>&1
+  python bench.py --config C5 --windows-per-gpu 8 --steps 10 --warmup 2 --no-cpu-baseline --full >> $O/${TAG}_ab.log 2>&1
+  python bench.py --config C5 --windows-per-gpu 16 --steps 10 --warmup 2 --no-cpu-baseline --full >> $O/${TAG}_ab.log 2>&1
+  python bench.py --config PROD --iterations 10 --steps 100 --warmup 10 --no-cpu-baseline --full >> $O/${TAG}_ab.log 2>&1
 }
 echo "== default" >> $O/${TAG}_ab.log
 run_all

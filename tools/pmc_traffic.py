@@ -3,7 +3,7 @@
 import json
 import sys
 
-METHOD = ("rocprofv3 --kernel-trace --pmc FETCH_SIZE and --pmc WRITE_SIZE in SEPARATE passes over `bench.py --config CFG --steps 4 --warmup 1 "
+METHOD = ("rocprofv3 --kernel-trace --pmc FETCH_SIZE and --pmc WRITE_SIZE in SEPARATE passes over `bench.py --full --config CFG --steps 4 --warmup 1 "
           "--no-cpu-baseline` (MI355X_MICROARCH.md §HBM / rocprofv3 PMC slots); per-kernel averages over the dispatches that did work; counters are "
           "KiB; traffic = (2*FETCH_SIZE + WRITE_SIZE)*1024: gfx950 FETCH_SIZE reports half of the fetched bytes of a coalesced stream (guide) — "
           "checked on k_eval, whose coalesced inputs are 1.85 MB and whose FETCH_SIZE reads 0.96 MB; Infinity-Cache hits are counted, so this is "
