@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define VISFS_BA_ABI_VERSION 8
+#define VISFS_BA_ABI_VERSION 9
 
 /* ---- status codes ------------------------------------------------------- */
 /* The reference signals failure by returning an EMPTY pose map
@@ -45,7 +45,8 @@ enum {
     VISFS_BA_ERR_BAD_ARGUMENT = 6,
     VISFS_BA_ERR_UNSUPPORTED = 7,  /* an unknown Optimizer/Framework, a size beyond a kernel's limits, ... */
     VISFS_BA_ERR_DEVICE = 8,       /* HIP runtime error / no MI355X present */
-    VISFS_BA_ERR_NOT_LOADED = 9    /* no graph resident in the handle */
+    VISFS_BA_ERR_NOT_LOADED = 9,   /* no graph resident in the handle */
+    VISFS_BA_ERR_SINGULAR = 10     /* ABI 9, covariances: no pose is fixed (free gauge), or a pivot of the factorisation is not positive */
 };
 
 /* ---- parameters: the eight Optimizer keys (Parameters.h:184-191, read at Optimizer.cpp:37-54) */
@@ -313,6 +314,39 @@ int visfs_ba_hook_dogleg_script(int32_t max_iter, double cost0, double x_norm0, 
  * scaled space: s1 = ||g_s||^2, s2 = ||gn_s||^2, s3 = g_s . gn_s, jv2 = ||J (g / m)||^2.  out = { A, B, step norm, model cost change }:
  * the step is A (g / m) + B dn in the unscaled variables. */
 int visfs_ba_hook_dogleg_combine(double s1, double s2, double s3, double jv2, double radius, double mu, double out[4]);
+
+/* ---- marginal covariances (ABI 9) ----------------------------------------------------------------------------------------------
+ * The reference publishes an identity matrix as the covariance of a bundle-adjusted pose (Estimator.cpp:301-302); g2o's
+ * SparseOptimizer::computeMarginals and ceres::Covariance are what its users call instead.  Definition: the covariance is the inverse
+ * of the Gauss-Newton Hessian of the g2o branch AT THE RESIDENT ESTIMATE,
+ *     H = sum_e J_e^T (rho'_e Omega_e) J_e
+ * over the ACTIVE edges (level 0 after the outlier pass, not all vertices fixed: stereo, odometry and laser), without lambda, in the
+ * variables [free poses | free landmarks] — the fixed poses fix the gauge.  Pose blocks are in the state's own tangent space (dt, dtheta)
+ * as CameraPose::update applies it (OptimizeTypeDefine.cpp:7-14, the order of VISFS_BA_BUF_DX_POSE); landmark blocks are world xyz.
+ * Computed on the GPU from the band of S^-1 (S: the Schur complement at lambda = 0): the factor and the band of Sigma by block selected
+ * inversion, then the landmark marginals Sigma_ll = D^-1 + D^-1 (sum_{i,j in obs(l)} W_il^T Sigma_ij W_jl) D^-1 (D = H_ll, W = H_pl).
+ * Special values: fixed poses and fixed landmarks 0; free poses without an active edge (outside g2o's active set) NaN; landmarks
+ * without an active edge NaN.  Every output block is row-major.  The call changes nothing a later call sees: the estimate, the edge
+ * levels and the LM state are as before; its device scratch is allocated at the first call on a handle.
+ * Returns VISFS_BA_ERR_UNSUPPORTED for windows whose reduced system has no band plan (graph_info.band_blocks < 0 with the direct
+ * solver, e.g. a block half-bandwidth above 21), for windows on the opt-in fused single-workgroup path (VISFS_BA_FUSED=1,
+ * graph_info.fused_path = 1), for Optimizer/Framework=1 (the Ceres branch) and for handles holding a batch.  On any error the output
+ * buffers are left as they were. */
+/* The resident graph of visfs_ba_graph_upload / visfs_ba_optimize, graph order.  pose_cov [n_poses][36]; pose_cross [n_poses - 1][36] or
+ * NULL: Sigma_{i,i+1} = Cov(x_i, x_{i+1}) (the relative motion's covariance needs it); point_cov [n_points][9] or NULL. */
+int visfs_ba_graph_covariance(visfs_ba_handle* h, double* pose_cov, double* pose_cross, double* point_cov);
+/* The last successful visfs_ba_solve_window on h, in that window's order: pose blocks as the covariance of (dp, dphi) of the robot pose
+ * Twr (visfs_ba_pose_cov_to_world); points with point_used == 0 NaN.  VISFS_BA_ERR_NOT_LOADED without such a solve (passthrough,
+ * failure, or a graph or batch uploaded since).  pose_cov_wr [n_poses][36]; point_cov [n_points][9] or NULL. */
+int visfs_ba_window_covariance(visfs_ba_handle* h, double* pose_cov_wr, double* point_cov);
+/* Host only: a pose-state covariance (tq: Tcw [tx ty tz qx qy qz qw], tangent (dt, dtheta)) as the covariance of (dp, dphi) with
+ * Twr' = (Exp(dphi) R_wr, p_wr + dp) — world-frame translation and rotation about the world axes (nav_msgs' convention), Twr =
+ * Tcw^-1 Trc^-1 as visfs_ba_unpack_pose forms it.  First order: cov_wr = J cov_tq J^T, J = [[-R_cw^T, [p_wr]x R_cw^T], [0, -R_cw^T]]. */
+void visfs_ba_pose_cov_to_world(const double tq[7], const double Trc[12], const double cov_tq[36], double cov_wr[36]);
+/* Host-only hook: the banded factorisation and the selected inversion of the kernels, compiled for the host.  S_band, Sigma_band:
+ * [n][B + 1][36], block (I, I - d) of the lower band at [I][d] (slots with I - d < 0 ignored / written as 0).  VISFS_BA_ERR_SINGULAR
+ * when S is not positive definite. */
+int visfs_ba_hook_band_selinv(int32_t n, int32_t B, const double* S_band, double* Sigma_band);
 
 /* ---- measurement hooks (bench.py) ------------------------------------------ */
 /* Sizes of the resident graph and of the index structures built at upload. */

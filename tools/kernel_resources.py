@@ -1,15 +1,18 @@
 #!/usr/bin/env python3
-"""Register / scratch / occupancy table of every kernel in ba_kernels.hip (hipcc -Rpass-analysis=kernel-resource-usage, device only).
+"""Register / scratch / occupancy table of every kernel in ba_kernels.hip and ba_cov.hip (hipcc -Rpass-analysis=kernel-resource-usage,
+device only).
 usage: tools/kernel_resources.py [filter-substring ...]   (extra -D flags through VISFS_BA_EXTRA_FLAGS; KRES_TXT=<file> reuses a saved remark dump)"""
 import os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-src = os.path.join(ROOT, "visfs_amd", "csrc", "ba_kernels.hip")
+srcs = [os.path.join(ROOT, "visfs_amd", "csrc", f) for f in ("ba_kernels.hip", "ba_cov.hip")]
 if os.environ.get("KRES_TXT"):
     txt = open(os.environ["KRES_TXT"]).read()
 else:
-    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", src, "-o", "/tmp/_kres.o"]
-    cmd += os.environ.get("VISFS_BA_EXTRA_FLAGS", "").split()
-    txt = subprocess.run(cmd, capture_output=True, text=True).stderr
+    txt = ""
+    for src in srcs:
+        cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", src, "-o", "/tmp/_kres.o"]
+        cmd += os.environ.get("VISFS_BA_EXTRA_FLAGS", "").split()
+        txt += subprocess.run(cmd, capture_output=True, text=True).stderr
 rows, cur = [], None
 for line in txt.splitlines():
     m = re.search(r"remark:\s+([A-Za-z][\w /\[\]]*?): (\S+) \[-Rpass", line)

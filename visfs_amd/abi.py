@@ -8,13 +8,13 @@ import ctypes as C
 
 import numpy as np
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 TUNE_LATENCY, TUNE_THROUGHPUT = 0, 1            # visfs_ba_set_tuning
 MAX_TRACE = 64
 
 # status codes (include/visfs_ba.h)
 OK, PASSTHROUGH, ERR_TOO_FEW_POSES, ERR_NAN_CHI2, ERR_HUGE_CHI2_1, ERR_HUGE_CHI2_2, \
-    ERR_BAD_ARGUMENT, ERR_UNSUPPORTED, ERR_DEVICE, ERR_NOT_LOADED = range(10)
+    ERR_BAD_ARGUMENT, ERR_UNSUPPORTED, ERR_DEVICE, ERR_NOT_LOADED, ERR_SINGULAR = range(11)
 
 # stage buffer ids
 BUF_OBS_ERR, BUF_OBS_CHI2, BUF_OBS_WEIGHT, BUF_HPL, BUF_HLL, BUF_BL, BUF_HPP, BUF_BP, \

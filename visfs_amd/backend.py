@@ -25,6 +25,7 @@ EXPORTS = [
     "visfs_ba_stage_trial", "visfs_ba_stage_fetch", "visfs_ba_graph_describe", "visfs_ba_profile_enable",
     "visfs_ba_profile_read", "visfs_ba_batch_upload", "visfs_ba_batch_reset", "visfs_ba_batch_optimize", "visfs_ba_batch_download",
     "visfs_ba_create_error", "visfs_ba_set_tuning", "visfs_ba_hook_lm_script", "visfs_ba_hook_ceres_script", "visfs_ba_hook_dogleg_script", "visfs_ba_hook_dogleg_combine", "visfs_ba_solve_batch_sharded", "visfs_ba_stage_commit", "visfs_ba_stage_begin_phase", "visfs_ba_stage_mark_outliers",
+    "visfs_ba_graph_covariance", "visfs_ba_window_covariance", "visfs_ba_pose_cov_to_world", "visfs_ba_hook_band_selinv",
 ]
 
 _lib = None
@@ -100,6 +101,14 @@ def load_library():
     lib.visfs_ba_hook_dogleg_combine.argtypes = [C.c_double] * 6 + [_pd]
     lib.visfs_ba_hook_dogleg_combine.restype = C.c_int
     lib.visfs_ba_hook_ceres_script.restype = C.c_int
+    lib.visfs_ba_graph_covariance.argtypes = [C.c_void_p, _pd, _pd, _pd]
+    lib.visfs_ba_graph_covariance.restype = C.c_int
+    lib.visfs_ba_window_covariance.argtypes = [C.c_void_p, _pd, _pd]
+    lib.visfs_ba_window_covariance.restype = C.c_int
+    lib.visfs_ba_pose_cov_to_world.argtypes = [_pd, _pd, _pd, _pd]
+    lib.visfs_ba_pose_cov_to_world.restype = None
+    lib.visfs_ba_hook_band_selinv.argtypes = [C.c_int32, C.c_int32, _pd, _pd]
+    lib.visfs_ba_hook_band_selinv.restype = C.c_int
     if lib.visfs_ba_abi_version() != abi.ABI_VERSION:
         raise BackendError("ABI version mismatch between visfs_amd/abi.py and libvisfs_ba_hip.so")
     _lib = lib
@@ -190,6 +199,25 @@ class Solver:
         out = np.zeros(max(g.n_obs, 1), np.uint8); chi = np.zeros(max(g.n_obs, 1))
         self._check(self.lib.visfs_ba_graph_download(self.h, _p(pose), _p(pt), out.ctypes.data_as(_pu8), _p(chi)), "graph_download")
         return pose, pt[:g.n_points], out[:g.n_obs], chi[:g.n_obs]
+
+    # ---- marginal covariances (include/visfs_ba.h, ABI 9)
+    def covariance(self, points=True, cross=False):
+        """visfs_ba_graph_covariance on the resident graph: (pose_cov [n_poses, 6, 6], pose_cross [n_poses - 1, 6, 6] or None,
+        point_cov [n_points, 3, 3] or None).  Raises BackendError on any status but OK."""
+        g = self.gb
+        pose = np.zeros((g.n_poses, 6, 6))
+        cr = np.zeros((max(g.n_poses - 1, 1), 6, 6)) if cross else None
+        pt = np.zeros((max(g.n_points, 1), 3, 3)) if points else None
+        self._check(self.lib.visfs_ba_graph_covariance(self.h, _p(pose), _p(cr) if cross else None, _p(pt) if points else None),
+                    "graph_covariance")
+        return pose, (cr[:g.n_poses - 1] if cross else None), (pt[:g.n_points] if points else None)
+
+    def window_covariance(self, n_poses, n_points, points=True):
+        """visfs_ba_window_covariance for the last successful solve_window: (pose_cov_wr [n_poses, 6, 6], point_cov [n_points, 3, 3] or None)."""
+        pose = np.zeros((max(n_poses, 1), 6, 6))
+        pt = np.zeros((max(n_points, 1), 3, 3)) if points else None
+        self._check(self.lib.visfs_ba_window_covariance(self.h, _p(pose), _p(pt) if points else None), "window_covariance")
+        return pose[:n_poses], (pt[:n_points] if points else None)
 
     # ---- measurement hooks
     def describe(self):

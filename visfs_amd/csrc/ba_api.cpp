@@ -14,6 +14,7 @@
 #include <cstring>
 #include <atomic>
 #include <functional>
+#include <limits>
 #include <map>
 #include <memory>
 #include <condition_variable>
@@ -23,6 +24,7 @@
 #include <vector>
 
 #include "../../include/visfs_ba.h"
+#include "ba_cov.hpp"
 #include "ba_kernels.hpp"
 #include "worker_pool.hpp"
 
@@ -147,6 +149,9 @@ struct Workspace {
     std::vector<ProfRec> recs;
     std::vector<float> durs[VISFS_BA_K_COUNT];
     int64_t active[VISFS_BA_K_COUNT] = { 0 };
+    // marginal covariances (visfs_ba_graph_covariance): device scratch allocated at the first call, never at upload — the factor and
+    // the band of Sigma ([Npf][band_B + 1][36] each), the landmark marginals ([Nl][9]) and the pivot flag
+    char* d_cov = nullptr; size_t d_cov_cap = 0;
     int n6() const { return 6 * g.Npf; }
 };
 
@@ -208,6 +213,9 @@ struct visfs_ba_handle {
     std::vector<hipStream_t> part_stream;
     std::unique_ptr<WorkerPool> pool;              // host threads of the window layer (created at the first visfs_ba_solve_window)
     bool pool_tried = false;
+    bool batch_last = false;                       // the last upload was a batch (visfs_ba_batch_upload / visfs_ba_solve_batch): no covariances
+    bool window_ok = false;                        // the resident graph is the last visfs_ba_solve_window's, solved successfully
+    double window_Trc[12] = { 0 };                 // ... its camera-to-robot transform (visfs_ba_window_covariance)
 };
 
 namespace {
@@ -260,6 +268,7 @@ void ws_release(Workspace& w) {
     for (auto& fg : w.frame_graphs) if (fg.exec) (void)hipGraphExecDestroy(fg.exec);
     if (w.d_state) (void)hipFree(w.d_state);
     if (w.d_graph) (void)hipFree(w.d_graph);
+    if (w.d_cov) (void)hipFree(w.d_cov);
     if (w.h_graph) (void)hipHostFree(w.h_graph);
     if (w.stream) (void)hipStreamDestroy(w.stream);
     w = Workspace{};
@@ -2009,6 +2018,92 @@ int batch_optimize_group(visfs_ba_handle* h, const std::vector<int>& members) {
 }
 
 
+// ---------------------------------------------------------------- marginal covariances (include/visfs_ba.h, ABI 9)
+// Re-linearise the resident estimate at lambda = 0 with the production kernels (the H_pl tiles under `debug`), factor S on its band,
+// invert the band, optionally the landmark marginals; the LM state is saved before and written back after, so the estimate, the edge
+// levels and every later call are as without this one.  Outputs in graph order (see the header for the special values).
+int ws_covariance(visfs_ba_handle* h, Workspace& w, double* pose_cov, double* pose_cross, double* point_cov) {
+    if (h->prm.framework != 0) { h->err = "covariances are computed for the g2o branch only (Optimizer/Framework=0)"; return VISFS_BA_ERR_UNSUPPORTED; }
+    if (h->batch_last) { h->err = "covariances of batched windows are not supported"; return VISFS_BA_ERR_UNSUPPORTED; }
+    if (!w.loaded) { h->err = "no graph resident"; return VISFS_BA_ERR_NOT_LOADED; }
+    const DeviceGraph& g0 = w.g;
+    const int Np = g0.Np, Nl = g0.Nl, Npf = g0.Npf;
+    if (Npf == Np) { h->err = "no pose is fixed: the gauge is free and the Hessian singular"; return VISFS_BA_ERR_SINGULAR; }
+    if (Npf > 0 && g0.band_B < 0) { h->err = "the reduced system has no band plan (block half-bandwidth above the banded solver's limit): no covariance"; return VISFS_BA_ERR_UNSUPPORTED; }
+    if (w.fused) { h->err = "covariances of windows on the fused single-workgroup path (VISFS_BA_FUSED=1) are not supported"; return VISFS_BA_ERR_UNSUPPORTED; }
+    HIP_TRY(h, hipSetDevice(h->device));
+    const int W = g0.band_B + 1;
+    const size_t nband = Npf > 0 ? (size_t)Npf * W * 36 : 0;
+    const size_t off_sig = ((nband * 8 + 255) & ~size_t(255)), off_pt = off_sig + ((nband * 8 + 255) & ~size_t(255));
+    const size_t off_flag = off_pt + (((size_t)std::max(Nl, 1) * 72 + 255) & ~size_t(255)), bytes = off_flag + 256;
+    if (w.d_cov_cap < bytes) {
+        HIP_TRY(h, hipStreamSynchronize(w.stream));
+        if (w.d_cov) (void)hipFree(w.d_cov);
+        w.d_cov = nullptr; w.d_cov_cap = 0;
+        HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&w.d_cov), bytes));
+        w.d_cov_cap = bytes;
+    }
+    double* dF = reinterpret_cast<double*>(w.d_cov);
+    double* dSg = reinterpret_cast<double*>(w.d_cov + off_sig);
+    double* dPt = reinterpret_cast<double*>(w.d_cov + off_pt);
+    int* dFail = reinterpret_cast<int*>(w.d_cov + off_flag);
+    int rc = ws_read_state(h, w);
+    if (rc != VISFS_BA_OK) return rc;
+    const LmState saved = *w.h_state;
+    DeviceGraph g = w.g;
+    g.debug = 1;                                          // k_linearize writes the H_pl tiles the landmark marginals need
+    launch_stage_arm(g, 0.0, MODE_LIN, w.stream);
+    launch_linearize(g, w.stream);
+    launch_lin_finalize(g, 1, w.stream);
+    launch_stage_arm(g, 0.0, MODE_TRIAL, w.stream);
+    launch_schur_partial(g, w.stream);
+    if (w.small_solve) launch_small_solve(g, h->prm.solver, w.stream);     // (S, H_pp of a reduced system <= 64 x 64 come from this launch)
+    else if (!g.fin_arrive) launch_schur_finalize(g, w.stream);
+    HIP_TRY(h, hipMemsetAsync(dFail, 0, sizeof(int), w.stream));
+    if (Npf > 0) {
+        launch_band_factor(g, dF, dFail, w.stream);
+        launch_band_selinv(g, dF, dSg, dFail, w.stream);      // (both return at once behind a failed pivot)
+    }
+    if (point_cov) launch_point_cov(g, dSg, dPt, dFail, w.stream);
+    HIP_TRY(h, hipGetLastError());
+    std::vector<double> sig(nband), hpp((size_t)Npf * 36), pts(point_cov ? (size_t)Nl * 9 : 0);
+    int fail = 0;
+    if (Npf > 0) {
+        HIP_TRY(h, hipMemcpyAsync(sig.data(), dSg, nband * 8, hipMemcpyDeviceToHost, w.stream));
+        HIP_TRY(h, hipMemcpyAsync(hpp.data(), g.Hpp, hpp.size() * 8, hipMemcpyDeviceToHost, w.stream));
+    }
+    HIP_TRY(h, hipMemcpyAsync(&fail, dFail, sizeof(int), hipMemcpyDeviceToHost, w.stream));
+    if (point_cov && Nl) HIP_TRY(h, hipMemcpyAsync(pts.data(), dPt, (size_t)Nl * 72, hipMemcpyDeviceToHost, w.stream));
+    HIP_TRY(h, hipStreamSynchronize(w.stream));
+    // the LM state as it was (the arm / trial launches above rewrote its mode, lambda, linearisation set, ...)
+    *w.h_state = saved;
+    HIP_TRY(h, hipMemcpyAsync(w.g.st, w.h_state, sizeof(LmState), hipMemcpyHostToDevice, w.stream));
+    HIP_TRY(h, hipStreamSynchronize(w.stream));
+    if (fail) { h->err = "the Hessian at the estimate is not positive definite (a pivot of its factorisation)"; return VISFS_BA_ERR_SINGULAR; }
+    // (the caller's buffers are written only from here on: an error leaves them as they were)
+    if (point_cov && Nl) std::memcpy(point_cov, pts.data(), (size_t)Nl * 72);
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    // free poses outside g2o's active set: no active edge, H_pp's diagonal is zero (k_schur_finalize pins their block of S to I)
+    auto pinned = [&](int a) { const double* d = hpp.data() + 36 * (size_t)a; for (int q = 0; q < 6; ++q) if (d[7 * q] != 0.0) return false; return true; };
+    for (int i = 0; i < Np; ++i) {
+        double* o = pose_cov + 36 * (size_t)i;
+        const int a = w.pose_free[i];
+        if (a < 0) { std::fill(o, o + 36, 0.0); continue; }
+        if (pinned(a)) { std::fill(o, o + 36, nan); continue; }
+        std::memcpy(o, cov::blk(sig.data(), W, a, 0), 36 * 8);
+    }
+    if (pose_cross)
+        for (int i = 0; i + 1 < Np; ++i) {
+            double* o = pose_cross + 36 * (size_t)i;
+            const int a = w.pose_free[i], b = w.pose_free[i + 1];
+            if (a < 0 || b < 0) { std::fill(o, o + 36, 0.0); continue; }
+            if (pinned(a) || pinned(b)) { std::fill(o, o + 36, nan); continue; }
+            // Sigma_{a,b} (b = a + 1) = Sigma_{b,a}^T; outside the band (B = 0: S block diagonal) it is zero
+            for (int r = 0; r < 6; ++r) for (int c = 0; c < 6; ++c) o[6 * r + c] = (b - a <= W - 1) ? cov::sym_at(sig.data(), W, a, b, r, c) : 0.0;
+        }
+    return VISFS_BA_OK;
+}
+
 }  // namespace
 
 // ====================================================================== exported C ABI
@@ -2113,6 +2208,7 @@ void visfs_ba_unpack_pose(const double* tq, const double* Trc, double* Twr_out) 
 int visfs_ba_graph_upload(visfs_ba_handle* h, const visfs_ba_graph* g) {
     if (!h || !g) return VISFS_BA_ERR_BAD_ARGUMENT;
     if (const char* why = framework_refusal(h->prm)) { h->err = why; return VISFS_BA_ERR_UNSUPPORTED; }
+    h->batch_last = false; h->window_ok = false;
     return guarded(h, [&]() { return ws_upload(h, h->ws, g); });
 }
 
@@ -2138,12 +2234,16 @@ int visfs_ba_graph_download(visfs_ba_handle* h, double* pose_tq, double* point_x
 
 int visfs_ba_solve_window(visfs_ba_handle* h, const visfs_ba_window* w, visfs_ba_result* r) {
     if (!h || !w || !r) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded(h, [&]() { return solve_window_on(h, h->ws, w, r); });
+    h->batch_last = false; h->window_ok = false;
+    const int rc = guarded(h, [&]() { return solve_window_on(h, h->ws, w, r); });
+    if (rc == VISFS_BA_OK) { h->window_ok = true; std::memcpy(h->window_Trc, w->Trc, sizeof(h->window_Trc)); }      // (visfs_ba_window_covariance)
+    return rc;
 }
 
 int visfs_ba_solve_batch(visfs_ba_handle* h, int32_t n, const visfs_ba_window* const* w, visfs_ba_result* const* r) {
     if (!h || n < 0 || (n > 0 && (!w || !r))) return VISFS_BA_ERR_BAD_ARGUMENT;
     for (int i = 0; i < n; ++i) if (!w[i] || !r[i]) return VISFS_BA_ERR_BAD_ARGUMENT;
+    h->batch_last = true; h->window_ok = false;
     // Independent windows (BASELINE config 5).  Host work (graph build, upload, write-back) runs on up to 8
     // threads, one workspace per window; the optimisation itself is ONE sequence of launches per group of windows with the
     // same launch-geometry class, blockIdx.y = window (batch_optimize).  Windows that cannot share launches (direct solver on
@@ -2243,6 +2343,7 @@ int visfs_ba_batch_upload(visfs_ba_handle* h, int32_t n, const visfs_ba_graph* c
     if (!h || n < 0 || (n > 0 && !graphs)) return VISFS_BA_ERR_BAD_ARGUMENT;
     for (int i = 0; i < n; ++i) if (!graphs[i]) return VISFS_BA_ERR_BAD_ARGUMENT;
     if (const char* why = framework_refusal(h->prm)) { h->err = why; return VISFS_BA_ERR_UNSUPPORTED; }
+    h->batch_last = true; h->window_ok = false;
     return guarded(h, [&]() -> int {
         while ((int)h->batch.size() < n) { h->batch.push_back(new Workspace()); h->batch.back()->batch_member = true; }
         for (int i = 0; i < n; ++i) h->batch[i]->batch_hint = n;
@@ -2583,6 +2684,80 @@ int visfs_ba_hook_dogleg_script(int32_t max_iter, double cost0, double x_norm0, 
 int visfs_ba_hook_dogleg_combine(double s1, double s2, double s3, double jv2, double radius, double mu, double out[4]) {
     if (!out) return VISFS_BA_ERR_BAD_ARGUMENT;
     dogleg_combine(s1, s2, s3, jv2, radius, mu, out[0], out[1], out[2], out[3]);
+    return VISFS_BA_OK;
+}
+
+// ---------------------------------------------------------------- marginal covariances (ABI 9)
+int visfs_ba_graph_covariance(visfs_ba_handle* h, double* pose_cov, double* pose_cross, double* point_cov) {
+    if (!h || !pose_cov) return VISFS_BA_ERR_BAD_ARGUMENT;
+    return guarded(h, [&]() { return ws_covariance(h, h->ws, pose_cov, pose_cross, point_cov); });
+}
+
+int visfs_ba_window_covariance(visfs_ba_handle* h, double* pose_cov_wr, double* point_cov) {
+    if (!h || !pose_cov_wr) return VISFS_BA_ERR_BAD_ARGUMENT;
+    if (h->prm.framework != 0) { h->err = "covariances are computed for the g2o branch only (Optimizer/Framework=0)"; return VISFS_BA_ERR_UNSUPPORTED; }
+    if (h->batch_last) { h->err = "covariances of batched windows are not supported"; return VISFS_BA_ERR_UNSUPPORTED; }
+    if (!h->window_ok || !h->ws.loaded) { h->err = "no successful visfs_ba_solve_window on this handle since its last upload"; return VISFS_BA_ERR_NOT_LOADED; }
+    return guarded(h, [&]() -> int {
+        Workspace& w = h->ws;
+        const int Np = w.g.Np, Nl = w.g.Nl;
+        std::vector<double> cov((size_t)Np * 36), tq((size_t)Np * 7);
+        int rc = ws_covariance(h, w, cov.data(), nullptr, point_cov);
+        if (rc != VISFS_BA_OK) return rc;
+        rc = ws_download(h, w, tq.data(), nullptr, nullptr, nullptr);
+        if (rc != VISFS_BA_OK) return rc;
+        for (int i = 0; i < Np; ++i) visfs_ba_pose_cov_to_world(tq.data() + 7 * i, h->window_Trc, cov.data() + 36 * i, pose_cov_wr + 36 * i);
+        if (point_cov)
+            for (int l = 0; l < Nl; ++l)
+                if (!w.pk.point_used[l]) std::fill(point_cov + 9 * (size_t)l, point_cov + 9 * (size_t)l + 9, std::numeric_limits<double>::quiet_NaN());
+        return (int)VISFS_BA_OK;
+    });
+}
+
+void visfs_ba_pose_cov_to_world(const double tq[7], const double Trc[12], const double cov_tq[36], double cov_wr[36]) {
+    // Twr = Tcw^-1 Trc^-1 (visfs_ba_unpack_pose); the state's update t += dt, R_cw <- Exp(dtheta) R_cw gives to first order
+    // dp = -R_cw^T dt + [p_wr]x R_cw^T dtheta, dphi = -R_cw^T dtheta
+    const Rt T = pose_to_Rt(tq);
+    double Twr[12];
+    visfs_ba_unpack_pose(tq, Trc, Twr);
+    const double Rt_[9] = { T.R.m00, T.R.m10, T.R.m20, T.R.m01, T.R.m11, T.R.m21, T.R.m02, T.R.m12, T.R.m22 };   // R_cw^T
+    const double p[3] = { Twr[3], Twr[7], Twr[11] };
+    const double P[9] = { 0.0, -p[2], p[1], p[2], 0.0, -p[0], -p[1], p[0], 0.0 };
+    double J[36] = { 0 };
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) {
+            J[6 * r + c] = -Rt_[3 * r + c];
+            J[6 * (r + 3) + c + 3] = -Rt_[3 * r + c];
+            double v = 0.0;
+            for (int e = 0; e < 3; ++e) v += P[3 * r + e] * Rt_[3 * e + c];
+            J[6 * r + c + 3] = v;
+        }
+    double JC[36];
+    for (int r = 0; r < 6; ++r)
+        for (int c = 0; c < 6; ++c) { double v = 0.0; for (int e = 0; e < 6; ++e) v += J[6 * r + e] * cov_tq[6 * e + c]; JC[6 * r + c] = v; }
+    for (int r = 0; r < 6; ++r)
+        for (int c = 0; c < 6; ++c) { double v = 0.0; for (int e = 0; e < 6; ++e) v += JC[6 * r + e] * J[6 * c + e]; cov_wr[6 * r + c] = v; }
+}
+
+int visfs_ba_hook_band_selinv(int32_t n, int32_t B, const double* S_band, double* Sigma_band) {
+    if (n < 1 || B < 0 || !S_band || !Sigma_band) return VISFS_BA_ERR_BAD_ARGUMENT;
+    const int W = B + 1;
+    const size_t nb_all = (size_t)n * W * 36;
+    std::vector<double> F(nb_all), N((size_t)36 * std::max(B, 1)), Ci(36);
+    for (size_t t = 0; t < nb_all; ++t) { const int I = (int)(t / (36 * (size_t)W)), d = (int)((t / 36) % W); F[t] = I - d >= 0 ? S_band[t] : 0.0; }
+    for (int k = 0; k < n; ++k) {                          // the steps of k_band_factor, every work item in order
+        const int nb = std::min(B, n - 1 - k);
+        if (!cov::factor_pivot(F.data(), W, k)) return VISFS_BA_ERR_SINGULAR;
+        cov::factor_rows(F.data(), W, k, nb, 0, 1);
+        cov::factor_update(F.data(), W, k, nb, 0, 1);
+    }
+    std::fill(Sigma_band, Sigma_band + nb_all, 0.0);
+    for (int k = n - 1; k >= 0; --k) {                     // the steps of k_band_selinv
+        const int nb = std::min(B, n - 1 - k);
+        cov::selinv_prep(F.data(), W, k, nb, N.data(), Ci.data(), 0, 1);
+        cov::selinv_off(Sigma_band, W, k, nb, N.data(), 0, 1);
+        cov::selinv_diag(Sigma_band, W, k, nb, N.data(), Ci.data(), 0, 1);
+    }
     return VISFS_BA_OK;
 }
 

@@ -58,6 +58,11 @@ void launch_small_optimize_batch(const DeviceGraph* gs, int B, int solver, int h
 void launch_gather_lm(const DeviceGraph* gs, int B, LmState* out, hipStream_t s);
 void launch_stage_arm(const DeviceGraph& g, double lambda, int mode, hipStream_t s);
 void launch_eval_mark(const DeviceGraph& g, hipStream_t s);           // stage hook: outlier pass on the committed estimate, ungated
+// marginal covariances (ba_cov.hip): banded factor of S to F ([Npf][band_B + 1][36], fail[0] = 1 on a bad pivot), the band of S^-1 to Sg,
+// the landmark marginals ([Nl][9]) from Sg, H_ll and the H_pl tiles of a `debug` linearisation
+void launch_band_factor(const DeviceGraph& g, double* F, int* fail, hipStream_t s);
+void launch_band_selinv(const DeviceGraph& g, const double* F, double* Sg, const int* fail, hipStream_t s);
+void launch_point_cov(const DeviceGraph& g, const double* Sg, double* out, const int* fail, hipStream_t s);
 // test hook: one phase of the LM state machine on the host, through the functions the kernels run, on scripted trial outcomes
 int ceres_script_host(int max_iter, double cost0, double x_norm0, double grad_max0, int n, const int32_t* ok, const double* mcc, const double* cand_cost,
                       const double* step_norm, const double* grad_max, const double* x_norm, LmState* st,

@@ -148,7 +148,12 @@ std::map<std::size_t, Eigen::Isometry3d> Optimizer::localOptimize(
     r.outlier_capacity = static_cast<int32_t>(refFeature.size() + 1);
     r.outlier_feature = outFeat.data(); r.outlier_pose = outPose.data();
 
+    lastPoseIds_.clear(); lastPointIds_.clear();
     lastStatus_ = visfs_ba_solve_window(handle_, &w, &r);
+    if (lastStatus_ == VISFS_BA_OK) {                          // what lastCovariance keys its blocks by
+        lastPoseIds_.assign(poseIds.begin(), poseIds.end());
+        lastPointIds_.assign(pointIds.begin(), pointIds.end());
+    }
 
     // ---- unpack: the reference appends outliers at :296 even when phase 2 aborts, and returns an empty map on failure
     for (int i = 0; i < r.n_outliers; ++i) _outliers.emplace_back(static_cast<std::size_t>(outFeat[i]), static_cast<std::size_t>(outPose[i]));
@@ -167,6 +172,27 @@ std::map<std::size_t, Eigen::Isometry3d> Optimizer::localOptimize(
             it->second = std::make_tuple(Eigen::Vector3d(pointXyz[3 * n], pointXyz[3 * n + 1], pointXyz[3 * n + 2]), std::get<1>(it->second));
     }
     return optimizedPoses;
+}
+
+bool Optimizer::lastCovariance(std::map<std::size_t, std::array<double, 36>>& poseCov,
+                               std::map<std::size_t, std::array<double, 9>>* pointCov) const {
+    poseCov.clear();
+    if (pointCov) pointCov->clear();
+    if (!handle_ || lastPoseIds_.empty()) return false;
+    std::vector<double> pc(36 * lastPoseIds_.size()), qc(pointCov ? 9 * (lastPointIds_.size() + 1) : 0);
+    if (visfs_ba_window_covariance(handle_, pc.data(), pointCov ? qc.data() : nullptr) != VISFS_BA_OK) return false;
+    for (std::size_t i = 0; i < lastPoseIds_.size(); ++i) {
+        std::array<double, 36> a;
+        std::memcpy(a.data(), &pc[36 * i], sizeof(a));
+        poseCov.emplace(lastPoseIds_[i], a);
+    }
+    if (pointCov)
+        for (std::size_t l = 0; l < lastPointIds_.size(); ++l) {
+            std::array<double, 9> a;
+            std::memcpy(a.data(), &qc[9 * l], sizeof(a));
+            pointCov->emplace(lastPointIds_[l], a);
+        }
+    return true;
 }
 
 }  // namespace Optimizer

@@ -8,6 +8,7 @@
 #ifndef VISFS_AMD_OPTIMIZER_H
 #define VISFS_AMD_OPTIMIZER_H
 
+#include <array>
 #include <cstddef>
 #include <map>
 #include <string>
@@ -63,12 +64,23 @@ public:
     int lastStatus() const { return lastStatus_; }
     const char* lastError() const;
 
+    // Marginal covariances of the last successful localOptimize (visfs_ba_window_covariance): the inverse Gauss-Newton Hessian of the
+    // active edges at the optimised estimate, the fixed pose as the gauge (definition: include/visfs_ba.h).  poseCov: per signature id,
+    // the 6x6 row-major covariance of (dp, dphi) of Twr — world-frame translation, rotation about the world axes (nav_msgs' convention);
+    // the root pose is all zeros, a pose without an active edge all NaN.  pointCov (optional): per feature id of _points3D, the 3x3
+    // row-major covariance of the world position; fixed points zeros, points without an active edge and points that never became a
+    // vertex NaN.  Returns false (maps cleared) when unavailable: no successful localOptimize since construction (passthrough and
+    // failures included), no fixed pose in the window, a window beyond the banded solver, Optimizer/Framework=1; lastError() says why.
+    bool lastCovariance(std::map<std::size_t, std::array<double, 36>>& poseCov,
+                        std::map<std::size_t, std::array<double, 9>>* pointCov = nullptr) const;
+
 private:
     int framework_, solver_, trustRegion_, iterations_;
     double pixelVariance_, odometryCovariance_, laserCovariance_, robustKernelDelta_;
     int device_;
     visfs_ba_handle* handle_;
     int lastStatus_;
+    std::vector<std::size_t> lastPoseIds_, lastPointIds_;   // ids of the last successful localOptimize, window order (lastCovariance)
     std::string createError_;      // why visfs_ba_create failed (visfs_ba_create_error), kept for lastError()
 };
 
