@@ -26,6 +26,7 @@
 #include "../../include/visfs_ba.h"
 #include "ba_cov.hpp"
 #include "ba_kernels.hpp"
+#include "ba_submap.hpp"
 #include "worker_pool.hpp"
 
 using namespace visfs_ba;
@@ -137,6 +138,7 @@ struct Workspace {
     // host mirrors for fetch / unpack
     std::vector<int32_t> free_pose, blk_i, blk_j, odo_i, odo_j, pose_free;
     PackedWindow pk;                               // window layer: what the graph build leaves on the host (persistent buffers)
+    const float* d_grid_src = nullptr;             // visfs_submaps_solve_window: the laser grid's costs already in device memory (copied device to device)
     std::vector<SummaryPart> sum_part;             // per-thread accumulators of summarize_graph (persistent buffers)
     std::vector<int32_t> sum_run;
     int64_t n_pairs = 0;
@@ -428,6 +430,7 @@ struct UploadOpts {
     WorkerPool* pool = nullptr;
     double baseline = 0.0;     // raw references (cap.raw_refs): the stereo baseline the device forms the disparity with
     int summary_slots = 0;     // > 0: the graph build has already fed w.sum_part[0 .. summary_slots) (no second pass over the observations)
+    const float* d_grid = nullptr;   // the laser grid's costs in device memory: copied device to device, gr->grid->correspondence_cost not read
 };
 
 int ws_upload(visfs_ba_handle* h, Workspace& w, const visfs_ba_graph* gr, const UploadOpts& opt = UploadOpts()) {
@@ -494,7 +497,7 @@ int ws_upload(visfs_ba_handle* h, Workspace& w, const visfs_ba_graph* gr, const 
     }
     if (Nz) {
         std::memcpy(const_cast<double*>(hg.laser_xyz), gr->laser_xyz, (size_t)Nz * 24);
-        std::memcpy(const_cast<float*>(hg.grid.cost), gr->grid->correspondence_cost, grid_cells * 4);
+        if (!opt.d_grid) std::memcpy(const_cast<float*>(hg.grid.cost), gr->grid->correspondence_cost, grid_cells * 4);
     }
     // buildIndexMapping: free poses in index (= id) order
     std::vector<int32_t> pose_free(Np), free_pose;
@@ -502,7 +505,12 @@ int ws_upload(visfs_ba_handle* h, Workspace& w, const visfs_ba_graph* gr, const 
     const int Npf = (int)free_pose.size();
     std::memcpy(const_cast<int32_t*>(hg.pose_free), pose_free.data(), (size_t)Np * 4);
     if (Npf) std::memcpy(const_cast<int32_t*>(hg.free_pose), free_pose.data(), (size_t)Npf * 4);
-    HIP_TRY(h, hipMemcpyAsync(w.d_prim, w.h_prim, pbytes, hipMemcpyHostToDevice, w.stream));
+    if (Nz && opt.d_grid) {
+        // the grid is the last array of the section: everything before it from the staging arena, the grid from device memory
+        const size_t at = (size_t)(reinterpret_cast<const char*>(hg.grid.cost) - w.h_prim);
+        HIP_TRY(h, hipMemcpyAsync(w.d_prim, w.h_prim, at, hipMemcpyHostToDevice, w.stream));
+        HIP_TRY(h, hipMemcpyAsync(w.d_prim + at, opt.d_grid, grid_cells * 4, hipMemcpyDeviceToDevice, w.stream));
+    } else HIP_TRY(h, hipMemcpyAsync(w.d_prim, w.h_prim, pbytes, hipMemcpyHostToDevice, w.stream));
     lap("primary");
 
     // ---- what the host needs of the O(N_obs) part: observations per free pose, co-observation pairs per block
@@ -1713,6 +1721,7 @@ int prepare_window(visfs_ba_handle* h, Workspace& w, const visfs_ba_window* win,
         const visfs_ba_grid& G = *win->grid;
         opt.cap.Nz = win->n_laser_points;
         if (G.num_x_cells > 0 && G.num_y_cells > 0 && (int64_t)G.num_x_cells * G.num_y_cells <= (int64_t)1 << 28) opt.cap.grid_cells = (size_t)G.num_x_cells * G.num_y_cells;
+        opt.d_grid = w.d_grid_src;
     }
     rc = ensure_prim(h, w, prim_bytes(opt.cap));
     if (rc != VISFS_BA_OK) { r->status = rc; return 0; }
@@ -2767,3 +2776,14 @@ int visfs_ba_stage_fetch(visfs_ba_handle* h, int32_t which, double* dst, size_t 
 }
 
 }  // extern "C"
+
+// ---- internal entry points of the laser sub-maps (ba_submap.hip)
+hipStream_t visfs_internal_stream(visfs_ba_handle* h) { return h->ws.stream; }
+int visfs_internal_device(visfs_ba_handle* h) { return h->device; }
+void visfs_internal_set_error(visfs_ba_handle* h, const char* msg) { try { h->err = msg; } catch (...) {} }
+int visfs_internal_solve_window(visfs_ba_handle* h, const visfs_ba_window* w, visfs_ba_result* r, const float* d_cost) {
+    h->ws.d_grid_src = d_cost;
+    const int rc = visfs_ba_solve_window(h, w, r);
+    h->ws.d_grid_src = nullptr;
+    return rc;
+}

@@ -1,0 +1,92 @@
+// ActiveSubmaps2D.h — drop-in for the sub-map side of VISFS::Map::ActiveSubmaps2D (corelib/include/Map/2d/Submap2D.h) backed by
+// the GPU-resident sub-maps of include/visfs_submap.h.  Header only, over the C ABI.
+//
+// It keeps what LocalMap uses of the reference class: the constructor taking the LocalMap/* keys, insertion of a frame's range data
+// at its pose (LocalMap::insertMatchingSubMap2d, LocalMap.cpp:355-360), whether a matching sub-map exists (hasMatchingSubmap2D) and
+// the BA against it (Estimator.cpp:247-250 + Optimizer::localOptimize).  The grids stay on the device: there is no Submap2D object to
+// hand out; download() copies one to the host for those who want grid2Image.
+#ifndef VISFS_AMD_ACTIVE_SUBMAPS_2D_H
+#define VISFS_AMD_ACTIVE_SUBMAPS_2D_H
+
+#include <cstdint>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "visfs_submap.h"
+
+namespace VISFS {
+namespace Map {
+
+class ActiveSubmaps2D {
+public:
+    // One Sensor::RangeData in the robot frame: origin, returns and misses as xyz triples.
+    struct RangeData {
+        double origin[3] = { 0.0, 0.0, 0.0 };
+        std::vector<double> returns;   // [k][3]
+        std::vector<double> misses;    // [m][3]
+    };
+
+    ActiveSubmaps2D(const ActiveSubmaps2D&) = delete;
+    ActiveSubmaps2D& operator=(const ActiveSubmaps2D&) = delete;
+
+    // ba: the handle whose device and stream the grids live on.  Throws std::runtime_error when creation fails (GridMapType 1 = TSDF
+    // included, where the reference stops with LOG_FATAL).
+    ActiveSubmaps2D(visfs_ba_handle* ba, int numRangeDataLimit = 50, int gridType = 0, double gridResolution = 0.05,
+                    bool insertFreeSpace = true, double hitProbability = 0.55, double missProbability = 0.49) : ba_(ba) {
+        visfs_submap_params p;
+        visfs_submap_default_params(&p);
+        p.num_range_data_limit = numRangeDataLimit; p.grid_map_type = gridType; p.map_resolution = gridResolution;
+        p.insert_free_space = insertFreeSpace ? 1 : 0; p.hit_probability = hitProbability; p.miss_probability = missProbability;
+        const int rc = visfs_submaps_create(ba, &p, &s_);
+        if (rc != VISFS_BA_OK) throw std::runtime_error("visfs_submaps_create failed with status " + std::to_string(rc));
+    }
+    ~ActiveSubmaps2D() { visfs_submaps_destroy(s_); }
+
+    // LocalMap::insertMatchingSubMap2d: each range data its own insertion, in order, at pose Twr (3x4 row-major).
+    int insertRangeData(const std::vector<RangeData>& rangeDatas, const double Twr[12]) {
+        std::vector<visfs_range_data> rd(rangeDatas.size());
+        for (size_t i = 0; i < rangeDatas.size(); ++i) {
+            const RangeData& r = rangeDatas[i];
+            for (int k = 0; k < 3; ++k) rd[i].origin[k] = r.origin[k];
+            rd[i].n_returns = (int32_t)(r.returns.size() / 3); rd[i].returns = r.returns.data();
+            rd[i].n_misses = (int32_t)(r.misses.size() / 3); rd[i].misses = r.misses.data();
+        }
+        return visfs_submaps_insert(s_, Twr, (int32_t)rd.size(), rd.data());
+    }
+
+    // LocalMap::hasMatchingSubmap2D
+    bool hasMatchingSubmap2D() const { int32_t n = 0; visfs_submaps_describe(s_, &n, nullptr); return n > 0; }
+
+    // the sub-maps, front (matching) first
+    std::vector<visfs_submap_info> submaps() const {
+        int32_t n = 0;
+        visfs_submap_info info[2];
+        visfs_submaps_describe(s_, &n, info);
+        return std::vector<visfs_submap_info>(info, info + n);
+    }
+
+    // Estimator.cpp:247-250 + localOptimize: the window's laser factor reads getMatchingSubmap2D() in device memory
+    int solveWindow(const visfs_ba_window* w, visfs_ba_result* r) const { return visfs_submaps_solve_window(ba_, s_, w, r); }
+
+    // one sub-map's cells and float costs on the host ([num_y_cells][num_x_cells])
+    int download(int index, std::vector<uint16_t>* cells, std::vector<float>* cost) const {
+        const std::vector<visfs_submap_info> v = submaps();
+        if (index < 0 || index >= (int)v.size()) return VISFS_BA_ERR_BAD_ARGUMENT;
+        const size_t n = (size_t)v[index].num_x_cells * v[index].num_y_cells;
+        if (cells) cells->resize(n);
+        if (cost) cost->resize(n);
+        return visfs_submaps_download(s_, index, cells ? cells->data() : nullptr, cost ? cost->data() : nullptr);
+    }
+
+    const char* lastError() const { return visfs_submaps_last_error(s_); }
+
+private:
+    visfs_ba_handle* ba_ = nullptr;
+    visfs_submaps* s_ = nullptr;
+};
+
+}  // namespace Map
+}  // namespace VISFS
+
+#endif
