@@ -1157,7 +1157,7 @@ void fill_stats(const LmState& st, visfs_ba_stats* out) {
 // carries a persistent PCG holds this per-device lock from its first launch to its last state read.  Other PROCESSES sharing the
 // GPU are not covered: the library assumes exclusive use of the device for Optimizer/Solver=2 (include/visfs_ba.h).
 //
-// Round 2: a budget instead of a mutex.  Grids of the ONE-WAVE kernel (k_pcg1: 64-thread workgroups, no LDS, 248 VGPRs) are
+// Round 2: a budget instead of a mutex.  Grids of the ONE-WAVE kernel (k_pcg1: 64-thread workgroups, no LDS, 242-256 VGPRs) are
 // homogeneous: every SIMD of the device holds two such waves, so 1024 of them (counted conservatively: one per SIMD) are resident
 // together wherever the dispatcher puts them — several handles / host threads may run such solves side by side as long as their
 // block rows sum to <= 1024 (two 4-window batches of C2 size overlap: the hand-off waits of one hide behind the gathers of the

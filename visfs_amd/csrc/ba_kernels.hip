@@ -184,13 +184,14 @@ __device__ __forceinline__ double block_max_256(double v, double* red) {
 }
 
 // Stage every pose of the window as R|t (12 doubles) in LDS: the observation tiles gather from here.
-__device__ __forceinline__ void stage_poses(const double* __restrict__ pose, int Np, double* sRt) {
-    for (int i = threadIdx.x; i < Np; i += blockDim.x) {
-        const Rt T = pose_to_Rt(pose + POSE_STRIDE * i);
-        double* o = sRt + 12 * i;
-        o[0] = T.R.m00; o[1] = T.R.m01; o[2] = T.R.m02; o[3] = T.R.m10; o[4] = T.R.m11; o[5] = T.R.m12;
-        o[6] = T.R.m20; o[7] = T.R.m21; o[8] = T.R.m22; o[9] = T.t.x; o[10] = T.t.y; o[11] = T.t.z;
-    }
+__device__ __forceinline__ void stage_pose(const double* tq, double* o) {
+    const Rt T = pose_to_Rt(tq);
+    o[0] = T.R.m00; o[1] = T.R.m01; o[2] = T.R.m02; o[3] = T.R.m10; o[4] = T.R.m11; o[5] = T.R.m12;
+    o[6] = T.R.m20; o[7] = T.R.m21; o[8] = T.R.m22; o[9] = T.t.x; o[10] = T.t.y; o[11] = T.t.z;
+}
+// (first: poses below `first` were staged by the caller from registers — k_backsub<LINA>)
+__device__ __forceinline__ void stage_poses(const double* __restrict__ pose, int Np, double* sRt, const int first = 0) {
+    for (int i = first + threadIdx.x; i < Np; i += blockDim.x) stage_pose(pose + POSE_STRIDE * i, sRt + 12 * i);
 }
 __device__ __forceinline__ Rt load_Rt(const double* sRt, int i) {
     const double* o = sRt + 12 * i;
@@ -353,14 +354,24 @@ __device__ __forceinline__ void pose_obs_terms_rec(const DeviceGraph& g, const D
 
 // Role A for one landmark handled by G lanes (sub = lane within the group): weights, chi2, tile seeds, Hll, b_l.
 // Shared by k_linearize<G> and the fused small-window kernel (G = 1: one thread per landmark).
-template <int G, bool STG = true>
+// What the fused tail of a lone window (k_backsub<LINA>) holds in registers when it reaches the per-landmark device functions (PRE):
+// the landmark's static index data and the static data of the lane's FIRST observation kf (-1: it has none), loaded in front of the
+// kernel's gate, and what the current linearisation set holds for them, loaded right behind it, in front of the staging barrier —
+// instead of a chain of dependent cold loads behind that barrier.  Same addresses, same values: nothing writes them inside a unit.
+struct LmPre {
+    int k0, k1; bool fixed; Vec3 pw;                 // lm_ptr[l], lm_ptr[l + 1], pt_fixed[l], pt[sel] of l
+    int kf, ipf, af; double u, v, ur; bool act;      // obs_pose[kf], pose_free of it, obs_uvr[kf], obs_level[kf] == 0 && obs_ok[kf]
+    double H[6], B[3], wf, sd[4];                    // current set: Hll, b_l of l; obs_w and the tile seed of kf
+};
+template <int G, bool STG = true, bool PRE = false>
 __device__ __forceinline__ void lin_landmark(const DeviceGraph& g, const LinBuf& L, const int l, const bool lvalid, const int sub, const PoseSrc<STG> P,
                                              const double* __restrict__ pt, const Intrinsics& K, const double iv, const double delta,
-                                             double& chi_acc, double& md, double* xn_acc = nullptr, const Vec3* pw_reg = nullptr) {
+                                             double& chi_acc, double& md, double* xn_acc = nullptr, const Vec3* pw_reg = nullptr, const LmPre* pre = nullptr) {
     int k0 = 0, k1 = 0;
     Vec3 pw{ 0, 0, 0 };
     bool lfree = false;
-    if (lvalid) {
+    if (PRE && lvalid) { k0 = pre->k0; k1 = pre->k1; pw = *pw_reg; lfree = !pre->fixed; }
+    if (!PRE && lvalid) {
         k0 = g.lm_ptr[l]; k1 = g.lm_ptr[l + 1];
         // (pw_reg: the caller has the landmark in registers — k_backsub<LINA> linearises the trial landmark its own lanes have just formed;
         // reading it back from pt would race with the one lane of the group that stores it)
@@ -377,18 +388,19 @@ __device__ __forceinline__ void lin_landmark(const DeviceGraph& g, const LinBuf&
 #pragma unroll
     for (int q = 0; q < 9; ++q) hb[q] = 0.0;
     for (int k = k0 + sub; k < k1; k += G) {
-        const int ip = g.obs_pose[k];
+        const bool first = PRE && k == pre->kf;          // (the lane's first observation: its static data is in registers)
+        const int ip = first ? pre->ipf : g.obs_pose[k];
         const Rt T = P.get(ip);
-        const double u = g.obs_uvr[3 * k], v = g.obs_uvr[3 * k + 1], ur = g.obs_uvr[3 * k + 2];
+        const double u = first ? pre->u : g.obs_uvr[3 * k], v = first ? pre->v : g.obs_uvr[3 * k + 1], ur = first ? pre->ur : g.obs_uvr[3 * k + 2];
         Vec3 pc;
         const Vec3 e = stereo_error(T, pw, u, v, ur, K, pc);
         const double c2 = chi2_of(e, iv);
-        const bool active = (g.obs_level[k] == 0) && g.obs_ok[k];
+        const bool active = first ? pre->act : ((g.obs_level[k] == 0) && g.obs_ok[k]);
         double rho0 = c2, rho1 = 1.0;
         robustify(g, c2, delta, rho0, rho1);
         L.obs_w[k] = active ? rho1 : 0.0;
         if (g.debug) { g.obs_chi2[k] = active ? c2 : 0.0; g.obs_err[3 * k] = active ? e.x : 0.0; g.obs_err[3 * k + 1] = active ? e.y : 0.0; g.obs_err[3 * k + 2] = active ? e.z : 0.0; }
-        const bool pfree = g.pose_free[ip] >= 0;
+        const bool pfree = (first ? pre->af : g.pose_free[ip]) >= 0;
         double wo_tile = 0.0;
         if (active) {
             chi_acc += rho0;
@@ -646,11 +658,20 @@ __device__ __forceinline__ void publish_trial(const DeviceGraph& g, const int w,
 // thread, fetched again after a pause while a tag is missing — add them in decide_role's order and step the LM state
 // machine.  LmState is written only here, after every workgroup has published, i.e. after every workgroup has read its gate and
 // its lambda / sel.  A wait that never ends (never expected) surfaces like a PCG hand-off time-out: VISFS_BA_ERR_DEVICE.
+// PREX (the fused tail of a lone window): the VALUES of the thread's first two terms of the pose part of computeScale (x and b_p are
+// final since the solver launch) are in registers before the poll loop, so no cold round trip stands between the arrival of the last
+// partial and lm_decide; the sum itself — term by term into sc, behind the gathered partials — is the same chain of operations.
+template <bool PREX = false>
 __device__ __forceinline__ void decide_gather_role(const DeviceGraph& g, LmState* st, const unsigned ep, const bool ok, double* red, const int spec = 0) {
     typedef unsigned v4u_t __attribute__((ext_vector_type(4)));
     const int tid = threadIdx.x;
     const double lambda = st->lambda;
     const int n = g.n_lin_a + 1;
+    double xa = 0.0, ba = 0.0, xb = 0.0, bb = 0.0;
+    if (PREX && ok) {
+        if (tid < 6 * g.Npf) { xa = g.x[tid]; ba = g.bp[tid]; }
+        if (tid + 256 < 6 * g.Npf) { xb = g.x[tid + 256]; bb = g.bp[tid + 256]; }
+    }
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)g.trial_gran, 0, (int)(n * 32), 0x00020000);
     double chi = 0.0, sc = 0.0;
     int bad = 0;
@@ -679,7 +700,11 @@ __device__ __forceinline__ void decide_gather_role(const DeviceGraph& g, LmState
             }
         }
     }
-    if (ok) for (int t = tid; t < 6 * g.Npf; t += 256) { const double x = g.x[t]; sc += x * (lambda * x + g.bp[t]); }
+    if (PREX && ok) {
+        if (tid < 6 * g.Npf) sc += xa * (lambda * xa + ba);
+        if (tid + 256 < 6 * g.Npf) sc += xb * (lambda * xb + bb);
+    }
+    if (ok) for (int t = tid + (PREX ? 512 : 0); t < 6 * g.Npf; t += 256) { const double x = g.x[t]; sc += x * (lambda * x + g.bp[t]); }
     chi = block_sum_256(chi, red);
     sc = block_sum_256(sc, red);
     bad = __syncthreads_or(bad);
@@ -696,14 +721,17 @@ __device__ __forceinline__ int decider_window() {
     return (blockIdx.y == gridDim.y - 1) ? (int)blockIdx.x - working : -2;          // -2: an idle filler of the rectangular grid
 }
 // The decider of window j.
+template <bool PREX = false>
 __device__ __forceinline__ void decider_run(const DeviceGraph& gd, double* red, const int spec = 0) {
     LmState* sd = gd.st;
-    if (sd->mode & MODE_TRIAL) decide_gather_role(gd, sd, sd->decide_epoch + 1u, !sd->solver_failed && !sd->pcg_timeout, red, spec);
+    if (sd->mode & MODE_TRIAL) decide_gather_role<PREX>(gd, sd, sd->decide_epoch + 1u, !sd->solver_failed && !sd->pcg_timeout, red, spec);
 }
-__device__ __forceinline__ void decider_of(const One& s, int, double* red, const int spec = 0) { decider_run(s.g, red, spec); }
+template <bool PREX = false>
+__device__ __forceinline__ void decider_of(const One& s, int, double* red, const int spec = 0) { decider_run<PREX>(s.g, red, spec); }
+template <bool PREX = false>
 __device__ __forceinline__ void decider_of(const Many& s, const int j, double* red, const int spec = 0) {
     typedef const __attribute__((address_space(4))) DeviceGraph* ConstGraphPtr;
-    decider_run(*(const DeviceGraph*)(ConstGraphPtr)(s.gs + j), red, spec);
+    decider_run<PREX>(*(const DeviceGraph*)(ConstGraphPtr)(s.gs + j), red, spec);
 }
 
 // ================================================================= K1/K2/K4: linearise the stereo edges
@@ -2237,19 +2265,52 @@ __global__ __launch_bounds__(64) void k_pcg1(const Src src) {
         const LinSel<Src> lsel(g, st->lin_sel);
         schur_block<true>(g, lsel.get(), st, b, lane, bd, be, 0.0, unit_tag);
     }
-    if (!(st->mode & MODE_TRIAL)) return;
     const int i0 = GV == 3 ? (int)(blockIdx.x >> 3) : (int)blockIdx.x;
-    if (i0 >= g.Npf) return;                          // a batched launch is sized for the largest window
+#ifdef VISFS_BA_STAMPS
+    const unsigned long long t_head = wall_clock64();
+#endif
+    // ---- set-up, the part in front of the gate (EARLY: the default gather variant of a lone window without the finalisation on
+    // board; the other variants and the batched form, which has no register to spare — 242 VGPRs + 32 AGPRs, and the pre-loaded
+    // form cost its iteration loop five instructions — keep their order): the addresses of code(i0, lane), Minv_lane, b_s lane and free_pose[i0] depend
+    // on blockIdx and the lane only, and their contents are final since k_schur_finalize / the upload — they are in flight together
+    // with the gate's own read (one cold round trip instead of two at the head of the kernel; a gated-off launch reads a few words
+    // for nothing and writes nothing).  Lanes without a pose read lane 0's addresses, as the set-up always did.
+    constexpr bool EARLY = !FIN && GV == 1 && !Src::batched;
+    int code_pre = -1, ip0 = 0, sel0 = 0;
+    double res_in0 = 0.0;
+    double2 m_pre[18];
+    double b_pre[6];
+    if (!EARLY) {
+        if (!(st->mode & MODE_TRIAL)) return;
+        if (i0 >= g.Npf) return;                      // a batched launch is sized for the largest window
+    } else {
+        if (i0 >= g.Npf) return;                      // a batched launch is sized for the largest window
+        const int lc = lane < g.Npf ? lane : 0;
+        code_pre = g.pcg1_code[i0 * g.Npf + lc];
+        const double2* Mb = reinterpret_cast<const double2*>(g.Minv + 36 * (size_t)lc);
+#pragma unroll
+        for (int q = 0; q < 18; ++q) m_pre[q] = Mb[q];
+#pragma unroll
+        for (int c = 0; c < 6; ++c) b_pre[c] = g.bs[6 * lc + c];
+        ip0 = g.free_pose[i0];
+        const int mode = st->mode;
+        sel0 = st->sel; res_in0 = st->pcg_res_in;
+        // (the loads above are issued before the gate is waited for, and the gate's wait covers the other state words and
+        // free_pose[i0]: the empty statement keeps the compiler from sinking those loads behind the branch)
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("" :: "s"(mode), "s"(sel0), "s"(res_in0), "s"(ip0));
+        if (!(mode & MODE_TRIAL)) return;
+    }
     const int Npf = g.Npf, n6 = 6 * Npf;
     const bool own = lane < Npf;
 #ifdef VISFS_BA_STAMPS
-#define PCG1_STAMP(slot) do { if (lane == 0 && i0 == g.stamp_wg && (slot) < 100) g.stamps[(slot)] = wall_clock64(); } while (0)
-    if (lane == 0 && i0 == g.stamp_wg) g.stamps[127] = wall_clock64();
+#define PCG1_STAMP(slot) do { if (lane == 0 && i0 == g.stamp_wg && (slot) < 97) g.stamps[(slot)] = wall_clock64(); } while (0)
+    if (lane == 0 && i0 == g.stamp_wg) { g.stamps[126] = t_head; g.stamps[127] = wall_clock64(); }      // head of the kernel, behind the gate
 #else
 #define PCG1_STAMP(slot) do { } while (0)
 #endif
     // ---- set-up: S(i0, lane), Minv_lane, r = b_s; every load below is independent of the others
-    const int code = own ? g.pcg1_code[i0 * Npf + lane] : -1;
+    const int code = EARLY ? (own ? code_pre : -1) : (own ? g.pcg1_code[i0 * Npf + lane] : -1);
     const unsigned spin_limit = g.fault_pcg ? (1u << 10) : (1u << 22);
     bool timeout = false;
     double Sr[36], mm[36], rr[6], dd[6], xx[6];
@@ -2293,6 +2354,7 @@ __global__ __launch_bounds__(64) void k_pcg1(const Src src) {
 #pragma unroll
         for (int c = 0; c < 6; ++c) xx[c] = 0.0;
     } else {
+        // (EARLY: only S still waits for `code`; Minv and b_s arrived with the gate)
         const double2* Sb = reinterpret_cast<const double2*>(g.S + 36 * (size_t)(code >= 0 ? (code >> 1) : 0));
         const double2* Mb = reinterpret_cast<const double2*>(g.Minv + 36 * (size_t)(own ? lane : 0));
         double sv[36];
@@ -2300,8 +2362,11 @@ __global__ __launch_bounds__(64) void k_pcg1(const Src src) {
         for (int q = 0; q < 18; ++q) {
             const double2 v = (code >= 0) ? Sb[q] : make_double2(0.0, 0.0);
             sv[2 * q] = v.x; sv[2 * q + 1] = v.y;
-            const double2 m = own ? Mb[q] : make_double2(0.0, 0.0);
-            mm[2 * q] = m.x; mm[2 * q + 1] = m.y;
+            if constexpr (EARLY) { mm[2 * q] = own ? m_pre[q].x : 0.0; mm[2 * q + 1] = own ? m_pre[q].y : 0.0; }
+            else {
+                const double2 m = own ? Mb[q] : make_double2(0.0, 0.0);
+                mm[2 * q] = m.x; mm[2 * q + 1] = m.y;
+            }
         }
         const bool tr = (code & 1) != 0;              // the stored block is (lane, i0): use its transpose
 #pragma unroll
@@ -2309,7 +2374,15 @@ __global__ __launch_bounds__(64) void k_pcg1(const Src src) {
 #pragma unroll
             for (int c = 0; c < 6; ++c) Sr[6 * r + c] = tr ? sv[6 * c + r] : sv[6 * r + c];
 #pragma unroll
-        for (int c = 0; c < 6; ++c) { rr[c] = own ? g.bs[6 * (own ? lane : 0) + c] : 0.0; xx[c] = 0.0; }
+        for (int c = 0; c < 6; ++c) { rr[c] = own ? (EARLY ? b_pre[c] : g.bs[6 * (own ? lane : 0) + c]) : 0.0; xx[c] = 0.0; }
+    }
+    // the epilogue's operand: pose free_pose[i0] of the current estimate (nobody writes pose[sel] during a unit) is fetched behind S,
+    // under the set-up, so that the launch ends with arithmetic on registers and stores instead of two more cold round trips
+    double tq0[7];
+    if (EARLY) {
+        const double* pp = g.pose[sel0] + POSE_STRIDE * ip0;
+#pragma unroll
+        for (int c = 0; c < 7; ++c) tq0[c] = pp[c];
     }
     double part = 0.0;
 #pragma unroll
@@ -2325,7 +2398,7 @@ __global__ __launch_bounds__(64) void k_pcg1(const Src src) {
     {
         // (FIN: block 0's wave copies pcg_residual to pcg_res_in in this very launch — read the source, which nobody writes before every
         // row has left its loop)
-        const double res_in = FIN ? st->pcg_residual : st->pcg_res_in;
+        const double res_in = FIN ? st->pcg_residual : EARLY ? res_in0 : st->pcg_res_in;
         if (res_in > 0.0 && res_in > d0) d0 = res_in;
     }
     int iter = 0;
@@ -2469,14 +2542,21 @@ __global__ __launch_bounds__(64) void k_pcg1(const Src src) {
         PCG1_STAMP(4 + 4 * iter);
         iter += 1;
     }
+#ifdef VISFS_BA_STAMPS
+    const unsigned long long t_exit = wall_clock64();
+#endif
     if (timeout) { if (lane == 0) st->pcg_timeout = 1; return; }
     // x is final: the lane owning this wave's block row stores it and does K8 (oplus); row 0 publishes the statistics
     if (lane == i0) {
 #pragma unroll
         for (int c = 0; c < 6; ++c) g.x[6 * i0 + c] = xx[c];
-        const int ip = g.free_pose[i0];
-        const int sel = st->sel;
-        pose_oplus(g.pose[sel] + POSE_STRIDE * ip, xx, g.pose[sel ^ 1] + POSE_STRIDE * ip);
+        if (!EARLY) {
+            const int ip = g.free_pose[i0];
+            const int sel = st->sel;
+            pose_oplus(g.pose[sel] + POSE_STRIDE * ip, xx, g.pose[sel ^ 1] + POSE_STRIDE * ip);
+        } else {
+            pose_oplus(tq0, xx, g.pose[sel0 ^ 1] + POSE_STRIDE * ip0);
+        }
     }
     if (lane == 0 && i0 == 0) {
         st->pcg_residual = 0.5 * dn;
@@ -2484,6 +2564,10 @@ __global__ __launch_bounds__(64) void k_pcg1(const Src src) {
         st->pcg_total += iter;
         if (iter > st->pcg_max) st->pcg_max = iter;
     }
+#ifdef VISFS_BA_STAMPS
+    // tail: iterations run, the loop's exit, behind the last store (slots of their own: the ones from 32 on are also k_backsub's)
+    if (lane == 0 && i0 == g.stamp_wg) { g.stamps[97] = (unsigned long long)iter; g.stamps[99] = t_exit; __builtin_amdgcn_s_waitcnt(0); g.stamps[98] = wall_clock64(); }
+#endif
 }
 
 // ---- K6, reduced systems that fit ONE compute unit: no cross-workgroup hand-off at all
@@ -3612,15 +3696,18 @@ __global__ __launch_bounds__(BAND_T) void k_band_chol(const Src src) {
 // (dxl), and instead of the trial evaluation the lane accumulates the inner products of the dogleg construction: chi_acc <- ||J v||^2
 // (v = g / m, the direction of the Cauchy point; per robustified residual block), scale_acc <- ||g_s||^2, *step_acc <- ||gn_s||^2,
 // *dot_acc <- g_s . gn_s (landmark shares);  2 = pass B — the landmark step is dl_A v + dl_B dn, then the usual trial evaluation.
-template <int G, bool STG = true, int DL = 0>
+template <int G, bool STG = true, int DL = 0, bool PRE = false>
 __device__ __forceinline__ void backsub_landmark(const DeviceGraph& g, const LinBuf& L, const int l, const bool lvalid, const int sub, const PoseSrc<STG> Pt, const PoseSrc<STG> P0,
                                                  const double* __restrict__ pt, double* __restrict__ pt_t, const double lambda, const Intrinsics& K,
                                                  const double iv, const double delta, double& chi_acc, double& scale_acc, double* step_acc = nullptr,
-                                                 double* dot_acc = nullptr, const double dlA = 0.0, const double dlB = 1.0, Vec3* pn_out = nullptr) {
+                                                 double* dot_acc = nullptr, const double dlA = 0.0, const double dlB = 1.0, Vec3* pn_out = nullptr,
+                                                 const LmPre* pre = nullptr) {
+    static_assert(!PRE || DL == 0, "the pre-loaded form serves the fused tail only");
     int k0 = 0, k1 = 0;
     Vec3 pw{ 0, 0, 0 };
     bool lfree = false;
-    if (lvalid) {
+    if (PRE && lvalid) { k0 = pre->k0; k1 = pre->k1; pw = pre->pw; lfree = !pre->fixed; }
+    if (!PRE && lvalid) {
         k0 = g.lm_ptr[l]; k1 = g.lm_ptr[l + 1];
         pw = Vec3{ pt[3 * l], pt[3 * l + 1], pt[3 * l + 2] };
         lfree = !g.pt_fixed[l];
@@ -3629,14 +3716,17 @@ __device__ __forceinline__ void backsub_landmark(const DeviceGraph& g, const Lin
     double t0 = 0, t1 = 0, t2 = 0, any = 0.0;
     if (DL != 2)
     for (int k = k0 + sub; k < k1; k += G) {
-        const double w = L.obs_w[k];
+        const bool first = PRE && k == pre->kf;          // (the lane's first observation: its data is in registers)
+        const double w = first ? pre->wf : L.obs_w[k];
         if (w == 0.0) continue;
         any = 1.0;
-        const int ipk = g.obs_pose[k];
-        const int a = g.pose_free[ipk];
+        const int ipk = first ? pre->ipf : g.obs_pose[k];
+        const int a = first ? pre->af : g.pose_free[ipk];
         if (a < 0 || !lfree) continue;
         const double2* seed = reinterpret_cast<const double2*>(L.obs_pcw + 4 * (size_t)k);
-        const double2 s0 = seed[0], s1 = seed[1];
+        double2 s0, s1;
+        if (first) { s0 = make_double2(pre->sd[0], pre->sd[1]); s1 = make_double2(pre->sd[2], pre->sd[3]); }
+        else { s0 = seed[0]; s1 = seed[1]; }
         // Hpl^T x through the tile structure W = [N ; [Pc]x N]:  W^T x = N^T (x_t - Pc x x_r)
         const Vec3 pcs{ s0.x, s0.y, s1.x };
         double N[9];
@@ -3665,8 +3755,8 @@ __device__ __forceinline__ void backsub_landmark(const DeviceGraph& g, const Lin
         }
     }
     if (DL != 2 && lvalid && lfree && any != 0.0) {
-        const double* H = L.Hll + 6 * (size_t)l;
-        const double* B = L.bl + 3 * (size_t)l;
+        const double* H = PRE ? pre->H : L.Hll + 6 * (size_t)l;
+        const double* B = PRE ? pre->B : L.bl + 3 * (size_t)l;
         double a0 = lambda, a1 = lambda, a2 = lambda;
         if (g.ceres) { a0 = damp_of(g, lambda, H[0], g.s2l, 3 * (size_t)l); a1 = damp_of(g, lambda, H[3], g.s2l, 3 * (size_t)l + 1); a2 = damp_of(g, lambda, H[5], g.s2l, 3 * (size_t)l + 2); }
         const double h[6] = { H[0] + a0, H[1], H[2], H[3] + a1, H[4], H[5] + a2 };
@@ -3719,12 +3809,16 @@ __device__ __forceinline__ void backsub_landmark(const DeviceGraph& g, const Lin
         }
         return;
     }
+#ifdef VISFS_BA_STAMPS
+    if (pn_out && threadIdx.x == 0 && blockIdx.x == (unsigned)g.stamp_wg) g.stamps[32 + 6] = wall_clock64();      // k_backsub<LINA>: back-substitution done, trial chi2 to come
+#endif
     // computeActiveErrors + activeRobustChi2 at the trial state
     for (int k = k0 + sub; k < k1; k += G) {
-        if (L.obs_w[k] == 0.0) continue;
-        const Rt T = Pt.get(g.obs_pose[k]);
+        const bool first = PRE && k == pre->kf;
+        if ((first ? pre->wf : L.obs_w[k]) == 0.0) continue;
+        const Rt T = Pt.get(first ? pre->ipf : g.obs_pose[k]);
         Vec3 pc;
-        const Vec3 e = stereo_error(T, pn, g.obs_uvr[3 * k], g.obs_uvr[3 * k + 1], g.obs_uvr[3 * k + 2], K, pc);
+        const Vec3 e = stereo_error(T, pn, first ? pre->u : g.obs_uvr[3 * k], first ? pre->v : g.obs_uvr[3 * k + 1], first ? pre->ur : g.obs_uvr[3 * k + 2], K, pc);
         const double c2 = chi2_of(e, iv);
         double rho0 = c2, rho1 = 1.0;
         robustify(g, c2, delta, rho0, rho1);
@@ -3756,9 +3850,11 @@ __global__ __launch_bounds__(256, (DEC && Src::batched) ? (LINA ? (ODOSPEC ? 2 :
     static_assert(DL == 0 || (!DEC && !ODOSPEC), "the dogleg passes are plain launches");
     static_assert(!LINA || (DEC && DL == 0), "the fused tail carries the decision");
     extern __shared__ __attribute__((aligned(16))) double smem[];
+    // PRE (the fused tail of a lone window): what does not depend on the LM state is loaded in front of the gate — see below
+    constexpr bool PRE = LINA && !Src::batched && STG;
     if (DEC) {
         const int dw = decider_window();
-        if (dw >= 0) { decider_of(src, dw, smem, LINA ? 2 : 0); return; }
+        if (dw >= 0) { decider_of<PRE>(src, dw, smem, LINA ? 2 : 0); return; }
         if (dw == -2) return;
     }
     const DeviceGraph& g = graph_of(src);
@@ -3769,21 +3865,86 @@ __global__ __launch_bounds__(256, (DEC && Src::batched) ? (LINA ? (ODOSPEC ? 2 :
 #define BS_STAMP(slot) do { } while (0)
 #endif
     BS_STAMP(0);
-    const bool trial = (st->mode & MODE_TRIAL) != 0;
-    const bool go = trial && !st->solver_failed && !st->pcg_timeout;
+    // PRE: the kernel is as long as its chain of dependent cold loads (gate -> poses -> index data -> operands), so everything whose
+    // address and contents do not depend on the LM state is in flight before the gate is waited for: BOTH estimate buffers of this
+    // thread's pose and of its landmark (the right one is picked once sel is known: the gate and the staging become one round trip),
+    // the landmark's index data and the static data of the lane's first observation.  Safe by the launch order: index arrays are
+    // written at upload (obs_level / obs_ok by k_reset and the phase-end launches), pose[sel ^ 1] by the solver launch in front,
+    // pose[sel] / pt[sel] by nobody inside a unit; pt[sel ^ 1] of landmark l only by this very group of lanes, further down.  Every
+    // index is clamped, so a gated-off launch reads a few words for nothing and writes nothing.
+    // The LM state itself is read ONCE, all its words together, behind the first level of those loads and in front of the dependent
+    // ones (the decider writes LmState only after every workgroup has published, i.e. after this read).
+    LmPre pre;
+    double pq0[7], pq1[7], pw0[3], pw1[3];
+    int lcl = 0;
+    unsigned fixed_raw = 1u;
+    int st_mode = 0, st_failed = 0, st_timeout = 0, st_sel = 0, st_ls = 0;
+    double st_lambda = 0.0;
+    unsigned st_epoch = 0u;
+    if constexpr (PRE) {
+        pre.k0 = 0; pre.k1 = 0; pre.fixed = true; pre.kf = -1; pre.ipf = 0; pre.af = -1; pre.u = pre.v = pre.ur = 0.0; pre.act = false;
+        if (g.Np > 0) {
+            const int ic = min((int)threadIdx.x, g.Np - 1);
+            const double* a0 = g.pose[0] + POSE_STRIDE * ic;
+            const double* a1 = g.pose[1] + POSE_STRIDE * ic;
+#pragma unroll
+            for (int c = 0; c < 7; ++c) { pq0[c] = a0[c]; pq1[c] = a1[c]; }
+        }
+        if (g.Nl > 0) {
+            lcl = min((int)blockIdx.x * (256 / G) + (int)threadIdx.x / G, g.Nl - 1);
+            pre.k0 = g.lm_ptr[lcl]; pre.k1 = g.lm_ptr[lcl + 1];
+            fixed_raw = g.pt_fixed[lcl];              // (compared behind the state's read: a flag formed here would wait for the byte)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) { pw0[c] = g.pt[0][3 * lcl + c]; pw1[c] = g.pt[1][3 * lcl + c]; }
+        }
+        __builtin_amdgcn_sched_barrier(0);            // (nothing that waits for those loads may move in front of the state's)
+        st_mode = st->mode; st_failed = st->solver_failed; st_timeout = st->pcg_timeout; st_sel = st->sel; st_ls = st->lin_sel;
+        st_lambda = st->lambda; st_epoch = st->decide_epoch;
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("" :: "s"(st_mode), "s"(st_failed), "s"(st_timeout), "s"(st_sel), "s"(st_ls), "s"(st_lambda), "s"(st_epoch));   // (one wait for all of them, here)
+        // second level: the lane's first observation, and what the CURRENT linearisation set (lin_sel: 0 or 1 whatever the gate says;
+        // this launch writes the other one) holds for it and for the landmark
+        pre.wf = 0.0; pre.sd[0] = pre.sd[1] = pre.sd[2] = pre.sd[3] = 0.0;
+        asm volatile("" : "+v"(fixed_raw));
+        pre.fixed = fixed_raw != 0u;
+        if (g.Nl > 0) {
+            const LinSel<Src> lnow(g, st_ls); const LinBuf& L = lnow.get();
+#pragma unroll
+            for (int c = 0; c < 6; ++c) pre.H[c] = L.Hll[6 * (size_t)lcl + c];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) pre.B[c] = L.bl[3 * (size_t)lcl + c];
+            if (g.No > 0 && g.Np > 0) {
+                const int kq = pre.k0 + (int)threadIdx.x % G;
+                const int kcl = min(max(kq, 0), g.No - 1);
+                pre.kf = kq < pre.k1 ? kq : -1;
+                const int ip_raw = g.obs_pose[kcl];
+                const unsigned lv = g.obs_level[kcl], okb = g.obs_ok[kcl];      // (both bytes at once: `&&` would chain the second load behind the first)
+                pre.u = g.obs_uvr[3 * kcl]; pre.v = g.obs_uvr[3 * kcl + 1]; pre.ur = g.obs_uvr[3 * kcl + 2];
+                pre.wf = L.obs_w[kcl];
+                const double2* seed = reinterpret_cast<const double2*>(L.obs_pcw + 4 * (size_t)kcl);
+                const double2 s0 = seed[0], s1 = seed[1];
+                pre.ipf = min(max(ip_raw, 0), g.Np - 1);                  // (a valid observation names a pose of the window: the clamp never acts on one)
+                pre.af = g.pose_free[pre.ipf];
+                pre.act = (lv == 0u) & (okb != 0u);
+                pre.sd[0] = s0.x; pre.sd[1] = s0.y; pre.sd[2] = s1.x; pre.sd[3] = s1.y;
+            }
+        }
+    }
+    const bool trial = ((PRE ? st_mode : st->mode) & MODE_TRIAL) != 0;
+    const bool go = trial && !(PRE ? st_failed : st->solver_failed) && !(PRE ? st_timeout : st->pcg_timeout);
     // a failed solve: nothing to compute, but the decision may only be taken once every workgroup has read the gate
-    // (the tag is read where it is used: nothing of the decision's bookkeeping stays live across the landmark role)
-    if (DEC && trial && !go && (int)blockIdx.x <= g.n_lin_a && threadIdx.x == 0) publish_trial(g, blockIdx.x, st->decide_epoch + 1u, 0.0, 0.0);
+    // (the tag is read where it is used: nothing of the decision's bookkeeping stays live across the landmark role; PRE: it came with the gate)
+    if (DEC && trial && !go && (int)blockIdx.x <= g.n_lin_a && threadIdx.x == 0) publish_trial(g, blockIdx.x, (PRE ? st_epoch : st->decide_epoch) + 1u, 0.0, 0.0);
     // snapshot for the speculative linearisation that may follow (its workgroups must not read what the LM decision writes)
     if (!DEC && !LINA && !Src::batched && blockIdx.x == 0 && threadIdx.x == 0) { st->spec_go = go ? 1 : 0; st->spec_src = st->sel ^ 1; st->spec_dst = st->lin_sel ^ 1; }
     if (!go) return;
     double* sRt = smem;
     double* red = smem + (STG ? 12 * g.Np : 0);
-    const int sel = st->sel, ls = st->lin_sel;
+    const int sel = PRE ? st_sel : st->sel, ls = PRE ? st_ls : st->lin_sel;
     const double* __restrict__ pose_t = g.pose[sel ^ 1];      // trial poses (written by the solver epilogue)
     const double* __restrict__ pt = g.pt[sel];
     double* __restrict__ pt_t = g.pt[sel ^ 1];
-    const double lambda = st->lambda;
+    const double lambda = PRE ? st_lambda : st->lambda;
     const Intrinsics K = intr_of(g);
     const double iv = g.inv_pixel_var, delta = g.huber_delta;
     const int bid = blockIdx.x, tid = threadIdx.x;
@@ -3826,7 +3987,7 @@ __global__ __launch_bounds__(256, (DEC && Src::batched) ? (LINA ? (ODOSPEC ? 2 :
             chi_acc += e * (g.inv_laser_cov * e);
         }
         const double chi_tot = block_sum_256(chi_acc, red);
-        if (tid == 0) { if (DEC) publish_trial(g, bid, st->decide_epoch + 1u, chi_tot, 0.0); else { g.trial_part[2 * bid] = chi_tot; g.trial_part[2 * bid + 1] = 0.0; } }
+        if (tid == 0) { if (DEC) publish_trial(g, bid, (PRE ? st_epoch : st->decide_epoch) + 1u, chi_tot, 0.0); else { g.trial_part[2 * bid] = chi_tot; g.trial_part[2 * bid + 1] = 0.0; } }
         if (ODOSPEC) {
             __syncthreads();
             const LinSel<Src> lspec(g, ls ^ 1);                      // == spec_dst of the snapshot above
@@ -3836,7 +3997,20 @@ __global__ __launch_bounds__(256, (DEC && Src::batched) ? (LINA ? (ODOSPEC ? 2 :
     }
     double* sRt0 = red + 8;                   // poses of the linearisation point (tiles are rebuilt there)
     BS_STAMP(1);
-    if (STG) {
+    if constexpr (PRE) {
+        pre.pw = sel ? Vec3{ pw1[0], pw1[1], pw1[2] } : Vec3{ pw0[0], pw0[1], pw0[2] };
+        // the first 256 poses come from registers: pose[sel ^ 1] is the trial, pose[sel] the linearisation point
+        if (tid < g.Np) {
+            double tq_t[7], tq_0[7];
+#pragma unroll
+            for (int c = 0; c < 7; ++c) { tq_t[c] = sel ? pq0[c] : pq1[c]; tq_0[c] = sel ? pq1[c] : pq0[c]; }
+            stage_pose(tq_t, sRt + 12 * tid);
+            stage_pose(tq_0, sRt0 + 12 * tid);
+        }
+        stage_poses(pose_t, g.Np, sRt, 256);
+        stage_poses(g.pose[sel], g.Np, sRt0, 256);
+        __syncthreads();
+    } else if (STG) {
         stage_poses(pose_t, g.Np, sRt);
         stage_poses(g.pose[sel], g.Np, sRt0);
         __syncthreads();
@@ -3849,7 +4023,8 @@ __global__ __launch_bounds__(256, (DEC && Src::batched) ? (LINA ? (ODOSPEC ? 2 :
     const bool lvalid = l < g.Nl;
     double chi_acc = 0.0, scale_acc = 0.0, step_acc = 0.0, dot_acc = 0.0;
     Vec3 pn{ 0.0, 0.0, 0.0 };
-    backsub_landmark<G, STG, DL>(g, L, l, lvalid, sub, Pt, P0, pt, pt_t, lambda, K, iv, delta, chi_acc, scale_acc, &step_acc, &dot_acc, st->dl_A, st->dl_B, LINA ? &pn : nullptr);
+    backsub_landmark<G, STG, DL, PRE>(g, L, l, lvalid, sub, Pt, P0, pt, pt_t, lambda, K, iv, delta, chi_acc, scale_acc, &step_acc, &dot_acc, st->dl_A, st->dl_B, LINA ? &pn : nullptr,
+                                      PRE ? &pre : nullptr);
     BS_STAMP(3);
     const double chi_tot = block_sum_256(chi_acc, red);
     const double sc_tot = block_sum_256(scale_acc, red);
@@ -3860,13 +4035,13 @@ __global__ __launch_bounds__(256, (DEC && Src::batched) ? (LINA ? (ODOSPEC ? 2 :
         return;
     }
     if (g.ceres) { const double st_tot = block_sum_256(step_acc, red); if (tid == 0) g.aux_part[bid] = st_tot; }
-    if (tid == 0) { if (DEC) publish_trial(g, bid, st->decide_epoch + 1u, chi_tot, sc_tot); else { g.trial_part[2 * bid] = chi_tot; g.trial_part[2 * bid + 1] = sc_tot; } }
+    if (tid == 0) { if (DEC) publish_trial(g, bid, (PRE ? st_epoch : st->decide_epoch) + 1u, chi_tot, sc_tot); else { g.trial_part[2 * bid] = chi_tot; g.trial_part[2 * bid + 1] = sc_tot; } }
     if (LINA) {
         // role A of the speculative linearisation for this workgroup's landmarks (LmState is not read from here on: the decider may
         // already be rewriting it — sel / ls are the values read at the top)
         const LinSel<Src> lspec(g, ls ^ 1);
         double chi2 = 0.0, md2 = 0.0;
-        lin_landmark<G, STG>(g, lspec.get(), l, lvalid, sub, Pt, pt_t, K, iv, delta, chi2, md2, nullptr, &pn);
+        lin_landmark<G, STG, PRE>(g, lspec.get(), l, lvalid, sub, Pt, pt_t, K, iv, delta, chi2, md2, nullptr, &pn, PRE ? &pre : nullptr);
         // (no lin_part here: the chi2 of an accepted trial is the trial's, max |diag H| is only read at the first iteration of a phase,
         // which linearises with k_linearize)
         BS_STAMP(5);
