@@ -1,0 +1,76 @@
+// FlowTracker.h — the pixel half of VISFS::Tracker::imageProcess (corelib/src/Tracker.cpp:233-274, :343-388) backed by the
+// GPU-resident image pyramids of include/visfs_flow.h.  Header only, over the C ABI.
+//
+// It keeps what imageProcess does with pixels: the four cv::calcOpticalFlowPyrLK passes of a frame with their forward-backward gates
+// and generateKeyPoints3DStereo.  Corner extraction (cv::goodFeaturesToTrack), the bounds test and the compaction of the surviving
+// words stay with the caller, as in the reference they surround these calls.
+#ifndef VISFS_AMD_FLOW_TRACKER_H
+#define VISFS_AMD_FLOW_TRACKER_H
+
+#include <cstdint>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "visfs_flow.h"
+
+namespace VISFS {
+
+class FlowTracker {
+public:
+    struct Point2f { float x, y; };
+    struct Point3f { float x, y, z; };
+
+    FlowTracker(const FlowTracker&) = delete;
+    FlowTracker& operator=(const FlowTracker&) = delete;
+
+    // ba: the handle whose device and stream the pyramids live on; the Tracker/* keys as the reference names them.
+    FlowTracker(visfs_ba_handle* ba, int width, int height, int flowWinSize = 21, int flowMaxLevel = 3, int flowIterations = 30,
+                float flowEps = 0.01f, bool flowBack = true, float minDepth = 0.2f, float maxDepth = 10.0f) {
+        visfs_flow_params p;
+        visfs_flow_default_params(&p);
+        p.win_size = flowWinSize; p.max_level = flowMaxLevel; p.iterations = flowIterations; p.eps = flowEps;
+        p.flow_back = flowBack ? 1 : 0; p.min_depth = minDepth; p.max_depth = maxDepth;
+        const int rc = visfs_flow_create(ba, &p, width, height, &f_);
+        if (rc != VISFS_BA_OK) throw std::runtime_error("visfs_flow_create failed with status " + std::to_string(rc));
+    }
+    ~FlowTracker() { visfs_flow_destroy(f_); }
+
+    // A new stereo pair (8-bit grey, `stride` bytes per row); the pair pushed before becomes imageFrom.
+    int pushFrame(const uint8_t* left, const uint8_t* right, int stride) { return visfs_flow_push_frame(f_, left, right, stride); }
+
+    // Tracker.cpp:257-274: cornersFrom -> cornersTo (cornersTo non-empty on entry: OPTFLOW_USE_INITIAL_FLOW), status after the gate.
+    int track(const std::vector<Point2f>& cornersFrom, std::vector<Point2f>& cornersTo, std::vector<unsigned char>& status,
+              std::vector<float>* err = nullptr) {
+        const bool guess = cornersTo.size() == cornersFrom.size() && !cornersFrom.empty();
+        std::vector<Point2f> init;
+        if (guess) init = cornersTo;
+        cornersTo.resize(cornersFrom.size());
+        status.resize(cornersFrom.size());
+        if (err) err->resize(cornersFrom.size());
+        return visfs_flow_track(f_, (int32_t)cornersFrom.size(), flat(cornersFrom), guess ? flat(init) : nullptr, flat(cornersTo),
+                                status.data(), err ? err->data() : nullptr);
+    }
+
+    // Tracker.cpp:354-371 + generateKeyPoints3DStereo (:388): cornersLeft -> cornersRight, status after the gate, kpts3D (robot frame,
+    // NaN where the reference leaves badPoint or the point was dropped).
+    int stereo(const std::vector<Point2f>& cornersLeft, const visfs_flow_camera& camera, std::vector<Point2f>& cornersRight,
+               std::vector<unsigned char>& status, std::vector<Point3f>& kpts3D) {
+        cornersRight.resize(cornersLeft.size());
+        status.resize(cornersLeft.size());
+        kpts3D.resize(cornersLeft.size());
+        return visfs_flow_stereo(f_, (int32_t)cornersLeft.size(), flat(cornersLeft), &camera, flat(cornersRight), status.data(),
+                                 kpts3D.empty() ? nullptr : &kpts3D[0].x);
+    }
+
+    const char* lastError() const { return visfs_flow_last_error(f_); }
+
+private:
+    static const float* flat(const std::vector<Point2f>& v) { return v.empty() ? nullptr : &v[0].x; }
+    static float* flat(std::vector<Point2f>& v) { return v.empty() ? nullptr : &v[0].x; }
+    visfs_flow* f_ = nullptr;
+};
+
+}  // namespace VISFS
+
+#endif
