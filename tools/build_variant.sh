@@ -4,4 +4,4 @@
 set -e
 cd "$(dirname "$0")/.."
 name=$1; shift
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared "$@" -o visfs_amd/lib/libvisfs_ba_hip_$name.so visfs_amd/csrc/ba_kernels.hip visfs_amd/csrc/ba_cov.hip visfs_amd/csrc/ba_submap.hip visfs_amd/csrc/ba_flow.hip visfs_amd/csrc/ba_api.cpp -lpthread
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared "$@" -o visfs_amd/lib/libvisfs_ba_hip_$name.so visfs_amd/csrc/ba_kernels.hip visfs_amd/csrc/ba_cov.hip visfs_amd/csrc/ba_submap.hip visfs_amd/csrc/ba_flow.hip visfs_amd/csrc/ba_corners.hip visfs_amd/csrc/ba_api.cpp -lpthread

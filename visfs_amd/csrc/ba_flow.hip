@@ -10,8 +10,7 @@
 //                         lane; an iteration gathers the moving window's four neighbours per cell, multiplies in int32 and adds
 //                         across the wavefront in int64; every lane then runs the scalar tail on the same sums.
 // The sums are exact integers, so device and host agree to the byte whatever the order of summation.
-#include "ba_flow.hpp"
-#include "../../include/visfs_flow.h"
+#include "ba_flow_object.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -107,34 +106,6 @@ static int blocks_for(int64_t n) { return (int)((n + FL_T - 1) / FL_T); }
 static size_t up256(size_t x) { return (x + 255) & ~size_t(255); }
 
 }  // namespace flow
-
-// ---------------------------------------------------------------- the tracker object
-struct visfs_flow {
-    visfs_flow_params prm{};
-    LkParams lk{};
-    int32_t w = 0, h = 0;
-    Layout lay{};
-    std::string err;
-    bool device = false;
-    int frames = 0;              // pushed so far
-    int cur = 0;                 // slot of the current pair
-
-    // host restatement: [slot][image]
-    std::vector<uint8_t> hpx[2][2];
-    std::vector<uint32_t> hder[2][2];
-
-    // device
-    visfs_ba_handle* ba = nullptr;
-    int dev = 0;
-    hipStream_t stream = nullptr;
-    char* d_mem = nullptr;       // the four images' pixels and derivatives
-    uint8_t* dpx[2][2] = {};
-    uint32_t* dder[2][2] = {};
-    uint8_t* h_img = nullptr;    // pinned: both level-0 images of a frame
-    char* h_io = nullptr;        // pinned: a call's points in, results out
-    char* d_io = nullptr;
-    int32_t io_cap = 0;          // points
-};
 
 namespace {
 
@@ -390,6 +361,7 @@ int visfs_flow_create(visfs_ba_handle* h, const visfs_flow_params* p, int32_t wi
 
 void visfs_flow_destroy(visfs_flow* f) {
     if (!f) return;
+    flow::corners_release(f);
     release(f);
     delete f;
 }

@@ -1,17 +1,21 @@
 // FlowTracker.h — the pixel half of VISFS::Tracker::imageProcess (corelib/src/Tracker.cpp:233-274, :343-388) backed by the
 // GPU-resident image pyramids of include/visfs_flow.h.  Header only, over the C ABI.
 //
-// It keeps what imageProcess does with pixels: the four cv::calcOpticalFlowPyrLK passes of a frame with their forward-backward gates
-// and generateKeyPoints3DStereo.  Corner extraction (cv::goodFeaturesToTrack), the bounds test and the compaction of the surviving
-// words stay with the caller, as in the reference they surround these calls.
+// It keeps what imageProcess does with pixels: the two cv::goodFeaturesToTrack calls behind the mask of getMask (:116-141, :181, :327,
+// include/visfs_corners.h), the four cv::calcOpticalFlowPyrLK passes of a frame with their forward-backward gates and
+// generateKeyPoints3DStereo.  The bounds test and the compaction of the surviving words stay with the caller, as in the reference
+// they surround these calls; so do the fundamental-matrix cull and the PnP guess.
 #ifndef VISFS_AMD_FLOW_TRACKER_H
 #define VISFS_AMD_FLOW_TRACKER_H
 
+#include <algorithm>
 #include <cstdint>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
+#include "visfs_corners.h"
 #include "visfs_flow.h"
 
 namespace VISFS {
@@ -61,6 +65,38 @@ public:
         kpts3D.resize(cornersLeft.size());
         return visfs_flow_stereo(f_, (int32_t)cornersLeft.size(), flat(cornersLeft), &camera, flat(cornersRight), status.data(),
                                  kpts3D.empty() ? nullptr : &kpts3D[0].x);
+    }
+
+    // cv::goodFeaturesToTrack(image, out, maxCorners, qualityLevel, minDistance, mask) on the resident left image of the newest pair
+    // (previous: of the pair before it), the mask given as the discs of maskDiscs.  Strongest first.
+    int corners(std::vector<Point2f>& out, int maxCorners, double qualityLevel, double minDistance,
+                const std::vector<visfs_corners_disc>& discs = {}, bool previous = false) {
+        visfs_corners_params p;
+        visfs_corners_default_params(&p);
+        p.max_corners = maxCorners; p.quality_level = qualityLevel; p.min_distance = minDistance;
+        out.resize((size_t)std::min(std::max(maxCorners, 0), VISFS_CORNERS_MAX_CORNERS));    // beyond it the library refuses
+        int32_t n = 0;
+        Point2f none{ 0.0f, 0.0f };
+        const int rc = visfs_flow_corners(f_, previous ? VISFS_FLOW_SLOT_PREVIOUS : VISFS_FLOW_SLOT_CURRENT, VISFS_FLOW_IMAGE_LEFT, &p,
+                                          (int32_t)discs.size(), discs.empty() ? nullptr : discs.data(), (int32_t)out.size(),
+                                          out.empty() ? &none.x : &out[0].x, &n);
+        out.resize(rc == VISFS_BA_OK ? (size_t)n : 0);
+        return rc;
+    }
+
+    // The disc list of Tracker::getMask (Tracker.cpp:116-141): the tracked points by track count descending at radius minDistance,
+    // then the blocked points at radius minDistance / 2 (integer division, as the reference writes it).  The reference's std::sort
+    // (:126) leaves the order among equal counts open; this helper uses std::stable_sort, so equal counts keep the order given.
+    static std::vector<visfs_corners_disc> maskDiscs(const std::vector<std::pair<int, Point2f>>& trackCountAndPoint,
+                                                     const std::vector<Point2f>& blocked, int minDistance) {
+        std::vector<std::pair<int, Point2f>> sorted = trackCountAndPoint;
+        std::stable_sort(sorted.begin(), sorted.end(),
+                         [](const std::pair<int, Point2f>& a, const std::pair<int, Point2f>& b) { return a.first > b.first; });
+        std::vector<visfs_corners_disc> discs;
+        discs.reserve(sorted.size() + blocked.size());
+        for (const auto& cp : sorted) discs.push_back(visfs_corners_disc{ cp.second.x, cp.second.y, minDistance });
+        for (const Point2f& b : blocked) discs.push_back(visfs_corners_disc{ b.x, b.y, minDistance / 2 });
+        return discs;
     }
 
     const char* lastError() const { return visfs_flow_last_error(f_); }
