@@ -26,6 +26,7 @@
 #include "../../include/visfs_ba.h"
 #include "ba_cov.hpp"
 #include "ba_kernels.hpp"
+#include "ba_plan.hpp"
 #include "ba_submap.hpp"
 #include "worker_pool.hpp"
 
@@ -49,45 +50,6 @@ struct Arena {
 
 // Host scratch of the window layer that survives from call to call (a fresh std::vector of this size is an mmap, a page fault per
 // 4 KiB on first touch and an munmap, every frame — and page faults from several threads at once serialise in the kernel).
-// What the run-based Schur kernel (k_schur_runs) needs to know about 8 consecutive landmarks: how many observations they have and
-// which poses (index space of the window, fixed ones included) those touch.
-struct RunGroup { int32_t cnt = 0; int32_t lo = 0x7fffffff, hi = -1; };
-constexpr int RUN_GROUP = 8;
-struct alignas(128) SummaryPart {          // (one per thread, updated per observation: no two may share a cache line)
-    std::vector<int32_t> cnt, run, pc, track;
-    std::vector<RunGroup> grp;
-    int64_t pairs = 0; int ok = 0; bool any_run = false, used = false; const char* bad = nullptr;
-    int npf = 0; int cur = -1; bool cur_fixed = false;
-    int first = -1, last = -1, c = 0; bool gap = false;         // the current landmark's free poses: a contiguous run unless `gap`
-    void begin(int Npf, int Nl) {
-        used = true; npf = Npf; cnt.assign(Npf + 1, 0); run.assign((size_t)Npf * Npf, 0); pc.clear(); track.clear();
-        grp.assign((size_t)(Nl + RUN_GROUP - 1) / RUN_GROUP + 1, RunGroup());
-        pairs = 0; ok = 0; any_run = false; bad = nullptr; cur = -1; first = last = -1; c = 0; gap = false;
-    }
-    // observations arrive landmark by landmark (a landmark never straddles two accumulators), poses ascending inside a landmark
-    inline void add(int landmark, bool landmark_fixed, int a /* free index of the pose, -1: fixed */, int pose /* its index in the window */) {
-        if (landmark != cur) { flush(); cur = landmark; cur_fixed = landmark_fixed; }
-        { RunGroup& G = grp[(size_t)landmark / RUN_GROUP]; G.cnt++; G.lo = std::min(G.lo, pose); G.hi = std::max(G.hi, pose); }
-        ok += !(a < 0 && landmark_fixed);
-        if (a < 0) return;
-        cnt[a + 1]++;
-        if (c == 0) { first = last = a; c = 1; return; }
-        if (!gap && a != last + 1) { gap = true; track.clear(); for (int q = first; q <= last; ++q) track.push_back(q); }   // (rare) the members so far were a run
-        if (gap) track.push_back(a);
-        last = a; ++c;
-    }
-    void flush() {
-        if (cur >= 0 && !cur_fixed && c > 0) {
-            pairs += (int64_t)c * (c + 1) / 2;
-            if (!gap) { run[(size_t)first * npf + last]++; any_run = true; }
-            else {
-                if (pc.empty()) pc.assign((size_t)npf * npf, 0);      // tracks with gaps are rare: their pairwise table only exists when one shows up
-                for (int i = 0; i < c; ++i) { int32_t* row = pc.data() + (size_t)track[i] * npf; for (int j = i; j < c; ++j) row[track[j]]++; }
-            }
-        }
-        c = 0; gap = false; first = last = -1;
-    }
-};
 struct PackedWindow {
     std::vector<uint8_t> pose_fixed, point_used;
     std::vector<int32_t> obs_ref;
@@ -240,10 +202,9 @@ int bad(visfs_ba_handle* h, const char* msg) { h->err = msg; return VISFS_BA_ERR
 WorkerPool* host_pool(visfs_ba_handle* h) {
     if (!h->pool_tried) {
         h->pool_tried = true;
-        const char* e = std::getenv("VISFS_BA_THREADS");
         const int llc = WorkerPool::llc_domain_cpus();
         const int dflt = llc >= 2 ? std::min(8, std::max(1, llc / 2)) : (int)std::min(4u, std::max(1u, std::thread::hardware_concurrency()));
-        int n = e ? std::atoi(e) : dflt;
+        int n = env_int("VISFS_BA_THREADS", dflt);
         n = std::max(1, std::min(n, 16));
         if (n > 1) { try { h->pool.reset(new WorkerPool(n - 1)); } catch (...) { h->pool.reset(); } }
     }
@@ -339,88 +300,119 @@ int ensure_prim(visfs_ba_handle* h, Workspace& w, size_t bytes) {
     return VISFS_BA_OK;
 }
 
-// What the host has to know about the O(N_obs) part of the graph: observations per free pose and co-observation pairs per block of S.
-struct GraphSummary {
-    std::vector<int32_t> cnt;          // [Npf + 1] prefix: observations of free pose a at pose-major positions [cnt[a], cnt[a + 1])
-    std::vector<int32_t> pcount;       // [Npf][Npf] (a <= b): free landmarks observed by both
-    int64_t pairs_seen = 0;
-    int n_edges_ok = 0;
-    const char* bad = nullptr;
-    std::vector<RunGroup> grp;         // per RUN_GROUP consecutive landmarks
+static_assert(sizeof(Desc4) == sizeof(int4) && alignof(Desc4) == alignof(int4), "the plan's descriptors are read by the device as int4");
+
+// The INDEX section (block-level structure of S, small): every array of it named once — the DeviceGraph member, the plan's data, the
+// element count, the minimum count of its slot and whether the array exists at all.  Walked three times per upload: to size the section,
+// to point the host DeviceGraph into the pinned staging arena and fill it (`copy`), to point the device DeviceGraph (same offsets).
+struct IndexWalk {
+    Arena A; bool copy;
+    template <typename T, typename U>
+    void operator()(const T*& member, const std::vector<U>& src, size_t n, size_t n_min = 0, bool present = true) {
+        static_assert(sizeof(T) == sizeof(U), "element types of the plan and of the device graph differ");
+        if (!present) { member = nullptr; return; }
+        T* p = A.take<T>(std::max(n, n_min));
+        if (copy && n) std::memcpy(p, src.data(), n * sizeof(T));
+        member = p;
+    }
 };
-// One pass over the observations (landmark-major), shared out over the pool at landmark boundaries.
-// A landmark seen by the free poses {a_1 < ... < a_k} adds one pair to every block (a_i, a_j), i <= j.  Tracks are runs of consecutive
-// key-frames almost always (a feature is tracked frame to frame and never re-acquired), so a landmark whose free poses form the
-// contiguous range [s, e] only bumps run[s][e]; the blocks are then counted by one 2-D inclusion sum, pcount[a][b] = sum over s <= a,
-// e >= b of run[s][e] — O(Nl + Npf^2) instead of O(sum k^2).  Landmarks with gaps in their track take the pairwise loop.
-void merge_summary(std::vector<SummaryPart>& part, const int NT, const int Npf, GraphSummary& S, std::vector<int32_t>& run) {
-    const size_t nn = (size_t)Npf * Npf;
-    S.cnt.assign(Npf + 1, 0); S.pcount.assign(nn, 0); S.pairs_seen = 0; S.n_edges_ok = 0; S.bad = nullptr;
-    run.assign(nn, 0);
-    bool any_run = false;
-    for (int t = 0; t < NT; ++t) {
-        const SummaryPart& P = part[t];
-        if (!P.used) continue;
-        if (P.bad) { S.bad = P.bad; return; }
-        for (int a = 0; a <= Npf; ++a) S.cnt[a] += P.cnt[a];
-        if (!P.pc.empty()) for (size_t q = 0; q < nn; ++q) S.pcount[q] += P.pc[q];
-        for (size_t q = 0; q < nn; ++q) run[q] += P.run[q];
-        S.pairs_seen += P.pairs; S.n_edges_ok += P.ok; any_run = any_run || P.any_run;
-    }
-    for (int a = 0; a < Npf; ++a) S.cnt[a + 1] += S.cnt[a];
-    S.grp.clear();
-    for (int t = 0; t < NT; ++t) {
-        const SummaryPart& P = part[t];
-        if (!P.used) continue;
-        if (S.grp.size() < P.grp.size()) S.grp.resize(P.grp.size());
-        for (size_t q = 0; q < P.grp.size(); ++q) { RunGroup& G = S.grp[q]; G.cnt += P.grp[q].cnt; G.lo = std::min(G.lo, P.grp[q].lo); G.hi = std::max(G.hi, P.grp[q].hi); }
-    }
-    if (any_run) {
-        // in place: run[a][b] <- sum_{s <= a, e >= b} run[s][e]
-        for (int a = 0; a < Npf; ++a)
-            for (int b2 = Npf - 1; b2 >= 0; --b2) {
-                int64_t v = run[(size_t)a * Npf + b2];
-                if (a > 0) v += run[(size_t)(a - 1) * Npf + b2];
-                if (b2 + 1 < Npf) v += run[(size_t)a * Npf + b2 + 1];
-                if (a > 0 && b2 + 1 < Npf) v -= run[(size_t)(a - 1) * Npf + b2 + 1];
-                run[(size_t)a * Npf + b2] = (int32_t)v;
-            }
-        for (int a = 0; a < Npf; ++a) for (int b2 = a; b2 < Npf; ++b2) S.pcount[(size_t)a * Npf + b2] += run[(size_t)a * Npf + b2];
-    }
+size_t layout_index(IndexWalk W, DeviceGraph& g, const UploadPlan& P) {
+    const size_t Npf = P.Npf, n_blk = P.n_blk, n_sch = P.n_sch, n_chunks = P.n_chunks;
+    W(g.chunk_pose, P.chunk_pose, n_chunks, 1);
+    W(g.chunk_ptr, P.chunk_ptr, n_chunks + 1);
+    W(g.pose_chunk_ptr, P.pose_chunk_ptr, Npf + 1);
+    W(g.pose_odo_ptr, P.pose_odo_ptr, Npf + 1);
+    W(g.pose_odo, P.pose_odo, P.pose_odo.size(), 1);
+    W(g.blk_i, P.blk_i, n_blk, 1);
+    W(g.blk_j, P.blk_j, n_blk, 1);
+    W(g.blk_ptr, P.blk_ptr, n_blk + 1);
+    W(g.blk_chunk_ptr, P.blk_chunk_ptr, n_blk + 1);
+    W(g.sch_desc, P.sch_desc, P.sch_desc.size());
+    W(g.blk_desc, P.blk_desc, P.blk_desc.size());
+    W(g.blk_odo_ptr, P.blk_odo_ptr, n_blk + 1);
+    W(g.blk_odo, P.blk_odo, P.blk_odo.size(), 1);
+    W(g.row_ptr, P.row_ptr, Npf + 1);
+    W(g.row_col, P.row_col, P.row_col.size(), 1);
+    W(g.row_blk, P.row_blk, P.row_blk.size(), 1);
+    W(g.blk_slot, P.blk_slot, n_blk, 1);
+    W(g.fin_exp, P.fin_exp, n_blk, 1);
+    W(g.sch_blk, P.sch_blk, n_sch, 1);
+    W(g.diag_blk, P.diag_blk, Npf, 1);
+    W(g.pcg1_code, P.pcg1_code, P.pcg1_code.size(), 0, P.pcg1);
+    W(g.band_code, P.band_code, P.band_code.size(), 0, P.band_B >= 0);
+    W(g.run_desc, P.run.desc, P.run.desc.size(), 0, P.run_path());
+    W(g.run_k0, P.run.k0, P.run.k0.size(), 0, P.run_path());
+    return (W.A.used + 255) & ~size_t(255);
 }
-void summarize_graph(const visfs_ba_graph* gr, const int32_t* pose_free, const int Npf, WorkerPool* pool, const bool check, GraphSummary& S,
-                     std::vector<SummaryPart>& part, std::vector<int32_t>& run) {
-    const int No = gr->n_obs, Nl = gr->n_points, Np = gr->n_poses;
-    const size_t nn = (size_t)Npf * Npf;
-    // several tasks per thread (a worker that wakes late still finds work); accumulators per THREAD, not per task
-    const int NT = (pool && No >= 16384 && nn <= ((size_t)1 << 17)) ? pool->size() : 1;
-    const int T = NT > 1 ? 4 * NT : 1;
-    std::vector<int> cut(T + 1, No);
-    cut[0] = 0;
-    for (int t = 1; t < T; ++t) {
-        int k = (int)((int64_t)No * t / T);
-        k = std::max(k, cut[t - 1]);
-        while (k > 0 && k < No && gr->obs_point[k] == gr->obs_point[k - 1]) ++k;     // a landmark's observations stay with one task
-        cut[t] = k;
+
+// The MUTABLE section, behind the index section in the same device arena: everything of size N_obs that is derived (lm_ptr, obs_ok,
+// pose_obs, obs_ppos, the pair lists) is built on the device from the primary section.  d_hist: scratch of launch_build_index;
+// zero_end: where the span that the upload clears ends.  Returns the arena's size.
+struct DynOpts { bool raw_refs = false, dogleg = false; LmState* st = nullptr; };
+size_t layout_dyn(Arena A, DeviceGraph& g, const UploadPlan& P, const DynOpts& o, int32_t** d_hist, size_t* zero_end) {
+    const int Np = P.Np, Nl = P.Nl, No = P.No, Ne = P.Ne, Npf = P.Npf, n_pose_obs = P.n_pose_obs, n_blk = P.n_blk, n_parts = P.n_parts;
+    const size_t n6 = (size_t)6 * Npf, chol_np = P.chol_np;
+    // device-built index arrays
+    g.lm_ptr = A.take<int32_t>(Nl + 1);
+    g.obs_ok = A.take<uint8_t>(std::max(No, 1));
+    g.obs_ppos = A.take<int32_t>(std::max(No, 1));
+    g.pose_obs = A.take<int32_t>(std::max(n_pose_obs, 1));
+    if (o.raw_refs) g.obs_uvr = A.take<double>((size_t)std::max(No, 1) * 3);      // written by k_index_count from obs_uvd
+    *d_hist = A.take<int32_t>(P.n_hist);
+    for (int k = 0; k < 2; ++k) {                       // the two linearisation sets: same layout, constant distance
+        LinBuf& L = g.lin[k];
+        L.obs_w = A.take<double>(std::max(No, 1));
+        L.obs_pcw = A.take<double>((size_t)std::max(No, 1) * 4);
+        L.pose_pcw = A.take<double>((size_t)std::max(n_pose_obs, 1) * 4);
+        L.Hll = A.take<double>((size_t)std::max(Nl, 1) * 6);
+        L.bl = A.take<double>((size_t)std::max(Nl, 1) * 3);
+        L.hpp_part = A.take<double>((size_t)std::max(P.n_chunks, 1) * 27);
+        L.odo_blk = A.take<double>((size_t)(Ne + 1) * 120);
     }
-    if ((int)part.size() < NT) part.resize(NT);
-    for (int t = 0; t < NT; ++t) part[t].used = false;
-    auto body = [&](int t, int slot) {
-        SummaryPart& P = part[slot];
-        if (!P.used) P.begin(Npf, Nl);
-        if (P.bad) return;
-        for (int k = cut[t]; k < cut[t + 1]; ++k) {
-            const int l = gr->obs_point[k], cp = gr->obs_pose[k];
-            if (check) {
-                if (l < 0 || l >= Nl || cp < 0 || cp >= Np) { P.bad = "observation index out of range"; return; }
-                if (k > 0 && (l < gr->obs_point[k - 1] || (l == gr->obs_point[k - 1] && cp <= gr->obs_pose[k - 1]))) { P.bad = "observations must be sorted by (point, pose) and unique"; return; }
-            }
-            P.add(l, gr->point_fixed[l] != 0, pose_free[cp], cp);
-        }
-        P.flush();
-    };
-    if (T > 1) pool->run(T, body); else body(0, 0);
-    merge_summary(part, NT, Npf, S, run);
+    g.lin_stride = reinterpret_cast<char*>(g.lin[1].obs_w) - reinterpret_cast<char*>(g.lin[0].obs_w);
+    g.pose[0] = A.take<double>((size_t)Np * POSE_STRIDE); g.pose[1] = A.take<double>((size_t)Np * POSE_STRIDE);
+    g.pt[0] = A.take<double>((size_t)std::max(Nl, 1) * 3); g.pt[1] = A.take<double>((size_t)std::max(Nl, 1) * 3);
+    g.obs_outlier = A.take<uint8_t>(std::max(No, 1));   // (right behind the estimates: pose[0] .. obs_outlier are one span in the order and alignment of
+                                                         // output_stage_of, so a solve's outputs come back in ONE device-to-host copy)
+    g.obs_level = A.take<uint8_t>(std::max(No, 1));
+    g.obs_chi2_out = A.take<double>(std::max(No, 1));
+    g.obs_chi2 = A.take<double>(std::max(No, 1));
+    g.Hpp = A.take<double>((size_t)std::max(Npf, 1) * 36);
+    g.bp = A.take<double>(std::max<size_t>(n6, 1));
+    g.lin_part = A.take<double>((size_t)n_parts * 2);
+    g.S = A.take<double>((size_t)std::max(n_blk, 1) * 36);
+    g.S_rows = A.take<double>(P.pcg_cu ? (size_t)P.cu_max_row * 6 * P.cu_T : 1);      // (inside the span the upload clears: slots a row does not use read as zero)
+    g.bs = A.take<double>(std::max<size_t>(n6, 1));
+    g.Minv = A.take<double>((size_t)std::max(Npf, 1) * 36);
+    g.x = A.take<double>(std::max<size_t>(n6, 1));
+    g.sch_part = A.take<double>((size_t)std::max<int64_t>(std::max<int64_t>(P.n_sch, P.run.total), 1) * 42);
+    g.granules = A.take<unsigned long long>(std::max<size_t>(4 * n6 + Npf, 1));        // + one placement word per block row (k_pcg1)
+    g.dxl = A.take<double>((size_t)std::max(Nl, 1) * 3);
+    g.trial_part = A.take<double>((size_t)n_parts * 2);
+    g.trial_gran = A.take<unsigned long long>((size_t)n_parts * 4);
+    g.fin_flag = A.take<uint32_t>((size_t)std::max(n_blk, 1));
+    g.fin_cnt = A.take<uint32_t>((size_t)std::max(n_blk, 1));
+    g.aux_part = A.take<double>((size_t)n_parts);
+    g.dl_part = A.take<double>(o.dogleg ? (size_t)n_parts * 4 : 1);
+    g.s2l = A.take<double>((size_t)std::max(Nl, 1) * 3);
+    g.s2p = A.take<double>(std::max<size_t>(n6, 1));
+    const bool dense_chol = P.band_B < 0 && (P.solver != 2 || (!P.small_fits && chol_np <= 2048));   // (PCG windows: the fallback's scratch, up to 67 MB)
+    g.dense = A.take<double>(dense_chol ? chol_np * chol_np : 1);
+    g.chol_f = A.take<double>(dense_chol ? chol_np * chol_np : 1);
+    g.band_L = A.take<double>(P.band_B >= 0 && P.band_rows < Npf ? (size_t)Npf * (P.band_B + 1) * 36 : 1);
+    g.chol_y = A.take<double>(chol_np);
+    g.chol_linv = A.take<double>(2 * 32 * 32);
+    g.stamps = A.take<unsigned long long>(128);
+    g.st = o.st;                                        // (its own allocation: the address does not move with the window's sizes)
+    // ---- from here on: arrays that are written in full before anything reads them — not part of the upload's clearing pass (a third
+    // of the arena at C2: the stage hooks' H_pl tiles and residuals exist for every window but are only written under `debug`)
+    *zero_end = (A.used + 255) & ~size_t(255);
+    g.blk_pairs = A.take<int4>((size_t)std::max<int64_t>(P.run_path() ? 0 : P.npairs, 1));      // every slot filled on the device (k_build_pairs: the counts are the summary's)
+    g.pose_lm = A.take<int32_t>(std::max(n_pose_obs, 1));                   // every slot filled by k_index_scatter
+    g.pose_rec = A.take<DeviceGraph::PoseRec>(std::max(n_pose_obs, 1));     // likewise
+    g.obs_err = A.take<double>((size_t)std::max(No, 1) * 3);               // debug: every observation, active or not (k_linearize)
+    g.W = A.take<double>((size_t)std::max(No, 1) * 18);                    // likewise
+    return (A.used + 255) & ~size_t(255);
 }
 
 struct UploadOpts {
@@ -433,16 +425,8 @@ struct UploadOpts {
     const float* d_grid = nullptr;   // the laser grid's costs in device memory: copied device to device, gr->grid->correspondence_cost not read
 };
 
-int ws_upload(visfs_ba_handle* h, Workspace& w, const visfs_ba_graph* gr, const UploadOpts& opt = UploadOpts()) {
-    const bool timing = std::getenv("VISFS_BA_TIMING") != nullptr;
-    auto T0 = std::chrono::steady_clock::now();
-    auto lap = [&](const char* what) { if (timing) { auto t = std::chrono::steady_clock::now(); std::fprintf(stderr, "  upload %-14s %8.1f us\n", what, std::chrono::duration<double, std::micro>(t - T0).count()); T0 = t; } };
-    const visfs_ba_params& prm = h->prm;
-    const bool ceres = prm.framework == 1;
-    // From the first mutation below (the primary arrays are overwritten before the graph has been validated) until the upload has gone
-    // through, NO graph is resident: a failed upload must not leave the previous graph's index structures marked usable over the
-    // rejected graph's arrays (visfs_ba_optimize then returns VISFS_BA_ERR_NOT_LOADED instead of walking them).
-    w.loaded = false;
+// Sizes and laser / grid arguments of a graph.  G: the sizes in use (no odometry in the Ceres branch, no laser points on a fixed pose).
+int validate_graph(visfs_ba_handle* h, const visfs_ba_graph* gr, const bool ceres, PlanGraph& G, size_t& grid_cells) {
     // (Optimizer.cpp:405-422: the Ceres branch never adds a wheel-odometry factor — links between two window poses fall in its "TODO" arm)
     const int Np = gr->n_poses, Nl = gr->n_points, No = gr->n_obs, Ne = ceres ? 0 : gr->n_odo;
     if (Np < 1 || Nl < 0 || No < 0 || Ne < 0) return bad(h, "negative sizes");
@@ -451,33 +435,30 @@ int ws_upload(visfs_ba_handle* h, Workspace& w, const visfs_ba_graph* gr, const 
             return bad(h, "odometry edge index out of range");
     // laser occupied-space edges (Optimizer.cpp:224-258): active only while their pose is free (allVerticesFixed otherwise)
     int Nz = 0;
-    size_t grid_cells = 0;
+    grid_cells = 0;
     if (gr->n_laser < 0) return bad(h, "negative sizes");
     if (gr->n_laser > 0) {
         if (!gr->grid || !gr->laser_xyz) return bad(h, "laser points need a grid and coordinates");
-        const visfs_ba_grid& G = *gr->grid;
+        const visfs_ba_grid& Gr = *gr->grid;
         if (gr->laser_pose < 0 || gr->laser_pose >= Np) return bad(h, "laser pose index out of range");
-        if (!(G.resolution > 0.0) || G.num_x_cells <= 0 || G.num_y_cells <= 0 || !G.correspondence_cost) return bad(h, "invalid grid");
-        if ((int64_t)G.num_x_cells * G.num_y_cells > (int64_t)1 << 28) { h->err = "grid larger than 2^28 cells"; return VISFS_BA_ERR_UNSUPPORTED; }
-        if (!gr->pose_fixed[gr->laser_pose]) { Nz = gr->n_laser; grid_cells = (size_t)G.num_x_cells * G.num_y_cells; }
+        if (!(Gr.resolution > 0.0) || Gr.num_x_cells <= 0 || Gr.num_y_cells <= 0 || !Gr.correspondence_cost) return bad(h, "invalid grid");
+        if ((int64_t)Gr.num_x_cells * Gr.num_y_cells > (int64_t)1 << 28) { h->err = "grid larger than 2^28 cells"; return VISFS_BA_ERR_UNSUPPORTED; }
+        if (!gr->pose_fixed[gr->laser_pose]) { Nz = gr->n_laser; grid_cells = (size_t)Gr.num_x_cells * Gr.num_y_cells; }
     }
-    int rc = ws_init(h, w);
-    if (rc != VISFS_BA_OK) return rc;
-    if (w.graph_exec) { (void)hipGraphExecDestroy(w.graph_exec); w.graph_exec = nullptr; w.graph_units[0] = w.graph_units[1] = -1; }   // kernel arguments change
-    w.solves_since_upload = 0;
-    HIP_TRY(h, hipSetDevice(h->device));
+    G.Np = Np; G.Nl = Nl; G.No = No; G.Ne = Ne; G.Nz = Nz;
+    G.odo_from = gr->odo_from; G.odo_to = gr->odo_to; G.laser_pose = gr->laser_pose;
+    return VISFS_BA_OK;
+}
 
-    // ---- the primary section: staged (or already there), then on its way to the device while the structure of S is worked out
-    PrimSizes pz;
-    if (opt.in_staging) pz = opt.cap;
-    else {
-        pz.Np = Np; pz.Nl = Nl; pz.cap_obs = No; pz.cap_odo = Ne; pz.Nz = Nz; pz.grid_cells = grid_cells;
-        HIP_TRY(h, hipStreamSynchronize(w.stream));        // the previous upload's H2D copy reads the pinned staging arenas filled below
-    }
-    const size_t pbytes = prim_bytes(pz);
-    rc = ensure_prim(h, w, pbytes);
+// ---- the primary section: staged (or already there), then on its way to the device while the structure of S is worked out.
+// hg: pointers into the pinned staging arena; P receives the free-pose mapping.
+int stage_primary(visfs_ba_handle* h, Workspace& w, const visfs_ba_graph* gr, const UploadOpts& opt, const PlanGraph& G, const PrimSizes& pz,
+                  const size_t pbytes, DeviceGraph& hg, UploadPlan& P) {
+    const int Np = G.Np, Nl = G.Nl, No = G.No, Ne = G.Ne, Nz = G.Nz;
+    const size_t grid_cells = pz.grid_cells;
+    if (!opt.in_staging) HIP_TRY(h, hipStreamSynchronize(w.stream));        // the previous upload's H2D copy reads the pinned staging arenas filled below
+    const int rc = ensure_prim(h, w, pbytes);
     if (rc != VISFS_BA_OK) return rc;
-    DeviceGraph hg{};                 // pointers into the pinned staging arenas
     { Arena hp{ w.h_prim, w.h_prim_cap, 0 }; layout_prim(hp, hg, pz); }
     if (!opt.in_staging) {
         double* p0 = const_cast<double*>(hg.pose0);
@@ -499,423 +480,20 @@ int ws_upload(visfs_ba_handle* h, Workspace& w, const visfs_ba_graph* gr, const 
         std::memcpy(const_cast<double*>(hg.laser_xyz), gr->laser_xyz, (size_t)Nz * 24);
         if (!opt.d_grid) std::memcpy(const_cast<float*>(hg.grid.cost), gr->grid->correspondence_cost, grid_cells * 4);
     }
-    // buildIndexMapping: free poses in index (= id) order
-    std::vector<int32_t> pose_free(Np), free_pose;
-    for (int i = 0; i < Np; ++i) { if (gr->pose_fixed[i]) pose_free[i] = -1; else { pose_free[i] = (int32_t)free_pose.size(); free_pose.push_back(i); } }
-    const int Npf = (int)free_pose.size();
-    std::memcpy(const_cast<int32_t*>(hg.pose_free), pose_free.data(), (size_t)Np * 4);
-    if (Npf) std::memcpy(const_cast<int32_t*>(hg.free_pose), free_pose.data(), (size_t)Npf * 4);
+    plan_poses(P, gr->pose_fixed, Np);
+    std::memcpy(const_cast<int32_t*>(hg.pose_free), P.pose_free.data(), (size_t)Np * 4);
+    if (P.Npf) std::memcpy(const_cast<int32_t*>(hg.free_pose), P.free_pose.data(), (size_t)P.Npf * 4);
     if (Nz && opt.d_grid) {
         // the grid is the last array of the section: everything before it from the staging arena, the grid from device memory
         const size_t at = (size_t)(reinterpret_cast<const char*>(hg.grid.cost) - w.h_prim);
         HIP_TRY(h, hipMemcpyAsync(w.d_prim, w.h_prim, at, hipMemcpyHostToDevice, w.stream));
         HIP_TRY(h, hipMemcpyAsync(w.d_prim + at, opt.d_grid, grid_cells * 4, hipMemcpyDeviceToDevice, w.stream));
     } else HIP_TRY(h, hipMemcpyAsync(w.d_prim, w.h_prim, pbytes, hipMemcpyHostToDevice, w.stream));
-    lap("primary");
+    return VISFS_BA_OK;
+}
 
-    // ---- what the host needs of the O(N_obs) part: observations per free pose, co-observation pairs per block
-    GraphSummary sum;
-    if (opt.summary_slots > 0) merge_summary(w.sum_part, opt.summary_slots, Npf, sum, w.sum_run);
-    else summarize_graph(gr, pose_free.data(), Npf, opt.pool, !opt.trusted, sum, w.sum_part, w.sum_run);
-    if (sum.bad) return bad(h, sum.bad);
-    const std::vector<int32_t>& cnt = sum.cnt;
-    std::vector<int32_t>& pcount = sum.pcount;
-    const int64_t pairs_seen = sum.pairs_seen;
-    const int n_edges_ok = sum.n_edges_ok;
-    const int n_pose_obs = cnt[Npf];
-    lap("summary");
-
-    // pose-major chunks
-    std::vector<int32_t> chunk_pose, chunk_ptr, pose_chunk_ptr(Npf + 1, 0);
-    chunk_pose.reserve((size_t)cnt[Npf] / LIN_CHUNK + Npf + 1); chunk_ptr.reserve((size_t)cnt[Npf] / LIN_CHUNK + Npf + 2);
-    for (int a = 0; a < Npf; ++a) {
-        pose_chunk_ptr[a] = (int32_t)chunk_pose.size();
-        for (int s = cnt[a]; s < cnt[a + 1]; s += LIN_CHUNK) { chunk_pose.push_back(a); chunk_ptr.push_back(s); }
-    }
-    pose_chunk_ptr[Npf] = (int32_t)chunk_pose.size();
-    const int n_chunks = (int)chunk_pose.size();
-    chunk_ptr.push_back(cnt[Npf]);
-    // k_linearize reads [chunk_ptr[c], chunk_ptr[c+1]) — consecutive chunks are contiguous: chunk c of pose a ends where the next starts
-    for (int c = 0; c + 1 < n_chunks; ++c) if (chunk_ptr[c + 1] != std::min(chunk_ptr[c] + LIN_CHUNK, cnt[chunk_pose[c] + 1])) return bad(h, "internal: chunk layout");
-
-    // odometry incidence (per free pose: its edges in edge order, 2e = as `from`, 2e + 1 = as `to`; counting pass, then fill — no
-    // per-pose containers: this section runs on the caller's thread between the graph build and the first launch)
-    std::vector<int32_t> pose_odo_ptr(Npf + 1, 0), pose_odo;
-    {
-        for (int e = 0; e < Ne; ++e) {
-            const int a = pose_free[gr->odo_from[e]], b = pose_free[gr->odo_to[e]];
-            if (a >= 0) pose_odo_ptr[a + 1]++;
-            if (b >= 0) pose_odo_ptr[b + 1]++;
-        }
-        // the laser edges' aggregate lives in slot Ne of odo_blk as the "from" side of a pseudo edge (added last, as g2o does)
-        if (Nz > 0) pose_odo_ptr[pose_free[gr->laser_pose] + 1]++;
-        for (int a = 0; a < Npf; ++a) pose_odo_ptr[a + 1] += pose_odo_ptr[a];
-        pose_odo.resize(pose_odo_ptr[Npf]);
-        std::vector<int32_t> at(pose_odo_ptr.begin(), pose_odo_ptr.end() - 1);
-        for (int e = 0; e < Ne; ++e) {
-            const int a = pose_free[gr->odo_from[e]], b = pose_free[gr->odo_to[e]];
-            if (a >= 0) pose_odo[at[a]++] = 2 * e;
-            if (b >= 0) pose_odo[at[b]++] = 2 * e + 1;
-        }
-        if (Nz > 0) pose_odo[at[pose_free[gr->laser_pose]]++] = 2 * Ne;
-    }
-
-    // S block structure (g2o buildStructure analogue): per block (i<=j) the co-observation pairs
-    std::vector<uint8_t> has_odo((size_t)Npf * Npf, 0);
-    if (pairs_seen > 0x7fffffff) { h->err = "window too large (pair list)"; return VISFS_BA_ERR_UNSUPPORTED; }
-    for (int e = 0; e < Ne; ++e) {
-        int a = pose_free[gr->odo_from[e]], b = pose_free[gr->odo_to[e]];
-        if (a < 0 || b < 0) continue;
-        if (a > b) std::swap(a, b);
-        has_odo[(size_t)a * Npf + b] = 1;
-    }
-    std::vector<int32_t> blk_i, blk_j, blk_ptr(1, 0), blk_of((size_t)Npf * Npf, -1);
-    blk_i.reserve((size_t)Npf * 16); blk_j.reserve((size_t)Npf * 16); blk_ptr.reserve((size_t)Npf * 16 + 1);
-    int64_t npairs = 0;
-    for (int a = 0; a < Npf; ++a)
-        for (int b = a; b < Npf; ++b) {
-            const size_t key = (size_t)a * Npf + b;
-            if (a == b || pcount[key] > 0 || has_odo[key]) {
-                blk_of[key] = (int32_t)blk_i.size();
-                blk_i.push_back(a); blk_j.push_back(b);
-                npairs += pcount[key];
-                if (npairs > 0x7fffffff) { h->err = "window too large (pair list)"; return VISFS_BA_ERR_UNSUPPORTED; }
-                blk_ptr.push_back((int32_t)npairs);
-            }
-        }
-    const int n_blk = (int)blk_i.size();
-    std::vector<int32_t> blk_odo_ptr(n_blk + 1, 0), blk_odo;
-    if (Ne > 0) {
-        // Aij is (row = from, col = to): stored block is (min,max); transposed when from > to
-        auto slot = [&](int e, int& code) {
-            const int a = pose_free[gr->odo_from[e]], b = pose_free[gr->odo_to[e]];
-            if (a < 0 || b < 0) return -1;
-            if (a < b) { code = 2 * e; return (int)blk_of[(size_t)a * Npf + b]; }
-            code = 2 * e + 1; return (int)blk_of[(size_t)b * Npf + a];
-        };
-        int code = 0;
-        for (int e = 0; e < Ne; ++e) { const int b = slot(e, code); if (b >= 0) blk_odo_ptr[b + 1]++; }
-        for (int b = 0; b < n_blk; ++b) blk_odo_ptr[b + 1] += blk_odo_ptr[b];
-        blk_odo.resize(blk_odo_ptr[n_blk]);
-        std::vector<int32_t> at(blk_odo_ptr.begin(), blk_odo_ptr.end() - 1);
-        for (int e = 0; e < Ne; ++e) { const int b = slot(e, code); if (b >= 0) blk_odo[at[b]++] = code; }
-    }
-    // block-row adjacency of the symmetric S for the mat-vec: row r = its transposed blocks (i < r, code 2b + 1) in ascending i, then its
-    // own blocks (j >= r, code 2b) in ascending j — the blocks are enumerated in (i, j) order, so both halves arrive sorted by column
-    std::vector<int32_t> row_ptr(Npf + 1, 0), row_col, row_blk;
-    {
-        for (int b = 0; b < n_blk; ++b) { row_ptr[blk_i[b] + 1]++; if (blk_i[b] != blk_j[b]) row_ptr[blk_j[b] + 1]++; }
-        for (int a = 0; a < Npf; ++a) row_ptr[a + 1] += row_ptr[a];
-        row_col.resize(row_ptr[Npf]); row_blk.resize(row_ptr[Npf]);
-        std::vector<int32_t> at(row_ptr.begin(), row_ptr.end() - 1);
-        for (int b = 0; b < n_blk; ++b) if (blk_i[b] != blk_j[b]) { const int r = blk_j[b]; row_col[at[r]] = blk_i[b]; row_blk[at[r]] = 2 * b + 1; at[r]++; }
-        for (int b = 0; b < n_blk; ++b) { const int r = blk_i[b]; row_col[at[r]] = blk_j[b]; row_blk[at[r]] = 2 * b; at[r]++; }
-    }
-
-    // ---- Schur complement by RUNS OF LANDMARKS (k_schur_runs, ba_kernels.hip): the plan.  A workgroup owns run_lr x run_m consecutive
-    // landmarks; run_lr is the largest of 64 / 32 / 16 / 8 whose sub-batches never hold more than RUN_MAX_TILES observations (their tiles are
-    // staged in LDS); a run's blocks are those of its pose span [lo, lo + W) — from the structure summary, which has seen every observation's
-    // landmark and pose.  Windows it does not fit (a span above RUN_MAX_W poses: landmarks whose ids do not grow with time; reduced systems
-    // that k_small_solve serves; VISFS_BA_SCHUR_RUNS=0) keep the pair-list gather.  A property of the window alone.
-    struct RunPlan { int LR = 0, M = 1, n = 0, cap = 0, wmax = 0; size_t lds = 0; int64_t total = 0; std::vector<int4> desc; std::vector<int32_t> first, last, k0; } rp;
-    {
-        // Measured (profiles/r04_schur_lds_tiles.log): a third of the gather's VALU instructions per pair, but every workgroup is a chain
-        // of barrier-separated phases (descriptors, global loads, D_l / R_i, tiles, accumulate, three reduction passes: 12 us stamped at C2)
-        // at two to three waves per SIMD — 15.7 us per launch against the gather's 8.7 at C2, 34 against 29.5 at the 200-key-frame window,
-        // 16 resident windows 78.6 k against 79.0 k it/s at best.  The gather stays the default; VISFS_BA_SCHUR_RUNS=1 selects this kernel
-        // (tests, A/B runs).
-        const char* e = std::getenv("VISFS_BA_SCHUR_RUNS");
-        const bool want = e && e[0] == '1';
-        const int ng = (Nl + RUN_GROUP - 1) / RUN_GROUP;
-        if (want && Npf >= 1 && No > 0 && Nl > 0 && (size_t)6 * Npf > (size_t)SM_MAX_N6 && (int)sum.grp.size() >= ng && Np < 65536) {
-            // (first choice: sub-batches of at most 176 tiles — 30 KB of LDS, three workgroups and more per CU; else whatever fits at all)
-            for (int limit : { 176, RUN_MAX_TILES }) {
-                for (int LR : { 64, 32, 16, 8 }) {
-                    const int gper = LR / RUN_GROUP;
-                    int maxc = 0;
-                    for (int g0 = 0; g0 < ng; g0 += gper) { int c = 0; for (int q = g0; q < std::min(ng, g0 + gper); ++q) c += sum.grp[q].cnt; maxc = std::max(maxc, c); }
-                    if (maxc <= limit) { rp.LR = LR; rp.cap = maxc; break; }
-                }
-                if (rp.LR) break;
-            }
-            { const char* el = std::getenv("VISFS_BA_RUN_LR"); const int q = el ? std::atoi(el) : 0;                    // tuning override (never above what fits)
-              if (rp.LR && (q == 8 || q == 16 || q == 32 || q == 64) && q < rp.LR) { rp.LR = q; rp.cap = 0; const int gper = q / RUN_GROUP;
-                  for (int g0 = 0; g0 < ng; g0 += gper) { int c = 0; for (int qq = g0; qq < std::min(ng, g0 + gper); ++qq) c += sum.grp[qq].cnt; rp.cap = std::max(rp.cap, c); } } }
-            if (rp.LR) {
-                // sub-batches per workgroup: one, until the window has so many landmarks that a partial per run and block costs more traffic
-                // than the workgroups it keeps busy (a 200-key-frame window: ~940 runs of 32 landmarks at M = 1)
-                rp.M = std::max(1, 32 / rp.LR);                 // at least 32 landmarks per workgroup: a partial per run and block is traffic
-                while ((Nl + rp.LR * rp.M - 1) / (rp.LR * rp.M) > 1024 && rp.M < 16) rp.M *= 2;
-                { const char* em = std::getenv("VISFS_BA_RUN_M"); const int q = em ? std::atoi(em) : 0; if (q >= 1 && q <= 16) rp.M = q; }
-                const int per = rp.LR * rp.M, gper = per / RUN_GROUP;
-                rp.n = (Nl + per - 1) / per;
-                rp.desc.assign(rp.n, make_int4(0, 0, 0, 0));
-                bool ok = rp.n < (1 << 20);
-                int nbmax = 0;
-                for (int r = 0; r < rp.n && ok; ++r) {
-                    int lo = 0x7fffffff, hi = -1;
-                    for (int q = r * gper; q < std::min(ng, (r + 1) * gper); ++q) if (sum.grp[q].cnt > 0) { lo = std::min(lo, sum.grp[q].lo); hi = std::max(hi, sum.grp[q].hi); }
-                    const int W = hi >= lo ? hi - lo + 1 : 0;
-                    if (W > RUN_MAX_W) { ok = false; break; }
-                    rp.desc[r] = make_int4(W ? lo : 0, W, (int)rp.total, 0);
-                    rp.total += (int64_t)W * (W + 1) / 2;
-                    rp.wmax = std::max(rp.wmax, W); nbmax = std::max(nbmax, W * (W + 1) / 2);
-                    if (rp.total > 0x3fffffff) ok = false;
-                }
-                if (ok) {
-                    // per stored block of S: the range of runs whose span holds both of its poses (k_schur_finalize walks it)
-                    rp.first.assign(n_blk, 0x7fffffff); rp.last.assign(n_blk, -1);
-                    for (int r = 0; r < rp.n; ++r) {
-                        const int lo = rp.desc[r].x, W = rp.desc[r].y;
-                        for (int li = 0; li < W; ++li) {
-                            const int a = pose_free[lo + li];
-                            if (a < 0) continue;
-                            for (int lj = li; lj < W; ++lj) {
-                                const int b2 = pose_free[lo + lj];
-                                if (b2 < 0) continue;
-                                const int bk = blk_of[(size_t)a * Npf + b2];
-                                if (bk >= 0) { rp.first[bk] = std::min(rp.first[bk], r); rp.last[bk] = std::max(rp.last[bk], r); }
-                            }
-                        }
-                    }
-                    for (int b = 0; b < n_blk && ok; ++b) if (rp.last[b] >= 0 && rp.last[b] - rp.first[b] + 1 > 4095) ok = false;
-                }
-                if (!ok) { rp = RunPlan(); }
-                else {
-                    rp.lds = (((size_t)std::max(rp.cap, (256 * 14 + RUN_TILE - 1) / RUN_TILE) * RUN_TILE + 9 * (size_t)rp.LR + 9 * (size_t)rp.wmax) * 8 + (((size_t)rp.LR * rp.wmax + 3) & ~size_t(3)) * 2 + (size_t)nbmax * 2 + 15) & ~size_t(15);
-                    // first observation of every sub-batch of run_lr landmarks (observations are landmark-major: a prefix sum of the groups' counts)
-                    const int nsub = rp.n * rp.M, gl = rp.LR / RUN_GROUP;
-                    rp.k0.assign((size_t)nsub + 1, 0);
-                    int acc = 0;
-                    for (int sb = 0; sb < nsub; ++sb) { rp.k0[sb] = acc; for (int q = sb * gl; q < std::min(ng, (sb + 1) * gl); ++q) acc += sum.grp[q].cnt; }
-                    rp.k0[nsub] = acc;
-                    if (acc != No) rp = RunPlan();                 // (cannot happen: every observation was counted once)
-                }
-            }
-        }
-    }
-    const bool run_path = rp.n > 0;
-    // Schur chunks: <= SCH_CHUNK co-observation pairs of one block per wavefront
-    // A lane may take several pairs of its chunk (64 per pass) and add them serially before the wave's reduce-scatter.  Measured
-    // (profiles/r01_v8_schur_passes.log): two passes win 4-5 % on a lone mid-size window (C2: half the waves, half the partials
-    // for k_schur_finalize to sum, all of them still resident in one round) and lose 4-7 % once the launch fills the machine
-    // (C4, batched windows: the serial variant needs 216 VGPRs, 2 waves per SIMD instead of 4).  Results differ from the
-    // one-pass chunking in the last bits only (summation order).
-    int64_t chunks64 = 0;
-    for (int b = 0; b < n_blk; ++b) chunks64 += (blk_ptr[b + 1] - blk_ptr[b] + SCH_CHUNK - 1) / SCH_CHUNK;
-    int sch_passes = (!w.batch_member && chunks64 >= 1024 && chunks64 <= 6144) ? 2 : 1;
-    { const char* e = std::getenv("VISFS_BA_SCH_PASSES"); if (e) { const int q = std::atoi(e); if (q >= 1 && q <= 8) sch_passes = q; } }
-    const int sch_chunk = SCH_CHUNK * sch_passes;
-    std::vector<int32_t> blk_chunk_ptr(n_blk + 1, 0), sch_blk, sch_ptr;
-    if (!run_path) { sch_blk.reserve((size_t)(npairs / sch_chunk) + n_blk + 1); sch_ptr.reserve((size_t)(npairs / sch_chunk) + n_blk + 1); }
-    for (int b = 0; b < n_blk; ++b) {
-        blk_chunk_ptr[b] = (int32_t)sch_blk.size();
-        if (run_path) continue;                             // (no pair lists, no chunks: the runs replace them)
-        for (int e = blk_ptr[b]; e < blk_ptr[b + 1]; e += sch_chunk) { sch_blk.push_back(b); sch_ptr.push_back(e); }
-    }
-    blk_chunk_ptr[n_blk] = (int32_t)sch_blk.size();
-    const int n_sch = (int)sch_blk.size();
-    std::vector<int4> sch_desc(std::max(n_sch, 1)), blk_desc(2 * (size_t)std::max(n_blk, 1));
-    for (int c = 0; c < n_sch; ++c) {
-        const int b = sch_blk[c];
-        sch_desc[c] = make_int4(sch_ptr[c], std::min(sch_ptr[c] + sch_chunk, blk_ptr[b + 1]), free_pose[blk_i[b]], free_pose[blk_j[b]]);
-    }
-    for (int b = 0; b < n_blk; ++b) {
-        const int a = blk_i[b];
-        const bool dg = (a == blk_j[b]);
-        blk_desc[2 * b] = make_int4(blk_chunk_ptr[b], blk_chunk_ptr[b + 1], dg ? pose_odo_ptr[a] : blk_odo_ptr[b], dg ? pose_odo_ptr[a + 1] : blk_odo_ptr[b + 1]);
-        if (run_path) {
-            const int cnt_r = rp.last[b] >= 0 ? rp.last[b] - rp.first[b] + 1 : 0;
-            blk_desc[2 * b].x = (int)((unsigned)(cnt_r ? rp.first[b] : 0) | ((unsigned)cnt_r << 20));
-            blk_desc[2 * b].y = (int)((unsigned)free_pose[a] | ((unsigned)free_pose[blk_j[b]] << 16));
-        }
-        blk_desc[2 * b + 1] = make_int4(a, blk_j[b], pose_chunk_ptr[a], pose_chunk_ptr[a + 1]);
-    }
-    if (prm.solver == 2 && Npf > MAX_PCG_FREE_POSES) { h->err = "Optimizer/Solver=2 (PCG) supports at most 1024 free poses; use the direct solver"; return VISFS_BA_ERR_UNSUPPORTED; }
-    int max_row = 0;
-    for (int a = 0; a < Npf; ++a) max_row = std::max(max_row, row_ptr[a + 1] - row_ptr[a]);
-    // persistent PCG: LDS plan.  d, q, scalars, the rows' column/code tables always; s = Minv r when an owner thread holds several
-    // blocks; the own block rows of S when they fit.  Co-residency of the hand-off needs every workgroup resident: one block row
-    // per workgroup up to 256 free poses, ceil(Npf / 256) rows per workgroup beyond (at most 256 workgroups, one per CU).
-    const int pcg_rpw = Npf > MAX_PCG_ONE_ROW_POSES ? (Npf + MAX_PCG_ONE_ROW_POSES - 1) / MAX_PCG_ONE_ROW_POSES : 1;
-    size_t pcg_lds = (size_t)(2 * 6 * Npf + 32 + 32 * pcg_rpw + (Npf > MAX_PCG_ONE_ROW_POSES ? 6 * Npf : 0)) * 8 + (size_t)8 * max_row * pcg_rpw + 16;
-    int lds_minv = 0, lds_srow = 0;                      // Minv: registers (one block per owner) or, beyond 256 free poses, read from HBM
-    {
-        const size_t budget = (size_t)150 * 1024;        // one workgroup per CU may own most of its 160 KiB
-        if (pcg_lds + (size_t)288 * max_row * pcg_rpw <= budget) { lds_srow = 1; pcg_lds += (size_t)288 * max_row * pcg_rpw; }
-    }
-    if (prm.solver == 2 && pcg_lds > (size_t)160 * 1024) { h->err = "reduced camera system too large for the persistent PCG (LDS); use the direct solver"; return VISFS_BA_ERR_UNSUPPORTED; }
-
-    // k_pcg1 (one wavefront per block row, <= 64 free poses): the block of S at (i, a) as a dense code table
-    const bool pcg1 = [&]() { const char* e = std::getenv("VISFS_BA_PCG1"); return prm.solver == 2 && Npf >= 1 && Npf <= 64 && !(e && e[0] == '0'); }();
-    std::vector<int32_t> pcg1_code;
-    if (pcg1) {
-        pcg1_code.assign((size_t)Npf * Npf, -1);
-        for (int a = 0; a < Npf; ++a)
-            for (int n = row_ptr[a]; n < row_ptr[a + 1]; ++n) pcg1_code[(size_t)a * Npf + row_col[n]] = row_blk[n];
-    }
-    // k_pcg_cu: the whole PCG in one workgroup when every block row is short enough to sit in registers (3 threads per scalar row)
-    // One window: slower than k_pcg1 (34.7 vs 21.6 us per solve at C2, profiles/r02_pcg_cu_vs_handoff.log).  Many windows sharing every
-    // launch: nothing spins and no hand-off is paid — 16 C2 windows 68.0 -> 70.6 k it/s, 32 windows 66.6 -> 74.3 k, but 8 windows
-    // 58.8 -> 55.6 k (profiles/r02_v3_pcg_cu_batches.log).  Its mat-vec sums associate differently from k_pcg1's, so a window's result
-    // would depend on how many OTHER windows were submitted with it if the kernel followed the batch size: it follows the HANDLE
-    // (visfs_ba_set_tuning(THROUGHPUT), ABI 8; VISFS_BA_PCG_CU=0|1 overrides), never the batch — every window is bit-identical to
-    // its solve as a batch of one through the same handle however a batch is cut or sharded.
-    const bool pcg_cu = [&]() { const char* e = std::getenv("VISFS_BA_PCG_CU"); int mr = 0; for (int a = 0; a < Npf; ++a) mr = std::max(mr, row_ptr[a + 1] - row_ptr[a]);
-                                const bool want = e ? e[0] == '1' : h->tuning == VISFS_BA_TUNE_THROUGHPUT;      // (the environment overrides every handle)
-                                return prm.solver == 2 && pcg_cu_fits(Npf, mr) && 6 * Npf > 64 && want; }();
-    // ... and where each stored block sits in the row lists: k_schur_finalize writes S a second time by scalar row for that kernel
-    const int cu_T = (int)((6 * (size_t)Npf + 63) / 64 * 64);
-    int cu_max_row = 0;
-    std::vector<int32_t> blk_slot(std::max(n_blk, 1), 255 | (255 << 8));
-    for (int a = 0; a < Npf; ++a) {
-        cu_max_row = std::max(cu_max_row, row_ptr[a + 1] - row_ptr[a]);
-        if (pcg_cu)
-            for (int n = row_ptr[a]; n < row_ptr[a + 1]; ++n) {
-                const int b = row_blk[n] >> 1, k = n - row_ptr[a];
-                if (row_blk[n] & 1) blk_slot[b] = (blk_slot[b] & 0xff) | (k << 8); else blk_slot[b] = (blk_slot[b] & ~0xff) | k;
-            }
-    }
-    // direct solver (Optimizer/Solver 0, 1, 3 and every solve of the Ceres branch): S of a sliding window is block-banded — the banded
-    // factorisation in one workgroup (k_band_chol) when the band is narrow enough, the dense blocked Cholesky otherwise (VISFS_BA_BAND=0 forces it)
-    int band_B = -1, band_rows = 0, band_lds = 0;
-    std::vector<int32_t> band_code;
-    // (Optimizer/Solver=2 windows get the plan too: it is what a solve falls back to when the persistent PCG's hand-off times out — a GPU
-    // kept busy by another process —, so that the call still returns a solution as the reference's solver always does, Optimizer.cpp:76-91)
-    if (Npf >= 1) {
-        int Bw = 0;
-        for (int b = 0; b < n_blk; ++b) Bw = std::max(Bw, blk_j[b] - blk_i[b]);
-        const char* e = std::getenv("VISFS_BA_BAND");
-        if (!(e && e[0] == '0') && band_plan(Npf, Bw, &band_rows, &band_lds)) {
-            { const char* er = std::getenv("VISFS_BA_BAND_ROWS"); const int q = er ? std::atoi(er) : 0;          // tests: force the streaming form
-              if (q >= Bw + 3 && q < band_rows) { band_rows = q; band_lds = (int)band_lds_bytes(Npf, Bw, q); } }
-            band_B = Bw;
-            band_code.assign((size_t)Npf * (Bw + 1), -1);
-            for (int b = 0; b < n_blk; ++b) band_code[(size_t)blk_j[b] * (Bw + 1) + (blk_j[b] - blk_i[b])] = b;
-        }
-    }
-    lap("structure");
-    // lanes per landmark: smallest power of two >= mean track length, in [4, 64] — but at most 8 once the window has a thousand landmarks:
-    // the landmark-major kernels of a 200-key-frame window or of a batch of 50-key-frame windows need more than one round of resident
-    // waves at 16 lanes per landmark (k_backsub: 121 VGPRs, four waves per SIMD), and a lane that loops twice over a track of ten costs
-    // less than the second round (measured: C4 5 631 -> 6 007 it/s, C4R 5 040 -> 5 330, 16 resident C2 windows 73.0 k -> 80.9 k,
-    // 8 windows 63.1 k -> 66.2 k; one C2 window flat: 20.3 k / 20.2 k).  A property of the WINDOW alone: a window's result never
-    // depends on what it is batched with.
-    int group = 4;
-    const double mean_track = Nl > 0 ? (double)No / Nl : 1.0;
-    while (group < 64 && group < mean_track) group *= 2;
-    if (Nl >= 1024 && group > 8) group = 8;
-    { const char* e = std::getenv("VISFS_BA_GROUP"); if (e) { const int gq = std::atoi(e); if (gq == 4 || gq == 8 || gq == 16 || gq == 32 || gq == 64) group = gq; } }   // tuning override
-    const int n_lin_a = std::max(1, (Nl + (256 / group) - 1) / (256 / group));
-    const int n_eval = (No + 255) / 256 + 1;
-    const int n_parts = std::max(n_lin_a + 1, n_eval);
-    const size_t n6 = (size_t)6 * Npf;
-    const size_t chol_np = std::max<size_t>(32, (n6 + 31) / 32 * 32);
-    const bool small_solve_fits_npf = Npf >= 1 && n6 <= (size_t)SM_MAX_N6;
-    const size_t n_hist = (size_t)std::max(index_blocks(No), 1) * std::max(Npf, 1);
-
-    // ---- the INDEX section (block-level structure of S, small) and the mutable section: one device arena, the index part staged in
-    // pinned memory with the same layout; everything of size N_obs that is derived (lm_ptr, obs_ok, pose_obs, obs_ppos, the pair
-    // lists) is built on the device from the primary section
-    auto layout = [&](Arena& A, DeviceGraph& g) {
-        g.chunk_pose = A.take<int32_t>(std::max(n_chunks, 1));
-        g.chunk_ptr = A.take<int32_t>(n_chunks + 1);
-        g.pose_chunk_ptr = A.take<int32_t>(Npf + 1);
-        g.pose_odo_ptr = A.take<int32_t>(Npf + 1);
-        g.pose_odo = A.take<int32_t>(std::max<size_t>(pose_odo.size(), 1));
-        g.blk_i = A.take<int32_t>(std::max(n_blk, 1));
-        g.blk_j = A.take<int32_t>(std::max(n_blk, 1));
-        g.blk_ptr = A.take<int32_t>(n_blk + 1);
-        g.blk_chunk_ptr = A.take<int32_t>(n_blk + 1);
-        g.sch_desc = A.take<int4>(std::max(n_sch, 1));
-        g.blk_desc = A.take<int4>(2 * (size_t)std::max(n_blk, 1));
-        g.blk_odo_ptr = A.take<int32_t>(n_blk + 1);
-        g.blk_odo = A.take<int32_t>(std::max<size_t>(blk_odo.size(), 1));
-        g.row_ptr = A.take<int32_t>(Npf + 1);
-        g.row_col = A.take<int32_t>(std::max<size_t>(row_col.size(), 1));
-        g.row_blk = A.take<int32_t>(std::max<size_t>(row_blk.size(), 1));
-        g.blk_slot = A.take<int32_t>(std::max(n_blk, 1));
-        g.fin_exp = A.take<int32_t>(std::max(n_blk, 1));
-        g.sch_blk = A.take<int32_t>(std::max(n_sch, 1));
-        g.diag_blk = A.take<int32_t>(std::max(Npf, 1));
-        g.pcg1_code = pcg1 ? A.take<int32_t>((size_t)Npf * Npf) : nullptr;
-        g.band_code = band_B >= 0 ? A.take<int32_t>(band_code.size()) : nullptr;
-        g.run_desc = run_path ? A.take<int4>(rp.desc.size()) : nullptr;
-        g.run_k0 = run_path ? A.take<int32_t>(rp.k0.size()) : nullptr;
-    };
-    Arena sizing{ nullptr, 0, 0 };
-    layout(sizing, hg);
-    const size_t static_bytes = (sizing.used + 255) & ~size_t(255);
-
-    Arena dyn{ nullptr, 0, static_bytes };
-    DeviceGraph dg{};
-    int32_t* d_hist = nullptr;
-    size_t zero_end = 0;
-    auto layout_dyn = [&](Arena& A, DeviceGraph& g) {
-        // device-built index arrays
-        g.lm_ptr = A.take<int32_t>(Nl + 1);
-        g.obs_ok = A.take<uint8_t>(std::max(No, 1));
-        g.obs_ppos = A.take<int32_t>(std::max(No, 1));
-        g.pose_obs = A.take<int32_t>(std::max(n_pose_obs, 1));
-        if (pz.raw_refs) g.obs_uvr = A.take<double>((size_t)std::max(No, 1) * 3);      // written by k_index_count from obs_uvd
-        d_hist = A.take<int32_t>(n_hist);
-        for (int k = 0; k < 2; ++k) {                       // the two linearisation sets: same layout, constant distance
-            LinBuf& L = g.lin[k];
-            L.obs_w = A.take<double>(std::max(No, 1));
-            L.obs_pcw = A.take<double>((size_t)std::max(No, 1) * 4);
-            L.pose_pcw = A.take<double>((size_t)std::max(n_pose_obs, 1) * 4);
-            L.Hll = A.take<double>((size_t)std::max(Nl, 1) * 6);
-            L.bl = A.take<double>((size_t)std::max(Nl, 1) * 3);
-            L.hpp_part = A.take<double>((size_t)std::max(n_chunks, 1) * 27);
-            L.odo_blk = A.take<double>((size_t)(Ne + 1) * 120);
-        }
-        g.lin_stride = reinterpret_cast<char*>(g.lin[1].obs_w) - reinterpret_cast<char*>(g.lin[0].obs_w);
-        g.pose[0] = A.take<double>((size_t)Np * POSE_STRIDE); g.pose[1] = A.take<double>((size_t)Np * POSE_STRIDE);
-        g.pt[0] = A.take<double>((size_t)std::max(Nl, 1) * 3); g.pt[1] = A.take<double>((size_t)std::max(Nl, 1) * 3);
-        g.obs_outlier = A.take<uint8_t>(std::max(No, 1));   // (right behind the estimates: pose[0] .. obs_outlier are one span in the order and alignment of
-                                                             // output_stage_of, so a solve's outputs come back in ONE device-to-host copy)
-        g.obs_level = A.take<uint8_t>(std::max(No, 1));
-        g.obs_chi2_out = A.take<double>(std::max(No, 1));
-        g.obs_chi2 = A.take<double>(std::max(No, 1));
-        g.Hpp = A.take<double>((size_t)std::max(Npf, 1) * 36);
-        g.bp = A.take<double>(std::max<size_t>(n6, 1));
-        g.lin_part = A.take<double>((size_t)n_parts * 2);
-        g.S = A.take<double>((size_t)std::max(n_blk, 1) * 36);
-        g.S_rows = A.take<double>(pcg_cu ? (size_t)cu_max_row * 6 * cu_T : 1);      // (inside the span the upload clears: slots a row does not use read as zero)
-        g.bs = A.take<double>(std::max<size_t>(n6, 1));
-        g.Minv = A.take<double>((size_t)std::max(Npf, 1) * 36);
-        g.x = A.take<double>(std::max<size_t>(n6, 1));
-        g.sch_part = A.take<double>((size_t)std::max<int64_t>(std::max<int64_t>(n_sch, rp.total), 1) * 42);
-        g.granules = A.take<unsigned long long>(std::max<size_t>(4 * n6 + Npf, 1));        // + one placement word per block row (k_pcg1)
-        g.dxl = A.take<double>((size_t)std::max(Nl, 1) * 3);
-        g.trial_part = A.take<double>((size_t)n_parts * 2);
-        g.trial_gran = A.take<unsigned long long>((size_t)n_parts * 4);
-        g.fin_flag = A.take<uint32_t>((size_t)std::max(n_blk, 1));
-        g.fin_cnt = A.take<uint32_t>((size_t)std::max(n_blk, 1));
-        g.aux_part = A.take<double>((size_t)n_parts);
-        g.dl_part = A.take<double>(ceres && prm.trust_region == 1 ? (size_t)n_parts * 4 : 1);
-        g.s2l = A.take<double>((size_t)std::max(Nl, 1) * 3);
-        g.s2p = A.take<double>(std::max<size_t>(n6, 1));
-        const bool dense_chol = band_B < 0 && (prm.solver != 2 || (!small_solve_fits_npf && chol_np <= 2048));   // (PCG windows: the fallback's scratch, up to 67 MB)
-        g.dense = A.take<double>(dense_chol ? chol_np * chol_np : 1);
-        g.chol_f = A.take<double>(dense_chol ? chol_np * chol_np : 1);
-        g.band_L = A.take<double>(band_B >= 0 && band_rows < Npf ? (size_t)Npf * (band_B + 1) * 36 : 1);
-        g.chol_y = A.take<double>(chol_np);
-        g.chol_linv = A.take<double>(2 * 32 * 32);
-        g.stamps = A.take<unsigned long long>(128);
-        g.st = w.d_state;                                   // (its own allocation: the address does not move with the window's sizes)
-        // ---- from here on: arrays that are written in full before anything reads them — not part of the upload's clearing pass (a third
-        // of the arena at C2: the stage hooks' H_pl tiles and residuals exist for every window but are only written under `debug`)
-        zero_end = (A.used + 255) & ~size_t(255);
-        g.blk_pairs = A.take<int4>((size_t)std::max<int64_t>(run_path ? 0 : npairs, 1));      // every slot filled on the device (k_build_pairs: the counts are the summary's)
-        g.pose_lm = A.take<int32_t>(std::max(n_pose_obs, 1));                   // every slot filled by k_index_scatter
-        g.pose_rec = A.take<DeviceGraph::PoseRec>(std::max(n_pose_obs, 1));     // likewise
-        g.obs_err = A.take<double>((size_t)std::max(No, 1) * 3);               // debug: every observation, active or not (k_linearize)
-        g.W = A.take<double>((size_t)std::max(No, 1) * 18);                    // likewise
-    };
-    layout_dyn(dyn, dg);
-    const size_t total_bytes = (dyn.used + 255) & ~size_t(255);
-
+// the device arena (index + mutable sections) and the pinned arena, grown when the window needs more
+int ensure_arenas(visfs_ba_handle* h, Workspace& w, const size_t total_bytes, const size_t host_need) {
     if (w.d_cap < total_bytes) {
         HIP_TRY(h, hipStreamSynchronize(w.stream));
         if (w.d_base) (void)hipFree(w.d_base);
@@ -924,9 +502,6 @@ int ws_upload(visfs_ba_handle* h, Workspace& w, const visfs_ba_graph* gr, const 
         HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&w.d_base), want));
         w.d_cap = want;
     }
-    // the pinned arena also receives the outputs of a solve (ws_read_state): both estimate buffers and the outlier flags
-    size_t host_need = static_bytes;
-    { DeviceGraph sz{}; sz.Np = Np; sz.Nl = Nl; sz.No = No; host_need = std::max(host_need, output_stage_bytes(sz)); }
     if (w.h_cap < host_need) {
         HIP_TRY(h, hipStreamSynchronize(w.stream));
         if (w.h_base) (void)hipHostFree(w.h_base);
@@ -935,67 +510,34 @@ int ws_upload(visfs_ba_handle* h, Workspace& w, const visfs_ba_graph* gr, const 
         HIP_TRY(h, hipHostMalloc(reinterpret_cast<void**>(&w.h_base), want, hipHostMallocDefault));
         w.h_cap = want;
     }
-    lap("alloc");
-    // fill the index staging
-    Arena hs{ w.h_base, w.h_cap, 0 };
-    layout(hs, hg);
-    {
-        if (n_chunks) std::memcpy(const_cast<int32_t*>(hg.chunk_pose), chunk_pose.data(), (size_t)n_chunks * 4);
-        std::memcpy(const_cast<int32_t*>(hg.chunk_ptr), chunk_ptr.data(), (size_t)(n_chunks + 1) * 4);
-        std::memcpy(const_cast<int32_t*>(hg.pose_chunk_ptr), pose_chunk_ptr.data(), (size_t)(Npf + 1) * 4);
-        std::memcpy(const_cast<int32_t*>(hg.pose_odo_ptr), pose_odo_ptr.data(), (size_t)(Npf + 1) * 4);
-        if (!pose_odo.empty()) std::memcpy(const_cast<int32_t*>(hg.pose_odo), pose_odo.data(), pose_odo.size() * 4);
-        if (n_blk) { std::memcpy(const_cast<int32_t*>(hg.blk_i), blk_i.data(), (size_t)n_blk * 4); std::memcpy(const_cast<int32_t*>(hg.blk_j), blk_j.data(), (size_t)n_blk * 4); }
-        std::memcpy(const_cast<int32_t*>(hg.blk_ptr), blk_ptr.data(), (size_t)(n_blk + 1) * 4);
-        std::memcpy(const_cast<int32_t*>(hg.blk_chunk_ptr), blk_chunk_ptr.data(), (size_t)(n_blk + 1) * 4);
-        std::memcpy(const_cast<int4*>(hg.sch_desc), sch_desc.data(), sch_desc.size() * sizeof(int4));
-        std::memcpy(const_cast<int4*>(hg.blk_desc), blk_desc.data(), blk_desc.size() * sizeof(int4));
-        std::memcpy(const_cast<int32_t*>(hg.blk_odo_ptr), blk_odo_ptr.data(), (size_t)(n_blk + 1) * 4);
-        if (!blk_odo.empty()) std::memcpy(const_cast<int32_t*>(hg.blk_odo), blk_odo.data(), blk_odo.size() * 4);
-        std::memcpy(const_cast<int32_t*>(hg.row_ptr), row_ptr.data(), (size_t)(Npf + 1) * 4);
-        if (!row_col.empty()) { std::memcpy(const_cast<int32_t*>(hg.row_col), row_col.data(), row_col.size() * 4); std::memcpy(const_cast<int32_t*>(hg.row_blk), row_blk.data(), row_blk.size() * 4); }
-        if (n_blk) std::memcpy(const_cast<int32_t*>(hg.blk_slot), blk_slot.data(), (size_t)n_blk * 4);
-        {
-            int32_t* fe = const_cast<int32_t*>(hg.fin_exp); int32_t* db = const_cast<int32_t*>(hg.diag_blk);
-            for (int b = 0; b < n_blk; ++b) {
-                const int a = blk_i[b];
-                const bool dgb = (a == blk_j[b]);
-                fe[b] = (blk_chunk_ptr[b + 1] - blk_chunk_ptr[b]) | ((dgb ? pose_chunk_ptr[a + 1] - pose_chunk_ptr[a] : 0) << 16);
-                if (dgb) db[a] = b;
-            }
-            if (n_sch) std::memcpy(const_cast<int32_t*>(hg.sch_blk), sch_blk.data(), (size_t)n_sch * 4);
-        }
-        if (pcg1) std::memcpy(const_cast<int32_t*>(hg.pcg1_code), pcg1_code.data(), pcg1_code.size() * 4);
-        if (band_B >= 0) std::memcpy(const_cast<int32_t*>(hg.band_code), band_code.data(), band_code.size() * 4);
-        if (run_path) { std::memcpy(const_cast<int4*>(hg.run_desc), rp.desc.data(), rp.desc.size() * sizeof(int4)); std::memcpy(const_cast<int32_t*>(hg.run_k0), rp.k0.data(), rp.k0.size() * 4); }
-    }
-    lap("stage fill");
-    // device pointers: same offsets
-    { Arena dp{ w.d_prim, w.d_prim_cap, 0 }; layout_prim(dp, dg, pz); }
-    Arena ds{ w.d_base, w.d_cap, 0 };
-    layout(ds, dg);
-    Arena dd{ w.d_base, w.d_cap, static_bytes };
-    layout_dyn(dd, dg);
-    dg.Np = Np; dg.Nl = Nl; dg.No = No; dg.Ne = Ne; dg.Npf = Npf;
-    dg.n_pose_obs = n_pose_obs;
-    dg.n_chunks = n_chunks; dg.n_blk = n_blk; dg.n_lin_a = n_lin_a; dg.group = group; dg.n_edges_ok = n_edges_ok;
+    return VISFS_BA_OK;
+}
+
+// the scalar fields of the DeviceGraph: from the graph, the parameters and the plan
+void fill_graph_scalars(DeviceGraph& dg, const visfs_ba_graph* gr, const visfs_ba_params& prm, const UploadPlan& P, const UploadSwitches& sw,
+                        const bool batch_member, const double baseline) {
+    const bool ceres = prm.framework == 1;
+    const int Npf = P.Npf, n_blk = P.n_blk, Nz = P.Nz;
+    const RunPlan& rp = P.run;
+    dg.Np = P.Np; dg.Nl = P.Nl; dg.No = P.No; dg.Ne = P.Ne; dg.Npf = Npf;
+    dg.n_pose_obs = P.n_pose_obs;
+    dg.n_chunks = P.n_chunks; dg.n_blk = n_blk; dg.n_lin_a = P.n_lin_a; dg.group = P.group; dg.n_edges_ok = P.n_edges_ok;
     // The finalisation of S as the prologue of the one-wave PCG launch (k_pcg1<FIN>; VERDICT r03 item 9's "drop the k_schur_finalize launch").
     // MEASURED (profiles/r04_fin_pcg_fusion_ab.log): bit-identical, and no faster — the fused launch takes 27.0 us where the two launches take
     // 5.65 + 20.9 (the in-launch hand-off, a drain + flag + sc1 reload, costs what the kernel boundary cost; the finalising waves run at
     // k_pcg1's one wave per SIMD); C2 19.8-20.0 k against 20.2 k it/s, 16 resident windows 65 k against 80 k.  Opt-in: VISFS_BA_FIN_PCG=1.
-    { const char* e = std::getenv("VISFS_BA_FIN_PCG"); const char* gv = std::getenv("VISFS_BA_PCG_GATHER");
-      dg.fin_pcg = (pcg1 && !pcg_cu && !small_solve_fits_npf && (e && e[0] == '1') && !(gv && std::atoi(gv) != 1)) ? 1 : 0; }
+    dg.fin_pcg = (P.pcg1 && !P.pcg_cu && !P.small_fits && sw.fin_pcg && sw.pcg_gather == 1) ? 1 : 0;
     dg.n_runs = rp.n; dg.run_lr = rp.LR; dg.run_m = rp.M; dg.run_cap = rp.cap; dg.run_wmax = rp.wmax; dg.run_lds_bytes = (int32_t)rp.lds;
-    dg.n_sch = n_sch; dg.sch_chunk = sch_chunk; dg.pcg_lds_minv = lds_minv; dg.pcg_lds_srow = lds_srow; dg.pcg_max_row = max_row; dg.pcg_rows_per_wg = pcg_rpw; { // fin_arrive (opt-in, VISFS_BA_FIN_ARRIVE=1): needs every stored block to own at least one gather chunk (somebody has to arrive) and counts that fit 16 bits
-      const char* e = std::getenv("VISFS_BA_FIN_ARRIVE");
-      bool ok = e && e[0] == '1' && !w.batch_member && !ceres && !run_path && !small_solve_fits_npf && n_blk > 0;
-      for (int b = 0; ok && b < n_blk; ++b) ok = blk_chunk_ptr[b + 1] > blk_chunk_ptr[b] && blk_chunk_ptr[b + 1] - blk_chunk_ptr[b] < 65536;
-      for (int a = 0; ok && a < Npf; ++a) ok = pose_chunk_ptr[a + 1] - pose_chunk_ptr[a] < 32768;
+    dg.n_sch = P.n_sch; dg.sch_chunk = P.sch_chunk; dg.pcg_lds_minv = 0; dg.pcg_lds_srow = P.lds_srow; dg.pcg_max_row = P.max_row; dg.pcg_rows_per_wg = P.pcg_rpw;
+    { // fin_arrive (opt-in, VISFS_BA_FIN_ARRIVE=1): needs every stored block to own at least one gather chunk (somebody has to arrive) and counts that fit 16 bits
+      bool ok = sw.fin_arrive && !batch_member && !ceres && !P.run_path() && !P.small_fits && n_blk > 0;
+      for (int b = 0; ok && b < n_blk; ++b) ok = P.blk_chunk_ptr[b + 1] > P.blk_chunk_ptr[b] && P.blk_chunk_ptr[b + 1] - P.blk_chunk_ptr[b] < 65536;
+      for (int a = 0; ok && a < Npf; ++a) ok = P.pose_chunk_ptr[a + 1] - P.pose_chunk_ptr[a] < 32768;
       dg.fin_arrive = ok ? 1 : 0; }
-    dg.pcg_cu = pcg_cu ? 1 : 0; dg.cu_T = cu_T; dg.pcg_lds_bytes = pcg_cu ? (int32_t)pcg_cu_lds_bytes(Npf, max_row) : (int32_t)pcg_lds; dg.chol_np = (int32_t)chol_np;
-    dg.band_B = band_B; dg.band_rows = band_rows; dg.band_lds_bytes = band_lds;
+    dg.pcg_cu = P.pcg_cu ? 1 : 0; dg.cu_T = P.cu_T; dg.pcg_lds_bytes = P.pcg_cu ? (int32_t)pcg_cu_lds_bytes(Npf, P.max_row) : (int32_t)P.pcg_lds; dg.chol_np = (int32_t)P.chol_np;
+    dg.band_B = P.band_B; dg.band_rows = P.band_rows; dg.band_lds_bytes = P.band_lds;
     dg.fx = gr->fx; dg.fy = gr->fy; dg.cx = gr->cx; dg.cy = gr->cy; dg.bf = gr->bf;
-    dg.stereo_baseline = opt.baseline;
+    dg.stereo_baseline = baseline;
     dg.inv_pixel_var = 1.0 / prm.pixel_variance;          // Optimizer.cpp:153
     dg.inv_pixel_var_out = dg.inv_pixel_var;
     dg.ceres = ceres ? 1 : 0;
@@ -1010,39 +552,112 @@ int ws_upload(visfs_ba_handle* h, Workspace& w, const visfs_ba_graph* gr, const 
     if (Nz) { dg.grid.nx = gr->grid->num_x_cells; dg.grid.ny = gr->grid->num_y_cells; dg.grid.resolution = gr->grid->resolution;
               dg.grid.max_x = gr->grid->max_x; dg.grid.max_y = gr->grid->max_y; }
     dg.debug = 0;
-    { const char* e = std::getenv("VISFS_BA_STAMP_WG"); dg.stamp_wg = e ? std::atoi(e) : 0; }
-    { const char* e = std::getenv("VISFS_BA_FAULT_PCG_TIMEOUT"); dg.fault_pcg = (e && e[0] == '1') ? 1 : 0; }      // test hook: force the time-out path once per solve
-    w.g = dg;
-    // the same graph at its fixed device address (what the launch sequences of the per-frame path read: Many{ d_graph, d_state })
-    *w.h_graph = dg;
-    HIP_TRY(h, hipMemcpyAsync(w.d_graph, w.h_graph, sizeof(DeviceGraph), hipMemcpyHostToDevice, w.stream));
+    dg.stamp_wg = sw.stamp_wg;
+    dg.fault_pcg = sw.fault_pcg ? 1 : 0;                  // test hook: force the time-out path once per solve
+}
+
+// which form of the LM unit the resident window (w.g) runs on
+void choose_unit_form(Workspace& w, const visfs_ba_params& prm, const UploadPlan& P, const UploadSwitches& sw) {
+    const bool ceres = prm.framework == 1;
     // opt-in (VISFS_BA_FUSED=1): one CU's fp64 rate makes the fused kernel slower than the multi-kernel path per window
     // (DESIGN.md §4); it pays only when many small windows run side by side
-    { const char* e = std::getenv("VISFS_BA_SMALL_SOLVE"); w.small_solve = small_solve_fits(dg) && !(e && e[0] == '0'); }
-    { const char* e = std::getenv("VISFS_BA_FUSED"); w.fused = small_path_fits(dg) && e && e[0] == '1'; }
+    w.small_solve = small_solve_fits(w.g) && sw.small_solve;
+    w.fused = small_path_fits(w.g) && sw.fused;
     // speculative linearise: a rejected trial wastes one linearisation, an accepted one saves k_decide + a launch gap — worth it
     // while the linearisation is cheap (latency-bound windows); large windows (C4: half the trials are rejected) and batch
     // members keep the gated form.
-    { const char* e = std::getenv("VISFS_BA_SPEC"); w.spec = (e ? (e[0] == '1') : (No <= 150000)) && Np <= MAX_STAGED_POSES; }
+    w.spec = (sw.spec >= 0 ? sw.spec == 1 : (P.No <= 150000)) && P.Np <= MAX_STAGED_POSES;
     // Optimizer/Framework=1 runs the plain gated unit with the direct solver (k_small_solve's Cholesky for reduced systems <= 64 x 64):
     // one unit = one iteration of Ceres' minimizer loop
     if (ceres) { w.fused = false; w.spec = false; }
     // the fused form of the speculative unit: one launch less per iteration (VISFS_BA_SPEC_FUSED=0: the two-launch form, A/B runs and tests)
-    { const char* e = std::getenv("VISFS_BA_SPEC_FUSED"); w.spec_fused = w.spec && !(e && e[0] == '0'); }
+    w.spec_fused = w.spec && sw.spec_fused;
     // Batch members (round 4) CAN run the same fused unit — 4 launches per iteration instead of the gated unit's 6; the two-launch form
     // does not exist for them.  Measured (profiles/r04_batch_fused_unit_ab.log): a batched launch is bound by its arithmetic, not by its
     // launch boundaries — fusing moves the linearisation's work into k_backsub (at 128 instead of 96 VGPRs) and behind the gather without
     // removing any of it: 16 x C2 80.3 k -> 74.4 k it/s, 8 x C2 66.9 k -> 65.8 k.  So the gated unit stays the default for batch members
     // (VISFS_BA_BATCH_SPEC=1 selects the fused unit: tests, A/B runs).
-    if (w.batch_member) { const char* e = std::getenv("VISFS_BA_BATCH_SPEC"); if (!w.spec_fused || !(e && e[0] == '1')) { w.spec = false; w.spec_fused = false; } }
+    if (w.batch_member && (!w.spec_fused || !sw.batch_spec)) { w.spec = false; w.spec_fused = false; }
     // default: on for a window on its own, off for batch members — measured in round 4 (profiles/r04_batch_decide_fused_ab.log): 8 windows
     // 71.1 -> 68.7 k it/s, 16 windows 90.3 -> 83.7 k with the decision on board k_backsub<Many> (VISFS_BA_DECIDE_FUSED=1 forces it on for both)
-    { const char* e = std::getenv("VISFS_BA_DECIDE_FUSED"); w.fused_decide = (e ? (e[0] != '0') : !w.batch_member) && !ceres; }
-    w.direct_ready = prm.solver == 2 && !ceres && Npf >= 1 && !w.small_solve && (band_B >= 0 || chol_np <= 2048);
+    w.fused_decide = (sw.decide_fused >= 0 ? sw.decide_fused == 1 : !w.batch_member) && !ceres;
+    w.direct_ready = prm.solver == 2 && !ceres && P.Npf >= 1 && !w.small_solve && (P.band_B >= 0 || P.chol_np <= 2048);
     w.solver_now = -1;
-    w.n_pairs = npairs; w.device_bytes = total_bytes + pbytes;
-    w.free_pose = free_pose; w.blk_i = blk_i; w.blk_j = blk_j; w.pose_free = pose_free;
-    w.odo_i.assign(gr->odo_from, gr->odo_from + Ne); w.odo_j.assign(gr->odo_to, gr->odo_to + Ne);
+}
+
+int ws_upload(visfs_ba_handle* h, Workspace& w, const visfs_ba_graph* gr, const UploadOpts& opt = UploadOpts()) {
+    const UploadSwitches sw = read_upload_switches();
+    const bool timing = sw.timing;
+    auto T0 = std::chrono::steady_clock::now();
+    auto lap = [&](const char* what) { if (timing) { auto t = std::chrono::steady_clock::now(); std::fprintf(stderr, "  upload %-14s %8.1f us\n", what, std::chrono::duration<double, std::micro>(t - T0).count()); T0 = t; } };
+    const visfs_ba_params& prm = h->prm;
+    const bool ceres = prm.framework == 1;
+    // From the first mutation below (the primary arrays are overwritten before the graph has been validated) until the upload has gone
+    // through, NO graph is resident: a failed upload must not leave the previous graph's index structures marked usable over the
+    // rejected graph's arrays (visfs_ba_optimize then returns VISFS_BA_ERR_NOT_LOADED instead of walking them).
+    w.loaded = false;
+    PlanGraph G;
+    size_t grid_cells = 0;
+    int rc = validate_graph(h, gr, ceres, G, grid_cells);
+    if (rc != VISFS_BA_OK) return rc;
+    rc = ws_init(h, w);
+    if (rc != VISFS_BA_OK) return rc;
+    if (w.graph_exec) { (void)hipGraphExecDestroy(w.graph_exec); w.graph_exec = nullptr; w.graph_units[0] = w.graph_units[1] = -1; }   // kernel arguments change
+    w.solves_since_upload = 0;
+    HIP_TRY(h, hipSetDevice(h->device));
+
+    PrimSizes pz;
+    if (opt.in_staging) pz = opt.cap;
+    else { pz.Np = G.Np; pz.Nl = G.Nl; pz.cap_obs = G.No; pz.cap_odo = G.Ne; pz.Nz = G.Nz; pz.grid_cells = grid_cells; }
+    const size_t pbytes = prim_bytes(pz);
+    UploadPlan P;
+    DeviceGraph hg{};                 // pointers into the pinned staging arenas
+    rc = stage_primary(h, w, gr, opt, G, pz, pbytes, hg, P);
+    if (rc != VISFS_BA_OK) return rc;
+    lap("primary");
+
+    // ---- what the host needs of the O(N_obs) part: observations per free pose, co-observation pairs per block
+    GraphSummary sum;
+    if (opt.summary_slots > 0) merge_summary(w.sum_part, opt.summary_slots, P.Npf, sum, w.sum_run);
+    else summarize_graph(gr, P.pose_free.data(), P.Npf, opt.pool, !opt.trusted, sum, w.sum_part, w.sum_run);
+    if (sum.bad) return bad(h, sum.bad);
+    lap("summary");
+
+    // ---- the index structure of S and every kernel form that follows from it (ba_plan.hpp)
+    PlanDecisions D;
+    D.solver = prm.solver; D.batch_member = w.batch_member; D.throughput = h->tuning == VISFS_BA_TUNE_THROUGHPUT; D.index_blocks = index_blocks(G.No);
+    D.sw = sw; D.band_plan = band_plan; D.band_lds_bytes = band_lds_bytes; D.pcg_cu_fits = pcg_cu_fits;
+    if (!plan_upload(P, G, sum, D)) { h->err = P.msg; return P.status; }
+    lap("structure");
+
+    // ---- the INDEX section and the mutable section: one device arena, the index part staged in pinned memory with the same layout
+    const size_t static_bytes = layout_index(IndexWalk{ Arena{ nullptr, 0, 0 }, false }, hg, P);
+    DynOpts dyo; dyo.raw_refs = pz.raw_refs; dyo.dogleg = ceres && prm.trust_region == 1; dyo.st = w.d_state;
+    DeviceGraph dg{};
+    int32_t* d_hist = nullptr;
+    size_t zero_end = 0;
+    const size_t total_bytes = layout_dyn(Arena{ nullptr, 0, static_bytes }, dg, P, dyo, &d_hist, &zero_end);
+    // the pinned arena also receives the outputs of a solve (ws_read_state): both estimate buffers and the outlier flags
+    size_t host_need = static_bytes;
+    { DeviceGraph sz{}; sz.Np = G.Np; sz.Nl = G.Nl; sz.No = G.No; host_need = std::max(host_need, output_stage_bytes(sz)); }
+    rc = ensure_arenas(h, w, total_bytes, host_need);
+    if (rc != VISFS_BA_OK) return rc;
+    lap("alloc");
+    layout_index(IndexWalk{ Arena{ w.h_base, w.h_cap, 0 }, true }, hg, P);          // fill the index staging
+    lap("stage fill");
+    // device pointers: same offsets
+    { Arena dp{ w.d_prim, w.d_prim_cap, 0 }; layout_prim(dp, dg, pz); }
+    layout_index(IndexWalk{ Arena{ w.d_base, w.d_cap, 0 }, false }, dg, P);
+    layout_dyn(Arena{ w.d_base, w.d_cap, static_bytes }, dg, P, dyo, &d_hist, &zero_end);
+    fill_graph_scalars(dg, gr, prm, P, sw, w.batch_member, opt.baseline);
+    w.g = dg;
+    // the same graph at its fixed device address (what the launch sequences of the per-frame path read: Many{ d_graph, d_state })
+    *w.h_graph = dg;
+    HIP_TRY(h, hipMemcpyAsync(w.d_graph, w.h_graph, sizeof(DeviceGraph), hipMemcpyHostToDevice, w.stream));
+    choose_unit_form(w, prm, P, sw);
+    w.n_pairs = P.npairs; w.device_bytes = total_bytes + pbytes;
+    w.free_pose = P.free_pose; w.blk_i = P.blk_i; w.blk_j = P.blk_j; w.pose_free = P.pose_free;
+    w.odo_i.assign(gr->odo_from, gr->odo_from + G.Ne); w.odo_j.assign(gr->odo_to, gr->odo_to + G.Ne);
     if (static_bytes) HIP_TRY(h, hipMemcpyAsync(w.d_base, w.h_base, static_bytes, hipMemcpyHostToDevice, w.stream));
     HIP_TRY(h, hipMemsetAsync(w.d_base + static_bytes, 0, zero_end - static_bytes, w.stream));
     if (configure_kernels(w.g) != 0) { h->err = "hipFuncSetAttribute failed"; return VISFS_BA_ERR_DEVICE; }
@@ -1208,7 +823,7 @@ static int pcg_budget_capacity(int device) {
 }
 // Wavefront slots a solve's persistent PCG grid needs (0: exclusive use of the budget).
 static int pcg_wave_cost(const LaunchDims& d, int members) {
-    static const int gv = []() { const char* e = std::getenv("VISFS_BA_PCG_GATHER"); return e ? std::atoi(e) : 1; }();
+    static const int gv = env_int("VISFS_BA_PCG_GATHER", 1);
     if (!d.pcg_one_wave || gv == 3) return 0;                  // four-wave kernel (or the 8x grid of the XCD-local variant): exclusive
     return d.pcg_rows * std::max(1, members);
 }
@@ -1221,7 +836,7 @@ int batch_members_per_launch(visfs_ba_handle* h, const std::vector<Workspace*>& 
     if (no_pcg) return 4096;                               // single-workgroup solvers: no co-residency requirement
     int cap = pcg_resident_capacity(d, true, h->device);
     if (cap <= 0) cap = 256;                               // query failed: one 256-thread workgroup per CU is always admitted
-    { const char* e = std::getenv("VISFS_BA_PCG_CAPACITY"); if (e && std::atoi(e) > 0) cap = std::atoi(e); }   // tests: force a split
+    { const int q = env_int("VISFS_BA_PCG_CAPACITY", 0); if (q > 0) cap = q; }   // tests: force a split
     return std::max(1, cap / std::max(1, d.pcg_rows));
 }
 
@@ -1269,7 +884,7 @@ int ws_optimize_run(visfs_ba_handle* h, Workspace& w, visfs_ba_stats* stats, con
     // call either way).  VERDICT r03 item 4's premise — r03's "0.98 ms replayed vs 1.06 eager" — compared a resident re-optimisation with a
     // per-frame call, not two launch modes of the same call.  The path stays available (VISFS_BA_FRAME_GRAPH=2; tests keep it honest); the
     // default is the by-value path.
-    const int frame_mode = []() { const char* e = std::getenv("VISFS_BA_FRAME_GRAPH"); return e ? std::atoi(e) : 0; }();   // 0: by-value path, 1: fixed-address path without capture, 2: with (read per call: tests switch it)
+    const int frame_mode = env_int("VISFS_BA_FRAME_GRAPH", 0);   // 0: by-value path, 1: fixed-address path without capture, 2: with (read per call: tests switch it)
     const bool band_direct = solver != 2 && !w.small_solve && w.g.band_B >= 0;
     const bool ref_mode = frame_mode != 0 && fresh_upload && w.solves_since_upload == 0 && !fallback_run && !w.prof_mask && !w.batch_member && w.d_graph && w.d_state &&
                           (h->prm.framework == 0 || w.small_solve || band_direct) && (solver == 2 || w.small_solve || band_direct) && !(w.spec && !w.spec_fused) &&
@@ -1300,7 +915,7 @@ int ws_optimize_run(visfs_ba_handle* h, Workspace& w, visfs_ba_stats* stats, con
     // for a window that is uploaded, solved once and replaced (visfs_ba_solve_window per frame).  Measured
     // (profiles/r02_hipgraph_replay.log): C2 19.0 -> 19.4 k it/s (GPU-bound stream), PROD 23.5 -> 25.6 k it/s (small kernels:
     // the eager host launch rate shows).
-    static const int graph_mode = []() { const char* e = std::getenv("VISFS_BA_GRAPH"); return e ? std::atoi(e) : 2; }();
+    static const int graph_mode = env_int("VISFS_BA_GRAPH", 2);
     const int n0 = half + w.extra_units[0], n1 = half2 > 0 ? half2 + w.extra_units[1] : 0;
     w.solves_since_upload += 1;
     bool replayed = false;
@@ -1321,7 +936,7 @@ int ws_optimize_run(visfs_ba_handle* h, Workspace& w, visfs_ba_stats* stats, con
             fg = &w.frame_graphs.back();
         }
         fg->last_use = ++w.frame_clock;
-        const int capture_at = []() { const char* e = std::getenv("VISFS_BA_FRAME_GRAPH_AT"); return e ? std::max(0, std::atoi(e)) : 1; }();
+        const int capture_at = std::max(0, env_int("VISFS_BA_FRAME_GRAPH_AT", 1));
         if (!fg->exec && fg->seen >= capture_at) {
             // (failure path as for the resident-graph capture below: the capture is always ended, a partial graph dropped, eager launches
             // from then on for this workspace)
@@ -1564,12 +1179,12 @@ int pack_window_impl(const visfs_ba_window* w, const PackOut& o, visfs_ba_graph*
     const int16_t* const ptab = pose_tab.empty() ? nullptr : pose_tab.data();
     struct Part { int no = 0, mono = 0, first_p = -1, first_c = -1, last_p = -1, last_c = -1; bool bad = false; };
     std::vector<Part> part(T);
-    static const bool timing = std::getenv("VISFS_BA_TIMING") != nullptr;
+    static const bool timing = env_set("VISFS_BA_TIMING");
     const auto tr0 = std::chrono::steady_clock::now();
     if (timing) std::fprintf(stderr, "   pack: before the reference loop %.1f us\n", std::chrono::duration<double, std::micro>(tr0 - te0).count());
     std::atomic<int> by_caller{ 0 };
     // (diagnostic, timing runs only — results are WRONG with it: 2 = no output stores, 4 = no point_used store, 8 = no summary accumulation)
-    static const int dbg = []() { const char* e = std::getenv("VISFS_BA_PACK_DEBUG"); return (e && std::getenv("VISFS_BA_TIMING")) ? std::atoi(e) : 0; }();
+    static const int dbg = env_set("VISFS_BA_TIMING") ? env_int("VISFS_BA_PACK_DEBUG", 0) : 0;
     struct TaskLap { int slot; double t0, t1; };
     std::vector<TaskLap> task_lap(timing ? T : 0);
     auto body = [&](int t, int slot) {
@@ -1638,7 +1253,7 @@ int pack_window_impl(const visfs_ba_window* w, const PackOut& o, visfs_ba_graph*
     if (timing) {
         std::fprintf(stderr, "   pack: poses + links + cuts, then %d tasks (%d by the caller): %.1f us since entry\n", T, by_caller.load(),
                      std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tr0).count());
-        if (T > 1 && std::getenv("VISFS_BA_TIMING_TASKS")) for (int t = 0; t < T; ++t) std::fprintf(stderr, "      task %2d on slot %d: %7.1f -> %7.1f us (%d references)\n", t, task_lap[t].slot, task_lap[t].t0, task_lap[t].t1, cut[t + 1] - cut[t]);
+        if (T > 1 && env_set("VISFS_BA_TIMING_TASKS")) for (int t = 0; t < T; ++t) std::fprintf(stderr, "      task %2d on slot %d: %7.1f -> %7.1f us (%d references)\n", t, task_lap[t].slot, task_lap[t].t0, task_lap[t].t1, cut[t + 1] - cut[t]);
     }
     int no = 0, mono = 0, last_p = -1, last_c = -1;
     for (int t = 0; t < T; ++t) {
@@ -1715,7 +1330,7 @@ int prepare_window(visfs_ba_handle* h, Workspace& w, const visfs_ba_window* win,
     opt.in_staging = true; opt.trusted = true; opt.pool = pool;
     opt.cap.Np = Np; opt.cap.Nl = Nl; opt.cap.cap_obs = Nr; opt.cap.cap_odo = Nk;
     // the references cross the memory bus and PCIe as localOptimize receives them (float u, v, depth: 12 bytes); the device forms (u_l, v_l, u_r)
-    { static const bool raw = []() { const char* e = std::getenv("VISFS_BA_RAW_REFS"); return !(e && e[0] == '0'); }(); opt.cap.raw_refs = raw; }
+    { static const bool raw = env_not_0("VISFS_BA_RAW_REFS"); opt.cap.raw_refs = raw; }
     opt.baseline = (win->n_cameras > 1) ? (double)win->baseline : 0.0;
     if (win->n_laser_points > 0 && win->grid != nullptr && win->laser_xyz != nullptr) {
         const visfs_ba_grid& G = *win->grid;
@@ -1732,7 +1347,7 @@ int prepare_window(visfs_ba_handle* h, Workspace& w, const visfs_ba_window* win,
     o.pose = const_cast<double*>(hg.pose0); o.pose_stride = POSE_STRIDE; o.pose_fixed = pk.pose_fixed.data(); o.point_used = pk.point_used.data();
     o.obs_point = const_cast<int32_t*>(hg.obs_pt); o.obs_pose = const_cast<int32_t*>(hg.obs_pose); o.obs_uvr = const_cast<double*>(hg.obs_uvr); o.obs_uvd = const_cast<float*>(hg.obs_uvd); o.obs_ref = pk.obs_ref.data();
     o.odo_from = const_cast<int32_t*>(hg.odo_i); o.odo_to = const_cast<int32_t*>(hg.odo_j); o.odo_tq = const_cast<double*>(hg.odo_tq);
-    const bool timing = std::getenv("VISFS_BA_TIMING") != nullptr;
+    const bool timing = env_set("VISFS_BA_TIMING");
     const auto tp0 = std::chrono::steady_clock::now();
     PackSummary psum; psum.part = &w.sum_part;
     rc = pack_window_impl(win, o, &pk.g, &pk.mono, pool, &psum);
@@ -1775,7 +1390,7 @@ int finish_window(visfs_ba_handle* h, Workspace& w, const visfs_ba_window* win, 
     }
     // outliers are appended at Optimizer.cpp:296, before the phase-2 abort check.  Large windows: counted and written by ranges of
     // observations on the pool (a range's outliers land where the serial loop would put them).
-    static const bool timing = std::getenv("VISFS_BA_TIMING") != nullptr;
+    static const bool timing = env_set("VISFS_BA_TIMING");
     auto F0 = std::chrono::steady_clock::now();
     auto flap = [&](const char* what) { if (timing) { auto t = std::chrono::steady_clock::now(); std::fprintf(stderr, "  finish %-16s %8.1f us\n", what, std::chrono::duration<double, std::micro>(t - F0).count()); F0 = t; } };
     int n = 0;
@@ -1842,7 +1457,7 @@ int finish_window(visfs_ba_handle* h, Workspace& w, const visfs_ba_window* win, 
 }
 
 int solve_window_on(visfs_ba_handle* h, Workspace& w, const visfs_ba_window* win, visfs_ba_result* r) {
-    static const bool timing = std::getenv("VISFS_BA_TIMING") != nullptr;
+    static const bool timing = env_set("VISFS_BA_TIMING");
     auto T0 = std::chrono::steady_clock::now();
     auto lap = [&](const char* what) { if (timing) { auto t = std::chrono::steady_clock::now(); std::fprintf(stderr, " window %-14s %8.1f us\n", what, std::chrono::duration<double, std::micro>(t - T0).count()); T0 = t; } };
     PackedWindow& pk = w.pk;
@@ -1966,7 +1581,7 @@ int batch_optimize(visfs_ba_handle* h, BatchScratch& bs, const std::vector<Works
 // it/s, 16 windows (k_pcg_cu) 70.5 -> 75.1 k, 32 windows 73.8 -> 77.6 k (bench.py --handles 2 shows the same from outside).  No result depends on how a batch is cut (every member's solve
 // is bit-identical to its single-window solve).  VISFS_BA_BATCH_SPLIT=0 keeps one sequence.
 int batch_optimize_group(visfs_ba_handle* h, const std::vector<int>& members) {
-    static const int parts_env = []() { const char* e = std::getenv("VISFS_BA_BATCH_SPLIT"); return e ? std::atoi(e) : -1; }();   // 0 / 1: one sequence; n: n parts
+    static const int parts_env = env_int("VISFS_BA_BATCH_SPLIT", -1);   // 0 / 1: one sequence; n: n parts
     const int B = (int)members.size();
     // (production-size windows on k_small_solve LOSE when cut: 8 windows 156.5 -> 130.9 k it/s, 16 windows 284 -> 178 k — their
     // launches are too short for a second host thread to feed a second stream beside them)
@@ -2285,8 +1900,7 @@ int visfs_ba_solve_batch(visfs_ba_handle* h, int32_t n, const visfs_ba_window* c
         };
         parallel([&](visfs_ba_handle& local, int i) { need[i] = prepare_window(&local, *h->batch[i], w[i], r[i], h->batch[i]->pk); if (!need[i]) rcs[i] = r[i]->status; });
         // groups: lanes per landmark, PCG variant class, small-solve / fused flags must agree inside one batched launch
-        const char* env = std::getenv("VISFS_BA_BATCH");
-        const bool batching = !(env && env[0] == '0');
+        const bool batching = env_not_0("VISFS_BA_BATCH");
         std::map<std::array<int, 5>, std::vector<int>> groups;
         std::vector<int> singles;
         for (int i = 0; i < n; ++i) {

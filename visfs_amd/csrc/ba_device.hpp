@@ -13,6 +13,7 @@
 
 #include <stdint.h>
 
+#include "ba_limits.hpp"   // LIN_CHUNK, SCH_CHUNK, RUN_*, SM_MAX_N6, MAX_PCG_*: shared with the host plan (ba_plan.hpp)
 #include "ba_math.hpp"
 
 namespace visfs_ba {
@@ -23,20 +24,12 @@ namespace visfs_ba {
 #ifndef VISFS_BA_RS_SWAP
 #define VISFS_BA_RS_SWAP 1           // 0: A/B builds — the reduce-scatters select send / keep and move one of them (round 1)
 #endif
-constexpr int LIN_CHUNK = 256;        // observations per pose-major workgroup
 constexpr int MAX_TRACE = 64;         // == VISFS_BA_MAX_TRACE
 constexpr int POSE_STRIDE = 8;        // doubles per pose in HBM (7 used; 64-byte rows)
 constexpr int MAX_STAGED_POSES = 840; // poses staged as R|t in LDS (12 doubles each; k_backsub stages two sets: 24 * 840 * 8 B + scratch <= 160 KiB);
                                       // larger windows take the kernels that read the poses from HBM (PoseSrc<false>)
-constexpr int MAX_PCG_ONE_ROW_POSES = 256; // persistent PCG with one workgroup per block row: all co-resident (256 CUs, >= 1 workgroup each)
-constexpr int MAX_PCG_FREE_POSES = 1024;   // beyond 256 free poses a workgroup owns several block rows (<= 256 workgroups) and an owner thread up to 4 blocks
-constexpr int RUN_MAX_W = 64;        // k_schur_runs: widest pose span of a run of landmarks (slot table [landmarks][span], 16-bit entries)
-constexpr int RUN_MAX_TILES = 416;   // ... observations of one sub-batch (21 doubles of LDS each: two workgroups per CU)
-constexpr int RUN_TILE = 21;         // ... doubles per staged tile: Q = N D (9), N (9), Pc (3)
-constexpr int SCH_CHUNK = 64;         // co-observation pairs per Schur wavefront and pass (DeviceGraph::sch_chunk = 64 x passes)
 // fused single-workgroup path (k_small_optimize): limits of a "small" window
 constexpr int SM_MAX_POSES = 16;      // R|t of every pose twice in LDS
-constexpr int SM_MAX_N6 = 64;         // <= 10 free poses: the reduced camera system is solved in LDS
 constexpr int SM_MAX_WCHUNKS = 192;   // 64-observation wave chunks of the pose-major pass (4 per LIN_CHUNK)
 constexpr int SM_MAX_OBS = 8192;      // beyond this one CU's arithmetic costs more than the launches it saves
 constexpr int SM_MAX_SCH = 1024;      // Schur chunks (<= 64 k co-observation pairs)
