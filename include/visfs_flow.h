@@ -6,7 +6,7 @@
  * gates, and generateKeyPoints3DStereo (MultiviewGeometry.cpp:57-92) for the stereo survivors.  It produces the `word_uv` /
  * `word_xyz` arguments of visfs_window_insert.  The image pyramids and their Scharr derivatives stay in device memory across frames;
  * the calls run as HIP kernels on the stream of the handle the object was created on.  Corner extraction on the same resident
- * images is include/visfs_corners.h and the PnP guess is include/visfs_pnp.h; the fundamental-matrix cull stays with the caller.  DESIGN.md section 9c states the arithmetic (restated from OpenCV's published
+ * images is include/visfs_corners.h and the PnP guess is include/visfs_pnp.h; the fundamental-matrix cull that replaces the forward-backward gate when flow_back is off is include/visfs_fund.h.  DESIGN.md section 9c states the arithmetic (restated from OpenCV's published
  * algorithm; parity with OpenCV itself is not pinned) and the one deliberate deviation (exact integer window sums).
  *
  * Error codes are the VISFS_BA_* of visfs_ba.h.

@@ -4,7 +4,7 @@
 // It keeps what imageProcess does with pixels: the two cv::goodFeaturesToTrack calls behind the mask of getMask (:116-141, :181, :327,
 // include/visfs_corners.h), the four cv::calcOpticalFlowPyrLK passes of a frame with their forward-backward gates and
 // generateKeyPoints3DStereo.  The bounds test and the compaction of the surviving words stay with the caller, as in the reference
-// they surround these calls; so does the fundamental-matrix cull.  The PnP guess is MotionEstimator.h.
+// they surround these calls.  The fundamental-matrix cull (flowBack off) is EpipolarCull.h, the PnP guess MotionEstimator.h.
 #ifndef VISFS_AMD_FLOW_TRACKER_H
 #define VISFS_AMD_FLOW_TRACKER_H
 
