@@ -211,11 +211,14 @@ template <class F> int guarded_fl(visfs_flow* f, F&& fn) noexcept {
     catch (...) { if (f) f->err = "unexpected exception"; return VISFS_BA_ERR_DEVICE; }
 }
 
-void host_push(visfs_flow* f, int slot, int image, const uint8_t* img, int32_t stride) {
+}  // namespace
+
+namespace flow {
+
+void host_pyramids(visfs_flow* f, int slot, int image) {
     std::vector<uint8_t>& px = f->hpx[slot][image];
     std::vector<uint32_t>& der = f->hder[slot][image];
     px.resize((size_t)f->lay.cells); der.resize((size_t)f->lay.cells);
-    for (int32_t y = 0; y < f->h; ++y) std::memcpy(px.data() + (size_t)y * f->w, img + (size_t)y * stride, (size_t)f->w);
     for (int l = 1; l < f->lay.n_levels; ++l) {
         const Level &S = f->lay.L[l - 1], &D = f->lay.L[l];
         for (int32_t y = 0; y < D.h; ++y)
@@ -228,15 +231,19 @@ void host_push(visfs_flow* f, int slot, int image, const uint8_t* img, int32_t s
     }
 }
 
-int device_push(visfs_flow* f, int slot, const uint8_t* left, const uint8_t* right, int32_t stride) {
+int device_stage(visfs_flow* f, uint8_t* const dst[2], const uint8_t* left, const uint8_t* right, int32_t stride) {
     FL_HIP(f, hipSetDevice(f->dev));
     FL_HIP(f, hipStreamSynchronize(f->stream));                        // the staging image of the frame before has left
     const size_t n0 = (size_t)f->w * f->h;
     const uint8_t* src[2] = { left, right };
     for (int i = 0; i < 2; ++i) {
         for (int32_t y = 0; y < f->h; ++y) std::memcpy(f->h_img + i * n0 + (size_t)y * f->w, src[i] + (size_t)y * stride, (size_t)f->w);
-        FL_HIP(f, hipMemcpyAsync(f->dpx[slot][i], f->h_img + i * n0, n0, hipMemcpyHostToDevice, f->stream));
+        FL_HIP(f, hipMemcpyAsync(dst[i], f->h_img + i * n0, n0, hipMemcpyHostToDevice, f->stream));
     }
+    return VISFS_BA_OK;
+}
+
+int device_pyramids(visfs_flow* f, int slot) {
     for (int l = 1; l < f->lay.n_levels; ++l) {
         const Level &S = f->lay.L[l - 1], &D = f->lay.L[l];
         PyrDownArgs A;
@@ -250,6 +257,22 @@ int device_push(visfs_flow* f, int slot, const uint8_t* left, const uint8_t* rig
     hipLaunchKernelGGL(k_flow_scharr, dim3(blocks_for(f->lay.cells), 2), dim3(FL_T), 0, f->stream, S, f->lay);
     FL_HIP(f, hipGetLastError());
     return VISFS_BA_OK;
+}
+
+}  // namespace flow
+
+namespace {
+
+void host_push(visfs_flow* f, int slot, int image, const uint8_t* img, int32_t stride) {
+    std::vector<uint8_t>& px = f->hpx[slot][image];
+    px.resize((size_t)f->lay.cells);
+    for (int32_t y = 0; y < f->h; ++y) std::memcpy(px.data() + (size_t)y * f->w, img + (size_t)y * stride, (size_t)f->w);
+    host_pyramids(f, slot, image);
+}
+
+int device_push(visfs_flow* f, int slot, const uint8_t* left, const uint8_t* right, int32_t stride) {
+    const int rc = device_stage(f, f->dpx[slot], left, right, stride);
+    return rc != VISFS_BA_OK ? rc : device_pyramids(f, slot);
 }
 
 Image host_image(const visfs_flow* f, int slot, int image) { return Image{ f->hpx[slot][image].data(), f->hder[slot][image].data() }; }
@@ -362,6 +385,7 @@ int visfs_flow_create(visfs_ba_handle* h, const visfs_flow_params* p, int32_t wi
 void visfs_flow_destroy(visfs_flow* f) {
     if (!f) return;
     flow::corners_release(f);
+    flow::clahe_release(f);
     release(f);
     delete f;
 }

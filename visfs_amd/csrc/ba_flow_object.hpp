@@ -1,5 +1,5 @@
 // The tracker object behind include/visfs_flow.h, shared by the translation units that work on it: ba_flow.hip (pyramids, LK passes)
-// and ba_corners.hip (corner extraction, include/visfs_corners.h).
+// ba_corners.hip (corner extraction, include/visfs_corners.h) and ba_clahe.hip (the equalised frame push, include/visfs_clahe.h).
 #pragma once
 #include "ba_flow.hpp"
 #include "../../include/visfs_flow.h"
@@ -10,6 +10,15 @@
 namespace flow {
 struct CornerState;                       // ba_corners.hip
 void corners_release(visfs_flow* f);      // frees what the first visfs_flow_corners call of f allocated (no-op before it)
+struct ClaheState;                        // ba_clahe.hip
+void clahe_release(visfs_flow* f);        // likewise for the first visfs_flow_push_frame_clahe call
+
+// The steps of a frame push (ba_flow.hip), for the pushes that put something else than the caller's bytes into level 0.
+// device_stage: waits for the stream, then copies both images through the pinned block to dst[0], dst[1] (w * h bytes each).
+int device_stage(visfs_flow* f, uint8_t* const dst[2], const uint8_t* left, const uint8_t* right, int32_t stride);
+// device_pyramids / host_pyramids: levels 1 .. max_level and the Scharr derivatives of every level from the level 0 of `slot`.
+int device_pyramids(visfs_flow* f, int slot);
+void host_pyramids(visfs_flow* f, int slot, int image);
 }  // namespace flow
 
 struct visfs_flow {
@@ -40,4 +49,7 @@ struct visfs_flow {
 
     // corner extraction (ba_corners.hip): nothing until the first visfs_flow_corners call
     flow::CornerState* corners = nullptr;
+
+    // equalised push (ba_clahe.hip): nothing until the first visfs_flow_push_frame_clahe call
+    flow::ClaheState* clahe = nullptr;
 };

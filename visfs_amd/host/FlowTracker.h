@@ -1,7 +1,8 @@
 // FlowTracker.h — the pixel half of VISFS::Tracker::imageProcess (corelib/src/Tracker.cpp:233-274, :343-388) backed by the
 // GPU-resident image pyramids of include/visfs_flow.h.  Header only, over the C ABI.
 //
-// It keeps what imageProcess does with pixels: the two cv::goodFeaturesToTrack calls behind the mask of getMask (:116-141, :181, :327,
+// It keeps what imageProcess does with pixels, and the equalisation System::inputPrimarySensorData runs in front of it when
+// System/CLAHE is set (System.cpp:107-111, include/visfs_clahe.h): the two cv::goodFeaturesToTrack calls behind the mask of getMask (:116-141, :181, :327,
 // include/visfs_corners.h), the four cv::calcOpticalFlowPyrLK passes of a frame with their forward-backward gates and
 // generateKeyPoints3DStereo.  The bounds test and the compaction of the surviving words stay with the caller, as in the reference
 // they surround these calls.  The fundamental-matrix cull (flowBack off) is EpipolarCull.h, the PnP guess MotionEstimator.h.
@@ -15,6 +16,7 @@
 #include <utility>
 #include <vector>
 
+#include "visfs_clahe.h"
 #include "visfs_corners.h"
 #include "visfs_flow.h"
 
@@ -42,6 +44,15 @@ public:
 
     // A new stereo pair (8-bit grey, `stride` bytes per row); the pair pushed before becomes imageFrom.
     int pushFrame(const uint8_t* left, const uint8_t* right, int stride) { return visfs_flow_push_frame(f_, left, right, stride); }
+
+    // pushFrame with System/CLAHE set: cv::createCLAHE(clipLimit, cv::Size(tilesX, tilesY))->apply on both images first
+    // (System.cpp:107-111), on the device; the buffers of the caller are not written.
+    int pushFrameCLAHE(const uint8_t* left, const uint8_t* right, int stride, double clipLimit = 3.0, int tilesX = 8, int tilesY = 8) {
+        visfs_clahe_params p;
+        visfs_clahe_default_params(&p);
+        p.clip_limit = clipLimit; p.tiles_x = tilesX; p.tiles_y = tilesY;
+        return visfs_flow_push_frame_clahe(f_, &p, left, right, stride);
+    }
 
     // Tracker.cpp:257-274: cornersFrom -> cornersTo (cornersTo non-empty on entry: OPTFLOW_USE_INITIAL_FLOW), status after the gate.
     int track(const std::vector<Point2f>& cornersFrom, std::vector<Point2f>& cornersTo, std::vector<unsigned char>& status,
