@@ -1,7 +1,14 @@
 #!/bin/bash
 # A/B measurement build of the HIP library with extra -D flags: tools/build_variant.sh <name> -DVISFS_BA_TILE_N=0 ...
 # -> visfs_amd/lib/libvisfs_ba_hip_<name>.so; select it with VISFS_BA_LIB=<path> (visfs_amd/backend.py).
+# VISFS_BA_SRC=<dir> builds the sources of another checkout's visfs_amd/csrc instead (the parent commit's library for an A/B:
+#   git archive <commit> visfs_amd/csrc include | tar -x -C <dir>; VISFS_BA_SRC=<dir>/visfs_amd/csrc tools/build_variant.sh parent).
 set -e
 cd "$(dirname "$0")/.."
 name=$1; shift
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared "$@" -o visfs_amd/lib/libvisfs_ba_hip_$name.so visfs_amd/csrc/ba_kernels.hip visfs_amd/csrc/ba_cov.hip visfs_amd/csrc/ba_submap.hip visfs_amd/csrc/ba_flow.hip visfs_amd/csrc/ba_corners.hip visfs_amd/csrc/ba_api.cpp -lpthread
+src=${VISFS_BA_SRC:-visfs_amd/csrc}
+files=""
+for f in ba_kernels.hip ba_cov.hip ba_submap.hip ba_flow.hip ba_corners.hip ba_clahe.hip ba_pnp.hip ba_fund.hip ba_tracker.hip ba_api.cpp; do
+  [ -f "$src/$f" ] && files="$files $src/$f"
+done
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared "$@" -o visfs_amd/lib/libvisfs_ba_hip_$name.so $files -lpthread

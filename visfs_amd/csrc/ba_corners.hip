@@ -42,7 +42,11 @@ struct CornerDev {                             // device words of a call, copied
 
 __global__ __launch_bounds__(CR_T) void k_corner_response(const uint8_t* __restrict__ px, int w, int h, const Disc* __restrict__ discs,
                                                           int n_discs, const int32_t* __restrict__ hw, float* __restrict__ eig,
-                                                          uint8_t* __restrict__ mask, CornerDev* st) {
+                                                          uint8_t* __restrict__ mask, CornerDev* st, const int32_t* dev_args) {
+    if (dev_args) {                            // a resident caller: { n_discs, max_corners } of this call live in device memory
+        if (dev_args[1] <= 0) return;          // nothing is wanted: no candidate is counted and the selection returns none
+        n_discs = dev_args[0];
+    }
     __shared__ int sI[CT_Y + 4][CT_X + 5];
     __shared__ int sDx[CT_Y + 2][CT_X + 3];
     __shared__ int sDy[CT_Y + 2][CT_X + 3];
@@ -109,7 +113,9 @@ __global__ __launch_bounds__(CR_T) void k_corner_response(const uint8_t* __restr
 }
 
 __global__ __launch_bounds__(CR_T) void k_corner_candidates(const float* __restrict__ eig, const uint8_t* __restrict__ mask, int w, int h,
-                                                            double quality, CornerDev* st, uint64_t* __restrict__ keys) {
+                                                            double quality, CornerDev* st, uint64_t* __restrict__ keys,
+                                                            const int32_t* dev_args) {
+    if (dev_args && dev_args[1] <= 0) return;  // the response map was not made
     const int64_t i = (int64_t)blockIdx.x * CR_T + threadIdx.x;
     const float t = quality_threshold(from_ordered_bits(st->max_bits), quality);
     bool cand = false;
@@ -167,7 +173,8 @@ __global__ __launch_bounds__(CR_T) void k_corner_sort(const uint64_t* __restrict
 }
 
 __global__ __launch_bounds__(kSelT) void k_corner_select(const uint64_t* __restrict__ sorted, CornerDev* st, int w, int32_t gate,
-                                                         int32_t max_corners, float* __restrict__ xy) {
+                                                         int32_t max_corners, float* __restrict__ xy, const int32_t* dev_args) {
+    if (dev_args) max_corners = dev_args[1] > 0 ? dev_args[1] : 0;
     __shared__ int32_t acc[kMaxCorners];       // accepted, x | y << 16
     __shared__ int32_t surv[kSelT];            // a chunk's survivors of the list as it stood when the chunk began, in order
     __shared__ int32_t wcount[kSelT / 64];
@@ -357,12 +364,6 @@ int check_call(visfs_flow* f, int32_t slot, int32_t image, const visfs_corners_p
     return VISFS_BA_OK;
 }
 
-// lrintf with the default rounding (half to even), kept within what the integer tests behind it can hold
-int32_t round_centre(float v) {
-    const double r = std::nearbyint((double)v);
-    return (int32_t)std::min(std::max(r, -1073741824.0), 1073741824.0);
-}
-
 // Tracker::getMask's draw decisions, in the order given: c->drawn, and the drawn discs that touch the image for the raster
 void decide_discs(const visfs_flow* f, CornerState* c, int32_t n_discs, const visfs_corners_disc* discs) {
     c->drawn.assign((size_t)n_discs, 0);
@@ -387,7 +388,8 @@ void decide_discs(const visfs_flow* f, CornerState* c, int32_t n_discs, const vi
 
 int32_t pack_xy(uint32_t index, int32_t w) { return (int32_t)(index % (uint32_t)w) | ((int32_t)(index / (uint32_t)w) << 16); }
 
-void host_corners(visfs_flow* f, CornerState* c, const uint8_t* px, const visfs_corners_params& p, float* xy, int32_t* n_out) {
+void host_corners(visfs_flow* f, CornerState* c, const uint8_t* px, const visfs_corners_params& p, const Disc* discs, int n_discs,
+                  const int32_t* hw, float* xy, int32_t* n_out) {
     const int w = f->w, h = f->h;
     const size_t n0 = (size_t)w * h;
     std::vector<int32_t> dxs(n0), dys(n0);
@@ -408,7 +410,7 @@ void host_corners(visfs_flow* f, CornerState* c, const uint8_t* px, const visfs_
                     sxx += dxs[at] * dxs[at]; sxy += dxs[at] * dys[at]; syy += dys[at] * dys[at];
                 }
             const float e = min_eig_response(sxx, sxy, syy);
-            const bool free_px = !masked(c->discs.data(), (int)c->discs.size(), c->hw.data(), x, y);
+            const bool free_px = !masked(discs, n_discs, hw, x, y);
             c->heig[(size_t)y * w + x] = e;
             c->hmask[(size_t)y * w + x] = free_px ? 255 : 0;
             if (free_px) max_bits = std::max(max_bits, ordered_bits(e));
@@ -465,17 +467,17 @@ int device_corners(visfs_flow* f, CornerState* c, const uint8_t* px, const visfs
     float* d_xy = reinterpret_cast<float*>(c->d_out + sizeof(CornerDev));
     CR_HIP(f, hipMemsetAsync(c->d_out, 0, sizeof(CornerDev), f->stream));
     hipLaunchKernelGGL(k_corner_response, dim3((w + CT_X - 1) / CT_X, (h + CT_Y - 1) / CT_Y), dim3(CR_T), 0, f->stream, px, w, h, d_discs,
-                       (int)c->discs.size(), d_hw, c->d_eig, c->d_mask, st);
+                       (int)c->discs.size(), d_hw, c->d_eig, c->d_mask, st, (const int32_t*)nullptr);
     CR_HIP(f, hipGetLastError());
     hipLaunchKernelGGL(k_corner_candidates, dim3((unsigned)(((size_t)w * h + CR_T - 1) / CR_T)), dim3(CR_T), 0, f->stream, c->d_eig, c->d_mask,
-                       w, h, p.quality_level, st, c->d_keys);
+                       w, h, p.quality_level, st, c->d_keys, (const int32_t*)nullptr);
     CR_HIP(f, hipGetLastError());
     const size_t chunks = (max_candidates(f) + 63) / 64;
     hipLaunchKernelGGL(k_corner_sort, dim3((unsigned)std::min<size_t>(std::max<size_t>(chunks, 1), kSortGrid)), dim3(CR_T), 0, f->stream,
                        c->d_keys, st, c->d_sorted);
     CR_HIP(f, hipGetLastError());
     hipLaunchKernelGGL(k_corner_select, dim3(1), dim3(kSelT), 0, f->stream, c->d_sorted, st, w, distance_gate(p.min_distance), p.max_corners,
-                       d_xy);
+                       d_xy, (const int32_t*)nullptr);
     CR_HIP(f, hipGetLastError());
     CR_HIP(f, hipMemcpyAsync(c->h_out, c->d_out, sizeof(CornerDev) + sizeof(float) * 2 * (size_t)p.max_corners, hipMemcpyDeviceToHost,
                              f->stream));
@@ -491,6 +493,51 @@ int device_corners(visfs_flow* f, CornerState* c, const uint8_t* px, const visfs
 }
 
 }  // namespace
+
+// ---------------------------------------------------------------- the resident caller's entry points (ba_tracker.hip)
+namespace flow {
+
+int corners_enqueue(visfs_flow* f, const uint8_t* px, double quality_level, double min_distance, const Disc* d_discs, const int32_t* d_hw,
+                    const int32_t* d_args, const int32_t** d_n_out, const float** d_xy) {
+    int rc = ensure_state(f);
+    if (rc != VISFS_BA_OK) return rc;
+    CornerState* c = f->corners;
+    c->valid = false;                          // the download hook reports staged calls only
+    const int w = f->w, h = f->h;
+    CornerDev* st = reinterpret_cast<CornerDev*>(c->d_out);
+    float* xy = reinterpret_cast<float*>(c->d_out + sizeof(CornerDev));
+    CR_HIP(f, hipMemsetAsync(c->d_out, 0, sizeof(CornerDev), f->stream));
+    hipLaunchKernelGGL(k_corner_response, dim3((w + CT_X - 1) / CT_X, (h + CT_Y - 1) / CT_Y), dim3(CR_T), 0, f->stream, px, w, h, d_discs, 0,
+                       d_hw, c->d_eig, c->d_mask, st, d_args);
+    CR_HIP(f, hipGetLastError());
+    hipLaunchKernelGGL(k_corner_candidates, dim3((unsigned)(((size_t)w * h + CR_T - 1) / CR_T)), dim3(CR_T), 0, f->stream, c->d_eig, c->d_mask,
+                       w, h, quality_level, st, c->d_keys, d_args);
+    CR_HIP(f, hipGetLastError());
+    const size_t chunks = (max_candidates(f) + 63) / 64;
+    hipLaunchKernelGGL(k_corner_sort, dim3((unsigned)std::min<size_t>(std::max<size_t>(chunks, 1), kSortGrid)), dim3(CR_T), 0, f->stream,
+                       c->d_keys, st, c->d_sorted);
+    CR_HIP(f, hipGetLastError());
+    hipLaunchKernelGGL(k_corner_select, dim3(1), dim3(kSelT), 0, f->stream, c->d_sorted, st, w, distance_gate(min_distance), 0, xy, d_args);
+    CR_HIP(f, hipGetLastError());
+    *d_n_out = &st->n_out;
+    *d_xy = xy;
+    return VISFS_BA_OK;
+}
+
+int corners_host(visfs_flow* f, const uint8_t* px, int32_t max_corners, double quality_level, double min_distance, const Disc* discs,
+                 int n_discs, const int32_t* hw, float* xy, int32_t* n_out) {
+    *n_out = 0;
+    if (max_corners <= 0) return VISFS_BA_OK;
+    const int rc = ensure_state(f);
+    if (rc != VISFS_BA_OK) return rc;
+    f->corners->valid = false;
+    visfs_corners_params p;
+    p.max_corners = max_corners; p.quality_level = quality_level; p.min_distance = min_distance;
+    host_corners(f, f->corners, px, p, discs, n_discs, hw, xy, n_out);
+    return VISFS_BA_OK;
+}
+
+}  // namespace flow
 
 // ====================================================================== exported C ABI
 extern "C" {
@@ -520,7 +567,7 @@ int visfs_flow_corners(visfs_flow* f, int32_t slot, int32_t image, const visfs_c
             rc = device_corners(f, c, f->dpx[s][image], *p, xy, n_out);
             if (rc != VISFS_BA_OK) return rc;
         } else {
-            host_corners(f, c, f->hpx[s][image].data(), *p, xy, n_out);
+            host_corners(f, c, f->hpx[s][image].data(), *p, c->discs.data(), (int)c->discs.size(), c->hw.data(), xy, n_out);
         }
         c->valid = true;
         return (int)VISFS_BA_OK;

@@ -81,6 +81,12 @@ inline void disc_halfwidth(int r, int32_t* hw) {
     }
 }
 
+// lrintf with the default rounding (half to even), kept within what the integer tests behind it can hold
+FLOW_HD int32_t round_centre(float v) {
+    const double r = rint((double)v);
+    return (int32_t)fmin(fmax(r, -1073741824.0), 1073741824.0);
+}
+
 FLOW_HD bool disc_covers(const Disc& d, const int32_t* hw, int x, int y) {
     int ay = y - d.cy;
     if (ay < 0) ay = -ay;
@@ -88,6 +94,17 @@ FLOW_HD bool disc_covers(const Disc& d, const int32_t* hw, int x, int y) {
     int ax = x - d.cx;
     if (ax < 0) ax = -ax;
     return ax <= hw[d.hw + ay];
+}
+
+// disc_covers without a branch: the table is read at a clamped row whatever the answer, so a loop over discs has no load that
+// waits for a comparison (hw: the table of this disc, hw[0 .. r])
+FLOW_HD bool disc_covers_flat(int cx, int cy, int r, const int32_t* hw, int x, int y) {
+    int ay = y - cy;
+    ay = ay < 0 ? -ay : ay;
+    int ax = x - cx;
+    ax = ax < 0 ? -ax : ax;
+    const int32_t half = hw[ay < r ? ay : r];
+    return ay <= r && ax <= half;
 }
 
 FLOW_HD bool masked(const Disc* discs, int n, const int32_t* hw, int x, int y) {

@@ -384,6 +384,7 @@ int visfs_flow_create(visfs_ba_handle* h, const visfs_flow_params* p, int32_t wi
 
 void visfs_flow_destroy(visfs_flow* f) {
     if (!f) return;
+    flow::tracker_release(f);
     flow::corners_release(f);
     flow::clahe_release(f);
     release(f);

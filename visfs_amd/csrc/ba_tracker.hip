@@ -1,0 +1,1014 @@
+// The resident front end (include/visfs_tracker.h): Tracker::pretreatment and Tracker::imageProcess of the
+// reference (corelib/src/Tracker.cpp:98-419) in one call, with the word table of the tracker kept next to the image pyramids.
+//
+// Two ways over the decisions of ba_tracker.hpp and the work items of ba_flow.hpp / ba_corners.hpp:
+//   * host restatement (trackers on objects of visfs_flow_create_host): every step in sequence on one core;
+//   * device: the table (id, left pixel, 3-D point, track count) and every intermediate list stay in HBM.  A call is one small
+//     upload (outlier ids, guess), the frame push, these launches on the stream of the owning handle, one copy of the output block
+//     and one synchronisation.  No launch waits for a value read back: counts travel through a control block in device memory, the
+//     grids are sized by what the host knows (the ids it returned last, max_features) and surplus workgroups leave at once.
+//       k_trk_pretreat  one workgroup: each row's id against the outlier list in LDS, order-preserving split into from-table and
+//                       blocked list (ballot + prefix over the wavefronts)                                          (:143-165)
+//       [bootstrap]     the corner kernels on the previous left image without a mask, k_trk_append, k_trk_stereo in its
+//                       forward-only, ungated, status-blind form for the 3-D points                                 (:179-230)
+//       k_trk_track     one wavefront per from-row: guess projection in fp64, lk_gated, the bounds test          (:237-274, :286)
+//       k_trk_reduce    one workgroup: compaction of the kept rows in row order: covisible output, kept count, LOST, the top-up's
+//                       corner budget                                                                               (:280-320)
+//       k_trk_discs     one workgroup: rank sort of the (count, row) keys, the serial draw decision of getMask 1024 discs at a time
+//                       (each against the raster so far in parallel; then wavefront after wavefront settles its 64 discs among
+//                       themselves through cover masks and the ones behind test against what it drew), the raster's Disc list
+//                       and its length                                                                              (:116-141)
+//       the corner kernels of ba_corners.hip on the current left image, disc count and budget read from device memory    (:327)
+//       k_trk_append    ids for the new corners, appended behind the kept rows                                      (:330-336)
+//       k_trk_stereo    one wavefront per row: lk_gated left -> right, bounds test, triangulate                     (:343-397)
+//       k_trk_finish    one workgroup: final compaction into the table, counts + 1, the output block's head        (:98-114, :414-417)
+#include "ba_tracker.hpp"
+#include "ba_flow_object.hpp"
+#include "../../include/visfs_tracker.h"
+
+#include <algorithm>
+#include <cstring>
+#include <new>
+#include <string>
+#include <unordered_set>
+#include <vector>
+
+using namespace flow;
+using namespace trk;
+
+struct visfs_tracker;
+
+namespace flow {
+struct TrackerState { std::vector<visfs_tracker*> list; };
+}
+
+namespace trk {
+
+constexpr int TK_T = 1024;                     // the one-workgroup kernels
+constexpr int TK_WAVES = TK_T / 64;
+
+struct Ctl {                                   // device words of a tracker
+    int32_t n_tab;                             // rows of the table (lives across calls)
+    int32_t n_from, n_blocked, n_kept, lost, n_list, n_new, n_rows;
+    int32_t corner_args[2];                    // the top-up: { raster discs, max_features - kept }
+    int32_t boot_args[2];                      // the bootstrap: { 0, max_features }
+    uint64_t next_id;                          // globalFeatureId_ (lives across calls)
+};
+
+struct Head {                                  // first words of the output block
+    int32_t flags, n_covis, n_new, n_words, n_blocked, pad;
+    uint64_t next_id;
+};
+
+struct InHead {                                // first words of the input block; the outlier ids follow
+    int32_t n_outliers, pad;
+};
+
+struct Out {                                   // the output block, one layout for the device, the pinned copy and the host twin
+    Head* head;
+    uint64_t* cov_id; float* cov_from; float* cov_xyz; float* cov_to;
+    uint64_t* new_id; float* new_xy;
+    uint64_t* w_id; float* w_l; float* w_r; float* w_xyz; int32_t* w_cnt;
+    uint64_t* blk_id;
+};
+
+struct Bufs {
+    Ctl* ctl;
+    const InHead* in; const uint64_t* outliers;
+    uint64_t* tab_id; float* tab_xy; float* tab_xyz; int32_t* tab_cnt;            // the table
+    uint64_t* from_id; float* from_xy; float* from_xyz; int32_t* from_cnt;        // the from-rows of a call
+    float* blk_xy;
+    float* guess; float* to; uint8_t* lk_st; uint8_t* inb;                        // per from-row
+    uint64_t* row_id; float* row_xy; int32_t* row_cnt;                            // kept + new rows
+    float* row_rxy; float* row_xyz; uint8_t* row_st; uint8_t* row_ok;
+    visfs_corners_disc* list; uint32_t* packed; uint8_t* drawn; Disc* raster;     // getMask's discs in draw order; the raster's
+    const int32_t* hw;                                                            // half-widths: min_distance, then min_distance / 2
+    Out o;
+};
+
+struct Carver {
+    char* base;
+    size_t off = 0;
+    template <class T> T* take(size_t n) {
+        off = (off + 255) & ~size_t(255);
+        T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+        off += n * sizeof(T);
+        return p;
+    }
+};
+
+size_t carve_out(char* base, size_t M, Out& o) {
+    Carver c{ base };
+    o.head = c.take<Head>(1);
+    o.cov_id = c.take<uint64_t>(M); o.cov_from = c.take<float>(2 * M); o.cov_xyz = c.take<float>(3 * M); o.cov_to = c.take<float>(2 * M);
+    o.new_id = c.take<uint64_t>(M); o.new_xy = c.take<float>(2 * M);
+    o.w_id = c.take<uint64_t>(M); o.w_l = c.take<float>(2 * M); o.w_r = c.take<float>(2 * M); o.w_xyz = c.take<float>(3 * M);
+    o.w_cnt = c.take<int32_t>(M);
+    o.blk_id = c.take<uint64_t>(M);
+    return (c.off + 255) & ~size_t(255);
+}
+
+size_t carve_work(char* base, size_t M, size_t hw_len, Bufs& b, int32_t** hw) {
+    Carver c{ base };
+    b.ctl = c.take<Ctl>(1);
+    b.tab_id = c.take<uint64_t>(M); b.tab_xy = c.take<float>(2 * M); b.tab_xyz = c.take<float>(3 * M); b.tab_cnt = c.take<int32_t>(M);
+    b.from_id = c.take<uint64_t>(M); b.from_xy = c.take<float>(2 * M); b.from_xyz = c.take<float>(3 * M); b.from_cnt = c.take<int32_t>(M);
+    b.blk_xy = c.take<float>(2 * M);
+    b.guess = c.take<float>(2 * M); b.to = c.take<float>(2 * M); b.lk_st = c.take<uint8_t>(M); b.inb = c.take<uint8_t>(M);
+    b.row_id = c.take<uint64_t>(M); b.row_xy = c.take<float>(2 * M); b.row_cnt = c.take<int32_t>(M);
+    b.row_rxy = c.take<float>(2 * M); b.row_xyz = c.take<float>(3 * M); b.row_st = c.take<uint8_t>(M); b.row_ok = c.take<uint8_t>(M);
+    b.list = c.take<visfs_corners_disc>(2 * M); b.packed = c.take<uint32_t>(2 * M); b.drawn = c.take<uint8_t>(2 * M);
+    b.raster = c.take<Disc>(2 * M);
+    *hw = c.take<int32_t>(hw_len);
+    b.hw = *hw;
+    return (c.off + 255) & ~size_t(255);
+}
+
+struct Shape { int32_t M, w, h, r_track, r_blocked, min_inliers; };
+
+// ---------------------------------------------------------------- kernels
+// where a flagged thread's item goes in an order-preserving compaction of the workgroup's items, and how many there are
+__device__ inline int wg_offset(bool flag, int32_t* wcount, int& total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long b = __ballot(flag);
+    if (lane == 0) wcount[wave] = __popcll(b);
+    __syncthreads();
+    int before = 0;
+    total = 0;
+#pragma unroll
+    for (int k = 0; k < TK_WAVES; ++k) {
+        const int c = wcount[k];
+        if (k < wave) before += c;
+        total += c;
+    }
+    __syncthreads();
+    return before + __popcll(b & ((1ull << lane) - 1ull));
+}
+
+__global__ __launch_bounds__(TK_T) void k_trk_pretreat(Bufs B, Shape S) {
+    __shared__ uint64_t s_out[kMaxOutliers];
+    __shared__ int32_t wcount[TK_WAVES];
+    const int tid = threadIdx.x;
+    const int n = min(B.ctl->n_tab, S.M);
+    const int n_o = min(max(B.in->n_outliers, 0), kMaxOutliers);
+    for (int k = tid; k < n_o; k += TK_T) s_out[k] = B.outliers[k];
+    __syncthreads();
+    int n_keep = 0, n_blk = 0;
+    for (int c0 = 0; c0 < n; c0 += TK_T) {
+        const int i = c0 + tid;
+        const bool valid = i < n;
+        const uint64_t id = valid ? B.tab_id[i] : 0ull;
+        bool hit = false;
+        if (valid)
+            for (int k = 0; k < n_o; ++k) hit = hit || s_out[k] == id;
+        int tk, tb;
+        const int ok = wg_offset(valid && !hit, wcount, tk);
+        const int ob = wg_offset(hit, wcount, tb);
+        if (valid && !hit) {
+            const int o = n_keep + ok;
+            B.from_id[o] = id;
+            B.from_xy[2 * o] = B.tab_xy[2 * i]; B.from_xy[2 * o + 1] = B.tab_xy[2 * i + 1];
+            B.from_xyz[3 * o] = B.tab_xyz[3 * i]; B.from_xyz[3 * o + 1] = B.tab_xyz[3 * i + 1]; B.from_xyz[3 * o + 2] = B.tab_xyz[3 * i + 2];
+            B.from_cnt[o] = B.tab_cnt[i];
+        }
+        if (hit) {
+            const int o = n_blk + ob;
+            B.o.blk_id[o] = id;
+            B.blk_xy[2 * o] = B.tab_xy[2 * i]; B.blk_xy[2 * o + 1] = B.tab_xy[2 * i + 1];
+        }
+        n_keep += tk;
+        n_blk += tb;
+    }
+    if (tid == 0) {
+        Ctl* c = B.ctl;
+        c->n_from = n_keep; c->n_blocked = n_blk;
+        c->n_kept = 0; c->lost = 0; c->n_list = 0; c->n_new = 0; c->n_rows = 0;
+        c->corner_args[0] = 0; c->corner_args[1] = 0;
+        c->boot_args[0] = 0; c->boot_args[1] = S.M;
+    }
+}
+
+// The corners of a selection get ids next_id, next_id + 1, ... strongest first.  BOOT: they are the from-rows of this call, without a
+// track count (Tracker.cpp:181-189).  Otherwise they follow the kept rows and are this frame's newly extracted words (:330-336).
+template <bool BOOT>
+__global__ __launch_bounds__(TK_T) void k_trk_append(Bufs B, Shape S, const int32_t* n_out, const float* xy) {
+    Ctl* c = B.ctl;
+    const int tid = threadIdx.x;
+    const int base = BOOT ? 0 : c->n_kept;
+    int n = (!BOOT && c->lost) ? 0 : *n_out;
+    n = max(min(n, S.M - base), 0);
+    const uint64_t id0 = c->next_id;
+    for (int a = tid; a < n; a += TK_T) {
+        const uint64_t id = id0 + (uint64_t)a;
+        const float x = xy[2 * a], y = xy[2 * a + 1];
+        if (BOOT) {
+            B.from_id[a] = id; B.from_xy[2 * a] = x; B.from_xy[2 * a + 1] = y; B.from_cnt[a] = 0;
+        } else {
+            const int r = base + a;
+            B.row_id[r] = id; B.row_xy[2 * r] = x; B.row_xy[2 * r + 1] = y; B.row_cnt[r] = 0;
+            B.o.new_id[a] = id; B.o.new_xy[2 * a] = x; B.o.new_xy[2 * a + 1] = y;
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        c->next_id = id0 + (uint64_t)n;
+        if (BOOT) c->n_from = n;
+        else { c->n_new = n; c->n_rows = base + n; }
+    }
+}
+
+struct WaveCells {                             // as in ba_flow.hip: cell s * 64 + lane in slot s, int64 butterfly
+    static constexpr int kSlots = kLaneSlots;
+    using acc_t = int32_t;
+    int lane;
+    __device__ int cell(int s) const { return s * 64 + lane; }
+    __device__ int64_t total(acc_t v) const {
+        long long x = v;
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) x += __shfl_xor(x, o, 64);
+        return x;
+    }
+};
+
+template <bool BACK>
+__global__ __launch_bounds__(64) void k_trk_track(Bufs B, Shape S, Image I, Image J, LkParams prm, Layout lay, Guess g, int has_guess, float gate) {
+    const int p = blockIdx.x;
+    if (p >= min(B.ctl->n_from, S.M)) return;
+    WaveCells pol{ (int)threadIdx.x };
+    const float ptx = B.from_xy[2 * p], pty = B.from_xy[2 * p + 1];
+    float inx = ptx, iny = pty;
+    if (has_guess) {
+        const float P[3] = { B.from_xyz[3 * p], B.from_xyz[3 * p + 1], B.from_xyz[3 * p + 2] };
+        project_guess(g, P, inx, iny);
+    }
+    float tox, toy, err;
+    uint8_t st;
+    lk_gated(pol, prm, lay, I, J, ptx, pty, has_guess != 0, inx, iny, BACK, gate, tox, toy, st, err);
+    if (threadIdx.x != 0) return;
+    B.guess[2 * p] = inx; B.guess[2 * p + 1] = iny;
+    B.to[2 * p] = tox; B.to[2 * p + 1] = toy;
+    B.lk_st[p] = st;
+    B.inb[p] = (in_bounds(tox, S.w) && in_bounds(toy, S.h)) ? 1 : 0;
+}
+
+__global__ __launch_bounds__(TK_T) void k_trk_reduce(Bufs B, Shape S) {
+    __shared__ int32_t wcount[TK_WAVES];
+    const int tid = threadIdx.x;
+    const int n = min(B.ctl->n_from, S.M);
+    int kept = 0;
+    for (int c0 = 0; c0 < n; c0 += TK_T) {
+        const int i = c0 + tid;
+        const bool keep = i < n && kept_row(B.lk_st[i], B.to[2 * i], B.to[2 * i + 1], S.w, S.h);
+        int total;
+        const int o = kept + wg_offset(keep, wcount, total);
+        if (keep) {
+            const uint64_t id = B.from_id[i];
+            const float tx = B.to[2 * i], ty = B.to[2 * i + 1];
+            B.o.cov_id[o] = id;
+            B.o.cov_from[2 * o] = B.from_xy[2 * i]; B.o.cov_from[2 * o + 1] = B.from_xy[2 * i + 1];
+            B.o.cov_xyz[3 * o] = B.from_xyz[3 * i]; B.o.cov_xyz[3 * o + 1] = B.from_xyz[3 * i + 1]; B.o.cov_xyz[3 * o + 2] = B.from_xyz[3 * i + 2];
+            B.o.cov_to[2 * o] = tx; B.o.cov_to[2 * o + 1] = ty;
+            B.row_id[o] = id; B.row_xy[2 * o] = tx; B.row_xy[2 * o + 1] = ty; B.row_cnt[o] = B.from_cnt[i];
+        }
+        kept += total;
+    }
+    if (tid == 0) {
+        Ctl* c = B.ctl;
+        const bool lost = kept < S.min_inliers;                                   // Tracker.cpp:303
+        c->n_kept = kept; c->n_rows = lost ? 0 : kept; c->lost = lost ? 1 : 0;
+        c->corner_args[1] = lost ? 0 : S.M - kept;                                // backUpCornersCnt (:324)
+    }
+}
+
+constexpr int kHwLds = 2048;                   // half-width entries kept in LDS (both radii together); larger tables are read in place
+
+// does the packed disc p cover the pixel (x, y)?  HW is the half-width storage (LDS or global), the two tables one behind the other
+template <class HW>
+__device__ inline bool packed_covers(uint32_t p, const Shape& S, HW hw, int x, int y) {
+    const int kind = (int)(p >> 30);
+    return disc_covers_flat((int)(p & 0x7fffu), (int)((p >> 15) & 0x7fffu), kind ? S.r_blocked : S.r_track, hw + (kind ? S.r_track + 1 : 0), x, y);
+}
+
+// The draw decision in list order (Tracker.cpp:131-138).  Thread t of a chunk owns disc c0 + t.  Every disc is first tested against
+// the raster of the chunks before; then the wavefronts take their turns: wavefront k settles its 64 discs among themselves and
+// appends the drawn ones, and the wavefronts behind it test theirs against what it appended.  No loop over discs leaves early, so
+// its reads do not wait for each other.
+template <class HW>
+__device__ inline int draw_decision(const Bufs& B, const Shape& S, HW hw, int n_list, uint32_t* s_buf, int32_t* s_nr) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int nr = 0, round = 0;
+    for (int c0 = 0; c0 < n_list; c0 += TK_T) {
+        const int i = c0 + tid;
+        const bool valid = i < n_list;
+        const uint32_t q = valid ? B.packed[i] : 0u;
+        const Disc dq = unpack_disc(q, S.r_track, S.r_blocked);
+        const bool inside = centre_inside(dq.cx, dq.cy, S.w, S.h);
+        bool alive = valid;
+        if (valid && inside) {
+            bool covered = false;
+#pragma unroll 8
+            for (int a = 0; a < nr; ++a) covered |= packed_covers(s_buf[a], S, hw, dq.cx, dq.cy);
+            alive = !covered;
+        }
+        const int waves = (min(TK_T, n_list - c0) + 63) / 64;
+        for (int k = 0; k < waves; ++k, ++round) {
+            if (wave == k) {
+                // which earlier discs of this wavefront would cover my centre, should they be drawn
+                const unsigned long long live = __ballot(alive);
+                unsigned long long cover = 0;
+#pragma unroll 8
+                for (int j = 0; j < 63; ++j) {
+                    const uint32_t qj = __shfl(q, j, 64);
+                    if (packed_covers(qj, S, hw, dq.cx, dq.cy)) cover |= 1ull << j;
+                }
+                cover &= live & ((1ull << lane) - 1ull);
+                if (!(alive && inside)) cover = 0;
+                // a disc nothing could cover is drawn; the others are settled in order, each once all before it are
+                unsigned long long drawn = __ballot(alive && cover == 0);
+                unsigned long long open = __ballot(alive && cover != 0);
+                while (open) {
+                    const int f = __ffsll(open) - 1;
+                    const unsigned long long cf = __shfl(cover, f, 64);
+                    if ((cf & drawn) == 0) drawn |= 1ull << f;
+                    open &= open - 1;
+                }
+                const bool mine = ((drawn >> lane) & 1ull) != 0;
+                const bool raster = mine && touches_image(dq, S.w, S.h);
+                const unsigned long long rb = __ballot(raster);
+                if (valid) B.drawn[i] = mine ? 1 : 0;
+                if (raster) {
+                    const int o = nr + __popcll(rb & ((1ull << lane) - 1ull));
+                    s_buf[o] = q;
+                    B.raster[o] = dq;
+                }
+                if (lane == 0) s_nr[round & 1] = nr + __popcll(rb);
+            }
+            __syncthreads();
+            const int nr_new = s_nr[round & 1];
+            if (wave > k && alive && inside) {
+                bool covered = false;
+#pragma unroll 8
+                for (int a = nr; a < nr_new; ++a) covered |= packed_covers(s_buf[a], S, hw, dq.cx, dq.cy);
+                alive = !covered;
+            }
+            nr = nr_new;
+        }
+        __syncthreads();
+    }
+    return nr;
+}
+
+__global__ __launch_bounds__(TK_T) void k_trk_discs(Bufs B, Shape S) {
+    __shared__ uint32_t s_buf[2 * kMaxFeatures];       // the counts for the rank sort, then the raster's discs packed
+    __shared__ int32_t s_hw[kHwLds];
+    __shared__ int32_t wcount[TK_WAVES];
+    __shared__ int32_t s_nr[2];
+    Ctl* c = B.ctl;
+    const int tid = threadIdx.x;
+    if (c->lost || c->corner_args[1] <= 0) return;     // no mask is made (Tracker.cpp:303, :325); n_list and the raster count are 0
+    const int n_kept = min(c->n_kept, S.M), n_blk = min(c->n_blocked, S.M);
+    const int hw_len = S.r_track + S.r_blocked + 2;
+    const bool hw_in_lds = hw_len <= kHwLds;
+    if (hw_in_lds)
+        for (int i = tid; i < hw_len; i += TK_T) s_hw[i] = B.hw[i];
+    // ---- the tracked words that have a count, by count descending, equal counts in id order
+    int32_t* s_cnt = reinterpret_cast<int32_t*>(s_buf);
+    for (int i = tid; i < n_kept; i += TK_T) s_cnt[i] = B.row_cnt[i];
+    __syncthreads();
+    int n_counted = 0;
+    for (int c0 = 0; c0 < n_kept; c0 += TK_T) {
+        const int i = c0 + tid;
+        const int32_t mine = i < n_kept ? s_cnt[i] : 0;
+        int total;
+        (void)wg_offset(mine > 0, wcount, total);
+        n_counted += total;
+        if (mine > 0) {
+            int rank = 0;
+#pragma unroll 8
+            for (int j = 0; j < n_kept; ++j) {
+                const int32_t other = s_cnt[j];
+                rank += (other > 0 && drawn_before(other, j, mine, i)) ? 1 : 0;
+            }
+            const float x = B.row_xy[2 * i], y = B.row_xy[2 * i + 1];
+            B.list[rank] = visfs_corners_disc{ x, y, S.r_track };
+            B.packed[rank] = pack_disc(round_centre(x), round_centre(y), 0);
+        }
+    }
+    for (int b = tid; b < n_blk; b += TK_T) {                                     // then the blocked words (:135)
+        const float x = B.blk_xy[2 * b], y = B.blk_xy[2 * b + 1];
+        const int o = n_counted + b;
+        B.list[o] = visfs_corners_disc{ x, y, S.r_blocked };
+        B.packed[o] = pack_disc(round_centre(x), round_centre(y), 1);
+    }
+    const int n_list = n_counted + n_blk;
+    __threadfence_block();
+    __syncthreads();
+    const int nr = hw_in_lds ? draw_decision(B, S, (const int32_t*)s_hw, n_list, s_buf, s_nr) : draw_decision(B, S, B.hw, n_list, s_buf, s_nr);
+    if (tid == 0) { c->n_list = n_list; c->corner_args[0] = nr; }
+}
+
+// BOOT: the 3-D points of bootstrapped words: one forward pass previous left -> previous right, no reverse pass, no gate, the status
+// not looked at (Tracker.cpp:207-219).  Otherwise: the stereo pass of the frame with its gate, the bounds test of :376 and the
+// finite test of :390.
+template <bool BACK, bool BOOT>
+__global__ __launch_bounds__(64) void k_trk_stereo(Bufs B, Shape S, Image I, Image J, LkParams prm, Layout lay, Camera cam, float gate) {
+    const int p = blockIdx.x;
+    const Ctl* c = B.ctl;
+    const int n = BOOT ? c->n_from : (c->lost ? 0 : c->n_rows);
+    if (p >= min(n, S.M)) return;
+    WaveCells pol{ (int)threadIdx.x };
+    const float* pts = BOOT ? B.from_xy : B.row_xy;
+    const float ptx = pts[2 * p], pty = pts[2 * p + 1];
+    float tox, toy, err;
+    uint8_t st;
+    lk_gated(pol, prm, lay, I, J, ptx, pty, false, 0.0f, 0.0f, BACK, gate, tox, toy, st, err);
+    if (threadIdx.x != 0) return;
+    float xyz[3] = { __builtin_nanf(""), __builtin_nanf(""), __builtin_nanf("") };
+    if (BOOT) {
+        triangulate(cam, ptx, pty, tox, xyz);
+        B.from_xyz[3 * p] = xyz[0]; B.from_xyz[3 * p + 1] = xyz[1]; B.from_xyz[3 * p + 2] = xyz[2];
+    } else {
+        if (st) triangulate(cam, ptx, pty, tox, xyz);
+        B.row_rxy[2 * p] = tox; B.row_rxy[2 * p + 1] = toy;
+        B.row_xyz[3 * p] = xyz[0]; B.row_xyz[3 * p + 1] = xyz[1]; B.row_xyz[3 * p + 2] = xyz[2];
+        B.row_st[p] = st;
+        B.row_ok[p] = stereo_row(st, tox, toy, xyz, S.w, S.h) ? 1 : 0;
+    }
+}
+
+__global__ __launch_bounds__(TK_T) void k_trk_finish(Bufs B, Shape S, int boot) {
+    __shared__ int32_t wcount[TK_WAVES];
+    Ctl* c = B.ctl;
+    const int tid = threadIdx.x;
+    const bool lost = c->lost != 0;
+    const int n = lost ? 0 : min(c->n_rows, S.M);
+    int words = 0;
+    for (int c0 = 0; c0 < n; c0 += TK_T) {
+        const int i = c0 + tid;
+        const bool keep = i < n && B.row_ok[i] != 0;
+        int total;
+        const int o = words + wg_offset(keep, wcount, total);
+        if (keep) {
+            const uint64_t id = B.row_id[i];
+            const int32_t cnt = B.row_cnt[i] + 1;                                 // updateTrackCounter (:98-114)
+            B.tab_id[o] = id; B.o.w_id[o] = id;
+            B.tab_cnt[o] = cnt; B.o.w_cnt[o] = cnt;
+            for (int k = 0; k < 2; ++k) {
+                B.tab_xy[2 * o + k] = B.row_xy[2 * i + k]; B.o.w_l[2 * o + k] = B.row_xy[2 * i + k];
+                B.o.w_r[2 * o + k] = B.row_rxy[2 * i + k];
+            }
+            for (int k = 0; k < 3; ++k) { B.tab_xyz[3 * o + k] = B.row_xyz[3 * i + k]; B.o.w_xyz[3 * o + k] = B.row_xyz[3 * i + k]; }
+        }
+        words += total;
+    }
+    if (tid == 0) {
+        c->n_tab = words;
+        Head hd;
+        hd.flags = lost ? kLost : (boot ? kBootstrapped : 0);
+        hd.n_covis = lost ? 0 : c->n_kept;
+        hd.n_new = lost ? 0 : c->n_new;
+        hd.n_words = words;
+        hd.n_blocked = lost ? 0 : c->n_blocked;
+        hd.pad = 0;
+        hd.next_id = c->next_id;
+        *B.o.head = hd;
+    }
+}
+
+}  // namespace trk
+
+// ---------------------------------------------------------------- the object
+struct visfs_tracker {
+    visfs_flow* f = nullptr;                   // nullptr once the flow object is gone
+    visfs_tracker_params prm{};
+    visfs_flow_camera cam{};
+    Shape S{};
+    std::string err;
+    int seen_frames = 0;                       // f->frames after this tracker's last push
+    bool have_call = false;                    // the download hook has something to report
+    bool boot_last = false;
+    std::vector<uint64_t> ids;                 // the table's ids as the last call returned them
+    std::vector<int32_t> hw;                   // half-widths of min_distance, then of min_distance / 2
+
+    // host restatement: the same blocks in host memory
+    std::vector<char> h_work, h_outblk, h_inblk;
+    // device
+    char* d_work = nullptr; char* d_out = nullptr; char* d_in = nullptr;
+    char* p_out = nullptr; char* p_in = nullptr;                                  // pinned
+    size_t out_bytes = 0, in_bytes = 0;
+
+    Bufs B{};                                  // where the kernels (or the host steps) work
+    Out R{};                                   // where the caller reads: the pinned copy, or the host twin's block itself
+};
+
+namespace {
+
+int fail(visfs_tracker* t, int rc, const std::string& why) { t->err = why; return rc; }
+#define TK_HIP(t, expr)                                                                                   \
+    do {                                                                                                  \
+        hipError_t e_ = (expr);                                                                           \
+        if (e_ != hipSuccess) return fail((t), VISFS_BA_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+template <class F> int guarded_tk(visfs_tracker* t, F&& fn) noexcept {
+    try { return fn(); }
+    catch (const std::bad_alloc&) { if (t) t->err = "out of host memory"; return VISFS_BA_ERR_DEVICE; }
+    catch (...) { if (t) t->err = "unexpected exception"; return VISFS_BA_ERR_DEVICE; }
+}
+
+Camera make_camera(const visfs_flow_params& p, const visfs_flow_camera& c) {
+    Camera k;
+    k.fx = c.fx; k.fy = c.fy; k.cx = c.cx; k.cy = c.cy; k.cx_right = c.cx_right; k.baseline = c.baseline;
+    k.min_depth = p.min_depth; k.max_depth = p.max_depth;
+    for (int i = 0; i < 12; ++i) k.T[i] = c.Tir[i];
+    return k;
+}
+
+void free_device(visfs_tracker* t) {
+    visfs_flow* f = t->f;
+    if (!f || !f->device) return;
+    (void)hipSetDevice(f->dev);
+    if (f->stream) (void)hipStreamSynchronize(f->stream);
+    if (t->d_work) (void)hipFree(t->d_work);
+    if (t->d_out) (void)hipFree(t->d_out);
+    if (t->d_in) (void)hipFree(t->d_in);
+    if (t->p_out) (void)hipHostFree(t->p_out);
+    if (t->p_in) (void)hipHostFree(t->p_in);
+    t->d_work = t->d_out = t->d_in = t->p_out = t->p_in = nullptr;
+}
+
+int allocate(visfs_tracker* t) {
+    visfs_flow* f = t->f;
+    const size_t M = (size_t)t->S.M;
+    Bufs& B = t->B;
+    int32_t* hw = nullptr;
+    const size_t work_bytes = carve_work(nullptr, M, t->hw.size(), B, &hw);
+    t->out_bytes = carve_out(nullptr, M, B.o);
+    t->in_bytes = (sizeof(InHead) + sizeof(uint64_t) * kMaxOutliers + 255) & ~size_t(255);
+    if (!f->device) {
+        t->h_work.assign(work_bytes, 0); t->h_outblk.assign(t->out_bytes, 0); t->h_inblk.assign(t->in_bytes, 0);
+        carve_work(t->h_work.data(), M, t->hw.size(), B, &hw);
+        carve_out(t->h_outblk.data(), M, B.o);
+        std::memcpy(hw, t->hw.data(), t->hw.size() * sizeof(int32_t));
+        B.in = reinterpret_cast<const InHead*>(t->h_inblk.data());
+        B.outliers = reinterpret_cast<const uint64_t*>(t->h_inblk.data() + sizeof(InHead));
+        t->R = B.o;
+        return VISFS_BA_OK;
+    }
+    TK_HIP(t, hipSetDevice(f->dev));
+    TK_HIP(t, hipMalloc(reinterpret_cast<void**>(&t->d_work), work_bytes));
+    TK_HIP(t, hipMalloc(reinterpret_cast<void**>(&t->d_out), t->out_bytes));
+    TK_HIP(t, hipMalloc(reinterpret_cast<void**>(&t->d_in), t->in_bytes));
+    TK_HIP(t, hipHostMalloc(reinterpret_cast<void**>(&t->p_out), t->out_bytes, hipHostMallocDefault));
+    TK_HIP(t, hipHostMalloc(reinterpret_cast<void**>(&t->p_in), t->in_bytes, hipHostMallocDefault));
+    carve_work(t->d_work, M, t->hw.size(), B, &hw);
+    carve_out(t->d_out, M, B.o);
+    carve_out(t->p_out, M, t->R);
+    B.in = reinterpret_cast<const InHead*>(t->d_in);
+    B.outliers = reinterpret_cast<const uint64_t*>(t->d_in + sizeof(InHead));
+    std::memset(t->p_out, 0, t->out_bytes);
+    TK_HIP(t, hipMemsetAsync(t->d_work, 0, work_bytes, f->stream));
+    TK_HIP(t, hipMemsetAsync(t->d_out, 0, t->out_bytes, f->stream));
+    TK_HIP(t, hipMemcpyAsync(hw, t->hw.data(), t->hw.size() * sizeof(int32_t), hipMemcpyHostToDevice, f->stream));
+    TK_HIP(t, hipStreamSynchronize(f->stream));                        // t->hw may move; nothing else waits here
+    return VISFS_BA_OK;
+}
+
+int check_params(const visfs_tracker_params* p, const visfs_flow_camera* cam, const char** why) {
+    if (p->max_features < 1) { *why = "max_features must be at least 1"; return VISFS_BA_ERR_BAD_ARGUMENT; }
+    if (p->max_features > kMaxFeatures) { *why = "max_features must not exceed 4096"; return VISFS_BA_ERR_UNSUPPORTED; }
+    if (!std::isfinite(p->quality_level) || !(p->quality_level > 0.0)) { *why = "quality_level must be finite and positive"; return VISFS_BA_ERR_BAD_ARGUMENT; }
+    if (p->min_distance < 0) { *why = "min_distance must not be negative"; return VISFS_BA_ERR_BAD_ARGUMENT; }
+    if (p->min_distance > kMaxRadius) { *why = "min_distance must not exceed 32768"; return VISFS_BA_ERR_UNSUPPORTED; }
+    if (p->min_inliers < 0) { *why = "min_inliers must not be negative"; return VISFS_BA_ERR_BAD_ARGUMENT; }
+    for (int i = 0; i < 12; ++i)
+        if (!std::isfinite(cam->Tir[i])) { *why = "Tir is not finite"; return VISFS_BA_ERR_BAD_ARGUMENT; }
+    return VISFS_BA_OK;
+}
+
+// ---------------------------------------------------------------- host restatement: the kernels' steps on one core
+void host_pretreat(visfs_tracker* t) {
+    Bufs& B = t->B;
+    Ctl* c = B.ctl;
+    const std::unordered_set<uint64_t> out(B.outliers, B.outliers + B.in->n_outliers);
+    int nk = 0, nb = 0;
+    for (int i = 0; i < c->n_tab; ++i) {
+        const uint64_t id = B.tab_id[i];
+        if (out.count(id)) {
+            B.o.blk_id[nb] = id; B.blk_xy[2 * nb] = B.tab_xy[2 * i]; B.blk_xy[2 * nb + 1] = B.tab_xy[2 * i + 1];
+            ++nb;
+        } else {
+            B.from_id[nk] = id; B.from_cnt[nk] = B.tab_cnt[i];
+            for (int k = 0; k < 2; ++k) B.from_xy[2 * nk + k] = B.tab_xy[2 * i + k];
+            for (int k = 0; k < 3; ++k) B.from_xyz[3 * nk + k] = B.tab_xyz[3 * i + k];
+            ++nk;
+        }
+    }
+    c->n_from = nk; c->n_blocked = nb;
+    c->n_kept = 0; c->lost = 0; c->n_list = 0; c->n_new = 0; c->n_rows = 0;
+    c->corner_args[0] = c->corner_args[1] = 0;
+}
+
+Image host_image(const visfs_flow* f, int slot, int image) { return Image{ f->hpx[slot][image].data(), f->hder[slot][image].data() }; }
+
+int host_bootstrap(visfs_tracker* t) {
+    visfs_flow* f = t->f;
+    Bufs& B = t->B;
+    Ctl* c = B.ctl;
+    const int prev = 1 - f->cur;
+    std::vector<float> xy(2 * (size_t)t->S.M);
+    int32_t n = 0;
+    const int rc = corners_host(f, f->hpx[prev][0].data(), t->S.M, t->prm.quality_level, (double)t->prm.min_distance, nullptr, 0, nullptr,
+                                xy.data(), &n);
+    if (rc != VISFS_BA_OK) return fail(t, rc, f->err);
+    const Camera cam = make_camera(f->prm, t->cam);
+    const Image I = host_image(f, prev, 0), J = host_image(f, prev, 1);
+    const HostCells pol;
+    for (int a = 0; a < n; ++a) {
+        B.from_id[a] = c->next_id + (uint64_t)a; B.from_cnt[a] = 0;
+        B.from_xy[2 * a] = xy[2 * a]; B.from_xy[2 * a + 1] = xy[2 * a + 1];
+        float tx, ty, e;
+        uint8_t st;
+        lk_gated(pol, f->lk, f->lay, I, J, xy[2 * a], xy[2 * a + 1], false, 0.0f, 0.0f, false, 0.0f, tx, ty, st, e);
+        triangulate(cam, xy[2 * a], xy[2 * a + 1], tx, B.from_xyz + 3 * a);
+    }
+    c->next_id += (uint64_t)n;
+    c->n_from = n;
+    return VISFS_BA_OK;
+}
+
+void host_track_reduce(visfs_tracker* t, const Guess* g) {
+    visfs_flow* f = t->f;
+    Bufs& B = t->B;
+    Ctl* c = B.ctl;
+    const Shape& S = t->S;
+    const Image I = host_image(f, 1 - f->cur, 0), J = host_image(f, f->cur, 0);
+    const HostCells pol;
+    int kept = 0;
+    for (int p = 0; p < c->n_from; ++p) {
+        const float ptx = B.from_xy[2 * p], pty = B.from_xy[2 * p + 1];
+        float inx = ptx, iny = pty;
+        if (g) project_guess(*g, B.from_xyz + 3 * p, inx, iny);
+        float tx, ty, e;
+        uint8_t st;
+        lk_gated(pol, f->lk, f->lay, I, J, ptx, pty, g != nullptr, inx, iny, f->prm.flow_back != 0, f->prm.back_gate_track, tx, ty, st, e);
+        B.guess[2 * p] = inx; B.guess[2 * p + 1] = iny;
+        B.to[2 * p] = tx; B.to[2 * p + 1] = ty;
+        B.lk_st[p] = st;
+        B.inb[p] = (in_bounds(tx, S.w) && in_bounds(ty, S.h)) ? 1 : 0;
+        if (!kept_row(st, tx, ty, S.w, S.h)) continue;
+        const int o = kept++;
+        B.o.cov_id[o] = B.from_id[p];
+        for (int k = 0; k < 2; ++k) B.o.cov_from[2 * o + k] = B.from_xy[2 * p + k];
+        for (int k = 0; k < 3; ++k) B.o.cov_xyz[3 * o + k] = B.from_xyz[3 * p + k];
+        B.o.cov_to[2 * o] = tx; B.o.cov_to[2 * o + 1] = ty;
+        B.row_id[o] = B.from_id[p]; B.row_xy[2 * o] = tx; B.row_xy[2 * o + 1] = ty; B.row_cnt[o] = B.from_cnt[p];
+    }
+    const bool lost = kept < S.min_inliers;
+    c->n_kept = kept; c->n_rows = lost ? 0 : kept; c->lost = lost ? 1 : 0;
+    c->corner_args[1] = lost ? 0 : S.M - kept;
+}
+
+void host_discs(visfs_tracker* t) {
+    Bufs& B = t->B;
+    Ctl* c = B.ctl;
+    const Shape& S = t->S;
+    if (c->lost || c->corner_args[1] <= 0) return;
+    std::vector<int32_t> order;
+    for (int i = 0; i < c->n_kept; ++i)
+        if (B.row_cnt[i] > 0) order.push_back(i);
+    std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return drawn_before(B.row_cnt[a], a, B.row_cnt[b], b); });
+    int n = 0;
+    for (int32_t i : order) { B.list[n] = visfs_corners_disc{ B.row_xy[2 * i], B.row_xy[2 * i + 1], S.r_track }; B.packed[n++] = 0; }
+    for (int b = 0; b < c->n_blocked; ++b) { B.list[n] = visfs_corners_disc{ B.blk_xy[2 * b], B.blk_xy[2 * b + 1], S.r_blocked }; B.packed[n++] = 1; }
+    int nr = 0;
+    for (int i = 0; i < n; ++i) {
+        const int kind = (int)B.packed[i];
+        const Disc d{ round_centre(B.list[i].x), round_centre(B.list[i].y), kind ? S.r_blocked : S.r_track, kind ? S.r_track + 1 : 0 };
+        B.drawn[i] = 0;
+        if (centre_inside(d.cx, d.cy, S.w, S.h) && masked(B.raster, nr, B.hw, d.cx, d.cy)) continue;
+        B.drawn[i] = 1;
+        if (touches_image(d, S.w, S.h)) B.raster[nr++] = d;
+    }
+    c->n_list = n; c->corner_args[0] = nr;
+}
+
+int host_topup_stereo_finish(visfs_tracker* t, bool boot) {
+    visfs_flow* f = t->f;
+    Bufs& B = t->B;
+    Ctl* c = B.ctl;
+    const Shape& S = t->S;
+    if (!c->lost) {
+        std::vector<float> xy(2 * (size_t)S.M);
+        int32_t n = 0;
+        const int rc = corners_host(f, f->hpx[f->cur][0].data(), c->corner_args[1], t->prm.quality_level, (double)t->prm.min_distance, B.raster,
+                                    c->corner_args[0], B.hw, xy.data(), &n);
+        if (rc != VISFS_BA_OK) return fail(t, rc, f->err);
+        for (int a = 0; a < n; ++a) {
+            const int r = c->n_kept + a;
+            const uint64_t id = c->next_id + (uint64_t)a;
+            B.row_id[r] = id; B.row_xy[2 * r] = xy[2 * a]; B.row_xy[2 * r + 1] = xy[2 * a + 1]; B.row_cnt[r] = 0;
+            B.o.new_id[a] = id; B.o.new_xy[2 * a] = xy[2 * a]; B.o.new_xy[2 * a + 1] = xy[2 * a + 1];
+        }
+        c->next_id += (uint64_t)n;
+        c->n_new = n; c->n_rows = c->n_kept + n;
+        const Camera cam = make_camera(f->prm, t->cam);
+        const Image I = host_image(f, f->cur, 0), J = host_image(f, f->cur, 1);
+        const HostCells pol;
+        for (int p = 0; p < c->n_rows; ++p) {
+            const float ptx = B.row_xy[2 * p], pty = B.row_xy[2 * p + 1];
+            float tx, ty, e;
+            uint8_t st;
+            lk_gated(pol, f->lk, f->lay, I, J, ptx, pty, false, 0.0f, 0.0f, f->prm.flow_back != 0, f->prm.back_gate_stereo, tx, ty, st, e);
+            float* xyz = B.row_xyz + 3 * p;
+            xyz[0] = xyz[1] = xyz[2] = __builtin_nanf("");
+            if (st) triangulate(cam, ptx, pty, tx, xyz);
+            B.row_rxy[2 * p] = tx; B.row_rxy[2 * p + 1] = ty;
+            B.row_st[p] = st;
+            B.row_ok[p] = stereo_row(st, tx, ty, xyz, S.w, S.h) ? 1 : 0;
+        }
+    }
+    const bool lost = c->lost != 0;
+    int words = 0;
+    for (int i = 0; i < (lost ? 0 : c->n_rows); ++i) {
+        if (!B.row_ok[i]) continue;
+        const int o = words++;
+        const int32_t cnt = B.row_cnt[i] + 1;
+        B.tab_id[o] = B.o.w_id[o] = B.row_id[i];
+        B.tab_cnt[o] = B.o.w_cnt[o] = cnt;
+        for (int k = 0; k < 2; ++k) { B.tab_xy[2 * o + k] = B.o.w_l[2 * o + k] = B.row_xy[2 * i + k]; B.o.w_r[2 * o + k] = B.row_rxy[2 * i + k]; }
+        for (int k = 0; k < 3; ++k) B.tab_xyz[3 * o + k] = B.o.w_xyz[3 * o + k] = B.row_xyz[3 * i + k];
+    }
+    c->n_tab = words;
+    Head hd;
+    hd.flags = lost ? kLost : (boot ? kBootstrapped : 0);
+    hd.n_covis = lost ? 0 : c->n_kept; hd.n_new = lost ? 0 : c->n_new; hd.n_words = words; hd.n_blocked = lost ? 0 : c->n_blocked;
+    hd.pad = 0; hd.next_id = c->next_id;
+    *B.o.head = hd;
+    return VISFS_BA_OK;
+}
+
+// ---------------------------------------------------------------- device: the launches of a call
+int device_call(visfs_tracker* t, bool boot, int32_t from_bound, const Guess* g, int32_t n_outliers, const uint64_t* outlier_ids) {
+    visfs_flow* f = t->f;
+    const Bufs& B = t->B;
+    const Shape& S = t->S;
+    TK_HIP(t, hipSetDevice(f->dev));
+    // (the pinned input block is free: the call that filled it last ended in a synchronise)
+    InHead ih{ n_outliers, 0 };
+    std::memcpy(t->p_in, &ih, sizeof(ih));
+    if (n_outliers > 0) std::memcpy(t->p_in + sizeof(InHead), outlier_ids, sizeof(uint64_t) * (size_t)n_outliers);
+    TK_HIP(t, hipMemcpyAsync(t->d_in, t->p_in, sizeof(InHead) + sizeof(uint64_t) * (size_t)n_outliers, hipMemcpyHostToDevice, f->stream));
+    hipLaunchKernelGGL(k_trk_pretreat, dim3(1), dim3(TK_T), 0, f->stream, B, S);
+    TK_HIP(t, hipGetLastError());
+    const int cur = f->cur, prev = 1 - f->cur;
+    const auto image = [&](int slot, int i) { return Image{ f->dpx[slot][i], f->dder[slot][i] }; };
+    const Camera cam = make_camera(f->prm, t->cam);
+    const bool back = f->prm.flow_back != 0;
+    const int32_t* d_n = nullptr;
+    const float* d_xy = nullptr;
+    if (boot) {
+        int rc = corners_enqueue(f, f->dpx[prev][0], t->prm.quality_level, (double)t->prm.min_distance, nullptr, nullptr, B.ctl->boot_args,
+                                 &d_n, &d_xy);
+        if (rc != VISFS_BA_OK) return fail(t, rc, f->err);
+        hipLaunchKernelGGL((k_trk_append<true>), dim3(1), dim3(TK_T), 0, f->stream, B, S, d_n, d_xy);
+        TK_HIP(t, hipGetLastError());
+        hipLaunchKernelGGL((k_trk_stereo<false, true>), dim3((unsigned)S.M), dim3(64), 0, f->stream, B, S, image(prev, 0), image(prev, 1), f->lk,
+                           f->lay, cam, 0.0f);
+        TK_HIP(t, hipGetLastError());
+    }
+    if (from_bound > 0) {
+        const Guess none{};
+        const dim3 grid((unsigned)from_bound), block(64);
+        if (back) hipLaunchKernelGGL((k_trk_track<true>), grid, block, 0, f->stream, B, S, image(prev, 0), image(cur, 0), f->lk, f->lay,
+                                     g ? *g : none, g ? 1 : 0, f->prm.back_gate_track);
+        else hipLaunchKernelGGL((k_trk_track<false>), grid, block, 0, f->stream, B, S, image(prev, 0), image(cur, 0), f->lk, f->lay,
+                                g ? *g : none, g ? 1 : 0, f->prm.back_gate_track);
+        TK_HIP(t, hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_trk_reduce, dim3(1), dim3(TK_T), 0, f->stream, B, S);
+    TK_HIP(t, hipGetLastError());
+    hipLaunchKernelGGL(k_trk_discs, dim3(1), dim3(TK_T), 0, f->stream, B, S);
+    TK_HIP(t, hipGetLastError());
+    const int rc = corners_enqueue(f, f->dpx[cur][0], t->prm.quality_level, (double)t->prm.min_distance, B.raster, B.hw, B.ctl->corner_args,
+                                   &d_n, &d_xy);
+    if (rc != VISFS_BA_OK) return fail(t, rc, f->err);
+    hipLaunchKernelGGL((k_trk_append<false>), dim3(1), dim3(TK_T), 0, f->stream, B, S, d_n, d_xy);
+    TK_HIP(t, hipGetLastError());
+    const dim3 grid((unsigned)S.M), block(64);
+    if (back) hipLaunchKernelGGL((k_trk_stereo<true, false>), grid, block, 0, f->stream, B, S, image(cur, 0), image(cur, 1), f->lk, f->lay, cam,
+                                 f->prm.back_gate_stereo);
+    else hipLaunchKernelGGL((k_trk_stereo<false, false>), grid, block, 0, f->stream, B, S, image(cur, 0), image(cur, 1), f->lk, f->lay, cam,
+                            f->prm.back_gate_stereo);
+    TK_HIP(t, hipGetLastError());
+    hipLaunchKernelGGL(k_trk_finish, dim3(1), dim3(TK_T), 0, f->stream, B, S, boot ? 1 : 0);
+    TK_HIP(t, hipGetLastError());
+    TK_HIP(t, hipMemcpyAsync(t->p_out, t->d_out, t->out_bytes, hipMemcpyDeviceToHost, f->stream));
+    TK_HIP(t, hipStreamSynchronize(f->stream));
+    return VISFS_BA_OK;
+}
+
+void clear_result(visfs_tracker* t, visfs_tracker_result* r, int32_t flags, uint64_t next_id) {
+    std::memset(r, 0, sizeof(*r));
+    r->flags = flags; r->next_id = next_id;
+    const Out& o = t->R;
+    r->covisible_id = o.cov_id; r->covisible_from_xy = o.cov_from; r->covisible_from_xyz = o.cov_xyz; r->covisible_to_xy = o.cov_to;
+    r->new_id = o.new_id; r->new_xy = o.new_xy;
+    r->word_id = o.w_id; r->word_left_xy = o.w_l; r->word_right_xy = o.w_r; r->word_xyz = o.w_xyz; r->word_count = o.w_cnt;
+    r->blocked_id = o.blk_id;
+}
+
+void detach(visfs_tracker* t) {
+    if (!t->f) return;
+    free_device(t);
+    if (t->f->trackers) {
+        auto& l = t->f->trackers->list;
+        l.erase(std::remove(l.begin(), l.end(), t), l.end());
+    }
+    t->f = nullptr;
+}
+
+}  // namespace
+
+namespace flow {
+void tracker_release(visfs_flow* f) {
+    TrackerState* s = f->trackers;
+    if (!s) return;
+    const std::vector<visfs_tracker*> list = s->list;
+    for (visfs_tracker* t : list) detach(t);
+    delete s;
+    f->trackers = nullptr;
+}
+}  // namespace flow
+
+// ====================================================================== exported C ABI
+extern "C" {
+
+int visfs_tracker_abi_version(void) { return VISFS_TRACKER_ABI_VERSION; }
+
+void visfs_tracker_default_params(visfs_tracker_params* p) {
+    if (!p) return;
+    p->max_features = 300; p->quality_level = 0.01; p->min_distance = 40; p->min_inliers = 10; p->clahe = 0;
+    visfs_clahe_default_params(&p->clahe_params);
+}
+
+int visfs_tracker_create(visfs_flow* f, const visfs_tracker_params* p, const visfs_flow_camera* cam, visfs_tracker** out) {
+    if (!f || !p || !cam || !out) return VISFS_BA_ERR_BAD_ARGUMENT;
+    *out = nullptr;
+    return guarded_tk(nullptr, [&]() -> int {
+        const char* why = "";
+        int rc = check_params(p, cam, &why);
+        if (rc != VISFS_BA_OK) { f->err = why; return rc; }
+        if (p->clahe) {
+            int32_t dummy = 0;
+            rc = visfs_clahe_hook_geometry(&p->clahe_params, f->w, f->h, &dummy, nullptr, nullptr, nullptr, nullptr);
+            if (rc != VISFS_BA_OK) { f->err = "the CLAHE setting is not one the equalised push accepts"; return rc; }
+        }
+        if (f->w < 3 || f->h < 3) { f->err = "the image is smaller than 3 x 3"; return (int)VISFS_BA_ERR_BAD_ARGUMENT; }
+        visfs_tracker* t = new visfs_tracker();
+        t->f = f; t->prm = *p; t->cam = *cam;
+        t->S = Shape{ p->max_features, f->w, f->h, p->min_distance, p->min_distance / 2, p->min_inliers };
+        t->hw.resize((size_t)t->S.r_track + 1 + (size_t)t->S.r_blocked + 1);
+        disc_halfwidth(t->S.r_track, t->hw.data());
+        disc_halfwidth(t->S.r_blocked, t->hw.data() + t->S.r_track + 1);
+        t->seen_frames = f->frames;
+        rc = allocate(t);
+        if (rc != VISFS_BA_OK) { f->err = t->err; free_device(t); delete t; return rc; }
+        if (!f->trackers) f->trackers = new TrackerState();
+        f->trackers->list.push_back(t);
+        *out = t;
+        return (int)VISFS_BA_OK;
+    });
+}
+
+void visfs_tracker_destroy(visfs_tracker* t) {
+    if (!t) return;
+    detach(t);
+    delete t;
+}
+
+const char* visfs_tracker_last_error(const visfs_tracker* t) { return t ? t->err.c_str() : "null tracker"; }
+
+int visfs_tracker_reset(visfs_tracker* t) {
+    if (!t) return VISFS_BA_ERR_BAD_ARGUMENT;
+    return guarded_tk(t, [&]() -> int {
+        if (!t->f) return fail(t, VISFS_BA_ERR_NOT_LOADED, "the flow object of this tracker is gone");
+        t->ids.clear();
+        if (!t->f->device) { t->B.ctl->n_tab = 0; return (int)VISFS_BA_OK; }
+        TK_HIP(t, hipSetDevice(t->f->dev));
+        TK_HIP(t, hipMemsetAsync(&t->B.ctl->n_tab, 0, sizeof(int32_t), t->f->stream));
+        return (int)VISFS_BA_OK;
+    });
+}
+
+int visfs_tracker_process(visfs_tracker* t, const uint8_t* left, const uint8_t* right, int32_t stride, const double* delta_guess,
+                          int32_t n_outliers, const uint64_t* outlier_ids, visfs_tracker_result* result) {
+    if (!t) return VISFS_BA_ERR_BAD_ARGUMENT;
+    return guarded_tk(t, [&]() -> int {
+        visfs_flow* f = t->f;
+        if (!f) return fail(t, VISFS_BA_ERR_NOT_LOADED, "the flow object of this tracker is gone");
+        if (!left || !right || !result) return fail(t, VISFS_BA_ERR_BAD_ARGUMENT, "a NULL argument");
+        if (stride < f->w) return fail(t, VISFS_BA_ERR_BAD_ARGUMENT, "stride is smaller than the image width");
+        if (n_outliers < 0 || n_outliers > kMaxOutliers) return fail(t, VISFS_BA_ERR_BAD_ARGUMENT, "n_outliers must lie in 0 .. 4096");
+        if (n_outliers > 0 && !outlier_ids) return fail(t, VISFS_BA_ERR_BAD_ARGUMENT, "outlier_ids is NULL");
+        if (delta_guess)
+            for (int i = 0; i < 12; ++i)
+                if (!std::isfinite(delta_guess[i])) return fail(t, VISFS_BA_ERR_BAD_ARGUMENT, "delta_guess is not finite");
+        if (f->frames != t->seen_frames)
+            return fail(t, VISFS_BA_ERR_NOT_LOADED, "the images of the flow object were pushed by another caller since this tracker's last call");
+        // what the table will hold after pretreatment is known from the ids handed out last (Tracker.cpp:143-165)
+        const std::unordered_set<uint64_t> out(outlier_ids, outlier_ids + n_outliers);
+        int32_t remaining = 0;
+        for (uint64_t id : t->ids) remaining += out.count(id) ? 0 : 1;
+        const bool boot = remaining == 0;
+        const bool no_previous = f->frames == 0;
+        const int rc_push = t->prm.clahe ? visfs_flow_push_frame_clahe(f, &t->prm.clahe_params, left, right, stride)
+                                         : visfs_flow_push_frame(f, left, right, stride);
+        if (rc_push != VISFS_BA_OK) return fail(t, rc_push, f->err);
+        t->seen_frames = f->frames;
+        if (no_previous) {                                             // Tracker.cpp:168
+            clear_result(t, result, kNoPrevious, 0);
+            t->have_call = false;
+            return (int)VISFS_BA_OK;
+        }
+        Guess g{};
+        const bool has_guess = delta_guess != nullptr;                 // (a bootstrapped table is never empty where corners exist: :238)
+        if (has_guess) {
+            guess_camera_ref(delta_guess, t->cam.Tir, g);
+            g.fx = (double)t->cam.fx; g.fy = (double)t->cam.fy; g.cx = (double)t->cam.cx; g.cy = (double)t->cam.cy;
+        }
+        t->have_call = false;
+        if (f->device) {
+            const int rc = device_call(t, boot, boot ? t->S.M : remaining, has_guess ? &g : nullptr, n_outliers, outlier_ids);
+            if (rc != VISFS_BA_OK) { t->ids.clear(); return rc; }
+        } else {
+            InHead ih{ n_outliers, 0 };
+            std::memcpy(t->h_inblk.data(), &ih, sizeof(ih));
+            if (n_outliers > 0) std::memcpy(t->h_inblk.data() + sizeof(InHead), outlier_ids, sizeof(uint64_t) * (size_t)n_outliers);
+            host_pretreat(t);
+            if (boot) {
+                const int rc = host_bootstrap(t);
+                if (rc != VISFS_BA_OK) return rc;
+            }
+            host_track_reduce(t, has_guess ? &g : nullptr);
+            host_discs(t);
+            const int rc = host_topup_stereo_finish(t, boot);
+            if (rc != VISFS_BA_OK) return rc;
+        }
+        const Head hd = *t->R.head;
+        if (hd.n_covis < 0 || hd.n_covis > t->S.M || hd.n_new < 0 || hd.n_new > t->S.M || hd.n_words < 0 || hd.n_words > t->S.M ||
+            hd.n_blocked < 0 || hd.n_blocked > t->S.M) {
+            t->ids.clear();
+            return fail(t, VISFS_BA_ERR_DEVICE, "the call returned an impossible count");
+        }
+        clear_result(t, result, hd.flags, hd.next_id);
+        result->n_covisible = hd.n_covis; result->n_new = hd.n_new; result->n_words = hd.n_words; result->n_blocked = hd.n_blocked;
+        t->ids.assign(t->R.w_id, t->R.w_id + hd.n_words);
+        t->have_call = true;
+        t->boot_last = boot;
+        return (int)VISFS_BA_OK;
+    });
+}
+
+int visfs_tracker_download(const visfs_tracker* ct, int32_t* n_from, float* guess_xy, float* to_xy, uint8_t* lk_status, uint8_t* in_bounds,
+                           int32_t* n_discs, visfs_corners_disc* discs, uint8_t* disc_drawn, int32_t* n_rows, uint8_t* stereo_status) {
+    visfs_tracker* t = const_cast<visfs_tracker*>(ct);
+    if (!t) return VISFS_BA_ERR_BAD_ARGUMENT;
+    return guarded_tk(t, [&]() -> int {
+        if (!t->f) return fail(t, VISFS_BA_ERR_NOT_LOADED, "the flow object of this tracker is gone");
+        if (!t->have_call) return fail(t, VISFS_BA_ERR_NOT_LOADED, "no call to report on");
+        visfs_flow* f = t->f;
+        const Bufs& B = t->B;
+        Ctl c;
+        if (f->device) {
+            TK_HIP(t, hipSetDevice(f->dev));
+            TK_HIP(t, hipMemcpyAsync(&c, B.ctl, sizeof(Ctl), hipMemcpyDeviceToHost, f->stream));
+            TK_HIP(t, hipStreamSynchronize(f->stream));
+        } else {
+            c = *B.ctl;
+        }
+        const size_t nf = (size_t)std::min(std::max(c.n_from, 0), t->S.M), nl = (size_t)std::min(std::max(c.n_list, 0), 2 * t->S.M),
+                     nr = (size_t)std::min(std::max(c.lost ? 0 : c.n_rows, 0), t->S.M);
+        if (n_from) *n_from = (int32_t)nf;
+        if (n_discs) *n_discs = (int32_t)nl;
+        if (n_rows) *n_rows = (int32_t)nr;
+        const auto get = [&](void* dst, const void* src, size_t bytes) -> int {
+            if (!dst || bytes == 0) return VISFS_BA_OK;
+            if (!f->device) { std::memcpy(dst, src, bytes); return VISFS_BA_OK; }
+            TK_HIP(t, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, f->stream));
+            return VISFS_BA_OK;
+        };
+        int rc = get(guess_xy, B.guess, 8 * nf);
+        if (rc == VISFS_BA_OK) rc = get(to_xy, B.to, 8 * nf);
+        if (rc == VISFS_BA_OK) rc = get(lk_status, B.lk_st, nf);
+        if (rc == VISFS_BA_OK) rc = get(in_bounds, B.inb, nf);
+        if (rc == VISFS_BA_OK) rc = get(discs, B.list, sizeof(visfs_corners_disc) * nl);
+        if (rc == VISFS_BA_OK) rc = get(disc_drawn, B.drawn, nl);
+        if (rc == VISFS_BA_OK) rc = get(stereo_status, B.row_st, nr);
+        if (rc != VISFS_BA_OK) return rc;
+        if (f->device) TK_HIP(t, hipStreamSynchronize(f->stream));
+        return (int)VISFS_BA_OK;
+    });
+}
+
+}  // extern "C"

@@ -1,0 +1,120 @@
+// ResidentTracker.h — VISFS::Tracker::pretreatment + VISFS::Tracker::imageProcess (corelib/src/Tracker.cpp:143-419) as one call
+// on the GPU-resident word table of include/visfs_tracker.h.  Header only, over the C ABI.
+//
+// What the reference keeps in trackCnt_, globalFeatureId_, the words of lastSignature_ and the blocked words of pretreatment lives
+// in the library; this class turns the arrays of a call into the std::maps the Signature setters take (ascending id, as uKeys and
+// uValues read them) and keeps the one test that belongs to the caller's types: getDeltaPoseGuess().isApprox(Identity) (:237).
+#ifndef VISFS_AMD_RESIDENT_TRACKER_H
+#define VISFS_AMD_RESIDENT_TRACKER_H
+
+#include <cstddef>
+#include <cstdint>
+#include <map>
+#include <set>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "visfs_tracker.h"
+
+namespace VISFS {
+
+class ResidentTracker {
+public:
+    struct Point2f { float x, y; };
+    struct Point3f { float x, y, z; };
+
+    // The contents imageProcess sets on the to-signature (and setBlockedWords on the from-signature).
+    struct Frame {
+        bool noPrevious = false, bootstrapped = false, lost = false;
+        std::map<std::size_t, Point2f> covisibleWords;              // setCovisibleWords
+        std::map<std::size_t, Point3f> covisibleWords3d;            // setCovisibleWords3d
+        std::map<std::size_t, Point2f> keyPointsMatchesFormer;      // setkeyPointsMatchesFormer
+        std::map<std::size_t, Point2f> keyPointsNewExtract;         // setKeyPointsNewExtract
+        std::map<std::size_t, Point2f> words;                       // setWords
+        std::map<std::size_t, Point2f> keyPointMatchesImageRight;   // setKeyPointMatchesImageRight
+        std::map<std::size_t, Point3f> words3d;                     // setWords3d
+        std::map<std::size_t, int> trackCount;                      // trackCnt_ after updateTrackCounter
+        std::set<std::size_t> blockedWords;                         // keys of setBlockedWords
+        std::size_t nextFeatureId = 0;                              // globalFeatureId_
+    };
+
+    ResidentTracker(const ResidentTracker&) = delete;
+    ResidentTracker& operator=(const ResidentTracker&) = delete;
+
+    // flow: the object that holds the pyramids (visfs_flow_create, or visfs_flow_create_host for the one-core twin); it must outlive
+    // this tracker.  The Tracker/* and Estimator/MinInliers keys as the reference names them.
+    ResidentTracker(visfs_flow* flow, const visfs_flow_camera& camera, int maxFeatures = 300, double qualityLevel = 0.01,
+                    int minFeatureDistance = 40, int minInliers = 10, bool clahe = false, double clipLimit = 3.0, int tilesX = 8,
+                    int tilesY = 8) {
+        visfs_tracker_params p;
+        visfs_tracker_default_params(&p);
+        p.max_features = maxFeatures; p.quality_level = qualityLevel; p.min_distance = minFeatureDistance; p.min_inliers = minInliers;
+        p.clahe = clahe ? 1 : 0; p.clahe_params.clip_limit = clipLimit; p.clahe_params.tiles_x = tilesX; p.clahe_params.tiles_y = tilesY;
+        const int rc = visfs_tracker_create(flow, &p, &camera, &t_);
+        if (rc != VISFS_BA_OK) throw std::runtime_error("visfs_tracker_create failed with status " + std::to_string(rc));
+    }
+    ~ResidentTracker() { visfs_tracker_destroy(t_); }
+
+    // Tracker::pretreatment (:143-165): the outliers Estimator::getOutliers() returned leave the table in the next imageProcess.
+    void pretreatment(const std::set<std::size_t>& outliers) { outliers_.assign(outliers.begin(), outliers.end()); }
+
+    // Eigen's isApprox against the identity (:237): ||T - I||^2 <= 1e-24 * min(||T||^2, ||I||^2) over the 4 x 4 matrix.
+    static bool isIdentity(const double T[16]) {
+        double diff = 0.0, norm = 0.0;
+        for (int i = 0; i < 16; ++i) {
+            const double e = (i % 5 == 0) ? 1.0 : 0.0;
+            diff += (T[i] - e) * (T[i] - e);
+            norm += T[i] * T[i];
+        }
+        return diff <= 1e-24 * (norm < 4.0 ? norm : 4.0);
+    }
+
+    // Tracker::imageProcess (:167-419) on a new stereo pair (8-bit grey).  deltaPoseGuess: getDeltaPoseGuess() as a 4 x 4 row-major
+    // matrix, or nullptr; an identity-equal guess is "not set", as in the reference.
+    int imageProcess(const uint8_t* left, const uint8_t* right, int stride, const double* deltaPoseGuess, Frame& out) {
+        const bool guessSet = deltaPoseGuess != nullptr && !isIdentity(deltaPoseGuess);
+        std::vector<uint64_t> ids(outliers_.begin(), outliers_.end());
+        outliers_.clear();
+        visfs_tracker_result r;
+        const int rc = visfs_tracker_process(t_, left, right, stride, guessSet ? deltaPoseGuess : nullptr, (int32_t)ids.size(),
+                                             ids.empty() ? nullptr : ids.data(), &r);
+        out = Frame();
+        if (rc != VISFS_BA_OK) return rc;
+        out.noPrevious = (r.flags & VISFS_TRACKER_NO_PREVIOUS) != 0;
+        out.bootstrapped = (r.flags & VISFS_TRACKER_BOOTSTRAPPED) != 0;
+        out.lost = (r.flags & VISFS_TRACKER_LOST) != 0;
+        out.nextFeatureId = (std::size_t)r.next_id;
+        for (int32_t i = 0; i < r.n_covisible; ++i) {
+            const std::size_t id = (std::size_t)r.covisible_id[i];
+            out.covisibleWords.emplace_hint(out.covisibleWords.end(), id, p2(r.covisible_from_xy, i));
+            out.covisibleWords3d.emplace_hint(out.covisibleWords3d.end(), id, p3(r.covisible_from_xyz, i));
+            out.keyPointsMatchesFormer.emplace_hint(out.keyPointsMatchesFormer.end(), id, p2(r.covisible_to_xy, i));
+        }
+        for (int32_t i = 0; i < r.n_new; ++i)
+            out.keyPointsNewExtract.emplace_hint(out.keyPointsNewExtract.end(), (std::size_t)r.new_id[i], p2(r.new_xy, i));
+        for (int32_t i = 0; i < r.n_words; ++i) {
+            const std::size_t id = (std::size_t)r.word_id[i];
+            out.words.emplace_hint(out.words.end(), id, p2(r.word_left_xy, i));
+            out.keyPointMatchesImageRight.emplace_hint(out.keyPointMatchesImageRight.end(), id, p2(r.word_right_xy, i));
+            out.words3d.emplace_hint(out.words3d.end(), id, p3(r.word_xyz, i));
+            out.trackCount.emplace_hint(out.trackCount.end(), id, (int)r.word_count[i]);
+        }
+        for (int32_t i = 0; i < r.n_blocked; ++i) out.blockedWords.insert(out.blockedWords.end(), (std::size_t)r.blocked_id[i]);
+        return rc;
+    }
+
+    int reset() { return visfs_tracker_reset(t_); }
+    const char* lastError() const { return visfs_tracker_last_error(t_); }
+    visfs_tracker* handle() { return t_; }
+
+private:
+    static Point2f p2(const float* a, int32_t i) { return Point2f{ a[2 * i], a[2 * i + 1] }; }
+    static Point3f p3(const float* a, int32_t i) { return Point3f{ a[3 * i], a[3 * i + 1], a[3 * i + 2] }; }
+    visfs_tracker* t_ = nullptr;
+    std::vector<std::size_t> outliers_;
+};
+
+}  // namespace VISFS
+
+#endif
