@@ -13,6 +13,7 @@
 // All sums are integers, so device and host agree to the byte whatever the order of summation.
 #include "ba_clahe.hpp"
 #include "ba_flow_object.hpp"
+#include "ba_group.hpp"
 #include "../../include/visfs_clahe.h"
 
 #include <cstring>
@@ -36,13 +37,12 @@ struct LutArgs {
     int32_t* hist[2];              // [tiles_y][tiles_x][256]
 };
 
-__global__ __launch_bounds__(CL_T) void k_clahe_lut(LutArgs A, Geom g) {
+__device__ __forceinline__ void clahe_lut_body(const uint8_t* __restrict__ src, uint8_t* lut, int32_t* hist, const Geom& g) {
     __shared__ int32_t sHist[CL_WAVES][kBins];
     __shared__ int32_t sPart[CL_WAVES];
     __shared__ int32_t sScan[CL_WAVES];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int tile = blockIdx.x, ty = tile / g.tiles_x, tx = tile - ty * g.tiles_x;
-    const uint8_t* __restrict__ src = A.raw[blockIdx.y];
 #pragma unroll
     for (int k = 0; k < CL_WAVES; ++k) sHist[k][tid] = 0;
     __syncthreads();
@@ -94,8 +94,18 @@ __global__ __launch_bounds__(CL_T) void k_clahe_lut(LutArgs A, Geom g) {
     __syncthreads();
     for (int k = 0; k < wave; ++k) cum += sScan[k];
     const int64_t o = (int64_t)tile * kBins + tid;
-    A.lut[blockIdx.y][o] = lut_value(cum, g.lut_scale);
-    A.hist[blockIdx.y][o] = count;
+    lut[o] = lut_value(cum, g.lut_scale);
+    hist[o] = count;
+}
+
+__global__ __launch_bounds__(CL_T) void k_clahe_lut(LutArgs A, Geom g) {
+    clahe_lut_body(A.raw[blockIdx.y], A.lut[blockIdx.y], A.hist[blockIdx.y], g);
+}
+
+// the batched forms (tracker groups): member blockIdx.z, its buffers read from the group's table
+__global__ __launch_bounds__(CL_T) void k_clahe_lut_g(const flow::ClaheRec* __restrict__ recs, Geom g) {
+    const flow::ClaheRec& r = recs[blockIdx.z];
+    clahe_lut_body(r.raw[blockIdx.y], r.lut[blockIdx.y], r.hist[blockIdx.y], g);
 }
 
 struct ApplyArgs {
@@ -104,13 +114,11 @@ struct ApplyArgs {
     uint8_t* dst[2];               // level 0 of the new slot; like raw, the base is 4-byte aligned
 };
 
-__global__ __launch_bounds__(CL_T) void k_clahe_apply(ApplyArgs A, Geom g) {
+__device__ __forceinline__ void clahe_apply_body(const uint8_t* __restrict__ src, const uint8_t* __restrict__ lut, uint8_t* __restrict__ dst,
+                                                 const Geom& g) {
     const int64_t n0 = (int64_t)g.w * g.h;
     const int64_t i0 = ((int64_t)blockIdx.x * CL_T + threadIdx.x) * CL_PX;
     if (i0 >= n0) return;
-    const uint8_t* __restrict__ src = A.raw[blockIdx.y];
-    const uint8_t* __restrict__ lut = A.lut[blockIdx.y];
-    uint8_t* __restrict__ dst = A.dst[blockIdx.y];
     int y = (int)(i0 / g.w), x = (int)(i0 - (int64_t)y * g.w);
     const bool whole = i0 + CL_PX <= n0;
     uint8_t v[CL_PX] = { 0, 0, 0, 0 }, out[CL_PX];
@@ -132,6 +140,15 @@ __global__ __launch_bounds__(CL_T) void k_clahe_apply(ApplyArgs A, Geom g) {
     } else {
         for (int k = 0; i0 + k < n0; ++k) dst[i0 + k] = out[k];
     }
+}
+
+__global__ __launch_bounds__(CL_T) void k_clahe_apply(ApplyArgs A, Geom g) {
+    clahe_apply_body(A.raw[blockIdx.y], A.lut[blockIdx.y], A.dst[blockIdx.y], g);
+}
+
+__global__ __launch_bounds__(CL_T) void k_clahe_apply_g(const flow::ClaheRec* __restrict__ recs, Geom g) {
+    const flow::ClaheRec& r = recs[blockIdx.z];
+    clahe_apply_body(r.raw[blockIdx.y], r.lut[blockIdx.y], r.dst[blockIdx.y], g);
 }
 
 }  // namespace clahe
@@ -267,6 +284,39 @@ int device_equalise(visfs_flow* f, ClaheState* c, const Geom& g, int slot, const
 }
 
 }  // namespace
+
+// ---------------------------------------------------------------- the tracker group's entry points (ba_tracker.hip)
+namespace flow {
+
+int group_clahe_prepare(visfs_flow* f) { return ensure_state(f); }
+
+void group_clahe_fill(visfs_flow* f, const Geom& g, int slot, ClaheRec* r, uint8_t* raw[2]) {
+    ClaheState* c = f->clahe;
+    const size_t tile_cells = (size_t)g.tiles_x * g.tiles_y * kBins;
+    for (int i = 0; i < 2; ++i) {
+        raw[i] = c->d_raw + i * c->raw_stride;
+        r->raw[i] = raw[i];
+        r->lut[i] = c->d_lut + i * tile_cells;
+        r->hist[i] = c->d_hist + i * tile_cells;
+        r->dst[i] = f->dpx[slot][i];
+    }
+    c->valid = false;
+}
+
+int group_clahe(visfs_flow* f, const Geom& g, int n, const ClaheRec* d_recs, GroupCounts* cnt) {
+    hipLaunchKernelGGL(k_clahe_lut_g, dim3((unsigned)(g.tiles_x * g.tiles_y), 2, (unsigned)n), dim3(CL_T), 0, f->stream, d_recs, g);
+    CL_HIP(f, hipGetLastError());
+    const int64_t per_block = (int64_t)CL_T * CL_PX;
+    const unsigned blocks = (unsigned)(((int64_t)g.w * g.h + per_block - 1) / per_block);
+    hipLaunchKernelGGL(k_clahe_apply_g, dim3(blocks, 2, (unsigned)n), dim3(CL_T), 0, f->stream, d_recs, g);
+    CL_HIP(f, hipGetLastError());
+    cnt->kernels += 2;
+    return VISFS_BA_OK;
+}
+
+void group_clahe_pushed(visfs_flow* f, const Geom& g) { f->clahe->g = g; f->clahe->valid = true; }
+
+}  // namespace flow
 
 // ====================================================================== exported C ABI
 extern "C" {

@@ -15,6 +15,7 @@
 // Which discs are drawn depends on the disc list alone; that short serial pass runs on the host before the launches, for both ways.
 #include "ba_corners.hpp"
 #include "ba_flow_object.hpp"
+#include "ba_group.hpp"
 #include "../../include/visfs_corners.h"
 
 #include <algorithm>
@@ -40,9 +41,9 @@ struct CornerDev {                             // device words of a call, copied
     int32_t pad;
 };
 
-__global__ __launch_bounds__(CR_T) void k_corner_response(const uint8_t* __restrict__ px, int w, int h, const Disc* __restrict__ discs,
-                                                          int n_discs, const int32_t* __restrict__ hw, float* __restrict__ eig,
-                                                          uint8_t* __restrict__ mask, CornerDev* st, const int32_t* dev_args) {
+__device__ __forceinline__ void corner_response_body(const uint8_t* __restrict__ px, int w, int h, const Disc* __restrict__ discs,
+                                                     int n_discs, const int32_t* __restrict__ hw, float* __restrict__ eig,
+                                                     uint8_t* __restrict__ mask, CornerDev* st, const int32_t* dev_args) {
     if (dev_args) {                            // a resident caller: { n_discs, max_corners } of this call live in device memory
         if (dev_args[1] <= 0) return;          // nothing is wanted: no candidate is counted and the selection returns none
         n_discs = dev_args[0];
@@ -112,9 +113,29 @@ __global__ __launch_bounds__(CR_T) void k_corner_response(const uint8_t* __restr
     }
 }
 
-__global__ __launch_bounds__(CR_T) void k_corner_candidates(const float* __restrict__ eig, const uint8_t* __restrict__ mask, int w, int h,
-                                                            double quality, CornerDev* st, uint64_t* __restrict__ keys,
-                                                            const int32_t* dev_args) {
+__global__ __launch_bounds__(CR_T) void k_corner_response(const uint8_t* __restrict__ px, int w, int h, const Disc* __restrict__ discs,
+                                                          int n_discs, const int32_t* __restrict__ hw, float* __restrict__ eig,
+                                                          uint8_t* __restrict__ mask, CornerDev* st, const int32_t* dev_args) {
+    corner_response_body(px, w, h, discs, n_discs, hw, eig, mask, st, dev_args);
+}
+
+// The batched forms (tracker groups): member blockIdx.z, its arguments read from the group's table.  A member that takes no part in
+// the extraction (skip) leaves at once; the words of every other member's call are zeroed by k_corner_reset_g in front.
+__global__ __launch_bounds__(64) void k_corner_reset_g(const CornerRec* __restrict__ recs, int n) {
+    const int m = blockIdx.x * 64 + threadIdx.x;
+    if (m >= n || recs[m].skip) return;
+    *recs[m].st = CornerDev{ 0u, 0u, 0, 0 };
+}
+
+__global__ __launch_bounds__(CR_T) void k_corner_response_g(const CornerRec* __restrict__ recs, int w, int h) {
+    const CornerRec r = recs[blockIdx.z];
+    if (r.skip) return;
+    corner_response_body(r.px, w, h, r.discs, 0, r.hw, r.eig, r.mask, r.st, r.args);
+}
+
+__device__ __forceinline__ void corner_candidates_body(const float* __restrict__ eig, const uint8_t* __restrict__ mask, int w, int h,
+                                                       double quality, CornerDev* st, uint64_t* __restrict__ keys,
+                                                       const int32_t* dev_args) {
     if (dev_args && dev_args[1] <= 0) return;  // the response map was not made
     const int64_t i = (int64_t)blockIdx.x * CR_T + threadIdx.x;
     const float t = quality_threshold(from_ordered_bits(st->max_bits), quality);
@@ -147,9 +168,21 @@ __global__ __launch_bounds__(CR_T) void k_corner_candidates(const float* __restr
     if (cand) keys[base + (uint32_t)__popcll(b & ((1ull << lane) - 1ull))] = corner_key(v, (uint32_t)i);
 }
 
+__global__ __launch_bounds__(CR_T) void k_corner_candidates(const float* __restrict__ eig, const uint8_t* __restrict__ mask, int w, int h,
+                                                            double quality, CornerDev* st, uint64_t* __restrict__ keys,
+                                                            const int32_t* dev_args) {
+    corner_candidates_body(eig, mask, w, h, quality, st, keys, dev_args);
+}
+
+__global__ __launch_bounds__(CR_T) void k_corner_candidates_g(const CornerRec* __restrict__ recs, int w, int h, double quality) {
+    const CornerRec r = recs[blockIdx.z];
+    if (r.skip) return;
+    corner_candidates_body(r.eig, r.mask, w, h, quality, r.st, r.keys, r.args);
+}
+
 // sorted[number of keys greater than k] = k.  A workgroup takes 64 candidates at a time (one per lane); its four wavefronts each
 // count over a quarter of every LDS tile of keys.
-__global__ __launch_bounds__(CR_T) void k_corner_sort(const uint64_t* __restrict__ keys, const CornerDev* st, uint64_t* __restrict__ sorted) {
+__device__ __forceinline__ void corner_sort_body(const uint64_t* __restrict__ keys, const CornerDev* st, uint64_t* __restrict__ sorted) {
     __shared__ uint64_t tile[kSortTile];
     __shared__ uint32_t part[CR_T / 64][64];
     const uint32_t n = st->count;
@@ -172,8 +205,18 @@ __global__ __launch_bounds__(CR_T) void k_corner_sort(const uint64_t* __restrict
     }
 }
 
-__global__ __launch_bounds__(kSelT) void k_corner_select(const uint64_t* __restrict__ sorted, CornerDev* st, int w, int32_t gate,
-                                                         int32_t max_corners, float* __restrict__ xy, const int32_t* dev_args) {
+__global__ __launch_bounds__(CR_T) void k_corner_sort(const uint64_t* __restrict__ keys, const CornerDev* st, uint64_t* __restrict__ sorted) {
+    corner_sort_body(keys, st, sorted);
+}
+
+__global__ __launch_bounds__(CR_T) void k_corner_sort_g(const CornerRec* __restrict__ recs) {
+    const CornerRec r = recs[blockIdx.z];
+    if (r.skip) return;
+    corner_sort_body(r.keys, r.st, r.sorted);
+}
+
+__device__ __forceinline__ void corner_select_body(const uint64_t* __restrict__ sorted, CornerDev* st, int w, int32_t gate,
+                                                   int32_t max_corners, float* __restrict__ xy, const int32_t* dev_args) {
     if (dev_args) max_corners = dev_args[1] > 0 ? dev_args[1] : 0;
     __shared__ int32_t acc[kMaxCorners];       // accepted, x | y << 16
     __shared__ int32_t surv[kSelT];            // a chunk's survivors of the list as it stood when the chunk began, in order
@@ -241,6 +284,17 @@ __global__ __launch_bounds__(kSelT) void k_corner_select(const uint64_t* __restr
         xy[2 * a + 1] = (float)(acc[a] >> 16);
     }
     if (tid == 0) st->n_out = nacc;
+}
+
+__global__ __launch_bounds__(kSelT) void k_corner_select(const uint64_t* __restrict__ sorted, CornerDev* st, int w, int32_t gate,
+                                                         int32_t max_corners, float* __restrict__ xy, const int32_t* dev_args) {
+    corner_select_body(sorted, st, w, gate, max_corners, xy, dev_args);
+}
+
+__global__ __launch_bounds__(kSelT) void k_corner_select_g(const CornerRec* __restrict__ recs, int w, int32_t gate) {
+    const CornerRec r = recs[blockIdx.z];
+    if (r.skip) return;
+    corner_select_body(r.sorted, r.st, w, gate, 0, r.xy, r.args);
 }
 
 // ---------------------------------------------------------------- per-object state
@@ -521,6 +575,41 @@ int corners_enqueue(visfs_flow* f, const uint8_t* px, double quality_level, doub
     CR_HIP(f, hipGetLastError());
     *d_n_out = &st->n_out;
     *d_xy = xy;
+    return VISFS_BA_OK;
+}
+
+int group_corners_prepare(visfs_flow* f) { return ensure_state(f); }
+
+void group_corners_fill(visfs_flow* f, const uint8_t* px, const Disc* d_discs, const int32_t* d_hw, const int32_t* d_args, bool skip,
+                        CornerRec* r, const int32_t** d_n_out, const float** d_xy) {
+    CornerState* c = f->corners;
+    if (!skip) c->valid = false;               // the download hook reports staged calls only
+    CornerDev* st = reinterpret_cast<CornerDev*>(c->d_out);
+    r->px = px; r->discs = d_discs; r->hw = d_hw; r->args = d_args;
+    r->eig = c->d_eig; r->mask = c->d_mask; r->keys = c->d_keys; r->sorted = c->d_sorted;
+    r->st = st; r->xy = reinterpret_cast<float*>(c->d_out + sizeof(CornerDev));
+    r->skip = skip ? 1 : 0; r->pad = 0;
+    *d_n_out = &st->n_out;
+    *d_xy = r->xy;
+}
+
+int group_corners(visfs_flow* f, double quality_level, double min_distance, int n, const CornerRec* d_recs, GroupCounts* cnt) {
+    const int w = f->w, h = f->h;
+    const unsigned z = (unsigned)n;
+    hipLaunchKernelGGL(k_corner_reset_g, dim3((z + 63) / 64), dim3(64), 0, f->stream, d_recs, n);
+    CR_HIP(f, hipGetLastError());
+    hipLaunchKernelGGL(k_corner_response_g, dim3((w + CT_X - 1) / CT_X, (h + CT_Y - 1) / CT_Y, z), dim3(CR_T), 0, f->stream, d_recs, w, h);
+    CR_HIP(f, hipGetLastError());
+    hipLaunchKernelGGL(k_corner_candidates_g, dim3((unsigned)(((size_t)w * h + CR_T - 1) / CR_T), 1, z), dim3(CR_T), 0, f->stream, d_recs, w, h,
+                       quality_level);
+    CR_HIP(f, hipGetLastError());
+    const size_t chunks = (max_candidates(f) + 63) / 64;
+    hipLaunchKernelGGL(k_corner_sort_g, dim3((unsigned)std::min<size_t>(std::max<size_t>(chunks, 1), kSortGrid), 1, z), dim3(CR_T), 0, f->stream,
+                       d_recs);
+    CR_HIP(f, hipGetLastError());
+    hipLaunchKernelGGL(k_corner_select_g, dim3(1, 1, z), dim3(kSelT), 0, f->stream, d_recs, w, distance_gate(min_distance));
+    CR_HIP(f, hipGetLastError());
+    cnt->kernels += 5;
     return VISFS_BA_OK;
 }
 

@@ -11,6 +11,7 @@
 //                         across the wavefront in int64; every lane then runs the scalar tail on the same sums.
 // The sums are exact integers, so device and host agree to the byte whatever the order of summation.
 #include "ba_flow_object.hpp"
+#include "ba_group.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -31,11 +32,22 @@ struct PyrDownArgs {
     int32_t sw, sh, dw, dh;
 };
 
-__global__ __launch_bounds__(FL_T) void k_flow_pyr_down(PyrDownArgs A) {
+__device__ __forceinline__ void pyr_down_body(const uint8_t* src, uint8_t* dst, int32_t sw, int32_t sh, int32_t dw, int32_t dh) {
     const int64_t i = (int64_t)blockIdx.x * FL_T + threadIdx.x;
-    if (i >= (int64_t)A.dw * A.dh) return;
-    const int y = (int)(i / A.dw), x = (int)(i - (int64_t)y * A.dw);
-    A.dst[blockIdx.y][i] = pyr_down_cell(A.src[blockIdx.y], A.sw, A.sh, x, y);
+    if (i >= (int64_t)dw * dh) return;
+    const int y = (int)(i / dw), x = (int)(i - (int64_t)y * dw);
+    dst[i] = pyr_down_cell(src, sw, sh, x, y);
+}
+
+__global__ __launch_bounds__(FL_T) void k_flow_pyr_down(PyrDownArgs A) {
+    pyr_down_body(A.src[blockIdx.y], A.dst[blockIdx.y], A.sw, A.sh, A.dw, A.dh);
+}
+
+// the batched forms (tracker groups): member blockIdx.z, its images read from the group's table
+__global__ __launch_bounds__(FL_T) void k_flow_pyr_down_g(const PyrRec* __restrict__ recs, int64_t soff, int64_t doff, int32_t sw, int32_t sh,
+                                                          int32_t dw, int32_t dh) {
+    uint8_t* px = recs[blockIdx.z].px[blockIdx.y];
+    pyr_down_body(px + soff, px + doff, sw, sh, dw, dh);
 }
 
 struct ScharrArgs {
@@ -43,7 +55,7 @@ struct ScharrArgs {
     uint32_t* der[2];
 };
 
-__global__ __launch_bounds__(FL_T) void k_flow_scharr(ScharrArgs A, Layout lay) {
+__device__ __forceinline__ void scharr_body(const uint8_t* px, uint32_t* der, const Layout& lay) {
     const int64_t i = (int64_t)blockIdx.x * FL_T + threadIdx.x;
     if (i >= lay.cells) return;
     int l = 0;
@@ -51,7 +63,14 @@ __global__ __launch_bounds__(FL_T) void k_flow_scharr(ScharrArgs A, Layout lay) 
     const Level L = lay.L[l];
     const int64_t c = i - L.off;
     const int y = (int)(c / L.w), x = (int)(c - (int64_t)y * L.w);
-    A.der[blockIdx.y][i] = scharr_cell(A.px[blockIdx.y] + L.off, L.w, L.h, x, y);
+    der[i] = scharr_cell(px + L.off, L.w, L.h, x, y);
+}
+
+__global__ __launch_bounds__(FL_T) void k_flow_scharr(ScharrArgs A, Layout lay) { scharr_body(A.px[blockIdx.y], A.der[blockIdx.y], lay); }
+
+__global__ __launch_bounds__(FL_T) void k_flow_scharr_g(const PyrRec* __restrict__ recs, Layout lay) {
+    const PyrRec& r = recs[blockIdx.z];
+    scharr_body(r.px[blockIdx.y], r.der[blockIdx.y], lay);
 }
 
 // the window cells of one wavefront: cell s * 64 + lane in slot s, per-lane int32 partial sums, int64 butterfly
@@ -231,15 +250,38 @@ void host_pyramids(visfs_flow* f, int slot, int image) {
     }
 }
 
-int device_stage(visfs_flow* f, uint8_t* const dst[2], const uint8_t* left, const uint8_t* right, int32_t stride) {
-    FL_HIP(f, hipSetDevice(f->dev));
-    FL_HIP(f, hipStreamSynchronize(f->stream));                        // the staging image of the frame before has left
+int group_stage(visfs_flow* f, uint8_t* const dst[2], const uint8_t* left, const uint8_t* right, int32_t stride, GroupCounts* cnt) {
     const size_t n0 = (size_t)f->w * f->h;
     const uint8_t* src[2] = { left, right };
     for (int i = 0; i < 2; ++i) {
         for (int32_t y = 0; y < f->h; ++y) std::memcpy(f->h_img + i * n0 + (size_t)y * f->w, src[i] + (size_t)y * stride, (size_t)f->w);
         FL_HIP(f, hipMemcpyAsync(dst[i], f->h_img + i * n0, n0, hipMemcpyHostToDevice, f->stream));
+        if (cnt) ++cnt->copies;
     }
+    return VISFS_BA_OK;
+}
+
+int device_stage(visfs_flow* f, uint8_t* const dst[2], const uint8_t* left, const uint8_t* right, int32_t stride) {
+    FL_HIP(f, hipSetDevice(f->dev));
+    FL_HIP(f, hipStreamSynchronize(f->stream));                        // the staging image of the frame before has left
+    return group_stage(f, dst, left, right, stride, nullptr);
+}
+
+void group_pyr_fill(const visfs_flow* f, int slot, PyrRec* r) {
+    for (int i = 0; i < 2; ++i) { r->px[i] = f->dpx[slot][i]; r->der[i] = f->dder[slot][i]; }
+}
+
+int group_pyramids(visfs_flow* f, int n, const PyrRec* d_recs, GroupCounts* cnt) {
+    for (int l = 1; l < f->lay.n_levels; ++l) {
+        const Level &S = f->lay.L[l - 1], &D = f->lay.L[l];
+        hipLaunchKernelGGL(k_flow_pyr_down_g, dim3(blocks_for((int64_t)D.w * D.h), 2, (unsigned)n), dim3(FL_T), 0, f->stream, d_recs, S.off, D.off,
+                           S.w, S.h, D.w, D.h);
+        FL_HIP(f, hipGetLastError());
+        ++cnt->kernels;
+    }
+    hipLaunchKernelGGL(k_flow_scharr_g, dim3(blocks_for(f->lay.cells), 2, (unsigned)n), dim3(FL_T), 0, f->stream, d_recs, f->lay);
+    FL_HIP(f, hipGetLastError());
+    ++cnt->kernels;
     return VISFS_BA_OK;
 }
 

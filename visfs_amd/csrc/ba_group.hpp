@@ -1,0 +1,57 @@
+// The member tables of a tracker group (include/visfs_tracker_group.h) and the batched enqueue functions of the
+// translation units that own the kernels: ba_flow.hip (pyramids), ba_clahe.hip (equalised level 0), ba_corners.hip (corner
+// extraction).  ba_tracker.hip owns the group, fills one pinned block with every table of a call, sends it up in one copy and hands each
+// function the device address of its records.  The member index of every batched kernel is blockIdx.z.
+#pragma once
+#include "ba_clahe.hpp"
+#include "ba_corners.hpp"
+#include "ba_flow_object.hpp"
+
+namespace flow {
+
+struct GroupCounts { int32_t kernels = 0, copies = 0, syncs = 0; };     // what a group call issued
+
+struct PyrRec {                                // the slot a member's frame goes into
+    uint8_t* px[2];
+    uint32_t* der[2];
+};
+
+struct ClaheRec {
+    const uint8_t* raw[2];
+    uint8_t* lut[2];
+    int32_t* hist[2];
+    uint8_t* dst[2];                           // level 0 of the slot
+};
+
+struct CornerDev;                              // ba_corners.hip
+struct CornerRec {                             // one corner extraction of a member: the arguments of corners_enqueue and its state
+    const uint8_t* px;
+    const Disc* discs;
+    const int32_t* hw;
+    const int32_t* args;                       // { number of raster discs, max_corners } in device memory
+    float* eig;
+    uint8_t* mask;
+    uint64_t* keys;
+    uint64_t* sorted;
+    CornerDev* st;
+    float* xy;
+    int32_t skip, pad;                         // the member takes no part in this extraction
+};
+
+// group_stage: the copies of device_stage without its wait (the caller has waited once for the whole group).
+int group_stage(visfs_flow* f, uint8_t* const dst[2], const uint8_t* left, const uint8_t* right, int32_t stride, GroupCounts* cnt);
+void group_pyr_fill(const visfs_flow* f, int slot, PyrRec* r);
+int group_pyramids(visfs_flow* f, int n, const PyrRec* d_recs, GroupCounts* cnt);          // f: any member (geometry, stream)
+
+// group_clahe_prepare: allocates the member's CLAHE state (at group creation).  group_clahe_fill returns where the raw images go.
+int group_clahe_prepare(visfs_flow* f);
+void group_clahe_fill(visfs_flow* f, const clahe::Geom& g, int slot, ClaheRec* r, uint8_t* raw[2]);
+int group_clahe(visfs_flow* f, const clahe::Geom& g, int n, const ClaheRec* d_recs, GroupCounts* cnt);
+void group_clahe_pushed(visfs_flow* f, const clahe::Geom& g);                              // the bookkeeping of a completed push
+
+int group_corners_prepare(visfs_flow* f);
+void group_corners_fill(visfs_flow* f, const uint8_t* px, const Disc* d_discs, const int32_t* d_hw, const int32_t* d_args, bool skip,
+                        CornerRec* r, const int32_t** d_n_out, const float** d_xy);
+int group_corners(visfs_flow* f, double quality_level, double min_distance, int n, const CornerRec* d_recs, GroupCounts* cnt);
+
+}  // namespace flow

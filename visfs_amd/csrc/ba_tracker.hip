@@ -22,9 +22,14 @@
 //       k_trk_append    ids for the new corners, appended behind the kept rows                                      (:330-336)
 //       k_trk_stereo    one wavefront per row: lk_gated left -> right, bounds test, triangulate                     (:343-397)
 //       k_trk_finish    one workgroup: final compaction into the table, counts + 1, the output block's head        (:98-114, :414-417)
+//   * tracker groups (include/visfs_tracker_group.h): every kernel above is a thin caller of a __device__ body;
+//     the batched k_*_g forms call the same bodies for member blockIdx.z of a table in device memory, so n trackers of one handle
+//     take one launch sequence and one synchronisation.
 #include "ba_tracker.hpp"
 #include "ba_flow_object.hpp"
+#include "ba_group.hpp"
 #include "../../include/visfs_tracker.h"
+#include "../../include/visfs_tracker_group.h"
 
 #include <algorithm>
 #include <cstring>
@@ -37,6 +42,7 @@ using namespace flow;
 using namespace trk;
 
 struct visfs_tracker;
+struct visfs_tracker_group;
 
 namespace flow {
 struct TrackerState { std::vector<visfs_tracker*> list; };
@@ -126,6 +132,20 @@ size_t carve_work(char* base, size_t M, size_t hw_len, Bufs& b, int32_t** hw) {
 
 struct Shape { int32_t M, w, h, r_track, r_blocked, min_inliers; };
 
+// A member of a tracker group in one call: what the launches of device_call take as kernel arguments, read by the
+// batched kernels from device memory instead.  B.in and B.outliers point into the group's own upload block.
+struct TrkRec {
+    Bufs B;
+    Image prev[2], cur[2];                     // left, right of the slot before and of the slot this call pushed into
+    Camera cam;
+    Guess g;
+    const int32_t* corner_n; const float* corner_xy;     // where the member's corner extraction leaves its count and its corners
+    int32_t has_guess;
+    int32_t skip;                              // NO_PREVIOUS: the pair is pushed and nothing else runs
+    int32_t boot;
+    int32_t pad;
+};
+
 // ---------------------------------------------------------------- kernels
 // where a flagged thread's item goes in an order-preserving compaction of the workgroup's items, and how many there are
 __device__ inline int wg_offset(bool flag, int32_t* wcount, int& total) {
@@ -145,7 +165,7 @@ __device__ inline int wg_offset(bool flag, int32_t* wcount, int& total) {
     return before + __popcll(b & ((1ull << lane) - 1ull));
 }
 
-__global__ __launch_bounds__(TK_T) void k_trk_pretreat(Bufs B, Shape S) {
+__device__ __forceinline__ void trk_pretreat_body(const Bufs& B, const Shape& S) {
     __shared__ uint64_t s_out[kMaxOutliers];
     __shared__ int32_t wcount[TK_WAVES];
     const int tid = threadIdx.x;
@@ -188,10 +208,20 @@ __global__ __launch_bounds__(TK_T) void k_trk_pretreat(Bufs B, Shape S) {
     }
 }
 
+__global__ __launch_bounds__(TK_T) void k_trk_pretreat(Bufs B, Shape S) { trk_pretreat_body(B, S); }
+
+// The batched forms (tracker groups): member blockIdx.z, its arguments read from the group's table.  A member without a previous
+// pair leaves every one of them at once; a member that does not bootstrap leaves the bootstrap's.
+__global__ __launch_bounds__(TK_T) void k_trk_pretreat_g(const TrkRec* __restrict__ recs, Shape S) {
+    const TrkRec& r = recs[blockIdx.z];
+    if (r.skip) return;
+    trk_pretreat_body(r.B, S);
+}
+
 // The corners of a selection get ids next_id, next_id + 1, ... strongest first.  BOOT: they are the from-rows of this call, without a
 // track count (Tracker.cpp:181-189).  Otherwise they follow the kept rows and are this frame's newly extracted words (:330-336).
 template <bool BOOT>
-__global__ __launch_bounds__(TK_T) void k_trk_append(Bufs B, Shape S, const int32_t* n_out, const float* xy) {
+__device__ __forceinline__ void trk_append_body(const Bufs& B, const Shape& S, const int32_t* n_out, const float* xy) {
     Ctl* c = B.ctl;
     const int tid = threadIdx.x;
     const int base = BOOT ? 0 : c->n_kept;
@@ -217,6 +247,18 @@ __global__ __launch_bounds__(TK_T) void k_trk_append(Bufs B, Shape S, const int3
     }
 }
 
+template <bool BOOT>
+__global__ __launch_bounds__(TK_T) void k_trk_append(Bufs B, Shape S, const int32_t* n_out, const float* xy) {
+    trk_append_body<BOOT>(B, S, n_out, xy);
+}
+
+template <bool BOOT>
+__global__ __launch_bounds__(TK_T) void k_trk_append_g(const TrkRec* __restrict__ recs, Shape S) {
+    const TrkRec& r = recs[blockIdx.z];
+    if (r.skip || (BOOT && !r.boot)) return;
+    trk_append_body<BOOT>(r.B, S, r.corner_n, r.corner_xy);
+}
+
 struct WaveCells {                             // as in ba_flow.hip: cell s * 64 + lane in slot s, int64 butterfly
     static constexpr int kSlots = kLaneSlots;
     using acc_t = int32_t;
@@ -231,7 +273,8 @@ struct WaveCells {                             // as in ba_flow.hip: cell s * 64
 };
 
 template <bool BACK>
-__global__ __launch_bounds__(64) void k_trk_track(Bufs B, Shape S, Image I, Image J, LkParams prm, Layout lay, Guess g, int has_guess, float gate) {
+__device__ __forceinline__ void trk_track_body(const Bufs& B, const Shape& S, const Image& I, const Image& J, const LkParams& prm,
+                                               const Layout& lay, const Guess& g, int has_guess, float gate) {
     const int p = blockIdx.x;
     if (p >= min(B.ctl->n_from, S.M)) return;
     WaveCells pol{ (int)threadIdx.x };
@@ -251,7 +294,19 @@ __global__ __launch_bounds__(64) void k_trk_track(Bufs B, Shape S, Image I, Imag
     B.inb[p] = (in_bounds(tox, S.w) && in_bounds(toy, S.h)) ? 1 : 0;
 }
 
-__global__ __launch_bounds__(TK_T) void k_trk_reduce(Bufs B, Shape S) {
+template <bool BACK>
+__global__ __launch_bounds__(64) void k_trk_track(Bufs B, Shape S, Image I, Image J, LkParams prm, Layout lay, Guess g, int has_guess, float gate) {
+    trk_track_body<BACK>(B, S, I, J, prm, lay, g, has_guess, gate);
+}
+
+template <bool BACK>
+__global__ __launch_bounds__(64) void k_trk_track_g(const TrkRec* __restrict__ recs, Shape S, LkParams prm, Layout lay, float gate) {
+    const TrkRec& r = recs[blockIdx.z];
+    if (r.skip) return;
+    trk_track_body<BACK>(r.B, S, r.prev[0], r.cur[0], prm, lay, r.g, r.has_guess, gate);
+}
+
+__device__ __forceinline__ void trk_reduce_body(const Bufs& B, const Shape& S) {
     __shared__ int32_t wcount[TK_WAVES];
     const int tid = threadIdx.x;
     const int n = min(B.ctl->n_from, S.M);
@@ -278,6 +333,14 @@ __global__ __launch_bounds__(TK_T) void k_trk_reduce(Bufs B, Shape S) {
         c->n_kept = kept; c->n_rows = lost ? 0 : kept; c->lost = lost ? 1 : 0;
         c->corner_args[1] = lost ? 0 : S.M - kept;                                // backUpCornersCnt (:324)
     }
+}
+
+__global__ __launch_bounds__(TK_T) void k_trk_reduce(Bufs B, Shape S) { trk_reduce_body(B, S); }
+
+__global__ __launch_bounds__(TK_T) void k_trk_reduce_g(const TrkRec* __restrict__ recs, Shape S) {
+    const TrkRec& r = recs[blockIdx.z];
+    if (r.skip) return;
+    trk_reduce_body(r.B, S);
 }
 
 constexpr int kHwLds = 2048;                   // half-width entries kept in LDS (both radii together); larger tables are read in place
@@ -358,7 +421,7 @@ __device__ inline int draw_decision(const Bufs& B, const Shape& S, HW hw, int n_
     return nr;
 }
 
-__global__ __launch_bounds__(TK_T) void k_trk_discs(Bufs B, Shape S) {
+__device__ __forceinline__ void trk_discs_body(const Bufs& B, const Shape& S) {
     __shared__ uint32_t s_buf[2 * kMaxFeatures];       // the counts for the rank sort, then the raster's discs packed
     __shared__ int32_t s_hw[kHwLds];
     __shared__ int32_t wcount[TK_WAVES];
@@ -407,11 +470,20 @@ __global__ __launch_bounds__(TK_T) void k_trk_discs(Bufs B, Shape S) {
     if (tid == 0) { c->n_list = n_list; c->corner_args[0] = nr; }
 }
 
+__global__ __launch_bounds__(TK_T) void k_trk_discs(Bufs B, Shape S) { trk_discs_body(B, S); }
+
+__global__ __launch_bounds__(TK_T) void k_trk_discs_g(const TrkRec* __restrict__ recs, Shape S) {
+    const TrkRec& r = recs[blockIdx.z];
+    if (r.skip) return;
+    trk_discs_body(r.B, S);
+}
+
 // BOOT: the 3-D points of bootstrapped words: one forward pass previous left -> previous right, no reverse pass, no gate, the status
 // not looked at (Tracker.cpp:207-219).  Otherwise: the stereo pass of the frame with its gate, the bounds test of :376 and the
 // finite test of :390.
 template <bool BACK, bool BOOT>
-__global__ __launch_bounds__(64) void k_trk_stereo(Bufs B, Shape S, Image I, Image J, LkParams prm, Layout lay, Camera cam, float gate) {
+__device__ __forceinline__ void trk_stereo_body(const Bufs& B, const Shape& S, const Image& I, const Image& J, const LkParams& prm,
+                                                const Layout& lay, const Camera& cam, float gate) {
     const int p = blockIdx.x;
     const Ctl* c = B.ctl;
     const int n = BOOT ? c->n_from : (c->lost ? 0 : c->n_rows);
@@ -436,7 +508,20 @@ __global__ __launch_bounds__(64) void k_trk_stereo(Bufs B, Shape S, Image I, Ima
     }
 }
 
-__global__ __launch_bounds__(TK_T) void k_trk_finish(Bufs B, Shape S, int boot) {
+template <bool BACK, bool BOOT>
+__global__ __launch_bounds__(64) void k_trk_stereo(Bufs B, Shape S, Image I, Image J, LkParams prm, Layout lay, Camera cam, float gate) {
+    trk_stereo_body<BACK, BOOT>(B, S, I, J, prm, lay, cam, gate);
+}
+
+template <bool BACK, bool BOOT>
+__global__ __launch_bounds__(64) void k_trk_stereo_g(const TrkRec* __restrict__ recs, Shape S, LkParams prm, Layout lay, float gate) {
+    const TrkRec& r = recs[blockIdx.z];
+    if (r.skip || (BOOT && !r.boot)) return;
+    const Image* im = BOOT ? r.prev : r.cur;
+    trk_stereo_body<BACK, BOOT>(r.B, S, im[0], im[1], prm, lay, r.cam, gate);
+}
+
+__device__ __forceinline__ void trk_finish_body(const Bufs& B, const Shape& S, int boot) {
     __shared__ int32_t wcount[TK_WAVES];
     Ctl* c = B.ctl;
     const int tid = threadIdx.x;
@@ -475,6 +560,14 @@ __global__ __launch_bounds__(TK_T) void k_trk_finish(Bufs B, Shape S, int boot) 
     }
 }
 
+__global__ __launch_bounds__(TK_T) void k_trk_finish(Bufs B, Shape S, int boot) { trk_finish_body(B, S, boot); }
+
+__global__ __launch_bounds__(TK_T) void k_trk_finish_g(const TrkRec* __restrict__ recs, Shape S) {
+    const TrkRec& r = recs[blockIdx.z];
+    if (r.skip) return;
+    trk_finish_body(r.B, S, r.boot);
+}
+
 }  // namespace trk
 
 // ---------------------------------------------------------------- the object
@@ -499,6 +592,21 @@ struct visfs_tracker {
 
     Bufs B{};                                  // where the kernels (or the host steps) work
     Out R{};                                   // where the caller reads: the pinned copy, or the host twin's block itself
+
+    visfs_tracker_group* group = nullptr;      // the tracker group this is a member of
+};
+
+// n trackers processed by one call (include/visfs_tracker_group.h).  A call's tables stand in one block, pinned and on the device:
+// [PyrRec n][ClaheRec n][CornerRec n: bootstrap][CornerRec n: top-up][TrkRec n][InHead n][outlier ids of the members, one behind the other]
+struct visfs_tracker_group {
+    std::vector<visfs_tracker*> m;             // nullptr: the member has been destroyed
+    bool device = false;
+    std::string err;
+    GroupCounts cnt;
+    int dev = 0;
+    hipStream_t stream = nullptr;
+    char* p_blk = nullptr; char* d_blk = nullptr;
+    size_t off_pyr = 0, off_clahe = 0, off_boot = 0, off_top = 0, off_trk = 0, off_in = 0, off_ids = 0, blk_bytes = 0;
 };
 
 namespace {
@@ -818,6 +926,54 @@ void clear_result(visfs_tracker* t, visfs_tracker_result* r, int32_t flags, uint
     r->blocked_id = o.blk_id;
 }
 
+void leave_group(visfs_tracker* t) {
+    if (!t->group) return;
+    for (visfs_tracker*& m : t->group->m)
+        if (m == t) m = nullptr;
+    t->group = nullptr;
+}
+
+// the argument checks of a call; nothing has been pushed or changed when one fails
+int check_call(visfs_tracker* t, const uint8_t* left, const uint8_t* right, int32_t stride, const double* delta_guess, int32_t n_outliers,
+               const uint64_t* outlier_ids, const visfs_tracker_result* result) {
+    visfs_flow* f = t->f;
+    if (!f) return fail(t, VISFS_BA_ERR_NOT_LOADED, "the flow object of this tracker is gone");
+    if (!left || !right || !result) return fail(t, VISFS_BA_ERR_BAD_ARGUMENT, "a NULL argument");
+    if (stride < f->w) return fail(t, VISFS_BA_ERR_BAD_ARGUMENT, "stride is smaller than the image width");
+    if (n_outliers < 0 || n_outliers > kMaxOutliers) return fail(t, VISFS_BA_ERR_BAD_ARGUMENT, "n_outliers must lie in 0 .. 4096");
+    if (n_outliers > 0 && !outlier_ids) return fail(t, VISFS_BA_ERR_BAD_ARGUMENT, "outlier_ids is NULL");
+    if (delta_guess)
+        for (int i = 0; i < 12; ++i)
+            if (!std::isfinite(delta_guess[i])) return fail(t, VISFS_BA_ERR_BAD_ARGUMENT, "delta_guess is not finite");
+    if (f->frames != t->seen_frames)
+        return fail(t, VISFS_BA_ERR_NOT_LOADED, "the images of the flow object were pushed by another caller since this tracker's last call");
+    return VISFS_BA_OK;
+}
+
+// what the table will hold after pretreatment is known from the ids handed out last (Tracker.cpp:143-165)
+int32_t remaining_rows(const visfs_tracker* t, int32_t n_outliers, const uint64_t* outlier_ids) {
+    const std::unordered_set<uint64_t> out(outlier_ids, outlier_ids + n_outliers);
+    int32_t remaining = 0;
+    for (uint64_t id : t->ids) remaining += out.count(id) ? 0 : 1;
+    return remaining;
+}
+
+// the output block of a finished call into the caller's result and the tracker's id list
+int take_result(visfs_tracker* t, bool boot, visfs_tracker_result* result) {
+    const Head hd = *t->R.head;
+    if (hd.n_covis < 0 || hd.n_covis > t->S.M || hd.n_new < 0 || hd.n_new > t->S.M || hd.n_words < 0 || hd.n_words > t->S.M ||
+        hd.n_blocked < 0 || hd.n_blocked > t->S.M) {
+        t->ids.clear();
+        return fail(t, VISFS_BA_ERR_DEVICE, "the call returned an impossible count");
+    }
+    clear_result(t, result, hd.flags, hd.next_id);
+    result->n_covisible = hd.n_covis; result->n_new = hd.n_new; result->n_words = hd.n_words; result->n_blocked = hd.n_blocked;
+    t->ids.assign(t->R.w_id, t->R.w_id + hd.n_words);
+    t->have_call = true;
+    t->boot_last = boot;
+    return VISFS_BA_OK;
+}
+
 void detach(visfs_tracker* t) {
     if (!t->f) return;
     free_device(t);
@@ -883,6 +1039,7 @@ int visfs_tracker_create(visfs_flow* f, const visfs_tracker_params* p, const vis
 
 void visfs_tracker_destroy(visfs_tracker* t) {
     if (!t) return;
+    leave_group(t);
     detach(t);
     delete t;
 }
@@ -906,20 +1063,9 @@ int visfs_tracker_process(visfs_tracker* t, const uint8_t* left, const uint8_t* 
     if (!t) return VISFS_BA_ERR_BAD_ARGUMENT;
     return guarded_tk(t, [&]() -> int {
         visfs_flow* f = t->f;
-        if (!f) return fail(t, VISFS_BA_ERR_NOT_LOADED, "the flow object of this tracker is gone");
-        if (!left || !right || !result) return fail(t, VISFS_BA_ERR_BAD_ARGUMENT, "a NULL argument");
-        if (stride < f->w) return fail(t, VISFS_BA_ERR_BAD_ARGUMENT, "stride is smaller than the image width");
-        if (n_outliers < 0 || n_outliers > kMaxOutliers) return fail(t, VISFS_BA_ERR_BAD_ARGUMENT, "n_outliers must lie in 0 .. 4096");
-        if (n_outliers > 0 && !outlier_ids) return fail(t, VISFS_BA_ERR_BAD_ARGUMENT, "outlier_ids is NULL");
-        if (delta_guess)
-            for (int i = 0; i < 12; ++i)
-                if (!std::isfinite(delta_guess[i])) return fail(t, VISFS_BA_ERR_BAD_ARGUMENT, "delta_guess is not finite");
-        if (f->frames != t->seen_frames)
-            return fail(t, VISFS_BA_ERR_NOT_LOADED, "the images of the flow object were pushed by another caller since this tracker's last call");
-        // what the table will hold after pretreatment is known from the ids handed out last (Tracker.cpp:143-165)
-        const std::unordered_set<uint64_t> out(outlier_ids, outlier_ids + n_outliers);
-        int32_t remaining = 0;
-        for (uint64_t id : t->ids) remaining += out.count(id) ? 0 : 1;
+        const int rc_args = check_call(t, left, right, stride, delta_guess, n_outliers, outlier_ids, result);
+        if (rc_args != VISFS_BA_OK) return rc_args;
+        const int32_t remaining = remaining_rows(t, n_outliers, outlier_ids);
         const bool boot = remaining == 0;
         const bool no_previous = f->frames == 0;
         const int rc_push = t->prm.clahe ? visfs_flow_push_frame_clahe(f, &t->prm.clahe_params, left, right, stride)
@@ -955,18 +1101,7 @@ int visfs_tracker_process(visfs_tracker* t, const uint8_t* left, const uint8_t* 
             const int rc = host_topup_stereo_finish(t, boot);
             if (rc != VISFS_BA_OK) return rc;
         }
-        const Head hd = *t->R.head;
-        if (hd.n_covis < 0 || hd.n_covis > t->S.M || hd.n_new < 0 || hd.n_new > t->S.M || hd.n_words < 0 || hd.n_words > t->S.M ||
-            hd.n_blocked < 0 || hd.n_blocked > t->S.M) {
-            t->ids.clear();
-            return fail(t, VISFS_BA_ERR_DEVICE, "the call returned an impossible count");
-        }
-        clear_result(t, result, hd.flags, hd.next_id);
-        result->n_covisible = hd.n_covis; result->n_new = hd.n_new; result->n_words = hd.n_words; result->n_blocked = hd.n_blocked;
-        t->ids.assign(t->R.w_id, t->R.w_id + hd.n_words);
-        t->have_call = true;
-        t->boot_last = boot;
-        return (int)VISFS_BA_OK;
+        return take_result(t, boot, result);
     });
 }
 
@@ -1009,6 +1144,343 @@ int visfs_tracker_download(const visfs_tracker* ct, int32_t* n_from, float* gues
         if (f->device) TK_HIP(t, hipStreamSynchronize(f->stream));
         return (int)VISFS_BA_OK;
     });
+}
+
+}  // extern "C"
+
+// ====================================================================== tracker groups (include/visfs_tracker_group.h)
+namespace {
+
+thread_local std::string g_create_err;         // why the last visfs_tracker_group_create of this thread refused
+
+int refuse(int rc, int member, const std::string& why) {
+    g_create_err = member >= 0 ? "member " + std::to_string(member) + ": " + why : why;
+    return rc;
+}
+
+int gfail(visfs_tracker_group* g, int rc, int member, const std::string& why) {
+    g->err = member >= 0 ? "member " + std::to_string(member) + ": " + why : why;
+    return rc;
+}
+#define GR_HIP(g, expr)                                                                                   \
+    do {                                                                                                  \
+        hipError_t e_ = (expr);                                                                           \
+        if (e_ != hipSuccess) return gfail((g), VISFS_BA_ERR_DEVICE, -1, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+bool same_flow_params(const visfs_flow_params& a, const visfs_flow_params& b) {
+    return a.win_size == b.win_size && a.max_level == b.max_level && a.iterations == b.iterations && a.eps == b.eps &&
+           a.flow_back == b.flow_back && a.min_eig_threshold == b.min_eig_threshold && a.back_gate_track == b.back_gate_track &&
+           a.back_gate_stereo == b.back_gate_stereo && a.min_depth == b.min_depth && a.max_depth == b.max_depth;
+}
+
+bool same_tracker_params(const visfs_tracker_params& a, const visfs_tracker_params& b) {
+    return a.max_features == b.max_features && a.quality_level == b.quality_level && a.min_distance == b.min_distance &&
+           a.min_inliers == b.min_inliers && (a.clahe != 0) == (b.clahe != 0) && a.clahe_params.clip_limit == b.clahe_params.clip_limit &&
+           a.clahe_params.tiles_x == b.clahe_params.tiles_x && a.clahe_params.tiles_y == b.clahe_params.tiles_y;
+}
+
+size_t up256(size_t x) { return (x + 255) & ~size_t(255); }
+
+void free_group(visfs_tracker_group* g) {
+    if (!g->device) return;
+    (void)hipSetDevice(g->dev);
+    if (g->stream) (void)hipStreamSynchronize(g->stream);
+    if (g->d_blk) (void)hipFree(g->d_blk);
+    if (g->p_blk) (void)hipHostFree(g->p_blk);
+    g->d_blk = g->p_blk = nullptr;
+}
+
+int allocate_group(visfs_tracker_group* g) {
+    const size_t n = g->m.size();
+    size_t off = 0;
+    const auto take = [&](size_t bytes) { const size_t at = off; off = up256(off + bytes); return at; };
+    g->off_pyr = take(n * sizeof(PyrRec));
+    g->off_clahe = take(n * sizeof(ClaheRec));
+    g->off_boot = take(n * sizeof(CornerRec));
+    g->off_top = take(n * sizeof(CornerRec));
+    g->off_trk = take(n * sizeof(TrkRec));
+    g->off_in = take(n * sizeof(InHead));
+    g->off_ids = take(n * sizeof(uint64_t) * kMaxOutliers);
+    g->blk_bytes = off;
+    GR_HIP(g, hipSetDevice(g->dev));
+    GR_HIP(g, hipMalloc(reinterpret_cast<void**>(&g->d_blk), g->blk_bytes));
+    GR_HIP(g, hipHostMalloc(reinterpret_cast<void**>(&g->p_blk), g->blk_bytes, hipHostMallocDefault));
+    std::memset(g->p_blk, 0, g->blk_bytes);
+    return VISFS_BA_OK;
+}
+
+struct MemberPlan {                            // what the host decides for a member before anything is pushed
+    bool no_previous, boot, has_guess;
+    int32_t from_bound;
+    int slot;                                  // where the pair goes
+    Guess g;
+};
+
+// The launches of device_call for every member at once.  Nothing here waits for a value read back; the one wait in front is the one
+// device_stage has (the pinned staging images and the pinned table of the call before have left), the one behind ends the call.
+int group_device_call(visfs_tracker_group* g, const visfs_tracker_frame* fr, const std::vector<MemberPlan>& plan) {
+    const int n = (int)g->m.size();
+    visfs_tracker* t0 = g->m[0];
+    visfs_flow* f0 = t0->f;
+    const Shape S = t0->S;
+    const bool clahe_on = t0->prm.clahe != 0, back = f0->prm.flow_back != 0;
+    const clahe::Geom geom = clahe_on ? clahe::make_geom(f0->w, f0->h, t0->prm.clahe_params.tiles_x, t0->prm.clahe_params.tiles_y,
+                                                         t0->prm.clahe_params.clip_limit)
+                                      : clahe::Geom{};
+    GroupCounts& cnt = g->cnt;
+    GR_HIP(g, hipSetDevice(g->dev));
+    GR_HIP(g, hipStreamSynchronize(g->stream));
+    ++cnt.syncs;
+    PyrRec* pyr = reinterpret_cast<PyrRec*>(g->p_blk + g->off_pyr);
+    ClaheRec* clr = reinterpret_cast<ClaheRec*>(g->p_blk + g->off_clahe);
+    CornerRec* cboot = reinterpret_cast<CornerRec*>(g->p_blk + g->off_boot);
+    CornerRec* ctop = reinterpret_cast<CornerRec*>(g->p_blk + g->off_top);
+    TrkRec* trk = reinterpret_cast<TrkRec*>(g->p_blk + g->off_trk);
+    InHead* inh = reinterpret_cast<InHead*>(g->p_blk + g->off_in);
+    uint64_t* ids = reinterpret_cast<uint64_t*>(g->p_blk + g->off_ids);
+    size_t n_ids = 0;
+    bool any_active = false, any_boot = false;
+    int32_t bound = 0;
+    for (int i = 0; i < n; ++i) {
+        visfs_tracker* t = g->m[i];
+        visfs_flow* f = t->f;
+        const MemberPlan& P = plan[i];
+        const int cur = P.slot, prev = 1 - P.slot;
+        int rc;
+        if (clahe_on) {
+            uint8_t* raw[2];
+            group_clahe_fill(f, geom, cur, &clr[i], raw);
+            rc = group_stage(f, raw, fr[i].left, fr[i].right, fr[i].stride, &cnt);
+        } else {
+            rc = group_stage(f, f->dpx[cur], fr[i].left, fr[i].right, fr[i].stride, &cnt);
+        }
+        if (rc != VISFS_BA_OK) return gfail(g, rc, i, f->err);
+        group_pyr_fill(f, cur, &pyr[i]);
+        const bool skip = P.no_previous;
+        TrkRec& r = trk[i];
+        r.B = t->B;
+        r.B.in = reinterpret_cast<const InHead*>(g->d_blk + g->off_in) + i;
+        r.B.outliers = reinterpret_cast<const uint64_t*>(g->d_blk + g->off_ids) + n_ids;
+        inh[i] = InHead{ fr[i].n_outliers, 0 };
+        if (fr[i].n_outliers > 0) std::memcpy(ids + n_ids, fr[i].outlier_ids, sizeof(uint64_t) * (size_t)fr[i].n_outliers);
+        n_ids += (size_t)fr[i].n_outliers;
+        for (int k = 0; k < 2; ++k) {
+            r.prev[k] = Image{ f->dpx[prev][k], f->dder[prev][k] };
+            r.cur[k] = Image{ f->dpx[cur][k], f->dder[cur][k] };
+        }
+        r.cam = make_camera(f->prm, t->cam);
+        r.g = P.g;
+        r.has_guess = P.has_guess ? 1 : 0; r.skip = skip ? 1 : 0; r.boot = P.boot ? 1 : 0; r.pad = 0;
+        // both extractions of a member work in the same state, one behind the other in stream order
+        group_corners_fill(f, f->dpx[prev][0], nullptr, nullptr, t->B.ctl->boot_args, skip || !P.boot, &cboot[i], &r.corner_n, &r.corner_xy);
+        group_corners_fill(f, f->dpx[cur][0], t->B.raster, t->B.hw, t->B.ctl->corner_args, skip, &ctop[i], &r.corner_n, &r.corner_xy);
+        if (!skip) {
+            any_active = true;
+            any_boot = any_boot || P.boot;
+            bound = std::max(bound, P.from_bound);
+            t->have_call = false;
+        }
+    }
+    GR_HIP(g, hipMemcpyAsync(g->d_blk, g->p_blk, g->off_ids + sizeof(uint64_t) * n_ids, hipMemcpyHostToDevice, g->stream));
+    ++cnt.copies;
+    const auto dev = [&](size_t off) { return g->d_blk + off; };
+    int rc;
+    if (clahe_on) {
+        rc = group_clahe(f0, geom, n, reinterpret_cast<const ClaheRec*>(dev(g->off_clahe)), &cnt);
+        if (rc != VISFS_BA_OK) return gfail(g, rc, -1, f0->err);
+    }
+    rc = group_pyramids(f0, n, reinterpret_cast<const PyrRec*>(dev(g->off_pyr)), &cnt);
+    if (rc != VISFS_BA_OK) return gfail(g, rc, -1, f0->err);
+    if (any_active) {
+        const TrkRec* d_trk = reinterpret_cast<const TrkRec*>(dev(g->off_trk));
+        const unsigned z = (unsigned)n;
+        const dim3 one(1, 1, z), rows((unsigned)S.M, 1, z), wg(TK_T), wave(64);
+        const double quality = t0->prm.quality_level, min_distance = (double)t0->prm.min_distance;
+#define GR_LAUNCH(kernel, grid, block, ...)                                                  \
+    do {                                                                                     \
+        hipLaunchKernelGGL(kernel, grid, block, 0, g->stream, __VA_ARGS__);                  \
+        GR_HIP(g, hipGetLastError());                                                        \
+        ++cnt.kernels;                                                                       \
+    } while (0)
+        GR_LAUNCH(k_trk_pretreat_g, one, wg, d_trk, S);
+        if (any_boot) {
+            rc = group_corners(f0, quality, min_distance, n, reinterpret_cast<const CornerRec*>(dev(g->off_boot)), &cnt);
+            if (rc != VISFS_BA_OK) return gfail(g, rc, -1, f0->err);
+            GR_LAUNCH((k_trk_append_g<true>), one, wg, d_trk, S);
+            GR_LAUNCH((k_trk_stereo_g<false, true>), rows, wave, d_trk, S, f0->lk, f0->lay, 0.0f);
+        }
+        if (bound > 0) {
+            const dim3 grid((unsigned)bound, 1, z);
+            if (back) GR_LAUNCH((k_trk_track_g<true>), grid, wave, d_trk, S, f0->lk, f0->lay, f0->prm.back_gate_track);
+            else GR_LAUNCH((k_trk_track_g<false>), grid, wave, d_trk, S, f0->lk, f0->lay, f0->prm.back_gate_track);
+        }
+        GR_LAUNCH(k_trk_reduce_g, one, wg, d_trk, S);
+        GR_LAUNCH(k_trk_discs_g, one, wg, d_trk, S);
+        rc = group_corners(f0, quality, min_distance, n, reinterpret_cast<const CornerRec*>(dev(g->off_top)), &cnt);
+        if (rc != VISFS_BA_OK) return gfail(g, rc, -1, f0->err);
+        GR_LAUNCH((k_trk_append_g<false>), one, wg, d_trk, S);
+        if (back) GR_LAUNCH((k_trk_stereo_g<true, false>), rows, wave, d_trk, S, f0->lk, f0->lay, f0->prm.back_gate_stereo);
+        else GR_LAUNCH((k_trk_stereo_g<false, false>), rows, wave, d_trk, S, f0->lk, f0->lay, f0->prm.back_gate_stereo);
+        GR_LAUNCH(k_trk_finish_g, one, wg, d_trk, S);
+#undef GR_LAUNCH
+        for (int i = 0; i < n; ++i) {
+            if (plan[i].no_previous) continue;
+            visfs_tracker* t = g->m[i];
+            GR_HIP(g, hipMemcpyAsync(t->p_out, t->d_out, t->out_bytes, hipMemcpyDeviceToHost, g->stream));
+            ++cnt.copies;
+        }
+    }
+    GR_HIP(g, hipStreamSynchronize(g->stream));
+    ++cnt.syncs;
+    return VISFS_BA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int visfs_tracker_group_abi_version(void) { return VISFS_TRACKER_GROUP_ABI_VERSION; }
+
+int visfs_tracker_group_create(int32_t n, visfs_tracker* const* members, visfs_tracker_group** out) {
+    if (!out) return refuse(VISFS_BA_ERR_BAD_ARGUMENT, -1, "out is NULL");
+    *out = nullptr;
+    try {
+        if (n < 1 || n > VISFS_TRACKER_GROUP_MAX) return refuse(VISFS_BA_ERR_UNSUPPORTED, -1, "the number of members must lie in 1 .. 64");
+        if (!members) return refuse(VISFS_BA_ERR_BAD_ARGUMENT, -1, "members is NULL");
+        for (int i = 0; i < n; ++i) {
+            const visfs_tracker* t = members[i];
+            if (!t) return refuse(VISFS_BA_ERR_BAD_ARGUMENT, i, "a NULL tracker");
+            if (!t->f) return refuse(VISFS_BA_ERR_NOT_LOADED, i, "the flow object of this tracker is gone");
+            if (t->group) return refuse(VISFS_BA_ERR_BAD_ARGUMENT, i, "the tracker is in a group already");
+            const visfs_flow *f = t->f, *f0 = members[0]->f;
+            if (f->device != f0->device) return refuse(VISFS_BA_ERR_BAD_ARGUMENT, i, "device and host-twin trackers cannot share a group");
+            if (f->device && f->ba != f0->ba) return refuse(VISFS_BA_ERR_BAD_ARGUMENT, i, "the tracker belongs to another handle");
+            for (int k = 0; k < i; ++k)
+                if (members[k]->f == f) return refuse(VISFS_BA_ERR_BAD_ARGUMENT, i, "the tracker shares its flow object with member " + std::to_string(k));
+            if (f->w != f0->w || f->h != f0->h) return refuse(VISFS_BA_ERR_BAD_ARGUMENT, i, "the image size differs from member 0's");
+            if (!same_flow_params(f->prm, f0->prm)) return refuse(VISFS_BA_ERR_BAD_ARGUMENT, i, "the flow parameters differ from member 0's");
+            if (!same_tracker_params(t->prm, members[0]->prm)) return refuse(VISFS_BA_ERR_BAD_ARGUMENT, i, "the tracker parameters differ from member 0's");
+        }
+        visfs_tracker_group* g = new visfs_tracker_group();
+        g->m.assign(members, members + n);
+        visfs_flow* f0 = members[0]->f;
+        g->device = f0->device;
+        if (g->device) {
+            g->dev = f0->dev; g->stream = f0->stream;
+            int rc = allocate_group(g);
+            for (int i = 0; i < n && rc == VISFS_BA_OK; ++i) {
+                visfs_flow* f = members[i]->f;
+                rc = group_corners_prepare(f);
+                if (rc == VISFS_BA_OK && members[i]->prm.clahe) rc = group_clahe_prepare(f);
+                if (rc != VISFS_BA_OK) gfail(g, rc, i, f->err);
+            }
+            if (rc != VISFS_BA_OK) {
+                g_create_err = g->err;
+                free_group(g);
+                delete g;
+                return rc;
+            }
+        }
+        for (int i = 0; i < n; ++i) members[i]->group = g;
+        g_create_err.clear();
+        *out = g;
+        return VISFS_BA_OK;
+    } catch (...) {
+        return refuse(VISFS_BA_ERR_DEVICE, -1, "out of host memory");
+    }
+}
+
+void visfs_tracker_group_destroy(visfs_tracker_group* g) {
+    if (!g) return;
+    for (visfs_tracker* t : g->m)
+        if (t) t->group = nullptr;
+    free_group(g);
+    delete g;
+}
+
+// g == NULL: why the last visfs_tracker_group_create of the calling thread refused
+const char* visfs_tracker_group_last_error(const visfs_tracker_group* g) { return g ? g->err.c_str() : g_create_err.c_str(); }
+
+int visfs_tracker_group_last_counts(const visfs_tracker_group* g, int32_t* kernel_launches, int32_t* copies_and_memsets,
+                                    int32_t* synchronisations) {
+    if (!g) return VISFS_BA_ERR_BAD_ARGUMENT;
+    if (kernel_launches) *kernel_launches = g->cnt.kernels;
+    if (copies_and_memsets) *copies_and_memsets = g->cnt.copies;
+    if (synchronisations) *synchronisations = g->cnt.syncs;
+    return VISFS_BA_OK;
+}
+
+int visfs_tracker_group_process(visfs_tracker_group* g, const visfs_tracker_frame* frames, visfs_tracker_result* results) {
+    if (!g) return VISFS_BA_ERR_BAD_ARGUMENT;
+    try {
+        g->cnt = GroupCounts{};
+        if (!frames || !results) return gfail(g, VISFS_BA_ERR_BAD_ARGUMENT, -1, "a NULL argument");
+        const int n = (int)g->m.size();
+        // every check of every member before anything is pushed
+        for (int i = 0; i < n; ++i) {
+            visfs_tracker* t = g->m[i];
+            if (!t) return gfail(g, VISFS_BA_ERR_NOT_LOADED, i, "the tracker has been destroyed");
+            const visfs_tracker_frame& fr = frames[i];
+            const int rc = check_call(t, fr.left, fr.right, fr.stride, fr.delta_guess, fr.n_outliers, fr.outlier_ids, &results[i]);
+            if (rc != VISFS_BA_OK) return gfail(g, rc, i, t->err);
+        }
+        if (!g->device) {                      // the host twin: its members in sequence on one core
+            for (int i = 0; i < n; ++i) {
+                const visfs_tracker_frame& fr = frames[i];
+                const int rc = visfs_tracker_process(g->m[i], fr.left, fr.right, fr.stride, fr.delta_guess, fr.n_outliers, fr.outlier_ids,
+                                                     &results[i]);
+                if (rc != VISFS_BA_OK) return gfail(g, rc, i, g->m[i]->err);
+            }
+            return VISFS_BA_OK;
+        }
+        std::vector<MemberPlan> plan((size_t)n);
+        for (int i = 0; i < n; ++i) {
+            visfs_tracker* t = g->m[i];
+            const visfs_flow* f = t->f;
+            const visfs_tracker_frame& fr = frames[i];
+            MemberPlan& P = plan[(size_t)i];
+            const int32_t remaining = remaining_rows(t, fr.n_outliers, fr.outlier_ids);
+            P.boot = remaining == 0;
+            P.no_previous = f->frames == 0;
+            P.from_bound = P.boot ? t->S.M : remaining;
+            P.slot = f->frames == 0 ? f->cur : 1 - f->cur;
+            P.has_guess = fr.delta_guess != nullptr;
+            P.g = Guess{};
+            if (P.has_guess) {
+                guess_camera_ref(fr.delta_guess, t->cam.Tir, P.g);
+                P.g.fx = (double)t->cam.fx; P.g.fy = (double)t->cam.fy; P.g.cx = (double)t->cam.cx; P.g.cy = (double)t->cam.cy;
+            }
+        }
+        const int rc = group_device_call(g, frames, plan);
+        if (rc != VISFS_BA_OK) {
+            for (visfs_tracker* t : g->m) t->ids.clear();
+            return rc;
+        }
+        const bool clahe_on = g->m[0]->prm.clahe != 0;
+        int rc_all = VISFS_BA_OK;
+        for (int i = 0; i < n; ++i) {
+            visfs_tracker* t = g->m[i];
+            visfs_flow* f = t->f;
+            const MemberPlan& P = plan[(size_t)i];
+            if (clahe_on)
+                group_clahe_pushed(f, clahe::make_geom(f->w, f->h, t->prm.clahe_params.tiles_x, t->prm.clahe_params.tiles_y,
+                                                       t->prm.clahe_params.clip_limit));
+            f->cur = P.slot;
+            ++f->frames;
+            t->seen_frames = f->frames;
+            if (P.no_previous) {
+                clear_result(t, &results[i], kNoPrevious, 0);
+                t->have_call = false;
+                continue;
+            }
+            const int rc_i = take_result(t, P.boot, &results[i]);
+            if (rc_i != VISFS_BA_OK && rc_all == VISFS_BA_OK) rc_all = gfail(g, rc_i, i, t->err);
+        }
+        return rc_all;
+    } catch (...) {
+        return gfail(g, VISFS_BA_ERR_DEVICE, -1, "out of host memory");
+    }
 }
 
 }  // extern "C"

@@ -4,6 +4,9 @@
 // What the reference keeps in trackCnt_, globalFeatureId_, the words of lastSignature_ and the blocked words of pretreatment lives
 // in the library; this class turns the arrays of a call into the std::maps the Signature setters take (ascending id, as uKeys and
 // uValues read them) and keeps the one test that belongs to the caller's types: getDeltaPoseGuess().isApprox(Identity) (:237).
+//
+// VISFS::ResidentTrackerGroup runs the imageProcess of several ResidentTrackers (a rig's cameras) in one call of
+// include/visfs_tracker_group.h.
 #ifndef VISFS_AMD_RESIDENT_TRACKER_H
 #define VISFS_AMD_RESIDENT_TRACKER_H
 
@@ -16,6 +19,7 @@
 #include <vector>
 
 #include "visfs_tracker.h"
+#include "visfs_tracker_group.h"
 
 namespace VISFS {
 
@@ -81,6 +85,18 @@ public:
                                              ids.empty() ? nullptr : ids.data(), &r);
         out = Frame();
         if (rc != VISFS_BA_OK) return rc;
+        fill(r, out);
+        return rc;
+    }
+
+    int reset() { return visfs_tracker_reset(t_); }
+    const char* lastError() const { return visfs_tracker_last_error(t_); }
+    visfs_tracker* handle() { return t_; }
+
+private:
+    friend class ResidentTrackerGroup;
+    // the arrays of a call as the maps the Signature setters take
+    static void fill(const visfs_tracker_result& r, Frame& out) {
         out.noPrevious = (r.flags & VISFS_TRACKER_NO_PREVIOUS) != 0;
         out.bootstrapped = (r.flags & VISFS_TRACKER_BOOTSTRAPPED) != 0;
         out.lost = (r.flags & VISFS_TRACKER_LOST) != 0;
@@ -101,18 +117,71 @@ public:
             out.trackCount.emplace_hint(out.trackCount.end(), id, (int)r.word_count[i]);
         }
         for (int32_t i = 0; i < r.n_blocked; ++i) out.blockedWords.insert(out.blockedWords.end(), (std::size_t)r.blocked_id[i]);
-        return rc;
     }
-
-    int reset() { return visfs_tracker_reset(t_); }
-    const char* lastError() const { return visfs_tracker_last_error(t_); }
-    visfs_tracker* handle() { return t_; }
-
-private:
     static Point2f p2(const float* a, int32_t i) { return Point2f{ a[2 * i], a[2 * i + 1] }; }
     static Point3f p3(const float* a, int32_t i) { return Point3f{ a[3 * i], a[3 * i + 1], a[3 * i + 2] }; }
     visfs_tracker* t_ = nullptr;
     std::vector<std::size_t> outliers_;
+};
+
+// Tracker::imageProcess of every camera of a rig in one call.  The members are ResidentTrackers on flow objects of their own (all of
+// one handle, or all host twins) with equal keys and image size; they must outlive the group and stay usable on their own.
+class ResidentTrackerGroup {
+public:
+    struct Input {
+        const uint8_t* left; const uint8_t* right; int stride;
+        const double* deltaPoseGuess;                                  // 4 x 4 row-major or nullptr, as ResidentTracker::imageProcess takes it
+    };
+
+    ResidentTrackerGroup(const ResidentTrackerGroup&) = delete;
+    ResidentTrackerGroup& operator=(const ResidentTrackerGroup&) = delete;
+
+    explicit ResidentTrackerGroup(const std::vector<ResidentTracker*>& members) : members_(members) {
+        std::vector<visfs_tracker*> h;
+        for (ResidentTracker* m : members_) h.push_back(m->t_);
+        const int rc = visfs_tracker_group_create((int32_t)h.size(), h.data(), &g_);
+        if (rc != VISFS_BA_OK)
+            throw std::runtime_error("visfs_tracker_group_create failed with status " + std::to_string(rc) + ": " + visfs_tracker_group_last_error(nullptr));
+    }
+    ~ResidentTrackerGroup() { visfs_tracker_group_destroy(g_); }
+
+    // Each member's pretreatment() outliers go in and are used up, as in its own imageProcess.  out[i] is member i's Frame.
+    int imageProcess(const std::vector<Input>& in, std::vector<ResidentTracker::Frame>& out) {
+        const std::size_t n = members_.size();
+        if (in.size() != n) return VISFS_BA_ERR_BAD_ARGUMENT;
+        std::vector<std::vector<uint64_t>> ids(n);
+        std::vector<visfs_tracker_frame> fr(n);
+        std::vector<visfs_tracker_result> res(n);
+        for (std::size_t i = 0; i < n; ++i) {
+            ids[i].assign(members_[i]->outliers_.begin(), members_[i]->outliers_.end());
+            const bool guessSet = in[i].deltaPoseGuess != nullptr && !ResidentTracker::isIdentity(in[i].deltaPoseGuess);
+            fr[i].left = in[i].left; fr[i].right = in[i].right; fr[i].stride = in[i].stride;
+            fr[i].delta_guess = guessSet ? in[i].deltaPoseGuess : nullptr;
+            fr[i].n_outliers = (int32_t)ids[i].size();
+            fr[i].outlier_ids = ids[i].empty() ? nullptr : ids[i].data();
+        }
+        const int rc = visfs_tracker_group_process(g_, fr.data(), res.data());
+        out.assign(n, ResidentTracker::Frame());
+        if (rc != VISFS_BA_OK) return rc;                              // nothing was pushed: the outliers stay for the next call
+        for (std::size_t i = 0; i < n; ++i) {
+            members_[i]->outliers_.clear();
+            ResidentTracker::fill(res[i], out[i]);
+        }
+        return rc;
+    }
+
+    // what the last imageProcess issued on the device (all zero for host twins)
+    void lastCounts(int& kernelLaunches, int& copiesAndMemsets, int& synchronisations) const {
+        int32_t k = 0, c = 0, s = 0;
+        visfs_tracker_group_last_counts(g_, &k, &c, &s);
+        kernelLaunches = k; copiesAndMemsets = c; synchronisations = s;
+    }
+    const char* lastError() const { return visfs_tracker_group_last_error(g_); }
+    std::size_t size() const { return members_.size(); }
+
+private:
+    std::vector<ResidentTracker*> members_;
+    visfs_tracker_group* g_ = nullptr;
 };
 
 }  // namespace VISFS

@@ -2,6 +2,7 @@
 
 `Tracker(flow_obj, cam, **params)` keeps the word table of Tracker::imageProcess next to the pyramids of a `flow.Flow`: HIP kernels
 when that object lives on a solver's device, the one-core host restatement otherwise.  `process(left, right, ...)` is one frame.
+`TrackerGroup(members)` (include/visfs_tracker_group.h) takes the frames of several trackers of one solver in one call.
 """
 import ctypes as C
 
@@ -16,6 +17,12 @@ EXPORTS = [
     "visfs_tracker_abi_version", "visfs_tracker_default_params", "visfs_tracker_create", "visfs_tracker_destroy",
     "visfs_tracker_last_error", "visfs_tracker_reset", "visfs_tracker_process", "visfs_tracker_download",
 ]
+GROUP_ABI_VERSION = 1
+GROUP_EXPORTS = [
+    "visfs_tracker_group_abi_version", "visfs_tracker_group_create", "visfs_tracker_group_destroy", "visfs_tracker_group_last_error",
+    "visfs_tracker_group_process", "visfs_tracker_group_last_counts",
+]
+GROUP_MAX = 64
 MAX_FEATURES = 4096
 MAX_OUTLIERS = 4096
 NO_PREVIOUS, BOOTSTRAPPED, LOST = 1, 2, 4
@@ -41,15 +48,21 @@ class Result(C.Structure):
                 ("blocked_id", _pu64)]
 
 
+class Frame(C.Structure):
+    _fields_ = [("left", C.c_void_p), ("right", C.c_void_p), ("stride", C.c_int32), ("delta_guess", _pd), ("n_outliers", C.c_int32),
+                ("outlier_ids", _pu64)]
+
+
 _lib = None
 
 
-def load():
+def load(require_group=True):
+    """require_group=False: for a library built before tracker groups existed (the timing tools load a parent commit's build)."""
     global _lib
     if _lib is not None:
         return _lib
     lib = backend.load_library()
-    for name in EXPORTS:
+    for name in EXPORTS + (GROUP_EXPORTS if require_group else []):
         if not hasattr(lib, name):
             raise backend.BackendError(f"libvisfs_ba_hip.so does not export {name}")
     lib.visfs_tracker_abi_version.restype = C.c_int
@@ -69,6 +82,20 @@ def load():
     lib.visfs_tracker_download.restype = C.c_int
     if lib.visfs_tracker_abi_version() != ABI_VERSION:
         raise backend.BackendError("ABI version mismatch between visfs_amd/tracker.py and libvisfs_ba_hip.so")
+    if require_group:
+        lib.visfs_tracker_group_abi_version.restype = C.c_int
+        lib.visfs_tracker_group_create.argtypes = [C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+        lib.visfs_tracker_group_create.restype = C.c_int
+        lib.visfs_tracker_group_destroy.argtypes = [C.c_void_p]
+        lib.visfs_tracker_group_destroy.restype = None
+        lib.visfs_tracker_group_last_error.argtypes = [C.c_void_p]
+        lib.visfs_tracker_group_last_error.restype = C.c_char_p
+        lib.visfs_tracker_group_process.argtypes = [C.c_void_p, C.POINTER(Frame), C.POINTER(Result)]
+        lib.visfs_tracker_group_process.restype = C.c_int
+        lib.visfs_tracker_group_last_counts.argtypes = [C.c_void_p, _pi32, _pi32, _pi32]
+        lib.visfs_tracker_group_last_counts.restype = C.c_int
+        if lib.visfs_tracker_group_abi_version() != GROUP_ABI_VERSION:
+            raise backend.BackendError("tracker group ABI version mismatch between visfs_amd/tracker.py and libvisfs_ba_hip.so")
     _lib = lib
     return lib
 
@@ -143,8 +170,8 @@ class Tracker:
         if rc != abi.OK:
             raise backend.BackendError(f"tracker reset: status {rc}: {self.last_error()}")
 
-    def process_status(self, left, right, delta_guess=None, outliers=(), n_outliers=None):
-        """(status, result dict or None).  delta_guess: None or 3x4 (or 4x4) row-major; outliers: ids."""
+    def _arguments(self, left, right, delta_guess, outliers, n_outliers):
+        """The arrays of a call, checked and contiguous: (left, right, guess or None, ids, n_outliers)."""
         f = self.flow
         imgs = []
         for im in (left, right):
@@ -159,19 +186,26 @@ class Tracker:
         if delta_guess is not None:
             g = np.ascontiguousarray(np.asarray(delta_guess, dtype=np.float64).reshape(-1)[:12])
         ids = np.ascontiguousarray(np.asarray(list(outliers), dtype=np.uint64))
-        n = len(ids) if n_outliers is None else int(n_outliers)
-        res = Result()
-        rc = self._lib.visfs_tracker_process(self.h, imgs[0].ctypes.data if imgs[0] is not None else None,
-                                             imgs[1].ctypes.data if imgs[1] is not None else None, f.width,
-                                             g.ctypes.data_as(_pd) if g is not None else None, n,
-                                             ids.ctypes.data_as(_pu64) if len(ids) else None, C.byref(res))
-        if rc != abi.OK:
-            return rc, None
+        return imgs[0], imgs[1], g, ids, (len(ids) if n_outliers is None else int(n_outliers))
+
+    def _unpack(self, res):
         counts = dict(covisible=res.n_covisible, new=res.n_new, word=res.n_words, blocked=res.n_blocked)
         out = dict(flags=res.flags, next_id=int(res.next_id))
         for name, width, dtype in _FIELDS:
             out[name] = self._take(res, name, counts[name.split("_")[0]], width, dtype)
-        return rc, out
+        return out
+
+    def process_status(self, left, right, delta_guess=None, outliers=(), n_outliers=None):
+        """(status, result dict or None).  delta_guess: None or 3x4 (or 4x4) row-major; outliers: ids."""
+        left, right, g, ids, n = self._arguments(left, right, delta_guess, outliers, n_outliers)
+        res = Result()
+        rc = self._lib.visfs_tracker_process(self.h, left.ctypes.data if left is not None else None,
+                                             right.ctypes.data if right is not None else None, self.flow.width,
+                                             g.ctypes.data_as(_pd) if g is not None else None, n,
+                                             ids.ctypes.data_as(_pu64) if len(ids) else None, C.byref(res))
+        if rc != abi.OK:
+            return rc, None
+        return rc, self._unpack(res)
 
     def process(self, left, right, delta_guess=None, outliers=()):
         rc, out = self.process_status(left, right, delta_guess, outliers)
@@ -196,3 +230,76 @@ class Tracker:
         return dict(guess_xy=guess[:nf.value].copy(), to_xy=to[:nf.value].copy(), lk_status=st[:nf.value].copy(),
                     in_bounds=inb[:nf.value].copy(), discs=discs[:nd.value].copy(), disc_drawn=drawn[:nd.value].copy(),
                     stereo_status=sst[:nr.value].copy())
+
+
+def group_create_status(members):
+    """(status, handle or None, error text) without raising: what the argument tests look at."""
+    lib = load()
+    arr = (C.c_void_p * max(len(members), 1))(*[m.h for m in members])
+    h = C.c_void_p()
+    rc = lib.visfs_tracker_group_create(len(members), arr, C.byref(h))
+    return rc, (h if rc == abi.OK else None), lib.visfs_tracker_group_last_error(None).decode()
+
+
+class TrackerGroup:
+    """Several Trackers (each on a Flow of its own, all on one solver or all host twins, equal parameters and image size) processed by
+    one call.  The members stay usable on their own and must stay open while the group is used."""
+
+    def __init__(self, members):
+        self._lib = load()
+        self.members = list(members)
+        rc, h, why = group_create_status(self.members)
+        if rc != abi.OK:
+            self.h = None
+            raise backend.BackendError(f"visfs_tracker_group_create failed with status {rc}: {why}")
+        self.h = h
+
+    def close(self):
+        if self.h:
+            self._lib.visfs_tracker_group_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def last_error(self):
+        return self._lib.visfs_tracker_group_last_error(self.h).decode()
+
+    def last_counts(self):
+        """dict(kernel_launches, copies_and_memsets, synchronisations) of the last process call; all zero for host twins."""
+        k, c, s = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        rc = self._lib.visfs_tracker_group_last_counts(self.h, C.byref(k), C.byref(c), C.byref(s))
+        if rc != abi.OK:
+            raise backend.BackendError(f"tracker group counts: status {rc}")
+        return dict(kernel_launches=k.value, copies_and_memsets=c.value, synchronisations=s.value)
+
+    def process_status(self, frames):
+        """frames: per member (left, right[, delta_guess[, outliers[, n_outliers]]]).  (status, [result dict] or None)."""
+        if len(frames) != len(self.members):
+            raise ValueError("one frame per member")
+        n = len(frames)
+        arr, keep = (Frame * n)(), []
+        for i, (m, fr) in enumerate(zip(self.members, frames)):
+            fr = tuple(fr) + (None, (), None)[len(fr) - 2:]
+            left, right, g, ids, n_out = m._arguments(*fr)
+            keep.append((left, right, g, ids))
+            arr[i].left = left.ctypes.data if left is not None else None
+            arr[i].right = right.ctypes.data if right is not None else None
+            arr[i].stride = m.flow.width
+            arr[i].delta_guess = g.ctypes.data_as(_pd) if g is not None else None
+            arr[i].n_outliers = n_out
+            arr[i].outlier_ids = ids.ctypes.data_as(_pu64) if len(ids) else None
+        res = (Result * n)()
+        rc = self._lib.visfs_tracker_group_process(self.h, arr, res)
+        if rc != abi.OK:
+            return rc, None
+        return rc, [m._unpack(res[i]) for i, m in enumerate(self.members)]
+
+    def process(self, frames):
+        rc, out = self.process_status(frames)
+        if rc != abi.OK:
+            raise backend.BackendError(f"tracker group process: status {rc}: {self.last_error()}")
+        return out
