@@ -72,6 +72,24 @@ def test_pretreatment_equals_the_host_twin(solver, name):
         assert any(len(r["blocked_id"]) > 0 for r, _ in log)
 
 
+def test_full_length_outlier_list_equals_the_host_twin(solver):
+    log = _run(tc.full_outliers(), solver, "4096 outliers")
+    assert len(tc.full_outlier_list(log[1][0])) == tracker.MAX_OUTLIERS
+    assert log[2][0]["flags"] == 0 and log[2][0]["blocked_id"].tolist() == tc.every_third(log[1][0])
+
+
+def test_the_flow_object_goes_before_its_tracker(solver):
+    """The tracker's own call block is freed while the flow object is still alive; the orphaned tracker refuses and can be destroyed."""
+    scn = tc.scenario(tc.sequence(3), 60, 12)
+    dev = tc.Subject(scn, solver=solver)
+    dev.process(*scn["frames"][0])
+    assert dev.process(*scn["frames"][1])[0]["flags"] == to.BOOTSTRAPPED
+    dev.flow.close()
+    rc, _ = dev.trk.process_status(*scn["frames"][2])
+    assert rc == abi.ERR_NOT_LOADED and "the flow object of this tracker is gone" in dev.trk.last_error()
+    dev.trk.close()
+
+
 def test_min_inliers_at_and_just_above_the_kept_count(solver):
     seq = tc.sequence(4)
     kept = len(_run(tc.scenario(seq, 60, 12, min_inliers=0), solver, "kept count")[2][0]["covisible_id"])
@@ -137,6 +155,7 @@ def test_foreign_push_is_refused(solver):
     dev.flow.push_frame(*scn["frames"][2])
     rc, _ = dev.trk.process_status(*scn["frames"][3])
     assert rc == abi.ERR_NOT_LOADED and "pushed" in dev.trk.last_error()
+    assert "member" not in dev.trk.last_error()
     dev.close()
 
 

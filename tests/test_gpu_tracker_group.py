@@ -91,6 +91,42 @@ def test_group_of_nine_with_two_cameras(solver):
         dev.close()
 
 
+def _two_with_full_outlier_lists():
+    rules = [None, None, tc.full_outlier_list, None]
+    return [gc.member(tc.sequence(8)[:4], outliers=rules), gc.member(gc.seeded(8, 11)[:4], outliers=rules)]
+
+
+def test_full_length_outlier_lists_of_both_members(solver):
+    """Both members send 4096 ids: member 1's list starts at the very end of member 0's share of the upload block."""
+    members = _two_with_full_outlier_lists()
+    log = _host_log(members, 60)
+    assert all(len(tc.full_outlier_list(log[1][i][0])) == tracker.MAX_OUTLIERS for i in range(2))
+    assert gc.flags(log, 2) == [0, 0] and all(log[2][i][0]["blocked_id"].tolist() == tc.every_third(log[1][i][0]) for i in range(2))
+    dev = gc.Rig(members, 60, solver=solver)
+    try:
+        gc.against(members, log, dev, "4096 outliers each")
+        _syncs_ok(dev)
+    finally:
+        dev.close()
+
+
+def test_a_member_goes_before_its_group_and_its_flow_object(solver):
+    members = gc.staggered_three(2)[:2]
+    dev = gc.Rig(members, 60, solver=solver)
+    for i, m in enumerate(members):
+        for pair in m["pre"]:
+            dev.single(i, *pair)
+    dev.grouped(gc.call_args(members, 0, [None] * 2))
+    dev.single(0, *members[0]["frames"][1])
+    dev.trks[0].close()
+    dev.group.close()
+    dev.flows[0].close()
+    dev.flows[1].close()                       # member 1: the flow object first, then the orphaned tracker
+    rc, _ = dev.trks[1].process_status(*members[1]["frames"][1])
+    assert rc == abi.ERR_NOT_LOADED and "the flow object of this tracker is gone" in dev.trks[1].last_error()
+    dev.trks[1].close()
+
+
 def test_single_calls_between_group_calls(solver):
     """Call 3 of every member is made singly between grouped calls; then member 0 alone runs a frame ahead by a single call."""
     members, log = gc.mixed_reference(60)

@@ -170,3 +170,20 @@ def test_a_destroyed_member_is_refused():
         assert rc == abi.ERR_NOT_LOADED and "member 2" in sub.group.last_error()
     finally:
         sub.close()
+
+
+def test_a_member_goes_before_its_group_and_its_flow_object():
+    members = gc.staggered_three(2)[:2]
+    sub = gc.Rig(members, 60)
+    for i, m in enumerate(members):
+        for pair in m["pre"]:
+            sub.single(i, *pair)
+    sub.grouped(gc.call_args(members, 0, [None] * 2))
+    sub.single(0, *members[0]["frames"][1])
+    sub.trks[0].close()
+    sub.group.close()
+    sub.flows[0].close()
+    sub.flows[1].close()                       # member 1: the flow object first, then the orphaned tracker
+    rc, _ = sub.trks[1].process_status(*members[1]["frames"][1])
+    assert rc == abi.ERR_NOT_LOADED and "the flow object of this tracker is gone" in sub.trks[1].last_error()
+    sub.trks[1].close()

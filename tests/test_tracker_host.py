@@ -112,6 +112,12 @@ def test_pretreatment_equals_the_checker(name):
         assert all(len(r["blocked_id"]) == 0 for r, _ in log)
 
 
+def test_full_length_outlier_list_equals_the_checker():
+    log, _ = _run(tc.full_outliers(), "4096 outliers")
+    assert len(tc.full_outlier_list(log[1][0])) == tracker.MAX_OUTLIERS
+    assert log[2][0]["flags"] == 0 and log[2][0]["blocked_id"].tolist() == tc.every_third(log[1][0])
+
+
 def test_lost_tracking_and_the_bootstrap_behind_it():
     scn = tc.lost_case()
     log, _ = _run(scn, "lost")

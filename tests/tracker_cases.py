@@ -75,6 +75,12 @@ def every_third(prev):
     return [int(i) for i in prev["word_id"][::3]]
 
 
+def full_outlier_list(prev):
+    """The 4096 ids a call may carry at the most: every third id of the previous result, then ids no tracker has handed out."""
+    ids = every_third(prev)
+    return ids + [int(prev["next_id"]) + 1000 + k for k in range(tracker.MAX_OUTLIERS - len(ids))]
+
+
 class Subject:
     """A tracker.Tracker on a flow.Flow (solver given: device; None: host twin) behind the checker's process() signature."""
 
@@ -158,6 +164,11 @@ def no_top_up():
 def empty_top_up():
     """min_distance 80 over a 40 x 40 patch: the disc of any counted word covers every corner the patch has."""
     return scenario(patch_sequence(4), 60, 80, min_inliers=1)
+
+
+def full_outliers():
+    """Frame 2, a steady frame, gets an outlier list of full length."""
+    return scenario(sequence(4), 60, 12, outliers=[None, None, full_outlier_list, None])
 
 
 def guess_cases():

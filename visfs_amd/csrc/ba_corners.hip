@@ -115,8 +115,8 @@ __device__ __forceinline__ void corner_response_body(const uint8_t* __restrict__
 
 __global__ __launch_bounds__(CR_T) void k_corner_response(const uint8_t* __restrict__ px, int w, int h, const Disc* __restrict__ discs,
                                                           int n_discs, const int32_t* __restrict__ hw, float* __restrict__ eig,
-                                                          uint8_t* __restrict__ mask, CornerDev* st, const int32_t* dev_args) {
-    corner_response_body(px, w, h, discs, n_discs, hw, eig, mask, st, dev_args);
+                                                          uint8_t* __restrict__ mask, CornerDev* st) {
+    corner_response_body(px, w, h, discs, n_discs, hw, eig, mask, st, nullptr);
 }
 
 // The batched forms (tracker groups): member blockIdx.z, its arguments read from the group's table.  A member that takes no part in
@@ -169,9 +169,8 @@ __device__ __forceinline__ void corner_candidates_body(const float* __restrict__
 }
 
 __global__ __launch_bounds__(CR_T) void k_corner_candidates(const float* __restrict__ eig, const uint8_t* __restrict__ mask, int w, int h,
-                                                            double quality, CornerDev* st, uint64_t* __restrict__ keys,
-                                                            const int32_t* dev_args) {
-    corner_candidates_body(eig, mask, w, h, quality, st, keys, dev_args);
+                                                            double quality, CornerDev* st, uint64_t* __restrict__ keys) {
+    corner_candidates_body(eig, mask, w, h, quality, st, keys, nullptr);
 }
 
 __global__ __launch_bounds__(CR_T) void k_corner_candidates_g(const CornerRec* __restrict__ recs, int w, int h, double quality) {
@@ -287,8 +286,8 @@ __device__ __forceinline__ void corner_select_body(const uint64_t* __restrict__ 
 }
 
 __global__ __launch_bounds__(kSelT) void k_corner_select(const uint64_t* __restrict__ sorted, CornerDev* st, int w, int32_t gate,
-                                                         int32_t max_corners, float* __restrict__ xy, const int32_t* dev_args) {
-    corner_select_body(sorted, st, w, gate, max_corners, xy, dev_args);
+                                                         int32_t max_corners, float* __restrict__ xy) {
+    corner_select_body(sorted, st, w, gate, max_corners, xy, nullptr);
 }
 
 __global__ __launch_bounds__(kSelT) void k_corner_select_g(const CornerRec* __restrict__ recs, int w, int32_t gate) {
@@ -521,17 +520,17 @@ int device_corners(visfs_flow* f, CornerState* c, const uint8_t* px, const visfs
     float* d_xy = reinterpret_cast<float*>(c->d_out + sizeof(CornerDev));
     CR_HIP(f, hipMemsetAsync(c->d_out, 0, sizeof(CornerDev), f->stream));
     hipLaunchKernelGGL(k_corner_response, dim3((w + CT_X - 1) / CT_X, (h + CT_Y - 1) / CT_Y), dim3(CR_T), 0, f->stream, px, w, h, d_discs,
-                       (int)c->discs.size(), d_hw, c->d_eig, c->d_mask, st, (const int32_t*)nullptr);
+                       (int)c->discs.size(), d_hw, c->d_eig, c->d_mask, st);
     CR_HIP(f, hipGetLastError());
     hipLaunchKernelGGL(k_corner_candidates, dim3((unsigned)(((size_t)w * h + CR_T - 1) / CR_T)), dim3(CR_T), 0, f->stream, c->d_eig, c->d_mask,
-                       w, h, p.quality_level, st, c->d_keys, (const int32_t*)nullptr);
+                       w, h, p.quality_level, st, c->d_keys);
     CR_HIP(f, hipGetLastError());
     const size_t chunks = (max_candidates(f) + 63) / 64;
     hipLaunchKernelGGL(k_corner_sort, dim3((unsigned)std::min<size_t>(std::max<size_t>(chunks, 1), kSortGrid)), dim3(CR_T), 0, f->stream,
                        c->d_keys, st, c->d_sorted);
     CR_HIP(f, hipGetLastError());
     hipLaunchKernelGGL(k_corner_select, dim3(1), dim3(kSelT), 0, f->stream, c->d_sorted, st, w, distance_gate(p.min_distance), p.max_corners,
-                       d_xy, (const int32_t*)nullptr);
+                       d_xy);
     CR_HIP(f, hipGetLastError());
     CR_HIP(f, hipMemcpyAsync(c->h_out, c->d_out, sizeof(CornerDev) + sizeof(float) * 2 * (size_t)p.max_corners, hipMemcpyDeviceToHost,
                              f->stream));
@@ -550,33 +549,6 @@ int device_corners(visfs_flow* f, CornerState* c, const uint8_t* px, const visfs
 
 // ---------------------------------------------------------------- the resident caller's entry points (ba_tracker.hip)
 namespace flow {
-
-int corners_enqueue(visfs_flow* f, const uint8_t* px, double quality_level, double min_distance, const Disc* d_discs, const int32_t* d_hw,
-                    const int32_t* d_args, const int32_t** d_n_out, const float** d_xy) {
-    int rc = ensure_state(f);
-    if (rc != VISFS_BA_OK) return rc;
-    CornerState* c = f->corners;
-    c->valid = false;                          // the download hook reports staged calls only
-    const int w = f->w, h = f->h;
-    CornerDev* st = reinterpret_cast<CornerDev*>(c->d_out);
-    float* xy = reinterpret_cast<float*>(c->d_out + sizeof(CornerDev));
-    CR_HIP(f, hipMemsetAsync(c->d_out, 0, sizeof(CornerDev), f->stream));
-    hipLaunchKernelGGL(k_corner_response, dim3((w + CT_X - 1) / CT_X, (h + CT_Y - 1) / CT_Y), dim3(CR_T), 0, f->stream, px, w, h, d_discs, 0,
-                       d_hw, c->d_eig, c->d_mask, st, d_args);
-    CR_HIP(f, hipGetLastError());
-    hipLaunchKernelGGL(k_corner_candidates, dim3((unsigned)(((size_t)w * h + CR_T - 1) / CR_T)), dim3(CR_T), 0, f->stream, c->d_eig, c->d_mask,
-                       w, h, quality_level, st, c->d_keys, d_args);
-    CR_HIP(f, hipGetLastError());
-    const size_t chunks = (max_candidates(f) + 63) / 64;
-    hipLaunchKernelGGL(k_corner_sort, dim3((unsigned)std::min<size_t>(std::max<size_t>(chunks, 1), kSortGrid)), dim3(CR_T), 0, f->stream,
-                       c->d_keys, st, c->d_sorted);
-    CR_HIP(f, hipGetLastError());
-    hipLaunchKernelGGL(k_corner_select, dim3(1), dim3(kSelT), 0, f->stream, c->d_sorted, st, w, distance_gate(min_distance), 0, xy, d_args);
-    CR_HIP(f, hipGetLastError());
-    *d_n_out = &st->n_out;
-    *d_xy = xy;
-    return VISFS_BA_OK;
-}
 
 int group_corners_prepare(visfs_flow* f) { return ensure_state(f); }
 

@@ -15,13 +15,9 @@ void clahe_release(visfs_flow* f);        // likewise for the first visfs_flow_p
 struct TrackerState;                      // ba_tracker.hip
 void tracker_release(visfs_flow* f);      // detaches the trackers made on f: their calls fail from then on, their memory is freed
 
-// Corner extraction for a caller whose disc list and corner budget live in device memory (ba_corners.hip).
-// corners_enqueue: the four launches of visfs_flow_corners on level-0 pixels `px`, no copy and no synchronisation; d_args points at
-// { number of raster discs, max_corners } (max_corners <= 0: nothing runs and the count is 0); *d_n_out and *d_xy are where the
-// count and the corners (strongest first) will stand.  corners_host: the host restatement with the raster's discs given as they are.
+// Corner extraction for the resident front end (ba_corners.hip): the host restatement with the raster's discs given as they are
+// (max_corners <= 0: nothing runs and the count is 0).  The device form is group_corners of ba_group.hpp.
 struct Disc;
-int corners_enqueue(visfs_flow* f, const uint8_t* px, double quality_level, double min_distance, const Disc* d_discs, const int32_t* d_hw,
-                    const int32_t* d_args, const int32_t** d_n_out, const float** d_xy);
 int corners_host(visfs_flow* f, const uint8_t* px, int32_t max_corners, double quality_level, double min_distance, const Disc* discs,
                  int n_discs, const int32_t* hw, float* xy, int32_t* n_out);
 

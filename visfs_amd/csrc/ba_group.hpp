@@ -24,7 +24,7 @@ struct ClaheRec {
 };
 
 struct CornerDev;                              // ba_corners.hip
-struct CornerRec {                             // one corner extraction of a member: the arguments of corners_enqueue and its state
+struct CornerRec {                             // one corner extraction of a member: its arguments and its state
     const uint8_t* px;
     const Disc* discs;
     const int32_t* hw;

@@ -3,28 +3,30 @@
 //
 // Two ways over the decisions of ba_tracker.hpp and the work items of ba_flow.hpp / ba_corners.hpp:
 //   * host restatement (trackers on objects of visfs_flow_create_host): every step in sequence on one core;
-//   * device: the table (id, left pixel, 3-D point, track count) and every intermediate list stay in HBM.  A call is one small
-//     upload (outlier ids, guess), the frame push, these launches on the stream of the owning handle, one copy of the output block
-//     and one synchronisation.  No launch waits for a value read back: counts travel through a control block in device memory, the
-//     grids are sized by what the host knows (the ids it returned last, max_features) and surplus workgroups leave at once.
-//       k_trk_pretreat  one workgroup: each row's id against the outlier list in LDS, order-preserving split into from-table and
+//   * device: the table (id, left pixel, 3-D point, track count) and every intermediate list stay in HBM.  A call is a tracker
+//     group of one: one upload of the call's tables (outlier ids and guess in them), the frame's pyramids,
+//     these launches on the stream of the owning handle, one copy of the output block and one synchronisation.  Every kernel reads
+//     its arguments from the table at member blockIdx.z and carries the suffix _g.  No launch waits for a value read back:
+//     counts travel through a control block in device memory, the grids are sized by what the host knows (the ids it returned
+//     last, max_features) and surplus workgroups leave at once.
+//       k_trk_pretreat_g  one workgroup: each row's id against the outlier list in LDS, order-preserving split into from-table and
 //                       blocked list (ballot + prefix over the wavefronts)                                          (:143-165)
-//       [bootstrap]     the corner kernels on the previous left image without a mask, k_trk_append, k_trk_stereo in its
+//       [bootstrap]     the corner kernels on the previous left image without a mask, k_trk_append_g, k_trk_stereo_g in its
 //                       forward-only, ungated, status-blind form for the 3-D points                                 (:179-230)
-//       k_trk_track     one wavefront per from-row: guess projection in fp64, lk_gated, the bounds test          (:237-274, :286)
-//       k_trk_reduce    one workgroup: compaction of the kept rows in row order: covisible output, kept count, LOST, the top-up's
+//       k_trk_track_g   one wavefront per from-row: guess projection in fp64, lk_gated, the bounds test          (:237-274, :286)
+//       k_trk_reduce_g  one workgroup: compaction of the kept rows in row order: covisible output, kept count, LOST, the top-up's
 //                       corner budget                                                                               (:280-320)
-//       k_trk_discs     one workgroup: rank sort of the (count, row) keys, the serial draw decision of getMask 1024 discs at a time
+//       k_trk_discs_g   one workgroup: rank sort of the (count, row) keys, the serial draw decision of getMask 1024 discs at a time
 //                       (each against the raster so far in parallel; then wavefront after wavefront settles its 64 discs among
 //                       themselves through cover masks and the ones behind test against what it drew), the raster's Disc list
 //                       and its length                                                                              (:116-141)
 //       the corner kernels of ba_corners.hip on the current left image, disc count and budget read from device memory    (:327)
-//       k_trk_append    ids for the new corners, appended behind the kept rows                                      (:330-336)
-//       k_trk_stereo    one wavefront per row: lk_gated left -> right, bounds test, triangulate                     (:343-397)
-//       k_trk_finish    one workgroup: final compaction into the table, counts + 1, the output block's head        (:98-114, :414-417)
-//   * tracker groups (include/visfs_tracker_group.h): every kernel above is a thin caller of a __device__ body;
-//     the batched k_*_g forms call the same bodies for member blockIdx.z of a table in device memory, so n trackers of one handle
-//     take one launch sequence and one synchronisation.
+//       k_trk_append_g  ids for the new corners, appended behind the kept rows                                      (:330-336)
+//       k_trk_stereo_g  one wavefront per row: lk_gated left -> right, bounds test, triangulate                     (:343-397)
+//       k_trk_finish_g  one workgroup: final compaction into the table, counts + 1, the output block's head        (:98-114, :414-417)
+//   * tracker groups (include/visfs_tracker_group.h): the same sequence (run_call) with n members in the
+//     table, so n trackers of one handle take one launch sequence and one synchronisation.  plan_member and commit_member are the
+//     per-member decisions in front of a call and the bookkeeping behind it, for both entry points.
 #include "ba_tracker.hpp"
 #include "ba_flow_object.hpp"
 #include "ba_group.hpp"
@@ -132,8 +134,8 @@ size_t carve_work(char* base, size_t M, size_t hw_len, Bufs& b, int32_t** hw) {
 
 struct Shape { int32_t M, w, h, r_track, r_blocked, min_inliers; };
 
-// A member of a tracker group in one call: what the launches of device_call take as kernel arguments, read by the
-// batched kernels from device memory instead.  B.in and B.outliers point into the group's own upload block.
+// A member of a call: the arguments of the kernels, read by them from the call's table in device memory at
+// blockIdx.z.  B.in and B.outliers point into the upload block the call goes through.
 struct TrkRec {
     Bufs B;
     Image prev[2], cur[2];                     // left, right of the slot before and of the slot this call pushed into
@@ -165,7 +167,12 @@ __device__ inline int wg_offset(bool flag, int32_t* wcount, int& total) {
     return before + __popcll(b & ((1ull << lane) - 1ull));
 }
 
-__device__ __forceinline__ void trk_pretreat_body(const Bufs& B, const Shape& S) {
+// Every kernel works for member blockIdx.z of the call's table in device memory (a single call is a table of one).  A member without
+// a previous pair leaves every one of them at once; a member that does not bootstrap leaves the bootstrap's.
+__global__ __launch_bounds__(TK_T) void k_trk_pretreat_g(const TrkRec* __restrict__ recs, Shape S) {
+    const TrkRec& r = recs[blockIdx.z];
+    if (r.skip) return;
+    const Bufs& B = r.B;
     __shared__ uint64_t s_out[kMaxOutliers];
     __shared__ int32_t wcount[TK_WAVES];
     const int tid = threadIdx.x;
@@ -208,20 +215,15 @@ __device__ __forceinline__ void trk_pretreat_body(const Bufs& B, const Shape& S)
     }
 }
 
-__global__ __launch_bounds__(TK_T) void k_trk_pretreat(Bufs B, Shape S) { trk_pretreat_body(B, S); }
-
-// The batched forms (tracker groups): member blockIdx.z, its arguments read from the group's table.  A member without a previous
-// pair leaves every one of them at once; a member that does not bootstrap leaves the bootstrap's.
-__global__ __launch_bounds__(TK_T) void k_trk_pretreat_g(const TrkRec* __restrict__ recs, Shape S) {
-    const TrkRec& r = recs[blockIdx.z];
-    if (r.skip) return;
-    trk_pretreat_body(r.B, S);
-}
-
 // The corners of a selection get ids next_id, next_id + 1, ... strongest first.  BOOT: they are the from-rows of this call, without a
 // track count (Tracker.cpp:181-189).  Otherwise they follow the kept rows and are this frame's newly extracted words (:330-336).
 template <bool BOOT>
-__device__ __forceinline__ void trk_append_body(const Bufs& B, const Shape& S, const int32_t* n_out, const float* xy) {
+__global__ __launch_bounds__(TK_T) void k_trk_append_g(const TrkRec* __restrict__ recs, Shape S) {
+    const TrkRec& r = recs[blockIdx.z];
+    if (r.skip || (BOOT && !r.boot)) return;
+    const Bufs& B = r.B;
+    const int32_t* n_out = r.corner_n;
+    const float* xy = r.corner_xy;
     Ctl* c = B.ctl;
     const int tid = threadIdx.x;
     const int base = BOOT ? 0 : c->n_kept;
@@ -247,18 +249,6 @@ __device__ __forceinline__ void trk_append_body(const Bufs& B, const Shape& S, c
     }
 }
 
-template <bool BOOT>
-__global__ __launch_bounds__(TK_T) void k_trk_append(Bufs B, Shape S, const int32_t* n_out, const float* xy) {
-    trk_append_body<BOOT>(B, S, n_out, xy);
-}
-
-template <bool BOOT>
-__global__ __launch_bounds__(TK_T) void k_trk_append_g(const TrkRec* __restrict__ recs, Shape S) {
-    const TrkRec& r = recs[blockIdx.z];
-    if (r.skip || (BOOT && !r.boot)) return;
-    trk_append_body<BOOT>(r.B, S, r.corner_n, r.corner_xy);
-}
-
 struct WaveCells {                             // as in ba_flow.hip: cell s * 64 + lane in slot s, int64 butterfly
     static constexpr int kSlots = kLaneSlots;
     using acc_t = int32_t;
@@ -273,8 +263,13 @@ struct WaveCells {                             // as in ba_flow.hip: cell s * 64
 };
 
 template <bool BACK>
-__device__ __forceinline__ void trk_track_body(const Bufs& B, const Shape& S, const Image& I, const Image& J, const LkParams& prm,
-                                               const Layout& lay, const Guess& g, int has_guess, float gate) {
+__global__ __launch_bounds__(64) void k_trk_track_g(const TrkRec* __restrict__ recs, Shape S, LkParams prm, Layout lay, float gate) {
+    const TrkRec& r = recs[blockIdx.z];
+    if (r.skip) return;
+    const Bufs& B = r.B;
+    const Image &I = r.prev[0], &J = r.cur[0];
+    const Guess& g = r.g;
+    const int has_guess = r.has_guess;
     const int p = blockIdx.x;
     if (p >= min(B.ctl->n_from, S.M)) return;
     WaveCells pol{ (int)threadIdx.x };
@@ -294,19 +289,10 @@ __device__ __forceinline__ void trk_track_body(const Bufs& B, const Shape& S, co
     B.inb[p] = (in_bounds(tox, S.w) && in_bounds(toy, S.h)) ? 1 : 0;
 }
 
-template <bool BACK>
-__global__ __launch_bounds__(64) void k_trk_track(Bufs B, Shape S, Image I, Image J, LkParams prm, Layout lay, Guess g, int has_guess, float gate) {
-    trk_track_body<BACK>(B, S, I, J, prm, lay, g, has_guess, gate);
-}
-
-template <bool BACK>
-__global__ __launch_bounds__(64) void k_trk_track_g(const TrkRec* __restrict__ recs, Shape S, LkParams prm, Layout lay, float gate) {
+__global__ __launch_bounds__(TK_T) void k_trk_reduce_g(const TrkRec* __restrict__ recs, Shape S) {
     const TrkRec& r = recs[blockIdx.z];
     if (r.skip) return;
-    trk_track_body<BACK>(r.B, S, r.prev[0], r.cur[0], prm, lay, r.g, r.has_guess, gate);
-}
-
-__device__ __forceinline__ void trk_reduce_body(const Bufs& B, const Shape& S) {
+    const Bufs& B = r.B;
     __shared__ int32_t wcount[TK_WAVES];
     const int tid = threadIdx.x;
     const int n = min(B.ctl->n_from, S.M);
@@ -333,14 +319,6 @@ __device__ __forceinline__ void trk_reduce_body(const Bufs& B, const Shape& S) {
         c->n_kept = kept; c->n_rows = lost ? 0 : kept; c->lost = lost ? 1 : 0;
         c->corner_args[1] = lost ? 0 : S.M - kept;                                // backUpCornersCnt (:324)
     }
-}
-
-__global__ __launch_bounds__(TK_T) void k_trk_reduce(Bufs B, Shape S) { trk_reduce_body(B, S); }
-
-__global__ __launch_bounds__(TK_T) void k_trk_reduce_g(const TrkRec* __restrict__ recs, Shape S) {
-    const TrkRec& r = recs[blockIdx.z];
-    if (r.skip) return;
-    trk_reduce_body(r.B, S);
 }
 
 constexpr int kHwLds = 2048;                   // half-width entries kept in LDS (both radii together); larger tables are read in place
@@ -470,8 +448,6 @@ __device__ __forceinline__ void trk_discs_body(const Bufs& B, const Shape& S) {
     if (tid == 0) { c->n_list = n_list; c->corner_args[0] = nr; }
 }
 
-__global__ __launch_bounds__(TK_T) void k_trk_discs(Bufs B, Shape S) { trk_discs_body(B, S); }
-
 __global__ __launch_bounds__(TK_T) void k_trk_discs_g(const TrkRec* __restrict__ recs, Shape S) {
     const TrkRec& r = recs[blockIdx.z];
     if (r.skip) return;
@@ -482,8 +458,13 @@ __global__ __launch_bounds__(TK_T) void k_trk_discs_g(const TrkRec* __restrict__
 // not looked at (Tracker.cpp:207-219).  Otherwise: the stereo pass of the frame with its gate, the bounds test of :376 and the
 // finite test of :390.
 template <bool BACK, bool BOOT>
-__device__ __forceinline__ void trk_stereo_body(const Bufs& B, const Shape& S, const Image& I, const Image& J, const LkParams& prm,
-                                                const Layout& lay, const Camera& cam, float gate) {
+__global__ __launch_bounds__(64) void k_trk_stereo_g(const TrkRec* __restrict__ recs, Shape S, LkParams prm, Layout lay, float gate) {
+    const TrkRec& r = recs[blockIdx.z];
+    if (r.skip || (BOOT && !r.boot)) return;
+    const Bufs& B = r.B;
+    const Image* im = BOOT ? r.prev : r.cur;
+    const Image &I = im[0], &J = im[1];
+    const Camera& cam = r.cam;
     const int p = blockIdx.x;
     const Ctl* c = B.ctl;
     const int n = BOOT ? c->n_from : (c->lost ? 0 : c->n_rows);
@@ -508,20 +489,11 @@ __device__ __forceinline__ void trk_stereo_body(const Bufs& B, const Shape& S, c
     }
 }
 
-template <bool BACK, bool BOOT>
-__global__ __launch_bounds__(64) void k_trk_stereo(Bufs B, Shape S, Image I, Image J, LkParams prm, Layout lay, Camera cam, float gate) {
-    trk_stereo_body<BACK, BOOT>(B, S, I, J, prm, lay, cam, gate);
-}
-
-template <bool BACK, bool BOOT>
-__global__ __launch_bounds__(64) void k_trk_stereo_g(const TrkRec* __restrict__ recs, Shape S, LkParams prm, Layout lay, float gate) {
+__global__ __launch_bounds__(TK_T) void k_trk_finish_g(const TrkRec* __restrict__ recs, Shape S) {
     const TrkRec& r = recs[blockIdx.z];
-    if (r.skip || (BOOT && !r.boot)) return;
-    const Image* im = BOOT ? r.prev : r.cur;
-    trk_stereo_body<BACK, BOOT>(r.B, S, im[0], im[1], prm, lay, r.cam, gate);
-}
-
-__device__ __forceinline__ void trk_finish_body(const Bufs& B, const Shape& S, int boot) {
+    if (r.skip) return;
+    const Bufs& B = r.B;
+    const int boot = r.boot;
     __shared__ int32_t wcount[TK_WAVES];
     Ctl* c = B.ctl;
     const int tid = threadIdx.x;
@@ -560,17 +532,38 @@ __device__ __forceinline__ void trk_finish_body(const Bufs& B, const Shape& S, i
     }
 }
 
-__global__ __launch_bounds__(TK_T) void k_trk_finish(Bufs B, Shape S, int boot) { trk_finish_body(B, S, boot); }
-
-__global__ __launch_bounds__(TK_T) void k_trk_finish_g(const TrkRec* __restrict__ recs, Shape S) {
-    const TrkRec& r = recs[blockIdx.z];
-    if (r.skip) return;
-    trk_finish_body(r.B, S, r.boot);
-}
-
 }  // namespace trk
 
-// ---------------------------------------------------------------- the object
+// ---------------------------------------------------------------- the objects
+// The tables of a call for n members stand in one block, pinned and on the device, and go up in one copy:
+// [PyrRec n][ClaheRec n][CornerRec n: bootstrap][CornerRec n: top-up][TrkRec n][InHead n][outlier ids of the members, one behind the other]
+struct CallBlock {
+    char* pinned = nullptr; char* dev = nullptr;
+    size_t off_pyr = 0, off_clahe = 0, off_boot = 0, off_top = 0, off_trk = 0, off_in = 0, off_ids = 0, bytes = 0;
+
+    hipError_t allocate(size_t n) {            // the caller has selected the device
+        size_t off = 0;
+        const auto take = [&](size_t b) { const size_t at = off; off = (off + b + 255) & ~size_t(255); return at; };
+        off_pyr = take(n * sizeof(PyrRec));
+        off_clahe = take(n * sizeof(ClaheRec));
+        off_boot = take(n * sizeof(CornerRec));
+        off_top = take(n * sizeof(CornerRec));
+        off_trk = take(n * sizeof(TrkRec));
+        off_in = take(n * sizeof(InHead));
+        off_ids = take(n * sizeof(uint64_t) * kMaxOutliers);
+        bytes = off;
+        hipError_t e = hipMalloc(reinterpret_cast<void**>(&dev), bytes);
+        if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&pinned), bytes, hipHostMallocDefault);
+        if (e == hipSuccess) std::memset(pinned, 0, bytes);
+        return e;
+    }
+    void release() {                           // the caller has waited for the stream that read it
+        if (dev) (void)hipFree(dev);
+        if (pinned) (void)hipHostFree(pinned);
+        dev = pinned = nullptr;
+    }
+};
+
 struct visfs_tracker {
     visfs_flow* f = nullptr;                   // nullptr once the flow object is gone
     visfs_tracker_params prm{};
@@ -586,9 +579,10 @@ struct visfs_tracker {
     // host restatement: the same blocks in host memory
     std::vector<char> h_work, h_outblk, h_inblk;
     // device
-    char* d_work = nullptr; char* d_out = nullptr; char* d_in = nullptr;
-    char* p_out = nullptr; char* p_in = nullptr;                                  // pinned
-    size_t out_bytes = 0, in_bytes = 0;
+    char* d_work = nullptr; char* d_out = nullptr;
+    char* p_out = nullptr;                                                        // pinned
+    size_t out_bytes = 0;
+    CallBlock blk;                             // the tables of a single call: a group of one
 
     Bufs B{};                                  // where the kernels (or the host steps) work
     Out R{};                                   // where the caller reads: the pinned copy, or the host twin's block itself
@@ -596,8 +590,7 @@ struct visfs_tracker {
     visfs_tracker_group* group = nullptr;      // the tracker group this is a member of
 };
 
-// n trackers processed by one call (include/visfs_tracker_group.h).  A call's tables stand in one block, pinned and on the device:
-// [PyrRec n][ClaheRec n][CornerRec n: bootstrap][CornerRec n: top-up][TrkRec n][InHead n][outlier ids of the members, one behind the other]
+// n trackers processed by one call (include/visfs_tracker_group.h)
 struct visfs_tracker_group {
     std::vector<visfs_tracker*> m;             // nullptr: the member has been destroyed
     bool device = false;
@@ -605,8 +598,7 @@ struct visfs_tracker_group {
     GroupCounts cnt;
     int dev = 0;
     hipStream_t stream = nullptr;
-    char* p_blk = nullptr; char* d_blk = nullptr;
-    size_t off_pyr = 0, off_clahe = 0, off_boot = 0, off_top = 0, off_trk = 0, off_in = 0, off_ids = 0, blk_bytes = 0;
+    CallBlock blk;                             // the tables of a call of all members
 };
 
 namespace {
@@ -639,10 +631,9 @@ void free_device(visfs_tracker* t) {
     if (f->stream) (void)hipStreamSynchronize(f->stream);
     if (t->d_work) (void)hipFree(t->d_work);
     if (t->d_out) (void)hipFree(t->d_out);
-    if (t->d_in) (void)hipFree(t->d_in);
     if (t->p_out) (void)hipHostFree(t->p_out);
-    if (t->p_in) (void)hipHostFree(t->p_in);
-    t->d_work = t->d_out = t->d_in = t->p_out = t->p_in = nullptr;
+    t->blk.release();
+    t->d_work = t->d_out = t->p_out = nullptr;
 }
 
 int allocate(visfs_tracker* t) {
@@ -652,9 +643,9 @@ int allocate(visfs_tracker* t) {
     int32_t* hw = nullptr;
     const size_t work_bytes = carve_work(nullptr, M, t->hw.size(), B, &hw);
     t->out_bytes = carve_out(nullptr, M, B.o);
-    t->in_bytes = (sizeof(InHead) + sizeof(uint64_t) * kMaxOutliers + 255) & ~size_t(255);
     if (!f->device) {
-        t->h_work.assign(work_bytes, 0); t->h_outblk.assign(t->out_bytes, 0); t->h_inblk.assign(t->in_bytes, 0);
+        t->h_work.assign(work_bytes, 0); t->h_outblk.assign(t->out_bytes, 0);
+        t->h_inblk.assign(sizeof(InHead) + sizeof(uint64_t) * kMaxOutliers, 0);
         carve_work(t->h_work.data(), M, t->hw.size(), B, &hw);
         carve_out(t->h_outblk.data(), M, B.o);
         std::memcpy(hw, t->hw.data(), t->hw.size() * sizeof(int32_t));
@@ -666,14 +657,11 @@ int allocate(visfs_tracker* t) {
     TK_HIP(t, hipSetDevice(f->dev));
     TK_HIP(t, hipMalloc(reinterpret_cast<void**>(&t->d_work), work_bytes));
     TK_HIP(t, hipMalloc(reinterpret_cast<void**>(&t->d_out), t->out_bytes));
-    TK_HIP(t, hipMalloc(reinterpret_cast<void**>(&t->d_in), t->in_bytes));
     TK_HIP(t, hipHostMalloc(reinterpret_cast<void**>(&t->p_out), t->out_bytes, hipHostMallocDefault));
-    TK_HIP(t, hipHostMalloc(reinterpret_cast<void**>(&t->p_in), t->in_bytes, hipHostMallocDefault));
+    TK_HIP(t, t->blk.allocate(1));
     carve_work(t->d_work, M, t->hw.size(), B, &hw);
     carve_out(t->d_out, M, B.o);
-    carve_out(t->p_out, M, t->R);
-    B.in = reinterpret_cast<const InHead*>(t->d_in);
-    B.outliers = reinterpret_cast<const uint64_t*>(t->d_in + sizeof(InHead));
+    carve_out(t->p_out, M, t->R);              // (B.in and B.outliers of a call point into the block the call goes through)
     std::memset(t->p_out, 0, t->out_bytes);
     TK_HIP(t, hipMemsetAsync(t->d_work, 0, work_bytes, f->stream));
     TK_HIP(t, hipMemsetAsync(t->d_out, 0, t->out_bytes, f->stream));
@@ -856,66 +844,6 @@ int host_topup_stereo_finish(visfs_tracker* t, bool boot) {
     return VISFS_BA_OK;
 }
 
-// ---------------------------------------------------------------- device: the launches of a call
-int device_call(visfs_tracker* t, bool boot, int32_t from_bound, const Guess* g, int32_t n_outliers, const uint64_t* outlier_ids) {
-    visfs_flow* f = t->f;
-    const Bufs& B = t->B;
-    const Shape& S = t->S;
-    TK_HIP(t, hipSetDevice(f->dev));
-    // (the pinned input block is free: the call that filled it last ended in a synchronise)
-    InHead ih{ n_outliers, 0 };
-    std::memcpy(t->p_in, &ih, sizeof(ih));
-    if (n_outliers > 0) std::memcpy(t->p_in + sizeof(InHead), outlier_ids, sizeof(uint64_t) * (size_t)n_outliers);
-    TK_HIP(t, hipMemcpyAsync(t->d_in, t->p_in, sizeof(InHead) + sizeof(uint64_t) * (size_t)n_outliers, hipMemcpyHostToDevice, f->stream));
-    hipLaunchKernelGGL(k_trk_pretreat, dim3(1), dim3(TK_T), 0, f->stream, B, S);
-    TK_HIP(t, hipGetLastError());
-    const int cur = f->cur, prev = 1 - f->cur;
-    const auto image = [&](int slot, int i) { return Image{ f->dpx[slot][i], f->dder[slot][i] }; };
-    const Camera cam = make_camera(f->prm, t->cam);
-    const bool back = f->prm.flow_back != 0;
-    const int32_t* d_n = nullptr;
-    const float* d_xy = nullptr;
-    if (boot) {
-        int rc = corners_enqueue(f, f->dpx[prev][0], t->prm.quality_level, (double)t->prm.min_distance, nullptr, nullptr, B.ctl->boot_args,
-                                 &d_n, &d_xy);
-        if (rc != VISFS_BA_OK) return fail(t, rc, f->err);
-        hipLaunchKernelGGL((k_trk_append<true>), dim3(1), dim3(TK_T), 0, f->stream, B, S, d_n, d_xy);
-        TK_HIP(t, hipGetLastError());
-        hipLaunchKernelGGL((k_trk_stereo<false, true>), dim3((unsigned)S.M), dim3(64), 0, f->stream, B, S, image(prev, 0), image(prev, 1), f->lk,
-                           f->lay, cam, 0.0f);
-        TK_HIP(t, hipGetLastError());
-    }
-    if (from_bound > 0) {
-        const Guess none{};
-        const dim3 grid((unsigned)from_bound), block(64);
-        if (back) hipLaunchKernelGGL((k_trk_track<true>), grid, block, 0, f->stream, B, S, image(prev, 0), image(cur, 0), f->lk, f->lay,
-                                     g ? *g : none, g ? 1 : 0, f->prm.back_gate_track);
-        else hipLaunchKernelGGL((k_trk_track<false>), grid, block, 0, f->stream, B, S, image(prev, 0), image(cur, 0), f->lk, f->lay,
-                                g ? *g : none, g ? 1 : 0, f->prm.back_gate_track);
-        TK_HIP(t, hipGetLastError());
-    }
-    hipLaunchKernelGGL(k_trk_reduce, dim3(1), dim3(TK_T), 0, f->stream, B, S);
-    TK_HIP(t, hipGetLastError());
-    hipLaunchKernelGGL(k_trk_discs, dim3(1), dim3(TK_T), 0, f->stream, B, S);
-    TK_HIP(t, hipGetLastError());
-    const int rc = corners_enqueue(f, f->dpx[cur][0], t->prm.quality_level, (double)t->prm.min_distance, B.raster, B.hw, B.ctl->corner_args,
-                                   &d_n, &d_xy);
-    if (rc != VISFS_BA_OK) return fail(t, rc, f->err);
-    hipLaunchKernelGGL((k_trk_append<false>), dim3(1), dim3(TK_T), 0, f->stream, B, S, d_n, d_xy);
-    TK_HIP(t, hipGetLastError());
-    const dim3 grid((unsigned)S.M), block(64);
-    if (back) hipLaunchKernelGGL((k_trk_stereo<true, false>), grid, block, 0, f->stream, B, S, image(cur, 0), image(cur, 1), f->lk, f->lay, cam,
-                                 f->prm.back_gate_stereo);
-    else hipLaunchKernelGGL((k_trk_stereo<false, false>), grid, block, 0, f->stream, B, S, image(cur, 0), image(cur, 1), f->lk, f->lay, cam,
-                            f->prm.back_gate_stereo);
-    TK_HIP(t, hipGetLastError());
-    hipLaunchKernelGGL(k_trk_finish, dim3(1), dim3(TK_T), 0, f->stream, B, S, boot ? 1 : 0);
-    TK_HIP(t, hipGetLastError());
-    TK_HIP(t, hipMemcpyAsync(t->p_out, t->d_out, t->out_bytes, hipMemcpyDeviceToHost, f->stream));
-    TK_HIP(t, hipStreamSynchronize(f->stream));
-    return VISFS_BA_OK;
-}
-
 void clear_result(visfs_tracker* t, visfs_tracker_result* r, int32_t flags, uint64_t next_id) {
     std::memset(r, 0, sizeof(*r));
     r->flags = flags; r->next_id = next_id;
@@ -974,6 +902,181 @@ int take_result(visfs_tracker* t, bool boot, visfs_tracker_result* result) {
     return VISFS_BA_OK;
 }
 
+struct MemberPlan {                            // what the host decides for a member before anything is pushed
+    bool no_previous, boot, has_guess;
+    int32_t from_bound;                        // rows the tracking launch must cover
+    int slot;                                  // where the pair goes
+    Guess g;
+};
+
+MemberPlan plan_member(const visfs_tracker* t, const double* delta_guess, int32_t n_outliers, const uint64_t* outlier_ids) {
+    const visfs_flow* f = t->f;
+    MemberPlan P;
+    const int32_t remaining = remaining_rows(t, n_outliers, outlier_ids);
+    P.boot = remaining == 0;                   // (a bootstrapped table is never empty where corners exist: Tracker.cpp:238)
+    P.no_previous = f->frames == 0;            // Tracker.cpp:168
+    P.from_bound = P.boot ? t->S.M : remaining;
+    P.slot = f->frames == 0 ? f->cur : 1 - f->cur;
+    P.has_guess = delta_guess != nullptr;
+    P.g = Guess{};
+    if (P.has_guess) {
+        guess_camera_ref(delta_guess, t->cam.Tir, P.g);
+        P.g.fx = (double)t->cam.fx; P.g.fy = (double)t->cam.fy; P.g.cx = (double)t->cam.cx; P.g.cy = (double)t->cam.cy;
+    }
+    return P;
+}
+
+// The books of a member after its call: the pair is in its slot (the host twin's push has moved the flow object on itself), the
+// result goes to the caller.
+int commit_member(visfs_tracker* t, const MemberPlan& P, visfs_tracker_result* result) {
+    visfs_flow* f = t->f;
+    if (f->device) {
+        if (t->prm.clahe)
+            group_clahe_pushed(f, clahe::make_geom(f->w, f->h, t->prm.clahe_params.tiles_x, t->prm.clahe_params.tiles_y,
+                                                   t->prm.clahe_params.clip_limit));
+        f->cur = P.slot;
+        ++f->frames;
+    }
+    t->seen_frames = f->frames;
+    if (P.no_previous) {
+        clear_result(t, result, kNoPrevious, 0);
+        t->have_call = false;
+        return VISFS_BA_OK;
+    }
+    return take_result(t, P.boot, result);
+}
+
+// ---------------------------------------------------------------- device: the launches of a call
+struct CallFault { int member = -1; std::string why; };               // which member a failed call blames (-1: none), and why
+
+#define RC_HIP(expr)                                                                                      \
+    do {                                                                                                  \
+        hipError_t e_ = (expr);                                                                           \
+        if (e_ != hipSuccess) { fault->member = -1; fault->why = std::string(#expr) + ": " + hipGetErrorString(e_); return VISFS_BA_ERR_DEVICE; } \
+    } while (0)
+
+// A call of n members (equal shapes and parameters, one handle) through the block `blk` on `stream`; a single call is n = 1 through
+// the tracker's own block.  Nothing here waits for a value read back: the one wait in front is for the pinned staging images and
+// the pinned tables of the call before to have left, the one behind ends the call.
+int run_call(visfs_tracker* const* m, int n, const visfs_tracker_frame* fr, const MemberPlan* plan, const CallBlock& blk, int device,
+             hipStream_t stream, GroupCounts* cnt_out, CallFault* fault) {
+    visfs_tracker* t0 = m[0];
+    visfs_flow* f0 = t0->f;
+    const Shape S = t0->S;
+    const bool clahe_on = t0->prm.clahe != 0, back = f0->prm.flow_back != 0;
+    const clahe::Geom geom = clahe_on ? clahe::make_geom(f0->w, f0->h, t0->prm.clahe_params.tiles_x, t0->prm.clahe_params.tiles_y,
+                                                         t0->prm.clahe_params.clip_limit)
+                                      : clahe::Geom{};
+    GroupCounts& cnt = *cnt_out;
+    const auto blame = [&](int rc, int member, const std::string& why) { fault->member = member; fault->why = why; return rc; };
+    RC_HIP(hipSetDevice(device));
+    RC_HIP(hipStreamSynchronize(stream));
+    ++cnt.syncs;
+    PyrRec* pyr = reinterpret_cast<PyrRec*>(blk.pinned + blk.off_pyr);
+    ClaheRec* clr = reinterpret_cast<ClaheRec*>(blk.pinned + blk.off_clahe);
+    CornerRec* cboot = reinterpret_cast<CornerRec*>(blk.pinned + blk.off_boot);
+    CornerRec* ctop = reinterpret_cast<CornerRec*>(blk.pinned + blk.off_top);
+    TrkRec* trk = reinterpret_cast<TrkRec*>(blk.pinned + blk.off_trk);
+    InHead* inh = reinterpret_cast<InHead*>(blk.pinned + blk.off_in);
+    uint64_t* ids = reinterpret_cast<uint64_t*>(blk.pinned + blk.off_ids);
+    size_t n_ids = 0;
+    bool any_active = false, any_boot = false;
+    int32_t bound = 0;
+    for (int i = 0; i < n; ++i) {
+        visfs_tracker* t = m[i];
+        visfs_flow* f = t->f;
+        const MemberPlan& P = plan[i];
+        const int cur = P.slot, prev = 1 - P.slot;
+        int rc;
+        if (clahe_on) {
+            uint8_t* raw[2];
+            group_clahe_fill(f, geom, cur, &clr[i], raw);
+            rc = group_stage(f, raw, fr[i].left, fr[i].right, fr[i].stride, &cnt);
+        } else {
+            rc = group_stage(f, f->dpx[cur], fr[i].left, fr[i].right, fr[i].stride, &cnt);
+        }
+        if (rc != VISFS_BA_OK) return blame(rc, i, f->err);
+        group_pyr_fill(f, cur, &pyr[i]);
+        const bool skip = P.no_previous;
+        TrkRec& r = trk[i];
+        r.B = t->B;
+        r.B.in = reinterpret_cast<const InHead*>(blk.dev + blk.off_in) + i;
+        r.B.outliers = reinterpret_cast<const uint64_t*>(blk.dev + blk.off_ids) + n_ids;
+        inh[i] = InHead{ fr[i].n_outliers, 0 };
+        if (fr[i].n_outliers > 0) std::memcpy(ids + n_ids, fr[i].outlier_ids, sizeof(uint64_t) * (size_t)fr[i].n_outliers);
+        n_ids += (size_t)fr[i].n_outliers;
+        for (int k = 0; k < 2; ++k) {
+            r.prev[k] = Image{ f->dpx[prev][k], f->dder[prev][k] };
+            r.cur[k] = Image{ f->dpx[cur][k], f->dder[cur][k] };
+        }
+        r.cam = make_camera(f->prm, t->cam);
+        r.g = P.g;
+        r.has_guess = P.has_guess ? 1 : 0; r.skip = skip ? 1 : 0; r.boot = P.boot ? 1 : 0; r.pad = 0;
+        // both extractions of a member work in the same state, one behind the other in stream order
+        group_corners_fill(f, f->dpx[prev][0], nullptr, nullptr, t->B.ctl->boot_args, skip || !P.boot, &cboot[i], &r.corner_n, &r.corner_xy);
+        group_corners_fill(f, f->dpx[cur][0], t->B.raster, t->B.hw, t->B.ctl->corner_args, skip, &ctop[i], &r.corner_n, &r.corner_xy);
+        if (!skip) {
+            any_active = true;
+            any_boot = any_boot || P.boot;
+            bound = std::max(bound, P.from_bound);
+            t->have_call = false;
+        }
+    }
+    RC_HIP(hipMemcpyAsync(blk.dev, blk.pinned, blk.off_ids + sizeof(uint64_t) * n_ids, hipMemcpyHostToDevice, stream));
+    ++cnt.copies;
+    const auto dev = [&](size_t off) { return blk.dev + off; };
+    int rc;
+    if (clahe_on) {
+        rc = group_clahe(f0, geom, n, reinterpret_cast<const ClaheRec*>(dev(blk.off_clahe)), &cnt);
+        if (rc != VISFS_BA_OK) return blame(rc, -1, f0->err);
+    }
+    rc = group_pyramids(f0, n, reinterpret_cast<const PyrRec*>(dev(blk.off_pyr)), &cnt);
+    if (rc != VISFS_BA_OK) return blame(rc, -1, f0->err);
+    if (any_active) {
+        const TrkRec* d_trk = reinterpret_cast<const TrkRec*>(dev(blk.off_trk));
+        const unsigned z = (unsigned)n;
+        const dim3 one(1, 1, z), rows((unsigned)S.M, 1, z), wg(TK_T), wave(64);
+        const double quality = t0->prm.quality_level, min_distance = (double)t0->prm.min_distance;
+#define RC_LAUNCH(kernel, grid, block, ...)                                                  \
+    do {                                                                                     \
+        hipLaunchKernelGGL(kernel, grid, block, 0, stream, __VA_ARGS__);                     \
+        RC_HIP(hipGetLastError());                                                           \
+        ++cnt.kernels;                                                                       \
+    } while (0)
+        RC_LAUNCH(k_trk_pretreat_g, one, wg, d_trk, S);
+        if (any_boot) {
+            rc = group_corners(f0, quality, min_distance, n, reinterpret_cast<const CornerRec*>(dev(blk.off_boot)), &cnt);
+            if (rc != VISFS_BA_OK) return blame(rc, -1, f0->err);
+            RC_LAUNCH((k_trk_append_g<true>), one, wg, d_trk, S);
+            RC_LAUNCH((k_trk_stereo_g<false, true>), rows, wave, d_trk, S, f0->lk, f0->lay, 0.0f);
+        }
+        if (bound > 0) {
+            const dim3 grid((unsigned)bound, 1, z);
+            if (back) RC_LAUNCH((k_trk_track_g<true>), grid, wave, d_trk, S, f0->lk, f0->lay, f0->prm.back_gate_track);
+            else RC_LAUNCH((k_trk_track_g<false>), grid, wave, d_trk, S, f0->lk, f0->lay, f0->prm.back_gate_track);
+        }
+        RC_LAUNCH(k_trk_reduce_g, one, wg, d_trk, S);
+        RC_LAUNCH(k_trk_discs_g, one, wg, d_trk, S);
+        rc = group_corners(f0, quality, min_distance, n, reinterpret_cast<const CornerRec*>(dev(blk.off_top)), &cnt);
+        if (rc != VISFS_BA_OK) return blame(rc, -1, f0->err);
+        RC_LAUNCH((k_trk_append_g<false>), one, wg, d_trk, S);
+        if (back) RC_LAUNCH((k_trk_stereo_g<true, false>), rows, wave, d_trk, S, f0->lk, f0->lay, f0->prm.back_gate_stereo);
+        else RC_LAUNCH((k_trk_stereo_g<false, false>), rows, wave, d_trk, S, f0->lk, f0->lay, f0->prm.back_gate_stereo);
+        RC_LAUNCH(k_trk_finish_g, one, wg, d_trk, S);
+#undef RC_LAUNCH
+        for (int i = 0; i < n; ++i) {
+            if (plan[i].no_previous) continue;
+            visfs_tracker* t = m[i];
+            RC_HIP(hipMemcpyAsync(t->p_out, t->d_out, t->out_bytes, hipMemcpyDeviceToHost, stream));
+            ++cnt.copies;
+        }
+    }
+    RC_HIP(hipStreamSynchronize(stream));
+    ++cnt.syncs;
+    return VISFS_BA_OK;
+}
+#undef RC_HIP
+
 void detach(visfs_tracker* t) {
     if (!t->f) return;
     free_device(t);
@@ -1030,6 +1133,11 @@ int visfs_tracker_create(visfs_flow* f, const visfs_tracker_params* p, const vis
         t->seen_frames = f->frames;
         rc = allocate(t);
         if (rc != VISFS_BA_OK) { f->err = t->err; free_device(t); delete t; return rc; }
+        if (f->device) {                       // the states the call's records point into
+            rc = group_corners_prepare(f);
+            if (rc == VISFS_BA_OK && p->clahe) rc = group_clahe_prepare(f);
+            if (rc != VISFS_BA_OK) { free_device(t); delete t; return rc; }
+        }
         if (!f->trackers) f->trackers = new TrackerState();
         f->trackers->list.push_back(t);
         *out = t;
@@ -1065,43 +1173,35 @@ int visfs_tracker_process(visfs_tracker* t, const uint8_t* left, const uint8_t* 
         visfs_flow* f = t->f;
         const int rc_args = check_call(t, left, right, stride, delta_guess, n_outliers, outlier_ids, result);
         if (rc_args != VISFS_BA_OK) return rc_args;
-        const int32_t remaining = remaining_rows(t, n_outliers, outlier_ids);
-        const bool boot = remaining == 0;
-        const bool no_previous = f->frames == 0;
+        const MemberPlan P = plan_member(t, delta_guess, n_outliers, outlier_ids);
+        if (f->device) {                                               // a group of one through the tracker's own block
+            const visfs_tracker_frame fr{ left, right, stride, delta_guess, n_outliers, outlier_ids };
+            GroupCounts counts;
+            CallFault fault;
+            const int rc = run_call(&t, 1, &fr, &P, t->blk, f->dev, f->stream, &counts, &fault);
+            if (rc != VISFS_BA_OK) { t->ids.clear(); return fail(t, rc, fault.why); }
+            return commit_member(t, P, result);
+        }
         const int rc_push = t->prm.clahe ? visfs_flow_push_frame_clahe(f, &t->prm.clahe_params, left, right, stride)
                                          : visfs_flow_push_frame(f, left, right, stride);
         if (rc_push != VISFS_BA_OK) return fail(t, rc_push, f->err);
         t->seen_frames = f->frames;
-        if (no_previous) {                                             // Tracker.cpp:168
-            clear_result(t, result, kNoPrevious, 0);
+        if (!P.no_previous) {
             t->have_call = false;
-            return (int)VISFS_BA_OK;
-        }
-        Guess g{};
-        const bool has_guess = delta_guess != nullptr;                 // (a bootstrapped table is never empty where corners exist: :238)
-        if (has_guess) {
-            guess_camera_ref(delta_guess, t->cam.Tir, g);
-            g.fx = (double)t->cam.fx; g.fy = (double)t->cam.fy; g.cx = (double)t->cam.cx; g.cy = (double)t->cam.cy;
-        }
-        t->have_call = false;
-        if (f->device) {
-            const int rc = device_call(t, boot, boot ? t->S.M : remaining, has_guess ? &g : nullptr, n_outliers, outlier_ids);
-            if (rc != VISFS_BA_OK) { t->ids.clear(); return rc; }
-        } else {
             InHead ih{ n_outliers, 0 };
             std::memcpy(t->h_inblk.data(), &ih, sizeof(ih));
             if (n_outliers > 0) std::memcpy(t->h_inblk.data() + sizeof(InHead), outlier_ids, sizeof(uint64_t) * (size_t)n_outliers);
             host_pretreat(t);
-            if (boot) {
+            if (P.boot) {
                 const int rc = host_bootstrap(t);
                 if (rc != VISFS_BA_OK) return rc;
             }
-            host_track_reduce(t, has_guess ? &g : nullptr);
+            host_track_reduce(t, P.has_guess ? &P.g : nullptr);
             host_discs(t);
-            const int rc = host_topup_stereo_finish(t, boot);
+            const int rc = host_topup_stereo_finish(t, P.boot);
             if (rc != VISFS_BA_OK) return rc;
         }
-        return take_result(t, boot, result);
+        return commit_member(t, P, result);
     });
 }
 
@@ -1162,12 +1262,6 @@ int gfail(visfs_tracker_group* g, int rc, int member, const std::string& why) {
     g->err = member >= 0 ? "member " + std::to_string(member) + ": " + why : why;
     return rc;
 }
-#define GR_HIP(g, expr)                                                                                   \
-    do {                                                                                                  \
-        hipError_t e_ = (expr);                                                                           \
-        if (e_ != hipSuccess) return gfail((g), VISFS_BA_ERR_DEVICE, -1, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 bool same_flow_params(const visfs_flow_params& a, const visfs_flow_params& b) {
     return a.win_size == b.win_size && a.max_level == b.max_level && a.iterations == b.iterations && a.eps == b.eps &&
            a.flow_back == b.flow_back && a.min_eig_threshold == b.min_eig_threshold && a.back_gate_track == b.back_gate_track &&
@@ -1180,160 +1274,11 @@ bool same_tracker_params(const visfs_tracker_params& a, const visfs_tracker_para
            a.clahe_params.tiles_x == b.clahe_params.tiles_x && a.clahe_params.tiles_y == b.clahe_params.tiles_y;
 }
 
-size_t up256(size_t x) { return (x + 255) & ~size_t(255); }
-
 void free_group(visfs_tracker_group* g) {
     if (!g->device) return;
     (void)hipSetDevice(g->dev);
     if (g->stream) (void)hipStreamSynchronize(g->stream);
-    if (g->d_blk) (void)hipFree(g->d_blk);
-    if (g->p_blk) (void)hipHostFree(g->p_blk);
-    g->d_blk = g->p_blk = nullptr;
-}
-
-int allocate_group(visfs_tracker_group* g) {
-    const size_t n = g->m.size();
-    size_t off = 0;
-    const auto take = [&](size_t bytes) { const size_t at = off; off = up256(off + bytes); return at; };
-    g->off_pyr = take(n * sizeof(PyrRec));
-    g->off_clahe = take(n * sizeof(ClaheRec));
-    g->off_boot = take(n * sizeof(CornerRec));
-    g->off_top = take(n * sizeof(CornerRec));
-    g->off_trk = take(n * sizeof(TrkRec));
-    g->off_in = take(n * sizeof(InHead));
-    g->off_ids = take(n * sizeof(uint64_t) * kMaxOutliers);
-    g->blk_bytes = off;
-    GR_HIP(g, hipSetDevice(g->dev));
-    GR_HIP(g, hipMalloc(reinterpret_cast<void**>(&g->d_blk), g->blk_bytes));
-    GR_HIP(g, hipHostMalloc(reinterpret_cast<void**>(&g->p_blk), g->blk_bytes, hipHostMallocDefault));
-    std::memset(g->p_blk, 0, g->blk_bytes);
-    return VISFS_BA_OK;
-}
-
-struct MemberPlan {                            // what the host decides for a member before anything is pushed
-    bool no_previous, boot, has_guess;
-    int32_t from_bound;
-    int slot;                                  // where the pair goes
-    Guess g;
-};
-
-// The launches of device_call for every member at once.  Nothing here waits for a value read back; the one wait in front is the one
-// device_stage has (the pinned staging images and the pinned table of the call before have left), the one behind ends the call.
-int group_device_call(visfs_tracker_group* g, const visfs_tracker_frame* fr, const std::vector<MemberPlan>& plan) {
-    const int n = (int)g->m.size();
-    visfs_tracker* t0 = g->m[0];
-    visfs_flow* f0 = t0->f;
-    const Shape S = t0->S;
-    const bool clahe_on = t0->prm.clahe != 0, back = f0->prm.flow_back != 0;
-    const clahe::Geom geom = clahe_on ? clahe::make_geom(f0->w, f0->h, t0->prm.clahe_params.tiles_x, t0->prm.clahe_params.tiles_y,
-                                                         t0->prm.clahe_params.clip_limit)
-                                      : clahe::Geom{};
-    GroupCounts& cnt = g->cnt;
-    GR_HIP(g, hipSetDevice(g->dev));
-    GR_HIP(g, hipStreamSynchronize(g->stream));
-    ++cnt.syncs;
-    PyrRec* pyr = reinterpret_cast<PyrRec*>(g->p_blk + g->off_pyr);
-    ClaheRec* clr = reinterpret_cast<ClaheRec*>(g->p_blk + g->off_clahe);
-    CornerRec* cboot = reinterpret_cast<CornerRec*>(g->p_blk + g->off_boot);
-    CornerRec* ctop = reinterpret_cast<CornerRec*>(g->p_blk + g->off_top);
-    TrkRec* trk = reinterpret_cast<TrkRec*>(g->p_blk + g->off_trk);
-    InHead* inh = reinterpret_cast<InHead*>(g->p_blk + g->off_in);
-    uint64_t* ids = reinterpret_cast<uint64_t*>(g->p_blk + g->off_ids);
-    size_t n_ids = 0;
-    bool any_active = false, any_boot = false;
-    int32_t bound = 0;
-    for (int i = 0; i < n; ++i) {
-        visfs_tracker* t = g->m[i];
-        visfs_flow* f = t->f;
-        const MemberPlan& P = plan[i];
-        const int cur = P.slot, prev = 1 - P.slot;
-        int rc;
-        if (clahe_on) {
-            uint8_t* raw[2];
-            group_clahe_fill(f, geom, cur, &clr[i], raw);
-            rc = group_stage(f, raw, fr[i].left, fr[i].right, fr[i].stride, &cnt);
-        } else {
-            rc = group_stage(f, f->dpx[cur], fr[i].left, fr[i].right, fr[i].stride, &cnt);
-        }
-        if (rc != VISFS_BA_OK) return gfail(g, rc, i, f->err);
-        group_pyr_fill(f, cur, &pyr[i]);
-        const bool skip = P.no_previous;
-        TrkRec& r = trk[i];
-        r.B = t->B;
-        r.B.in = reinterpret_cast<const InHead*>(g->d_blk + g->off_in) + i;
-        r.B.outliers = reinterpret_cast<const uint64_t*>(g->d_blk + g->off_ids) + n_ids;
-        inh[i] = InHead{ fr[i].n_outliers, 0 };
-        if (fr[i].n_outliers > 0) std::memcpy(ids + n_ids, fr[i].outlier_ids, sizeof(uint64_t) * (size_t)fr[i].n_outliers);
-        n_ids += (size_t)fr[i].n_outliers;
-        for (int k = 0; k < 2; ++k) {
-            r.prev[k] = Image{ f->dpx[prev][k], f->dder[prev][k] };
-            r.cur[k] = Image{ f->dpx[cur][k], f->dder[cur][k] };
-        }
-        r.cam = make_camera(f->prm, t->cam);
-        r.g = P.g;
-        r.has_guess = P.has_guess ? 1 : 0; r.skip = skip ? 1 : 0; r.boot = P.boot ? 1 : 0; r.pad = 0;
-        // both extractions of a member work in the same state, one behind the other in stream order
-        group_corners_fill(f, f->dpx[prev][0], nullptr, nullptr, t->B.ctl->boot_args, skip || !P.boot, &cboot[i], &r.corner_n, &r.corner_xy);
-        group_corners_fill(f, f->dpx[cur][0], t->B.raster, t->B.hw, t->B.ctl->corner_args, skip, &ctop[i], &r.corner_n, &r.corner_xy);
-        if (!skip) {
-            any_active = true;
-            any_boot = any_boot || P.boot;
-            bound = std::max(bound, P.from_bound);
-            t->have_call = false;
-        }
-    }
-    GR_HIP(g, hipMemcpyAsync(g->d_blk, g->p_blk, g->off_ids + sizeof(uint64_t) * n_ids, hipMemcpyHostToDevice, g->stream));
-    ++cnt.copies;
-    const auto dev = [&](size_t off) { return g->d_blk + off; };
-    int rc;
-    if (clahe_on) {
-        rc = group_clahe(f0, geom, n, reinterpret_cast<const ClaheRec*>(dev(g->off_clahe)), &cnt);
-        if (rc != VISFS_BA_OK) return gfail(g, rc, -1, f0->err);
-    }
-    rc = group_pyramids(f0, n, reinterpret_cast<const PyrRec*>(dev(g->off_pyr)), &cnt);
-    if (rc != VISFS_BA_OK) return gfail(g, rc, -1, f0->err);
-    if (any_active) {
-        const TrkRec* d_trk = reinterpret_cast<const TrkRec*>(dev(g->off_trk));
-        const unsigned z = (unsigned)n;
-        const dim3 one(1, 1, z), rows((unsigned)S.M, 1, z), wg(TK_T), wave(64);
-        const double quality = t0->prm.quality_level, min_distance = (double)t0->prm.min_distance;
-#define GR_LAUNCH(kernel, grid, block, ...)                                                  \
-    do {                                                                                     \
-        hipLaunchKernelGGL(kernel, grid, block, 0, g->stream, __VA_ARGS__);                  \
-        GR_HIP(g, hipGetLastError());                                                        \
-        ++cnt.kernels;                                                                       \
-    } while (0)
-        GR_LAUNCH(k_trk_pretreat_g, one, wg, d_trk, S);
-        if (any_boot) {
-            rc = group_corners(f0, quality, min_distance, n, reinterpret_cast<const CornerRec*>(dev(g->off_boot)), &cnt);
-            if (rc != VISFS_BA_OK) return gfail(g, rc, -1, f0->err);
-            GR_LAUNCH((k_trk_append_g<true>), one, wg, d_trk, S);
-            GR_LAUNCH((k_trk_stereo_g<false, true>), rows, wave, d_trk, S, f0->lk, f0->lay, 0.0f);
-        }
-        if (bound > 0) {
-            const dim3 grid((unsigned)bound, 1, z);
-            if (back) GR_LAUNCH((k_trk_track_g<true>), grid, wave, d_trk, S, f0->lk, f0->lay, f0->prm.back_gate_track);
-            else GR_LAUNCH((k_trk_track_g<false>), grid, wave, d_trk, S, f0->lk, f0->lay, f0->prm.back_gate_track);
-        }
-        GR_LAUNCH(k_trk_reduce_g, one, wg, d_trk, S);
-        GR_LAUNCH(k_trk_discs_g, one, wg, d_trk, S);
-        rc = group_corners(f0, quality, min_distance, n, reinterpret_cast<const CornerRec*>(dev(g->off_top)), &cnt);
-        if (rc != VISFS_BA_OK) return gfail(g, rc, -1, f0->err);
-        GR_LAUNCH((k_trk_append_g<false>), one, wg, d_trk, S);
-        if (back) GR_LAUNCH((k_trk_stereo_g<true, false>), rows, wave, d_trk, S, f0->lk, f0->lay, f0->prm.back_gate_stereo);
-        else GR_LAUNCH((k_trk_stereo_g<false, false>), rows, wave, d_trk, S, f0->lk, f0->lay, f0->prm.back_gate_stereo);
-        GR_LAUNCH(k_trk_finish_g, one, wg, d_trk, S);
-#undef GR_LAUNCH
-        for (int i = 0; i < n; ++i) {
-            if (plan[i].no_previous) continue;
-            visfs_tracker* t = g->m[i];
-            GR_HIP(g, hipMemcpyAsync(t->p_out, t->d_out, t->out_bytes, hipMemcpyDeviceToHost, g->stream));
-            ++cnt.copies;
-        }
-    }
-    GR_HIP(g, hipStreamSynchronize(g->stream));
-    ++cnt.syncs;
-    return VISFS_BA_OK;
+    g->blk.release();
 }
 
 }  // namespace
@@ -1368,7 +1313,10 @@ int visfs_tracker_group_create(int32_t n, visfs_tracker* const* members, visfs_t
         g->device = f0->device;
         if (g->device) {
             g->dev = f0->dev; g->stream = f0->stream;
-            int rc = allocate_group(g);
+            int rc = VISFS_BA_OK;
+            hipError_t e = hipSetDevice(g->dev);
+            if (e == hipSuccess) e = g->blk.allocate((size_t)n);
+            if (e != hipSuccess) rc = gfail(g, VISFS_BA_ERR_DEVICE, -1, std::string("the group's call block: ") + hipGetErrorString(e));
             for (int i = 0; i < n && rc == VISFS_BA_OK; ++i) {
                 visfs_flow* f = members[i]->f;
                 rc = group_corners_prepare(f);
@@ -1435,47 +1383,17 @@ int visfs_tracker_group_process(visfs_tracker_group* g, const visfs_tracker_fram
             return VISFS_BA_OK;
         }
         std::vector<MemberPlan> plan((size_t)n);
-        for (int i = 0; i < n; ++i) {
-            visfs_tracker* t = g->m[i];
-            const visfs_flow* f = t->f;
-            const visfs_tracker_frame& fr = frames[i];
-            MemberPlan& P = plan[(size_t)i];
-            const int32_t remaining = remaining_rows(t, fr.n_outliers, fr.outlier_ids);
-            P.boot = remaining == 0;
-            P.no_previous = f->frames == 0;
-            P.from_bound = P.boot ? t->S.M : remaining;
-            P.slot = f->frames == 0 ? f->cur : 1 - f->cur;
-            P.has_guess = fr.delta_guess != nullptr;
-            P.g = Guess{};
-            if (P.has_guess) {
-                guess_camera_ref(fr.delta_guess, t->cam.Tir, P.g);
-                P.g.fx = (double)t->cam.fx; P.g.fy = (double)t->cam.fy; P.g.cx = (double)t->cam.cx; P.g.cy = (double)t->cam.cy;
-            }
-        }
-        const int rc = group_device_call(g, frames, plan);
+        for (int i = 0; i < n; ++i) plan[(size_t)i] = plan_member(g->m[i], frames[i].delta_guess, frames[i].n_outliers, frames[i].outlier_ids);
+        CallFault fault;
+        const int rc = run_call(g->m.data(), n, frames, plan.data(), g->blk, g->dev, g->stream, &g->cnt, &fault);
         if (rc != VISFS_BA_OK) {
             for (visfs_tracker* t : g->m) t->ids.clear();
-            return rc;
+            return gfail(g, rc, fault.member, fault.why);
         }
-        const bool clahe_on = g->m[0]->prm.clahe != 0;
         int rc_all = VISFS_BA_OK;
         for (int i = 0; i < n; ++i) {
-            visfs_tracker* t = g->m[i];
-            visfs_flow* f = t->f;
-            const MemberPlan& P = plan[(size_t)i];
-            if (clahe_on)
-                group_clahe_pushed(f, clahe::make_geom(f->w, f->h, t->prm.clahe_params.tiles_x, t->prm.clahe_params.tiles_y,
-                                                       t->prm.clahe_params.clip_limit));
-            f->cur = P.slot;
-            ++f->frames;
-            t->seen_frames = f->frames;
-            if (P.no_previous) {
-                clear_result(t, &results[i], kNoPrevious, 0);
-                t->have_call = false;
-                continue;
-            }
-            const int rc_i = take_result(t, P.boot, &results[i]);
-            if (rc_i != VISFS_BA_OK && rc_all == VISFS_BA_OK) rc_all = gfail(g, rc_i, i, t->err);
+            const int rc_i = commit_member(g->m[i], plan[(size_t)i], &results[i]);
+            if (rc_i != VISFS_BA_OK && rc_all == VISFS_BA_OK) rc_all = gfail(g, rc_i, i, g->m[i]->err);
         }
         return rc_all;
     } catch (...) {
