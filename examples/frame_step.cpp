@@ -5,6 +5,8 @@
 //
 //   g++ -std=c++17 -O2 -Iinclude -Ivisfs_amd/host examples/frame_step.cpp -Lvisfs_amd/lib -lvisfs_window -lvisfs_ba_hip
 //       -Wl,-rpath,$PWD/visfs_amd/lib -o frame_step && ./frame_step 5          (./frame_step 5 host: the one-core twins, no GPU)
+//   ./frame_step 5 cull (or: 5 host cull): the configuration of the launch files that set Tracker/FlowBack to false: no reverse
+//   passes, and Tracker/CullByFundationMatrix inside the resident call in their place.
 //
 // A stereo camera slides sideways in front of a textured wall 5 m away, so the true motion and depth are known.  The pose PnP finds
 // in one frame is the guess of the next; the first guess is the identity, which the wrapper treats as "not set" (Tracker.cpp:237).
@@ -61,7 +63,8 @@ struct Summary {
     double max_translation_err = 0.0, max_depth_err = 0.0, ms = 0.0;
 };
 
-inline int run(int frames, visfs_flow* flow, visfs_pnp* pnp, Summary& out) {
+// cull: Tracker/CullByFundationMatrix; the flow object must then have been made with flow_back off
+inline int run(int frames, visfs_flow* flow, visfs_pnp* pnp, Summary& out, bool cull = false) {
     const int W = 640, H = 400;
     const float fx = 435.2f, baseline = 0.11f;
     const double depth = 5.0, step = 0.06;                                      // metres per frame to the right: flow = -fx * step / depth
@@ -72,7 +75,7 @@ inline int run(int frames, visfs_flow* flow, visfs_pnp* pnp, Summary& out) {
     visfs_pnp_camera pcam{};
     pcam.fx = pcam.fy = fx; pcam.cx = 0.5 * W; pcam.cy = 0.5 * H;
     for (int i = 0; i < 12; ++i) { cam.Tir[i] = Tir[i]; pcam.Tir[i] = Tir[i]; }
-    VISFS::ResidentTracker tracker(flow, cam, 300, 0.01, 20, 10);
+    VISFS::ResidentTracker tracker(flow, cam, 300, 0.01, 20, 10, false, 3.0, 8, 8, cull, 1.0f);
     visfs_pnp_params pp;
     visfs_pnp_default_params(&pp);
     visfs_window_map* window = nullptr;
@@ -146,12 +149,17 @@ inline int run(int frames, visfs_flow* flow, visfs_pnp* pnp, Summary& out) {
 #ifndef FRAME_STEP_NO_MAIN
 int main(int argc, char** argv) {
     const int frames = argc > 1 ? std::atoi(argv[1]) : 5;
-    const bool host = argc > 2 && std::strcmp(argv[2], "host") == 0;
+    bool host = false, cull = false;
+    for (int i = 2; i < argc; ++i) {
+        host = host || std::strcmp(argv[i], "host") == 0;
+        cull = cull || std::strcmp(argv[i], "cull") == 0;
+    }
     visfs_ba_handle* ba = nullptr;
     visfs_flow* flow = nullptr;
     visfs_pnp* pnp = nullptr;
     visfs_flow_params fp;
     visfs_flow_default_params(&fp);
+    if (cull) fp.flow_back = 0;
     if (host) {
         if (visfs_flow_create_host(&fp, 640, 400, &flow) != VISFS_BA_OK || visfs_pnp_create_host(4096, &pnp) != VISFS_BA_OK) return 3;
     } else {
@@ -162,15 +170,15 @@ int main(int argc, char** argv) {
     }
     frame_step::Summary s;
     int rc;
-    try { rc = frame_step::run(frames, flow, pnp, s); } catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); rc = 1; }
+    try { rc = frame_step::run(frames, flow, pnp, s, cull); } catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); rc = 1; }
     visfs_pnp_destroy(pnp);
     visfs_flow_destroy(flow);
     if (ba) visfs_ba_destroy(ba);
     if (rc != 0) return 1;
     std::printf("{\"frames\": %d, \"inserted\": %d, \"words\": %d, \"covisible\": %d, \"new_words\": %d, \"bootstrapped\": %d, "
-                "\"identity_guesses\": %d, \"min_pnp_inliers\": %d, \"max_translation_err_m\": %.4g, \"max_depth_err_m\": %.4g, \"frame_ms\": %.2f}\n",
+                "\"identity_guesses\": %d, \"min_pnp_inliers\": %d, \"max_translation_err_m\": %.4g, \"max_depth_err_m\": %.4g, \"frame_ms\": %.2f, \"cull\": %d}\n",
                 s.frames, s.inserted, s.words, s.covisible, s.new_words, s.bootstrapped, s.identity_guesses, s.min_pnp_inliers,
-                s.max_translation_err, s.max_depth_err, s.ms);
+                s.max_translation_err, s.max_depth_err, s.ms, cull ? 1 : 0);
     return 0;
 }
 #endif

@@ -9,8 +9,9 @@
  * visfs_flow_create_host.  DESIGN.md section 9h lists the steps, the quirks of the reference that are kept and the two things dropped.
  *
  * The flow keys (window, levels, gates, flow_back, depth gates) are those of the visfs_flow object.  Tracker/CullByFundationMatrix
- * (flowBack off, Tracker.cpp:275) is not part of this call: a caller that needs it runs the staged chain (visfs_flow_track ->
- * visfs_fund_cull of visfs_fund.h -> its own reduce) instead.
+ * (Tracker.cpp:275-277, :83-96) is part of this call since ABI 2: with `cull` set and the flow object's flow_back off, the mask of the
+ * fundamental-matrix search of visfs_fund.h is ANDed into the Lucas-Kanade status between the temporal track and the reduce, on rows
+ * that never leave the device.
  *
  * Error codes are the VISFS_BA_* of visfs_ba.h.
  */
@@ -21,12 +22,13 @@
 #include "visfs_clahe.h"
 #include "visfs_corners.h"
 #include "visfs_flow.h"
+#include "visfs_fund.h"
 
 #ifdef __cplusplus
 extern "C" {
 #endif
 
-#define VISFS_TRACKER_ABI_VERSION  1
+#define VISFS_TRACKER_ABI_VERSION  2
 #define VISFS_TRACKER_MAX_FEATURES 4096
 #define VISFS_TRACKER_MAX_OUTLIERS 4096
 
@@ -44,6 +46,11 @@ typedef struct visfs_tracker_params {
     int32_t min_inliers;        /* Estimator/MinInliers  (default 10; >= 0) */
     int32_t clahe;              /* System/CLAHE: 0 pushes the raw pair, else the pair equalised with clahe_params */
     visfs_clahe_params clahe_params;
+    int32_t cull;               /* Tracker/CullByFundationMatrix (default 0).  As in the reference it runs only when the flow object's
+                                 * flow_back is 0; with flow_back set the field is ignored */
+    visfs_fund_params cull_params;  /* pixel_error: Tracker/FundationPixelError (default 1.0; <= 0 means 3.0), iterations (default
+                                 * 1000; 1 .. 4096), seed (default 0; used as given in every call, as OpenCV's RANSAC restarts its
+                                 * generator per call) */
 } visfs_tracker_params;
 
 /* The arrays belong to the tracker and stay valid until its next call.  Every list is in ascending id order, the order uKeys and
@@ -71,12 +78,16 @@ typedef struct visfs_tracker_result {
 } visfs_tracker_result;
 
 int  visfs_tracker_abi_version(void);
-void visfs_tracker_default_params(visfs_tracker_params* p);      /* 300, 0.01, 40, 10, CLAHE off (3.0, 8, 8) */
+void visfs_tracker_default_params(visfs_tracker_params* p);      /* 300, 0.01, 40, 10, CLAHE off (3.0, 8, 8), cull off (1.0, 1000, 0) */
 
 /* A tracker on the pyramids, device and stream of f (a visfs_flow_create or a visfs_flow_create_host object), which must outlive it.
  * cam: the stereo camera of visfs_flow_stereo.  The half-width tables of the two mask radii are made here.
  * VISFS_BA_ERR_UNSUPPORTED: max_features > 4096, min_distance > 32768.  VISFS_BA_ERR_BAD_ARGUMENT: max_features < 1, quality_level
- * not finite or <= 0, min_distance or min_inliers negative, a non-finite Tir, a CLAHE setting visfs_flow_push_frame_clahe refuses. */
+ * not finite or <= 0, min_distance or min_inliers negative, a non-finite Tir, a CLAHE setting visfs_flow_push_frame_clahe refuses.
+ * The cull fields are looked at only when cull != 0: VISFS_BA_ERR_BAD_ARGUMENT for iterations < 1 or a pixel_error that is not
+ * finite, VISFS_BA_ERR_UNSUPPORTED for iterations > 4096.  Every buffer of the cull is allocated here.
+ * (visfs_tracker_group_create is stricter: the members of a group must agree in cull and in every field of cull_params, as in every
+ * other field of this struct, also where cull is 0 or flow_back makes it inert.) */
 int  visfs_tracker_create(visfs_flow* f, const visfs_tracker_params* p, const visfs_flow_camera* cam, visfs_tracker** out);
 void visfs_tracker_destroy(visfs_tracker* t);
 const char* visfs_tracker_last_error(const visfs_tracker* t);
@@ -101,6 +112,17 @@ int  visfs_tracker_process(visfs_tracker* t, const uint8_t* left, const uint8_t*
 int  visfs_tracker_download(const visfs_tracker* t, int32_t* n_from, float* guess_xy, float* to_xy, uint8_t* lk_status,
                             uint8_t* in_bounds, int32_t* n_discs, visfs_corners_disc* discs, uint8_t* disc_drawn, int32_t* n_rows,
                             uint8_t* stereo_status);
+
+/* The fundamental-matrix cull of the last visfs_tracker_process call that got past NO_PREVIOUS; any pointer may be NULL.  The values
+ * mean what visfs_fund_cull, visfs_fund_last_sizes and visfs_fund_download report for the same from-rows: *applied (0: fewer than seven
+ * rows entered and the status passed through), *m (rows with four finite coordinates), *n_hypotheses (0, 1 for seven rows, else
+ * iterations), *n_inliers, mask[n_from], status[n_from] (the Lucas-Kanade status after the AND, which the reduce kept its rows on;
+ * lk_status of visfs_tracker_download stays the status before it), F[9], T1[9], T2[9], the winner (h, k) or (-1, -1).
+ * A tracker whose cull is inactive (cull == 0, or flow_back set) reports *applied = 0 and *m = 0, zeros elsewhere, writes neither mask
+ * nor status and returns VISFS_BA_OK.  VISFS_BA_ERR_NOT_LOADED before the first call that got past NO_PREVIOUS. */
+int  visfs_tracker_download_cull(const visfs_tracker* t, int32_t* applied, int32_t* m, int32_t* n_hypotheses, int32_t* n_inliers,
+                                 uint8_t* mask, uint8_t* status, double* F, double* T1, double* T2, int32_t* winner_h,
+                                 int32_t* winner_k);
 
 #ifdef __cplusplus
 }

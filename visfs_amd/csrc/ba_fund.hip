@@ -10,7 +10,12 @@
 // A call is one copy in (a header with the zeroed winner key and the two Hartley transforms, the kept rows at 16 B, their status
 // bytes), the two launches and one copy out (the result block, the mask, the status).  The transforms are computed on the host in
 // both flavours.  The arithmetic is ba_fund.hpp.
+//
+// The resident tracker (include/visfs_tracker.h) runs the same search on rows that never leave the device:
+// k_fund_ransac_g and k_fund_mask_g read their member's CullRec at blockIdx.z and m from device memory (fund::group_cull), and the
+// host twin of that tracker goes through fund::cull_host.
 #include "ba_fund.hpp"
+#include "ba_group.hpp"      // fund::group_cull, fund::cull_host
 #include "../../include/visfs_fund.h"
 
 #include <algorithm>
@@ -80,7 +85,8 @@ struct DevicePolicy {
     }
 };
 
-__global__ __launch_bounds__(FD_T) void k_fund_ransac(RansacArgs A) {
+// One body for the by-value kernel of the staged call and the record-reading kernel of the resident tracker.
+__device__ __forceinline__ void fund_ransac_body(const RansacArgs& A) {
     __shared__ Row s_rows[kMaxPoints];
     {
         const float4* src = reinterpret_cast<const float4*>(A.rows);
@@ -94,7 +100,34 @@ __global__ __launch_bounds__(FD_T) void k_fund_ransac(RansacArgs A) {
     Call c;
     c.T1 = A.head->T1; c.T2 = A.head->T2; c.m = A.m; c.iterations = A.iterations; c.seed = A.seed; c.thr2 = A.thr2;
     DevicePolicy pol{ A, s_rows, (int)(threadIdx.x & 63) };
+    // seven_rows: the models of the rows 0 .. 6 as hypothesis 0, unscored; every row is an inlier.  Only k_fund_ransac_g gets here:
+    // visfs_fund_cull handles seven rows on the host and never launches the by-value kernel with them.
+    if (A.m == kMinRows) {
+        const int32_t s[7] = { 0, 1, 2, 3, 4, 5, 6 };
+        double Fh[3][9];
+        const int n = solve_sample(pol, c, s, Fh);
+        const int32_t counts[3] = { 0, 0, 0 };
+        pol.record(h, s, n, Fh, counts);
+        if (pol.lane == 0) *A.key = n > 0 ? winner_key(kMinRows, 0, 0) : 0ull;
+        return;
+    }
     hypothesis(pol, c, h);
+}
+
+__global__ __launch_bounds__(FD_T) void k_fund_ransac(RansacArgs A) { fund_ransac_body(A); }
+
+// Member blockIdx.z of a tracker call: m comes from device memory.  Fewer than seven rows: nothing runs.  Seven: hypothesis 0 alone.
+__global__ __launch_bounds__(FD_T) void k_fund_ransac_g(const CullRec* __restrict__ recs, CullShape S) {
+    const CullRec* r = recs + blockIdx.z;
+    if (r->skip) return;
+    const int32_t m = min(*r->m, kMaxPoints);
+    if (m < kMinRows) return;
+    RansacArgs A;                              // the record's fields once, into scalars, in front of the body
+    Header* const head = r->head;
+    A.head = head; A.rows = r->rows; A.m = m; A.iterations = m == kMinRows ? 1 : S.iterations; A.seed = S.seed; A.thr2 = S.thr2;
+    A.samples = r->samples; A.nc = r->nc; A.models = r->models; A.key = &head->key;
+    if ((int)blockIdx.x * (FD_T / 64) >= A.iterations) return;
+    fund_ransac_body(A);
 }
 
 struct MaskArgs {
@@ -121,6 +154,39 @@ __global__ __launch_bounds__(FD_T) void k_fund_mask(MaskArgs A) {
         A.status[i] = (in && A.status_in[i] != 0) ? 1 : 0;
     }
     if (i == 0) *A.res = res;
+}
+
+// The winner's mask of member blockIdx.z over the rows that entered, scattered to their from-rows, and the status after the AND
+// (the rows kernel has written both for the rows that did not enter).
+__global__ __launch_bounds__(FD_T) void k_fund_mask_g(const CullRec* __restrict__ recs, CullShape S) {
+    const CullRec& r = recs[blockIdx.z];
+    if (r.skip) return;
+    const int32_t m = min(*r.m, kMaxPoints);
+    if (m < kMinRows) return;
+    const int k = blockIdx.x * FD_T + threadIdx.x;
+    if (k >= m) return;
+    Call c;
+    c.T1 = r.head->T1; c.T2 = r.head->T2; c.m = m; c.iterations = 0; c.seed = 0; c.thr2 = S.thr2;
+    const unsigned long long key = r.head->key;
+    Result res = winner_of(key, r.models, c);
+    const bool seven = m == kMinRows;
+    if (seven) res.count = kMinRows;
+    const bool in = seven || (key != 0 && inlier(res.F, r.rows[k], S.thr2));
+    const int32_t i = r.keep[k];
+    r.mask[i] = in ? 1 : 0;
+    r.status[i] = (in && r.st[k] != 0) ? 1 : 0;
+    if (k == 0) *r.res = res;
+}
+
+int group_cull(hipStream_t stream, int n, const CullRec* d_recs, int32_t max_rows, const CullShape& S, flow::GroupCounts* cnt) {
+    hipLaunchKernelGGL(k_fund_ransac_g, dim3((unsigned)((S.iterations + FD_T / 64 - 1) / (FD_T / 64)), 1, (unsigned)n), dim3(FD_T), 0, stream,
+                       d_recs, S);
+    if (hipGetLastError() != hipSuccess) return VISFS_BA_ERR_DEVICE;
+    ++cnt->kernels;
+    hipLaunchKernelGGL(k_fund_mask_g, dim3((unsigned)((max_rows + FD_T - 1) / FD_T), 1, (unsigned)n), dim3(FD_T), 0, stream, d_recs, S);
+    if (hipGetLastError() != hipSuccess) return VISFS_BA_ERR_DEVICE;
+    ++cnt->kernels;
+    return VISFS_BA_OK;
 }
 
 }  // namespace fund
@@ -202,26 +268,9 @@ void release(visfs_fund* p) {
     p->d_in = p->d_out = p->d_state = p->h_in = p->h_out = nullptr;
 }
 
-// The Hartley transform of one image (section 9f step 2): serial double sums in kept-row order.
-Hartley hartley(const std::vector<Row>& rows, bool to) {
-    const double m = (double)rows.size();
-    double sx = 0.0, sy = 0.0;
-    for (const Row& r : rows) { sx += (double)(to ? r.x2 : r.x1); sy += (double)(to ? r.y2 : r.y1); }
-    Hartley T;
-    T.cx = sx / m; T.cy = sy / m;
-    double sd = 0.0;
-    for (const Row& r : rows) {
-        const double dx = (double)(to ? r.x2 : r.x1) - T.cx, dy = (double)(to ? r.y2 : r.y1) - T.cy;
-        sd += std::sqrt(dx * dx + dy * dy);
-    }
-    const double mean = sd / m;
-    T.s = mean > 0.0 ? 1.4142135623730951 / mean : 1.0;
-    return T;
-}
-
 // The host twin's side of fund::hypothesis: the same functions over the rows in sequence.
 struct HostPolicy {
-    visfs_fund* p;
+    int32_t* samples; int32_t* nc; double* models;     // per hypothesis
     const Row* rows;
     int32_t m;
     float thr2;
@@ -234,11 +283,11 @@ struct HostPolicy {
             for (int i = 0; i < m; ++i) counts[k] += inlier(F[k], rows[i], thr2) ? 1 : 0;
     }
     void record(int32_t h, const int32_t s[7], int n, const double Fh[3][9], const int32_t counts[3]) {
-        for (int k = 0; k < 7; ++k) p->samples[7 * (size_t)h + k] = s[k];
-        p->nc[4 * (size_t)h] = n;
+        for (int k = 0; k < 7; ++k) samples[7 * (size_t)h + k] = s[k];
+        nc[4 * (size_t)h] = n;
         for (int k = 0; k < 3; ++k) {
-            p->nc[4 * (size_t)h + 1 + k] = counts[k];
-            for (int i = 0; i < 9; ++i) p->models[27 * (size_t)h + 9 * k + i] = Fh[k][i];
+            nc[4 * (size_t)h + 1 + k] = counts[k];
+            for (int i = 0; i < 9; ++i) models[27 * (size_t)h + 9 * k + i] = Fh[k][i];
             if (k < n && counts[k] >= kMinRows) key = std::max(key, winner_key(counts[k], h, k));
         }
     }
@@ -250,29 +299,40 @@ void host_state(visfs_fund* p, int H) {
 }
 
 // m == 7 (both flavours): the models of the rows 0 .. 6, recorded as the one hypothesis of the call; every kept row is an inlier.
-void seven_rows(visfs_fund* p, const Call& c) {
-    host_state(p, 1);
-    HostPolicy pol{ p, p->rows.data(), c.m, c.thr2 };
+// mask and status are per row that entered.
+Result seven_rows_core(HostPolicy pol, const Call& c, const uint8_t* st, uint8_t* mask, uint8_t* status) {
     const int32_t s[7] = { 0, 1, 2, 3, 4, 5, 6 };
     double Fh[3][9];
     const int n = solve_sample(pol, c, s, Fh);
     const int32_t counts[3] = { 0, 0, 0 };
     pol.record(0, s, n, Fh, counts);
-    p->res = winner_of(n > 0 ? winner_key(kMinRows, 0, 0) : 0ull, p->models.data(), c);
-    p->res.count = kMinRows;
-    for (int i = 0; i < c.m; ++i) { p->mask_k[i] = 1; p->status_k[i] = p->st[i] ? 1 : 0; }
+    Result res = winner_of(n > 0 ? winner_key(kMinRows, 0, 0) : 0ull, pol.models, c);
+    res.count = kMinRows;
+    for (int i = 0; i < c.m; ++i) { mask[i] = 1; status[i] = st[i] ? 1 : 0; }
+    return res;
+}
+
+Result host_cull_core(HostPolicy pol, const Call& c, const uint8_t* st, uint8_t* mask, uint8_t* status) {
+    for (int h = 0; h < c.iterations; ++h) hypothesis(pol, c, h);
+    const Result res = winner_of(pol.key, pol.models, c);
+    for (int i = 0; i < c.m; ++i) {
+        const bool in = pol.key != 0 && inlier(res.F, pol.rows[i], c.thr2);
+        mask[i] = in ? 1 : 0;
+        status[i] = (in && st[i] != 0) ? 1 : 0;
+    }
+    return res;
+}
+
+void seven_rows(visfs_fund* p, const Call& c) {
+    host_state(p, 1);
+    p->res = seven_rows_core(HostPolicy{ p->samples.data(), p->nc.data(), p->models.data(), p->rows.data(), c.m, c.thr2 }, c, p->st.data(),
+                             p->mask_k.data(), p->status_k.data());
 }
 
 void host_cull(visfs_fund* p, const Call& c) {
     host_state(p, c.iterations);
-    HostPolicy pol{ p, p->rows.data(), c.m, c.thr2 };
-    for (int h = 0; h < c.iterations; ++h) hypothesis(pol, c, h);
-    p->res = winner_of(pol.key, p->models.data(), c);
-    for (int i = 0; i < c.m; ++i) {
-        const bool in = pol.key != 0 && inlier(p->res.F, p->rows[i], c.thr2);
-        p->mask_k[i] = in ? 1 : 0;
-        p->status_k[i] = (in && p->st[i] != 0) ? 1 : 0;
-    }
+    p->res = host_cull_core(HostPolicy{ p->samples.data(), p->nc.data(), p->models.data(), p->rows.data(), c.m, c.thr2 }, c, p->st.data(),
+                            p->mask_k.data(), p->status_k.data());
 }
 
 int device_cull(visfs_fund* p, const Call& c) {
@@ -306,11 +366,34 @@ int device_cull(visfs_fund* p, const Call& c) {
     return VISFS_BA_OK;
 }
 
-void hartley_matrix(const Hartley& T, double* o) {
-    o[0] = T.s; o[1] = 0.0; o[2] = -(T.s * T.cx); o[3] = 0.0; o[4] = T.s; o[5] = -(T.s * T.cy); o[6] = 0.0; o[7] = 0.0; o[8] = 1.0;
-}
-
 }  // namespace
+
+// The cull of a host-twin tracker on its from-rows: the steps of visfs_fund_cull in sequence, into the arrays of `r`.
+void fund::cull_host(const CullRec& r, const float* from_xy, const float* to_xy, const uint8_t* lk_st, int32_t n_from, const CullShape& S) {
+    int32_t m = 0;
+    for (int32_t i = 0; i < n_from; ++i) {
+        const float* a = from_xy + 2 * (size_t)i;
+        const float* b = to_xy + 2 * (size_t)i;
+        if (!(std::isfinite(a[0]) && std::isfinite(a[1]) && std::isfinite(b[0]) && std::isfinite(b[1]))) continue;
+        r.rows[m] = Row{ a[0], a[1], b[0], b[1] };
+        r.keep[m] = i;
+        r.st[m] = lk_st[i] ? 1 : 0;
+        ++m;
+    }
+    *r.m = m;
+    for (int32_t i = 0; i < n_from; ++i) { r.mask[i] = 0; r.status[i] = (m < kMinRows && lk_st[i]) ? 1 : 0; }
+    if (m < kMinRows) return;
+    Call c;
+    std::vector<double> term((size_t)m);
+    c.T1 = hartley(r.rows, m, false, term.data()); c.T2 = hartley(r.rows, m, true, term.data());
+    c.m = m; c.iterations = S.iterations; c.seed = S.seed; c.thr2 = S.thr2;
+    *r.head = Header{ 0ull, 0ull, c.T1, c.T2 };
+    std::vector<uint8_t> mask_k((size_t)m), status_k((size_t)m);
+    const HostPolicy pol{ r.samples, r.nc, r.models, r.rows, m, c.thr2 };
+    *r.res = m == kMinRows ? seven_rows_core(pol, c, r.st, mask_k.data(), status_k.data())
+                           : host_cull_core(pol, c, r.st, mask_k.data(), status_k.data());
+    for (int32_t k = 0; k < m; ++k) { r.mask[r.keep[k]] = mask_k[(size_t)k]; r.status[r.keep[k]] = status_k[(size_t)k]; }
+}
 
 // ====================================================================== exported C ABI
 extern "C" {
@@ -395,10 +478,10 @@ int visfs_fund_cull(visfs_fund* p, const visfs_fund_params* params, int32_t n, c
         }
         // step 2: the conditioning
         Call c;
-        c.T1 = hartley(p->rows, false); c.T2 = hartley(p->rows, true);
+        std::vector<double> term((size_t)m);
+        c.T1 = hartley(p->rows.data(), m, false, term.data()); c.T2 = hartley(p->rows.data(), m, true, term.data());
         c.m = m; c.iterations = params->iterations; c.seed = params->seed;
-        const float thr = params->pixel_error > 0.0f ? params->pixel_error : 3.0f;
-        c.thr2 = (float)((double)thr * (double)thr);
+        c.thr2 = cull_thr2(params->pixel_error);
         p->T1 = c.T1; p->T2 = c.T2; p->have_T = true;
         p->mask_k.assign((size_t)m, 0); p->status_k.assign((size_t)m, 0);
         if (m == kMinRows) {

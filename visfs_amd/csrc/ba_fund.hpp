@@ -72,6 +72,38 @@ BA_HD void denormalise(const double Fh[9], const Hartley& T1, const Hartley& T2,
     }
 }
 
+// The Hartley transform of one image (section 9f step 2) in pieces that the host and the rows kernel of the resident tracker
+// (section 9j) share: every sum is one serial chain of rounded double additions in row order, so where a chain runs changes no bit.
+// The terms of a chain do not depend on it and may be made by anybody.
+template <class T>
+BA_HD double serial_sum(const T* v, int m, int stride) {
+    double s = 0.0;
+#pragma unroll 8
+    for (int i = 0; i < m; ++i) s += (double)v[(size_t)i * stride];
+    return s;
+}
+BA_HD double centre_distance(double x, double y, double cx, double cy) {
+    const double dx = x - cx, dy = y - cy;
+    return sqrt(dx * dx + dy * dy);
+}
+BA_HD Hartley hartley_of(double cx, double cy, double sd, double m) {
+    Hartley T;
+    T.cx = cx; T.cy = cy;
+    const double mean = sd / m;
+    T.s = mean > 0.0 ? 1.4142135623730951 / mean : 1.0;
+    return T;
+}
+// one image of m rows (to: the second); term[m]: room for the distances
+BA_HD Hartley hartley(const Row* rows, int m, bool to, double* term) {
+    const float *x = to ? &rows->x2 : &rows->x1, *y = to ? &rows->y2 : &rows->y1;
+    const double cx = serial_sum(x, m, 4) / (double)m, cy = serial_sum(y, m, 4) / (double)m;
+    for (int i = 0; i < m; ++i) term[i] = centre_distance((double)x[4 * (size_t)i], (double)y[4 * (size_t)i], cx, cy);
+    return hartley_of(cx, cy, serial_sum(term, m, 1), (double)m);
+}
+BA_HD void hartley_matrix(const Hartley& T, double* o) {
+    o[0] = T.s; o[1] = 0.0; o[2] = -(T.s * T.cx); o[3] = 0.0; o[4] = T.s; o[5] = -(T.s * T.cy); o[6] = 0.0; o[7] = 0.0; o[8] = 1.0;
+}
+
 // ---- step 5: FMEstimatorCallback::computeError; the row is an inlier iff both halves, narrowed to float, are within thr2 ----------
 BA_HD bool inlier(const double F[9], const Row& r, float thr2) {
     const double x1 = (double)r.x1, y1 = (double)r.y1, x2 = (double)r.x2, y2 = (double)r.y2;
@@ -320,5 +352,28 @@ BA_HD Result winner_of(unsigned long long key, const double* models, const Call&
     denormalise(Fh, c.T1, c.T2, res.F);
     return res;
 }
+
+// ---- the cull inside the resident tracker (include/visfs_tracker.h, section 9j) ------------------------------------------------------
+// Where the cull of one tracker works, in device memory or, for the host twin, in host memory.  The rows kernel of ba_tracker.hip fills
+// m, head, rows, keep, st and the pass-through of mask and status; the search and the mask of ba_fund.hip read a table of these at
+// member blockIdx.z.
+struct CullRec {
+    int32_t* m;                                // rows that entered
+    Header* head;                              // the winner key and the two transforms
+    Row* rows; int32_t* keep; uint8_t* st;     // [m]: the rows that entered, their from-row numbers, their Lucas-Kanade status
+    int32_t* samples; int32_t* nc; double* models;     // per hypothesis, as RansacArgs has them
+    Result* res;
+    uint8_t* mask; uint8_t* status;            // per from-row: the winner's mask, the status after the AND
+    int32_t skip, pad;                         // the member takes no part in this call
+};
+
+// what every member of a call shares
+struct CullShape { int32_t iterations; float thr2; uint64_t seed; };
+
+BA_HD float cull_thr2(float pixel_error) {
+    const float thr = pixel_error > 0.0f ? pixel_error : 3.0f;
+    return (float)((double)thr * (double)thr);
+}
+
 
 }  // namespace fund

@@ -55,3 +55,15 @@ void group_corners_fill(visfs_flow* f, const uint8_t* px, const Disc* d_discs, c
 int group_corners(visfs_flow* f, double quality_level, double min_distance, int n, const CornerRec* d_recs, GroupCounts* cnt);
 
 }  // namespace flow
+
+namespace fund {
+
+struct CullRec;                                // ba_fund.hpp
+struct CullShape;
+// The search and the winner's mask of the fundamental-matrix cull for the n members of a tracker call (ba_fund.hip, DESIGN.md section
+// 9j): two launches with grid.z = n behind the rows kernel of ba_tracker.hip.  max_rows: the most rows any member can have.
+int group_cull(hipStream_t stream, int n, const CullRec* d_recs, int32_t max_rows, const CullShape& S, flow::GroupCounts* cnt);
+// The same steps for a host-twin tracker, the rows and the conditioning included.
+void cull_host(const CullRec& r, const float* from_xy, const float* to_xy, const uint8_t* lk_st, int32_t n_from, const CullShape& S);
+
+}  // namespace fund

@@ -14,6 +14,10 @@
 //       [bootstrap]     the corner kernels on the previous left image without a mask, k_trk_append_g, k_trk_stereo_g in its
 //                       forward-only, ungated, status-blind form for the 3-D points                                 (:179-230)
 //       k_trk_track_g   one wavefront per from-row: guess projection in fp64, lk_gated, the bounds test          (:237-274, :286)
+//       [cull]          Tracker/CullByFundationMatrix with flow_back off: k_trk_cull_rows_g, one workgroup:
+//                       the from-rows with four finite coordinates compacted in row order, the two Hartley transforms with the
+//                       serial sums of fund::hartley, the winner key zeroed; then k_fund_ransac_g and k_fund_mask_g of ba_fund.hip
+//                       (fund::group_cull), which leave the status after the AND for the reduce to keep its rows on    (:275-277, :83-96)
 //       k_trk_reduce_g  one workgroup: compaction of the kept rows in row order: covisible output, kept count, LOST, the top-up's
 //                       corner budget                                                                               (:280-320)
 //       k_trk_discs_g   one workgroup: rank sort of the (count, row) keys, the serial draw decision of getMask 1024 discs at a time
@@ -30,6 +34,7 @@
 #include "ba_tracker.hpp"
 #include "ba_flow_object.hpp"
 #include "ba_group.hpp"
+#include "ba_fund.hpp"
 #include "../../include/visfs_tracker.h"
 #include "../../include/visfs_tracker_group.h"
 
@@ -61,6 +66,7 @@ struct Ctl {                                   // device words of a tracker
     int32_t corner_args[2];                    // the top-up: { raster discs, max_features - kept }
     int32_t boot_args[2];                      // the bootstrap: { 0, max_features }
     uint64_t next_id;                          // globalFeatureId_ (lives across calls)
+    int32_t cull_m, pad;                       // from-rows that entered the fundamental-matrix cull
 };
 
 struct Head {                                  // first words of the output block
@@ -87,6 +93,8 @@ struct Bufs {
     uint64_t* from_id; float* from_xy; float* from_xyz; int32_t* from_cnt;        // the from-rows of a call
     float* blk_xy;
     float* guess; float* to; uint8_t* lk_st; uint8_t* inb;                        // per from-row
+    const uint8_t* keep_st;                                                       // the status the reduce keeps a row on: lk_st, or the cull's
+    fund::CullRec cull;                                                           // all NULL without the cull
     uint64_t* row_id; float* row_xy; int32_t* row_cnt;                            // kept + new rows
     float* row_rxy; float* row_xyz; uint8_t* row_st; uint8_t* row_ok;
     visfs_corners_disc* list; uint32_t* packed; uint8_t* drawn; Disc* raster;     // getMask's discs in draw order; the raster's
@@ -116,7 +124,8 @@ size_t carve_out(char* base, size_t M, Out& o) {
     return (c.off + 255) & ~size_t(255);
 }
 
-size_t carve_work(char* base, size_t M, size_t hw_len, Bufs& b, int32_t** hw) {
+// cull_iters: the hypotheses of the fundamental-matrix cull, 0 without it
+size_t carve_work(char* base, size_t M, size_t hw_len, size_t cull_iters, Bufs& b, int32_t** hw) {
     Carver c{ base };
     b.ctl = c.take<Ctl>(1);
     b.tab_id = c.take<uint64_t>(M); b.tab_xy = c.take<float>(2 * M); b.tab_xyz = c.take<float>(3 * M); b.tab_cnt = c.take<int32_t>(M);
@@ -129,6 +138,17 @@ size_t carve_work(char* base, size_t M, size_t hw_len, Bufs& b, int32_t** hw) {
     b.raster = c.take<Disc>(2 * M);
     *hw = c.take<int32_t>(hw_len);
     b.hw = *hw;
+    b.keep_st = b.lk_st;
+    b.cull = fund::CullRec{};
+    if (cull_iters > 0) {
+        fund::CullRec& q = b.cull;
+        q.m = base ? &b.ctl->cull_m : nullptr;
+        q.head = c.take<fund::Header>(1); q.res = c.take<fund::Result>(1);
+        q.rows = c.take<fund::Row>(M); q.keep = c.take<int32_t>(M); q.st = c.take<uint8_t>(M);
+        q.samples = c.take<int32_t>(7 * cull_iters); q.nc = c.take<int32_t>(4 * cull_iters); q.models = c.take<double>(27 * cull_iters);
+        q.mask = c.take<uint8_t>(M); q.status = c.take<uint8_t>(M);
+        b.keep_st = q.status;
+    }
     return (c.off + 255) & ~size_t(255);
 }
 
@@ -212,6 +232,7 @@ __global__ __launch_bounds__(TK_T) void k_trk_pretreat_g(const TrkRec* __restric
         c->n_kept = 0; c->lost = 0; c->n_list = 0; c->n_new = 0; c->n_rows = 0;
         c->corner_args[0] = 0; c->corner_args[1] = 0;
         c->boot_args[0] = 0; c->boot_args[1] = S.M;
+        c->cull_m = 0;
     }
 }
 
@@ -289,6 +310,79 @@ __global__ __launch_bounds__(64) void k_trk_track_g(const TrkRec* __restrict__ r
     B.inb[p] = (in_bounds(tox, S.w) && in_bounds(toy, S.h)) ? 1 : 0;
 }
 
+// The first two steps of the fundamental-matrix cull, which the staged visfs_fund_cull does on the host: the from-rows whose four
+// coordinates are finite, whatever their status, compacted in row order, and the two Hartley transforms.  The terms of the sums are
+// made by all lanes into LDS; the additions are the serial chains of fund::hartley (four for the means, then two for the
+// distances, each on the first lane of a wavefront of its own), so the bytes are those of the host conditioning.  Rows that do not
+// enter get mask 0 and status 0 here; with fewer than seven rows the status passes through and nothing else of the cull runs.
+static_assert(kMaxFeatures <= fund::kMaxPoints && fund::kMaxPoints == 4 * TK_T, "a thread of the rows kernel owns up to four rows");
+__global__ __launch_bounds__(TK_T) void k_trk_cull_rows_g(const TrkRec* __restrict__ recs, Shape S) {
+    const TrkRec& r = recs[blockIdx.z];
+    if (r.skip) return;
+    const Bufs& B = r.B;
+    const fund::CullRec& C = B.cull;
+    __shared__ fund::Row s_rows[fund::kMaxPoints];     // the rows that entered; then the distance terms, double [2][kMaxPoints]
+    __shared__ int32_t wcount[TK_WAVES];
+    __shared__ double s_sum[6];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = min(B.ctl->n_from, S.M);
+    if (n <= 0) {
+        if (tid == 0) *C.m = 0;
+        return;
+    }
+    int m = 0;
+    for (int c0 = 0; c0 < n; c0 += TK_T) {
+        const int i = c0 + tid;
+        const bool valid = i < n;
+        fund::Row q{ 0.0f, 0.0f, 0.0f, 0.0f };
+        if (valid) q = fund::Row{ B.from_xy[2 * i], B.from_xy[2 * i + 1], B.to[2 * i], B.to[2 * i + 1] };
+        const bool enters = valid && isfinite(q.x1) && isfinite(q.y1) && isfinite(q.x2) && isfinite(q.y2);
+        int total;
+        const int o = m + wg_offset(enters, wcount, total);
+        if (enters) {
+            s_rows[o] = q;
+            C.rows[o] = q; C.keep[o] = i; C.st[o] = B.lk_st[i] ? 1 : 0;
+        }
+        m += total;
+    }
+    const bool passes = m < fund::kMinRows;
+    for (int i = tid; i < n; i += TK_T) { C.mask[i] = 0; C.status[i] = (passes && B.lk_st[i]) ? 1 : 0; }
+    if (tid == 0) *C.m = m;
+    if (passes) return;
+    __syncthreads();
+    if (lane == 0 && wave < 4) s_sum[wave] = fund::serial_sum(&s_rows[0].x1 + wave, m, 4);      // x1, y1, x2, y2
+    __syncthreads();
+    const double dm = (double)m;
+    const double cx1 = s_sum[0] / dm, cy1 = s_sum[1] / dm, cx2 = s_sum[2] / dm, cy2 = s_sum[3] / dm;
+    double d1[4], d2[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int i = tid + k * TK_T;
+        d1[k] = d2[k] = 0.0;
+        if (i < m) {
+            const fund::Row q = s_rows[i];
+            d1[k] = fund::centre_distance((double)q.x1, (double)q.y1, cx1, cy1);
+            d2[k] = fund::centre_distance((double)q.x2, (double)q.y2, cx2, cy2);
+        }
+    }
+    __syncthreads();
+    double* s_term = reinterpret_cast<double*>(s_rows);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int i = tid + k * TK_T;
+        if (i < m) { s_term[i] = d1[k]; s_term[fund::kMaxPoints + i] = d2[k]; }
+    }
+    __syncthreads();
+    if (lane == 0 && wave < 2) s_sum[4 + wave] = fund::serial_sum(s_term + wave * fund::kMaxPoints, m, 1);
+    __syncthreads();
+    if (tid == 0) {
+        fund::Header hd;
+        hd.key = 0; hd.pad = 0;                                                   // no winner yet
+        hd.T1 = fund::hartley_of(cx1, cy1, s_sum[4], dm); hd.T2 = fund::hartley_of(cx2, cy2, s_sum[5], dm);
+        *C.head = hd;
+    }
+}
+
 __global__ __launch_bounds__(TK_T) void k_trk_reduce_g(const TrkRec* __restrict__ recs, Shape S) {
     const TrkRec& r = recs[blockIdx.z];
     if (r.skip) return;
@@ -299,7 +393,7 @@ __global__ __launch_bounds__(TK_T) void k_trk_reduce_g(const TrkRec* __restrict_
     int kept = 0;
     for (int c0 = 0; c0 < n; c0 += TK_T) {
         const int i = c0 + tid;
-        const bool keep = i < n && kept_row(B.lk_st[i], B.to[2 * i], B.to[2 * i + 1], S.w, S.h);
+        const bool keep = i < n && kept_row(B.keep_st[i], B.to[2 * i], B.to[2 * i + 1], S.w, S.h);
         int total;
         const int o = kept + wg_offset(keep, wcount, total);
         if (keep) {
@@ -536,10 +630,11 @@ __global__ __launch_bounds__(TK_T) void k_trk_finish_g(const TrkRec* __restrict_
 
 // ---------------------------------------------------------------- the objects
 // The tables of a call for n members stand in one block, pinned and on the device, and go up in one copy:
-// [PyrRec n][ClaheRec n][CornerRec n: bootstrap][CornerRec n: top-up][TrkRec n][InHead n][outlier ids of the members, one behind the other]
+// [PyrRec n][ClaheRec n][CornerRec n: bootstrap][CornerRec n: top-up][TrkRec n][CullRec n][InHead n][outlier ids of the members, one
+// behind the other]
 struct CallBlock {
     char* pinned = nullptr; char* dev = nullptr;
-    size_t off_pyr = 0, off_clahe = 0, off_boot = 0, off_top = 0, off_trk = 0, off_in = 0, off_ids = 0, bytes = 0;
+    size_t off_pyr = 0, off_clahe = 0, off_boot = 0, off_top = 0, off_trk = 0, off_cull = 0, off_in = 0, off_ids = 0, bytes = 0;
 
     hipError_t allocate(size_t n) {            // the caller has selected the device
         size_t off = 0;
@@ -549,6 +644,7 @@ struct CallBlock {
         off_boot = take(n * sizeof(CornerRec));
         off_top = take(n * sizeof(CornerRec));
         off_trk = take(n * sizeof(TrkRec));
+        off_cull = take(n * sizeof(fund::CullRec));
         off_in = take(n * sizeof(InHead));
         off_ids = take(n * sizeof(uint64_t) * kMaxOutliers);
         bytes = off;
@@ -569,6 +665,8 @@ struct visfs_tracker {
     visfs_tracker_params prm{};
     visfs_flow_camera cam{};
     Shape S{};
+    bool cull_on = false;                      // cull set and the flow object's flow_back off (Tracker.cpp:275)
+    fund::CullShape cull{};
     std::string err;
     int seen_frames = 0;                       // f->frames after this tracker's last push
     bool have_call = false;                    // the download hook has something to report
@@ -641,12 +739,13 @@ int allocate(visfs_tracker* t) {
     const size_t M = (size_t)t->S.M;
     Bufs& B = t->B;
     int32_t* hw = nullptr;
-    const size_t work_bytes = carve_work(nullptr, M, t->hw.size(), B, &hw);
+    const size_t H = t->cull_on ? (size_t)t->cull.iterations : 0;
+    const size_t work_bytes = carve_work(nullptr, M, t->hw.size(), H, B, &hw);
     t->out_bytes = carve_out(nullptr, M, B.o);
     if (!f->device) {
         t->h_work.assign(work_bytes, 0); t->h_outblk.assign(t->out_bytes, 0);
         t->h_inblk.assign(sizeof(InHead) + sizeof(uint64_t) * kMaxOutliers, 0);
-        carve_work(t->h_work.data(), M, t->hw.size(), B, &hw);
+        carve_work(t->h_work.data(), M, t->hw.size(), H, B, &hw);
         carve_out(t->h_outblk.data(), M, B.o);
         std::memcpy(hw, t->hw.data(), t->hw.size() * sizeof(int32_t));
         B.in = reinterpret_cast<const InHead*>(t->h_inblk.data());
@@ -659,7 +758,7 @@ int allocate(visfs_tracker* t) {
     TK_HIP(t, hipMalloc(reinterpret_cast<void**>(&t->d_out), t->out_bytes));
     TK_HIP(t, hipHostMalloc(reinterpret_cast<void**>(&t->p_out), t->out_bytes, hipHostMallocDefault));
     TK_HIP(t, t->blk.allocate(1));
-    carve_work(t->d_work, M, t->hw.size(), B, &hw);
+    carve_work(t->d_work, M, t->hw.size(), H, B, &hw);
     carve_out(t->d_out, M, B.o);
     carve_out(t->p_out, M, t->R);              // (B.in and B.outliers of a call point into the block the call goes through)
     std::memset(t->p_out, 0, t->out_bytes);
@@ -679,6 +778,11 @@ int check_params(const visfs_tracker_params* p, const visfs_flow_camera* cam, co
     if (p->min_inliers < 0) { *why = "min_inliers must not be negative"; return VISFS_BA_ERR_BAD_ARGUMENT; }
     for (int i = 0; i < 12; ++i)
         if (!std::isfinite(cam->Tir[i])) { *why = "Tir is not finite"; return VISFS_BA_ERR_BAD_ARGUMENT; }
+    if (p->cull) {
+        if (!std::isfinite(p->cull_params.pixel_error)) { *why = "cull_params.pixel_error is not finite"; return VISFS_BA_ERR_BAD_ARGUMENT; }
+        if (p->cull_params.iterations < 1) { *why = "cull_params.iterations must be at least 1"; return VISFS_BA_ERR_BAD_ARGUMENT; }
+        if (p->cull_params.iterations > fund::kMaxHypotheses) { *why = "cull_params.iterations above 4096"; return VISFS_BA_ERR_UNSUPPORTED; }
+    }
     return VISFS_BA_OK;
 }
 
@@ -703,6 +807,7 @@ void host_pretreat(visfs_tracker* t) {
     c->n_from = nk; c->n_blocked = nb;
     c->n_kept = 0; c->lost = 0; c->n_list = 0; c->n_new = 0; c->n_rows = 0;
     c->corner_args[0] = c->corner_args[1] = 0;
+    c->cull_m = 0;
 }
 
 Image host_image(const visfs_flow* f, int slot, int image) { return Image{ f->hpx[slot][image].data(), f->hder[slot][image].data() }; }
@@ -740,7 +845,6 @@ void host_track_reduce(visfs_tracker* t, const Guess* g) {
     const Shape& S = t->S;
     const Image I = host_image(f, 1 - f->cur, 0), J = host_image(f, f->cur, 0);
     const HostCells pol;
-    int kept = 0;
     for (int p = 0; p < c->n_from; ++p) {
         const float ptx = B.from_xy[2 * p], pty = B.from_xy[2 * p + 1];
         float inx = ptx, iny = pty;
@@ -752,7 +856,12 @@ void host_track_reduce(visfs_tracker* t, const Guess* g) {
         B.to[2 * p] = tx; B.to[2 * p + 1] = ty;
         B.lk_st[p] = st;
         B.inb[p] = (in_bounds(tx, S.w) && in_bounds(ty, S.h)) ? 1 : 0;
-        if (!kept_row(st, tx, ty, S.w, S.h)) continue;
+    }
+    if (t->cull_on) fund::cull_host(B.cull, B.from_xy, B.to, B.lk_st, c->n_from, t->cull);     // Tracker.cpp:275-277
+    int kept = 0;
+    for (int p = 0; p < c->n_from; ++p) {
+        const float tx = B.to[2 * p], ty = B.to[2 * p + 1];
+        if (!kept_row(B.keep_st[p], tx, ty, S.w, S.h)) continue;
         const int o = kept++;
         B.o.cov_id[o] = B.from_id[p];
         for (int k = 0; k < 2; ++k) B.o.cov_from[2 * o + k] = B.from_xy[2 * p + k];
@@ -963,7 +1072,7 @@ int run_call(visfs_tracker* const* m, int n, const visfs_tracker_frame* fr, cons
     visfs_tracker* t0 = m[0];
     visfs_flow* f0 = t0->f;
     const Shape S = t0->S;
-    const bool clahe_on = t0->prm.clahe != 0, back = f0->prm.flow_back != 0;
+    const bool clahe_on = t0->prm.clahe != 0, back = f0->prm.flow_back != 0, cull_on = t0->cull_on;
     const clahe::Geom geom = clahe_on ? clahe::make_geom(f0->w, f0->h, t0->prm.clahe_params.tiles_x, t0->prm.clahe_params.tiles_y,
                                                          t0->prm.clahe_params.clip_limit)
                                       : clahe::Geom{};
@@ -977,6 +1086,7 @@ int run_call(visfs_tracker* const* m, int n, const visfs_tracker_frame* fr, cons
     CornerRec* cboot = reinterpret_cast<CornerRec*>(blk.pinned + blk.off_boot);
     CornerRec* ctop = reinterpret_cast<CornerRec*>(blk.pinned + blk.off_top);
     TrkRec* trk = reinterpret_cast<TrkRec*>(blk.pinned + blk.off_trk);
+    fund::CullRec* cull = reinterpret_cast<fund::CullRec*>(blk.pinned + blk.off_cull);
     InHead* inh = reinterpret_cast<InHead*>(blk.pinned + blk.off_in);
     uint64_t* ids = reinterpret_cast<uint64_t*>(blk.pinned + blk.off_ids);
     size_t n_ids = 0;
@@ -1012,6 +1122,8 @@ int run_call(visfs_tracker* const* m, int n, const visfs_tracker_frame* fr, cons
         r.cam = make_camera(f->prm, t->cam);
         r.g = P.g;
         r.has_guess = P.has_guess ? 1 : 0; r.skip = skip ? 1 : 0; r.boot = P.boot ? 1 : 0; r.pad = 0;
+        cull[i] = t->B.cull;
+        cull[i].skip = skip ? 1 : 0;
         // both extractions of a member work in the same state, one behind the other in stream order
         group_corners_fill(f, f->dpx[prev][0], nullptr, nullptr, t->B.ctl->boot_args, skip || !P.boot, &cboot[i], &r.corner_n, &r.corner_xy);
         group_corners_fill(f, f->dpx[cur][0], t->B.raster, t->B.hw, t->B.ctl->corner_args, skip, &ctop[i], &r.corner_n, &r.corner_xy);
@@ -1054,6 +1166,11 @@ int run_call(visfs_tracker* const* m, int n, const visfs_tracker_frame* fr, cons
             const dim3 grid((unsigned)bound, 1, z);
             if (back) RC_LAUNCH((k_trk_track_g<true>), grid, wave, d_trk, S, f0->lk, f0->lay, f0->prm.back_gate_track);
             else RC_LAUNCH((k_trk_track_g<false>), grid, wave, d_trk, S, f0->lk, f0->lay, f0->prm.back_gate_track);
+        }
+        if (cull_on) {                                                 // Tracker.cpp:275-277: between the forward pass and the reduce
+            RC_LAUNCH(k_trk_cull_rows_g, one, wg, d_trk, S);
+            rc = fund::group_cull(stream, n, reinterpret_cast<const fund::CullRec*>(dev(blk.off_cull)), S.M, t0->cull, &cnt);
+            if (rc != VISFS_BA_OK) return blame(rc, -1, "a launch of the fundamental-matrix cull failed");
         }
         RC_LAUNCH(k_trk_reduce_g, one, wg, d_trk, S);
         RC_LAUNCH(k_trk_discs_g, one, wg, d_trk, S);
@@ -1109,6 +1226,8 @@ void visfs_tracker_default_params(visfs_tracker_params* p) {
     if (!p) return;
     p->max_features = 300; p->quality_level = 0.01; p->min_distance = 40; p->min_inliers = 10; p->clahe = 0;
     visfs_clahe_default_params(&p->clahe_params);
+    p->cull = 0;
+    visfs_fund_default_params(&p->cull_params);
 }
 
 int visfs_tracker_create(visfs_flow* f, const visfs_tracker_params* p, const visfs_flow_camera* cam, visfs_tracker** out) {
@@ -1131,6 +1250,9 @@ int visfs_tracker_create(visfs_flow* f, const visfs_tracker_params* p, const vis
         disc_halfwidth(t->S.r_track, t->hw.data());
         disc_halfwidth(t->S.r_blocked, t->hw.data() + t->S.r_track + 1);
         t->seen_frames = f->frames;
+        t->cull_on = p->cull != 0 && f->prm.flow_back == 0;
+        if (t->cull_on)
+            t->cull = fund::CullShape{ p->cull_params.iterations, fund::cull_thr2(p->cull_params.pixel_error), p->cull_params.seed };
         rc = allocate(t);
         if (rc != VISFS_BA_OK) { f->err = t->err; free_device(t); delete t; return rc; }
         if (f->device) {                       // the states the call's records point into
@@ -1246,6 +1368,60 @@ int visfs_tracker_download(const visfs_tracker* ct, int32_t* n_from, float* gues
     });
 }
 
+int visfs_tracker_download_cull(const visfs_tracker* ct, int32_t* applied, int32_t* m, int32_t* n_hypotheses, int32_t* n_inliers, uint8_t* mask,
+                                uint8_t* status, double* F, double* T1, double* T2, int32_t* winner_h, int32_t* winner_k) {
+    visfs_tracker* t = const_cast<visfs_tracker*>(ct);
+    if (!t) return VISFS_BA_ERR_BAD_ARGUMENT;
+    return guarded_tk(t, [&]() -> int {
+        if (!t->f) return fail(t, VISFS_BA_ERR_NOT_LOADED, "the flow object of this tracker is gone");
+        if (!t->have_call) return fail(t, VISFS_BA_ERR_NOT_LOADED, "no call to report on");
+        if (applied) *applied = 0;
+        if (m) *m = 0;
+        if (n_hypotheses) *n_hypotheses = 0;
+        if (n_inliers) *n_inliers = 0;
+        if (winner_h) *winner_h = -1;
+        if (winner_k) *winner_k = -1;
+        for (int i = 0; i < 9; ++i) { if (F) F[i] = 0.0; if (T1) T1[i] = 0.0; if (T2) T2[i] = 0.0; }
+        if (!t->cull_on) return (int)VISFS_BA_OK;
+        visfs_flow* f = t->f;
+        const fund::CullRec& C = t->B.cull;
+        const size_t M = (size_t)t->S.M;
+        Ctl c;
+        fund::Header hd{};
+        fund::Result res{};
+        std::vector<uint8_t> h_mask(M), h_status(M);
+        if (f->device) {
+            TK_HIP(t, hipSetDevice(f->dev));
+            TK_HIP(t, hipMemcpyAsync(&c, t->B.ctl, sizeof(Ctl), hipMemcpyDeviceToHost, f->stream));
+            TK_HIP(t, hipMemcpyAsync(&hd, C.head, sizeof(hd), hipMemcpyDeviceToHost, f->stream));
+            TK_HIP(t, hipMemcpyAsync(&res, C.res, sizeof(res), hipMemcpyDeviceToHost, f->stream));
+            TK_HIP(t, hipMemcpyAsync(h_mask.data(), C.mask, M, hipMemcpyDeviceToHost, f->stream));
+            TK_HIP(t, hipMemcpyAsync(h_status.data(), C.status, M, hipMemcpyDeviceToHost, f->stream));
+            TK_HIP(t, hipStreamSynchronize(f->stream));
+        } else {
+            c = *t->B.ctl; hd = *C.head; res = *C.res;
+            std::memcpy(h_mask.data(), C.mask, M); std::memcpy(h_status.data(), C.status, M);
+        }
+        const size_t nf = (size_t)std::min(std::max(c.n_from, 0), t->S.M);
+        const int32_t rows = std::min(std::max(c.cull_m, 0), t->S.M);
+        if (m) *m = rows;
+        if (status) std::memcpy(status, h_status.data(), nf);
+        if (mask) std::memcpy(mask, h_mask.data(), nf);
+        if (rows < fund::kMinRows) return (int)VISFS_BA_OK;            // not applied: the status passed through, the rest is zero
+        if (applied) *applied = 1;
+        if (n_hypotheses) *n_hypotheses = rows == fund::kMinRows ? 1 : t->cull.iterations;
+        int32_t inl = 0;
+        for (size_t i = 0; i < nf; ++i) inl += h_mask[i];
+        if (n_inliers) *n_inliers = inl;
+        if (winner_h) *winner_h = res.winner_h;
+        if (winner_k) *winner_k = res.winner_k;
+        if (F) for (int i = 0; i < 9; ++i) F[i] = res.F[i];
+        if (T1) fund::hartley_matrix(hd.T1, T1);
+        if (T2) fund::hartley_matrix(hd.T2, T2);
+        return (int)VISFS_BA_OK;
+    });
+}
+
 }  // extern "C"
 
 // ====================================================================== tracker groups (include/visfs_tracker_group.h)
@@ -1271,7 +1447,9 @@ bool same_flow_params(const visfs_flow_params& a, const visfs_flow_params& b) {
 bool same_tracker_params(const visfs_tracker_params& a, const visfs_tracker_params& b) {
     return a.max_features == b.max_features && a.quality_level == b.quality_level && a.min_distance == b.min_distance &&
            a.min_inliers == b.min_inliers && (a.clahe != 0) == (b.clahe != 0) && a.clahe_params.clip_limit == b.clahe_params.clip_limit &&
-           a.clahe_params.tiles_x == b.clahe_params.tiles_x && a.clahe_params.tiles_y == b.clahe_params.tiles_y;
+           a.clahe_params.tiles_x == b.clahe_params.tiles_x && a.clahe_params.tiles_y == b.clahe_params.tiles_y &&
+           (a.cull != 0) == (b.cull != 0) && a.cull_params.pixel_error == b.cull_params.pixel_error &&
+           a.cull_params.iterations == b.cull_params.iterations && a.cull_params.seed == b.cull_params.seed;
 }
 
 void free_group(visfs_tracker_group* g) {

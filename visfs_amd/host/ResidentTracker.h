@@ -47,14 +47,19 @@ public:
     ResidentTracker& operator=(const ResidentTracker&) = delete;
 
     // flow: the object that holds the pyramids (visfs_flow_create, or visfs_flow_create_host for the one-core twin); it must outlive
-    // this tracker.  The Tracker/* and Estimator/MinInliers keys as the reference names them.
+    // this tracker.  The Tracker/* and Estimator/MinInliers keys as the reference names them.  cullByFundationMatrix
+    // (Tracker/CullByFundationMatrix, with Tracker/FundationPixelError) takes effect, as in the reference, only on a flow object whose
+    // flow_back is off (Tracker.cpp:275); cullIterations and cullSeed are the two keys the search has on top (visfs_fund.h).
     ResidentTracker(visfs_flow* flow, const visfs_flow_camera& camera, int maxFeatures = 300, double qualityLevel = 0.01,
                     int minFeatureDistance = 40, int minInliers = 10, bool clahe = false, double clipLimit = 3.0, int tilesX = 8,
-                    int tilesY = 8) {
+                    int tilesY = 8, bool cullByFundationMatrix = false, float fundationPixelError = 1.0f, int cullIterations = 1000,
+                    uint64_t cullSeed = 0) {
         visfs_tracker_params p;
         visfs_tracker_default_params(&p);
         p.max_features = maxFeatures; p.quality_level = qualityLevel; p.min_distance = minFeatureDistance; p.min_inliers = minInliers;
         p.clahe = clahe ? 1 : 0; p.clahe_params.clip_limit = clipLimit; p.clahe_params.tiles_x = tilesX; p.clahe_params.tiles_y = tilesY;
+        p.cull = cullByFundationMatrix ? 1 : 0; p.cull_params.pixel_error = fundationPixelError; p.cull_params.iterations = cullIterations;
+        p.cull_params.seed = cullSeed;
         const int rc = visfs_tracker_create(flow, &p, &camera, &t_);
         if (rc != VISFS_BA_OK) throw std::runtime_error("visfs_tracker_create failed with status " + std::to_string(rc));
     }
@@ -125,7 +130,8 @@ private:
 };
 
 // Tracker::imageProcess of every camera of a rig in one call.  The members are ResidentTrackers on flow objects of their own (all of
-// one handle, or all host twins) with equal keys and image size; they must outlive the group and stay usable on their own.
+// one handle, or all host twins) with equal keys (cullByFundationMatrix and fundationPixelError among them: the cull of every member
+// runs inside the one call) and image size; they must outlive the group and stay usable on their own.
 class ResidentTrackerGroup {
 public:
     struct Input {

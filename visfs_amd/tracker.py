@@ -11,11 +11,13 @@ import numpy as np
 from . import abi, backend
 from . import clahe as _clahe
 from . import corners as _corners
+from . import fund as _fund
 
-ABI_VERSION = 1
+ABI_VERSION = 2
 EXPORTS = [
     "visfs_tracker_abi_version", "visfs_tracker_default_params", "visfs_tracker_create", "visfs_tracker_destroy",
     "visfs_tracker_last_error", "visfs_tracker_reset", "visfs_tracker_process", "visfs_tracker_download",
+    "visfs_tracker_download_cull",
 ]
 GROUP_ABI_VERSION = 1
 GROUP_EXPORTS = [
@@ -36,7 +38,7 @@ _pd = C.POINTER(C.c_double)
 
 class Params(C.Structure):
     _fields_ = [("max_features", C.c_int32), ("quality_level", C.c_double), ("min_distance", C.c_int32), ("min_inliers", C.c_int32),
-                ("clahe", C.c_int32), ("clahe_params", _clahe.Params)]
+                ("clahe", C.c_int32), ("clahe_params", _clahe.Params), ("cull", C.c_int32), ("cull_params", _fund.Params)]
 
 
 class Result(C.Structure):
@@ -57,15 +59,21 @@ _lib = None
 
 
 def load(require_group=True):
-    """require_group=False: for a library built before tracker groups existed (the timing tools load a parent commit's build)."""
+    """require_group=False: for a library of a parent commit (the timing tools load one): it may lack the tracker groups, and it may
+    have ABI 1, which knows neither the cull fields behind clahe_params, which it does not read, nor visfs_tracker_download_cull."""
     global _lib
     if _lib is not None:
         return _lib
     lib = backend.load_library()
+    if not hasattr(lib, "visfs_tracker_abi_version"):
+        raise backend.BackendError("libvisfs_ba_hip.so does not export visfs_tracker_abi_version")
+    lib.visfs_tracker_abi_version.restype = C.c_int
+    older = lib.visfs_tracker_abi_version() == 1 and not require_group          # ABI 1: a parent commit's build, for the timing tools alone
     for name in EXPORTS + (GROUP_EXPORTS if require_group else []):
+        if older and name == "visfs_tracker_download_cull":
+            continue
         if not hasattr(lib, name):
             raise backend.BackendError(f"libvisfs_ba_hip.so does not export {name}")
-    lib.visfs_tracker_abi_version.restype = C.c_int
     lib.visfs_tracker_default_params.argtypes = [C.POINTER(Params)]
     lib.visfs_tracker_default_params.restype = None
     lib.visfs_tracker_create.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.POINTER(C.c_void_p)]
@@ -80,7 +88,10 @@ def load(require_group=True):
     lib.visfs_tracker_process.restype = C.c_int
     lib.visfs_tracker_download.argtypes = [C.c_void_p, _pi32, _pf, _pf, _pu8, _pu8, _pi32, C.c_void_p, _pu8, _pi32, _pu8]
     lib.visfs_tracker_download.restype = C.c_int
-    if lib.visfs_tracker_abi_version() != ABI_VERSION:
+    if not older:
+        lib.visfs_tracker_download_cull.argtypes = [C.c_void_p, _pi32, _pi32, _pi32, _pi32, _pu8, _pu8, _pd, _pd, _pd, _pi32, _pi32]
+        lib.visfs_tracker_download_cull.restype = C.c_int
+    if lib.visfs_tracker_abi_version() != ABI_VERSION and not older:
         raise backend.BackendError("ABI version mismatch between visfs_amd/tracker.py and libvisfs_ba_hip.so")
     if require_group:
         lib.visfs_tracker_group_abi_version.restype = C.c_int
@@ -100,13 +111,16 @@ def load(require_group=True):
     return lib
 
 
-def default_params(clahe_params=None, **kw):
+def default_params(clahe_params=None, cull_params=None, **kw):
+    """cull=1 with a flow object whose flow_back is 0 runs Tracker/CullByFundationMatrix inside the call; cull_params: a fund.Params."""
     p = Params()
     load().visfs_tracker_default_params(C.byref(p))
     for k, v in kw.items():
         setattr(p, k, v)
     if clahe_params is not None:
         p.clahe_params = clahe_params
+    if cull_params is not None:
+        p.cull_params = cull_params
     return p
 
 
@@ -230,6 +244,26 @@ class Tracker:
         return dict(guess_xy=guess[:nf.value].copy(), to_xy=to[:nf.value].copy(), lk_status=st[:nf.value].copy(),
                     in_bounds=inb[:nf.value].copy(), discs=discs[:nd.value].copy(), disc_drawn=drawn[:nd.value].copy(),
                     stereo_status=sst[:nr.value].copy())
+
+    def download_cull(self):
+        """The fundamental-matrix cull of the last call, as fund.Fund.cull and fund.Fund.download report it for the same from-rows:
+        dict(applied, m, n_hypotheses, n_inliers, mask and status per from-row (status: after the AND), F, T1, T2 [3][3], winner
+        (h, k)).  A tracker whose cull is inactive reports applied 0, m 0 and empty mask and status."""
+        n = int(self.params.max_features)
+        mask = np.zeros(n, dtype=np.uint8); status = np.zeros(n, dtype=np.uint8)
+        F, T1, T2 = np.zeros((3, 3)), np.zeros((3, 3)), np.zeros((3, 3))
+        ap, m, nh, ni, wh, wk, nf = (C.c_int32(0) for _ in range(7))
+        rc = self._lib.visfs_tracker_download_cull(self.h, C.byref(ap), C.byref(m), C.byref(nh), C.byref(ni), mask.ctypes.data_as(_pu8),
+                                                   status.ctypes.data_as(_pu8), F.ctypes.data_as(_pd), T1.ctypes.data_as(_pd),
+                                                   T2.ctypes.data_as(_pd), C.byref(wh), C.byref(wk))
+        if rc == abi.OK:
+            rc = self._lib.visfs_tracker_download(self.h, C.byref(nf), None, None, None, None, None, None, None, None, None)
+        if rc != abi.OK:
+            raise backend.BackendError(f"tracker download_cull: status {rc}: {self.last_error()}")
+        active = bool(self.params.cull) and not self.flow.params.flow_back
+        rows = nf.value if active else 0
+        return dict(applied=ap.value, m=m.value, n_hypotheses=nh.value, n_inliers=ni.value, mask=mask[:rows].copy(),
+                    status=status[:rows].copy(), F=F, T1=T1, T2=T2, winner=(wh.value, wk.value))
 
 
 def group_create_status(members):
