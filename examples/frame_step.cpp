@@ -7,6 +7,8 @@
 //       -Wl,-rpath,$PWD/visfs_amd/lib -o frame_step && ./frame_step 5          (./frame_step 5 host: the one-core twins, no GPU)
 //   ./frame_step 5 cull (or: 5 host cull): the configuration of the launch files that set Tracker/FlowBack to false: no reverse
 //   passes, and Tracker/CullByFundationMatrix inside the resident call in their place.
+//   ./frame_step 5 pnp (or: 5 host pnp): the pose guess runs inside the resident call too (include/visfs_tracker_pnp.h, DESIGN.md
+//   section 9k): the pose comes from VISFS::ResidentTracker::poseGuess() and no visfs_pnp object is created.
 //
 // A stereo camera slides sideways in front of a textured wall 5 m away, so the true motion and depth are known.  The pose PnP finds
 // in one frame is the guess of the next; the first guess is the identity, which the wrapper treats as "not set" (Tracker.cpp:237).
@@ -64,7 +66,8 @@ struct Summary {
 };
 
 // cull: Tracker/CullByFundationMatrix; the flow object must then have been made with flow_back off
-inline int run(int frames, visfs_flow* flow, visfs_pnp* pnp, Summary& out, bool cull = false) {
+// resident_pnp: the pose guess inside the tracker call; pnp is not used then and may be NULL
+inline int run(int frames, visfs_flow* flow, visfs_pnp* pnp, Summary& out, bool cull = false, bool resident_pnp = false) {
     const int W = 640, H = 400;
     const float fx = 435.2f, baseline = 0.11f;
     const double depth = 5.0, step = 0.06;                                      // metres per frame to the right: flow = -fx * step / depth
@@ -78,6 +81,7 @@ inline int run(int frames, visfs_flow* flow, visfs_pnp* pnp, Summary& out, bool 
     VISFS::ResidentTracker tracker(flow, cam, 300, 0.01, 20, 10, false, 3.0, 8, 8, cull, 1.0f);
     visfs_pnp_params pp;
     visfs_pnp_default_params(&pp);
+    if (resident_pnp) tracker.enablePnP(pp.min_inliers, pp.iterations, (double)pp.reproj_error, pp.refine_iterations, pp.seed);
     visfs_window_map* window = nullptr;
     if (visfs_window_create(0, nullptr, nullptr, &window) != VISFS_BA_OK) return 2;
     const Texture wall(2024);
@@ -110,7 +114,13 @@ inline int run(int frames, visfs_flow* flow, visfs_pnp* pnp, Summary& out, bool 
         double T[16], cov[36];
         std::vector<int32_t> matches((size_t)n + 1), inliers((size_t)n + 1);
         int32_t nm = 0, ni = 0;
-        if (visfs_pnp_solve(pnp, &pp, &pcam, n, from3.data(), to2.data(), nullptr, T, cov, matches.data(), &nm, inliers.data(), &ni) != VISFS_BA_OK) {
+        if (resident_pnp) {                                                     // it came down with the tracker call
+            VISFS::ResidentTracker::PoseGuess pg;
+            if (tracker.poseGuess(pg) != VISFS_BA_OK || !pg.ran) { std::fprintf(stderr, "no pose guess in frame %d\n", f); return 1; }
+            std::memcpy(T, pg.transform.data(), sizeof(T));
+            std::memcpy(cov, pg.covariance.data(), sizeof(cov));
+            nm = (int32_t)pg.matches.size(); ni = (int32_t)pg.inliers.size();
+        } else if (visfs_pnp_solve(pnp, &pp, &pcam, n, from3.data(), to2.data(), nullptr, T, cov, matches.data(), &nm, inliers.data(), &ni) != VISFS_BA_OK) {
             std::fprintf(stderr, "pnp failed: %s\n", visfs_pnp_last_error(pnp));
             return 1;
         }
@@ -149,10 +159,11 @@ inline int run(int frames, visfs_flow* flow, visfs_pnp* pnp, Summary& out, bool 
 #ifndef FRAME_STEP_NO_MAIN
 int main(int argc, char** argv) {
     const int frames = argc > 1 ? std::atoi(argv[1]) : 5;
-    bool host = false, cull = false;
+    bool host = false, cull = false, resident_pnp = false;
     for (int i = 2; i < argc; ++i) {
         host = host || std::strcmp(argv[i], "host") == 0;
         cull = cull || std::strcmp(argv[i], "cull") == 0;
+        resident_pnp = resident_pnp || std::strcmp(argv[i], "pnp") == 0;
     }
     visfs_ba_handle* ba = nullptr;
     visfs_flow* flow = nullptr;
@@ -161,16 +172,18 @@ int main(int argc, char** argv) {
     visfs_flow_default_params(&fp);
     if (cull) fp.flow_back = 0;
     if (host) {
-        if (visfs_flow_create_host(&fp, 640, 400, &flow) != VISFS_BA_OK || visfs_pnp_create_host(4096, &pnp) != VISFS_BA_OK) return 3;
+        if (visfs_flow_create_host(&fp, 640, 400, &flow) != VISFS_BA_OK) return 3;
+        if (!resident_pnp && visfs_pnp_create_host(4096, &pnp) != VISFS_BA_OK) return 3;
     } else {
         visfs_ba_params prm;
         visfs_ba_default_params(&prm);
         if (visfs_ba_create(&prm, 0, &ba) != VISFS_BA_OK) { std::fprintf(stderr, "no MI355X / gfx950 device\n"); return 3; }
-        if (visfs_flow_create(ba, &fp, 640, 400, &flow) != VISFS_BA_OK || visfs_pnp_create(ba, 4096, &pnp) != VISFS_BA_OK) return 3;
+        if (visfs_flow_create(ba, &fp, 640, 400, &flow) != VISFS_BA_OK) return 3;
+        if (!resident_pnp && visfs_pnp_create(ba, 4096, &pnp) != VISFS_BA_OK) return 3;
     }
     frame_step::Summary s;
     int rc;
-    try { rc = frame_step::run(frames, flow, pnp, s, cull); } catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); rc = 1; }
+    try { rc = frame_step::run(frames, flow, pnp, s, cull, resident_pnp); } catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); rc = 1; }
     visfs_pnp_destroy(pnp);
     visfs_flow_destroy(flow);
     if (ba) visfs_ba_destroy(ba);

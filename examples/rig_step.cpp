@@ -27,6 +27,8 @@
 int main(int argc, char** argv) {
     const int frames = argc > 1 ? std::atoi(argv[1]) : 5;
     const bool host = argc > 2 && std::strcmp(argv[2], "host") == 0;
+    // ./rig_step N [host] pnp: the pose guess of every camera inside the one call too (include/visfs_tracker_pnp.h)
+    const bool resident_pnp = std::strcmp(argv[argc - 1], "pnp") == 0;
     constexpr int kCams = 4;
     const int W = 640, H = 400;
     const float fx = 435.2f, baseline = 0.11f;
@@ -52,13 +54,15 @@ int main(int argc, char** argv) {
         if (rc != VISFS_BA_OK || visfs_window_create(0, nullptr, nullptr, &windows[c]) != VISFS_BA_OK) return 3;
     }
     int status = 0, inserted = 0, words = 0, bootstrapped = 0, launches = 0, copies = 0, syncs = 0, solved = 0, max_launches = 0;
-    double max_depth_err = 0.0, group_ms = 0.0, max_pose_shift = 0.0;
+    double max_depth_err = 0.0, group_ms = 0.0, max_pose_shift = 0.0, max_translation_err = 0.0;
+    int min_pnp_inliers = 1 << 30;
     try {
         std::vector<std::unique_ptr<VISFS::ResidentTracker>> trackers;
         std::vector<VISFS::ResidentTracker*> members;
         std::vector<frame_step::Texture> walls;
         for (int c = 0; c < kCams; ++c) {
             trackers.emplace_back(new VISFS::ResidentTracker(flows[c], cam, 300, 0.01, 20, 10));
+            if (resident_pnp) trackers.back()->enablePnP();
             members.push_back(trackers.back().get());
             walls.emplace_back(2024 + 17 * c);
         }
@@ -82,6 +86,13 @@ int main(int argc, char** argv) {
                 if (fr.noPrevious) continue;
                 if (fr.lost) { std::fprintf(stderr, "camera %d lost tracking in frame %d\n", c, f); status = 5; break; }
                 bootstrapped += fr.bootstrapped ? 1 : 0;
+                if (resident_pnp) {                                     // the robot moved by (0, -step, 0), as in frame_step.cpp
+                    VISFS::ResidentTracker::PoseGuess pg;
+                    if (trackers[c]->poseGuess(pg) != VISFS_BA_OK || !pg.ran) { std::fprintf(stderr, "camera %d: no pose guess\n", c); status = 8; break; }
+                    const double* T = pg.transform.data();
+                    max_translation_err = std::fmax(max_translation_err, std::sqrt(T[3] * T[3] + (T[7] + step) * (T[7] + step) + T[11] * T[11]));
+                    min_pnp_inliers = (int)pg.inliers.size() < min_pnp_inliers ? (int)pg.inliers.size() : min_pnp_inliers;
+                }
                 std::vector<uint64_t> wid, covIds;
                 std::vector<float> uv, p3, covUv;
                 std::vector<uint8_t> has3d;
@@ -141,7 +152,9 @@ int main(int argc, char** argv) {
     if (status != 0) return status;
     std::printf("{\"cameras\": %d, \"frames\": %d, \"inserted\": %d, \"words\": %d, \"bootstrapped\": %d, \"max_depth_err_m\": %.4g, "
                 "\"windows_solved\": %d, \"max_pose_shift_m\": %.4g, \"kernel_launches_last\": %d, \"kernel_launches_max\": %d, "
-                "\"copies_last\": %d, \"synchronisations_last\": %d, \"group_ms\": %.2f}\n",
+                "\"copies_last\": %d, \"synchronisations_last\": %d, \"group_ms\": %.2f",
                 kCams, frames, inserted, words, bootstrapped, max_depth_err, solved, max_pose_shift, launches, max_launches, copies, syncs, group_ms);
+    if (resident_pnp) std::printf(", \"min_pnp_inliers\": %d, \"max_translation_err_m\": %.4g", min_pnp_inliers, max_translation_err);
+    std::printf("}\n");
     return 0;
 }

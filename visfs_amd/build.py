@@ -12,7 +12,7 @@ HEADERS = ["ba_math.hpp", "ba_pnp.hpp", os.path.join("..", "..", "include", "vis
            os.path.join("..", "..", "include", "visfs_submap.h"), os.path.join("..", "..", "include", "visfs_flow.h"),
            os.path.join("..", "..", "include", "visfs_corners.h"), "ba_clahe.hpp", os.path.join("..", "..", "include", "visfs_clahe.h"),
            "ba_tracker.hpp", os.path.join("..", "..", "include", "visfs_tracker.h"),
-           os.path.join("..", "..", "include", "visfs_tracker_group.h")]
+           os.path.join("..", "..", "include", "visfs_tracker_group.h"), os.path.join("..", "..", "include", "visfs_tracker_pnp.h")]
 
 
 def _stale(target, deps):

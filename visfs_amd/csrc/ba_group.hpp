@@ -67,3 +67,26 @@ int group_cull(hipStream_t stream, int n, const CullRec* d_recs, int32_t max_row
 void cull_host(const CullRec& r, const float* from_xy, const float* to_xy, const uint8_t* lk_st, int32_t n_from, const CullShape& S);
 
 }  // namespace fund
+
+struct visfs_pnp_params;                       // include/visfs_pnp.h
+struct visfs_pnp_camera;
+
+namespace pnp {
+
+struct PnpRec;                                 // ba_pnp.hpp
+struct PnpShape;
+struct Row;
+struct Result;
+struct Cam;
+// The search and the refinement of the pose guess for the n members of a tracker call (ba_pnp.hip): two
+// launches with grid.z = n behind the rows kernel of ba_tracker.hip.
+int group_pnp(hipStream_t stream, int n, const PnpRec* d_recs, const PnpShape& S, flow::GroupCounts* cnt);
+// The parameter check of visfs_pnp_solve; `why` is a string literal.
+int check_params(const visfs_pnp_params& q, const visfs_pnp_camera& c, const char** why);
+// MultiviewGeometry.cpp:147-205 from the model and the inliers (numbers of `rows`), on the host in every flavour: the transform
+// (Tir * pnp)^-1 into T_out[16] and the scaling of the covariance cov[36], which the caller has set to the identity.  matches[k]:
+// the input row of rows[k]; to_xyz: per input row, or NULL.
+void finalize(const Result& res, const Row* rows, const double Tir[12], const Cam& K, const int32_t* inliers, size_t n_inliers,
+              const int32_t* matches, const float* to_xyz, double* T_out, double* cov);
+
+}  // namespace pnp

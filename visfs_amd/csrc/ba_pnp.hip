@@ -10,8 +10,13 @@
 //
 // A call is one copy in (a zeroed header with the winner key, the kept rows), the two launches and one copy out (the result block and
 // the inlier list).  The covariance is computed on the host in both flavours.  The arithmetic is ba_pnp.hpp.
+//
+// The resident tracker (include/visfs_tracker_pnp.h) runs the same two stages on rows that never leave the
+// device: k_pnp_ransac_g and k_pnp_refine_g read their member's PnpRec at blockIdx.z and m from device memory (pnp::group_pnp) and
+// share their bodies with the by-value kernels.
 #include "ba_pnp.hpp"
 #include "ba_flow.hpp"
+#include "ba_group.hpp"      // pnp::group_pnp, pnp::check_params, pnp::finalize
 #include "../../include/visfs_pnp.h"
 
 #include <algorithm>
@@ -52,7 +57,8 @@ BA_HD Rt load_model(const double* o) {
     return T;
 }
 
-__global__ __launch_bounds__(PN_T) void k_pnp_ransac(RansacArgs A) {
+// One body for the by-value kernel of the staged call and the record-reading kernel of the resident tracker.
+__device__ __forceinline__ void pnp_ransac_body(const RansacArgs& A) {
     __shared__ Row s_rows[kMaxPoints];
     {
         const float* src = reinterpret_cast<const float*>(A.rows);
@@ -81,6 +87,21 @@ __global__ __launch_bounds__(PN_T) void k_pnp_ransac(RansacArgs A) {
         store_model(A.models + 12 * (size_t)h, ok, T);
         if (ok) atomicMax(A.key, ((unsigned long long)count << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)h));
     }
+}
+
+__global__ __launch_bounds__(PN_T) void k_pnp_ransac(RansacArgs A) { pnp_ransac_body(A); }
+
+// Member blockIdx.z of a tracker call: m comes from device memory.  Fewer rows than min_inliers: nothing of the pose guess runs for
+// the member (the rows kernel has written its result).  The record's fields go into the argument struct once, in front of the body.
+__global__ __launch_bounds__(PN_T) void k_pnp_ransac_g(const PnpRec* __restrict__ recs, PnpShape S) {
+    const PnpRec* r = recs + blockIdx.z;
+    if (r->skip) return;
+    const int32_t m = min(*r->m, kMaxPoints);
+    if (m < S.min_inliers || (int)blockIdx.x * (PN_T / 64) >= S.iterations) return;
+    RansacArgs A;
+    A.rows = r->rows; A.m = m; A.iterations = S.iterations; A.seed = S.seed; A.K = r->K; A.thr = S.thr;
+    A.samples = r->samples; A.vc = r->vc; A.models = r->models; A.key = r->key;
+    pnp_ransac_body(A);
 }
 
 struct RefineArgs {
@@ -188,7 +209,7 @@ struct DevicePolicy {
     }
 };
 
-__global__ __launch_bounds__(PN_T) void k_pnp_refine(RefineArgs A) {
+__device__ __forceinline__ void pnp_refine_body(const RefineArgs& A) {
     __shared__ int32_t s_lists[2][kMaxPoints];
     __shared__ float s_errs[kMaxPoints];
     __shared__ double s_red[PN_T / 64][28];
@@ -202,6 +223,31 @@ __global__ __launch_bounds__(PN_T) void k_pnp_refine(RefineArgs A) {
     Rt W = load_model(A.models + 12 * (size_t)(key ? res.winner : 0));
     refine_all(pol, A.K, key != 0, W, A.min_inliers, A.refine_iterations, A.thr0, A.sigma, res);
     if (threadIdx.x == 0) *A.res = res;
+}
+
+__global__ __launch_bounds__(PN_T) void k_pnp_refine(RefineArgs A) { pnp_refine_body(A); }
+
+__global__ __launch_bounds__(PN_T) void k_pnp_refine_g(const PnpRec* __restrict__ recs, PnpShape S) {
+    const PnpRec* r = recs + blockIdx.z;
+    if (r->skip) return;
+    const int32_t m = min(*r->m, kMaxPoints);
+    if (m < S.min_inliers) return;
+    RefineArgs A;
+    A.rows = r->rows; A.m = m; A.cap = r->cap; A.K = r->K; A.min_inliers = S.min_inliers; A.refine_iterations = S.refine_iterations;
+    A.thr0 = S.thr; A.sigma = S.sigma; A.key = r->key; A.models = r->models; A.res = r->res; A.inliers = r->inliers;
+    A.pass_tq = r->pass_tq; A.pass_thr = r->pass_thr; A.pass_cnt = r->pass_cnt; A.pass_lists = r->pass_lists;
+    pnp_refine_body(A);
+}
+
+int group_pnp(hipStream_t stream, int n, const PnpRec* d_recs, const PnpShape& S, flow::GroupCounts* cnt) {
+    hipLaunchKernelGGL(k_pnp_ransac_g, dim3((unsigned)((S.iterations + PN_T / 64 - 1) / (PN_T / 64)), 1, (unsigned)n), dim3(PN_T), 0, stream,
+                       d_recs, S);
+    if (hipGetLastError() != hipSuccess) return VISFS_BA_ERR_DEVICE;
+    ++cnt->kernels;
+    hipLaunchKernelGGL(k_pnp_refine_g, dim3(1, 1, (unsigned)n), dim3(PN_T), 0, stream, d_recs, S);
+    if (hipGetLastError() != hipSuccess) return VISFS_BA_ERR_DEVICE;
+    ++cnt->kernels;
+    return VISFS_BA_OK;
 }
 
 }  // namespace pnp
@@ -411,23 +457,26 @@ float angle3d(const float a[3], const float b[3]) {
     return (float)std::acos((double)rad);
 }
 
-// MultiviewGeometry.cpp:147-205 from the model and the inliers (kept-row numbers), on the host in both flavours.
-void finalize(const visfs_pnp* p, const visfs_pnp_camera& cam, const Cam& K, const std::vector<int32_t>& inliers, const int32_t* matches,
-              const float* to_xyz, double* T_out, double* cov) {
-    const Rt M = tq_to_rt(p->res.tq);
+}  // namespace
+
+namespace pnp {
+
+// MultiviewGeometry.cpp:147-205 from the model and the inliers (kept-row numbers), on the host in every flavour (ba_group.hpp).
+void finalize(const Result& res, const Row* rows, const double Tir[12], const Cam& K, const int32_t* inliers, size_t n,
+              const int32_t* matches, const float* to_xyz, double* T_out, double* cov) {
+    const Rt M = tq_to_rt(res.tq);
     const double pnp34[12] = { M.R.m00, M.R.m01, M.R.m02, M.t.x, M.R.m10, M.R.m11, M.R.m12, M.t.y, M.R.m20, M.R.m21, M.R.m22, M.t.z };
     double prod[12], T[12];
-    visfs_ba::iso_mul(cam.Tir, pnp34, prod);
+    visfs_ba::iso_mul(Tir, pnp34, prod);
     visfs_ba::iso_inv(prod, T);
     for (int i = 0; i < 12; ++i) T_out[i] = T[i];
     T_out[12] = T_out[13] = T_out[14] = 0.0; T_out[15] = 1.0;
-    const size_t n = inliers.size();
     if (to_xyz) {
         std::vector<float> d2, ang;
         for (size_t i = 0; i < n; ++i) {
             const float* q = to_xyz + 3 * (size_t)matches[inliers[i]];
             if (!finite3(q)) continue;
-            const Row& r = p->rows[inliers[i]];
+            const Row& r = rows[inliers[i]];
             float np[3];
             for (int k = 0; k < 3; ++k) np[k] = (float)(T[4 * k] * (double)q[0] + T[4 * k + 1] * (double)q[1] + T[4 * k + 2] * (double)q[2] + T[4 * k + 3]);
             const float dx = r.X - np[0], dy = r.Y - np[1], dz = r.Z - np[2];
@@ -446,7 +495,7 @@ void finalize(const visfs_pnp* p, const visfs_pnp_camera& cam, const Cam& K, con
     } else {
         float err = 0.0f;
         for (size_t i = 0; i < n; ++i) {
-            const Row& r = p->rows[inliers[i]];
+            const Row& r = rows[inliers[i]];
             double pu, pv;
             project(M, K, r, pu, pv);
             const float dx = r.u - (float)pu, dy = r.v - (float)pv;
@@ -457,7 +506,8 @@ void finalize(const visfs_pnp* p, const visfs_pnp_camera& cam, const Cam& K, con
     }
 }
 
-int check_params(const visfs_pnp_params& q, const visfs_pnp_camera& c, std::string& why) {
+int check_params(const visfs_pnp_params& q, const visfs_pnp_camera& c, const char** why_out) {
+    const char*& why = *why_out;
     if (!std::isfinite(q.reproj_error) || q.reproj_error < 0.0f || !std::isfinite(q.refine_sigma) || q.refine_sigma < 0.0f) {
         why = "a threshold is not finite or is negative"; return VISFS_BA_ERR_BAD_ARGUMENT;
     }
@@ -471,7 +521,7 @@ int check_params(const visfs_pnp_params& q, const visfs_pnp_camera& c, std::stri
     return VISFS_BA_OK;
 }
 
-}  // namespace
+}  // namespace pnp
 
 // ====================================================================== exported C ABI
 extern "C" {
@@ -528,8 +578,8 @@ int visfs_pnp_solve(visfs_pnp* p, const visfs_pnp_params* params, const visfs_pn
         (n > 0 && (!from_xyz || !to_xy || !matches_out || !inliers_out)))
         return fail(p, VISFS_BA_ERR_BAD_ARGUMENT, "a required pointer is null or n is negative");
     return guarded_pn(p, [&]() -> int {
-        std::string why;
-        const int rc = check_params(*params, *camera, why);
+        const char* why = "";
+        const int rc = check_params(*params, *camera, &why);
         if (rc != VISFS_BA_OK) return fail(p, rc, why);
         if (n > p->cap) return fail(p, VISFS_BA_ERR_BAD_ARGUMENT, "n is above the capacity of the solver");
         if (p->device) {
@@ -563,7 +613,7 @@ int visfs_pnp_solve(visfs_pnp* p, const visfs_pnp_params* params, const visfs_pn
         if (rc2 != VISFS_BA_OK) { p->solved = false; return rc2; }
         p->last_hyp = params->iterations; p->last_passes = p->res.n_passes;
         if ((int)inliers.size() < min_inliers) return (int)VISFS_BA_OK;
-        finalize(p, *camera, K, inliers, matches_out, to_xyz, T_out, cov_out);
+        finalize(p->res, p->rows.data(), camera->Tir, K, inliers.data(), inliers.size(), matches_out, to_xyz, T_out, cov_out);
         *n_inliers = (int32_t)inliers.size();
         for (size_t i = 0; i < inliers.size(); ++i) inliers_out[i] = matches_out[inliers[i]];
         return (int)VISFS_BA_OK;

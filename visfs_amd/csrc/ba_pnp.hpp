@@ -362,4 +362,22 @@ BA_HD void refine_all(P& pol, const Cam& K, bool have_winner, const Rt& W, int m
     pol.finish(cur, ncur);                               // std::swap(_inliers, newInliers) (:310)
 }
 
+// ---- the pose guess inside a tracker call (include/visfs_tracker_pnp.h) ----------------------------------
+// A member of the call: where its rows and its state stand in device memory.  k_pnp_ransac_g and k_pnp_refine_g read the record at
+// blockIdx.z; the rows kernel of ba_tracker.hip has left the rows, their number and the zeroed winner key.
+struct PnpRec {
+    const int32_t* m;                          // rows with a finite 3-D point
+    const Row* rows;
+    unsigned long long* key;                   // (count << 32) | (0xFFFFFFFF - h) of the best hypothesis so far; 0: none
+    int32_t* samples; int32_t* vc; double* models;     // per hypothesis, as RansacArgs has them
+    Result* res; int32_t* inliers;             // in the output block of the member
+    double* pass_tq; float* pass_thr; int32_t* pass_cnt; int32_t* pass_lists;
+    Cam K;
+    int32_t cap;                               // row stride of pass_lists
+    int32_t skip;                              // the member takes no part in this call
+};
+
+// what every member of a call shares; min_inliers is already raised to 4
+struct PnpShape { int32_t iterations, min_inliers, refine_iterations; float thr, sigma; uint64_t seed; };
+
 }  // namespace pnp

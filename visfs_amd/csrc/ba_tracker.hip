@@ -20,6 +20,10 @@
 //                       (fund::group_cull), which leave the status after the AND for the reduce to keep its rows on    (:275-277, :83-96)
 //       k_trk_reduce_g  one workgroup: compaction of the kept rows in row order: covisible output, kept count, LOST, the top-up's
 //                       corner budget                                                                               (:280-320)
+//       [pose guess]    estimateMotion3DTo2D on the covisible rows (include/visfs_tracker_pnp.h): k_trk_pnp_rows_g,
+//                       one workgroup: the covisible rows with a finite 3-D point compacted in row order, their number, the winner
+//                       key zeroed, the result of a call without a search; then k_pnp_ransac_g and k_pnp_refine_g of ba_pnp.hip
+//                       (pnp::group_pnp), which leave model and inlier list in the output block       (MultiviewGeometry.cpp:94-216)
 //       k_trk_discs_g   one workgroup: rank sort of the (count, row) keys, the serial draw decision of getMask 1024 discs at a time
 //                       (each against the raster so far in parallel; then wavefront after wavefront settles its 64 discs among
 //                       themselves through cover masks and the ones behind test against what it drew), the raster's Disc list
@@ -35,13 +39,16 @@
 #include "ba_flow_object.hpp"
 #include "ba_group.hpp"
 #include "ba_fund.hpp"
+#include "ba_pnp.hpp"
 #include "../../include/visfs_tracker.h"
+#include "../../include/visfs_tracker_pnp.h"
 #include "../../include/visfs_tracker_group.h"
 
 #include <algorithm>
 #include <cstring>
 #include <new>
 #include <string>
+#include <unordered_map>
 #include <unordered_set>
 #include <vector>
 
@@ -66,7 +73,8 @@ struct Ctl {                                   // device words of a tracker
     int32_t corner_args[2];                    // the top-up: { raster discs, max_features - kept }
     int32_t boot_args[2];                      // the bootstrap: { 0, max_features }
     uint64_t next_id;                          // globalFeatureId_ (lives across calls)
-    int32_t cull_m, pad;                       // from-rows that entered the fundamental-matrix cull
+    int32_t cull_m;                            // from-rows that entered the fundamental-matrix cull
+    int32_t pnp_m;                             // covisible rows that entered the pose guess
 };
 
 struct Head {                                  // first words of the output block
@@ -84,6 +92,9 @@ struct Out {                                   // the output block, one layout f
     uint64_t* new_id; float* new_xy;
     uint64_t* w_id; float* w_l; float* w_r; float* w_xyz; int32_t* w_cnt;
     uint64_t* blk_id;
+    // the pose guess (all NULL on a tracker that never enabled it): rows that entered, the refine stage's block, its inlier list
+    // (numbers of rows that entered), the covisible row of every row that entered
+    int32_t* p_m; pnp::Result* p_res; int32_t* p_inl; int32_t* p_match;
 };
 
 struct Bufs {
@@ -95,6 +106,7 @@ struct Bufs {
     float* guess; float* to; uint8_t* lk_st; uint8_t* inb;                        // per from-row
     const uint8_t* keep_st;                                                       // the status the reduce keeps a row on: lk_st, or the cull's
     fund::CullRec cull;                                                           // all NULL without the cull
+    pnp::Row* pnp_rows; unsigned long long* pnp_key;                              // the pose guess: NULL without it
     uint64_t* row_id; float* row_xy; int32_t* row_cnt;                            // kept + new rows
     float* row_rxy; float* row_xyz; uint8_t* row_st; uint8_t* row_ok;
     visfs_corners_disc* list; uint32_t* packed; uint8_t* drawn; Disc* raster;     // getMask's discs in draw order; the raster's
@@ -113,7 +125,8 @@ struct Carver {
     }
 };
 
-size_t carve_out(char* base, size_t M, Out& o) {
+// with_pnp: the pose guess's part behind the block of a tracker without it, whose layout stays what it is
+size_t carve_out(char* base, size_t M, bool with_pnp, Out& o) {
     Carver c{ base };
     o.head = c.take<Head>(1);
     o.cov_id = c.take<uint64_t>(M); o.cov_from = c.take<float>(2 * M); o.cov_xyz = c.take<float>(3 * M); o.cov_to = c.take<float>(2 * M);
@@ -121,6 +134,10 @@ size_t carve_out(char* base, size_t M, Out& o) {
     o.w_id = c.take<uint64_t>(M); o.w_l = c.take<float>(2 * M); o.w_r = c.take<float>(2 * M); o.w_xyz = c.take<float>(3 * M);
     o.w_cnt = c.take<int32_t>(M);
     o.blk_id = c.take<uint64_t>(M);
+    o.p_m = nullptr; o.p_res = nullptr; o.p_inl = nullptr; o.p_match = nullptr;
+    if (with_pnp) {
+        o.p_m = c.take<int32_t>(1); o.p_res = c.take<pnp::Result>(1); o.p_inl = c.take<int32_t>(M); o.p_match = c.take<int32_t>(M);
+    }
     return (c.off + 255) & ~size_t(255);
 }
 
@@ -139,6 +156,7 @@ size_t carve_work(char* base, size_t M, size_t hw_len, size_t cull_iters, Bufs& 
     *hw = c.take<int32_t>(hw_len);
     b.hw = *hw;
     b.keep_st = b.lk_st;
+    b.pnp_rows = nullptr; b.pnp_key = nullptr;
     b.cull = fund::CullRec{};
     if (cull_iters > 0) {
         fund::CullRec& q = b.cull;
@@ -415,6 +433,38 @@ __global__ __launch_bounds__(TK_T) void k_trk_reduce_g(const TrkRec* __restrict_
     }
 }
 
+// Step 1 of the pose guess, which the staged visfs_pnp_solve does on the host: the covisible rows with three finite from_xyz
+// coordinates compacted in row order into the row list and the match index.  It leaves m, the zeroed winner key and the result of a
+// call whose search does not run (too few rows); the refine stage writes over that one when it runs.  A LOST call has no rows.
+__global__ __launch_bounds__(TK_T) void k_trk_pnp_rows_g(const TrkRec* __restrict__ recs, Shape S) {
+    const TrkRec& r = recs[blockIdx.z];
+    if (r.skip) return;
+    const Bufs& B = r.B;
+    __shared__ int32_t wcount[TK_WAVES];
+    const int tid = threadIdx.x;
+    Ctl* c = B.ctl;
+    const int n = c->lost ? 0 : min(c->n_kept, S.M);
+    int m = 0;
+    for (int c0 = 0; c0 < n; c0 += TK_T) {
+        const int i = c0 + tid;
+        const bool valid = i < n;
+        pnp::Row q{ 0.0f, 0.0f, 0.0f, 0.0f, 0.0f };
+        if (valid) q = pnp::Row{ B.o.cov_xyz[3 * i], B.o.cov_xyz[3 * i + 1], B.o.cov_xyz[3 * i + 2], B.o.cov_to[2 * i], B.o.cov_to[2 * i + 1] };
+        const bool enters = valid && isfinite(q.X) && isfinite(q.Y) && isfinite(q.Z);
+        int total;
+        const int o = m + wg_offset(enters, wcount, total);
+        if (enters) { B.pnp_rows[o] = q; B.o.p_match[o] = i; }
+        m += total;
+    }
+    if (tid == 0) {
+        c->pnp_m = m; *B.o.p_m = m;
+        *B.pnp_key = 0ull;                                                        // no winner yet
+        pnp::Result res{};
+        res.winner = -1;
+        *B.o.p_res = res;
+    }
+}
+
 constexpr int kHwLds = 2048;                   // half-width entries kept in LDS (both radii together); larger tables are read in place
 
 // does the packed disc p cover the pixel (x, y)?  HW is the half-width storage (LDS or global), the two tables one behind the other
@@ -630,11 +680,11 @@ __global__ __launch_bounds__(TK_T) void k_trk_finish_g(const TrkRec* __restrict_
 
 // ---------------------------------------------------------------- the objects
 // The tables of a call for n members stand in one block, pinned and on the device, and go up in one copy:
-// [PyrRec n][ClaheRec n][CornerRec n: bootstrap][CornerRec n: top-up][TrkRec n][CullRec n][InHead n][outlier ids of the members, one
-// behind the other]
+// [PyrRec n][ClaheRec n][CornerRec n: bootstrap][CornerRec n: top-up][TrkRec n][CullRec n][PnpRec n][InHead n][outlier ids of the
+// members, one behind the other]
 struct CallBlock {
     char* pinned = nullptr; char* dev = nullptr;
-    size_t off_pyr = 0, off_clahe = 0, off_boot = 0, off_top = 0, off_trk = 0, off_cull = 0, off_in = 0, off_ids = 0, bytes = 0;
+    size_t off_pyr = 0, off_clahe = 0, off_boot = 0, off_top = 0, off_trk = 0, off_cull = 0, off_pnp = 0, off_in = 0, off_ids = 0, bytes = 0;
 
     hipError_t allocate(size_t n) {            // the caller has selected the device
         size_t off = 0;
@@ -645,6 +695,7 @@ struct CallBlock {
         off_top = take(n * sizeof(CornerRec));
         off_trk = take(n * sizeof(TrkRec));
         off_cull = take(n * sizeof(fund::CullRec));
+        off_pnp = take(n * sizeof(pnp::PnpRec));
         off_in = take(n * sizeof(InHead));
         off_ids = take(n * sizeof(uint64_t) * kMaxOutliers);
         bytes = off;
@@ -686,6 +737,24 @@ struct visfs_tracker {
     Out R{};                                   // where the caller reads: the pinned copy, or the host twin's block itself
 
     visfs_tracker_group* group = nullptr;      // the tracker group this is a member of
+
+    // the pose guess (include/visfs_tracker_pnp.h)
+    bool pnp_on = false;
+    bool called = false;                       // a process call has completed: visfs_tracker_pnp_last has something to report
+    visfs_pnp_params pnp_prm{};
+    visfs_pnp_camera pnp_cam{};
+    pnp::PnpShape pnp_shape{};
+    pnp::PnpRec pnp_rec{};                     // device: where the stages work
+    char* d_pnp = nullptr;                     // device: rows, winner key, hypotheses, passes
+    size_t out_base_bytes = 0;                 // the output block of a tracker without the pose guess; what a call brings down with it off
+    visfs_pnp* pnp_host = nullptr;             // host twin: the staged host solver its steps run on
+    visfs_tracker_pnp_result pnp_res{};
+    int32_t pnp_last_m = 0, pnp_last_hyp = 0, pnp_last_passes = 0;
+    pnp::Result pnp_model{};
+    std::vector<int32_t> pnp_matches, pnp_inliers, pnp_list;
+    std::vector<float> pnp_to_xyz;
+    std::vector<pnp::Row> pnp_rows;
+    std::unordered_map<uint64_t, int32_t> pnp_index;
 };
 
 // n trackers processed by one call (include/visfs_tracker_group.h)
@@ -730,8 +799,9 @@ void free_device(visfs_tracker* t) {
     if (t->d_work) (void)hipFree(t->d_work);
     if (t->d_out) (void)hipFree(t->d_out);
     if (t->p_out) (void)hipHostFree(t->p_out);
+    if (t->d_pnp) (void)hipFree(t->d_pnp);
     t->blk.release();
-    t->d_work = t->d_out = t->p_out = nullptr;
+    t->d_work = t->d_out = t->p_out = t->d_pnp = nullptr;
 }
 
 int allocate(visfs_tracker* t) {
@@ -741,12 +811,12 @@ int allocate(visfs_tracker* t) {
     int32_t* hw = nullptr;
     const size_t H = t->cull_on ? (size_t)t->cull.iterations : 0;
     const size_t work_bytes = carve_work(nullptr, M, t->hw.size(), H, B, &hw);
-    t->out_bytes = carve_out(nullptr, M, B.o);
+    t->out_bytes = t->out_base_bytes = carve_out(nullptr, M, false, B.o);
     if (!f->device) {
         t->h_work.assign(work_bytes, 0); t->h_outblk.assign(t->out_bytes, 0);
         t->h_inblk.assign(sizeof(InHead) + sizeof(uint64_t) * kMaxOutliers, 0);
         carve_work(t->h_work.data(), M, t->hw.size(), H, B, &hw);
-        carve_out(t->h_outblk.data(), M, B.o);
+        carve_out(t->h_outblk.data(), M, false, B.o);
         std::memcpy(hw, t->hw.data(), t->hw.size() * sizeof(int32_t));
         B.in = reinterpret_cast<const InHead*>(t->h_inblk.data());
         B.outliers = reinterpret_cast<const uint64_t*>(t->h_inblk.data() + sizeof(InHead));
@@ -759,8 +829,8 @@ int allocate(visfs_tracker* t) {
     TK_HIP(t, hipHostMalloc(reinterpret_cast<void**>(&t->p_out), t->out_bytes, hipHostMallocDefault));
     TK_HIP(t, t->blk.allocate(1));
     carve_work(t->d_work, M, t->hw.size(), H, B, &hw);
-    carve_out(t->d_out, M, B.o);
-    carve_out(t->p_out, M, t->R);              // (B.in and B.outliers of a call point into the block the call goes through)
+    carve_out(t->d_out, M, false, B.o);
+    carve_out(t->p_out, M, false, t->R);              // (B.in and B.outliers of a call point into the block the call goes through)
     std::memset(t->p_out, 0, t->out_bytes);
     TK_HIP(t, hipMemsetAsync(t->d_work, 0, work_bytes, f->stream));
     TK_HIP(t, hipMemsetAsync(t->d_out, 0, t->out_bytes, f->stream));
@@ -808,6 +878,7 @@ void host_pretreat(visfs_tracker* t) {
     c->n_kept = 0; c->lost = 0; c->n_list = 0; c->n_new = 0; c->n_rows = 0;
     c->corner_args[0] = c->corner_args[1] = 0;
     c->cull_m = 0;
+    c->pnp_m = 0;
 }
 
 Image host_image(const visfs_flow* f, int slot, int image) { return Image{ f->hpx[slot][image].data(), f->hder[slot][image].data() }; }
@@ -1011,6 +1082,72 @@ int take_result(visfs_tracker* t, bool boot, visfs_tracker_result* result) {
     return VISFS_BA_OK;
 }
 
+// ---------------------------------------------------------------- the pose guess behind a call (include/visfs_tracker_pnp.h)
+void pnp_clear(visfs_tracker* t, int ran) {
+    visfs_tracker_pnp_result& r = t->pnp_res;
+    r.ran = ran; r.n_matches = 0; r.n_inliers = 0; r.pad = 0;
+    r.matches = t->pnp_matches.data(); r.inliers = t->pnp_inliers.data();
+    for (int i = 0; i < 16; ++i) r.T[i] = 0.0;
+    for (int i = 0; i < 36; ++i) r.cov[i] = (i % 7 == 0) ? 1.0 : 0.0;
+    t->pnp_last_m = t->pnp_last_hyp = t->pnp_last_passes = 0;
+    t->pnp_model = pnp::Result{};
+    t->pnp_model.winner = -1;
+}
+
+// The result of the pose guess from the output block of a finished call (take_result has checked its counts).  to_xyz is matched by
+// id from the call's words, as visfs_amd/host/MotionEstimator.h builds it from its maps; the transform and the covariance are the
+// host's in both flavours (pnp::finalize).  A host-twin tracker runs the staged host solver on the rows.
+int pnp_finish(visfs_tracker* t) {
+    pnp_clear(t, 1);
+    visfs_tracker_pnp_result& r = t->pnp_res;
+    const Out& o = t->R;
+    const Head hd = *o.head;
+    const int32_t n = hd.n_covis;
+    const float* to_xyz = nullptr;
+    if (hd.n_words > 0) {                                              // MultiviewGeometry.cpp:160 tests _words3dTo.size()
+        t->pnp_index.clear();
+        for (int32_t k = 0; k < hd.n_words; ++k) t->pnp_index.emplace(o.w_id[k], k);
+        for (int32_t i = 0; i < n; ++i) {
+            const auto it = t->pnp_index.find(o.cov_id[i]);
+            for (int k = 0; k < 3; ++k)
+                t->pnp_to_xyz[3 * (size_t)i + k] = it == t->pnp_index.end() ? __builtin_nanf("") : o.w_xyz[3 * (size_t)it->second + k];
+        }
+        to_xyz = t->pnp_to_xyz.data();
+    }
+    if (!t->f->device) {
+        const int rc = visfs_pnp_solve(t->pnp_host, &t->pnp_prm, &t->pnp_cam, n, o.cov_xyz, o.cov_to, to_xyz, r.T, r.cov, t->pnp_matches.data(),
+                                       &r.n_matches, t->pnp_inliers.data(), &r.n_inliers);
+        if (rc != VISFS_BA_OK) { pnp_clear(t, 0); return fail(t, rc, std::string("the pose guess: ") + visfs_pnp_last_error(t->pnp_host)); }
+        return VISFS_BA_OK;
+    }
+    const int32_t m = *o.p_m;
+    const pnp::Result res = *o.p_res;
+    const int32_t min_inliers = t->pnp_shape.min_inliers;
+    bool sane = m >= 0 && m <= n;
+    for (int32_t k = 0; sane && k < m; ++k) sane = o.p_match[k] >= 0 && o.p_match[k] < n;
+    const bool searched = sane && m >= min_inliers;
+    if (searched) sane = res.n_inliers >= 0 && res.n_inliers <= m && res.n_passes >= 0 && res.n_passes <= pnp::kMaxRefine;
+    for (int32_t k = 0; sane && searched && k < res.n_inliers; ++k) sane = o.p_inl[k] >= 0 && o.p_inl[k] < m;
+    if (!sane) { pnp_clear(t, 0); return fail(t, VISFS_BA_ERR_DEVICE, "the pose guess returned an impossible count or row number"); }
+    std::copy(o.p_match, o.p_match + m, t->pnp_matches.begin());
+    r.n_matches = m;
+    t->pnp_last_m = m;
+    if (!searched) return VISFS_BA_OK;
+    t->pnp_last_hyp = t->pnp_shape.iterations; t->pnp_last_passes = res.n_passes;
+    t->pnp_model = res;
+    if (res.n_inliers < min_inliers) return VISFS_BA_OK;
+    for (int32_t k = 0; k < m; ++k) {
+        const size_t i = (size_t)o.p_match[k];
+        t->pnp_rows[(size_t)k] = pnp::Row{ o.cov_xyz[3 * i], o.cov_xyz[3 * i + 1], o.cov_xyz[3 * i + 2], o.cov_to[2 * i], o.cov_to[2 * i + 1] };
+    }
+    std::copy(o.p_inl, o.p_inl + res.n_inliers, t->pnp_list.begin());
+    const pnp::Cam K{ t->pnp_cam.fx, t->pnp_cam.fy, t->pnp_cam.cx, t->pnp_cam.cy };
+    pnp::finalize(res, t->pnp_rows.data(), t->pnp_cam.Tir, K, t->pnp_list.data(), (size_t)res.n_inliers, t->pnp_matches.data(), to_xyz, r.T, r.cov);
+    r.n_inliers = res.n_inliers;
+    for (int32_t k = 0; k < res.n_inliers; ++k) t->pnp_inliers[(size_t)k] = t->pnp_matches[(size_t)t->pnp_list[(size_t)k]];
+    return VISFS_BA_OK;
+}
+
 struct MemberPlan {                            // what the host decides for a member before anything is pushed
     bool no_previous, boot, has_guess;
     int32_t from_bound;                        // rows the tracking launch must cover
@@ -1047,12 +1184,16 @@ int commit_member(visfs_tracker* t, const MemberPlan& P, visfs_tracker_result* r
         ++f->frames;
     }
     t->seen_frames = f->frames;
+    t->called = true;
+    pnp_clear(t, 0);
     if (P.no_previous) {
         clear_result(t, result, kNoPrevious, 0);
         t->have_call = false;
         return VISFS_BA_OK;
     }
-    return take_result(t, P.boot, result);
+    const int rc = take_result(t, P.boot, result);
+    if (rc != VISFS_BA_OK || !t->pnp_on) return rc;
+    return pnp_finish(t);
 }
 
 // ---------------------------------------------------------------- device: the launches of a call
@@ -1072,7 +1213,7 @@ int run_call(visfs_tracker* const* m, int n, const visfs_tracker_frame* fr, cons
     visfs_tracker* t0 = m[0];
     visfs_flow* f0 = t0->f;
     const Shape S = t0->S;
-    const bool clahe_on = t0->prm.clahe != 0, back = f0->prm.flow_back != 0, cull_on = t0->cull_on;
+    const bool clahe_on = t0->prm.clahe != 0, back = f0->prm.flow_back != 0, cull_on = t0->cull_on, pnp_on = t0->pnp_on;
     const clahe::Geom geom = clahe_on ? clahe::make_geom(f0->w, f0->h, t0->prm.clahe_params.tiles_x, t0->prm.clahe_params.tiles_y,
                                                          t0->prm.clahe_params.clip_limit)
                                       : clahe::Geom{};
@@ -1087,6 +1228,7 @@ int run_call(visfs_tracker* const* m, int n, const visfs_tracker_frame* fr, cons
     CornerRec* ctop = reinterpret_cast<CornerRec*>(blk.pinned + blk.off_top);
     TrkRec* trk = reinterpret_cast<TrkRec*>(blk.pinned + blk.off_trk);
     fund::CullRec* cull = reinterpret_cast<fund::CullRec*>(blk.pinned + blk.off_cull);
+    pnp::PnpRec* pnr = reinterpret_cast<pnp::PnpRec*>(blk.pinned + blk.off_pnp);
     InHead* inh = reinterpret_cast<InHead*>(blk.pinned + blk.off_in);
     uint64_t* ids = reinterpret_cast<uint64_t*>(blk.pinned + blk.off_ids);
     size_t n_ids = 0;
@@ -1124,6 +1266,8 @@ int run_call(visfs_tracker* const* m, int n, const visfs_tracker_frame* fr, cons
         r.has_guess = P.has_guess ? 1 : 0; r.skip = skip ? 1 : 0; r.boot = P.boot ? 1 : 0; r.pad = 0;
         cull[i] = t->B.cull;
         cull[i].skip = skip ? 1 : 0;
+        pnr[i] = t->pnp_rec;
+        pnr[i].skip = skip ? 1 : 0;
         // both extractions of a member work in the same state, one behind the other in stream order
         group_corners_fill(f, f->dpx[prev][0], nullptr, nullptr, t->B.ctl->boot_args, skip || !P.boot, &cboot[i], &r.corner_n, &r.corner_xy);
         group_corners_fill(f, f->dpx[cur][0], t->B.raster, t->B.hw, t->B.ctl->corner_args, skip, &ctop[i], &r.corner_n, &r.corner_xy);
@@ -1173,6 +1317,11 @@ int run_call(visfs_tracker* const* m, int n, const visfs_tracker_frame* fr, cons
             if (rc != VISFS_BA_OK) return blame(rc, -1, "a launch of the fundamental-matrix cull failed");
         }
         RC_LAUNCH(k_trk_reduce_g, one, wg, d_trk, S);
+        if (pnp_on) {                                                  // the covisible rows exist; nothing behind this reads what it writes
+            RC_LAUNCH(k_trk_pnp_rows_g, one, wg, d_trk, S);
+            rc = pnp::group_pnp(stream, n, reinterpret_cast<const pnp::PnpRec*>(dev(blk.off_pnp)), t0->pnp_shape, &cnt);
+            if (rc != VISFS_BA_OK) return blame(rc, -1, "a launch of the pose guess failed");
+        }
         RC_LAUNCH(k_trk_discs_g, one, wg, d_trk, S);
         rc = group_corners(f0, quality, min_distance, n, reinterpret_cast<const CornerRec*>(dev(blk.off_top)), &cnt);
         if (rc != VISFS_BA_OK) return blame(rc, -1, f0->err);
@@ -1184,7 +1333,7 @@ int run_call(visfs_tracker* const* m, int n, const visfs_tracker_frame* fr, cons
         for (int i = 0; i < n; ++i) {
             if (plan[i].no_previous) continue;
             visfs_tracker* t = m[i];
-            RC_HIP(hipMemcpyAsync(t->p_out, t->d_out, t->out_bytes, hipMemcpyDeviceToHost, stream));
+            RC_HIP(hipMemcpyAsync(t->p_out, t->d_out, pnp_on ? t->out_bytes : t->out_base_bytes, hipMemcpyDeviceToHost, stream));
             ++cnt.copies;
         }
     }
@@ -1271,6 +1420,7 @@ void visfs_tracker_destroy(visfs_tracker* t) {
     if (!t) return;
     leave_group(t);
     detach(t);
+    if (t->pnp_host) visfs_pnp_destroy(t->pnp_host);
     delete t;
 }
 
@@ -1422,6 +1572,158 @@ int visfs_tracker_download_cull(const visfs_tracker* ct, int32_t* applied, int32
     });
 }
 
+// ---------------------------------------------------------------- the pose guess (include/visfs_tracker_pnp.h)
+int visfs_tracker_pnp_abi_version(void) { return VISFS_TRACKER_PNP_ABI_VERSION; }
+
+int visfs_tracker_enable_pnp(visfs_tracker* t, const visfs_pnp_params* p) {
+    if (!t) return VISFS_BA_ERR_BAD_ARGUMENT;
+    return guarded_tk(t, [&]() -> int {
+        visfs_flow* f = t->f;
+        if (!f) return fail(t, VISFS_BA_ERR_NOT_LOADED, "the flow object of this tracker is gone");
+        if (t->group) return fail(t, VISFS_BA_ERR_BAD_ARGUMENT, "the tracker is in a group: set the pose guess first, then create the group");
+        if (!p) { t->pnp_on = false; return (int)VISFS_BA_OK; }
+        visfs_pnp_camera cam;
+        cam.fx = (double)t->cam.fx; cam.fy = (double)t->cam.fy; cam.cx = (double)t->cam.cx; cam.cy = (double)t->cam.cy;
+        for (int i = 0; i < 12; ++i) cam.Tir[i] = t->cam.Tir[i];
+        const char* why = "";
+        const int rc = pnp::check_params(*p, cam, &why);
+        if (rc != VISFS_BA_OK) return fail(t, rc, why);
+        const size_t M = (size_t)t->S.M, H = (size_t)p->iterations;
+        t->pnp_matches.assign(M, 0); t->pnp_inliers.assign(M, 0); t->pnp_list.assign(M, 0);
+        t->pnp_to_xyz.assign(3 * M, 0.0f); t->pnp_rows.assign(M, pnp::Row{});
+        t->pnp_index.reserve(M);
+        pnp_clear(t, 0);                                               // (the arrays of the result before have moved)
+        if (!f->device) {
+            if (!t->pnp_host) {
+                const int rc_h = visfs_pnp_create_host(t->S.M, &t->pnp_host);
+                if (rc_h != VISFS_BA_OK) return fail(t, rc_h, "the host solver of the pose guess could not be created");
+            }
+        } else {
+            TK_HIP(t, hipSetDevice(f->dev));
+            TK_HIP(t, hipStreamSynchronize(f->stream));                // nothing reads the blocks that go
+            t->pnp_on = false;
+            // the state of the two stages; then the output block again, with the pose guess's part behind what it holds today
+            Carver c{ nullptr };
+            const auto carve = [&](Carver& k, pnp::PnpRec& q, Bufs& b) {
+                b.pnp_key = k.take<unsigned long long>(1); b.pnp_rows = k.take<pnp::Row>(M);
+                q.models = k.take<double>(12 * H); q.pass_tq = k.take<double>(7 * pnp::kMaxRefine);
+                q.samples = k.take<int32_t>(4 * H); q.vc = k.take<int32_t>(2 * H);
+                q.pass_thr = k.take<float>(pnp::kMaxRefine); q.pass_cnt = k.take<int32_t>(pnp::kMaxRefine);
+                q.pass_lists = k.take<int32_t>((size_t)pnp::kMaxRefine * M);
+                return (k.off + 255) & ~size_t(255);
+            };
+            pnp::PnpRec q{};
+            Bufs scratch{};
+            const size_t state_bytes = carve(c, q, scratch);
+            Out sized{};
+            const size_t out_bytes = carve_out(nullptr, M, true, sized);
+            char *d_pnp = nullptr, *d_out = nullptr, *p_out = nullptr;
+            hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_pnp), state_bytes);
+            if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_out), out_bytes);
+            if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&p_out), out_bytes, hipHostMallocDefault);
+            if (e == hipSuccess) e = hipMemsetAsync(d_pnp, 0, state_bytes, f->stream);
+            if (e == hipSuccess) e = hipMemsetAsync(d_out, 0, out_bytes, f->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(f->stream);
+            if (e != hipSuccess) {
+                if (d_pnp) (void)hipFree(d_pnp);
+                if (d_out) (void)hipFree(d_out);
+                if (p_out) (void)hipHostFree(p_out);
+                return fail(t, VISFS_BA_ERR_DEVICE, std::string("the buffers of the pose guess: ") + hipGetErrorString(e));
+            }
+            std::memset(p_out, 0, out_bytes);
+            if (t->d_pnp) (void)hipFree(t->d_pnp);
+            (void)hipFree(t->d_out);
+            (void)hipHostFree(t->p_out);
+            t->d_pnp = d_pnp; t->d_out = d_out; t->p_out = p_out; t->out_bytes = out_bytes;
+            Carver k{ d_pnp };
+            carve(k, q, t->B);
+            carve_out(d_out, M, true, t->B.o);
+            carve_out(p_out, M, true, t->R);
+            q.m = &t->B.ctl->pnp_m; q.rows = t->B.pnp_rows; q.key = t->B.pnp_key;
+            q.res = t->B.o.p_res; q.inliers = t->B.o.p_inl;
+            q.K = pnp::Cam{ cam.fx, cam.fy, cam.cx, cam.cy };
+            q.cap = t->S.M; q.skip = 0;
+            t->pnp_rec = q;
+            t->have_call = false;                                      // (the hooks' arrays of the call before are gone with the block)
+        }
+        t->pnp_prm = *p; t->pnp_cam = cam;
+        t->pnp_shape = pnp::PnpShape{ p->iterations, p->min_inliers < 4 ? 4 : p->min_inliers, p->refine_iterations, p->reproj_error,
+                                      p->refine_sigma, p->seed };
+        t->pnp_on = true;
+        return (int)VISFS_BA_OK;
+    });
+}
+
+int visfs_tracker_pnp_last(const visfs_tracker* t, visfs_tracker_pnp_result* out) {
+    if (!t || !out) return VISFS_BA_ERR_BAD_ARGUMENT;
+    if (!t->called) return VISFS_BA_ERR_NOT_LOADED;
+    *out = t->pnp_res;
+    return VISFS_BA_OK;
+}
+
+int visfs_tracker_download_pnp(const visfs_tracker* ct, int32_t* m, int32_t* n_hypotheses, int32_t* n_passes, int32_t* samples,
+                               int32_t* valid, double* models, int32_t* counts, int32_t* winner, double* refit_tq, double* pass_tq,
+                               float* pass_threshold, int32_t* pass_count, int32_t* pass_inliers) {
+    visfs_tracker* t = const_cast<visfs_tracker*>(ct);
+    if (!t) return VISFS_BA_ERR_BAD_ARGUMENT;
+    return guarded_tk(t, [&]() -> int {
+        if (!t->f) return fail(t, VISFS_BA_ERR_NOT_LOADED, "the flow object of this tracker is gone");
+        if (!t->have_call) return fail(t, VISFS_BA_ERR_NOT_LOADED, "no call to report on");
+        if (m) *m = 0;
+        if (n_hypotheses) *n_hypotheses = 0;
+        if (n_passes) *n_passes = 0;
+        if (winner) *winner = -1;
+        if (refit_tq) for (int i = 0; i < 7; ++i) refit_tq[i] = 0.0;
+        if (!t->pnp_on || !t->pnp_res.ran) return (int)VISFS_BA_OK;
+        visfs_flow* f = t->f;
+        if (!f->device) {
+            int rc = visfs_pnp_last_sizes(t->pnp_host, m, n_hypotheses, n_passes);
+            if (rc == VISFS_BA_OK)
+                rc = visfs_pnp_download(t->pnp_host, samples, valid, models, counts, winner, refit_tq, pass_tq, pass_threshold, pass_count,
+                                        pass_inliers);
+            if (rc != VISFS_BA_OK) return fail(t, rc, visfs_pnp_last_error(t->pnp_host));
+            return (int)VISFS_BA_OK;
+        }
+        const size_t H = (size_t)t->pnp_last_hyp, R = (size_t)t->pnp_last_passes, rows = (size_t)t->pnp_last_m, cap = (size_t)t->S.M;
+        if (m) *m = t->pnp_last_m;
+        if (n_hypotheses) *n_hypotheses = t->pnp_last_hyp;
+        if (n_passes) *n_passes = t->pnp_last_passes;
+        if (winner) *winner = t->pnp_model.winner;
+        if (refit_tq) for (int i = 0; i < 7; ++i) refit_tq[i] = t->pnp_model.refit0[i];
+        if (H == 0) return (int)VISFS_BA_OK;
+        const pnp::PnpRec& q = t->pnp_rec;
+        std::vector<int32_t> h_samples(4 * H), h_vc(2 * H), h_pcnt(pnp::kMaxRefine), h_plists(R * cap);
+        std::vector<double> h_models(12 * H), h_ptq(7 * pnp::kMaxRefine);
+        std::vector<float> h_pthr(pnp::kMaxRefine);
+        TK_HIP(t, hipSetDevice(f->dev));
+        TK_HIP(t, hipMemcpyAsync(h_samples.data(), q.samples, 16 * H, hipMemcpyDeviceToHost, f->stream));
+        TK_HIP(t, hipMemcpyAsync(h_vc.data(), q.vc, 8 * H, hipMemcpyDeviceToHost, f->stream));
+        TK_HIP(t, hipMemcpyAsync(h_models.data(), q.models, 96 * H, hipMemcpyDeviceToHost, f->stream));
+        if (R > 0) {
+            TK_HIP(t, hipMemcpyAsync(h_ptq.data(), q.pass_tq, 56 * R, hipMemcpyDeviceToHost, f->stream));
+            TK_HIP(t, hipMemcpyAsync(h_pthr.data(), q.pass_thr, 4 * R, hipMemcpyDeviceToHost, f->stream));
+            TK_HIP(t, hipMemcpyAsync(h_pcnt.data(), q.pass_cnt, 4 * R, hipMemcpyDeviceToHost, f->stream));
+            TK_HIP(t, hipMemcpyAsync(h_plists.data(), q.pass_lists, 4 * R * cap, hipMemcpyDeviceToHost, f->stream));
+        }
+        TK_HIP(t, hipStreamSynchronize(f->stream));
+        for (size_t h = 0; h < H; ++h) {
+            if (samples) for (int k = 0; k < 4; ++k) samples[4 * h + k] = h_samples[4 * h + k];
+            if (valid) valid[h] = h_vc[2 * h];
+            if (counts) counts[h] = h_vc[2 * h + 1];
+            if (models) for (int k = 0; k < 12; ++k) models[12 * h + k] = h_models[12 * h + k];
+        }
+        for (size_t k = 0; k < R; ++k) {
+            if (pass_tq) for (int i = 0; i < 7; ++i) pass_tq[7 * k + i] = h_ptq[7 * k + i];
+            if (pass_threshold) pass_threshold[k] = h_pthr[k];
+            if (pass_count) pass_count[k] = h_pcnt[k];
+            const size_t cnt_k = (size_t)std::min(std::max(h_pcnt[k], 0), t->pnp_last_m);
+            if (pass_inliers)
+                for (size_t i = 0; i < rows; ++i) pass_inliers[k * rows + i] = i < cnt_k ? h_plists[k * cap + i] : -1;
+        }
+        return (int)VISFS_BA_OK;
+    });
+}
+
 }  // extern "C"
 
 // ====================================================================== tracker groups (include/visfs_tracker_group.h)
@@ -1450,6 +1752,14 @@ bool same_tracker_params(const visfs_tracker_params& a, const visfs_tracker_para
            a.clahe_params.tiles_x == b.clahe_params.tiles_x && a.clahe_params.tiles_y == b.clahe_params.tiles_y &&
            (a.cull != 0) == (b.cull != 0) && a.cull_params.pixel_error == b.cull_params.pixel_error &&
            a.cull_params.iterations == b.cull_params.iterations && a.cull_params.seed == b.cull_params.seed;
+}
+
+bool same_pnp(const visfs_tracker* a, const visfs_tracker* b) {
+    if (a->pnp_on != b->pnp_on) return false;
+    if (!a->pnp_on) return true;
+    const visfs_pnp_params &p = a->pnp_prm, &q = b->pnp_prm;
+    return p.min_inliers == q.min_inliers && p.iterations == q.iterations && p.reproj_error == q.reproj_error &&
+           p.refine_iterations == q.refine_iterations && p.refine_sigma == q.refine_sigma && p.seed == q.seed;
 }
 
 void free_group(visfs_tracker_group* g) {
@@ -1484,6 +1794,7 @@ int visfs_tracker_group_create(int32_t n, visfs_tracker* const* members, visfs_t
             if (f->w != f0->w || f->h != f0->h) return refuse(VISFS_BA_ERR_BAD_ARGUMENT, i, "the image size differs from member 0's");
             if (!same_flow_params(f->prm, f0->prm)) return refuse(VISFS_BA_ERR_BAD_ARGUMENT, i, "the flow parameters differ from member 0's");
             if (!same_tracker_params(t->prm, members[0]->prm)) return refuse(VISFS_BA_ERR_BAD_ARGUMENT, i, "the tracker parameters differ from member 0's");
+            if (!same_pnp(t, members[0])) return refuse(VISFS_BA_ERR_BAD_ARGUMENT, i, "the pose guess setting differs from member 0's");
         }
         visfs_tracker_group* g = new visfs_tracker_group();
         g->m.assign(members, members + n);

@@ -5,11 +5,16 @@
 // in the library; this class turns the arrays of a call into the std::maps the Signature setters take (ascending id, as uKeys and
 // uValues read them) and keeps the one test that belongs to the caller's types: getDeltaPoseGuess().isApprox(Identity) (:237).
 //
+// enablePnP() puts VISFS::estimateMotion3DTo2D (MultiviewGeometry.cpp:94-216) into the same call (include/visfs_tracker_pnp.h):
+// poseGuess() then hands out the transform, the covariance and the match and inlier ids of the last imageProcess, with the row
+// numbers turned into ids as MotionEstimator.h does.
+//
 // VISFS::ResidentTrackerGroup runs the imageProcess of several ResidentTrackers (a rig's cameras) in one call of
 // include/visfs_tracker_group.h.
 #ifndef VISFS_AMD_RESIDENT_TRACKER_H
 #define VISFS_AMD_RESIDENT_TRACKER_H
 
+#include <array>
 #include <cstddef>
 #include <cstdint>
 #include <map>
@@ -20,6 +25,7 @@
 
 #include "visfs_tracker.h"
 #include "visfs_tracker_group.h"
+#include "visfs_tracker_pnp.h"
 
 namespace VISFS {
 
@@ -41,6 +47,14 @@ public:
         std::map<std::size_t, int> trackCount;                      // trackCnt_ after updateTrackCounter
         std::set<std::size_t> blockedWords;                         // keys of setBlockedWords
         std::size_t nextFeatureId = 0;                              // globalFeatureId_
+    };
+
+    // What estimateMotion3DTo2D returns: `transform` all zero is the reference's null transform (Estimator.cpp:209).
+    struct PoseGuess {
+        bool ran = false;                                           // false: enablePnP() is not in force, or the frame had no previous one
+        std::array<double, 16> transform{};                         // 4 x 4 row-major
+        std::array<double, 36> covariance{};                        // 6 x 6 row-major
+        std::vector<std::size_t> matches, inliers;                  // word ids
     };
 
     ResidentTracker(const ResidentTracker&) = delete;
@@ -91,6 +105,35 @@ public:
         out = Frame();
         if (rc != VISFS_BA_OK) return rc;
         fill(r, out);
+        remember(r);
+        return rc;
+    }
+
+    // Estimator/MinInliers, Estimator/PnPIterations, Estimator/PnPReprojError and Estimator/RefineIterations as the reference names
+    // them: from the next imageProcess on the pose guess runs inside it.  Call it before the tracker joins a ResidentTrackerGroup,
+    // with the same values on every member.
+    void enablePnP(int minInliers = 12, int iterations = 50, double reProjError = 2.0, int refineIterations = 5, uint64_t seed = 0) {
+        visfs_pnp_params p;
+        visfs_pnp_default_params(&p);
+        p.min_inliers = minInliers; p.iterations = iterations; p.reproj_error = (float)reProjError; p.refine_iterations = refineIterations;
+        p.seed = seed;
+        const int rc = visfs_tracker_enable_pnp(t_, &p);
+        if (rc != VISFS_BA_OK)
+            throw std::runtime_error("visfs_tracker_enable_pnp failed with status " + std::to_string(rc) + ": " + visfs_tracker_last_error(t_));
+    }
+    int disablePnP() { return visfs_tracker_enable_pnp(t_, nullptr); }
+
+    // The pose guess of the last imageProcess (of this tracker or of its group).  Nothing is issued to the device.
+    int poseGuess(PoseGuess& out) const {
+        out = PoseGuess();
+        visfs_tracker_pnp_result r;
+        const int rc = visfs_tracker_pnp_last(t_, &r);
+        if (rc != VISFS_BA_OK) return rc;
+        out.ran = r.ran != 0;
+        for (int i = 0; i < 16; ++i) out.transform[(std::size_t)i] = r.T[i];
+        for (int i = 0; i < 36; ++i) out.covariance[(std::size_t)i] = r.cov[i];
+        for (int32_t i = 0; i < r.n_matches; ++i) out.matches.push_back(covisibleIds_.at((std::size_t)r.matches[i]));
+        for (int32_t i = 0; i < r.n_inliers; ++i) out.inliers.push_back(covisibleIds_.at((std::size_t)r.inliers[i]));
         return rc;
     }
 
@@ -123,15 +166,19 @@ private:
         }
         for (int32_t i = 0; i < r.n_blocked; ++i) out.blockedWords.insert(out.blockedWords.end(), (std::size_t)r.blocked_id[i]);
     }
+    void remember(const visfs_tracker_result& r) {                  // the ids poseGuess() turns row numbers into
+        covisibleIds_.assign(r.covisible_id, r.covisible_id + r.n_covisible);
+    }
     static Point2f p2(const float* a, int32_t i) { return Point2f{ a[2 * i], a[2 * i + 1] }; }
     static Point3f p3(const float* a, int32_t i) { return Point3f{ a[3 * i], a[3 * i + 1], a[3 * i + 2] }; }
     visfs_tracker* t_ = nullptr;
     std::vector<std::size_t> outliers_;
+    std::vector<std::size_t> covisibleIds_;
 };
 
 // Tracker::imageProcess of every camera of a rig in one call.  The members are ResidentTrackers on flow objects of their own (all of
 // one handle, or all host twins) with equal keys (cullByFundationMatrix and fundationPixelError among them: the cull of every member
-// runs inside the one call) and image size; they must outlive the group and stay usable on their own.
+// runs inside the one call; enablePnP and its values too: a group takes its members' setting) and image size; they must outlive the group and stay usable on their own.
 class ResidentTrackerGroup {
 public:
     struct Input {
@@ -172,6 +219,7 @@ public:
         for (std::size_t i = 0; i < n; ++i) {
             members_[i]->outliers_.clear();
             ResidentTracker::fill(res[i], out[i]);
+            members_[i]->remember(res[i]);
         }
         return rc;
     }
