@@ -11,6 +11,7 @@
 //       k_submap_crop   Submap2D::finish: the known box, value -> probability -> value (a table built on the host)
 // A cell changes at most once per insertion and a hit wins over a miss: exactly the reference's update markers, in one pass.
 #include "ba_submap.hpp"
+#include "ba_submap_access.hpp"
 #include "../../include/visfs_submap.h"
 
 #include <algorithm>
@@ -294,6 +295,10 @@ struct visfs_submaps {
     MarkRec* h_recs = nullptr; size_t h_recs_cap = 0;
     MarkRec* d_recs = nullptr; size_t d_recs_cap = 0;
     bool recs_in_flight = false;
+
+    // the scan matcher's state (ba_scan.hip), freed with the sub-maps
+    void* scan_state = nullptr;
+    void (*scan_destroy)(void*) = nullptr;
 };
 
 namespace {
@@ -633,6 +638,11 @@ int visfs_submaps_create(visfs_ba_handle* h, const visfs_submap_params* p, visfs
 
 void visfs_submaps_destroy(visfs_submaps* s) {
     if (!s) return;
+    if (s->scan_state && s->scan_destroy) {
+        if (s->device) { (void)hipSetDevice(s->dev); if (s->stream) (void)hipStreamSynchronize(s->stream); }
+        s->scan_destroy(s->scan_state);
+        s->scan_state = nullptr;
+    }
     release(s);
     delete s;
 }
@@ -768,3 +778,33 @@ int visfs_submap_hook_crop(int32_t nx, int32_t ny, const uint16_t* cells, const 
 }
 
 }  // extern "C"
+
+// ====================================================================== what the scan matcher (ba_scan.hip) reads
+int visfs_internal_scan_access(visfs_submaps* s, int32_t index, submap::ScanAccess* a) {
+    *a = submap::ScanAccess();
+    a->device = s->device; a->dev = s->dev; a->stream = s->stream;
+    if (s->device) {
+        SM_HIP(s, hipSetDevice(s->dev));
+        const int rc = flush_batch(s);
+        if (rc != VISFS_BA_OK) return rc;
+        a->count = (int32_t)s->dsubs.size();
+        if (index < 0 || index >= a->count) return VISFS_BA_OK;
+        const visfs_submaps::DSub& d = s->dsubs[index];
+        a->L = d.L;
+        a->grid.cells = d.cells; a->grid.nx = d.La.nx; a->grid.ny = d.La.ny; a->grid.ox = d.gx; a->grid.oy = d.gy;
+        return VISFS_BA_OK;
+    }
+    a->count = (int32_t)s->hsubs.size();
+    if (index < 0 || index >= a->count) return VISFS_BA_OK;
+    const HostGrid& g = s->hsubs[index].g;
+    a->L = g.L;
+    a->grid.cells = g.cells.data(); a->grid.nx = g.L.nx; a->grid.ny = g.L.ny;
+    return VISFS_BA_OK;
+}
+
+int visfs_internal_scan_fail(visfs_submaps* s, int rc, const char* why) { return fail(s, rc, why); }
+
+void** visfs_internal_scan_slot(visfs_submaps* s, void (*destroy)(void*)) {
+    s->scan_destroy = destroy;
+    return &s->scan_state;
+}

@@ -4,7 +4,8 @@
 // It keeps what LocalMap uses of the reference class: the constructor taking the LocalMap/* keys, insertion of a frame's range data
 // at its pose (LocalMap::insertMatchingSubMap2d, LocalMap.cpp:355-360), whether a matching sub-map exists (hasMatchingSubmap2D) and
 // the BA against it (Estimator.cpp:247-250 + Optimizer::localOptimize).  The grids stay on the device: there is no Submap2D object to
-// hand out; download() copies one to the host for those who want grid2Image.
+// hand out; download() copies one to the host for those who want grid2Image.  match() is the correlative scan match that
+// Estimator::laserPretreatment names and leaves out (include/visfs_scan_match.h): it corrects a pose guess against a sub-map.
 #ifndef VISFS_AMD_ACTIVE_SUBMAPS_2D_H
 #define VISFS_AMD_ACTIVE_SUBMAPS_2D_H
 
@@ -13,6 +14,7 @@
 #include <string>
 #include <vector>
 
+#include "visfs_scan_match.h"
 #include "visfs_submap.h"
 
 namespace VISFS {
@@ -68,6 +70,21 @@ public:
 
     // Estimator.cpp:247-250 + localOptimize: the window's laser factor reads getMatchingSubmap2D() in device memory
     int solveWindow(const visfs_ba_window* w, visfs_ba_result* r) const { return visfs_submaps_solve_window(ba_, s_, w, r); }
+
+    // The pose guess (x, y, yaw) corrected by the correlative scan match of the returns (robot frame, xyz triples) against sub-map
+    // `index` (0: the matching sub-map).  Before the first insertion, or without returns, the guess comes back with matched = false.
+    struct Match { double x = 0.0, y = 0.0, yaw = 0.0, score = 0.0; bool matched = false; };
+    int match(const double guess[3], const std::vector<double>& returns, Match* out, const visfs_scan_match_params* params = nullptr,
+              int index = 0, visfs_scan_match_result* full = nullptr) const {
+        visfs_scan_match_params p;
+        if (params) p = *params; else visfs_scan_match_default_params(&p);
+        visfs_scan_match_result r;
+        const int rc = visfs_scan_match(s_, index, &p, guess, (int32_t)(returns.size() / 3), returns.data(), &r);
+        if (rc != VISFS_BA_OK) return rc;
+        if (out) { out->x = r.x; out->y = r.y; out->yaw = r.yaw; out->score = r.score; out->matched = r.matched != 0; }
+        if (full) *full = r;
+        return rc;
+    }
 
     // one sub-map's cells and float costs on the host ([num_y_cells][num_x_cells])
     int download(int index, std::vector<uint16_t>* cells, std::vector<float>* cost) const {
