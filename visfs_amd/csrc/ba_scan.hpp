@@ -83,30 +83,44 @@ struct Plan {
 
 // Returns VISFS_BA_OK, VISFS_BA_ERR_UNSUPPORTED when the search exceeds a limit, or VISFS_BA_ERR_BAD_ARGUMENT when the weights make a
 // candidate's weight NaN (`why` says which).  Arguments already checked finite.
-inline int make_plan(const submap::Limits& L, const visfs_scan_match_params& p, const double g[3], int32_t n, const double* xyz, Plan& P,
-                     const char** why) {
-    P.L = L; P.gx = g[0]; P.gy = g[1]; P.gyaw = g[2]; P.n = n;
-    const double res = L.res;
+// The two halves of a plan that the branch-and-bound matcher (ba_scan_fast.hip) forms in the same way: the search's angular step and
+// its half-widths as doubles (the caller holds them to its own limits before they become integers) ...
+inline bool plan_search(double res, double linear_window, double angular_window, int32_t n, const double* xyz, double& step, double& fa,
+                        double& fl) {
     double max_range = 3.0 * res;
     for (int32_t i = 0; i < n; ++i) {
         const double px = xyz[3 * i], py = xyz[3 * i + 1];
         const double r = std::sqrt(px * px + py * py);
         if (r > max_range) max_range = r;
     }
-    if (!std::isfinite(max_range)) { *why = "the scan's range overflows"; return VISFS_BA_ERR_UNSUPPORTED; }
-    const double step = (1.0 - 1e-3) * std::acos(1.0 - (res * res) / (2.0 * (max_range * max_range)));
-    const double fa = std::ceil(p.angular_search_window / step), fl = std::ceil(p.linear_search_window / res);
+    if (!std::isfinite(max_range)) return false;
+    step = (1.0 - 1e-3) * std::acos(1.0 - (res * res) / (2.0 * (max_range * max_range)));
+    fa = std::ceil(angular_window / step); fl = std::ceil(linear_window / res);
+    return true;
+}
+
+// ... and, once P.n, P.na, P.S, P.gyaw and P.step stand, the points' x, y and the rotation table
+inline void plan_tables(const double* xyz, Plan& P) {
+    P.pts.resize(2 * (size_t)P.n);
+    for (int32_t i = 0; i < P.n; ++i) { P.pts[2 * i] = xyz[3 * i]; P.pts[2 * i + 1] = xyz[3 * i + 1]; }
+    P.rot.resize(2 * (size_t)P.S);
+    for (int32_t k = 0; k < P.S; ++k) {
+        const double a = P.gyaw + (double)(k - P.na) * P.step;
+        P.rot[2 * k] = std::cos(a); P.rot[2 * k + 1] = std::sin(a);
+    }
+}
+
+inline int make_plan(const submap::Limits& L, const visfs_scan_match_params& p, const double g[3], int32_t n, const double* xyz, Plan& P,
+                     const char** why) {
+    P.L = L; P.gx = g[0]; P.gy = g[1]; P.gyaw = g[2]; P.n = n;
+    const double res = L.res;
+    double step, fa, fl;
+    if (!plan_search(res, p.linear_search_window, p.angular_search_window, n, xyz, step, fa, fl)) { *why = "the scan's range overflows"; return VISFS_BA_ERR_UNSUPPORTED; }
     if (!(fl <= (double)VISFS_SCAN_MATCH_MAX_LINEAR)) { *why = "the linear window spans more than 32 cells"; return VISFS_BA_ERR_UNSUPPORTED; }
     if (!(2.0 * fa + 1.0 <= (double)VISFS_SCAN_MATCH_MAX_SCANS)) { *why = "the angular window holds more than 1025 rotations"; return VISFS_BA_ERR_UNSUPPORTED; }
     P.step = step; P.na = (int32_t)fa; P.nl = (int32_t)fl; P.S = 2 * P.na + 1; P.Lw = 2 * P.nl + 1;
     if (P.candidates() > (int64_t)VISFS_SCAN_MATCH_MAX_CANDIDATES) { *why = "more than 2^21 candidates"; return VISFS_BA_ERR_UNSUPPORTED; }
-    P.pts.resize(2 * (size_t)n);
-    for (int32_t i = 0; i < n; ++i) { P.pts[2 * i] = xyz[3 * i]; P.pts[2 * i + 1] = xyz[3 * i + 1]; }
-    P.rot.resize(2 * (size_t)P.S);
-    for (int32_t k = 0; k < P.S; ++k) {
-        const double a = P.gyaw + (double)(k - P.na) * step;
-        P.rot[2 * k] = std::cos(a); P.rot[2 * k + 1] = std::sin(a);
-    }
+    plan_tables(xyz, P);
     const int32_t m = P.nl + 1;
     P.weight.resize((size_t)(P.na + 1) * m * m);
     for (int32_t ka = 0; ka <= P.na; ++ka)

@@ -1,0 +1,673 @@
+// Branch-and-bound scan matching over frozen grid stacks (include/visfs_scan_fast.h).
+//
+// A stack is P_0 = scan::cell_gain of one grid and its window-maximum levels P_1 .. P_(depth-1), each stored with its low-side
+// extension (ba_scan_fast.hpp).  Building it is one launch per level:
+//   k_fast_base    P_0 from the grid's cells (through the GridView's offsets), one work item per cell;
+//   k_fast_up      P_h from P_(h-1), one work item per stored cell.
+// A match is one upload (points, rotation table), H + 5 launches on the stack's stream whatever the data, one download (the Ctrl
+// record) and one wait; nothing is read back between levels, the frontier counts live in the Ctrl record on the device:
+//   k_fast_cells   the discretised cells [S][n] (scan::discretise), and the Ctrl record zeroed;
+//   k_fast_bounds  the bound of every level-H node, one wavefront per node, lanes along the points;
+//   k_fast_seeds   one workgroup per scan: its best level-H node, then H greedy steps, its four wavefronts scoring the four
+//                  children of a step; the leaf's sum joins the incumbent B through an integer atomic maximum;
+//   k_fast_keep    the level-H nodes with U >= B appended to the frontier;
+//   k_fast_level   for h = H .. 1: a fixed grid of wavefronts strides over the frontier of level h (its length read on the
+//                  device), scores the up-to-four in-window children of a node from one pass over the scan's cells, and appends
+//                  those with U >= B to the frontier of level h - 1 through an integer atomic counter; entries beyond the capacity
+//                  are dropped and the overflow flag is raised;
+//   k_fast_best    one workgroup selects the winner among the level-0 survivors: Q descending, index ascending.
+// All sums are int32, so no reduction or append order can show in a result.  The one-core twin runs the same schedule through the
+// same functions of ba_scan_fast.hpp.
+#include "ba_scan_fast.hpp"
+
+#include <algorithm>
+#include <climits>
+#include <cstring>
+#include <new>
+#include <string>
+#include <utility>
+
+#pragma clang fp contract(off)
+
+using namespace scanfast;
+using scan::Plan;
+using submap::GridView;
+using submap::Limits;
+
+namespace scanfast {
+
+__global__ __launch_bounds__(kThreads) void k_fast_base(GridView g, int32_t nx, int64_t total, uint16_t* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= total) return;
+    const int32_t y = (int32_t)(i / nx), x = (int32_t)(i - (int64_t)y * nx);
+    out[i] = (uint16_t)scan::cell_gain(g, x, y);
+}
+
+__global__ __launch_bounds__(kThreads) void k_fast_up(LevelView lo, int32_t w, int32_t e_hi, int32_t half, int64_t total, uint16_t* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= total) return;
+    const int32_t sy = (int32_t)(i / w), sx = (int32_t)(i - (int64_t)sy * w);
+    out[i] = level_up(lo, e_hi, half, sx, sy);
+}
+
+__global__ __launch_bounds__(kThreads) void k_fast_cells(const double* __restrict__ pts, const double* __restrict__ rot, int32_t n, int64_t total,
+                                                         double gx, double gy, double res, double max_x, double max_y, int2* __restrict__ cells,
+                                                         Ctrl* __restrict__ ctrl) {
+    if (blockIdx.x == 0 && threadIdx.x < sizeof(Ctrl) / sizeof(int32_t)) reinterpret_cast<int32_t*>(ctrl)[threadIdx.x] = 0;
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= total) return;
+    const int32_t k = (int32_t)(i / n), j = (int32_t)(i - (int64_t)k * n);
+    int32_t ix, iy;
+    scan::discretise(rot[2 * k], rot[2 * k + 1], pts[2 * j], pts[2 * j + 1], gx, gy, res, max_x, max_y, ix, iy);
+    cells[i] = make_int2(ix, iy);
+}
+
+__device__ inline int32_t wave_sum(int32_t v) {
+    for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// sum over the scan's n cells of P_h(cell + (xo, yo)): every lane of the wavefront calls, every lane gets the sum
+__device__ inline int32_t wave_node_sum(const int2* __restrict__ c, int32_t n, const LevelView& v, int32_t xo, int32_t yo, int lane) {
+    int32_t q = 0;
+    for (int32_t i = lane; i < n; i += kWave) { const int2 p = c[i]; q += level_read(v, p.x + xo, p.y + yo); }
+    return wave_sum(q);
+}
+
+__global__ __launch_bounds__(kThreads) void k_fast_bounds(const int2* __restrict__ cells, int32_t n, LevelView vH, int32_t nl, int32_t H, int32_t mH,
+                                                          int32_t total, int32_t* __restrict__ bounds) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const int32_t nw = gridDim.x * kWaves;
+    for (int32_t id = blockIdx.x * kWaves + (threadIdx.x >> 6); id < total; id += nw) {
+        int32_t k, i, j;
+        node_decode(mH, id, k, i, j);
+        const int32_t U = wave_node_sum(cells + (int64_t)k * n, n, vH, -nl + (i << H), -nl + (j << H), lane);
+        if (lane == 0) bounds[id] = U;
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void k_fast_seeds(const int32_t* __restrict__ bounds, const int2* __restrict__ cells, int32_t n, Levels lv,
+                                                         int32_t nl, int32_t L, int32_t H, int32_t mH, Ctrl* __restrict__ ctrl) {
+    __shared__ int32_t s_u[kThreads];
+    __shared__ int32_t s_i[kThreads];
+    __shared__ int32_t s_c[kWaves];
+    const int t = threadIdx.x, lane = t & (kWave - 1), w = t >> 6;
+    const int32_t k = blockIdx.x, per = mH * mH;
+    int32_t u = -1, id = INT_MAX;
+    for (int32_t a = t; a < per; a += kThreads) {
+        const int32_t ua = bounds[k * per + a];
+        if (better(ua, a, u, id)) { u = ua; id = a; }
+    }
+    s_u[t] = u; s_i[t] = id;
+    for (int h = kThreads / 2; h > 0; h >>= 1) {
+        __syncthreads();
+        if (t < h && better(s_u[t + h], s_i[t + h], s_u[t], s_i[t])) { s_u[t] = s_u[t + h]; s_i[t] = s_i[t + h]; }
+    }
+    __syncthreads();
+    int32_t i = s_i[0] / mH, j = s_i[0] % mH, cur = s_u[0];
+    const int2* c = cells + (int64_t)k * n;
+    for (int32_t h = H; h >= 1; --h) {                                     // every choice: the larger bound, then the lower index
+        const int32_t m = nodes_per_axis(L, h - 1);
+        const int32_t ci = 2 * i + (w >> 1), cj = 2 * j + (w & 1);
+        int32_t U = -1;
+        if (ci < m && cj < m) U = wave_node_sum(c, n, lv.v[h - 1], -nl + (ci << (h - 1)), -nl + (cj << (h - 1)), lane);
+        if (lane == 0) s_c[w] = U;
+        __syncthreads();
+        int bw = 0;
+        for (int a = 1; a < kWaves; ++a) if (s_c[a] > s_c[bw]) bw = a;
+        cur = s_c[bw];
+        i = 2 * i + (bw >> 1); j = 2 * j + (bw & 1);
+        __syncthreads();
+    }
+    if (t == 0) atomicMax(&ctrl->B, cur);
+}
+
+__global__ __launch_bounds__(kThreads) void k_fast_keep(const int32_t* __restrict__ bounds, int32_t total, int32_t H, int2* __restrict__ out, int32_t cap,
+                                                        Ctrl* __restrict__ ctrl) {
+    const int32_t B = ctrl->B;
+    const int32_t nt = gridDim.x * kThreads;
+    if (blockIdx.x == 0 && threadIdx.x == 0) ctrl->scored[H] = total;
+    for (int32_t id = blockIdx.x * kThreads + threadIdx.x; id < total; id += nt) {
+        const int32_t U = bounds[id];
+        if (U < B) continue;
+        const int32_t slot = atomicAdd(&ctrl->kept[H], 1);
+        if (slot < cap) out[slot] = make_int2(id, U);
+        else atomicMax(&ctrl->overflow, H + 1);
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void k_fast_level(int32_t h, const int2* __restrict__ in, int2* __restrict__ out, int32_t cap,
+                                                         const int2* __restrict__ cells, int32_t n, LevelView lo, int32_t nl, int32_t L,
+                                                         Ctrl* __restrict__ ctrl) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const int32_t nw = gridDim.x * kWaves;
+    const int32_t cnt = min(ctrl->kept[h], cap), B = ctrl->B;
+    const int32_t mh = nodes_per_axis(L, h), ml = nodes_per_axis(L, h - 1), half = 1 << (h - 1);
+    int32_t nscored = 0;
+    for (int32_t e = blockIdx.x * kWaves + (threadIdx.x >> 6); e < cnt; e += nw) {
+        int32_t k, i, j;
+        node_decode(mh, in[e].x, k, i, j);
+        const int32_t ci = 2 * i, cj = 2 * j;
+        const int32_t xo = -nl + ci * half, yo = -nl + cj * half;
+        const bool vx = ci + 1 < ml, vy = cj + 1 < ml;                     // the children clipped by the window
+        const int2* c = cells + (int64_t)k * n;
+        int32_t q00 = 0, q01 = 0, q10 = 0, q11 = 0;
+        for (int32_t a = lane; a < n; a += kWave) {
+            const int2 p = c[a];
+            const int32_t x = p.x + xo, y = p.y + yo;
+            q00 += level_read(lo, x, y);
+            if (vy) q01 += level_read(lo, x, y + half);
+            if (vx) q10 += level_read(lo, x + half, y);
+            if (vx && vy) q11 += level_read(lo, x + half, y + half);
+        }
+        q00 = wave_sum(q00); q01 = wave_sum(q01); q10 = wave_sum(q10); q11 = wave_sum(q11);
+        if (lane == 0) {
+            const int32_t U[4] = { q00, q01, q10, q11 };
+            const bool ok[4] = { true, vy, vx, vx && vy };
+#pragma unroll
+            for (int a = 0; a < 4; ++a) {
+                if (!ok[a]) continue;
+                ++nscored;
+                if (U[a] < B) continue;
+                const int32_t slot = atomicAdd(&ctrl->kept[h - 1], 1);
+                if (slot < cap) out[slot] = make_int2(node_id(ml, k, ci + (a >> 1), cj + (a & 1)), U[a]);
+                else atomicMax(&ctrl->overflow, h);                        // 1 + the level that overflowed
+            }
+        }
+    }
+    if (lane == 0 && nscored) atomicAdd(&ctrl->scored[h - 1], nscored);
+}
+
+__global__ __launch_bounds__(kThreads) void k_fast_best(const int2* __restrict__ in, int32_t cap, Ctrl* __restrict__ ctrl) {
+    __shared__ int32_t s_u[kThreads];
+    __shared__ int32_t s_i[kThreads];
+    const int t = threadIdx.x;
+    const int32_t cnt = min(ctrl->kept[0], cap);
+    int32_t u = -1, id = INT_MAX;
+    for (int32_t a = t; a < cnt; a += kThreads) {
+        const int2 e = in[a];
+        if (better(e.y, e.x, u, id)) { u = e.y; id = e.x; }
+    }
+    s_u[t] = u; s_i[t] = id;
+    for (int h = kThreads / 2; h > 0; h >>= 1) {
+        __syncthreads();
+        if (t < h && better(s_u[t + h], s_i[t + h], s_u[t], s_i[t])) { s_u[t] = s_u[t + h]; s_i[t] = s_i[t + h]; }
+    }
+    __syncthreads();
+    if (t == 0) { ctrl->best_index = s_i[0]; ctrl->best_sum = s_u[0]; }
+}
+
+}  // namespace scanfast
+
+// ---------------------------------------------------------------- the stack object
+namespace {
+
+struct Frontier { int2* p = nullptr; size_t cap = 0; };
+struct Bounds { int32_t* p = nullptr; size_t cap = 0; };
+
+// the last successful match, as the hook reports it
+struct Last {
+    bool have = false;
+    int32_t S = 0, L = 0, n = 0, H = 0, mH = 0, survivors = 0;
+    Ctrl c{};
+    std::vector<int32_t> bounds;              // host twin
+    std::vector<int2> surv;                   // host twin
+};
+
+}  // namespace
+
+struct visfs_scan_stack {
+    bool device = false;
+    int dev = 0;
+    hipStream_t stream = nullptr;
+    int32_t blocks = 1;                       // the fixed grid of the striding kernels: sized from the compute units
+    Limits L;
+    int32_t depth = 0;
+    int64_t bytes = 0;
+    std::string err;
+    size_t off[kMaxDepth] = {};               // in uint16 items
+    std::vector<uint16_t> h_mem;
+    uint16_t* d_mem = nullptr;
+    Levels lv;
+    // a match on the device: the upload with its pinned source, the cells, the record with its pinned copy; bounds and frontiers
+    // of the call in work, and those of the last successful call (the hook's), which a failed call must leave
+    char* h_up = nullptr; char* d_up = nullptr; size_t up_cap = 0;
+    int2* d_cells = nullptr; size_t cells_cap = 0;
+    Ctrl* d_ctrl = nullptr; Ctrl* h_ctrl = nullptr;
+    Bounds bnd[2];
+    Frontier fr[3];
+    Last last;
+};
+
+namespace {
+
+int sfail(visfs_scan_stack* st, int rc, const std::string& why) { st->err = why; return rc; }
+
+#define SF_HIP(st, expr)                                                                                              \
+    do {                                                                                                              \
+        hipError_t e_ = (expr);                                                                                       \
+        if (e_ != hipSuccess) return sfail((st), VISFS_BA_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+unsigned blocks_for(int64_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
+
+template <class T> int grow(visfs_scan_stack* st, T** p, size_t* cap, size_t need) {
+    if (*cap >= need) return VISFS_BA_OK;
+    if (*p) SF_HIP(st, hipFree(*p));
+    *p = nullptr; *cap = 0;
+    SF_HIP(st, hipMalloc(reinterpret_cast<void**>(p), need * sizeof(T)));
+    *cap = need;
+    return VISFS_BA_OK;
+}
+
+void stack_free(visfs_scan_stack* st) {
+    if (st->device) {
+        (void)hipSetDevice(st->dev);
+        if (st->stream) (void)hipStreamSynchronize(st->stream);
+        if (st->d_mem) (void)hipFree(st->d_mem);
+        if (st->h_up) (void)hipHostFree(st->h_up);
+        if (st->d_up) (void)hipFree(st->d_up);
+        if (st->d_cells) (void)hipFree(st->d_cells);
+        if (st->d_ctrl) (void)hipFree(st->d_ctrl);
+        if (st->h_ctrl) (void)hipHostFree(st->h_ctrl);
+        for (Bounds& b : st->bnd) if (b.p) (void)hipFree(b.p);
+        for (Frontier& f : st->fr) if (f.p) (void)hipFree(f.p);
+    }
+    delete st;
+}
+
+// The levels' sizes and places; VISFS_BA_ERR_UNSUPPORTED beyond 1 GiB.
+int stack_layout(visfs_scan_stack* st) {
+    size_t items = 0;
+    for (int32_t h = 0; h < st->depth; ++h) {
+        const int64_t e = ((int64_t)1 << h) - 1, w = st->L.nx + e, ht = st->L.ny + e;
+        st->off[h] = items;
+        st->lv.v[h].w = (int32_t)w; st->lv.v[h].ht = (int32_t)ht; st->lv.v[h].e = (int32_t)e;
+        items += ((size_t)(w * ht) + 127) & ~size_t(127);                  // every level starts on 256 bytes
+        if ((int64_t)items * 2 > (int64_t)VISFS_SCAN_FAST_MAX_BYTES) return sfail(st, VISFS_BA_ERR_UNSUPPORTED, "the levels together exceed 1 GiB");
+    }
+    st->bytes = (int64_t)items * 2;
+    return VISFS_BA_OK;
+}
+
+// `g`: the grid in the memory of the stack's flavour (device: read on the stack's stream)
+int stack_build(visfs_scan_stack* st, const GridView& g) {
+    int rc = stack_layout(st);
+    if (rc != VISFS_BA_OK) return rc;
+    const size_t items = (size_t)(st->bytes / 2);
+    if (!st->device) {
+        st->h_mem.assign(items, 0);
+        for (int32_t h = 0; h < st->depth; ++h) st->lv.v[h].p = st->h_mem.data() + st->off[h];
+        uint16_t* p0 = st->h_mem.data();
+        for (int32_t y = 0; y < st->L.ny; ++y)
+            for (int32_t x = 0; x < st->L.nx; ++x) p0[(size_t)y * st->L.nx + x] = (uint16_t)scan::cell_gain(g, x, y);
+        for (int32_t h = 1; h < st->depth; ++h) {
+            const LevelView& hi = st->lv.v[h];
+            uint16_t* o = st->h_mem.data() + st->off[h];
+            for (int32_t sy = 0; sy < hi.ht; ++sy)
+                for (int32_t sx = 0; sx < hi.w; ++sx) o[(size_t)sy * hi.w + sx] = level_up(st->lv.v[h - 1], hi.e, 1 << (h - 1), sx, sy);
+        }
+        return VISFS_BA_OK;
+    }
+    int cus = 0;
+    SF_HIP(st, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, st->dev));
+    st->blocks = std::max(1, cus) * 8;
+    SF_HIP(st, hipMalloc(reinterpret_cast<void**>(&st->d_mem), items * 2));
+    for (int32_t h = 0; h < st->depth; ++h) st->lv.v[h].p = st->d_mem + st->off[h];
+    const int64_t n0 = (int64_t)st->L.nx * st->L.ny;
+    hipLaunchKernelGGL(k_fast_base, dim3(blocks_for(n0)), dim3(kThreads), 0, st->stream, g, st->L.nx, n0, st->d_mem);
+    SF_HIP(st, hipGetLastError());
+    for (int32_t h = 1; h < st->depth; ++h) {
+        const LevelView& hi = st->lv.v[h];
+        const int64_t nh = (int64_t)hi.w * hi.ht;
+        hipLaunchKernelGGL(k_fast_up, dim3(blocks_for(nh)), dim3(kThreads), 0, st->stream, st->lv.v[h - 1], hi.w, hi.e, 1 << (h - 1), nh,
+                           st->d_mem + st->off[h]);
+        SF_HIP(st, hipGetLastError());
+    }
+    SF_HIP(st, hipStreamSynchronize(st->stream));                          // the source grid may change or go from here on
+    return VISFS_BA_OK;
+}
+
+// ---------------------------------------------------------------- the search of one call
+struct Search {
+    Plan P;
+    int32_t H = 0, mH = 0, cap = 0;
+    int32_t top() const { return P.S * mH * mH; }
+};
+
+int make_search(const visfs_scan_stack* st, const visfs_scan_stack_params& p, const double g[3], int32_t n, const double* xyz, Search& s,
+                const char** why) {
+    Plan& P = s.P;
+    P.L = st->L; P.gx = g[0]; P.gy = g[1]; P.gyaw = g[2]; P.n = n;
+    double step, fa, fl;
+    if (!scan::plan_search(st->L.res, p.linear_search_window, p.angular_search_window, n, xyz, step, fa, fl)) { *why = "the scan's range overflows"; return VISFS_BA_ERR_UNSUPPORTED; }
+    if (!(fl <= (double)VISFS_SCAN_FAST_MAX_LINEAR)) { *why = "the linear window spans more than 512 cells"; return VISFS_BA_ERR_UNSUPPORTED; }
+    if (!(2.0 * fa + 1.0 <= (double)VISFS_SCAN_FAST_MAX_SCANS)) { *why = "the angular window holds more than 1025 rotations"; return VISFS_BA_ERR_UNSUPPORTED; }
+    P.step = step; P.na = (int32_t)fa; P.nl = (int32_t)fl; P.S = 2 * P.na + 1; P.Lw = 2 * P.nl + 1;
+    if ((int64_t)P.S * n > (int64_t)VISFS_SCAN_FAST_MAX_CELLS) { *why = "more than 2^22 cells (rotations times points)"; return VISFS_BA_ERR_UNSUPPORTED; }
+    int32_t h = 0;
+    while (h < st->depth - 1 && (1 << h) < P.Lw) ++h;
+    s.H = h; s.mH = nodes_per_axis(P.Lw, h);
+    if ((int64_t)P.S * s.mH * s.mH > (int64_t)VISFS_SCAN_FAST_MAX_TOP_NODES) { *why = "more than 2^22 nodes at the top level: the stack is too shallow for this window"; return VISFS_BA_ERR_UNSUPPORTED; }
+    s.cap = p.frontier_capacity;
+    scan::plan_tables(xyz, P);
+    return VISFS_BA_OK;
+}
+
+std::string overflow_text(int32_t level, int32_t cap) {
+    return "frontier overflow at level " + std::to_string(level) + ": more than " + std::to_string(cap) + " nodes kept";
+}
+
+void finish(const Search& s, const visfs_scan_stack_params& p, int32_t index, int32_t Q, visfs_scan_stack_result* out) {
+    const double score = scan::candidate_score(Q, s.P.n, 1.0);
+    scan::fill_result(s.P, index, score, Q, out->match);
+    out->match.matched = score >= p.min_score ? 1 : 0;
+    out->depth_used = s.H + 1;
+}
+
+// the scan's node sum, sequentially
+int32_t host_node_sum(const int32_t* c, int32_t n, const LevelView& v, int32_t xo, int32_t yo) {
+    int32_t q = 0;
+    for (int32_t i = 0; i < n; ++i) q += level_read(v, c[2 * i] + xo, c[2 * i + 1] + yo);
+    return q;
+}
+
+int host_match(visfs_scan_stack* st, Search& s, const visfs_scan_stack_params& p, visfs_scan_stack_result* out) {
+    const Plan& P = s.P;
+    const int32_t n = P.n, nl = P.nl, L = P.Lw, H = s.H, mH = s.mH, per = mH * mH;
+    std::vector<int32_t> cells(2 * (size_t)P.S * n);
+    for (int32_t k = 0; k < P.S; ++k)
+        for (int32_t i = 0; i < n; ++i)
+            scan::discretise(P.rot[2 * k], P.rot[2 * k + 1], P.pts[2 * i], P.pts[2 * i + 1], P.gx, P.gy, P.L.res, P.L.max_x, P.L.max_y,
+                             cells[2 * ((size_t)k * n + i)], cells[2 * ((size_t)k * n + i) + 1]);
+    auto scan_cells = [&](int32_t k) { return cells.data() + 2 * (size_t)k * n; };
+    Last now;
+    now.S = P.S; now.L = L; now.n = n; now.H = H; now.mH = mH;
+    now.bounds.resize((size_t)s.top());
+    for (int32_t id = 0; id < s.top(); ++id) {
+        int32_t k, i, j;
+        node_decode(mH, id, k, i, j);
+        now.bounds[id] = host_node_sum(scan_cells(k), n, st->lv.v[H], -nl + (i << H), -nl + (j << H));
+    }
+    int32_t B = 0;
+    for (int32_t k = 0; k < P.S; ++k) {                                    // the greedy descents
+        int32_t u = -1, id = INT_MAX;
+        for (int32_t a = 0; a < per; ++a) if (better(now.bounds[(size_t)k * per + a], a, u, id)) { u = now.bounds[(size_t)k * per + a]; id = a; }
+        int32_t i = id / mH, j = id % mH, cur = u;
+        for (int32_t h = H; h >= 1; --h) {
+            const int32_t m = nodes_per_axis(L, h - 1);
+            int32_t bu = -1, bw = 0;
+            for (int w = 0; w < 4; ++w) {
+                const int32_t ci = 2 * i + (w >> 1), cj = 2 * j + (w & 1);
+                if (ci >= m || cj >= m) continue;
+                const int32_t U = host_node_sum(scan_cells(k), n, st->lv.v[h - 1], -nl + (ci << (h - 1)), -nl + (cj << (h - 1)));
+                if (U > bu) { bu = U; bw = w; }
+            }
+            cur = bu; i = 2 * i + (bw >> 1); j = 2 * j + (bw & 1);
+        }
+        if (cur > B) B = cur;
+    }
+    now.c.B = B;
+    std::vector<int2> F, G;
+    now.c.scored[H] = s.top();
+    for (int32_t id = 0; id < s.top(); ++id)
+        if (now.bounds[id] >= B) { ++now.c.kept[H]; if ((int32_t)F.size() < s.cap) F.push_back(make_int2(id, now.bounds[id])); }
+    if (now.c.kept[H] > s.cap) return sfail(st, VISFS_BA_ERR_UNSUPPORTED, overflow_text(H, s.cap));
+    for (int32_t h = H; h >= 1; --h) {
+        const int32_t mh = nodes_per_axis(L, h), ml = nodes_per_axis(L, h - 1), half = 1 << (h - 1);
+        G.clear();
+        for (const int2& e : F) {
+            int32_t k, i, j;
+            node_decode(mh, e.x, k, i, j);
+            for (int a = 0; a < 4; ++a) {
+                const int32_t ci = 2 * i + (a >> 1), cj = 2 * j + (a & 1);
+                if (ci >= ml || cj >= ml) continue;
+                const int32_t U = host_node_sum(scan_cells(k), n, st->lv.v[h - 1], -nl + ci * half, -nl + cj * half);
+                ++now.c.scored[h - 1];
+                if (U < B) continue;
+                ++now.c.kept[h - 1];
+                if ((int32_t)G.size() < s.cap) G.push_back(make_int2(node_id(ml, k, ci, cj), U));
+            }
+        }
+        if (now.c.kept[h - 1] > s.cap) return sfail(st, VISFS_BA_ERR_UNSUPPORTED, overflow_text(h - 1, s.cap));
+        F.swap(G);
+    }
+    int32_t u = -1, id = INT_MAX;
+    for (const int2& e : F) if (better(e.y, e.x, u, id)) { u = e.y; id = e.x; }
+    if (id == INT_MAX) return sfail(st, VISFS_BA_ERR_DEVICE, "the search returned no candidate");
+    now.c.best_index = id; now.c.best_sum = u;
+    std::sort(F.begin(), F.end(), [](const int2& a, const int2& b) { return a.x < b.x; });
+    now.survivors = (int32_t)F.size();
+    now.surv.swap(F);
+    now.have = true;
+    finish(s, p, id, u, out);
+    st->last = std::move(now);
+    return VISFS_BA_OK;
+}
+
+int device_match(visfs_scan_stack* st, Search& s, const visfs_scan_stack_params& p, visfs_scan_stack_result* out) {
+    const Plan& P = s.P;
+    const int32_t n = P.n, nl = P.nl, L = P.Lw, H = s.H, mH = s.mH, total = s.top();
+    SF_HIP(st, hipSetDevice(st->dev));
+    const size_t npts = 2 * (size_t)n, nrot = 2 * (size_t)P.S, bytes = (npts + nrot) * sizeof(double);
+    if (st->up_cap < bytes) {
+        if (st->h_up) SF_HIP(st, hipHostFree(st->h_up));
+        if (st->d_up) SF_HIP(st, hipFree(st->d_up));
+        st->h_up = st->d_up = nullptr; st->up_cap = 0;
+        const size_t cap = bytes + bytes / 2;
+        SF_HIP(st, hipHostMalloc(reinterpret_cast<void**>(&st->h_up), cap, hipHostMallocDefault));
+        SF_HIP(st, hipMalloc(reinterpret_cast<void**>(&st->d_up), cap));
+        st->up_cap = cap;
+    }
+    if (!st->d_ctrl) {
+        SF_HIP(st, hipMalloc(reinterpret_cast<void**>(&st->d_ctrl), sizeof(Ctrl)));
+        SF_HIP(st, hipHostMalloc(reinterpret_cast<void**>(&st->h_ctrl), sizeof(Ctrl), hipHostMallocDefault));
+    }
+    int rc;
+    if ((rc = grow(st, &st->d_cells, &st->cells_cap, (size_t)P.S * n)) != VISFS_BA_OK) return rc;
+    if ((rc = grow(st, &st->bnd[0].p, &st->bnd[0].cap, (size_t)total)) != VISFS_BA_OK) return rc;
+    for (int f = 0; f < 2; ++f)
+        if ((rc = grow(st, &st->fr[f].p, &st->fr[f].cap, (size_t)s.cap)) != VISFS_BA_OK) return rc;
+    double* hup = reinterpret_cast<double*>(st->h_up);
+    std::memcpy(hup, P.pts.data(), npts * sizeof(double));
+    std::memcpy(hup + npts, P.rot.data(), nrot * sizeof(double));
+    SF_HIP(st, hipMemcpyAsync(st->d_up, st->h_up, bytes, hipMemcpyHostToDevice, st->stream));
+    const double* d = reinterpret_cast<const double*>(st->d_up);
+    const int64_t ncell = (int64_t)P.S * n;
+    const dim3 fixed(st->blocks), wg(kThreads);
+    hipLaunchKernelGGL(k_fast_cells, dim3(blocks_for(ncell)), wg, 0, st->stream, d, d + npts, n, ncell, P.gx, P.gy, P.L.res, P.L.max_x, P.L.max_y,
+                       st->d_cells, st->d_ctrl);
+    SF_HIP(st, hipGetLastError());
+    hipLaunchKernelGGL(k_fast_bounds, fixed, wg, 0, st->stream, st->d_cells, n, st->lv.v[H], nl, H, mH, total, st->bnd[0].p);
+    SF_HIP(st, hipGetLastError());
+    hipLaunchKernelGGL(k_fast_seeds, dim3(P.S), wg, 0, st->stream, st->bnd[0].p, st->d_cells, n, st->lv, nl, L, H, mH, st->d_ctrl);
+    SF_HIP(st, hipGetLastError());
+    int cur = 0;                                                           // the frontier of the level in work: fr[cur]
+    hipLaunchKernelGGL(k_fast_keep, fixed, wg, 0, st->stream, st->bnd[0].p, total, H, st->fr[cur].p, s.cap, st->d_ctrl);
+    SF_HIP(st, hipGetLastError());
+    for (int32_t h = H; h >= 1; --h) {
+        hipLaunchKernelGGL(k_fast_level, fixed, wg, 0, st->stream, h, st->fr[cur].p, st->fr[1 - cur].p, s.cap, st->d_cells, n, st->lv.v[h - 1], nl, L,
+                           st->d_ctrl);
+        SF_HIP(st, hipGetLastError());
+        cur = 1 - cur;
+    }
+    hipLaunchKernelGGL(k_fast_best, dim3(1), wg, 0, st->stream, st->fr[cur].p, s.cap, st->d_ctrl);
+    SF_HIP(st, hipGetLastError());
+    SF_HIP(st, hipMemcpyAsync(st->h_ctrl, st->d_ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, st->stream));
+    SF_HIP(st, hipStreamSynchronize(st->stream));
+    const Ctrl c = *st->h_ctrl;
+    if (c.overflow) return sfail(st, VISFS_BA_ERR_UNSUPPORTED, overflow_text(c.overflow - 1, s.cap));
+    if (c.best_index < 0 || (int64_t)c.best_index >= P.candidates()) return sfail(st, VISFS_BA_ERR_DEVICE, "the search returned no candidate");
+    // the hook's buffers change hands: what this call wrote stays until the next successful call
+    std::swap(st->bnd[0], st->bnd[1]);
+    std::swap(st->fr[cur], st->fr[2]);
+    Last now;
+    now.have = true; now.S = P.S; now.L = L; now.n = n; now.H = H; now.mH = mH; now.survivors = c.kept[0]; now.c = c;
+    finish(s, p, c.best_index, c.best_sum, out);
+    st->last = std::move(now);
+    return VISFS_BA_OK;
+}
+
+template <class F> int guarded(F&& f) noexcept {
+    try { return f(); }
+    catch (...) { return (int)VISFS_BA_ERR_DEVICE; }
+}
+
+int check_depth(int32_t depth) { return depth >= 1 && depth <= kMaxDepth; }
+
+}  // namespace
+
+// ====================================================================== exported C ABI
+extern "C" {
+
+int visfs_scan_fast_abi_version(void) { return VISFS_SCAN_FAST_ABI_VERSION; }
+
+void visfs_scan_stack_default_params(visfs_scan_stack_params* p) {
+    if (!p) return;
+    p->linear_search_window = 7.0;
+    p->angular_search_window = 30.0 * 3.14159265358979323846 / 180.0;
+    p->min_score = 0.0;
+    p->frontier_capacity = 1 << 20;
+}
+
+int visfs_scan_stack_create(visfs_submaps* s, int32_t index, int32_t depth, visfs_scan_stack** out) {
+    if (!s || !out) return VISFS_BA_ERR_BAD_ARGUMENT;
+    *out = nullptr;
+    return guarded([&]() -> int {
+        if (!check_depth(depth)) return visfs_internal_scan_fail(s, VISFS_BA_ERR_BAD_ARGUMENT, "the depth must lie in [1, 16]");
+        submap::ScanAccess acc;
+        int rc = visfs_internal_scan_access(s, index, &acc);
+        if (rc != VISFS_BA_OK) return rc;
+        if (index < 0 || index >= acc.count) return visfs_internal_scan_fail(s, VISFS_BA_ERR_BAD_ARGUMENT, "sub-map index out of range");
+        visfs_scan_stack* st = new visfs_scan_stack();
+        st->device = acc.device; st->dev = acc.dev; st->stream = acc.stream;
+        st->L = acc.L; st->depth = depth;
+        rc = stack_build(st, acc.grid);
+        if (rc != VISFS_BA_OK) { (void)visfs_internal_scan_fail(s, rc, st->err.c_str()); stack_free(st); return rc; }
+        *out = st;
+        return (int)VISFS_BA_OK;
+    });
+}
+
+int visfs_scan_stack_create_from_grid(visfs_ba_handle* h, const visfs_submap_info* lim, const uint16_t* cells, int32_t depth, visfs_scan_stack** out) {
+    if (!lim || !cells || !out) return VISFS_BA_ERR_BAD_ARGUMENT;
+    *out = nullptr;
+    return guarded([&]() -> int {
+        auto bad = [&](int rc, const char* why) { if (h) visfs_internal_set_error(h, why); return rc; };
+        if (!check_depth(depth)) return bad(VISFS_BA_ERR_BAD_ARGUMENT, "the depth must lie in [1, 16]");
+        if (!(lim->resolution > 0.0) || !std::isfinite(lim->resolution) || !std::isfinite(lim->max_x) || !std::isfinite(lim->max_y) ||
+            lim->num_x_cells < 1 || lim->num_y_cells < 1)
+            return bad(VISFS_BA_ERR_BAD_ARGUMENT, "the limits need a positive resolution, a finite corner and at least one cell per axis");
+        if ((int64_t)lim->num_x_cells * lim->num_y_cells * 2 > (int64_t)VISFS_SCAN_FAST_MAX_BYTES) return bad(VISFS_BA_ERR_UNSUPPORTED, "the levels together exceed 1 GiB");
+        visfs_scan_stack* st = new visfs_scan_stack();
+        st->L.res = lim->resolution; st->L.max_x = lim->max_x; st->L.max_y = lim->max_y; st->L.nx = lim->num_x_cells; st->L.ny = lim->num_y_cells;
+        st->depth = depth;
+        GridView g;
+        g.cells = cells; g.nx = st->L.nx; g.ny = st->L.ny;
+        int rc;
+        if (!h) rc = stack_build(st, g);
+        else {
+            st->device = true; st->dev = visfs_internal_device(h); st->stream = visfs_internal_stream(h);
+            uint16_t* tmp = nullptr;
+            auto run = [&]() -> int {
+                const size_t nb = (size_t)g.nx * g.ny * 2;
+                SF_HIP(st, hipSetDevice(st->dev));
+                SF_HIP(st, hipMalloc(reinterpret_cast<void**>(&tmp), nb));
+                SF_HIP(st, hipMemcpyAsync(tmp, cells, nb, hipMemcpyHostToDevice, st->stream));
+                g.cells = tmp;
+                return stack_build(st, g);                                 // ends with a wait on the stream
+            };
+            rc = run();
+            if (tmp) { (void)hipStreamSynchronize(st->stream); (void)hipFree(tmp); }
+        }
+        if (rc != VISFS_BA_OK) { (void)bad(rc, st->err.c_str()); stack_free(st); return rc; }
+        *out = st;
+        return (int)VISFS_BA_OK;
+    });
+}
+
+void visfs_scan_stack_destroy(visfs_scan_stack* st) { if (st) stack_free(st); }
+
+const char* visfs_scan_stack_last_error(const visfs_scan_stack* st) { return st ? st->err.c_str() : "null stack"; }
+
+int visfs_scan_stack_describe(const visfs_scan_stack* st, visfs_scan_stack_info* info) {
+    if (!st || !info) return VISFS_BA_ERR_BAD_ARGUMENT;
+    info->resolution = st->L.res; info->max_x = st->L.max_x; info->max_y = st->L.max_y;
+    info->num_x_cells = st->L.nx; info->num_y_cells = st->L.ny; info->depth = st->depth; info->device = st->device ? 1 : 0;
+    info->bytes = st->bytes;
+    return VISFS_BA_OK;
+}
+
+int visfs_scan_stack_match(visfs_scan_stack* st, const visfs_scan_stack_params* p, const double g[3], int32_t n, const double* xyz,
+                           visfs_scan_stack_result* out) {
+    if (!st || !p || !g || !out || n < 0 || (n > 0 && !xyz)) return VISFS_BA_ERR_BAD_ARGUMENT;
+    return guarded([&]() -> int {
+        if (n > VISFS_SCAN_FAST_MAX_POINTS) return sfail(st, VISFS_BA_ERR_UNSUPPORTED, "more than 16384 points");
+        for (int i = 0; i < 3; ++i) if (!std::isfinite(g[i])) return sfail(st, VISFS_BA_ERR_BAD_ARGUMENT, "the guess is not finite");
+        for (int64_t i = 0; i < 3 * (int64_t)n; ++i) if (!std::isfinite(xyz[i])) return sfail(st, VISFS_BA_ERR_BAD_ARGUMENT, "a point is not finite");
+        if (!std::isfinite(p->linear_search_window) || !std::isfinite(p->angular_search_window) || p->linear_search_window < 0.0 || p->angular_search_window < 0.0)
+            return sfail(st, VISFS_BA_ERR_BAD_ARGUMENT, "the search windows must be finite and not negative");
+        if (std::isnan(p->min_score)) return sfail(st, VISFS_BA_ERR_BAD_ARGUMENT, "min_score is not a number");
+        if (p->frontier_capacity < 4 || p->frontier_capacity > VISFS_SCAN_FAST_MAX_FRONTIER)
+            return sfail(st, VISFS_BA_ERR_BAD_ARGUMENT, "frontier_capacity must lie in [4, 2^26]");
+        if (n == 0) {                                                      // nothing to match: the guess back
+            std::memset(out, 0, sizeof *out);
+            out->match.x = g[0]; out->match.y = g[1]; out->match.yaw = g[2];
+            return (int)VISFS_BA_OK;
+        }
+        Search s;
+        const char* why = "";
+        const int rc = make_search(st, *p, g, n, xyz, s, &why);
+        if (rc != VISFS_BA_OK) return sfail(st, rc, why);
+        return st->device ? device_match(st, s, *p, out) : host_match(st, s, *p, out);
+    });
+}
+
+int visfs_scan_stack_download_level(visfs_scan_stack* st, int32_t h, int64_t cap, uint16_t* out, int32_t dims[4]) {
+    if (!st || !dims || cap < 0) return VISFS_BA_ERR_BAD_ARGUMENT;
+    return guarded([&]() -> int {
+        if (h < 0 || h >= st->depth) return sfail(st, VISFS_BA_ERR_BAD_ARGUMENT, "the stack has no such level");
+        const LevelView& v = st->lv.v[h];
+        dims[0] = v.w; dims[1] = v.ht; dims[2] = v.e; dims[3] = 0;
+        if (!out) return (int)VISFS_BA_OK;
+        const int64_t items = (int64_t)v.w * v.ht;
+        if (cap < items) return sfail(st, VISFS_BA_ERR_BAD_ARGUMENT, "the hook's array is too small");
+        if (!st->device) { std::memcpy(out, v.p, (size_t)items * 2); return (int)VISFS_BA_OK; }
+        SF_HIP(st, hipSetDevice(st->dev));
+        SF_HIP(st, hipMemcpyAsync(out, v.p, (size_t)items * 2, hipMemcpyDeviceToHost, st->stream));
+        SF_HIP(st, hipStreamSynchronize(st->stream));
+        return (int)VISFS_BA_OK;
+    });
+}
+
+int visfs_scan_stack_match_download(visfs_scan_stack* st, int32_t header[8], int32_t scored[16], int32_t kept[16], int64_t bounds_cap,
+                                    int32_t* bounds, int64_t survivors_cap, int32_t* survivors) {
+    if (!st || !header || bounds_cap < 0 || survivors_cap < 0) return VISFS_BA_ERR_BAD_ARGUMENT;
+    return guarded([&]() -> int {
+        const Last& l = st->last;
+        std::memset(header, 0, 8 * sizeof(int32_t));
+        if (!l.have) return (int)VISFS_BA_OK;
+        const int32_t per = l.mH * l.mH;
+        const int64_t nb = (int64_t)l.S * per;
+        header[0] = l.S; header[1] = l.L; header[2] = l.n; header[3] = l.H; header[4] = per; header[5] = l.survivors; header[6] = l.c.B;
+        if (scored) std::memcpy(scored, l.c.scored, sizeof l.c.scored);
+        if (kept) std::memcpy(kept, l.c.kept, sizeof l.c.kept);
+        if ((bounds && bounds_cap < nb) || (survivors && survivors_cap < l.survivors)) return sfail(st, VISFS_BA_ERR_BAD_ARGUMENT, "the hook's arrays are too small");
+        if (!st->device) {
+            if (bounds) std::memcpy(bounds, l.bounds.data(), (size_t)nb * sizeof(int32_t));
+            if (survivors) std::memcpy(survivors, l.surv.data(), (size_t)l.survivors * sizeof(int2));
+            return (int)VISFS_BA_OK;
+        }
+        SF_HIP(st, hipSetDevice(st->dev));
+        if (bounds) SF_HIP(st, hipMemcpyAsync(bounds, st->bnd[1].p, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost, st->stream));
+        if (survivors) SF_HIP(st, hipMemcpyAsync(survivors, st->fr[2].p, (size_t)l.survivors * sizeof(int2), hipMemcpyDeviceToHost, st->stream));
+        SF_HIP(st, hipStreamSynchronize(st->stream));
+        if (survivors) {                                                   // the device appends unordered
+            int2* sv = reinterpret_cast<int2*>(survivors);
+            std::sort(sv, sv + l.survivors, [](const int2& a, const int2& b) { return a.x < b.x; });
+        }
+        return (int)VISFS_BA_OK;
+    });
+}
+
+}  // extern "C"

@@ -6,6 +6,7 @@
 // the BA against it (Estimator.cpp:247-250 + Optimizer::localOptimize).  The grids stay on the device: there is no Submap2D object to
 // hand out; download() copies one to the host for those who want grid2Image.  match() is the correlative scan match that
 // Estimator::laserPretreatment names and leaves out (include/visfs_scan_match.h): it corrects a pose guess against a sub-map.
+// freeze() snapshots a sub-map as a VISFS::ScanStack (ScanStack.h) for relocalisation and loop closure.
 #ifndef VISFS_AMD_ACTIVE_SUBMAPS_2D_H
 #define VISFS_AMD_ACTIVE_SUBMAPS_2D_H
 
@@ -14,6 +15,7 @@
 #include <string>
 #include <vector>
 
+#include "ScanStack.h"
 #include "visfs_scan_match.h"
 #include "visfs_submap.h"
 
@@ -84,6 +86,15 @@ public:
         if (out) { out->x = r.x; out->y = r.y; out->yaw = r.yaw; out->score = r.score; out->matched = r.matched != 0; }
         if (full) *full = r;
         return rc;
+    }
+
+    // Sub-map `index` as it is now, frozen with `depth` levels for the branch-and-bound search (include/visfs_scan_fast.h): later
+    // insertions, finishing and cropping do not change the stack.  Throws std::runtime_error when there is no such sub-map.
+    ScanStack freeze(int index = 0, int depth = 7) const {
+        visfs_scan_stack* st = nullptr;
+        const int rc = visfs_scan_stack_create(s_, index, depth, &st);
+        if (rc != VISFS_BA_OK) throw std::runtime_error("visfs_scan_stack_create failed with status " + std::to_string(rc) + ": " + lastError());
+        return ScanStack(st);
     }
 
     // one sub-map's cells and float costs on the host ([num_y_cells][num_x_cells])
