@@ -17,8 +17,9 @@
 //                  are dropped and the overflow flag is raised;
 //   k_fast_best    one workgroup selects the winner among the level-0 survivors: Q descending, index ascending.
 // All sums are int32, so no reduction or append order can show in a result.  The one-core twin runs the same schedule through the
-// same functions of ba_scan_fast.hpp.
-#include "ba_scan_fast.hpp"
+// same functions of ba_scan_fast.hpp.  The bodies of the six match kernels, the stack object and the search of one call are in
+// ba_scan_stack.hpp: the group call over several stacks (ba_scan_group.hip) runs the same bodies and the same search.
+#include "ba_scan_stack.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -53,192 +54,37 @@ __global__ __launch_bounds__(kThreads) void k_fast_up(LevelView lo, int32_t w, i
 __global__ __launch_bounds__(kThreads) void k_fast_cells(const double* __restrict__ pts, const double* __restrict__ rot, int32_t n, int64_t total,
                                                          double gx, double gy, double res, double max_x, double max_y, int2* __restrict__ cells,
                                                          Ctrl* __restrict__ ctrl) {
-    if (blockIdx.x == 0 && threadIdx.x < sizeof(Ctrl) / sizeof(int32_t)) reinterpret_cast<int32_t*>(ctrl)[threadIdx.x] = 0;
-    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-    if (i >= total) return;
-    const int32_t k = (int32_t)(i / n), j = (int32_t)(i - (int64_t)k * n);
-    int32_t ix, iy;
-    scan::discretise(rot[2 * k], rot[2 * k + 1], pts[2 * j], pts[2 * j + 1], gx, gy, res, max_x, max_y, ix, iy);
-    cells[i] = make_int2(ix, iy);
-}
-
-__device__ inline int32_t wave_sum(int32_t v) {
-    for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// sum over the scan's n cells of P_h(cell + (xo, yo)): every lane of the wavefront calls, every lane gets the sum
-__device__ inline int32_t wave_node_sum(const int2* __restrict__ c, int32_t n, const LevelView& v, int32_t xo, int32_t yo, int lane) {
-    int32_t q = 0;
-    for (int32_t i = lane; i < n; i += kWave) { const int2 p = c[i]; q += level_read(v, p.x + xo, p.y + yo); }
-    return wave_sum(q);
+    cells_body(pts, rot, n, total, gx, gy, res, max_x, max_y, cells, ctrl);
 }
 
 __global__ __launch_bounds__(kThreads) void k_fast_bounds(const int2* __restrict__ cells, int32_t n, LevelView vH, int32_t nl, int32_t H, int32_t mH,
                                                           int32_t total, int32_t* __restrict__ bounds) {
-    const int lane = threadIdx.x & (kWave - 1);
-    const int32_t nw = gridDim.x * kWaves;
-    for (int32_t id = blockIdx.x * kWaves + (threadIdx.x >> 6); id < total; id += nw) {
-        int32_t k, i, j;
-        node_decode(mH, id, k, i, j);
-        const int32_t U = wave_node_sum(cells + (int64_t)k * n, n, vH, -nl + (i << H), -nl + (j << H), lane);
-        if (lane == 0) bounds[id] = U;
-    }
+    bounds_body(cells, n, vH, nl, H, mH, total, bounds);
 }
 
 __global__ __launch_bounds__(kThreads) void k_fast_seeds(const int32_t* __restrict__ bounds, const int2* __restrict__ cells, int32_t n, Levels lv,
                                                          int32_t nl, int32_t L, int32_t H, int32_t mH, Ctrl* __restrict__ ctrl) {
-    __shared__ int32_t s_u[kThreads];
-    __shared__ int32_t s_i[kThreads];
-    __shared__ int32_t s_c[kWaves];
-    const int t = threadIdx.x, lane = t & (kWave - 1), w = t >> 6;
-    const int32_t k = blockIdx.x, per = mH * mH;
-    int32_t u = -1, id = INT_MAX;
-    for (int32_t a = t; a < per; a += kThreads) {
-        const int32_t ua = bounds[k * per + a];
-        if (better(ua, a, u, id)) { u = ua; id = a; }
-    }
-    s_u[t] = u; s_i[t] = id;
-    for (int h = kThreads / 2; h > 0; h >>= 1) {
-        __syncthreads();
-        if (t < h && better(s_u[t + h], s_i[t + h], s_u[t], s_i[t])) { s_u[t] = s_u[t + h]; s_i[t] = s_i[t + h]; }
-    }
-    __syncthreads();
-    int32_t i = s_i[0] / mH, j = s_i[0] % mH, cur = s_u[0];
-    const int2* c = cells + (int64_t)k * n;
-    for (int32_t h = H; h >= 1; --h) {                                     // every choice: the larger bound, then the lower index
-        const int32_t m = nodes_per_axis(L, h - 1);
-        const int32_t ci = 2 * i + (w >> 1), cj = 2 * j + (w & 1);
-        int32_t U = -1;
-        if (ci < m && cj < m) U = wave_node_sum(c, n, lv.v[h - 1], -nl + (ci << (h - 1)), -nl + (cj << (h - 1)), lane);
-        if (lane == 0) s_c[w] = U;
-        __syncthreads();
-        int bw = 0;
-        for (int a = 1; a < kWaves; ++a) if (s_c[a] > s_c[bw]) bw = a;
-        cur = s_c[bw];
-        i = 2 * i + (bw >> 1); j = 2 * j + (bw & 1);
-        __syncthreads();
-    }
-    if (t == 0) atomicMax(&ctrl->B, cur);
+    seeds_body(bounds, cells, n, lv, nl, L, H, mH, ctrl);
 }
 
 __global__ __launch_bounds__(kThreads) void k_fast_keep(const int32_t* __restrict__ bounds, int32_t total, int32_t H, int2* __restrict__ out, int32_t cap,
                                                         Ctrl* __restrict__ ctrl) {
-    const int32_t B = ctrl->B;
-    const int32_t nt = gridDim.x * kThreads;
-    if (blockIdx.x == 0 && threadIdx.x == 0) ctrl->scored[H] = total;
-    for (int32_t id = blockIdx.x * kThreads + threadIdx.x; id < total; id += nt) {
-        const int32_t U = bounds[id];
-        if (U < B) continue;
-        const int32_t slot = atomicAdd(&ctrl->kept[H], 1);
-        if (slot < cap) out[slot] = make_int2(id, U);
-        else atomicMax(&ctrl->overflow, H + 1);
-    }
+    keep_body(bounds, total, H, out, cap, ctrl);
 }
 
 __global__ __launch_bounds__(kThreads) void k_fast_level(int32_t h, const int2* __restrict__ in, int2* __restrict__ out, int32_t cap,
                                                          const int2* __restrict__ cells, int32_t n, LevelView lo, int32_t nl, int32_t L,
                                                          Ctrl* __restrict__ ctrl) {
-    const int lane = threadIdx.x & (kWave - 1);
-    const int32_t nw = gridDim.x * kWaves;
-    const int32_t cnt = min(ctrl->kept[h], cap), B = ctrl->B;
-    const int32_t mh = nodes_per_axis(L, h), ml = nodes_per_axis(L, h - 1), half = 1 << (h - 1);
-    int32_t nscored = 0;
-    for (int32_t e = blockIdx.x * kWaves + (threadIdx.x >> 6); e < cnt; e += nw) {
-        int32_t k, i, j;
-        node_decode(mh, in[e].x, k, i, j);
-        const int32_t ci = 2 * i, cj = 2 * j;
-        const int32_t xo = -nl + ci * half, yo = -nl + cj * half;
-        const bool vx = ci + 1 < ml, vy = cj + 1 < ml;                     // the children clipped by the window
-        const int2* c = cells + (int64_t)k * n;
-        int32_t q00 = 0, q01 = 0, q10 = 0, q11 = 0;
-        for (int32_t a = lane; a < n; a += kWave) {
-            const int2 p = c[a];
-            const int32_t x = p.x + xo, y = p.y + yo;
-            q00 += level_read(lo, x, y);
-            if (vy) q01 += level_read(lo, x, y + half);
-            if (vx) q10 += level_read(lo, x + half, y);
-            if (vx && vy) q11 += level_read(lo, x + half, y + half);
-        }
-        q00 = wave_sum(q00); q01 = wave_sum(q01); q10 = wave_sum(q10); q11 = wave_sum(q11);
-        if (lane == 0) {
-            const int32_t U[4] = { q00, q01, q10, q11 };
-            const bool ok[4] = { true, vy, vx, vx && vy };
-#pragma unroll
-            for (int a = 0; a < 4; ++a) {
-                if (!ok[a]) continue;
-                ++nscored;
-                if (U[a] < B) continue;
-                const int32_t slot = atomicAdd(&ctrl->kept[h - 1], 1);
-                if (slot < cap) out[slot] = make_int2(node_id(ml, k, ci + (a >> 1), cj + (a & 1)), U[a]);
-                else atomicMax(&ctrl->overflow, h);                        // 1 + the level that overflowed
-            }
-        }
-    }
-    if (lane == 0 && nscored) atomicAdd(&ctrl->scored[h - 1], nscored);
+    level_body(h, in, out, cap, cells, n, lo, nl, L, ctrl);
 }
 
 __global__ __launch_bounds__(kThreads) void k_fast_best(const int2* __restrict__ in, int32_t cap, Ctrl* __restrict__ ctrl) {
-    __shared__ int32_t s_u[kThreads];
-    __shared__ int32_t s_i[kThreads];
-    const int t = threadIdx.x;
-    const int32_t cnt = min(ctrl->kept[0], cap);
-    int32_t u = -1, id = INT_MAX;
-    for (int32_t a = t; a < cnt; a += kThreads) {
-        const int2 e = in[a];
-        if (better(e.y, e.x, u, id)) { u = e.y; id = e.x; }
-    }
-    s_u[t] = u; s_i[t] = id;
-    for (int h = kThreads / 2; h > 0; h >>= 1) {
-        __syncthreads();
-        if (t < h && better(s_u[t + h], s_i[t + h], s_u[t], s_i[t])) { s_u[t] = s_u[t + h]; s_i[t] = s_i[t + h]; }
-    }
-    __syncthreads();
-    if (t == 0) { ctrl->best_index = s_i[0]; ctrl->best_sum = s_u[0]; }
+    best_body(in, cap, ctrl);
 }
 
 }  // namespace scanfast
 
 // ---------------------------------------------------------------- the stack object
-namespace {
-
-struct Frontier { int2* p = nullptr; size_t cap = 0; };
-struct Bounds { int32_t* p = nullptr; size_t cap = 0; };
-
-// the last successful match, as the hook reports it
-struct Last {
-    bool have = false;
-    int32_t S = 0, L = 0, n = 0, H = 0, mH = 0, survivors = 0;
-    Ctrl c{};
-    std::vector<int32_t> bounds;              // host twin
-    std::vector<int2> surv;                   // host twin
-};
-
-}  // namespace
-
-struct visfs_scan_stack {
-    bool device = false;
-    int dev = 0;
-    hipStream_t stream = nullptr;
-    int32_t blocks = 1;                       // the fixed grid of the striding kernels: sized from the compute units
-    Limits L;
-    int32_t depth = 0;
-    int64_t bytes = 0;
-    std::string err;
-    size_t off[kMaxDepth] = {};               // in uint16 items
-    std::vector<uint16_t> h_mem;
-    uint16_t* d_mem = nullptr;
-    Levels lv;
-    // a match on the device: the upload with its pinned source, the cells, the record with its pinned copy; bounds and frontiers
-    // of the call in work, and those of the last successful call (the hook's), which a failed call must leave
-    char* h_up = nullptr; char* d_up = nullptr; size_t up_cap = 0;
-    int2* d_cells = nullptr; size_t cells_cap = 0;
-    Ctrl* d_ctrl = nullptr; Ctrl* h_ctrl = nullptr;
-    Bounds bnd[2];
-    Frontier fr[3];
-    Last last;
-};
-
 namespace {
 
 int sfail(visfs_scan_stack* st, int rc, const std::string& why) { st->err = why; return rc; }
@@ -328,12 +174,10 @@ int stack_build(visfs_scan_stack* st, const GridView& g) {
     return VISFS_BA_OK;
 }
 
-// ---------------------------------------------------------------- the search of one call
-struct Search {
-    Plan P;
-    int32_t H = 0, mH = 0, cap = 0;
-    int32_t top() const { return P.S * mH * mH; }
-};
+}  // namespace
+
+// ---------------------------------------------------------------- the search of one call (shared with ba_scan_group.hip)
+namespace scanfast {
 
 int make_search(const visfs_scan_stack* st, const visfs_scan_stack_params& p, const double g[3], int32_t n, const double* xyz, Search& s,
                 const char** why) {
@@ -365,14 +209,31 @@ void finish(const Search& s, const visfs_scan_stack_params& p, int32_t index, in
     out->depth_used = s.H + 1;
 }
 
+void no_points(const double g[3], visfs_scan_stack_result* out) {
+    std::memset(out, 0, sizeof *out);
+    out->match.x = g[0]; out->match.y = g[1]; out->match.yaw = g[2];
+}
+
+int check_call(const visfs_scan_stack_params& p, const double g[3], int32_t n, const double* xyz, const char** why) {
+    if (n > VISFS_SCAN_FAST_MAX_POINTS) { *why = "more than 16384 points"; return VISFS_BA_ERR_UNSUPPORTED; }
+    for (int i = 0; i < 3; ++i) if (!std::isfinite(g[i])) { *why = "the guess is not finite"; return VISFS_BA_ERR_BAD_ARGUMENT; }
+    for (int64_t i = 0; i < 3 * (int64_t)n; ++i) if (!std::isfinite(xyz[i])) { *why = "a point is not finite"; return VISFS_BA_ERR_BAD_ARGUMENT; }
+    if (!std::isfinite(p.linear_search_window) || !std::isfinite(p.angular_search_window) || p.linear_search_window < 0.0 || p.angular_search_window < 0.0) {
+        *why = "the search windows must be finite and not negative"; return VISFS_BA_ERR_BAD_ARGUMENT;
+    }
+    if (std::isnan(p.min_score)) { *why = "min_score is not a number"; return VISFS_BA_ERR_BAD_ARGUMENT; }
+    if (p.frontier_capacity < 4 || p.frontier_capacity > VISFS_SCAN_FAST_MAX_FRONTIER) { *why = "frontier_capacity must lie in [4, 2^26]"; return VISFS_BA_ERR_BAD_ARGUMENT; }
+    return VISFS_BA_OK;
+}
+
 // the scan's node sum, sequentially
-int32_t host_node_sum(const int32_t* c, int32_t n, const LevelView& v, int32_t xo, int32_t yo) {
+static int32_t host_node_sum(const int32_t* c, int32_t n, const LevelView& v, int32_t xo, int32_t yo) {
     int32_t q = 0;
     for (int32_t i = 0; i < n; ++i) q += level_read(v, c[2 * i] + xo, c[2 * i + 1] + yo);
     return q;
 }
 
-int host_match(visfs_scan_stack* st, Search& s, const visfs_scan_stack_params& p, visfs_scan_stack_result* out) {
+int host_search(const Levels& lv, const Search& s, Last& now, std::string& why) {
     const Plan& P = s.P;
     const int32_t n = P.n, nl = P.nl, L = P.Lw, H = s.H, mH = s.mH, per = mH * mH;
     std::vector<int32_t> cells(2 * (size_t)P.S * n);
@@ -381,13 +242,13 @@ int host_match(visfs_scan_stack* st, Search& s, const visfs_scan_stack_params& p
             scan::discretise(P.rot[2 * k], P.rot[2 * k + 1], P.pts[2 * i], P.pts[2 * i + 1], P.gx, P.gy, P.L.res, P.L.max_x, P.L.max_y,
                              cells[2 * ((size_t)k * n + i)], cells[2 * ((size_t)k * n + i) + 1]);
     auto scan_cells = [&](int32_t k) { return cells.data() + 2 * (size_t)k * n; };
-    Last now;
+    now = Last();
     now.S = P.S; now.L = L; now.n = n; now.H = H; now.mH = mH;
     now.bounds.resize((size_t)s.top());
     for (int32_t id = 0; id < s.top(); ++id) {
         int32_t k, i, j;
         node_decode(mH, id, k, i, j);
-        now.bounds[id] = host_node_sum(scan_cells(k), n, st->lv.v[H], -nl + (i << H), -nl + (j << H));
+        now.bounds[id] = host_node_sum(scan_cells(k), n, lv.v[H], -nl + (i << H), -nl + (j << H));
     }
     int32_t B = 0;
     for (int32_t k = 0; k < P.S; ++k) {                                    // the greedy descents
@@ -400,7 +261,7 @@ int host_match(visfs_scan_stack* st, Search& s, const visfs_scan_stack_params& p
             for (int w = 0; w < 4; ++w) {
                 const int32_t ci = 2 * i + (w >> 1), cj = 2 * j + (w & 1);
                 if (ci >= m || cj >= m) continue;
-                const int32_t U = host_node_sum(scan_cells(k), n, st->lv.v[h - 1], -nl + (ci << (h - 1)), -nl + (cj << (h - 1)));
+                const int32_t U = host_node_sum(scan_cells(k), n, lv.v[h - 1], -nl + (ci << (h - 1)), -nl + (cj << (h - 1)));
                 if (U > bu) { bu = U; bw = w; }
             }
             cur = bu; i = 2 * i + (bw >> 1); j = 2 * j + (bw & 1);
@@ -412,7 +273,7 @@ int host_match(visfs_scan_stack* st, Search& s, const visfs_scan_stack_params& p
     now.c.scored[H] = s.top();
     for (int32_t id = 0; id < s.top(); ++id)
         if (now.bounds[id] >= B) { ++now.c.kept[H]; if ((int32_t)F.size() < s.cap) F.push_back(make_int2(id, now.bounds[id])); }
-    if (now.c.kept[H] > s.cap) return sfail(st, VISFS_BA_ERR_UNSUPPORTED, overflow_text(H, s.cap));
+    if (now.c.kept[H] > s.cap) { why = overflow_text(H, s.cap); return VISFS_BA_ERR_UNSUPPORTED; }
     for (int32_t h = H; h >= 1; --h) {
         const int32_t mh = nodes_per_axis(L, h), ml = nodes_per_axis(L, h - 1), half = 1 << (h - 1);
         G.clear();
@@ -422,25 +283,37 @@ int host_match(visfs_scan_stack* st, Search& s, const visfs_scan_stack_params& p
             for (int a = 0; a < 4; ++a) {
                 const int32_t ci = 2 * i + (a >> 1), cj = 2 * j + (a & 1);
                 if (ci >= ml || cj >= ml) continue;
-                const int32_t U = host_node_sum(scan_cells(k), n, st->lv.v[h - 1], -nl + ci * half, -nl + cj * half);
+                const int32_t U = host_node_sum(scan_cells(k), n, lv.v[h - 1], -nl + ci * half, -nl + cj * half);
                 ++now.c.scored[h - 1];
                 if (U < B) continue;
                 ++now.c.kept[h - 1];
                 if ((int32_t)G.size() < s.cap) G.push_back(make_int2(node_id(ml, k, ci, cj), U));
             }
         }
-        if (now.c.kept[h - 1] > s.cap) return sfail(st, VISFS_BA_ERR_UNSUPPORTED, overflow_text(h - 1, s.cap));
+        if (now.c.kept[h - 1] > s.cap) { why = overflow_text(h - 1, s.cap); return VISFS_BA_ERR_UNSUPPORTED; }
         F.swap(G);
     }
     int32_t u = -1, id = INT_MAX;
     for (const int2& e : F) if (better(e.y, e.x, u, id)) { u = e.y; id = e.x; }
-    if (id == INT_MAX) return sfail(st, VISFS_BA_ERR_DEVICE, "the search returned no candidate");
+    if (id == INT_MAX) { why = "the search returned no candidate"; return VISFS_BA_ERR_DEVICE; }
     now.c.best_index = id; now.c.best_sum = u;
     std::sort(F.begin(), F.end(), [](const int2& a, const int2& b) { return a.x < b.x; });
     now.survivors = (int32_t)F.size();
     now.surv.swap(F);
     now.have = true;
-    finish(s, p, id, u, out);
+    return VISFS_BA_OK;
+}
+
+}  // namespace scanfast
+
+namespace {
+
+int host_match(visfs_scan_stack* st, Search& s, const visfs_scan_stack_params& p, visfs_scan_stack_result* out) {
+    Last now;
+    std::string why;
+    const int rc = host_search(st->lv, s, now, why);
+    if (rc != VISFS_BA_OK) return sfail(st, rc, why);
+    finish(s, p, now.c.best_index, now.c.best_sum, out);
     st->last = std::move(now);
     return VISFS_BA_OK;
 }
@@ -602,22 +475,12 @@ int visfs_scan_stack_match(visfs_scan_stack* st, const visfs_scan_stack_params* 
                            visfs_scan_stack_result* out) {
     if (!st || !p || !g || !out || n < 0 || (n > 0 && !xyz)) return VISFS_BA_ERR_BAD_ARGUMENT;
     return guarded([&]() -> int {
-        if (n > VISFS_SCAN_FAST_MAX_POINTS) return sfail(st, VISFS_BA_ERR_UNSUPPORTED, "more than 16384 points");
-        for (int i = 0; i < 3; ++i) if (!std::isfinite(g[i])) return sfail(st, VISFS_BA_ERR_BAD_ARGUMENT, "the guess is not finite");
-        for (int64_t i = 0; i < 3 * (int64_t)n; ++i) if (!std::isfinite(xyz[i])) return sfail(st, VISFS_BA_ERR_BAD_ARGUMENT, "a point is not finite");
-        if (!std::isfinite(p->linear_search_window) || !std::isfinite(p->angular_search_window) || p->linear_search_window < 0.0 || p->angular_search_window < 0.0)
-            return sfail(st, VISFS_BA_ERR_BAD_ARGUMENT, "the search windows must be finite and not negative");
-        if (std::isnan(p->min_score)) return sfail(st, VISFS_BA_ERR_BAD_ARGUMENT, "min_score is not a number");
-        if (p->frontier_capacity < 4 || p->frontier_capacity > VISFS_SCAN_FAST_MAX_FRONTIER)
-            return sfail(st, VISFS_BA_ERR_BAD_ARGUMENT, "frontier_capacity must lie in [4, 2^26]");
-        if (n == 0) {                                                      // nothing to match: the guess back
-            std::memset(out, 0, sizeof *out);
-            out->match.x = g[0]; out->match.y = g[1]; out->match.yaw = g[2];
-            return (int)VISFS_BA_OK;
-        }
-        Search s;
         const char* why = "";
-        const int rc = make_search(st, *p, g, n, xyz, s, &why);
+        int rc = check_call(*p, g, n, xyz, &why);
+        if (rc != VISFS_BA_OK) return sfail(st, rc, why);
+        if (n == 0) { no_points(g, out); return (int)VISFS_BA_OK; }        // nothing to match: the guess back
+        Search s;
+        rc = make_search(st, *p, g, n, xyz, s, &why);
         if (rc != VISFS_BA_OK) return sfail(st, rc, why);
         return st->device ? device_match(st, s, *p, out) : host_match(st, s, *p, out);
     });

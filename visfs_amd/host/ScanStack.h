@@ -4,6 +4,9 @@
 // A ScanStack comes from ActiveSubmaps2D::freeze (a snapshot of a live sub-map: later insertions do not change it) or from a saved
 // grid (fromGrid: the cells and limits ActiveSubmaps2D::download and submaps() hand out).  A device stack runs on the stream of the
 // handle it was made on, which must outlive it.
+//
+// A ScanStackGroup (include/visfs_scan_group.h) matches one scan against several stacks in one call: the candidate sub-maps of a loop
+// closure, or every sub-map of a saved map.  On the device its launches, copies and waits do not grow with the number of stacks.
 #ifndef VISFS_AMD_SCAN_STACK_H
 #define VISFS_AMD_SCAN_STACK_H
 
@@ -14,6 +17,7 @@
 #include <vector>
 
 #include "visfs_scan_fast.h"
+#include "visfs_scan_group.h"
 
 namespace VISFS {
 
@@ -38,6 +42,7 @@ public:
     }
 
     bool valid() const { return st_ != nullptr; }
+    visfs_scan_stack* get() const { return st_; }
     visfs_scan_stack_info info() const { visfs_scan_stack_info i{}; visfs_scan_stack_describe(st_, &i); return i; }
 
     // The pose guess (x, y, yaw) corrected by the search of the returns (robot frame, xyz triples) within the windows of `params`
@@ -59,6 +64,69 @@ public:
 
 private:
     visfs_scan_stack* st_ = nullptr;
+};
+
+// Several stacks of one flavour (device stacks of one handle, or host twins) with equal resolution and depth, searched in one call.
+// The stacks must outlive the group; a stack may be in several groups.
+class ScanStackGroup {
+public:
+    // Throws std::runtime_error when creation fails; the text names the offending member.
+    explicit ScanStackGroup(const std::vector<const ScanStack*>& stacks) {
+        std::vector<visfs_scan_stack*> m;
+        for (const ScanStack* s : stacks) m.push_back(s ? s->get() : nullptr);
+        const int rc = visfs_scan_group_create((int32_t)m.size(), m.data(), &g_);
+        if (rc != VISFS_BA_OK)
+            throw std::runtime_error("visfs_scan_group_create failed with status " + std::to_string(rc) + ": " + visfs_scan_group_last_error(nullptr));
+        m_ = m.size();
+    }
+    ScanStackGroup(const ScanStackGroup&) = delete;
+    ScanStackGroup& operator=(const ScanStackGroup&) = delete;
+    ~ScanStackGroup() { visfs_scan_group_destroy(g_); }
+
+    size_t size() const { return m_; }
+
+    // One member's outcome: ok is false when its frontier overflowed (the other fields are then not filled).
+    struct Match : ScanStack::Match { bool ok = false; int32_t sum = 0; };
+    // The returns (robot frame, xyz triples) against every member, each about its own guess (guesses: [size()][3]).  `best` gets the
+    // matched member of the largest sum (the lowest index among equal sums), or -1.
+    int match(const std::vector<double>& guesses, const std::vector<double>& returns, std::vector<Match>* out, int* best,
+              const visfs_scan_stack_params* params = nullptr, std::vector<visfs_scan_stack_result>* full = nullptr) const {
+        if (guesses.size() != 3 * m_) return VISFS_BA_ERR_BAD_ARGUMENT;
+        visfs_scan_stack_params p;
+        if (params) p = *params; else visfs_scan_stack_default_params(&p);
+        std::vector<visfs_scan_stack_result> r(m_);
+        std::vector<int32_t> status(m_);
+        int32_t b = -1;
+        const int rc = visfs_scan_group_match(g_, &p, guesses.data(), (int32_t)(returns.size() / 3), returns.data(), r.data(), status.data(), &b);
+        if (rc != VISFS_BA_OK) return rc;
+        if (out) {
+            out->assign(m_, Match());
+            for (size_t i = 0; i < m_; ++i) {
+                if (status[i] != VISFS_BA_OK) continue;
+                Match& o = (*out)[i];
+                o.ok = true; o.x = r[i].match.x; o.y = r[i].match.y; o.yaw = r[i].match.yaw; o.score = r[i].match.score; o.sum = r[i].match.sum;
+                o.matched = r[i].match.matched != 0;
+            }
+        }
+        if (best) *best = b;
+        if (full) *full = r;
+        return rc;
+    }
+
+    // what the last match issued on the device (all zero for host twins)
+    void lastCounts(int* launches, int* copies, int* synchronisations) const {
+        int32_t k = 0, c = 0, s = 0;
+        visfs_scan_group_last_counts(g_, &k, &c, &s);
+        if (launches) *launches = k;
+        if (copies) *copies = c;
+        if (synchronisations) *synchronisations = s;
+    }
+
+    const char* lastError() const { return visfs_scan_group_last_error(g_); }
+
+private:
+    visfs_scan_group* g_ = nullptr;
+    size_t m_ = 0;
 };
 
 }  // namespace VISFS
