@@ -3,11 +3,13 @@
 // weighted correlative match (include/visfs_scan_match.h) as relocalise_step.cpp does, and would then go to the window solve.
 //
 //   g++ -std=c++17 -O2 -Iinclude -Ivisfs_amd/host examples/loop_closure_step.cpp -Lvisfs_amd/lib -lvisfs_ba_hip
-//       -Wl,-rpath,$PWD/visfs_amd/lib -o loop_closure_step && ./loop_closure_step [host]
+//       -Wl,-rpath,$PWD/visfs_amd/lib -o loop_closure_step && ./loop_closure_step [host] [refine]
 //
 // The room and the pillar are those of relocalise_step.cpp.  With LocalMap/NumRangeDataLimit = 3 a sub-map is finished (and cropped)
 // after six insertions and dropped at the next one; twelve frames along the arc finish three, each frozen while it is the front.
-// `host` runs the insertions, the stacks, the group and the local match on the one-core host twins.  Prints one JSON line.
+// `host` runs the insertions, the stacks, the group and the local match on the one-core host twins.  `refine` makes the group call
+// visfs_scan_group_match_refine (include/visfs_scan_refine.h): every matched member's pose leaves the search lattice in the same call,
+// and the best member's refined pose, its costs and the trace of its information matrix join the output.  Prints one JSON line.
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -83,6 +85,10 @@ struct Summary {
     std::vector<double> scores;
     std::vector<int> matched, cells_x;
     double err_before = 0.0, err_closure = 0.0, yaw_err_closure = 0.0, err_refined = 0.0, yaw_err_refined = 0.0, angular_step = 0.0;
+    // with `refine`: the members refined in the group call, and the best member's refinement
+    std::vector<int> subcell;
+    int subcell_iterations = 0;
+    double err_subcell = 0.0, yaw_err_subcell = 0.0, cost_before = 0.0, cost_after = 0.0, information_trace = 0.0;
 };
 
 // What the two flavours differ in: inserting a frame, whether the front is finished, freezing it, and the local match on the front.
@@ -93,7 +99,7 @@ struct Map {
     std::function<int(const double g[3], const std::vector<double>& returns, visfs_scan_match_result* out)> local_match;
 };
 
-inline int run(const Map& map, Summary& out) {
+inline int run(const Map& map, Summary& out, bool refine) {
     Rng rng{ 99 };
     std::vector<VISFS::ScanStack> stacks;
     for (int f = 0; f < kFrames; ++f) {
@@ -120,7 +126,12 @@ inline int run(const Map& map, Summary& out) {
     const visfs_scan_stack_params wp = wide_search();
     std::vector<VISFS::ScanStackGroup::Match> ms;
     std::vector<visfs_scan_stack_result> full;
-    int rc = group.match(guesses, ret, &ms, &out.best, &wp, &full);
+    std::vector<VISFS::RefinedPose> fp;
+    // the group call refines towards each member's guess; a loop closure's guess has drifted by a metre, so it gets no weight here
+    visfs_scan_refine_params rp;
+    visfs_scan_refine_default_params(&rp);
+    rp.translation_weight = 0.0;
+    int rc = refine ? group.matchRefine(guesses, ret, &ms, &out.best, &fp, &wp, &rp, &full) : group.match(guesses, ret, &ms, &out.best, &wp, &full);
     if (rc != VISFS_BA_OK) { std::fprintf(stderr, "group match failed: %d (%s)\n", rc, group.lastError()); return 1; }
     group.lastCounts(&out.launches, &out.copies, &out.waits);
     for (const VISFS::ScanStackGroup::Match& m : ms) { out.scores.push_back(m.ok ? m.score : -1.0); out.matched.push_back(m.ok && m.matched ? 1 : 0); }
@@ -130,6 +141,14 @@ inline int run(const Map& map, Summary& out) {
     out.depth_used = w.depth_used; out.num_linear = w.match.num_linear; out.angular_step = w.match.angular_step;
     out.err_closure = std::max(std::fabs(w.match.x - truth[0]), std::fabs(w.match.y - truth[1]));
     out.yaw_err_closure = std::fabs(w.match.yaw - truth[2]);
+    if (refine) {
+        for (const VISFS::RefinedPose& f : fp) out.subcell.push_back(f.refined ? 1 : 0);
+        const VISFS::RefinedPose& f = fp[(size_t)out.best];
+        out.subcell_iterations = f.iterations; out.cost_before = f.initialCost; out.cost_after = f.finalCost;
+        out.information_trace = f.information[0] + f.information[4] + f.information[8];
+        out.err_subcell = std::max(std::fabs(f.x - truth[0]), std::fabs(f.y - truth[1]));
+        out.yaw_err_subcell = std::fabs(f.yaw - truth[2]);
+    }
     const double g2[3] = { w.match.x, w.match.y, w.match.yaw };
     visfs_scan_match_result fine{};
     rc = map.local_match(g2, ret, &fine);
@@ -141,7 +160,7 @@ inline int run(const Map& map, Summary& out) {
 }
 
 // the one-core twins: host sub-maps over the C ABI, host stacks
-inline int run_host(Summary& out) {
+inline int run_host(Summary& out, bool refine) {
     visfs_submap_params sp;
     visfs_submap_default_params(&sp);
     sp.num_range_data_limit = kLimit;
@@ -170,13 +189,13 @@ inline int run_host(Summary& out) {
         visfs_scan_match_default_params(&lp);                                  // Cartographer's real-time defaults: 0.1 m, 20 degrees, weighted
         return visfs_scan_match(s, 0, &lp, g, (int32_t)(ret.size() / 3), ret.data(), r);
     };
-    const int rc = run(map, out);                                              // the stacks and the group go inside
+    const int rc = run(map, out, refine);                                              // the stacks and the group go inside
     visfs_submaps_destroy(s);
     return rc;
 }
 
 // the device: VISFS::Map::ActiveSubmaps2D, device stacks and the group's kernels on the handle's stream
-inline int run_device(visfs_ba_handle* ba, Summary& out) {
+inline int run_device(visfs_ba_handle* ba, Summary& out, bool refine) {
     VISFS::Map::ActiveSubmaps2D submaps(ba, kLimit);
     Map map;
     map.insert = [&submaps](const double T[12], const std::vector<double>& ret) {
@@ -195,7 +214,7 @@ inline int run_device(visfs_ba_handle* ba, Summary& out) {
     map.local_match = [&submaps](const double g[3], const std::vector<double>& ret, visfs_scan_match_result* r) {
         return submaps.match(g, ret, nullptr, nullptr, 0, r);
     };
-    return run(map, out);
+    return run(map, out, refine);
 }
 
 template <class T> std::string list(const std::vector<T>& v, const char* fmt) {
@@ -208,18 +227,22 @@ template <class T> std::string list(const std::vector<T>& v, const char* fmt) {
 }  // namespace loop_closure_step
 
 int main(int argc, char** argv) {
-    const bool host = argc > 1 && std::strcmp(argv[1], "host") == 0;
+    bool host = false, refine = false;
+    for (int i = 1; i < argc; ++i) {
+        if (std::strcmp(argv[i], "host") == 0) host = true;
+        else if (std::strcmp(argv[i], "refine") == 0) refine = true;
+    }
     loop_closure_step::Summary s;
     int rc;
     try {
     if (host) {
-        rc = loop_closure_step::run_host(s);
+        rc = loop_closure_step::run_host(s, refine);
     } else {
         visfs_ba_params prm;
         visfs_ba_default_params(&prm);
         visfs_ba_handle* ba = nullptr;
         if (visfs_ba_create(&prm, 0, &ba) != VISFS_BA_OK) { std::fprintf(stderr, "no MI355X / gfx950 device\n"); return 3; }
-        rc = loop_closure_step::run_device(ba, s);                             // the group, the stacks and the sub-maps go before the handle
+        rc = loop_closure_step::run_device(ba, s, refine);                             // the group, the stacks and the sub-maps go before the handle
         visfs_ba_destroy(ba);
     }
     } catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); return 1; }
@@ -227,10 +250,15 @@ int main(int argc, char** argv) {
     std::printf("{\"mode\": \"%s\", \"inserted\": %d, \"frozen\": %d, \"cells_x\": %s, \"scores\": %s, \"matched\": %s, \"best_member\": %d, "
                 "\"depth_used\": %d, \"num_linear\": %d, \"angular_step\": %.6g, \"err_before_m\": %.4g, \"err_closure_m\": %.17g, "
                 "\"yaw_err_closure\": %.17g, \"refined\": %d, \"err_refined_m\": %.17g, \"yaw_err_refined\": %.17g, \"launches\": %d, "
-                "\"copies\": %d, \"waits\": %d}\n",
+                "\"copies\": %d, \"waits\": %d",
                 host ? "host" : "device", s.inserted, s.frozen, loop_closure_step::list(s.cells_x, "%d").c_str(),
                 loop_closure_step::list(s.scores, "%.17g").c_str(), loop_closure_step::list(s.matched, "%d").c_str(), s.best, s.depth_used,
                 s.num_linear, s.angular_step, s.err_before, s.err_closure, s.yaw_err_closure, s.refined, s.err_refined, s.yaw_err_refined,
                 s.launches, s.copies, s.waits);
+    if (refine)
+        std::printf(", \"subcell\": %s, \"subcell_iterations\": %d, \"cost_before\": %.17g, \"cost_after\": %.17g, \"information_trace\": %.17g, "
+                    "\"err_subcell_m\": %.17g, \"yaw_err_subcell\": %.17g", loop_closure_step::list(s.subcell, "%d").c_str(), s.subcell_iterations,
+                    s.cost_before, s.cost_after, s.information_trace, s.err_subcell, s.yaw_err_subcell);
+    std::printf("}\n");
     return 0;
 }

@@ -3,10 +3,11 @@
 // a third of a radian, the weighted correlative match (include/visfs_scan_match.h) settles it locally, and the window solve takes it.
 //
 //   g++ -std=c++17 -O2 -Iinclude -Ivisfs_amd/host examples/relocalise_step.cpp -Lvisfs_amd/lib -lvisfs_ba_hip
-//       -Wl,-rpath,$PWD/visfs_amd/lib -o relocalise_step && ./relocalise_step [host]
+//       -Wl,-rpath,$PWD/visfs_amd/lib -o relocalise_step && ./relocalise_step [host] [refine]
 //
 // The room, the pillar and the five inserted frames are those of scan_match_step.cpp.  `host` runs the insertions, the stack and both
-// matches on the one-core host twins (no device, no window solve).  Prints one JSON line.
+// matches on the one-core host twins (no device, no window solve).  `refine` adds the sub-cell refinement of the settled pose on the live
+// sub-map (include/visfs_scan_refine.h) and its fields to the output.  Prints one JSON line.
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -18,6 +19,7 @@
 #include "visfs_ba.h"
 #include "visfs_scan_fast.h"
 #include "visfs_scan_match.h"
+#include "visfs_scan_refine.h"
 
 namespace relocalise_step {
 
@@ -64,7 +66,16 @@ struct Summary {
     int inserted = 0, matched = 0, refined = 0, solved = 0, num_scans = 0, num_linear = 0, depth_used = 0;
     double err_before = 0.0, err_reloc = 0.0, yaw_err_reloc = 0.0, err_refined = 0.0, yaw_err_refined = 0.0, angular_step = 0.0, score = 0.0,
            solve_err = -1.0;
+    // with `refine`: the sub-cell refinement of the settled pose
+    int subcell = 0, subcell_iterations = 0;
+    double err_subcell = 0.0, yaw_err_subcell = 0.0, cost_before = 0.0, cost_after = 0.0;
 };
+
+inline void report_subcell(const double truth[3], const visfs_scan_refine_result& f, Summary& out) {
+    out.subcell = f.refined; out.subcell_iterations = f.iterations; out.cost_before = f.initial_cost; out.cost_after = f.final_cost;
+    out.err_subcell = std::max(std::fabs(f.x - truth[0]), std::fabs(f.y - truth[1]));
+    out.yaw_err_subcell = std::fabs(f.yaw - truth[2]);
+}
 
 constexpr int kFrames = 5;
 constexpr int kDepth = 7;
@@ -97,7 +108,7 @@ inline void report(const double truth[3], const double guess[3], const visfs_sca
 }
 
 // the one-core twins: host sub-maps and a host stack over the C ABI
-inline int run_host(Summary& out) {
+inline int run_host(Summary& out, bool refine) {
     visfs_submap_params sp;
     visfs_submap_default_params(&sp);
     visfs_submaps* s = nullptr;
@@ -130,6 +141,15 @@ inline int run_host(Summary& out) {
         if (rc != VISFS_BA_OK) std::fprintf(stderr, "local match failed: %d (%s)\n", rc, visfs_submaps_last_error(s));
     }
     if (rc == VISFS_BA_OK) report(truth, guess, r, fine, out);
+    if (rc == VISFS_BA_OK && refine) {                                         // from the settled pose, held to its translation
+        visfs_scan_refine_params rp;
+        visfs_scan_refine_default_params(&rp);
+        const double a[3] = { fine.x, fine.y, fine.yaw };
+        visfs_scan_refine_result f;
+        rc = visfs_scan_refine(s, 0, &rp, a, a, n, ret.data(), &f);
+        if (rc != VISFS_BA_OK) std::fprintf(stderr, "refinement failed: %d (%s)\n", rc, visfs_submaps_last_error(s));
+        else report_subcell(truth, f, out);
+    }
     visfs_scan_stack_destroy(st);
     visfs_submaps_destroy(s);
     return rc == VISFS_BA_OK ? 0 : 1;
@@ -144,7 +164,7 @@ inline void rel(const double A[12], const double B[12], double out[12]) {
 }
 
 // the device: VISFS::Map::ActiveSubmaps2D and VISFS::ScanStack on the handle's stream, the recovered pose handed to the window solve
-inline int run_device(visfs_ba_handle* ba, Summary& out) {
+inline int run_device(visfs_ba_handle* ba, Summary& out, bool refine) {
     VISFS::Map::ActiveSubmaps2D submaps(ba);
     Rng rng{ 99 };
     std::vector<uint64_t> ids;
@@ -174,6 +194,13 @@ inline int run_device(visfs_ba_handle* ba, Summary& out) {
     rc = submaps.match(g2, ret, &m, &lp, 0, &fine);
     if (rc != VISFS_BA_OK) { std::fprintf(stderr, "local match failed: %d (%s)\n", rc, submaps.lastError()); return 1; }
     report(truth, guess, r, fine, out);
+    if (refine) {
+        const double a[3] = { m.x, m.y, m.yaw };
+        visfs_scan_refine_result f;
+        rc = submaps.refine(a, a, ret, nullptr, nullptr, 0, &f);
+        if (rc != VISFS_BA_OK) { std::fprintf(stderr, "refinement failed: %d (%s)\n", rc, submaps.lastError()); return 1; }
+        report_subcell(truth, f, out);
+    }
     // the window: the last two inserted poses and the new one at the recovered pose, odometry links from the true motion
     double Tn[12];
     planar(m.x, m.y, m.yaw, Tn);
@@ -211,24 +238,32 @@ inline int run_device(visfs_ba_handle* ba, Summary& out) {
 }  // namespace relocalise_step
 
 int main(int argc, char** argv) {
-    const bool host = argc > 1 && std::strcmp(argv[1], "host") == 0;
+    bool host = false, refine = false;
+    for (int i = 1; i < argc; ++i) {
+        if (std::strcmp(argv[i], "host") == 0) host = true;
+        else if (std::strcmp(argv[i], "refine") == 0) refine = true;
+    }
     relocalise_step::Summary s;
     int rc;
     if (host) {
-        rc = relocalise_step::run_host(s);
+        rc = relocalise_step::run_host(s, refine);
     } else {
         visfs_ba_params prm;
         visfs_ba_default_params(&prm);
         visfs_ba_handle* ba = nullptr;
         if (visfs_ba_create(&prm, 0, &ba) != VISFS_BA_OK) { std::fprintf(stderr, "no MI355X / gfx950 device\n"); return 3; }
-        rc = relocalise_step::run_device(ba, s);                               // the stack and the sub-maps go before the handle
+        rc = relocalise_step::run_device(ba, s, refine);                               // the stack and the sub-maps go before the handle
         visfs_ba_destroy(ba);
     }
     if (rc != 0) return 1;
     std::printf("{\"mode\": \"%s\", \"inserted\": %d, \"matched\": %d, \"depth_used\": %d, \"num_scans\": %d, \"num_linear\": %d, \"angular_step\": %.6g, "
                 "\"score\": %.17g, \"err_before_m\": %.4g, \"err_reloc_m\": %.17g, \"yaw_err_reloc\": %.17g, \"refined\": %d, \"err_refined_m\": %.17g, "
-                "\"yaw_err_refined\": %.17g, \"solved\": %d, \"solve_err_m\": %.4g}\n",
+                "\"yaw_err_refined\": %.17g, \"solved\": %d, \"solve_err_m\": %.4g",
                 host ? "host" : "device", s.inserted, s.matched, s.depth_used, s.num_scans, s.num_linear, s.angular_step, s.score, s.err_before,
                 s.err_reloc, s.yaw_err_reloc, s.refined, s.err_refined, s.yaw_err_refined, s.solved, s.solve_err);
+    if (refine)
+        std::printf(", \"subcell\": %d, \"subcell_iterations\": %d, \"cost_before\": %.17g, \"cost_after\": %.17g, \"err_subcell_m\": %.17g, "
+                    "\"yaw_err_subcell\": %.17g", s.subcell, s.subcell_iterations, s.cost_before, s.cost_after, s.err_subcell, s.yaw_err_subcell);
+    std::printf("}\n");
     return 0;
 }

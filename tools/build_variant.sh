@@ -8,7 +8,7 @@ cd "$(dirname "$0")/.."
 name=$1; shift
 src=${VISFS_BA_SRC:-visfs_amd/csrc}
 files=""
-for f in ba_kernels.hip ba_cov.hip ba_submap.hip ba_flow.hip ba_corners.hip ba_clahe.hip ba_pnp.hip ba_fund.hip ba_tracker.hip ba_scan.hip ba_scan_fast.hip ba_api.cpp; do
+for f in ba_kernels.hip ba_cov.hip ba_submap.hip ba_flow.hip ba_corners.hip ba_clahe.hip ba_pnp.hip ba_fund.hip ba_tracker.hip ba_scan.hip ba_scan_fast.hip ba_api.cpp ba_scan_group.hip ba_scan_refine.hip; do
   [ -f "$src/$f" ] && files="$files $src/$f"
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared "$@" -o visfs_amd/lib/libvisfs_ba_hip_$name.so $files -lpthread

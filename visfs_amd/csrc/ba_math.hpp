@@ -427,7 +427,8 @@ BA_HD void cubic_hermite(double p0, double p1, double p2, double p3, double x, d
     dfdx = c + x * (2.0 * b + 3.0 * a * x);
 }
 // [ceres-upstream] BiCubicInterpolator::Evaluate(r, c, f, dfdr, dfdc): four row splines, then the column spline.
-BA_HD void bicubic(const GridView& g, double r, double c, double& f, double& dfdr, double& dfdc) {
+// Grid: the GridView above, or any type with a grid_value(g, row, col) of its own (ba_scan_refine.hpp reads uint16 cells).
+template <class Grid> BA_HD void bicubic(const Grid& g, double r, double c, double& f, double& dfdr, double& dfdc) {
     const int row = static_cast<int>(floor(r)), col = static_cast<int>(floor(c));
     double fr[4], dfr[4];
     for (int i = 0; i < 4; ++i)

@@ -119,6 +119,7 @@ void stack_free(visfs_scan_stack* st) {
         for (Bounds& b : st->bnd) if (b.p) (void)hipFree(b.p);
         for (Frontier& f : st->fr) if (f.p) (void)hipFree(f.p);
     }
+    scanrefine::state_free(st->refine);
     delete st;
 }
 

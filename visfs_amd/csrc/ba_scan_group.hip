@@ -14,7 +14,11 @@
 // x is the single call's fixed grid divided by m, at least 1; no result depends on it (integer sums, integer atomics, the total order
 // of `better`).  The members share nothing but the scan, so member i's bytes are the single call's on that stack.  A group of
 // host-twin stacks runs the one-core twin (host_search) per member.
-#include "ba_scan_stack.hpp"
+//
+// visfs_scan_group_match_refine (include/visfs_scan_refine.h, section 9o) is the same sequence with the members' refinement jobs
+// appended to the upload, k_scan_refine (ba_scan_refine.hip) launched after k_group_best with the member as blockIdx.x, reading each
+// member's winner from its Ctrl, and the refinement records behind the Ctrl records in the one download.
+#include "ba_scan_refine.hpp"
 #include "../../include/visfs_scan_group.h"
 
 #include <algorithm>
@@ -90,7 +94,12 @@ struct visfs_scan_group {
     // change hands with the working ones after a call that ran to its end
     char* h_up = nullptr; char* d_up = nullptr; size_t up_cap = 0;
     int2* d_cells = nullptr; size_t cells_cap = 0;
-    Ctrl* d_ctrl = nullptr; Ctrl* h_ctrl = nullptr;   // [m]
+    Ctrl* d_ctrl = nullptr; Ctrl* h_ctrl = nullptr;   // [m], and behind them the refinement records [m]
+    // match_refine: the traces [m][kMaxTrials][kTraceItems] of the call in work ([0]) and of the hook ([1]); the twin's traces; the
+    // trials per member of the last call that ran to its end
+    double* d_rtrace[2] = { nullptr, nullptr };
+    std::vector<std::vector<double>> h_rtrace;
+    std::vector<int32_t> rtrials;
     Bounds bnd[2];
     Frontier fr[3];
     // the last call that ran to its end, per member (have = false: its status was not OK); the strides of the hook's arenas
@@ -131,6 +140,7 @@ void group_free(visfs_scan_group* g) {
         if (g->d_cells) (void)hipFree(g->d_cells);
         if (g->d_ctrl) (void)hipFree(g->d_ctrl);
         if (g->h_ctrl) (void)hipHostFree(g->h_ctrl);
+        for (double* p : g->d_rtrace) if (p) (void)hipFree(p);
         for (Bounds& b : g->bnd) if (b.p) (void)hipFree(b.p);
         for (Frontier& f : g->fr) if (f.p) (void)hipFree(f.p);
     }
@@ -139,15 +149,31 @@ void group_free(visfs_scan_group* g) {
 
 std::string member_text(int32_t i, const std::string& why) { return "member " + std::to_string(i) + ": " + why; }
 
-// Every member's search on the device: fills the Ctrl records of h_ctrl and leaves the frontier of level 0 in fr[*cur].
-int device_run(visfs_scan_group* g, const std::vector<Search>& ss, int* cur_out) {
+size_t ctrl_bytes(int32_t m) { return (size_t)m * sizeof(Ctrl); }
+size_t record_bytes(int32_t m) { return (size_t)m * sizeof(visfs_scan_refine_result); }
+visfs_scan_refine_result* records_of(Ctrl* c, int32_t m) { return reinterpret_cast<visfs_scan_refine_result*>(reinterpret_cast<char*>(c) + ctrl_bytes(m)); }
+
+// member i's refinement job of a match_refine call: the start is formed on the device from the member's Ctrl
+scanrefine::Job match_job(const visfs_scan_stack* st, const Search& s, double min_score, const Ctrl* ctrl, const double* rot) {
+    const double zero[3] = { 0.0, 0.0, 0.0 };
+    scanrefine::Job J = scanrefine::stack_job(st, zero, zero);
+    J.from_match = 1; J.na = s.P.na; J.nl = s.P.nl; J.S = s.P.S;
+    J.gx = s.P.gx; J.gy = s.P.gy; J.gyaw = s.P.gyaw; J.step = s.P.step; J.min_score = min_score;
+    J.ctrl = ctrl; J.rot = rot;
+    return J;
+}
+
+// Every member's search on the device: fills the Ctrl records of h_ctrl and leaves the frontier of level 0 in fr[*cur].  With `rp`
+// every matched member's refinement follows in the same sequence: its records come behind the Ctrl records.
+int device_run(visfs_scan_group* g, const std::vector<Search>& ss, int* cur_out, const scanrefine::Prm* rp = nullptr, double min_score = 0.0) {
     const int32_t m = (int32_t)g->mem.size();
     const Search& s0 = ss[0];
     const int32_t n = s0.P.n, S = s0.P.S, nl = s0.P.nl, L = s0.P.Lw, H = s0.H, mH = s0.mH, total = s0.top(), cap = s0.cap;
     const int64_t ncell = (int64_t)S * n;
     SG_HIP(g, hipSetDevice(g->dev));
     const size_t npts = 2 * (size_t)n, nrot = 2 * (size_t)S * m;
-    const size_t bytes = (npts + nrot) * sizeof(double) + (size_t)m * sizeof(Member);
+    const size_t match_bytes = (npts + nrot) * sizeof(double) + (size_t)m * sizeof(Member);
+    const size_t bytes = match_bytes + (rp ? (size_t)m * sizeof(scanrefine::Job) : 0);
     if (g->up_cap < bytes) {
         if (g->h_up) SG_HIP(g, hipHostFree(g->h_up));
         if (g->d_up) SG_HIP(g, hipFree(g->d_up));
@@ -158,9 +184,12 @@ int device_run(visfs_scan_group* g, const std::vector<Search>& ss, int* cur_out)
         g->up_cap = want;
     }
     if (!g->d_ctrl) {
-        SG_HIP(g, hipMalloc(reinterpret_cast<void**>(&g->d_ctrl), (size_t)m * sizeof(Ctrl)));
-        SG_HIP(g, hipHostMalloc(reinterpret_cast<void**>(&g->h_ctrl), (size_t)m * sizeof(Ctrl), hipHostMallocDefault));
+        SG_HIP(g, hipMalloc(reinterpret_cast<void**>(&g->d_ctrl), ctrl_bytes(m) + record_bytes(m)));
+        SG_HIP(g, hipHostMalloc(reinterpret_cast<void**>(&g->h_ctrl), ctrl_bytes(m) + record_bytes(m), hipHostMallocDefault));
     }
+    if (rp)
+        for (double*& p : g->d_rtrace)
+            if (!p) SG_HIP(g, hipMalloc(reinterpret_cast<void**>(&p), (size_t)m * scanrefine::kMaxTrials * scanrefine::kTraceItems * sizeof(double)));
     int rc;
     if ((rc = grow(g, &g->d_cells, &g->cells_cap, (size_t)m * (size_t)ncell)) != VISFS_BA_OK) return rc;
     if ((rc = grow(g, &g->bnd[0].p, &g->bnd[0].cap, (size_t)m * (size_t)total)) != VISFS_BA_OK) return rc;
@@ -175,6 +204,13 @@ int device_run(visfs_scan_group* g, const std::vector<Search>& ss, int* cur_out)
         Member M;
         M.gx = P.gx; M.gy = P.gy; M.res = P.L.res; M.max_x = P.L.max_x; M.max_y = P.L.max_y; M.lv = g->mem[i]->lv;
         std::memcpy(hmt + i, &M, sizeof M);
+    }
+    if (rp) {                                                              // the jobs point into the device's copies
+        const double* drot0 = reinterpret_cast<const double*>(g->d_up) + npts;
+        for (int32_t i = 0; i < m; ++i) {
+            const scanrefine::Job J = match_job(g->mem[i], ss[i], min_score, g->d_ctrl + i, drot0 + 2 * (size_t)S * i);
+            std::memcpy(g->h_up + match_bytes + (size_t)i * sizeof J, &J, sizeof J);
+        }
     }
     SG_HIP(g, hipMemcpyAsync(g->d_up, g->h_up, bytes, hipMemcpyHostToDevice, g->stream));
     ++g->copies;
@@ -198,7 +234,12 @@ int device_run(visfs_scan_group* g, const std::vector<Search>& ss, int* cur_out)
     }
     hipLaunchKernelGGL(k_group_best, dim3(1, (unsigned)m), wg, 0, g->stream, g->fr[cur].p, cap, g->d_ctrl);
     SG_HIP(g, hipGetLastError()); ++g->launches;
-    SG_HIP(g, hipMemcpyAsync(g->h_ctrl, g->d_ctrl, (size_t)m * sizeof(Ctrl), hipMemcpyDeviceToHost, g->stream));
+    if (rp) {
+        SG_HIP(g, (hipError_t)scanrefine::launch_refine(g->stream, m, reinterpret_cast<const scanrefine::Job*>(g->d_up + match_bytes), *rp, d,
+                                                        records_of(g->d_ctrl, m), g->d_rtrace[0]));
+        ++g->launches;
+    }
+    SG_HIP(g, hipMemcpyAsync(g->h_ctrl, g->d_ctrl, ctrl_bytes(m) + (rp ? record_bytes(m) : 0), hipMemcpyDeviceToHost, g->stream));
     ++g->copies;
     SG_HIP(g, hipStreamSynchronize(g->stream));
     ++g->syncs;
@@ -206,18 +247,27 @@ int device_run(visfs_scan_group* g, const std::vector<Search>& ss, int* cur_out)
     return VISFS_BA_OK;
 }
 
+// rp and refined: both or neither (visfs_scan_group_match_refine)
 int group_match(visfs_scan_group* g, const visfs_scan_stack_params& p, const double* guesses, int32_t n, const double* xyz,
-                visfs_scan_stack_result* results, int32_t* status, int32_t* best_member) {
+                visfs_scan_stack_result* results, int32_t* status, int32_t* best_member, const visfs_scan_refine_params* rp = nullptr,
+                visfs_scan_refine_result* refined = nullptr) {
     const int32_t m = (int32_t)g->mem.size();
     const char* why = "";
     int rc;
     for (int32_t i = 0; i < m; ++i)
         if ((rc = check_call(p, guesses + 3 * i, n, xyz, &why)) != VISFS_BA_OK) return gfail(g, rc, member_text(i, why));
+    if (rp)
+        for (int32_t i = 0; i < m; ++i)
+            if ((rc = scanrefine::check_call(*rp, guesses + 3 * i, guesses + 3 * i, n, xyz, &why)) != VISFS_BA_OK) return gfail(g, rc, member_text(i, why));
     if ((int64_t)m * p.frontier_capacity > (int64_t)VISFS_SCAN_GROUP_MAX_FRONTIER)
         return gfail(g, VISFS_BA_ERR_UNSUPPORTED, "members times frontier_capacity exceed 2^26");
     if (n == 0) {                                                          // nothing to match: every guess back
         g->launches = g->copies = g->syncs = 0;
         for (int32_t i = 0; i < m; ++i) { no_points(guesses + 3 * i, results + i); status[i] = VISFS_BA_OK; }
+        if (rp) {
+            for (int32_t i = 0; i < m; ++i) scanrefine::not_refined(VISFS_BA_OK, guesses[3 * i], guesses[3 * i + 1], guesses[3 * i + 2], refined + i);
+            g->rtrials.assign((size_t)m, 0);
+        }
         *best_member = -1;
         g->err.clear();
         return VISFS_BA_OK;
@@ -233,8 +283,10 @@ int group_match(visfs_scan_group* g, const visfs_scan_stack_params& p, const dou
     std::vector<Last> now((size_t)m);
     std::string first_overflow;
     int cur = 0;
+    scanrefine::Prm RP;
+    if (rp) RP = scanrefine::make_prm(*rp, n);
     if (g->device) {
-        if ((rc = device_run(g, ss, &cur)) != VISFS_BA_OK) return rc;
+        if ((rc = device_run(g, ss, &cur, rp ? &RP : nullptr, p.min_score)) != VISFS_BA_OK) return rc;
         for (int32_t i = 0; i < m; ++i) {
             const Ctrl& c = g->h_ctrl[i];
             const Search& s = ss[i];
@@ -267,6 +319,30 @@ int group_match(visfs_scan_group* g, const visfs_scan_stack_params& p, const dou
         if (results[i].match.matched && results[i].match.sum > best_sum) { best = i; best_sum = results[i].match.sum; }
     }
     *best_member = best;
+    if (rp) {
+        // a member that overflowed or stayed below min_score is not refined; the others from their winner towards their guess
+        std::vector<std::vector<double>> traces;
+        std::vector<int32_t> trials((size_t)m, 0);
+        if (!g->device) traces.resize((size_t)m);
+        for (int32_t i = 0; i < m; ++i) {
+            const double* gi = guesses + 3 * i;
+            if (status[i] != VISFS_BA_OK) { scanrefine::not_refined(status[i], gi[0], gi[1], gi[2], refined + i); continue; }
+            const visfs_scan_match_result& w = results[i].match;
+            if (!w.matched) { scanrefine::not_refined(VISFS_BA_OK, w.x, w.y, w.yaw, refined + i); continue; }
+            if (g->device) {
+                refined[i] = records_of(g->h_ctrl, m)[i];
+                if (!refined[i].refined) return gfail(g, VISFS_BA_ERR_DEVICE, member_text(i, "the refinement skipped a matched member"));
+            } else {
+                const double start[3] = { w.x, w.y, w.yaw };
+                traces[i].assign((size_t)scanrefine::kMaxTrials * scanrefine::kTraceItems, 0.0);
+                scanrefine::host_refine(scanrefine::stack_job(g->mem[i], start, gi), RP, ss[i].P.pts.data(), refined + i, traces[i].data());
+            }
+            trials[i] = refined[i].trials;
+        }
+        if (g->device) std::swap(g->d_rtrace[0], g->d_rtrace[1]);
+        g->h_rtrace.swap(traces);
+        g->rtrials.swap(trials);
+    }
     g->last = std::move(now);
     g->last_top = ss[0].top(); g->last_cap = ss[0].cap;
     g->err = first_overflow;
@@ -348,6 +424,30 @@ int visfs_scan_group_match_download(visfs_scan_group* g, int32_t member, int32_t
             int2* sv = reinterpret_cast<int2*>(survivors);
             std::sort(sv, sv + l.survivors, [](const int2& a, const int2& b) { return a.x < b.x; });
         }
+        return (int)VISFS_BA_OK;
+    });
+}
+
+int visfs_scan_group_match_refine(visfs_scan_group* g, const visfs_scan_stack_params* mp, const visfs_scan_refine_params* rp, const double* guesses,
+                                  int32_t n, const double* xyz, visfs_scan_stack_result* results, int32_t* status, int32_t* best_member,
+                                  visfs_scan_refine_result* refined) {
+    if (!g || !mp || !rp || !guesses || !results || !status || !best_member || !refined || n < 0 || (n > 0 && !xyz)) return VISFS_BA_ERR_BAD_ARGUMENT;
+    return guarded([&]() -> int { return group_match(g, *mp, guesses, n, xyz, results, status, best_member, rp, refined); });
+}
+
+int visfs_scan_group_refine_download(visfs_scan_group* g, int32_t member, int32_t cap, double* trace, int32_t* trials) {
+    if (!g || !trials || cap < 0) return VISFS_BA_ERR_BAD_ARGUMENT;
+    return guarded([&]() -> int {
+        if (member < 0 || member >= (int32_t)g->mem.size()) return gfail(g, VISFS_BA_ERR_BAD_ARGUMENT, "the group has no such member");
+        const int32_t nt = (size_t)member < g->rtrials.size() ? g->rtrials[(size_t)member] : 0;
+        *trials = nt;
+        if (!trace || nt == 0) return (int)VISFS_BA_OK;
+        if (cap < nt) return gfail(g, VISFS_BA_ERR_BAD_ARGUMENT, "the hook's array is too small");
+        const size_t bytes = (size_t)nt * scanrefine::kTraceItems * sizeof(double);
+        if (!g->device) { std::memcpy(trace, g->h_rtrace[(size_t)member].data(), bytes); return (int)VISFS_BA_OK; }
+        SG_HIP(g, hipSetDevice(g->dev));
+        SG_HIP(g, hipMemcpyAsync(trace, g->d_rtrace[1] + (size_t)member * scanrefine::kMaxTrials * scanrefine::kTraceItems, bytes, hipMemcpyDeviceToHost, g->stream));
+        SG_HIP(g, hipStreamSynchronize(g->stream));
         return (int)VISFS_BA_OK;
     });
 }

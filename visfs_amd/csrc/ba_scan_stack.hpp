@@ -33,6 +33,12 @@ struct Search {
 
 }  // namespace scanfast
 
+// the buffers of visfs_scan_stack_refine on a stack (ba_scan_refine.hip), made by its first call
+namespace scanrefine {
+struct State;
+void state_free(State* s);
+}
+
 struct visfs_scan_stack {
     bool device = false;
     int dev = 0;
@@ -54,6 +60,7 @@ struct visfs_scan_stack {
     scanfast::Bounds bnd[2];
     scanfast::Frontier fr[3];
     scanfast::Last last;
+    scanrefine::State* refine = nullptr;
 };
 
 namespace scanfast {

@@ -299,6 +299,8 @@ struct visfs_submaps {
     // the scan matcher's state (ba_scan.hip), freed with the sub-maps
     void* scan_state = nullptr;
     void (*scan_destroy)(void*) = nullptr;
+    void* refine_state = nullptr;
+    void (*refine_destroy)(void*) = nullptr;
 };
 
 namespace {
@@ -643,6 +645,11 @@ void visfs_submaps_destroy(visfs_submaps* s) {
         s->scan_destroy(s->scan_state);
         s->scan_state = nullptr;
     }
+    if (s->refine_state && s->refine_destroy) {
+        if (s->device) { (void)hipSetDevice(s->dev); if (s->stream) (void)hipStreamSynchronize(s->stream); }
+        s->refine_destroy(s->refine_state);
+        s->refine_state = nullptr;
+    }
     release(s);
     delete s;
 }
@@ -807,4 +814,9 @@ int visfs_internal_scan_fail(visfs_submaps* s, int rc, const char* why) { return
 void** visfs_internal_scan_slot(visfs_submaps* s, void (*destroy)(void*)) {
     s->scan_destroy = destroy;
     return &s->scan_state;
+}
+
+void** visfs_internal_refine_slot(visfs_submaps* s, void (*destroy)(void*)) {
+    s->refine_destroy = destroy;
+    return &s->refine_state;
 }

@@ -30,3 +30,5 @@ int visfs_internal_scan_access(visfs_submaps* s, int32_t index, submap::ScanAcce
 int visfs_internal_scan_fail(visfs_submaps* s, int rc, const char* why);
 // The matcher's state, kept by the sub-maps object and freed with `destroy` (on the sub-maps' device) when they go.
 void** visfs_internal_scan_slot(visfs_submaps* s, void (*destroy)(void*));
+// The same for the refinement's state (ba_scan_refine.hip).
+void** visfs_internal_refine_slot(visfs_submaps* s, void (*destroy)(void*));

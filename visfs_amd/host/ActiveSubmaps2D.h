@@ -6,7 +6,8 @@
 // the BA against it (Estimator.cpp:247-250 + Optimizer::localOptimize).  The grids stay on the device: there is no Submap2D object to
 // hand out; download() copies one to the host for those who want grid2Image.  match() is the correlative scan match that
 // Estimator::laserPretreatment names and leaves out (include/visfs_scan_match.h): it corrects a pose guess against a sub-map.
-// freeze() snapshots a sub-map as a VISFS::ScanStack (ScanStack.h) for relocalisation and loop closure.
+// freeze() snapshots a sub-map as a VISFS::ScanStack (ScanStack.h) for relocalisation and loop closure.  refine() takes a matched
+// pose off the search lattice (include/visfs_scan_refine.h).
 #ifndef VISFS_AMD_ACTIVE_SUBMAPS_2D_H
 #define VISFS_AMD_ACTIVE_SUBMAPS_2D_H
 
@@ -84,6 +85,20 @@ public:
         const int rc = visfs_scan_match(s_, index, &p, guess, (int32_t)(returns.size() / 3), returns.data(), &r);
         if (rc != VISFS_BA_OK) return rc;
         if (out) { out->x = r.x; out->y = r.y; out->yaw = r.yaw; out->score = r.score; out->matched = r.matched != 0; }
+        if (full) *full = r;
+        return rc;
+    }
+
+    // The pose `initial` (x, y, yaw; match()'s result) refined on sub-map `index` towards the translation `target` (the prediction):
+    // the continuous step that follows the correlative match (include/visfs_scan_refine.h).  Nothing in the sub-maps changes.
+    int refine(const double initial[3], const double target[2], const std::vector<double>& returns, RefinedPose* out,
+               const visfs_scan_refine_params* params = nullptr, int index = 0, visfs_scan_refine_result* full = nullptr) const {
+        visfs_scan_refine_params p;
+        if (params) p = *params; else visfs_scan_refine_default_params(&p);
+        visfs_scan_refine_result r;
+        const int rc = visfs_scan_refine(s_, index, &p, initial, target, (int32_t)(returns.size() / 3), returns.data(), &r);
+        if (rc != VISFS_BA_OK) return rc;
+        if (out) *out = RefinedPose::from(r);
         if (full) *full = r;
         return rc;
     }

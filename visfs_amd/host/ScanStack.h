@@ -7,6 +7,9 @@
 //
 // A ScanStackGroup (include/visfs_scan_group.h) matches one scan against several stacks in one call: the candidate sub-maps of a loop
 // closure, or every sub-map of a saved map.  On the device its launches, copies and waits do not grow with the number of stacks.
+//
+// refine / matchRefine (include/visfs_scan_refine.h) take a matched pose off the search lattice: the continuous refinement of the
+// occupied-space cost on the same grid, with a pull towards a target translation and the start's yaw.
 #ifndef VISFS_AMD_SCAN_STACK_H
 #define VISFS_AMD_SCAN_STACK_H
 
@@ -18,8 +21,24 @@
 
 #include "visfs_scan_fast.h"
 #include "visfs_scan_group.h"
+#include "visfs_scan_refine.h"
 
 namespace VISFS {
+
+// A refined pose with the 3 x 3 information matrix (J^T J, row-major over x, y, yaw) of the constraint it stands for.
+struct RefinedPose {
+    double x = 0.0, y = 0.0, yaw = 0.0, initialCost = 0.0, finalCost = 0.0;
+    double information[9] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };
+    int iterations = 0;
+    bool refined = false;                     // false: nothing to refine (no returns, no sub-map yet, a skipped member): the start back
+    static RefinedPose from(const visfs_scan_refine_result& r) {
+        RefinedPose o;
+        o.x = r.x; o.y = r.y; o.yaw = r.yaw; o.initialCost = r.initial_cost; o.finalCost = r.final_cost;
+        for (int i = 0; i < 9; ++i) o.information[i] = r.information[i];
+        o.iterations = r.iterations; o.refined = r.refined != 0;
+        return o;
+    }
+};
 
 class ScanStack {
 public:
@@ -56,6 +75,20 @@ public:
         const int rc = visfs_scan_stack_match(st_, &p, guess, (int32_t)(returns.size() / 3), returns.data(), &r);
         if (rc != VISFS_BA_OK) return rc;
         if (out) { out->x = r.match.x; out->y = r.match.y; out->yaw = r.match.yaw; out->score = r.match.score; out->matched = r.match.matched != 0; }
+        if (full) *full = r;
+        return rc;
+    }
+
+    // The pose `initial` (x, y, yaw; a match's winner) refined on the grid's level 0 towards the translation `target` (x, y; the
+    // prediction).  params == nullptr: Cartographer's weights 1, 10, 40.
+    int refine(const double initial[3], const double target[2], const std::vector<double>& returns, RefinedPose* out,
+               const visfs_scan_refine_params* params = nullptr, visfs_scan_refine_result* full = nullptr) const {
+        visfs_scan_refine_params p;
+        if (params) p = *params; else visfs_scan_refine_default_params(&p);
+        visfs_scan_refine_result r;
+        const int rc = visfs_scan_stack_refine(st_, &p, initial, target, (int32_t)(returns.size() / 3), returns.data(), &r);
+        if (rc != VISFS_BA_OK) return rc;
+        if (out) *out = RefinedPose::from(r);
         if (full) *full = r;
         return rc;
     }
@@ -107,6 +140,41 @@ public:
                 o.ok = true; o.x = r[i].match.x; o.y = r[i].match.y; o.yaw = r[i].match.yaw; o.score = r[i].match.score; o.sum = r[i].match.sum;
                 o.matched = r[i].match.matched != 0;
             }
+        }
+        if (best) *best = b;
+        if (full) *full = r;
+        return rc;
+    }
+
+    // match, and in the same call every matched member's winner refined towards its guess's translation (refined[i].refined is false
+    // for a member that overflowed or stayed below min_score).  On the device: one launch more than match.
+    int matchRefine(const std::vector<double>& guesses, const std::vector<double>& returns, std::vector<Match>* out, int* best,
+                    std::vector<RefinedPose>* refined, const visfs_scan_stack_params* params = nullptr,
+                    const visfs_scan_refine_params* refineParams = nullptr, std::vector<visfs_scan_stack_result>* full = nullptr) const {
+        if (guesses.size() != 3 * m_) return VISFS_BA_ERR_BAD_ARGUMENT;
+        visfs_scan_stack_params p;
+        if (params) p = *params; else visfs_scan_stack_default_params(&p);
+        visfs_scan_refine_params q;
+        if (refineParams) q = *refineParams; else visfs_scan_refine_default_params(&q);
+        std::vector<visfs_scan_stack_result> r(m_);
+        std::vector<visfs_scan_refine_result> f(m_);
+        std::vector<int32_t> status(m_);
+        int32_t b = -1;
+        const int rc = visfs_scan_group_match_refine(g_, &p, &q, guesses.data(), (int32_t)(returns.size() / 3), returns.data(), r.data(), status.data(), &b,
+                                                     f.data());
+        if (rc != VISFS_BA_OK) return rc;
+        if (out) {
+            out->assign(m_, Match());
+            for (size_t i = 0; i < m_; ++i) {
+                if (status[i] != VISFS_BA_OK) continue;
+                Match& o = (*out)[i];
+                o.ok = true; o.x = r[i].match.x; o.y = r[i].match.y; o.yaw = r[i].match.yaw; o.score = r[i].match.score; o.sum = r[i].match.sum;
+                o.matched = r[i].match.matched != 0;
+            }
+        }
+        if (refined) {
+            refined->clear();
+            for (size_t i = 0; i < m_; ++i) refined->push_back(RefinedPose::from(f[i]));
         }
         if (best) *best = b;
         if (full) *full = r;
