@@ -6,30 +6,10 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from helpers import drop_refs, rel_err
+from helpers import drop_refs, random_case, rel_err
 from visfs_amd import abi, synth
 
 pytestmark = pytest.mark.gpu
-
-
-def random_case(i):
-    rng = np.random.default_rng(9000 + i)
-    n_kf = int(rng.integers(2, 15))
-    n_lm = int(rng.integers(20, 400))
-    track = int(rng.integers(2, min(n_kf, 8) + 1))
-    n_obs = n_lm * track
-    laser = bool(rng.random() < 0.25) and n_kf >= 3
-    if laser:
-        w = synth.make_laser_window(n_kf=max(n_kf, 3), n_points=int(rng.integers(50, 600)), with_visual=bool(rng.random() < 0.7), seed=i)
-    else:
-        w = synth.make_window("custom", n_kf=n_kf, n_lm=n_lm, n_obs=n_obs, odo=bool(rng.random() < 0.5), seed=777 + i,
-                              fixed_frac=float(rng.choice([0.0, 0.2, 0.6])), point_noise=float(rng.choice([0.02, 0.05, 0.3])),
-                              outlier_frac=float(rng.choice([0.0, 0.02, 0.1])))
-    if len(w["ref_feature"]) and rng.random() < 0.6:                     # ragged tracks, landmarks with 0 / 1 observations
-        w = drop_refs(w, rng.random(len(w["ref_feature"])) > rng.uniform(0.05, 0.4))
-    prm = dict(iterations=int(rng.choice([2, 4, 10, 20])), solver=int(rng.choice([0, 2])), trust_region=int(rng.random() < 0.2),
-               robust_kernel_delta=float(rng.choice([8.0, 8.0, 2.0, 0.0])))
-    return w, prm
 
 
 @pytest.mark.parametrize("i", range(32))

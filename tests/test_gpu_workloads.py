@@ -596,8 +596,10 @@ def test_banded_solver_keeps_the_checker_s_accuracy_on_ill_conditioned_systems(o
     """VERDICT r03 item 3.  Windows without enough landmarks on some pose (random cases whose reduced system has cond(S) of 1e8 at
     lambda = 1e-2 and 1e11 at 1e-5): the reference-default solver is a backward-stable Cholesky (Parameters.h:185), and production windows
     have no fixed pose (Estimator.cpp:252), so S is routinely this badly conditioned.  k_band_chol must solve ITS system as accurately as
-    the checker's scalar Cholesky solves its own — measured against numpy.linalg.solve on each side's S and b_s; round 3's closed-form
+    the checker's scalar Cholesky solves its own — measured against a long-double solve of each side's S and b_s (tests/solver_truth.py:
+    an fp64 numpy.linalg.solve is itself 1e-8 .. 1e-5 off at these condition numbers, no better than what it judged); round 3's closed-form
     pivot inverses were 1e2 (lambda = 1e-2) to 4e4 (1e-5) times worse (profiles/r03_stage_precision.log, profiles/r04_band_pivot_study.log)."""
+    import solver_truth
     import test_gpu_random as T
     w, kw = T.random_case(seed)
     o, s, gb = make_pair(olib, w, iterations=10, solver=0, robust_kernel_delta=kw["robust_kernel_delta"])
@@ -609,8 +611,8 @@ def test_banded_solver_keeps_the_checker_s_accuracy_on_ill_conditioned_systems(o
         assert ot[3] == gt[3] == 1                                                  # both factorisations succeed
         So = o.fetch(abi.BUF_S).reshape(n6, n6); Sg = s.fetch(abi.BUF_S).reshape(n6, n6)
         xo, xg = o.fetch(abi.BUF_DX_POSE), s.fetch(abi.BUF_DX_POSE)
-        eo = rel_err(xo, np.linalg.solve(So, o.fetch(abi.BUF_BS)))
-        eg = rel_err(xg, np.linalg.solve(Sg, s.fetch(abi.BUF_BS)))
+        eo = solver_truth.rel_err_ld(xo, solver_truth.solve_truth(So, o.fetch(abi.BUF_BS))[0])
+        eg = solver_truth.rel_err_ld(xg, solver_truth.solve_truth(Sg, s.fetch(abi.BUF_BS))[0])
         assert eg <= 10.0 * max(eo, 1e-13), (seed, lam, eo, eg)
     s.close(); o.close()
 

@@ -3049,7 +3049,8 @@ __global__ __launch_bounds__(1024) void k_chol_solve(const DeviceGraph g) {
 // triangular factor keeps that band.  This kernel factors the band block column by block column inside one workgroup — no dense
 // matrix, no launch per panel — and solves in the same launch.  The factorisation is the plain BLOCK CHOLESKY S = W W^T (6x6 blocks; the
 // diagonal block of W is the Cholesky factor C_k of the pivot block, the blocks below are W_ik = G_ik C_k^-T by a triangular solve per
-// row: nothing is ever inverted, so the factor is as accurate as a scalar Cholesky — see band_chol6 for the history).
+// row: the FACTORISATION and the forward substitution invert nothing, so the factor is as accurate as a scalar Cholesky — see band_chol6
+// for the history.  The BACKWARD substitution of bands of B <= 9 does form an inverse, see below).
 //   ring  [rows][B + 1][36]  LDS: block (I, I - d) of the lower band at [(I mod rows)][d]; rows == Npf when the whole band fits
 //                            (C2: 136 KB), else a sliding window of rows >= B + 3 block rows and the factor streams to band_L (HBM);
 //   step k (pivot factor C_k published, column k final and unscaled):
@@ -3058,7 +3059,17 @@ __global__ __launch_bounds__(1024) void k_chol_solve(const DeviceGraph g) {
 //             column k - 1;
 //     half 2  wave 0: D_{k+1} = C C^T (every lane redundantly, operands by LDS broadcast: no cross-lane traffic; positive definiteness
 //             = positive pivots) WHILE the helpers apply A_ij -= W_ik W_jk^T for k + 3 <= i, k < j <= i (twelve lanes a block);
-//   then the backward substitution on one wavefront (right-looking: x_k = C_k^-T z_k, z_j -= W_kj^T x_k) and K8 (pose oplus).
+//   then the backward substitution on one wavefront and K8 (pose oplus), in one of two forms:
+//     6 (B + 1) <= 64, i.e. B <= 9 (`fast_bwd`: every BASELINE window; resident and streaming, the streaming form transforms each reloaded
+//             chunk of rows the same way): X_k = C_k^-1 is FORMED EXPLICITLY (the triangular inverse of the 6x6 pivot factor by forward
+//             recurrence, a thread a row), the factor rows are rewritten in place as X_k W_kj, the chain u_j = y_j - sum_{k > j} (X_k W_kj)^T u_k
+//             then holds no triangular solve, and x_k = X_k^T u_k falls out in parallel afterwards.  X_k is the inverse of a 6x6 TRIANGULAR
+//             Cholesky factor computed by substitution (each column a backward-stable triangular solve), not of S or of a pivot block D_k:
+//             its error is u * cond(C_k) = u * sqrt(cond(D_k)) per block, which the solve as a whole already carries through cond(S) —
+//             but it is not the textbook backward-stable bound of two triangular solves, and it is held to a measurement instead:
+//             tests/test_gpu_solver_forms.py (both forms against a long-double solve of the device's own system, cond(S) up to 2e11:
+//             profiles/solver_forms_truth.log);
+//     B > 9   right-looking through LDS, triangular solves only: x_k = C_k^-T z_k (band_trsv_bwd), z_j -= W_kj^T x_k.
 // Every sum has a fixed order: results are bitwise reproducible.  A non-positive or non-finite pivot sets LmState::solver_failed: g2o's
 // solver returns false and the LM trial is rejected.
 constexpr int BAND_T = 256;
