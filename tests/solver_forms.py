@@ -50,7 +50,7 @@ def _case(window, solver, code, npf=None, env=None, tuning=None, seqs=(FRESH,), 
     return dict(window=window, solver=solver, code=code, npf=npf, env=dict(env or {}), tuning=tuning, seqs=tuple(seqs), band=band)
 
 
-def _custom(npf):
+def custom_window(npf):
     if npf <= 64:
         return ("custom", npf + 1, 400 + npf + 1)
     # (257 free poses: seeds 17 and 18 bring a stopping test of the commit sequence within 5 % of its threshold on the truth — replaced)
@@ -61,7 +61,7 @@ def _build_cases():
     cases = {}
     def pcg(form, code, sizes, env=None, tuning=None, both_first=True, window=None):
         for n, npf in enumerate(sizes):
-            cases[f"pcg-{form}-{npf}"] = _case(window or _custom(npf), 2, code, npf, env, tuning, (FRESH, COMMIT) if both_first and n == 0 else (FRESH,))
+            cases[f"pcg-{form}-{npf}"] = _case(window or custom_window(npf), 2, code, npf, env, tuning, (FRESH, COMMIT) if both_first and n == 0 else (FRESH,))
     pcg("small", 5, (1, 6, 7, 10))
     pcg("pcg1", 1, (11, 63, 64))
     pcg("pcg1-nosmall", 1, (1, 10), env={"VISFS_BA_SMALL_SOLVE": "0"}, both_first=False)
@@ -81,7 +81,7 @@ def _build_cases():
     def direct(name, window, code, env=None, npf=None, band=None):
         cases[f"direct-{name}"] = _case(window, 0, code, npf, env, None, (DIRECT,), band)
     for npf in (1, 5, 6, 10):
-        direct(f"small-{npf}", _custom(npf), 5, npf=npf)
+        direct(f"small-{npf}", custom_window(npf), 5, npf=npf)
     for seed in ILL_SEEDS:
         direct(f"band-ill{seed}", ("ill", seed), 7, band=("fast", None))
         direct(f"dense-ill{seed}", ("ill", seed), 6, env={"VISFS_BA_BAND": "0"})

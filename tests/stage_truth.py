@@ -1,0 +1,726 @@
+"""Extended-precision truth for every stage around the reduced-system solve: linearisation, Schur complement, back-substitution, the
+trial state and its sums.  Plain NumPy in numpy.longdouble.
+
+TEST INFRASTRUCTURE ONLY.  Imports nothing from visfs_amd and nothing from the oracle (as tests/solver_truth.py does not): it takes plain
+arrays — the fields of a packed graph (`graph` below) and the buffers fetched from one side — and restates the reference's formulae
+(OptimizeTypeDefine.h/.cpp: CameraPose, EdgeStereo, EdgePoseConstraint; TypeOccupiedSpace2D.h: EdgeOccupiedObservation; Math.h: deltaQ,
+QuaternionLeft / QuaternionRight; g2o's RobustKernelHuber, BlockSolver's Schur complement and computeScale; ceres' BiCubicInterpolator).
+
+Every stage is judged ON ITS OWN INPUTS, so that no stage's rounding is charged to the next:
+
+    err                 shared graph and committed state               |x - truth| / (|uvr| + |projection|)
+    chi2                the side's own err                             / the observation's own |truth|
+    weight              the side's own chi2                            / own |truth|
+    H_pl, H_ll, H_pp    the side's own weight, the truth's Jacobians   / the block's own |truth|_inf (sum|terms| where a laser or odometry term enters)
+    b_l, b_p            the side's own err and weight                  / sum|terms|
+    chi2_total          the side's own chi2 (+ odometry, laser)        / sum|terms|
+    max_diag            the side's own H_pp and H_ll diagonals         bit for bit (a maximum rounds nothing)
+    S, b_s              lambda and the side's own H_pp, b_p, H_pl, H_ll, b_l, weight     S / block |truth|_inf (sum|terms| reported too), b_s / sum|terms|
+    dx_point            the side's own dx_pose, b_l, H_pl, H_ll        / sum|terms|
+    pose_trial, point_trial   the side's own dx and the committed state / own |truth|_inf (translation and quaternion are blocks of their own)
+    trial_chi2          the side's own trial state                     / sum|terms|
+    scale               the side's own dx, b_p, b_l                    / sum|terms|
+
+The error of a stage is max over blocks of |x - truth|_inf / normaliser; a block is one observation's 6x3, 3-vector or scalar, one
+landmark, or one 6x6 pose block.  Where the truth of a block is exactly zero (an inactive edge, a fixed landmark, a level-1 edge) the
+fetched block must be exactly zero: anything else is an infinite error.  Laser and odometry residuals cannot be fetched; their
+contributions come from the shared inputs.
+
+`graph` is a dict of plain arrays and numbers:
+    pose_fixed [Np] bool, point_fixed [Nl] bool, obs_point [No], obs_pose [No], obs_uvr [No][3], odo_from [Ne], odo_to [Ne], odo_tq [Ne][7],
+    intr (fx, fy, cx, cy, bf), w_px, w_odo, w_laser (the information values AS THE PROGRAMS HOLD THEM: fp64 1/variance), delta,
+    laser: None or dict(pose, xyz [Nz][3], Tcr [12], resolution, max_x, max_y, cost [num_y][num_x] float32)
+"""
+import numpy as np
+
+from solver_truth import LD
+
+U = 2.0 ** -53                                   # unit roundoff of fp64
+K_PADDING = 2147483647 // 4                      # kPadding = INT_MAX / 4, TypeOccupiedSpace2D.h:20
+K_MAX_COST = LD(np.float64(1.0) - np.float64(0.1))   # Map::kMaxCorrespondenceCost = 1 - kMinProbability, a double
+INF = float("inf")
+
+
+def _ld(x):
+    return np.asarray(x, dtype=LD)
+
+
+def floor_of(n):
+    """The criterion's floor for a stage whose blocks sum n terms: the forward-error bound n u of a sum plus a fixed allowance for the
+    ~60 roundings of one edge's Jacobian chain."""
+    return (64 + n) * U
+
+
+# ===================================================================== quaternions (x y z w), Eigen semantics
+def quat_to_R(q):
+    """Eigen::Quaternion::toRotationMatrix(), no normalisation."""
+    q = _ld(q)
+    x, y, z, w = q[..., 0], q[..., 1], q[..., 2], q[..., 3]
+    tx, ty, tz = 2 * x, 2 * y, 2 * z
+    twx, twy, twz = tx * w, ty * w, tz * w
+    txx, txy, txz = tx * x, ty * x, tz * x
+    tyy, tyz, tzz = ty * y, tz * y, tz * z
+    R = np.empty(q.shape[:-1] + (3, 3), dtype=LD)
+    R[..., 0, 0] = 1 - (tyy + tzz); R[..., 0, 1] = txy - twz; R[..., 0, 2] = txz + twy
+    R[..., 1, 0] = txy + twz; R[..., 1, 1] = 1 - (txx + tzz); R[..., 1, 2] = tyz - twx
+    R[..., 2, 0] = txz - twy; R[..., 2, 1] = tyz + twx; R[..., 2, 2] = 1 - (txx + tyy)
+    return R
+
+
+def quat_mul(a, b):
+    a = _ld(a); b = _ld(b)
+    ax, ay, az, aw = a[..., 0], a[..., 1], a[..., 2], a[..., 3]
+    bx, by, bz, bw = b[..., 0], b[..., 1], b[..., 2], b[..., 3]
+    return np.stack([aw * bx + ax * bw + ay * bz - az * by, aw * by + ay * bw + az * bx - ax * bz,
+                     aw * bz + az * bw + ax * by - ay * bx, aw * bw - ax * bx - ay * by - az * bz], axis=-1)
+
+
+def quat_inv(q):
+    """Eigen::Quaternion::inverse(): conjugate / squaredNorm."""
+    q = _ld(q)
+    n2 = (q * q).sum(axis=-1, keepdims=True)
+    return q * np.array([-1, -1, -1, 1], dtype=LD) / n2
+
+
+def quat_normalize(q):
+    q = _ld(q)
+    return q / np.sqrt((q * q).sum(axis=-1, keepdims=True))
+
+
+def quat_positify(q):
+    """QuaternionPositify (Math.h) == CameraPose::normalizeRotation: w >= 0, unit norm."""
+    q = _ld(q)
+    return quat_normalize(np.where(q[..., 3:4] < 0, -q, q))
+
+
+def quat_rot(q, v):
+    """q * v for a unit quaternion: the rotation matrix applied (Eigen's _transformVector is the same function)."""
+    return np.einsum("...ij,...j->...i", quat_to_R(q), _ld(v))
+
+
+def skew(v):
+    """skewSymmetric (Math.h)."""
+    v = _ld(v)
+    S = np.zeros(v.shape[:-1] + (3, 3), dtype=LD)
+    S[..., 0, 1] = -v[..., 2]; S[..., 0, 2] = v[..., 1]
+    S[..., 1, 0] = v[..., 2]; S[..., 1, 2] = -v[..., 0]
+    S[..., 2, 0] = -v[..., 1]; S[..., 2, 1] = v[..., 0]
+    return S
+
+
+def _quat_lr4(q, sign):
+    """QuaternionLeft (sign +1) / QuaternionRight (-1) of the POSITIFIED quaternion, 4x4 in the order (w; x y z) (Math.h)."""
+    q = quat_positify(q)
+    w, v = q[..., 3], q[..., :3]
+    M = np.zeros(q.shape[:-1] + (4, 4), dtype=LD)
+    M[..., 0, 0] = w
+    M[..., 0, 1:] = -v
+    M[..., 1:, 0] = v
+    M[..., 1:, 1:] = w[..., None, None] * np.eye(3, dtype=LD) + sign * skew(v)
+    return M
+
+
+def quat_left4(q):
+    return _quat_lr4(q, 1)
+
+
+def quat_right4(q):
+    return _quat_lr4(q, -1)
+
+
+def pose_update(tq, d):
+    """CameraPose::update: t += d[:3]; q <- normalise(deltaQ(d[3:]) * q) with deltaQ = (d/2, 1) (first order, not normalised), no
+    re-positify."""
+    tq = _ld(tq); d = _ld(d)
+    dq = np.concatenate([d[..., 3:6] / 2, np.ones(d.shape[:-1] + (1,), dtype=LD)], axis=-1)
+    return np.concatenate([tq[..., :3] + d[..., :3], quat_normalize(quat_mul(dq, tq[..., 3:7]))], axis=-1)
+
+
+# ===================================================================== edges
+def stereo_edge(tq, pw, uvr, intr):
+    """EdgeStereo over n observations: (e [n][3], operand scale [n], Ji [n][3][3], Jj [n][3][6]).  The operand scale is
+    max(|uvr| + |projection|): what the subtraction uvr - project(map(pw)) cancels from."""
+    tq = _ld(tq).reshape(-1, 7); pw = _ld(pw).reshape(-1, 3); uvr = _ld(uvr).reshape(-1, 3)
+    fx, fy, cx, cy, bf = (LD(v) for v in intr)
+    R = quat_to_R(tq[:, 3:7])
+    pc = np.einsum("nij,nj->ni", R, pw) + tq[:, :3]
+    x, y, z = pc[:, 0], pc[:, 1], pc[:, 2]
+    inv_z = 1 / z
+    res = np.empty_like(pc)
+    res[:, 0] = x * inv_z * fx + cx
+    res[:, 1] = y * inv_z * fy + cy
+    res[:, 2] = res[:, 0] - bf * inv_z
+    e = uvr - res
+    scale = (np.abs(uvr) + np.abs(res)).max(axis=1)
+    z2 = z * z
+    n = len(tq)
+    Ji = np.empty((n, 3, 3), dtype=LD)
+    for c in range(3):
+        Ji[:, 0, c] = -fx * R[:, 0, c] / z + fx * x * R[:, 2, c] / z2
+        Ji[:, 1, c] = -fy * R[:, 1, c] / z + fy * y * R[:, 2, c] / z2
+        Ji[:, 2, c] = Ji[:, 0, c] - bf * R[:, 2, c] / z2
+    Jj = np.zeros((n, 3, 6), dtype=LD)
+    Jj[:, 0, 0] = -1 / z * fx
+    Jj[:, 0, 2] = x / z2 * fx
+    Jj[:, 0, 3] = x * y / z2 * fx
+    Jj[:, 0, 4] = -(1 + x * x / z2) * fx
+    Jj[:, 0, 5] = y / z * fx
+    Jj[:, 1, 1] = -1 / z * fy
+    Jj[:, 1, 2] = y / z2 * fy
+    Jj[:, 1, 3] = (1 + y * y / z2) * fy
+    Jj[:, 1, 4] = -x * y / z2 * fy
+    Jj[:, 1, 5] = -x / z * fy
+    Jj[:, 2, 0] = Jj[:, 0, 0]
+    Jj[:, 2, 2] = Jj[:, 0, 2] - bf / z2
+    Jj[:, 2, 3] = Jj[:, 0, 3] - bf * y / z2
+    Jj[:, 2, 4] = Jj[:, 0, 4] + bf * x / z2
+    Jj[:, 2, 5] = Jj[:, 0, 5]
+    return e, scale, Ji, Jj
+
+
+def odo_edge(tq1, tq2, m):
+    """EdgePoseConstraint over n edges ("Left update"): (e [n][6], Ji [n][6][6], Jj [n][6][6]); vertex 0 = tq1, vertex 1 = tq2."""
+    tq1 = _ld(tq1).reshape(-1, 7); tq2 = _ld(tq2).reshape(-1, 7); m = _ld(m).reshape(-1, 7)
+    P1, Q1, P2, Q2, mP, mQ = tq1[:, :3], tq1[:, 3:], tq2[:, :3], tq2[:, 3:], m[:, :3], m[:, 3:]
+    n = len(tq1)
+    Q2i = quat_inv(Q2)
+    Q12 = quat_mul(Q1, Q2i)
+    e = np.empty((n, 6), dtype=LD)
+    e[:, :3] = quat_rot(Q12, -P2) + P1 - mP
+    t2 = quat_mul(quat_mul(quat_inv(mQ), Q1), Q2i)
+    e[:, 3:] = 2 * t2[:, :3]
+    Ji = np.zeros((n, 6, 6), dtype=LD)
+    Ji[:, :3, :3] = np.eye(3, dtype=LD)
+    Ji[:, :3, 3:] = -skew(quat_rot(Q1, quat_rot(Q2i, -P2)))
+    LR = np.einsum("nij,njk->nik", quat_left4(quat_mul(Q2, quat_inv(Q1))), quat_right4(mQ))
+    Ji[:, 3:, 3:] = LR[:, 1:, 1:]
+    Jj = np.zeros((n, 6, 6), dtype=LD)
+    Jj[:, :3, :3] = -quat_to_R(Q12)
+    Jj[:, :3, 3:] = np.einsum("nij,njk,nkl->nil", quat_to_R(Q1), quat_to_R(Q2i), skew(-P2))
+    Jj[:, 3:, 3:] = -quat_left4(t2)[:, 1:, 1:]
+    return e, Ji, Jj
+
+
+def huber(chi2, delta):
+    """g2o's RobustKernelHuber::robustify: (rho, rho').  chi2 <= delta^2: (chi2, 1); else (2 sqrt(chi2) delta - delta^2, delta / sqrt(chi2)).
+    delta <= 0: no kernel."""
+    chi2 = _ld(chi2)
+    if not delta > 0:
+        return chi2.copy(), np.ones_like(chi2)
+    d = LD(delta)
+    inl = chi2 <= d * d
+    s = np.sqrt(np.where(inl, LD(1), chi2))
+    return np.where(inl, chi2, 2 * s * d - d * d), np.where(inl, LD(1), d / s)
+
+
+# ----------------------------------------------------------------- the laser edge
+class _Jet:
+    """A value with its six partials (ceres::Jet restricted to the six pose directions), over n range points."""
+
+    def __init__(self, a, v=None):
+        self.a = _ld(a)
+        self.v = np.zeros(self.a.shape + (6,), dtype=LD) if v is None else v
+
+    def __add__(self, o):
+        return _Jet(self.a + o.a, self.v + o.v)
+
+    def __sub__(self, o):
+        return _Jet(self.a - o.a, self.v - o.v)
+
+    def __mul__(self, o):
+        return _Jet(self.a * o.a, self.a[..., None] * o.v + self.v * o.a[..., None])
+
+    def __neg__(self):
+        return _Jet(-self.a, -self.v)
+
+    def times(self, k):
+        k = _ld(k)
+        return _Jet(self.a * k, self.v * (k[..., None] if k.ndim else k))
+
+
+def grid_value(grid, row, col):
+    """GridArrayAdapter::GetValue at (row - kPadding, col - kPadding): the float cost inside the grid, kMaxCorrespondenceCost on the
+    padding."""
+    cost = np.asarray(grid["cost"])
+    ny, nx = cost.shape
+    y = row; x = col                                                                  # (unpadded: see _laser_functor)
+    inside = (y >= 0) & (x >= 0) & (y < ny) & (x < nx)
+    out = np.full(row.shape, K_MAX_COST, dtype=LD)
+    out[inside] = cost[y[inside], x[inside]].astype(LD)
+    return out
+
+
+def _cubic_hermite(p0, p1, p2, p3, x):
+    """ceres CubicHermiteSpline<1> (Catmull-Rom): (f, df/dx)."""
+    a = (-p0 + 3 * p1 - 3 * p2 + p3) / 2
+    b = (2 * p0 - 5 * p1 + 4 * p2 - p3) / 2
+    c = (-p0 + p2) / 2
+    return p1 + x * (c + x * (b + x * a)), c + x * (2 * b + 3 * a * x)
+
+
+def bicubic(grid, r, c):
+    """ceres BiCubicInterpolator::Evaluate(r + kPadding, c + kPadding): (f, df/dr, df/dc): the four row splines, then the column spline."""
+    r = _ld(r); c = _ld(c)
+    row = np.floor(r).astype(np.int64); col = np.floor(c).astype(np.int64)
+    fr, dfr = [], []
+    for i in range(4):
+        p = [grid_value(grid, row - 1 + i, col - 1 + j) for j in range(4)]
+        f, df = _cubic_hermite(p[0], p[1], p[2], p[3], c - col)
+        fr.append(f); dfr.append(df)
+    f, dfdr = _cubic_hermite(fr[0], fr[1], fr[2], fr[3], r - row)
+    dfdc, _ = _cubic_hermite(dfr[0], dfr[1], dfr[2], dfr[3], r - row)
+    return f, dfdr, dfdc
+
+
+def _laser_functor(pose, P, Tcr, grid, exact=False):
+    """EdgeOccupiedObservation::operator() on jets: R of the quaternion WITHOUT normalisation, Twc = [R | t]^-1 * Tcr, Po = Twc * P, the
+    grid coordinates (max - Po) / resolution - 0.5 + kPadding.  The coordinate's VALUE is handed to the interpolator as a double (the
+    interpolator's signature): it is rounded to fp64 there, once, and nowhere else.  Beside kPadding = 2^29 a double has a spacing of
+    2^-23 cells, so that rounding is a DISCRETE decision: an fp64 evaluation whose own chain errs by up to tol = 64 u (|max| + |Po|) /
+    resolution cells may round a coordinate the other way when it lies within tol of a rounding boundary, and then differs by a whole
+    2^-23.  kPadding is an integer multiple of that spacing, so the rounding is taken on the coordinate WITHOUT kPadding (where long
+    double still resolves 1e-17 of a cell; with kPadding added it would resolve no more than 6e-11) and the interpolator below works on
+    unpadded rows and columns.  Returns (r, c, margin), r and c without kPadding: margin is the smallest distance of a coordinate from a rounding boundary in units of tol; a case is
+    admitted only with margin >= 1 (a condition on the input, as for Huber's threshold: take another seed)."""
+    x, y, z, w = pose[3], pose[4], pose[5], pose[6]
+    tx, ty, tz = x.times(2), y.times(2), z.times(2)
+    twx, twy, twz = tx * w, ty * w, tz * w
+    txx, txy, txz = tx * x, ty * x, tz * x
+    tyy, tyz, tzz = ty * y, tz * y, tz * z
+    one = _Jet(np.ones_like(x.a))
+    R = [[one - (tyy + tzz), txy - twz, txz + twy], [txy + twz, one - (txx + tzz), tyz - twx], [txz - twy, tyz + twx, one - (txx + tyy)]]
+    Ri = [[R[c][r] for c in range(3)] for r in range(3)]
+    ti = [-(Ri[r][0] * pose[0] + Ri[r][1] * pose[1] + Ri[r][2] * pose[2]) for r in range(3)]
+    T = _ld(Tcr).reshape(3, 4)
+    Po = []
+    for r in range(2):
+        L = [Ri[r][0].times(T[0, c]) + Ri[r][1].times(T[1, c]) + Ri[r][2].times(T[2, c]) for c in range(3)]
+        t = Ri[r][0].times(T[0, 3]) + Ri[r][1].times(T[1, 3]) + Ri[r][2].times(T[2, 3]) + ti[r]
+        Po.append(L[0].times(P[:, 0]) + L[1].times(P[:, 1]) + L[2].times(P[:, 2]) + t)
+    res = LD(grid["resolution"])
+    out = []
+    margin = INF
+    for po, mx in ((Po[0], grid["max_x"]), (Po[1], grid["max_y"])):
+        q = (LD(mx) - po.a) / res - LD(0.5)                                           # the coordinate WITHOUT kPadding: long double keeps 1e-17 here
+        ulp = np.where(q >= 1, LD(2.0 ** -23), LD(2.0 ** -24))                        # spacing of a double at q + kPadding (kPadding = 2^29 - 1, a multiple of it)
+        if q.size:
+            assert float(q.min()) > 1 - 2.0 ** 28 and float(q.max()) < 2.0 ** 29
+            frac = q / ulp - np.floor(q / ulp)                                        # boundaries lie half-way between neighbouring doubles
+            tol = 64 * U * (abs(LD(mx)) + np.abs(po.a)) / res
+            margin = min(margin, float((np.abs(frac - LD(0.5)) * ulp / tol).min()))
+        out.append(_Jet(q if exact else np.floor(q / ulp + LD(0.5)) * ulp, -po.v / res))   # (exact: no rounding, for finite differences)
+    return out[0], out[1], margin
+
+
+def laser_edge(tq, Tcr, P, grid, exact=False, alias_w=False):
+    """EdgeOccupiedObservation over n range points of one pose: (e [n], J [n][6], margin of _laser_functor).  computeError reads the pose's seven numbers; the
+    Jacobian is the reference's: AutoDifferentiate over StaticParameterDims<6, 3> gives the pose block SIX jets, so the functor's pose[6]
+    reads the next jet, the range point's x — q.w := P.x, no partial, differentiated with respect to (t, qx, qy, qz).
+    alias_w: e too is taken with q.w := P.x (the function J differentiates; the finite-difference test)."""
+    tq = _ld(tq).reshape(7); P = _ld(P).reshape(-1, 3)
+    n = len(P)
+    ones = np.ones(n, dtype=LD)
+    r, c, margin = _laser_functor([_Jet(ones * tq[i]) for i in range(6)] + [_Jet(P[:, 0].copy() if alias_w else ones * tq[6])], P, Tcr, grid, exact)
+    e, _, _ = bicubic(grid, r.a, c.a)
+    pose = []
+    for i in range(6):
+        j = _Jet(ones * tq[i]); j.v[:, i] = 1
+        pose.append(j)
+    pose.append(_Jet(P[:, 0].copy()))
+    r, c, margin_j = _laser_functor(pose, P, Tcr, grid, exact)
+    _, dfdr, dfdc = bicubic(grid, r.a, c.a)
+    return e, dfdr[:, None] * r.v + dfdc[:, None] * c.v, min(margin, margin_j)
+
+
+# ===================================================================== bookkeeping
+def pose_index(graph):
+    """Free index of every pose, -1 for a fixed one (hessianIndex: non-fixed poses in index order)."""
+    fixed = np.asarray(graph["pose_fixed"]).astype(bool)
+    idx = np.cumsum(~fixed) - 1
+    idx[fixed] = -1
+    return idx.astype(np.int64)
+
+
+def active_edges(graph, level):
+    """Level 0 and not allVerticesFixed."""
+    pf = np.asarray(graph["pose_fixed"]).astype(bool)[graph["obs_pose"]]
+    lf = np.asarray(graph["point_fixed"]).astype(bool)[graph["obs_point"]]
+    return (np.asarray(level) == 0) & ~(pf & lf)
+
+
+def block_error(x, truth, norm):
+    """(max over blocks of |x - truth|_inf / norm, the block).  Blocks along axis 0.  A block whose normaliser is zero must be matched
+    exactly."""
+    truth = _ld(truth)
+    nb = truth.shape[0] if truth.ndim else 1
+    if truth.size == 0:
+        return 0.0, -1
+    d = np.abs(_ld(x).reshape(nb, -1) - truth.reshape(nb, -1)).max(axis=1)
+    norm = _ld(norm).reshape(nb)
+    pos = norm > 0
+    r = np.where(pos, d / np.where(pos, norm, LD(1)), np.where(d == 0, LD(0), LD(INF)))
+    r = np.where(np.isfinite(d), r, LD(INF))
+    k = int(np.argmax(r))
+    return float(r[k]), k
+
+
+def _own(truth):
+    """A block's own |truth|_inf."""
+    t = np.abs(_ld(truth))
+    return t.reshape(t.shape[0], -1).max(axis=1) if t.size else np.zeros(0, dtype=LD)
+
+
+def _scatter(n, idx, terms):
+    out = np.zeros((n,) + terms.shape[1:], dtype=LD)
+    np.add.at(out, idx, terms)
+    return out
+
+
+def _count_max(idx, n):
+    return int(np.bincount(idx, minlength=max(n, 1)).max()) if len(idx) else 0
+
+
+def closest_to_thresholds(chi2, active, delta):
+    """The smallest relative distance of an active observation's chi2 from delta^2 (the Huber branch) and from delta (mark_outliers), on
+    the truth.  A case is admitted only if neither lies within 1e-9."""
+    if not delta > 0 or not np.any(active):
+        return INF, INF
+    c = _ld(chi2)[active]
+    d = LD(delta)
+    return float(np.abs(c / (d * d) - 1).min()), float(np.abs(c / d - 1).min())
+
+
+# ===================================================================== linearisation
+def _odo_terms(graph, pose):
+    """Per odometry edge with a free end: (edge index i, j, e, Ji, Jj)."""
+    fixed = np.asarray(graph["pose_fixed"]).astype(bool)
+    i = np.asarray(graph["odo_from"], dtype=np.int64); j = np.asarray(graph["odo_to"], dtype=np.int64)
+    keep = ~(fixed[i] & fixed[j]) if len(i) else np.zeros(0, bool)
+    i, j = i[keep], j[keep]
+    e, Ji, Jj = odo_edge(_ld(pose)[i], _ld(pose)[j], _ld(graph["odo_tq"]).reshape(-1, 7)[keep])
+    return i, j, e, Ji, Jj
+
+
+def _laser_terms(graph, pose):
+    la = graph.get("laser")
+    if la is None or len(la["xyz"]) == 0 or bool(np.asarray(graph["pose_fixed"])[la["pose"]]):
+        return None
+    e, J, margin = laser_edge(_ld(pose)[la["pose"]], la["Tcr"], la["xyz"], la)
+    return la["pose"], e, J, margin
+
+
+def other_chi2(graph, pose):
+    """(sum, number of terms, laser margin) of the odometry and laser edges' chi2 at `pose` (no robust kernel on either)."""
+    _, _, e, _, _ = _odo_terms(graph, pose)
+    total = (e * (LD(graph["w_odo"]) * e)).sum()
+    n = len(e)
+    la = _laser_terms(graph, pose)
+    if la is not None:
+        total = total + (la[1] * (LD(graph["w_laser"]) * la[1])).sum()
+        n += len(la[1])
+    return total, n, (la[3] if la is not None else INF)
+
+
+def judge_linearize(graph, pose, pt, level, side, chi2_total, max_diag):
+    """One side's linearisation against the truth.  pose, pt: that side's committed state; level [No]: its level-1 flags; side: its
+    fetched err, chi2, weight, Hpl, Hll, bl, Hpp, bp; chi2_total, max_diag: what its linearize() returned.
+    Returns {stage: dict(e, n, block)} and (the two threshold distances of the truth's chi2, the laser coordinates' margin)."""
+    op = np.asarray(graph["obs_pose"], dtype=np.int64); ol = np.asarray(graph["obs_point"], dtype=np.int64)
+    pose_fixed = np.asarray(graph["pose_fixed"]).astype(bool); point_fixed = np.asarray(graph["point_fixed"]).astype(bool)
+    Np, Nl, No = len(pose_fixed), len(point_fixed), len(op)
+    pidx = pose_index(graph); npf = int((~pose_fixed).sum()); n6 = 6 * npf
+    w_px = LD(graph["w_px"]); delta = graph["delta"]
+    active = active_edges(graph, level)
+    out = {}
+
+    def put(stage, x, truth, norm, n):
+        e, k = block_error(x, truth, norm)
+        out[stage] = dict(e=e, n=int(n), block=k)
+
+    e_t, scale, Ji, Jj = stereo_edge(_ld(pose)[op], _ld(pt)[ol], graph["obs_uvr"], graph["intr"])
+    e_t = np.where(active[:, None], e_t, LD(0))
+    put("err", side["err"].reshape(No, 3), e_t, np.where(active, scale, LD(0)), 0)
+    chi_truth = (e_t * (w_px * e_t)).sum(axis=1)
+    closest = closest_to_thresholds(chi_truth, active, delta)
+
+    e_own = _ld(side["err"]).reshape(No, 3)
+    c_t = np.where(active, (e_own * (w_px * e_own)).sum(axis=1), LD(0))
+    put("chi2", side["chi2"], c_t, np.abs(c_t), 0)
+    c_own = _ld(side["chi2"])
+    rho, rho1 = huber(c_own, delta)
+    w_t = np.where(active, rho1, LD(0))
+    put("weight", side["weight"], w_t, np.abs(w_t), 0)
+
+    wo = _ld(side["weight"]) * w_px                                                   # weightedOmega = rho' Omega (diagonal)
+    pfree = ~pose_fixed[op]; lfree = ~point_fixed[ol]
+    both = active & pfree & lfree
+    tile = np.einsum("nmr,n,nmc->nrc", Jj, wo, Ji)                                    # H_pl (pose row, point column) = Jj^T (wo) Ji
+    tile = np.where(both[:, None, None], tile, LD(0))
+    put("Hpl", side["Hpl"].reshape(No, 6, 3), tile, _own(tile), 0)
+
+    iu = np.triu_indices(3)
+    ml = active & lfree
+    kl = np.nonzero(ml)[0]
+    t_ll = np.einsum("nmr,n,nmc->nrc", Ji[kl], wo[kl], Ji[kl])[:, iu[0], iu[1]]
+    Hll = _scatter(Nl, ol[kl], t_ll)
+    put("Hll", side["Hll"].reshape(Nl, 6), Hll, _own(Hll), _count_max(ol[kl], Nl))
+    t_bl = np.einsum("nmr,n,nm->nmr", Ji[kl], wo[kl], e_own[kl])
+    bl = -_scatter(Nl, ol[kl], t_bl.sum(axis=1))
+    bl_mag = _scatter(Nl, ol[kl], np.abs(t_bl).sum(axis=1))
+    put("bl", side["bl"].reshape(Nl, 3), bl, bl_mag.max(axis=1) if Nl else np.zeros(0), _count_max(ol[kl], Nl))
+
+    # H_pp, b_p: the stereo edges of every free pose (the landmark may be fixed), the odometry edges, the laser points
+    kp = np.nonzero(active & pfree)[0]
+    a_of = pidx[op[kp]]
+    t_pp = np.einsum("nmr,n,nmc->nrc", Jj[kp], wo[kp], Jj[kp])
+    D = _scatter(npf, a_of, t_pp); Dmag = _scatter(npf, a_of, np.abs(t_pp))
+    t_bp = np.einsum("nmr,n,nm->nmr", Jj[kp], wo[kp], e_own[kp])
+    bp = -_scatter(npf, a_of, t_bp.sum(axis=1)); bp_mag = _scatter(npf, a_of, np.abs(t_bp).sum(axis=1))
+    cnt = np.bincount(a_of, minlength=max(npf, 1))[:max(npf, 1)].astype(np.int64)
+    extra = np.zeros(max(npf, 1), bool)
+    off, off_mag = {}, {}
+    oi, oj, oe, oJi, oJj = _odo_terms(graph, pose)
+    w_odo = LD(graph["w_odo"])
+    for k in range(len(oi)):
+        a, b = pidx[oi[k]], pidx[oj[k]]
+        for v, J in ((a, oJi[k]), (b, oJj[k])):
+            if v >= 0:
+                D[v] += J.T @ (w_odo * J); Dmag[v] += np.abs(J).T @ (w_odo * np.abs(J))
+                bp[v] -= J.T @ (w_odo * oe[k]); bp_mag[v] += np.abs(J).T @ (w_odo * np.abs(oe[k]))
+                cnt[v] += 1; extra[v] = True
+        if a >= 0 and b >= 0:
+            for key, A, B in (((a, b), oJi[k], oJj[k]), ((b, a), oJj[k], oJi[k])):
+                off[key] = off.get(key, 0) + A.T @ (w_odo * B)
+                off_mag[key] = off_mag.get(key, 0) + np.abs(A).T @ (w_odo * np.abs(B))
+    la = _laser_terms(graph, pose)
+    if la is not None:
+        a = pidx[la[0]]; w_la = LD(graph["w_laser"]); J = la[2]; el = la[1]
+        D[a] += np.einsum("nr,nc->rc", J, w_la * J); Dmag[a] += np.einsum("nr,nc->rc", np.abs(J), w_la * np.abs(J))
+        bp[a] -= (J * (w_la * el)[:, None]).sum(axis=0); bp_mag[a] += (np.abs(J) * (w_la * np.abs(el))[:, None]).sum(axis=0)
+        cnt[a] += len(el); extra[a] = True
+    n_pp = int(cnt.max()) if npf else 0
+    Hpp_side = np.asarray(side["Hpp"]).reshape(npf, 6, npf, 6)
+    ar = np.arange(npf)
+    keys = sorted(off)
+    blocks = np.concatenate([D, np.stack([off[k] for k in keys])]) if keys else D
+    norms = np.concatenate([np.where(extra[:npf], _own(Dmag), _own(D)), _ld([np.abs(off_mag[k]).max() for k in keys])]) if keys else np.where(extra[:npf], _own(Dmag), _own(D))
+    rows = np.concatenate([ar, np.array([k[0] for k in keys], dtype=np.int64)]); cols = np.concatenate([ar, np.array([k[1] for k in keys], dtype=np.int64)])
+    got = Hpp_side[rows, :, cols, :] if npf else np.zeros((0, 6, 6))
+    put("Hpp", got, blocks, norms, n_pp)
+    if npf and np.count_nonzero(Hpp_side) != np.count_nonzero(got):
+        out["Hpp"].update(e=INF, block=-2)                                            # an entry outside the truth's block set
+    put("bp", np.asarray(side["bp"]).reshape(npf, 6), bp, bp_mag.max(axis=1) if npf else np.zeros(0), n_pp)
+
+    other, n_other, margin = other_chi2(graph, pose)
+    total = np.where(active, rho, LD(0)).sum() + other
+    put("chi2_total", np.array([chi2_total]), _ld([total]), np.abs(_ld([total])), int(active.sum()) + n_other)
+    diag = [np.abs(np.asarray(side["Hpp"]).reshape(n6, n6).diagonal())] if npf else []
+    if Nl:
+        diag.append(np.abs(np.asarray(side["Hll"]).reshape(Nl, 6)[~point_fixed][:, [0, 3, 5]]).ravel())
+    md = max([float(d.max()) for d in diag if d.size] + [0.0])
+    out["max_diag"] = dict(e=0.0 if md == max_diag else INF, n=0, block=-1)
+    return out, closest + (margin,)
+
+
+# ===================================================================== Schur complement, back-substitution, trial state
+def sym3_inverse(h6, lam):
+    """Inverses of the symmetric 3x3 blocks (xx xy xz yy yz zz) + lam I, in long double: cofactors, then Newton steps
+    X <- X (2I - A X) until |A X - I| is below 1e-17 (or stops falling).  Returns (X [n][3][3], the largest |A X - I|)."""
+    h = _ld(h6).reshape(-1, 6)
+    n = len(h)
+    A = np.empty((n, 3, 3), dtype=LD)
+    A[:, 0, 0] = h[:, 0] + LD(lam); A[:, 1, 1] = h[:, 3] + LD(lam); A[:, 2, 2] = h[:, 5] + LD(lam)
+    A[:, 0, 1] = A[:, 1, 0] = h[:, 1]; A[:, 0, 2] = A[:, 2, 0] = h[:, 2]; A[:, 1, 2] = A[:, 2, 1] = h[:, 4]
+    if n == 0:
+        return A, 0.0
+    a, b, c, d, e, f = A[:, 0, 0], A[:, 0, 1], A[:, 0, 2], A[:, 1, 1], A[:, 1, 2], A[:, 2, 2]
+    c00, c01, c02 = d * f - e * e, c * e - b * f, b * e - c * d
+    det = a * c00 + b * c01 + c * c02
+    X = np.empty_like(A)
+    X[:, 0, 0] = c00; X[:, 0, 1] = X[:, 1, 0] = c01; X[:, 0, 2] = X[:, 2, 0] = c02
+    X[:, 1, 1] = a * f - c * c; X[:, 1, 2] = X[:, 2, 1] = b * c - a * e; X[:, 2, 2] = a * d - b * b
+    X = X / det[:, None, None]
+    I = np.eye(3, dtype=LD)
+    res = np.abs(A @ X - I).reshape(n, -1).max(axis=1)
+    for _ in range(6):
+        todo = res >= 1e-17
+        if not todo.any():
+            break
+        X2 = X[todo] @ (2 * I - A[todo] @ X[todo])
+        X2 = (X2 + X2.transpose(0, 2, 1)) / 2
+        r2 = np.abs(A[todo] @ X2 - I).reshape(len(X2), -1).max(axis=1)
+        better = r2 < res[todo]
+        idx = np.nonzero(todo)[0][better]
+        X[idx] = X2[better]; res[idx] = r2[better]
+        if not better.any():
+            break
+    return X, float(res.max())
+
+
+def cond_sym3(h6, lam):
+    """2-norm condition numbers of the blocks H_ll + lam I (fp64 eigenvalues: a figure for the log and the ill-conditioned bound)."""
+    h = np.asarray(h6, dtype=np.float64).reshape(-1, 6)
+    A = np.empty((len(h), 3, 3))
+    A[:, 0, 0] = h[:, 0] + lam; A[:, 1, 1] = h[:, 3] + lam; A[:, 2, 2] = h[:, 5] + lam
+    A[:, 0, 1] = A[:, 1, 0] = h[:, 1]; A[:, 0, 2] = A[:, 2, 0] = h[:, 2]; A[:, 1, 2] = A[:, 2, 1] = h[:, 4]
+    if len(h) == 0:
+        return np.zeros(0)
+    ev = np.abs(np.linalg.eigvalsh(A))
+    return ev.max(axis=1) / np.maximum(ev.min(axis=1), 1e-300)
+
+
+def schur_truth(graph, lam, Hpp, bp, Hpl, Hll, bl, weight, drop_term=None):
+    """S = H_pp + lam I - sum_l B_l (H_ll + lam I)^-1 B_l^T and b_s = b_p - sum_l B_l (H_ll + lam I)^-1 b_l from one side's OWN buffers,
+    block-sparse: {(i, j), i <= j: 6x6} with sum|terms| per block (never a dense long-double n6 x n6 array).  An edge enters iff its
+    weight is non-zero and its pose and landmark are free; a free pose whose H_pp diagonal is all zero is pinned (unit diagonal).
+    drop_term: the index of one co-observation term to leave out (the tests show that the checks notice).
+    Returns dict(keys [nk][2], S [nk][6][6], S_mag, n_S, bs [npf][6], bs_mag, n_bs, D, used [Nl] bool, residual)."""
+    op = np.asarray(graph["obs_pose"], dtype=np.int64); ol = np.asarray(graph["obs_point"], dtype=np.int64)
+    pose_fixed = np.asarray(graph["pose_fixed"]).astype(bool); point_fixed = np.asarray(graph["point_fixed"]).astype(bool)
+    Nl, No = len(point_fixed), len(op)
+    pidx = pose_index(graph); npf = int((~pose_fixed).sum()); n6 = 6 * npf
+    weight = np.asarray(weight)
+    lam_ld = LD(lam)
+    used = np.zeros(Nl, bool)
+    used[ol[(weight != 0) & ~point_fixed[ol]]] = True                                 # free landmarks with an active edge
+    D = np.zeros((Nl, 3, 3), dtype=LD)
+    D[used], residual = sym3_inverse(_ld(Hll).reshape(Nl, 6)[used], lam)
+    el = np.nonzero((weight != 0) & ~point_fixed[ol] & ~pose_fixed[op])[0]
+    el = el[np.lexsort((pidx[op[el]], ol[el]))]                                       # by landmark, poses ascending inside
+    lm = ol[el]; pi = pidx[op[el]]
+    B = _ld(Hpl).reshape(No, 6, 3)[el]
+    Dl = D[lm]
+    BD = np.einsum("mrc,mcd->mrd", B, Dl)
+    aBD = np.einsum("mrc,mcd->mrd", np.abs(B), np.abs(Dl))
+    m = len(el)
+    H4 = np.asarray(Hpp).reshape(npf, 6, npf, 6)
+    k_list, t_list, g_list = [], [], []
+    maxL = _count_max(lm, Nl)
+    for d in range(maxL):
+        k1 = np.arange(m - d); k2 = k1 + d
+        ok = lm[k1] == lm[k2]
+        if d:
+            ok &= pi[k1] != pi[k2]                                                    # one edge per (pose, landmark) pair
+        k1, k2 = k1[ok], k2[ok]
+        k_list.append(pi[k1] * npf + pi[k2])
+        t_list.append(np.einsum("mrc,msc->mrs", BD[k1], B[k2]))
+        g_list.append(np.einsum("mrc,msc->mrs", aBD[k1], np.abs(B[k2])))
+    if k_list:
+        pk = np.concatenate(k_list); pt_ = np.concatenate(t_list); pg = np.concatenate(g_list)
+    else:
+        pk = np.zeros(0, np.int64); pt_ = np.zeros((0, 6, 6), dtype=LD); pg = np.zeros((0, 6, 6), dtype=LD)
+    if drop_term is not None:
+        keep = np.ones(len(pk), bool); keep[drop_term] = False
+        pk, pt_, pg = pk[keep], pt_[keep], pg[keep]
+    # the block set: the diagonal, every non-zero block of H_pp's upper triangle, every co-observing pair
+    nzb = np.abs(H4).max(axis=(1, 3)) > 0 if npf else np.zeros((0, 0), bool)
+    hi, hj = np.nonzero(np.triu(nzb, 1))
+    ar = np.arange(npf)
+    keys = np.unique(np.concatenate([ar * npf + ar, hi * npf + hj, pk]).astype(np.int64))
+    inv = np.searchsorted(keys, pk)
+    ki, kj = keys // max(npf, 1), keys % max(npf, 1)
+    S = _ld(H4[ki, :, kj, :]) if npf else np.zeros((0, 6, 6), dtype=LD)
+    S_mag = np.abs(S)
+    dg = np.nonzero(ki == kj)[0]
+    r6 = np.arange(6)
+    pinned = (np.abs(S[dg][:, r6, r6]).max(axis=1) == 0) if len(dg) else np.zeros(0, bool)
+    S[dg[:, None], r6, r6] += lam_ld; S_mag[dg[:, None], r6, r6] += lam_ld
+    for k in dg[pinned]:
+        S[k, r6, r6] = 1; S_mag[k, r6, r6] = 1
+    np.subtract.at(S, inv, pt_); np.add.at(S_mag, inv, pg)
+    n_S = 2 + _count_max(inv, len(keys))
+    Db = np.einsum("lrc,lc->lr", D, _ld(bl).reshape(Nl, 3))
+    aDb = np.einsum("lrc,lc->lr", np.abs(D), np.abs(_ld(bl).reshape(Nl, 3)))
+    bs = _ld(bp).reshape(npf, 6).copy(); bs_mag = np.abs(bs)
+    np.subtract.at(bs, pi, np.einsum("mrc,mc->mr", B, Db[lm])); np.add.at(bs_mag, pi, np.einsum("mrc,mc->mr", np.abs(B), aDb[lm]))
+    return dict(keys=np.stack([ki, kj], axis=1), S=S, S_mag=S_mag, n_S=n_S, bs=bs, bs_mag=bs_mag, n_bs=1 + _count_max(pi, npf), D=D, used=used,
+                residual=residual, el=el, n_terms=len(pk), term_block=inv, term_max=np.abs(pt_).reshape(len(pk), 36).max(axis=1))
+
+
+def compare_S(S_side, npf, T):
+    """(error on the block's own magnitude, error on sum|terms|, block, that block's cancellation sum|terms| / own magnitude).  Both triangles are compared (the lower against the transposed
+    truth); entries outside the truth's block set must be exactly zero."""
+    if npf == 0:
+        return 0.0, 0.0, -1, 1.0
+    S4 = np.asarray(S_side).reshape(npf, 6, npf, 6)
+    ki, kj = T["keys"][:, 0], T["keys"][:, 1]
+    up = S4[ki, :, kj, :]; lo = S4[kj, :, ki, :].transpose(0, 2, 1)
+    d = np.maximum(np.abs(_ld(up) - T["S"]), np.abs(_ld(lo) - T["S"])).reshape(len(ki), -1).max(axis=1)
+    own = _own(T["S"]); mag = _own(T["S_mag"])
+    e_own = np.where(own > 0, d / np.where(own > 0, own, LD(1)), np.where(d == 0, LD(0), LD(INF)))
+    e_mag = np.where(mag > 0, d / np.where(mag > 0, mag, LD(1)), np.where(d == 0, LD(0), LD(INF)))
+    k = int(np.argmax(e_own))
+    e = float(e_own[k])
+    cancel = float(mag[k] / own[k]) if own[k] > 0 else INF
+    offd = ki != kj
+    if np.count_nonzero(S4) != np.count_nonzero(up) + np.count_nonzero(lo[offd]):
+        e, k = INF, -2
+    return e, float(e_mag.max()), k, cancel
+
+
+def judge_trial(graph, pose, pt, level, lam, side, trial_chi2, scale):
+    """One side's damped trial against the truth of its own inputs.  pose, pt: its committed state; side: its own Hpp, bp, Hpl, Hll, bl,
+    weight (of the last linearisation) and S, bs, dx_pose, dx_point, pose_trial, point_trial; trial_chi2, scale: what trial() returned.
+    Returns ({stage: dict(e, n, block)}, the laser coordinates' margin at the trial state)."""
+    op = np.asarray(graph["obs_pose"], dtype=np.int64); ol = np.asarray(graph["obs_point"], dtype=np.int64)
+    pose_fixed = np.asarray(graph["pose_fixed"]).astype(bool); point_fixed = np.asarray(graph["point_fixed"]).astype(bool)
+    Np, Nl, No = len(pose_fixed), len(point_fixed), len(op)
+    pidx = pose_index(graph); npf = int((~pose_fixed).sum())
+    out = {}
+
+    def put(stage, x, truth, norm, n):
+        e, k = block_error(x, truth, norm)
+        out[stage] = dict(e=e, n=int(n), block=k)
+
+    T = schur_truth(graph, lam, side["Hpp"], side["bp"], side["Hpl"], side["Hll"], side["bl"], side["weight"])
+    e_own, e_mag, k, cancel = compare_S(side["S"], npf, T)
+    cond = cond_sym3(np.asarray(side["Hll"]).reshape(Nl, 6)[T["used"]], lam)
+    out["S"] = dict(e=e_own, n=T["n_S"], block=k, e_mag=e_mag, cancel=cancel, cond=float(cond.max()) if cond.size else 1.0, residual=T["residual"])
+    put("bs", np.asarray(side["bs"]).reshape(npf, 6), T["bs"], T["bs_mag"].max(axis=1) if npf else np.zeros(0), T["n_bs"])
+
+    # back-substitution: x_l = (H_ll + lam I)^-1 (b_l - sum B^T x_p) for free landmarks with an active edge
+    xp = _ld(side["dx_pose"]).reshape(npf, 6)
+    el = T["el"]; lm = ol[el]; pi = pidx[op[el]]
+    B = _ld(side["Hpl"]).reshape(No, 6, 3)[el]
+    c = _ld(side["bl"]).reshape(Nl, 3).copy(); c_mag = np.abs(c)
+    np.subtract.at(c, lm, np.einsum("mrc,mr->mc", B, xp[pi])); np.add.at(c_mag, lm, np.einsum("mrc,mr->mc", np.abs(B), np.abs(xp[pi])))
+    xl = np.where(T["used"][:, None], np.einsum("lrc,lc->lr", T["D"], c), LD(0))
+    xl_mag = np.where(T["used"][:, None], np.einsum("lrc,lc->lr", np.abs(T["D"]), c_mag), LD(0))
+    put("dx_point", np.asarray(side["dx_point"]).reshape(Nl, 3), xl, xl_mag.max(axis=1) if Nl else np.zeros(0), 3 + _count_max(lm, Nl))
+
+    # the trial state from the side's own increments
+    dxp = np.zeros((Np, 6), dtype=LD)
+    dxp[~pose_fixed] = xp
+    pose_t = np.where(pose_fixed[:, None], _ld(pose), pose_update(pose, dxp))
+    got = np.asarray(side["pose_trial"]).reshape(Np, 7)
+    put("pose_trial", _split_tq(got), _split_tq(pose_t), _own(_split_tq(pose_t)), 0)
+    dl = _ld(side["dx_point"]).reshape(Nl, 3)
+    pt_t = np.where(point_fixed[:, None], _ld(pt), _ld(pt) + dl)
+    put("point_trial", np.asarray(side["point_trial"]).reshape(Nl, 3), pt_t, _own(pt_t), 0)
+
+    # the trial chi2 at the side's OWN trial state, and computeScale from its own dx
+    active = active_edges(graph, level)
+    e, _, _, _ = stereo_edge(_ld(got)[op], _ld(side["point_trial"]).reshape(Nl, 3)[ol], graph["obs_uvr"], graph["intr"])
+    chi = (e * (LD(graph["w_px"]) * e)).sum(axis=1)
+    rho, _ = huber(chi, graph["delta"])
+    other, n_other, margin = other_chi2(graph, got)
+    total = np.where(active, rho, LD(0)).sum() + other
+    put("trial_chi2", np.array([trial_chi2]), _ld([total]), np.abs(_ld([total])), int(active.sum()) + n_other)
+    bpv = _ld(side["bp"]).reshape(npf, 6); blv = _ld(side["bl"]).reshape(Nl, 3)[~point_fixed]; dlf = dl[~point_fixed]
+    lam_ld = LD(lam)
+    sc = (xp * (lam_ld * xp + bpv)).sum() + (dlf * (lam_ld * dlf + blv)).sum()
+    sc_mag = (np.abs(xp) * (lam_ld * np.abs(xp) + np.abs(bpv))).sum() + (np.abs(dlf) * (lam_ld * np.abs(dlf) + np.abs(blv))).sum()
+    put("scale", np.array([scale]), _ld([sc]), _ld([sc_mag]), xp.size + dlf.size)
+    return out, margin
+
+
+def _split_tq(tq):
+    """[Np][7] -> [2 Np][4] blocks: the translation (padded with a zero) and the quaternion, judged separately."""
+    tq = _ld(tq).reshape(-1, 7)
+    t = np.concatenate([tq[:, :3], np.zeros((len(tq), 1), dtype=LD)], axis=1)
+    return np.concatenate([t, tq[:, 3:]], axis=0)
+
+
+LIN_STAGES = ("err", "chi2", "weight", "Hpl", "Hll", "bl", "Hpp", "bp", "chi2_total", "max_diag")
+TRIAL_STAGES = ("S", "bs", "dx_point", "pose_trial", "point_trial", "trial_chi2", "scale")
+STAGES = LIN_STAGES + TRIAL_STAGES

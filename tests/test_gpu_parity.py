@@ -4,6 +4,11 @@ Tolerances (fp64 everywhere): the device sums in a different (fixed) order than 
 compiler contracts multiply-adds into FMAs, so stage outputs agree to ~1e-13 relative; bounds are
 set to 1e-9 for linearisation products, 1e-7 for solved increments (conditioning of S) and 1e-6
 relative on final poses (north_star demands 1e-4).  Outlier sets (a discrete output) must be identical.
+
+check_stages below is a coarse net: its 1e-9 is taken against the largest entry of a whole buffer and every
+stage is computed from the other side's inputs.  The test that HOLDS the stages is tests/test_gpu_stage_forms.py:
+every stage of both sides against a long-double truth of that side's own inputs, block by block, at
+eg <= 10 max(eo, (64 + n) u); the solved increment is held by tests/test_gpu_solver_forms.py (§4a).
 """
 import ctypes as C
 
