@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
-"""Register / scratch / occupancy table of every kernel in ba_kernels.hip, ba_cov.hip, ba_flow.hip, ba_corners.hip, ba_pnp.hip, ba_fund.hip, ba_clahe.hip, ba_tracker.hip, ba_scan.hip, ba_scan_fast.hip, ba_scan_group.hip and ba_scan_refine.hip (hipcc -Rpass-analysis=kernel-resource-usage,
+"""Register / scratch / occupancy table of every kernel in ba_kernels.hip, ba_cov.hip, ba_flow.hip, ba_corners.hip, ba_pnp.hip, ba_fund.hip, ba_clahe.hip, ba_tracker.hip, ba_scan.hip, ba_scan_fast.hip, ba_scan_group.hip, ba_scan_refine.hip and ba_pose_graph.hip (hipcc -Rpass-analysis=kernel-resource-usage,
 device only).
 usage: tools/kernel_resources.py [filter-substring ...]   (extra -D flags through VISFS_BA_EXTRA_FLAGS; KRES_TXT=<file> reuses a saved remark dump)"""
 import os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-srcs = [os.path.join(ROOT, "visfs_amd", "csrc", f) for f in ("ba_kernels.hip", "ba_cov.hip", "ba_flow.hip", "ba_corners.hip", "ba_pnp.hip", "ba_fund.hip", "ba_clahe.hip", "ba_tracker.hip", "ba_scan.hip", "ba_scan_fast.hip", "ba_scan_group.hip", "ba_scan_refine.hip")]
+srcs = [os.path.join(ROOT, "visfs_amd", "csrc", f) for f in ("ba_kernels.hip", "ba_cov.hip", "ba_flow.hip", "ba_corners.hip", "ba_pnp.hip", "ba_fund.hip", "ba_clahe.hip", "ba_tracker.hip", "ba_scan.hip", "ba_scan_fast.hip", "ba_scan_group.hip", "ba_scan_refine.hip", "ba_pose_graph.hip")]
 if os.environ.get("KRES_TXT"):
     txt = open(os.environ["KRES_TXT"]).read()
 else:

@@ -1,0 +1,428 @@
+// The 2-D pose graph over the loop-closure constraints (include/visfs_pose_graph.h).
+//
+//   k_pose_graph   grid (1): one workgroup of kLanes work items runs posegraph::run from start to end: the edge-parallel
+//                  linearisation, the row-parallel gathers, the cyclic-reduction set-up, the preconditioned conjugate gradients, the
+//                  trial and the Levenberg-Marquardt control, separated by workgroup barriers.  Vectors and coefficients live in
+//                  device memory, LDS holds the lanes' partial sums and the State.  Nothing is read back during the loop and no
+//                  workgroup waits for another.
+// A call is one upload (the plan), one launch, one download (the record, the poses, chi2) and one wait.  The one-core twin runs the
+// same `run` with loops for the collective operations.
+#pragma clang fp contract(off)
+#include "ba_pose_graph.hpp"
+
+#include <cmath>
+#include <cstring>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "ba_submap.hpp"
+
+using namespace posegraph;
+
+namespace posegraph {
+
+// one workgroup: the collective operations of `run`
+struct DeviceExec {
+    double* part;                             // LDS [kLanes]
+    int32_t t;
+    // The work item's index as a value the compiler cannot trace: the addresses formed from it are then computed where they are
+    // used, not once for the whole kernel and kept in registers across every loop (which spilled to scratch).
+    __device__ int32_t lane() const {
+        int32_t l = t;
+        asm volatile("" : "+v"(l));
+        return l;
+    }
+    template <class F> __device__ void par(int32_t n, F f) {
+#pragma nounroll
+        for (int32_t i = lane(); i < n; i += kLanes) f(i);
+        __syncthreads();
+    }
+    template <class F> __device__ double sum(int32_t n, F f) {
+        double a = 0.0;
+#pragma nounroll
+        for (int32_t i = lane(); i < n; i += kLanes) a += f(i);
+        part[t] = a;
+        for (int32_t s = kLanes / 2; s > 0; s >>= 1) {
+            __syncthreads();
+            if (t < s) part[t] += part[t + s];
+        }
+        __syncthreads();
+        const double r = part[0];
+        __syncthreads();
+        return r;
+    }
+    template <class F> __device__ double maxv(int32_t n, F f) {
+        double a = -kRejectedCost;
+        for (int32_t i = lane(); i < n; i += kLanes) { const double b = f(i); if (b > a) a = b; }
+        part[t] = a;
+        for (int32_t s = kLanes / 2; s > 0; s >>= 1) {
+            __syncthreads();
+            if (t < s && part[t + s] > part[t]) part[t] = part[t + s];
+        }
+        __syncthreads();
+        const double r = part[0];
+        __syncthreads();
+        return r;
+    }
+    template <class F> __device__ void one(F f) {
+        __syncthreads();
+        if (t == 0) f();
+        __syncthreads();
+    }
+};
+
+// the same on one core
+struct HostExec {
+    std::vector<double> part = std::vector<double>((size_t)kLanes);
+    template <class F> void par(int32_t n, F f) { for (int32_t i = 0; i < n; ++i) f(i); }
+    template <class F> double sum(int32_t n, F f) {
+        for (int32_t t = 0; t < kLanes; ++t) {
+            double a = 0.0;
+            for (int32_t i = t; i < n; i += kLanes) a += f(i);
+            part[(size_t)t] = a;
+        }
+        for (int32_t s = kLanes / 2; s > 0; s >>= 1)
+            for (int32_t t = 0; t < s; ++t) part[(size_t)t] += part[(size_t)(t + s)];
+        return part[0];
+    }
+    template <class F> double maxv(int32_t n, F f) {
+        double a = -kRejectedCost;
+        for (int32_t i = 0; i < n; ++i) { const double b = f(i); if (b > a) a = b; }
+        return a;
+    }
+    template <class F> void one(F f) { f(); }
+};
+
+__global__ __launch_bounds__(kLanes) void k_pose_graph(View v, Prm P) {
+    __shared__ double s_part[kLanes];
+    __shared__ State s_state;
+    DeviceExec x{ s_part, (int32_t)threadIdx.x };
+    run(x, v, P, s_state);
+}
+
+}  // namespace posegraph
+
+struct visfs_pose_graph {
+    bool device = false;
+    int dev = 0;
+    hipStream_t stream = nullptr;
+    int32_t maxN = 0, maxE = 0;
+    std::string err;
+    size_t up_bytes = 0, work_doubles = 0;
+    char* h_up = nullptr; char* d_up = nullptr;       // the upload: pinned, device
+    double* d_work = nullptr; char* h_out = nullptr;  // the work (its tail is the download), the pinned download
+    std::vector<char> up;                             // twin
+    std::vector<double> work;
+    View view;                                        // of the last run
+    int32_t trials = 0, launches = 0, copies = 0, waits = 0;
+};
+
+namespace {
+
+size_t up_capacity(int32_t N, int32_t E) {
+    return sizeof(double) * ((size_t)kPoseDoubles * N + (size_t)kEdgeDoubles * E + 3 * (size_t)N) +
+           sizeof(int32_t) * (2 * (size_t)E + (size_t)N + 2 * ((size_t)N + 1) + 2 * (size_t)E + (size_t)E + 2);
+}
+
+constexpr size_t kResDoubles = (sizeof(visfs_pose_graph_result) + 7) / 8;
+
+size_t out_doubles(int32_t N, int32_t E) { return kResDoubles + 3 * (size_t)N + (size_t)E; }
+
+size_t work_capacity(int32_t N, int32_t E) {
+    const size_t n = (size_t)N;
+    return 6 * n + 34 * (size_t)E + 21 * n + 54 * n + 9 * n + 2 * (size_t)kMaxLevels * 9 * n + 21 * n + (size_t)kMaxTrials * kTraceItems + out_doubles(N, E);
+}
+
+// The upload of a plan packed at `dst` (host memory); the view's upload pointers set relative to `base` (where dst will lie).
+size_t pack(const Plan& pl, const double* hook_r, char* dst, const char* base, View& v) {
+    size_t off = 0;
+    auto put = [&](const void* src, size_t bytes) -> const char* {
+        if (src && bytes) std::memcpy(dst + off, src, bytes); else if (bytes) std::memset(dst + off, 0, bytes);
+        const char* at = base + off;
+        off += (bytes + 7) & ~(size_t)7;
+        return at;
+    };
+    v.N = pl.N; v.E = pl.E; v.n = pl.n;
+    v.pose0 = reinterpret_cast<const double*>(put(pl.pose0.data(), pl.pose0.size() * sizeof(double)));
+    v.ed = reinterpret_cast<const double*>(put(pl.ed.data(), pl.ed.size() * sizeof(double)));
+    v.hook_r = reinterpret_cast<const double*>(put(hook_r, 3 * (size_t)pl.n * sizeof(double)));
+    v.eij = reinterpret_cast<const int32_t*>(put(pl.eij.data(), pl.eij.size() * sizeof(int32_t)));
+    v.row_of = reinterpret_cast<const int32_t*>(put(pl.row_of.data(), pl.row_of.size() * sizeof(int32_t)));
+    v.inc_ptr = reinterpret_cast<const int32_t*>(put(pl.inc_ptr.data(), pl.inc_ptr.size() * sizeof(int32_t)));
+    v.inc = reinterpret_cast<const int32_t*>(put(pl.inc.data(), pl.inc.size() * sizeof(int32_t)));
+    v.chain_ptr = reinterpret_cast<const int32_t*>(put(pl.chain_ptr.data(), pl.chain_ptr.size() * sizeof(int32_t)));
+    v.chain = reinterpret_cast<const int32_t*>(put(pl.chain.data(), pl.chain.size() * sizeof(int32_t)));
+    return off;
+}
+
+// the work arrays of a view carved from `w`; returns where the download starts
+double* carve(View& v, double* w) {
+    const size_t N = (size_t)v.N, E = (size_t)v.E, n = (size_t)v.n;
+    auto take = [&](size_t count) { double* p = w; w += count; return p; };
+    v.x = take(3 * N); v.xt = take(3 * N);
+    v.eb = take(27 * E); v.eg = take(6 * E); v.chi2 = take(E);
+    v.g = take(3 * n); v.D = take(9 * n); v.C = take(9 * n);
+    for (int k = 0; k < 2; ++k) { v.pD[k] = take(9 * n); v.pA[k] = take(9 * n); v.pC[k] = take(9 * n); }
+    v.Dinv = take(9 * n);
+    v.al = take((size_t)kMaxLevels * 9 * n); v.ga = take((size_t)kMaxLevels * 9 * n);
+    v.r = take(3 * n); v.z = take(3 * n); v.p = take(3 * n); v.q = take(3 * n); v.dx = take(3 * n);
+    v.t[0] = take(3 * n); v.t[1] = take(3 * n);
+    v.trace = take((size_t)kMaxTrials * kTraceItems);
+    double* out = w;
+    v.res = reinterpret_cast<visfs_pose_graph_result*>(take(kResDoubles));
+    v.out_poses = take(3 * N); v.out_chi2 = take(E);
+    return out;
+}
+
+#define PG_HIP(expr)                                                                               \
+    do {                                                                                           \
+        hipError_t e_ = (expr);                                                                    \
+        if (e_ != hipSuccess) { pg->err = std::string(#expr) + ": " + hipGetErrorString(e_); return (int)VISFS_BA_ERR_DEVICE; } \
+    } while (0)
+
+void release(visfs_pose_graph* pg) {
+    if (pg->h_up) (void)hipHostFree(pg->h_up);
+    if (pg->d_up) (void)hipFree(pg->d_up);
+    if (pg->d_work) (void)hipFree(pg->d_work);
+    if (pg->h_out) (void)hipHostFree(pg->h_out);
+    pg->h_up = pg->d_up = pg->h_out = nullptr; pg->d_work = nullptr;
+}
+
+// One run of `mode` on the plan: the record, the poses and chi2 land at `out` (out_doubles of them, host memory).
+int run_plan(visfs_pose_graph* pg, const Plan& pl, const Prm& P, const double* hook_r, const double** out) {
+    View v;
+    if (!pg->device) {
+        const size_t bytes = pack(pl, hook_r, pg->up.data(), pg->up.data(), v);
+        (void)bytes;
+        double* o = carve(v, pg->work.data());
+        HostExec x;
+        State s;
+        run(x, v, P, s);
+        pg->view = v;
+        *out = o;
+        return VISFS_BA_OK;
+    }
+    PG_HIP(hipSetDevice(pg->dev));
+    const size_t bytes = pack(pl, hook_r, pg->h_up, pg->d_up, v);
+    double* d_out = carve(v, pg->d_work);
+    const size_t out_bytes = out_doubles(pl.N, pl.E) * sizeof(double);
+    PG_HIP(hipMemcpyAsync(pg->d_up, pg->h_up, bytes, hipMemcpyHostToDevice, pg->stream));
+    hipLaunchKernelGGL(k_pose_graph, dim3(1), dim3(kLanes), 0, pg->stream, v, P);
+    PG_HIP(hipGetLastError());
+    PG_HIP(hipMemcpyAsync(pg->h_out, d_out, out_bytes, hipMemcpyDeviceToHost, pg->stream));
+    PG_HIP(hipStreamSynchronize(pg->stream));
+    pg->view = v;
+    *out = reinterpret_cast<const double*>(pg->h_out);
+    return VISFS_BA_OK;
+}
+
+// a work array of the last run to host memory (hooks)
+int fetch(visfs_pose_graph* pg, const double* src, size_t count, double* dst) {
+    if (!dst || count == 0) return VISFS_BA_OK;
+    if (!pg->device) { std::memcpy(dst, src, count * sizeof(double)); return VISFS_BA_OK; }
+    PG_HIP(hipSetDevice(pg->dev));
+    PG_HIP(hipMemcpyAsync(dst, src, count * sizeof(double), hipMemcpyDeviceToHost, pg->stream));
+    PG_HIP(hipStreamSynchronize(pg->stream));
+    return VISFS_BA_OK;
+}
+
+int fail(visfs_pose_graph* pg, int rc, const std::string& why) { pg->err = why; return rc; }
+
+template <class F> int guarded(F&& f) noexcept {
+    try { return f(); }
+    catch (...) { return (int)VISFS_BA_ERR_DEVICE; }
+}
+
+Prm hook_prm(int32_t mode) {
+    Prm P;
+    P.mode = mode; P.max_it = 1; P.max_pcg = 1; P.budget = 1;
+    return P;
+}
+
+}  // namespace
+
+// ====================================================================== exported C ABI
+extern "C" {
+
+int visfs_pose_graph_abi_version(void) { return VISFS_POSE_GRAPH_ABI_VERSION; }
+
+void visfs_pose_graph_default_params(visfs_pose_graph_params* p) {
+    if (!p) return;
+    p->function_tolerance = 1e-6; p->pcg_tolerance = 1e-8;
+    p->max_iterations = 20; p->max_pcg_iterations = 500; p->pcg_budget = 10000; p->preconditioner = 1;
+}
+
+int visfs_pose_graph_create(visfs_ba_handle* h, int32_t max_vertices, int32_t max_edges, visfs_pose_graph** out) {
+    if (!out) return VISFS_BA_ERR_BAD_ARGUMENT;
+    *out = nullptr;
+    if (max_vertices < 1 || max_edges < 1) return VISFS_BA_ERR_BAD_ARGUMENT;
+    if (max_vertices > VISFS_POSE_GRAPH_MAX_VERTICES || max_edges > VISFS_POSE_GRAPH_MAX_EDGES) return VISFS_BA_ERR_UNSUPPORTED;
+    return guarded([&]() -> int {
+        visfs_pose_graph* pg = new visfs_pose_graph();
+        pg->maxN = max_vertices; pg->maxE = max_edges;
+        pg->up_bytes = up_capacity(max_vertices, max_edges) + 128;
+        pg->work_doubles = work_capacity(max_vertices, max_edges);
+        if (!h) {
+            pg->up.assign(pg->up_bytes, 0);
+            pg->work.assign(pg->work_doubles, 0.0);
+            *out = pg;
+            return (int)VISFS_BA_OK;
+        }
+        pg->device = true; pg->dev = visfs_internal_device(h); pg->stream = visfs_internal_stream(h);
+        const int rc = [&]() -> int {
+            PG_HIP(hipSetDevice(pg->dev));
+            PG_HIP(hipHostMalloc(reinterpret_cast<void**>(&pg->h_up), pg->up_bytes, hipHostMallocDefault));
+            PG_HIP(hipMalloc(reinterpret_cast<void**>(&pg->d_up), pg->up_bytes));
+            PG_HIP(hipMalloc(reinterpret_cast<void**>(&pg->d_work), pg->work_doubles * sizeof(double)));
+            PG_HIP(hipHostMalloc(reinterpret_cast<void**>(&pg->h_out), out_doubles(max_vertices, max_edges) * sizeof(double), hipHostMallocDefault));
+            return (int)VISFS_BA_OK;
+        }();
+        if (rc != VISFS_BA_OK) { visfs_internal_set_error(h, pg->err.c_str()); release(pg); delete pg; return rc; }
+        *out = pg;
+        return (int)VISFS_BA_OK;
+    });
+}
+
+void visfs_pose_graph_destroy(visfs_pose_graph* pg) {
+    if (!pg) return;
+    release(pg);
+    delete pg;
+}
+
+const char* visfs_pose_graph_last_error(const visfs_pose_graph* pg) { return pg ? pg->err.c_str() : ""; }
+
+int visfs_pose_graph_optimize(visfs_pose_graph* pg, const visfs_pose_graph_params* p, int32_t N, const double* poses, const uint8_t* fixed, int32_t E,
+                              const visfs_pose_graph_edge* edges, double* poses_out, double* chi2_out, visfs_pose_graph_result* result) {
+    if (!pg || !p || !poses || !fixed || !edges || !poses_out || !result) return VISFS_BA_ERR_BAD_ARGUMENT;
+    return guarded([&]() -> int {
+        if (p->max_iterations < 1 || p->max_iterations > VISFS_POSE_GRAPH_MAX_ITERATIONS) return fail(pg, VISFS_BA_ERR_BAD_ARGUMENT, "max_iterations must lie in [1, 50]");
+        if (p->max_pcg_iterations < 1 || p->pcg_budget < 1) return fail(pg, VISFS_BA_ERR_BAD_ARGUMENT, "max_pcg_iterations and pcg_budget must be at least 1");
+        if (p->preconditioner != 0 && p->preconditioner != 1) return fail(pg, VISFS_BA_ERR_BAD_ARGUMENT, "preconditioner must be 0 or 1");
+        const double w[2] = { p->function_tolerance, p->pcg_tolerance };
+        for (double a : w) if (!std::isfinite(a) || a < 0.0) return fail(pg, VISFS_BA_ERR_BAD_ARGUMENT, "the tolerances must be finite and not negative");
+        Plan pl;
+        std::string why;
+        int rc = make_plan(N, poses, fixed, E, edges, pg->maxN, pg->maxE, pl, why);
+        if (rc != VISFS_BA_OK) return fail(pg, rc, why);
+        Prm P;
+        P.ftol = p->function_tolerance; P.pcg_tol2 = p->pcg_tolerance * p->pcg_tolerance;
+        P.max_it = p->max_iterations; P.max_pcg = p->max_pcg_iterations; P.budget = p->pcg_budget; P.precond = p->preconditioner;
+        P.mode = kOptimize;
+        const double* out = nullptr;
+        if ((rc = run_plan(pg, pl, P, nullptr, &out)) != VISFS_BA_OK) return rc;
+        std::memcpy(result, out, sizeof *result);
+        std::memcpy(poses_out, out + kResDoubles, 3 * (size_t)N * sizeof(double));
+        if (chi2_out) std::memcpy(chi2_out, out + kResDoubles + 3 * (size_t)N, (size_t)E * sizeof(double));
+        pg->trials = result->trials;
+        pg->launches = pg->device ? 1 : 0; pg->copies = pg->device ? 2 : 0; pg->waits = pg->device ? 1 : 0;
+        pg->err.clear();
+        return (int)VISFS_BA_OK;
+    });
+}
+
+int visfs_pose_graph_download_trace(visfs_pose_graph* pg, int32_t cap, double* trace, int32_t* trials) {
+    if (!pg || !trials || cap < 0) return VISFS_BA_ERR_BAD_ARGUMENT;
+    return guarded([&]() -> int {
+        const int32_t n = pg->trials < kMaxTrials ? pg->trials : kMaxTrials;
+        *trials = n;
+        if (!trace || n == 0) return (int)VISFS_BA_OK;
+        if (cap < n) return fail(pg, VISFS_BA_ERR_BAD_ARGUMENT, "the hook's array is too small");
+        return fetch(pg, pg->view.trace, (size_t)n * kTraceItems, trace);
+    });
+}
+
+int visfs_pose_graph_linearize(visfs_pose_graph* pg, int32_t N, const double* poses, const uint8_t* fixed, int32_t E, const visfs_pose_graph_edge* edges,
+                               int32_t* n_rows, double* edge_blocks, double* g, double* D, double* C, double* cost, double* chi2) {
+    if (!pg || !poses || !fixed || !edges) return VISFS_BA_ERR_BAD_ARGUMENT;
+    return guarded([&]() -> int {
+        Plan pl;
+        std::string why;
+        int rc = make_plan(N, poses, fixed, E, edges, pg->maxN, pg->maxE, pl, why);
+        if (rc != VISFS_BA_OK) return fail(pg, rc, why);
+        const double* out = nullptr;
+        if ((rc = run_plan(pg, pl, hook_prm(kLinearize), nullptr, &out)) != VISFS_BA_OK) return rc;
+        pg->trials = 0;
+        visfs_pose_graph_result res;
+        std::memcpy(&res, out, sizeof res);
+        if (n_rows) *n_rows = pl.n;
+        if (cost) *cost = res.initial_cost;
+        if (chi2) std::memcpy(chi2, out + kResDoubles + 3 * (size_t)N, (size_t)E * sizeof(double));
+        const View& v = pg->view;
+        if ((rc = fetch(pg, v.eb, 27 * (size_t)E, edge_blocks)) != VISFS_BA_OK) return rc;
+        if ((rc = fetch(pg, v.g, 3 * (size_t)pl.n, g)) != VISFS_BA_OK) return rc;
+        if ((rc = fetch(pg, v.D, 9 * (size_t)pl.n, D)) != VISFS_BA_OK) return rc;
+        return fetch(pg, v.C, 9 * (size_t)pl.n, C);
+    });
+}
+
+int visfs_pose_graph_precondition(visfs_pose_graph* pg, int32_t preconditioner, double lambda, int32_t N, const double* poses, const uint8_t* fixed, int32_t E,
+                                  const visfs_pose_graph_edge* edges, const double* r, double* z) {
+    if (!pg || !poses || !fixed || !edges || !r || !z) return VISFS_BA_ERR_BAD_ARGUMENT;
+    return guarded([&]() -> int {
+        if (preconditioner != 0 && preconditioner != 1) return fail(pg, VISFS_BA_ERR_BAD_ARGUMENT, "preconditioner must be 0 or 1");
+        if (!std::isfinite(lambda) || lambda < 0.0) return fail(pg, VISFS_BA_ERR_BAD_ARGUMENT, "lambda must be finite and not negative");
+        Plan pl;
+        std::string why;
+        int rc = make_plan(N, poses, fixed, E, edges, pg->maxN, pg->maxE, pl, why);
+        if (rc != VISFS_BA_OK) return fail(pg, rc, why);
+        for (int64_t k = 0; k < 3 * (int64_t)pl.n; ++k) if (!std::isfinite(r[k])) return fail(pg, VISFS_BA_ERR_BAD_ARGUMENT, "r is not finite");
+        Prm P = hook_prm(kPrecondition);
+        P.hook_lambda = lambda; P.precond = preconditioner;
+        const double* out = nullptr;
+        if ((rc = run_plan(pg, pl, P, r, &out)) != VISFS_BA_OK) return rc;
+        pg->trials = 0;
+        visfs_pose_graph_result res;
+        std::memcpy(&res, out, sizeof res);
+        if (res.status != VISFS_BA_OK) return fail(pg, res.status, "a pivot of the preconditioner is not positive");
+        return fetch(pg, pg->view.z, 3 * (size_t)pl.n, z);
+    });
+}
+
+int visfs_pose_graph_plan(int32_t N, const uint8_t* fixed, int32_t E, const visfs_pose_graph_edge* edges, int32_t* n_rows, int32_t* row_of, int32_t* inc_ptr,
+                          int32_t* inc, int32_t* chain_ptr, int32_t* chain) {
+    if (!fixed || !edges || !n_rows || !row_of || !inc_ptr || !inc || !chain_ptr || !chain) return VISFS_BA_ERR_BAD_ARGUMENT;
+    return guarded([&]() -> int {
+        Plan pl;
+        std::string why;
+        const std::vector<double> poses(3 * (size_t)(N > 0 ? N : 0), 0.0);
+        const int rc = make_plan(N, poses.data(), fixed, E, edges, VISFS_POSE_GRAPH_MAX_VERTICES, VISFS_POSE_GRAPH_MAX_EDGES, pl, why);
+        if (rc != VISFS_BA_OK) return rc;
+        *n_rows = pl.n;
+        std::memcpy(row_of, pl.row_of.data(), pl.row_of.size() * sizeof(int32_t));
+        std::memcpy(inc_ptr, pl.inc_ptr.data(), pl.inc_ptr.size() * sizeof(int32_t));
+        if (!pl.inc.empty()) std::memcpy(inc, pl.inc.data(), pl.inc.size() * sizeof(int32_t));
+        std::memcpy(chain_ptr, pl.chain_ptr.data(), pl.chain_ptr.size() * sizeof(int32_t));
+        if (!pl.chain.empty()) std::memcpy(chain, pl.chain.data(), pl.chain.size() * sizeof(int32_t));
+        return (int)VISFS_BA_OK;
+    });
+}
+
+int visfs_pose_graph_last_counts(const visfs_pose_graph* pg, int32_t* launches, int32_t* copies, int32_t* waits) {
+    if (!pg) return VISFS_BA_ERR_BAD_ARGUMENT;
+    if (launches) *launches = pg->launches;
+    if (copies) *copies = pg->copies;
+    if (waits) *waits = pg->waits;
+    return VISFS_BA_OK;
+}
+
+int visfs_pose_graph_edge_from_refine(const double a[3], const visfs_scan_refine_result* r, double z[3], double W[9]) {
+    if (!a || !r || !z || !W || !r->refined) return VISFS_BA_ERR_BAD_ARGUMENT;
+    const double in[6] = { a[0], a[1], a[2], r->x, r->y, r->yaw };
+    for (double v : in) if (!std::isfinite(v)) return VISFS_BA_ERR_BAD_ARGUMENT;
+    for (double v : r->information) if (!std::isfinite(v)) return VISFS_BA_ERR_BAD_ARGUMENT;
+    const double c = std::cos(a[2]), s = std::sin(a[2]);
+    const double dx = r->x - a[0], dy = r->y - a[1], dth = r->yaw - a[2];
+    z[0] = c * dx + s * dy;
+    z[1] = c * dy - s * dx;
+    z[2] = dth - kTwoPi * std::rint(dth / kTwoPi);
+    const double B[9] = { c, -s, 0.0, s, c, 0.0, 0.0, 0.0, 1.0 };           // blkdiag(R, 1)
+    double T[9], M[9];
+    mm3(r->information, B, T);
+    mtm3(B, T, 1.0, M);
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) W[3 * i + j] = 0.5 * (M[3 * i + j] + M[3 * j + i]);
+    return VISFS_BA_OK;
+}
+
+}  // extern "C"
