@@ -1,10 +1,13 @@
 #!/usr/bin/env python3
 """Register / scratch / occupancy table of every kernel in ba_kernels.hip, ba_cov.hip, ba_flow.hip, ba_corners.hip, ba_pnp.hip, ba_fund.hip, ba_clahe.hip, ba_tracker.hip, ba_scan.hip, ba_scan_fast.hip, ba_scan_group.hip, ba_scan_refine.hip and ba_pose_graph.hip (hipcc -Rpass-analysis=kernel-resource-usage,
 device only).
-usage: tools/kernel_resources.py [filter-substring ...]   (extra -D flags through VISFS_BA_EXTRA_FLAGS; KRES_TXT=<file> reuses a saved remark dump)"""
+usage: tools/kernel_resources.py [filter-substring ...]   (extra -D flags through VISFS_BA_EXTRA_FLAGS; KRES_TXT=<file> reuses a saved remark dump;
+VISFS_BA_SRC=<dir>: another checkout's visfs_amd/csrc)"""
 import os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-srcs = [os.path.join(ROOT, "visfs_amd", "csrc", f) for f in ("ba_kernels.hip", "ba_cov.hip", "ba_flow.hip", "ba_corners.hip", "ba_pnp.hip", "ba_fund.hip", "ba_clahe.hip", "ba_tracker.hip", "ba_scan.hip", "ba_scan_fast.hip", "ba_scan_group.hip", "ba_scan_refine.hip", "ba_pose_graph.hip")]
+sys.path.insert(0, ROOT)
+from visfs_amd.build import KERNEL_FLAGS, KERNEL_SOURCES
+srcs = [os.path.join(os.environ.get("VISFS_BA_SRC", os.path.join(ROOT, "visfs_amd", "csrc")), f) for f in ("ba_kernels.hip", "ba_cov.hip", "ba_flow.hip", "ba_corners.hip", "ba_pnp.hip", "ba_fund.hip", "ba_clahe.hip", "ba_tracker.hip", "ba_scan.hip", "ba_scan_fast.hip", "ba_scan_group.hip", "ba_scan_refine.hip", "ba_pose_graph.hip")]
 if os.environ.get("KRES_TXT"):
     txt = open(os.environ["KRES_TXT"]).read()
 else:
@@ -12,6 +15,8 @@ else:
     for src in srcs:
         cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", src, "-o", "/tmp/_kres.o"]
         cmd += os.environ.get("VISFS_BA_EXTRA_FLAGS", "").split()
+        if os.path.basename(src) in KERNEL_SOURCES and not os.environ.get("KRES_NO_PRELOAD"):      # (as the product compiles it; KRES_NO_PRELOAD=1: as the commits before the head arguments did)
+            cmd += KERNEL_FLAGS
         txt += subprocess.run(cmd, capture_output=True, text=True).stderr
 rows, cur = [], None
 for line in txt.splitlines():

@@ -236,6 +236,46 @@ __device__ __forceinline__ const DeviceGraph& graph_of(const Many& s) {
     return *(const DeviceGraph*)p;
 }
 
+// HEAD ARGUMENTS.  The by-value graph of One is ~1.1 KB of kernel arguments, cold at every launch: each field the
+// head of a kernel needs in front of its first wait is a scalar round trip of its own, and the compiler fetches them one test at a
+// time.  The four kernels of the lone-window unit therefore also exist in a form (k_*_head) whose FIRST kernel parameters are the
+// few pointers and counts of that head, as separate scalars: ba_kernels.hip is compiled with -amdgpu-kernarg-preload-count, so they
+// arrive in user SGPRs with the wave and the front loads leave without touching the argument segment.  One body serves both forms:
+// it reads the head fields through `head_ref`, which is the head struct where the launch carries one and the graph itself (members
+// of the same names) where it does not, so the forms without a head compile to what they were.  The launchers fill a head from the
+// graph they pass (head_of), nowhere else: a head value cannot differ from the graph's.
+struct NoHead { static constexpr bool present = false; };
+struct SchurHead {                  // k_schur_partial<MULTI, One, false, ROLEB>: 14 dwords
+    static constexpr bool present = true;
+    LmState* st; const int4* sch_desc; int4* blk_pairs; DeviceGraph::PoseRec* pose_rec; const int32_t* chunk_ptr; const int32_t* chunk_pose; int32_t n_sch, n_chunks;
+};
+struct FinHead {                    // k_schur_finalize<One, false>: 5 dwords
+    static constexpr bool present = true;
+    LmState* st; const int4* blk_desc; int32_t n_blk;
+};
+struct PcgHead {                    // k_pcg1<One, 1, false>: 13 dwords
+    static constexpr bool present = true;
+    LmState* st; const int32_t* pcg1_code; double* Minv; double* bs; const int32_t* free_pose; double* S; int32_t Npf;
+};
+struct BacksubHead {                // k_backsub<G, One, ., true, true, 0, true>: 11 dwords.  pt[0], pt[1] and pt_fixed stay behind the graph: their
+    static constexpr bool present = true;   // loads are leaves (nothing is addressed through them), the chain runs through lm_ptr and the poses
+    LmState* st; double* pose[2]; const int32_t* lm_ptr; int32_t Np, Nl;
+    int32_t n_work;                 // workgroups in front of the decider (gridDim.x - 1): decider_window() reads the hidden grid-size argument
+};
+template <class H> __device__ __forceinline__ const H& head_ref(const H& h, const DeviceGraph&) { return h; }
+__device__ __forceinline__ const DeviceGraph& head_ref(const NoHead&, const DeviceGraph& g) { return g; }
+template <class Src, class H> __device__ __forceinline__ LmState* state_of(const Src& src, const DeviceGraph& g, const H& h) {
+    if constexpr (H::present) return h.st;
+    else return state_of(src, g);
+}
+// estimate buffer k of a head / of the graph (a run-time index into the head's two registers would put them on the stack)
+__device__ __forceinline__ double* pose_of(const BacksubHead& h, const int k) { return k ? h.pose[1] : h.pose[0]; }
+__device__ __forceinline__ double* pose_of(const DeviceGraph& g, const int k) { return g.pose[k]; }
+inline FinHead head_of_fin(const DeviceGraph& g) { return FinHead{ g.st, g.blk_desc, g.n_blk }; }
+inline PcgHead head_of_pcg(const DeviceGraph& g) { return PcgHead{ g.st, g.pcg1_code, g.Minv, g.bs, g.free_pose, g.S, g.Npf }; }
+inline SchurHead head_of_schur(const DeviceGraph& g) { return SchurHead{ g.st, g.sch_desc, g.blk_pairs, g.pose_rec, g.chunk_ptr, g.chunk_pose, g.n_sch, g.n_chunks }; }
+inline BacksubHead head_of_backsub(const DeviceGraph& g, const int n_work) { return BacksubHead{ g.st, { g.pose[0], g.pose[1] }, g.lm_ptr, g.Np, g.Nl, n_work }; }
+
 // chi2() = e . (Omega e), Omega = I3 / pixelVariance (Optimizer.cpp:153)
 // How a kernel gets its linearisation set: chosen at run time (LmState::lin_sel; lin_of: seven pointers in SGPRs).  Round 4: the
 // windows of a batched launch (Many) run the fused speculative unit too, so they select between their two sets like a window on its
@@ -1379,17 +1419,17 @@ __device__ __forceinline__ void schur_chunk(const DeviceGraph& g, const LinBuf& 
 }
 
 // The pose-major role of the linearisation as a workgroup behind a Schur launch (ROLEB): chunk c of a pose's observations.
-template <class Src>
-__device__ __forceinline__ void roleb_chunk(const DeviceGraph& g, const LmState* st, const int c, double* redb) {
-    if (c >= g.n_chunks) return;
+template <class Src, class HR>
+__device__ __forceinline__ void roleb_chunk(const DeviceGraph& g, const HR& h, const LmState* st, const int c, double* redb) {
+    if (c >= h.n_chunks) return;
     // chunk -> pose, range, record: none of it depends on the LM state — in flight before the gate
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int a = g.chunk_pose[c];
-    const int begin = g.chunk_ptr[c], end = g.chunk_ptr[c + 1];
+    const int a = h.chunk_pose[c];
+    const int begin = h.chunk_ptr[c], end = h.chunk_ptr[c + 1];
     const bool mine = begin + tid < end;
     DeviceGraph::PoseRec rec;
     rec.k = 0; rec.l_ok = -1; rec.u = rec.v = rec.ur = 0.0;
-    if (mine) rec = g.pose_rec[begin + tid];
+    if (mine) rec = h.pose_rec[begin + tid];
     const int ipose = g.free_pose[a];
     if (!st->lin_b_pending || !(st->mode & MODE_TRIAL)) return;
     const int sel = st->sel;
@@ -1415,40 +1455,67 @@ __device__ __forceinline__ void roleb_chunk(const DeviceGraph& g, const LmState*
 // the linearisation the previous unit's k_backsub<LINA> left half done (LmState::lin_b_pending): upper triangle of Jx^T (rho' Omega) Jx
 // and -Jx^T (rho' Omega) e per chunk of a pose's observations, at the committed estimate, into the current set's hpp_part — read by
 // k_schur_finalize / k_small_solve, the launch after this one.
-template <bool MULTI, class Src, bool CERES = false, bool ROLEB = false>
-__global__ __launch_bounds__(256, MULTI ? 2 : 4) void k_schur_partial(const Src src) {
+template <bool MULTI, class Src, bool CERES, bool ROLEB, class H>
+__device__ __forceinline__ void schur_partial_body(const Src& src, const H& hd) {
+    static_assert(!H::present || (!CERES && !Src::batched), "head arguments serve the lone-window gather only");
     const DeviceGraph& g = graph_of(src);
-    const LmState* st = state_of(src, g);
+    const auto& h = head_ref(hd, g);
+    const LmState* st = state_of(src, g, hd);
     const int lane = threadIdx.x & 63;
     // (role B sits BEHIND the gather in dispatch order: in front of it — measured — it delays the chunk workgroups, which are the launch's
     // critical path, and costs C2 4 %; behind it the launch is 1.5 us longer than the plain gather)
     if (ROLEB) {
-        const int first_b = (((g.n_sch + 3) / 4) + 7) / 8 * 8;
+        const int first_b = (((h.n_sch + 3) / 4) + 7) / 8 * 8;
         if ((int)blockIdx.x >= first_b) {
             __shared__ double redb[4 * 27];
-            roleb_chunk<Src>(g, st, (int)blockIdx.x - first_b, redb);
+            roleb_chunk<Src>(g, h, st, (int)blockIdx.x - first_b, redb);
             return;
         }
     }
     // XCD-aware mapping: workgroups are dealt round-robin over the 8 XCDs, chunks are sorted by block row, so give
     // every XCD one contiguous slice of the chunk list: the tiles of a block row are then served by ONE 4 MiB L2
     // instead of eight (speed only; any placement is correct).  gridDim.x is a multiple of 8.
-    const int nwg = (((g.n_sch + 3) / 4) + 7) / 8 * 8;        // this window's share of the launch (== gridDim.x for a single window)
+    const int nwg = (((h.n_sch + 3) / 4) + 7) / 8 * 8;        // this window's share of the launch (== gridDim.x for a single window)
     const int bx = (int)blockIdx.x;
     if (bx >= nwg) return;
     const int per_xcd = nwg >> 3;
     const int wg = (bx & 7) * per_xcd + (bx >> 3);
     const int ch = wg * 4 + (threadIdx.x >> 6);
-    if (ch >= g.n_sch) return;
+    if (ch >= h.n_sch) return;
     // the chunk descriptor and the lane's first pair do not depend on the LM state: fetch them BEFORE the gate, so the gate's own
     // load (a cold L2 round trip at the head of every kernel) overlaps two levels of the index chain instead of preceding them
-    const int4 dsc = g.sch_desc[ch];
+    const int4 dsc = h.sch_desc[ch];
+    if constexpr (H::present) {
+        // (head form: the descriptor and the LM state leave from preloaded registers, the graph's fields that the gather needs as one
+        // burst of argument loads beside them; one wait, then the pair — the only load that depends on another)
+        const int mode_h = st->mode, ls_h = st->lin_sel, sel_h = st->sel;
+        const double lam_h = st->lambda;
+        const LinBuf& L0 = g.lin[0];
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("" :: "v"(dsc.x), "v"(dsc.y), "v"(dsc.z), "v"(dsc.w), "s"(mode_h), "s"(ls_h), "s"(sel_h), "s"(lam_h),
+                     "s"(g.lin_stride), "s"(L0.pose_pcw), "s"(L0.Hll), "s"(g.pose[0]), "s"(g.pose[1]), "s"(g.sch_part), "s"(g.fin_arrive));
+        const int e0 = dsc.x + lane;
+        const int4 pr = e0 < dsc.y ? h.blk_pairs[e0] : make_int4(0, 0, 0, 0);
+        if (!(mode_h & MODE_TRIAL)) return;
+        const LinSel<Src> lsel(g, ls_h); const LinBuf& L = lsel.get();
+        schur_chunk<MULTI, CERES>(g, L, ch, lane, lam_h, g.pose[sel_h], dsc, pr);
+        if (g.fin_arrive) fin_arrive_at<ROLEB>(g, L, const_cast<LmState*>(st), g.sch_blk[ch], lane);
+        return;
+    }
     const int e0 = dsc.x + lane;
-    const int4 pr = e0 < dsc.y ? g.blk_pairs[e0] : make_int4(0, 0, 0, 0);
+    const int4 pr = e0 < dsc.y ? h.blk_pairs[e0] : make_int4(0, 0, 0, 0);
     if (!(st->mode & MODE_TRIAL)) return;
     const LinSel<Src> lsel(g, st->lin_sel); const LinBuf& L = lsel.get();
     schur_chunk<MULTI, CERES>(g, L, ch, lane, st->lambda, g.pose[st->sel], dsc, pr);
     if (!Src::batched && !CERES && g.fin_arrive) fin_arrive_at<ROLEB>(g, L, const_cast<LmState*>(st), g.sch_blk[ch], lane);
+}
+template <bool MULTI, class Src, bool CERES = false, bool ROLEB = false>
+__global__ __launch_bounds__(256, MULTI ? 2 : 4) void k_schur_partial(const Src src) { schur_partial_body<MULTI, Src, CERES, ROLEB>(src, NoHead{}); }
+// (lone window, g2o flavour: the head arrives in user SGPRs)
+template <bool MULTI, bool ROLEB>
+__global__ __launch_bounds__(256, MULTI ? 2 : 4) void k_schur_partial_head(LmState* st, const int4* sch_desc, int4* blk_pairs, DeviceGraph::PoseRec* pose_rec, const int32_t* chunk_ptr,
+                                                                          const int32_t* chunk_pose, const int32_t n_sch, const int32_t n_chunks, const One src) {
+    schur_partial_body<MULTI, One, false, ROLEB>(src, SchurHead{ st, sch_desc, blk_pairs, pose_rec, chunk_ptr, chunk_pose, n_sch, n_chunks });
 }
 
 // ================================================================= K5, round 4: Schur complement by RUNS OF LANDMARKS
@@ -1486,7 +1553,7 @@ __global__ __launch_bounds__(256, VISFS_BA_RUN_WAVES) void k_schur_runs(const Sr
     const int tid = threadIdx.x;
     const int nwg = (g.n_runs + 7) / 8 * 8;                  // this window's share of the launch
     if (ROLEB) {
-        if ((int)blockIdx.x >= nwg) { roleb_chunk<Src>(g, st, (int)blockIdx.x - nwg, run_lds); return; }
+        if ((int)blockIdx.x >= nwg) { roleb_chunk<Src>(g, g, st, (int)blockIdx.x - nwg, run_lds); return; }
     }
     const int bx = (int)blockIdx.x;
     if (bx >= nwg) return;
@@ -1864,17 +1931,30 @@ __device__ __forceinline__ void fin_arrive_at(const DeviceGraph& g, const LinBuf
 
 // RUNS (the Schur complement came from k_schur_runs): one WORKGROUP per stored block — a block collects one partial per run whose span
 // holds it (tens, where the gather left a handful of chunk partials), so the four waves each add a quarter of them and wave 0 finishes.
-template <class Src, bool RUNS = false>
-__global__ __launch_bounds__(256) void k_schur_finalize(const Src src) {
+template <class Src, bool RUNS, class H>
+__device__ __forceinline__ void schur_finalize_body(const Src& src, const H& hd) {
     const DeviceGraph& g = graph_of(src);
-    LmState* st = state_of(src, g);
+    const auto& h = head_ref(hd, g);
+    LmState* st = state_of(src, g, hd);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int b = RUNS ? (int)blockIdx.x : (int)blockIdx.x * 4 + wave;
-    if (b >= g.n_blk) return;
+    if (b >= h.n_blk) return;
     // the block descriptors first, the gate after: one cold-L2 round trip instead of two at the head of the kernel
-    const int4 bd = g.blk_desc[2 * b], be = g.blk_desc[2 * b + 1];
-    if (!(st->mode & MODE_TRIAL)) return;
-    const LinSel<Src> lsel(g, st->lin_sel); const LinBuf& L = lsel.get();
+    const int4 bd = h.blk_desc[2 * b], be = h.blk_desc[2 * b + 1];
+    int mode_h = 0, ls_h = 0;
+    if constexpr (H::present) {
+        // (head form: descriptors, the gate's words and what the block's sums start from leave together — the descriptors and the
+        // state from preloaded registers, the graph's fields as one burst of argument loads — and ONE wait follows; the empty
+        // statement keeps the compiler from sinking any of it behind the gate's branch, as it did with the descriptors)
+        mode_h = st->mode; ls_h = st->lin_sel;
+        const LinBuf& L0 = g.lin[0];
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("" :: "v"(bd.x), "v"(bd.y), "v"(bd.z), "v"(bd.w), "v"(be.x), "v"(be.y), "v"(be.z), "v"(be.w), "s"(mode_h), "s"(ls_h),
+                     "s"(g.lin_stride), "s"(L0.hpp_part), "s"(L0.odo_blk), "s"(g.sch_part), "s"(g.S), "s"(g.bs), "s"(g.Minv), "s"(g.granules), "s"(g.pose_odo), "s"(g.blk_odo),
+                     "s"(g.Npf), "s"(g.n_blk), "s"(g.n_runs), "s"(g.pcg_cu), "s"(g.ceres), "s"(g.Hpp), "s"(g.bp));
+        if (!(mode_h & MODE_TRIAL)) return;
+    } else if (!(st->mode & MODE_TRIAL)) return;
+    const LinSel<Src> lsel(g, H::present ? ls_h : st->lin_sel); const LinBuf& L = lsel.get();
     if (RUNS) {
         __shared__ double sp[4 * 42];
         const double mine = run_partial_sum(g, bd.x, bd.y, lane, wave, 4);
@@ -1884,6 +1964,12 @@ __global__ __launch_bounds__(256) void k_schur_finalize(const Src src) {
         const double part = lane < 42 ? ((sp[lane] + sp[42 + lane]) + sp[84 + lane]) + sp[126 + lane] : 0.0;
         schur_block<false>(g, L, st, b, lane, bd, be, part);
     } else schur_block<false>(g, L, st, b, lane, bd, be);
+}
+template <class Src, bool RUNS = false>
+__global__ __launch_bounds__(256) void k_schur_finalize(const Src src) { schur_finalize_body<Src, RUNS>(src, NoHead{}); }
+// (lone window, pair-list gather: the head arrives in user SGPRs)
+__global__ __launch_bounds__(256) void k_schur_finalize_head(LmState* st, const int4* blk_desc, const int32_t n_blk, const One src) {
+    schur_finalize_body<One, false>(src, FinHead{ st, blk_desc, n_blk });
 }
 
 // ================================================================= K6: block-Jacobi PCG on S, persistent
@@ -2248,11 +2334,13 @@ struct ReduceScatterUp<N, 64> {
 // damped solve.  Finalise-only waves never wait, row waves wait for finalise waves (dispatched right behind them) and for each other as
 // before: the co-residency requirement is still "the Npf row waves of a window".  The q hand-off tags carry the unit (tag =
 // unit << 10 | iteration + 1) because nobody zeroes the granules between the units of one optimise call any more (k_reset does, once).
-template <class Src, int GV, bool FIN = false>
-__global__ __launch_bounds__(64) void k_pcg1(const Src src) {
+template <class Src, int GV, bool FIN, class H>
+__device__ __forceinline__ void pcg1_body(const Src& src, const H& hd) {
     static_assert(!FIN || GV == 1, "the fused finalisation rides on the default gather variant");
+    static_assert(!H::present || (!FIN && GV == 1 && !Src::batched), "head arguments serve the EARLY form only");
     const DeviceGraph& g = graph_of(src);
-    LmState* st = state_of(src, g);
+    const auto& h = head_ref(hd, g);
+    LmState* st = state_of(src, g, hd);
     if (GV == 3 && (blockIdx.x & 7) != (blockIdx.y & 7)) return;
     const int lane = threadIdx.x;
     unsigned unit_tag = 0u;
@@ -2284,24 +2372,27 @@ __global__ __launch_bounds__(64) void k_pcg1(const Src src) {
         if (!(st->mode & MODE_TRIAL)) return;
         if (i0 >= g.Npf) return;                      // a batched launch is sized for the largest window
     } else {
-        if (i0 >= g.Npf) return;                      // a batched launch is sized for the largest window
-        const int lc = lane < g.Npf ? lane : 0;
-        code_pre = g.pcg1_code[i0 * g.Npf + lc];
-        const double2* Mb = reinterpret_cast<const double2*>(g.Minv + 36 * (size_t)lc);
+        if (i0 >= h.Npf) return;                      // a batched launch is sized for the largest window
+        const int lc = lane < h.Npf ? lane : 0;
+        code_pre = h.pcg1_code[i0 * h.Npf + lc];
+        const double2* Mb = reinterpret_cast<const double2*>(h.Minv + 36 * (size_t)lc);
 #pragma unroll
         for (int q = 0; q < 18; ++q) m_pre[q] = Mb[q];
 #pragma unroll
-        for (int c = 0; c < 6; ++c) b_pre[c] = g.bs[6 * lc + c];
-        ip0 = g.free_pose[i0];
+        for (int c = 0; c < 6; ++c) b_pre[c] = h.bs[6 * lc + c];
+        ip0 = h.free_pose[i0];
         const int mode = st->mode;
         sel0 = st->sel; res_in0 = st->pcg_res_in;
         // (the loads above are issued before the gate is waited for, and the gate's wait covers the other state words and
         // free_pose[i0]: the empty statement keeps the compiler from sinking those loads behind the branch)
         __builtin_amdgcn_sched_barrier(0);
-        asm volatile("" :: "s"(mode), "s"(sel0), "s"(res_in0), "s"(ip0));
+        if constexpr (H::present)     // (head form: all of the above left from preloaded registers; what the rest of the kernel takes from the graph is requested here, under the same wait)
+            asm volatile("" :: "s"(mode), "s"(sel0), "s"(res_in0), "s"(ip0), "s"(g.pose[0]), "s"(g.pose[1]), "s"(g.granules), "s"(g.x), "s"(g.fault_pcg));
+        else
+            asm volatile("" :: "s"(mode), "s"(sel0), "s"(res_in0), "s"(ip0));
         if (!(mode & MODE_TRIAL)) return;
     }
-    const int Npf = g.Npf, n6 = 6 * Npf;
+    const int Npf = h.Npf, n6 = 6 * Npf;
     const bool own = lane < Npf;
 #ifdef VISFS_BA_STAMPS
 #define PCG1_STAMP(slot) do { if (lane == 0 && i0 == g.stamp_wg && (slot) < 97) g.stamps[(slot)] = wall_clock64(); } while (0)
@@ -2310,7 +2401,7 @@ __global__ __launch_bounds__(64) void k_pcg1(const Src src) {
 #define PCG1_STAMP(slot) do { } while (0)
 #endif
     // ---- set-up: S(i0, lane), Minv_lane, r = b_s; every load below is independent of the others
-    const int code = EARLY ? (own ? code_pre : -1) : (own ? g.pcg1_code[i0 * Npf + lane] : -1);
+    const int code = EARLY ? (own ? code_pre : -1) : (own ? h.pcg1_code[i0 * Npf + lane] : -1);
     const unsigned spin_limit = g.fault_pcg ? (1u << 10) : (1u << 22);
     bool timeout = false;
     double Sr[36], mm[36], rr[6], dd[6], xx[6];
@@ -2355,8 +2446,8 @@ __global__ __launch_bounds__(64) void k_pcg1(const Src src) {
         for (int c = 0; c < 6; ++c) xx[c] = 0.0;
     } else {
         // (EARLY: only S still waits for `code`; Minv and b_s arrived with the gate)
-        const double2* Sb = reinterpret_cast<const double2*>(g.S + 36 * (size_t)(code >= 0 ? (code >> 1) : 0));
-        const double2* Mb = reinterpret_cast<const double2*>(g.Minv + 36 * (size_t)(own ? lane : 0));
+        const double2* Sb = reinterpret_cast<const double2*>(h.S + 36 * (size_t)(code >= 0 ? (code >> 1) : 0));
+        const double2* Mb = reinterpret_cast<const double2*>(h.Minv + 36 * (size_t)(own ? lane : 0));
         double sv[36];
 #pragma unroll
         for (int q = 0; q < 18; ++q) {
@@ -2374,7 +2465,7 @@ __global__ __launch_bounds__(64) void k_pcg1(const Src src) {
 #pragma unroll
             for (int c = 0; c < 6; ++c) Sr[6 * r + c] = tr ? sv[6 * c + r] : sv[6 * r + c];
 #pragma unroll
-        for (int c = 0; c < 6; ++c) { rr[c] = own ? (EARLY ? b_pre[c] : g.bs[6 * (own ? lane : 0) + c]) : 0.0; xx[c] = 0.0; }
+        for (int c = 0; c < 6; ++c) { rr[c] = own ? (EARLY ? b_pre[c] : h.bs[6 * (own ? lane : 0) + c]) : 0.0; xx[c] = 0.0; }
     }
     // the epilogue's operand: pose free_pose[i0] of the current estimate (nobody writes pose[sel] during a unit) is fetched behind S,
     // under the set-up, so that the launch ends with arithmetic on registers and stores instead of two more cold round trips
@@ -2568,6 +2659,12 @@ __global__ __launch_bounds__(64) void k_pcg1(const Src src) {
     // tail: iterations run, the loop's exit, behind the last store (slots of their own: the ones from 32 on are also k_backsub's)
     if (lane == 0 && i0 == g.stamp_wg) { g.stamps[97] = (unsigned long long)iter; g.stamps[99] = t_exit; __builtin_amdgcn_s_waitcnt(0); g.stamps[98] = wall_clock64(); }
 #endif
+}
+template <class Src, int GV, bool FIN = false>
+__global__ __launch_bounds__(64) void k_pcg1(const Src src) { pcg1_body<Src, GV, FIN>(src, NoHead{}); }
+// (lone window, default gather variant, no finalisation on board: the head arrives in user SGPRs)
+__global__ __launch_bounds__(64) void k_pcg1_head(LmState* st, const int32_t* pcg1_code, double* Minv, double* bs, const int32_t* free_pose, double* S, const int32_t Npf, const One src) {
+    pcg1_body<One, 1, false>(src, PcgHead{ st, pcg1_code, Minv, bs, free_pose, S, Npf });
 }
 
 // ---- K6, reduced systems that fit ONE compute unit: no cross-workgroup hand-off at all
@@ -3855,21 +3952,25 @@ __device__ __forceinline__ void backsub_landmark(const DeviceGraph& g, const Lin
 #ifndef VISFS_BA_BATCH_LINA_WAVES
 #define VISFS_BA_BATCH_LINA_WAVES 4      // waves per SIMD the batched fused tail is compiled for (A/B builds)
 #endif
-template <int G, class Src, bool ODOSPEC, bool STG = true, bool DEC = false, int DL = 0, bool LINA = false>
-__global__ __launch_bounds__(256, (DEC && Src::batched) ? (LINA ? (ODOSPEC ? 2 : VISFS_BA_BATCH_LINA_WAVES) : 5) : 1) void k_backsub(const Src src) {
+template <int G, class Src, bool ODOSPEC, bool STG, bool DEC, int DL, bool LINA, class H>
+__device__ __forceinline__ void backsub_body(const Src& src, const H& hd) {
     static_assert(!(DEC && ODOSPEC) || LINA, "the decision rides on the gated unit only");
     static_assert(DL == 0 || (!DEC && !ODOSPEC), "the dogleg passes are plain launches");
     static_assert(!LINA || (DEC && DL == 0), "the fused tail carries the decision");
     extern __shared__ __attribute__((aligned(16))) double smem[];
     // PRE (the fused tail of a lone window): what does not depend on the LM state is loaded in front of the gate — see below
     constexpr bool PRE = LINA && !Src::batched && STG;
+    static_assert(!H::present || PRE, "head arguments serve the fused tail of a lone window only");
+    const DeviceGraph& g = graph_of(src);
+    const auto& h = head_ref(hd, g);
     if (DEC) {
-        const int dw = decider_window();
+        int dw;
+        if constexpr (H::present) dw = (int)blockIdx.x < hd.n_work ? -1 : (int)blockIdx.x - hd.n_work;     // (one grid row: decider_window() without the hidden grid-size argument)
+        else dw = decider_window();
         if (dw >= 0) { decider_of<PRE>(src, dw, smem, LINA ? 2 : 0); return; }
         if (dw == -2) return;
     }
-    const DeviceGraph& g = graph_of(src);
-    LmState* st = state_of(src, g);
+    LmState* st = state_of(src, g, hd);
 #ifdef VISFS_BA_STAMPS
 #define BS_STAMP(slot) do { if (LINA && threadIdx.x == 0 && blockIdx.x == (unsigned)g.stamp_wg) g.stamps[32 + (slot)] = wall_clock64(); } while (0)
 #else
@@ -3894,37 +3995,52 @@ __global__ __launch_bounds__(256, (DEC && Src::batched) ? (LINA ? (ODOSPEC ? 2 :
     unsigned st_epoch = 0u;
     if constexpr (PRE) {
         pre.k0 = 0; pre.k1 = 0; pre.fixed = true; pre.kf = -1; pre.ipf = 0; pre.af = -1; pre.u = pre.v = pre.ur = 0.0; pre.act = false;
-        if (g.Np > 0) {
-            const int ic = min((int)threadIdx.x, g.Np - 1);
-            const double* a0 = g.pose[0] + POSE_STRIDE * ic;
-            const double* a1 = g.pose[1] + POSE_STRIDE * ic;
+        if constexpr (H::present) {
+            // (head form: st, both pose buffers, lm_ptr and the counts arrived in registers with the wave, so the state's words leave
+            // FIRST, the pose and index loads right behind them, and the graph's fields — pt, pt_fixed and what the second level
+            // needs — are requested in the same window: one wait covers the state and the argument segment)
+            st_mode = st->mode; st_failed = st->solver_failed; st_timeout = st->pcg_timeout; st_sel = st->sel; st_ls = st->lin_sel;
+            st_lambda = st->lambda; st_epoch = st->decide_epoch;
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        if (h.Np > 0) {
+            const int ic = min((int)threadIdx.x, h.Np - 1);
+            const double* a0 = h.pose[0] + POSE_STRIDE * ic;
+            const double* a1 = h.pose[1] + POSE_STRIDE * ic;
 #pragma unroll
             for (int c = 0; c < 7; ++c) { pq0[c] = a0[c]; pq1[c] = a1[c]; }
         }
-        if (g.Nl > 0) {
-            lcl = min((int)blockIdx.x * (256 / G) + (int)threadIdx.x / G, g.Nl - 1);
-            pre.k0 = g.lm_ptr[lcl]; pre.k1 = g.lm_ptr[lcl + 1];
+        if (h.Nl > 0) {
+            lcl = min((int)blockIdx.x * (256 / G) + (int)threadIdx.x / G, h.Nl - 1);
+            pre.k0 = h.lm_ptr[lcl]; pre.k1 = h.lm_ptr[lcl + 1];
             fixed_raw = g.pt_fixed[lcl];              // (compared behind the state's read: a flag formed here would wait for the byte)
 #pragma unroll
             for (int c = 0; c < 3; ++c) { pw0[c] = g.pt[0][3 * lcl + c]; pw1[c] = g.pt[1][3 * lcl + c]; }
         }
         __builtin_amdgcn_sched_barrier(0);            // (nothing that waits for those loads may move in front of the state's)
-        st_mode = st->mode; st_failed = st->solver_failed; st_timeout = st->pcg_timeout; st_sel = st->sel; st_ls = st->lin_sel;
-        st_lambda = st->lambda; st_epoch = st->decide_epoch;
+        if constexpr (!H::present) {
+            st_mode = st->mode; st_failed = st->solver_failed; st_timeout = st->pcg_timeout; st_sel = st->sel; st_ls = st->lin_sel;
+            st_lambda = st->lambda; st_epoch = st->decide_epoch;
+        }
         __builtin_amdgcn_sched_barrier(0);
+        if constexpr (H::present)     // (... and for the graph's fields that the second level and the landmark role start from)
+            asm volatile("" :: "s"(st_mode), "s"(st_failed), "s"(st_timeout), "s"(st_sel), "s"(st_ls), "s"(st_lambda), "s"(st_epoch), "s"(g.No), "s"(g.n_lin_a), "s"(g.obs_pose),
+                         "s"(g.obs_level), "s"(g.obs_ok), "s"(g.obs_uvr), "s"(g.pose_free), "s"(g.lin_stride), "s"(g.lin[0].Hll), "s"(g.lin[0].bl), "s"(g.lin[0].obs_w),
+                         "s"(g.lin[0].obs_pcw), "s"(g.x));
+        else
         asm volatile("" :: "s"(st_mode), "s"(st_failed), "s"(st_timeout), "s"(st_sel), "s"(st_ls), "s"(st_lambda), "s"(st_epoch));   // (one wait for all of them, here)
         // second level: the lane's first observation, and what the CURRENT linearisation set (lin_sel: 0 or 1 whatever the gate says;
         // this launch writes the other one) holds for it and for the landmark
         pre.wf = 0.0; pre.sd[0] = pre.sd[1] = pre.sd[2] = pre.sd[3] = 0.0;
         asm volatile("" : "+v"(fixed_raw));
         pre.fixed = fixed_raw != 0u;
-        if (g.Nl > 0) {
+        if (h.Nl > 0) {
             const LinSel<Src> lnow(g, st_ls); const LinBuf& L = lnow.get();
 #pragma unroll
             for (int c = 0; c < 6; ++c) pre.H[c] = L.Hll[6 * (size_t)lcl + c];
 #pragma unroll
             for (int c = 0; c < 3; ++c) pre.B[c] = L.bl[3 * (size_t)lcl + c];
-            if (g.No > 0 && g.Np > 0) {
+            if (g.No > 0 && h.Np > 0) {
                 const int kq = pre.k0 + (int)threadIdx.x % G;
                 const int kcl = min(max(kq, 0), g.No - 1);
                 pre.kf = kq < pre.k1 ? kq : -1;
@@ -3934,7 +4050,7 @@ __global__ __launch_bounds__(256, (DEC && Src::batched) ? (LINA ? (ODOSPEC ? 2 :
                 pre.wf = L.obs_w[kcl];
                 const double2* seed = reinterpret_cast<const double2*>(L.obs_pcw + 4 * (size_t)kcl);
                 const double2 s0 = seed[0], s1 = seed[1];
-                pre.ipf = min(max(ip_raw, 0), g.Np - 1);                  // (a valid observation names a pose of the window: the clamp never acts on one)
+                pre.ipf = min(max(ip_raw, 0), h.Np - 1);                  // (a valid observation names a pose of the window: the clamp never acts on one)
                 pre.af = g.pose_free[pre.ipf];
                 pre.act = (lv == 0u) & (okb != 0u);
                 pre.sd[0] = s0.x; pre.sd[1] = s0.y; pre.sd[2] = s1.x; pre.sd[3] = s1.y;
@@ -3950,9 +4066,9 @@ __global__ __launch_bounds__(256, (DEC && Src::batched) ? (LINA ? (ODOSPEC ? 2 :
     if (!DEC && !LINA && !Src::batched && blockIdx.x == 0 && threadIdx.x == 0) { st->spec_go = go ? 1 : 0; st->spec_src = st->sel ^ 1; st->spec_dst = st->lin_sel ^ 1; }
     if (!go) return;
     double* sRt = smem;
-    double* red = smem + (STG ? 12 * g.Np : 0);
+    double* red = smem + (STG ? 12 * h.Np : 0);
     const int sel = PRE ? st_sel : st->sel, ls = PRE ? st_ls : st->lin_sel;
-    const double* __restrict__ pose_t = g.pose[sel ^ 1];      // trial poses (written by the solver epilogue)
+    const double* __restrict__ pose_t = pose_of(h, sel ^ 1);      // trial poses (written by the solver epilogue)
     const double* __restrict__ pt = g.pt[sel];
     double* __restrict__ pt_t = g.pt[sel ^ 1];
     const double lambda = PRE ? st_lambda : st->lambda;
@@ -3970,7 +4086,7 @@ __global__ __launch_bounds__(256, (DEC && Src::batched) ? (LINA ? (ODOSPEC ? 2 :
             for (int c = 0; c < 6; ++c) vp[c] = -g.bp[6 * (size_t)a + c] / damp_of(g, 1.0, g.Hpp[36 * (size_t)a + 7 * c], g.s2p, 6 * (size_t)a + c);
             for (int z = tid; z < g.Nz; z += 256) {
                 double J[6];
-                laser_jacobian(g.pose[sel] + POSE_STRIDE * g.laser_pose, g.Tcr, Vec3{ g.laser_xyz[3 * z], g.laser_xyz[3 * z + 1], g.laser_xyz[3 * z + 2] }, g.grid, J, true);
+                laser_jacobian(pose_of(h, sel) + POSE_STRIDE * g.laser_pose, g.Tcr, Vec3{ g.laser_xyz[3 * z], g.laser_xyz[3 * z + 1], g.laser_xyz[3 * z + 2] }, g.grid, J, true);
                 double r = 0.0;
 #pragma unroll
                 for (int c = 0; c < 6; ++c) r += J[c] * vp[c];
@@ -4011,27 +4127,27 @@ __global__ __launch_bounds__(256, (DEC && Src::batched) ? (LINA ? (ODOSPEC ? 2 :
     if constexpr (PRE) {
         pre.pw = sel ? Vec3{ pw1[0], pw1[1], pw1[2] } : Vec3{ pw0[0], pw0[1], pw0[2] };
         // the first 256 poses come from registers: pose[sel ^ 1] is the trial, pose[sel] the linearisation point
-        if (tid < g.Np) {
+        if (tid < h.Np) {
             double tq_t[7], tq_0[7];
 #pragma unroll
             for (int c = 0; c < 7; ++c) { tq_t[c] = sel ? pq0[c] : pq1[c]; tq_0[c] = sel ? pq1[c] : pq0[c]; }
             stage_pose(tq_t, sRt + 12 * tid);
             stage_pose(tq_0, sRt0 + 12 * tid);
         }
-        stage_poses(pose_t, g.Np, sRt, 256);
-        stage_poses(g.pose[sel], g.Np, sRt0, 256);
+        stage_poses(pose_t, h.Np, sRt, 256);
+        stage_poses(pose_of(h, sel), h.Np, sRt0, 256);
         __syncthreads();
     } else if (STG) {
-        stage_poses(pose_t, g.Np, sRt);
-        stage_poses(g.pose[sel], g.Np, sRt0);
+        stage_poses(pose_t, h.Np, sRt);
+        stage_poses(pose_of(h, sel), h.Np, sRt0);
         __syncthreads();
     }
     BS_STAMP(2);
-    const PoseSrc<STG> Pt{ STG ? sRt : pose_t }, P0{ STG ? sRt0 : (const double*)g.pose[sel] };
+    const PoseSrc<STG> Pt{ STG ? sRt : pose_t }, P0{ STG ? sRt0 : (const double*)pose_of(h, sel) };
     const LinSel<Src> lsel(g, ls); const LinBuf& L = lsel.get();
     constexpr int LPW = 256 / G;
     const int l = bid * LPW + tid / G, sub = tid % G;
-    const bool lvalid = l < g.Nl;
+    const bool lvalid = l < h.Nl;
     double chi_acc = 0.0, scale_acc = 0.0, step_acc = 0.0, dot_acc = 0.0;
     Vec3 pn{ 0.0, 0.0, 0.0 };
     backsub_landmark<G, STG, DL, PRE>(g, L, l, lvalid, sub, Pt, P0, pt, pt_t, lambda, K, iv, delta, chi_acc, scale_acc, &step_acc, &dot_acc, st->dl_A, st->dl_B, LINA ? &pn : nullptr,
@@ -4057,6 +4173,15 @@ __global__ __launch_bounds__(256, (DEC && Src::batched) ? (LINA ? (ODOSPEC ? 2 :
         // which linearises with k_linearize)
         BS_STAMP(5);
     }
+}
+template <int G, class Src, bool ODOSPEC, bool STG = true, bool DEC = false, int DL = 0, bool LINA = false>
+__global__ __launch_bounds__(256, (DEC && Src::batched) ? (LINA ? (ODOSPEC ? 2 : VISFS_BA_BATCH_LINA_WAVES) : 5) : 1) void k_backsub(const Src src) {
+    backsub_body<G, Src, ODOSPEC, STG, DEC, DL, LINA>(src, NoHead{});
+}
+// (the fused tail of a lone window's speculative unit: the head arrives in user SGPRs; n_work = the workgroups in front of the decider)
+template <int G, bool ODOSPEC>
+__global__ __launch_bounds__(256, 1) void k_backsub_head(LmState* st, double* pose0, double* pose1, const int32_t* lm_ptr, const int32_t Np, const int32_t Nl, const int32_t n_work, const One src) {
+    backsub_body<G, One, ODOSPEC, true, true, 0, true>(src, BacksubHead{ st, { pose0, pose1 }, lm_ptr, Np, Nl, n_work });
 }
 
 // Between the two dogleg passes (one workgroup): the inner products summed in a fixed order, the step coefficients and the model cost
@@ -4998,13 +5123,22 @@ static void launch_schur_partial_src(const Src& src, const LaunchDims& d, int B,
         else TIMED_LAUNCH((k_schur_partial<false, Src, true>), dim3(d.sch_wgs, B), dim3(256), 0, s, src);
         return;
     }
-    if (d.sch_multi) TIMED_LAUNCH((k_schur_partial<true, Src>), dim3(d.sch_wgs, B), dim3(256), 0, s, src);
-    else TIMED_LAUNCH((k_schur_partial<false, Src>), dim3(d.sch_wgs, B), dim3(256), 0, s, src);
+    if constexpr (!Src::batched) {                                         // a lone window: the head arguments travel in front of the graph
+        const SchurHead h = head_of_schur(src.g);
+        if (d.sch_multi) TIMED_LAUNCH((k_schur_partial_head<true, false>), dim3(d.sch_wgs, B), dim3(256), 0, s, h.st, h.sch_desc, h.blk_pairs, h.pose_rec, h.chunk_ptr, h.chunk_pose, h.n_sch, h.n_chunks, src);
+        else TIMED_LAUNCH((k_schur_partial_head<false, false>), dim3(d.sch_wgs, B), dim3(256), 0, s, h.st, h.sch_desc, h.blk_pairs, h.pose_rec, h.chunk_ptr, h.chunk_pose, h.n_sch, h.n_chunks, src);
+    } else {
+        if (d.sch_multi) TIMED_LAUNCH((k_schur_partial<true, Src>), dim3(d.sch_wgs, B), dim3(256), 0, s, src);
+        else TIMED_LAUNCH((k_schur_partial<false, Src>), dim3(d.sch_wgs, B), dim3(256), 0, s, src);
+    }
 }
 template <class Src>
 static void launch_schur_finalize_src(const Src& src, const LaunchDims& d, int B, hipStream_t s) {
     if (d.run_wgs > 0) TIMED_LAUNCH((k_schur_finalize<Src, true>), dim3(d.fin_wgs, B), dim3(256), 0, s, src);     // one workgroup per block
-    else TIMED_LAUNCH((k_schur_finalize<Src>), dim3(d.fin_wgs, B), dim3(256), 0, s, src);
+    else if constexpr (!Src::batched) {
+        const FinHead h = head_of_fin(src.g);
+        TIMED_LAUNCH(k_schur_finalize_head, dim3(d.fin_wgs, B), dim3(256), 0, s, h.st, h.blk_desc, h.n_blk, src);
+    } else TIMED_LAUNCH((k_schur_finalize<Src>), dim3(d.fin_wgs, B), dim3(256), 0, s, src);
 }
 template <class Src>
 static void launch_pcg_src(const Src& src, const LaunchDims& d, int B, hipStream_t s) {
@@ -5018,7 +5152,12 @@ static void launch_pcg_src(const Src& src, const LaunchDims& d, int B, hipStream
         if (gv == 3 && !Src::batched) TIMED_LAUNCH((k_pcg1<One, 3>), dim3(8 * d.pcg_rows, B), dim3(64), 0, s, One{ graph_of_host(src) });
         else if (gv >= 2) TIMED_LAUNCH((k_pcg1<Src, 2>), dim3(d.pcg_rows, B), dim3(64), 0, s, src);
         else if (gv == 1 && d.fin_pcg) TIMED_LAUNCH((k_pcg1<Src, 1, true>), dim3(d.fin_pcg_wgs, B), dim3(64), 0, s, src);     // finalisation on board
-        else if (gv == 1) TIMED_LAUNCH((k_pcg1<Src, 1>), dim3(d.pcg_rows, B), dim3(64), 0, s, src);
+        else if (gv == 1) {
+            if constexpr (!Src::batched) {
+                const PcgHead h = head_of_pcg(src.g);
+                TIMED_LAUNCH(k_pcg1_head, dim3(d.pcg_rows, B), dim3(64), 0, s, h.st, h.pcg1_code, h.Minv, h.bs, h.free_pose, h.S, h.Npf, src);
+            } else TIMED_LAUNCH((k_pcg1<Src, 1>), dim3(d.pcg_rows, B), dim3(64), 0, s, src);
+        }
         else TIMED_LAUNCH((k_pcg1<Src, 0>), dim3(d.pcg_rows, B), dim3(64), 0, s, src);
     }
     else if (d.pcg_rows <= 64) TIMED_LAUNCH((k_pcg<1, true, Src, false>), dim3(d.pcg_rows, B), dim3(256), (size_t)d.pcg_lds, s, src);
@@ -5079,8 +5218,14 @@ template <int G, class Src>
 static void launch_backsub_lin_t(const Src& src, const LaunchDims& d, int B, hipStream_t s) {
     const size_t lds = (size_t)std::max(24 * d.np + 8, 128) * sizeof(double);
     // grid: the landmark workgroups + the odometry / laser workgroup of the largest window, then one decider per window in the last grid row
-    if (d.has_odo) { ensure_lds(k_backsub<G, Src, true, true, true, 0, true>, lds); TIMED_LAUNCH((k_backsub<G, Src, true, true, true, 0, true>), dim3(d.backsub_blocks + B, B), dim3(256), lds, s, src); }
-    else { ensure_lds(k_backsub<G, Src, false, true, true, 0, true>, lds); TIMED_LAUNCH((k_backsub<G, Src, false, true, true, 0, true>), dim3(d.backsub_blocks + B, B), dim3(256), lds, s, src); }
+    if constexpr (!Src::batched) {                                         // a lone window (B == 1): the head arguments travel in front of the graph
+        const BacksubHead h = head_of_backsub(src.g, d.backsub_blocks);
+        if (d.has_odo) { ensure_lds(k_backsub_head<G, true>, lds); TIMED_LAUNCH((k_backsub_head<G, true>), dim3(d.backsub_blocks + 1, 1), dim3(256), lds, s, h.st, h.pose[0], h.pose[1], h.lm_ptr, h.Np, h.Nl, h.n_work, src); }
+        else { ensure_lds(k_backsub_head<G, false>, lds); TIMED_LAUNCH((k_backsub_head<G, false>), dim3(d.backsub_blocks + 1, 1), dim3(256), lds, s, h.st, h.pose[0], h.pose[1], h.lm_ptr, h.Np, h.Nl, h.n_work, src); }
+    } else {
+        if (d.has_odo) { ensure_lds(k_backsub<G, Src, true, true, true, 0, true>, lds); TIMED_LAUNCH((k_backsub<G, Src, true, true, true, 0, true>), dim3(d.backsub_blocks + B, B), dim3(256), lds, s, src); }
+        else { ensure_lds(k_backsub<G, Src, false, true, true, 0, true>, lds); TIMED_LAUNCH((k_backsub<G, Src, false, true, true, 0, true>), dim3(d.backsub_blocks + B, B), dim3(256), lds, s, src); }
+    }
 }
 template <class Src>
 static void launch_backsub_lin_src(const Src& src, const LaunchDims& d, int B, hipStream_t s) {
@@ -5102,8 +5247,14 @@ static void launch_schur_partial_roleb_src(const Src& src, const LaunchDims& d, 
     }
     const int grid = d.sch_wgs + d.chunks;                    // (a window's role-B workgroups start right behind ITS share of the chunk list)
     if (grid <= 0) return;
-    if (d.sch_multi) TIMED_LAUNCH((k_schur_partial<true, Src, false, true>), dim3(grid, B), dim3(256), 0, s, src);
-    else TIMED_LAUNCH((k_schur_partial<false, Src, false, true>), dim3(grid, B), dim3(256), 0, s, src);
+    if constexpr (!Src::batched) {
+        const SchurHead h = head_of_schur(src.g);
+        if (d.sch_multi) TIMED_LAUNCH((k_schur_partial_head<true, true>), dim3(grid, B), dim3(256), 0, s, h.st, h.sch_desc, h.blk_pairs, h.pose_rec, h.chunk_ptr, h.chunk_pose, h.n_sch, h.n_chunks, src);
+        else TIMED_LAUNCH((k_schur_partial_head<false, true>), dim3(grid, B), dim3(256), 0, s, h.st, h.sch_desc, h.blk_pairs, h.pose_rec, h.chunk_ptr, h.chunk_pose, h.n_sch, h.n_chunks, src);
+    } else {
+        if (d.sch_multi) TIMED_LAUNCH((k_schur_partial<true, Src, false, true>), dim3(grid, B), dim3(256), 0, s, src);
+        else TIMED_LAUNCH((k_schur_partial<false, Src, false, true>), dim3(grid, B), dim3(256), 0, s, src);
+    }
 }
 void launch_backsub_lin_decide(const DeviceGraph& g, hipStream_t s) { launch_backsub_lin_src(One{ g }, dims_of(g), 1, s); }
 void launch_schur_partial_roleb(const DeviceGraph& g, hipStream_t s) { launch_schur_partial_roleb_src(One{ g }, dims_of(g), 1, s); }
@@ -5233,15 +5384,18 @@ void launch_small_optimize_batch(const DeviceGraph* gs, int B, int solver, int h
     hipLaunchKernelGGL((k_small_optimize<Many>), dim3(1, B), dim3(SM_T), 0, s, Many{ gs }, solver, half);
 }
 // Every window's whole LmState, contiguous (one D2H copy instead of one per window).
-__global__ void k_gather_lm(const DeviceGraph* gs, int B, LmState* out) {
+// (its arguments travel as one by-value struct: separate scalars would be preloaded into user SGPRs by the flag this file is built with,
+// which is meant for the k_*_head kernels alone)
+struct GatherLmArgs { const DeviceGraph* gs; int B; LmState* out; };
+__global__ void k_gather_lm(const GatherLmArgs a) {
     const int b = blockIdx.x;
-    if (b >= B) return;
-    const unsigned* src = reinterpret_cast<const unsigned*>(gs[b].st);
-    unsigned* dst = reinterpret_cast<unsigned*>(out + b);
+    if (b >= a.B) return;
+    const unsigned* src = reinterpret_cast<const unsigned*>(a.gs[b].st);
+    unsigned* dst = reinterpret_cast<unsigned*>(a.out + b);
     for (int t = threadIdx.x; t < (int)(sizeof(LmState) / 4); t += blockDim.x) dst[t] = src[t];
 }
 void launch_gather_lm(const DeviceGraph* gs, int B, LmState* out, hipStream_t s) {
-    hipLaunchKernelGGL(k_gather_lm, dim3(B), dim3(64), 0, s, gs, B, out);
+    hipLaunchKernelGGL(k_gather_lm, dim3(B), dim3(64), 0, s, GatherLmArgs{ gs, B, out });
 }
 
 // How many workgroups of the persistent PCG kernel this launch geometry would use can be RESIDENT on the device at once
