@@ -1828,9 +1828,96 @@ __device__ __forceinline__ double run_partial_sum(const DeviceGraph& g, const in
 __device__ __forceinline__ void st_pub(double* p, const double v) {
     __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-template <bool PUB = false, bool ARR = false>
+// VISFS_BA_CHAINS (a measurement switch like VISFS_BA_POSE_SEEDS): 1 — k_schur_finalize_head sums a block's partials
+// from windows of loads (WIN below); 0 — it keeps the form of the other instantiations, i.e. the code it had before.
+#ifndef VISFS_BA_CHAINS
+#define VISFS_BA_CHAINS 1
+#endif
+// ONE unconditional load from `on ? p : safe`.  The address passes through an empty asm statement: left to itself the compiler turns
+// the select of two addresses back into a branch around the load, and the branch takes the first use — and its wait — with it.
+template <class T>
+__device__ __forceinline__ T ld_sel(const T* p, const void* safe, const bool on) {
+    static_assert(sizeof(T) == 4 || sizeof(T) == 8 || sizeof(T) == 16, "one global load of 4, 8 or 16 bytes");
+    typedef int words_t __attribute__((ext_vector_type(sizeof(T) / 4)));
+    unsigned long long a = on ? reinterpret_cast<unsigned long long>(p) : reinterpret_cast<unsigned long long>(safe);
+    asm("" : "+v"(a));
+    const words_t w = *reinterpret_cast<const __attribute__((address_space(1))) words_t*>(a);
+    T out;
+    __builtin_memcpy(&out, &w, sizeof(T));
+    return out;
+}
+// In-kernel stamps of the finalisation (-DVISFS_BA_STAMPS, tools/schur_stamps.py): the wave of block g.stamp_wg writes slots 110..115 —
+// entry, gate passed, gather partials summed, all sums done, last store issued, stores drained.  `dep` is a value the stamp must not
+// be taken in front of (the empty asm wants it in a register, i.e. its loads waited for).
+#ifdef VISFS_BA_STAMPS
+#define FIN_STAMP(slot, dep) do { asm volatile("" :: "v"(dep)); if (lane == 0 && b == g.stamp_wg) g.stamps[110 + (slot)] = wall_clock64(); } while (0)
+#else
+#define FIN_STAMP(slot, dep) do { } while (0)
+#endif
+// WIN (the lone window's k_schur_finalize_head): a block's partials are loaded a WINDOW at a time — FIN_W loads in flight
+// before the first add — instead of one round trip per (unrolled group of) partials; the adds keep their order (chunks ascending, then
+// odometry entries ascending).  A load beyond the range is turned to `safe` — a word that always exists, the LM state's first: the
+// arrays may be empty, and a branch around the load would take the first add (and its wait) with it — and its add is skipped with a
+// select on the running sum: adding a masked 0.0 would turn a -0.0 into +0.0.
+constexpr int FIN_W = 8;        // gather / pose-major partials per window (C2: at most 8 gather chunks a block, 5 pose-major chunks a pose)
+constexpr int FIN_WO = 4;       // odometry entries per window (a chain gives a pose two and an off-diagonal block one; a graph may hold any number: further windows loop)
+__device__ __forceinline__ int fin_odo_off(const int code, const bool diag, const int lane);
+template <int W>
+__device__ __forceinline__ void win_load(double (&v)[W], const double* base, const int stride, const int c0, const int c1, const int off, const bool on, const void* safe) {
+#pragma unroll
+    for (int k = 0; k < W; ++k) v[k] = ld_sel(base + ((size_t)stride * (size_t)(c0 + k) + off), safe, on && c0 + k < c1);
+}
+template <int W>
+__device__ __forceinline__ void win_load_codes(int (&v)[W], const int32_t* base, const int n0, const int n1, const void* safe) {
+#pragma unroll
+    for (int k = 0; k < W; ++k) v[k] = ld_sel(base + (n0 + k), safe, n0 + k < n1);
+}
+// (operands of a window of odometry codes: entry n0 + k of the block's list, the lane's word of its edge record)
+template <int W>
+__device__ __forceinline__ void win_load_odo(double (&v)[W], const double* odo_blk, const int (&code)[W], const int n0, const int n1, const bool diag, const int lane, const bool on, const void* safe) {
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+        const bool ok = on && n0 + k < n1;
+        const int cd = ok ? code[k] : 0;           // (beyond the range the code is a word of the LM state: no address from it)
+        v[k] = ld_sel(odo_blk + (120 * (size_t)(cd >> 1) + fin_odo_off(cd, diag, lane)), safe, ok);
+    }
+}
+template <int W>
+__device__ __forceinline__ double win_add(double acc, const double (&v)[W], const int c0, const int c1, const bool on) {
+#pragma unroll
+    for (int k = 0; k < W; ++k) acc = (on && c0 + k < c1) ? acc + v[k] : acc;
+    return acc;
+}
+// What the head kernel has in flight in front of its gate: the first window of the block's gather partials and of its odometry codes
+// (neither depends on the LM state or on lin_sel), and lambda beside the gate's words.
+struct FinPre { double part[FIN_W]; int code[FIN_WO]; double lambda; };
+// Offset of the lane's operand inside an odometry edge's record odo_blk[edge][120] (hpp_entry_r / the off-diagonal sum of schur_block).
+__device__ __forceinline__ int fin_odo_off(const int code, const bool diag, const int lane) {
+    const int r = lane / 6, c = lane % 6;
+    if (diag) return lane < 36 ? ((code & 1) ? 36 : 0) + lane : ((code & 1) ? 114 : 108) + (lane - 36);
+    return 72 + ((code & 1) ? (c * 6 + r) : lane);
+}
+template <bool PUB = false, bool ARR = false, bool WIN = false>
 __device__ __forceinline__ void schur_block(const DeviceGraph& g, const LinBuf& L, LmState* st, const int b, const int lane, const int4 bd, const int4 be, const double part_in = 0.0,
-                                            const unsigned pub_tag = 0u) {
+                                            const unsigned pub_tag = 0u, const FinPre* pre = nullptr) {
+    // (WIN: everything behind the gate that is a load leaves first — the first window of the pose-major partials, then, for a block
+    // with odometry entries only, the operands behind their codes: that is a level more, which a block without does not wait for —
+    // then the stores that clear the granules, then the sums)
+    [[maybe_unused]] double ov[FIN_WO], hw[FIN_W];
+    [[maybe_unused]] int hu = 0;
+    [[maybe_unused]] const int32_t* codes = nullptr;
+    [[maybe_unused]] bool on_odo = false;
+    if constexpr (WIN) {
+        const bool dg = (be.x == be.y);
+        codes = dg ? g.pose_odo : g.blk_odo;
+        on_odo = dg ? lane < 42 : lane < 36;
+        const int r = lane / 6, c = lane % 6;
+        hu = lane < 36 ? (r <= c ? upper_idx(r, c) : upper_idx(c, r)) : 21 + (lane - 36);
+        win_load(hw, L.hpp_part, 27, be.z, be.w, hu, dg && lane < 42, st);
+#pragma unroll
+        for (int k = 0; k < FIN_WO; ++k) ov[k] = 0.0;
+        if (bd.z < bd.w) win_load_odo(ov, L.odo_blk, pre->code, bd.z, bd.w, dg, lane, on_odo, st);
+    }
     if (!PUB) {   // zero the granules: n_blk >= Npf waves x 64 lanes cover 4 * 6 Npf words in one pass.
         // CONTRACT with the persistent PCG (k_pcg / k_pcg1) that follows: (1) EVERY block's wave runs this loop — the words are dealt
         // over all n_blk waves (stride n_blk * 64), so a kernel that calls schur_block for a subset of the blocks clears only a
@@ -1844,25 +1931,59 @@ __device__ __forceinline__ void schur_block(const DeviceGraph& g, const LinBuf& 
         const int nwords = 4 * 6 * g.Npf + g.Npf;           // q granules of both parities + one placement word per block row
         for (int w = b * 64 + lane; w < nwords; w += g.n_blk * 64) g.granules[w] = 0ull;
     }
-    const double lambda = st->lambda;
+    double lambda;
+    if constexpr (WIN) lambda = pre->lambda; else lambda = st->lambda;
     const int i = be.x, j = be.y;
     const bool diag = (i == j);
     const int r = lane / 6, c = lane % 6;    // meaningful for lane < 36
     double part = part_in;
-    if (g.n_runs > 0) {
+    [[maybe_unused]] double osum = 0.0;      // WIN: the odometry entries of the block, in entry order (0.0 + first, as the loops below start)
+    if constexpr (WIN) {
+        // (the head kernel is never launched behind k_schur_runs — launch_schur_finalize_src — so there is no n_runs test here)
+        part = win_add(part, pre->part, bd.x, bd.y, lane < 42);
+        for (int c0 = bd.x + FIN_W; c0 < bd.y; c0 += FIN_W) {       // more than FIN_W chunks: window by window (C2 never does)
+            double v[FIN_W];
+            win_load(v, g.sch_part, 42, c0, bd.y, lane, lane < 42, st);
+            part = win_add(part, v, c0, bd.y, lane < 42);
+        }
+    } else if (g.n_runs > 0) {
         // (k_schur_runs' partials: summed by run_partial_sum on the four waves of the block's workgroup, handed in)
     } else if (lane < 42) {
-        // (unroll 8 measured slower than 4: a C2 block has ~5 two-pass chunks, most of them would run in the remainder loop)
+        // (the compiler runs the REMAINDER loop of an unrolled loop first, one serial round trip — load, wait, add — per partial: n mod 4
+        // of them here, then one round trip per four.  "unroll 8 measured slower than 4" was that: up to seven serial round trips in
+        // front of the eight-wide loop.  The lone window's head kernel takes the windowed form above instead)
 #pragma unroll 4
         for (int ch = bd.x; ch < bd.y; ++ch) part += ARR ? ld_coherent(g.sch_part + 42 * (size_t)ch + lane) : g.sch_part[42 * (size_t)ch + lane];
+    }
+    FIN_STAMP(2, part);
+    if constexpr (WIN) {
+        // pose-major partials of a diagonal block first (hpp_entry_r's order), then the odometry entries
+        if (diag) {
+            osum = win_add(osum, hw, be.z, be.w, lane < 42);
+            for (int c0 = be.z + FIN_W; c0 < be.w; c0 += FIN_W) {
+                double v[FIN_W];
+                win_load(v, L.hpp_part, 27, c0, be.w, hu, lane < 42, st);
+                osum = win_add(osum, v, c0, be.w, lane < 42);
+            }
+        }
+        osum = win_add(osum, ov, bd.z, bd.w, on_odo);
+        for (int n0 = bd.z + FIN_WO; n0 < bd.w; n0 += FIN_WO) {          // codes in one window, then their operands in one window
+            int cd[FIN_WO];
+            double v[FIN_WO];
+            win_load_codes(cd, codes, n0, bd.w, st);
+            win_load_odo(v, L.odo_blk, cd, n0, bd.w, diag, lane, on_odo, st);
+            osum = win_add(osum, v, n0, bd.w, on_odo);
+        }
     }
     if (!diag) {
         if (lane < 36) {
             double base = 0.0;
-            for (int n = bd.z; n < bd.w; ++n) {
+            if constexpr (WIN) base = osum;
+            else for (int n = bd.z; n < bd.w; ++n) {
                 const int code = g.blk_odo[n];
                 base += L.odo_blk[120 * (size_t)(code >> 1) + 72 + ((code & 1) ? (c * 6 + r) : lane)];
             }
+            FIN_STAMP(3, base);
             if (PUB) st_pub(g.S + 36 * (size_t)b + lane, base - part); else g.S[36 * (size_t)b + lane] = base - part;
             if (!PUB && g.pcg_cu) {                           // k_pcg_cu reads S by scalar row: entry (r, c) belongs to row 6 i + r and, transposed, to row 6 j + c
                 const int sl = g.blk_slot[b];
@@ -1874,9 +1995,16 @@ __device__ __forceinline__ void schur_block(const DeviceGraph& g, const LinBuf& 
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             if (lane == 0) __hip_atomic_store(g.fin_flag + b, pub_tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
+#ifdef VISFS_BA_STAMPS
+        FIN_STAMP(4, part);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        FIN_STAMP(5, part);
+#endif
         return;
     }
-    const double hv = (lane < 42) ? hpp_entry_r<ARR>(g, L, lane, be.z, be.w, bd.z, bd.w) : 0.0;
+    double hv;
+    if constexpr (WIN) hv = osum; else hv = (lane < 42) ? hpp_entry_r<ARR>(g, L, lane, be.z, be.w, bd.z, bd.w) : 0.0;
+    FIN_STAMP(3, hv);
     const bool on_diag = lane < 36 && r == c;
     const unsigned long long nz = __ballot(on_diag && hv != 0.0);
     const bool pin = (nz == 0ull);
@@ -1898,6 +2026,11 @@ __device__ __forceinline__ void schur_block(const DeviceGraph& g, const LinBuf& 
         st->n_active[1] += 1;
         if (st->mode & MODE_LIN) st->n_active[0] += 1;
     }
+#ifdef VISFS_BA_STAMPS
+    FIN_STAMP(4, v);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    FIN_STAMP(5, v);
+#endif
     if (PUB) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (lane == 0) __hip_atomic_store(g.fin_flag + b, pub_tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1939,6 +2072,12 @@ __device__ __forceinline__ void schur_finalize_body(const Src& src, const H& hd)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int b = RUNS ? (int)blockIdx.x : (int)blockIdx.x * 4 + wave;
     if (b >= h.n_blk) return;
+#ifdef VISFS_BA_STAMPS
+    const unsigned long long t_entry = wall_clock64();
+#define FIN_STAMP_GATE() do { if (lane == 0 && b == g.stamp_wg) { g.stamps[110] = t_entry; g.stamps[111] = wall_clock64(); } } while (0)
+#else
+#define FIN_STAMP_GATE() do { } while (0)
+#endif
     // the block descriptors first, the gate after: one cold-L2 round trip instead of two at the head of the kernel
     const int4 bd = h.blk_desc[2 * b], be = h.blk_desc[2 * b + 1];
     int mode_h = 0, ls_h = 0;
@@ -1952,8 +2091,26 @@ __device__ __forceinline__ void schur_finalize_body(const Src& src, const H& hd)
         asm volatile("" :: "v"(bd.x), "v"(bd.y), "v"(bd.z), "v"(bd.w), "v"(be.x), "v"(be.y), "v"(be.z), "v"(be.w), "s"(mode_h), "s"(ls_h),
                      "s"(g.lin_stride), "s"(L0.hpp_part), "s"(L0.odo_blk), "s"(g.sch_part), "s"(g.S), "s"(g.bs), "s"(g.Minv), "s"(g.granules), "s"(g.pose_odo), "s"(g.blk_odo),
                      "s"(g.Npf), "s"(g.n_blk), "s"(g.n_runs), "s"(g.pcg_cu), "s"(g.ceres), "s"(g.Hpp), "s"(g.bp));
+        if constexpr (!RUNS && VISFS_BA_CHAINS != 0) {
+            // (the first window of the gather partials and of the odometry codes follows from the descriptor alone and their contents
+            // have been final since the previous launch: in flight across the gate, the codes first — their operands are a level
+            // further.  A gated-off launch reads these few words (beyond a range: the LM state's first word) for nothing and writes
+            // nothing; the memory clobber keeps the loads from sinking behind the gate's branch)
+            FinPre pre;
+            pre.lambda = st->lambda;
+            const int32_t* codes = (be.x == be.y) ? g.pose_odo : g.blk_odo;
+            win_load_codes(pre.code, codes, bd.z, bd.w, st);
+            win_load(pre.part, g.sch_part, 42, bd.x, bd.y, lane, lane < 42, st);
+            asm volatile("" ::: "memory");
+            if (!(mode_h & MODE_TRIAL)) return;
+            FIN_STAMP_GATE();
+            const LinSel<Src> lsel(g, ls_h);
+            schur_block<false, false, true>(g, lsel.get(), st, b, lane, bd, be, 0.0, 0u, &pre);
+            return;
+        }
         if (!(mode_h & MODE_TRIAL)) return;
     } else if (!(st->mode & MODE_TRIAL)) return;
+    FIN_STAMP_GATE();
     const LinSel<Src> lsel(g, H::present ? ls_h : st->lin_sel); const LinBuf& L = lsel.get();
     if (RUNS) {
         __shared__ double sp[4 * 42];
