@@ -162,6 +162,12 @@ PG_HD double edge_cost(const View& v, const double* __restrict__ x, int32_t k) {
     return o.rho;
 }
 
+// The derivatives of an edge's residual by the poses of its i and of its j, row-major, from the edge's evaluation.
+PG_HD void edge_jacobians(const EdgeEval& o, double Ji[9], double Jj[9]) {
+    Ji[0] = -o.c; Ji[1] = -o.s; Ji[2] = o.uy; Ji[3] = o.s; Ji[4] = -o.c; Ji[5] = -o.ux; Ji[6] = 0.0; Ji[7] = 0.0; Ji[8] = -1.0;
+    Jj[0] = o.c; Jj[1] = o.s; Jj[2] = 0.0; Jj[3] = -o.s; Jj[4] = o.c; Jj[5] = 0.0; Jj[6] = 0.0; Jj[7] = 0.0; Jj[8] = 1.0;
+}
+
 // Edge k's chi2, gradient shares and three blocks at v.x; returns its cost.
 PG_HD double edge_linearize(const View& v, int32_t k) {
     EdgeEval o;
@@ -169,8 +175,8 @@ PG_HD double edge_linearize(const View& v, int32_t k) {
     v.chi2[k] = o.chi2;
     const double* d = v.ed + (int64_t)kEdgeDoubles * k;
     const double Om[9] = { d[3], d[4], d[5], d[4], d[6], d[7], d[5], d[7], d[8] };
-    const double Ji[9] = { -o.c, -o.s, o.uy, o.s, -o.c, -o.ux, 0.0, 0.0, -1.0 };
-    const double Jj[9] = { o.c, o.s, 0.0, -o.s, o.c, 0.0, 0.0, 0.0, 1.0 };
+    double Ji[9], Jj[9];
+    edge_jacobians(o, Ji, Jj);
     double* eb = v.eb + (int64_t)27 * k;
     double* eg = v.eg + (int64_t)6 * k;
     double OJ[9], t[3];
