@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define VISFS_BA_ABI_VERSION 9
+#define VISFS_BA_ABI_VERSION 10
 
 /* ---- status codes ------------------------------------------------------- */
 /* The reference signals failure by returning an EMPTY pose map
@@ -268,19 +268,38 @@ enum {
     VISFS_BA_BUF_DX_POSE = 10,    /* [6*npf]                                    */
     VISFS_BA_BUF_DX_POINT = 11,   /* [n_points][3], 0 for fixed points          */
     VISFS_BA_BUF_POSE_TRIAL = 12, /* [n_poses][7]  state after the update       */
-    VISFS_BA_BUF_POINT_TRIAL = 13 /* [n_points][3]                              */
+    VISFS_BA_BUF_POINT_TRIAL = 13,/* [n_points][3]                              */
+    /* ABI 10, Optimizer/Framework=1 handles only: the squared Jacobi scaling (1 / (1 + sqrt(H_ii)))^2 estimated at iteration zero */
+    VISFS_BA_BUF_S2P = 14,        /* [6*npf]                                    */
+    VISFS_BA_BUF_S2L = 15         /* [n_points][3]                              */
 };
 /* number of free (non-fixed) poses of the resident graph */
 int visfs_ba_graph_free_poses(visfs_ba_handle* h);
 /* Linearise at the current estimate (K1,K2,K3,K4): fills ERR/CHI2/WEIGHT/HPL/HLL/BL/HPP/BP.
- * Returns the robust chi2 (activeRobustChi2) and the max |diag H| used for lambda init. */
+ * Returns the robust chi2 (activeRobustChi2) and the max |diag H| used for lambda init.
+ * ABI 10: the hooks also step an Optimizer/Framework=1 handle, with the launches of one unit of its solve.  There this is
+ * k_linearize + k_ceres_lin_finalize; the first call after an upload, a reset or stage_begin_phase is iteration zero (the Jacobi scaling
+ * is estimated), every later one keeps the scaling.  robust_chi2 = sum of rho (2 x cost); max_diag receives ||g||_inf; HPP has no
+ * odometry blocks. */
 int visfs_ba_stage_linearize(visfs_ba_handle* h, double* robust_chi2, double* max_diag);
 /* One damped solve at the given lambda (K5,K6,K7,K8 + chi2 at the trial state).
- * solver follows the handle's params.  Does not commit the trial state. */
+ * solver follows the handle's params.  Does not commit the trial state.
+ * ABI 10, Optimizer/Framework=1: LEVENBERG_MARQUARDT handles only (a DOGLEG handle is refused with an error text); lambda = 1 / radius;
+ * gather and solver with the per-variable damping, back-substitution, decision; trial_chi2 = sum of rho at the candidate (2 x candidate
+ * cost) and scale = 2 x model cost change as ceres_decide received them; the decision is undone. */
 int visfs_ba_stage_trial(visfs_ba_handle* h, double lambda, double* trial_chi2, double* scale,
                          int32_t* pcg_iterations, int32_t* solver_ok);
 /* Copies a stage buffer to host memory as fp64 in the layout documented above. */
 int visfs_ba_stage_fetch(visfs_ba_handle* h, int32_t which, double* dst, size_t n_doubles);
+/* ABI 10.  One trial of a DOGLEG handle (Optimizer/Framework=1, Optimizer/TrustRegion=1) at the given radius and mu: the solve at mu,
+ * k_backsub pass 1, k_dogleg_mid, pass 2 and the decision, which is then undone (the resident estimate is unchanged; the candidate is in
+ * the TRIAL buffers; DX_* hold the regularised Gauss-Newton step dn — the dogleg step itself only exists inside the (+)).  out = { A, B, dogleg step norm, model cost change, ||J v||^2, S1, S2, S3 (as k_dogleg_mid summed them),
+ * candidate cost, ||x - candidate|| (as ceres_decide received them), solver_ok, 0 }.  VISFS_BA_ERR_UNSUPPORTED with an error text on
+ * a g2o handle and on a LEVENBERG_MARQUARDT handle. */
+int visfs_ba_stage_dogleg_trial(visfs_ba_handle* h, double radius, double mu, double out[12]);
+/* ABI 10, Optimizer/Framework=1 handles: out = { ||g||_inf, ||x|| as ceres_lin_update received them from the last stage_linearize,
+ * ||x - candidate|| as ceres_decide received it from the last trial, 0 }. */
+int visfs_ba_stage_ceres_values(visfs_ba_handle* h, double out[4]);
 
 /* Stepping a solve by hand (tools/soak_diverge.py): make the last trial state the estimate (discardTop); start a phase
  * (LinearSolverPCG::init(): the carried residual is forgotten); the outlier pass of Optimizer.cpp:283-303 on the estimate
@@ -374,6 +393,8 @@ typedef struct visfs_ba_graph_info {
                                    * schur_run_landmarks consecutive landmarks (tiles staged in LDS); 0: the pair-list gather (k_schur_partial,
                                    * n_schur_chunks wavefronts) */
     int32_t schur_run_landmarks;
+    int32_t landmark_partials;    /* ABI 10: workgroups of the landmark-major passes (k_linearize, k_backsub), each leaving one partial of every sum that
+                                   * k_lin_finalize / k_ceres_lin_finalize, k_dogleg_mid and k_decide add up (DeviceGraph::n_lin_a) */
 } visfs_ba_graph_info;
 /* GRAPH layer for a batch of independent windows (BASELINE config 5): n graphs resident side by side; one optimise call runs
  * them through ONE sequence of launches (blockIdx.y = window, each window gated by its own LM state).  Needs

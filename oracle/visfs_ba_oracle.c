@@ -559,6 +559,7 @@ struct oracle_sys {
     double w_px, w_laser;
     double *ml, *mp;            /* [3 Nl], [n6] */
     double *s2l, *s2p;          /* Jacobi scaling squared, fixed at iteration zero [ceres-upstream] */
+    int stage_iter0;            /* stage stepping: the next oracle_sys_ceres_linearize is iteration zero (create, reset, begin_phase) */
     double pcg_residual;        /* LinearSolverPCG::_residual */
     double *pcg_r, *pcg_d, *pcg_q, *pcg_s, *pcg_J;
     /* outputs */
@@ -645,6 +646,7 @@ void oracle_sys_reset(oracle_sys* s) {
     memset(s->outlier, 0, s->No);
     memset(s->final_chi2, 0, (size_t)s->No * 8);
     s->pcg_residual = -1.0;
+    s->stage_iter0 = 1;
 }
 
 void oracle_sys_destroy(oracle_sys* s) {
@@ -1104,6 +1106,8 @@ int oracle_sys_fetch(oracle_sys* s, int32_t which, double* dst, size_t n) {
         case VISFS_BA_BUF_DX_POINT: src = s->dxl; m = (size_t)s->Nl * 3; break;
         case VISFS_BA_BUF_POSE_TRIAL: src = s->pose_trial; m = (size_t)s->Np * 7; break;
         case VISFS_BA_BUF_POINT_TRIAL: src = s->pt_trial; m = (size_t)s->Nl * 3; break;
+        case VISFS_BA_BUF_S2P: if (!s->ceres) return VISFS_BA_ERR_BAD_ARGUMENT; src = s->s2p; m = s->n6; break;
+        case VISFS_BA_BUF_S2L: if (!s->ceres) return VISFS_BA_ERR_BAD_ARGUMENT; src = s->s2l; m = (size_t)s->Nl * 3; break;
         default: return VISFS_BA_ERR_BAD_ARGUMENT;
     }
     if (n < m) return VISFS_BA_ERR_BAD_ARGUMENT;
@@ -1236,7 +1240,7 @@ static int mark_outliers(oracle_sys* s) {
 }
 /* stepping a solve by hand (tools/soak_diverge.py) */
 void oracle_sys_commit(oracle_sys* s) { sys_commit(s); }
-void oracle_sys_begin_phase(oracle_sys* s) { sys_begin(s); }
+void oracle_sys_begin_phase(oracle_sys* s) { sys_begin(s); s->stage_iter0 = 1; }
 int oracle_sys_mark_outliers(oracle_sys* s) {
     (void)active_robust_chi2(s, s->pose, s->pt, 1);          /* computeActiveErrors at the estimate (:270) */
     memcpy(s->final_chi2, s->chi2, (size_t)s->No * 8);
@@ -1389,7 +1393,10 @@ void oracle_dogleg_combine(double S1, double S2, double S3, double JV2, double r
     const double sHs = A * A * JV2 + 2.0 * A * B * (-S1 - mu * S3) + B * B * (-S3 - mu * S2);
     out[0] = A; out[1] = B; out[2] = norm; out[3] = -(A * S1 + B * S3 + 0.5 * sHs);
 }
-static int ceres_dogleg_step(oracle_sys* s, ceres_tr* t, double* mcc) {
+static int ceres_dogleg_step_ex(oracle_sys* s, ceres_tr* t, double* mcc, double* prod, double* dn_p, double* dn_l);
+static int ceres_dogleg_step(oracle_sys* s, ceres_tr* t, double* mcc) { return ceres_dogleg_step_ex(s, t, mcc, NULL, NULL, NULL); }
+/* prod (or NULL): { ||J v||^2, S1, S2, S3, A, B }; dn_p / dn_l (or NULL): the regularised Gauss-Newton step before it is combined */
+static int ceres_dogleg_step_ex(oracle_sys* s, ceres_tr* t, double* mcc, double* prod, double* dn_p, double* dn_l) {
     int pit = 0;
     if (!schur_solve(s, t->mu, &pit) || !step_is_finite(s)) return 0;     /* (H + mu M) dn = b: s->dxp, s->dxl = dn */
     const int n6 = s->n6, Nl = s->Nl;
@@ -1429,6 +1436,9 @@ static int ceres_dogleg_step(oracle_sys* s, ceres_tr* t, double* mcc) {
     const double A = out[0], B = out[1];
     t->dogleg_step_norm = out[2];
     *mcc = out[3];
+    if (prod) { prod[0] = JV2; prod[1] = S1; prod[2] = S2; prod[3] = S3; prod[4] = A; prod[5] = B; }
+    if (dn_p) memcpy(dn_p, s->dxp, (size_t)n6 * 8);
+    if (dn_l) memcpy(dn_l, s->dxl, (size_t)Nl * 24);
     if (getenv("VISFS_ORACLE_TRACE")) fprintf(stderr, "[oracle dogleg] it %d radius %.6g mu %.3g |gn| %.6g |cauchy| %.6g -> A %.6g B %.6g mcc %.6g\n", t->iter, t->radius, t->mu, sqrt(S2), sqrt(S1) * S1 / JV2, A, B, *mcc);
     for (int i = 0; i < n6; ++i) s->dxp[i] = A * (-s->bp[i] / s->mp[i]) + B * s->dxp[i];
     for (int l = 0; l < Nl; ++l) {
@@ -1463,6 +1473,20 @@ int oracle_sys_dogleg_trial(oracle_sys* s, double radius, double mu, double out[
     apply_update(s);
     out[0] = mcc; out[1] = t.dogleg_step_norm; out[2] = 0.5 * active_robust_chi2(s, s->pose_trial, s->pt_trial, 0);
     return 1;
+}
+
+/* :529-540: every stereo residual block (both-constant ones included), error . (pixelInfo error) > delta, unsquared */
+static int ceres_mark(oracle_sys* s) {
+    const double iv = 1.0 / s->prm.pixel_variance;
+    int n_out = 0;
+    for (int k = 0; k < s->No; ++k) {
+        double e[3];
+        oracle_stereo_edge(s->pose + 7 * s->obs_pose[k], s->pt + 3 * s->obs_pt[k], s->obs_uvr + 3 * k, s->intr, e, NULL, NULL);
+        const double c = e[0] * (iv * e[0]) + e[1] * (iv * e[1]) + e[2] * (iv * e[2]);
+        s->final_chi2[k] = c;
+        if (s->prm.robust_kernel_delta > 0.0 && c > s->prm.robust_kernel_delta) { s->outlier[k] = 1; ++n_out; }
+    }
+    return n_out;
 }
 
 static int ceres_optimize(oracle_sys* s, visfs_ba_stats* st) {
@@ -1520,18 +1544,65 @@ static int ceres_optimize(oracle_sys* s, visfs_ba_stats* st) {
     /* :529-540: every stereo residual block (both-constant ones included), error . (pixelInfo error) > delta, unsquared */
     const double chi_final = active_robust_chi2(s, s->pose, s->pt, 0);
     st->chi2_phase1 = st->chi2_final = chi_final;
-    const double iv = 1.0 / s->prm.pixel_variance;
-    int n_out = 0;
-    for (int k = 0; k < s->No; ++k) {
-        double e[3];
-        oracle_stereo_edge(s->pose + 7 * s->obs_pose[k], s->pt + 3 * s->obs_pt[k], s->obs_uvr + 3 * k, s->intr, e, NULL, NULL);
-        const double c = e[0] * (iv * e[0]) + e[1] * (iv * e[1]) + e[2] * (iv * e[2]);
-        s->final_chi2[k] = c;
-        if (s->prm.robust_kernel_delta > 0.0 && c > s->prm.robust_kernel_delta) { s->outlier[k] = 1; ++n_out; }
-    }
-    st->n_outliers = n_out;
+    st->n_outliers = ceres_mark(s);
     return VISFS_BA_OK;
 }
+
+/* ---- stage stepping of an Optimizer/Framework=1 system, as the device's stage hooks step theirs (tests only; ceres_optimize above does
+ * not come through here) */
+/* out = { sum of rho (2 x cost), ||g||_inf, ||x|| }.  The Jacobi scaling is estimated at iteration zero only: the first call after
+ * create, reset or begin_phase; later calls keep it, across commits. */
+void oracle_sys_ceres_linearize(oracle_sys* s, double out[3]) {
+    double chi = 0.0, md = 0.0;
+    oracle_sys_linearize(s, &chi, &md);
+    if (s->ceres && s->stage_iter0) { ceres_estimate_scale(s); s->stage_iter0 = 0; }
+    out[0] = chi; out[1] = ceres_grad_max(s); out[2] = sqrt(ceres_x_norm2(s, s->pose, s->pt));
+}
+/* LEVENBERG_MARQUARDT: (H + lambda diag(m)) dx = b with lambda = 1 / radius, Plus, the candidate's cost.  out = { sum of rho at the
+ * candidate, 2 x model cost change, ||x - candidate|| }.  Returns 0 when the factorisation fails. */
+int oracle_sys_ceres_trial(oracle_sys* s, double lambda, double out[3]) {
+    if (!s->ceres) return 0;
+    const int saved_solver = s->prm.solver;
+    s->prm.solver = 0;
+    ceres_multipliers(s);
+    int pit = 0;
+    const int ok = schur_solve(s, lambda, &pit) && step_is_finite(s);
+    s->prm.solver = saved_solver;
+    if (!ok) return 0;
+    apply_update(s);
+    out[0] = active_robust_chi2(s, s->pose_trial, s->pt_trial, 0);
+    out[1] = compute_scale(s, lambda);
+    out[2] = sqrt(ceres_step_norm2(s));
+    return 1;
+}
+/* DOGLEG: out as visfs_ba_stage_dogleg_trial's — { A, B, dogleg step norm, model cost change, ||J v||^2, S1, S2, S3, candidate cost,
+ * ||x - candidate||, ok, 0 }.  The DX buffers are left holding the regularised Gauss-Newton step dn, as the device's are. */
+int oracle_sys_ceres_dogleg_trial(oracle_sys* s, double radius, double mu, double out[12]) {
+    if (!s->ceres) return 0;
+    const int saved_solver = s->prm.solver;
+    s->prm.solver = 0;
+    ceres_multipliers(s);
+    ceres_tr t;
+    ceres_tr_init(&t, 0.0, 0.0);
+    t.dogleg = 1; t.radius = radius; t.mu = mu; t.iter = 1;
+    double mcc = 0.0, prod[6];
+    double* dn_p = xcalloc(s->n6, 8); double* dn_l = xcalloc((size_t)s->Nl * 3, 8);
+    const int ok = ceres_dogleg_step_ex(s, &t, &mcc, prod, dn_p, dn_l);
+    s->prm.solver = saved_solver;
+    memset(out, 0, 12 * 8);
+    if (ok) {
+        apply_update(s);
+        out[0] = prod[4]; out[1] = prod[5]; out[2] = t.dogleg_step_norm; out[3] = mcc;
+        out[4] = prod[0]; out[5] = prod[1]; out[6] = prod[2]; out[7] = prod[3];
+        out[8] = 0.5 * active_robust_chi2(s, s->pose_trial, s->pt_trial, 0);
+        out[9] = sqrt(ceres_step_norm2(s));
+        out[10] = 1.0;
+        memcpy(s->dxp, dn_p, (size_t)s->n6 * 8); memcpy(s->dxl, dn_l, (size_t)s->Nl * 24);
+    }
+    free(dn_p); free(dn_l);
+    return ok;
+}
+int oracle_sys_ceres_mark_outliers(oracle_sys* s) { return s->ceres ? ceres_mark(s) : 0; }
 
 /* The trust-region schedule on SCRIPTED outcomes: iteration t's solve reports (ok[t], model_cost_change[t], cand_cost[t],
  * step_norm[t]); an accepted step then reports (grad_max[t], x_norm[t]).  Fills trace_lambda (radius after each iteration),

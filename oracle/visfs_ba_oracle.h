@@ -71,6 +71,15 @@ void oracle_sys_trial(oracle_sys* s, double lambda, double* trial_chi2, double* 
 /* Optimizer/Framework=1 systems: one DOGLEG step (radius, mu) from the current linearisation; step -> DX buffers, trial state -> TRIAL
  * buffers, out = { model cost change, scaled step norm, trial cost }.  Returns 0 when the factorisation fails. */
 int oracle_sys_dogleg_trial(oracle_sys* s, double radius, double mu, double out[3]);
+/* Stage stepping of an Optimizer/Framework=1 system beside the device's stage hooks (include/visfs_ba.h, ABI 10):
+ * ceres_linearize: out = { sum of rho, ||g||_inf, ||x|| }; the Jacobi scaling is estimated by the first call after create, reset or
+ * begin_phase and kept by every later one.  ceres_trial (LEVENBERG_MARQUARDT, lambda = 1 / radius): out = { sum of rho at the candidate,
+ * 2 x model cost change, ||x - candidate|| }.  ceres_dogleg_trial: out as visfs_ba_stage_dogleg_trial's; the DX buffers keep the
+ * regularised Gauss-Newton step.  Both return 0 when the factorisation fails.  ceres_mark_outliers: Optimizer.cpp:529-540. */
+void oracle_sys_ceres_linearize(oracle_sys* s, double out[3]);
+int oracle_sys_ceres_trial(oracle_sys* s, double lambda, double out[3]);
+int oracle_sys_ceres_dogleg_trial(oracle_sys* s, double radius, double mu, double out[12]);
+int oracle_sys_ceres_mark_outliers(oracle_sys* s);
 /* Same buffer ids and layouts as visfs_ba_stage_fetch. */
 int oracle_sys_fetch(oracle_sys* s, int32_t which, double* dst, size_t n_doubles);
 /* Both phases + outlier marking (Optimizer.cpp:261-318). Returns status; seconds = wall time of that region. */

@@ -79,6 +79,14 @@ def load(omp=False, v4=False):
     lib.oracle_dogleg_combine.restype = None
     lib.oracle_sys_dogleg_trial.argtypes = [C.c_void_p, C.c_double, C.c_double, _pd]
     lib.oracle_sys_dogleg_trial.restype = C.c_int
+    lib.oracle_sys_ceres_linearize.argtypes = [C.c_void_p, _pd]
+    lib.oracle_sys_ceres_linearize.restype = None
+    lib.oracle_sys_ceres_trial.argtypes = [C.c_void_p, C.c_double, _pd]
+    lib.oracle_sys_ceres_trial.restype = C.c_int
+    lib.oracle_sys_ceres_dogleg_trial.argtypes = [C.c_void_p, C.c_double, C.c_double, _pd]
+    lib.oracle_sys_ceres_dogleg_trial.restype = C.c_int
+    lib.oracle_sys_ceres_mark_outliers.argtypes = [C.c_void_p]
+    lib.oracle_sys_ceres_mark_outliers.restype = C.c_int
     lib.oracle_solve_window.argtypes = [C.POINTER(abi.Params), C.POINTER(abi.Window), C.POINTER(abi.Result), C.c_int]
     lib.oracle_solve_window.restype = C.c_int
     return lib
@@ -119,6 +127,23 @@ class OracleSystem:
         ok = self.lib.oracle_sys_dogleg_trial(self.h, radius, mu, out.ctypes.data_as(C.POINTER(C.c_double)))
         return ok, out[0], out[1], out[2]
 
+    # ---- Optimizer/Framework=1 systems stepped as the device's stage hooks step theirs (same surface as backend.Solver)
+    def ceres_linearize(self):
+        out = np.zeros(3)
+        self.lib.oracle_sys_ceres_linearize(self.h, _p(out))
+        return float(out[0]), float(out[1]), float(out[2])
+
+    def ceres_trial(self, lam):
+        out = np.zeros(3)
+        ok = self.lib.oracle_sys_ceres_trial(self.h, lam, _p(out))
+        return float(out[0]), float(out[1]), float(out[2]), int(ok)
+
+    def dogleg_stage(self, radius, mu):
+        out = np.zeros(12)
+        self.lib.oracle_sys_ceres_dogleg_trial(self.h, radius, mu, _p(out))
+        keys = ("A", "B", "norm", "mcc", "jv2", "s1", "s2", "s3", "cand_cost", "step_norm", "ok")
+        return dict(zip(keys, (float(v) for v in out[:11])))
+
     def commit(self):
         self.lib.oracle_sys_commit(self.h)
 
@@ -126,6 +151,8 @@ class OracleSystem:
         self.lib.oracle_sys_begin_phase(self.h)
 
     def mark_outliers(self):
+        if self.params.framework == 1:
+            return self.lib.oracle_sys_ceres_mark_outliers(self.h)
         return self.lib.oracle_sys_mark_outliers(self.h)
 
     def fetch(self, which):
@@ -135,7 +162,8 @@ class OracleSystem:
                 abi.BUF_HPL: g.n_obs * 18, abi.BUF_HLL: g.n_points * 6, abi.BUF_BL: g.n_points * 3,
                 abi.BUF_HPP: n6 * n6, abi.BUF_BP: n6, abi.BUF_S: n6 * n6, abi.BUF_BS: n6,
                 abi.BUF_DX_POSE: n6, abi.BUF_DX_POINT: g.n_points * 3,
-                abi.BUF_POSE_TRIAL: g.n_poses * 7, abi.BUF_POINT_TRIAL: g.n_points * 3}[which]
+                abi.BUF_POSE_TRIAL: g.n_poses * 7, abi.BUF_POINT_TRIAL: g.n_points * 3,
+                abi.BUF_S2P: n6, abi.BUF_S2L: g.n_points * 3}[which]
         out = np.zeros(max(size, 1))
         rc = self.lib.oracle_sys_fetch(self.h, which, _p(out), size)
         assert rc == 0

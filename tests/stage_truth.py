@@ -30,6 +30,8 @@ contributions come from the shared inputs.
     pose_fixed [Np] bool, point_fixed [Nl] bool, obs_point [No], obs_pose [No], obs_uvr [No][3], odo_from [Ne], odo_to [Ne], odo_tq [Ne][7],
     intr (fx, fy, cx, cy, bf), w_px, w_odo, w_laser (the information values AS THE PROGRAMS HOLD THEM: fp64 1/variance), delta,
     laser: None or dict(pose, xyz [Nz][3], Tcr [12], resolution, max_x, max_y, cost [num_y][num_x] float32)
+    ceres (optional, default False): the graph is read as Optimizer/Framework=1 builds its problem (Optimizer.cpp:366-593) — see the
+    section at the end of the module, which adds the stages of Ceres' trust-region minimizer.
 """
 import numpy as np
 
@@ -213,6 +215,30 @@ def huber(chi2, delta):
     return np.where(inl, chi2, 2 * s * d - d * d), np.where(inl, LD(1), d / s)
 
 
+def huber_loss(s, a):
+    """ceres::HuberLoss(a)::Evaluate on s = ||residual||^2 (Ceres' documented loss: rho(s) = s for s <= a^2, 2 a sqrt(s) - a^2 beyond) and
+    what the Corrector makes of it: rho'' <= 0, so residual and Jacobian are scaled by sqrt(rho') and the block enters J^T J with rho'.
+    The Ceres branch attaches the loss whatever delta is (Optimizer.cpp:370, :481).  Returns (rho, rho')."""
+    s = _ld(s)
+    a = LD(a)
+    out = s > a * a
+    r = np.sqrt(np.where(out, s, LD(1)))
+    return np.where(out, 2 * a * r - a * a, s), np.where(out, np.maximum(a / r, LD(np.finfo(np.float64).tiny)), LD(1))
+
+
+def weights_of(graph):
+    """(pixel weight, laser weight, Ceres branch?) as the quadratic forms carry them.  g2o: chi2 = e^T Omega e, Omega = I / variance.
+    Ceres: the residual is info * e (StereoObservationFactor.cpp:24-25, OccupiedSpace2dFactor.cpp:43), so its squared norm — and J^T J
+    through the Jacobians of :43, :73 — carries the information value twice."""
+    ceres = bool(graph.get("ceres", False))
+    w_px, w_la = LD(graph["w_px"]), LD(graph["w_laser"])
+    return (w_px * w_px, w_la * w_la, True) if ceres else (w_px, w_la, False)
+
+
+def loss_of(graph, chi2):
+    return huber_loss(chi2, graph["delta"]) if graph.get("ceres", False) else huber(chi2, graph["delta"])
+
+
 # ----------------------------------------------------------------- the laser edge
 class _Jet:
     """A value with its six partials (ceres::Jet restricted to the six pose directions), over n range points."""
@@ -312,11 +338,14 @@ def _laser_functor(pose, P, Tcr, grid, exact=False):
     return out[0], out[1], margin
 
 
-def laser_edge(tq, Tcr, P, grid, exact=False, alias_w=False):
+def laser_edge(tq, Tcr, P, grid, exact=False, alias_w=False, own_w=False):
     """EdgeOccupiedObservation over n range points of one pose: (e [n], J [n][6], margin of _laser_functor).  computeError reads the pose's seven numbers; the
     Jacobian is the reference's: AutoDifferentiate over StaticParameterDims<6, 3> gives the pose block SIX jets, so the functor's pose[6]
     reads the next jet, the range point's x — q.w := P.x, no partial, differentiated with respect to (t, qx, qy, qz).
-    alias_w: e too is taken with q.w := P.x (the function J differentiates; the finite-difference test)."""
+    alias_w: e too is taken with q.w := P.x (the function J differentiates; the finite-difference test).
+    own_w: the Ceres factor instead (OccupiedSpace2dFactor.cpp:19-47, :93): AutoDiffCostFunction<..., DYNAMIC, 7> differentiates the functor
+    over the pose's seven raw parameters and PoseLocalParameterization::ComputeJacobian = [I6; 0] (LocalParameterization.cpp:25-31) drops
+    the q.w column: the partials with respect to (t, qx, qy, qz) at the pose's OWN q.w, no aliasing."""
     tq = _ld(tq).reshape(7); P = _ld(P).reshape(-1, 3)
     n = len(P)
     ones = np.ones(n, dtype=LD)
@@ -326,7 +355,7 @@ def laser_edge(tq, Tcr, P, grid, exact=False, alias_w=False):
     for i in range(6):
         j = _Jet(ones * tq[i]); j.v[:, i] = 1
         pose.append(j)
-    pose.append(_Jet(P[:, 0].copy()))
+    pose.append(_Jet(ones * tq[6]) if own_w else _Jet(P[:, 0].copy()))
     r, c, margin_j = _laser_functor(pose, P, Tcr, grid, exact)
     _, dfdr, dfdc = bicubic(grid, r.a, c.a)
     return e, dfdr[:, None] * r.v + dfdc[:, None] * c.v, min(margin, margin_j)
@@ -396,6 +425,8 @@ def _odo_terms(graph, pose):
     fixed = np.asarray(graph["pose_fixed"]).astype(bool)
     i = np.asarray(graph["odo_from"], dtype=np.int64); j = np.asarray(graph["odo_to"], dtype=np.int64)
     keep = ~(fixed[i] & fixed[j]) if len(i) else np.zeros(0, bool)
+    if graph.get("ceres", False):                                                     # Optimizer.cpp:415-430: a link between two poses of the window is "TODO",
+        keep = np.zeros(len(i), bool)                                                 # any other finds no index: the Ceres problem has no odometry factor
     i, j = i[keep], j[keep]
     e, Ji, Jj = odo_edge(_ld(pose)[i], _ld(pose)[j], _ld(graph["odo_tq"]).reshape(-1, 7)[keep])
     return i, j, e, Ji, Jj
@@ -405,7 +436,7 @@ def _laser_terms(graph, pose):
     la = graph.get("laser")
     if la is None or len(la["xyz"]) == 0 or bool(np.asarray(graph["pose_fixed"])[la["pose"]]):
         return None
-    e, J, margin = laser_edge(_ld(pose)[la["pose"]], la["Tcr"], la["xyz"], la)
+    e, J, margin = laser_edge(_ld(pose)[la["pose"]], la["Tcr"], la["xyz"], la, own_w=bool(graph.get("ceres", False)))
     return la["pose"], e, J, margin
 
 
@@ -416,7 +447,7 @@ def other_chi2(graph, pose):
     n = len(e)
     la = _laser_terms(graph, pose)
     if la is not None:
-        total = total + (la[1] * (LD(graph["w_laser"]) * la[1])).sum()
+        total = total + (la[1] * (weights_of(graph)[1] * la[1])).sum()
         n += len(la[1])
     return total, n, (la[3] if la is not None else INF)
 
@@ -429,7 +460,7 @@ def judge_linearize(graph, pose, pt, level, side, chi2_total, max_diag):
     pose_fixed = np.asarray(graph["pose_fixed"]).astype(bool); point_fixed = np.asarray(graph["point_fixed"]).astype(bool)
     Np, Nl, No = len(pose_fixed), len(point_fixed), len(op)
     pidx = pose_index(graph); npf = int((~pose_fixed).sum()); n6 = 6 * npf
-    w_px = LD(graph["w_px"]); delta = graph["delta"]
+    w_px, w_la_q, ceres = weights_of(graph); delta = graph["delta"]
     active = active_edges(graph, level)
     out = {}
 
@@ -447,7 +478,7 @@ def judge_linearize(graph, pose, pt, level, side, chi2_total, max_diag):
     c_t = np.where(active, (e_own * (w_px * e_own)).sum(axis=1), LD(0))
     put("chi2", side["chi2"], c_t, np.abs(c_t), 0)
     c_own = _ld(side["chi2"])
-    rho, rho1 = huber(c_own, delta)
+    rho, rho1 = loss_of(graph, c_own)
     w_t = np.where(active, rho1, LD(0))
     put("weight", side["weight"], w_t, np.abs(w_t), 0)
 
@@ -494,7 +525,7 @@ def judge_linearize(graph, pose, pt, level, side, chi2_total, max_diag):
                 off_mag[key] = off_mag.get(key, 0) + np.abs(A).T @ (w_odo * np.abs(B))
     la = _laser_terms(graph, pose)
     if la is not None:
-        a = pidx[la[0]]; w_la = LD(graph["w_laser"]); J = la[2]; el = la[1]
+        a = pidx[la[0]]; w_la = w_la_q; J = la[2]; el = la[1]
         D[a] += np.einsum("nr,nc->rc", J, w_la * J); Dmag[a] += np.einsum("nr,nc->rc", np.abs(J), w_la * np.abs(J))
         bp[a] -= (J * (w_la * el)[:, None]).sum(axis=0); bp_mag[a] += (np.abs(J) * (w_la * np.abs(el))[:, None]).sum(axis=0)
         cnt[a] += len(el); extra[a] = True
@@ -518,7 +549,14 @@ def judge_linearize(graph, pose, pt, level, side, chi2_total, max_diag):
     if Nl:
         diag.append(np.abs(np.asarray(side["Hll"]).reshape(Nl, 6)[~point_fixed][:, [0, 3, 5]]).ravel())
     md = max([float(d.max()) for d in diag if d.size] + [0.0])
-    out["max_diag"] = dict(e=0.0 if md == max_diag else INF, n=0, block=-1)
+    if ceres:
+        # (no lambda to initialise: the Ceres branch reports ||g||_inf there — the maximum over the side's own b_p and the b_l of its free
+        #  landmarks, bit for bit)
+        gb = [np.abs(np.asarray(side["bp"]).ravel())] + ([np.abs(np.asarray(side["bl"]).reshape(Nl, 3)[~point_fixed]).ravel()] if Nl else [])
+        md = max([float(d.max()) for d in gb if d.size] + [0.0])
+        out["grad_max"] = dict(e=0.0 if md == max_diag else INF, n=0, block=-1)
+    else:
+        out["max_diag"] = dict(e=0.0 if md == max_diag else INF, n=0, block=-1)
     return out, closest + (margin,)
 
 
@@ -529,7 +567,8 @@ def sym3_inverse(h6, lam):
     h = _ld(h6).reshape(-1, 6)
     n = len(h)
     A = np.empty((n, 3, 3), dtype=LD)
-    A[:, 0, 0] = h[:, 0] + LD(lam); A[:, 1, 1] = h[:, 3] + LD(lam); A[:, 2, 2] = h[:, 5] + LD(lam)
+    lam3 = np.broadcast_to(_ld(lam).reshape(-1, 3) if np.ndim(lam) else LD(lam), (n, 3))     # (a scalar, or the damping of every diagonal entry [n][3])
+    A[:, 0, 0] = h[:, 0] + lam3[:, 0]; A[:, 1, 1] = h[:, 3] + lam3[:, 1]; A[:, 2, 2] = h[:, 5] + lam3[:, 2]
     A[:, 0, 1] = A[:, 1, 0] = h[:, 1]; A[:, 0, 2] = A[:, 2, 0] = h[:, 2]; A[:, 1, 2] = A[:, 2, 1] = h[:, 4]
     if n == 0:
         return A, 0.0
@@ -561,7 +600,8 @@ def cond_sym3(h6, lam):
     """2-norm condition numbers of the blocks H_ll + lam I (fp64 eigenvalues: a figure for the log and the ill-conditioned bound)."""
     h = np.asarray(h6, dtype=np.float64).reshape(-1, 6)
     A = np.empty((len(h), 3, 3))
-    A[:, 0, 0] = h[:, 0] + lam; A[:, 1, 1] = h[:, 3] + lam; A[:, 2, 2] = h[:, 5] + lam
+    lam = np.broadcast_to(np.asarray(lam, dtype=np.float64).reshape(-1, 3) if np.ndim(lam) else float(lam), (len(h), 3))
+    A[:, 0, 0] = h[:, 0] + lam[:, 0]; A[:, 1, 1] = h[:, 3] + lam[:, 1]; A[:, 2, 2] = h[:, 5] + lam[:, 2]
     A[:, 0, 1] = A[:, 1, 0] = h[:, 1]; A[:, 0, 2] = A[:, 2, 0] = h[:, 2]; A[:, 1, 2] = A[:, 2, 1] = h[:, 4]
     if len(h) == 0:
         return np.zeros(0)
@@ -569,11 +609,12 @@ def cond_sym3(h6, lam):
     return ev.max(axis=1) / np.maximum(ev.min(axis=1), 1e-300)
 
 
-def schur_truth(graph, lam, Hpp, bp, Hpl, Hll, bl, weight, drop_term=None):
+def schur_truth(graph, lam, Hpp, bp, Hpl, Hll, bl, weight, drop_term=None, mp=None, ml=None):
     """S = H_pp + lam I - sum_l B_l (H_ll + lam I)^-1 B_l^T and b_s = b_p - sum_l B_l (H_ll + lam I)^-1 b_l from one side's OWN buffers,
     block-sparse: {(i, j), i <= j: 6x6} with sum|terms| per block (never a dense long-double n6 x n6 array).  An edge enters iff its
     weight is non-zero and its pose and landmark are free; a free pose whose H_pp diagonal is all zero is pinned (unit diagonal).
     drop_term: the index of one co-observation term to leave out (the tests show that the checks notice).
+    mp [npf][6], ml [Nl][3] (the Ceres branch): the damping of variable i is lam * m_i instead of lam (H + lam diag(m)).
     Returns dict(keys [nk][2], S [nk][6][6], S_mag, n_S, bs [npf][6], bs_mag, n_bs, D, used [Nl] bool, residual)."""
     op = np.asarray(graph["obs_pose"], dtype=np.int64); ol = np.asarray(graph["obs_point"], dtype=np.int64)
     pose_fixed = np.asarray(graph["pose_fixed"]).astype(bool); point_fixed = np.asarray(graph["point_fixed"]).astype(bool)
@@ -584,7 +625,7 @@ def schur_truth(graph, lam, Hpp, bp, Hpl, Hll, bl, weight, drop_term=None):
     used = np.zeros(Nl, bool)
     used[ol[(weight != 0) & ~point_fixed[ol]]] = True                                 # free landmarks with an active edge
     D = np.zeros((Nl, 3, 3), dtype=LD)
-    D[used], residual = sym3_inverse(_ld(Hll).reshape(Nl, 6)[used], lam)
+    D[used], residual = sym3_inverse(_ld(Hll).reshape(Nl, 6)[used], lam if ml is None else lam_ld * _ld(ml).reshape(Nl, 3)[used])
     el = np.nonzero((weight != 0) & ~point_fixed[ol] & ~pose_fixed[op])[0]
     el = el[np.lexsort((pidx[op[el]], ol[el]))]                                       # by landmark, poses ascending inside
     lm = ol[el]; pi = pidx[op[el]]
@@ -624,7 +665,8 @@ def schur_truth(graph, lam, Hpp, bp, Hpl, Hll, bl, weight, drop_term=None):
     dg = np.nonzero(ki == kj)[0]
     r6 = np.arange(6)
     pinned = (np.abs(S[dg][:, r6, r6]).max(axis=1) == 0) if len(dg) else np.zeros(0, bool)
-    S[dg[:, None], r6, r6] += lam_ld; S_mag[dg[:, None], r6, r6] += lam_ld
+    dmp = lam_ld if mp is None else lam_ld * _ld(mp).reshape(npf, 6)[ki[dg]]
+    S[dg[:, None], r6, r6] += dmp; S_mag[dg[:, None], r6, r6] += dmp
     for k in dg[pinned]:
         S[k, r6, r6] = 1; S_mag[k, r6, r6] = 1
     np.subtract.at(S, inv, pt_); np.add.at(S_mag, inv, pg)
@@ -658,9 +700,11 @@ def compare_S(S_side, npf, T):
     return e, float(e_mag.max()), k, cancel
 
 
-def judge_trial(graph, pose, pt, level, lam, side, trial_chi2, scale):
+def judge_trial(graph, pose, pt, level, lam, side, trial_chi2, scale, mp=None, ml=None, dl_AB=None):
     """One side's damped trial against the truth of its own inputs.  pose, pt: its committed state; side: its own Hpp, bp, Hpl, Hll, bl,
     weight (of the last linearisation) and S, bs, dx_pose, dx_point, pose_trial, point_trial; trial_chi2, scale: what trial() returned.
+    mp, ml: the Ceres branch's multipliers (schur_truth).  dl_AB = (A, B): a dogleg trial — dx_pose / dx_point hold the regularised
+    Gauss-Newton step dn and the trial state is x (+) (A v + B dn) with v = -b / m; no scale.
     Returns ({stage: dict(e, n, block)}, the laser coordinates' margin at the trial state)."""
     op = np.asarray(graph["obs_pose"], dtype=np.int64); ol = np.asarray(graph["obs_point"], dtype=np.int64)
     pose_fixed = np.asarray(graph["pose_fixed"]).astype(bool); point_fixed = np.asarray(graph["point_fixed"]).astype(bool)
@@ -672,9 +716,9 @@ def judge_trial(graph, pose, pt, level, lam, side, trial_chi2, scale):
         e, k = block_error(x, truth, norm)
         out[stage] = dict(e=e, n=int(n), block=k)
 
-    T = schur_truth(graph, lam, side["Hpp"], side["bp"], side["Hpl"], side["Hll"], side["bl"], side["weight"])
+    T = schur_truth(graph, lam, side["Hpp"], side["bp"], side["Hpl"], side["Hll"], side["bl"], side["weight"], mp=mp, ml=ml)
     e_own, e_mag, k, cancel = compare_S(side["S"], npf, T)
-    cond = cond_sym3(np.asarray(side["Hll"]).reshape(Nl, 6)[T["used"]], lam)
+    cond = cond_sym3(np.asarray(side["Hll"]).reshape(Nl, 6)[T["used"]], lam if ml is None else lam * np.asarray(ml, dtype=np.float64).reshape(Nl, 3)[T["used"]])
     out["S"] = dict(e=e_own, n=T["n_S"], block=k, e_mag=e_mag, cancel=cancel, cond=float(cond.max()) if cond.size else 1.0, residual=T["residual"])
     put("bs", np.asarray(side["bs"]).reshape(npf, 6), T["bs"], T["bs_mag"].max(axis=1) if npf else np.zeros(0), T["n_bs"])
 
@@ -689,27 +733,35 @@ def judge_trial(graph, pose, pt, level, lam, side, trial_chi2, scale):
     put("dx_point", np.asarray(side["dx_point"]).reshape(Nl, 3), xl, xl_mag.max(axis=1) if Nl else np.zeros(0), 3 + _count_max(lm, Nl))
 
     # the trial state from the side's own increments
+    dl = _ld(side["dx_point"]).reshape(Nl, 3)
+    xs = xp
+    if dl_AB is not None:                                                             # the dogleg step from the side's own A, B, dn, b and m
+        A_, B_ = LD(dl_AB[0]), LD(dl_AB[1])
+        xs = A_ * (-_ld(side["bp"]).reshape(npf, 6) / _ld(mp).reshape(npf, 6)) + B_ * xp
+        dl = np.where(T["used"][:, None], A_ * (-_ld(side["bl"]).reshape(Nl, 3) / _ld(ml).reshape(Nl, 3)) + B_ * dl, LD(0))
     dxp = np.zeros((Np, 6), dtype=LD)
-    dxp[~pose_fixed] = xp
+    dxp[~pose_fixed] = xs
     pose_t = np.where(pose_fixed[:, None], _ld(pose), pose_update(pose, dxp))
     got = np.asarray(side["pose_trial"]).reshape(Np, 7)
     put("pose_trial", _split_tq(got), _split_tq(pose_t), _own(_split_tq(pose_t)), 0)
-    dl = _ld(side["dx_point"]).reshape(Nl, 3)
     pt_t = np.where(point_fixed[:, None], _ld(pt), _ld(pt) + dl)
     put("point_trial", np.asarray(side["point_trial"]).reshape(Nl, 3), pt_t, _own(pt_t), 0)
 
     # the trial chi2 at the side's OWN trial state, and computeScale from its own dx
     active = active_edges(graph, level)
     e, _, _, _ = stereo_edge(_ld(got)[op], _ld(side["point_trial"]).reshape(Nl, 3)[ol], graph["obs_uvr"], graph["intr"])
-    chi = (e * (LD(graph["w_px"]) * e)).sum(axis=1)
-    rho, _ = huber(chi, graph["delta"])
+    chi = (e * (weights_of(graph)[0] * e)).sum(axis=1)
+    rho, _ = loss_of(graph, chi)
     other, n_other, margin = other_chi2(graph, got)
     total = np.where(active, rho, LD(0)).sum() + other
     put("trial_chi2", np.array([trial_chi2]), _ld([total]), np.abs(_ld([total])), int(active.sum()) + n_other)
+    if dl_AB is not None:
+        return out, margin
     bpv = _ld(side["bp"]).reshape(npf, 6); blv = _ld(side["bl"]).reshape(Nl, 3)[~point_fixed]; dlf = dl[~point_fixed]
-    lam_ld = LD(lam)
-    sc = (xp * (lam_ld * xp + bpv)).sum() + (dlf * (lam_ld * dlf + blv)).sum()
-    sc_mag = (np.abs(xp) * (lam_ld * np.abs(xp) + np.abs(bpv))).sum() + (np.abs(dlf) * (lam_ld * np.abs(dlf) + np.abs(blv))).sum()
+    lam_p = LD(lam) if mp is None else LD(lam) * _ld(mp).reshape(npf, 6)
+    lam_l = LD(lam) if ml is None else LD(lam) * _ld(ml).reshape(Nl, 3)[~point_fixed]
+    sc = (xp * (lam_p * xp + bpv)).sum() + (dlf * (lam_l * dlf + blv)).sum()
+    sc_mag = (np.abs(xp) * (lam_p * np.abs(xp) + np.abs(bpv))).sum() + (np.abs(dlf) * (lam_l * np.abs(dlf) + np.abs(blv))).sum()
     put("scale", np.array([scale]), _ld([sc]), _ld([sc_mag]), xp.size + dlf.size)
     return out, margin
 
@@ -724,3 +776,224 @@ def _split_tq(tq):
 LIN_STAGES = ("err", "chi2", "weight", "Hpl", "Hll", "bl", "Hpp", "bp", "chi2_total", "max_diag")
 TRIAL_STAGES = ("S", "bs", "dx_point", "pose_trial", "point_trial", "trial_chi2", "scale")
 STAGES = LIN_STAGES + TRIAL_STAGES
+
+
+# ===================================================================== Optimizer/Framework=1: the Ceres branch (Optimizer.cpp:366-593)
+# A graph dict with ceres=True is read by the functions above as that branch builds its problem: the residual is info * e for stereo and
+# laser (the squared norm carries the information value twice), HuberLoss is attached whatever delta is, no odometry factor, the laser
+# Jacobian over the raw parameters at the pose's own q.w; there are no edge levels.  Below: what Ceres' trust-region minimizer adds, from
+# its documented semantics (Solver::Options defaults: jacobi_scaling, min / max_lm_diagonal 1e-6 / 1e32, TRADITIONAL_DOGLEG).
+#
+#     s2p, s2l            the side's own H_pp / H_ll diagonals at iteration zero       / own; later linearisations: the kept values, bit for bit
+#     grad_max            the side's own b_p, b_l                                      bit for bit
+#     x_norm              the shared committed state                                   / own, n = its numbers
+#     S, b_s, dx_point    as above, damped with lambda m_i, m from the side's own s^2 and diagonal
+#     jv2                 the side's own b, weight, m and the truth's Jacobians       / own (a sum of squares), n = residual blocks
+#     s1, s2, s3          the side's own b, dn, m                                      / sum|terms|, n = variables
+#     A, B, norm, mcc     the side's own four sums                                     A, B, norm / own; mcc / sum|terms|
+#     pose_trial, point_trial   the side's own A, B, dn, b, m (LM: its own dx) and the committed state
+#     trial_chi2 (2 x candidate cost)   the side's own trial state                     / sum|terms|, n = residual blocks
+#     step_norm           the side's own trial state and the committed state           / own, n = its numbers
+CLAMP_LO, CLAMP_HI = 1e-6, 1e32                  # min_lm_diagonal, max_lm_diagonal
+CERES_LIN_STAGES = ("err", "chi2", "weight", "Hpl", "Hll", "bl", "Hpp", "bp", "chi2_total", "grad_max", "x_norm", "s2p", "s2l")
+CERES_TRIAL_STAGES = ("S", "bs", "dx_point", "pose_trial", "point_trial", "trial_chi2", "scale", "step_norm")
+DOGLEG_STAGES = ("S", "bs", "dx_point", "jv2", "s1", "s2", "s3", "A", "B", "norm", "mcc", "pose_trial", "point_trial", "trial_chi2", "step_norm")
+
+
+def jacobi_scale2(diag):
+    """TrustRegionMinimizer::IterationZero with jacobi_scaling: the column scale 1 / (1 + sqrt(diag(J^T J)_i)), squared."""
+    q = 1 / (1 + np.sqrt(_ld(diag)))
+    return q * q
+
+
+def multipliers(diag, s2):
+    """The damping of the UNSCALED variables: Ceres solves (S H S + lambda D^2) y = S b with D_i^2 = clamp((S H S)_ii, 1e-6, 1e32) and steps
+    by S y, which is (H + lambda diag(m)) dx = b with m_i = clamp(H_ii s_i^2, 1e-6, 1e32) / s_i^2.
+    Returns (m, the smallest relative distance of an H_ii s_i^2 from a clamp bound, how many non-zero ones sit on the lower bound)."""
+    h = _ld(diag) * _ld(s2)
+    m = np.minimum(np.maximum(h, LD(CLAMP_LO)), LD(CLAMP_HI)) / _ld(s2)
+    if h.size == 0:
+        return m, INF, 0
+    margin = min(float(np.abs(h / LD(CLAMP_LO) - 1).min()), float(np.abs(h / LD(CLAMP_HI) - 1).min()))
+    return m, margin, int(((h < LD(CLAMP_LO)) & (h > 0)).sum())                       # (H_ii = 0: a variable no residual block touches)
+
+
+def reduced_program(graph):
+    """(pose_in [Np], point_in [Nl]): the non-constant parameter blocks that appear in a residual block — what ||x|| and the step norm run
+    over (Ceres' reduced program)."""
+    pose_fixed = np.asarray(graph["pose_fixed"]).astype(bool); point_fixed = np.asarray(graph["point_fixed"]).astype(bool)
+    pose_in = ~pose_fixed & (np.bincount(np.asarray(graph["obs_pose"], dtype=np.int64), minlength=len(pose_fixed)) > 0)
+    la = graph.get("laser")
+    if la is not None and len(la["xyz"]) > 0 and not pose_fixed[la["pose"]]:
+        pose_in[la["pose"]] = True
+    point_in = ~point_fixed & (np.bincount(np.asarray(graph["obs_point"], dtype=np.int64), minlength=len(point_fixed)) > 0)
+    return pose_in, point_in
+
+
+def _diagonals(side, npf, Nl):
+    n6 = 6 * npf
+    dp = _ld(np.asarray(side["Hpp"]).reshape(n6, n6).diagonal()).reshape(npf, 6) if npf else np.zeros((0, 6), dtype=LD)
+    dl = _ld(np.asarray(side["Hll"]).reshape(Nl, 6)[:, [0, 3, 5]])
+    return dp, dl
+
+
+def own_multipliers(graph, side):
+    """(m_p [npf][6], m_l [Nl][3], clamp margin, variables on the lower clamp) from one side's own diagonals and s^2.  Fixed landmarks: 1."""
+    point_fixed = np.asarray(graph["point_fixed"]).astype(bool)
+    npf = int((~np.asarray(graph["pose_fixed"]).astype(bool)).sum()); Nl = len(point_fixed)
+    dp, dl = _diagonals(side, npf, Nl)
+    mp, mg_p, lo_p = multipliers(dp, _ld(side["s2p"]).reshape(npf, 6))
+    free = ~point_fixed
+    ml = np.ones((Nl, 3), dtype=LD)
+    ml[free], mg_l, lo_l = multipliers(dl[free], _ld(side["s2l"]).reshape(Nl, 3)[free])
+    return mp, ml, min(mg_p, mg_l), lo_p + lo_l
+
+
+def _norm_over(graph, a_pose, a_pt, b_pose=None, b_pt=None):
+    """(sqrt(sum of squares), number of terms) of a_* (minus b_*) over the reduced program: 7 numbers per pose, 3 per landmark."""
+    pose_in, point_in = reduced_program(graph)
+    dp = _ld(a_pose).reshape(-1, 7)[pose_in] - (0 if b_pose is None else _ld(b_pose).reshape(-1, 7)[pose_in])
+    dl = _ld(a_pt).reshape(-1, 3)[point_in] - (0 if b_pt is None else _ld(b_pt).reshape(-1, 3)[point_in])
+    return np.sqrt((dp * dp).sum() + (dl * dl).sum()), dp.size + dl.size
+
+
+def judge_ceres_linearize(graph, pose, pt, side, chi2_total, grad_max, x_norm, kept=None):
+    """One side's linearisation under Optimizer/Framework=1.  side: as judge_linearize's plus its fetched s2p, s2l; kept: None at iteration
+    zero (the scaling is judged from the side's own diagonals), else the (s2p, s2l) that side fetched at iteration zero (they must be what
+    they were, bit for bit).  Returns ({stage: ...}, (threshold / clamp distance, delta distance, laser margin), variables on the lower clamp)."""
+    point_fixed = np.asarray(graph["point_fixed"]).astype(bool)
+    npf = int((~np.asarray(graph["pose_fixed"]).astype(bool)).sum()); Nl = len(point_fixed)
+    out, closest = judge_linearize(graph, pose, pt, np.zeros(len(graph["obs_pose"]), np.uint8), side, chi2_total, grad_max)
+    free = ~point_fixed
+    s2p = np.asarray(side["s2p"]).reshape(npf, 6); s2l = np.asarray(side["s2l"]).reshape(Nl, 3)[free]
+    if kept is None:
+        dp, dl = _diagonals(side, npf, Nl)
+        for name, got, truth in (("s2p", s2p, jacobi_scale2(dp)), ("s2l", s2l, jacobi_scale2(dl[free]))):
+            e, k = block_error(got, truth, _own(truth))
+            out[name] = dict(e=e, n=0, block=k)
+    else:
+        out["s2p"] = dict(e=0.0 if np.array_equal(s2p, np.asarray(kept[0]).reshape(npf, 6)) else INF, n=0, block=-1)
+        out["s2l"] = dict(e=0.0 if np.array_equal(s2l, np.asarray(kept[1]).reshape(Nl, 3)[free]) else INF, n=0, block=-1)
+    xn, n_x = _norm_over(graph, pose, pt)
+    e, k = block_error(np.array([x_norm]), _ld([xn]), _ld([xn]))
+    out["x_norm"] = dict(e=e, n=n_x, block=k)
+    _, _, clamp_margin, n_low = own_multipliers(graph, side)
+    return out, (min(closest[0], clamp_margin), closest[1], closest[2]), n_low
+
+
+def judge_ceres_trial(graph, pose, pt, lam, side, trial_chi2, scale, step_norm):
+    """One side's LEVENBERG_MARQUARDT trial at lambda = 1 / radius: judge_trial with the damping lambda m_i, plus the step norm over the
+    reduced program from the side's own trial state.  scale = 2 x model cost change = step^T (lambda M step + b)."""
+    zeros = np.zeros(len(graph["obs_pose"]), np.uint8)
+    mp, ml, _, _ = own_multipliers(graph, side)
+    out, margin = judge_trial(graph, pose, pt, zeros, lam, side, trial_chi2, scale, mp=mp, ml=ml)
+    sn, n_s = _norm_over(graph, side["pose_trial"], side["point_trial"], pose, pt)
+    e, k = block_error(np.array([step_norm]), _ld([sn]), _ld([sn]))
+    out["step_norm"] = dict(e=e, n=n_s, block=k)
+    return out, margin
+
+
+def dogleg_truth(s1, s2, s3, jv2, radius, mu):
+    """DoglegStrategy::ComputeTraditionalDoglegStep on the inner products of the scaled space, S1 = ||g_s||^2, S2 = ||gn_s||^2, S3 = g_s . gn_s,
+    ||J v||^2 (v = g / m; alpha = S1 / ||J v||^2, the Cauchy point is -alpha g_s): the Gauss-Newton step when it lies inside the region (1),
+    the gradient step of length radius when the Cauchy point lies outside (2), else the point where the segment Cauchy -> Gauss-Newton
+    leaves the region (3).  The scaled step is A g_s + B gn_s, i.e. A v + B dn.  model cost change = -(g . step + step^T H step / 2) with
+    g . v = S1, g . dn = S3, v^T H v = ||J v||^2, H dn = -g - mu M dn.
+    Returns dict(A, B, norm, mcc, mcc_mag, case, margin): margin = the smaller relative distance of ||gn_s|| and of alpha ||g_s|| from the radius."""
+    s1, s2, s3, jv2, r, mu = (LD(v) for v in (s1, s2, s3, jv2, radius, mu))
+    gnorm, gn = np.sqrt(s1), np.sqrt(s2)
+    alpha = s1 / jv2
+    margin = min(float(abs(gn / r - 1)), float(abs(alpha * gnorm / r - 1)))
+    if gn <= r:
+        A, B, norm, case = LD(0), LD(1), gn, 1
+    elif alpha * gnorm >= r:
+        A, B, norm, case = -r / gnorm, LD(0), r, 2
+    else:
+        # a = -alpha g_s, b = gn_s; beta in (0, 1) with ||a + beta (b - a)|| = radius
+        b_dot_a = -alpha * s3
+        a_sq = alpha * alpha * s1
+        bma_sq = a_sq - 2 * b_dot_a + s2
+        c = b_dot_a - a_sq
+        d = np.sqrt(c * c + bma_sq * (r * r - a_sq))
+        beta = (d - c) / bma_sq if c <= 0 else (r * r - a_sq) / (d + c)
+        A, B, case = -alpha * (1 - beta), beta, 3
+        norm = np.sqrt(A * A * s1 + 2 * A * B * s3 + B * B * s2)
+    shs = A * A * jv2 + 2 * A * B * (-s1 - mu * s3) + B * B * (-s3 - mu * s2)
+    mcc = -(A * s1 + B * s3 + shs / 2)
+    mag = abs(A * s1) + abs(B * s3) + (A * A * jv2 + 2 * abs(A * B) * (s1 + mu * abs(s3)) + B * B * (abs(s3) + mu * s2)) / 2
+    return dict(A=A, B=B, norm=norm, mcc=mcc, mcc_mag=mag, case=case, margin=margin)
+
+
+def dogleg_products(graph, pose, pt, side, mp, ml, used, drop_laser=False):
+    """The four inner products from one side's own b_p, b_l, weight, dn (dx_pose, dx_point) and m, with the truth's Jacobians at the
+    committed state: dict(jv2, s1, s2, s3, s3_mag, n_blocks, n_vars).  ||J v||^2 is summed residual block by residual block (every active
+    stereo observation with its rho', every laser point), v = g / m = -b / m on the free variables.  drop_laser: without the laser blocks
+    (the tests show that the checks notice)."""
+    op = np.asarray(graph["obs_pose"], dtype=np.int64); ol = np.asarray(graph["obs_point"], dtype=np.int64)
+    pose_fixed = np.asarray(graph["pose_fixed"]).astype(bool); point_fixed = np.asarray(graph["point_fixed"]).astype(bool)
+    Nl = len(point_fixed); npf = int((~pose_fixed).sum()); pidx = pose_index(graph)
+    w_px, w_la, _ = weights_of(graph)
+    bp = _ld(side["bp"]).reshape(npf, 6); bl = _ld(side["bl"]).reshape(Nl, 3)
+    vp = np.zeros((len(pose_fixed), 6), dtype=LD); vp[~pose_fixed] = -bp / mp
+    vl = np.where(point_fixed[:, None], LD(0), -bl / ml)
+    _, _, Ji, Jj = stereo_edge(_ld(pose)[op], _ld(pt)[ol], graph["obs_uvr"], graph["intr"])
+    r = np.einsum("nmc,nc->nm", Ji, vl[ol]) + np.einsum("nmc,nc->nm", Jj, vp[op])
+    wgt = _ld(side["weight"])
+    jv2 = (wgt * w_px * (r * r).sum(axis=1)).sum()
+    n_blocks = int((np.asarray(side["weight"]) != 0).sum())
+    la = None if drop_laser else _laser_terms(graph, pose)
+    if la is not None:
+        rl = np.einsum("nc,c->n", la[2], vp[la[0]])
+        jv2 = jv2 + (w_la * rl * rl).sum()
+        n_blocks += len(rl)
+    dnp = _ld(side["dx_pose"]).reshape(npf, 6); dnl = _ld(side["dx_point"]).reshape(Nl, 3)
+    u = used[:, None]
+    t1 = [bp * bp / mp, np.where(u, bl * bl / ml, LD(0))]
+    t2 = [mp * dnp * dnp, np.where(u, ml * dnl * dnl, LD(0))]
+    t3 = [-bp * dnp, np.where(u, -bl * dnl, LD(0))]
+    return dict(jv2=jv2, s1=sum(t.sum() for t in t1), s2=sum(t.sum() for t in t2), s3=sum(t.sum() for t in t3),
+                s3_mag=sum(np.abs(t).sum() for t in t3), n_blocks=n_blocks, n_vars=bp.size + 3 * int(used.sum()))
+
+
+def used_landmarks(graph, weight):
+    """Free landmarks with an active edge: the ones that are eliminated and stepped."""
+    point_fixed = np.asarray(graph["point_fixed"]).astype(bool); ol = np.asarray(graph["obs_point"], dtype=np.int64)
+    used = np.zeros(len(point_fixed), bool)
+    used[ol[(np.asarray(weight) != 0) & ~point_fixed[ol]]] = True
+    return used
+
+
+def dogleg_norms(graph, pose, pt, side):
+    """(|gn_s|, |cauchy| = alpha |g_s|) in long double from one side's linearisation buffers, s^2 and dn (dx_pose, dx_point): what a case
+    table takes its radii from."""
+    mp, ml, _, _ = own_multipliers(graph, side)
+    P = dogleg_products(graph, pose, pt, side, mp, ml, used_landmarks(graph, side["weight"]))
+    return np.sqrt(P["s2"]), np.sqrt(P["s1"]) * P["s1"] / P["jv2"]
+
+
+def judge_dogleg(graph, pose, pt, radius, mu, side, res):
+    """One side's DOGLEG trial at (radius, mu).  side: its own linearisation buffers, s2p, s2l, and S, bs, dx_pose / dx_point (= dn),
+    pose_trial, point_trial; res: what its trial returned (A, B, norm, mcc, jv2, s1, s2, s3, cand_cost, step_norm).
+    Returns ({stage: ...}, laser margin at the trial state, the dogleg case and its margin ON THE TRUTH of the side's own sums)."""
+    zeros = np.zeros(len(graph["obs_pose"]), np.uint8)
+    mp, ml, _, _ = own_multipliers(graph, side)
+    out, margin = judge_trial(graph, pose, pt, zeros, mu, side, 2.0 * res["cand_cost"], None, mp=mp, ml=ml, dl_AB=(res["A"], res["B"]))
+    used = used_landmarks(graph, side["weight"])
+    P = dogleg_products(graph, pose, pt, side, mp, ml, used)
+
+    def put(stage, x, truth, norm, n):
+        e, k = block_error(np.array([x]), _ld([truth]), _ld([norm]))
+        out[stage] = dict(e=e, n=int(n), block=k)
+
+    put("jv2", res["jv2"], P["jv2"], abs(P["jv2"]), P["n_blocks"])
+    put("s1", res["s1"], P["s1"], abs(P["s1"]), P["n_vars"])
+    put("s2", res["s2"], P["s2"], abs(P["s2"]), P["n_vars"])
+    put("s3", res["s3"], P["s3"], P["s3_mag"], P["n_vars"])
+    D = dogleg_truth(res["s1"], res["s2"], res["s3"], res["jv2"], radius, mu)
+    put("A", res["A"], D["A"], abs(D["A"]), 0)
+    put("B", res["B"], D["B"], abs(D["B"]), 0)
+    put("norm", res["norm"], D["norm"], abs(D["norm"]), 0)
+    put("mcc", res["mcc"], D["mcc"], D["mcc_mag"], 0)
+    sn, n_s = _norm_over(graph, side["pose_trial"], side["point_trial"], pose, pt)
+    put("step_norm", res["step_norm"], sn, sn, n_s)
+    return out, margin, D["case"], D["margin"]

@@ -151,9 +151,9 @@ def test_pose_cov_to_world_matches_finite_differences(hiplib, seed):
 
 
 def test_abi_version_and_error_code(hiplib):
-    assert abi.ABI_VERSION == 9
+    assert abi.ABI_VERSION == 10
     assert abi.ERR_SINGULAR == 10
-    assert hiplib.visfs_ba_abi_version() == 9
+    assert hiplib.visfs_ba_abi_version() == 10
     from visfs_amd import backend
     for name in ("visfs_ba_graph_covariance", "visfs_ba_window_covariance", "visfs_ba_pose_cov_to_world", "visfs_ba_hook_band_selinv"):
         assert name in backend.EXPORTS

@@ -2,7 +2,12 @@
 oracle's restatement of it (tests/test_ceres_flavour.py says what pins that restatement).  Same kernels as the g2o branch — the
 objective differs by the weights (1 / var^2), the damping is LevenbergMarquardtStrategy's per-variable diagonal, the control is
 Ceres' trust-region loop (k_ceres_lin_finalize, ceres_decide) — so the bar is the same: identical iteration / step decisions and
-radius trace, identical outlier sets, poses and landmarks to rounding."""
+radius trace, identical outlier sets, poses and landmarks to rounding.
+
+That bar is 1e-6 of a whole buffer after a whole solve, which the trust region lets a step wrong by a part in 1e8 pass.  The stages of the
+branch — the Jacobi scaling, the per-variable damping in every gather form and solver, the dogleg's inner products, coefficients and
+model cost change, the (+), the candidate cost, the norms — are held one by one to an extended-precision truth of their own inputs in
+tests/test_gpu_ceres_stage_forms.py; this file keeps the control flow and the end result."""
 import ctypes as C
 
 import numpy as np
@@ -72,16 +77,33 @@ def test_ceres_branch_window_level_and_batch_entry(olib):
     s.close()
 
 
-def test_stage_hooks_are_g2o_only(olib):
+def test_stage_hooks_refuse_the_trial_of_another_strategy(olib):
+    """The stage hooks step both branches since ABI 10.  What is still refused, each with an error text: the dogleg trial on a g2o handle
+    and on a LEVENBERG_MARQUARDT handle, and stage_trial on a DOGLEG handle.  A refusal leaves the handle usable."""
     from visfs_amd import backend
     w = synth.make_window("C1")
-    prm = abi.default_params(framework=1)
-    s = backend.Solver(prm)
-    gb, *_ = abi.pack_window_with(s.lib.visfs_ba_pack_window, prm, abi.WindowBuffers(w))
-    s.upload(gb)
-    chi, md = C.c_double(), C.c_double()
-    assert s.lib.visfs_ba_stage_linearize(s.h, C.byref(chi), C.byref(md)) == abi.ERR_UNSUPPORTED
-    s.close()
+    out = np.zeros(12)
+    pd = out.ctypes.data_as(C.POINTER(C.c_double))
+    for kw, call, word in ((dict(framework=0), "dogleg", "g2o"), (dict(framework=1, trust_region=0), "dogleg", "LEVENBERG_MARQUARDT"),
+                           (dict(framework=1, trust_region=1), "trial", "DOGLEG")):
+        prm = abi.default_params(**kw)
+        s = backend.Solver(prm)
+        gb, *_ = abi.pack_window_with(s.lib.visfs_ba_pack_window, prm, abi.WindowBuffers(w))
+        s.upload(gb)
+        chi0, _ = s.linearize()
+        if call == "dogleg":
+            rc = s.lib.visfs_ba_stage_dogleg_trial(s.h, 1e4, 1e-8, pd)
+        else:
+            chi, sc, it, ok = C.c_double(), C.c_double(), C.c_int32(), C.c_int32()
+            rc = s.lib.visfs_ba_stage_trial(s.h, 1e-4, C.byref(chi), C.byref(sc), C.byref(it), C.byref(ok))
+        assert rc == abi.ERR_UNSUPPORTED, (kw, rc)
+        text = s.lib.visfs_ba_last_error(s.h).decode()
+        assert word in text and "stage" in text, (kw, text)
+        assert s.linearize()[0] == chi0                       # nothing was stepped
+        s.reset()
+        rc, st = s.optimize()
+        assert rc == abi.OK
+        s.close()
 
 
 # ------------------------------------------------------------------ Optimizer/TrustRegion=1 under Framework=1: DOGLEG (Optimizer.cpp:515-519)

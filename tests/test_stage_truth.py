@@ -1,7 +1,12 @@
 """The extended-precision truth of tests/stage_truth.py, checked on the CPU: its Jacobians against central differences in long double,
 its Schur complement against a dense long-double A - B D^-1 B^T, the oracle against it on every window of the GPU case table
 (tests/stage_forms.py), and the criterion eg <= 10 max(eo, (64 + n) u) shown to bite on nine single wrongs applied to the oracle's own
-buffers.  tests/test_gpu_stage_forms.py holds every device kernel form to the same truth."""
+buffers.  tests/test_gpu_stage_forms.py holds every device kernel form to the same truth.
+
+The second half does the same for the Ceres branch (Optimizer/Framework=1, tests/ceres_stage_forms.py): the factor's
+Jacobians against central differences, the damped Schur truth against the dense long-double solve of (H + lambda diag m) dx = b, the
+dogleg truth against the textbook construction in the scaled variables, the oracle on every window under both strategies, and nine
+single wrongs of that branch refused at their own stage.  tests/test_gpu_ceres_stage_forms.py holds the device to it."""
 import numpy as np
 import pytest
 
@@ -384,3 +389,369 @@ def test_criterion_rejects_dx_point_computed_with_hll_without_lambda(stepped):
     xm = s["tr"]["dx_point"].copy().reshape(Nl, 3)
     xm[used] = np.einsum("lrc,lc->lr", D0.astype(np.float64), c)
     assert _failing("trial", _trial(s), _trial(s, dx_point=xm.reshape(-1)))[0] == "dx_point"
+
+
+# ===================================================================== Optimizer/Framework=1: the Ceres branch (tests/ceres_stage_forms.py)
+import ceres_stage_forms as CF  # noqa: E402
+
+
+def _solve_ld(A, b):
+    """A x = b in long double: an fp64 solve refined three times."""
+    A = ST._ld(A); b = ST._ld(b)
+    x = np.linalg.solve(A.astype(np.float64), b.astype(np.float64)).astype(LD)
+    for _ in range(3):
+        x = x + np.linalg.solve(A.astype(np.float64), (b - A @ x).astype(np.float64)).astype(LD)
+    return x
+
+
+# ----------------------------------------------------------------- (a) the truth is right
+def test_ceres_stereo_jacobians_agree_with_central_differences(c3):
+    """The residual info * e (StereoObservationFactor.cpp:24-25) against info * (Jj, Ji) (:43, :73), to 1e-8 of the block.  The pose
+    block is the factor's own: written, as EdgeStereo's, for the camera-frame point moved by dt + dtheta x pc, and handed to
+    PoseLocalParameterization's [I6; 0] as it is; the translation columns are also what Plus (t + dt) gives."""
+    gb, g = c3
+    k = np.arange(0, gb.n_obs, 97)
+    tq = ST._ld(gb.pose_tq)[g["obs_pose"][k]]; pw = ST._ld(gb.point_xyz)[g["obs_point"][k]]; uvr = g["obs_uvr"][k]
+    info = LD(g["w_px"])
+    _, _, Ji, Jj = ST.stereo_edge(tq, pw, uvr, g["intr"])
+    pc = np.einsum("nij,nj->ni", ST.quat_to_R(tq[:, 3:]), pw) + tq[:, :3]
+    ident = np.tile(ST._ld([0, 0, 0, 0, 0, 0, 1]), (len(k), 1))
+    h = LD(1e-9) * np.abs(pc).max()
+    fd = np.empty_like(Jj)
+    for c in range(6):
+        d = np.zeros(6, dtype=LD); d[c] = h
+        move = d[:3] + np.cross(d[3:], pc)
+        fd[:, :, c] = info * (ST.stereo_edge(ident, pc + move, uvr, g["intr"])[0] - ST.stereo_edge(ident, pc - move, uvr, g["intr"])[0]) / (2 * h)
+    assert max(_rel(fd[n], info * Jj[n]) for n in range(len(k))) < FD_TOL
+    for c in range(3):
+        d = np.zeros(6, dtype=LD); d[c] = h
+        plus = info * (ST.stereo_edge(ST.pose_update(tq, d), pw, uvr, g["intr"])[0] - ST.stereo_edge(ST.pose_update(tq, -d), pw, uvr, g["intr"])[0]) / (2 * h)
+        assert max(_rel(plus[n], info * Jj[n, :, c]) for n in range(len(k))) < FD_TOL
+    fl = np.empty_like(Ji)
+    h = LD(1e-9) * np.abs(pw).max()
+    for c in range(3):
+        d = np.zeros(3, dtype=LD); d[c] = h
+        fl[:, :, c] = info * (ST.stereo_edge(tq, pw + d, uvr, g["intr"])[0] - ST.stereo_edge(tq, pw - d, uvr, g["intr"])[0]) / (2 * h)
+    assert max(_rel(fl[n], info * Ji[n]) for n in range(len(k))) < FD_TOL
+
+
+def test_ceres_laser_jacobian_is_taken_over_the_raw_parameters_at_the_poses_own_w(olib):
+    """OccupiedSpace2dFactor differentiates over the seven raw parameters and the local parameterisation drops q.w: central differences
+    in (t, qx, qy, qz) with q.w held — not the g2o edge's aliased function, which differs from it."""
+    prm, wb, gb, g, steps, lams, npf = F.oracle_steps(olib, "laser-only")
+    la = g["laser"]
+    tq = ST._ld(gb.pose_tq)[la["pose"]]; P = ST._ld(la["xyz"])
+    e0, J, _ = ST.laser_edge(tq, la["Tcr"], P, la, exact=True, own_w=True)
+    Jg2o = ST.laser_edge(tq, la["Tcr"], P, la, exact=True)[1]
+    fd = np.empty_like(J)
+    for c in range(6):
+        h = LD(1e-9) * (np.abs(tq[:3]).max() if c < 3 else 1)
+        d = np.zeros(7, dtype=LD); d[c] = h
+        fd[:, c] = (ST.laser_edge(tq + d, la["Tcr"], P, la, exact=True)[0] - ST.laser_edge(tq - d, la["Tcr"], P, la, exact=True)[0]) / (2 * h)
+    ones = np.ones(len(P), dtype=LD)
+    r, c_, _ = ST._laser_functor([ST._Jet(ones * tq[i]) for i in range(7)], P, la["Tcr"], la, exact=True)
+    knot = np.minimum(np.abs(r.a - np.round(r.a)), np.abs(c_.a - np.round(c_.a))) < 1e-5
+    strong = ~knot & (np.abs(J).max(axis=1) > 1e-3)
+    assert strong.sum() > 30 and max(_rel(fd[n], J[n]) for n in np.nonzero(strong)[0]) < FD_TOL
+    assert max(_rel(Jg2o[n], J[n]) for n in np.nonzero(strong)[0]) > 1e-3
+
+
+def _hand_system(rng):
+    """3 free poses, 4 landmarks, 8 observations: H = J^T J of a random Jacobian (so every Schur term and ||J v||^2 exist), gradient, and
+    Ceres' scaling and multipliers of it."""
+    npf, Nl = 3, 4
+    obs = sorted([(0, 0), (1, 0), (2, 0), (0, 1), (2, 1), (1, 2), (2, 2), (0, 3)], key=lambda t: (t[1], t[0]))
+    n = 6 * npf + 3 * Nl
+    J = np.zeros((3 * len(obs), n))
+    for k, (a, l) in enumerate(obs):
+        J[3 * k:3 * k + 3, 6 * a:6 * a + 6] = rng.standard_normal((3, 6))
+        J[3 * k:3 * k + 3, 6 * npf + 3 * l:6 * npf + 3 * l + 3] = rng.standard_normal((3, 3)) * (1e-4 if l == 3 else 1.0)   # (landmark 3: on the lower clamp)
+    f = rng.standard_normal(3 * len(obs))
+    H = ST._ld(J).T @ ST._ld(J); b = -(ST._ld(J).T @ ST._ld(f))
+    s2 = ST.jacobi_scale2(np.diag(H))
+    m, margin, n_low = ST.multipliers(np.diag(H), s2)
+    assert n_low == 3 and margin > 1e-3
+    return npf, Nl, obs, J, H, b, m
+
+
+def test_damped_schur_truth_equals_the_dense_long_double_solve(olib):
+    npf, Nl, obs, J, H, b, m = _hand_system(np.random.default_rng(5))
+    n6 = 6 * npf
+    lam = 0.37
+    g = dict(pose_fixed=np.zeros(npf, bool), point_fixed=np.zeros(Nl, bool), obs_pose=np.array([o[0] for o in obs]), obs_point=np.array([o[1] for o in obs]))
+    Hf = H.astype(np.float64)
+    Hpl = np.stack([Hf[6 * a:6 * a + 6, n6 + 3 * l:n6 + 3 * l + 3] for a, l in obs])
+    Hll = np.stack([Hf[n6 + 3 * l:n6 + 3 * l + 3, n6 + 3 * l:n6 + 3 * l + 3][np.triu_indices(3)] for l in range(Nl)])
+    Hpp = np.zeros((n6, n6))
+    for a in range(npf):
+        Hpp[6 * a:6 * a + 6, 6 * a:6 * a + 6] = Hf[6 * a:6 * a + 6, 6 * a:6 * a + 6]
+    bf = b.astype(np.float64)
+    # (the multipliers are taken from the fp64 copies the truth is given)
+    s2 = ST.jacobi_scale2(np.diag(Hf)); mm, _, _ = ST.multipliers(np.diag(Hf), s2)
+    mp, ml = mm[:n6].reshape(npf, 6), mm[n6:].reshape(Nl, 3)
+    tr = ST.schur_truth(g, lam, Hpp, bf[:n6], Hpl, Hll, bf[n6:].reshape(Nl, 3), np.ones(len(obs)), mp=mp, ml=ml)
+    A = ST._ld(Hf) + LD(lam) * np.diag(mm)
+    dx = _solve_ld(A, bf)
+    S = np.zeros((n6, n6), dtype=LD)
+    for (i, j), blk in zip(tr["keys"], tr["S"]):
+        S[6 * i:6 * i + 6, 6 * j:6 * j + 6] = blk; S[6 * j:6 * j + 6, 6 * i:6 * i + 6] = blk.T
+    xp = _solve_ld(S, tr["bs"].reshape(-1))
+    assert np.abs(xp - dx[:n6]).max() < 1e-15 * np.abs(dx).max()
+    Bm = ST._ld(Hf)[:n6, n6:]
+    xl = np.einsum("lrc,lc->lr", tr["D"], ST._ld(bf[n6:]).reshape(Nl, 3) - (Bm.T @ xp).reshape(Nl, 3))
+    assert np.abs(xl.reshape(-1) - dx[n6:]).max() < 1e-15 * np.abs(dx).max()
+    # with the plain lambda in place of lambda m the solve is another one
+    tr0 = ST.schur_truth(g, lam, Hpp, bf[:n6], Hpl, Hll, bf[n6:].reshape(Nl, 3), np.ones(len(obs)))
+    assert np.abs(tr0["bs"] - tr["bs"]).max() > 1e-3 * np.abs(tr["bs"]).max()
+
+
+def test_dogleg_truth_equals_the_textbook_construction_in_the_scaled_variables():
+    npf, Nl, obs, J, H, b, m = _hand_system(np.random.default_rng(6))
+    g = -b
+    mu = LD(1e-3)
+    D = np.sqrt(m)
+    Hs = H / np.outer(D, D); gs = g / D
+    gn_s = _solve_ld(Hs + mu * np.eye(len(D), dtype=LD), -gs)                      # the regularised Gauss-Newton step, scaled
+    alpha = (gs @ gs) / (gs @ Hs @ gs)
+    cauchy = -alpha * gs
+    dn = gn_s / D; v = g / m
+    Jv = ST._ld(J) @ v
+    s1, s2, s3, jv2 = gs @ gs, gn_s @ gn_s, gs @ gn_s, Jv @ Jv
+    gn_norm, c_norm = float(np.sqrt(s2)), float(np.sqrt(cauchy @ cauchy))
+    assert c_norm < gn_norm
+    seen = set()
+    for radius in (2 * gn_norm, 0.5 * c_norm, 0.5 * (c_norm + gn_norm)):
+        r = LD(radius)
+        if gn_norm <= radius:
+            step_s = gn_s
+        elif c_norm >= radius:
+            step_s = -(r / np.sqrt(gs @ gs)) * gs
+        else:                                                                        # |cauchy + t (gn - cauchy)| = radius, t in (0, 1): bisection
+            lo, hi = LD(0), LD(1)
+            for _ in range(200):
+                t = (lo + hi) / 2
+                p = cauchy + t * (gn_s - cauchy)
+                lo, hi = (t, hi) if p @ p < r * r else (lo, t)
+            step_s = cauchy + lo * (gn_s - cauchy)
+        T_ = ST.dogleg_truth(s1, s2, s3, jv2, radius, mu)
+        seen.add(T_["case"])
+        assert T_["margin"] > 0.01
+        got_s = T_["A"] * gs + T_["B"] * gn_s
+        assert np.abs(got_s - step_s).max() < 1e-15 * np.abs(step_s).max()
+        assert abs(T_["norm"] - np.sqrt(step_s @ step_s)) < 1e-15 * np.sqrt(step_s @ step_s)
+        step = T_["A"] * v + T_["B"] * dn                                            # the same step in the unscaled variables
+        assert np.abs(step - step_s / D).max() < 1e-15 * np.abs(step).max()
+        mcc = -(g @ step + (step @ H @ step) / 2)
+        assert abs(T_["mcc"] - mcc) < 1e-14 * T_["mcc_mag"]
+        # without mu in s^T H s the model cost change is another one (H dn = -g - mu M dn)
+        shs0 = T_["A"] ** 2 * jv2 + 2 * T_["A"] * T_["B"] * (-s1) + T_["B"] ** 2 * (-s3)
+        if T_["B"] != 0:
+            assert abs(-(T_["A"] * s1 + T_["B"] * s3 + shs0 / 2) - mcc) > 1e-9 * T_["mcc_mag"]
+    assert seen == {1, 2, 3}
+
+
+# ----------------------------------------------------------------- (c) the oracle meets the truth
+@pytest.mark.parametrize("name", CF.CPU_CASES)
+def test_oracle_meets_the_ceres_truth_on_every_window_of_the_case_table(olib, name):
+    """Every stage's eo below 10 x its floor; S as in the g2o test above: on sum|terms| below the bound, on the block's own magnitude
+    within the block's measured cancellation.  No window needs a conditioning term, the clamp window's far landmarks (cond 2e6 at the
+    dogleg's mu = 1e-8) included."""
+    recs = CF.run_oracle_case(olib, name)
+    assert recs
+    print("\n".join(CF.log_lines(recs)))
+    CF.check_sequence(name, recs)
+    for r in recs:
+        tag = (name, r["step"], r["stage"])
+        CF.check_record(dict(r, e_g=r["e_o"]), device=False)                          # the conditions on the input; the criterion is trivially met
+        if r["stage"] == "mark":
+            continue
+        bound = 10 * ST.floor_of(r["n"])
+        if r["stage"] == "S":
+            assert r["e_mag_o"] < bound and r["e_o"] < bound * max(r["cancel_o"], 1.0), (tag, r["e_o"], r["e_mag_o"], r["cancel_o"], r["cond"], bound)
+        else:
+            assert r["e_o"] < bound, (tag, r["e_o"], bound)
+
+
+def test_ceres_cpu_cases_cover_every_window_of_the_table():
+    assert {(CF.CASES[n]["window"], CF.CASES[n]["strategy"]) for n in CF.CPU_CASES} == {(c["window"], c["strategy"]) for c in CF.CASES.values()}
+
+
+def test_the_clamp_window_has_variables_on_the_lower_clamp(olib):
+    for name in ("lm-clamp", "dl-clamp"):
+        recs = CF.run_oracle_case(olib, name)
+        low = [r["n_low"] for r in recs if r["kind"] == "linearize" and r["stage"] == "s2l"]
+        assert low and all(v == [3 * CF.CLAMP_FAR] for v in low), low
+        assert min(r["closest"] for r in recs) >= CF.MIN_CLOSEST
+
+
+# ----------------------------------------------------------------- (b) the criterion bites on the Ceres stages
+def _ceres_stepped(olib, window, strategy, trial, prm_kw=None):
+    """The oracle on `window` under `strategy`: its iteration-zero linearisation and one trial (("trial", lambda) or ("dogleg", mu, which)),
+    with every buffer and what the calls returned."""
+    w, kw = CF.stage_window(window)
+    prm = CF.params_of(strategy, {**kw, **(prm_kw or {})})
+    wb, gb, *_ = F.graph_of(olib.oracle_pack_window, prm, w)
+    g = CF.graph_arrays(gb, prm)
+    o = oracle_lib.OracleSystem(olib, prm, gb)
+    try:
+        chi, gmax, xn = o.ceres_linearize()
+        lin = CF._fetch(o, CF.LIN_BUFS)
+        s = dict(g=g, gb=gb, pose=gb.pose_tq.copy(), pt=gb.point_xyz.copy(), lin=lin, chi=chi, gmax=gmax, xn=xn)
+        if trial[0] == "trial":
+            tchi, sc, sn, ok = o.ceres_trial(trial[1])
+            s.update(lam=trial[1], tchi=tchi, sc=sc, sn=sn)
+        else:
+            assert o.dogleg_stage(1e300, trial[1])["ok"] == 1                        # (leaves dn in the DX buffers: the truth's norms of it)
+            gn, cauchy = ST.dogleg_norms(g, s["pose"], s["pt"], {**lin, **CF._fetch(o, F.TRIAL_BUFS)})
+            radius = float((2 * gn, cauchy / 2, (cauchy + gn) / 2)[trial[2]])
+            res = o.dogleg_stage(radius, trial[1])
+            ok = res["ok"]
+            s.update(mu=trial[1], radius=radius, res=res)
+        assert ok == 1
+        s["tr"] = CF._fetch(o, F.TRIAL_BUFS)
+    finally:
+        o.close()
+    return s
+
+
+@pytest.fixture(scope="module")
+def lv_lm(olib):
+    return _ceres_stepped(olib, ("laser", True, F.LASER_SEED), "lm", ("trial", 1e-4), dict(pixel_variance=2.0))
+
+
+@pytest.fixture(scope="module")
+def lv_dl(olib):
+    return _ceres_stepped(olib, ("laser", True, F.LASER_SEED), "dl", ("dogleg", 1e-3, 2), dict(pixel_variance=2.0))
+
+
+@pytest.fixture(scope="module")
+def clamp_lm(olib):
+    return _ceres_stepped(olib, ("clamp",), "lm", ("trial", 1e-4))
+
+
+def _clin(s, **mut):
+    return ST.judge_ceres_linearize(s["g"], s["pose"], s["pt"], {**s["lin"], **mut}, s["chi"], s["gmax"], s["xn"])[0]
+
+
+def _ctrial(s, **mut):
+    return ST.judge_ceres_trial(s["g"], s["pose"], s["pt"], s["lam"], {**s["lin"], **s["tr"], **mut}, s["tchi"], s["sc"], s["sn"])[0]
+
+
+def _cdog(s, res=None, **mut):
+    return ST.judge_dogleg(s["g"], s["pose"], s["pt"], s["radius"], s["mu"], {**s["lin"], **s["tr"], **mut}, {**s["res"], **(res or {})})[0]
+
+
+def _refused(kind, so, sg):
+    """The stages of one step at which CF.check_record refuses the (mutated) side `sg` beside the oracle `so`, in stage order."""
+    base = dict(step=0, kind=kind, lam=0.0, radius=0.0, closest=(1.0, 1.0, ST.INF), ok=1, n_out=0, flags_ok=1, case=0, dl_margin=ST.INF, n_low=0,
+                s2_vs_prev=-1, s2_vs_first=-1)
+    bad = []
+    for rec in CF.records_of("lm-laser-visual", [dict(base, stages=so)], [dict(base, stages=sg)], dict(n_free_poses=0)):
+        try:
+            CF.check_record(rec, device=False)
+        except AssertionError:
+            bad.append(rec["stage"])
+    return bad
+
+
+def _dense_S(tr, npf):
+    S = np.zeros((npf, 6, npf, 6))
+    for (i, j), blk in zip(tr["keys"], tr["S"]):
+        S[i, :, j, :] = blk.astype(np.float64); S[j, :, i, :] = blk.T.astype(np.float64)
+    return S.reshape(-1)
+
+
+def test_the_unmutated_oracle_passes_every_ceres_stage(lv_lm, lv_dl, clamp_lm):
+    assert _refused("linearize", _clin(lv_lm), _clin(lv_lm)) == [] and _refused("trial", _ctrial(lv_lm), _ctrial(lv_lm)) == []
+    assert _refused("dogleg", _cdog(lv_dl), _cdog(lv_dl)) == [] and _refused("trial", _ctrial(clamp_lm), _ctrial(clamp_lm)) == []
+    assert lv_dl["res"]["A"] != 0 and lv_dl["res"]["B"] not in (0.0, 1.0)              # the dogleg trial is on the segment (case 3)
+
+
+def test_criterion_rejects_the_jacobi_scale_without_the_square_root(lv_lm):
+    s = lv_lm; lin = s["lin"]
+    n6 = len(lin["bp"])
+    q = 1.0 / (1.0 + lin["Hpp"].reshape(n6, n6).diagonal())
+    assert _refused("linearize", _clin(s), _clin(s, s2p=q * q))[0] == "s2p"
+    ql = 1.0 / (1.0 + lin["Hll"].reshape(-1, 6)[:, [0, 3, 5]])
+    assert _refused("linearize", _clin(s), _clin(s, s2l=(ql * ql).reshape(-1)))[0] == "s2l"
+
+
+def test_criterion_rejects_the_information_value_not_squared(lv_lm):
+    s = lv_lm
+    assert s["g"]["w_px"] == 0.5
+    assert _refused("linearize", _clin(s), _clin(s, chi2=s["lin"]["chi2"] / s["g"]["w_px"]))[0] == "chi2"
+    # one pass that squares it once too few: H_ll with rho' info in place of rho' info^2
+    assert _refused("linearize", _clin(s), _clin(s, Hll=s["lin"]["Hll"] / s["g"]["w_px"]))[0] == "Hll"
+
+
+def test_criterion_rejects_g2os_kernel_weight_in_place_of_huber_loss(lv_lm):
+    """g2o's rho' is a function of ITS chi2 = e^T Omega e; HuberLoss's of ||info e||^2."""
+    s = lv_lm; g = s["g"]
+    w = np.asarray(ST.huber(s["lin"]["chi2"] / g["w_px"], g["delta"])[1], dtype=np.float64) * (s["lin"]["weight"] != 0)
+    assert (w != s["lin"]["weight"]).sum() > 0
+    assert _refused("linearize", _clin(s), _clin(s, weight=w))[0] == "weight"
+
+
+def _wrong_multiplier_trial(s, mp, ml):
+    lin = s["lin"]
+    npf = len(lin["bp"]) // 6
+    tr = ST.schur_truth(s["g"], s["lam"], lin["Hpp"], lin["bp"], lin["Hpl"], lin["Hll"], lin["bl"], lin["weight"], mp=mp, ml=ml)
+    return dict(S=_dense_S(tr, npf), bs=tr["bs"].astype(np.float64).reshape(-1))
+
+
+def test_criterion_rejects_the_lower_clamp_missing(clamp_lm):
+    s = clamp_lm
+    mp, ml, margin, n_low = ST.own_multipliers(s["g"], s["lin"])
+    assert n_low == 3 * CF.CLAMP_FAR and margin > CF.MIN_CLOSEST
+    npf = len(s["lin"]["bp"]) // 6
+    dp, dl = ST._diagonals(s["lin"], npf, len(s["g"]["point_fixed"]))
+    ml_wrong = np.where(dl > 0, dl, ml)                                                # m = H_ii s^2 / s^2, no clamp
+    assert (ml_wrong != ml).sum() == n_low
+    bad = _refused("trial", _ctrial(s), _ctrial(s, **_wrong_multiplier_trial(s, mp, ml_wrong)))
+    assert bad[0] == "S", bad
+
+
+def test_criterion_rejects_one_damping_term_taken_with_the_plain_lambda(lv_lm):
+    s = lv_lm
+    mp, ml, _, _ = ST.own_multipliers(s["g"], s["lin"])
+    n6 = len(s["lin"]["bp"])
+    i = n6 - 2
+    S = s["tr"]["S"].copy().reshape(n6, n6)
+    S[i, i] += s["lam"] * (1.0 - float(mp.reshape(-1)[i]))
+    assert abs(float(mp.reshape(-1)[i]) - 1.0) > 1e-3
+    assert _refused("trial", _ctrial(s), _ctrial(s, S=S.reshape(-1)))[0] == "S"
+
+
+def test_criterion_rejects_one_partial_missing_from_s1(lv_dl):
+    s = lv_dl; lin = s["lin"]
+    mp, ml, _, _ = ST.own_multipliers(s["g"], lin)
+    Nl = len(s["g"]["point_fixed"])
+    used = np.nonzero(np.abs(s["tr"]["dx_point"].reshape(Nl, 3)).max(axis=1) > 0)[0]
+    l = int(used[-1])                                                                   # the last landmark's share
+    part = float((ST._ld(lin["bl"]).reshape(Nl, 3)[l] ** 2 / ml[l]).sum())
+    assert part > 0
+    assert _refused("dogleg", _cdog(s), _cdog(s, res=dict(s1=s["res"]["s1"] - part)))[0] == "s1"
+
+
+def test_criterion_rejects_the_laser_blocks_missing_from_jv2(lv_dl):
+    s = lv_dl; lin = s["lin"]
+    mp, ml, _, _ = ST.own_multipliers(s["g"], lin)
+    Nl = len(s["g"]["point_fixed"])
+    used = np.abs(s["tr"]["dx_point"].reshape(Nl, 3)).max(axis=1) > 0
+    P = ST.dogleg_products(s["g"], s["pose"], s["pt"], {**lin, **s["tr"]}, mp, ml, used, drop_laser=True)
+    assert float(P["jv2"]) < s["res"]["jv2"]
+    assert _refused("dogleg", _cdog(s), _cdog(s, res=dict(jv2=float(P["jv2"]))))[0] == "jv2"
+
+
+def test_criterion_rejects_mu_missing_from_the_model_cost_change(lv_dl):
+    s = lv_dl; r = s["res"]
+    shs = r["A"] ** 2 * r["jv2"] + 2 * r["A"] * r["B"] * (-r["s1"]) + r["B"] ** 2 * (-r["s3"])
+    mcc = -(r["A"] * r["s1"] + r["B"] * r["s3"] + 0.5 * shs)
+    assert _refused("dogleg", _cdog(s), _cdog(s, res=dict(mcc=mcc)))[0] == "mcc"
+
+
+def test_criterion_rejects_the_gradient_part_missing_from_the_landmark_step(lv_dl):
+    s = lv_dl
+    Nl = len(s["g"]["point_fixed"])
+    pt = s["pt"].reshape(Nl, 3) + s["res"]["B"] * s["tr"]["dx_point"].reshape(Nl, 3)   # B dn alone, A v left out
+    assert _refused("dogleg", _cdog(s), _cdog(s, point_trial=pt.reshape(-1)))[0] == "point_trial"

@@ -8,7 +8,7 @@ import ctypes as C
 
 import numpy as np
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 TUNE_LATENCY, TUNE_THROUGHPUT = 0, 1            # visfs_ba_set_tuning
 MAX_TRACE = 64
 
@@ -18,7 +18,7 @@ OK, PASSTHROUGH, ERR_TOO_FEW_POSES, ERR_NAN_CHI2, ERR_HUGE_CHI2_1, ERR_HUGE_CHI2
 
 # stage buffer ids
 BUF_OBS_ERR, BUF_OBS_CHI2, BUF_OBS_WEIGHT, BUF_HPL, BUF_HLL, BUF_BL, BUF_HPP, BUF_BP, \
-    BUF_S, BUF_BS, BUF_DX_POSE, BUF_DX_POINT, BUF_POSE_TRIAL, BUF_POINT_TRIAL = range(14)
+    BUF_S, BUF_BS, BUF_DX_POSE, BUF_DX_POINT, BUF_POSE_TRIAL, BUF_POINT_TRIAL, BUF_S2P, BUF_S2L = range(16)
 
 _pd = C.POINTER(C.c_double)
 _pf = C.POINTER(C.c_float)
@@ -101,7 +101,7 @@ class GraphInfo(C.Structure):
                 ("n_odo", C.c_int32), ("n_blk", C.c_int32), ("n_pairs", C.c_int64), ("lanes_per_landmark", C.c_int32),
                 ("n_schur_chunks", C.c_int32), ("device_bytes", C.c_int64), ("fused_path", C.c_int32), ("solver_kernel", C.c_int32),
                 ("band_blocks", C.c_int32), ("graph_replayed", C.c_int32), ("unit_form", C.c_int32),
-                ("schur_runs", C.c_int32), ("schur_run_landmarks", C.c_int32)]
+                ("schur_runs", C.c_int32), ("schur_run_landmarks", C.c_int32), ("landmark_partials", C.c_int32)]
 
 
 class Profile(C.Structure):

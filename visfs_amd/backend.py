@@ -26,6 +26,7 @@ EXPORTS = [
     "visfs_ba_profile_read", "visfs_ba_batch_upload", "visfs_ba_batch_reset", "visfs_ba_batch_optimize", "visfs_ba_batch_download",
     "visfs_ba_create_error", "visfs_ba_set_tuning", "visfs_ba_hook_lm_script", "visfs_ba_hook_ceres_script", "visfs_ba_hook_dogleg_script", "visfs_ba_hook_dogleg_combine", "visfs_ba_solve_batch_sharded", "visfs_ba_stage_commit", "visfs_ba_stage_begin_phase", "visfs_ba_stage_mark_outliers",
     "visfs_ba_graph_covariance", "visfs_ba_window_covariance", "visfs_ba_pose_cov_to_world", "visfs_ba_hook_band_selinv",
+    "visfs_ba_stage_dogleg_trial", "visfs_ba_stage_ceres_values",
 ]
 
 _lib = None
@@ -109,6 +110,10 @@ def load_library():
     lib.visfs_ba_pose_cov_to_world.restype = None
     lib.visfs_ba_hook_band_selinv.argtypes = [C.c_int32, C.c_int32, _pd, _pd]
     lib.visfs_ba_hook_band_selinv.restype = C.c_int
+    lib.visfs_ba_stage_dogleg_trial.argtypes = [C.c_void_p, C.c_double, C.c_double, _pd]
+    lib.visfs_ba_stage_dogleg_trial.restype = C.c_int
+    lib.visfs_ba_stage_ceres_values.argtypes = [C.c_void_p, _pd]
+    lib.visfs_ba_stage_ceres_values.restype = C.c_int
     if lib.visfs_ba_abi_version() != abi.ABI_VERSION:
         raise BackendError("ABI version mismatch between visfs_amd/abi.py and libvisfs_ba_hip.so")
     _lib = lib
@@ -254,6 +259,30 @@ class Solver:
         self._check(self.lib.visfs_ba_stage_trial(self.h, lam, C.byref(chi), C.byref(sc), C.byref(it), C.byref(ok)), "stage_trial")
         return chi.value, sc.value, it.value, ok.value
 
+    def ceres_linearize(self):
+        """stage_linearize of an Optimizer/Framework=1 handle: (sum of rho, ||g||_inf, ||x||)."""
+        chi, gmax = self.linearize()
+        return chi, gmax, self.ceres_values()[1]
+
+    def ceres_trial(self, lam):
+        """stage_trial of a LEVENBERG_MARQUARDT handle at lambda = 1 / radius: (sum of rho at the candidate, 2 x model cost change,
+        ||x - candidate||, solver_ok)."""
+        chi, sc, _, ok = self.trial(lam)
+        return chi, sc, self.ceres_values()[2], ok
+
+    def dogleg_stage(self, radius, mu):
+        """One trial of a DOGLEG handle: dict(A, B, norm, mcc, jv2, s1, s2, s3, cand_cost, step_norm, ok)."""
+        out = np.zeros(12)
+        self._check(self.lib.visfs_ba_stage_dogleg_trial(self.h, radius, mu, _p(out)), "stage_dogleg_trial")
+        keys = ("A", "B", "norm", "mcc", "jv2", "s1", "s2", "s3", "cand_cost", "step_norm", "ok")
+        return dict(zip(keys, (float(v) for v in out[:11])))
+
+    def ceres_values(self):
+        """(||g||_inf, ||x||) of the last linearize and ||x - candidate|| of the last trial of an Optimizer/Framework=1 handle."""
+        out = np.zeros(4)
+        self._check(self.lib.visfs_ba_stage_ceres_values(self.h, _p(out)), "stage_ceres_values")
+        return float(out[0]), float(out[1]), float(out[2])
+
     def commit(self):
         self._check(self.lib.visfs_ba_stage_commit(self.h), "stage_commit")
 
@@ -270,7 +299,8 @@ class Solver:
                 abi.BUF_HPL: g.n_obs * 18, abi.BUF_HLL: g.n_points * 6, abi.BUF_BL: g.n_points * 3,
                 abi.BUF_HPP: n6 * n6, abi.BUF_BP: n6, abi.BUF_S: n6 * n6, abi.BUF_BS: n6,
                 abi.BUF_DX_POSE: n6, abi.BUF_DX_POINT: g.n_points * 3,
-                abi.BUF_POSE_TRIAL: g.n_poses * 7, abi.BUF_POINT_TRIAL: g.n_points * 3}[which]
+                abi.BUF_POSE_TRIAL: g.n_poses * 7, abi.BUF_POINT_TRIAL: g.n_points * 3,
+                abi.BUF_S2P: n6, abi.BUF_S2L: g.n_points * 3}[which]
         out = np.zeros(max(size, 1))
         self._check(self.lib.visfs_ba_stage_fetch(self.h, which, _p(out), size), "stage_fetch")
         return out[:size]

@@ -88,6 +88,9 @@ struct Workspace {
     bool pristine = false;                         // the estimates are the uploaded ones (upload / reset, no optimise since): a solve can be re-run from its start
     bool direct_ready = false;                     // the structures of the direct solver exist although Optimizer/Solver=2: the fallback of a timed-out persistent PCG
     int solver_now = -1;                           // >= 0: the linear solver of the run in progress when it is not Optimizer/Solver (the fallback run: 0)
+    // stage hooks on an Optimizer/Framework=1 handle
+    bool stage_iter0 = true;                       // the next stage_linearize is iteration zero (upload, reset, stage_begin_phase)
+    double stage_vals[3] = { 0.0, 0.0, 0.0 };      // ||g||_inf, ||x|| of the last stage_linearize, ||x - candidate|| of the last trial (visfs_ba_stage_ceres_values)
     int fallbacks = 0;                             // solves of this workspace that were re-run on the direct solver
     bool fell_back_last = false;                   // ... the last one was (batch members: read when their statistics are filled)
     // VISFS_BA_GRAPH=1 (measurement): the up-front launch sequence of a solve captured once per resident graph and replayed
@@ -583,6 +586,7 @@ void choose_unit_form(Workspace& w, const visfs_ba_params& prm, const UploadPlan
     w.fused_decide = (sw.decide_fused >= 0 ? sw.decide_fused == 1 : !w.batch_member) && !ceres;
     w.direct_ready = prm.solver == 2 && !ceres && P.Npf >= 1 && !w.small_solve && (P.band_B >= 0 || P.chol_np <= 2048);
     w.solver_now = -1;
+    w.stage_iter0 = true;
 }
 
 int ws_upload(visfs_ba_handle* h, Workspace& w, const visfs_ba_graph* gr, const UploadOpts& opt = UploadOpts()) {
@@ -1843,6 +1847,7 @@ int visfs_ba_graph_reset(visfs_ba_handle* h) {
     launch_reset(h->ws.g, h->ws.g.ceres ? h->prm.iterations : h->prm.iterations / 2, h->prm.trust_region == 1, 1, h->ws.stream);
     HIP_TRY(h, hipGetLastError());
     h->ws.pristine = true;
+    h->ws.stage_iter0 = true;
     return VISFS_BA_OK;
 }
 
@@ -2043,6 +2048,7 @@ int visfs_ba_graph_describe(visfs_ba_handle* h, visfs_ba_graph_info* out) {
     out->n_poses = w.g.Np; out->n_free_poses = w.g.Npf; out->n_points = w.g.Nl; out->n_obs = w.g.No; out->n_odo = w.g.Ne;
     out->n_blk = w.g.n_blk; out->n_pairs = w.n_pairs; out->lanes_per_landmark = w.g.group; out->n_schur_chunks = w.g.n_sch;
     out->schur_runs = w.g.n_runs; out->schur_run_landmarks = w.g.run_lr * w.g.run_m;
+    out->landmark_partials = w.g.n_lin_a;
     out->device_bytes = (int64_t)w.device_bytes;
     out->fused_path = w.fused ? 1 : 0;
     out->band_blocks = (h->prm.solver != 2 && !w.small_solve) ? w.g.band_B : -1;
@@ -2097,11 +2103,74 @@ int visfs_ba_profile_read(visfs_ba_handle* h, visfs_ba_profile* out) {
 // ---------------------------------------------------------------- stage hooks
 int visfs_ba_graph_free_poses(visfs_ba_handle* h) { return (h && h->ws.loaded) ? h->ws.g.Npf : -1; }
 
+// Optimizer/Framework=1: the linearisation and the trial of enqueue_unit for such a handle, launch by launch.  The copy of the graph with
+// `debug` set goes to the kernels that store for the hooks alone (k_linearize, k_dogleg_mid, k_decide); every other launch is the unit's own.
+static int stage_ceres_linearize(visfs_ba_handle* h, double* robust_chi2, double* grad_max) {
+    Workspace& w = h->ws;
+    DeviceGraph g = w.g;
+    g.debug = 1;
+    launch_stage_arm(g, 0.0, MODE_LIN, w.stream, w.stage_iter0 ? 0 : 1);          // (iteration zero: k_linearize / k_ceres_lin_finalize estimate s2l / s2p)
+    launch_linearize(g, w.stream);
+    launch_ceres_lin_finalize(g, w.stream);
+    HIP_TRY(h, hipGetLastError());
+    w.stage_iter0 = false;
+    int rc = ws_read_state(h, w);
+    if (rc != VISFS_BA_OK) return rc;
+    w.stage_vals[0] = w.h_state->max_diag; w.stage_vals[1] = w.h_state->tr_x_norm;   // ||g||_inf, ||x|| as ceres_lin_update received them
+    if (robust_chi2) *robust_chi2 = w.h_state->current_chi;
+    if (grad_max) *grad_max = w.h_state->max_diag;
+    return VISFS_BA_OK;
+}
+
+// lambda: what the gather and the solver damp with (1 / radius, or the dogleg's mu).  out (dogleg only): visfs_ba_stage_dogleg_trial's.
+static int stage_ceres_trial(visfs_ba_handle* h, const double lambda, const double radius, const double mu, double* chi, double* sc, int32_t* solver_ok, double* out) {
+    Workspace& w = h->ws;
+    int rc = ws_read_state(h, w);
+    if (rc != VISFS_BA_OK) return rc;
+    const LmState st0 = *w.h_state;
+    DeviceGraph g = w.g;
+    g.debug = 1;
+    const int solver = h->prm.solver;                                                // (0 for Optimizer/Framework=1: visfs_ba_create)
+    launch_stage_arm(w.g, lambda, MODE_TRIAL, w.stream, 1, radius, mu);
+    launch_schur_partial(w.g, w.stream);
+    if (w.small_solve) launch_small_solve(w.g, solver, w.stream);
+    else {
+        const bool fin_on_board = solver == 2 && w.g.fin_pcg && w.g.pcg1_code != nullptr && !w.g.pcg_cu;
+        if (!fin_on_board && !w.g.fin_arrive) launch_schur_finalize(w.g, w.stream);
+        if (solver == 2) launch_pcg(w.g, w.stream); else launch_direct(w.g, w.stream);
+    }
+    if (w.g.dogleg) { launch_backsub_dogleg(w.g, 1, w.stream); launch_dogleg_mid(g, w.stream); launch_backsub_dogleg(w.g, 2, w.stream); }
+    else launch_backsub(w.g, w.stream);
+    HIP_TRY(h, hipGetLastError());
+    rc = ws_read_state(h, w);                                                        // (ceres_decide clears solver_failed: read it first)
+    if (rc != VISFS_BA_OK) return rc;
+    const int ok = !w.h_state->solver_failed && !w.h_state->pcg_timeout;
+    if (solver_ok) *solver_ok = ok;
+    launch_decide(g, w.stream);
+    HIP_TRY(h, hipGetLastError());
+    rc = ws_read_state(h, w);
+    if (rc != VISFS_BA_OK) return rc;
+    const LmState& st = *w.h_state;
+    w.stage_vals[2] = st.stage_out[6];
+    if (chi) *chi = st.stage_out[4];
+    if (sc) *sc = st.stage_out[5];
+    if (out) {
+        out[0] = st.dl_A; out[1] = st.dl_B; out[2] = st.dl_step_norm; out[3] = st.dl_mcc;
+        for (int q = 0; q < 4; ++q) out[4 + q] = st.stage_out[q];
+        out[8] = 0.5 * st.stage_out[4]; out[9] = st.stage_out[6]; out[10] = ok; out[11] = 0.0;
+    }
+    // undo the decision: the resident estimate, the trust region and the counters are what they were; the candidate stays in the trial buffers
+    *w.h_state = st0;
+    HIP_TRY(h, hipMemcpyAsync(w.g.st, w.h_state, sizeof(LmState), hipMemcpyHostToDevice, w.stream));
+    HIP_TRY(h, hipStreamSynchronize(w.stream));
+    return VISFS_BA_OK;
+}
+
 int visfs_ba_stage_linearize(visfs_ba_handle* h, double* robust_chi2, double* max_diag) {
-    if (h && h->prm.framework != 0) { h->err = "the stage hooks step the g2o branch only (Optimizer/Framework=0)"; return VISFS_BA_ERR_UNSUPPORTED; }
     if (!h) return VISFS_BA_ERR_BAD_ARGUMENT;
     Workspace& w = h->ws;
     if (!w.loaded) { h->err = "no graph resident"; return VISFS_BA_ERR_NOT_LOADED; }
+    if (w.g.ceres) return guarded(h, [&]() -> int { HIP_TRY(h, hipSetDevice(h->device)); return stage_ceres_linearize(h, robust_chi2, max_diag); });
     DeviceGraph g = w.g;
     g.debug = 1;
     launch_stage_arm(g, 0.0, MODE_LIN, w.stream);
@@ -2116,10 +2185,15 @@ int visfs_ba_stage_linearize(visfs_ba_handle* h, double* robust_chi2, double* ma
 }
 
 int visfs_ba_stage_trial(visfs_ba_handle* h, double lambda, double* trial_chi2, double* scale, int32_t* pcg_iterations, int32_t* solver_ok) {
-    if (h && h->prm.framework != 0) { h->err = "the stage hooks step the g2o branch only (Optimizer/Framework=0)"; return VISFS_BA_ERR_UNSUPPORTED; }
     if (!h) return VISFS_BA_ERR_BAD_ARGUMENT;
     Workspace& w = h->ws;
     if (!w.loaded) { h->err = "no graph resident"; return VISFS_BA_ERR_NOT_LOADED; }
+    if (w.g.dogleg) { h->err = "visfs_ba_stage_trial steps LEVENBERG_MARQUARDT; a DOGLEG handle (Optimizer/TrustRegion=1 under Framework=1) is stepped with visfs_ba_stage_dogleg_trial"; return VISFS_BA_ERR_UNSUPPORTED; }
+    if (w.g.ceres) {
+        if (!(lambda > 0.0)) return bad(h, "Optimizer/Framework=1: lambda is 1 / radius and must be positive");
+        if (pcg_iterations) *pcg_iterations = 0;
+        return guarded(h, [&]() -> int { HIP_TRY(h, hipSetDevice(h->device)); return stage_ceres_trial(h, lambda, 1.0 / lambda, -1.0, trial_chi2, scale, solver_ok, nullptr); });
+    }
     int rc = ws_read_state(h, w);
     if (rc != VISFS_BA_OK) return rc;
     const int sel0 = w.h_state->sel;
@@ -2153,6 +2227,25 @@ int visfs_ba_stage_trial(visfs_ba_handle* h, double lambda, double* trial_chi2, 
     return VISFS_BA_OK;
 }
 
+int visfs_ba_stage_dogleg_trial(visfs_ba_handle* h, double radius, double mu, double out[12]) {
+    if (!h || !out) return VISFS_BA_ERR_BAD_ARGUMENT;
+    Workspace& w = h->ws;
+    if (!w.loaded) { h->err = "no graph resident"; return VISFS_BA_ERR_NOT_LOADED; }
+    if (!w.g.ceres) { h->err = "visfs_ba_stage_dogleg_trial: the g2o branch (Optimizer/Framework=0) has no dogleg strategy"; return VISFS_BA_ERR_UNSUPPORTED; }
+    if (!w.g.dogleg) { h->err = "visfs_ba_stage_dogleg_trial: the handle runs LEVENBERG_MARQUARDT (Optimizer/TrustRegion=0): step it with visfs_ba_stage_trial"; return VISFS_BA_ERR_UNSUPPORTED; }
+    if (!(radius > 0.0) || !(mu >= 0.0)) return bad(h, "the radius must be positive and mu not negative");
+    return guarded(h, [&]() -> int { HIP_TRY(h, hipSetDevice(h->device)); return stage_ceres_trial(h, mu, radius, mu, nullptr, nullptr, nullptr, out); });
+}
+
+int visfs_ba_stage_ceres_values(visfs_ba_handle* h, double out[4]) {
+    if (!h || !out) return VISFS_BA_ERR_BAD_ARGUMENT;
+    Workspace& w = h->ws;
+    if (!w.loaded) { h->err = "no graph resident"; return VISFS_BA_ERR_NOT_LOADED; }
+    if (!w.g.ceres) { h->err = "visfs_ba_stage_ceres_values: an Optimizer/Framework=1 handle is needed"; return VISFS_BA_ERR_UNSUPPORTED; }
+    out[0] = w.stage_vals[0]; out[1] = w.stage_vals[1]; out[2] = w.stage_vals[2]; out[3] = 0.0;
+    return VISFS_BA_OK;
+}
+
 static int stage_fetch_impl(visfs_ba_handle* h, int32_t which, double* dst, size_t n_doubles) {
     Workspace& w = h->ws;
     if (!w.loaded) { h->err = "no graph resident"; return VISFS_BA_ERR_NOT_LOADED; }
@@ -2174,6 +2267,8 @@ static int stage_fetch_impl(visfs_ba_handle* h, int32_t which, double* dst, size
         case VISFS_BA_BUF_DX_POSE: src = g.x; m = n6; break;
         case VISFS_BA_BUF_DX_POINT: src = g.dxl; m = (size_t)g.Nl * 3; break;
         case VISFS_BA_BUF_POINT_TRIAL: src = g.pt[sel ^ 1]; m = (size_t)g.Nl * 3; break;
+        case VISFS_BA_BUF_S2P: if (!g.ceres) return bad(h, "the Jacobi scaling exists under Optimizer/Framework=1 only"); src = g.s2p; m = n6; break;
+        case VISFS_BA_BUF_S2L: if (!g.ceres) return bad(h, "the Jacobi scaling exists under Optimizer/Framework=1 only"); src = g.s2l; m = (size_t)g.Nl * 3; break;
         case VISFS_BA_BUF_HPP: case VISFS_BA_BUF_S: m = n6 * n6; break;
         case VISFS_BA_BUF_POSE_TRIAL: m = (size_t)g.Np * 7; break;
         case 101: src = g.pcg_cu ? g.S_rows : nullptr; m = g.pcg_cu ? (size_t)g.pcg_max_row * 6 * g.cu_T : 0; if (!src) return bad(h, "not a k_pcg_cu window"); break;     // diagnostic: S by scalar row
@@ -2234,7 +2329,6 @@ static int stage_fetch_impl(visfs_ba_handle* h, int32_t which, double* dst, size
 // (LinearSolverPCG::init()), run the outlier pass on the committed estimate.
 int visfs_ba_stage_commit(visfs_ba_handle* h) {
     if (!h) return VISFS_BA_ERR_BAD_ARGUMENT;
-    if (h->prm.framework != 0) { h->err = "the stage hooks step the g2o branch only (Optimizer/Framework=0)"; return VISFS_BA_ERR_UNSUPPORTED; }
     return guarded(h, [&]() -> int {
     HIP_TRY(h, hipSetDevice(h->device));          // a process may hold handles on several GPUs
     Workspace& w = h->ws;
@@ -2249,7 +2343,6 @@ int visfs_ba_stage_commit(visfs_ba_handle* h) {
 }
 int visfs_ba_stage_begin_phase(visfs_ba_handle* h) {
     if (!h) return VISFS_BA_ERR_BAD_ARGUMENT;
-    if (h->prm.framework != 0) { h->err = "the stage hooks step the g2o branch only (Optimizer/Framework=0)"; return VISFS_BA_ERR_UNSUPPORTED; }
     return guarded(h, [&]() -> int {
     HIP_TRY(h, hipSetDevice(h->device));          // a process may hold handles on several GPUs
     Workspace& w = h->ws;
@@ -2257,6 +2350,7 @@ int visfs_ba_stage_begin_phase(visfs_ba_handle* h) {
     int rc = ws_read_state(h, w);
     if (rc != VISFS_BA_OK) return rc;
     w.h_state->pcg_residual = -1.0; w.h_state->pcg_res_in = -1.0; w.h_state->status = 0;
+    w.stage_iter0 = true;                         // Optimizer/Framework=1: the next stage_linearize estimates the Jacobi scaling again
     HIP_TRY(h, hipMemcpyAsync(w.g.st, w.h_state, sizeof(LmState), hipMemcpyHostToDevice, w.stream));
     HIP_TRY(h, hipStreamSynchronize(w.stream));
     return (int)VISFS_BA_OK;
@@ -2264,7 +2358,6 @@ int visfs_ba_stage_begin_phase(visfs_ba_handle* h) {
 }
 int visfs_ba_stage_mark_outliers(visfs_ba_handle* h) {
     if (!h) return VISFS_BA_ERR_BAD_ARGUMENT;
-    if (h->prm.framework != 0) { h->err = "the stage hooks step the g2o branch only (Optimizer/Framework=0)"; return VISFS_BA_ERR_UNSUPPORTED; }
     return guarded(h, [&]() -> int {
     HIP_TRY(h, hipSetDevice(h->device));          // a process may hold handles on several GPUs
     Workspace& w = h->ws;

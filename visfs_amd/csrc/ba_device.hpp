@@ -85,6 +85,9 @@ struct LmState {
     int32_t dogleg;
     uint32_t decide_epoch;  // tag of the last k_backsub launch that carried the LM decision; never reset (k_reset leaves it): stale
                             // hand-off words of an earlier launch or solve can then never match the tag a launch waits for
+    // stage hooks on an Optimizer/Framework=1 handle (DeviceGraph::debug set, never in a solve): what k_dogleg_mid summed — ||J v||^2, S1, S2,
+    // S3 — and what ceres_decide received — sum of rho at the candidate, 2 x model cost change, ||x - candidate||
+    double stage_out[8];
 };
 
 // The outputs of a linearisation that the Schur complement and the back-substitution consume.  Two sets: while the LM decision

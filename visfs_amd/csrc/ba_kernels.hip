@@ -657,6 +657,7 @@ __device__ __forceinline__ void ceres_decide_role(const DeviceGraph& g, LmState*
     n2 = block_sum_256(n2, red);
     if (tid != 0) return;
     const bool finite_step = fabs(n2) <= DBL_MAX;                           // IsArrayValid(step)
+    if (g.debug) { st->stage_out[4] = chi; st->stage_out[5] = sc; st->stage_out[6] = sqrt(n2); }   // (stage hooks only)
     ceres_decide(st, ok && finite_step, chi, sc, sqrt(n2));
 }
 
@@ -4361,6 +4362,7 @@ __global__ __launch_bounds__(256) void k_dogleg_mid(const Src src) {
     dogleg_combine(s1, s2, s3, jv, st->tr_radius, st->dl_mu, A, B, norm, mcc);     // (every thread: the same inputs, the same result)
     __syncthreads();
     if (tid == 0) { st->dl_A = A; st->dl_B = B; st->dl_step_norm = norm; st->dl_mcc = mcc; }
+    if (tid == 0 && g.debug) { st->stage_out[0] = jv; st->stage_out[1] = s1; st->stage_out[2] = s2; st->stage_out[3] = s3; }   // (stage hooks only)
     const int sel = st->sel;
     for (int a = tid; a < g.Npf; a += 256) {
         const int ip = g.free_pose[a];
@@ -4526,10 +4528,14 @@ __global__ __launch_bounds__(256) void k_reset(const Src src, const int max_iter
 }
 
 // Test hook: force the gates for a single stage call (visfs_ba_stage_*).
-__global__ void k_stage_arm(const DeviceGraph g, const double lambda, const int mode) {
+// iter: phase_iter of the armed call — 0 arms iteration zero of Optimizer/Framework=1 (the Jacobi scaling is estimated), 1 any other
+// call.  radius > 0 / mu >= 0: the trust-region radius and the dogleg's mu of an Optimizer/Framework=1 trial (left alone otherwise).
+__global__ void k_stage_arm(const DeviceGraph g, const double lambda, const int mode, const int iter, const double radius, const double mu) {
     LmState* st = g.st;
-    st->done = 0; st->mode = mode; st->solver_failed = 0; st->lambda = lambda; st->phase_iter = 1;
+    st->done = 0; st->mode = mode; st->solver_failed = 0; st->lambda = lambda; st->phase_iter = iter;
     st->max_iter = 1 << 30; st->trial_q = 0; st->gauss_newton = 0;
+    if (radius > 0.0) st->tr_radius = radius;
+    if (mu >= 0.0) st->dl_mu = mu;
 }
 
 // ================================================================= fused single-workgroup path (small windows)
@@ -5478,8 +5484,8 @@ void launch_direct(const DeviceGraph& g, hipStream_t s) {
     hipLaunchKernelGGL(k_chol_solve, dim3(1), dim3(1024), 0, s, g);
 }
 
-void launch_stage_arm(const DeviceGraph& g, double lambda, int mode, hipStream_t s) {
-    hipLaunchKernelGGL(k_stage_arm, dim3(1), dim3(1), 0, s, g, lambda, mode);
+void launch_stage_arm(const DeviceGraph& g, double lambda, int mode, hipStream_t s, int iter, double radius, double mu) {
+    hipLaunchKernelGGL(k_stage_arm, dim3(1), dim3(1), 0, s, g, lambda, mode, iter, radius, mu);
 }
 
 // ---- a batch of independent windows (gs: B DeviceGraphs in HBM; d: element-wise maximum of their launch geometry)

@@ -56,7 +56,7 @@ LaunchDims dims_class(const LaunchDims& d);                           // launch 
 bool dims_equal(const LaunchDims& a, const LaunchDims& b);
 void launch_small_optimize_batch(const DeviceGraph* gs, int B, int solver, int half, hipStream_t s);
 void launch_gather_lm(const DeviceGraph* gs, int B, LmState* out, hipStream_t s);
-void launch_stage_arm(const DeviceGraph& g, double lambda, int mode, hipStream_t s);
+void launch_stage_arm(const DeviceGraph& g, double lambda, int mode, hipStream_t s, int iter = 1, double radius = -1.0, double mu = -1.0);
 void launch_eval_mark(const DeviceGraph& g, hipStream_t s);           // stage hook: outlier pass on the committed estimate, ungated
 // marginal covariances (ba_cov.hip): banded factor of S to F ([Npf][band_B + 1][36], fail[0] = 1 on a bad pivot), the band of S^-1 to Sg,
 // the landmark marginals ([Nl][9]) from Sg, H_ll and the H_pl tiles of a `debug` linearisation
