@@ -1,0 +1,431 @@
+// A global occupancy map composed on the GPU from frozen sub-maps (include/visfs_map.h).
+//
+//   k_map_tile     the device-to-device freeze of visfs_map_add_submap: one work item per tile cell reads the sub-map's allocation
+//                  through its GridView (growth offset) and writes the dense [ny][nx] tile with the update marker stripped;
+//   k_map_compose  one work item per output cell, a workgroup of 256 laid out 64 along ix by 4 along iy: a wavefront stores 128
+//                  contiguous bytes of a row, and its reads of a tile run along one line of it.  A workgroup skips every tile whose
+//                  box misses its block (scalars only).  No atomics, no LDS, no workgroup waits for another.
+// A compose is one upload (the tile table), one launch and one wait; the grid and the count plane stay on the device until
+// visfs_map_download or visfs_scan_stack_create_from_map asks for them.  The one-core twin calls the same compose_cell of ba_map.hpp.
+#include "ba_map.hpp"
+#include "ba_scan_stack_access.hpp"
+
+#include <cstring>
+#include <new>
+#include <string>
+#include <vector>
+
+#pragma clang fp contract(off)
+
+using namespace gmap;
+using submap::GridView;
+using submap::Limits;
+
+namespace gmap {
+
+__global__ __launch_bounds__(kThreads) void k_map_tile(GridView g, int32_t nx, int64_t total, uint16_t* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= total) return;
+    const int32_t y = (int32_t)(i / nx), x = (int32_t)(i - (int64_t)y * nx);
+    out[i] = frozen_cell(g, x, y);
+}
+
+// blocks_x: workgroups along ix; the grid is one-dimensional (a tall grid of one column has more rows of blocks than a grid's y
+// dimension may have).
+__global__ __launch_bounds__(kThreads) void k_map_compose(const TileRec* __restrict__ tiles, int32_t nt, const int32_t* __restrict__ L, int32_t combine,
+                                                          double max_x, double max_y, double res, int32_t nx, int32_t ny, int32_t blocks_x,
+                                                          uint16_t* __restrict__ cells, uint8_t* __restrict__ count) {
+    const int32_t b = (int32_t)blockIdx.x;
+    const int32_t by = (b / blocks_x) * kBlockY, bx = (b - (b / blocks_x) * blocks_x) * kBlockX;
+    const int32_t ix = bx + (int32_t)(threadIdx.x & (kBlockX - 1)), iy = by + (int32_t)(threadIdx.x / kBlockX);
+    if (ix >= nx || iy >= ny) return;
+    uint16_t v;
+    uint8_t c;
+    compose_cell(tiles, nt, L, combine, max_x, max_y, res, bx, by, ix, iy, v, c);
+    const int64_t o = (int64_t)iy * nx + ix;
+    cells[o] = v;
+    count[o] = c;
+}
+
+}  // namespace gmap
+
+struct visfs_map {
+    bool device = false;
+    int dev = 0;
+    hipStream_t stream = nullptr;
+    std::string err;
+    struct Tile {
+        PlanTile p;
+        std::vector<uint16_t> h;              // twin
+        uint16_t* d = nullptr;                // device
+    };
+    std::vector<Tile> tiles;
+    int64_t tile_bytes = 0;
+    std::vector<int32_t> L;                   // the log-odds table
+    int32_t* d_L = nullptr;
+    // the last composed grid
+    bool have = false;
+    Limits G;
+    std::vector<uint16_t> h_cells;
+    std::vector<uint8_t> h_count;
+    uint16_t* d_cells = nullptr;
+    uint8_t* d_count = nullptr;
+    size_t out_cap = 0;                       // cells
+    TileRec* h_tab = nullptr;                 // pinned
+    TileRec* d_tab = nullptr;
+    size_t tab_cap = 0;                       // records
+    int32_t launches = 0, copies = 0, waits = 0;
+};
+
+namespace {
+
+int mfail(visfs_map* m, int rc, const std::string& why) { m->err = why; return rc; }
+
+#define GM_HIP(m, expr)                                                                                               \
+    do {                                                                                                              \
+        hipError_t e_ = (expr);                                                                                       \
+        if (e_ != hipSuccess) return mfail((m), VISFS_BA_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+template <class F> int guarded(F&& f) noexcept {
+    try { return f(); }
+    catch (...) { return (int)VISFS_BA_ERR_DEVICE; }
+}
+
+std::vector<int32_t> odds_table() {
+    std::vector<double> cost(kValues);
+    std::vector<int32_t> L(kValues, 0);
+    if (visfs_submap_hook_value_tables(cost.data(), nullptr) != VISFS_BA_OK) throw std::bad_alloc();
+    for (int v = 1; v < kValues; ++v) L[v] = (int32_t)std::llround(std::log((1.0 - cost[v]) / cost[v]) * 1048576.0);
+    return L;
+}
+
+void free_tiles(visfs_map* m) {
+    for (visfs_map::Tile& t : m->tiles) if (t.d) (void)hipFree(t.d);
+    m->tiles.clear();
+    m->tile_bytes = 0;
+}
+
+void map_free(visfs_map* m) {
+    if (m->device) {
+        (void)hipSetDevice(m->dev);
+        if (m->stream) (void)hipStreamSynchronize(m->stream);
+        free_tiles(m);
+        if (m->d_L) (void)hipFree(m->d_L);
+        if (m->d_cells) (void)hipFree(m->d_cells);
+        if (m->d_count) (void)hipFree(m->d_count);
+        if (m->h_tab) (void)hipHostFree(m->h_tab);
+        if (m->d_tab) (void)hipFree(m->d_tab);
+    }
+    delete m;
+}
+
+bool pose_ok(const double p[3]) { return std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]); }
+
+// The checks every new tile passes before anything is allocated or pushed.
+int check_tile(visfs_map* m, const Limits& L, const double pose[3]) {
+    if (!pose_ok(pose)) return mfail(m, VISFS_BA_ERR_BAD_ARGUMENT, "the pose is not finite");
+    if (!limits_ok(L.res, L.max_x, L.max_y, L.nx, L.ny))
+        return mfail(m, VISFS_BA_ERR_BAD_ARGUMENT, "the limits need a positive resolution, a finite corner and at least one cell per axis");
+    if (m->tiles.size() >= (size_t)VISFS_MAP_MAX_TILES) return mfail(m, VISFS_BA_ERR_UNSUPPORTED, "more than 256 tiles");
+    const int64_t bytes = (int64_t)L.nx * L.ny * 2;
+    if (bytes > (int64_t)VISFS_MAP_MAX_TILE_BYTES || m->tile_bytes + bytes > (int64_t)VISFS_MAP_MAX_TILE_BYTES)
+        return mfail(m, VISFS_BA_ERR_UNSUPPORTED, "the tiles together exceed 1 GiB");
+    return VISFS_BA_OK;
+}
+
+// The new tile's cells from `g` (memory of the map's flavour; `staged`: host cells for a device map).
+int push_tile(visfs_map* m, const Limits& L, const double pose[3], const GridView& g, bool staged, int32_t* tile) {
+    visfs_map::Tile t;
+    t.p.L = L;
+    for (int i = 0; i < 3; ++i) t.p.pose[i] = pose[i];
+    const int64_t n = (int64_t)L.nx * L.ny;
+    if (!m->device) {
+        t.h.resize((size_t)n);
+        for (int32_t y = 0; y < L.ny; ++y)
+            for (int32_t x = 0; x < L.nx; ++x) t.h[(size_t)y * L.nx + x] = frozen_cell(g, x, y);
+    } else {
+        GM_HIP(m, hipSetDevice(m->dev));
+        GM_HIP(m, hipMalloc(reinterpret_cast<void**>(&t.d), (size_t)n * 2));
+        auto run = [&]() -> int {
+            if (staged) {
+                std::vector<uint16_t> tmp((size_t)n);
+                for (int32_t y = 0; y < L.ny; ++y)
+                    for (int32_t x = 0; x < L.nx; ++x) tmp[(size_t)y * L.nx + x] = frozen_cell(g, x, y);
+                GM_HIP(m, hipMemcpyAsync(t.d, tmp.data(), (size_t)n * 2, hipMemcpyHostToDevice, m->stream));
+                GM_HIP(m, hipStreamSynchronize(m->stream));
+                return VISFS_BA_OK;
+            }
+            hipLaunchKernelGGL(k_map_tile, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, m->stream, g, L.nx, n, t.d);
+            GM_HIP(m, hipGetLastError());
+            GM_HIP(m, hipStreamSynchronize(m->stream));                     // the sub-map may change or go from here on
+            return VISFS_BA_OK;
+        };
+        const int rc = run();
+        if (rc != VISFS_BA_OK) { (void)hipFree(t.d); return rc; }
+    }
+    m->tile_bytes += n * 2;
+    m->tiles.push_back(std::move(t));
+    if (tile) *tile = (int32_t)m->tiles.size() - 1;
+    return VISFS_BA_OK;
+}
+
+int device_compose(visfs_map* m, const visfs_map_params& p, Plan& P) {
+    const Limits& G = P.G;
+    const size_t cells = (size_t)G.nx * G.ny, nt = P.recs.size(), recs = nt ? nt : 1;
+    GM_HIP(m, hipSetDevice(m->dev));
+    if (m->out_cap < cells) {
+        if (m->d_cells) GM_HIP(m, hipFree(m->d_cells));
+        if (m->d_count) GM_HIP(m, hipFree(m->d_count));
+        m->d_cells = nullptr; m->d_count = nullptr; m->out_cap = 0; m->have = false;       // the old grid went with its buffers
+        GM_HIP(m, hipMalloc(reinterpret_cast<void**>(&m->d_cells), cells * 2));
+        GM_HIP(m, hipMalloc(reinterpret_cast<void**>(&m->d_count), cells));
+        m->out_cap = cells;
+    }
+    if (m->tab_cap < recs) {
+        if (m->h_tab) GM_HIP(m, hipHostFree(m->h_tab));
+        if (m->d_tab) GM_HIP(m, hipFree(m->d_tab));
+        m->h_tab = nullptr; m->d_tab = nullptr; m->tab_cap = 0;
+        const size_t cap = recs < 16 ? 16 : recs;
+        GM_HIP(m, hipHostMalloc(reinterpret_cast<void**>(&m->h_tab), cap * sizeof(TileRec), hipHostMallocDefault));
+        GM_HIP(m, hipMalloc(reinterpret_cast<void**>(&m->d_tab), cap * sizeof(TileRec)));
+        m->tab_cap = cap;
+    }
+    std::memset(m->h_tab, 0, recs * sizeof(TileRec));
+    for (size_t k = 0; k < nt; ++k) { m->h_tab[k] = P.recs[k]; m->h_tab[k].cells = m->tiles[k].d; }
+    m->have = false;                                                       // the grid is being overwritten from here on
+    GM_HIP(m, hipMemcpyAsync(m->d_tab, m->h_tab, recs * sizeof(TileRec), hipMemcpyHostToDevice, m->stream));
+    const int32_t blocks_x = (G.nx + kBlockX - 1) / kBlockX, blocks_y = (G.ny + kBlockY - 1) / kBlockY;
+    hipLaunchKernelGGL(k_map_compose, dim3((unsigned)((int64_t)blocks_x * blocks_y)), dim3(kThreads), 0, m->stream, m->d_tab, (int32_t)nt, m->d_L,
+                       p.combine, G.max_x, G.max_y, G.res, G.nx, G.ny, blocks_x, m->d_cells, m->d_count);
+    GM_HIP(m, hipGetLastError());
+    GM_HIP(m, hipStreamSynchronize(m->stream));
+    m->launches = 1; m->copies = 1; m->waits = 1;
+    return VISFS_BA_OK;
+}
+
+void host_compose(visfs_map* m, const visfs_map_params& p, Plan& P) {
+    const Limits& G = P.G;
+    for (size_t k = 0; k < P.recs.size(); ++k) P.recs[k].cells = m->tiles[k].h.data();
+    m->h_cells.assign((size_t)G.nx * G.ny, 0);
+    m->h_count.assign((size_t)G.nx * G.ny, 0);
+    for (int32_t iy = 0; iy < G.ny; ++iy)
+        for (int32_t ix = 0; ix < G.nx; ++ix) {
+            const size_t o = (size_t)iy * G.nx + ix;
+            compose_cell(P.recs.data(), (int32_t)P.recs.size(), m->L.data(), p.combine, G.max_x, G.max_y, G.res, (ix / kBlockX) * kBlockX,
+                         (iy / kBlockY) * kBlockY, ix, iy, m->h_cells[o], m->h_count[o]);
+        }
+    m->launches = m->copies = m->waits = 0;
+}
+
+Limits limits_of(const visfs_submap_info& l) {
+    Limits L;
+    L.res = l.resolution; L.max_x = l.max_x; L.max_y = l.max_y; L.nx = l.num_x_cells; L.ny = l.num_y_cells;
+    return L;
+}
+
+}  // namespace
+
+// ====================================================================== exported C ABI
+extern "C" {
+
+int visfs_map_abi_version(void) { return VISFS_MAP_ABI_VERSION; }
+
+void visfs_map_default_params(visfs_map_params* p) {
+    if (!p) return;
+    std::memset(p, 0, sizeof *p);
+    p->combine = VISFS_MAP_ODDS;
+    p->resolution = 0.05;
+    p->explicit_limits = 0;
+}
+
+int visfs_map_create(visfs_ba_handle* h, visfs_map** out) {
+    if (!out) return VISFS_BA_ERR_BAD_ARGUMENT;
+    *out = nullptr;
+    return guarded([&]() -> int {
+        visfs_map* m = new visfs_map();
+        m->L = odds_table();
+        if (h) {
+            m->device = true; m->dev = visfs_internal_device(h); m->stream = visfs_internal_stream(h);
+            auto run = [&]() -> int {
+                GM_HIP(m, hipSetDevice(m->dev));
+                GM_HIP(m, hipMalloc(reinterpret_cast<void**>(&m->d_L), kValues * sizeof(int32_t)));
+                GM_HIP(m, hipMemcpyAsync(m->d_L, m->L.data(), kValues * sizeof(int32_t), hipMemcpyHostToDevice, m->stream));
+                GM_HIP(m, hipStreamSynchronize(m->stream));
+                return VISFS_BA_OK;
+            };
+            const int rc = run();
+            if (rc != VISFS_BA_OK) { visfs_internal_set_error(h, m->err.c_str()); map_free(m); return rc; }
+        }
+        *out = m;
+        return (int)VISFS_BA_OK;
+    });
+}
+
+void visfs_map_destroy(visfs_map* m) { if (m) map_free(m); }
+
+const char* visfs_map_last_error(const visfs_map* m) { return m ? m->err.c_str() : "null map"; }
+
+int visfs_map_add_submap(visfs_map* m, visfs_submaps* s, int32_t index, const double pose[3], int32_t* tile) {
+    if (!m || !s || !pose) return VISFS_BA_ERR_BAD_ARGUMENT;
+    return guarded([&]() -> int {
+        submap::ScanAccess acc;
+        int rc = visfs_internal_scan_access(s, index, &acc);               // flushes a staged batch
+        if (rc != VISFS_BA_OK) return mfail(m, rc, std::string("the sub-maps: ") + visfs_submaps_last_error(s));
+        if (acc.device != m->device || (m->device && (acc.dev != m->dev || acc.stream != m->stream)))
+            return mfail(m, VISFS_BA_ERR_BAD_ARGUMENT, "the sub-maps are not of the map's flavour, device and stream");
+        if (index < 0 || index >= acc.count) return mfail(m, VISFS_BA_ERR_BAD_ARGUMENT, "sub-map index out of range");
+        if ((rc = check_tile(m, acc.L, pose)) != VISFS_BA_OK) return rc;
+        return push_tile(m, acc.L, pose, acc.grid, false, tile);
+    });
+}
+
+int visfs_map_add_grid(visfs_map* m, const visfs_submap_info* lim, const uint16_t* cells, const double pose[3], int32_t* tile) {
+    if (!m || !lim || !cells || !pose) return VISFS_BA_ERR_BAD_ARGUMENT;
+    return guarded([&]() -> int {
+        const Limits L = limits_of(*lim);
+        const int rc = check_tile(m, L, pose);
+        if (rc != VISFS_BA_OK) return rc;
+        GridView g;
+        g.cells = cells; g.nx = L.nx; g.ny = L.ny;
+        return push_tile(m, L, pose, g, true, tile);
+    });
+}
+
+int visfs_map_set_poses(visfs_map* m, int32_t first, int32_t count, const double* poses) {
+    if (!m || (count > 0 && !poses)) return VISFS_BA_ERR_BAD_ARGUMENT;
+    return guarded([&]() -> int {
+        if (first < 0 || count < 0 || (int64_t)first + count > (int64_t)m->tiles.size()) return mfail(m, VISFS_BA_ERR_BAD_ARGUMENT, "tile index out of range");
+        for (int32_t i = 0; i < count; ++i) if (!pose_ok(poses + 3 * (size_t)i)) return mfail(m, VISFS_BA_ERR_BAD_ARGUMENT, "a pose is not finite");
+        for (int32_t i = 0; i < count; ++i)
+            for (int k = 0; k < 3; ++k) m->tiles[(size_t)first + i].p.pose[k] = poses[3 * (size_t)i + k];
+        return (int)VISFS_BA_OK;
+    });
+}
+
+int visfs_map_clear(visfs_map* m) {
+    if (!m) return VISFS_BA_ERR_BAD_ARGUMENT;
+    return guarded([&]() -> int {
+        if (m->device) { GM_HIP(m, hipSetDevice(m->dev)); GM_HIP(m, hipStreamSynchronize(m->stream)); }
+        free_tiles(m);
+        return (int)VISFS_BA_OK;
+    });
+}
+
+int visfs_map_describe_tile(const visfs_map* m, int32_t tile, visfs_submap_info* limits, double pose[3]) {
+    if (!m) return VISFS_BA_ERR_BAD_ARGUMENT;
+    if (tile < 0 || (size_t)tile >= m->tiles.size()) return VISFS_BA_ERR_BAD_ARGUMENT;
+    const PlanTile& t = m->tiles[(size_t)tile].p;
+    if (limits) {
+        std::memset(limits, 0, sizeof *limits);
+        limits->resolution = t.L.res; limits->max_x = t.L.max_x; limits->max_y = t.L.max_y; limits->num_x_cells = t.L.nx; limits->num_y_cells = t.L.ny;
+        limits->known_min_x = limits->known_min_y = 1;                     // not tracked: empty
+    }
+    if (pose) for (int k = 0; k < 3; ++k) pose[k] = t.pose[k];
+    return VISFS_BA_OK;
+}
+
+int visfs_map_compose(visfs_map* m, const visfs_map_params* p, visfs_map_info* info) {
+    if (!m || !p) return VISFS_BA_ERR_BAD_ARGUMENT;
+    return guarded([&]() -> int {
+        std::vector<PlanTile> tiles;
+        for (const visfs_map::Tile& t : m->tiles) tiles.push_back(t.p);
+        Plan P;
+        const char* why = "";
+        int rc = make_plan(*p, tiles, P, &why);
+        if (rc != VISFS_BA_OK) return mfail(m, rc, why);
+        if (m->device) { if ((rc = device_compose(m, *p, P)) != VISFS_BA_OK) return rc; }
+        else host_compose(m, *p, P);
+        m->G = P.G; m->have = true;
+        if (info) {
+            fill_info(P, info->limits);
+            info->tiles = (int32_t)tiles.size(); info->tiles_drawn = P.drawn;
+        }
+        return (int)VISFS_BA_OK;
+    });
+}
+
+int visfs_map_download(visfs_map* m, uint16_t* cells, uint8_t* count) {
+    if (!m) return VISFS_BA_ERR_BAD_ARGUMENT;
+    return guarded([&]() -> int {
+        if (!m->have) return mfail(m, VISFS_BA_ERR_BAD_ARGUMENT, "no composed grid: call visfs_map_compose first");
+        const size_t n = (size_t)m->G.nx * m->G.ny;
+        if (!m->device) {
+            if (cells) std::memcpy(cells, m->h_cells.data(), n * 2);
+            if (count) std::memcpy(count, m->h_count.data(), n);
+            return (int)VISFS_BA_OK;
+        }
+        GM_HIP(m, hipSetDevice(m->dev));
+        if (cells) GM_HIP(m, hipMemcpyAsync(cells, m->d_cells, n * 2, hipMemcpyDeviceToHost, m->stream));
+        if (count) GM_HIP(m, hipMemcpyAsync(count, m->d_count, n, hipMemcpyDeviceToHost, m->stream));
+        GM_HIP(m, hipStreamSynchronize(m->stream));
+        return (int)VISFS_BA_OK;
+    });
+}
+
+int visfs_scan_stack_create_from_map(visfs_map* m, int32_t depth, visfs_scan_stack** out) {
+    if (!m || !out) return VISFS_BA_ERR_BAD_ARGUMENT;
+    *out = nullptr;
+    return guarded([&]() -> int {
+        if (depth < 1 || depth > VISFS_SCAN_FAST_MAX_DEPTH) return mfail(m, VISFS_BA_ERR_BAD_ARGUMENT, "the depth must lie in [1, 16]");
+        if (!m->have) return mfail(m, VISFS_BA_ERR_BAD_ARGUMENT, "no composed grid: call visfs_map_compose first");
+        GridView g;
+        g.cells = m->device ? m->d_cells : m->h_cells.data(); g.nx = m->G.nx; g.ny = m->G.ny;
+        std::string why;
+        const int rc = visfs_internal_stack_from_view(m->device, m->dev, m->stream, m->G, g, depth, out, &why);
+        if (rc != VISFS_BA_OK) return mfail(m, rc, why);
+        return (int)VISFS_BA_OK;
+    });
+}
+
+int visfs_map_pose_from_anchor(const double a[3], const double b[3], double out[3]) {
+    if (!a || !b || !out) return VISFS_BA_ERR_BAD_ARGUMENT;
+    if (!pose_ok(a) || !pose_ok(b)) return VISFS_BA_ERR_BAD_ARGUMENT;
+    const double yaw = b[2] - a[2], c = std::cos(yaw), s = std::sin(yaw);
+    out[0] = b[0] - (c * a[0] - s * a[1]);
+    out[1] = b[1] - (s * a[0] + c * a[1]);
+    out[2] = yaw;
+    return VISFS_BA_OK;
+}
+
+int visfs_map_hook_odds_table(int32_t table[32768]) {
+    if (!table) return VISFS_BA_ERR_BAD_ARGUMENT;
+    return guarded([&]() -> int { const std::vector<int32_t> L = odds_table(); std::memcpy(table, L.data(), kValues * sizeof(int32_t)); return (int)VISFS_BA_OK; });
+}
+
+int visfs_map_plan(int32_t n, const visfs_submap_info* tile_limits, const double* poses, const visfs_map_params* p, visfs_submap_info* limits,
+                   int32_t* boxes, int32_t* tiles_drawn) {
+    if (n < 0 || (n > 0 && (!tile_limits || !poses)) || !p) return VISFS_BA_ERR_BAD_ARGUMENT;
+    return guarded([&]() -> int {
+        if (n > VISFS_MAP_MAX_TILES) return (int)VISFS_BA_ERR_UNSUPPORTED;
+        std::vector<PlanTile> tiles((size_t)n);
+        for (int32_t k = 0; k < n; ++k) {
+            tiles[(size_t)k].L = limits_of(tile_limits[k]);
+            const Limits& L = tiles[(size_t)k].L;
+            if (!pose_ok(poses + 3 * (size_t)k) || !limits_ok(L.res, L.max_x, L.max_y, L.nx, L.ny)) return (int)VISFS_BA_ERR_BAD_ARGUMENT;
+            for (int i = 0; i < 3; ++i) tiles[(size_t)k].pose[i] = poses[3 * (size_t)k + i];
+        }
+        Plan P;
+        const char* why = "";
+        const int rc = make_plan(*p, tiles, P, &why);
+        if (rc != VISFS_BA_OK) return rc;
+        if (limits) fill_info(P, *limits);
+        if (boxes)
+            for (int32_t k = 0; k < n; ++k) {
+                const TileRec& r = P.recs[(size_t)k];
+                boxes[4 * k] = r.bx0; boxes[4 * k + 1] = r.by0; boxes[4 * k + 2] = r.bx1; boxes[4 * k + 3] = r.by1;
+            }
+        if (tiles_drawn) *tiles_drawn = P.drawn;
+        return (int)VISFS_BA_OK;
+    });
+}
+
+int visfs_map_last_counts(const visfs_map* m, int32_t* launches, int32_t* copies, int32_t* waits) {
+    if (!m) return VISFS_BA_ERR_BAD_ARGUMENT;
+    if (launches) *launches = m->launches;
+    if (copies) *copies = m->copies;
+    if (waits) *waits = m->waits;
+    return VISFS_BA_OK;
+}
+
+}  // extern "C"

@@ -20,6 +20,7 @@
 // same functions of ba_scan_fast.hpp.  The bodies of the six match kernels, the stack object and the search of one call are in
 // ba_scan_stack.hpp: the group call over several stacks (ba_scan_group.hip) runs the same bodies and the same search.
 #include "ba_scan_stack.hpp"
+#include "ba_scan_stack_access.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -535,3 +536,22 @@ int visfs_scan_stack_match_download(visfs_scan_stack* st, int32_t header[8], int
 }
 
 }  // extern "C"
+
+// ====================================================================== what the global map (ba_map.hip) borrows
+int visfs_internal_stack_from_view(bool device, int dev, hipStream_t stream, const Limits& L, const GridView& g, int32_t depth,
+                                   visfs_scan_stack** out, std::string* err) {
+    *out = nullptr;
+    return guarded([&]() -> int {
+        visfs_scan_stack* st = new visfs_scan_stack();
+        st->device = device; st->dev = dev; st->stream = stream;
+        st->L = L; st->depth = depth;
+        auto run = [&]() -> int {
+            if (device) SF_HIP(st, hipSetDevice(dev));
+            return stack_build(st, g);
+        };
+        const int rc = run();
+        if (rc != VISFS_BA_OK) { if (err) *err = st->err; stack_free(st); return rc; }
+        *out = st;
+        return (int)VISFS_BA_OK;
+    });
+}

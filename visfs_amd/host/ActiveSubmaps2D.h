@@ -7,7 +7,8 @@
 // hand out; download() copies one to the host for those who want grid2Image.  match() is the correlative scan match that
 // Estimator::laserPretreatment names and leaves out (include/visfs_scan_match.h): it corrects a pose guess against a sub-map.
 // freeze() snapshots a sub-map as a VISFS::ScanStack (ScanStack.h) for relocalisation and loop closure.  refine() takes a matched
-// pose off the search lattice (include/visfs_scan_refine.h).
+// pose off the search lattice (include/visfs_scan_refine.h).  addToMap() freezes a sub-map's raw cells as a tile of a
+// VISFS::GlobalMap2D (GlobalMap2D.h), the map drawn from the sub-maps at their corrected poses.
 #ifndef VISFS_AMD_ACTIVE_SUBMAPS_2D_H
 #define VISFS_AMD_ACTIVE_SUBMAPS_2D_H
 
@@ -16,6 +17,7 @@
 #include <string>
 #include <vector>
 
+#include "GlobalMap2D.h"
 #include "ScanStack.h"
 #include "visfs_scan_match.h"
 #include "visfs_submap.h"
@@ -110,6 +112,12 @@ public:
         const int rc = visfs_scan_stack_create(s_, index, depth, &st);
         if (rc != VISFS_BA_OK) throw std::runtime_error("visfs_scan_stack_create failed with status " + std::to_string(rc) + ": " + lastError());
         return ScanStack(st);
+    }
+
+    // Sub-map `index` as it is now becomes the next tile of `map` (GlobalMap2D.h) at `pose` (nullptr: the identity): the way to keep
+    // a finished front sub-map's raw cells, which are dropped with it.  The cells go from device memory to device memory.
+    int addToMap(GlobalMap2D& map, int index = 0, const double pose[3] = nullptr, int* tile = nullptr) const {
+        return map.addSubmap(s_, index, pose, tile);
     }
 
     // one sub-map's cells and float costs on the host ([num_y_cells][num_x_cells])
