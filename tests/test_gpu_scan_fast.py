@@ -203,6 +203,35 @@ def test_overflow_then_a_good_call(shared):
     match_both(sd, sh, over)                                # within the default capacity: everything ties
 
 
+def test_overflow_text_is_the_twin_s(shared):
+    """The device single call runs the group's launch sequence with one member: its text carries no member prefix and nothing of
+    an earlier call."""
+    dev, host, sd, sh = shared
+    over = cases.overflow_case()
+    match_both(sd, sh, BASE[1])
+    texts = []
+    for st in (sd, sh):
+        rc, _ = st.match(over["guess"], over["points"], cases.params(over, frontier_capacity=8))
+        assert rc == abi.ERR_UNSUPPORTED
+        texts.append(st.last_error())
+    assert texts[0] == texts[1] == "frontier overflow at level 2: more than 8 nodes kept"
+
+
+def test_two_stacks_have_their_own_blocks(shared):
+    """A match on stack A, one on stack B with another guess and n, then A's hook: still that of A's call."""
+    dev, host, sd, sh = shared
+    a, b = BASE[0], dict(EDGE["n65"], guess=BASE[3]["guess"])
+    bd, bh = freeze_both(dev, host, b)
+    ra, ha = match_both(sd, sh, a)
+    _, hb = match_both(bd, bh, b)
+    assert (ha["n"], hb["n"]) == (200, 65) and a["guess"] != b["guess"]
+    cases.same_hook(sd.match_download(), sh.match_download())
+    cases.same_hook(sd.match_download(), ha)
+    cases.same_hook(bd.match_download(), hb)
+    bd.close(); bh.close()
+    cases.same_hook(sd.match_download(), ha)                 # B's buffers are gone: A's are its own
+
+
 def test_matches_in_a_row_reuse_and_grow_the_buffers(shared):
     """Different S, L and n on one stack: small, larger in every dimension, small again; a small capacity that holds."""
     dev, host, sd, sh = shared

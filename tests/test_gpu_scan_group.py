@@ -214,3 +214,52 @@ def test_a_single_call_between_two_group_calls(world):
     for i in range(3):
         cases.same_hook(gd.match_download(i), hooks0[i])
     gd.close(); gh.close()
+
+
+def fresh_pair(world, member=0):
+    """A (device stack, host stack) of its own on a member sub-map: the caller closes both."""
+    dev, host, index = world.subs[member]
+    out = []
+    for sub in (dev, host):
+        st = sub.freeze(index, cases.DEPTH)
+        assert st.status == abi.OK, sub.last_error()
+        out.append(st)
+    return out
+
+
+def single_equals_the_twin(sd, sh, case):
+    rc, r, hk = gc.single_call(sd, case["guess"], case["points"], **gc.windows(case))
+    assert rc == abi.OK, sd.last_error()
+    rc, rt, hkt = gc.single_call(sh, case["guess"], case["points"], **gc.windows(case))
+    assert rc == abi.OK, sh.last_error()
+    cases.same_record(r, rt)
+    cases.same_hook(hk, hkt)
+    return r, hk
+
+
+def test_a_single_call_after_its_group_is_gone(world):
+    """The stack's single calls run on its own block: the group's buffers going takes nothing from under them."""
+    case, other = BASE[0], BASE[3]
+    sd, sh = fresh_pair(world)
+    gd, gh = sg.ScanStackGroup([sd]), sg.ScanStackGroup([sh])
+    assert gd.status == gh.status == abi.OK, sg.create_error()
+    same_groups(gd, gh, [case["guess"]], case["points"], **gc.windows(case))
+    gd.close(); gh.close()
+    single_equals_the_twin(sd, sh, other)
+    cases.same_hook(sd.match_download(), sh.match_download())
+    sd.close(); sh.close()
+
+
+def test_a_stack_closed_before_its_group(world):
+    """A single call, a group call, then the stack goes first: the group is only closed afterwards, never used.  The stack's and
+    the group's blocks are apart, so each is freed once."""
+    case, other = BASE[0], BASE[3]
+    sd, sh = fresh_pair(world)
+    gd, gh = sg.ScanStackGroup([sd]), sg.ScanStackGroup([sh])
+    assert gd.status == gh.status == abi.OK, sg.create_error()
+    r, hk = single_equals_the_twin(sd, sh, other)
+    res, status, best = same_groups(gd, gh, [case["guess"]], case["points"], **gc.windows(case))
+    assert status == [abi.OK] and res[0] != r
+    cases.same_hook(sd.match_download(), hk)                               # the group call left the stack's own hook
+    sd.close(); sh.close()
+    gd.close(); gh.close()

@@ -220,3 +220,22 @@ def test_no_points_min_score_limits_and_single_calls_in_between(trio):
         cases.same_record(res1[i], res0[i])
         cases.same_hook(g.match_download(i), hooks0[i])
     cases.same_hook(stacks[1].match_download(), hk_single)
+
+
+def test_the_members_times_capacity_limit_is_the_group_s_alone():
+    """frontier_capacity = 2^26 is a single call's own limit and is accepted there; a group of two refuses it."""
+    case = BASE[0]
+    st = stacks_of([case])[0]
+    kw = windows(case, frontier_capacity=sg.MAX_FRONTIER)
+    assert sg.MAX_FRONTIER == sf.MAX_FRONTIER == 2 ** 26
+    rc, r, hk = single_call(st, case["guess"], case["points"], **kw)
+    assert rc == abi.OK, st.last_error()
+    rc, r0, hk0 = single_call(st, case["guess"], case["points"], **windows(case))
+    assert rc == abi.OK
+    cases.same_record(r, r0)
+    cases.same_hook(hk, hk0)
+    g = sg.ScanStackGroup([st, st])
+    assert g.status == abi.OK
+    assert g.match([case["guess"]] * 2, case["points"], **kw) == (None, None, None)
+    assert g.rc == abi.ERR_UNSUPPORTED and g.last_error() == "members times frontier_capacity exceed 2^26"
+    g.close()

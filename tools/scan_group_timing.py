@@ -10,8 +10,19 @@ Nothing is reported unless every member's record and hook data (B, per-level cou
 call's.  Writes one JSON line per workload: the times of both sides, and the launches, copies and waits the group counted.
 
     python tools/scan_group_timing.py [--repeats 20] [--out profiles/scan_group_timing.log]
+
+--single-ab compares the single call of this tree's library with that of the library VISFS_BA_PARENT_LIB names (the parent commit's
+build, see tools/build_variant.sh) on `room` and `hall`, each with one member: --children children per library and workload, each
+loading one library through VISFS_BA_LIB, interleaved (parent, here, parent, ...); the first child that fails ends the run.  The
+`single_calls` medians of the children are compared; the yardstick is the parent's own spread (max - min of its children's medians
+on that workload).  The single call's record and hook arrays go into a digest, which must be the same in every child of both
+libraries.
+
+    VISFS_BA_PARENT_LIB=visfs_amd/lib/libvisfs_ba_hip_parent.so python tools/scan_group_timing.py --single-ab [--children 5]
+                                                                        [--out profiles/scan_single_timing.log]
 """
 import argparse
+import hashlib
 import json
 import os
 import subprocess
@@ -27,6 +38,7 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 DEPTH = 7
 WORKLOADS = [("room", 1), ("room", 4), ("room", 16), ("room", 64), ("hall", 4)]
+AB_WORKLOADS = [("room", 1), ("hall", 1)]
 
 
 def stats(ts):
@@ -37,6 +49,17 @@ def stats(ts):
 def same_hook(a, b):
     return ((a["S"], a["L"], a["n"], a["H"], a["B"], a["scored"], a["kept"]) == (b["S"], b["L"], b["n"], b["H"], b["B"], b["scored"], b["kept"])
             and a["bounds"].tobytes() == b["bounds"].tobytes() and a["survivors"].tobytes() == b["survivors"].tobytes())
+
+
+def single_digest(rs, stacks):
+    """The single calls' records and hook arrays, as bytes."""
+    h = hashlib.sha256()
+    for r, st in zip(rs, stacks):
+        hk = st.match_download()
+        h.update(json.dumps({k: (np.float64(v).tobytes().hex() if isinstance(v, float) else v) for k, v in r.items()}, sort_keys=True).encode())
+        h.update(json.dumps([hk[k] for k in ("S", "L", "n", "H", "B", "scored", "kept")]).encode())
+        h.update(hk["bounds"].tobytes()); h.update(hk["survivors"].tobytes())
+    return h.hexdigest()
 
 
 def child(name, m, repeats):
@@ -96,7 +119,7 @@ def child(name, m, repeats):
     out.update(num_scans=rg[0]["num_scans"], num_linear=rg[0]["num_linear"], H=H, identical=True, best_member=best,
                scored_member0=hk["scored"], kept_member0=hk["kept"], group_counts=group.last_counts(),
                single_counts=dict(kernel_launches=m * (H + 5), copies_and_memsets=2 * m, synchronisations=m),
-               group_call=stats(t_group), single_calls=stats(t_single))
+               group_call=stats(t_group), single_calls=stats(t_single), single_digest=single_digest(rs, stacks))
     print(json.dumps(out))
     group.close()
     for st in stacks:
@@ -105,23 +128,79 @@ def child(name, m, repeats):
     return 0
 
 
+def run_child(name, m, repeats, lib=None):
+    """One measuring child under its time limit; anything but success ends the run, and nothing more is started."""
+    env = dict(os.environ)
+    if lib:
+        env["VISFS_BA_LIB"] = lib
+    else:
+        env.pop("VISFS_BA_LIB", None)
+    res = subprocess.run(["timeout", "-k", "10", "240", sys.executable, os.path.abspath(__file__), "--child", name, "--members", str(m),
+                          "--repeats", str(repeats)], capture_output=True, text=True, env=env)
+    if res.returncode != 0:
+        sys.stderr.write(res.stdout + res.stderr)
+        sys.exit(f"workload {name} m = {m} ({lib or 'the library of this tree'}) ended with status {res.returncode}: nothing reported")
+    return res.stdout.strip().splitlines()[-1]
+
+
+def single_ab(children, repeats, out_path):
+    parent = os.environ.get("VISFS_BA_PARENT_LIB")
+    if not parent:
+        sys.exit("--single-ab needs VISFS_BA_PARENT_LIB: the parent commit's library (tools/build_variant.sh)")
+    parent = os.path.abspath(parent)
+    libs = [("parent", parent), ("here", None)]
+    lines = [f"scan_single_timing: visfs_scan_stack_match on a device stack of depth {DEPTH}, ms per call up to its return; per child the median of "
+             f"{repeats} timed calls after 2 warm-ups; {children} children per library and workload, interleaved; parent: "
+             f"{os.path.relpath(parent, ROOT)}, here: the library of this tree"]
+    rows, ok = [], True
+    for name, m in AB_WORKLOADS:
+        runs = {k: [] for k, _ in libs}
+        for _ in range(children):
+            for k, lib in libs:
+                runs[k].append(json.loads(run_child(name, m, repeats, lib)))
+        digests = {r["single_digest"] for rs in runs.values() for r in rs}
+        if len(digests) != 1:
+            sys.exit(f"{name} m = {m}: the single call's record and hook arrays differ between the libraries: {sorted(digests)}")
+        med = {k: [r["single_calls"]["median_ms"] / m for r in rs] for k, rs in runs.items()}
+        a, b = float(np.median(med["parent"])), float(np.median(med["here"]))
+        spread = max(med["parent"]) - min(med["parent"])
+        inside = b - a <= spread
+        ok = ok and inside
+        r0 = runs["here"][0]
+        lines.append(f"{name} m = {m}  n = {r0['points']}, S = {r0['num_scans']}, nl = {r0['num_linear']}, H = {r0['H']}; record and hook digest "
+                     f"{digests.pop()[:16]} in all {2 * children} children")
+        for k, _ in libs:
+            lines.append(f"        {k:<7} medians {[round(v, 4) for v in med[k]]}  median {float(np.median(med[k])):.4f} ms  "
+                         f"min {min(r['single_calls']['min_ms'] for r in runs[k]) / m:.4f}  max {max(r['single_calls']['max_ms'] for r in runs[k]) / m:.4f}")
+        lines.append(f"        here - parent = {b - a:+.4f} ms ({(b - a) / a * 100.0:+.1f} %); the parent's own spread is {spread:.4f} ms: "
+                     f"{'inside' if inside else 'OUTSIDE'}")
+        rows.append(dict(workload=name, members=m, parent_ms=med["parent"], here_ms=med["here"], parent_median_ms=a, here_median_ms=b,
+                         parent_spread_ms=spread, inside=inside))
+    lines.append(json.dumps(dict(tool="scan_group_timing --single-ab", children=children, repeats=repeats, rows=rows)))
+    text = "\n".join(lines)
+    print(text)
+    if out_path:
+        with open(out_path, "w") as fh:
+            fh.write(text + "\n")
+    return 0 if ok else 3
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=20)
     ap.add_argument("--out", default=None)
     ap.add_argument("--child", default=None)
     ap.add_argument("--members", type=int, default=1)
+    ap.add_argument("--single-ab", action="store_true", help="the single call here against VISFS_BA_PARENT_LIB's")
+    ap.add_argument("--children", type=int, default=5)
     a = ap.parse_args()
     if a.child:
         sys.exit(child(a.child, a.members, a.repeats))
+    if a.single_ab:
+        sys.exit(single_ab(a.children, a.repeats, a.out))
     lines = []
     for name, m in WORKLOADS:
-        res = subprocess.run(["timeout", "-k", "10", "240", sys.executable, os.path.abspath(__file__), "--child", name, "--members", str(m),
-                              "--repeats", str(a.repeats)], capture_output=True, text=True)
-        if res.returncode != 0:
-            sys.stderr.write(res.stdout + res.stderr)
-            sys.exit(f"workload {name} m = {m} ended with status {res.returncode}: nothing reported")      # and nothing more is started
-        lines.append(res.stdout.strip().splitlines()[-1])
+        lines.append(run_child(name, m, a.repeats, os.environ.get("VISFS_BA_LIB")))
         print(lines[-1], flush=True)
     if a.out:
         with open(a.out, "w") as fh:

@@ -4,21 +4,14 @@
 // extension (ba_scan_fast.hpp).  Building it is one launch per level:
 //   k_fast_base    P_0 from the grid's cells (through the GridView's offsets), one work item per cell;
 //   k_fast_up      P_h from P_(h-1), one work item per stored cell.
-// A match is one upload (points, rotation table), H + 5 launches on the stack's stream whatever the data, one download (the Ctrl
-// record) and one wait; nothing is read back between levels, the frontier counts live in the Ctrl record on the device:
-//   k_fast_cells   the discretised cells [S][n] (scan::discretise), and the Ctrl record zeroed;
-//   k_fast_bounds  the bound of every level-H node, one wavefront per node, lanes along the points;
-//   k_fast_seeds   one workgroup per scan: its best level-H node, then H greedy steps, its four wavefronts scoring the four
-//                  children of a step; the leaf's sum joins the incumbent B through an integer atomic maximum;
-//   k_fast_keep    the level-H nodes with U >= B appended to the frontier;
-//   k_fast_level   for h = H .. 1: a fixed grid of wavefronts strides over the frontier of level h (its length read on the
-//                  device), scores the up-to-four in-window children of a node from one pass over the scan's cells, and appends
-//                  those with U >= B to the frontier of level h - 1 through an integer atomic counter; entries beyond the capacity
-//                  are dropped and the overflow flag is raised;
-//   k_fast_best    one workgroup selects the winner among the level-0 survivors: Q descending, index ascending.
-// All sums are int32, so no reduction or append order can show in a result.  The one-core twin runs the same schedule through the
-// same functions of ba_scan_fast.hpp.  The bodies of the six match kernels, the stack object and the search of one call are in
-// ba_scan_stack.hpp: the group call over several stacks (ba_scan_group.hip) runs the same bodies and the same search.
+// A match on a device stack is a scan group of one: visfs_scan_stack_match checks the call, makes its search and runs the one launch
+// sequence there is (device_run, ba_scan_group.hip) with m = 1 on the stack's own call block: one upload (points, rotation table,
+// a member table of one), H + 5 launches on the stack's stream whatever the data, one download (the Ctrl record) and one wait.  What
+// is the single call's own is its reading of that record: an overflow or an empty result fails the call under the single call's
+// texts and leaves the hook's arenas and the last record as they were.  All sums are int32, so no reduction or append order can
+// show in a result.  The one-core twin (host_search) runs the same schedule through the same functions of ba_scan_fast.hpp.  The
+// stack object, the search of one call, the call block and the kernels' bodies are in ba_scan_stack.hpp; this file defines the host
+// functions declared there, the launch sequence excepted.
 #include "ba_scan_stack.hpp"
 #include "ba_scan_stack_access.hpp"
 
@@ -52,37 +45,6 @@ __global__ __launch_bounds__(kThreads) void k_fast_up(LevelView lo, int32_t w, i
     out[i] = level_up(lo, e_hi, half, sx, sy);
 }
 
-__global__ __launch_bounds__(kThreads) void k_fast_cells(const double* __restrict__ pts, const double* __restrict__ rot, int32_t n, int64_t total,
-                                                         double gx, double gy, double res, double max_x, double max_y, int2* __restrict__ cells,
-                                                         Ctrl* __restrict__ ctrl) {
-    cells_body(pts, rot, n, total, gx, gy, res, max_x, max_y, cells, ctrl);
-}
-
-__global__ __launch_bounds__(kThreads) void k_fast_bounds(const int2* __restrict__ cells, int32_t n, LevelView vH, int32_t nl, int32_t H, int32_t mH,
-                                                          int32_t total, int32_t* __restrict__ bounds) {
-    bounds_body(cells, n, vH, nl, H, mH, total, bounds);
-}
-
-__global__ __launch_bounds__(kThreads) void k_fast_seeds(const int32_t* __restrict__ bounds, const int2* __restrict__ cells, int32_t n, Levels lv,
-                                                         int32_t nl, int32_t L, int32_t H, int32_t mH, Ctrl* __restrict__ ctrl) {
-    seeds_body(bounds, cells, n, lv, nl, L, H, mH, ctrl);
-}
-
-__global__ __launch_bounds__(kThreads) void k_fast_keep(const int32_t* __restrict__ bounds, int32_t total, int32_t H, int2* __restrict__ out, int32_t cap,
-                                                        Ctrl* __restrict__ ctrl) {
-    keep_body(bounds, total, H, out, cap, ctrl);
-}
-
-__global__ __launch_bounds__(kThreads) void k_fast_level(int32_t h, const int2* __restrict__ in, int2* __restrict__ out, int32_t cap,
-                                                         const int2* __restrict__ cells, int32_t n, LevelView lo, int32_t nl, int32_t L,
-                                                         Ctrl* __restrict__ ctrl) {
-    level_body(h, in, out, cap, cells, n, lo, nl, L, ctrl);
-}
-
-__global__ __launch_bounds__(kThreads) void k_fast_best(const int2* __restrict__ in, int32_t cap, Ctrl* __restrict__ ctrl) {
-    best_body(in, cap, ctrl);
-}
-
 }  // namespace scanfast
 
 // ---------------------------------------------------------------- the stack object
@@ -90,35 +52,12 @@ namespace {
 
 int sfail(visfs_scan_stack* st, int rc, const std::string& why) { st->err = why; return rc; }
 
-#define SF_HIP(st, expr)                                                                                              \
-    do {                                                                                                              \
-        hipError_t e_ = (expr);                                                                                       \
-        if (e_ != hipSuccess) return sfail((st), VISFS_BA_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-unsigned blocks_for(int64_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
-
-template <class T> int grow(visfs_scan_stack* st, T** p, size_t* cap, size_t need) {
-    if (*cap >= need) return VISFS_BA_OK;
-    if (*p) SF_HIP(st, hipFree(*p));
-    *p = nullptr; *cap = 0;
-    SF_HIP(st, hipMalloc(reinterpret_cast<void**>(p), need * sizeof(T)));
-    *cap = need;
-    return VISFS_BA_OK;
-}
-
 void stack_free(visfs_scan_stack* st) {
     if (st->device) {
         (void)hipSetDevice(st->dev);
         if (st->stream) (void)hipStreamSynchronize(st->stream);
         if (st->d_mem) (void)hipFree(st->d_mem);
-        if (st->h_up) (void)hipHostFree(st->h_up);
-        if (st->d_up) (void)hipFree(st->d_up);
-        if (st->d_cells) (void)hipFree(st->d_cells);
-        if (st->d_ctrl) (void)hipFree(st->d_ctrl);
-        if (st->h_ctrl) (void)hipHostFree(st->h_ctrl);
-        for (Bounds& b : st->bnd) if (b.p) (void)hipFree(b.p);
-        for (Frontier& f : st->fr) if (f.p) (void)hipFree(f.p);
+        block_free(st->blk);
     }
     scanrefine::state_free(st->refine);
     delete st;
@@ -158,21 +97,21 @@ int stack_build(visfs_scan_stack* st, const GridView& g) {
         return VISFS_BA_OK;
     }
     int cus = 0;
-    SF_HIP(st, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, st->dev));
+    SCAN_HIP(st->err, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, st->dev));
     st->blocks = std::max(1, cus) * 8;
-    SF_HIP(st, hipMalloc(reinterpret_cast<void**>(&st->d_mem), items * 2));
+    SCAN_HIP(st->err, hipMalloc(reinterpret_cast<void**>(&st->d_mem), items * 2));
     for (int32_t h = 0; h < st->depth; ++h) st->lv.v[h].p = st->d_mem + st->off[h];
     const int64_t n0 = (int64_t)st->L.nx * st->L.ny;
     hipLaunchKernelGGL(k_fast_base, dim3(blocks_for(n0)), dim3(kThreads), 0, st->stream, g, st->L.nx, n0, st->d_mem);
-    SF_HIP(st, hipGetLastError());
+    SCAN_HIP(st->err, hipGetLastError());
     for (int32_t h = 1; h < st->depth; ++h) {
         const LevelView& hi = st->lv.v[h];
         const int64_t nh = (int64_t)hi.w * hi.ht;
         hipLaunchKernelGGL(k_fast_up, dim3(blocks_for(nh)), dim3(kThreads), 0, st->stream, st->lv.v[h - 1], hi.w, hi.e, 1 << (h - 1), nh,
                            st->d_mem + st->off[h]);
-        SF_HIP(st, hipGetLastError());
+        SCAN_HIP(st->err, hipGetLastError());
     }
-    SF_HIP(st, hipStreamSynchronize(st->stream));                          // the source grid may change or go from here on
+    SCAN_HIP(st->err, hipStreamSynchronize(st->stream));                          // the source grid may change or go from here on
     return VISFS_BA_OK;
 }
 
@@ -306,6 +245,49 @@ int host_search(const Levels& lv, const Search& s, Last& now, std::string& why) 
     return VISFS_BA_OK;
 }
 
+void block_free(CallBlock& b) {
+    if (b.h_up) (void)hipHostFree(b.h_up);
+    if (b.d_up) (void)hipFree(b.d_up);
+    if (b.d_cells) (void)hipFree(b.d_cells);
+    if (b.d_ctrl) (void)hipFree(b.d_ctrl);
+    if (b.h_ctrl) (void)hipHostFree(b.h_ctrl);
+    for (Bounds& x : b.bnd) if (x.p) (void)hipFree(x.p);
+    for (Frontier& f : b.fr) if (f.p) (void)hipFree(f.p);
+    b = CallBlock();
+}
+
+Last device_last(const Search& s, const Ctrl& c) {
+    Last l;
+    l.have = true; l.S = s.P.S; l.L = s.P.Lw; l.n = s.P.n; l.H = s.H; l.mH = s.mH; l.survivors = c.kept[0]; l.c = c;
+    return l;
+}
+
+int match_download(bool device, int dev, hipStream_t stream, const CallBlock& b, int64_t member, const Last& l, std::string& why, int32_t header[8],
+                   int32_t scored[16], int32_t kept[16], int64_t bounds_cap, int32_t* bounds, int64_t survivors_cap, int32_t* survivors) {
+    std::memset(header, 0, 8 * sizeof(int32_t));
+    if (!l.have) return VISFS_BA_OK;
+    const int32_t per = l.mH * l.mH;
+    const int64_t nb = (int64_t)l.S * per;
+    header[0] = l.S; header[1] = l.L; header[2] = l.n; header[3] = l.H; header[4] = per; header[5] = l.survivors; header[6] = l.c.B;
+    if (scored) std::memcpy(scored, l.c.scored, sizeof l.c.scored);
+    if (kept) std::memcpy(kept, l.c.kept, sizeof l.c.kept);
+    if ((bounds && bounds_cap < nb) || (survivors && survivors_cap < l.survivors)) { why = "the hook's arrays are too small"; return VISFS_BA_ERR_BAD_ARGUMENT; }
+    if (!device) {
+        if (bounds) std::memcpy(bounds, l.bounds.data(), (size_t)nb * sizeof(int32_t));
+        if (survivors) std::memcpy(survivors, l.surv.data(), (size_t)l.survivors * sizeof(int2));
+        return VISFS_BA_OK;
+    }
+    SCAN_HIP(why, hipSetDevice(dev));
+    if (bounds) SCAN_HIP(why, hipMemcpyAsync(bounds, b.bnd[1].p + member * b.top, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    if (survivors) SCAN_HIP(why, hipMemcpyAsync(survivors, b.fr[2].p + member * b.cap, (size_t)l.survivors * sizeof(int2), hipMemcpyDeviceToHost, stream));
+    SCAN_HIP(why, hipStreamSynchronize(stream));
+    if (survivors) {                                                       // the device appends unordered
+        int2* sv = reinterpret_cast<int2*>(survivors);
+        std::sort(sv, sv + l.survivors, [](const int2& u, const int2& v) { return u.x < v.x; });
+    }
+    return VISFS_BA_OK;
+}
+
 }  // namespace scanfast
 
 namespace {
@@ -318,74 +300,6 @@ int host_match(visfs_scan_stack* st, Search& s, const visfs_scan_stack_params& p
     finish(s, p, now.c.best_index, now.c.best_sum, out);
     st->last = std::move(now);
     return VISFS_BA_OK;
-}
-
-int device_match(visfs_scan_stack* st, Search& s, const visfs_scan_stack_params& p, visfs_scan_stack_result* out) {
-    const Plan& P = s.P;
-    const int32_t n = P.n, nl = P.nl, L = P.Lw, H = s.H, mH = s.mH, total = s.top();
-    SF_HIP(st, hipSetDevice(st->dev));
-    const size_t npts = 2 * (size_t)n, nrot = 2 * (size_t)P.S, bytes = (npts + nrot) * sizeof(double);
-    if (st->up_cap < bytes) {
-        if (st->h_up) SF_HIP(st, hipHostFree(st->h_up));
-        if (st->d_up) SF_HIP(st, hipFree(st->d_up));
-        st->h_up = st->d_up = nullptr; st->up_cap = 0;
-        const size_t cap = bytes + bytes / 2;
-        SF_HIP(st, hipHostMalloc(reinterpret_cast<void**>(&st->h_up), cap, hipHostMallocDefault));
-        SF_HIP(st, hipMalloc(reinterpret_cast<void**>(&st->d_up), cap));
-        st->up_cap = cap;
-    }
-    if (!st->d_ctrl) {
-        SF_HIP(st, hipMalloc(reinterpret_cast<void**>(&st->d_ctrl), sizeof(Ctrl)));
-        SF_HIP(st, hipHostMalloc(reinterpret_cast<void**>(&st->h_ctrl), sizeof(Ctrl), hipHostMallocDefault));
-    }
-    int rc;
-    if ((rc = grow(st, &st->d_cells, &st->cells_cap, (size_t)P.S * n)) != VISFS_BA_OK) return rc;
-    if ((rc = grow(st, &st->bnd[0].p, &st->bnd[0].cap, (size_t)total)) != VISFS_BA_OK) return rc;
-    for (int f = 0; f < 2; ++f)
-        if ((rc = grow(st, &st->fr[f].p, &st->fr[f].cap, (size_t)s.cap)) != VISFS_BA_OK) return rc;
-    double* hup = reinterpret_cast<double*>(st->h_up);
-    std::memcpy(hup, P.pts.data(), npts * sizeof(double));
-    std::memcpy(hup + npts, P.rot.data(), nrot * sizeof(double));
-    SF_HIP(st, hipMemcpyAsync(st->d_up, st->h_up, bytes, hipMemcpyHostToDevice, st->stream));
-    const double* d = reinterpret_cast<const double*>(st->d_up);
-    const int64_t ncell = (int64_t)P.S * n;
-    const dim3 fixed(st->blocks), wg(kThreads);
-    hipLaunchKernelGGL(k_fast_cells, dim3(blocks_for(ncell)), wg, 0, st->stream, d, d + npts, n, ncell, P.gx, P.gy, P.L.res, P.L.max_x, P.L.max_y,
-                       st->d_cells, st->d_ctrl);
-    SF_HIP(st, hipGetLastError());
-    hipLaunchKernelGGL(k_fast_bounds, fixed, wg, 0, st->stream, st->d_cells, n, st->lv.v[H], nl, H, mH, total, st->bnd[0].p);
-    SF_HIP(st, hipGetLastError());
-    hipLaunchKernelGGL(k_fast_seeds, dim3(P.S), wg, 0, st->stream, st->bnd[0].p, st->d_cells, n, st->lv, nl, L, H, mH, st->d_ctrl);
-    SF_HIP(st, hipGetLastError());
-    int cur = 0;                                                           // the frontier of the level in work: fr[cur]
-    hipLaunchKernelGGL(k_fast_keep, fixed, wg, 0, st->stream, st->bnd[0].p, total, H, st->fr[cur].p, s.cap, st->d_ctrl);
-    SF_HIP(st, hipGetLastError());
-    for (int32_t h = H; h >= 1; --h) {
-        hipLaunchKernelGGL(k_fast_level, fixed, wg, 0, st->stream, h, st->fr[cur].p, st->fr[1 - cur].p, s.cap, st->d_cells, n, st->lv.v[h - 1], nl, L,
-                           st->d_ctrl);
-        SF_HIP(st, hipGetLastError());
-        cur = 1 - cur;
-    }
-    hipLaunchKernelGGL(k_fast_best, dim3(1), wg, 0, st->stream, st->fr[cur].p, s.cap, st->d_ctrl);
-    SF_HIP(st, hipGetLastError());
-    SF_HIP(st, hipMemcpyAsync(st->h_ctrl, st->d_ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, st->stream));
-    SF_HIP(st, hipStreamSynchronize(st->stream));
-    const Ctrl c = *st->h_ctrl;
-    if (c.overflow) return sfail(st, VISFS_BA_ERR_UNSUPPORTED, overflow_text(c.overflow - 1, s.cap));
-    if (c.best_index < 0 || (int64_t)c.best_index >= P.candidates()) return sfail(st, VISFS_BA_ERR_DEVICE, "the search returned no candidate");
-    // the hook's buffers change hands: what this call wrote stays until the next successful call
-    std::swap(st->bnd[0], st->bnd[1]);
-    std::swap(st->fr[cur], st->fr[2]);
-    Last now;
-    now.have = true; now.S = P.S; now.L = L; now.n = n; now.H = H; now.mH = mH; now.survivors = c.kept[0]; now.c = c;
-    finish(s, p, c.best_index, c.best_sum, out);
-    st->last = std::move(now);
-    return VISFS_BA_OK;
-}
-
-template <class F> int guarded(F&& f) noexcept {
-    try { return f(); }
-    catch (...) { return (int)VISFS_BA_ERR_DEVICE; }
 }
 
 int check_depth(int32_t depth) { return depth >= 1 && depth <= kMaxDepth; }
@@ -446,9 +360,9 @@ int visfs_scan_stack_create_from_grid(visfs_ba_handle* h, const visfs_submap_inf
             uint16_t* tmp = nullptr;
             auto run = [&]() -> int {
                 const size_t nb = (size_t)g.nx * g.ny * 2;
-                SF_HIP(st, hipSetDevice(st->dev));
-                SF_HIP(st, hipMalloc(reinterpret_cast<void**>(&tmp), nb));
-                SF_HIP(st, hipMemcpyAsync(tmp, cells, nb, hipMemcpyHostToDevice, st->stream));
+                SCAN_HIP(st->err, hipSetDevice(st->dev));
+                SCAN_HIP(st->err, hipMalloc(reinterpret_cast<void**>(&tmp), nb));
+                SCAN_HIP(st->err, hipMemcpyAsync(tmp, cells, nb, hipMemcpyHostToDevice, st->stream));
                 g.cells = tmp;
                 return stack_build(st, g);                                 // ends with a wait on the stream
             };
@@ -484,7 +398,17 @@ int visfs_scan_stack_match(visfs_scan_stack* st, const visfs_scan_stack_params* 
         Search s;
         rc = make_search(st, *p, g, n, xyz, s, &why);
         if (rc != VISFS_BA_OK) return sfail(st, rc, why);
-        return st->device ? device_match(st, s, *p, out) : host_match(st, s, *p, out);
+        if (!st->device) return host_match(st, s, *p, out);
+        int cur = 0;
+        rc = device_run(st->blk, st->dev, st->stream, st->blocks, 1, &st, &s, &cur, st->err);
+        if (rc != VISFS_BA_OK) return rc;
+        const Ctrl& c = st->blk.h_ctrl[0];
+        if (c.overflow) return sfail(st, VISFS_BA_ERR_UNSUPPORTED, overflow_text(c.overflow - 1, s.cap));
+        if (c.best_index < 0 || (int64_t)c.best_index >= s.P.candidates()) return sfail(st, VISFS_BA_ERR_DEVICE, "the search returned no candidate");
+        st->blk.hand_over(cur, s);                                         // only now: a failed call leaves the hook's arenas and `last`
+        finish(s, *p, c.best_index, c.best_sum, out);
+        st->last = device_last(s, c);
+        return (int)VISFS_BA_OK;
     });
 }
 
@@ -498,9 +422,9 @@ int visfs_scan_stack_download_level(visfs_scan_stack* st, int32_t h, int64_t cap
         const int64_t items = (int64_t)v.w * v.ht;
         if (cap < items) return sfail(st, VISFS_BA_ERR_BAD_ARGUMENT, "the hook's array is too small");
         if (!st->device) { std::memcpy(out, v.p, (size_t)items * 2); return (int)VISFS_BA_OK; }
-        SF_HIP(st, hipSetDevice(st->dev));
-        SF_HIP(st, hipMemcpyAsync(out, v.p, (size_t)items * 2, hipMemcpyDeviceToHost, st->stream));
-        SF_HIP(st, hipStreamSynchronize(st->stream));
+        SCAN_HIP(st->err, hipSetDevice(st->dev));
+        SCAN_HIP(st->err, hipMemcpyAsync(out, v.p, (size_t)items * 2, hipMemcpyDeviceToHost, st->stream));
+        SCAN_HIP(st->err, hipStreamSynchronize(st->stream));
         return (int)VISFS_BA_OK;
     });
 }
@@ -509,29 +433,8 @@ int visfs_scan_stack_match_download(visfs_scan_stack* st, int32_t header[8], int
                                     int32_t* bounds, int64_t survivors_cap, int32_t* survivors) {
     if (!st || !header || bounds_cap < 0 || survivors_cap < 0) return VISFS_BA_ERR_BAD_ARGUMENT;
     return guarded([&]() -> int {
-        const Last& l = st->last;
-        std::memset(header, 0, 8 * sizeof(int32_t));
-        if (!l.have) return (int)VISFS_BA_OK;
-        const int32_t per = l.mH * l.mH;
-        const int64_t nb = (int64_t)l.S * per;
-        header[0] = l.S; header[1] = l.L; header[2] = l.n; header[3] = l.H; header[4] = per; header[5] = l.survivors; header[6] = l.c.B;
-        if (scored) std::memcpy(scored, l.c.scored, sizeof l.c.scored);
-        if (kept) std::memcpy(kept, l.c.kept, sizeof l.c.kept);
-        if ((bounds && bounds_cap < nb) || (survivors && survivors_cap < l.survivors)) return sfail(st, VISFS_BA_ERR_BAD_ARGUMENT, "the hook's arrays are too small");
-        if (!st->device) {
-            if (bounds) std::memcpy(bounds, l.bounds.data(), (size_t)nb * sizeof(int32_t));
-            if (survivors) std::memcpy(survivors, l.surv.data(), (size_t)l.survivors * sizeof(int2));
-            return (int)VISFS_BA_OK;
-        }
-        SF_HIP(st, hipSetDevice(st->dev));
-        if (bounds) SF_HIP(st, hipMemcpyAsync(bounds, st->bnd[1].p, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost, st->stream));
-        if (survivors) SF_HIP(st, hipMemcpyAsync(survivors, st->fr[2].p, (size_t)l.survivors * sizeof(int2), hipMemcpyDeviceToHost, st->stream));
-        SF_HIP(st, hipStreamSynchronize(st->stream));
-        if (survivors) {                                                   // the device appends unordered
-            int2* sv = reinterpret_cast<int2*>(survivors);
-            std::sort(sv, sv + l.survivors, [](const int2& a, const int2& b) { return a.x < b.x; });
-        }
-        return (int)VISFS_BA_OK;
+        return match_download(st->device, st->dev, st->stream, st->blk, 0, st->last, st->err, header, scored, kept, bounds_cap, bounds, survivors_cap,
+                              survivors);
     });
 }
 
@@ -546,7 +449,7 @@ int visfs_internal_stack_from_view(bool device, int dev, hipStream_t stream, con
         st->device = device; st->dev = dev; st->stream = stream;
         st->L = L; st->depth = depth;
         auto run = [&]() -> int {
-            if (device) SF_HIP(st, hipSetDevice(dev));
+            if (device) SCAN_HIP(st->err, hipSetDevice(dev));
             return stack_build(st, g);
         };
         const int rc = run();

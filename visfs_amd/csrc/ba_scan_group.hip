@@ -1,18 +1,27 @@
 // One scan matched against many frozen grid stacks in one call (include/visfs_scan_group.h).
 //
-// The launch sequence is that of the single call (ba_scan_fast.hip) with the member as blockIdx.y: every kernel runs the single
-// call's body (ba_scan_stack.hpp) on member blockIdx.y's slices of the group's arenas, its levels and limits read from the member
-// table.  One call is one upload from a pinned buffer (points, a rotation table per member [m][S][2], the member table), H + 5
-// launches for any m, one download (Ctrl[m]) and one stream wait:
-//   k_group_cells   grid (S n / 256, m): cells[m][S][n], and every member's Ctrl zeroed;
-//   k_group_bounds  grid (x, m): one wavefront per level-H node, striding: bounds[m][S m_H^2];
-//   k_group_seeds   grid (S, m): member i's incumbent into Ctrl[i].B through the int32 atomic maximum;
+// This file holds the one device call path of the stack matcher: the match kernels and their launch sequence device_run, which
+// the single call (visfs_scan_stack_match, ba_scan_fast.hip) runs with m = 1 on the stack's call block and the group call with its m
+// members on the group's.  The member is blockIdx.y: every kernel runs one search's body (ba_scan_stack.hpp) on member blockIdx.y's
+// slices of the block's arenas, its levels and limits read from the member table.  One call is one upload from a pinned buffer
+// (points, a rotation table per member [m][S][2], the member table), H + 5 launches for any m, one download (Ctrl[m]) and one stream
+// wait; nothing is read back between levels, the frontier counts live in the Ctrl records on the device:
+//   k_group_cells   grid (S n / 256, m): the discretised cells[m][S][n] (scan::discretise), and every member's Ctrl zeroed;
+//   k_group_bounds  grid (x, m): one wavefront per level-H node, lanes along the points, striding: bounds[m][S m_H^2];
+//   k_group_seeds   grid (S, m): one workgroup per scan: its best level-H node, then H greedy steps, its four wavefronts scoring the
+//                   four children of a step; the leaf's sum joins member i's incumbent Ctrl[i].B through the int32 atomic maximum;
 //   k_group_keep    grid (x, m): the level-H nodes with U >= B_i appended to member i's frontier segment;
-//   k_group_level   grid (x, m), for h = H .. 1: frontier segments [m][cap] of two working arenas, counters in Ctrl[i]; overflow is
-//                   decided per member as in the single kernel;
-//   k_group_best    grid (1, m): each member's winner among its level-0 survivors.
-// x is the single call's fixed grid divided by m, at least 1; no result depends on it (integer sums, integer atomics, the total order
-// of `better`).  The members share nothing but the scan, so member i's bytes are the single call's on that stack.  A group of
+//   k_group_level   grid (x, m), for h = H .. 1: a fixed grid of wavefronts strides over member i's frontier of level h (its length
+//                   read on the device), scores the up-to-four in-window children of a node from one pass over the scan's cells, and
+//                   appends those with U >= B_i to its frontier of level h - 1 through an integer atomic counter in Ctrl[i]; frontier
+//                   segments [m][cap] of two working arenas; entries beyond the capacity are dropped and the member's overflow flag
+//                   is raised;
+//   k_group_best    grid (1, m): one workgroup per member selects its winner among its level-0 survivors: Q descending, index
+//                   ascending.
+// x is the stack's fixed grid divided by m, at least 1; no result depends on it (integer sums, integer atomics, the total order of
+// `better`).  The members share nothing but the scan, so member i's bytes are those of a single call on that stack.  The two callers
+// differ in what they make of the records: the single call fails on an overflow and hands the hook's arenas over only after a good
+// call; the group reports an overflow in that member's status and hands over after every call that ran to its end.  A group of
 // host-twin stacks runs the one-core twin (host_search) per member.
 //
 // visfs_scan_group_match_refine (include/visfs_scan_refine.h, section 9o) is the same sequence with the members' refinement jobs
@@ -87,25 +96,18 @@ struct visfs_scan_group {
     bool device = false;
     int dev = 0;
     hipStream_t stream = nullptr;
-    int32_t blocks = 1;                       // the single call's fixed grid, shared among the members
+    int32_t blocks = 1;                       // member 0's fixed grid, shared among the members
     std::vector<visfs_scan_stack*> mem;
     std::string err;
-    // a match on the device: as the single call's buffers, every one an arena over the members; the hook's arenas (bnd[1], fr[2])
-    // change hands with the working ones after a call that ran to its end
-    char* h_up = nullptr; char* d_up = nullptr; size_t up_cap = 0;
-    int2* d_cells = nullptr; size_t cells_cap = 0;
-    Ctrl* d_ctrl = nullptr; Ctrl* h_ctrl = nullptr;   // [m], and behind them the refinement records [m]
+    // a match on the device: a block for the m members; the hook's arenas change hands after every call that ran to its end
+    CallBlock blk;
     // match_refine: the traces [m][kMaxTrials][kTraceItems] of the call in work ([0]) and of the hook ([1]); the twin's traces; the
     // trials per member of the last call that ran to its end
     double* d_rtrace[2] = { nullptr, nullptr };
     std::vector<std::vector<double>> h_rtrace;
     std::vector<int32_t> rtrials;
-    Bounds bnd[2];
-    Frontier fr[3];
-    // the last call that ran to its end, per member (have = false: its status was not OK); the strides of the hook's arenas
+    // the last call that ran to its end, per member (have = false: its status was not OK)
     std::vector<Last> last;
-    int64_t last_top = 0, last_cap = 0;
-    int32_t launches = 0, copies = 0, syncs = 0;
 };
 
 namespace {
@@ -114,35 +116,12 @@ thread_local std::string t_create_err;
 
 int gfail(visfs_scan_group* g, int rc, const std::string& why) { g->err = why; return rc; }
 
-#define SG_HIP(g, expr)                                                                                               \
-    do {                                                                                                              \
-        hipError_t e_ = (expr);                                                                                       \
-        if (e_ != hipSuccess) return gfail((g), VISFS_BA_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-unsigned blocks_for(int64_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
-
-template <class T> int grow(visfs_scan_group* g, T** p, size_t* cap, size_t need) {
-    if (*cap >= need) return VISFS_BA_OK;
-    if (*p) SG_HIP(g, hipFree(*p));
-    *p = nullptr; *cap = 0;
-    SG_HIP(g, hipMalloc(reinterpret_cast<void**>(p), need * sizeof(T)));
-    *cap = need;
-    return VISFS_BA_OK;
-}
-
 void group_free(visfs_scan_group* g) {
     if (g->device) {
         (void)hipSetDevice(g->dev);
         if (g->stream) (void)hipStreamSynchronize(g->stream);
-        if (g->h_up) (void)hipHostFree(g->h_up);
-        if (g->d_up) (void)hipFree(g->d_up);
-        if (g->d_cells) (void)hipFree(g->d_cells);
-        if (g->d_ctrl) (void)hipFree(g->d_ctrl);
-        if (g->h_ctrl) (void)hipHostFree(g->h_ctrl);
+        block_free(g->blk);
         for (double* p : g->d_rtrace) if (p) (void)hipFree(p);
-        for (Bounds& b : g->bnd) if (b.p) (void)hipFree(b.p);
-        for (Frontier& f : g->fr) if (f.p) (void)hipFree(f.p);
     }
     delete g;
 }
@@ -163,89 +142,90 @@ scanrefine::Job match_job(const visfs_scan_stack* st, const Search& s, double mi
     return J;
 }
 
-// Every member's search on the device: fills the Ctrl records of h_ctrl and leaves the frontier of level 0 in fr[*cur].  With `rp`
-// every matched member's refinement follows in the same sequence: its records come behind the Ctrl records.
-int device_run(visfs_scan_group* g, const std::vector<Search>& ss, int* cur_out, const scanrefine::Prm* rp = nullptr, double min_score = 0.0) {
-    const int32_t m = (int32_t)g->mem.size();
+}  // namespace
+
+// ---------------------------------------------------------------- the launch sequence (ba_scan_stack.hpp)
+int scanfast::device_run(CallBlock& b, int dev, hipStream_t stream, int32_t blocks, int32_t m, visfs_scan_stack* const* mem, const Search* ss, int* cur_out,
+                         std::string& why, const scanrefine::Prm* rp, double min_score, double* rtrace) {
     const Search& s0 = ss[0];
     const int32_t n = s0.P.n, S = s0.P.S, nl = s0.P.nl, L = s0.P.Lw, H = s0.H, mH = s0.mH, total = s0.top(), cap = s0.cap;
     const int64_t ncell = (int64_t)S * n;
-    SG_HIP(g, hipSetDevice(g->dev));
+    b.launches = b.copies = b.syncs = 0;
+    SCAN_HIP(why, hipSetDevice(dev));
     const size_t npts = 2 * (size_t)n, nrot = 2 * (size_t)S * m;
     const size_t match_bytes = (npts + nrot) * sizeof(double) + (size_t)m * sizeof(Member);
     const size_t bytes = match_bytes + (rp ? (size_t)m * sizeof(scanrefine::Job) : 0);
-    if (g->up_cap < bytes) {
-        if (g->h_up) SG_HIP(g, hipHostFree(g->h_up));
-        if (g->d_up) SG_HIP(g, hipFree(g->d_up));
-        g->h_up = g->d_up = nullptr; g->up_cap = 0;
+    if (b.up_cap < bytes) {
+        if (b.h_up) SCAN_HIP(why, hipHostFree(b.h_up));
+        if (b.d_up) SCAN_HIP(why, hipFree(b.d_up));
+        b.h_up = b.d_up = nullptr; b.up_cap = 0;
         const size_t want = bytes + bytes / 2;
-        SG_HIP(g, hipHostMalloc(reinterpret_cast<void**>(&g->h_up), want, hipHostMallocDefault));
-        SG_HIP(g, hipMalloc(reinterpret_cast<void**>(&g->d_up), want));
-        g->up_cap = want;
+        SCAN_HIP(why, hipHostMalloc(reinterpret_cast<void**>(&b.h_up), want, hipHostMallocDefault));
+        SCAN_HIP(why, hipMalloc(reinterpret_cast<void**>(&b.d_up), want));
+        b.up_cap = want;
     }
-    if (!g->d_ctrl) {
-        SG_HIP(g, hipMalloc(reinterpret_cast<void**>(&g->d_ctrl), ctrl_bytes(m) + record_bytes(m)));
-        SG_HIP(g, hipHostMalloc(reinterpret_cast<void**>(&g->h_ctrl), ctrl_bytes(m) + record_bytes(m), hipHostMallocDefault));
+    if (!b.d_ctrl) {
+        SCAN_HIP(why, hipMalloc(reinterpret_cast<void**>(&b.d_ctrl), ctrl_bytes(m) + record_bytes(m)));
+        SCAN_HIP(why, hipHostMalloc(reinterpret_cast<void**>(&b.h_ctrl), ctrl_bytes(m) + record_bytes(m), hipHostMallocDefault));
     }
-    if (rp)
-        for (double*& p : g->d_rtrace)
-            if (!p) SG_HIP(g, hipMalloc(reinterpret_cast<void**>(&p), (size_t)m * scanrefine::kMaxTrials * scanrefine::kTraceItems * sizeof(double)));
     int rc;
-    if ((rc = grow(g, &g->d_cells, &g->cells_cap, (size_t)m * (size_t)ncell)) != VISFS_BA_OK) return rc;
-    if ((rc = grow(g, &g->bnd[0].p, &g->bnd[0].cap, (size_t)m * (size_t)total)) != VISFS_BA_OK) return rc;
+    if ((rc = grow(why, &b.d_cells, &b.cells_cap, (size_t)m * (size_t)ncell)) != VISFS_BA_OK) return rc;
+    if ((rc = grow(why, &b.bnd[0].p, &b.bnd[0].cap, (size_t)m * (size_t)total)) != VISFS_BA_OK) return rc;
     for (int f = 0; f < 2; ++f)
-        if ((rc = grow(g, &g->fr[f].p, &g->fr[f].cap, (size_t)m * (size_t)cap)) != VISFS_BA_OK) return rc;
-    double* hup = reinterpret_cast<double*>(g->h_up);
+        if ((rc = grow(why, &b.fr[f].p, &b.fr[f].cap, (size_t)m * (size_t)cap)) != VISFS_BA_OK) return rc;
+    double* hup = reinterpret_cast<double*>(b.h_up);
     std::memcpy(hup, s0.P.pts.data(), npts * sizeof(double));
     Member* hmt = reinterpret_cast<Member*>(hup + npts + nrot);                // doubles in front of it: aligned to 8
     for (int32_t i = 0; i < m; ++i) {
         const Plan& P = ss[i].P;
         std::memcpy(hup + npts + 2 * (size_t)S * i, P.rot.data(), 2 * (size_t)S * sizeof(double));
         Member M;
-        M.gx = P.gx; M.gy = P.gy; M.res = P.L.res; M.max_x = P.L.max_x; M.max_y = P.L.max_y; M.lv = g->mem[i]->lv;
+        M.gx = P.gx; M.gy = P.gy; M.res = P.L.res; M.max_x = P.L.max_x; M.max_y = P.L.max_y; M.lv = mem[i]->lv;
         std::memcpy(hmt + i, &M, sizeof M);
     }
     if (rp) {                                                              // the jobs point into the device's copies
-        const double* drot0 = reinterpret_cast<const double*>(g->d_up) + npts;
+        const double* drot0 = reinterpret_cast<const double*>(b.d_up) + npts;
         for (int32_t i = 0; i < m; ++i) {
-            const scanrefine::Job J = match_job(g->mem[i], ss[i], min_score, g->d_ctrl + i, drot0 + 2 * (size_t)S * i);
-            std::memcpy(g->h_up + match_bytes + (size_t)i * sizeof J, &J, sizeof J);
+            const scanrefine::Job J = match_job(mem[i], ss[i], min_score, b.d_ctrl + i, drot0 + 2 * (size_t)S * i);
+            std::memcpy(b.h_up + match_bytes + (size_t)i * sizeof J, &J, sizeof J);
         }
     }
-    SG_HIP(g, hipMemcpyAsync(g->d_up, g->h_up, bytes, hipMemcpyHostToDevice, g->stream));
-    ++g->copies;
-    const double* d = reinterpret_cast<const double*>(g->d_up);
+    SCAN_HIP(why, hipMemcpyAsync(b.d_up, b.h_up, bytes, hipMemcpyHostToDevice, stream));
+    ++b.copies;
+    const double* d = reinterpret_cast<const double*>(b.d_up);
     const double* drot = d + npts;
     const Member* dmt = reinterpret_cast<const Member*>(drot + nrot);
-    const dim3 fixed((unsigned)std::max(1, g->blocks / m), (unsigned)m), wg(kThreads);
-    hipLaunchKernelGGL(k_group_cells, dim3(blocks_for(ncell), (unsigned)m), wg, 0, g->stream, d, drot, dmt, n, S, ncell, g->d_cells, g->d_ctrl);
-    SG_HIP(g, hipGetLastError()); ++g->launches;
-    hipLaunchKernelGGL(k_group_bounds, fixed, wg, 0, g->stream, g->d_cells, ncell, n, dmt, nl, H, mH, total, g->bnd[0].p);
-    SG_HIP(g, hipGetLastError()); ++g->launches;
-    hipLaunchKernelGGL(k_group_seeds, dim3((unsigned)S, (unsigned)m), wg, 0, g->stream, g->bnd[0].p, total, g->d_cells, ncell, n, dmt, nl, L, H, mH, g->d_ctrl);
-    SG_HIP(g, hipGetLastError()); ++g->launches;
+    const dim3 fixed((unsigned)std::max(1, blocks / m), (unsigned)m), wg(kThreads);
+    hipLaunchKernelGGL(k_group_cells, dim3(blocks_for(ncell), (unsigned)m), wg, 0, stream, d, drot, dmt, n, S, ncell, b.d_cells, b.d_ctrl);
+    SCAN_HIP(why, hipGetLastError()); ++b.launches;
+    hipLaunchKernelGGL(k_group_bounds, fixed, wg, 0, stream, b.d_cells, ncell, n, dmt, nl, H, mH, total, b.bnd[0].p);
+    SCAN_HIP(why, hipGetLastError()); ++b.launches;
+    hipLaunchKernelGGL(k_group_seeds, dim3((unsigned)S, (unsigned)m), wg, 0, stream, b.bnd[0].p, total, b.d_cells, ncell, n, dmt, nl, L, H, mH, b.d_ctrl);
+    SCAN_HIP(why, hipGetLastError()); ++b.launches;
     int cur = 0;                                                           // the frontiers of the level in work: fr[cur]
-    hipLaunchKernelGGL(k_group_keep, fixed, wg, 0, g->stream, g->bnd[0].p, total, H, g->fr[cur].p, cap, g->d_ctrl);
-    SG_HIP(g, hipGetLastError()); ++g->launches;
+    hipLaunchKernelGGL(k_group_keep, fixed, wg, 0, stream, b.bnd[0].p, total, H, b.fr[cur].p, cap, b.d_ctrl);
+    SCAN_HIP(why, hipGetLastError()); ++b.launches;
     for (int32_t h = H; h >= 1; --h) {
-        hipLaunchKernelGGL(k_group_level, fixed, wg, 0, g->stream, h, g->fr[cur].p, g->fr[1 - cur].p, cap, g->d_cells, ncell, n, dmt, nl, L, g->d_ctrl);
-        SG_HIP(g, hipGetLastError()); ++g->launches;
+        hipLaunchKernelGGL(k_group_level, fixed, wg, 0, stream, h, b.fr[cur].p, b.fr[1 - cur].p, cap, b.d_cells, ncell, n, dmt, nl, L, b.d_ctrl);
+        SCAN_HIP(why, hipGetLastError()); ++b.launches;
         cur = 1 - cur;
     }
-    hipLaunchKernelGGL(k_group_best, dim3(1, (unsigned)m), wg, 0, g->stream, g->fr[cur].p, cap, g->d_ctrl);
-    SG_HIP(g, hipGetLastError()); ++g->launches;
+    hipLaunchKernelGGL(k_group_best, dim3(1, (unsigned)m), wg, 0, stream, b.fr[cur].p, cap, b.d_ctrl);
+    SCAN_HIP(why, hipGetLastError()); ++b.launches;
     if (rp) {
-        SG_HIP(g, (hipError_t)scanrefine::launch_refine(g->stream, m, reinterpret_cast<const scanrefine::Job*>(g->d_up + match_bytes), *rp, d,
-                                                        records_of(g->d_ctrl, m), g->d_rtrace[0]));
-        ++g->launches;
+        SCAN_HIP(why, (hipError_t)scanrefine::launch_refine(stream, m, reinterpret_cast<const scanrefine::Job*>(b.d_up + match_bytes), *rp, d,
+                                                            records_of(b.d_ctrl, m), rtrace));
+        ++b.launches;
     }
-    SG_HIP(g, hipMemcpyAsync(g->h_ctrl, g->d_ctrl, ctrl_bytes(m) + (rp ? record_bytes(m) : 0), hipMemcpyDeviceToHost, g->stream));
-    ++g->copies;
-    SG_HIP(g, hipStreamSynchronize(g->stream));
-    ++g->syncs;
+    SCAN_HIP(why, hipMemcpyAsync(b.h_ctrl, b.d_ctrl, ctrl_bytes(m) + (rp ? record_bytes(m) : 0), hipMemcpyDeviceToHost, stream));
+    ++b.copies;
+    SCAN_HIP(why, hipStreamSynchronize(stream));
+    ++b.syncs;
     *cur_out = cur;
     return VISFS_BA_OK;
 }
+
+namespace {
 
 // rp and refined: both or neither (visfs_scan_group_match_refine)
 int group_match(visfs_scan_group* g, const visfs_scan_stack_params& p, const double* guesses, int32_t n, const double* xyz,
@@ -262,7 +242,7 @@ int group_match(visfs_scan_group* g, const visfs_scan_stack_params& p, const dou
     if ((int64_t)m * p.frontier_capacity > (int64_t)VISFS_SCAN_GROUP_MAX_FRONTIER)
         return gfail(g, VISFS_BA_ERR_UNSUPPORTED, "members times frontier_capacity exceed 2^26");
     if (n == 0) {                                                          // nothing to match: every guess back
-        g->launches = g->copies = g->syncs = 0;
+        g->blk.launches = g->blk.copies = g->blk.syncs = 0;
         for (int32_t i = 0; i < m; ++i) { no_points(guesses + 3 * i, results + i); status[i] = VISFS_BA_OK; }
         if (rp) {
             for (int32_t i = 0; i < m; ++i) scanrefine::not_refined(VISFS_BA_OK, guesses[3 * i], guesses[3 * i + 1], guesses[3 * i + 2], refined + i);
@@ -279,28 +259,32 @@ int group_match(visfs_scan_group* g, const visfs_scan_stack_params& p, const dou
         if (ss[i].P.S != ss[0].P.S || ss[i].P.nl != ss[0].P.nl || ss[i].H != ss[0].H || ss[i].mH != ss[0].mH)
             return gfail(g, VISFS_BA_ERR_DEVICE, member_text(i, "its search differs in shape from member 0's"));
     }
-    g->launches = g->copies = g->syncs = 0;
+    g->blk.launches = g->blk.copies = g->blk.syncs = 0;
     std::vector<Last> now((size_t)m);
     std::string first_overflow;
     int cur = 0;
     scanrefine::Prm RP;
     if (rp) RP = scanrefine::make_prm(*rp, n);
     if (g->device) {
-        if ((rc = device_run(g, ss, &cur, rp ? &RP : nullptr, p.min_score)) != VISFS_BA_OK) return rc;
+        if (rp) {
+            SCAN_HIP(g->err, hipSetDevice(g->dev));
+            for (double*& t : g->d_rtrace)
+                if (!t) SCAN_HIP(g->err, hipMalloc(reinterpret_cast<void**>(&t), (size_t)m * scanrefine::kMaxTrials * scanrefine::kTraceItems * sizeof(double)));
+        }
+        if ((rc = device_run(g->blk, g->dev, g->stream, g->blocks, m, g->mem.data(), ss.data(), &cur, g->err, rp ? &RP : nullptr, p.min_score,
+                             g->d_rtrace[0])) != VISFS_BA_OK)
+            return rc;
         for (int32_t i = 0; i < m; ++i) {
-            const Ctrl& c = g->h_ctrl[i];
+            const Ctrl& c = g->blk.h_ctrl[i];
             const Search& s = ss[i];
             if (c.overflow) {
                 if (first_overflow.empty()) first_overflow = member_text(i, overflow_text(c.overflow - 1, s.cap));
                 continue;
             }
             if (c.best_index < 0 || (int64_t)c.best_index >= s.P.candidates()) return gfail(g, VISFS_BA_ERR_DEVICE, member_text(i, "the search returned no candidate"));
-            Last& l = now[i];
-            l.have = true; l.S = s.P.S; l.L = s.P.Lw; l.n = n; l.H = s.H; l.mH = s.mH; l.survivors = c.kept[0]; l.c = c;
+            now[i] = device_last(s, c);
         }
-        // the hook's arenas change hands: what this call wrote stays until the next call that runs to its end
-        std::swap(g->bnd[0], g->bnd[1]);
-        std::swap(g->fr[cur], g->fr[2]);
+        g->blk.hand_over(cur, ss[0]);                                      // after any call that ran to its end
     } else {
         for (int32_t i = 0; i < m; ++i) {
             std::string text;
@@ -330,7 +314,7 @@ int group_match(visfs_scan_group* g, const visfs_scan_stack_params& p, const dou
             const visfs_scan_match_result& w = results[i].match;
             if (!w.matched) { scanrefine::not_refined(VISFS_BA_OK, w.x, w.y, w.yaw, refined + i); continue; }
             if (g->device) {
-                refined[i] = records_of(g->h_ctrl, m)[i];
+                refined[i] = records_of(g->blk.h_ctrl, m)[i];
                 if (!refined[i].refined) return gfail(g, VISFS_BA_ERR_DEVICE, member_text(i, "the refinement skipped a matched member"));
             } else {
                 const double start[3] = { w.x, w.y, w.yaw };
@@ -344,14 +328,8 @@ int group_match(visfs_scan_group* g, const visfs_scan_stack_params& p, const dou
         g->rtrials.swap(trials);
     }
     g->last = std::move(now);
-    g->last_top = ss[0].top(); g->last_cap = ss[0].cap;
     g->err = first_overflow;
     return VISFS_BA_OK;
-}
-
-template <class F> int guarded(F&& f) noexcept {
-    try { return f(); }
-    catch (...) { return (int)VISFS_BA_ERR_DEVICE; }
 }
 
 }  // namespace
@@ -402,29 +380,8 @@ int visfs_scan_group_match_download(visfs_scan_group* g, int32_t member, int32_t
     if (!g || !header || bounds_cap < 0 || survivors_cap < 0) return VISFS_BA_ERR_BAD_ARGUMENT;
     return guarded([&]() -> int {
         if (member < 0 || member >= (int32_t)g->mem.size()) return gfail(g, VISFS_BA_ERR_BAD_ARGUMENT, "the group has no such member");
-        const Last& l = g->last[(size_t)member];
-        std::memset(header, 0, 8 * sizeof(int32_t));
-        if (!l.have) return (int)VISFS_BA_OK;
-        const int32_t per = l.mH * l.mH;
-        const int64_t nb = (int64_t)l.S * per;
-        header[0] = l.S; header[1] = l.L; header[2] = l.n; header[3] = l.H; header[4] = per; header[5] = l.survivors; header[6] = l.c.B;
-        if (scored) std::memcpy(scored, l.c.scored, sizeof l.c.scored);
-        if (kept) std::memcpy(kept, l.c.kept, sizeof l.c.kept);
-        if ((bounds && bounds_cap < nb) || (survivors && survivors_cap < l.survivors)) return gfail(g, VISFS_BA_ERR_BAD_ARGUMENT, "the hook's arrays are too small");
-        if (!g->device) {
-            if (bounds) std::memcpy(bounds, l.bounds.data(), (size_t)nb * sizeof(int32_t));
-            if (survivors) std::memcpy(survivors, l.surv.data(), (size_t)l.survivors * sizeof(int2));
-            return (int)VISFS_BA_OK;
-        }
-        SG_HIP(g, hipSetDevice(g->dev));
-        if (bounds) SG_HIP(g, hipMemcpyAsync(bounds, g->bnd[1].p + (int64_t)member * g->last_top, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
-        if (survivors) SG_HIP(g, hipMemcpyAsync(survivors, g->fr[2].p + (int64_t)member * g->last_cap, (size_t)l.survivors * sizeof(int2), hipMemcpyDeviceToHost, g->stream));
-        SG_HIP(g, hipStreamSynchronize(g->stream));
-        if (survivors) {                                                   // the device appends unordered
-            int2* sv = reinterpret_cast<int2*>(survivors);
-            std::sort(sv, sv + l.survivors, [](const int2& a, const int2& b) { return a.x < b.x; });
-        }
-        return (int)VISFS_BA_OK;
+        return match_download(g->device, g->dev, g->stream, g->blk, member, g->last[(size_t)member], g->err, header, scored, kept, bounds_cap, bounds,
+                              survivors_cap, survivors);
     });
 }
 
@@ -445,18 +402,18 @@ int visfs_scan_group_refine_download(visfs_scan_group* g, int32_t member, int32_
         if (cap < nt) return gfail(g, VISFS_BA_ERR_BAD_ARGUMENT, "the hook's array is too small");
         const size_t bytes = (size_t)nt * scanrefine::kTraceItems * sizeof(double);
         if (!g->device) { std::memcpy(trace, g->h_rtrace[(size_t)member].data(), bytes); return (int)VISFS_BA_OK; }
-        SG_HIP(g, hipSetDevice(g->dev));
-        SG_HIP(g, hipMemcpyAsync(trace, g->d_rtrace[1] + (size_t)member * scanrefine::kMaxTrials * scanrefine::kTraceItems, bytes, hipMemcpyDeviceToHost, g->stream));
-        SG_HIP(g, hipStreamSynchronize(g->stream));
+        SCAN_HIP(g->err, hipSetDevice(g->dev));
+        SCAN_HIP(g->err, hipMemcpyAsync(trace, g->d_rtrace[1] + (size_t)member * scanrefine::kMaxTrials * scanrefine::kTraceItems, bytes, hipMemcpyDeviceToHost, g->stream));
+        SCAN_HIP(g->err, hipStreamSynchronize(g->stream));
         return (int)VISFS_BA_OK;
     });
 }
 
 int visfs_scan_group_last_counts(const visfs_scan_group* g, int32_t* kernel_launches, int32_t* copies_and_memsets, int32_t* synchronisations) {
     if (!g) return VISFS_BA_ERR_BAD_ARGUMENT;
-    if (kernel_launches) *kernel_launches = g->launches;
-    if (copies_and_memsets) *copies_and_memsets = g->copies;
-    if (synchronisations) *synchronisations = g->syncs;
+    if (kernel_launches) *kernel_launches = g->blk.launches;
+    if (copies_and_memsets) *copies_and_memsets = g->blk.copies;
+    if (synchronisations) *synchronisations = g->blk.syncs;
     return VISFS_BA_OK;
 }
 

@@ -1,11 +1,14 @@
-// The stack object of the branch-and-bound scan matcher and what its single call (ba_scan_fast.hip) shares with
-// the group call over several stacks (ba_scan_group.hip, section 9n): the search of one call, the one-core twin's schedule, the
-// record, and the bodies of the match kernels.  The host functions are defined in ba_scan_fast.hip.
+// The stack object of the branch-and-bound scan matcher (ba_scan_fast.hip) and the one device call path that
+// its single call and the group call over several stacks (ba_scan_group.hip, section 9n) both take: the search of one call, the
+// one-core twin's schedule, the record, the call block (the device buffers of a call over m members), the launch sequence device_run
+// and the bodies of its kernels.  The single call is the sequence at m = 1 on the stack's own block.  device_run and its kernels are
+// defined in ba_scan_group.hip, the other host functions in ba_scan_fast.hip.
 #pragma once
 #include "ba_scan_fast.hpp"
 
 #include <climits>
 #include <string>
+#include <utility>
 #include <vector>
 
 #pragma clang fp contract(off)
@@ -31,11 +34,32 @@ struct Search {
     int32_t top() const { return P.S * mH * mH; }
 };
 
+// The device buffers of a call over m members, m fixed for the block's life (1: a stack's own, for its single calls): the upload
+// with its pinned source, and every other one an arena of m equal slices: the cells, the records with their pinned copy (behind them
+// room for m refinement records), bounds and frontiers of the call in work (bnd[0], fr[0], fr[1]) and those the hook reads (bnd[1],
+// fr[2]), which change hands in hand_over.  Made by the first call, let go by block_free.
+struct CallBlock {
+    char* h_up = nullptr; char* d_up = nullptr; size_t up_cap = 0;
+    int2* d_cells = nullptr; size_t cells_cap = 0;
+    Ctrl* d_ctrl = nullptr; Ctrl* h_ctrl = nullptr;
+    Bounds bnd[2];
+    Frontier fr[3];
+    int64_t top = 0, cap = 0;                 // the strides of the hook's arenas: those of the last call handed over
+    int32_t launches = 0, copies = 0, syncs = 0;      // of the last device_run
+    // the hook's arenas become what a call wrote, its level-0 frontier in fr[cur]; they stay until the next hand-over
+    void hand_over(int cur, const Search& s) {
+        std::swap(bnd[0], bnd[1]);
+        std::swap(fr[cur], fr[2]);
+        top = s.top(); cap = s.cap;
+    }
+};
+
 }  // namespace scanfast
 
 // the buffers of visfs_scan_stack_refine on a stack (ba_scan_refine.hip), made by its first call
 namespace scanrefine {
 struct State;
+struct Prm;
 void state_free(State* s);
 }
 
@@ -52,13 +76,9 @@ struct visfs_scan_stack {
     std::vector<uint16_t> h_mem;
     uint16_t* d_mem = nullptr;
     scanfast::Levels lv;
-    // a match on the device: the upload with its pinned source, the cells, the record with its pinned copy; bounds and frontiers
-    // of the call in work, and those of the last successful call (the hook's), which a failed call must leave
-    char* h_up = nullptr; char* d_up = nullptr; size_t up_cap = 0;
-    int2* d_cells = nullptr; size_t cells_cap = 0;
-    scanfast::Ctrl* d_ctrl = nullptr; scanfast::Ctrl* h_ctrl = nullptr;
-    scanfast::Bounds bnd[2];
-    scanfast::Frontier fr[3];
+    // a match on the device: a block for one member, whatever groups the stack is a member of; handed over by successful calls
+    // only, so a failed call leaves the hook's arenas and `last`
+    scanfast::CallBlock blk;
     scanfast::Last last;
     scanrefine::State* refine = nullptr;
 };
@@ -80,6 +100,44 @@ void no_points(const double g[3], visfs_scan_stack_result* out);
 // on a frontier overflow VISFS_BA_ERR_UNSUPPORTED, on an empty result VISFS_BA_ERR_DEVICE, with `why`.
 int host_search(const Levels& lv, const Search& s, Last& now, std::string& why);
 
+#define SCAN_HIP(err, expr)                                                                                           \
+    do {                                                                                                              \
+        hipError_t e_ = (expr);                                                                                       \
+        if (e_ != hipSuccess) { (err) = std::string(#expr) + ": " + hipGetErrorString(e_); return VISFS_BA_ERR_DEVICE; } \
+    } while (0)
+
+inline unsigned blocks_for(int64_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
+
+template <class F> int guarded(F&& f) noexcept {
+    try { return f(); }
+    catch (...) { return (int)VISFS_BA_ERR_DEVICE; }
+}
+
+template <class T> int grow(std::string& err, T** p, size_t* cap, size_t need) {
+    if (*cap >= need) return VISFS_BA_OK;
+    if (*p) SCAN_HIP(err, hipFree(*p));
+    *p = nullptr; *cap = 0;
+    SCAN_HIP(err, hipMalloc(reinterpret_cast<void**>(p), need * sizeof(T)));
+    *cap = need;
+    return VISFS_BA_OK;
+}
+
+// Every buffer of the block let go; the caller has selected the device and waited for the stream.
+void block_free(CallBlock& b);
+// The searches ss[0..m) of one scan, equal in S, nl, H, m_H and capacity, on the stacks mem[0..m) in one sequence on `stream`: one
+// upload, H + 5 launches, one download and one wait, `blocks` being the fixed grid of the striding kernels shared among the members.
+// Fills b.h_ctrl[0..m) and leaves member i's level-0 frontier in slice i of b.fr[*cur]; the hand-over is the caller's.  With `rp`
+// every matched member's refinement follows in the same sequence, its traces into `rtrace` [m][kMaxTrials][kTraceItems] and its
+// records behind the Ctrl records.  VISFS_BA_OK, or VISFS_BA_ERR_DEVICE with `why`.
+int device_run(CallBlock& b, int dev, hipStream_t stream, int32_t blocks, int32_t m, visfs_scan_stack* const* mem, const Search* ss, int* cur,
+               std::string& why, const scanrefine::Prm* rp = nullptr, double min_score = 0.0, double* rtrace = nullptr);
+// the record of a member whose search on the device came to its end with the winner in `c`
+Last device_last(const Search& s, const Ctrl& c);
+// The hook of both calls on `l`, the record of member `member` of the last call handed over in `b` (a host twin's arrays stand in
+// `l` itself).  VISFS_BA_OK, or the code with `why`.
+int match_download(bool device, int dev, hipStream_t stream, const CallBlock& b, int64_t member, const Last& l, std::string& why, int32_t header[8],
+                   int32_t scored[16], int32_t kept[16], int64_t bounds_cap, int32_t* bounds, int64_t survivors_cap, int32_t* survivors);
+
 #ifdef __HIPCC__
 __device__ inline int32_t wave_sum(int32_t v) {
     for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
@@ -93,9 +151,8 @@ __device__ inline int32_t wave_node_sum(const int2* __restrict__ c, int32_t n, c
     return wave_sum(q);
 }
 
-// The bodies of the match kernels.  Each works on one search: the single call's kernels (k_fast_*, ba_scan_fast.hip) pass their
-// arguments through, the group's (k_group_*, ba_scan_group.hip) pass member blockIdx.y's slices.  Only blockIdx.x and gridDim.x are
-// read here.
+// The bodies of the match kernels.  Each works on one search: the kernels (k_group_*, ba_scan_group.hip) pass member blockIdx.y's
+// slices.  Only blockIdx.x and gridDim.x are read here.
 __device__ inline void cells_body(const double* __restrict__ pts, const double* __restrict__ rot, int32_t n, int64_t total, double gx, double gy,
                                   double res, double max_x, double max_y, int2* __restrict__ cells, Ctrl* __restrict__ ctrl) {
     if (blockIdx.x == 0 && threadIdx.x < sizeof(Ctrl) / sizeof(int32_t)) reinterpret_cast<int32_t*>(ctrl)[threadIdx.x] = 0;
