@@ -11,7 +11,7 @@ name=$1; shift
 src=${VISFS_BA_SRC:-visfs_amd/csrc}
 kflags=${VISFS_BA_KERNEL_FLAGS--mllvm -amdgpu-kernarg-preload-count=8}
 files=""
-for f in ba_cov.hip ba_submap.hip ba_flow.hip ba_corners.hip ba_clahe.hip ba_pnp.hip ba_fund.hip ba_tracker.hip ba_scan.hip ba_scan_fast.hip ba_api.cpp ba_scan_group.hip ba_scan_refine.hip ba_pose_graph.hip ba_pose_graph_cov.hip ba_map.hip; do
+for f in ba_cov.hip ba_submap.hip ba_flow.hip ba_corners.hip ba_clahe.hip ba_pnp.hip ba_fund.hip ba_tracker.hip ba_scan.hip ba_scan_fast.hip ba_api.cpp ba_scan_group.hip ba_scan_refine.hip ba_pose_graph.hip ba_pose_graph_cov.hip ba_map.hip ba_scan_filter.hip; do
   [ -f "$src/$f" ] && files="$files $src/$f"
 done
 mkdir -p build/obj visfs_amd/lib

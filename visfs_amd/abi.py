@@ -268,3 +268,18 @@ def pack_window_with(lib_pack, params, wb):
 
 PACK_ARGTYPES = [C.POINTER(Params), C.POINTER(Window), _pd, _pu8, _pu8, _pi32, _pi32, _pd, _pi32,
                  _pi32, _pi32, _pd, C.POINTER(Graph), _pi32]
+
+
+# ---- include/visfs_scan_filter.h: the layouts without a dependency on another binding (the parameter block embeds
+# scan_match.PretreatParams and lives in visfs_amd.scan_filter)
+class ScanFilterScan(C.Structure):
+    _fields_ = [("T_laser_to_camera", C.c_double * 12), ("origin", C.c_double * 3), ("n", C.c_int32), ("points_xyz", _pd)]
+
+
+class ScanFilterRecord(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_range_data", C.c_int32), ("n_returns", C.c_int32), ("n_misses", C.c_int32),
+                ("n_in_range", C.c_int32), ("n_match", C.c_int32), ("passes", C.c_int32), ("reserved", C.c_int32),
+                ("match_length", C.c_double)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
