@@ -283,3 +283,27 @@ class ScanFilterRecord(C.Structure):
 
     def as_dict(self):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
+
+# ---- include/visfs_mcl.h: Monte-Carlo localisation on the likelihood field (the limits are submap.Info, embedded in visfs_amd.mcl)
+class MclFieldParams(C.Structure):
+    _fields_ = [("occupied_probability", C.c_double), ("max_dist", C.c_double), ("z_hit", C.c_double), ("z_rand", C.c_double),
+                ("sigma_hit", C.c_double), ("range_max", C.c_double)]
+
+
+class MclParams(C.Structure):
+    _fields_ = [("alpha1", C.c_double), ("alpha2", C.c_double), ("alpha3", C.c_double), ("alpha4", C.c_double),
+                ("n_eff_ratio", C.c_double), ("resample_interval", C.c_int32), ("max_beams", C.c_int32)]
+
+
+class MclResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("resampled", C.c_int32), ("best", C.c_int32), ("n_beams", C.c_int32), ("update", C.c_int64),
+                ("mean", C.c_double * 3), ("covariance", C.c_double * 9), ("n_eff", C.c_double), ("W", C.c_double),
+                ("best_pose", C.c_double * 3), ("best_weight", C.c_double)]
+
+    def as_dict(self):
+        d = {}
+        for name, t in self._fields_:
+            v = getattr(self, name)
+            d[name] = list(v) if hasattr(v, "__len__") else v
+        return d

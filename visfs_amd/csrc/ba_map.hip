@@ -9,6 +9,7 @@
 // visfs_map_download or visfs_scan_stack_create_from_map asks for them.  The one-core twin calls the same compose_cell of ba_map.hpp.
 #include "ba_map.hpp"
 #include "ba_scan_stack_access.hpp"
+#include "ba_map_access.hpp"
 
 #include <cstring>
 #include <new>
@@ -225,6 +226,13 @@ Limits limits_of(const visfs_submap_info& l) {
 }
 
 }  // namespace
+
+int visfs_internal_map_access(visfs_map* m, gmap::MapAccess* a) {
+    if (!m || !a) return VISFS_BA_ERR_BAD_ARGUMENT;
+    a->device = m->device; a->dev = m->dev; a->stream = m->stream; a->have = m->have; a->L = m->G;
+    a->cells = m->device ? m->d_cells : m->h_cells.data();
+    return VISFS_BA_OK;
+}
 
 // ====================================================================== exported C ABI
 extern "C" {
