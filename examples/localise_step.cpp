@@ -2,14 +2,16 @@
 // (VISFS::MonteCarloLocalizer over include/visfs_mcl.h).
 //
 //   g++ -std=c++17 -O2 -Iinclude -Ivisfs_amd/host examples/localise_step.cpp -Lvisfs_amd/lib -lvisfs_ba_hip
-//       -Wl,-rpath,$PWD/visfs_amd/lib -o localise_step && ./localise_step [host]
+//       -Wl,-rpath,$PWD/visfs_amd/lib -o localise_step && ./localise_step [host] [kld]
 //
 // A robot drives 16 poses of a circle in a room and inserts every scan into the sub-maps; each finished front sub-map becomes a
 // tile of a global map, which is composed once.  From that map come a likelihood field and a scan stack.  The robot then starts
 // again with a pose guess that is off by 15 cm and 0.08 rad: one visfs_scan_stack_match of the first scan corrects it, and its
 // result is the mean of the filter's initial belief.  Twenty steps follow, each an update with noisy odometry and a scan of 120
 // returns, and the estimate after each.  `host` runs the one-core twins.  Prints one JSON line; the device and the twin print the
-// same numbers and the same hash over every estimate's bits and the final particles.
+// same numbers and the same hash over every estimate's bits and the final particles.  `kld` makes the filter a KLD filter
+// (include/visfs_mcl_kld.h: min_particles 100, kld_err 0.01, kld_z 0.99, at most the 2000 it starts with) and adds the particle
+// count after every step to the line.
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -63,6 +65,8 @@ struct Summary {
     int tiles = 0, obstacles = 0, resampled = 0, launches = 0, copies = 0, waits = 0, field_launches = 0;
     double match_error = 0.0, guess_error = 0.0, final_error = 0.0, final_yaw_error = 0.0, first_n_eff = 0.0, first_trace = 0.0, last_trace = 0.0;
     uint64_t hash = 1469598103934665603ull;
+    bool kld = false;
+    std::vector<int> counts;      // the particle count after every step (kld only)
 };
 
 inline void mix(uint64_t& h, const void* p, size_t bytes) {
@@ -121,6 +125,7 @@ inline int run(visfs_ba_handle* ba, const Submaps& subs, Summary& out) {
 
     VISFS::MonteCarloLocalizer mcl(field, kParticles, 7);
     const double mean[3] = { m.x, m.y, m.yaw }, sigma[3] = { 0.3, 0.3, 0.15 };
+    if (out.kld && mcl.enableKld(100, 0.01, 0.99) != VISFS_BA_OK) { std::fprintf(stderr, "enableKld failed: %s\n", mcl.lastError()); return 1; }
     if (mcl.init(mean, sigma) != VISFS_BA_OK) { std::fprintf(stderr, "init failed: %s\n", mcl.lastError()); return 1; }
     for (int k = 0; k < kSteps; ++k) {
         truth = compose(truth, step);
@@ -132,6 +137,7 @@ inline int run(visfs_ba_handle* ba, const Submaps& subs, Summary& out) {
         mix(out.hash, r.mean, sizeof r.mean); mix(out.hash, r.covariance, sizeof r.covariance); mix(out.hash, &r.n_eff, sizeof r.n_eff);
         mix(out.hash, &r.W, sizeof r.W); mix(out.hash, &r.best, sizeof r.best); mix(out.hash, r.best_pose, sizeof r.best_pose);
         out.resampled += r.resampled;
+        if (out.kld) out.counts.push_back(mcl.particleCount());
         const double trace = r.covariance[0] + r.covariance[4] + r.covariance[8];
         if (k == 0) { out.first_n_eff = r.n_eff; out.first_trace = trace; }
         out.last_trace = trace;
@@ -189,8 +195,11 @@ inline int run_device(visfs_ba_handle* ba, Summary& out) {
 
 int main(int argc, char** argv) {
     bool host = false;
-    for (int i = 1; i < argc; ++i) if (std::strcmp(argv[i], "host") == 0) host = true;
     localise_step::Summary s;
+    for (int i = 1; i < argc; ++i) {
+        if (std::strcmp(argv[i], "host") == 0) host = true;
+        if (std::strcmp(argv[i], "kld") == 0) s.kld = true;
+    }
     int rc;
     try {
         if (host) {
@@ -207,9 +216,15 @@ int main(int argc, char** argv) {
     if (rc != 0) return 1;
     std::printf("{\"mode\": \"%s\", \"tiles\": %d, \"obstacle_cells\": %d, \"steps\": %d, \"particles\": %d, \"guess_error_m\": %.17g, "
                 "\"match_error_m\": %.17g, \"final_error_m\": %.17g, \"final_yaw_error_rad\": %.17g, \"first_n_eff\": %.17g, \"first_trace\": %.17g, "
-                "\"last_trace\": %.17g, \"resampled\": %d, \"hash\": \"%016llx\", \"field_launches\": %d, \"launches\": %d, \"copies\": %d, \"waits\": %d}\n",
+                "\"last_trace\": %.17g, \"resampled\": %d, \"hash\": \"%016llx\", \"field_launches\": %d, \"launches\": %d, \"copies\": %d, \"waits\": %d",
                 host ? "host" : "device", s.tiles, s.obstacles, localise_step::kSteps, localise_step::kParticles, s.guess_error, s.match_error,
                 s.final_error, s.final_yaw_error, s.first_n_eff, s.first_trace, s.last_trace, s.resampled, (unsigned long long)s.hash, s.field_launches,
                 s.launches, s.copies, s.waits);
+    if (s.kld) {
+        std::printf(", \"kld\": 1, \"counts\": [");
+        for (size_t i = 0; i < s.counts.size(); ++i) std::printf("%s%d", i ? ", " : "", s.counts[i]);
+        std::printf("]");
+    }
+    std::printf("}\n");
     return 0;
 }

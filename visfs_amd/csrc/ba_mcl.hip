@@ -15,7 +15,9 @@
 //                   item per new particle finds its ancestor by two binary searches and copies it into the other buffer.
 // No floating atomics, no workgroup waits for another: the kernels' order on the stream is the only dependence.  The one-core
 // twin calls the same functions of ba_mcl.hpp in plain loops.
-#include "ba_mcl.hpp"
+// A filter has an active count n, which is also the stride of its particle arrays; it is N unless the filter was made a KLD filter
+// (include/visfs_mcl_kld.h), whose fourth launch is k_mcl_kld_resample of ba_mcl_kld.hip.  ba_mcl_state.hpp holds the objects.
+#include "ba_mcl_state.hpp"
 #include "ba_map_access.hpp"
 
 #include <algorithm>
@@ -211,72 +213,15 @@ __global__ __launch_bounds__(kThreads) void k_mcl_resample(const Hdr* __restrict
 
 }  // namespace mcl
 
-struct visfs_mcl_field {
-    bool device = false;
-    int dev = 0;
-    hipStream_t stream = nullptr;
-    Limits L;
-    int32_t R = 0, T = 0, v_occ = 0;
-    std::vector<uint16_t> h_t;
-    std::vector<int64_t> h_q;                 // both flavours keep the table
-    uint16_t* d_t = nullptr;
-    int64_t* d_q = nullptr;
-    int32_t launches = 0, copies = 0, waits = 0;
-};
-
-struct visfs_mcl {
-    visfs_mcl_field* field = nullptr;
-    bool device = false;
-    int dev = 0;
-    hipStream_t stream = nullptr;
-    std::string err;
-    int32_t N = 0, P = 1, lanes = 0, cur = 0;
-    uint64_t seed = 0;
-    int64_t update = 0;
-    // twin: x, y, yaw, w each [N], two buffers
-    std::vector<double> h_st[2];
-    std::vector<int64_t> h_Q;
-    std::vector<int32_t> h_anc;
-    // device
-    double* d_st[2] = { nullptr, nullptr };
-    double* d_cs = nullptr;
-    int64_t* d_Q = nullptr;
-    int32_t* d_anc = nullptr;
-    uint64_t* d_C = nullptr;
-    uint64_t* d_bsum = nullptr;
-    double* d_part = nullptr;
-    double* d_pbw = nullptr;
-    int32_t* d_pbi = nullptr;
-    char* h_up = nullptr;                     // pinned: the header and the beams
-    char* d_up = nullptr;
-    Rec* h_rec = nullptr;                     // pinned
-    Rec* d_rec = nullptr;
-    visfs_mcl_result last;
-    bool have_last = false;
-    int32_t launches = 0, copies = 0, waits = 0;
-};
-
 namespace {
 
 constexpr size_t kUpBytes = sizeof(Hdr) + (size_t)VISFS_MCL_MAX_BEAMS * 2 * sizeof(double);
 static_assert(sizeof(Hdr) % 8 == 0 && sizeof(InitHdr) <= sizeof(Hdr), "the beams follow the header as doubles");
 
-int ffail(visfs_mcl* f, int rc, const std::string& why) { f->err = why; return rc; }
-
-#define MC_HIP(f, expr)                                                                                               \
-    do {                                                                                                              \
-        hipError_t e_ = (expr);                                                                                       \
-        if (e_ != hipSuccess) return ffail((f), VISFS_BA_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 #define MC_HIPQ(expr)                                                       \
     do {                                                                    \
         if ((expr) != hipSuccess) return (int)VISFS_BA_ERR_DEVICE;          \
     } while (0)
-
-template <class F> int guarded(F&& f) noexcept {
-    try { return f(); }
-    catch (...) { return (int)VISFS_BA_ERR_DEVICE; }
-}
 
 unsigned blocks_of(int64_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
 
@@ -344,6 +289,7 @@ FieldView view_of(const visfs_mcl_field* f) {
 }
 
 void mcl_free(visfs_mcl* f) {
+    if (f->kld) kld_free(f);
     if (f->device) {
         (void)hipSetDevice(f->dev);
         if (f->stream) (void)hipStreamSynchronize(f->stream);
@@ -377,12 +323,12 @@ int mcl_alloc(visfs_mcl* f) {
 int32_t lanes_for(const visfs_mcl* f, int32_t n) {
     if (f->lanes > 0) return f->lanes;
     int32_t G = 1;
-    while (G < 64 && (int64_t)f->N * G < 32768 && G < n) G *= 2;
+    while (G < 64 && (int64_t)f->n * G < 32768 && G < n) G *= 2;
     return G;
 }
 
 int device_update(visfs_mcl* f, const Hdr& H, const std::vector<double>& beams, Rec& rec) {
-    const int32_t N = f->N, blocks = (int32_t)blocks_of(N);
+    const int32_t N = H.N, blocks = (int32_t)blocks_of(N);                 // the active count
     MC_HIP(f, hipSetDevice(f->dev));
     std::memcpy(f->h_up, &H, sizeof H);
     if (!beams.empty()) std::memcpy(f->h_up + sizeof H, beams.data(), beams.size() * sizeof(double));
@@ -393,9 +339,15 @@ int device_update(visfs_mcl* f, const Hdr& H, const std::vector<double>& beams, 
     MC_HIP(f, hipGetLastError());
     hipLaunchKernelGGL(k_mcl_sums, dim3((unsigned)blocks), dim3(kThreads), 0, f->stream, up, st, f->d_cs, f->d_part, f->d_pbw, f->d_pbi);
     MC_HIP(f, hipGetLastError());
-    hipLaunchKernelGGL(k_mcl_finish, dim3((unsigned)blocks), dim3(kThreads), 0, f->stream, up, st, f->d_part, f->d_pbw, f->d_pbi, blocks, f->d_rec,
-                       f->d_C, f->d_bsum, f->d_anc);
+    hipLaunchKernelGGL(k_mcl_finish, dim3((unsigned)blocks), dim3(kThreads), 0, f->stream, up, st, f->d_part, f->d_pbw, f->d_pbi, blocks,
+                       f->kld ? kld_device_rec(f) : f->d_rec, f->d_C, f->d_bsum, f->d_anc);
     MC_HIP(f, hipGetLastError());
+    if (f->kld) {                                                          // k_mcl_kld_resample takes the fourth launch's place
+        const int rc = kld_device_resample(f, up, st, f->d_st[f->cur ^ 1], blocks, rec);
+        if (rc != VISFS_BA_OK) return rc;
+        f->launches = VISFS_MCL_UPDATE_LAUNCHES; f->copies = 2; f->waits = 1;
+        return VISFS_BA_OK;
+    }
     hipLaunchKernelGGL(k_mcl_resample, dim3((unsigned)blocks), dim3(kThreads), 0, f->stream, up, f->d_rec, st, f->d_st[f->cur ^ 1], f->d_C,
                        f->d_bsum, blocks, f->d_anc);
     MC_HIP(f, hipGetLastError());
@@ -407,7 +359,7 @@ int device_update(visfs_mcl* f, const Hdr& H, const std::vector<double>& beams, 
 }
 
 void host_update(visfs_mcl* f, const Hdr& H, const std::vector<double>& beams, Rec& rec) {
-    const size_t N = (size_t)f->N;
+    const size_t N = (size_t)H.N;                                          // the active count
     const FieldView F = view_of(f->field);
     std::vector<double>& st = f->h_st[f->cur];
     double *X = st.data(), *Y = X + N, *A = Y + N, *Wt = A + N;
@@ -441,6 +393,7 @@ void host_update(visfs_mcl* f, const Hdr& H, const std::vector<double>& beams, R
     }
     const uint64_t K = C[N];
     if (!rec.resampled || K == 0) { rec.resampled = 0; return; }
+    if (f->kld) { kld_host_resample(f, H, C, rec); return; }
     const uint64_t r0 = key(H.seed, H.update, (uint64_t)N, 0) % K;
     rec.K = K; rec.r0 = r0;
     std::vector<double>& out = f->h_st[f->cur ^ 1];
@@ -586,7 +539,7 @@ int visfs_mcl_create(visfs_mcl_field* field, int32_t n_particles, uint64_t seed,
     return guarded([&]() -> int {
         visfs_mcl* f = new visfs_mcl();
         f->field = field; f->device = field->device; f->dev = field->dev; f->stream = field->stream;
-        f->N = n_particles; f->P = pow2_at_least(n_particles); f->seed = seed;
+        f->N = f->n = n_particles; f->seed = seed;
         const size_t N = (size_t)n_particles;
         if (f->device) {
             const int rc = mcl_alloc(f);
@@ -640,7 +593,7 @@ int visfs_mcl_init(visfs_mcl* f, const double mean[3], const double sigma[3]) {
             MC_HIP(f, hipStreamSynchronize(f->stream));
             f->launches = VISFS_MCL_INIT_LAUNCHES; f->copies = 1; f->waits = 1;
         }
-        f->cur = 0; f->update = 0;
+        f->cur = 0; f->update = 0; f->n = f->N;
         return (int)VISFS_BA_OK;
     });
 }
@@ -665,8 +618,9 @@ int visfs_mcl_update(visfs_mcl* f, const visfs_mcl_params* p, const double odom_
             beams.push_back(px); beams.push_back(py);
         }
         H.n = (int32_t)(beams.size() / 2);
-        H.N = f->N; H.P = f->P;
-        H.ratio_n = p->n_eff_ratio * (double)f->N; H.inv_n = 1.0 / (double)f->N;
+        const int32_t n_before = f->n;
+        H.N = n_before; H.P = pow2_at_least(n_before);
+        H.ratio_n = p->n_eff_ratio * (double)n_before; H.inv_n = 1.0 / (double)n_before;
         H.seed = f->seed; H.update = (uint64_t)(f->update + 1);
         H.gate = ((f->update + 1) % p->resample_interval) == 0 ? 1 : 0;
         H.lanes = lanes_for(f, H.n);
@@ -676,6 +630,7 @@ int visfs_mcl_update(visfs_mcl* f, const visfs_mcl_params* p, const double odom_
         else { host_update(f, H, beams, rec); f->launches = f->copies = f->waits = 0; }
         f->update += 1;
         if (rec.resampled) f->cur ^= 1;
+        if (f->kld) kld_commit(f, rec, n_before);
         finalize(rec, H.n, f->update, f->last);
         f->have_last = true;
         if (result) *result = f->last;
@@ -693,7 +648,7 @@ int visfs_mcl_last_result(const visfs_mcl* f, visfs_mcl_result* result) {
 int visfs_mcl_download(visfs_mcl* f, double* x, double* y, double* yaw, double* w, int64_t* Q, int32_t* ancestors) {
     if (!f) return VISFS_BA_ERR_BAD_ARGUMENT;
     return guarded([&]() -> int {
-        const size_t N = (size_t)f->N;
+        const size_t N = (size_t)f->n;                                                 // the active count, and the arrays' stride
         double* dst[4] = { x, y, yaw, w };
         if (!f->device) {
             for (int k = 0; k < 4; ++k) if (dst[k]) std::memcpy(dst[k], f->h_st[f->cur].data() + k * N, N * sizeof(double));
@@ -713,8 +668,14 @@ int visfs_mcl_download(visfs_mcl* f, double* x, double* y, double* yaw, double* 
 
 int visfs_mcl_upload(visfs_mcl* f, const double* x, const double* y, const double* yaw, const double* w) {
     if (!f || !x || !y || !yaw || !w) return VISFS_BA_ERR_BAD_ARGUMENT;
+    return upload_n(f, f->N, x, y, yaw, w);
+}
+
+}  // extern "C"
+
+int mcl::upload_n(visfs_mcl* f, int32_t n, const double* x, const double* y, const double* yaw, const double* w) {
     return guarded([&]() -> int {
-        const size_t N = (size_t)f->N;
+        const size_t N = (size_t)n;
         double sum = 0.0;
         for (size_t j = 0; j < N; ++j) {
             if (!(std::fabs(x[j]) <= 1e9) || !(std::fabs(y[j]) <= 1e9) || !(yaw[j] > -kPi && yaw[j] <= kPi) || !(std::isfinite(w[j]) && w[j] >= 0.0))
@@ -725,14 +686,18 @@ int visfs_mcl_upload(visfs_mcl* f, const double* x, const double* y, const doubl
         const double* src[4] = { x, y, yaw, w };
         if (!f->device) {
             for (int k = 0; k < 4; ++k) std::memcpy(f->h_st[f->cur].data() + k * N, src[k], N * sizeof(double));
+            f->n = n;
             return (int)VISFS_BA_OK;
         }
         MC_HIP(f, hipSetDevice(f->dev));
         for (int k = 0; k < 4; ++k) MC_HIP(f, hipMemcpyAsync(f->d_st[f->cur] + k * N, src[k], N * sizeof(double), hipMemcpyHostToDevice, f->stream));
         MC_HIP(f, hipStreamSynchronize(f->stream));
+        f->n = n;
         return (int)VISFS_BA_OK;
     });
 }
+
+extern "C" {
 
 int visfs_mcl_hook_set_lanes(visfs_mcl* f, int32_t lanes) {
     if (!f) return VISFS_BA_ERR_BAD_ARGUMENT;

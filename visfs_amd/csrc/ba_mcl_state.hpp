@@ -1,0 +1,92 @@
+// The objects of include/visfs_mcl.h as ba_mcl.hip holds them, and what ba_mcl.hip and ba_mcl_kld.hip ask of each other
+// (include/visfs_mcl_kld.h).  Internal: nothing here is exported.
+#pragma once
+
+#include "ba_mcl.hpp"
+#include "ba_submap.hpp"
+
+#include <hip/hip_runtime.h>
+
+#include <string>
+#include <vector>
+
+namespace mcl { struct Kld; }
+
+struct visfs_mcl_field {
+    bool device = false;
+    int dev = 0;
+    hipStream_t stream = nullptr;
+    submap::Limits L;
+    int32_t R = 0, T = 0, v_occ = 0;
+    std::vector<uint16_t> h_t;
+    std::vector<int64_t> h_q;                 // both flavours keep the table
+    uint16_t* d_t = nullptr;
+    int64_t* d_q = nullptr;
+    int32_t launches = 0, copies = 0, waits = 0;
+};
+
+struct visfs_mcl {
+    visfs_mcl_field* field = nullptr;
+    bool device = false;
+    int dev = 0;
+    hipStream_t stream = nullptr;
+    std::string err;
+    int32_t N = 0, lanes = 0, cur = 0;
+    int32_t n = 0;                            // the active count, which is also the stride of the particle arrays: N unless kld moved it
+    uint64_t seed = 0;
+    int64_t update = 0;
+    // twin: x, y, yaw, w each [n] at stride n, two buffers of 4 N
+    std::vector<double> h_st[2];
+    std::vector<int64_t> h_Q;
+    std::vector<int32_t> h_anc;
+    // device
+    double* d_st[2] = { nullptr, nullptr };
+    double* d_cs = nullptr;
+    int64_t* d_Q = nullptr;
+    int32_t* d_anc = nullptr;
+    uint64_t* d_C = nullptr;
+    uint64_t* d_bsum = nullptr;
+    double* d_part = nullptr;
+    double* d_pbw = nullptr;
+    int32_t* d_pbi = nullptr;
+    char* h_up = nullptr;                     // pinned: the header and the beams
+    char* d_up = nullptr;
+    mcl::Rec* h_rec = nullptr;                // pinned
+    mcl::Rec* d_rec = nullptr;
+    visfs_mcl_result last;
+    bool have_last = false;
+    int32_t launches = 0, copies = 0, waits = 0;
+    mcl::Kld* kld = nullptr;                  // null: the plain filter
+};
+
+namespace mcl {
+
+inline int ffail(visfs_mcl* f, int rc, const std::string& why) { f->err = why; return rc; }
+
+#define MC_HIP(f, expr)                                                                                               \
+    do {                                                                                                              \
+        hipError_t e_ = (expr);                                                                                       \
+        if (e_ != hipSuccess) return mcl::ffail((f), VISFS_BA_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+template <class F> int guarded(F&& f) noexcept {
+    try { return f(); }
+    catch (...) { return (int)VISFS_BA_ERR_DEVICE; }
+}
+
+// ---- ba_mcl.hip
+// visfs_mcl_upload with a count: the refusals, the copy at stride n, and n becomes the active count.
+int upload_n(visfs_mcl* f, int32_t n, const double* x, const double* y, const double* yaw, const double* w);
+
+// ---- ba_mcl_kld.hip, called only when f->kld is set
+void kld_free(visfs_mcl* f);
+// Where k_mcl_finish writes the record of a KLD update: the head of the longer record that the update downloads.
+Rec* kld_device_rec(visfs_mcl* f);
+// The fourth launch of a KLD update, its one download and its one wait; `rec` and the pending counts are filled.
+int kld_device_resample(visfs_mcl* f, const Hdr* up, const double* st, double* out, int32_t blocks, Rec& rec);
+// The twin's resampling: C [n + 1] is the inclusive-exclusive prefix of the counts, rec.resampled is set.
+void kld_host_resample(visfs_mcl* f, const Hdr& H, const std::vector<uint64_t>& C, Rec& rec);
+// After an update that succeeded: the last KLD result, and the new active count.
+void kld_commit(visfs_mcl* f, const Rec& rec, int32_t n_before);
+
+}  // namespace mcl

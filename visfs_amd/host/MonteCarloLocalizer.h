@@ -17,6 +17,7 @@
 
 #include "GlobalMap2D.h"
 #include "visfs_mcl.h"
+#include "visfs_mcl_kld.h"
 
 namespace VISFS {
 
@@ -86,9 +87,20 @@ public:
         visfs_mcl_last_result(f_, &r);
         return r;
     }
-    // the particles on the host; any pointer may be null
+    // KLD-adaptive particle counts (include/visfs_mcl_kld.h): from now on a resampling draws only as many particles as the spread
+    // of the belief asks for, between minParticles and the particles of the constructor (at most 16384).  The other settings keep
+    // the header's defaults; there is no way back.
+    int enableKld(int minParticles, double kldErr, double kldZ) {
+        visfs_mcl_kld_params p;
+        visfs_mcl_kld_default_params(&p);
+        p.min_particles = minParticles; p.kld_err = kldErr; p.kld_z = kldZ;
+        return visfs_mcl_kld_enable(f_, &p);
+    }
+    // the active count: particles() unless enableKld() has let it fall
+    int particleCount() const { return visfs_mcl_kld_count(f_); }
+    // the particles on the host (particleCount() of them); any pointer may be null
     int download(std::vector<double>* x, std::vector<double>* y, std::vector<double>* yaw, std::vector<double>* w) const {
-        for (std::vector<double>* v : { x, y, yaw, w }) if (v) v->resize((size_t)n_);
+        for (std::vector<double>* v : { x, y, yaw, w }) if (v) v->resize((size_t)particleCount());
         return visfs_mcl_download(f_, x ? x->data() : nullptr, y ? y->data() : nullptr, yaw ? yaw->data() : nullptr, w ? w->data() : nullptr,
                                   nullptr, nullptr);
     }
