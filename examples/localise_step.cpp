@@ -2,7 +2,7 @@
 // (VISFS::MonteCarloLocalizer over include/visfs_mcl.h).
 //
 //   g++ -std=c++17 -O2 -Iinclude -Ivisfs_amd/host examples/localise_step.cpp -Lvisfs_amd/lib -lvisfs_ba_hip
-//       -Wl,-rpath,$PWD/visfs_amd/lib -o localise_step && ./localise_step [host] [kld]
+//       -Wl,-rpath,$PWD/visfs_amd/lib -o localise_step && ./localise_step [host] [kld | hyp]
 //
 // A robot drives 16 poses of a circle in a room and inserts every scan into the sub-maps; each finished front sub-map becomes a
 // tile of a global map, which is composed once.  From that map come a likelihood field and a scan stack.  The robot then starts
@@ -11,7 +11,8 @@
 // returns, and the estimate after each.  `host` runs the one-core twins.  Prints one JSON line; the device and the twin print the
 // same numbers and the same hash over every estimate's bits and the final particles.  `kld` makes the filter a KLD filter
 // (include/visfs_mcl_kld.h: min_particles 100, kld_err 0.01, kld_z 0.99, at most the 2000 it starts with) and adds the particle
-// count after every step to the line.
+// count after every step to the line.  `hyp` is `kld` with AMCL's pose hypotheses (include/visfs_mcl_hyp.h): for every step that
+// resampled the line also tells the number of clusters and the best hypothesis, the pose AMCL would publish, beside the mean.
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -65,8 +66,12 @@ struct Summary {
     int tiles = 0, obstacles = 0, resampled = 0, launches = 0, copies = 0, waits = 0, field_launches = 0;
     double match_error = 0.0, guess_error = 0.0, final_error = 0.0, final_yaw_error = 0.0, first_n_eff = 0.0, first_trace = 0.0, last_trace = 0.0;
     uint64_t hash = 1469598103934665603ull;
-    bool kld = false;
+    bool kld = false, hyp = false;
     std::vector<int> counts;      // the particle count after every step (kld only)
+    struct Hyp { int step, clusters, count; double best[3], mean[3]; };
+    std::vector<Hyp> hyps;        // of every step that resampled (hyp only)
+    uint64_t hyp_hash = 1469598103934665603ull;
+    double hyp_final_error = 0.0;
 };
 
 inline void mix(uint64_t& h, const void* p, size_t bytes) {
@@ -126,6 +131,7 @@ inline int run(visfs_ba_handle* ba, const Submaps& subs, Summary& out) {
     VISFS::MonteCarloLocalizer mcl(field, kParticles, 7);
     const double mean[3] = { m.x, m.y, m.yaw }, sigma[3] = { 0.3, 0.3, 0.15 };
     if (out.kld && mcl.enableKld(100, 0.01, 0.99) != VISFS_BA_OK) { std::fprintf(stderr, "enableKld failed: %s\n", mcl.lastError()); return 1; }
+    if (out.hyp && mcl.enableHypotheses() != VISFS_BA_OK) { std::fprintf(stderr, "enableHypotheses failed: %s\n", mcl.lastError()); return 1; }
     if (mcl.init(mean, sigma) != VISFS_BA_OK) { std::fprintf(stderr, "init failed: %s\n", mcl.lastError()); return 1; }
     for (int k = 0; k < kSteps; ++k) {
         truth = compose(truth, step);
@@ -138,6 +144,17 @@ inline int run(visfs_ba_handle* ba, const Submaps& subs, Summary& out) {
         mix(out.hash, &r.W, sizeof r.W); mix(out.hash, &r.best, sizeof r.best); mix(out.hash, r.best_pose, sizeof r.best_pose);
         out.resampled += r.resampled;
         if (out.kld) out.counts.push_back(mcl.particleCount());
+        if (out.hyp && r.resampled) {
+            const visfs_mcl_hyp_result h = mcl.hypotheses();
+            visfs_mcl_hypothesis best;
+            if (!h.fresh || h.update != r.update || !mcl.bestHypothesis(&best) || std::memcmp(&best, &h.hyp[0], sizeof best) != 0) {
+                std::fprintf(stderr, "step %d resampled, but its hypotheses are not the fresh ones of update %lld\n", k, (long long)r.update);
+                return 1;
+            }
+            mix(out.hyp_hash, &h, sizeof h);
+            out.hyps.push_back({ k, h.n_clusters, best.count, { best.mean[0], best.mean[1], best.mean[2] }, { r.mean[0], r.mean[1], r.mean[2] } });
+            out.hyp_final_error = std::hypot(best.mean[0] - truth.x, best.mean[1] - truth.y);
+        }
         const double trace = r.covariance[0] + r.covariance[4] + r.covariance[8];
         if (k == 0) { out.first_n_eff = r.n_eff; out.first_trace = trace; }
         out.last_trace = trace;
@@ -199,6 +216,7 @@ int main(int argc, char** argv) {
     for (int i = 1; i < argc; ++i) {
         if (std::strcmp(argv[i], "host") == 0) host = true;
         if (std::strcmp(argv[i], "kld") == 0) s.kld = true;
+        if (std::strcmp(argv[i], "hyp") == 0) s.kld = s.hyp = true;
     }
     int rc;
     try {
@@ -223,6 +241,15 @@ int main(int argc, char** argv) {
     if (s.kld) {
         std::printf(", \"kld\": 1, \"counts\": [");
         for (size_t i = 0; i < s.counts.size(); ++i) std::printf("%s%d", i ? ", " : "", s.counts[i]);
+        std::printf("]");
+    }
+    if (s.hyp) {
+        std::printf(", \"hyp\": 1, \"hyp_hash\": \"%016llx\", \"hyp_final_error_m\": %.17g, \"hypotheses\": [", (unsigned long long)s.hyp_hash, s.hyp_final_error);
+        for (size_t i = 0; i < s.hyps.size(); ++i) {
+            const auto& h = s.hyps[i];
+            std::printf("%s{\"step\": %d, \"clusters\": %d, \"count\": %d, \"best\": [%.17g, %.17g, %.17g], \"mean\": [%.17g, %.17g, %.17g]}", i ? ", " : "",
+                        h.step, h.clusters, h.count, h.best[0], h.best[1], h.best[2], h.mean[0], h.mean[1], h.mean[2]);
+        }
         std::printf("]");
     }
     std::printf("}\n");

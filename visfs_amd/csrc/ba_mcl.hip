@@ -594,6 +594,7 @@ int visfs_mcl_init(visfs_mcl* f, const double mean[3], const double sigma[3]) {
             f->launches = VISFS_MCL_INIT_LAUNCHES; f->copies = 1; f->waits = 1;
         }
         f->cur = 0; f->update = 0; f->n = f->N;
+        if (f->kld) kld_particles_replaced(f);
         return (int)VISFS_BA_OK;
     });
 }
@@ -687,12 +688,14 @@ int mcl::upload_n(visfs_mcl* f, int32_t n, const double* x, const double* y, con
         if (!f->device) {
             for (int k = 0; k < 4; ++k) std::memcpy(f->h_st[f->cur].data() + k * N, src[k], N * sizeof(double));
             f->n = n;
+            if (f->kld) kld_particles_replaced(f);
             return (int)VISFS_BA_OK;
         }
         MC_HIP(f, hipSetDevice(f->dev));
         for (int k = 0; k < 4; ++k) MC_HIP(f, hipMemcpyAsync(f->d_st[f->cur] + k * N, src[k], N * sizeof(double), hipMemcpyHostToDevice, f->stream));
         MC_HIP(f, hipStreamSynchronize(f->stream));
         f->n = n;
+        if (f->kld) kld_particles_replaced(f);
         return (int)VISFS_BA_OK;
     });
 }

@@ -9,8 +9,11 @@
 //                   copies the n* ancestors into the other buffer at stride n*.
 // Integer LDS atomics only; no work item waits for another (a probe ends because the table is never full).  The one-core twin runs
 // the definition's sequential loop with a std::set of bins.
+// On a filter with hypotheses (include/visfs_mcl_hyp.h) the launch is the kernel's second instantiation,
+// which clusters the new set's bins behind step 7 (hyp_tail of ba_mcl_hyp.hpp); the first is the kernel as it was.
 #include "ba_mcl_state.hpp"
 #include "ba_mcl_kld.hpp"
+#include "ba_mcl_hyp.hpp"
 
 #include <algorithm>
 #include <array>
@@ -24,6 +27,8 @@ using namespace mcl;
 
 namespace mcl {
 
+struct Hyp;
+
 struct Kld {
     visfs_mcl_kld_params p;
     std::vector<int32_t> h_limit;             // [N + 1], both flavours
@@ -35,6 +40,19 @@ struct Kld {
     int32_t pending[3] = { 0, 0, 0 };         // n_after, bins, limit of the update that is running
     visfs_mcl_kld_result last;
     bool have_last = false;
+    Hyp* hyp = nullptr;                       // null: no hypotheses (include/visfs_mcl_hyp.h)
+};
+
+// The hypotheses of section 9v on a KLD filter.
+struct Hyp {
+    int32_t* d_work = nullptr;                // [kHypWorkInts N]
+    double* d_cs = nullptr;                   // [2 N]
+    HypRec* d_rec = nullptr;                  // takes the place of Kld::d_rec
+    HypRec* h_rec = nullptr;                  // pinned
+    HypBlock pending;                         // of the update that is running
+    std::vector<int32_t> h_label;             // the twin's labels of the last resampling
+    visfs_mcl_hyp_result last;                // all zero while there are none
+    int32_t rounds = 0;
 };
 
 __device__ inline uint64_t shfl_up64(uint64_t v, int d) {
@@ -60,9 +78,13 @@ __device__ inline uint32_t kld_insert(int32_t* table, uint32_t mask, uint32_t h,
     }
 }
 
+// Two instantiations: <false> is the KLD resampling alone; <true> adds the hypotheses of section 9v (ba_mcl_hyp.hpp) behind the new
+// set, and its rec is the head of a HypRec.
+template <bool HYP>
 __global__ __launch_bounds__(kKldThreads) void k_mcl_kld_resample(const Hdr* __restrict__ up, KldRec* __restrict__ rec, const double* __restrict__ st,
                                                                   double* __restrict__ out, const uint64_t* __restrict__ C,
-                                                                  const uint64_t* __restrict__ bsum, int32_t blocks, int32_t* __restrict__ anc, KldArgs A) {
+                                                                  const uint64_t* __restrict__ bsum, int32_t blocks, int32_t* __restrict__ anc, KldArgs A,
+                                                                  HypArgs G) {
     __shared__ int32_t table[kKldMaxSlots];
     __shared__ uint64_t sc[kKldMaxBlocks];                                 // the exclusive offsets of k_mcl_finish's workgroups
     __shared__ uint64_t s_K;
@@ -164,6 +186,24 @@ __global__ __launch_bounds__(kKldThreads) void k_mcl_kld_resample(const Hdr* __r
         out[3 * (size_t)n_new + i] = inv;
         anc[i] = a;
     }
+    if constexpr (HYP) {
+        __shared__ int32_t s_bins;
+        if (cand_m == n_new) s_bins = cand_k;                              // the bins of the new set, from the one work item that knows
+        __syncthreads();                                                   // ... and the new set is written before its poses are read
+        hyp_tail(table, mask, (uint32_t)A.home_mask, w_slot, w_bin, n_new, s_bins, cap, out, G, &reinterpret_cast<HypRec*>(rec)->h);
+    }
+}
+
+// Frees what a Hyp holds on the device (the stream is idle) and the object.
+void hyp_free(visfs_mcl* f, Hyp* h) {
+    if (!h) return;
+    if (f->device) {
+        if (h->d_work) (void)hipFree(h->d_work);
+        if (h->d_cs) (void)hipFree(h->d_cs);
+        if (h->d_rec) (void)hipFree(h->d_rec);
+        if (h->h_rec) (void)hipHostFree(h->h_rec);
+    }
+    delete h;
 }
 
 void kld_free(visfs_mcl* f) {
@@ -172,16 +212,25 @@ void kld_free(visfs_mcl* f) {
     if (f->device) {
         (void)hipSetDevice(f->dev);
         if (f->stream) (void)hipStreamSynchronize(f->stream);
+        hyp_free(f, k->hyp);
         if (k->d_limit) (void)hipFree(k->d_limit);
         if (k->d_work) (void)hipFree(k->d_work);
         if (k->d_rec) (void)hipFree(k->d_rec);
         if (k->h_rec) (void)hipHostFree(k->h_rec);
     }
+    else hyp_free(f, k->hyp);
     delete k;
     f->kld = nullptr;
 }
 
-Rec* kld_device_rec(visfs_mcl* f) { return &f->kld->d_rec->r; }
+Rec* kld_device_rec(visfs_mcl* f) { return f->kld->hyp ? &f->kld->hyp->d_rec->k.r : &f->kld->d_rec->r; }
+
+void kld_particles_replaced(visfs_mcl* f) {
+    Hyp* h = f->kld->hyp;
+    if (!h) return;
+    std::memset(&h->last, 0, sizeof h->last);
+    h->rounds = 0;
+}
 
 int kld_device_resample(visfs_mcl* f, const Hdr* up, const double* st, double* out, int32_t blocks, Rec& rec) {
     Kld* k = f->kld;
@@ -194,7 +243,21 @@ int kld_device_resample(visfs_mcl* f, const Hdr* up, const double* st, double* o
     while ((1 << width) < A.slots) ++width;
     const int32_t bits = k->hash_bits < 0 || k->hash_bits > width ? width : k->hash_bits;
     A.home_mask = (int32_t)((1u << bits) - 1u);
-    hipLaunchKernelGGL(k_mcl_kld_resample, dim3(1), dim3(kKldThreads), 0, f->stream, up, k->d_rec, st, out, f->d_C, f->d_bsum, blocks, f->d_anc, A);
+    if (Hyp* h = k->hyp) {                                                 // the same launch with the hypotheses; their block comes down behind KldRec
+        HypArgs G;
+        G.work = h->d_work; G.cs = h->d_cs;
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mcl_kld_resample<true>), dim3(1), dim3(kKldThreads), 0, f->stream, up, &h->d_rec->k, st, out, f->d_C, f->d_bsum, blocks,
+                           f->d_anc, A, G);
+        MC_HIP(f, hipGetLastError());
+        MC_HIP(f, hipMemcpyAsync(h->h_rec, h->d_rec, sizeof(HypRec), hipMemcpyDeviceToHost, f->stream));
+        MC_HIP(f, hipStreamSynchronize(f->stream));
+        rec = h->h_rec->k.r;
+        k->pending[0] = h->h_rec->k.n_after; k->pending[1] = h->h_rec->k.bins; k->pending[2] = h->h_rec->k.limit;
+        h->pending = h->h_rec->h;
+        return VISFS_BA_OK;
+    }
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mcl_kld_resample<false>), dim3(1), dim3(kKldThreads), 0, f->stream, up, k->d_rec, st, out, f->d_C, f->d_bsum, blocks,
+                       f->d_anc, A, HypArgs());
     MC_HIP(f, hipGetLastError());
     MC_HIP(f, hipMemcpyAsync(k->h_rec, k->d_rec, sizeof(KldRec), hipMemcpyDeviceToHost, f->stream));
     MC_HIP(f, hipStreamSynchronize(f->stream));
@@ -230,6 +293,7 @@ void kld_host_resample(visfs_mcl* f, const Hdr& H, const std::vector<uint64_t>& 
     }
     rec.K = K; rec.r0 = 0;
     k->pending[0] = m; k->pending[1] = bins; k->pending[2] = k->h_limit[(size_t)bins];
+    if (Hyp* h = k->hyp) hyp_host(out.data(), out.data() + ns, out.data() + 2 * ns, m, k->p.bin_xy, k->p.bin_yaw, h->h_label, h->pending);
 }
 
 void kld_commit(visfs_mcl* f, const Rec& rec, int32_t n_before) {
@@ -238,7 +302,12 @@ void kld_commit(visfs_mcl* f, const Rec& rec, int32_t n_before) {
     if (rec.resampled) {
         k->last.n_after = k->pending[0]; k->last.bins = k->pending[1]; k->last.limit = k->pending[2];
         f->n = k->pending[0];
+        if (Hyp* h = k->hyp) {
+            hyp_finish(h->pending, k->pending[0], f->update, h->last);
+            h->rounds = h->pending.rounds;
+        }
     } else {
+        if (k->hyp) k->hyp->last.fresh = 0;                                // the last hypotheses stay readable
         k->last.n_after = n_before; k->last.bins = 0; k->last.limit = 0;
     }
     k->have_last = true;
@@ -330,6 +399,65 @@ int visfs_mcl_kld_hook_set_hash_bits(visfs_mcl* f, int32_t bits) {
     if (!f->kld) return ffail(f, VISFS_BA_ERR_BAD_ARGUMENT, "the filter is no KLD filter");
     if (bits < -1) return VISFS_BA_ERR_BAD_ARGUMENT;
     f->kld->hash_bits = bits;
+    return VISFS_BA_OK;
+}
+
+// ---------------------------------------------------------------------- include/visfs_mcl_hyp.h
+int visfs_mcl_hyp_abi_version(void) { return VISFS_MCL_HYP_ABI_VERSION; }
+
+int visfs_mcl_hyp_enable(visfs_mcl* f) {
+    if (!f) return VISFS_BA_ERR_BAD_ARGUMENT;
+    if (!f->kld) return ffail(f, VISFS_BA_ERR_BAD_ARGUMENT, "the filter is no KLD filter");
+    if (f->kld->hyp) return VISFS_BA_OK;
+    return guarded([&]() -> int {
+        Hyp* h = new Hyp();
+        std::memset(&h->pending, 0, sizeof h->pending);
+        std::memset(&h->last, 0, sizeof h->last);
+        auto push = [&]() -> int {
+            if (!f->device) return (int)VISFS_BA_OK;
+            const size_t N = (size_t)f->N;
+            MC_HIP(f, hipSetDevice(f->dev));
+            MC_HIP(f, hipMalloc(reinterpret_cast<void**>(&h->d_work), (size_t)kHypWorkInts * N * sizeof(int32_t)));
+            MC_HIP(f, hipMalloc(reinterpret_cast<void**>(&h->d_cs), 2 * N * sizeof(double)));
+            MC_HIP(f, hipMalloc(reinterpret_cast<void**>(&h->d_rec), sizeof(HypRec)));
+            MC_HIP(f, hipHostMalloc(reinterpret_cast<void**>(&h->h_rec), sizeof(HypRec), hipHostMallocDefault));
+            MC_HIP(f, hipMemsetAsync(h->d_rec, 0, sizeof(HypRec), f->stream));
+            MC_HIP(f, hipStreamSynchronize(f->stream));
+            return (int)VISFS_BA_OK;
+        };
+        const int rc = push();
+        if (rc != VISFS_BA_OK) { hyp_free(f, h); return rc; }
+        f->kld->hyp = h;
+        return (int)VISFS_BA_OK;
+    });
+}
+
+int visfs_mcl_hyp_last(const visfs_mcl* f, visfs_mcl_hyp_result* r) {
+    if (!f || !r) return VISFS_BA_ERR_BAD_ARGUMENT;
+    if (!f->kld || !f->kld->hyp) { std::memset(r, 0, sizeof *r); return VISFS_BA_ERR_BAD_ARGUMENT; }
+    *r = f->kld->hyp->last;
+    return VISFS_BA_OK;
+}
+
+int visfs_mcl_hyp_download_labels(visfs_mcl* f, int32_t* label) {
+    if (!f || !label) return VISFS_BA_ERR_BAD_ARGUMENT;
+    if (!f->kld || !f->kld->hyp) return ffail(f, VISFS_BA_ERR_BAD_ARGUMENT, "hypotheses are not enabled");
+    Hyp* h = f->kld->hyp;
+    if (h->last.n_hypotheses == 0) return ffail(f, VISFS_BA_ERR_BAD_ARGUMENT, "there are no hypotheses since the particles were replaced");
+    return guarded([&]() -> int {
+        const size_t bytes = (size_t)h->last.n * sizeof(int32_t);
+        if (!f->device) { std::memcpy(label, h->h_label.data(), bytes); return (int)VISFS_BA_OK; }
+        MC_HIP(f, hipSetDevice(f->dev));
+        MC_HIP(f, hipMemcpyAsync(label, h->d_work, bytes, hipMemcpyDeviceToHost, f->stream));
+        MC_HIP(f, hipStreamSynchronize(f->stream));
+        return (int)VISFS_BA_OK;
+    });
+}
+
+int visfs_mcl_hyp_hook_rounds(const visfs_mcl* f, int32_t* rounds) {
+    if (!f || !rounds) return VISFS_BA_ERR_BAD_ARGUMENT;
+    if (!f->kld || !f->kld->hyp) { *rounds = 0; return VISFS_BA_ERR_BAD_ARGUMENT; }
+    *rounds = f->kld->hyp->rounds;
     return VISFS_BA_OK;
 }
 

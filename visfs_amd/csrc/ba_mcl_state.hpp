@@ -88,5 +88,7 @@ int kld_device_resample(visfs_mcl* f, const Hdr* up, const double* st, double* o
 void kld_host_resample(visfs_mcl* f, const Hdr& H, const std::vector<uint64_t>& C, Rec& rec);
 // After an update that succeeded: the last KLD result, and the new active count.
 void kld_commit(visfs_mcl* f, const Rec& rec, int32_t n_before);
+// After an init or an upload that succeeded: hypotheses of the particles that were replaced (include/visfs_mcl_hyp.h) are gone.
+void kld_particles_replaced(visfs_mcl* f);
 
 }  // namespace mcl

@@ -18,6 +18,7 @@
 #include "GlobalMap2D.h"
 #include "visfs_mcl.h"
 #include "visfs_mcl_kld.h"
+#include "visfs_mcl_hyp.h"
 
 namespace VISFS {
 
@@ -95,6 +96,22 @@ public:
         visfs_mcl_kld_default_params(&p);
         p.min_particles = minParticles; p.kld_err = kldErr; p.kld_z = kldZ;
         return visfs_mcl_kld_enable(f_, &p);
+    }
+    // AMCL's pose hypotheses (include/visfs_mcl_hyp.h), after enableKld(): from now on every resampling also clusters the new
+    // particles and keeps the mean and covariance of the at most VISFS_MCL_HYP_MAX largest clusters.  There is no way back.
+    int enableHypotheses() { return visfs_mcl_hyp_enable(f_); }
+    // the hypotheses of the last resampling, the largest first; n_hypotheses is 0 before the first one and when they are not enabled
+    visfs_mcl_hyp_result hypotheses() const {
+        visfs_mcl_hyp_result r{};
+        visfs_mcl_hyp_last(f_, &r);
+        return r;
+    }
+    // The pose AMCL would publish: the mean of the cluster that holds the most particles.  False while there is no hypothesis.
+    bool bestHypothesis(visfs_mcl_hypothesis* out) const {
+        const visfs_mcl_hyp_result r = hypotheses();
+        if (r.n_hypotheses < 1) return false;
+        if (out) *out = r.hyp[0];
+        return true;
     }
     // the active count: particles() unless enableKld() has let it fall
     int particleCount() const { return visfs_mcl_kld_count(f_); }
