@@ -1,4 +1,5 @@
 """Build helper: hipcc for the gfx950 library (the test-side checker under oracle/ has its own Makefile)."""
+import glob
 import os
 import shutil
 import subprocess
@@ -8,11 +9,7 @@ CSRC = os.path.join(ROOT, "visfs_amd", "csrc")
 LIB_DIR = os.path.join(ROOT, "visfs_amd", "lib")
 LIB = os.path.join(LIB_DIR, "libvisfs_ba_hip.so")
 SOURCES = ["ba_kernels.hip", "ba_cov.hip", "ba_submap.hip", "ba_flow.hip", "ba_corners.hip", "ba_clahe.hip", "ba_pnp.hip", "ba_fund.hip", "ba_tracker.hip", "ba_scan.hip", "ba_scan_fast.hip", "ba_api.cpp", "ba_scan_group.hip", "ba_scan_refine.hip", "ba_pose_graph.hip", "ba_pose_graph_cov.hip", "ba_map.hip", "ba_scan_filter.hip", "ba_mcl.hip", "ba_mcl_kld.hip"]
-HEADERS = ["ba_math.hpp", "ba_pnp.hpp", os.path.join("..", "..", "include", "visfs_pnp.h"), "ba_fund.hpp", os.path.join("..", "..", "include", "visfs_fund.h"), "ba_device.hpp", "ba_limits.hpp", "ba_plan.hpp", "ba_kernels.hpp", "ba_cov.hpp", "ba_submap.hpp", "ba_submap_access.hpp", "ba_scan.hpp", os.path.join("..", "..", "include", "visfs_scan_match.h"), "ba_scan_fast.hpp", os.path.join("..", "..", "include", "visfs_scan_fast.h"), "ba_scan_stack.hpp", "ba_scan_stack_access.hpp", "ba_map.hpp", os.path.join("..", "..", "include", "visfs_map.h"), "ba_scan_filter.hpp", os.path.join("..", "..", "include", "visfs_scan_filter.h"), "ba_map_access.hpp", "ba_mcl.hpp", os.path.join("..", "..", "include", "visfs_mcl.h"), "ba_mcl_state.hpp", "ba_mcl_kld.hpp", os.path.join("..", "..", "include", "visfs_mcl_kld.h"), "ba_mcl_hyp.hpp", os.path.join("..", "..", "include", "visfs_mcl_hyp.h"), os.path.join("..", "..", "include", "visfs_scan_group.h"), "ba_scan_refine.hpp", os.path.join("..", "..", "include", "visfs_scan_refine.h"), "ba_pose_graph.hpp", "ba_pose_graph_object.hpp", "ba_pose_graph_cov.hpp", os.path.join("..", "..", "include", "visfs_pose_graph.h"), os.path.join("..", "..", "include", "visfs_pose_graph_cov.h"), "ba_flow.hpp", "ba_flow_object.hpp", "ba_corners.hpp", "ba_group.hpp", "worker_pool.hpp", os.path.join("..", "..", "include", "visfs_ba.h"),
-           os.path.join("..", "..", "include", "visfs_submap.h"), os.path.join("..", "..", "include", "visfs_flow.h"),
-           os.path.join("..", "..", "include", "visfs_corners.h"), "ba_clahe.hpp", os.path.join("..", "..", "include", "visfs_clahe.h"),
-           "ba_tracker.hpp", os.path.join("..", "..", "include", "visfs_tracker.h"),
-           os.path.join("..", "..", "include", "visfs_tracker_group.h"), os.path.join("..", "..", "include", "visfs_tracker_pnp.h")]
+HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.hpp")) + glob.glob(os.path.join(ROOT, "include", "*.h")))      # every header: a new one cannot be forgotten
 
 
 # ba_kernels.hip alone is compiled with kernel-argument preloading: the leading scalar parameters of its k_*_head kernels
@@ -33,7 +30,7 @@ def _stale(target, deps):
 def build_hip(force=False, verbose=False):
     """hipcc --offload-arch=gfx950 → visfs_amd/lib/libvisfs_ba_hip.so (in-tree, travels with gpurun)."""
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
-    deps = srcs + [os.path.join(CSRC, h) for h in HEADERS]
+    deps = srcs + HEADERS
     if not force and not _stale(LIB, deps):
         return LIB
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"

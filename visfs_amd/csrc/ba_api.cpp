@@ -25,12 +25,14 @@
 
 #include "../../include/visfs_ba.h"
 #include "ba_cov.hpp"
+#include "ba_host.hpp"
 #include "ba_kernels.hpp"
 #include "ba_plan.hpp"
 #include "ba_submap.hpp"
 #include "worker_pool.hpp"
 
 using namespace visfs_ba;
+using namespace host;
 
 static_assert(MAX_TRACE == VISFS_BA_MAX_TRACE, "trace size mismatch");
 
@@ -187,15 +189,6 @@ struct visfs_ba_handle {
 
 namespace {
 
-#define HIP_TRY(h, expr)                                                                  \
-    do {                                                                                  \
-        hipError_t e_ = (expr);                                                           \
-        if (e_ != hipSuccess) {                                                           \
-            (h)->err = std::string(#expr) + ": " + hipGetErrorString(e_);                 \
-            return VISFS_BA_ERR_DEVICE;                                                   \
-        }                                                                                 \
-    } while (0)
-
 int bad(visfs_ba_handle* h, const char* msg) { h->err = msg; return VISFS_BA_ERR_BAD_ARGUMENT; }
 
 // Host threads for the O(N_obs) passes of a window solve: VISFS_BA_THREADS in total, 1 = none.  Default: the cores that share the
@@ -212,15 +205,6 @@ WorkerPool* host_pool(visfs_ba_handle* h) {
         if (n > 1) { try { h->pool.reset(new WorkerPool(n - 1)); } catch (...) { h->pool.reset(); } }
     }
     return h->pool.get();
-}
-
-// No exception may cross the C ABI: host allocations (std::vector, std::string, std::thread) can throw.
-template <typename F>
-int guarded(visfs_ba_handle* h, F&& f) noexcept {
-    try { return f(); }
-    catch (const std::bad_alloc&) { try { if (h) h->err = "out of host memory"; } catch (...) {} return VISFS_BA_ERR_DEVICE; }
-    catch (const std::exception& e) { try { if (h) h->err = e.what(); } catch (...) {} return VISFS_BA_ERR_DEVICE; }
-    catch (...) { return VISFS_BA_ERR_DEVICE; }
 }
 
 void ws_release(Workspace& w) {

@@ -14,6 +14,7 @@
 #include "ba_clahe.hpp"
 #include "ba_flow_object.hpp"
 #include "ba_group.hpp"
+#include "ba_host.hpp"
 #include "../../include/visfs_clahe.h"
 
 #include <cstring>
@@ -22,6 +23,7 @@
 #include <vector>
 
 using namespace clahe;
+using namespace host;
 
 // ---------------------------------------------------------------- kernels
 namespace clahe {
@@ -193,19 +195,6 @@ using flow::ClaheState;
 
 constexpr size_t kTableCells = (size_t)kMaxTiles * kMaxTiles * kBins;      // of one image
 
-int fail(visfs_flow* f, int rc, const std::string& why) { f->err = why; return rc; }
-#define CL_HIP(f, expr)                                                                                   \
-    do {                                                                                                  \
-        hipError_t e_ = (expr);                                                                           \
-        if (e_ != hipSuccess) return fail((f), VISFS_BA_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-template <class F> int guarded_cl(visfs_flow* f, F&& fn) noexcept {
-    try { return fn(); }
-    catch (const std::bad_alloc&) { if (f) f->err = "out of host memory"; return VISFS_BA_ERR_DEVICE; }
-    catch (...) { if (f) f->err = "unexpected exception"; return VISFS_BA_ERR_DEVICE; }
-}
-
 int check_params(const visfs_clahe_params* p, int32_t w, int32_t h, const char** why) {
     if (!std::isfinite(p->clip_limit) || p->clip_limit < 0.0) { *why = "clip_limit must be finite and not negative"; return VISFS_BA_ERR_BAD_ARGUMENT; }
     if (p->tiles_x < 1 || p->tiles_y < 1) { *why = "a tile count is below 1"; return VISFS_BA_ERR_BAD_ARGUMENT; }
@@ -224,10 +213,10 @@ int ensure_state(visfs_flow* f) {
     const size_t n0 = (size_t)f->w * f->h;
     c->raw_stride = (n0 + 255) & ~size_t(255);
     const auto alloc = [&]() -> int {
-        CL_HIP(f, hipSetDevice(f->dev));
-        CL_HIP(f, hipMalloc(reinterpret_cast<void**>(&c->d_raw), 2 * c->raw_stride));
-        CL_HIP(f, hipMalloc(reinterpret_cast<void**>(&c->d_lut), 2 * kTableCells));
-        CL_HIP(f, hipMalloc(reinterpret_cast<void**>(&c->d_hist), 2 * kTableCells * sizeof(int32_t)));
+        HIP_TRY(f, hipSetDevice(f->dev));
+        HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&c->d_raw), 2 * c->raw_stride));
+        HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&c->d_lut), 2 * kTableCells));
+        HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&c->d_hist), 2 * kTableCells * sizeof(int32_t)));
         return VISFS_BA_OK;
     };
     const int rc = alloc();
@@ -275,11 +264,11 @@ int device_equalise(visfs_flow* f, ClaheState* c, const Geom& g, int slot, const
         P.dst[i] = f->dpx[slot][i];
     }
     hipLaunchKernelGGL(k_clahe_lut, dim3((unsigned)(g.tiles_x * g.tiles_y), 2), dim3(CL_T), 0, f->stream, L, g);
-    CL_HIP(f, hipGetLastError());
+    HIP_TRY(f, hipGetLastError());
     const int64_t per_block = (int64_t)CL_T * CL_PX;
     const unsigned blocks = (unsigned)(((int64_t)g.w * g.h + per_block - 1) / per_block);
     hipLaunchKernelGGL(k_clahe_apply, dim3(blocks, 2), dim3(CL_T), 0, f->stream, P, g);
-    CL_HIP(f, hipGetLastError());
+    HIP_TRY(f, hipGetLastError());
     return flow::device_pyramids(f, slot);
 }
 
@@ -305,12 +294,12 @@ void group_clahe_fill(visfs_flow* f, const Geom& g, int slot, ClaheRec* r, uint8
 
 int group_clahe(visfs_flow* f, const Geom& g, int n, const ClaheRec* d_recs, GroupCounts* cnt) {
     hipLaunchKernelGGL(k_clahe_lut_g, dim3((unsigned)(g.tiles_x * g.tiles_y), 2, (unsigned)n), dim3(CL_T), 0, f->stream, d_recs, g);
-    CL_HIP(f, hipGetLastError());
+    HIP_TRY(f, hipGetLastError());
     const int64_t per_block = (int64_t)CL_T * CL_PX;
     const unsigned blocks = (unsigned)(((int64_t)g.w * g.h + per_block - 1) / per_block);
     hipLaunchKernelGGL(k_clahe_apply_g, dim3(blocks, 2, (unsigned)n), dim3(CL_T), 0, f->stream, d_recs, g);
-    CL_HIP(f, hipGetLastError());
-    cnt->kernels += 2;
+    HIP_TRY(f, hipGetLastError());
+    cnt->launches += 2;
     return VISFS_BA_OK;
 }
 
@@ -330,7 +319,7 @@ void visfs_clahe_default_params(visfs_clahe_params* p) {
 
 int visfs_flow_push_frame_clahe(visfs_flow* f, const visfs_clahe_params* p, const uint8_t* left, const uint8_t* right, int32_t stride) {
     if (!f) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded_cl(f, [&]() -> int {
+    return guarded(f, [&]() -> int {
         if (!p || !left || !right) return fail(f, VISFS_BA_ERR_BAD_ARGUMENT, "a NULL argument");
         const char* why = "";
         int rc = check_params(p, f->w, f->h, &why);
@@ -388,7 +377,7 @@ int visfs_flow_clahe_last_tiles(const visfs_flow* f, int32_t* tiles_x, int32_t* 
 int visfs_flow_clahe_download(const visfs_flow* cf, int32_t image, uint8_t* lut, int32_t* hist) {
     visfs_flow* f = const_cast<visfs_flow*>(cf);
     if (!f) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded_cl(f, [&]() -> int {
+    return guarded(f, [&]() -> int {
         if (image < 0 || image > 1) return fail(f, VISFS_BA_ERR_BAD_ARGUMENT, "image out of range");
         const ClaheState* c = f->clahe;
         if (!c || !c->valid) return fail(f, VISFS_BA_ERR_NOT_LOADED, "no equalised push to report on");
@@ -398,10 +387,10 @@ int visfs_flow_clahe_download(const visfs_flow* cf, int32_t image, uint8_t* lut,
             if (hist) std::memcpy(hist, c->hhist[image].data(), tile_cells * sizeof(int32_t));
             return (int)VISFS_BA_OK;
         }
-        CL_HIP(f, hipSetDevice(f->dev));
-        if (lut) CL_HIP(f, hipMemcpyAsync(lut, c->d_lut + image * tile_cells, tile_cells, hipMemcpyDeviceToHost, f->stream));
-        if (hist) CL_HIP(f, hipMemcpyAsync(hist, c->d_hist + image * tile_cells, tile_cells * sizeof(int32_t), hipMemcpyDeviceToHost, f->stream));
-        CL_HIP(f, hipStreamSynchronize(f->stream));
+        HIP_TRY(f, hipSetDevice(f->dev));
+        if (lut) HIP_TRY(f, hipMemcpyAsync(lut, c->d_lut + image * tile_cells, tile_cells, hipMemcpyDeviceToHost, f->stream));
+        if (hist) HIP_TRY(f, hipMemcpyAsync(hist, c->d_hist + image * tile_cells, tile_cells * sizeof(int32_t), hipMemcpyDeviceToHost, f->stream));
+        HIP_TRY(f, hipStreamSynchronize(f->stream));
         return (int)VISFS_BA_OK;
     });
 }

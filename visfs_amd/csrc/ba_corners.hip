@@ -16,6 +16,7 @@
 #include "ba_corners.hpp"
 #include "ba_flow_object.hpp"
 #include "ba_group.hpp"
+#include "ba_host.hpp"
 #include "../../include/visfs_corners.h"
 
 #include <algorithm>
@@ -24,6 +25,7 @@
 #include <new>
 
 using namespace flow;
+using namespace host;
 
 // ---------------------------------------------------------------- kernels
 namespace flow {
@@ -348,19 +350,6 @@ namespace {
 
 constexpr size_t kOutBytes = sizeof(CornerDev) + sizeof(float) * 2 * kMaxCorners;
 
-int fail(visfs_flow* f, int rc, const std::string& why) { f->err = why; return rc; }
-#define CR_HIP(f, expr)                                                                                   \
-    do {                                                                                                  \
-        hipError_t e_ = (expr);                                                                           \
-        if (e_ != hipSuccess) return fail((f), VISFS_BA_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-template <class F> int guarded_cr(visfs_flow* f, F&& fn) noexcept {
-    try { return fn(); }
-    catch (const std::bad_alloc&) { if (f) f->err = "out of host memory"; return VISFS_BA_ERR_DEVICE; }
-    catch (...) { if (f) f->err = "unexpected exception"; return VISFS_BA_ERR_DEVICE; }
-}
-
 size_t max_candidates(const visfs_flow* f) { return (size_t)std::max(f->w - 2, 0) * (size_t)std::max(f->h - 2, 0); }
 
 // the first call of an object allocates; a call that fails here leaves the object without corner state
@@ -371,13 +360,13 @@ int ensure_state(visfs_flow* f) {
     if (!f->device) return VISFS_BA_OK;
     const size_t n0 = (size_t)f->w * f->h, nc = std::max<size_t>(max_candidates(f), 1);
     const auto alloc = [&]() -> int {
-        CR_HIP(f, hipSetDevice(f->dev));
-        CR_HIP(f, hipMalloc(reinterpret_cast<void**>(&c->d_eig), n0 * sizeof(float)));
-        CR_HIP(f, hipMalloc(reinterpret_cast<void**>(&c->d_mask), n0));
-        CR_HIP(f, hipMalloc(reinterpret_cast<void**>(&c->d_keys), 2 * nc * sizeof(uint64_t)));
+        HIP_TRY(f, hipSetDevice(f->dev));
+        HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&c->d_eig), n0 * sizeof(float)));
+        HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&c->d_mask), n0));
+        HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&c->d_keys), 2 * nc * sizeof(uint64_t)));
         c->d_sorted = c->d_keys + nc;
-        CR_HIP(f, hipMalloc(reinterpret_cast<void**>(&c->d_out), kOutBytes));
-        CR_HIP(f, hipHostMalloc(reinterpret_cast<void**>(&c->h_out), kOutBytes, hipHostMallocDefault));
+        HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&c->d_out), kOutBytes));
+        HIP_TRY(f, hipHostMalloc(reinterpret_cast<void**>(&c->h_out), kOutBytes, hipHostMallocDefault));
         return VISFS_BA_OK;
     };
     const int rc = alloc();
@@ -388,13 +377,13 @@ int ensure_state(visfs_flow* f) {
 int disc_reserve(visfs_flow* f, size_t bytes) {
     CornerState* c = f->corners;
     if (bytes <= c->disc_cap) return VISFS_BA_OK;
-    CR_HIP(f, hipStreamSynchronize(f->stream));
-    if (c->h_disc) CR_HIP(f, hipHostFree(c->h_disc));
-    if (c->d_disc) CR_HIP(f, hipFree(c->d_disc));
+    HIP_TRY(f, hipStreamSynchronize(f->stream));
+    if (c->h_disc) HIP_TRY(f, hipHostFree(c->h_disc));
+    if (c->d_disc) HIP_TRY(f, hipFree(c->d_disc));
     c->h_disc = nullptr; c->d_disc = nullptr; c->disc_cap = 0;
     const size_t cap = std::max<size_t>(2 * bytes, 16384);
-    CR_HIP(f, hipHostMalloc(reinterpret_cast<void**>(&c->h_disc), cap, hipHostMallocDefault));
-    CR_HIP(f, hipMalloc(reinterpret_cast<void**>(&c->d_disc), cap));
+    HIP_TRY(f, hipHostMalloc(reinterpret_cast<void**>(&c->h_disc), cap, hipHostMallocDefault));
+    HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&c->d_disc), cap));
     c->disc_cap = cap;
     return VISFS_BA_OK;
 }
@@ -501,7 +490,7 @@ void host_corners(visfs_flow* f, CornerState* c, const uint8_t* px, const visfs_
 }
 
 int device_corners(visfs_flow* f, CornerState* c, const uint8_t* px, const visfs_corners_params& p, float* xy, int32_t* n_out) {
-    CR_HIP(f, hipSetDevice(f->dev));
+    HIP_TRY(f, hipSetDevice(f->dev));
     const int w = f->w, h = f->h;
     const size_t disc_bytes = c->discs.size() * sizeof(Disc), hw_bytes = c->hw.size() * sizeof(int32_t);
     const Disc* d_discs = nullptr;
@@ -512,29 +501,29 @@ int device_corners(visfs_flow* f, CornerState* c, const uint8_t* px, const visfs
         // the pinned block is free: the call that filled it last ended in a synchronise behind its copy
         std::memcpy(c->h_disc, c->discs.data(), disc_bytes);
         std::memcpy(c->h_disc + disc_bytes, c->hw.data(), hw_bytes);
-        CR_HIP(f, hipMemcpyAsync(c->d_disc, c->h_disc, disc_bytes + hw_bytes, hipMemcpyHostToDevice, f->stream));
+        HIP_TRY(f, hipMemcpyAsync(c->d_disc, c->h_disc, disc_bytes + hw_bytes, hipMemcpyHostToDevice, f->stream));
         d_discs = reinterpret_cast<const Disc*>(c->d_disc);
         d_hw = reinterpret_cast<const int32_t*>(c->d_disc + disc_bytes);
     }
     CornerDev* st = reinterpret_cast<CornerDev*>(c->d_out);
     float* d_xy = reinterpret_cast<float*>(c->d_out + sizeof(CornerDev));
-    CR_HIP(f, hipMemsetAsync(c->d_out, 0, sizeof(CornerDev), f->stream));
+    HIP_TRY(f, hipMemsetAsync(c->d_out, 0, sizeof(CornerDev), f->stream));
     hipLaunchKernelGGL(k_corner_response, dim3((w + CT_X - 1) / CT_X, (h + CT_Y - 1) / CT_Y), dim3(CR_T), 0, f->stream, px, w, h, d_discs,
                        (int)c->discs.size(), d_hw, c->d_eig, c->d_mask, st);
-    CR_HIP(f, hipGetLastError());
+    HIP_TRY(f, hipGetLastError());
     hipLaunchKernelGGL(k_corner_candidates, dim3((unsigned)(((size_t)w * h + CR_T - 1) / CR_T)), dim3(CR_T), 0, f->stream, c->d_eig, c->d_mask,
                        w, h, p.quality_level, st, c->d_keys);
-    CR_HIP(f, hipGetLastError());
+    HIP_TRY(f, hipGetLastError());
     const size_t chunks = (max_candidates(f) + 63) / 64;
     hipLaunchKernelGGL(k_corner_sort, dim3((unsigned)std::min<size_t>(std::max<size_t>(chunks, 1), kSortGrid)), dim3(CR_T), 0, f->stream,
                        c->d_keys, st, c->d_sorted);
-    CR_HIP(f, hipGetLastError());
+    HIP_TRY(f, hipGetLastError());
     hipLaunchKernelGGL(k_corner_select, dim3(1), dim3(kSelT), 0, f->stream, c->d_sorted, st, w, distance_gate(p.min_distance), p.max_corners,
                        d_xy);
-    CR_HIP(f, hipGetLastError());
-    CR_HIP(f, hipMemcpyAsync(c->h_out, c->d_out, sizeof(CornerDev) + sizeof(float) * 2 * (size_t)p.max_corners, hipMemcpyDeviceToHost,
+    HIP_TRY(f, hipGetLastError());
+    HIP_TRY(f, hipMemcpyAsync(c->h_out, c->d_out, sizeof(CornerDev) + sizeof(float) * 2 * (size_t)p.max_corners, hipMemcpyDeviceToHost,
                              f->stream));
-    CR_HIP(f, hipStreamSynchronize(f->stream));
+    HIP_TRY(f, hipStreamSynchronize(f->stream));
     CornerDev out;
     std::memcpy(&out, c->h_out, sizeof(out));
     if (out.n_out < 0 || out.n_out > p.max_corners) return fail(f, VISFS_BA_ERR_DEVICE, "the selection returned an impossible count");
@@ -569,19 +558,19 @@ int group_corners(visfs_flow* f, double quality_level, double min_distance, int 
     const int w = f->w, h = f->h;
     const unsigned z = (unsigned)n;
     hipLaunchKernelGGL(k_corner_reset_g, dim3((z + 63) / 64), dim3(64), 0, f->stream, d_recs, n);
-    CR_HIP(f, hipGetLastError());
+    HIP_TRY(f, hipGetLastError());
     hipLaunchKernelGGL(k_corner_response_g, dim3((w + CT_X - 1) / CT_X, (h + CT_Y - 1) / CT_Y, z), dim3(CR_T), 0, f->stream, d_recs, w, h);
-    CR_HIP(f, hipGetLastError());
+    HIP_TRY(f, hipGetLastError());
     hipLaunchKernelGGL(k_corner_candidates_g, dim3((unsigned)(((size_t)w * h + CR_T - 1) / CR_T), 1, z), dim3(CR_T), 0, f->stream, d_recs, w, h,
                        quality_level);
-    CR_HIP(f, hipGetLastError());
+    HIP_TRY(f, hipGetLastError());
     const size_t chunks = (max_candidates(f) + 63) / 64;
     hipLaunchKernelGGL(k_corner_sort_g, dim3((unsigned)std::min<size_t>(std::max<size_t>(chunks, 1), kSortGrid), 1, z), dim3(CR_T), 0, f->stream,
                        d_recs);
-    CR_HIP(f, hipGetLastError());
+    HIP_TRY(f, hipGetLastError());
     hipLaunchKernelGGL(k_corner_select_g, dim3(1, 1, z), dim3(kSelT), 0, f->stream, d_recs, w, distance_gate(min_distance));
-    CR_HIP(f, hipGetLastError());
-    cnt->kernels += 5;
+    HIP_TRY(f, hipGetLastError());
+    cnt->launches += 5;
     return VISFS_BA_OK;
 }
 
@@ -613,7 +602,7 @@ void visfs_corners_default_params(visfs_corners_params* p) {
 int visfs_flow_corners(visfs_flow* f, int32_t slot, int32_t image, const visfs_corners_params* p, int32_t n_discs,
                        const visfs_corners_disc* discs, int32_t capacity, float* xy, int32_t* n_out) {
     if (!f || !p || !xy || !n_out || n_discs < 0 || (n_discs > 0 && !discs)) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded_cr(f, [&]() -> int {
+    return guarded(f, [&]() -> int {
         *n_out = 0;
         int rc = check_call(f, slot, image, p, n_discs, discs, capacity);
         if (rc != VISFS_BA_OK) return rc;
@@ -638,7 +627,7 @@ int visfs_flow_corners(visfs_flow* f, int32_t slot, int32_t image, const visfs_c
 int visfs_flow_corners_download(const visfs_flow* cf, float* eig, uint8_t* mask, uint8_t* disc_drawn, int32_t* n_candidates, float* max_val) {
     visfs_flow* f = const_cast<visfs_flow*>(cf);
     if (!f) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded_cr(f, [&]() -> int {
+    return guarded(f, [&]() -> int {
         const CornerState* c = f->corners;
         if (!c || !c->valid) return fail(f, VISFS_BA_ERR_NOT_LOADED, "no corner call to report on");
         const size_t n0 = (size_t)f->w * f->h;
@@ -650,10 +639,10 @@ int visfs_flow_corners_download(const visfs_flow* cf, float* eig, uint8_t* mask,
             if (mask) std::memcpy(mask, c->hmask.data(), n0);
             return (int)VISFS_BA_OK;
         }
-        CR_HIP(f, hipSetDevice(f->dev));
-        if (eig) CR_HIP(f, hipMemcpyAsync(eig, c->d_eig, n0 * sizeof(float), hipMemcpyDeviceToHost, f->stream));
-        if (mask) CR_HIP(f, hipMemcpyAsync(mask, c->d_mask, n0, hipMemcpyDeviceToHost, f->stream));
-        CR_HIP(f, hipStreamSynchronize(f->stream));
+        HIP_TRY(f, hipSetDevice(f->dev));
+        if (eig) HIP_TRY(f, hipMemcpyAsync(eig, c->d_eig, n0 * sizeof(float), hipMemcpyDeviceToHost, f->stream));
+        if (mask) HIP_TRY(f, hipMemcpyAsync(mask, c->d_mask, n0, hipMemcpyDeviceToHost, f->stream));
+        HIP_TRY(f, hipStreamSynchronize(f->stream));
         return (int)VISFS_BA_OK;
     });
 }

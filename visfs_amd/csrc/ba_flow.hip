@@ -12,6 +12,7 @@
 // The sums are exact integers, so device and host agree to the byte whatever the order of summation.
 #include "ba_flow_object.hpp"
 #include "ba_group.hpp"
+#include "ba_host.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -20,6 +21,7 @@
 #include <vector>
 
 using namespace flow;
+using namespace host;
 
 // ---------------------------------------------------------------- kernels
 namespace flow {
@@ -121,21 +123,11 @@ __global__ __launch_bounds__(64) void k_flow_lk(LkArgs A, LkParams prm, Layout l
     }
 }
 
-static int blocks_for(int64_t n) { return (int)((n + FL_T - 1) / FL_T); }
-static size_t up256(size_t x) { return (x + 255) & ~size_t(255); }
-
 }  // namespace flow
 
 namespace {
 
 constexpr int32_t kInitialPoints = 1024;
-
-int fail(visfs_flow* f, int rc, const std::string& why) { f->err = why; return rc; }
-#define FL_HIP(f, expr)                                                                                   \
-    do {                                                                                                  \
-        hipError_t e_ = (expr);                                                                           \
-        if (e_ != hipSuccess) return fail((f), VISFS_BA_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 int check_params(const visfs_flow_params* p, int32_t w, int32_t h, std::string& why) {
     if (p->win_size < 3 || p->win_size > kMaxWin) { why = "win_size must lie in 3 .. 21"; return VISFS_BA_ERR_UNSUPPORTED; }
@@ -187,29 +179,29 @@ IoLayout io_layout(size_t n) {
 
 int io_reserve(visfs_flow* f, int32_t n) {
     if (n <= f->io_cap) return VISFS_BA_OK;
-    FL_HIP(f, hipStreamSynchronize(f->stream));
-    if (f->h_io) FL_HIP(f, hipHostFree(f->h_io));
-    if (f->d_io) FL_HIP(f, hipFree(f->d_io));
+    HIP_TRY(f, hipStreamSynchronize(f->stream));
+    if (f->h_io) HIP_TRY(f, hipHostFree(f->h_io));
+    if (f->d_io) HIP_TRY(f, hipFree(f->d_io));
     f->h_io = nullptr; f->d_io = nullptr; f->io_cap = 0;
     const int32_t cap = std::max(n, kInitialPoints);
     const size_t bytes = io_layout((size_t)cap).bytes;
-    FL_HIP(f, hipHostMalloc(reinterpret_cast<void**>(&f->h_io), bytes, hipHostMallocDefault));
-    FL_HIP(f, hipMalloc(reinterpret_cast<void**>(&f->d_io), bytes));
+    HIP_TRY(f, hipHostMalloc(reinterpret_cast<void**>(&f->h_io), bytes, hipHostMallocDefault));
+    HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&f->d_io), bytes));
     f->io_cap = cap;
     return VISFS_BA_OK;
 }
 
 int device_init(visfs_flow* f) {
-    FL_HIP(f, hipSetDevice(f->dev));
+    HIP_TRY(f, hipSetDevice(f->dev));
     const size_t bpx = up256((size_t)f->lay.cells), bder = up256((size_t)f->lay.cells * 4);
-    FL_HIP(f, hipMalloc(reinterpret_cast<void**>(&f->d_mem), 4 * (bpx + bder)));
+    HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&f->d_mem), 4 * (bpx + bder)));
     char* m = f->d_mem;
     for (int s = 0; s < 2; ++s)
         for (int i = 0; i < 2; ++i) {
             f->dder[s][i] = reinterpret_cast<uint32_t*>(m); m += bder;
             f->dpx[s][i] = reinterpret_cast<uint8_t*>(m); m += bpx;
         }
-    FL_HIP(f, hipHostMalloc(reinterpret_cast<void**>(&f->h_img), 2 * (size_t)f->w * f->h, hipHostMallocDefault));
+    HIP_TRY(f, hipHostMalloc(reinterpret_cast<void**>(&f->h_img), 2 * (size_t)f->w * f->h, hipHostMallocDefault));
     return io_reserve(f, kInitialPoints);
 }
 
@@ -222,12 +214,6 @@ void release(visfs_flow* f) {
     if (f->h_io) (void)hipHostFree(f->h_io);
     if (f->h_img) (void)hipHostFree(f->h_img);
     f->d_mem = f->d_io = f->h_io = nullptr; f->h_img = nullptr;
-}
-
-template <class F> int guarded_fl(visfs_flow* f, F&& fn) noexcept {
-    try { return fn(); }
-    catch (const std::bad_alloc&) { if (f) f->err = "out of host memory"; return VISFS_BA_ERR_DEVICE; }
-    catch (...) { if (f) f->err = "unexpected exception"; return VISFS_BA_ERR_DEVICE; }
 }
 
 }  // namespace
@@ -255,15 +241,15 @@ int group_stage(visfs_flow* f, uint8_t* const dst[2], const uint8_t* left, const
     const uint8_t* src[2] = { left, right };
     for (int i = 0; i < 2; ++i) {
         for (int32_t y = 0; y < f->h; ++y) std::memcpy(f->h_img + i * n0 + (size_t)y * f->w, src[i] + (size_t)y * stride, (size_t)f->w);
-        FL_HIP(f, hipMemcpyAsync(dst[i], f->h_img + i * n0, n0, hipMemcpyHostToDevice, f->stream));
+        HIP_TRY(f, hipMemcpyAsync(dst[i], f->h_img + i * n0, n0, hipMemcpyHostToDevice, f->stream));
         if (cnt) ++cnt->copies;
     }
     return VISFS_BA_OK;
 }
 
 int device_stage(visfs_flow* f, uint8_t* const dst[2], const uint8_t* left, const uint8_t* right, int32_t stride) {
-    FL_HIP(f, hipSetDevice(f->dev));
-    FL_HIP(f, hipStreamSynchronize(f->stream));                        // the staging image of the frame before has left
+    HIP_TRY(f, hipSetDevice(f->dev));
+    HIP_TRY(f, hipStreamSynchronize(f->stream));                        // the staging image of the frame before has left
     return group_stage(f, dst, left, right, stride, nullptr);
 }
 
@@ -274,14 +260,14 @@ void group_pyr_fill(const visfs_flow* f, int slot, PyrRec* r) {
 int group_pyramids(visfs_flow* f, int n, const PyrRec* d_recs, GroupCounts* cnt) {
     for (int l = 1; l < f->lay.n_levels; ++l) {
         const Level &S = f->lay.L[l - 1], &D = f->lay.L[l];
-        hipLaunchKernelGGL(k_flow_pyr_down_g, dim3(blocks_for((int64_t)D.w * D.h), 2, (unsigned)n), dim3(FL_T), 0, f->stream, d_recs, S.off, D.off,
+        hipLaunchKernelGGL(k_flow_pyr_down_g, dim3(blocks_for((int64_t)D.w * D.h, FL_T), 2, (unsigned)n), dim3(FL_T), 0, f->stream, d_recs, S.off, D.off,
                            S.w, S.h, D.w, D.h);
-        FL_HIP(f, hipGetLastError());
-        ++cnt->kernels;
+        HIP_TRY(f, hipGetLastError());
+        ++cnt->launches;
     }
-    hipLaunchKernelGGL(k_flow_scharr_g, dim3(blocks_for(f->lay.cells), 2, (unsigned)n), dim3(FL_T), 0, f->stream, d_recs, f->lay);
-    FL_HIP(f, hipGetLastError());
-    ++cnt->kernels;
+    hipLaunchKernelGGL(k_flow_scharr_g, dim3(blocks_for(f->lay.cells, FL_T), 2, (unsigned)n), dim3(FL_T), 0, f->stream, d_recs, f->lay);
+    HIP_TRY(f, hipGetLastError());
+    ++cnt->launches;
     return VISFS_BA_OK;
 }
 
@@ -291,13 +277,13 @@ int device_pyramids(visfs_flow* f, int slot) {
         PyrDownArgs A;
         for (int i = 0; i < 2; ++i) { A.src[i] = f->dpx[slot][i] + S.off; A.dst[i] = f->dpx[slot][i] + D.off; }
         A.sw = S.w; A.sh = S.h; A.dw = D.w; A.dh = D.h;
-        hipLaunchKernelGGL(k_flow_pyr_down, dim3(blocks_for((int64_t)D.w * D.h), 2), dim3(FL_T), 0, f->stream, A);
-        FL_HIP(f, hipGetLastError());
+        hipLaunchKernelGGL(k_flow_pyr_down, dim3(blocks_for((int64_t)D.w * D.h, FL_T), 2), dim3(FL_T), 0, f->stream, A);
+        HIP_TRY(f, hipGetLastError());
     }
     ScharrArgs S;
     for (int i = 0; i < 2; ++i) { S.px[i] = f->dpx[slot][i]; S.der[i] = f->dder[slot][i]; }
-    hipLaunchKernelGGL(k_flow_scharr, dim3(blocks_for(f->lay.cells), 2), dim3(FL_T), 0, f->stream, S, f->lay);
-    FL_HIP(f, hipGetLastError());
+    hipLaunchKernelGGL(k_flow_scharr, dim3(blocks_for(f->lay.cells, FL_T), 2), dim3(FL_T), 0, f->stream, S, f->lay);
+    HIP_TRY(f, hipGetLastError());
     return VISFS_BA_OK;
 }
 
@@ -344,14 +330,14 @@ int run_pass(visfs_flow* f, int si, int ii, int sj, int ij, int32_t n, const flo
         }
         return VISFS_BA_OK;
     }
-    FL_HIP(f, hipSetDevice(f->dev));
+    HIP_TRY(f, hipSetDevice(f->dev));
     int rc = io_reserve(f, n);
     if (rc != VISFS_BA_OK) return rc;
-    FL_HIP(f, hipStreamSynchronize(f->stream));                        // (the pinned block is free again)
+    HIP_TRY(f, hipStreamSynchronize(f->stream));                        // (the pinned block is free again)
     const IoLayout o = io_layout((size_t)n);
     std::memcpy(f->h_io + o.pts, pts, 8 * (size_t)n);
     if (init) std::memcpy(f->h_io + o.init, init, 8 * (size_t)n);
-    FL_HIP(f, hipMemcpyAsync(f->d_io, f->h_io, init ? o.in_bytes : o.init, hipMemcpyHostToDevice, f->stream));
+    HIP_TRY(f, hipMemcpyAsync(f->d_io, f->h_io, init ? o.in_bytes : o.init, hipMemcpyHostToDevice, f->stream));
     LkArgs A;
     A.I = device_image(f, si, ii); A.J = device_image(f, sj, ij);
     A.pts = reinterpret_cast<const float*>(f->d_io + o.pts);
@@ -370,9 +356,9 @@ int run_pass(visfs_flow* f, int si, int ii, int sj, int ij, int32_t n, const flo
         if (back) hipLaunchKernelGGL((k_flow_lk<true, false>), grid, block, 0, f->stream, A, f->lk, f->lay, c);
         else hipLaunchKernelGGL((k_flow_lk<false, false>), grid, block, 0, f->stream, A, f->lk, f->lay, c);
     }
-    FL_HIP(f, hipGetLastError());
-    FL_HIP(f, hipMemcpyAsync(f->h_io + o.to, f->d_io + o.to, o.status + (size_t)n - o.to, hipMemcpyDeviceToHost, f->stream));
-    FL_HIP(f, hipStreamSynchronize(f->stream));
+    HIP_TRY(f, hipGetLastError());
+    HIP_TRY(f, hipMemcpyAsync(f->h_io + o.to, f->d_io + o.to, o.status + (size_t)n - o.to, hipMemcpyDeviceToHost, f->stream));
+    HIP_TRY(f, hipStreamSynchronize(f->stream));
     std::memcpy(to, f->h_io + o.to, 8 * (size_t)n);
     std::memcpy(status, f->h_io + o.status, (size_t)n);
     if (err) std::memcpy(err, f->h_io + o.err, 4 * (size_t)n);
@@ -396,7 +382,7 @@ void visfs_flow_default_params(visfs_flow_params* p) {
 int visfs_flow_create_host(const visfs_flow_params* p, int32_t width, int32_t height, visfs_flow** out) {
     if (!p || !out) return VISFS_BA_ERR_BAD_ARGUMENT;
     *out = nullptr;
-    return guarded_fl(nullptr, [&]() -> int {
+    return guarded(nullptr, [&]() -> int {
         std::string why;
         const int rc = check_params(p, width, height, why);
         if (rc != VISFS_BA_OK) return rc;
@@ -410,7 +396,7 @@ int visfs_flow_create_host(const visfs_flow_params* p, int32_t width, int32_t he
 int visfs_flow_create(visfs_ba_handle* h, const visfs_flow_params* p, int32_t width, int32_t height, visfs_flow** out) {
     if (!h || !p || !out) return VISFS_BA_ERR_BAD_ARGUMENT;
     *out = nullptr;
-    return guarded_fl(nullptr, [&]() -> int {
+    return guarded(nullptr, [&]() -> int {
         std::string why;
         int rc = check_params(p, width, height, why);
         if (rc != VISFS_BA_OK) { visfs_internal_set_error(h, why.c_str()); return rc; }
@@ -437,7 +423,7 @@ const char* visfs_flow_last_error(const visfs_flow* f) { return f ? f->err.c_str
 
 int visfs_flow_push_frame(visfs_flow* f, const uint8_t* left, const uint8_t* right, int32_t stride) {
     if (!f || !left || !right) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded_fl(f, [&]() -> int {
+    return guarded(f, [&]() -> int {
         if (stride < f->w) return fail(f, VISFS_BA_ERR_BAD_ARGUMENT, "stride is smaller than the image width");
         const int slot = f->frames == 0 ? f->cur : 1 - f->cur;
         if (f->device) {
@@ -455,7 +441,7 @@ int visfs_flow_push_frame(visfs_flow* f, const uint8_t* left, const uint8_t* rig
 
 int visfs_flow_track(visfs_flow* f, int32_t n, const float* from_xy, const float* guess_xy, float* to_xy, uint8_t* status, float* err) {
     if (!f || n < 0 || (n > 0 && (!from_xy || !to_xy || !status))) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded_fl(f, [&]() -> int {
+    return guarded(f, [&]() -> int {
         if (f->frames < 2) return fail(f, VISFS_BA_ERR_NOT_LOADED, "track needs two pushed frames");
         return run_pass(f, 1 - f->cur, 0, f->cur, 0, n, from_xy, guess_xy, f->prm.back_gate_track, nullptr, to_xy, status, err, nullptr);
     });
@@ -464,7 +450,7 @@ int visfs_flow_track(visfs_flow* f, int32_t n, const float* from_xy, const float
 int visfs_flow_stereo(visfs_flow* f, int32_t n, const float* left_xy, const visfs_flow_camera* cam, float* right_xy, uint8_t* status,
                       float* xyz) {
     if (!f || !cam || n < 0 || (n > 0 && (!left_xy || !right_xy || !status || !xyz))) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded_fl(f, [&]() -> int {
+    return guarded(f, [&]() -> int {
         if (f->frames < 1) return fail(f, VISFS_BA_ERR_NOT_LOADED, "stereo needs a pushed frame");
         for (int i = 0; i < 12; ++i) if (!std::isfinite(cam->Tir[i])) return fail(f, VISFS_BA_ERR_BAD_ARGUMENT, "Tir is not finite");
         const Camera c = make_camera(f->prm, *cam);
@@ -482,7 +468,7 @@ int visfs_flow_level_size(const visfs_flow* f, int32_t level, int32_t* width, in
 int visfs_flow_download_level(const visfs_flow* cf, int32_t slot, int32_t image, int32_t level, uint8_t* pixels, int16_t* derivative) {
     visfs_flow* f = const_cast<visfs_flow*>(cf);
     if (!f) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded_fl(f, [&]() -> int {
+    return guarded(f, [&]() -> int {
         if (slot < 0 || slot > 1 || image < 0 || image > 1 || level < 0 || level >= f->lay.n_levels)
             return fail(f, VISFS_BA_ERR_BAD_ARGUMENT, "slot, image or level out of range");
         if (f->frames < (slot == VISFS_FLOW_SLOT_CURRENT ? 1 : 2)) return fail(f, VISFS_BA_ERR_NOT_LOADED, "no frame in that slot");
@@ -494,10 +480,10 @@ int visfs_flow_download_level(const visfs_flow* cf, int32_t slot, int32_t image,
             if (derivative) std::memcpy(derivative, f->hder[s][image].data() + L.off, 4 * n);
             return (int)VISFS_BA_OK;
         }
-        FL_HIP(f, hipSetDevice(f->dev));
-        if (pixels) FL_HIP(f, hipMemcpyAsync(pixels, f->dpx[s][image] + L.off, n, hipMemcpyDeviceToHost, f->stream));
-        if (derivative) FL_HIP(f, hipMemcpyAsync(derivative, f->dder[s][image] + L.off, 4 * n, hipMemcpyDeviceToHost, f->stream));
-        FL_HIP(f, hipStreamSynchronize(f->stream));
+        HIP_TRY(f, hipSetDevice(f->dev));
+        if (pixels) HIP_TRY(f, hipMemcpyAsync(pixels, f->dpx[s][image] + L.off, n, hipMemcpyDeviceToHost, f->stream));
+        if (derivative) HIP_TRY(f, hipMemcpyAsync(derivative, f->dder[s][image] + L.off, 4 * n, hipMemcpyDeviceToHost, f->stream));
+        HIP_TRY(f, hipStreamSynchronize(f->stream));
         return (int)VISFS_BA_OK;
     });
 }

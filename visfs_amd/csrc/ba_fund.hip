@@ -16,6 +16,7 @@
 // host twin of that tracker goes through fund::cull_host.
 #include "ba_fund.hpp"
 #include "ba_group.hpp"      // fund::group_cull, fund::cull_host
+#include "ba_host.hpp"
 #include "../../include/visfs_fund.h"
 
 #include <algorithm>
@@ -31,6 +32,7 @@ int visfs_internal_device(visfs_ba_handle* h);
 void visfs_internal_set_error(visfs_ba_handle* h, const char* msg);
 
 using namespace fund;
+using namespace host;
 
 namespace fund {
 
@@ -182,10 +184,10 @@ int group_cull(hipStream_t stream, int n, const CullRec* d_recs, int32_t max_row
     hipLaunchKernelGGL(k_fund_ransac_g, dim3((unsigned)((S.iterations + FD_T / 64 - 1) / (FD_T / 64)), 1, (unsigned)n), dim3(FD_T), 0, stream,
                        d_recs, S);
     if (hipGetLastError() != hipSuccess) return VISFS_BA_ERR_DEVICE;
-    ++cnt->kernels;
+    ++cnt->launches;
     hipLaunchKernelGGL(k_fund_mask_g, dim3((unsigned)((max_rows + FD_T - 1) / FD_T), 1, (unsigned)n), dim3(FD_T), 0, stream, d_recs, S);
     if (hipGetLastError() != hipSuccess) return VISFS_BA_ERR_DEVICE;
-    ++cnt->kernels;
+    ++cnt->launches;
     return VISFS_BA_OK;
 }
 
@@ -225,31 +227,17 @@ struct visfs_fund {
 
 namespace {
 
-size_t up256(size_t x) { return (x + 255) & ~size_t(255); }
-int fail(visfs_fund* p, int rc, const std::string& why) { p->err = why; return rc; }
-#define FD_HIP(p, expr)                                                                                   \
-    do {                                                                                                  \
-        hipError_t e_ = (expr);                                                                           \
-        if (e_ != hipSuccess) return fail((p), VISFS_BA_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-template <class F> int guarded_fd(visfs_fund* p, F&& fn) noexcept {
-    try { return fn(); }
-    catch (const std::bad_alloc&) { if (p) p->err = "out of host memory"; return VISFS_BA_ERR_DEVICE; }
-    catch (...) { if (p) p->err = "unexpected exception"; return VISFS_BA_ERR_DEVICE; }
-}
-
 int device_init(visfs_fund* p) {
-    FD_HIP(p, hipSetDevice(p->dev));
+    HIP_TRY(p, hipSetDevice(p->dev));
     const size_t cap = (size_t)p->cap;
     const size_t in_bytes = kHeaderBytes + up256(17 * cap), out_bytes = kHeaderBytes + up256(2 * cap);
-    FD_HIP(p, hipHostMalloc(reinterpret_cast<void**>(&p->h_in), in_bytes, hipHostMallocDefault));
-    FD_HIP(p, hipHostMalloc(reinterpret_cast<void**>(&p->h_out), out_bytes, hipHostMallocDefault));
-    FD_HIP(p, hipMalloc(reinterpret_cast<void**>(&p->d_in), in_bytes));
-    FD_HIP(p, hipMalloc(reinterpret_cast<void**>(&p->d_out), out_bytes));
+    HIP_TRY(p, hipHostMalloc(reinterpret_cast<void**>(&p->h_in), in_bytes, hipHostMallocDefault));
+    HIP_TRY(p, hipHostMalloc(reinterpret_cast<void**>(&p->h_out), out_bytes, hipHostMallocDefault));
+    HIP_TRY(p, hipMalloc(reinterpret_cast<void**>(&p->d_in), in_bytes));
+    HIP_TRY(p, hipMalloc(reinterpret_cast<void**>(&p->d_out), out_bytes));
     const size_t H = kMaxHypotheses;
     const size_t o_models = 0, o_samples = o_models + up256(216 * H), o_nc = o_samples + up256(28 * H), bytes = o_nc + up256(16 * H);
-    FD_HIP(p, hipMalloc(reinterpret_cast<void**>(&p->d_state), bytes));
+    HIP_TRY(p, hipMalloc(reinterpret_cast<void**>(&p->d_state), bytes));
     p->d_models = reinterpret_cast<double*>(p->d_state + o_models);
     p->d_samples = reinterpret_cast<int32_t*>(p->d_state + o_samples);
     p->d_nc = reinterpret_cast<int32_t*>(p->d_state + o_nc);
@@ -343,21 +331,21 @@ int device_cull(visfs_fund* p, const Call& c) {
     std::memcpy(p->h_in, &hd, sizeof hd);
     std::memcpy(p->h_in + kHeaderBytes, p->rows.data(), sizeof(Row) * m);
     std::memcpy(p->h_in + kHeaderBytes + sizeof(Row) * m, p->st.data(), m);
-    FD_HIP(p, hipMemcpyAsync(p->d_in, p->h_in, kHeaderBytes + 17 * m, hipMemcpyHostToDevice, p->stream));
+    HIP_TRY(p, hipMemcpyAsync(p->d_in, p->h_in, kHeaderBytes + 17 * m, hipMemcpyHostToDevice, p->stream));
     RansacArgs A;
     A.head = reinterpret_cast<const Header*>(p->d_in); A.rows = reinterpret_cast<const Row*>(p->d_in + kHeaderBytes);
     A.m = c.m; A.iterations = c.iterations; A.seed = c.seed; A.thr2 = c.thr2;
     A.samples = p->d_samples; A.nc = p->d_nc; A.models = p->d_models; A.key = reinterpret_cast<unsigned long long*>(p->d_in);
     hipLaunchKernelGGL(k_fund_ransac, dim3((unsigned)((c.iterations + FD_T / 64 - 1) / (FD_T / 64))), dim3(FD_T), 0, p->stream, A);
-    FD_HIP(p, hipGetLastError());
+    HIP_TRY(p, hipGetLastError());
     MaskArgs B;
     B.head = A.head; B.rows = A.rows; B.status_in = reinterpret_cast<const uint8_t*>(p->d_in + kHeaderBytes + sizeof(Row) * m);
     B.m = c.m; B.thr2 = c.thr2; B.models = p->d_models; B.res = reinterpret_cast<Result*>(p->d_out);
     B.mask = reinterpret_cast<uint8_t*>(p->d_out + kHeaderBytes); B.status = B.mask + m;
     hipLaunchKernelGGL(k_fund_mask, dim3((unsigned)((c.m + FD_T - 1) / FD_T)), dim3(FD_T), 0, p->stream, B);
-    FD_HIP(p, hipGetLastError());
-    FD_HIP(p, hipMemcpyAsync(p->h_out, p->d_out, kHeaderBytes + 2 * m, hipMemcpyDeviceToHost, p->stream));
-    FD_HIP(p, hipStreamSynchronize(p->stream));
+    HIP_TRY(p, hipGetLastError());
+    HIP_TRY(p, hipMemcpyAsync(p->h_out, p->d_out, kHeaderBytes + 2 * m, hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(p, hipStreamSynchronize(p->stream));
     std::memcpy(&p->res, p->h_out, sizeof(Result));
     if (p->res.count < 0 || p->res.count > c.m) return fail(p, VISFS_BA_ERR_DEVICE, "the device returned an impossible inlier count");
     std::memcpy(p->mask_k.data(), p->h_out + kHeaderBytes, m);
@@ -410,7 +398,7 @@ int visfs_fund_create_host(int32_t capacity_points, visfs_fund** out) {
     *out = nullptr;
     if (capacity_points < 1) return VISFS_BA_ERR_BAD_ARGUMENT;
     if (capacity_points > kMaxPoints) return VISFS_BA_ERR_UNSUPPORTED;
-    return guarded_fd(nullptr, [&]() -> int {
+    return guarded(nullptr, [&]() -> int {
         visfs_fund* p = new visfs_fund();
         p->cap = capacity_points;
         *out = p;
@@ -423,7 +411,7 @@ int visfs_fund_create(visfs_ba_handle* h, int32_t capacity_points, visfs_fund** 
     *out = nullptr;
     if (capacity_points < 1) { visfs_internal_set_error(h, "capacity_points must be at least 1"); return VISFS_BA_ERR_BAD_ARGUMENT; }
     if (capacity_points > kMaxPoints) { visfs_internal_set_error(h, "capacity_points above 4096"); return VISFS_BA_ERR_UNSUPPORTED; }
-    return guarded_fd(nullptr, [&]() -> int {
+    return guarded(nullptr, [&]() -> int {
         visfs_fund* p = new visfs_fund();
         p->cap = capacity_points;
         p->device = true; p->ba = h; p->dev = visfs_internal_device(h); p->stream = visfs_internal_stream(h);
@@ -448,14 +436,14 @@ int visfs_fund_cull(visfs_fund* p, const visfs_fund_params* params, int32_t n, c
     if (!p) return VISFS_BA_ERR_BAD_ARGUMENT;
     if (!params || !n_inliers || !applied || n < 0 || (n > 0 && (!from_xy || !to_xy || !status_in || !status_out || !mask_out)))
         return fail(p, VISFS_BA_ERR_BAD_ARGUMENT, "a required pointer is null or n is negative");
-    return guarded_fd(p, [&]() -> int {
+    return guarded(p, [&]() -> int {
         if (!std::isfinite(params->pixel_error)) return fail(p, VISFS_BA_ERR_BAD_ARGUMENT, "pixel_error is not finite");
         if (params->iterations < 1) return fail(p, VISFS_BA_ERR_BAD_ARGUMENT, "iterations must be at least 1");
         if (params->iterations > kMaxHypotheses) return fail(p, VISFS_BA_ERR_UNSUPPORTED, "iterations above 4096");
         if (n > p->cap) return fail(p, VISFS_BA_ERR_BAD_ARGUMENT, "n is above the capacity of the cull");
         if (p->device) {
-            FD_HIP(p, hipSetDevice(p->dev));
-            FD_HIP(p, hipStreamSynchronize(p->stream));            // (the pinned blocks are free again)
+            HIP_TRY(p, hipSetDevice(p->dev));
+            HIP_TRY(p, hipStreamSynchronize(p->stream));            // (the pinned blocks are free again)
         }
         // step 1: the rows
         p->rows.clear(); p->keep.clear(); p->st.clear();
@@ -521,7 +509,7 @@ int visfs_fund_download(visfs_fund* p, int32_t* samples, int32_t* n_models, doub
                         int32_t* winner_k, double* T1, double* T2) {
     if (!p) return VISFS_BA_ERR_BAD_ARGUMENT;
     if (!p->called) return fail(p, VISFS_BA_ERR_NOT_LOADED, "no visfs_fund_cull call yet");
-    return guarded_fd(p, [&]() -> int {
+    return guarded(p, [&]() -> int {
         const size_t H = (size_t)p->last_hyp;
         if (winner_h) *winner_h = p->res.winner_h;
         if (winner_k) *winner_k = p->res.winner_k;
@@ -532,12 +520,12 @@ int visfs_fund_download(visfs_fund* p, int32_t* samples, int32_t* n_models, doub
         const std::vector<int32_t>*s = &p->samples, *nc = &p->nc;
         const std::vector<double>* mo = &p->models;
         if (!p->state_on_host && H > 0) {
-            FD_HIP(p, hipSetDevice(p->dev));
-            FD_HIP(p, hipStreamSynchronize(p->stream));
+            HIP_TRY(p, hipSetDevice(p->dev));
+            HIP_TRY(p, hipStreamSynchronize(p->stream));
             h_samples.resize(7 * H); h_nc.resize(4 * H); h_models.resize(27 * H);
-            FD_HIP(p, hipMemcpy(h_samples.data(), p->d_samples, 28 * H, hipMemcpyDeviceToHost));
-            FD_HIP(p, hipMemcpy(h_nc.data(), p->d_nc, 16 * H, hipMemcpyDeviceToHost));
-            FD_HIP(p, hipMemcpy(h_models.data(), p->d_models, 216 * H, hipMemcpyDeviceToHost));
+            HIP_TRY(p, hipMemcpy(h_samples.data(), p->d_samples, 28 * H, hipMemcpyDeviceToHost));
+            HIP_TRY(p, hipMemcpy(h_nc.data(), p->d_nc, 16 * H, hipMemcpyDeviceToHost));
+            HIP_TRY(p, hipMemcpy(h_models.data(), p->d_models, 216 * H, hipMemcpyDeviceToHost));
             s = &h_samples; nc = &h_nc; mo = &h_models;
         }
         for (size_t h = 0; h < H; ++h) {

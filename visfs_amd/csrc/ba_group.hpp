@@ -6,10 +6,11 @@
 #include "ba_clahe.hpp"
 #include "ba_corners.hpp"
 #include "ba_flow_object.hpp"
+#include "ba_host.hpp"
 
 namespace flow {
 
-struct GroupCounts { int32_t kernels = 0, copies = 0, syncs = 0; };     // what a group call issued
+struct GroupCounts : host::Counts {};         // what a group call issued
 
 struct PyrRec {                                // the slot a member's frame goes into
     uint8_t* px[2];

@@ -10,6 +10,7 @@
 #include "ba_map.hpp"
 #include "ba_scan_stack_access.hpp"
 #include "ba_map_access.hpp"
+#include "ba_host.hpp"
 
 #include <cstring>
 #include <new>
@@ -19,6 +20,7 @@
 #pragma clang fp contract(off)
 
 using namespace gmap;
+using namespace host;
 using submap::GridView;
 using submap::Limits;
 
@@ -75,23 +77,10 @@ struct visfs_map {
     TileRec* h_tab = nullptr;                 // pinned
     TileRec* d_tab = nullptr;
     size_t tab_cap = 0;                       // records
-    int32_t launches = 0, copies = 0, waits = 0;
+    host::Counts counts;
 };
 
 namespace {
-
-int mfail(visfs_map* m, int rc, const std::string& why) { m->err = why; return rc; }
-
-#define GM_HIP(m, expr)                                                                                               \
-    do {                                                                                                              \
-        hipError_t e_ = (expr);                                                                                       \
-        if (e_ != hipSuccess) return mfail((m), VISFS_BA_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-template <class F> int guarded(F&& f) noexcept {
-    try { return f(); }
-    catch (...) { return (int)VISFS_BA_ERR_DEVICE; }
-}
 
 std::vector<int32_t> odds_table() {
     std::vector<double> cost(kValues);
@@ -125,13 +114,13 @@ bool pose_ok(const double p[3]) { return std::isfinite(p[0]) && std::isfinite(p[
 
 // The checks every new tile passes before anything is allocated or pushed.
 int check_tile(visfs_map* m, const Limits& L, const double pose[3]) {
-    if (!pose_ok(pose)) return mfail(m, VISFS_BA_ERR_BAD_ARGUMENT, "the pose is not finite");
+    if (!pose_ok(pose)) return fail(m, VISFS_BA_ERR_BAD_ARGUMENT, "the pose is not finite");
     if (!limits_ok(L.res, L.max_x, L.max_y, L.nx, L.ny))
-        return mfail(m, VISFS_BA_ERR_BAD_ARGUMENT, "the limits need a positive resolution, a finite corner and at least one cell per axis");
-    if (m->tiles.size() >= (size_t)VISFS_MAP_MAX_TILES) return mfail(m, VISFS_BA_ERR_UNSUPPORTED, "more than 256 tiles");
+        return fail(m, VISFS_BA_ERR_BAD_ARGUMENT, "the limits need a positive resolution, a finite corner and at least one cell per axis");
+    if (m->tiles.size() >= (size_t)VISFS_MAP_MAX_TILES) return fail(m, VISFS_BA_ERR_UNSUPPORTED, "more than 256 tiles");
     const int64_t bytes = (int64_t)L.nx * L.ny * 2;
     if (bytes > (int64_t)VISFS_MAP_MAX_TILE_BYTES || m->tile_bytes + bytes > (int64_t)VISFS_MAP_MAX_TILE_BYTES)
-        return mfail(m, VISFS_BA_ERR_UNSUPPORTED, "the tiles together exceed 1 GiB");
+        return fail(m, VISFS_BA_ERR_UNSUPPORTED, "the tiles together exceed 1 GiB");
     return VISFS_BA_OK;
 }
 
@@ -146,20 +135,20 @@ int push_tile(visfs_map* m, const Limits& L, const double pose[3], const GridVie
         for (int32_t y = 0; y < L.ny; ++y)
             for (int32_t x = 0; x < L.nx; ++x) t.h[(size_t)y * L.nx + x] = frozen_cell(g, x, y);
     } else {
-        GM_HIP(m, hipSetDevice(m->dev));
-        GM_HIP(m, hipMalloc(reinterpret_cast<void**>(&t.d), (size_t)n * 2));
+        HIP_TRY(m, hipSetDevice(m->dev));
+        HIP_TRY(m, hipMalloc(reinterpret_cast<void**>(&t.d), (size_t)n * 2));
         auto run = [&]() -> int {
             if (staged) {
                 std::vector<uint16_t> tmp((size_t)n);
                 for (int32_t y = 0; y < L.ny; ++y)
                     for (int32_t x = 0; x < L.nx; ++x) tmp[(size_t)y * L.nx + x] = frozen_cell(g, x, y);
-                GM_HIP(m, hipMemcpyAsync(t.d, tmp.data(), (size_t)n * 2, hipMemcpyHostToDevice, m->stream));
-                GM_HIP(m, hipStreamSynchronize(m->stream));
+                HIP_TRY(m, hipMemcpyAsync(t.d, tmp.data(), (size_t)n * 2, hipMemcpyHostToDevice, m->stream));
+                HIP_TRY(m, hipStreamSynchronize(m->stream));
                 return VISFS_BA_OK;
             }
             hipLaunchKernelGGL(k_map_tile, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, m->stream, g, L.nx, n, t.d);
-            GM_HIP(m, hipGetLastError());
-            GM_HIP(m, hipStreamSynchronize(m->stream));                     // the sub-map may change or go from here on
+            HIP_TRY(m, hipGetLastError());
+            HIP_TRY(m, hipStreamSynchronize(m->stream));                     // the sub-map may change or go from here on
             return VISFS_BA_OK;
         };
         const int rc = run();
@@ -174,34 +163,34 @@ int push_tile(visfs_map* m, const Limits& L, const double pose[3], const GridVie
 int device_compose(visfs_map* m, const visfs_map_params& p, Plan& P) {
     const Limits& G = P.G;
     const size_t cells = (size_t)G.nx * G.ny, nt = P.recs.size(), recs = nt ? nt : 1;
-    GM_HIP(m, hipSetDevice(m->dev));
+    HIP_TRY(m, hipSetDevice(m->dev));
     if (m->out_cap < cells) {
-        if (m->d_cells) GM_HIP(m, hipFree(m->d_cells));
-        if (m->d_count) GM_HIP(m, hipFree(m->d_count));
+        if (m->d_cells) HIP_TRY(m, hipFree(m->d_cells));
+        if (m->d_count) HIP_TRY(m, hipFree(m->d_count));
         m->d_cells = nullptr; m->d_count = nullptr; m->out_cap = 0; m->have = false;       // the old grid went with its buffers
-        GM_HIP(m, hipMalloc(reinterpret_cast<void**>(&m->d_cells), cells * 2));
-        GM_HIP(m, hipMalloc(reinterpret_cast<void**>(&m->d_count), cells));
+        HIP_TRY(m, hipMalloc(reinterpret_cast<void**>(&m->d_cells), cells * 2));
+        HIP_TRY(m, hipMalloc(reinterpret_cast<void**>(&m->d_count), cells));
         m->out_cap = cells;
     }
     if (m->tab_cap < recs) {
-        if (m->h_tab) GM_HIP(m, hipHostFree(m->h_tab));
-        if (m->d_tab) GM_HIP(m, hipFree(m->d_tab));
+        if (m->h_tab) HIP_TRY(m, hipHostFree(m->h_tab));
+        if (m->d_tab) HIP_TRY(m, hipFree(m->d_tab));
         m->h_tab = nullptr; m->d_tab = nullptr; m->tab_cap = 0;
         const size_t cap = recs < 16 ? 16 : recs;
-        GM_HIP(m, hipHostMalloc(reinterpret_cast<void**>(&m->h_tab), cap * sizeof(TileRec), hipHostMallocDefault));
-        GM_HIP(m, hipMalloc(reinterpret_cast<void**>(&m->d_tab), cap * sizeof(TileRec)));
+        HIP_TRY(m, hipHostMalloc(reinterpret_cast<void**>(&m->h_tab), cap * sizeof(TileRec), hipHostMallocDefault));
+        HIP_TRY(m, hipMalloc(reinterpret_cast<void**>(&m->d_tab), cap * sizeof(TileRec)));
         m->tab_cap = cap;
     }
     std::memset(m->h_tab, 0, recs * sizeof(TileRec));
     for (size_t k = 0; k < nt; ++k) { m->h_tab[k] = P.recs[k]; m->h_tab[k].cells = m->tiles[k].d; }
     m->have = false;                                                       // the grid is being overwritten from here on
-    GM_HIP(m, hipMemcpyAsync(m->d_tab, m->h_tab, recs * sizeof(TileRec), hipMemcpyHostToDevice, m->stream));
+    HIP_TRY(m, hipMemcpyAsync(m->d_tab, m->h_tab, recs * sizeof(TileRec), hipMemcpyHostToDevice, m->stream));
     const int32_t blocks_x = (G.nx + kBlockX - 1) / kBlockX, blocks_y = (G.ny + kBlockY - 1) / kBlockY;
     hipLaunchKernelGGL(k_map_compose, dim3((unsigned)((int64_t)blocks_x * blocks_y)), dim3(kThreads), 0, m->stream, m->d_tab, (int32_t)nt, m->d_L,
                        p.combine, G.max_x, G.max_y, G.res, G.nx, G.ny, blocks_x, m->d_cells, m->d_count);
-    GM_HIP(m, hipGetLastError());
-    GM_HIP(m, hipStreamSynchronize(m->stream));
-    m->launches = 1; m->copies = 1; m->waits = 1;
+    HIP_TRY(m, hipGetLastError());
+    HIP_TRY(m, hipStreamSynchronize(m->stream));
+    m->counts = { 1, 1, 1 };
     return VISFS_BA_OK;
 }
 
@@ -216,13 +205,7 @@ void host_compose(visfs_map* m, const visfs_map_params& p, Plan& P) {
             compose_cell(P.recs.data(), (int32_t)P.recs.size(), m->L.data(), p.combine, G.max_x, G.max_y, G.res, (ix / kBlockX) * kBlockX,
                          (iy / kBlockY) * kBlockY, ix, iy, m->h_cells[o], m->h_count[o]);
         }
-    m->launches = m->copies = m->waits = 0;
-}
-
-Limits limits_of(const visfs_submap_info& l) {
-    Limits L;
-    L.res = l.resolution; L.max_x = l.max_x; L.max_y = l.max_y; L.nx = l.num_x_cells; L.ny = l.num_y_cells;
-    return L;
+    m->counts = {};
 }
 
 }  // namespace
@@ -250,16 +233,16 @@ void visfs_map_default_params(visfs_map_params* p) {
 int visfs_map_create(visfs_ba_handle* h, visfs_map** out) {
     if (!out) return VISFS_BA_ERR_BAD_ARGUMENT;
     *out = nullptr;
-    return guarded([&]() -> int {
+    return guarded(nullptr, [&]() -> int {
         visfs_map* m = new visfs_map();
         m->L = odds_table();
         if (h) {
             m->device = true; m->dev = visfs_internal_device(h); m->stream = visfs_internal_stream(h);
             auto run = [&]() -> int {
-                GM_HIP(m, hipSetDevice(m->dev));
-                GM_HIP(m, hipMalloc(reinterpret_cast<void**>(&m->d_L), kValues * sizeof(int32_t)));
-                GM_HIP(m, hipMemcpyAsync(m->d_L, m->L.data(), kValues * sizeof(int32_t), hipMemcpyHostToDevice, m->stream));
-                GM_HIP(m, hipStreamSynchronize(m->stream));
+                HIP_TRY(m, hipSetDevice(m->dev));
+                HIP_TRY(m, hipMalloc(reinterpret_cast<void**>(&m->d_L), kValues * sizeof(int32_t)));
+                HIP_TRY(m, hipMemcpyAsync(m->d_L, m->L.data(), kValues * sizeof(int32_t), hipMemcpyHostToDevice, m->stream));
+                HIP_TRY(m, hipStreamSynchronize(m->stream));
                 return VISFS_BA_OK;
             };
             const int rc = run();
@@ -276,13 +259,13 @@ const char* visfs_map_last_error(const visfs_map* m) { return m ? m->err.c_str()
 
 int visfs_map_add_submap(visfs_map* m, visfs_submaps* s, int32_t index, const double pose[3], int32_t* tile) {
     if (!m || !s || !pose) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded([&]() -> int {
+    return guarded(m, [&]() -> int {
         submap::ScanAccess acc;
         int rc = visfs_internal_scan_access(s, index, &acc);               // flushes a staged batch
-        if (rc != VISFS_BA_OK) return mfail(m, rc, std::string("the sub-maps: ") + visfs_submaps_last_error(s));
+        if (rc != VISFS_BA_OK) return fail(m, rc, std::string("the sub-maps: ") + visfs_submaps_last_error(s));
         if (acc.device != m->device || (m->device && (acc.dev != m->dev || acc.stream != m->stream)))
-            return mfail(m, VISFS_BA_ERR_BAD_ARGUMENT, "the sub-maps are not of the map's flavour, device and stream");
-        if (index < 0 || index >= acc.count) return mfail(m, VISFS_BA_ERR_BAD_ARGUMENT, "sub-map index out of range");
+            return fail(m, VISFS_BA_ERR_BAD_ARGUMENT, "the sub-maps are not of the map's flavour, device and stream");
+        if (index < 0 || index >= acc.count) return fail(m, VISFS_BA_ERR_BAD_ARGUMENT, "sub-map index out of range");
         if ((rc = check_tile(m, acc.L, pose)) != VISFS_BA_OK) return rc;
         return push_tile(m, acc.L, pose, acc.grid, false, tile);
     });
@@ -290,8 +273,8 @@ int visfs_map_add_submap(visfs_map* m, visfs_submaps* s, int32_t index, const do
 
 int visfs_map_add_grid(visfs_map* m, const visfs_submap_info* lim, const uint16_t* cells, const double pose[3], int32_t* tile) {
     if (!m || !lim || !cells || !pose) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded([&]() -> int {
-        const Limits L = limits_of(*lim);
+    return guarded(m, [&]() -> int {
+        const Limits L = submap::limits_of(*lim);
         const int rc = check_tile(m, L, pose);
         if (rc != VISFS_BA_OK) return rc;
         GridView g;
@@ -302,9 +285,9 @@ int visfs_map_add_grid(visfs_map* m, const visfs_submap_info* lim, const uint16_
 
 int visfs_map_set_poses(visfs_map* m, int32_t first, int32_t count, const double* poses) {
     if (!m || (count > 0 && !poses)) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded([&]() -> int {
-        if (first < 0 || count < 0 || (int64_t)first + count > (int64_t)m->tiles.size()) return mfail(m, VISFS_BA_ERR_BAD_ARGUMENT, "tile index out of range");
-        for (int32_t i = 0; i < count; ++i) if (!pose_ok(poses + 3 * (size_t)i)) return mfail(m, VISFS_BA_ERR_BAD_ARGUMENT, "a pose is not finite");
+    return guarded(m, [&]() -> int {
+        if (first < 0 || count < 0 || (int64_t)first + count > (int64_t)m->tiles.size()) return fail(m, VISFS_BA_ERR_BAD_ARGUMENT, "tile index out of range");
+        for (int32_t i = 0; i < count; ++i) if (!pose_ok(poses + 3 * (size_t)i)) return fail(m, VISFS_BA_ERR_BAD_ARGUMENT, "a pose is not finite");
         for (int32_t i = 0; i < count; ++i)
             for (int k = 0; k < 3; ++k) m->tiles[(size_t)first + i].p.pose[k] = poses[3 * (size_t)i + k];
         return (int)VISFS_BA_OK;
@@ -313,8 +296,8 @@ int visfs_map_set_poses(visfs_map* m, int32_t first, int32_t count, const double
 
 int visfs_map_clear(visfs_map* m) {
     if (!m) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded([&]() -> int {
-        if (m->device) { GM_HIP(m, hipSetDevice(m->dev)); GM_HIP(m, hipStreamSynchronize(m->stream)); }
+    return guarded(m, [&]() -> int {
+        if (m->device) { HIP_TRY(m, hipSetDevice(m->dev)); HIP_TRY(m, hipStreamSynchronize(m->stream)); }
         free_tiles(m);
         return (int)VISFS_BA_OK;
     });
@@ -335,13 +318,13 @@ int visfs_map_describe_tile(const visfs_map* m, int32_t tile, visfs_submap_info*
 
 int visfs_map_compose(visfs_map* m, const visfs_map_params* p, visfs_map_info* info) {
     if (!m || !p) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded([&]() -> int {
+    return guarded(m, [&]() -> int {
         std::vector<PlanTile> tiles;
         for (const visfs_map::Tile& t : m->tiles) tiles.push_back(t.p);
         Plan P;
         const char* why = "";
         int rc = make_plan(*p, tiles, P, &why);
-        if (rc != VISFS_BA_OK) return mfail(m, rc, why);
+        if (rc != VISFS_BA_OK) return fail(m, rc, why);
         if (m->device) { if ((rc = device_compose(m, *p, P)) != VISFS_BA_OK) return rc; }
         else host_compose(m, *p, P);
         m->G = P.G; m->have = true;
@@ -355,18 +338,18 @@ int visfs_map_compose(visfs_map* m, const visfs_map_params* p, visfs_map_info* i
 
 int visfs_map_download(visfs_map* m, uint16_t* cells, uint8_t* count) {
     if (!m) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded([&]() -> int {
-        if (!m->have) return mfail(m, VISFS_BA_ERR_BAD_ARGUMENT, "no composed grid: call visfs_map_compose first");
+    return guarded(m, [&]() -> int {
+        if (!m->have) return fail(m, VISFS_BA_ERR_BAD_ARGUMENT, "no composed grid: call visfs_map_compose first");
         const size_t n = (size_t)m->G.nx * m->G.ny;
         if (!m->device) {
             if (cells) std::memcpy(cells, m->h_cells.data(), n * 2);
             if (count) std::memcpy(count, m->h_count.data(), n);
             return (int)VISFS_BA_OK;
         }
-        GM_HIP(m, hipSetDevice(m->dev));
-        if (cells) GM_HIP(m, hipMemcpyAsync(cells, m->d_cells, n * 2, hipMemcpyDeviceToHost, m->stream));
-        if (count) GM_HIP(m, hipMemcpyAsync(count, m->d_count, n, hipMemcpyDeviceToHost, m->stream));
-        GM_HIP(m, hipStreamSynchronize(m->stream));
+        HIP_TRY(m, hipSetDevice(m->dev));
+        if (cells) HIP_TRY(m, hipMemcpyAsync(cells, m->d_cells, n * 2, hipMemcpyDeviceToHost, m->stream));
+        if (count) HIP_TRY(m, hipMemcpyAsync(count, m->d_count, n, hipMemcpyDeviceToHost, m->stream));
+        HIP_TRY(m, hipStreamSynchronize(m->stream));
         return (int)VISFS_BA_OK;
     });
 }
@@ -374,14 +357,14 @@ int visfs_map_download(visfs_map* m, uint16_t* cells, uint8_t* count) {
 int visfs_scan_stack_create_from_map(visfs_map* m, int32_t depth, visfs_scan_stack** out) {
     if (!m || !out) return VISFS_BA_ERR_BAD_ARGUMENT;
     *out = nullptr;
-    return guarded([&]() -> int {
-        if (depth < 1 || depth > VISFS_SCAN_FAST_MAX_DEPTH) return mfail(m, VISFS_BA_ERR_BAD_ARGUMENT, "the depth must lie in [1, 16]");
-        if (!m->have) return mfail(m, VISFS_BA_ERR_BAD_ARGUMENT, "no composed grid: call visfs_map_compose first");
+    return guarded(m, [&]() -> int {
+        if (depth < 1 || depth > VISFS_SCAN_FAST_MAX_DEPTH) return fail(m, VISFS_BA_ERR_BAD_ARGUMENT, "the depth must lie in [1, 16]");
+        if (!m->have) return fail(m, VISFS_BA_ERR_BAD_ARGUMENT, "no composed grid: call visfs_map_compose first");
         GridView g;
         g.cells = m->device ? m->d_cells : m->h_cells.data(); g.nx = m->G.nx; g.ny = m->G.ny;
         std::string why;
         const int rc = visfs_internal_stack_from_view(m->device, m->dev, m->stream, m->G, g, depth, out, &why);
-        if (rc != VISFS_BA_OK) return mfail(m, rc, why);
+        if (rc != VISFS_BA_OK) return fail(m, rc, why);
         return (int)VISFS_BA_OK;
     });
 }
@@ -398,17 +381,17 @@ int visfs_map_pose_from_anchor(const double a[3], const double b[3], double out[
 
 int visfs_map_hook_odds_table(int32_t table[32768]) {
     if (!table) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded([&]() -> int { const std::vector<int32_t> L = odds_table(); std::memcpy(table, L.data(), kValues * sizeof(int32_t)); return (int)VISFS_BA_OK; });
+    return guarded(nullptr, [&]() -> int { const std::vector<int32_t> L = odds_table(); std::memcpy(table, L.data(), kValues * sizeof(int32_t)); return (int)VISFS_BA_OK; });
 }
 
 int visfs_map_plan(int32_t n, const visfs_submap_info* tile_limits, const double* poses, const visfs_map_params* p, visfs_submap_info* limits,
                    int32_t* boxes, int32_t* tiles_drawn) {
     if (n < 0 || (n > 0 && (!tile_limits || !poses)) || !p) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded([&]() -> int {
+    return guarded(nullptr, [&]() -> int {
         if (n > VISFS_MAP_MAX_TILES) return (int)VISFS_BA_ERR_UNSUPPORTED;
         std::vector<PlanTile> tiles((size_t)n);
         for (int32_t k = 0; k < n; ++k) {
-            tiles[(size_t)k].L = limits_of(tile_limits[k]);
+            tiles[(size_t)k].L = submap::limits_of(tile_limits[k]);
             const Limits& L = tiles[(size_t)k].L;
             if (!pose_ok(poses + 3 * (size_t)k) || !limits_ok(L.res, L.max_x, L.max_y, L.nx, L.ny)) return (int)VISFS_BA_ERR_BAD_ARGUMENT;
             for (int i = 0; i < 3; ++i) tiles[(size_t)k].pose[i] = poses[3 * (size_t)k + i];
@@ -429,11 +412,7 @@ int visfs_map_plan(int32_t n, const visfs_submap_info* tile_limits, const double
 }
 
 int visfs_map_last_counts(const visfs_map* m, int32_t* launches, int32_t* copies, int32_t* waits) {
-    if (!m) return VISFS_BA_ERR_BAD_ARGUMENT;
-    if (launches) *launches = m->launches;
-    if (copies) *copies = m->copies;
-    if (waits) *waits = m->waits;
-    return VISFS_BA_OK;
+    return m ? m->counts.read(launches, copies, waits) : (int)VISFS_BA_ERR_BAD_ARGUMENT;
 }
 
 }  // extern "C"

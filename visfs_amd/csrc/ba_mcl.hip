@@ -19,6 +19,7 @@
 // (include/visfs_mcl_kld.h), whose fourth launch is k_mcl_kld_resample of ba_mcl_kld.hip.  ba_mcl_state.hpp holds the objects.
 #include "ba_mcl_state.hpp"
 #include "ba_map_access.hpp"
+#include "ba_host.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -29,6 +30,7 @@
 #pragma clang fp contract(off)
 
 using namespace mcl;
+using namespace host;
 using submap::Limits;
 
 namespace mcl {
@@ -218,13 +220,6 @@ namespace {
 constexpr size_t kUpBytes = sizeof(Hdr) + (size_t)VISFS_MCL_MAX_BEAMS * 2 * sizeof(double);
 static_assert(sizeof(Hdr) % 8 == 0 && sizeof(InitHdr) <= sizeof(Hdr), "the beams follow the header as doubles");
 
-#define MC_HIPQ(expr)                                                       \
-    do {                                                                    \
-        if ((expr) != hipSuccess) return (int)VISFS_BA_ERR_DEVICE;          \
-    } while (0)
-
-unsigned blocks_of(int64_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
-
 void field_free(visfs_mcl_field* f) {
     if (f->device) {
         (void)hipSetDevice(f->dev);
@@ -249,22 +244,22 @@ int field_build(visfs_mcl_field* f, const uint16_t* cells) {
         return VISFS_BA_OK;
     }
     uint16_t* g = nullptr;
-    MC_HIPQ(hipSetDevice(f->dev));
-    MC_HIPQ(hipMalloc(reinterpret_cast<void**>(&f->d_t), (size_t)total * 2));
-    MC_HIPQ(hipMalloc(reinterpret_cast<void**>(&f->d_q), f->h_q.size() * sizeof(int64_t)));
-    MC_HIPQ(hipMalloc(reinterpret_cast<void**>(&g), (size_t)total * 2));
+    HIP_TRY(nullptr, hipSetDevice(f->dev));
+    HIP_TRY(nullptr, hipMalloc(reinterpret_cast<void**>(&f->d_t), (size_t)total * 2));
+    HIP_TRY(nullptr, hipMalloc(reinterpret_cast<void**>(&f->d_q), f->h_q.size() * sizeof(int64_t)));
+    HIP_TRY(nullptr, hipMalloc(reinterpret_cast<void**>(&g), (size_t)total * 2));
     auto run = [&]() -> int {
-        MC_HIPQ(hipMemcpyAsync(f->d_q, f->h_q.data(), f->h_q.size() * sizeof(int64_t), hipMemcpyHostToDevice, f->stream));
-        hipLaunchKernelGGL(k_mcl_rows, dim3(blocks_of(total)), dim3(kThreads), 0, f->stream, cells, nx, total, f->v_occ, f->R, g);
-        MC_HIPQ(hipGetLastError());
-        hipLaunchKernelGGL(k_mcl_cols, dim3(blocks_of(total)), dim3(kThreads), 0, f->stream, g, nx, ny, total, f->R, f->T, f->d_t);
-        MC_HIPQ(hipGetLastError());
-        MC_HIPQ(hipStreamSynchronize(f->stream));
+        HIP_TRY(nullptr, hipMemcpyAsync(f->d_q, f->h_q.data(), f->h_q.size() * sizeof(int64_t), hipMemcpyHostToDevice, f->stream));
+        hipLaunchKernelGGL(k_mcl_rows, dim3(blocks_for(total, kThreads)), dim3(kThreads), 0, f->stream, cells, nx, total, f->v_occ, f->R, g);
+        HIP_TRY(nullptr, hipGetLastError());
+        hipLaunchKernelGGL(k_mcl_cols, dim3(blocks_for(total, kThreads)), dim3(kThreads), 0, f->stream, g, nx, ny, total, f->R, f->T, f->d_t);
+        HIP_TRY(nullptr, hipGetLastError());
+        HIP_TRY(nullptr, hipStreamSynchronize(f->stream));
         return VISFS_BA_OK;
     };
     const int rc = run();
     (void)hipFree(g);
-    f->launches = VISFS_MCL_FIELD_LAUNCHES; f->copies = 1; f->waits = 1;
+    f->counts = { VISFS_MCL_FIELD_LAUNCHES, 1, 1 };
     return rc;
 }
 
@@ -303,20 +298,20 @@ void mcl_free(visfs_mcl* f) {
 
 int mcl_alloc(visfs_mcl* f) {
     const size_t N = (size_t)f->N;
-    MC_HIP(f, hipSetDevice(f->dev));
-    for (int b = 0; b < 2; ++b) MC_HIP(f, hipMalloc(reinterpret_cast<void**>(&f->d_st[b]), 4 * N * sizeof(double)));
-    MC_HIP(f, hipMalloc(reinterpret_cast<void**>(&f->d_cs), 2 * N * sizeof(double)));
-    MC_HIP(f, hipMalloc(reinterpret_cast<void**>(&f->d_Q), N * sizeof(int64_t)));
-    MC_HIP(f, hipMalloc(reinterpret_cast<void**>(&f->d_anc), N * sizeof(int32_t)));
-    MC_HIP(f, hipMalloc(reinterpret_cast<void**>(&f->d_C), N * sizeof(uint64_t)));
-    MC_HIP(f, hipMalloc(reinterpret_cast<void**>(&f->d_bsum), kMaxBlocks * sizeof(uint64_t)));
-    MC_HIP(f, hipMalloc(reinterpret_cast<void**>(&f->d_part), (size_t)kMaxBlocks * kSums * sizeof(double)));
-    MC_HIP(f, hipMalloc(reinterpret_cast<void**>(&f->d_pbw), kMaxBlocks * sizeof(double)));
-    MC_HIP(f, hipMalloc(reinterpret_cast<void**>(&f->d_pbi), kMaxBlocks * sizeof(int32_t)));
-    MC_HIP(f, hipMalloc(reinterpret_cast<void**>(&f->d_up), kUpBytes));
-    MC_HIP(f, hipMalloc(reinterpret_cast<void**>(&f->d_rec), sizeof(Rec)));
-    MC_HIP(f, hipHostMalloc(reinterpret_cast<void**>(&f->h_up), kUpBytes, hipHostMallocDefault));
-    MC_HIP(f, hipHostMalloc(reinterpret_cast<void**>(&f->h_rec), sizeof(Rec), hipHostMallocDefault));
+    HIP_TRY(f, hipSetDevice(f->dev));
+    for (int b = 0; b < 2; ++b) HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&f->d_st[b]), 4 * N * sizeof(double)));
+    HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&f->d_cs), 2 * N * sizeof(double)));
+    HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&f->d_Q), N * sizeof(int64_t)));
+    HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&f->d_anc), N * sizeof(int32_t)));
+    HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&f->d_C), N * sizeof(uint64_t)));
+    HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&f->d_bsum), kMaxBlocks * sizeof(uint64_t)));
+    HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&f->d_part), (size_t)kMaxBlocks * kSums * sizeof(double)));
+    HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&f->d_pbw), kMaxBlocks * sizeof(double)));
+    HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&f->d_pbi), kMaxBlocks * sizeof(int32_t)));
+    HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&f->d_up), kUpBytes));
+    HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&f->d_rec), sizeof(Rec)));
+    HIP_TRY(f, hipHostMalloc(reinterpret_cast<void**>(&f->h_up), kUpBytes, hipHostMallocDefault));
+    HIP_TRY(f, hipHostMalloc(reinterpret_cast<void**>(&f->h_rec), sizeof(Rec), hipHostMallocDefault));
     return VISFS_BA_OK;
 }
 
@@ -328,33 +323,33 @@ int32_t lanes_for(const visfs_mcl* f, int32_t n) {
 }
 
 int device_update(visfs_mcl* f, const Hdr& H, const std::vector<double>& beams, Rec& rec) {
-    const int32_t N = H.N, blocks = (int32_t)blocks_of(N);                 // the active count
-    MC_HIP(f, hipSetDevice(f->dev));
+    const int32_t N = H.N, blocks = (int32_t)blocks_for(N, kThreads);                 // the active count
+    HIP_TRY(f, hipSetDevice(f->dev));
     std::memcpy(f->h_up, &H, sizeof H);
     if (!beams.empty()) std::memcpy(f->h_up + sizeof H, beams.data(), beams.size() * sizeof(double));
-    MC_HIP(f, hipMemcpyAsync(f->d_up, f->h_up, sizeof H + beams.size() * sizeof(double), hipMemcpyHostToDevice, f->stream));
+    HIP_TRY(f, hipMemcpyAsync(f->d_up, f->h_up, sizeof H + beams.size() * sizeof(double), hipMemcpyHostToDevice, f->stream));
     const Hdr* up = reinterpret_cast<const Hdr*>(f->d_up);
     double* st = f->d_st[f->cur];
-    hipLaunchKernelGGL(k_mcl_weight, dim3(blocks_of((int64_t)N * H.lanes)), dim3(kThreads), 0, f->stream, up, view_of(f->field), st, f->d_cs, f->d_Q);
-    MC_HIP(f, hipGetLastError());
+    hipLaunchKernelGGL(k_mcl_weight, dim3(blocks_for((int64_t)N * H.lanes, kThreads)), dim3(kThreads), 0, f->stream, up, view_of(f->field), st, f->d_cs, f->d_Q);
+    HIP_TRY(f, hipGetLastError());
     hipLaunchKernelGGL(k_mcl_sums, dim3((unsigned)blocks), dim3(kThreads), 0, f->stream, up, st, f->d_cs, f->d_part, f->d_pbw, f->d_pbi);
-    MC_HIP(f, hipGetLastError());
+    HIP_TRY(f, hipGetLastError());
     hipLaunchKernelGGL(k_mcl_finish, dim3((unsigned)blocks), dim3(kThreads), 0, f->stream, up, st, f->d_part, f->d_pbw, f->d_pbi, blocks,
                        f->kld ? kld_device_rec(f) : f->d_rec, f->d_C, f->d_bsum, f->d_anc);
-    MC_HIP(f, hipGetLastError());
+    HIP_TRY(f, hipGetLastError());
     if (f->kld) {                                                          // k_mcl_kld_resample takes the fourth launch's place
         const int rc = kld_device_resample(f, up, st, f->d_st[f->cur ^ 1], blocks, rec);
         if (rc != VISFS_BA_OK) return rc;
-        f->launches = VISFS_MCL_UPDATE_LAUNCHES; f->copies = 2; f->waits = 1;
+        f->counts = { VISFS_MCL_UPDATE_LAUNCHES, 2, 1 };
         return VISFS_BA_OK;
     }
     hipLaunchKernelGGL(k_mcl_resample, dim3((unsigned)blocks), dim3(kThreads), 0, f->stream, up, f->d_rec, st, f->d_st[f->cur ^ 1], f->d_C,
                        f->d_bsum, blocks, f->d_anc);
-    MC_HIP(f, hipGetLastError());
-    MC_HIP(f, hipMemcpyAsync(f->h_rec, f->d_rec, sizeof(Rec), hipMemcpyDeviceToHost, f->stream));
-    MC_HIP(f, hipStreamSynchronize(f->stream));
+    HIP_TRY(f, hipGetLastError());
+    HIP_TRY(f, hipMemcpyAsync(f->h_rec, f->d_rec, sizeof(Rec), hipMemcpyDeviceToHost, f->stream));
+    HIP_TRY(f, hipStreamSynchronize(f->stream));
     rec = *f->h_rec;
-    f->launches = VISFS_MCL_UPDATE_LAUNCHES; f->copies = 2; f->waits = 1;
+    f->counts = { VISFS_MCL_UPDATE_LAUNCHES, 2, 1 };
     return VISFS_BA_OK;
 }
 
@@ -405,12 +400,6 @@ void host_update(visfs_mcl* f, const Hdr& H, const std::vector<double>& beams, R
     }
 }
 
-Limits limits_of(const visfs_submap_info& l) {
-    Limits L;
-    L.res = l.resolution; L.max_x = l.max_x; L.max_y = l.max_y; L.nx = l.num_x_cells; L.ny = l.num_y_cells;
-    return L;
-}
-
 bool limits_ok(const Limits& L) {
     return std::isfinite(L.res) && L.res > 0.0 && std::isfinite(L.max_x) && std::isfinite(L.max_y) && L.nx >= 1 && L.ny >= 1 &&
            (int64_t)L.nx * L.ny <= (int64_t)VISFS_MAP_MAX_CELLS;
@@ -438,7 +427,7 @@ void visfs_mcl_default_params(visfs_mcl_params* p) {
 int visfs_mcl_field_create_from_map(visfs_map* m, const visfs_mcl_field_params* p, visfs_mcl_field** out) {
     if (!m || !p || !out) return VISFS_BA_ERR_BAD_ARGUMENT;
     *out = nullptr;
-    return guarded([&]() -> int {
+    return guarded(nullptr, [&]() -> int {
         gmap::MapAccess a;
         int rc = visfs_internal_map_access(m, &a);
         if (rc != VISFS_BA_OK) return rc;
@@ -457,8 +446,8 @@ int visfs_mcl_field_create_from_grid(visfs_ba_handle* h, const visfs_submap_info
                                      visfs_mcl_field** out) {
     if (!limits || !cells || !p || !out) return VISFS_BA_ERR_BAD_ARGUMENT;
     *out = nullptr;
-    return guarded([&]() -> int {
-        const Limits L = limits_of(*limits);
+    return guarded(nullptr, [&]() -> int {
+        const Limits L = submap::limits_of(*limits);
         if (!limits_ok(L)) return (int)VISFS_BA_ERR_BAD_ARGUMENT;
         visfs_mcl_field* f = nullptr;
         const char* why = "";
@@ -473,9 +462,9 @@ int visfs_mcl_field_create_from_grid(visfs_ba_handle* h, const visfs_submap_info
         const size_t bytes = (size_t)L.nx * L.ny * 2;
         uint16_t* d_cells = nullptr;
         auto run = [&]() -> int {
-            MC_HIPQ(hipSetDevice(f->dev));
-            MC_HIPQ(hipMalloc(reinterpret_cast<void**>(&d_cells), bytes));
-            MC_HIPQ(hipMemcpyAsync(d_cells, cells, bytes, hipMemcpyHostToDevice, f->stream));
+            HIP_TRY(nullptr, hipSetDevice(f->dev));
+            HIP_TRY(nullptr, hipMalloc(reinterpret_cast<void**>(&d_cells), bytes));
+            HIP_TRY(nullptr, hipMemcpyAsync(d_cells, cells, bytes, hipMemcpyHostToDevice, f->stream));
             return field_build(f, d_cells);
         };
         rc = run();
@@ -500,22 +489,22 @@ int visfs_mcl_field_describe(const visfs_mcl_field* f, visfs_mcl_field_info* inf
 
 int visfs_mcl_field_download(visfs_mcl_field* f, uint16_t* t, int64_t* q, int32_t* v_occ, int32_t* T) {
     if (!f) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded([&]() -> int {
+    return guarded(nullptr, [&]() -> int {
         const size_t n = (size_t)f->L.nx * f->L.ny;
         if (t) {
             if (!f->device) std::memcpy(t, f->h_t.data(), n * 2);
             else {
-                MC_HIPQ(hipSetDevice(f->dev));
-                MC_HIPQ(hipMemcpyAsync(t, f->d_t, n * 2, hipMemcpyDeviceToHost, f->stream));
-                MC_HIPQ(hipStreamSynchronize(f->stream));
+                HIP_TRY(nullptr, hipSetDevice(f->dev));
+                HIP_TRY(nullptr, hipMemcpyAsync(t, f->d_t, n * 2, hipMemcpyDeviceToHost, f->stream));
+                HIP_TRY(nullptr, hipStreamSynchronize(f->stream));
             }
         }
         if (q) {
             if (!f->device) std::memcpy(q, f->h_q.data(), f->h_q.size() * sizeof(int64_t));
             else {                                                                     // what the device holds, not the host's copy
-                MC_HIPQ(hipSetDevice(f->dev));
-                MC_HIPQ(hipMemcpyAsync(q, f->d_q, f->h_q.size() * sizeof(int64_t), hipMemcpyDeviceToHost, f->stream));
-                MC_HIPQ(hipStreamSynchronize(f->stream));
+                HIP_TRY(nullptr, hipSetDevice(f->dev));
+                HIP_TRY(nullptr, hipMemcpyAsync(q, f->d_q, f->h_q.size() * sizeof(int64_t), hipMemcpyDeviceToHost, f->stream));
+                HIP_TRY(nullptr, hipStreamSynchronize(f->stream));
             }
         }
         if (v_occ) *v_occ = f->v_occ;
@@ -525,18 +514,14 @@ int visfs_mcl_field_download(visfs_mcl_field* f, uint16_t* t, int64_t* q, int32_
 }
 
 int visfs_mcl_field_last_counts(const visfs_mcl_field* f, int32_t* launches, int32_t* copies, int32_t* waits) {
-    if (!f) return VISFS_BA_ERR_BAD_ARGUMENT;
-    if (launches) *launches = f->launches;
-    if (copies) *copies = f->copies;
-    if (waits) *waits = f->waits;
-    return VISFS_BA_OK;
+    return f ? f->counts.read(launches, copies, waits) : (int)VISFS_BA_ERR_BAD_ARGUMENT;
 }
 
 int visfs_mcl_create(visfs_mcl_field* field, int32_t n_particles, uint64_t seed, visfs_mcl** out) {
     if (!field || !out) return VISFS_BA_ERR_BAD_ARGUMENT;
     *out = nullptr;
     if (n_particles < 1 || n_particles > VISFS_MCL_MAX_PARTICLES) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded([&]() -> int {
+    return guarded(nullptr, [&]() -> int {
         visfs_mcl* f = new visfs_mcl();
         f->field = field; f->device = field->device; f->dev = field->dev; f->stream = field->stream;
         f->N = f->n = n_particles; f->seed = seed;
@@ -552,7 +537,7 @@ int visfs_mcl_create(visfs_mcl_field* field, int32_t n_particles, uint64_t seed,
         const double zero[3] = { 0.0, 0.0, 0.0 };
         const int rc = visfs_mcl_init(f, zero, zero);                                  // a defined state from the start
         if (rc != VISFS_BA_OK) { *out = nullptr; mcl_free(f); return rc; }
-        f->launches = f->copies = f->waits = 0;
+        f->counts = {};
         return (int)VISFS_BA_OK;
     });
 }
@@ -563,16 +548,16 @@ const char* visfs_mcl_last_error(const visfs_mcl* f) { return f ? f->err.c_str()
 
 int visfs_mcl_init(visfs_mcl* f, const double mean[3], const double sigma[3]) {
     if (!f || !mean || !sigma) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded([&]() -> int {
+    return guarded(f, [&]() -> int {
         InitHdr I;
         std::memset(&I, 0, sizeof I);
         for (int i = 0; i < 3; ++i) {
-            if (!std::isfinite(mean[i]) || !(std::isfinite(sigma[i]) && sigma[i] >= 0.0)) return ffail(f, VISFS_BA_ERR_BAD_ARGUMENT, "the mean must be finite, the sigmas finite and not negative");
+            if (!std::isfinite(mean[i]) || !(std::isfinite(sigma[i]) && sigma[i] >= 0.0)) return fail(f, VISFS_BA_ERR_BAD_ARGUMENT, "the mean must be finite, the sigmas finite and not negative");
             I.mean[i] = mean[i]; I.sigma[i] = sigma[i];
         }
-        if (std::fabs(mean[2]) + 6.0 * sigma[2] > 3.0 * kPi) return ffail(f, VISFS_BA_ERR_BAD_ARGUMENT, "the yaw would need more than one wrap");
+        if (std::fabs(mean[2]) + 6.0 * sigma[2] > 3.0 * kPi) return fail(f, VISFS_BA_ERR_BAD_ARGUMENT, "the yaw would need more than one wrap");
         I.mean[2] = wrap(mean[2]);
-        if (!(std::fabs(I.mean[2]) + 6.0 * sigma[2] <= 3.0 * kPi)) return ffail(f, VISFS_BA_ERR_BAD_ARGUMENT, "the yaw would need more than one wrap");
+        if (!(std::fabs(I.mean[2]) + 6.0 * sigma[2] <= 3.0 * kPi)) return fail(f, VISFS_BA_ERR_BAD_ARGUMENT, "the yaw would need more than one wrap");
         I.inv_n = 1.0 / (double)f->N; I.seed = f->seed; I.N = f->N;
         const size_t N = (size_t)f->N;
         if (!f->device) {
@@ -582,16 +567,16 @@ int visfs_mcl_init(visfs_mcl* f, const double mean[3], const double sigma[3]) {
                 st[3 * N + j] = I.inv_n;
                 f->h_Q[j] = 0; f->h_anc[j] = (int32_t)j;
             }
-            f->launches = f->copies = f->waits = 0;
+            f->counts = {};
         } else {
-            MC_HIP(f, hipSetDevice(f->dev));
+            HIP_TRY(f, hipSetDevice(f->dev));
             std::memcpy(f->h_up, &I, sizeof I);
-            MC_HIP(f, hipMemcpyAsync(f->d_up, f->h_up, sizeof I, hipMemcpyHostToDevice, f->stream));
-            hipLaunchKernelGGL(k_mcl_init, dim3(blocks_of(f->N)), dim3(kThreads), 0, f->stream, reinterpret_cast<const InitHdr*>(f->d_up), f->d_st[0],
+            HIP_TRY(f, hipMemcpyAsync(f->d_up, f->h_up, sizeof I, hipMemcpyHostToDevice, f->stream));
+            hipLaunchKernelGGL(k_mcl_init, dim3(blocks_for(f->N, kThreads)), dim3(kThreads), 0, f->stream, reinterpret_cast<const InitHdr*>(f->d_up), f->d_st[0],
                                f->d_Q, f->d_anc);
-            MC_HIP(f, hipGetLastError());
-            MC_HIP(f, hipStreamSynchronize(f->stream));
-            f->launches = VISFS_MCL_INIT_LAUNCHES; f->copies = 1; f->waits = 1;
+            HIP_TRY(f, hipGetLastError());
+            HIP_TRY(f, hipStreamSynchronize(f->stream));
+            f->counts = { VISFS_MCL_INIT_LAUNCHES, 1, 1 };
         }
         f->cur = 0; f->update = 0; f->n = f->N;
         if (f->kld) kld_particles_replaced(f);
@@ -602,20 +587,20 @@ int visfs_mcl_init(visfs_mcl* f, const double mean[3], const double sigma[3]) {
 int visfs_mcl_update(visfs_mcl* f, const visfs_mcl_params* p, const double odom_delta[3], int32_t n, const double* points_xyz,
                      visfs_mcl_result* result) {
     if (!f || !p || !odom_delta || (n > 0 && !points_xyz)) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded([&]() -> int {
-        if (n < 0 || n > VISFS_MCL_MAX_BEAMS) return ffail(f, VISFS_BA_ERR_BAD_ARGUMENT, "the points must number 0 .. 16384");
+    return guarded(f, [&]() -> int {
+        if (n < 0 || n > VISFS_MCL_MAX_BEAMS) return fail(f, VISFS_BA_ERR_BAD_ARGUMENT, "the points must number 0 .. 16384");
         if (p->resample_interval < 1 || p->max_beams < 0 || !(std::isfinite(p->n_eff_ratio) && p->n_eff_ratio >= 0.0))
-            return ffail(f, VISFS_BA_ERR_BAD_ARGUMENT, "resample_interval >= 1, max_beams >= 0 and a finite n_eff_ratio >= 0 are needed");
+            return fail(f, VISFS_BA_ERR_BAD_ARGUMENT, "resample_interval >= 1, max_beams >= 0 and a finite n_eff_ratio >= 0 are needed");
         Hdr H;
         std::memset(&H, 0, sizeof H);
         const char* why = "";
         const int rc = motion_plan(*p, odom_delta, H.M, &why);
-        if (rc != VISFS_BA_OK) return ffail(f, rc, why);
+        if (rc != VISFS_BA_OK) return fail(f, rc, why);
         const int32_t step = p->max_beams > 0 ? (n + p->max_beams - 1) / p->max_beams : 1;
         std::vector<double> beams;
         for (int32_t i = 0; i < n; i += (step > 0 ? step : 1)) {
             const double px = points_xyz[3 * (size_t)i], py = points_xyz[3 * (size_t)i + 1];
-            if (!(std::fabs(px) <= 1e6) || !(std::fabs(py) <= 1e6)) return ffail(f, VISFS_BA_ERR_BAD_ARGUMENT, "a point is not finite");
+            if (!(std::fabs(px) <= 1e6) || !(std::fabs(py) <= 1e6)) return fail(f, VISFS_BA_ERR_BAD_ARGUMENT, "a point is not finite");
             beams.push_back(px); beams.push_back(py);
         }
         H.n = (int32_t)(beams.size() / 2);
@@ -628,7 +613,7 @@ int visfs_mcl_update(visfs_mcl* f, const visfs_mcl_params* p, const double odom_
         Rec rec;
         std::memset(&rec, 0, sizeof rec);
         if (f->device) { const int rd = device_update(f, H, beams, rec); if (rd != VISFS_BA_OK) return rd; }
-        else { host_update(f, H, beams, rec); f->launches = f->copies = f->waits = 0; }
+        else { host_update(f, H, beams, rec); f->counts = {}; }
         f->update += 1;
         if (rec.resampled) f->cur ^= 1;
         if (f->kld) kld_commit(f, rec, n_before);
@@ -648,7 +633,7 @@ int visfs_mcl_last_result(const visfs_mcl* f, visfs_mcl_result* result) {
 
 int visfs_mcl_download(visfs_mcl* f, double* x, double* y, double* yaw, double* w, int64_t* Q, int32_t* ancestors) {
     if (!f) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded([&]() -> int {
+    return guarded(f, [&]() -> int {
         const size_t N = (size_t)f->n;                                                 // the active count, and the arrays' stride
         double* dst[4] = { x, y, yaw, w };
         if (!f->device) {
@@ -657,12 +642,12 @@ int visfs_mcl_download(visfs_mcl* f, double* x, double* y, double* yaw, double* 
             if (ancestors) std::memcpy(ancestors, f->h_anc.data(), N * sizeof(int32_t));
             return (int)VISFS_BA_OK;
         }
-        MC_HIP(f, hipSetDevice(f->dev));
+        HIP_TRY(f, hipSetDevice(f->dev));
         for (int k = 0; k < 4; ++k)
-            if (dst[k]) MC_HIP(f, hipMemcpyAsync(dst[k], f->d_st[f->cur] + k * N, N * sizeof(double), hipMemcpyDeviceToHost, f->stream));
-        if (Q) MC_HIP(f, hipMemcpyAsync(Q, f->d_Q, N * sizeof(int64_t), hipMemcpyDeviceToHost, f->stream));
-        if (ancestors) MC_HIP(f, hipMemcpyAsync(ancestors, f->d_anc, N * sizeof(int32_t), hipMemcpyDeviceToHost, f->stream));
-        MC_HIP(f, hipStreamSynchronize(f->stream));
+            if (dst[k]) HIP_TRY(f, hipMemcpyAsync(dst[k], f->d_st[f->cur] + k * N, N * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+        if (Q) HIP_TRY(f, hipMemcpyAsync(Q, f->d_Q, N * sizeof(int64_t), hipMemcpyDeviceToHost, f->stream));
+        if (ancestors) HIP_TRY(f, hipMemcpyAsync(ancestors, f->d_anc, N * sizeof(int32_t), hipMemcpyDeviceToHost, f->stream));
+        HIP_TRY(f, hipStreamSynchronize(f->stream));
         return (int)VISFS_BA_OK;
     });
 }
@@ -675,15 +660,15 @@ int visfs_mcl_upload(visfs_mcl* f, const double* x, const double* y, const doubl
 }  // extern "C"
 
 int mcl::upload_n(visfs_mcl* f, int32_t n, const double* x, const double* y, const double* yaw, const double* w) {
-    return guarded([&]() -> int {
+    return guarded(f, [&]() -> int {
         const size_t N = (size_t)n;
         double sum = 0.0;
         for (size_t j = 0; j < N; ++j) {
             if (!(std::fabs(x[j]) <= 1e9) || !(std::fabs(y[j]) <= 1e9) || !(yaw[j] > -kPi && yaw[j] <= kPi) || !(std::isfinite(w[j]) && w[j] >= 0.0))
-                return ffail(f, VISFS_BA_ERR_BAD_ARGUMENT, "finite poses, yaw in (-pi, pi] and finite weights >= 0 are needed");
+                return fail(f, VISFS_BA_ERR_BAD_ARGUMENT, "finite poses, yaw in (-pi, pi] and finite weights >= 0 are needed");
             sum += w[j];
         }
-        if (!(std::isfinite(sum) && sum > 0.0)) return ffail(f, VISFS_BA_ERR_BAD_ARGUMENT, "the weights need a positive finite sum");
+        if (!(std::isfinite(sum) && sum > 0.0)) return fail(f, VISFS_BA_ERR_BAD_ARGUMENT, "the weights need a positive finite sum");
         const double* src[4] = { x, y, yaw, w };
         if (!f->device) {
             for (int k = 0; k < 4; ++k) std::memcpy(f->h_st[f->cur].data() + k * N, src[k], N * sizeof(double));
@@ -691,9 +676,9 @@ int mcl::upload_n(visfs_mcl* f, int32_t n, const double* x, const double* y, con
             if (f->kld) kld_particles_replaced(f);
             return (int)VISFS_BA_OK;
         }
-        MC_HIP(f, hipSetDevice(f->dev));
-        for (int k = 0; k < 4; ++k) MC_HIP(f, hipMemcpyAsync(f->d_st[f->cur] + k * N, src[k], N * sizeof(double), hipMemcpyHostToDevice, f->stream));
-        MC_HIP(f, hipStreamSynchronize(f->stream));
+        HIP_TRY(f, hipSetDevice(f->dev));
+        for (int k = 0; k < 4; ++k) HIP_TRY(f, hipMemcpyAsync(f->d_st[f->cur] + k * N, src[k], N * sizeof(double), hipMemcpyHostToDevice, f->stream));
+        HIP_TRY(f, hipStreamSynchronize(f->stream));
         f->n = n;
         if (f->kld) kld_particles_replaced(f);
         return (int)VISFS_BA_OK;
@@ -710,11 +695,7 @@ int visfs_mcl_hook_set_lanes(visfs_mcl* f, int32_t lanes) {
 }
 
 int visfs_mcl_last_counts(const visfs_mcl* f, int32_t* launches, int32_t* copies, int32_t* waits) {
-    if (!f) return VISFS_BA_ERR_BAD_ARGUMENT;
-    if (launches) *launches = f->launches;
-    if (copies) *copies = f->copies;
-    if (waits) *waits = f->waits;
-    return VISFS_BA_OK;
+    return f ? f->counts.read(launches, copies, waits) : (int)VISFS_BA_ERR_BAD_ARGUMENT;
 }
 
 int visfs_mcl_hook_sincos(int32_t n, const double* a, double* s, double* c) {

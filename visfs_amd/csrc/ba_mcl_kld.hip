@@ -14,6 +14,7 @@
 #include "ba_mcl_state.hpp"
 #include "ba_mcl_kld.hpp"
 #include "ba_mcl_hyp.hpp"
+#include "ba_host.hpp"
 
 #include <algorithm>
 #include <array>
@@ -24,6 +25,7 @@
 #pragma clang fp contract(off)
 
 using namespace mcl;
+using namespace host;
 
 namespace mcl {
 
@@ -243,26 +245,19 @@ int kld_device_resample(visfs_mcl* f, const Hdr* up, const double* st, double* o
     while ((1 << width) < A.slots) ++width;
     const int32_t bits = k->hash_bits < 0 || k->hash_bits > width ? width : k->hash_bits;
     A.home_mask = (int32_t)((1u << bits) - 1u);
-    if (Hyp* h = k->hyp) {                                                 // the same launch with the hypotheses; their block comes down behind KldRec
-        HypArgs G;
-        G.work = h->d_work; G.cs = h->d_cs;
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mcl_kld_resample<true>), dim3(1), dim3(kKldThreads), 0, f->stream, up, &h->d_rec->k, st, out, f->d_C, f->d_bsum, blocks,
-                           f->d_anc, A, G);
-        MC_HIP(f, hipGetLastError());
-        MC_HIP(f, hipMemcpyAsync(h->h_rec, h->d_rec, sizeof(HypRec), hipMemcpyDeviceToHost, f->stream));
-        MC_HIP(f, hipStreamSynchronize(f->stream));
-        rec = h->h_rec->k.r;
-        k->pending[0] = h->h_rec->k.n_after; k->pending[1] = h->h_rec->k.bins; k->pending[2] = h->h_rec->k.limit;
-        h->pending = h->h_rec->h;
-        return VISFS_BA_OK;
-    }
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mcl_kld_resample<false>), dim3(1), dim3(kKldThreads), 0, f->stream, up, k->d_rec, st, out, f->d_C, f->d_bsum, blocks,
-                       f->d_anc, A, HypArgs());
-    MC_HIP(f, hipGetLastError());
-    MC_HIP(f, hipMemcpyAsync(k->h_rec, k->d_rec, sizeof(KldRec), hipMemcpyDeviceToHost, f->stream));
-    MC_HIP(f, hipStreamSynchronize(f->stream));
-    rec = k->h_rec->r;
-    k->pending[0] = k->h_rec->n_after; k->pending[1] = k->h_rec->bins; k->pending[2] = k->h_rec->limit;
+    Hyp* h = k->hyp;                                                       // the same launch with the hypotheses; their block comes down behind KldRec
+    HypArgs G = HypArgs();
+    if (h) { G.work = h->d_work; G.cs = h->d_cs; }
+    const auto kernel = h ? k_mcl_kld_resample<true> : k_mcl_kld_resample<false>;
+    KldRec* d_rec = h ? &h->d_rec->k : k->d_rec;
+    KldRec* h_rec = h ? &h->h_rec->k : k->h_rec;
+    hipLaunchKernelGGL(kernel, dim3(1), dim3(kKldThreads), 0, f->stream, up, d_rec, st, out, f->d_C, f->d_bsum, blocks, f->d_anc, A, G);
+    HIP_TRY(f, hipGetLastError());
+    HIP_TRY(f, hipMemcpyAsync(h_rec, d_rec, h ? sizeof(HypRec) : sizeof(KldRec), hipMemcpyDeviceToHost, f->stream));
+    HIP_TRY(f, hipStreamSynchronize(f->stream));
+    rec = h_rec->r;
+    k->pending[0] = h_rec->n_after; k->pending[1] = h_rec->bins; k->pending[2] = h_rec->limit;
+    if (h) h->pending = h->h_rec->h;
     return VISFS_BA_OK;
 }
 
@@ -329,11 +324,11 @@ void visfs_mcl_kld_default_params(visfs_mcl_kld_params* p) {
 
 int visfs_mcl_kld_enable(visfs_mcl* f, const visfs_mcl_kld_params* p) {
     if (!f || !p) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded([&]() -> int {
-        if (p->min_particles < 1 || p->min_particles > f->N) return ffail(f, VISFS_BA_ERR_BAD_ARGUMENT, "min_particles must lie in 1 .. N");
+    return guarded(f, [&]() -> int {
+        if (p->min_particles < 1 || p->min_particles > f->N) return fail(f, VISFS_BA_ERR_BAD_ARGUMENT, "min_particles must lie in 1 .. N");
         if (!finite_pos(p->kld_err) || !finite_pos(p->kld_z) || !finite_pos(p->bin_xy) || !finite_pos(p->bin_yaw) || !(p->kld_err < 1.0))
-            return ffail(f, VISFS_BA_ERR_BAD_ARGUMENT, "kld_err, kld_z, bin_xy and bin_yaw must be finite and positive, kld_err below 1");
-        if (f->N > VISFS_MCL_KLD_MAX_PARTICLES) return ffail(f, VISFS_BA_ERR_UNSUPPORTED, "a KLD filter holds at most 16384 particles");
+            return fail(f, VISFS_BA_ERR_BAD_ARGUMENT, "kld_err, kld_z, bin_xy and bin_yaw must be finite and positive, kld_err below 1");
+        if (f->N > VISFS_MCL_KLD_MAX_PARTICLES) return fail(f, VISFS_BA_ERR_UNSUPPORTED, "a KLD filter holds at most 16384 particles");
         std::vector<int32_t> limit;
         kld_limits(*p, f->N, limit);
         Kld* k = f->kld;
@@ -342,15 +337,15 @@ int visfs_mcl_kld_enable(visfs_mcl* f, const visfs_mcl_kld_params* p) {
         auto push = [&]() -> int {
             if (!f->device) return (int)VISFS_BA_OK;
             const size_t N = (size_t)f->N;
-            MC_HIP(f, hipSetDevice(f->dev));
+            HIP_TRY(f, hipSetDevice(f->dev));
             if (fresh) {
-                MC_HIP(f, hipMalloc(reinterpret_cast<void**>(&k->d_limit), (N + 1) * sizeof(int32_t)));
-                MC_HIP(f, hipMalloc(reinterpret_cast<void**>(&k->d_work), 5 * N * sizeof(int32_t)));
-                MC_HIP(f, hipMalloc(reinterpret_cast<void**>(&k->d_rec), sizeof(KldRec)));
-                MC_HIP(f, hipHostMalloc(reinterpret_cast<void**>(&k->h_rec), sizeof(KldRec), hipHostMallocDefault));
+                HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&k->d_limit), (N + 1) * sizeof(int32_t)));
+                HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&k->d_work), 5 * N * sizeof(int32_t)));
+                HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&k->d_rec), sizeof(KldRec)));
+                HIP_TRY(f, hipHostMalloc(reinterpret_cast<void**>(&k->h_rec), sizeof(KldRec), hipHostMallocDefault));
             }
-            MC_HIP(f, hipMemcpyAsync(k->d_limit, limit.data(), (N + 1) * sizeof(int32_t), hipMemcpyHostToDevice, f->stream));
-            MC_HIP(f, hipStreamSynchronize(f->stream));                               // `limit` is pageable and leaves scope
+            HIP_TRY(f, hipMemcpyAsync(k->d_limit, limit.data(), (N + 1) * sizeof(int32_t), hipMemcpyHostToDevice, f->stream));
+            HIP_TRY(f, hipStreamSynchronize(f->stream));                               // `limit` is pageable and leaves scope
             return (int)VISFS_BA_OK;
         };
         const int rc = push();
@@ -376,27 +371,27 @@ int32_t visfs_mcl_kld_count(const visfs_mcl* f) { return f ? f->n : 0; }
 
 int visfs_mcl_kld_upload(visfs_mcl* f, int32_t n, const double* x, const double* y, const double* yaw, const double* w) {
     if (!f || !x || !y || !yaw || !w) return VISFS_BA_ERR_BAD_ARGUMENT;
-    if (!f->kld) return ffail(f, VISFS_BA_ERR_BAD_ARGUMENT, "the filter is no KLD filter");
-    if (n < 1 || n > f->N) return ffail(f, VISFS_BA_ERR_BAD_ARGUMENT, "the count must lie in 1 .. N");
+    if (!f->kld) return fail(f, VISFS_BA_ERR_BAD_ARGUMENT, "the filter is no KLD filter");
+    if (n < 1 || n > f->N) return fail(f, VISFS_BA_ERR_BAD_ARGUMENT, "the count must lie in 1 .. N");
     return upload_n(f, n, x, y, yaw, w);
 }
 
 int visfs_mcl_kld_limits(visfs_mcl* f, int32_t* limit) {
     if (!f || !limit) return VISFS_BA_ERR_BAD_ARGUMENT;
-    if (!f->kld) return ffail(f, VISFS_BA_ERR_BAD_ARGUMENT, "the filter is no KLD filter");
-    return guarded([&]() -> int {
+    if (!f->kld) return fail(f, VISFS_BA_ERR_BAD_ARGUMENT, "the filter is no KLD filter");
+    return guarded(f, [&]() -> int {
         const size_t bytes = ((size_t)f->N + 1) * sizeof(int32_t);
         if (!f->device) { std::memcpy(limit, f->kld->h_limit.data(), bytes); return (int)VISFS_BA_OK; }
-        MC_HIP(f, hipSetDevice(f->dev));                                              // what the device holds, not the host's copy
-        MC_HIP(f, hipMemcpyAsync(limit, f->kld->d_limit, bytes, hipMemcpyDeviceToHost, f->stream));
-        MC_HIP(f, hipStreamSynchronize(f->stream));
+        HIP_TRY(f, hipSetDevice(f->dev));                                              // what the device holds, not the host's copy
+        HIP_TRY(f, hipMemcpyAsync(limit, f->kld->d_limit, bytes, hipMemcpyDeviceToHost, f->stream));
+        HIP_TRY(f, hipStreamSynchronize(f->stream));
         return (int)VISFS_BA_OK;
     });
 }
 
 int visfs_mcl_kld_hook_set_hash_bits(visfs_mcl* f, int32_t bits) {
     if (!f) return VISFS_BA_ERR_BAD_ARGUMENT;
-    if (!f->kld) return ffail(f, VISFS_BA_ERR_BAD_ARGUMENT, "the filter is no KLD filter");
+    if (!f->kld) return fail(f, VISFS_BA_ERR_BAD_ARGUMENT, "the filter is no KLD filter");
     if (bits < -1) return VISFS_BA_ERR_BAD_ARGUMENT;
     f->kld->hash_bits = bits;
     return VISFS_BA_OK;
@@ -407,22 +402,22 @@ int visfs_mcl_hyp_abi_version(void) { return VISFS_MCL_HYP_ABI_VERSION; }
 
 int visfs_mcl_hyp_enable(visfs_mcl* f) {
     if (!f) return VISFS_BA_ERR_BAD_ARGUMENT;
-    if (!f->kld) return ffail(f, VISFS_BA_ERR_BAD_ARGUMENT, "the filter is no KLD filter");
+    if (!f->kld) return fail(f, VISFS_BA_ERR_BAD_ARGUMENT, "the filter is no KLD filter");
     if (f->kld->hyp) return VISFS_BA_OK;
-    return guarded([&]() -> int {
+    return guarded(f, [&]() -> int {
         Hyp* h = new Hyp();
         std::memset(&h->pending, 0, sizeof h->pending);
         std::memset(&h->last, 0, sizeof h->last);
         auto push = [&]() -> int {
             if (!f->device) return (int)VISFS_BA_OK;
             const size_t N = (size_t)f->N;
-            MC_HIP(f, hipSetDevice(f->dev));
-            MC_HIP(f, hipMalloc(reinterpret_cast<void**>(&h->d_work), (size_t)kHypWorkInts * N * sizeof(int32_t)));
-            MC_HIP(f, hipMalloc(reinterpret_cast<void**>(&h->d_cs), 2 * N * sizeof(double)));
-            MC_HIP(f, hipMalloc(reinterpret_cast<void**>(&h->d_rec), sizeof(HypRec)));
-            MC_HIP(f, hipHostMalloc(reinterpret_cast<void**>(&h->h_rec), sizeof(HypRec), hipHostMallocDefault));
-            MC_HIP(f, hipMemsetAsync(h->d_rec, 0, sizeof(HypRec), f->stream));
-            MC_HIP(f, hipStreamSynchronize(f->stream));
+            HIP_TRY(f, hipSetDevice(f->dev));
+            HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&h->d_work), (size_t)kHypWorkInts * N * sizeof(int32_t)));
+            HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&h->d_cs), 2 * N * sizeof(double)));
+            HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&h->d_rec), sizeof(HypRec)));
+            HIP_TRY(f, hipHostMalloc(reinterpret_cast<void**>(&h->h_rec), sizeof(HypRec), hipHostMallocDefault));
+            HIP_TRY(f, hipMemsetAsync(h->d_rec, 0, sizeof(HypRec), f->stream));
+            HIP_TRY(f, hipStreamSynchronize(f->stream));
             return (int)VISFS_BA_OK;
         };
         const int rc = push();
@@ -441,15 +436,15 @@ int visfs_mcl_hyp_last(const visfs_mcl* f, visfs_mcl_hyp_result* r) {
 
 int visfs_mcl_hyp_download_labels(visfs_mcl* f, int32_t* label) {
     if (!f || !label) return VISFS_BA_ERR_BAD_ARGUMENT;
-    if (!f->kld || !f->kld->hyp) return ffail(f, VISFS_BA_ERR_BAD_ARGUMENT, "hypotheses are not enabled");
+    if (!f->kld || !f->kld->hyp) return fail(f, VISFS_BA_ERR_BAD_ARGUMENT, "hypotheses are not enabled");
     Hyp* h = f->kld->hyp;
-    if (h->last.n_hypotheses == 0) return ffail(f, VISFS_BA_ERR_BAD_ARGUMENT, "there are no hypotheses since the particles were replaced");
-    return guarded([&]() -> int {
+    if (h->last.n_hypotheses == 0) return fail(f, VISFS_BA_ERR_BAD_ARGUMENT, "there are no hypotheses since the particles were replaced");
+    return guarded(f, [&]() -> int {
         const size_t bytes = (size_t)h->last.n * sizeof(int32_t);
         if (!f->device) { std::memcpy(label, h->h_label.data(), bytes); return (int)VISFS_BA_OK; }
-        MC_HIP(f, hipSetDevice(f->dev));
-        MC_HIP(f, hipMemcpyAsync(label, h->d_work, bytes, hipMemcpyDeviceToHost, f->stream));
-        MC_HIP(f, hipStreamSynchronize(f->stream));
+        HIP_TRY(f, hipSetDevice(f->dev));
+        HIP_TRY(f, hipMemcpyAsync(label, h->d_work, bytes, hipMemcpyDeviceToHost, f->stream));
+        HIP_TRY(f, hipStreamSynchronize(f->stream));
         return (int)VISFS_BA_OK;
     });
 }

@@ -2,6 +2,7 @@
 // (include/visfs_mcl_kld.h).  Internal: nothing here is exported.
 #pragma once
 
+#include "ba_host.hpp"
 #include "ba_mcl.hpp"
 #include "ba_submap.hpp"
 
@@ -22,7 +23,7 @@ struct visfs_mcl_field {
     std::vector<int64_t> h_q;                 // both flavours keep the table
     uint16_t* d_t = nullptr;
     int64_t* d_q = nullptr;
-    int32_t launches = 0, copies = 0, waits = 0;
+    host::Counts counts;
 };
 
 struct visfs_mcl {
@@ -55,24 +56,11 @@ struct visfs_mcl {
     mcl::Rec* d_rec = nullptr;
     visfs_mcl_result last;
     bool have_last = false;
-    int32_t launches = 0, copies = 0, waits = 0;
+    host::Counts counts;
     mcl::Kld* kld = nullptr;                  // null: the plain filter
 };
 
 namespace mcl {
-
-inline int ffail(visfs_mcl* f, int rc, const std::string& why) { f->err = why; return rc; }
-
-#define MC_HIP(f, expr)                                                                                               \
-    do {                                                                                                              \
-        hipError_t e_ = (expr);                                                                                       \
-        if (e_ != hipSuccess) return mcl::ffail((f), VISFS_BA_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-template <class F> int guarded(F&& f) noexcept {
-    try { return f(); }
-    catch (...) { return (int)VISFS_BA_ERR_DEVICE; }
-}
 
 // ---- ba_mcl.hip
 // visfs_mcl_upload with a count: the refusals, the copy at stride n, and n becomes the active count.

@@ -17,6 +17,7 @@
 #include "ba_pnp.hpp"
 #include "ba_flow.hpp"
 #include "ba_group.hpp"      // pnp::group_pnp, pnp::check_params, pnp::finalize
+#include "ba_host.hpp"
 #include "../../include/visfs_pnp.h"
 
 #include <algorithm>
@@ -27,6 +28,7 @@
 #include <vector>
 
 using namespace pnp;
+using namespace host;
 
 namespace pnp {
 
@@ -243,10 +245,10 @@ int group_pnp(hipStream_t stream, int n, const PnpRec* d_recs, const PnpShape& S
     hipLaunchKernelGGL(k_pnp_ransac_g, dim3((unsigned)((S.iterations + PN_T / 64 - 1) / (PN_T / 64)), 1, (unsigned)n), dim3(PN_T), 0, stream,
                        d_recs, S);
     if (hipGetLastError() != hipSuccess) return VISFS_BA_ERR_DEVICE;
-    ++cnt->kernels;
+    ++cnt->launches;
     hipLaunchKernelGGL(k_pnp_refine_g, dim3(1, 1, (unsigned)n), dim3(PN_T), 0, stream, d_recs, S);
     if (hipGetLastError() != hipSuccess) return VISFS_BA_ERR_DEVICE;
-    ++cnt->kernels;
+    ++cnt->launches;
     return VISFS_BA_OK;
 }
 
@@ -283,34 +285,20 @@ struct visfs_pnp {
 
 namespace {
 
-size_t up256(size_t x) { return (x + 255) & ~size_t(255); }
-int fail(visfs_pnp* p, int rc, const std::string& why) { p->err = why; return rc; }
-#define PN_HIP(p, expr)                                                                                   \
-    do {                                                                                                  \
-        hipError_t e_ = (expr);                                                                           \
-        if (e_ != hipSuccess) return fail((p), VISFS_BA_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-template <class F> int guarded_pn(visfs_pnp* p, F&& fn) noexcept {
-    try { return fn(); }
-    catch (const std::bad_alloc&) { if (p) p->err = "out of host memory"; return VISFS_BA_ERR_DEVICE; }
-    catch (...) { if (p) p->err = "unexpected exception"; return VISFS_BA_ERR_DEVICE; }
-}
-
 int device_init(visfs_pnp* p) {
-    PN_HIP(p, hipSetDevice(p->dev));
+    HIP_TRY(p, hipSetDevice(p->dev));
     const size_t cap = (size_t)p->cap;
     const size_t in_bytes = kHeaderBytes + up256(sizeof(Row) * cap), out_bytes = kHeaderBytes + up256(4 * cap);
     static_assert(sizeof(Result) <= kHeaderBytes, "the result block is one header");
-    PN_HIP(p, hipHostMalloc(reinterpret_cast<void**>(&p->h_in), in_bytes, hipHostMallocDefault));
-    PN_HIP(p, hipHostMalloc(reinterpret_cast<void**>(&p->h_out), out_bytes, hipHostMallocDefault));
-    PN_HIP(p, hipMalloc(reinterpret_cast<void**>(&p->d_in), in_bytes));
-    PN_HIP(p, hipMalloc(reinterpret_cast<void**>(&p->d_out), out_bytes));
+    HIP_TRY(p, hipHostMalloc(reinterpret_cast<void**>(&p->h_in), in_bytes, hipHostMallocDefault));
+    HIP_TRY(p, hipHostMalloc(reinterpret_cast<void**>(&p->h_out), out_bytes, hipHostMallocDefault));
+    HIP_TRY(p, hipMalloc(reinterpret_cast<void**>(&p->d_in), in_bytes));
+    HIP_TRY(p, hipMalloc(reinterpret_cast<void**>(&p->d_out), out_bytes));
     const size_t H = kMaxHypotheses, R = kMaxRefine;
     const size_t o_models = 0, o_ptq = o_models + up256(96 * H), o_samples = o_ptq + up256(56 * R), o_vc = o_samples + up256(16 * H),
                  o_pthr = o_vc + up256(8 * H), o_pcnt = o_pthr + up256(4 * R), o_plists = o_pcnt + up256(4 * R),
                  bytes = o_plists + up256(4 * R * cap);
-    PN_HIP(p, hipMalloc(reinterpret_cast<void**>(&p->d_state), bytes));
+    HIP_TRY(p, hipMalloc(reinterpret_cast<void**>(&p->d_state), bytes));
     p->d_models = reinterpret_cast<double*>(p->d_state + o_models);
     p->d_pass_tq = reinterpret_cast<double*>(p->d_state + o_ptq);
     p->d_samples = reinterpret_cast<int32_t*>(p->d_state + o_samples);
@@ -418,25 +406,25 @@ int host_solve(visfs_pnp* p, const visfs_pnp_params& prm, const Cam& K, int32_t 
 }
 
 int device_solve(visfs_pnp* p, const visfs_pnp_params& prm, const Cam& K, int32_t m, int min_inliers, std::vector<int32_t>& inliers) {
-    PN_HIP(p, hipSetDevice(p->dev));
+    HIP_TRY(p, hipSetDevice(p->dev));
     // (the rows were written into h_in behind the header by the caller, after the stream had drained)
     std::memset(p->h_in, 0, kHeaderBytes);
-    PN_HIP(p, hipMemcpyAsync(p->d_in, p->h_in, kHeaderBytes + sizeof(Row) * (size_t)m, hipMemcpyHostToDevice, p->stream));
+    HIP_TRY(p, hipMemcpyAsync(p->d_in, p->h_in, kHeaderBytes + sizeof(Row) * (size_t)m, hipMemcpyHostToDevice, p->stream));
     RansacArgs A;
     A.rows = reinterpret_cast<const Row*>(p->d_in + kHeaderBytes); A.m = m; A.iterations = prm.iterations; A.seed = prm.seed; A.K = K;
     A.thr = prm.reproj_error; A.samples = p->d_samples; A.vc = p->d_vc; A.models = p->d_models;
     A.key = reinterpret_cast<unsigned long long*>(p->d_in);
     hipLaunchKernelGGL(k_pnp_ransac, dim3((unsigned)((prm.iterations + PN_T / 64 - 1) / (PN_T / 64))), dim3(PN_T), 0, p->stream, A);
-    PN_HIP(p, hipGetLastError());
+    HIP_TRY(p, hipGetLastError());
     RefineArgs B;
     B.rows = A.rows; B.m = m; B.cap = p->cap; B.K = K; B.min_inliers = min_inliers; B.refine_iterations = prm.refine_iterations;
     B.thr0 = prm.reproj_error; B.sigma = prm.refine_sigma; B.key = A.key; B.models = p->d_models;
     B.res = reinterpret_cast<Result*>(p->d_out); B.inliers = reinterpret_cast<int32_t*>(p->d_out + kHeaderBytes);
     B.pass_tq = p->d_pass_tq; B.pass_thr = p->d_pass_thr; B.pass_cnt = p->d_pass_cnt; B.pass_lists = p->d_pass_lists;
     hipLaunchKernelGGL(k_pnp_refine, dim3(1), dim3(PN_T), 0, p->stream, B);
-    PN_HIP(p, hipGetLastError());
-    PN_HIP(p, hipMemcpyAsync(p->h_out, p->d_out, kHeaderBytes + 4 * (size_t)m, hipMemcpyDeviceToHost, p->stream));
-    PN_HIP(p, hipStreamSynchronize(p->stream));
+    HIP_TRY(p, hipGetLastError());
+    HIP_TRY(p, hipMemcpyAsync(p->h_out, p->d_out, kHeaderBytes + 4 * (size_t)m, hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(p, hipStreamSynchronize(p->stream));
     std::memcpy(&p->res, p->h_out, sizeof(Result));
     if (p->res.n_inliers < 0 || p->res.n_inliers > m) return fail(p, VISFS_BA_ERR_DEVICE, "the device returned an impossible inlier count");
     const int32_t* li = reinterpret_cast<const int32_t*>(p->h_out + kHeaderBytes);
@@ -538,7 +526,7 @@ int visfs_pnp_create_host(int32_t capacity_points, visfs_pnp** out) {
     *out = nullptr;
     if (capacity_points < 1) return VISFS_BA_ERR_BAD_ARGUMENT;
     if (capacity_points > kMaxPoints) return VISFS_BA_ERR_UNSUPPORTED;
-    return guarded_pn(nullptr, [&]() -> int {
+    return guarded(nullptr, [&]() -> int {
         visfs_pnp* p = new visfs_pnp();
         p->cap = capacity_points;
         *out = p;
@@ -551,7 +539,7 @@ int visfs_pnp_create(visfs_ba_handle* h, int32_t capacity_points, visfs_pnp** ou
     *out = nullptr;
     if (capacity_points < 1) { visfs_internal_set_error(h, "capacity_points must be at least 1"); return VISFS_BA_ERR_BAD_ARGUMENT; }
     if (capacity_points > kMaxPoints) { visfs_internal_set_error(h, "capacity_points above 4096"); return VISFS_BA_ERR_UNSUPPORTED; }
-    return guarded_pn(nullptr, [&]() -> int {
+    return guarded(nullptr, [&]() -> int {
         visfs_pnp* p = new visfs_pnp();
         p->cap = capacity_points;
         p->device = true; p->ba = h; p->dev = visfs_internal_device(h); p->stream = visfs_internal_stream(h);
@@ -577,14 +565,14 @@ int visfs_pnp_solve(visfs_pnp* p, const visfs_pnp_params* params, const visfs_pn
     if (!params || !camera || !T_out || !cov_out || !n_matches || !n_inliers || n < 0 ||
         (n > 0 && (!from_xyz || !to_xy || !matches_out || !inliers_out)))
         return fail(p, VISFS_BA_ERR_BAD_ARGUMENT, "a required pointer is null or n is negative");
-    return guarded_pn(p, [&]() -> int {
+    return guarded(p, [&]() -> int {
         const char* why = "";
         const int rc = check_params(*params, *camera, &why);
         if (rc != VISFS_BA_OK) return fail(p, rc, why);
         if (n > p->cap) return fail(p, VISFS_BA_ERR_BAD_ARGUMENT, "n is above the capacity of the solver");
         if (p->device) {
-            PN_HIP(p, hipSetDevice(p->dev));
-            PN_HIP(p, hipStreamSynchronize(p->stream));            // (the pinned blocks are free again)
+            HIP_TRY(p, hipSetDevice(p->dev));
+            HIP_TRY(p, hipStreamSynchronize(p->stream));            // (the pinned blocks are free again)
         }
         // step 1: the correspondences
         p->rows.clear();
@@ -633,7 +621,7 @@ int visfs_pnp_download(visfs_pnp* p, int32_t* samples, int32_t* valid, double* m
                        double* refit_tq, double* pass_tq, float* pass_threshold, int32_t* pass_count, int32_t* pass_inliers) {
     if (!p) return VISFS_BA_ERR_BAD_ARGUMENT;
     if (!p->solved) return fail(p, VISFS_BA_ERR_NOT_LOADED, "no visfs_pnp_solve call yet");
-    return guarded_pn(p, [&]() -> int {
+    return guarded(p, [&]() -> int {
         const size_t H = (size_t)p->last_hyp, R = (size_t)p->last_passes, m = (size_t)p->last_m;
         if (winner) *winner = p->res.winner;
         if (refit_tq) for (int i = 0; i < 7; ++i) refit_tq[i] = p->res.refit0[i];
@@ -645,18 +633,18 @@ int visfs_pnp_download(visfs_pnp* p, int32_t* samples, int32_t* valid, double* m
         const std::vector<float>* ph = &p->pass_thr;
         size_t stride = m;
         if (p->device && H > 0) {
-            PN_HIP(p, hipSetDevice(p->dev));
-            PN_HIP(p, hipStreamSynchronize(p->stream));
+            HIP_TRY(p, hipSetDevice(p->dev));
+            HIP_TRY(p, hipStreamSynchronize(p->stream));
             h_samples.resize(4 * H); h_vc.resize(2 * H); h_models.resize(12 * H);
             h_ptq.resize(7 * kMaxRefine); h_pthr.resize(kMaxRefine); h_pcnt.resize(kMaxRefine); h_plists.resize((size_t)kMaxRefine * p->cap);
-            PN_HIP(p, hipMemcpy(h_samples.data(), p->d_samples, 16 * H, hipMemcpyDeviceToHost));
-            PN_HIP(p, hipMemcpy(h_vc.data(), p->d_vc, 8 * H, hipMemcpyDeviceToHost));
-            PN_HIP(p, hipMemcpy(h_models.data(), p->d_models, 96 * H, hipMemcpyDeviceToHost));
+            HIP_TRY(p, hipMemcpy(h_samples.data(), p->d_samples, 16 * H, hipMemcpyDeviceToHost));
+            HIP_TRY(p, hipMemcpy(h_vc.data(), p->d_vc, 8 * H, hipMemcpyDeviceToHost));
+            HIP_TRY(p, hipMemcpy(h_models.data(), p->d_models, 96 * H, hipMemcpyDeviceToHost));
             if (R > 0) {
-                PN_HIP(p, hipMemcpy(h_ptq.data(), p->d_pass_tq, 56 * R, hipMemcpyDeviceToHost));
-                PN_HIP(p, hipMemcpy(h_pthr.data(), p->d_pass_thr, 4 * R, hipMemcpyDeviceToHost));
-                PN_HIP(p, hipMemcpy(h_pcnt.data(), p->d_pass_cnt, 4 * R, hipMemcpyDeviceToHost));
-                PN_HIP(p, hipMemcpy(h_plists.data(), p->d_pass_lists, 4 * R * (size_t)p->cap, hipMemcpyDeviceToHost));
+                HIP_TRY(p, hipMemcpy(h_ptq.data(), p->d_pass_tq, 56 * R, hipMemcpyDeviceToHost));
+                HIP_TRY(p, hipMemcpy(h_pthr.data(), p->d_pass_thr, 4 * R, hipMemcpyDeviceToHost));
+                HIP_TRY(p, hipMemcpy(h_pcnt.data(), p->d_pass_cnt, 4 * R, hipMemcpyDeviceToHost));
+                HIP_TRY(p, hipMemcpy(h_plists.data(), p->d_pass_lists, 4 * R * (size_t)p->cap, hipMemcpyDeviceToHost));
             }
             s = &h_samples; vc = &h_vc; pc = &h_pcnt; pl = &h_plists; mo = &h_models; pt = &h_ptq; ph = &h_pthr;
             stride = (size_t)p->cap;

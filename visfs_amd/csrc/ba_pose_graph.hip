@@ -9,6 +9,7 @@
 // same `run` with loops for the collective operations.
 #pragma clang fp contract(off)
 #include "ba_pose_graph_object.hpp"
+#include "ba_host.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -19,6 +20,7 @@
 #include "ba_submap.hpp"
 
 using namespace posegraph;
+using namespace host;
 
 namespace posegraph {
 
@@ -57,15 +59,15 @@ int run_plan(visfs_pose_graph* pg, const Plan& pl, const Prm& P, const double* h
         *out = o;
         return VISFS_BA_OK;
     }
-    PG_HIP(hipSetDevice(pg->dev));
+    HIP_TRY(pg, hipSetDevice(pg->dev));
     const size_t bytes = pack(pl, hook_r, pg->h_up, pg->d_up, v);
     double* d_out = carve(v, pg->d_work);
     const size_t out_bytes = out_doubles(pl.N, pl.E) * sizeof(double);
-    PG_HIP(hipMemcpyAsync(pg->d_up, pg->h_up, bytes, hipMemcpyHostToDevice, pg->stream));
+    HIP_TRY(pg, hipMemcpyAsync(pg->d_up, pg->h_up, bytes, hipMemcpyHostToDevice, pg->stream));
     hipLaunchKernelGGL(k_pose_graph, dim3(1), dim3(kLanes), 0, pg->stream, v, P);
-    PG_HIP(hipGetLastError());
-    PG_HIP(hipMemcpyAsync(pg->h_out, d_out, out_bytes, hipMemcpyDeviceToHost, pg->stream));
-    PG_HIP(hipStreamSynchronize(pg->stream));
+    HIP_TRY(pg, hipGetLastError());
+    HIP_TRY(pg, hipMemcpyAsync(pg->h_out, d_out, out_bytes, hipMemcpyDeviceToHost, pg->stream));
+    HIP_TRY(pg, hipStreamSynchronize(pg->stream));
     pg->view = v;
     *out = reinterpret_cast<const double*>(pg->h_out);
     return VISFS_BA_OK;
@@ -75,9 +77,9 @@ int run_plan(visfs_pose_graph* pg, const Plan& pl, const Prm& P, const double* h
 int fetch(visfs_pose_graph* pg, const double* src, size_t count, double* dst) {
     if (!dst || count == 0) return VISFS_BA_OK;
     if (!pg->device) { std::memcpy(dst, src, count * sizeof(double)); return VISFS_BA_OK; }
-    PG_HIP(hipSetDevice(pg->dev));
-    PG_HIP(hipMemcpyAsync(dst, src, count * sizeof(double), hipMemcpyDeviceToHost, pg->stream));
-    PG_HIP(hipStreamSynchronize(pg->stream));
+    HIP_TRY(pg, hipSetDevice(pg->dev));
+    HIP_TRY(pg, hipMemcpyAsync(dst, src, count * sizeof(double), hipMemcpyDeviceToHost, pg->stream));
+    HIP_TRY(pg, hipStreamSynchronize(pg->stream));
     return VISFS_BA_OK;
 }
 
@@ -105,7 +107,7 @@ int visfs_pose_graph_create(visfs_ba_handle* h, int32_t max_vertices, int32_t ma
     *out = nullptr;
     if (max_vertices < 1 || max_edges < 1) return VISFS_BA_ERR_BAD_ARGUMENT;
     if (max_vertices > VISFS_POSE_GRAPH_MAX_VERTICES || max_edges > VISFS_POSE_GRAPH_MAX_EDGES) return VISFS_BA_ERR_UNSUPPORTED;
-    return guarded([&]() -> int {
+    return guarded(nullptr, [&]() -> int {
         visfs_pose_graph* pg = new visfs_pose_graph();
         pg->maxN = max_vertices; pg->maxE = max_edges;
         pg->up_bytes = up_capacity(max_vertices, max_edges) + 128;
@@ -118,11 +120,11 @@ int visfs_pose_graph_create(visfs_ba_handle* h, int32_t max_vertices, int32_t ma
         }
         pg->device = true; pg->dev = visfs_internal_device(h); pg->stream = visfs_internal_stream(h);
         const int rc = [&]() -> int {
-            PG_HIP(hipSetDevice(pg->dev));
-            PG_HIP(hipHostMalloc(reinterpret_cast<void**>(&pg->h_up), pg->up_bytes, hipHostMallocDefault));
-            PG_HIP(hipMalloc(reinterpret_cast<void**>(&pg->d_up), pg->up_bytes));
-            PG_HIP(hipMalloc(reinterpret_cast<void**>(&pg->d_work), pg->work_doubles * sizeof(double)));
-            PG_HIP(hipHostMalloc(reinterpret_cast<void**>(&pg->h_out), out_doubles(max_vertices, max_edges) * sizeof(double), hipHostMallocDefault));
+            HIP_TRY(pg, hipSetDevice(pg->dev));
+            HIP_TRY(pg, hipHostMalloc(reinterpret_cast<void**>(&pg->h_up), pg->up_bytes, hipHostMallocDefault));
+            HIP_TRY(pg, hipMalloc(reinterpret_cast<void**>(&pg->d_up), pg->up_bytes));
+            HIP_TRY(pg, hipMalloc(reinterpret_cast<void**>(&pg->d_work), pg->work_doubles * sizeof(double)));
+            HIP_TRY(pg, hipHostMalloc(reinterpret_cast<void**>(&pg->h_out), out_doubles(max_vertices, max_edges) * sizeof(double), hipHostMallocDefault));
             return (int)VISFS_BA_OK;
         }();
         if (rc != VISFS_BA_OK) { visfs_internal_set_error(h, pg->err.c_str()); release(pg); delete pg; return rc; }
@@ -142,7 +144,7 @@ const char* visfs_pose_graph_last_error(const visfs_pose_graph* pg) { return pg 
 int visfs_pose_graph_optimize(visfs_pose_graph* pg, const visfs_pose_graph_params* p, int32_t N, const double* poses, const uint8_t* fixed, int32_t E,
                               const visfs_pose_graph_edge* edges, double* poses_out, double* chi2_out, visfs_pose_graph_result* result) {
     if (!pg || !p || !poses || !fixed || !edges || !poses_out || !result) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded([&]() -> int {
+    return guarded(pg, [&]() -> int {
         if (p->max_iterations < 1 || p->max_iterations > VISFS_POSE_GRAPH_MAX_ITERATIONS) return fail(pg, VISFS_BA_ERR_BAD_ARGUMENT, "max_iterations must lie in [1, 50]");
         if (p->max_pcg_iterations < 1 || p->pcg_budget < 1) return fail(pg, VISFS_BA_ERR_BAD_ARGUMENT, "max_pcg_iterations and pcg_budget must be at least 1");
         if (p->preconditioner != 0 && p->preconditioner != 1) return fail(pg, VISFS_BA_ERR_BAD_ARGUMENT, "preconditioner must be 0 or 1");
@@ -162,7 +164,7 @@ int visfs_pose_graph_optimize(visfs_pose_graph* pg, const visfs_pose_graph_param
         std::memcpy(poses_out, out + kResDoubles, 3 * (size_t)N * sizeof(double));
         if (chi2_out) std::memcpy(chi2_out, out + kResDoubles + 3 * (size_t)N, (size_t)E * sizeof(double));
         pg->trials = result->trials;
-        pg->launches = pg->device ? 1 : 0; pg->copies = pg->device ? 2 : 0; pg->waits = pg->device ? 1 : 0;
+        pg->counts = { pg->device ? 1 : 0, pg->device ? 2 : 0, pg->device ? 1 : 0 };
         pg->err.clear();
         return (int)VISFS_BA_OK;
     });
@@ -170,7 +172,7 @@ int visfs_pose_graph_optimize(visfs_pose_graph* pg, const visfs_pose_graph_param
 
 int visfs_pose_graph_download_trace(visfs_pose_graph* pg, int32_t cap, double* trace, int32_t* trials) {
     if (!pg || !trials || cap < 0) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded([&]() -> int {
+    return guarded(pg, [&]() -> int {
         const int32_t n = pg->trials < kMaxTrials ? pg->trials : kMaxTrials;
         *trials = n;
         if (!trace || n == 0) return (int)VISFS_BA_OK;
@@ -182,7 +184,7 @@ int visfs_pose_graph_download_trace(visfs_pose_graph* pg, int32_t cap, double* t
 int visfs_pose_graph_linearize(visfs_pose_graph* pg, int32_t N, const double* poses, const uint8_t* fixed, int32_t E, const visfs_pose_graph_edge* edges,
                                int32_t* n_rows, double* edge_blocks, double* g, double* D, double* C, double* cost, double* chi2) {
     if (!pg || !poses || !fixed || !edges) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded([&]() -> int {
+    return guarded(pg, [&]() -> int {
         Plan pl;
         std::string why;
         int rc = make_plan(N, poses, fixed, E, edges, pg->maxN, pg->maxE, pl, why);
@@ -206,7 +208,7 @@ int visfs_pose_graph_linearize(visfs_pose_graph* pg, int32_t N, const double* po
 int visfs_pose_graph_precondition(visfs_pose_graph* pg, int32_t preconditioner, double lambda, int32_t N, const double* poses, const uint8_t* fixed, int32_t E,
                                   const visfs_pose_graph_edge* edges, const double* r, double* z) {
     if (!pg || !poses || !fixed || !edges || !r || !z) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded([&]() -> int {
+    return guarded(pg, [&]() -> int {
         if (preconditioner != 0 && preconditioner != 1) return fail(pg, VISFS_BA_ERR_BAD_ARGUMENT, "preconditioner must be 0 or 1");
         if (!std::isfinite(lambda) || lambda < 0.0) return fail(pg, VISFS_BA_ERR_BAD_ARGUMENT, "lambda must be finite and not negative");
         Plan pl;
@@ -229,7 +231,7 @@ int visfs_pose_graph_precondition(visfs_pose_graph* pg, int32_t preconditioner, 
 int visfs_pose_graph_plan(int32_t N, const uint8_t* fixed, int32_t E, const visfs_pose_graph_edge* edges, int32_t* n_rows, int32_t* row_of, int32_t* inc_ptr,
                           int32_t* inc, int32_t* chain_ptr, int32_t* chain) {
     if (!fixed || !edges || !n_rows || !row_of || !inc_ptr || !inc || !chain_ptr || !chain) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded([&]() -> int {
+    return guarded(nullptr, [&]() -> int {
         Plan pl;
         std::string why;
         const std::vector<double> poses(3 * (size_t)(N > 0 ? N : 0), 0.0);
@@ -246,11 +248,7 @@ int visfs_pose_graph_plan(int32_t N, const uint8_t* fixed, int32_t E, const visf
 }
 
 int visfs_pose_graph_last_counts(const visfs_pose_graph* pg, int32_t* launches, int32_t* copies, int32_t* waits) {
-    if (!pg) return VISFS_BA_ERR_BAD_ARGUMENT;
-    if (launches) *launches = pg->launches;
-    if (copies) *copies = pg->copies;
-    if (waits) *waits = pg->waits;
-    return VISFS_BA_OK;
+    return pg ? pg->counts.read(launches, copies, waits) : (int)VISFS_BA_ERR_BAD_ARGUMENT;
 }
 
 int visfs_pose_graph_edge_from_refine(const double a[3], const visfs_scan_refine_result* r, double z[3], double W[9]) {

@@ -14,6 +14,7 @@
 #pragma clang fp contract(off)
 #include "ba_pose_graph_object.hpp"
 #include "ba_pose_graph_cov.hpp"
+#include "ba_host.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -22,6 +23,7 @@
 #include <vector>
 
 using namespace posegraph;
+using namespace host;
 
 namespace posegraph {
 
@@ -43,7 +45,7 @@ struct CovObject {
     const double* sol = nullptr;
     int64_t sol_stride = 0;
     std::vector<int32_t> flags;
-    int32_t launches = 0, copies = 0, waits = 0;
+    Counts counts;
 };
 
 void cov_release(CovObject* c) {
@@ -135,11 +137,11 @@ int cov_reserve(visfs_pose_graph* pg, int32_t columns, int32_t n) {
             c->up.assign(c->up_bytes, 0);
             c->work.assign(fixed, 0.0);
         } else {
-            PG_HIP(hipSetDevice(pg->dev));
-            PG_HIP(hipHostMalloc(reinterpret_cast<void**>(&c->h_up), c->up_bytes, hipHostMallocDefault));
-            PG_HIP(hipMalloc(reinterpret_cast<void**>(&c->d_up), c->up_bytes));
-            PG_HIP(hipMalloc(reinterpret_cast<void**>(&c->d_work), fixed * sizeof(double)));
-            PG_HIP(hipHostMalloc(reinterpret_cast<void**>(&c->h_out), cov_out_doubles(3 * kCovMaxSources, kCovMaxQueries) * sizeof(double), hipHostMallocDefault));
+            HIP_TRY(pg, hipSetDevice(pg->dev));
+            HIP_TRY(pg, hipHostMalloc(reinterpret_cast<void**>(&c->h_up), c->up_bytes, hipHostMallocDefault));
+            HIP_TRY(pg, hipMalloc(reinterpret_cast<void**>(&c->d_up), c->up_bytes));
+            HIP_TRY(pg, hipMalloc(reinterpret_cast<void**>(&c->d_work), fixed * sizeof(double)));
+            HIP_TRY(pg, hipHostMalloc(reinterpret_cast<void**>(&c->h_out), cov_out_doubles(3 * kCovMaxSources, kCovMaxQueries) * sizeof(double), hipHostMallocDefault));
         }
         c->fixed_doubles = fixed;
     }
@@ -149,10 +151,10 @@ int cov_reserve(visfs_pose_graph* pg, int32_t columns, int32_t n) {
     }
     const size_t need = (size_t)columns * kCovColumnVectors * 3 * (size_t)n;
     if (need > c->arena_doubles) {
-        PG_HIP(hipSetDevice(pg->dev));
+        HIP_TRY(pg, hipSetDevice(pg->dev));
         c->valid = false;                                                    // the stored columns go with the old arena
         if (c->d_arena) { (void)hipFree(c->d_arena); c->d_arena = nullptr; c->arena_doubles = 0; }
-        PG_HIP(hipMalloc(reinterpret_cast<void**>(&c->d_arena), need * sizeof(double)));
+        HIP_TRY(pg, hipMalloc(reinterpret_cast<void**>(&c->d_arena), need * sizeof(double)));
         c->arena_doubles = need;
     }
     return VISFS_BA_OK;
@@ -187,11 +189,11 @@ int run_cov(visfs_pose_graph* pg, const Plan& pl, const CovPlan& cp, const Prm& 
             }
             for (int32_t k = 0; k < q.Q; ++k) cov_query(v, q, k);
         }
-        c->launches = c->copies = c->waits = 0;
+        c->counts = {};
         *out = o;
         return VISFS_BA_OK;
     }
-    PG_HIP(hipSetDevice(pg->dev));
+    HIP_TRY(pg, hipSetDevice(pg->dev));
     const size_t off = pack(pl, nullptr, c->h_up, c->d_up, v);
     const size_t bytes = pack_cov(cp, c->h_up, c->d_up, off, q);
     carve(v, c->d_work);
@@ -202,21 +204,21 @@ int run_cov(visfs_pose_graph* pg, const Plan& pl, const CovPlan& cp, const Prm& 
     q.sol = c->d_arena + kCovSolutionVector * 3 * (int64_t)pl.n;
     const size_t out_bytes = cov_out_doubles(columns, cp.Q) * sizeof(double);
     int32_t launches = 0;
-    PG_HIP(hipMemcpyAsync(c->d_up, c->h_up, bytes, hipMemcpyHostToDevice, pg->stream));
+    HIP_TRY(pg, hipMemcpyAsync(c->d_up, c->h_up, bytes, hipMemcpyHostToDevice, pg->stream));
     hipLaunchKernelGGL(k_pose_graph_cov_setup, dim3(1), dim3(kLanes), 0, pg->stream, v, q, P.precond);
-    PG_HIP(hipGetLastError());
+    HIP_TRY(pg, hipGetLastError());
     ++launches;
     if (columns > 0) {
         hipLaunchKernelGGL(k_pose_graph_cov_solve, dim3((unsigned)columns), dim3(kLanes), 0, pg->stream, v, q, P);
-        PG_HIP(hipGetLastError());
+        HIP_TRY(pg, hipGetLastError());
         ++launches;
     }
     hipLaunchKernelGGL(k_pose_graph_cov_gather, dim3((unsigned)((cp.Q + kGatherLanes - 1) / kGatherLanes)), dim3(kGatherLanes), 0, pg->stream, v, q);
-    PG_HIP(hipGetLastError());
+    HIP_TRY(pg, hipGetLastError());
     ++launches;
-    PG_HIP(hipMemcpyAsync(c->h_out, d_out, out_bytes, hipMemcpyDeviceToHost, pg->stream));
-    PG_HIP(hipStreamSynchronize(pg->stream));
-    c->launches = launches; c->copies = 2; c->waits = 1;
+    HIP_TRY(pg, hipMemcpyAsync(c->h_out, d_out, out_bytes, hipMemcpyDeviceToHost, pg->stream));
+    HIP_TRY(pg, hipStreamSynchronize(pg->stream));
+    c->counts = { launches, 2, 1 };
     *out = reinterpret_cast<const double*>(c->h_out);
     return VISFS_BA_OK;
 }
@@ -244,7 +246,7 @@ int visfs_pose_graph_covariance(visfs_pose_graph* pg, const visfs_pose_graph_cov
                                 const visfs_pose_graph_edge* edges, int32_t Q, const int32_t* queries, double* joint_out, double* relative_out,
                                 visfs_pose_graph_cov_result* result) {
     if (!pg || !p || !poses || !fixed || !edges || !queries || !result) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded([&]() -> int {
+    return guarded(pg, [&]() -> int {
         int rc = check_params(pg, p);
         if (rc != VISFS_BA_OK) return rc;
         Plan pl;
@@ -287,7 +289,7 @@ int visfs_pose_graph_covariance(visfs_pose_graph* pg, const visfs_pose_graph_cov
 
 int visfs_pose_graph_cov_download_columns(visfs_pose_graph* pg, int32_t source, double* columns, int32_t* iterations) {
     if (!pg) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded([&]() -> int {
+    return guarded(pg, [&]() -> int {
         const CovObject* c = pg->cov;
         if (!c || !c->valid) return fail(pg, VISFS_BA_ERR_BAD_ARGUMENT, "no successful covariance call to read from");
         if (source < 0 || source >= c->sources) return fail(pg, VISFS_BA_ERR_BAD_ARGUMENT, "the source is out of range");
@@ -298,10 +300,10 @@ int visfs_pose_graph_cov_download_columns(visfs_pose_graph* pg, int32_t source, 
             if (!columns) continue;
             const double* src = c->sol + (int64_t)col * c->sol_stride;
             if (!pg->device) { std::memcpy(columns + k * m, src, m * sizeof(double)); continue; }
-            PG_HIP(hipSetDevice(pg->dev));
-            PG_HIP(hipMemcpyAsync(columns + k * m, src, m * sizeof(double), hipMemcpyDeviceToHost, pg->stream));
+            HIP_TRY(pg, hipSetDevice(pg->dev));
+            HIP_TRY(pg, hipMemcpyAsync(columns + k * m, src, m * sizeof(double), hipMemcpyDeviceToHost, pg->stream));
         }
-        if (pg->device && columns) PG_HIP(hipStreamSynchronize(pg->stream));
+        if (pg->device && columns) HIP_TRY(pg, hipStreamSynchronize(pg->stream));
         return (int)VISFS_BA_OK;
     });
 }
@@ -309,7 +311,7 @@ int visfs_pose_graph_cov_download_columns(visfs_pose_graph* pg, int32_t source, 
 int visfs_pose_graph_cov_plan(int32_t N, const uint8_t* fixed, int32_t E, const visfs_pose_graph_edge* edges, int32_t Q, const int32_t* queries,
                               int32_t* n_sources, int32_t* sources, int32_t* query_sources) {
     if (!fixed || !edges || !queries || !n_sources || !sources || !query_sources) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded([&]() -> int {
+    return guarded(nullptr, [&]() -> int {
         Plan pl;
         CovPlan cp;
         std::string why;
@@ -325,12 +327,7 @@ int visfs_pose_graph_cov_plan(int32_t N, const uint8_t* fixed, int32_t E, const 
 }
 
 int visfs_pose_graph_cov_last_counts(const visfs_pose_graph* pg, int32_t* launches, int32_t* copies, int32_t* waits) {
-    if (!pg) return VISFS_BA_ERR_BAD_ARGUMENT;
-    const CovObject* c = pg->cov;
-    if (launches) *launches = c ? c->launches : 0;
-    if (copies) *copies = c ? c->copies : 0;
-    if (waits) *waits = c ? c->waits : 0;
-    return VISFS_BA_OK;
+    return pg ? (pg->cov ? pg->cov->counts : Counts{}).read(launches, copies, waits) : (int)VISFS_BA_ERR_BAD_ARGUMENT;
 }
 
 int visfs_pose_graph_cov_search_window(const double relative[9], double sigmas, double* linear, double* angular) {

@@ -3,6 +3,7 @@
 // ba_pose_graph.hip holds the optimisation and its hooks, ba_pose_graph_cov.hip the covariances (DESIGN.md sections 9p and 9q).
 #pragma once
 #pragma clang fp contract(off)
+#include "ba_host.hpp"
 #include "ba_pose_graph.hpp"
 
 #include <hip/hip_runtime.h>
@@ -102,7 +103,8 @@ struct visfs_pose_graph {
     std::vector<char> up;                             // twin
     std::vector<double> work;
     posegraph::View view;                             // of the last run
-    int32_t trials = 0, launches = 0, copies = 0, waits = 0;
+    int32_t trials = 0;
+    host::Counts counts;
     posegraph::CovObject* cov = nullptr;              // made at the first covariance call
 };
 
@@ -161,19 +163,6 @@ inline double* carve(View& v, double* w) {
     v.res = reinterpret_cast<visfs_pose_graph_result*>(take(kResDoubles));
     v.out_poses = take(3 * N); v.out_chi2 = take(E);
     return out;
-}
-
-#define PG_HIP(expr)                                                                               \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) { pg->err = std::string(#expr) + ": " + hipGetErrorString(e_); return (int)VISFS_BA_ERR_DEVICE; } \
-    } while (0)
-
-inline int fail(visfs_pose_graph* pg, int rc, const std::string& why) { pg->err = why; return rc; }
-
-template <class F> inline int guarded(F&& f) noexcept {
-    try { return f(); }
-    catch (...) { return (int)VISFS_BA_ERR_DEVICE; }
 }
 
 }  // namespace posegraph

@@ -10,6 +10,7 @@
 //   k_scan_best   one workgroup reduces the slots under the same total order and writes the result record.
 // The host twin (host sub-maps) runs the same functions of ba_scan.hpp sequentially.
 #include "ba_scan.hpp"
+#include "ba_host.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -20,6 +21,7 @@
 #pragma clang fp contract(off)
 
 using namespace scan;
+using namespace host;
 
 namespace scan {
 
@@ -160,22 +162,6 @@ State* state_of(visfs_submaps* s) {
     return static_cast<State*>(*slot);
 }
 
-#define SC_HIP(s, expr)                                                                                                   \
-    do {                                                                                                                  \
-        hipError_t e_ = (expr);                                                                                           \
-        if (e_ != hipSuccess) return visfs_internal_scan_fail((s), VISFS_BA_ERR_DEVICE, (std::string(#expr) + ": " + hipGetErrorString(e_)).c_str()); \
-    } while (0)
-
-template <class T> int grow(visfs_submaps* s, T** p, size_t* cap, size_t need) {
-    if (*cap >= need) return VISFS_BA_OK;
-    if (*p) SC_HIP(s, hipFree(*p));
-    *p = nullptr; *cap = 0;
-    const size_t n = need + need / 2;
-    SC_HIP(s, hipMalloc(reinterpret_cast<void**>(p), n * sizeof(T)));
-    *cap = n;
-    return VISFS_BA_OK;
-}
-
 // candidates of one tile and point slices of a workgroup: small windows share the workgroup's items among slices of the points
 void tiling(int32_t Lsq, int32_t& tc, int32_t& slices, int32_t& tiles) {
     tc = std::min<int32_t>(Lsq, kThreads);
@@ -187,32 +173,32 @@ int device_match(visfs_submaps* s, State* st, const submap::ScanAccess& acc, Pla
     const size_t npts = 2 * (size_t)P.n, nrot = 2 * (size_t)P.S, nw = P.weight.size();
     const size_t bytes = (npts + nrot + nw) * sizeof(double);
     if (st->up_cap < bytes) {
-        if (st->h_up) SC_HIP(s, hipHostFree(st->h_up));
-        if (st->d_up) SC_HIP(s, hipFree(st->d_up));
+        if (st->h_up) HIP_TRY(s, hipHostFree(st->h_up));
+        if (st->d_up) HIP_TRY(s, hipFree(st->d_up));
         st->h_up = st->d_up = nullptr; st->up_cap = 0; st->have = false;
         const size_t cap = bytes + bytes / 2;
-        SC_HIP(s, hipHostMalloc(reinterpret_cast<void**>(&st->h_up), cap, hipHostMallocDefault));
-        SC_HIP(s, hipMalloc(reinterpret_cast<void**>(&st->d_up), cap));
+        HIP_TRY(s, hipHostMalloc(reinterpret_cast<void**>(&st->h_up), cap, hipHostMallocDefault));
+        HIP_TRY(s, hipMalloc(reinterpret_cast<void**>(&st->d_up), cap));
         st->up_cap = cap;
     }
     if (!st->d_rec) {
-        SC_HIP(s, hipMalloc(reinterpret_cast<void**>(&st->d_rec), sizeof(Record)));
-        SC_HIP(s, hipHostMalloc(reinterpret_cast<void**>(&st->h_rec), sizeof(Record), hipHostMallocDefault));
+        HIP_TRY(s, hipMalloc(reinterpret_cast<void**>(&st->d_rec), sizeof(Record)));
+        HIP_TRY(s, hipHostMalloc(reinterpret_cast<void**>(&st->h_rec), sizeof(Record), hipHostMallocDefault));
     }
     int32_t tc, slices, tiles;
     tiling(P.Lw * P.Lw, tc, slices, tiles);
     const size_t ncand = (size_t)P.candidates(), nslots = (size_t)P.S * tiles;
     int rc;
     if (st->sums_cap < ncand || st->scores_cap < ncand) st->have = false;
-    if ((rc = grow(s, &st->d_sums, &st->sums_cap, ncand)) != VISFS_BA_OK) return rc;
-    if ((rc = grow(s, &st->d_scores, &st->scores_cap, ncand)) != VISFS_BA_OK) return rc;
-    if ((rc = grow(s, &st->d_slots, &st->slot_cap, nslots)) != VISFS_BA_OK) return rc;
+    if ((rc = grow(s, &st->d_sums, &st->sums_cap, ncand, ncand / 2)) != VISFS_BA_OK) return rc;
+    if ((rc = grow(s, &st->d_scores, &st->scores_cap, ncand, ncand / 2)) != VISFS_BA_OK) return rc;
+    if ((rc = grow(s, &st->d_slots, &st->slot_cap, nslots, nslots / 2)) != VISFS_BA_OK) return rc;
     st->have = false;                                                      // the buffers are about to hold this call
     double* h = reinterpret_cast<double*>(st->h_up);
     std::memcpy(h, P.pts.data(), npts * sizeof(double));
     std::memcpy(h + npts, P.rot.data(), nrot * sizeof(double));
     std::memcpy(h + npts + nrot, P.weight.data(), nw * sizeof(double));
-    SC_HIP(s, hipMemcpyAsync(st->d_up, st->h_up, bytes, hipMemcpyHostToDevice, acc.stream));
+    HIP_TRY(s, hipMemcpyAsync(st->d_up, st->h_up, bytes, hipMemcpyHostToDevice, acc.stream));
     const double* d = reinterpret_cast<const double*>(st->d_up);
     ScoreArgs A{};
     A.pts = d; A.rot = d + npts; A.weight = d + npts + nrot;
@@ -222,11 +208,11 @@ int device_match(visfs_submaps* s, State* st, const submap::ScanAccess& acc, Pla
     A.tc = tc; A.slices = slices; A.tiles = tiles;
     A.sums = st->d_sums; A.scores = st->d_scores; A.slots = st->d_slots;
     hipLaunchKernelGGL(k_scan_score, dim3(tiles, P.S), dim3(kThreads), 0, acc.stream, A);
-    SC_HIP(s, hipGetLastError());
+    HIP_TRY(s, hipGetLastError());
     hipLaunchKernelGGL(k_scan_best, dim3(1), dim3(kThreads), 0, acc.stream, st->d_slots, (int32_t)nslots, st->d_sums, st->d_rec);
-    SC_HIP(s, hipGetLastError());
-    SC_HIP(s, hipMemcpyAsync(st->h_rec, st->d_rec, sizeof(Record), hipMemcpyDeviceToHost, acc.stream));
-    SC_HIP(s, hipStreamSynchronize(acc.stream));
+    HIP_TRY(s, hipGetLastError());
+    HIP_TRY(s, hipMemcpyAsync(st->h_rec, st->d_rec, sizeof(Record), hipMemcpyDeviceToHost, acc.stream));
+    HIP_TRY(s, hipStreamSynchronize(acc.stream));
     const Record r = *st->h_rec;
     if (r.index < 0 || (int64_t)r.index >= P.candidates()) return visfs_internal_scan_fail(s, VISFS_BA_ERR_DEVICE, "the reduction returned no candidate");
     fill_result(P, r.index, r.score, r.sum, *out);
@@ -264,12 +250,6 @@ int host_match(State* st, const submap::ScanAccess& acc, Plan& P, visfs_scan_mat
     st->plan = std::move(P);
     st->have = true;
     return VISFS_BA_OK;
-}
-
-template <class F> int guarded(visfs_submaps* s, F&& f) noexcept {
-    try { return f(); }
-    catch (const std::bad_alloc&) { return s ? visfs_internal_scan_fail(s, VISFS_BA_ERR_DEVICE, "out of host memory") : (int)VISFS_BA_ERR_DEVICE; }
-    catch (...) { return s ? visfs_internal_scan_fail(s, VISFS_BA_ERR_DEVICE, "unexpected exception") : (int)VISFS_BA_ERR_DEVICE; }
 }
 
 }  // namespace
@@ -337,16 +317,16 @@ int visfs_scan_match_download(visfs_submaps* s, int64_t cap, int32_t* sums, doub
         submap::ScanAccess acc;
         int rc = visfs_internal_scan_access(s, -1, &acc);                  // the device and the stream
         if (rc != VISFS_BA_OK) return rc;
-        if (sums) SC_HIP(s, hipMemcpyAsync(sums, st->d_sums, (size_t)nc * sizeof(int32_t), hipMemcpyDeviceToHost, acc.stream));
-        if (scores) SC_HIP(s, hipMemcpyAsync(scores, st->d_scores, (size_t)nc * sizeof(double), hipMemcpyDeviceToHost, acc.stream));
+        if (sums) HIP_TRY(s, hipMemcpyAsync(sums, st->d_sums, (size_t)nc * sizeof(int32_t), hipMemcpyDeviceToHost, acc.stream));
+        if (scores) HIP_TRY(s, hipMemcpyAsync(scores, st->d_scores, (size_t)nc * sizeof(double), hipMemcpyDeviceToHost, acc.stream));
         if (cells_xy) {
-            if ((rc = grow(s, &st->d_cells, &st->cells_cap, 2 * (size_t)ncell)) != VISFS_BA_OK) return rc;
+            if ((rc = grow(s, &st->d_cells, &st->cells_cap, 2 * (size_t)ncell, (size_t)ncell)) != VISFS_BA_OK) return rc;
             hipLaunchKernelGGL(k_scan_cells, dim3((unsigned)((ncell + kThreads - 1) / kThreads)), dim3(kThreads), 0, acc.stream, st->d_pts(), st->d_rot(),
                                P.n, ncell, P.gx, P.gy, P.L.res, P.L.max_x, P.L.max_y, st->d_cells);
-            SC_HIP(s, hipGetLastError());
-            SC_HIP(s, hipMemcpyAsync(cells_xy, st->d_cells, 2 * (size_t)ncell * sizeof(int32_t), hipMemcpyDeviceToHost, acc.stream));
+            HIP_TRY(s, hipGetLastError());
+            HIP_TRY(s, hipMemcpyAsync(cells_xy, st->d_cells, 2 * (size_t)ncell * sizeof(int32_t), hipMemcpyDeviceToHost, acc.stream));
         }
-        SC_HIP(s, hipStreamSynchronize(acc.stream));
+        HIP_TRY(s, hipStreamSynchronize(acc.stream));
         return (int)VISFS_BA_OK;
     });
 }

@@ -14,6 +14,7 @@
 // functions declared there, the launch sequence excepted.
 #include "ba_scan_stack.hpp"
 #include "ba_scan_stack_access.hpp"
+#include "ba_host.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -25,6 +26,7 @@
 #pragma clang fp contract(off)
 
 using namespace scanfast;
+using namespace host;
 using scan::Plan;
 using submap::GridView;
 using submap::Limits;
@@ -50,7 +52,6 @@ __global__ __launch_bounds__(kThreads) void k_fast_up(LevelView lo, int32_t w, i
 // ---------------------------------------------------------------- the stack object
 namespace {
 
-int sfail(visfs_scan_stack* st, int rc, const std::string& why) { st->err = why; return rc; }
 
 void stack_free(visfs_scan_stack* st) {
     if (st->device) {
@@ -71,7 +72,7 @@ int stack_layout(visfs_scan_stack* st) {
         st->off[h] = items;
         st->lv.v[h].w = (int32_t)w; st->lv.v[h].ht = (int32_t)ht; st->lv.v[h].e = (int32_t)e;
         items += ((size_t)(w * ht) + 127) & ~size_t(127);                  // every level starts on 256 bytes
-        if ((int64_t)items * 2 > (int64_t)VISFS_SCAN_FAST_MAX_BYTES) return sfail(st, VISFS_BA_ERR_UNSUPPORTED, "the levels together exceed 1 GiB");
+        if ((int64_t)items * 2 > (int64_t)VISFS_SCAN_FAST_MAX_BYTES) return fail(st, VISFS_BA_ERR_UNSUPPORTED, "the levels together exceed 1 GiB");
     }
     st->bytes = (int64_t)items * 2;
     return VISFS_BA_OK;
@@ -97,21 +98,21 @@ int stack_build(visfs_scan_stack* st, const GridView& g) {
         return VISFS_BA_OK;
     }
     int cus = 0;
-    SCAN_HIP(st->err, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, st->dev));
+    HIP_TRY(&st->err, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, st->dev));
     st->blocks = std::max(1, cus) * 8;
-    SCAN_HIP(st->err, hipMalloc(reinterpret_cast<void**>(&st->d_mem), items * 2));
+    HIP_TRY(&st->err, hipMalloc(reinterpret_cast<void**>(&st->d_mem), items * 2));
     for (int32_t h = 0; h < st->depth; ++h) st->lv.v[h].p = st->d_mem + st->off[h];
     const int64_t n0 = (int64_t)st->L.nx * st->L.ny;
-    hipLaunchKernelGGL(k_fast_base, dim3(blocks_for(n0)), dim3(kThreads), 0, st->stream, g, st->L.nx, n0, st->d_mem);
-    SCAN_HIP(st->err, hipGetLastError());
+    hipLaunchKernelGGL(k_fast_base, dim3(blocks_for(n0, kThreads)), dim3(kThreads), 0, st->stream, g, st->L.nx, n0, st->d_mem);
+    HIP_TRY(&st->err, hipGetLastError());
     for (int32_t h = 1; h < st->depth; ++h) {
         const LevelView& hi = st->lv.v[h];
         const int64_t nh = (int64_t)hi.w * hi.ht;
-        hipLaunchKernelGGL(k_fast_up, dim3(blocks_for(nh)), dim3(kThreads), 0, st->stream, st->lv.v[h - 1], hi.w, hi.e, 1 << (h - 1), nh,
+        hipLaunchKernelGGL(k_fast_up, dim3(blocks_for(nh, kThreads)), dim3(kThreads), 0, st->stream, st->lv.v[h - 1], hi.w, hi.e, 1 << (h - 1), nh,
                            st->d_mem + st->off[h]);
-        SCAN_HIP(st->err, hipGetLastError());
+        HIP_TRY(&st->err, hipGetLastError());
     }
-    SCAN_HIP(st->err, hipStreamSynchronize(st->stream));                          // the source grid may change or go from here on
+    HIP_TRY(&st->err, hipStreamSynchronize(st->stream));                          // the source grid may change or go from here on
     return VISFS_BA_OK;
 }
 
@@ -277,10 +278,10 @@ int match_download(bool device, int dev, hipStream_t stream, const CallBlock& b,
         if (survivors) std::memcpy(survivors, l.surv.data(), (size_t)l.survivors * sizeof(int2));
         return VISFS_BA_OK;
     }
-    SCAN_HIP(why, hipSetDevice(dev));
-    if (bounds) SCAN_HIP(why, hipMemcpyAsync(bounds, b.bnd[1].p + member * b.top, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-    if (survivors) SCAN_HIP(why, hipMemcpyAsync(survivors, b.fr[2].p + member * b.cap, (size_t)l.survivors * sizeof(int2), hipMemcpyDeviceToHost, stream));
-    SCAN_HIP(why, hipStreamSynchronize(stream));
+    HIP_TRY(&why, hipSetDevice(dev));
+    if (bounds) HIP_TRY(&why, hipMemcpyAsync(bounds, b.bnd[1].p + member * b.top, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    if (survivors) HIP_TRY(&why, hipMemcpyAsync(survivors, b.fr[2].p + member * b.cap, (size_t)l.survivors * sizeof(int2), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(&why, hipStreamSynchronize(stream));
     if (survivors) {                                                       // the device appends unordered
         int2* sv = reinterpret_cast<int2*>(survivors);
         std::sort(sv, sv + l.survivors, [](const int2& u, const int2& v) { return u.x < v.x; });
@@ -296,7 +297,7 @@ int host_match(visfs_scan_stack* st, Search& s, const visfs_scan_stack_params& p
     Last now;
     std::string why;
     const int rc = host_search(st->lv, s, now, why);
-    if (rc != VISFS_BA_OK) return sfail(st, rc, why);
+    if (rc != VISFS_BA_OK) return fail(st, rc, why);
     finish(s, p, now.c.best_index, now.c.best_sum, out);
     st->last = std::move(now);
     return VISFS_BA_OK;
@@ -322,7 +323,7 @@ void visfs_scan_stack_default_params(visfs_scan_stack_params* p) {
 int visfs_scan_stack_create(visfs_submaps* s, int32_t index, int32_t depth, visfs_scan_stack** out) {
     if (!s || !out) return VISFS_BA_ERR_BAD_ARGUMENT;
     *out = nullptr;
-    return guarded([&]() -> int {
+    return guarded(s, [&]() -> int {
         if (!check_depth(depth)) return visfs_internal_scan_fail(s, VISFS_BA_ERR_BAD_ARGUMENT, "the depth must lie in [1, 16]");
         submap::ScanAccess acc;
         int rc = visfs_internal_scan_access(s, index, &acc);
@@ -341,7 +342,7 @@ int visfs_scan_stack_create(visfs_submaps* s, int32_t index, int32_t depth, visf
 int visfs_scan_stack_create_from_grid(visfs_ba_handle* h, const visfs_submap_info* lim, const uint16_t* cells, int32_t depth, visfs_scan_stack** out) {
     if (!lim || !cells || !out) return VISFS_BA_ERR_BAD_ARGUMENT;
     *out = nullptr;
-    return guarded([&]() -> int {
+    return guarded(nullptr, [&]() -> int {
         auto bad = [&](int rc, const char* why) { if (h) visfs_internal_set_error(h, why); return rc; };
         if (!check_depth(depth)) return bad(VISFS_BA_ERR_BAD_ARGUMENT, "the depth must lie in [1, 16]");
         if (!(lim->resolution > 0.0) || !std::isfinite(lim->resolution) || !std::isfinite(lim->max_x) || !std::isfinite(lim->max_y) ||
@@ -360,9 +361,9 @@ int visfs_scan_stack_create_from_grid(visfs_ba_handle* h, const visfs_submap_inf
             uint16_t* tmp = nullptr;
             auto run = [&]() -> int {
                 const size_t nb = (size_t)g.nx * g.ny * 2;
-                SCAN_HIP(st->err, hipSetDevice(st->dev));
-                SCAN_HIP(st->err, hipMalloc(reinterpret_cast<void**>(&tmp), nb));
-                SCAN_HIP(st->err, hipMemcpyAsync(tmp, cells, nb, hipMemcpyHostToDevice, st->stream));
+                HIP_TRY(&st->err, hipSetDevice(st->dev));
+                HIP_TRY(&st->err, hipMalloc(reinterpret_cast<void**>(&tmp), nb));
+                HIP_TRY(&st->err, hipMemcpyAsync(tmp, cells, nb, hipMemcpyHostToDevice, st->stream));
                 g.cells = tmp;
                 return stack_build(st, g);                                 // ends with a wait on the stream
             };
@@ -390,21 +391,21 @@ int visfs_scan_stack_describe(const visfs_scan_stack* st, visfs_scan_stack_info*
 int visfs_scan_stack_match(visfs_scan_stack* st, const visfs_scan_stack_params* p, const double g[3], int32_t n, const double* xyz,
                            visfs_scan_stack_result* out) {
     if (!st || !p || !g || !out || n < 0 || (n > 0 && !xyz)) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded([&]() -> int {
+    return guarded(st, [&]() -> int {
         const char* why = "";
         int rc = check_call(*p, g, n, xyz, &why);
-        if (rc != VISFS_BA_OK) return sfail(st, rc, why);
+        if (rc != VISFS_BA_OK) return fail(st, rc, why);
         if (n == 0) { no_points(g, out); return (int)VISFS_BA_OK; }        // nothing to match: the guess back
         Search s;
         rc = make_search(st, *p, g, n, xyz, s, &why);
-        if (rc != VISFS_BA_OK) return sfail(st, rc, why);
+        if (rc != VISFS_BA_OK) return fail(st, rc, why);
         if (!st->device) return host_match(st, s, *p, out);
         int cur = 0;
         rc = device_run(st->blk, st->dev, st->stream, st->blocks, 1, &st, &s, &cur, st->err);
         if (rc != VISFS_BA_OK) return rc;
         const Ctrl& c = st->blk.h_ctrl[0];
-        if (c.overflow) return sfail(st, VISFS_BA_ERR_UNSUPPORTED, overflow_text(c.overflow - 1, s.cap));
-        if (c.best_index < 0 || (int64_t)c.best_index >= s.P.candidates()) return sfail(st, VISFS_BA_ERR_DEVICE, "the search returned no candidate");
+        if (c.overflow) return fail(st, VISFS_BA_ERR_UNSUPPORTED, overflow_text(c.overflow - 1, s.cap));
+        if (c.best_index < 0 || (int64_t)c.best_index >= s.P.candidates()) return fail(st, VISFS_BA_ERR_DEVICE, "the search returned no candidate");
         st->blk.hand_over(cur, s);                                         // only now: a failed call leaves the hook's arenas and `last`
         finish(s, *p, c.best_index, c.best_sum, out);
         st->last = device_last(s, c);
@@ -414,17 +415,17 @@ int visfs_scan_stack_match(visfs_scan_stack* st, const visfs_scan_stack_params* 
 
 int visfs_scan_stack_download_level(visfs_scan_stack* st, int32_t h, int64_t cap, uint16_t* out, int32_t dims[4]) {
     if (!st || !dims || cap < 0) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded([&]() -> int {
-        if (h < 0 || h >= st->depth) return sfail(st, VISFS_BA_ERR_BAD_ARGUMENT, "the stack has no such level");
+    return guarded(st, [&]() -> int {
+        if (h < 0 || h >= st->depth) return fail(st, VISFS_BA_ERR_BAD_ARGUMENT, "the stack has no such level");
         const LevelView& v = st->lv.v[h];
         dims[0] = v.w; dims[1] = v.ht; dims[2] = v.e; dims[3] = 0;
         if (!out) return (int)VISFS_BA_OK;
         const int64_t items = (int64_t)v.w * v.ht;
-        if (cap < items) return sfail(st, VISFS_BA_ERR_BAD_ARGUMENT, "the hook's array is too small");
+        if (cap < items) return fail(st, VISFS_BA_ERR_BAD_ARGUMENT, "the hook's array is too small");
         if (!st->device) { std::memcpy(out, v.p, (size_t)items * 2); return (int)VISFS_BA_OK; }
-        SCAN_HIP(st->err, hipSetDevice(st->dev));
-        SCAN_HIP(st->err, hipMemcpyAsync(out, v.p, (size_t)items * 2, hipMemcpyDeviceToHost, st->stream));
-        SCAN_HIP(st->err, hipStreamSynchronize(st->stream));
+        HIP_TRY(&st->err, hipSetDevice(st->dev));
+        HIP_TRY(&st->err, hipMemcpyAsync(out, v.p, (size_t)items * 2, hipMemcpyDeviceToHost, st->stream));
+        HIP_TRY(&st->err, hipStreamSynchronize(st->stream));
         return (int)VISFS_BA_OK;
     });
 }
@@ -432,7 +433,7 @@ int visfs_scan_stack_download_level(visfs_scan_stack* st, int32_t h, int64_t cap
 int visfs_scan_stack_match_download(visfs_scan_stack* st, int32_t header[8], int32_t scored[16], int32_t kept[16], int64_t bounds_cap,
                                     int32_t* bounds, int64_t survivors_cap, int32_t* survivors) {
     if (!st || !header || bounds_cap < 0 || survivors_cap < 0) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded([&]() -> int {
+    return guarded(st, [&]() -> int {
         return match_download(st->device, st->dev, st->stream, st->blk, 0, st->last, st->err, header, scored, kept, bounds_cap, bounds, survivors_cap,
                               survivors);
     });
@@ -444,12 +445,12 @@ int visfs_scan_stack_match_download(visfs_scan_stack* st, int32_t header[8], int
 int visfs_internal_stack_from_view(bool device, int dev, hipStream_t stream, const Limits& L, const GridView& g, int32_t depth,
                                    visfs_scan_stack** out, std::string* err) {
     *out = nullptr;
-    return guarded([&]() -> int {
+    return guarded(nullptr, [&]() -> int {
         visfs_scan_stack* st = new visfs_scan_stack();
         st->device = device; st->dev = dev; st->stream = stream;
         st->L = L; st->depth = depth;
         auto run = [&]() -> int {
-            if (device) SCAN_HIP(st->err, hipSetDevice(dev));
+            if (device) HIP_TRY(&st->err, hipSetDevice(dev));
             return stack_build(st, g);
         };
         const int rc = run();

@@ -12,6 +12,7 @@
 // wait.  The one-core twin walks the same definition (ba_scan_filter.hpp) in index order.
 #include "ba_scan_filter.hpp"
 #include "ba_submap.hpp"
+#include "ba_host.hpp"
 
 #include <cstring>
 #include <new>
@@ -21,6 +22,7 @@
 #pragma clang fp contract(off)
 
 using namespace sfilt;
+using namespace host;
 
 namespace sfilt {
 
@@ -375,24 +377,12 @@ struct visfs_scan_filter {
     uint8_t* d_out = nullptr;
     uint8_t* d_work = nullptr;
     size_t in_cap = 0, out_cap = 0, work_cap = 0;
-    int32_t launches = 0, copies = 0, waits = 0;
+    host::Counts counts;
     const uint8_t* out() const { return device ? h_out : h_out_v.data(); }
 };
 
 namespace {
 
-int ffail(visfs_scan_filter* f, int rc, const std::string& why) { f->err = why; return rc; }
-
-#define SF_HIP(f, expr)                                                                                               \
-    do {                                                                                                              \
-        hipError_t e_ = (expr);                                                                                       \
-        if (e_ != hipSuccess) return ffail((f), VISFS_BA_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-template <class F> int guarded(F&& f) noexcept {
-    try { return f(); }
-    catch (...) { return (int)VISFS_BA_ERR_DEVICE; }
-}
 
 void filter_free(visfs_scan_filter* f) {
     if (f->device) {
@@ -411,28 +401,28 @@ size_t pad8(size_t v) { return (v + 7) & ~(size_t)7; }
 
 // Room for the call's three blocks; growing a block drops the results that lay in it.
 int device_room(visfs_scan_filter* f, size_t in_bytes, size_t out_bytes, size_t work_bytes) {
-    SF_HIP(f, hipSetDevice(f->dev));
+    HIP_TRY(f, hipSetDevice(f->dev));
     if (f->in_cap < in_bytes) {
-        if (f->h_in) SF_HIP(f, hipHostFree(f->h_in));
-        if (f->d_in) SF_HIP(f, hipFree(f->d_in));
+        if (f->h_in) HIP_TRY(f, hipHostFree(f->h_in));
+        if (f->d_in) HIP_TRY(f, hipFree(f->d_in));
         f->h_in = nullptr; f->d_in = nullptr; f->in_cap = 0;
-        SF_HIP(f, hipHostMalloc(reinterpret_cast<void**>(&f->h_in), in_bytes, hipHostMallocDefault));
-        SF_HIP(f, hipMalloc(reinterpret_cast<void**>(&f->d_in), in_bytes));
+        HIP_TRY(f, hipHostMalloc(reinterpret_cast<void**>(&f->h_in), in_bytes, hipHostMallocDefault));
+        HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&f->d_in), in_bytes));
         f->in_cap = in_bytes;
     }
     if (f->out_cap < out_bytes) {
         f->m = 0;
-        if (f->h_out) SF_HIP(f, hipHostFree(f->h_out));
-        if (f->d_out) SF_HIP(f, hipFree(f->d_out));
+        if (f->h_out) HIP_TRY(f, hipHostFree(f->h_out));
+        if (f->d_out) HIP_TRY(f, hipFree(f->d_out));
         f->h_out = nullptr; f->d_out = nullptr; f->out_cap = 0;
-        SF_HIP(f, hipHostMalloc(reinterpret_cast<void**>(&f->h_out), out_bytes, hipHostMallocDefault));
-        SF_HIP(f, hipMalloc(reinterpret_cast<void**>(&f->d_out), out_bytes));
+        HIP_TRY(f, hipHostMalloc(reinterpret_cast<void**>(&f->h_out), out_bytes, hipHostMallocDefault));
+        HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&f->d_out), out_bytes));
         f->out_cap = out_bytes;
     }
     if (f->work_cap < work_bytes) {
-        if (f->d_work) SF_HIP(f, hipFree(f->d_work));
+        if (f->d_work) HIP_TRY(f, hipFree(f->d_work));
         f->d_work = nullptr; f->work_cap = 0;
-        SF_HIP(f, hipMalloc(reinterpret_cast<void**>(&f->d_work), work_bytes));
+        HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&f->d_work), work_bytes));
         f->work_cap = work_bytes;
     }
     return VISFS_BA_OK;
@@ -475,7 +465,7 @@ void visfs_scan_filter_default_params(visfs_scan_filter_params* p) {
 int visfs_scan_filter_create(visfs_ba_handle* h, visfs_scan_filter** out) {
     if (!out) return VISFS_BA_ERR_BAD_ARGUMENT;
     *out = nullptr;
-    return guarded([&]() -> int {
+    return guarded(nullptr, [&]() -> int {
         visfs_scan_filter* f = new visfs_scan_filter();
         if (h) { f->device = true; f->dev = visfs_internal_device(h); f->stream = visfs_internal_stream(h); }
         *out = f;
@@ -490,22 +480,22 @@ const char* visfs_scan_filter_last_error(const visfs_scan_filter* f) { return f 
 int visfs_scan_filter_process(visfs_scan_filter* f, const visfs_scan_filter_params* p, int32_t m, const visfs_scan_filter_scan* scans,
                               visfs_scan_filter_record* records) {
     if (!f || !p || m < 0 || (m > 0 && !scans)) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded([&]() -> int {
+    return guarded(f, [&]() -> int {
         // ---- every refusal, before anything is touched
-        if (p->pretreat.num_subdivisions < 1) return ffail(f, VISFS_BA_ERR_BAD_ARGUMENT, "num_subdivisions must be at least 1");
+        if (p->pretreat.num_subdivisions < 1) return fail(f, VISFS_BA_ERR_BAD_ARGUMENT, "num_subdivisions must be at least 1");
         if (!(p->voxel_size >= 0.0) || !(p->adaptive_max_length >= 0.0) || !(p->adaptive_max_range >= 0.0) || !std::isfinite(p->voxel_size) ||
             !std::isfinite(p->adaptive_max_length) || !std::isfinite(p->adaptive_max_range))
-            return ffail(f, VISFS_BA_ERR_BAD_ARGUMENT, "voxel_size, adaptive_max_length and adaptive_max_range must be finite and not negative");
-        if (p->adaptive_min_num_points < 0) return ffail(f, VISFS_BA_ERR_BAD_ARGUMENT, "adaptive_min_num_points must not be negative");
-        if (m > VISFS_SCAN_FILTER_MAX_SCANS) return ffail(f, VISFS_BA_ERR_UNSUPPORTED, "more than 64 scans");
-        if (p->pretreat.num_subdivisions > VISFS_SCAN_FILTER_MAX_SUBDIVISIONS) return ffail(f, VISFS_BA_ERR_UNSUPPORTED, "more than 16 subdivisions");
+            return fail(f, VISFS_BA_ERR_BAD_ARGUMENT, "voxel_size, adaptive_max_length and adaptive_max_range must be finite and not negative");
+        if (p->adaptive_min_num_points < 0) return fail(f, VISFS_BA_ERR_BAD_ARGUMENT, "adaptive_min_num_points must not be negative");
+        if (m > VISFS_SCAN_FILTER_MAX_SCANS) return fail(f, VISFS_BA_ERR_UNSUPPORTED, "more than 64 scans");
+        if (p->pretreat.num_subdivisions > VISFS_SCAN_FILTER_MAX_SUBDIVISIONS) return fail(f, VISFS_BA_ERR_UNSUPPORTED, "more than 16 subdivisions");
         for (int32_t b = 0; b < m; ++b) {
-            if (scans[b].n < 0 || (scans[b].n > 0 && !scans[b].points_xyz)) return ffail(f, VISFS_BA_ERR_BAD_ARGUMENT, "a scan without points");
-            if (scans[b].n > VISFS_SCAN_FILTER_MAX_POINTS) return ffail(f, VISFS_BA_ERR_UNSUPPORTED, "a scan of more than 16384 points");
+            if (scans[b].n < 0 || (scans[b].n > 0 && !scans[b].points_xyz)) return fail(f, VISFS_BA_ERR_BAD_ARGUMENT, "a scan without points");
+            if (scans[b].n > VISFS_SCAN_FILTER_MAX_POINTS) return fail(f, VISFS_BA_ERR_UNSUPPORTED, "a scan of more than 16384 points");
         }
         for (int32_t b = 0; b < m; ++b)
             if (!finite_n(scans[b].T_laser_to_camera, 12) || !finite_n(scans[b].origin, 3) || !finite_n(scans[b].points_xyz, 3 * (size_t)scans[b].n))
-                return ffail(f, VISFS_BA_ERR_BAD_ARGUMENT, "a point, transform or origin is not finite");
+                return fail(f, VISFS_BA_ERR_BAD_ARGUMENT, "a point, transform or origin is not finite");
 
         // ---- the layout of the three blocks
         std::vector<ScanHdr> hdr((size_t)m);
@@ -539,18 +529,18 @@ int visfs_scan_filter_process(visfs_scan_filter* f, const visfs_scan_filter_para
             in = f->h_in_v.data(); out = f->h_out_v.data();
         }
         f->m = 0;                                                               // the last results are being overwritten from here on
-        f->launches = f->copies = f->waits = 0;
+        f->counts = {};
         if (m > 0) {
             std::memcpy(in, hdr.data(), (size_t)m * sizeof(ScanHdr));
             for (int32_t b = 0; b < m; ++b)
                 if (hdr[(size_t)b].n) std::memcpy(in + hdr[(size_t)b].in_pts, scans[b].points_xyz, 24 * (size_t)hdr[(size_t)b].n);
             if (f->device) {
-                SF_HIP(f, hipMemcpyAsync(f->d_in, in, in_bytes, hipMemcpyHostToDevice, f->stream));
+                HIP_TRY(f, hipMemcpyAsync(f->d_in, in, in_bytes, hipMemcpyHostToDevice, f->stream));
                 hipLaunchKernelGGL(k_scan_filter, dim3((unsigned)m), dim3(kThreads), 0, f->stream, f->d_in, f->d_out, f->d_work, K);
-                SF_HIP(f, hipGetLastError());
-                SF_HIP(f, hipMemcpyAsync(out, f->d_out, out_bytes, hipMemcpyDeviceToHost, f->stream));
-                SF_HIP(f, hipStreamSynchronize(f->stream));
-                f->launches = 1; f->copies = 2; f->waits = 1;
+                HIP_TRY(f, hipGetLastError());
+                HIP_TRY(f, hipMemcpyAsync(out, f->d_out, out_bytes, hipMemcpyDeviceToHost, f->stream));
+                HIP_TRY(f, hipStreamSynchronize(f->stream));
+                f->counts = { 1, 2, 1 };
             } else {
                 for (int32_t b = 0; b < m; ++b) host_scan(in, out, b, K);
             }
@@ -652,11 +642,7 @@ int visfs_scan_filter_hook_slot(const int32_t voxel[3], int32_t list, int32_t co
 }
 
 int visfs_scan_filter_last_counts(const visfs_scan_filter* f, int32_t* launches, int32_t* copies, int32_t* waits) {
-    if (!f) return VISFS_BA_ERR_BAD_ARGUMENT;
-    if (launches) *launches = f->launches;
-    if (copies) *copies = f->copies;
-    if (waits) *waits = f->waits;
-    return VISFS_BA_OK;
+    return f ? f->counts.read(launches, copies, waits) : (int)VISFS_BA_ERR_BAD_ARGUMENT;
 }
 
 }  // extern "C"

@@ -28,6 +28,7 @@
 // appended to the upload, k_scan_refine (ba_scan_refine.hip) launched after k_group_best with the member as blockIdx.x, reading each
 // member's winner from its Ctrl, and the refinement records behind the Ctrl records in the one download.
 #include "ba_scan_refine.hpp"
+#include "ba_host.hpp"
 #include "../../include/visfs_scan_group.h"
 
 #include <algorithm>
@@ -38,6 +39,7 @@
 #pragma clang fp contract(off)
 
 using namespace scanfast;
+using namespace host;
 using scan::Plan;
 
 namespace scanfast {
@@ -114,7 +116,6 @@ namespace {
 
 thread_local std::string t_create_err;
 
-int gfail(visfs_scan_group* g, int rc, const std::string& why) { g->err = why; return rc; }
 
 void group_free(visfs_scan_group* g) {
     if (g->device) {
@@ -150,29 +151,29 @@ int scanfast::device_run(CallBlock& b, int dev, hipStream_t stream, int32_t bloc
     const Search& s0 = ss[0];
     const int32_t n = s0.P.n, S = s0.P.S, nl = s0.P.nl, L = s0.P.Lw, H = s0.H, mH = s0.mH, total = s0.top(), cap = s0.cap;
     const int64_t ncell = (int64_t)S * n;
-    b.launches = b.copies = b.syncs = 0;
-    SCAN_HIP(why, hipSetDevice(dev));
+    b.counts = {};
+    HIP_TRY(&why, hipSetDevice(dev));
     const size_t npts = 2 * (size_t)n, nrot = 2 * (size_t)S * m;
     const size_t match_bytes = (npts + nrot) * sizeof(double) + (size_t)m * sizeof(Member);
     const size_t bytes = match_bytes + (rp ? (size_t)m * sizeof(scanrefine::Job) : 0);
     if (b.up_cap < bytes) {
-        if (b.h_up) SCAN_HIP(why, hipHostFree(b.h_up));
-        if (b.d_up) SCAN_HIP(why, hipFree(b.d_up));
+        if (b.h_up) HIP_TRY(&why, hipHostFree(b.h_up));
+        if (b.d_up) HIP_TRY(&why, hipFree(b.d_up));
         b.h_up = b.d_up = nullptr; b.up_cap = 0;
         const size_t want = bytes + bytes / 2;
-        SCAN_HIP(why, hipHostMalloc(reinterpret_cast<void**>(&b.h_up), want, hipHostMallocDefault));
-        SCAN_HIP(why, hipMalloc(reinterpret_cast<void**>(&b.d_up), want));
+        HIP_TRY(&why, hipHostMalloc(reinterpret_cast<void**>(&b.h_up), want, hipHostMallocDefault));
+        HIP_TRY(&why, hipMalloc(reinterpret_cast<void**>(&b.d_up), want));
         b.up_cap = want;
     }
     if (!b.d_ctrl) {
-        SCAN_HIP(why, hipMalloc(reinterpret_cast<void**>(&b.d_ctrl), ctrl_bytes(m) + record_bytes(m)));
-        SCAN_HIP(why, hipHostMalloc(reinterpret_cast<void**>(&b.h_ctrl), ctrl_bytes(m) + record_bytes(m), hipHostMallocDefault));
+        HIP_TRY(&why, hipMalloc(reinterpret_cast<void**>(&b.d_ctrl), ctrl_bytes(m) + record_bytes(m)));
+        HIP_TRY(&why, hipHostMalloc(reinterpret_cast<void**>(&b.h_ctrl), ctrl_bytes(m) + record_bytes(m), hipHostMallocDefault));
     }
     int rc;
-    if ((rc = grow(why, &b.d_cells, &b.cells_cap, (size_t)m * (size_t)ncell)) != VISFS_BA_OK) return rc;
-    if ((rc = grow(why, &b.bnd[0].p, &b.bnd[0].cap, (size_t)m * (size_t)total)) != VISFS_BA_OK) return rc;
+    if ((rc = grow(&why, &b.d_cells, &b.cells_cap, (size_t)m * (size_t)ncell)) != VISFS_BA_OK) return rc;
+    if ((rc = grow(&why, &b.bnd[0].p, &b.bnd[0].cap, (size_t)m * (size_t)total)) != VISFS_BA_OK) return rc;
     for (int f = 0; f < 2; ++f)
-        if ((rc = grow(why, &b.fr[f].p, &b.fr[f].cap, (size_t)m * (size_t)cap)) != VISFS_BA_OK) return rc;
+        if ((rc = grow(&why, &b.fr[f].p, &b.fr[f].cap, (size_t)m * (size_t)cap)) != VISFS_BA_OK) return rc;
     double* hup = reinterpret_cast<double*>(b.h_up);
     std::memcpy(hup, s0.P.pts.data(), npts * sizeof(double));
     Member* hmt = reinterpret_cast<Member*>(hup + npts + nrot);                // doubles in front of it: aligned to 8
@@ -190,37 +191,37 @@ int scanfast::device_run(CallBlock& b, int dev, hipStream_t stream, int32_t bloc
             std::memcpy(b.h_up + match_bytes + (size_t)i * sizeof J, &J, sizeof J);
         }
     }
-    SCAN_HIP(why, hipMemcpyAsync(b.d_up, b.h_up, bytes, hipMemcpyHostToDevice, stream));
-    ++b.copies;
+    HIP_TRY(&why, hipMemcpyAsync(b.d_up, b.h_up, bytes, hipMemcpyHostToDevice, stream));
+    ++b.counts.copies;
     const double* d = reinterpret_cast<const double*>(b.d_up);
     const double* drot = d + npts;
     const Member* dmt = reinterpret_cast<const Member*>(drot + nrot);
     const dim3 fixed((unsigned)std::max(1, blocks / m), (unsigned)m), wg(kThreads);
-    hipLaunchKernelGGL(k_group_cells, dim3(blocks_for(ncell), (unsigned)m), wg, 0, stream, d, drot, dmt, n, S, ncell, b.d_cells, b.d_ctrl);
-    SCAN_HIP(why, hipGetLastError()); ++b.launches;
+    hipLaunchKernelGGL(k_group_cells, dim3(blocks_for(ncell, kThreads), (unsigned)m), wg, 0, stream, d, drot, dmt, n, S, ncell, b.d_cells, b.d_ctrl);
+    HIP_TRY(&why, hipGetLastError()); ++b.counts.launches;
     hipLaunchKernelGGL(k_group_bounds, fixed, wg, 0, stream, b.d_cells, ncell, n, dmt, nl, H, mH, total, b.bnd[0].p);
-    SCAN_HIP(why, hipGetLastError()); ++b.launches;
+    HIP_TRY(&why, hipGetLastError()); ++b.counts.launches;
     hipLaunchKernelGGL(k_group_seeds, dim3((unsigned)S, (unsigned)m), wg, 0, stream, b.bnd[0].p, total, b.d_cells, ncell, n, dmt, nl, L, H, mH, b.d_ctrl);
-    SCAN_HIP(why, hipGetLastError()); ++b.launches;
+    HIP_TRY(&why, hipGetLastError()); ++b.counts.launches;
     int cur = 0;                                                           // the frontiers of the level in work: fr[cur]
     hipLaunchKernelGGL(k_group_keep, fixed, wg, 0, stream, b.bnd[0].p, total, H, b.fr[cur].p, cap, b.d_ctrl);
-    SCAN_HIP(why, hipGetLastError()); ++b.launches;
+    HIP_TRY(&why, hipGetLastError()); ++b.counts.launches;
     for (int32_t h = H; h >= 1; --h) {
         hipLaunchKernelGGL(k_group_level, fixed, wg, 0, stream, h, b.fr[cur].p, b.fr[1 - cur].p, cap, b.d_cells, ncell, n, dmt, nl, L, b.d_ctrl);
-        SCAN_HIP(why, hipGetLastError()); ++b.launches;
+        HIP_TRY(&why, hipGetLastError()); ++b.counts.launches;
         cur = 1 - cur;
     }
     hipLaunchKernelGGL(k_group_best, dim3(1, (unsigned)m), wg, 0, stream, b.fr[cur].p, cap, b.d_ctrl);
-    SCAN_HIP(why, hipGetLastError()); ++b.launches;
+    HIP_TRY(&why, hipGetLastError()); ++b.counts.launches;
     if (rp) {
-        SCAN_HIP(why, (hipError_t)scanrefine::launch_refine(stream, m, reinterpret_cast<const scanrefine::Job*>(b.d_up + match_bytes), *rp, d,
+        HIP_TRY(&why, (hipError_t)scanrefine::launch_refine(stream, m, reinterpret_cast<const scanrefine::Job*>(b.d_up + match_bytes), *rp, d,
                                                             records_of(b.d_ctrl, m), rtrace));
-        ++b.launches;
+        ++b.counts.launches;
     }
-    SCAN_HIP(why, hipMemcpyAsync(b.h_ctrl, b.d_ctrl, ctrl_bytes(m) + (rp ? record_bytes(m) : 0), hipMemcpyDeviceToHost, stream));
-    ++b.copies;
-    SCAN_HIP(why, hipStreamSynchronize(stream));
-    ++b.syncs;
+    HIP_TRY(&why, hipMemcpyAsync(b.h_ctrl, b.d_ctrl, ctrl_bytes(m) + (rp ? record_bytes(m) : 0), hipMemcpyDeviceToHost, stream));
+    ++b.counts.copies;
+    HIP_TRY(&why, hipStreamSynchronize(stream));
+    ++b.counts.waits;
     *cur_out = cur;
     return VISFS_BA_OK;
 }
@@ -235,14 +236,14 @@ int group_match(visfs_scan_group* g, const visfs_scan_stack_params& p, const dou
     const char* why = "";
     int rc;
     for (int32_t i = 0; i < m; ++i)
-        if ((rc = check_call(p, guesses + 3 * i, n, xyz, &why)) != VISFS_BA_OK) return gfail(g, rc, member_text(i, why));
+        if ((rc = check_call(p, guesses + 3 * i, n, xyz, &why)) != VISFS_BA_OK) return fail(g, rc, member_text(i, why));
     if (rp)
         for (int32_t i = 0; i < m; ++i)
-            if ((rc = scanrefine::check_call(*rp, guesses + 3 * i, guesses + 3 * i, n, xyz, &why)) != VISFS_BA_OK) return gfail(g, rc, member_text(i, why));
+            if ((rc = scanrefine::check_call(*rp, guesses + 3 * i, guesses + 3 * i, n, xyz, &why)) != VISFS_BA_OK) return fail(g, rc, member_text(i, why));
     if ((int64_t)m * p.frontier_capacity > (int64_t)VISFS_SCAN_GROUP_MAX_FRONTIER)
-        return gfail(g, VISFS_BA_ERR_UNSUPPORTED, "members times frontier_capacity exceed 2^26");
+        return fail(g, VISFS_BA_ERR_UNSUPPORTED, "members times frontier_capacity exceed 2^26");
     if (n == 0) {                                                          // nothing to match: every guess back
-        g->blk.launches = g->blk.copies = g->blk.syncs = 0;
+        g->blk.counts = {};
         for (int32_t i = 0; i < m; ++i) { no_points(guesses + 3 * i, results + i); status[i] = VISFS_BA_OK; }
         if (rp) {
             for (int32_t i = 0; i < m; ++i) scanrefine::not_refined(VISFS_BA_OK, guesses[3 * i], guesses[3 * i + 1], guesses[3 * i + 2], refined + i);
@@ -254,12 +255,12 @@ int group_match(visfs_scan_group* g, const visfs_scan_stack_params& p, const dou
     }
     std::vector<Search> ss((size_t)m);
     for (int32_t i = 0; i < m; ++i) {
-        if ((rc = make_search(g->mem[i], p, guesses + 3 * i, n, xyz, ss[i], &why)) != VISFS_BA_OK) return gfail(g, rc, member_text(i, why));
+        if ((rc = make_search(g->mem[i], p, guesses + 3 * i, n, xyz, ss[i], &why)) != VISFS_BA_OK) return fail(g, rc, member_text(i, why));
         // equal resolution and depth: one S, nl, H and m_H for all, which the launches rely on
         if (ss[i].P.S != ss[0].P.S || ss[i].P.nl != ss[0].P.nl || ss[i].H != ss[0].H || ss[i].mH != ss[0].mH)
-            return gfail(g, VISFS_BA_ERR_DEVICE, member_text(i, "its search differs in shape from member 0's"));
+            return fail(g, VISFS_BA_ERR_DEVICE, member_text(i, "its search differs in shape from member 0's"));
     }
-    g->blk.launches = g->blk.copies = g->blk.syncs = 0;
+    g->blk.counts = {};
     std::vector<Last> now((size_t)m);
     std::string first_overflow;
     int cur = 0;
@@ -267,9 +268,9 @@ int group_match(visfs_scan_group* g, const visfs_scan_stack_params& p, const dou
     if (rp) RP = scanrefine::make_prm(*rp, n);
     if (g->device) {
         if (rp) {
-            SCAN_HIP(g->err, hipSetDevice(g->dev));
+            HIP_TRY(&g->err, hipSetDevice(g->dev));
             for (double*& t : g->d_rtrace)
-                if (!t) SCAN_HIP(g->err, hipMalloc(reinterpret_cast<void**>(&t), (size_t)m * scanrefine::kMaxTrials * scanrefine::kTraceItems * sizeof(double)));
+                if (!t) HIP_TRY(&g->err, hipMalloc(reinterpret_cast<void**>(&t), (size_t)m * scanrefine::kMaxTrials * scanrefine::kTraceItems * sizeof(double)));
         }
         if ((rc = device_run(g->blk, g->dev, g->stream, g->blocks, m, g->mem.data(), ss.data(), &cur, g->err, rp ? &RP : nullptr, p.min_score,
                              g->d_rtrace[0])) != VISFS_BA_OK)
@@ -281,7 +282,7 @@ int group_match(visfs_scan_group* g, const visfs_scan_stack_params& p, const dou
                 if (first_overflow.empty()) first_overflow = member_text(i, overflow_text(c.overflow - 1, s.cap));
                 continue;
             }
-            if (c.best_index < 0 || (int64_t)c.best_index >= s.P.candidates()) return gfail(g, VISFS_BA_ERR_DEVICE, member_text(i, "the search returned no candidate"));
+            if (c.best_index < 0 || (int64_t)c.best_index >= s.P.candidates()) return fail(g, VISFS_BA_ERR_DEVICE, member_text(i, "the search returned no candidate"));
             now[i] = device_last(s, c);
         }
         g->blk.hand_over(cur, ss[0]);                                      // after any call that ran to its end
@@ -292,7 +293,7 @@ int group_match(visfs_scan_group* g, const visfs_scan_stack_params& p, const dou
             if (rc == VISFS_BA_ERR_UNSUPPORTED) {
                 now[i] = Last();
                 if (first_overflow.empty()) first_overflow = member_text(i, text);
-            } else if (rc != VISFS_BA_OK) return gfail(g, rc, member_text(i, text));
+            } else if (rc != VISFS_BA_OK) return fail(g, rc, member_text(i, text));
         }
     }
     int32_t best = -1, best_sum = -1;
@@ -315,7 +316,7 @@ int group_match(visfs_scan_group* g, const visfs_scan_stack_params& p, const dou
             if (!w.matched) { scanrefine::not_refined(VISFS_BA_OK, w.x, w.y, w.yaw, refined + i); continue; }
             if (g->device) {
                 refined[i] = records_of(g->blk.h_ctrl, m)[i];
-                if (!refined[i].refined) return gfail(g, VISFS_BA_ERR_DEVICE, member_text(i, "the refinement skipped a matched member"));
+                if (!refined[i].refined) return fail(g, VISFS_BA_ERR_DEVICE, member_text(i, "the refinement skipped a matched member"));
             } else {
                 const double start[3] = { w.x, w.y, w.yaw };
                 traces[i].assign((size_t)scanrefine::kMaxTrials * scanrefine::kTraceItems, 0.0);
@@ -342,7 +343,7 @@ int visfs_scan_group_abi_version(void) { return VISFS_SCAN_GROUP_ABI_VERSION; }
 int visfs_scan_group_create(int32_t m, visfs_scan_stack* const* members, visfs_scan_group** out) {
     if (!out) return VISFS_BA_ERR_BAD_ARGUMENT;
     *out = nullptr;
-    return guarded([&]() -> int {
+    return guarded(nullptr, [&]() -> int {
         auto bad = [&](int rc, const std::string& why) { t_create_err = why; return rc; };
         if (m < 1 || m > VISFS_SCAN_GROUP_MAX) return bad(VISFS_BA_ERR_UNSUPPORTED, "a group holds 1 to 64 members");
         if (!members) return bad(VISFS_BA_ERR_BAD_ARGUMENT, "no members");
@@ -372,14 +373,14 @@ const char* visfs_scan_group_last_error(const visfs_scan_group* g) { return g ? 
 int visfs_scan_group_match(visfs_scan_group* g, const visfs_scan_stack_params* p, const double* guesses, int32_t n, const double* xyz,
                            visfs_scan_stack_result* results, int32_t* status, int32_t* best_member) {
     if (!g || !p || !guesses || !results || !status || !best_member || n < 0 || (n > 0 && !xyz)) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded([&]() -> int { return group_match(g, *p, guesses, n, xyz, results, status, best_member); });
+    return guarded(g, [&]() -> int { return group_match(g, *p, guesses, n, xyz, results, status, best_member); });
 }
 
 int visfs_scan_group_match_download(visfs_scan_group* g, int32_t member, int32_t header[8], int32_t scored[16], int32_t kept[16],
                                     int64_t bounds_cap, int32_t* bounds, int64_t survivors_cap, int32_t* survivors) {
     if (!g || !header || bounds_cap < 0 || survivors_cap < 0) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded([&]() -> int {
-        if (member < 0 || member >= (int32_t)g->mem.size()) return gfail(g, VISFS_BA_ERR_BAD_ARGUMENT, "the group has no such member");
+    return guarded(g, [&]() -> int {
+        if (member < 0 || member >= (int32_t)g->mem.size()) return fail(g, VISFS_BA_ERR_BAD_ARGUMENT, "the group has no such member");
         return match_download(g->device, g->dev, g->stream, g->blk, member, g->last[(size_t)member], g->err, header, scored, kept, bounds_cap, bounds,
                               survivors_cap, survivors);
     });
@@ -389,32 +390,28 @@ int visfs_scan_group_match_refine(visfs_scan_group* g, const visfs_scan_stack_pa
                                   int32_t n, const double* xyz, visfs_scan_stack_result* results, int32_t* status, int32_t* best_member,
                                   visfs_scan_refine_result* refined) {
     if (!g || !mp || !rp || !guesses || !results || !status || !best_member || !refined || n < 0 || (n > 0 && !xyz)) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded([&]() -> int { return group_match(g, *mp, guesses, n, xyz, results, status, best_member, rp, refined); });
+    return guarded(g, [&]() -> int { return group_match(g, *mp, guesses, n, xyz, results, status, best_member, rp, refined); });
 }
 
 int visfs_scan_group_refine_download(visfs_scan_group* g, int32_t member, int32_t cap, double* trace, int32_t* trials) {
     if (!g || !trials || cap < 0) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded([&]() -> int {
-        if (member < 0 || member >= (int32_t)g->mem.size()) return gfail(g, VISFS_BA_ERR_BAD_ARGUMENT, "the group has no such member");
+    return guarded(g, [&]() -> int {
+        if (member < 0 || member >= (int32_t)g->mem.size()) return fail(g, VISFS_BA_ERR_BAD_ARGUMENT, "the group has no such member");
         const int32_t nt = (size_t)member < g->rtrials.size() ? g->rtrials[(size_t)member] : 0;
         *trials = nt;
         if (!trace || nt == 0) return (int)VISFS_BA_OK;
-        if (cap < nt) return gfail(g, VISFS_BA_ERR_BAD_ARGUMENT, "the hook's array is too small");
+        if (cap < nt) return fail(g, VISFS_BA_ERR_BAD_ARGUMENT, "the hook's array is too small");
         const size_t bytes = (size_t)nt * scanrefine::kTraceItems * sizeof(double);
         if (!g->device) { std::memcpy(trace, g->h_rtrace[(size_t)member].data(), bytes); return (int)VISFS_BA_OK; }
-        SCAN_HIP(g->err, hipSetDevice(g->dev));
-        SCAN_HIP(g->err, hipMemcpyAsync(trace, g->d_rtrace[1] + (size_t)member * scanrefine::kMaxTrials * scanrefine::kTraceItems, bytes, hipMemcpyDeviceToHost, g->stream));
-        SCAN_HIP(g->err, hipStreamSynchronize(g->stream));
+        HIP_TRY(&g->err, hipSetDevice(g->dev));
+        HIP_TRY(&g->err, hipMemcpyAsync(trace, g->d_rtrace[1] + (size_t)member * scanrefine::kMaxTrials * scanrefine::kTraceItems, bytes, hipMemcpyDeviceToHost, g->stream));
+        HIP_TRY(&g->err, hipStreamSynchronize(g->stream));
         return (int)VISFS_BA_OK;
     });
 }
 
 int visfs_scan_group_last_counts(const visfs_scan_group* g, int32_t* kernel_launches, int32_t* copies_and_memsets, int32_t* synchronisations) {
-    if (!g) return VISFS_BA_ERR_BAD_ARGUMENT;
-    if (kernel_launches) *kernel_launches = g->blk.launches;
-    if (copies_and_memsets) *copies_and_memsets = g->blk.copies;
-    if (synchronisations) *synchronisations = g->blk.syncs;
-    return VISFS_BA_OK;
+    return g ? g->blk.counts.read(kernel_launches, copies_and_memsets, synchronisations) : (int)VISFS_BA_ERR_BAD_ARGUMENT;
 }
 
 }  // extern "C"

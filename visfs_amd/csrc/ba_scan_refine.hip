@@ -10,6 +10,7 @@
 // launch to its match sequence.
 #pragma clang fp contract(off)
 #include "ba_scan_refine.hpp"
+#include "ba_host.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -19,6 +20,7 @@
 #include <vector>
 
 using namespace scanrefine;
+using namespace host;
 
 namespace scanrefine {
 
@@ -148,12 +150,6 @@ namespace {
 
 constexpr size_t kTraceBytes = (size_t)kMaxTrials * kTraceItems * sizeof(double);
 
-#define SR_HIP(expr)                                                                               \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) { why = std::string(#expr) + ": " + hipGetErrorString(e_); return (int)VISFS_BA_ERR_DEVICE; } \
-    } while (0)
-
 std::vector<double> points_xy(int32_t n, const double* xyz) {
     std::vector<double> p(2 * (size_t)n);
     for (int32_t i = 0; i < n; ++i) { p[2 * i] = xyz[3 * i]; p[2 * i + 1] = xyz[3 * i + 1]; }
@@ -171,29 +167,29 @@ int run_single(State& st, bool device, int dev, hipStream_t stream, const Job& J
         st.trials = out->trials;
         return VISFS_BA_OK;
     }
-    SR_HIP(hipSetDevice(dev));
+    HIP_TRY(&why, hipSetDevice(dev));
     const size_t bytes = sizeof(Job) + pts.size() * sizeof(double);
     if (st.up_cap < bytes) {
-        if (st.h_up) SR_HIP(hipHostFree(st.h_up));
-        if (st.d_up) SR_HIP(hipFree(st.d_up));
+        if (st.h_up) HIP_TRY(&why, hipHostFree(st.h_up));
+        if (st.d_up) HIP_TRY(&why, hipFree(st.d_up));
         st.h_up = st.d_up = nullptr; st.up_cap = 0;
         const size_t cap = bytes + bytes / 2;
-        SR_HIP(hipHostMalloc(reinterpret_cast<void**>(&st.h_up), cap, hipHostMallocDefault));
-        SR_HIP(hipMalloc(reinterpret_cast<void**>(&st.d_up), cap));
+        HIP_TRY(&why, hipHostMalloc(reinterpret_cast<void**>(&st.h_up), cap, hipHostMallocDefault));
+        HIP_TRY(&why, hipMalloc(reinterpret_cast<void**>(&st.d_up), cap));
         st.up_cap = cap;
     }
     if (!st.d_out) {
-        SR_HIP(hipMalloc(reinterpret_cast<void**>(&st.d_out), sizeof(visfs_scan_refine_result)));
-        SR_HIP(hipHostMalloc(reinterpret_cast<void**>(&st.h_out), sizeof(visfs_scan_refine_result), hipHostMallocDefault));
+        HIP_TRY(&why, hipMalloc(reinterpret_cast<void**>(&st.d_out), sizeof(visfs_scan_refine_result)));
+        HIP_TRY(&why, hipHostMalloc(reinterpret_cast<void**>(&st.h_out), sizeof(visfs_scan_refine_result), hipHostMallocDefault));
     }
-    for (double*& p : st.d_trace) if (!p) SR_HIP(hipMalloc(reinterpret_cast<void**>(&p), kTraceBytes));
+    for (double*& p : st.d_trace) if (!p) HIP_TRY(&why, hipMalloc(reinterpret_cast<void**>(&p), kTraceBytes));
     std::memcpy(st.h_up, &J, sizeof(Job));
     std::memcpy(st.h_up + sizeof(Job), pts.data(), pts.size() * sizeof(double));
-    SR_HIP(hipMemcpyAsync(st.d_up, st.h_up, bytes, hipMemcpyHostToDevice, stream));
-    SR_HIP((hipError_t)launch_refine(stream, 1, reinterpret_cast<const Job*>(st.d_up), P, reinterpret_cast<const double*>(st.d_up + sizeof(Job)), st.d_out,
+    HIP_TRY(&why, hipMemcpyAsync(st.d_up, st.h_up, bytes, hipMemcpyHostToDevice, stream));
+    HIP_TRY(&why, (hipError_t)launch_refine(stream, 1, reinterpret_cast<const Job*>(st.d_up), P, reinterpret_cast<const double*>(st.d_up + sizeof(Job)), st.d_out,
                                      st.d_trace[0]));
-    SR_HIP(hipMemcpyAsync(st.h_out, st.d_out, sizeof(visfs_scan_refine_result), hipMemcpyDeviceToHost, stream));
-    SR_HIP(hipStreamSynchronize(stream));
+    HIP_TRY(&why, hipMemcpyAsync(st.h_out, st.d_out, sizeof(visfs_scan_refine_result), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(&why, hipStreamSynchronize(stream));
     *out = *st.h_out;
     std::swap(st.d_trace[0], st.d_trace[1]);
     st.trials = out->trials;
@@ -207,9 +203,9 @@ int download_trace(State* st, bool device, int dev, hipStream_t stream, int32_t 
     if (cap < n) { why = "the hook's array is too small"; return VISFS_BA_ERR_BAD_ARGUMENT; }
     const size_t bytes = (size_t)n * kTraceItems * sizeof(double);
     if (!device) { std::memcpy(trace, st->trace.data(), bytes); return VISFS_BA_OK; }
-    SR_HIP(hipSetDevice(dev));
-    SR_HIP(hipMemcpyAsync(trace, st->d_trace[1], bytes, hipMemcpyDeviceToHost, stream));
-    SR_HIP(hipStreamSynchronize(stream));
+    HIP_TRY(&why, hipSetDevice(dev));
+    HIP_TRY(&why, hipMemcpyAsync(trace, st->d_trace[1], bytes, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(&why, hipStreamSynchronize(stream));
     return VISFS_BA_OK;
 }
 
@@ -226,12 +222,6 @@ State* state_of(visfs_scan_stack* st) {
     return st->refine;
 }
 
-int sfail(visfs_scan_stack* st, int rc, const std::string& why) { st->err = why; return rc; }
-
-template <class F> int guarded(F&& f) noexcept {
-    try { return f(); }
-    catch (...) { return (int)VISFS_BA_ERR_DEVICE; }
-}
 
 }  // namespace
 
@@ -249,7 +239,7 @@ void visfs_scan_refine_default_params(visfs_scan_refine_params* p) {
 int visfs_scan_refine(visfs_submaps* s, int32_t index, const visfs_scan_refine_params* p, const double a[3], const double tg[2], int32_t n,
                       const double* xyz, visfs_scan_refine_result* out) {
     if (!s || !p || !a || !tg || !out || n < 0 || (n > 0 && !xyz)) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded([&]() -> int {
+    return guarded(s, [&]() -> int {
         if (index < 0) return visfs_internal_scan_fail(s, VISFS_BA_ERR_BAD_ARGUMENT, "sub-map index out of range");
         const char* why = "";
         int rc = check_call(*p, a, tg, n, xyz, &why);
@@ -276,21 +266,21 @@ int visfs_scan_refine(visfs_submaps* s, int32_t index, const visfs_scan_refine_p
 int visfs_scan_stack_refine(visfs_scan_stack* st, const visfs_scan_refine_params* p, const double a[3], const double tg[2], int32_t n,
                             const double* xyz, visfs_scan_refine_result* out) {
     if (!st || !p || !a || !tg || !out || n < 0 || (n > 0 && !xyz)) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded([&]() -> int {
+    return guarded(st, [&]() -> int {
         const char* why = "";
         int rc = check_call(*p, a, tg, n, xyz, &why);
-        if (rc != VISFS_BA_OK) return sfail(st, rc, why);
+        if (rc != VISFS_BA_OK) return fail(st, rc, why);
         State* rs = state_of(st);
         if (n == 0) { not_refined(VISFS_BA_OK, a[0], a[1], a[2], out); rs->trials = 0; return (int)VISFS_BA_OK; }
         std::string text;
         rc = run_single(*rs, st->device, st->dev, st->stream, stack_job(st, a, tg), make_prm(*p, n), xyz, out, text);
-        return rc == VISFS_BA_OK ? rc : sfail(st, rc, text);
+        return rc == VISFS_BA_OK ? rc : fail(st, rc, text);
     });
 }
 
 int visfs_scan_refine_download(visfs_submaps* s, int32_t cap, double* trace, int32_t* trials) {
     if (!s || !trials || cap < 0) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded([&]() -> int {
+    return guarded(s, [&]() -> int {
         submap::ScanAccess acc;
         int rc = visfs_internal_scan_access(s, -1, &acc);                  // the device and the stream
         if (rc != VISFS_BA_OK) return rc;
@@ -302,10 +292,10 @@ int visfs_scan_refine_download(visfs_submaps* s, int32_t cap, double* trace, int
 
 int visfs_scan_stack_refine_download(visfs_scan_stack* st, int32_t cap, double* trace, int32_t* trials) {
     if (!st || !trials || cap < 0) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded([&]() -> int {
+    return guarded(st, [&]() -> int {
         std::string text;
         const int rc = download_trace(st->refine, st->device, st->dev, st->stream, cap, trace, trials, text);
-        return rc == VISFS_BA_OK ? rc : sfail(st, rc, text);
+        return rc == VISFS_BA_OK ? rc : fail(st, rc, text);
     });
 }
 

@@ -4,6 +4,7 @@
 // and the bodies of its kernels.  The single call is the sequence at m = 1 on the stack's own block.  device_run and its kernels are
 // defined in ba_scan_group.hip, the other host functions in ba_scan_fast.hip.
 #pragma once
+#include "ba_host.hpp"
 #include "ba_scan_fast.hpp"
 
 #include <climits>
@@ -45,7 +46,7 @@ struct CallBlock {
     Bounds bnd[2];
     Frontier fr[3];
     int64_t top = 0, cap = 0;                 // the strides of the hook's arenas: those of the last call handed over
-    int32_t launches = 0, copies = 0, syncs = 0;      // of the last device_run
+    host::Counts counts;                      // of the last device_run
     // the hook's arenas become what a call wrote, its level-0 frontier in fr[cur]; they stay until the next hand-over
     void hand_over(int cur, const Search& s) {
         std::swap(bnd[0], bnd[1]);
@@ -99,28 +100,6 @@ void no_points(const double g[3], visfs_scan_stack_result* out);
 // The one-core twin's schedule over the levels `lv`: fills `now` (counts, bounds, sorted survivors, winner) and returns VISFS_BA_OK;
 // on a frontier overflow VISFS_BA_ERR_UNSUPPORTED, on an empty result VISFS_BA_ERR_DEVICE, with `why`.
 int host_search(const Levels& lv, const Search& s, Last& now, std::string& why);
-
-#define SCAN_HIP(err, expr)                                                                                           \
-    do {                                                                                                              \
-        hipError_t e_ = (expr);                                                                                       \
-        if (e_ != hipSuccess) { (err) = std::string(#expr) + ": " + hipGetErrorString(e_); return VISFS_BA_ERR_DEVICE; } \
-    } while (0)
-
-inline unsigned blocks_for(int64_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
-
-template <class F> int guarded(F&& f) noexcept {
-    try { return f(); }
-    catch (...) { return (int)VISFS_BA_ERR_DEVICE; }
-}
-
-template <class T> int grow(std::string& err, T** p, size_t* cap, size_t need) {
-    if (*cap >= need) return VISFS_BA_OK;
-    if (*p) SCAN_HIP(err, hipFree(*p));
-    *p = nullptr; *cap = 0;
-    SCAN_HIP(err, hipMalloc(reinterpret_cast<void**>(p), need * sizeof(T)));
-    *cap = need;
-    return VISFS_BA_OK;
-}
 
 // Every buffer of the block let go; the caller has selected the device and waited for the stream.
 void block_free(CallBlock& b);

@@ -12,6 +12,7 @@
 // A cell changes at most once per insertion and a hit wins over a miss: exactly the reference's update markers, in one pass.
 #include "ba_submap.hpp"
 #include "ba_submap_access.hpp"
+#include "ba_host.hpp"
 #include "../../include/visfs_submap.h"
 
 #include <algorithm>
@@ -22,6 +23,7 @@
 #include <vector>
 
 using namespace submap;
+using namespace host;
 
 namespace {
 
@@ -257,8 +259,6 @@ __global__ __launch_bounds__(SM_T) void k_submap_crop(const uint16_t* __restrict
     nc[i] = v; nf[i] = costT[v]; nh[i] = 0u; nm[i] = 0u;
 }
 
-int blocks_for(int64_t n) { return (int)((n + SM_T - 1) / SM_T); }
-
 }  // namespace
 
 // ---------------------------------------------------------------- the sub-maps object
@@ -305,21 +305,13 @@ struct visfs_submaps {
 
 namespace {
 
-int fail(visfs_submaps* s, int rc, const std::string& why) { s->err = why; return rc; }
-#define SM_HIP(s, expr)                                                                                   \
-    do {                                                                                                  \
-        hipError_t e_ = (expr);                                                                           \
-        if (e_ != hipSuccess) return fail((s), VISFS_BA_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-size_t up256(size_t x) { return (x + 255) & ~size_t(255); }
 
 // one allocation: cells, cost mirror, hit and miss marks
 int dsub_alloc(visfs_submaps* s, visfs_submaps::DSub& d, const Limits& L, char** mem, uint16_t** c, float** f, uint32_t** hm, uint32_t** mm) {
     const size_t n = (size_t)L.nx * L.ny;
     const size_t b2 = up256(n * 2), b4 = up256(n * 4);
     (void)d;
-    SM_HIP(s, hipMalloc(reinterpret_cast<void**>(mem), b2 + 3 * b4));
+    HIP_TRY(s, hipMalloc(reinterpret_cast<void**>(mem), b2 + 3 * b4));
     *c = reinterpret_cast<uint16_t*>(*mem);
     *f = reinterpret_cast<float*>(*mem + b2);
     *hm = reinterpret_cast<uint32_t*>(*mem + b2 + b4);
@@ -334,10 +326,10 @@ int dsub_realize(visfs_submaps* s, visfs_submaps::DSub& d) {
     int rc = dsub_alloc(s, d, d.L, &mem, &c, &f, &hm, &mm);
     if (rc != VISFS_BA_OK) return rc;
     const int64_t n = (int64_t)d.L.nx * d.L.ny;
-    hipLaunchKernelGGL(k_submap_grow, dim3(blocks_for(n)), dim3(SM_T), 0, s->stream, d.cells, d.cost, d.La.nx, d.La.ny, d.gx, d.gy,
+    hipLaunchKernelGGL(k_submap_grow, dim3(blocks_for(n, SM_T)), dim3(SM_T), 0, s->stream, d.cells, d.cost, d.La.nx, d.La.ny, d.gx, d.gy,
                        c, f, hm, mm, d.L.nx, n, s->tab.cost_f[0]);
-    SM_HIP(s, hipGetLastError());
-    if (d.mem) SM_HIP(s, hipFree(d.mem));                              // (waits for the copy above)
+    HIP_TRY(s, hipGetLastError());
+    if (d.mem) HIP_TRY(s, hipFree(d.mem));                              // (waits for the copy above)
     d.mem = mem; d.cells = c; d.cost = f; d.hit = hm; d.miss = mm;
     d.La = d.L; d.gx = d.gy = 0;
     return VISFS_BA_OK;
@@ -381,27 +373,27 @@ int flush_batch(visfs_submaps* s) {
     if (total >= ((int64_t)1 << 31)) return fail(s, VISFS_BA_ERR_UNSUPPORTED, "a batch of more than 2^31 work items");
     const size_t nrec = s->recs.size();
     if (nrec > 0) {
-        if (s->recs_in_flight) { SM_HIP(s, hipStreamSynchronize(s->stream)); s->recs_in_flight = false; }
+        if (s->recs_in_flight) { HIP_TRY(s, hipStreamSynchronize(s->stream)); s->recs_in_flight = false; }
         if (s->h_recs_cap < nrec) {
             if (s->h_recs) (void)hipHostFree(s->h_recs);
             s->h_recs = nullptr; s->h_recs_cap = 0;
-            SM_HIP(s, hipHostMalloc(reinterpret_cast<void**>(&s->h_recs), (nrec + nrec / 2) * sizeof(MarkRec), hipHostMallocDefault));
+            HIP_TRY(s, hipHostMalloc(reinterpret_cast<void**>(&s->h_recs), (nrec + nrec / 2) * sizeof(MarkRec), hipHostMallocDefault));
             s->h_recs_cap = nrec + nrec / 2;
         }
         if (s->d_recs_cap < nrec) {
-            if (s->d_recs) SM_HIP(s, hipFree(s->d_recs));
+            if (s->d_recs) HIP_TRY(s, hipFree(s->d_recs));
             s->d_recs = nullptr; s->d_recs_cap = 0;
-            SM_HIP(s, hipMalloc(reinterpret_cast<void**>(&s->d_recs), (nrec + nrec / 2) * sizeof(MarkRec)));
+            HIP_TRY(s, hipMalloc(reinterpret_cast<void**>(&s->d_recs), (nrec + nrec / 2) * sizeof(MarkRec)));
             s->d_recs_cap = nrec + nrec / 2;
         }
         std::memcpy(s->h_recs, s->recs.data(), nrec * sizeof(MarkRec));
-        SM_HIP(s, hipMemcpyAsync(s->d_recs, s->h_recs, nrec * sizeof(MarkRec), hipMemcpyHostToDevice, s->stream));
+        HIP_TRY(s, hipMemcpyAsync(s->d_recs, s->h_recs, nrec * sizeof(MarkRec), hipMemcpyHostToDevice, s->stream));
         s->recs_in_flight = true;
         MarkArgs M{};
         for (int k = 0; k < ns; ++k) { M.hit[k] = s->dsubs[k].hit; M.miss[k] = s->dsubs[k].miss; M.nx[k] = s->dsubs[k].L.nx; M.ny[k] = s->dsubs[k].L.ny; }
         if (total > 0) {
-            hipLaunchKernelGGL(k_submap_mark, dim3(blocks_for(total)), dim3(SM_T), 0, s->stream, s->d_recs, (int32_t)nrec, (int32_t)total, M);
-            SM_HIP(s, hipGetLastError());
+            hipLaunchKernelGGL(k_submap_mark, dim3(blocks_for(total, SM_T)), dim3(SM_T), 0, s->stream, s->d_recs, (int32_t)nrec, (int32_t)total, M);
+            HIP_TRY(s, hipGetLastError());
         }
         ApplyArgs A{};
         int64_t most = 0;
@@ -413,8 +405,8 @@ int flush_batch(visfs_submaps* s) {
             most = std::max(most, (int64_t)A.w[k] * A.h[k]);
         }
         if (most > 0) {
-            hipLaunchKernelGGL(k_submap_apply, dim3(blocks_for(most), ns), dim3(SM_T), 0, s->stream, A, s->d_hit, s->d_miss, s->d_cost);
-            SM_HIP(s, hipGetLastError());
+            hipLaunchKernelGGL(k_submap_apply, dim3(blocks_for(most, SM_T), ns), dim3(SM_T), 0, s->stream, A, s->d_hit, s->d_miss, s->d_cost);
+            HIP_TRY(s, hipGetLastError());
         }
     }
     s->recs.clear();
@@ -435,9 +427,9 @@ int device_finish(visfs_submaps* s, visfs_submaps::DSub& d) {
     int rc = dsub_alloc(s, d, l, &mem, &c, &f, &hm, &mm);
     if (rc != VISFS_BA_OK) return rc;
     const int64_t n = (int64_t)cx * cy;
-    hipLaunchKernelGGL(k_submap_crop, dim3(blocks_for(n)), dim3(SM_T), 0, s->stream, d.cells, d.L.nx, offx, offy, c, f, hm, mm, cx, n, s->d_crop, s->d_cost);
-    SM_HIP(s, hipGetLastError());
-    SM_HIP(s, hipFree(d.mem));
+    hipLaunchKernelGGL(k_submap_crop, dim3(blocks_for(n, SM_T)), dim3(SM_T), 0, s->stream, d.cells, d.L.nx, offx, offy, c, f, hm, mm, cx, n, s->d_crop, s->d_cost);
+    HIP_TRY(s, hipGetLastError());
+    HIP_TRY(s, hipFree(d.mem));
     d.mem = mem; d.cells = c; d.cost = f; d.hit = hm; d.miss = mm;
     d.L = d.La = l; d.gx = d.gy = 0;
     Box b;
@@ -488,7 +480,7 @@ int device_insert(visfs_submaps* s, const double T[12], const Transformed& t) {
     int rc;
     if (s->dsubs.empty() || s->dsubs.back().count == limit) {                              // addSubmap (the front, finished, dropped)
         if ((rc = flush_batch(s)) != VISFS_BA_OK) return rc;
-        if (s->dsubs.size() >= 2) { if (s->dsubs.front().mem) SM_HIP(s, hipFree(s->dsubs.front().mem)); s->dsubs.pop_front(); }
+        if (s->dsubs.size() >= 2) { if (s->dsubs.front().mem) HIP_TRY(s, hipFree(s->dsubs.front().mem)); s->dsubs.pop_front(); }
         visfs_submaps::DSub d;
         d.L = initial_limits(s->prm.map_resolution, T);
         s->dsubs.push_back(d);
@@ -558,12 +550,6 @@ int check_params(const visfs_submap_params* p, std::string& why) {
     return VISFS_BA_OK;
 }
 
-template <class F> int guarded_sm(visfs_submaps* s, F&& f) noexcept {
-    try { return f(); }
-    catch (const std::bad_alloc&) { if (s) s->err = "out of host memory"; return VISFS_BA_ERR_DEVICE; }
-    catch (...) { if (s) s->err = "unexpected exception"; return VISFS_BA_ERR_DEVICE; }
-}
-
 void release(visfs_submaps* s) {
     if (!s->device) return;
     (void)hipSetDevice(s->dev);
@@ -592,7 +578,7 @@ void visfs_submap_default_params(visfs_submap_params* p) {
 int visfs_submaps_create_host(const visfs_submap_params* p, visfs_submaps** out) {
     if (!p || !out) return VISFS_BA_ERR_BAD_ARGUMENT;
     *out = nullptr;
-    return guarded_sm(nullptr, [&]() -> int {
+    return guarded(nullptr, [&]() -> int {
         std::string why;
         const int rc = check_params(p, why);
         if (rc != VISFS_BA_OK) return rc;
@@ -607,7 +593,7 @@ int visfs_submaps_create_host(const visfs_submap_params* p, visfs_submaps** out)
 int visfs_submaps_create(visfs_ba_handle* h, const visfs_submap_params* p, visfs_submaps** out) {
     if (!h || !p || !out) return VISFS_BA_ERR_BAD_ARGUMENT;
     *out = nullptr;
-    return guarded_sm(nullptr, [&]() -> int {
+    return guarded(nullptr, [&]() -> int {
         std::string why;
         int rc = check_params(p, why);
         if (rc != VISFS_BA_OK) { visfs_internal_set_error(h, why.c_str()); return rc; }
@@ -616,19 +602,19 @@ int visfs_submaps_create(visfs_ba_handle* h, const visfs_submap_params* p, visfs
         s->tab.build(p->hit_probability, p->miss_probability);
         s->device = true; s->h = h; s->dev = visfs_internal_device(h); s->stream = visfs_internal_stream(h);
         auto init = [&]() -> int {
-            SM_HIP(s, hipSetDevice(s->dev));
+            HIP_TRY(s, hipSetDevice(s->dev));
             // the tables, one allocation: hit, miss (without the update marker), crop round trip (uint16), cost (float)
             const size_t b2 = up256((size_t)kValueCount * 2), b4 = up256((size_t)kValueCount * 4);
             char* mem = nullptr;
-            SM_HIP(s, hipMalloc(reinterpret_cast<void**>(&mem), 3 * b2 + b4));
+            HIP_TRY(s, hipMalloc(reinterpret_cast<void**>(&mem), 3 * b2 + b4));
             s->d_hit = reinterpret_cast<uint16_t*>(mem); s->d_miss = reinterpret_cast<uint16_t*>(mem + b2);
             s->d_crop = reinterpret_cast<uint16_t*>(mem + 2 * b2); s->d_cost = reinterpret_cast<float*>(mem + 3 * b2);
             std::vector<uint16_t> hit(kValueCount), miss(kValueCount);
             for (int v = 0; v < kValueCount; ++v) { hit[v] = (uint16_t)(s->tab.hit[v] - kUpdateMarker); miss[v] = (uint16_t)(s->tab.miss[v] - kUpdateMarker); }
-            SM_HIP(s, hipMemcpy(s->d_hit, hit.data(), kValueCount * 2, hipMemcpyHostToDevice));
-            SM_HIP(s, hipMemcpy(s->d_miss, miss.data(), kValueCount * 2, hipMemcpyHostToDevice));
-            SM_HIP(s, hipMemcpy(s->d_crop, s->tab.crop.data(), kValueCount * 2, hipMemcpyHostToDevice));
-            SM_HIP(s, hipMemcpy(s->d_cost, s->tab.cost_f.data(), kValueCount * 4, hipMemcpyHostToDevice));
+            HIP_TRY(s, hipMemcpy(s->d_hit, hit.data(), kValueCount * 2, hipMemcpyHostToDevice));
+            HIP_TRY(s, hipMemcpy(s->d_miss, miss.data(), kValueCount * 2, hipMemcpyHostToDevice));
+            HIP_TRY(s, hipMemcpy(s->d_crop, s->tab.crop.data(), kValueCount * 2, hipMemcpyHostToDevice));
+            HIP_TRY(s, hipMemcpy(s->d_cost, s->tab.cost_f.data(), kValueCount * 4, hipMemcpyHostToDevice));
             return VISFS_BA_OK;
         };
         rc = init();
@@ -658,7 +644,7 @@ const char* visfs_submaps_last_error(const visfs_submaps* s) { return s ? s->err
 
 int visfs_submaps_insert(visfs_submaps* s, const double Twr[12], int32_t n, const visfs_range_data* rd) {
     if (!s || !Twr || n < 0 || (n > 0 && !rd)) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded_sm(s, [&]() -> int {
+    return guarded(s, [&]() -> int {
         for (int i = 0; i < 12; ++i) if (!std::isfinite(Twr[i])) return fail(s, VISFS_BA_ERR_BAD_ARGUMENT, "Twr is not finite");
         for (int k = 0; k < n; ++k) {
             const visfs_range_data& r = rd[k];
@@ -668,7 +654,7 @@ int visfs_submaps_insert(visfs_submaps* s, const double Twr[12], int32_t n, cons
             for (int64_t i = 0; i < 3 * (int64_t)r.n_returns; ++i) if (!std::isfinite(r.returns[i])) return fail(s, VISFS_BA_ERR_BAD_ARGUMENT, "a return is not finite");
             for (int64_t i = 0; i < 3 * (int64_t)r.n_misses; ++i) if (!std::isfinite(r.misses[i])) return fail(s, VISFS_BA_ERR_BAD_ARGUMENT, "a miss is not finite");
         }
-        if (s->device) SM_HIP(s, hipSetDevice(s->dev));
+        if (s->device) HIP_TRY(s, hipSetDevice(s->dev));
         Transformed t;
         for (int k = 0; k < n; ++k) {                                  // each range data its own insertion, in order
             transform_rd(Twr, rd[k], t);
@@ -696,7 +682,7 @@ int visfs_submaps_describe(const visfs_submaps* s, int32_t* n, visfs_submap_info
 int visfs_submaps_download(const visfs_submaps* cs, int32_t index, uint16_t* cells, float* cost) {
     visfs_submaps* s = const_cast<visfs_submaps*>(cs);
     if (!s) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded_sm(s, [&]() -> int {
+    return guarded(s, [&]() -> int {
         const int ns = s->device ? (int)s->dsubs.size() : (int)s->hsubs.size();
         if (index < 0 || index >= ns) return fail(s, VISFS_BA_ERR_BAD_ARGUMENT, "sub-map index out of range");
         if (!s->device) {
@@ -707,10 +693,10 @@ int visfs_submaps_download(const visfs_submaps* cs, int32_t index, uint16_t* cel
         }
         const visfs_submaps::DSub& d = s->dsubs[index];
         const size_t n = (size_t)d.L.nx * d.L.ny;
-        SM_HIP(s, hipSetDevice(s->dev));
-        if (cells) SM_HIP(s, hipMemcpyAsync(cells, d.cells, n * 2, hipMemcpyDeviceToHost, s->stream));
-        if (cost) SM_HIP(s, hipMemcpyAsync(cost, d.cost, n * 4, hipMemcpyDeviceToHost, s->stream));
-        SM_HIP(s, hipStreamSynchronize(s->stream));
+        HIP_TRY(s, hipSetDevice(s->dev));
+        if (cells) HIP_TRY(s, hipMemcpyAsync(cells, d.cells, n * 2, hipMemcpyDeviceToHost, s->stream));
+        if (cost) HIP_TRY(s, hipMemcpyAsync(cost, d.cost, n * 4, hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(s, hipStreamSynchronize(s->stream));
         s->recs_in_flight = false;
         return (int)VISFS_BA_OK;
     });
@@ -749,11 +735,11 @@ int visfs_submap_hook_ray(const int32_t begin[2], const int32_t end[2], int32_t 
 
 int visfs_submap_hook_odds_table(double o, uint16_t* table) {
     if (!table || !(o > 0.0)) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded_sm(nullptr, [&]() -> int { const std::vector<uint16_t> t = odds_table(o); std::memcpy(table, t.data(), kValueCount * 2); return (int)VISFS_BA_OK; });
+    return guarded(nullptr, [&]() -> int { const std::vector<uint16_t> t = odds_table(o); std::memcpy(table, t.data(), kValueCount * 2); return (int)VISFS_BA_OK; });
 }
 
 int visfs_submap_hook_value_tables(double* cost, uint16_t* crop) {
-    return guarded_sm(nullptr, [&]() -> int {
+    return guarded(nullptr, [&]() -> int {
         Tables t;
         t.build(0.55, 0.49);
         if (cost) std::memcpy(cost, t.cost.data(), kValueCount * 8);
@@ -765,7 +751,7 @@ int visfs_submap_hook_value_tables(double* cost, uint16_t* crop) {
 int visfs_submap_hook_crop(int32_t nx, int32_t ny, const uint16_t* cells, const int32_t box[4], int64_t cap, int32_t out_dims[4],
                            uint16_t* out_cells, int32_t out_box[4]) {
     if (nx <= 0 || ny <= 0 || !cells || !box || !out_dims || !out_box || cap < 0) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded_sm(nullptr, [&]() -> int {
+    return guarded(nullptr, [&]() -> int {
         Tables t;
         t.build(0.55, 0.49);
         HostGrid g;
@@ -791,7 +777,7 @@ int visfs_internal_scan_access(visfs_submaps* s, int32_t index, submap::ScanAcce
     *a = submap::ScanAccess();
     a->device = s->device; a->dev = s->dev; a->stream = s->stream;
     if (s->device) {
-        SM_HIP(s, hipSetDevice(s->dev));
+        HIP_TRY(s, hipSetDevice(s->dev));
         const int rc = flush_batch(s);
         if (rc != VISFS_BA_OK) return rc;
         a->count = (int32_t)s->dsubs.size();

@@ -9,6 +9,8 @@
 #include <cmath>
 #include <cstdint>
 
+#include "../../include/visfs_submap.h"
+
 struct visfs_ba_handle;
 struct visfs_ba_window;
 struct visfs_ba_result;
@@ -32,6 +34,12 @@ struct Limits {
     double res = 0.0, max_x = 0.0, max_y = 0.0;
     int32_t nx = 0, ny = 0;
 };
+
+inline Limits limits_of(const visfs_submap_info& l) {
+    Limits L;
+    L.res = l.resolution; L.max_x = l.max_x; L.max_y = l.max_y; L.nx = l.num_x_cells; L.ny = l.num_y_cells;
+    return L;
+}
 
 // AlignedBox2i of the known cells; empty as Eigen's default box (min > max)
 struct Box {

@@ -2,6 +2,8 @@
 #pragma once
 #include "ba_submap.hpp"
 
+#include <string>
+
 struct visfs_submaps;
 
 namespace submap {
@@ -28,6 +30,8 @@ struct ScanAccess {
 // `device`, `dev`, `stream` and `count` are filled when `index` names no active sub-map.
 int visfs_internal_scan_access(visfs_submaps* s, int32_t index, submap::ScanAccess* a);
 int visfs_internal_scan_fail(visfs_submaps* s, int rc, const char* why);
+// the opaque sub-maps as a sink of ba_host.hpp's HIP_TRY and guarded
+inline void set_error(visfs_submaps* s, const std::string& text) { if (s) (void)visfs_internal_scan_fail(s, VISFS_BA_ERR_DEVICE, text.c_str()); }
 // The matcher's state, kept by the sub-maps object and freed with `destroy` (on the sub-maps' device) when they go.
 void** visfs_internal_scan_slot(visfs_submaps* s, void (*destroy)(void*));
 // The same for the refinement's state (ba_scan_refine.hip).

@@ -40,6 +40,7 @@
 #include "ba_group.hpp"
 #include "ba_fund.hpp"
 #include "ba_pnp.hpp"
+#include "ba_host.hpp"
 #include "../../include/visfs_tracker.h"
 #include "../../include/visfs_tracker_pnp.h"
 #include "../../include/visfs_tracker_group.h"
@@ -54,6 +55,7 @@
 
 using namespace flow;
 using namespace trk;
+using namespace host;
 
 struct visfs_tracker;
 struct visfs_tracker_group;
@@ -770,19 +772,6 @@ struct visfs_tracker_group {
 
 namespace {
 
-int fail(visfs_tracker* t, int rc, const std::string& why) { t->err = why; return rc; }
-#define TK_HIP(t, expr)                                                                                   \
-    do {                                                                                                  \
-        hipError_t e_ = (expr);                                                                           \
-        if (e_ != hipSuccess) return fail((t), VISFS_BA_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-template <class F> int guarded_tk(visfs_tracker* t, F&& fn) noexcept {
-    try { return fn(); }
-    catch (const std::bad_alloc&) { if (t) t->err = "out of host memory"; return VISFS_BA_ERR_DEVICE; }
-    catch (...) { if (t) t->err = "unexpected exception"; return VISFS_BA_ERR_DEVICE; }
-}
-
 Camera make_camera(const visfs_flow_params& p, const visfs_flow_camera& c) {
     Camera k;
     k.fx = c.fx; k.fy = c.fy; k.cx = c.cx; k.cy = c.cy; k.cx_right = c.cx_right; k.baseline = c.baseline;
@@ -823,19 +812,19 @@ int allocate(visfs_tracker* t) {
         t->R = B.o;
         return VISFS_BA_OK;
     }
-    TK_HIP(t, hipSetDevice(f->dev));
-    TK_HIP(t, hipMalloc(reinterpret_cast<void**>(&t->d_work), work_bytes));
-    TK_HIP(t, hipMalloc(reinterpret_cast<void**>(&t->d_out), t->out_bytes));
-    TK_HIP(t, hipHostMalloc(reinterpret_cast<void**>(&t->p_out), t->out_bytes, hipHostMallocDefault));
-    TK_HIP(t, t->blk.allocate(1));
+    HIP_TRY(t, hipSetDevice(f->dev));
+    HIP_TRY(t, hipMalloc(reinterpret_cast<void**>(&t->d_work), work_bytes));
+    HIP_TRY(t, hipMalloc(reinterpret_cast<void**>(&t->d_out), t->out_bytes));
+    HIP_TRY(t, hipHostMalloc(reinterpret_cast<void**>(&t->p_out), t->out_bytes, hipHostMallocDefault));
+    HIP_TRY(t, t->blk.allocate(1));
     carve_work(t->d_work, M, t->hw.size(), H, B, &hw);
     carve_out(t->d_out, M, false, B.o);
     carve_out(t->p_out, M, false, t->R);              // (B.in and B.outliers of a call point into the block the call goes through)
     std::memset(t->p_out, 0, t->out_bytes);
-    TK_HIP(t, hipMemsetAsync(t->d_work, 0, work_bytes, f->stream));
-    TK_HIP(t, hipMemsetAsync(t->d_out, 0, t->out_bytes, f->stream));
-    TK_HIP(t, hipMemcpyAsync(hw, t->hw.data(), t->hw.size() * sizeof(int32_t), hipMemcpyHostToDevice, f->stream));
-    TK_HIP(t, hipStreamSynchronize(f->stream));                        // t->hw may move; nothing else waits here
+    HIP_TRY(t, hipMemsetAsync(t->d_work, 0, work_bytes, f->stream));
+    HIP_TRY(t, hipMemsetAsync(t->d_out, 0, t->out_bytes, f->stream));
+    HIP_TRY(t, hipMemcpyAsync(hw, t->hw.data(), t->hw.size() * sizeof(int32_t), hipMemcpyHostToDevice, f->stream));
+    HIP_TRY(t, hipStreamSynchronize(f->stream));                        // t->hw may move; nothing else waits here
     return VISFS_BA_OK;
 }
 
@@ -1198,12 +1187,7 @@ int commit_member(visfs_tracker* t, const MemberPlan& P, visfs_tracker_result* r
 
 // ---------------------------------------------------------------- device: the launches of a call
 struct CallFault { int member = -1; std::string why; };               // which member a failed call blames (-1: none), and why
-
-#define RC_HIP(expr)                                                                                      \
-    do {                                                                                                  \
-        hipError_t e_ = (expr);                                                                           \
-        if (e_ != hipSuccess) { fault->member = -1; fault->why = std::string(#expr) + ": " + hipGetErrorString(e_); return VISFS_BA_ERR_DEVICE; } \
-    } while (0)
+void set_error(CallFault* fault, const std::string& text) { fault->member = -1; fault->why = text; }      // a sink of HIP_TRY
 
 // A call of n members (equal shapes and parameters, one handle) through the block `blk` on `stream`; a single call is n = 1 through
 // the tracker's own block.  Nothing here waits for a value read back: the one wait in front is for the pinned staging images and
@@ -1219,9 +1203,9 @@ int run_call(visfs_tracker* const* m, int n, const visfs_tracker_frame* fr, cons
                                       : clahe::Geom{};
     GroupCounts& cnt = *cnt_out;
     const auto blame = [&](int rc, int member, const std::string& why) { fault->member = member; fault->why = why; return rc; };
-    RC_HIP(hipSetDevice(device));
-    RC_HIP(hipStreamSynchronize(stream));
-    ++cnt.syncs;
+    HIP_TRY(fault, hipSetDevice(device));
+    HIP_TRY(fault, hipStreamSynchronize(stream));
+    ++cnt.waits;
     PyrRec* pyr = reinterpret_cast<PyrRec*>(blk.pinned + blk.off_pyr);
     ClaheRec* clr = reinterpret_cast<ClaheRec*>(blk.pinned + blk.off_clahe);
     CornerRec* cboot = reinterpret_cast<CornerRec*>(blk.pinned + blk.off_boot);
@@ -1278,7 +1262,7 @@ int run_call(visfs_tracker* const* m, int n, const visfs_tracker_frame* fr, cons
             t->have_call = false;
         }
     }
-    RC_HIP(hipMemcpyAsync(blk.dev, blk.pinned, blk.off_ids + sizeof(uint64_t) * n_ids, hipMemcpyHostToDevice, stream));
+    HIP_TRY(fault, hipMemcpyAsync(blk.dev, blk.pinned, blk.off_ids + sizeof(uint64_t) * n_ids, hipMemcpyHostToDevice, stream));
     ++cnt.copies;
     const auto dev = [&](size_t off) { return blk.dev + off; };
     int rc;
@@ -1296,8 +1280,8 @@ int run_call(visfs_tracker* const* m, int n, const visfs_tracker_frame* fr, cons
 #define RC_LAUNCH(kernel, grid, block, ...)                                                  \
     do {                                                                                     \
         hipLaunchKernelGGL(kernel, grid, block, 0, stream, __VA_ARGS__);                     \
-        RC_HIP(hipGetLastError());                                                           \
-        ++cnt.kernels;                                                                       \
+        HIP_TRY(fault, hipGetLastError());                                                           \
+        ++cnt.launches;                                                                       \
     } while (0)
         RC_LAUNCH(k_trk_pretreat_g, one, wg, d_trk, S);
         if (any_boot) {
@@ -1333,15 +1317,14 @@ int run_call(visfs_tracker* const* m, int n, const visfs_tracker_frame* fr, cons
         for (int i = 0; i < n; ++i) {
             if (plan[i].no_previous) continue;
             visfs_tracker* t = m[i];
-            RC_HIP(hipMemcpyAsync(t->p_out, t->d_out, pnp_on ? t->out_bytes : t->out_base_bytes, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(fault, hipMemcpyAsync(t->p_out, t->d_out, pnp_on ? t->out_bytes : t->out_base_bytes, hipMemcpyDeviceToHost, stream));
             ++cnt.copies;
         }
     }
-    RC_HIP(hipStreamSynchronize(stream));
-    ++cnt.syncs;
+    HIP_TRY(fault, hipStreamSynchronize(stream));
+    ++cnt.waits;
     return VISFS_BA_OK;
 }
-#undef RC_HIP
 
 void detach(visfs_tracker* t) {
     if (!t->f) return;
@@ -1382,7 +1365,7 @@ void visfs_tracker_default_params(visfs_tracker_params* p) {
 int visfs_tracker_create(visfs_flow* f, const visfs_tracker_params* p, const visfs_flow_camera* cam, visfs_tracker** out) {
     if (!f || !p || !cam || !out) return VISFS_BA_ERR_BAD_ARGUMENT;
     *out = nullptr;
-    return guarded_tk(nullptr, [&]() -> int {
+    return guarded(nullptr, [&]() -> int {
         const char* why = "";
         int rc = check_params(p, cam, &why);
         if (rc != VISFS_BA_OK) { f->err = why; return rc; }
@@ -1428,12 +1411,12 @@ const char* visfs_tracker_last_error(const visfs_tracker* t) { return t ? t->err
 
 int visfs_tracker_reset(visfs_tracker* t) {
     if (!t) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded_tk(t, [&]() -> int {
+    return guarded(t, [&]() -> int {
         if (!t->f) return fail(t, VISFS_BA_ERR_NOT_LOADED, "the flow object of this tracker is gone");
         t->ids.clear();
         if (!t->f->device) { t->B.ctl->n_tab = 0; return (int)VISFS_BA_OK; }
-        TK_HIP(t, hipSetDevice(t->f->dev));
-        TK_HIP(t, hipMemsetAsync(&t->B.ctl->n_tab, 0, sizeof(int32_t), t->f->stream));
+        HIP_TRY(t, hipSetDevice(t->f->dev));
+        HIP_TRY(t, hipMemsetAsync(&t->B.ctl->n_tab, 0, sizeof(int32_t), t->f->stream));
         return (int)VISFS_BA_OK;
     });
 }
@@ -1441,7 +1424,7 @@ int visfs_tracker_reset(visfs_tracker* t) {
 int visfs_tracker_process(visfs_tracker* t, const uint8_t* left, const uint8_t* right, int32_t stride, const double* delta_guess,
                           int32_t n_outliers, const uint64_t* outlier_ids, visfs_tracker_result* result) {
     if (!t) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded_tk(t, [&]() -> int {
+    return guarded(t, [&]() -> int {
         visfs_flow* f = t->f;
         const int rc_args = check_call(t, left, right, stride, delta_guess, n_outliers, outlier_ids, result);
         if (rc_args != VISFS_BA_OK) return rc_args;
@@ -1481,16 +1464,16 @@ int visfs_tracker_download(const visfs_tracker* ct, int32_t* n_from, float* gues
                            int32_t* n_discs, visfs_corners_disc* discs, uint8_t* disc_drawn, int32_t* n_rows, uint8_t* stereo_status) {
     visfs_tracker* t = const_cast<visfs_tracker*>(ct);
     if (!t) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded_tk(t, [&]() -> int {
+    return guarded(t, [&]() -> int {
         if (!t->f) return fail(t, VISFS_BA_ERR_NOT_LOADED, "the flow object of this tracker is gone");
         if (!t->have_call) return fail(t, VISFS_BA_ERR_NOT_LOADED, "no call to report on");
         visfs_flow* f = t->f;
         const Bufs& B = t->B;
         Ctl c;
         if (f->device) {
-            TK_HIP(t, hipSetDevice(f->dev));
-            TK_HIP(t, hipMemcpyAsync(&c, B.ctl, sizeof(Ctl), hipMemcpyDeviceToHost, f->stream));
-            TK_HIP(t, hipStreamSynchronize(f->stream));
+            HIP_TRY(t, hipSetDevice(f->dev));
+            HIP_TRY(t, hipMemcpyAsync(&c, B.ctl, sizeof(Ctl), hipMemcpyDeviceToHost, f->stream));
+            HIP_TRY(t, hipStreamSynchronize(f->stream));
         } else {
             c = *B.ctl;
         }
@@ -1502,7 +1485,7 @@ int visfs_tracker_download(const visfs_tracker* ct, int32_t* n_from, float* gues
         const auto get = [&](void* dst, const void* src, size_t bytes) -> int {
             if (!dst || bytes == 0) return VISFS_BA_OK;
             if (!f->device) { std::memcpy(dst, src, bytes); return VISFS_BA_OK; }
-            TK_HIP(t, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, f->stream));
+            HIP_TRY(t, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, f->stream));
             return VISFS_BA_OK;
         };
         int rc = get(guess_xy, B.guess, 8 * nf);
@@ -1513,7 +1496,7 @@ int visfs_tracker_download(const visfs_tracker* ct, int32_t* n_from, float* gues
         if (rc == VISFS_BA_OK) rc = get(disc_drawn, B.drawn, nl);
         if (rc == VISFS_BA_OK) rc = get(stereo_status, B.row_st, nr);
         if (rc != VISFS_BA_OK) return rc;
-        if (f->device) TK_HIP(t, hipStreamSynchronize(f->stream));
+        if (f->device) HIP_TRY(t, hipStreamSynchronize(f->stream));
         return (int)VISFS_BA_OK;
     });
 }
@@ -1522,7 +1505,7 @@ int visfs_tracker_download_cull(const visfs_tracker* ct, int32_t* applied, int32
                                 uint8_t* status, double* F, double* T1, double* T2, int32_t* winner_h, int32_t* winner_k) {
     visfs_tracker* t = const_cast<visfs_tracker*>(ct);
     if (!t) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded_tk(t, [&]() -> int {
+    return guarded(t, [&]() -> int {
         if (!t->f) return fail(t, VISFS_BA_ERR_NOT_LOADED, "the flow object of this tracker is gone");
         if (!t->have_call) return fail(t, VISFS_BA_ERR_NOT_LOADED, "no call to report on");
         if (applied) *applied = 0;
@@ -1541,13 +1524,13 @@ int visfs_tracker_download_cull(const visfs_tracker* ct, int32_t* applied, int32
         fund::Result res{};
         std::vector<uint8_t> h_mask(M), h_status(M);
         if (f->device) {
-            TK_HIP(t, hipSetDevice(f->dev));
-            TK_HIP(t, hipMemcpyAsync(&c, t->B.ctl, sizeof(Ctl), hipMemcpyDeviceToHost, f->stream));
-            TK_HIP(t, hipMemcpyAsync(&hd, C.head, sizeof(hd), hipMemcpyDeviceToHost, f->stream));
-            TK_HIP(t, hipMemcpyAsync(&res, C.res, sizeof(res), hipMemcpyDeviceToHost, f->stream));
-            TK_HIP(t, hipMemcpyAsync(h_mask.data(), C.mask, M, hipMemcpyDeviceToHost, f->stream));
-            TK_HIP(t, hipMemcpyAsync(h_status.data(), C.status, M, hipMemcpyDeviceToHost, f->stream));
-            TK_HIP(t, hipStreamSynchronize(f->stream));
+            HIP_TRY(t, hipSetDevice(f->dev));
+            HIP_TRY(t, hipMemcpyAsync(&c, t->B.ctl, sizeof(Ctl), hipMemcpyDeviceToHost, f->stream));
+            HIP_TRY(t, hipMemcpyAsync(&hd, C.head, sizeof(hd), hipMemcpyDeviceToHost, f->stream));
+            HIP_TRY(t, hipMemcpyAsync(&res, C.res, sizeof(res), hipMemcpyDeviceToHost, f->stream));
+            HIP_TRY(t, hipMemcpyAsync(h_mask.data(), C.mask, M, hipMemcpyDeviceToHost, f->stream));
+            HIP_TRY(t, hipMemcpyAsync(h_status.data(), C.status, M, hipMemcpyDeviceToHost, f->stream));
+            HIP_TRY(t, hipStreamSynchronize(f->stream));
         } else {
             c = *t->B.ctl; hd = *C.head; res = *C.res;
             std::memcpy(h_mask.data(), C.mask, M); std::memcpy(h_status.data(), C.status, M);
@@ -1577,7 +1560,7 @@ int visfs_tracker_pnp_abi_version(void) { return VISFS_TRACKER_PNP_ABI_VERSION; 
 
 int visfs_tracker_enable_pnp(visfs_tracker* t, const visfs_pnp_params* p) {
     if (!t) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded_tk(t, [&]() -> int {
+    return guarded(t, [&]() -> int {
         visfs_flow* f = t->f;
         if (!f) return fail(t, VISFS_BA_ERR_NOT_LOADED, "the flow object of this tracker is gone");
         if (t->group) return fail(t, VISFS_BA_ERR_BAD_ARGUMENT, "the tracker is in a group: set the pose guess first, then create the group");
@@ -1599,8 +1582,8 @@ int visfs_tracker_enable_pnp(visfs_tracker* t, const visfs_pnp_params* p) {
                 if (rc_h != VISFS_BA_OK) return fail(t, rc_h, "the host solver of the pose guess could not be created");
             }
         } else {
-            TK_HIP(t, hipSetDevice(f->dev));
-            TK_HIP(t, hipStreamSynchronize(f->stream));                // nothing reads the blocks that go
+            HIP_TRY(t, hipSetDevice(f->dev));
+            HIP_TRY(t, hipStreamSynchronize(f->stream));                // nothing reads the blocks that go
             t->pnp_on = false;
             // the state of the two stages; then the output block again, with the pose guess's part behind what it holds today
             Carver c{ nullptr };
@@ -1666,7 +1649,7 @@ int visfs_tracker_download_pnp(const visfs_tracker* ct, int32_t* m, int32_t* n_h
                                float* pass_threshold, int32_t* pass_count, int32_t* pass_inliers) {
     visfs_tracker* t = const_cast<visfs_tracker*>(ct);
     if (!t) return VISFS_BA_ERR_BAD_ARGUMENT;
-    return guarded_tk(t, [&]() -> int {
+    return guarded(t, [&]() -> int {
         if (!t->f) return fail(t, VISFS_BA_ERR_NOT_LOADED, "the flow object of this tracker is gone");
         if (!t->have_call) return fail(t, VISFS_BA_ERR_NOT_LOADED, "no call to report on");
         if (m) *m = 0;
@@ -1695,17 +1678,17 @@ int visfs_tracker_download_pnp(const visfs_tracker* ct, int32_t* m, int32_t* n_h
         std::vector<int32_t> h_samples(4 * H), h_vc(2 * H), h_pcnt(pnp::kMaxRefine), h_plists(R * cap);
         std::vector<double> h_models(12 * H), h_ptq(7 * pnp::kMaxRefine);
         std::vector<float> h_pthr(pnp::kMaxRefine);
-        TK_HIP(t, hipSetDevice(f->dev));
-        TK_HIP(t, hipMemcpyAsync(h_samples.data(), q.samples, 16 * H, hipMemcpyDeviceToHost, f->stream));
-        TK_HIP(t, hipMemcpyAsync(h_vc.data(), q.vc, 8 * H, hipMemcpyDeviceToHost, f->stream));
-        TK_HIP(t, hipMemcpyAsync(h_models.data(), q.models, 96 * H, hipMemcpyDeviceToHost, f->stream));
+        HIP_TRY(t, hipSetDevice(f->dev));
+        HIP_TRY(t, hipMemcpyAsync(h_samples.data(), q.samples, 16 * H, hipMemcpyDeviceToHost, f->stream));
+        HIP_TRY(t, hipMemcpyAsync(h_vc.data(), q.vc, 8 * H, hipMemcpyDeviceToHost, f->stream));
+        HIP_TRY(t, hipMemcpyAsync(h_models.data(), q.models, 96 * H, hipMemcpyDeviceToHost, f->stream));
         if (R > 0) {
-            TK_HIP(t, hipMemcpyAsync(h_ptq.data(), q.pass_tq, 56 * R, hipMemcpyDeviceToHost, f->stream));
-            TK_HIP(t, hipMemcpyAsync(h_pthr.data(), q.pass_thr, 4 * R, hipMemcpyDeviceToHost, f->stream));
-            TK_HIP(t, hipMemcpyAsync(h_pcnt.data(), q.pass_cnt, 4 * R, hipMemcpyDeviceToHost, f->stream));
-            TK_HIP(t, hipMemcpyAsync(h_plists.data(), q.pass_lists, 4 * R * cap, hipMemcpyDeviceToHost, f->stream));
+            HIP_TRY(t, hipMemcpyAsync(h_ptq.data(), q.pass_tq, 56 * R, hipMemcpyDeviceToHost, f->stream));
+            HIP_TRY(t, hipMemcpyAsync(h_pthr.data(), q.pass_thr, 4 * R, hipMemcpyDeviceToHost, f->stream));
+            HIP_TRY(t, hipMemcpyAsync(h_pcnt.data(), q.pass_cnt, 4 * R, hipMemcpyDeviceToHost, f->stream));
+            HIP_TRY(t, hipMemcpyAsync(h_plists.data(), q.pass_lists, 4 * R * cap, hipMemcpyDeviceToHost, f->stream));
         }
-        TK_HIP(t, hipStreamSynchronize(f->stream));
+        HIP_TRY(t, hipStreamSynchronize(f->stream));
         for (size_t h = 0; h < H; ++h) {
             if (samples) for (int k = 0; k < 4; ++k) samples[4 * h + k] = h_samples[4 * h + k];
             if (valid) valid[h] = h_vc[2 * h];
@@ -1841,11 +1824,7 @@ const char* visfs_tracker_group_last_error(const visfs_tracker_group* g) { retur
 
 int visfs_tracker_group_last_counts(const visfs_tracker_group* g, int32_t* kernel_launches, int32_t* copies_and_memsets,
                                     int32_t* synchronisations) {
-    if (!g) return VISFS_BA_ERR_BAD_ARGUMENT;
-    if (kernel_launches) *kernel_launches = g->cnt.kernels;
-    if (copies_and_memsets) *copies_and_memsets = g->cnt.copies;
-    if (synchronisations) *synchronisations = g->cnt.syncs;
-    return VISFS_BA_OK;
+    return g ? g->cnt.read(kernel_launches, copies_and_memsets, synchronisations) : (int)VISFS_BA_ERR_BAD_ARGUMENT;
 }
 
 int visfs_tracker_group_process(visfs_tracker_group* g, const visfs_tracker_frame* frames, visfs_tracker_result* results) {
