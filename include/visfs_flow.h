@@ -25,7 +25,7 @@ extern "C" {
 
 /* The Tracker keys (Parameters.h:148-157) and the two gates written into Tracker.cpp. */
 typedef struct visfs_flow_params {
-    int32_t win_size;           /* Tracker/FlowWinSize      (default 21; odd, 3 .. 21) */
+    int32_t win_size;           /* Tracker/FlowWinSize      (default 21; 3 .. 21 (even sizes allowed, as in calcOpticalFlowPyrLK)) */
     int32_t max_level;          /* Tracker/FlowMaxLevel     (default 3; 0 .. 7) */
     int32_t iterations;         /* Tracker/FlowIterations   (default 30) */
     float   eps;                /* Tracker/FlowEps          (default 0.01) */

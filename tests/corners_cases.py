@@ -4,6 +4,7 @@ import functools
 
 import numpy as np
 
+import clahe_cases
 import corners_oracle as co
 import flow_cases as fc
 
@@ -14,6 +15,45 @@ MAX_CORNERS = [300, 20]
 # The device sorts through LDS tiles of this many keys and selects in chunks of this many candidates: the "many candidates" inputs
 # must need several of each.
 DEVICE_TILE = 1024
+
+
+# The images at which k_corner_response's 32 x 8 tile with its 2-pixel apron meets both borders in one workgroup, and the parameter
+# values at which the selection takes another path.  name -> (width, height, corner keywords); the image is edge_image(width, height).
+EDGE_FLOW_PARAMS = dict(max_level=0, win_size=3)           # the flow object under them: 5 x 5 must be accepted
+
+
+def _edge():
+    out = {}
+    for tag, (w, h) in (("narrower_than_a_tile", (31, 7)), ("exactly_a_tile", (32, 8)), ("one_past_a_tile", (33, 9)), ("smallest", (5, 5))):
+        for md in (2.0, 0.0):
+            out[f"{tag}_{w}x{h}_md{md:g}"] = (w, h, dict(max_corners=100, quality_level=0.01, min_distance=md))
+    out["every_candidate_200x100"] = (200, 100, dict(max_corners=4096, quality_level=1e-6, min_distance=1.0))
+    out["one_corner_64x48"] = (64, 48, dict(max_corners=1, quality_level=0.01, min_distance=40.0))
+    out["quality_0.999_64x48"] = (64, 48, dict(max_corners=300, quality_level=0.999, min_distance=40.0))
+    out["quality_1.5_64x48"] = (64, 48, dict(max_corners=300, quality_level=1.5, min_distance=40.0))
+    return out
+
+
+EDGE = _edge()
+SMALL_TILE_CASES = [n for n in EDGE if n.split("_md")[0].endswith(("31x7", "32x8", "33x9"))]
+
+
+@functools.lru_cache(maxsize=None)
+def edge_image(width, height):
+    img = clahe_cases.image("texture", width, height, 3)
+    img.setflags(write=False)
+    return img
+
+
+@functools.lru_cache(maxsize=None)
+def edge_checked(name):
+    """The checker's result of an EDGE case: computed once, shared, never written to."""
+    w, h, kw = EDGE[name]
+    out = co.good_features(edge_image(w, h), kw["max_corners"], kw["quality_level"], kw["min_distance"])
+    for v in out.values():
+        if isinstance(v, np.ndarray):
+            v.setflags(write=False)
+    return out
 
 
 def tiled_image():

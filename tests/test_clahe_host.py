@@ -9,17 +9,17 @@ import clahe_oracle as co
 from visfs_amd import abi, backend, clahe, flow
 
 
-def _flow(w, h, solver=None):
-    return flow.Flow(flow.default_params(**cc.FLOW_PARAMS), w, h, solver=solver)
+def _flow(w, h, solver=None, params=cc.FLOW_PARAMS):
+    return flow.Flow(flow.default_params(**params), w, h, solver=solver)
 
 
 def _pushed(c):
-    f = _flow(c["w"], c["h"])
+    f = _flow(c["w"], c["h"], params=c["flow"])
     clahe.push_frame(f, clahe.default_params(**c["params"]), c["left"], c["right"])
     return f
 
 
-@pytest.mark.parametrize("name", cc.NAMES)
+@pytest.mark.parametrize("name", cc.NAMES + cc.EDGE_NAMES)
 def test_case_equals_the_checker(name):
     c = cc.case(name)
     assert not np.array_equal(c["left"], c["right"])
@@ -69,6 +69,26 @@ def test_cases_reach_every_branch_of_the_checker():
             assert e["ties"] >= (100 if (c["w"], c["h"]) in ((64, 48), (256, 128)) else 1), (c["name"], image, e["ties"])
 
 
+def test_edge_cases_have_the_geometry_their_names_state():
+    """On the checker's geometry alone: the tile widths around 256, the area that is no multiple of 4, one tile on an axis."""
+    geo = {c["tag"]: (c, cc.expected(c["name"], 0)["geometry"]) for c in cc.edge_cases()}
+    assert len(geo) == len(cc.EDGE) == 10
+    for tag, tile_w in cc.EDGE_TILE_W.items():
+        assert geo[tag][1]["tile_w"] == tile_w, tag
+    assert geo["tile_w_300_one_tile"][1]["tile_h"] == 40 and geo["tile_w_256"][1]["ext_w"] == 512
+    assert geo["tile_w_258_clip_40"][1]["clip"] == int(40.0 * 258 * 13 / 256.0) and geo["no_clip"][1]["clip"] == 0
+    c = geo["area_mod4_3"][0]
+    assert (c["w"] * c["h"]) % 4 == 3 and c["w"] % 4 != 0
+    assert (geo["tiles_32x32"][1]["tile_w"], geo["tiles_32x32"][1]["tile_h"]) == (2, 2)
+    assert (geo["width_tiles_plus_1"][1]["ext_w"], geo["width_tiles_plus_1"][1]["ext_h"]) == (16, 12)
+    assert (geo["narrowest"][1]["tile_w"], geo["narrowest"][1]["tile_h"]) == (2, 2)
+    assert (geo["one_tile"][1]["tile_w"], geo["one_tile"][1]["tile_h"]) == (5, 5)
+    for c, g in geo.values():                       # no case is an identity or a constant: the equalised image differs from the raw one
+        for image in (0, 1):
+            dst = cc.expected(c["name"], image)["dst"]
+            assert not np.array_equal(dst, c["right" if image else "left"]) and len(np.unique(dst)) > 4, c["name"]
+
+
 @pytest.mark.parametrize("name", ["texture_70x52_c3_t8x8", "noise_256x128_c3_t4x2"])
 def test_pyramids_and_derivatives_follow_the_equalised_image(name):
     c = cc.case(name)
@@ -94,7 +114,7 @@ def test_slots_rotate_as_with_push_frame():
 
 
 def test_every_table_is_monotone_and_ends_at_255():
-    for c in cc.cases():
+    for c in cc.cases() + cc.edge_cases():
         f = _pushed(c)
         for image in (0, 1):
             st = clahe.download(f, image)

@@ -10,9 +10,9 @@ import flow_cases as fc
 from visfs_amd import abi, backend, corners, flow
 
 
-def _twin(img):
+def _twin(img, **flow_kw):
     h, w = img.shape
-    f = flow.Flow(flow.default_params(), w, h)
+    f = flow.Flow(flow.default_params(**flow_kw), w, h)
     f.push_frame(img, img)
     return f
 
@@ -120,6 +120,27 @@ def test_many_candidates():
         want = co.good_features(img, mc, 0.01, md)
         assert want["n_candidates"] == 23888 and want["n_candidates"] > 4 * cc.DEVICE_TILE
         _compare(f, want, max_corners=mc, min_distance=md)
+    f.close()
+
+
+@pytest.mark.parametrize("name", list(cc.EDGE))
+def test_edge_case_equals_the_checker(name):
+    """Images narrower and lower than the device's 32 x 8 response tile, exactly one tile, one pixel past it and the smallest a flow
+    object accepts; every candidate wanted, one corner wanted, and thresholds no response passes.  The checker gives 4 / 5 / 6
+    corners at 31 x 7 / 32 x 8 / 33 x 9 (none at 5 x 5, whose interior is 3 x 3), 384 at 200 x 100 and 1 of 64 candidates at 64 x 48."""
+    w, h, kw = cc.EDGE[name]
+    want = cc.edge_checked(name)
+    print(f"{name}: the checker has {want['n_candidates']} candidates and returns {len(want['xy'])}")
+    if name in cc.SMALL_TILE_CASES:
+        assert len(want["xy"]) >= 4
+    if name.startswith("every_candidate"):
+        assert len(want["xy"]) == want["n_candidates"] == 384
+    if name.startswith("one_corner"):
+        assert len(want["xy"]) == 1 and want["n_candidates"] > 1 and not want["exhausted"]
+    if name.startswith("quality"):
+        assert want["n_candidates"] == 0 and len(want["xy"]) == 0 and want["max_val"] > 0
+    f = _twin(cc.edge_image(w, h), **cc.EDGE_FLOW_PARAMS)
+    _compare(f, want, **kw)
     f.close()
 
 

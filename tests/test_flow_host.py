@@ -88,6 +88,49 @@ def test_track_and_stereo_equal_the_checker(name):
     f.close()
 
 
+@pytest.mark.parametrize("name", list(fc.EDGE_CASES))
+def test_edge_case_equals_the_checker(name):
+    """The window sizes, pyramid depths, image sizes and iteration limits of fc.EDGE_CASES: track without and with a guess, and
+    stereo.  What the checker alone keeps and drops is printed and held to the case's `need`, so that no case compares two empty
+    outcomes; smallest_5x5_win_3 keeps nothing and smallest_23x23_win_21 keeps nothing in stereo: bytes only there."""
+    c = fc.edge_case(name)
+    f, o = _twin(c["width"], c["height"], **c["prm"]), _checker(c["width"], c["height"], **c["prm"])
+    for pair in c["frames"]:
+        f.push_frame(*pair)
+        o.push_frame(*pair)
+    for guess, what in ((None, "track"), (c["guess"], "track from a guess")):
+        to, st, err = f.track(c["pts"], guess)
+        with np.errstate(invalid="ignore"):            # the checker's round-trip distance of the row that is inf
+            to_o, st_o, err_o = o.track(c["pts"], guess)
+        fc.check_not_vacuous(name, st_o, what)
+        assert st.tobytes() == st_o.tobytes(), what
+        assert to.tobytes() == to_o.tobytes(), what
+        assert err.tobytes() == err_o.tobytes(), what
+    rt, st2, xyz = f.stereo(c["pts"], flow.camera(baseline=fc.EDGE_BASELINE))
+    with np.errstate(invalid="ignore"):
+        rt_o, st2_o, xyz_o = o.stereo(c["pts"], fo.Camera(baseline=fc.EDGE_BASELINE))
+    print(f"{name} stereo: the checker keeps {int(st2_o.sum())} of {len(st2_o)}, {int(np.isfinite(xyz_o[:, 0]).sum())} with a depth")
+    assert st2.tobytes() == st2_o.tobytes()
+    assert rt.tobytes() == rt_o.tobytes()
+    assert xyz.tobytes() == xyz_o.tobytes()
+    assert np.isnan(xyz[st2 == 0]).all()
+    f.close()
+
+
+def test_edge_pyramid_of_eight_levels_equals_the_checker():
+    c = fc.edge_case("levels_8_top_5x5")
+    f, o = _twin(c["width"], c["height"], **c["prm"]), _checker(c["width"], c["height"], **c["prm"])
+    f.push_frame(*c["frames"][1])
+    o.push_frame(*c["frames"][1])
+    assert f.level_size(7) == (5, 5)
+    for image in (flow.IMAGE_LEFT, flow.IMAGE_RIGHT):
+        for level in range(8):
+            px, der = f.download_level(flow.SLOT_CURRENT, image, level)
+            assert px.tobytes() == o.cur[image][level][0].tobytes(), (image, level)
+            assert der.tobytes() == o.cur[image][level][1].tobytes(), (image, level)
+    f.close()
+
+
 def test_triangulation_known_answers():
     """projectDisparityTo3D: zero and negative disparity give NaN; c = cx_right - cx only when both are positive; depth must lie in
     (0.2, 10.0]."""
@@ -218,11 +261,15 @@ def test_argument_checks():
     lib = flow.load()
     h = C.c_void_p()
     for kw, rc in ((dict(win_size=23), abi.ERR_UNSUPPORTED), (dict(max_level=8), abi.ERR_UNSUPPORTED), (dict(iterations=-1), abi.ERR_BAD_ARGUMENT),
-                   (dict(eps=float("nan")), abi.ERR_BAD_ARGUMENT)):
+                   (dict(eps=float("nan")), abi.ERR_BAD_ARGUMENT), (dict(win_size=2), abi.ERR_UNSUPPORTED)):
         p = flow.default_params(**kw)
         assert lib.visfs_flow_create_host(C.byref(p), 752, 480, C.byref(h)) == rc, kw
     p = flow.default_params()
     assert lib.visfs_flow_create_host(C.byref(p), 120, 100, C.byref(h)) == abi.ERR_BAD_ARGUMENT      # top level 15 x 13 < window
+    p = flow.default_params(win_size=3, max_level=0)
+    assert lib.visfs_flow_create_host(C.byref(p), 4, 4, C.byref(h)) == abi.ERR_BAD_ARGUMENT          # smaller than win_size + 2
+    _twin(5, 5, win_size=3, max_level=0).close()                                                      # exactly win_size + 2: created
+    _twin(752, 480, win_size=4).close()                                                               # an even window: created
     f = _twin(320, 240)
     with pytest.raises(backend.BackendError):
         f.stereo([[10.0, 10.0]], flow.camera())                                                       # no frame yet

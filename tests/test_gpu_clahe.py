@@ -29,14 +29,14 @@ def _same_state(dev, host, levels):
             assert pa[1].tobytes() == pb[1].tobytes(), (image, level)
 
 
-@pytest.mark.parametrize("name", cc.NAMES)
+@pytest.mark.parametrize("name", cc.NAMES + cc.EDGE_NAMES)
 def test_case_equals_the_host_twin(solver, name):
     c = cc.case(name)
-    prm = flow.default_params(**cc.FLOW_PARAMS)
+    prm = flow.default_params(**c["flow"])
     dev, host = flow.Flow(prm, c["w"], c["h"], solver=solver), flow.Flow(prm, c["w"], c["h"])
     for f in (dev, host):
         clahe.push_frame(f, clahe.default_params(**c["params"]), c["left"], c["right"])
-    _same_state(dev, host, cc.FLOW_PARAMS["max_level"] + 1)
+    _same_state(dev, host, c["flow"]["max_level"] + 1)
     # the checker's bytes as well: the host tests pin the twin to them, this pins the device without the detour
     for image in (0, 1):
         assert dev.download_level(flow.SLOT_CURRENT, image, 0)[0].tobytes() == cc.expected(name, image)["dst"].tobytes()

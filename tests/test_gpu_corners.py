@@ -19,9 +19,9 @@ def solver():
     s.close()
 
 
-def _pair(img, solver):
+def _pair(img, solver, **flow_kw):
     h, w = img.shape
-    dev, host = flow.Flow(flow.default_params(), w, h, solver=solver), flow.Flow(flow.default_params(), w, h)
+    dev, host = flow.Flow(flow.default_params(**flow_kw), w, h, solver=solver), flow.Flow(flow.default_params(**flow_kw), w, h)
     dev.push_frame(img, img)
     host.push_frame(img, img)
     return dev, host
@@ -50,6 +50,19 @@ def test_base_image_equals_the_host_twin(solver, size):
             counts.add(len(got) == mc)
             assert st["n_candidates"] > cc.DEVICE_TILE
     assert counts == {True, False}
+    dev.close(); host.close()
+
+
+@pytest.mark.parametrize("name", list(cc.EDGE))
+def test_edge_case_equals_the_host_twin(solver, name):
+    """cc.EDGE on the device: both image borders inside one workgroup of the response kernel, and the selection's other paths.
+    tests/test_corners_host.py holds the twin to the checker on the same inputs and states what the checker returns."""
+    w, h, kw = cc.EDGE[name]
+    dev, host = _pair(cc.edge_image(w, h), solver, **cc.EDGE_FLOW_PARAMS)
+    got, st = _same_call(dev, host, **kw)
+    want = cc.edge_checked(name)
+    assert got.tobytes() == want["xy"].tobytes() and st["n_candidates"] == want["n_candidates"]
+    assert st["eig"].tobytes() == want["eig"].tobytes()
     dev.close(); host.close()
 
 

@@ -58,6 +58,34 @@ def test_device_track_and_stereo_equal_the_host_twin(solver, name):
     dev.close(); host.close()
 
 
+@pytest.mark.parametrize("name", list(fc.EDGE_CASES))
+def test_device_edge_case_equals_the_host_twin(solver, name):
+    """fc.EDGE_CASES on the device: the slot occupancies of the wavefront's window cells, 0 / 255 images under the int32 partial sums,
+    the 8-level layout, the smallest images and the iteration limits.  tests/test_flow_host.py holds the twin to the checker on the
+    same inputs and the checker's counts to the case's `need`."""
+    c = fc.edge_case(name)
+    p = flow.default_params(**c["prm"])
+    dev, host = flow.Flow(p, c["width"], c["height"], solver=solver), flow.Flow(p, c["width"], c["height"])
+    for pair in c["frames"]:
+        dev.push_frame(*pair)
+        host.push_frame(*pair)
+    if c["prm"]["max_level"] == 7:
+        for slot in (flow.SLOT_PREVIOUS, flow.SLOT_CURRENT):
+            for image in (flow.IMAGE_LEFT, flow.IMAGE_RIGHT):
+                for level in range(8):
+                    assert _same(dev.download_level(slot, image, level), host.download_level(slot, image, level)), (slot, image, level)
+    for guess in (None, c["guess"]):
+        got, want = dev.track(c["pts"], guess), host.track(c["pts"], guess)
+        print(f"{name} track{' from a guess' if guess is not None else ''}: the twin keeps {int(want[1].sum())} of {len(want[1])}")
+        assert got[1].tobytes() == want[1].tobytes()
+        assert _same(got, want)
+    cam = flow.camera(baseline=fc.EDGE_BASELINE)
+    got, want = dev.stereo(c["pts"], cam), host.stereo(c["pts"], cam)
+    assert got[1].tobytes() == want[1].tobytes()
+    assert _same(got, want)
+    dev.close(); host.close()
+
+
 def test_slot_rotation_over_twenty_frames(solver):
     frames = fc.sequence(20)
     h, w = frames[0][0].shape

@@ -45,6 +45,14 @@ def test_wave_boundary_counts_equal_the_host_twin(solver, name):
     assert max(len(r["covisible_id"]) for r, _ in log) >= scn["trk"]["max_features"] - 8
 
 
+@pytest.mark.parametrize("name", list(tc.WINDOW))
+def test_window_sizes_equal_the_host_twin(solver, name):
+    """tc.WINDOW on the device: the slot occupancies of the tracker's own copy of the wavefront's window cells."""
+    log = _run(tc.WINDOW[name](), solver, name)
+    assert log[1][0]["flags"] == to.BOOTSTRAPPED
+    assert all(not (r["flags"] & to.LOST) for r, _ in log[2:]) and min(len(r["word_id"]) for r, _ in log[2:]) >= 40
+
+
 @pytest.mark.parametrize("case", ["blocked_bootstrap", "bootstrap_nan", "lost_case", "no_top_up", "empty_top_up"])
 def test_special_frames_equal_the_host_twin(solver, case):
     log = _run(getattr(tc, case)(), solver, case)

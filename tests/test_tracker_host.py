@@ -41,6 +41,17 @@ def test_wave_boundary_counts_equal_the_checker(name):
     assert max(len(r["covisible_id"]) for r, _ in log) >= scn["trk"]["max_features"] - 8      # the rows do reach the boundary
 
 
+@pytest.mark.parametrize("name", list(tc.WINDOW))
+def test_window_sizes_equal_the_checker(name):
+    """Window sizes other than 21 through the whole front end.  Every scenario bootstraps on frame 1 and then tracks: frames 2-4
+    carry no LOST flag and at least 40 words on the checker, so the comparison is not one of empty lists."""
+    log, _ = _run(tc.WINDOW[name](), name)
+    words = [len(r["word_id"]) for r, _ in log]
+    print(f"{name}: flags {[int(r['flags']) for r, _ in log]}, words per frame {words}, covisible {[len(r['covisible_id']) for r, _ in log]}")
+    assert log[1][0]["flags"] == to.BOOTSTRAPPED
+    assert all(not (r["flags"] & to.LOST) for r, _ in log[2:]) and min(words[2:]) >= 40
+
+
 def test_bootstrap_and_its_quirk():
     scn = tc.scenario(tc.sequence(4), 60, 12)
     ref, sub = tc.checker(scn), tc.Subject(scn)

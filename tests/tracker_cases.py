@@ -136,6 +136,14 @@ def base_cases():
 
 BASE = base_cases()
 WAVE = {f"mf{mf}": functools.partial(scenario, sequence(6), mf, 12) for mf in (63, 64, 65, 129)}
+# k_trk_track_g and k_trk_stereo_g carry their own copy of the wavefront's window cells (7 slots of 64): window sizes that end one
+# row of cells past a slot boundary (9), exactly on one (8: 64 cells, 16: 256 cells) and inside slot 0 (3), at other pyramid depths
+WINDOW = {
+    "win_9_levels_3": functools.partial(scenario, sequence(5), 65, 12, win_size=9, max_level=2),
+    "win_8_levels_2": functools.partial(scenario, sequence(5), 65, 12, win_size=8, max_level=1),
+    "win_16_levels_3_back0": functools.partial(scenario, sequence(5), 65, 12, win_size=16, max_level=2, flow_back=0),
+    "win_3_levels_5": functools.partial(scenario, sequence(5), 65, 12, win_size=3, max_level=4),
+}
 
 
 def full_size():

@@ -76,6 +76,12 @@ __global__ __launch_bounds__(FL_T) void k_flow_scharr_g(const PyrRec* __restrict
 }
 
 // the window cells of one wavefront: cell s * 64 + lane in slot s, per-lane int32 partial sums, int64 butterfly
+//
+// Why int32 holds a lane's partial sum: the unnormalised Scharr of 8-bit pixels is at most (3 + 10 + 3) * 255 = 4080 in size, and
+// the bilinear weights sum to 2^14, so |gx|, |gy| <= 4080 after the descale (4081 with its rounding); a pixel sample keeps 5
+// fractional bits, 0 .. 8160, so |diff| <= 8160.  A lane adds kLaneSlots = 7 products: at most 7 * 4081^2 = 1.17e8 for the normal
+// matrix and 7 * 8160 * 4081 = 2.33e8 for the right-hand side, against 2^31 = 2.15e9.  The 0 / 255 images of
+// tests/flow_cases.py (saturated_*) run this on the device.
 struct WaveCells {
     static constexpr int kSlots = kLaneSlots;
     using acc_t = int32_t;

@@ -292,6 +292,8 @@ __global__ __launch_bounds__(TK_T) void k_trk_append_g(const TrkRec* __restrict_
 
 struct WaveCells {                             // as in ba_flow.hip: cell s * 64 + lane in slot s, int64 butterfly
     static constexpr int kSlots = kLaneSlots;
+    // int32 holds a lane's 7 products (derivation in ba_flow.hip): |gx|, |gy| <= 4081 and |diff| <= 8160 give at most
+    // 7 * 8160 * 4081 = 2.33e8, against 2^31
     using acc_t = int32_t;
     int lane;
     __device__ int cell(int s) const { return s * 64 + lane; }
