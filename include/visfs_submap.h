@@ -78,6 +78,10 @@ int  visfs_submaps_solve_window(visfs_ba_handle* h, const visfs_submaps* s, cons
 /* The cells of rayToPixelMask(begin, end, scale) from the per-column work items the kernels run, in the reference's order.
  * Returns the number of cells (written up to `cap`), or a negative VISFS_BA_* code. */
 int  visfs_submap_hook_ray(const int32_t begin[2], const int32_t end[2], int32_t scale, int32_t cap, int32_t* cells_xy);
+/* The same cells from the mark kernel's work items of the ray's record, sized as a batch sizes them (columns x chunks of 8 cells)
+ * and walked in item order.  *n_items: the number of work items.  Returns the number of cells, or a negative VISFS_BA_* code. */
+int  visfs_submap_hook_mark_items(const int32_t begin[2], const int32_t end[2], int32_t scale, int32_t cap, int32_t* cells_xy,
+                                  int64_t* n_items);
 /* computeLookupTableToApplyCorrespondenceCostOdds(odds) (32768 entries, each with the update marker). */
 int  visfs_submap_hook_odds_table(double odds, uint16_t* table);
 /* The value tables: correspondence cost of every value (0 = unknown -> max cost; 32768 doubles) and the crop's

@@ -1,11 +1,14 @@
-"""Laser sub-maps on the GPU (include/visfs_submap.h): the device grids against the host restatement byte for byte, and the
-laser window solved against the resident matching grid against the same window with the grid handed over from the host."""
+"""Laser sub-maps on the GPU (include/visfs_submap.h): the device grids against the host restatement byte for byte (a robot loop
+at workload size, and every case of tests/submap_cases.py: batches of 1 to 65 insertions, growth and life-cycle events inside a
+batch, the chunks of a column, the refusals), and the laser window solved against the resident matching grid against the same
+window with the grid handed over from the host."""
 import ctypes as C
 import math
 
 import numpy as np
 import pytest
 
+from test_submap_cases import CASES, check_known, check_not_finite, check_too_far, snapshot_of
 from visfs_amd import abi, backend, synth
 from visfs_amd import submap as sm
 
@@ -105,6 +108,104 @@ def test_empty_range_data_count_toward_the_limit():
     d = dev.describe()
     assert sum(x["num_range_data"] for x in d) > 0
     dev.close(); host.close(); s.close()
+
+
+# ---------------------------------------------------------------- the shared cases: batch, chunk, growth and life-cycle edges
+CASE_IDS = [c["name"] for c in CASES]
+_twin = {}
+
+
+@pytest.fixture(scope="module")
+def solver():
+    s = backend.Solver(abi.default_params())
+    yield s
+    s.close()
+
+
+@pytest.fixture
+def device_maps(solver):
+    """Device sub-maps on the shared solver, closed after the test whether it passed or not (before the solver goes)."""
+    made = []
+
+    def make(**params):
+        made.append(sm.Submaps(sm.default_params(**params), solver=solver))
+        return made[-1]
+
+    yield make
+    for m in made:
+        m.close()
+
+
+def twin_states(case):
+    """The twin's (describe, [(cells, mirror)]) after every call of the case, computed once and shared."""
+    if case["name"] not in _twin:
+        host = sm.Submaps(sm.default_params(**case["params"]))
+        states = []
+        for T, rds in case["calls"]:
+            assert host.insert(T, rds) == abi.OK
+            d = host.describe()
+            states.append((d, [host.download(i) for i in range(len(d))]))
+        host.close()
+        _twin[case["name"]] = states
+    return _twin[case["name"]]
+
+
+def compare_state(dev, state):
+    d, grids = state
+    assert dev.describe() == d
+    for i, (ch, fh) in enumerate(grids):
+        cd, fd = dev.download(i)
+        assert np.array_equal(cd, ch), i
+        assert fd.tobytes() == fh.tobytes(), i
+
+
+@pytest.mark.parametrize("case", CASES, ids=CASE_IDS)
+def test_case_on_device_equals_the_twin_after_every_call(device_maps, case):
+    dev = device_maps(**case["params"])
+    for (T, rds), state in zip(case["calls"], twin_states(case)):
+        assert dev.insert(T, rds) == abi.OK, dev.last_error()
+        compare_state(dev, state)
+    check_known(case, dev)
+
+
+@pytest.mark.parametrize("case", CASES, ids=CASE_IDS)
+def test_case_on_device_downloaded_at_the_end_only(device_maps, case):
+    """No download (and so no synchronisation) between the calls: each call stages its records with the last ones in flight."""
+    dev = device_maps(**case["params"])
+    for T, rds in case["calls"]:
+        assert dev.insert(T, rds) == abi.OK, dev.last_error()
+    compare_state(dev, twin_states(case)[-1])
+    check_known(case, dev)
+
+
+@pytest.mark.parametrize("k", range(len(CASES)), ids=CASE_IDS)
+def test_two_device_objects_interleaved_on_one_solver(device_maps, k):
+    """Case k and the next one, their calls taken in turn on two objects of one solver (one stream)."""
+    pair = [CASES[k], CASES[(k + 1) % len(CASES)]]
+    devs = [device_maps(**c["params"]) for c in pair]
+    for j in range(max(len(c["calls"]) for c in pair)):
+        for c, dev in zip(pair, devs):
+            if j < len(c["calls"]):
+                assert dev.insert(*c["calls"][j]) == abi.OK, dev.last_error()
+    for c, dev in zip(pair, devs):
+        compare_state(dev, twin_states(c)[-1])
+        check_known(c, dev)
+
+
+def test_growth_beyond_the_cell_limit_is_refused_on_device_as_on_the_twin(device_maps):
+    dev = device_maps()
+    host = sm.Submaps(sm.default_params())
+
+    def reference(T, rds):
+        assert host.insert(T, rds) == abi.OK
+
+    check_too_far(dev, lambda: compare(dev, host), reference)
+    host.close()
+
+
+def test_a_return_that_is_not_finite_changes_nothing_on_device(device_maps):
+    dev = device_maps()
+    check_not_finite(dev, lambda: snapshot_of(dev))
 
 
 def _laser_window(with_visual, seed=0):

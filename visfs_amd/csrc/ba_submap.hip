@@ -199,18 +199,13 @@ __global__ __launch_bounds__(SM_T) void k_submap_mark(const MarkRec* __restrict_
         if (x >= 0 && y >= 0 && x < nx && y < ny) atomicOr(A.hit[s] + (int64_t)y * nx + x, bit);
         return;
     }
-    const int32_t local = t - r.base;
-    const int32_t j = local / r.nchunk, q = local - j * r.nchunk;
-    int32_t x, y0, y1, st;
-    ray_column(Ray{ r.bx, r.by, r.ex, r.ey }, j, x, y0, y1, st);
-    const int32_t n = (y1 - y0) * st + 1;
-    const int32_t a = q * kCellsPerItem;
-    if (a >= n) return;
-    const int32_t b = min(n, a + kCellsPerItem);
+    int32_t x, y0, st;
+    const int32_t n = ray_item(Ray{ r.bx, r.by, r.ex, r.ey }, r.nchunk, t - r.base, x, y0, st);
+    if (n == 0) return;
     x += r.ox;
     if (x < 0 || x >= nx) return;
     uint32_t* m = A.miss[s];
-    for (int32_t k = a; k < b; ++k) {
+    for (int32_t k = 0; k < n; ++k) {
         const int32_t y = y0 + st * k + r.oy;
         if (y >= 0 && y < ny) atomicOr(m + (int64_t)y * nx + x, bit);
     }
@@ -367,7 +362,7 @@ int flush_batch(visfs_submaps* s) {
         r.base = (int32_t)total;
         if (r.flags & 64u) { r.nchunk = 1; total += 1; continue; }
         const Ray ray{ r.bx, r.by, r.ex, r.ey };
-        r.nchunk = (ray_max_span(ray) + kCellsPerItem - 1) / kCellsPerItem;
+        r.nchunk = ray_nchunk(ray);
         total += (int64_t)ray_columns(ray) * r.nchunk;
     }
     if (total >= ((int64_t)1 << 31)) return fail(s, VISFS_BA_ERR_UNSUPPORTED, "a batch of more than 2^31 work items");
@@ -730,6 +725,26 @@ int visfs_submap_hook_ray(const int32_t begin[2], const int32_t end[2], int32_t 
     int32_t n = 0;
     auto put = [&](int32_t x, int32_t y) { if (n < cap) { cells_xy[2 * n] = x; cells_xy[2 * n + 1] = y; } ++n; };
     ray_cells(ray_make(begin[0], begin[1], end[0], end[1]), put, scale);
+    return n;
+}
+
+int visfs_submap_hook_mark_items(const int32_t begin[2], const int32_t end[2], int32_t scale, int32_t cap, int32_t* cells_xy, int64_t* n_items) {
+    if (!begin || !end || !n_items || cap < 0 || (cap > 0 && !cells_xy)) return -VISFS_BA_ERR_BAD_ARGUMENT;
+    if (scale < 1 || scale > (1 << 20)) return -VISFS_BA_ERR_BAD_ARGUMENT;
+    const Ray r = ray_make(begin[0], begin[1], end[0], end[1]);
+    const int32_t nchunk = ray_nchunk(r, scale);                     // as flush_batch sizes the ray's record
+    const int64_t total = (int64_t)ray_columns(r, scale) * nchunk;
+    *n_items = total;
+    if (total >= ((int64_t)1 << 31)) return -VISFS_BA_ERR_UNSUPPORTED;
+    int32_t n = 0;
+    for (int32_t local = 0; local < (int32_t)total; ++local) {       // k_submap_mark's items of the record, in index order
+        int32_t x, y, st;
+        const int32_t cnt = ray_item(r, nchunk, local, x, y, st, scale);
+        for (int32_t k = 0; k < cnt; ++k) {
+            if (n < cap) { cells_xy[2 * n] = x; cells_xy[2 * n + 1] = y + st * k; }
+            ++n;
+        }
+    }
     return n;
 }
 

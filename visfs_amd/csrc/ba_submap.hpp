@@ -108,16 +108,17 @@ __host__ __device__ inline Ray ray_make(int32_t bx, int32_t by, int32_t ex, int3
 }
 __host__ __device__ inline int32_t ray_columns(const Ray& r, int S = kSubpixelScale) { return r.ex / S - r.bx / S + 1; }
 
-// Cells one column may hold, at most (sizes the work items of a column): exact for the vertical case; otherwise a column's share of
-// the y travel, |dy| / dx cells, plus the two partial cells at its ends.
+// Cells one column may hold, at most (sizes the work items of a column): exact for the vertical case; otherwise the smaller of two
+// upper bounds: a column's share of the y travel, |dy| / dx cells, plus the two partial cells at its ends, and the rows between the
+// ray's own end cells (a steep ray that crosses one column border has a huge |dy| / dx and a few tens of rows).
 __host__ __device__ inline int32_t ray_max_span(const Ray& r, int S = kSubpixelScale) {
-    if (r.bx / S == r.ex / S) {
-        const int32_t a = r.by / S, b = r.ey / S;
-        return (a > b ? a - b : b - a) + 1;
-    }
+    const int32_t a = r.by / S, b = r.ey / S;
+    const int64_t rows = (int64_t)(a > b ? a - b : b - a) + 1;
+    if (r.bx / S == r.ex / S) return (int32_t)rows;
     const int64_t dx = (int64_t)r.ex - r.bx, dy = (int64_t)r.ey - r.by;
     const int64_t ady = dy < 0 ? -dy : dy;
-    return (int32_t)(ady / dx + 2);
+    const int64_t slope = ady / dx + 2;
+    return (int32_t)(slope < rows ? slope : rows);
 }
 
 // Column j (0 .. ray_columns - 1) of the ray: its x and the first and last y in the reference's stepping order (step +1 or -1).
@@ -158,6 +159,23 @@ __host__ __device__ inline void ray_column(const Ray& r, int32_t j, int32_t& x, 
         if (end > start) end = start;
         y_first = y0 + (int32_t)start; y_last = y0 + (int32_t)end; step = -1;
     }
+}
+
+// Work items per column of the ray: chunks of kCellsPerItem cells that cover ray_max_span.
+__host__ __device__ inline int32_t ray_nchunk(const Ray& r, int S = kSubpixelScale) { return (ray_max_span(r, S) + kCellsPerItem - 1) / kCellsPerItem; }
+
+// Work item `local` (0 .. ray_columns * nchunk - 1) of the ray: column local / nchunk, chunk local % nchunk of it.  Returns the
+// number of cells the item holds (0: the chunk lies past the column's end), at (x, y + step * k), k = 0 .. count - 1.
+__host__ __device__ inline int32_t ray_item(const Ray& r, int32_t nchunk, int32_t local, int32_t& x, int32_t& y, int32_t& step,
+                                            int S = kSubpixelScale) {
+    const int32_t j = local / nchunk, q = local - j * nchunk;
+    int32_t y0, y1;
+    ray_column(r, j, x, y0, y1, step, S);
+    const int32_t n = (y1 - y0) * step + 1;
+    const int32_t a = q * kCellsPerItem;
+    if (a >= n) return 0;
+    y = y0 + step * a;
+    return (n < a + kCellsPerItem ? n : a + kCellsPerItem) - a;
 }
 
 // ---------------------------------------------------------------- device records of one batch

@@ -14,7 +14,7 @@ EXPORTS = [
     "visfs_submap_abi_version", "visfs_submap_default_params", "visfs_submaps_create", "visfs_submaps_create_host",
     "visfs_submaps_destroy", "visfs_submaps_last_error", "visfs_submaps_insert", "visfs_submaps_describe",
     "visfs_submaps_download", "visfs_submaps_solve_window", "visfs_submap_hook_ray", "visfs_submap_hook_odds_table",
-    "visfs_submap_hook_value_tables", "visfs_submap_hook_crop",
+    "visfs_submap_hook_value_tables", "visfs_submap_hook_crop", "visfs_submap_hook_mark_items",
 ]
 
 
@@ -69,6 +69,8 @@ def load():
     lib.visfs_submaps_solve_window.restype = C.c_int
     lib.visfs_submap_hook_ray.argtypes = [_pi32, _pi32, C.c_int32, C.c_int32, _pi32]
     lib.visfs_submap_hook_ray.restype = C.c_int
+    lib.visfs_submap_hook_mark_items.argtypes = [_pi32, _pi32, C.c_int32, C.c_int32, _pi32, C.POINTER(C.c_int64)]
+    lib.visfs_submap_hook_mark_items.restype = C.c_int
     lib.visfs_submap_hook_odds_table.argtypes = [C.c_double, _pu16]
     lib.visfs_submap_hook_odds_table.restype = C.c_int
     lib.visfs_submap_hook_value_tables.argtypes = [_pd, _pu16]
@@ -174,6 +176,19 @@ def hook_ray(begin, end, scale=1000):
     n2 = lib.visfs_submap_hook_ray(_ptr(b, C.c_int32), _ptr(e, C.c_int32), scale, n, _ptr(out, C.c_int32))
     assert n2 == n
     return [tuple(int(v) for v in c) for c in out[:n]]
+
+
+def hook_mark_items(begin, end, scale=1000):
+    """(cells, items): the ray's cells as the mark kernel's work items enumerate them, and the number of work items."""
+    lib = load()
+    b = np.asarray(begin, dtype=np.int32); e = np.asarray(end, dtype=np.int32)
+    items = C.c_int64()
+    n = lib.visfs_submap_hook_mark_items(_ptr(b, C.c_int32), _ptr(e, C.c_int32), scale, 0, None, C.byref(items))
+    assert n >= 0, n
+    out = np.zeros((max(n, 1), 2), dtype=np.int32)
+    n2 = lib.visfs_submap_hook_mark_items(_ptr(b, C.c_int32), _ptr(e, C.c_int32), scale, n, _ptr(out, C.c_int32), C.byref(items))
+    assert n2 == n
+    return [tuple(int(v) for v in c) for c in out[:n]], int(items.value)
 
 
 def hook_odds_table(odds):
