@@ -395,6 +395,11 @@ typedef struct visfs_ba_graph_info {
     int32_t schur_run_landmarks;
     int32_t landmark_partials;    /* ABI 10: workgroups of the landmark-major passes (k_linearize, k_backsub), each leaving one partial of every sum that
                                    * k_lin_finalize / k_ceres_lin_finalize, k_dogleg_mid and k_decide add up (DeviceGraph::n_lin_a) */
+    int32_t resets_skipped;       /* visfs_ba_optimize calls on this handle's resident workspace that launched no reset of their own, because the
+                                   * workspace was still exactly as visfs_ba_graph_reset or the upload's reset had left it (counted since the handle
+                                   * was created) */
+    int32_t state_mirrored;       /* state reads of such solves that enqueued no device-to-host copy: the last launch of the sequence had left the
+                                   * LM state in the host's pinned copy itself (counted likewise) */
 } visfs_ba_graph_info;
 /* GRAPH layer for a batch of independent windows (BASELINE config 5): n graphs resident side by side; one optimise call runs
  * them through ONE sequence of launches (blockIdx.y = window, each window gated by its own LM state).  Needs

@@ -67,6 +67,7 @@ struct Workspace {
     char* d_prim = nullptr;  size_t d_prim_cap = 0;   // the primary section (poses, landmarks, observations, odometry / laser measurements) ...
     char* h_prim = nullptr;  size_t h_prim_cap = 0;   // ... and its pinned staging arena: the window layer packs straight into it
     LmState* h_state = nullptr;                    // pinned
+    LmState* h_state_dev = nullptr;                // ... at its device address: the last launch of a lone window's sequence writes the state there itself
     LmState* d_state = nullptr;                    // the LM state at a FIXED device address (DeviceGraph::st): survives uploads
     DeviceGraph* d_graph = nullptr;                // the resident window's DeviceGraph at a fixed device address (re-written by every upload) ...
     DeviceGraph* h_graph = nullptr;                // ... and its pinned source
@@ -88,6 +89,16 @@ struct Workspace {
     int extra_units[2] = { 0, 0 };                 // rejected trials per phase of the previous solve: units enqueued on top of `half`
     bool small_solve = false;                      // reduced system <= 64 x 64: k_small_solve replaces k_schur_finalize + solver
     bool pristine = false;                         // the estimates are the uploaded ones (upload / reset, no optimise since): a solve can be re-run from its start
+    // the workspace is exactly as a k_reset left it (the upload's own, or visfs_ba_graph_reset's): nothing has been launched on its stream and
+    // nothing has written LmState or obs_level since.  reset_armed_iter / _gn: the max_iter and gauss_newton that reset armed.  A solve that
+    // would arm the same values skips its own k_reset(restore = 0), which would rewrite the very same state.  Set ONLY where a reset is
+    // launched; cleared by every other entry point that uses the workspace (reset_disarm).  Not `pristine`: that one speaks of the estimates
+    // alone and survives what this one must not (a stage hook leaves the estimates and changes the state).
+    bool reset_armed = false;
+    int reset_armed_iter = 0, reset_armed_gn = 0;
+    int resets_skipped = 0;                        // solves of this workspace that skipped their reset launch (visfs_ba_graph_info)
+    int state_mirrored = 0;                        // state reads of this workspace served by the phase end's own copy (no D2H copy enqueued)
+    uint32_t mirror_seq = 0;                       // LmState::mirror_seq as of the last state read: the next mirrored launch leaves this + 1
     bool direct_ready = false;                     // the structures of the direct solver exist although Optimizer/Solver=2: the fallback of a timed-out persistent PCG
     int solver_now = -1;                           // >= 0: the linear solver of the run in progress when it is not Optimizer/Solver (the fallback run: 0)
     // stage hooks on an Optimizer/Framework=1 handle
@@ -191,6 +202,10 @@ namespace {
 
 int bad(visfs_ba_handle* h, const char* msg) { h->err = msg; return VISFS_BA_ERR_BAD_ARGUMENT; }
 
+// An entry point other than a reset is about to launch on the resident workspace's stream or to write its LmState / obs_level: the workspace
+// is no longer "as a reset left it" (Workspace::reset_armed), so the next solve launches its own reset.
+void reset_disarm(visfs_ba_handle* h) { h->ws.reset_armed = false; }
+
 // Host threads for the O(N_obs) passes of a window solve: VISFS_BA_THREADS in total, 1 = none.  Default: the cores that share the
 // last-level cache with the calling thread (half its CPUs: SMT siblings do not help a streaming loop), at most 8 — the workers are kept
 // on that cache domain (worker_pool.hpp), so more threads than it has cores would only queue up; min(4, hardware threads) when the
@@ -229,6 +244,8 @@ int ws_init(visfs_ba_handle* h, Workspace& w) {
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking));
     HIP_TRY(h, hipHostMalloc(reinterpret_cast<void**>(&w.h_state), sizeof(LmState), hipHostMallocDefault));
+    std::memset(w.h_state, 0, sizeof(LmState));
+    HIP_TRY(h, hipHostGetDevicePointer(reinterpret_cast<void**>(&w.h_state_dev), w.h_state, 0));
     HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&w.d_state), sizeof(LmState)));
     HIP_TRY(h, hipMemset(w.d_state, 0, sizeof(LmState)));                       // (decide_epoch counts on from zero, across uploads)
     HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&w.d_graph), sizeof(DeviceGraph)));
@@ -377,6 +394,7 @@ size_t layout_dyn(Arena A, DeviceGraph& g, const UploadPlan& P, const DynOpts& o
     g.dxl = A.take<double>((size_t)std::max(Nl, 1) * 3);
     g.trial_part = A.take<double>((size_t)n_parts * 2);
     g.trial_gran = A.take<unsigned long long>((size_t)n_parts * 4);
+    g.eval_gran = A.take<unsigned long long>(((size_t)(No + 255) / 256 + 1) * 4);    // (inside the span the upload clears)
     g.fin_flag = A.take<uint32_t>((size_t)std::max(n_blk, 1));
     g.fin_cnt = A.take<uint32_t>((size_t)std::max(n_blk, 1));
     g.aux_part = A.take<double>((size_t)n_parts);
@@ -584,6 +602,7 @@ int ws_upload(visfs_ba_handle* h, Workspace& w, const visfs_ba_graph* gr, const 
     // through, NO graph is resident: a failed upload must not leave the previous graph's index structures marked usable over the
     // rejected graph's arrays (visfs_ba_optimize then returns VISFS_BA_ERR_NOT_LOADED instead of walking them).
     w.loaded = false;
+    w.reset_armed = false;
     PlanGraph G;
     size_t grid_cells = 0;
     int rc = validate_graph(h, gr, ceres, G, grid_cells);
@@ -653,6 +672,7 @@ int ws_upload(visfs_ba_handle* h, Workspace& w, const visfs_ba_graph* gr, const 
     launch_build_pairs(w.g, w.stream);                     // the co-observation pair lists never exist on the host
     launch_reset(w.g, ceres ? prm.iterations : prm.iterations / 2, prm.trust_region == 1, 1, w.stream);
     HIP_TRY(h, hipGetLastError());
+    w.reset_armed = true; w.reset_armed_iter = ceres ? prm.iterations : prm.iterations / 2; w.reset_armed_gn = prm.trust_region == 1 ? 1 : 0;
     lap("enqueue");
     // no synchronisation here: the launches that follow queue up behind the copies; the pinned staging arenas are only reused by the
     // NEXT upload, which drains the stream first
@@ -674,8 +694,33 @@ static OutputStage output_stage_of(const DeviceGraph& g) {
     return o;
 }
 
-int ws_read_state(visfs_ba_handle* h, Workspace& w) {
-    HIP_TRY(h, hipMemcpyAsync(w.h_state, w.g.st, sizeof(LmState), hipMemcpyDeviceToHost, w.stream));
+// mirrored: the sequence this read waits for ended in a phase end that left the state in h_state itself (launch_phase_end with a mirror):
+// no copy of the state is enqueued, only the outputs' (want_outputs) and the synchronisation remain.
+// The mirror's last word carries LmState::mirror_seq, written behind a system-scope fence (phase_decider): when nothing else has to come back,
+// the host waits for that count in the pinned copy itself instead of for the stream — the completion signal of a stream whose last command
+// is a kernel reaches the host ~30 us later than the copy's used to (profiles/pe_*: 40 -> 69 us between the last kernel of a step and the
+// first of the next), which would give back more than the removed launches bought.  The wait is bounded: after STATE_POLL_US of polling
+// (a long solve, or a launch that never ran) it falls back to the synchronisation, and to the copy if the mirror still has not arrived.
+// VISFS_BA_STATE_POLL=0: always synchronise (A/B runs, tests of that path).
+constexpr int STATE_POLL_US = 20000;
+static inline uint32_t mirror_seq_of(const LmState* st) {
+    const uint64_t v = __atomic_load_n(reinterpret_cast<const uint64_t*>(&st->phase_epoch), __ATOMIC_ACQUIRE);
+    return (uint32_t)(v >> 32);
+}
+int ws_read_state(visfs_ba_handle* h, Workspace& w, const bool mirrored = false) {
+    const int poll_mode = env_int("VISFS_BA_STATE_POLL", 1);          // (read per call: tests switch it)
+    const uint32_t want_seq = w.mirror_seq + 1u;
+    if (mirrored && poll_mode != 0 && !w.want_outputs && w.recs.empty()) {
+        const auto t0 = std::chrono::steady_clock::now();
+        for (int spin = 1;; ++spin) {
+            if (mirror_seq_of(w.h_state) == want_seq) { w.outputs_staged = false; w.mirror_seq = want_seq; w.state_mirrored += 1; return VISFS_BA_OK; }
+#if defined(__x86_64__) || defined(__i386__)
+            __builtin_ia32_pause();
+#endif
+            if ((spin & 1023) == 0 && std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count() > STATE_POLL_US) break;
+        }
+    }
+    if (!mirrored) HIP_TRY(h, hipMemcpyAsync(w.h_state, w.g.st, sizeof(LmState), hipMemcpyDeviceToHost, w.stream));
     w.outputs_staged = false;
     const OutputStage os = output_stage_of(w.g);
     // (the arena is also the source of the upload's H2D copy: that copy precedes these on the same stream, so it has read its data)
@@ -700,6 +745,14 @@ int ws_read_state(visfs_ba_handle* h, Workspace& w) {
         }
     }
     HIP_TRY(h, hipStreamSynchronize(w.stream));
+    if (mirrored) {
+        if (mirror_seq_of(w.h_state) == want_seq) w.state_mirrored += 1;
+        else {                                            // (never expected: the sequence did not end in a mirroring launch after all)
+            HIP_TRY(h, hipMemcpyAsync(w.h_state, w.g.st, sizeof(LmState), hipMemcpyDeviceToHost, w.stream));
+            HIP_TRY(h, hipStreamSynchronize(w.stream));
+        }
+    }
+    w.mirror_seq = w.h_state->mirror_seq;
     w.outputs_staged = with_outputs;
     if (!w.recs.empty()) prof_harvest(w);
     return VISFS_BA_OK;
@@ -842,7 +895,11 @@ int ws_optimize_run(visfs_ba_handle* h, Workspace& w, visfs_ba_stats* stats, con
     PcgLease pcg_lease;                                                                         // persistent PCG: co-residency budget of the device
     if (solver == 2 && !w.small_solve && !w.fused && !w.g.pcg_cu) pcg_lease.acquire(h->device, pcg_wave_cost(dims_of(w.g), 1));
     // a fresh optimizer per call (Optimizer.cpp:75): all edges level 0, LM state re-armed, estimates kept
-    const bool reset_launched = !fallback_run && !(fresh_upload && w.solves_since_upload == 0);
+    // (the reset is also skipped when the workspace is provably as a reset armed with the same values left it: Workspace::reset_armed)
+    const bool reset_standing = w.reset_armed && !fallback_run && !w.batch_member && w.reset_armed_iter == half && w.reset_armed_gn == (h->prm.trust_region == 1 ? 1 : 0);
+    w.reset_armed = false;
+    const bool reset_launched = !fallback_run && !(fresh_upload && w.solves_since_upload == 0) && !reset_standing;
+    if (reset_standing && !(fresh_upload && w.solves_since_upload == 0)) w.resets_skipped += 1;
     if (reset_launched) { ProfScope p(w, VISFS_BA_K_RESET); launch_reset(w.g, half, h->prm.trust_region == 1, 0, w.stream); }
     if (w.fused) {
         // small window: both phases, the outlier pass and the final evaluation in one launch of one workgroup
@@ -878,6 +935,12 @@ int ws_optimize_run(visfs_ba_handle* h, Workspace& w, visfs_ba_stats* stats, con
                           (h->prm.framework == 0 || w.small_solve || band_direct) && (solver == 2 || w.small_solve || band_direct) && !(w.spec && !w.spec_fused) &&
                           w.g.Np <= MAX_STAGED_POSES && w.g.Npf <= MAX_PCG_ONE_ROW_POSES && !w.g.pcg_cu;
     const LaunchDims fd = ref_mode ? dims_class(dims_of(w.g)) : LaunchDims{};
+    // A lone window on the by-value path closes its phases on board the k_eval launch (k_eval<DEC>: one launch instead of two), and the
+    // phase-2 end — the last launch of EVERY sequence enqueued below — leaves the state in the pinned h_state itself, so the read behind it
+    // enqueues no copy.  VISFS_BA_PHASE_ON_BOARD=0: k_eval + k_phase_end and the copy, as the batched and fixed-address paths (A/B runs).
+    static const int phase_board_mode = env_int("VISFS_BA_PHASE_ON_BOARD", 1);
+    const bool phase_on_board = phase_board_mode != 0 && !ref_mode && !w.batch_member;
+    LmState* const state_mirror = (phase_on_board && !w.prof_mask) ? w.h_state_dev : nullptr;   // (profiling runs keep the copy)
     auto enqueue_units = [&](int n, bool first) {
         for (int u = 0; u < n; ++u) {
             if (ref_mode) launch_unit_batch(w.d_graph, 1, fd, first, w.small_solve, solver, w.fused_decide, w.spec_fused, w.stream, w.d_state);
@@ -892,8 +955,8 @@ int ws_optimize_run(visfs_ba_handle* h, Workspace& w, visfs_ba_stats* stats, con
             return;
         }
         ProfScope p(w, VISFS_BA_K_PHASE_END);
-        if (which == 0) launch_phase_end(w.g, 0, 1, half2, w.stream);                               // :270-303
-        else launch_phase_end(w.g, 1, 0, 0, w.stream);                                              // :315-318
+        if (which == 0) launch_phase_end(w.g, 0, 1, half2, w.stream, phase_on_board);               // :270-303
+        else launch_phase_end(w.g, 1, 0, 0, w.stream, phase_on_board, state_mirror);                // :315-318
     };
     // (a window that rejected trials last time — an estimator's consecutive frames behave alike — gets that many units more up
     // front: a gated no-op unit costs ~7 us, the state read it saves ~25 us plus the bubble behind it)
@@ -979,7 +1042,7 @@ int ws_optimize_run(visfs_ba_handle* h, Workspace& w, visfs_ba_stats* stats, con
     int rc = VISFS_BA_OK;
     for (int guard = 0;; ++guard) {
         HIP_TRY(h, hipGetLastError());
-        rc = ws_read_state(h, w);
+        rc = ws_read_state(h, w, state_mirror != nullptr);
         if (rc != VISFS_BA_OK) return rc;
         const LmState& st = *w.h_state;
         if (st.status == VISFS_BA_ERR_DEVICE) { h->err = "a device-side hand-off (persistent PCG / LM decision) timed out"; return VISFS_BA_ERR_DEVICE; }
@@ -1832,6 +1895,7 @@ int visfs_ba_graph_reset(visfs_ba_handle* h) {
     HIP_TRY(h, hipGetLastError());
     h->ws.pristine = true;
     h->ws.stage_iter0 = true;
+    h->ws.reset_armed = true; h->ws.reset_armed_iter = h->ws.g.ceres ? h->prm.iterations : h->prm.iterations / 2; h->ws.reset_armed_gn = h->prm.trust_region == 1 ? 1 : 0;
     return VISFS_BA_OK;
 }
 
@@ -1847,6 +1911,7 @@ int visfs_ba_graph_download(visfs_ba_handle* h, double* pose_tq, double* point_x
 
 int visfs_ba_solve_window(visfs_ba_handle* h, const visfs_ba_window* w, visfs_ba_result* r) {
     if (!h || !w || !r) return VISFS_BA_ERR_BAD_ARGUMENT;
+    reset_disarm(h);
     h->batch_last = false; h->window_ok = false;
     const int rc = guarded(h, [&]() { return solve_window_on(h, h->ws, w, r); });
     if (rc == VISFS_BA_OK) { h->window_ok = true; std::memcpy(h->window_Trc, w->Trc, sizeof(h->window_Trc)); }      // (visfs_ba_window_covariance)
@@ -1855,6 +1920,7 @@ int visfs_ba_solve_window(visfs_ba_handle* h, const visfs_ba_window* w, visfs_ba
 
 int visfs_ba_solve_batch(visfs_ba_handle* h, int32_t n, const visfs_ba_window* const* w, visfs_ba_result* const* r) {
     if (!h || n < 0 || (n > 0 && (!w || !r))) return VISFS_BA_ERR_BAD_ARGUMENT;
+    reset_disarm(h);
     for (int i = 0; i < n; ++i) if (!w[i] || !r[i]) return VISFS_BA_ERR_BAD_ARGUMENT;
     h->batch_last = true; h->window_ok = false;
     // Independent windows (BASELINE config 5).  Host work (graph build, upload, write-back) runs on up to 8
@@ -1931,6 +1997,7 @@ int visfs_ba_solve_batch_sharded(visfs_ba_handle* const* handles, int32_t n_hand
     if (!handles || n_handles < 1 || n < 0 || (n > 0 && (!w || !r))) return VISFS_BA_ERR_BAD_ARGUMENT;
     for (int k = 0; k < n_handles; ++k) if (!handles[k]) return VISFS_BA_ERR_BAD_ARGUMENT;
     for (int k = 0; k < n_handles; ++k) for (int m = 0; m < k; ++m) if (handles[k] == handles[m]) return VISFS_BA_ERR_BAD_ARGUMENT;   // a handle is not thread-safe
+    for (int k = 0; k < n_handles; ++k) reset_disarm(handles[k]);
     if (n == 0) return VISFS_BA_OK;
     const int per = (n + n_handles - 1) / n_handles;          // contiguous blocks: window i -> handle i / per (visfs_amd/dist.py:shard_windows)
     std::vector<int> rc(n_handles, VISFS_BA_OK);
@@ -1953,6 +2020,7 @@ int visfs_ba_solve_batch_sharded(visfs_ba_handle* const* handles, int32_t n_hand
 // GRAPH layer for a batch: n graphs resident side by side, optimised by one sequence of batched launches (bench config 5).
 int visfs_ba_batch_upload(visfs_ba_handle* h, int32_t n, const visfs_ba_graph* const* graphs) {
     if (!h || n < 0 || (n > 0 && !graphs)) return VISFS_BA_ERR_BAD_ARGUMENT;
+    reset_disarm(h);
     for (int i = 0; i < n; ++i) if (!graphs[i]) return VISFS_BA_ERR_BAD_ARGUMENT;
     if (const char* why = framework_refusal(h->prm)) { h->err = why; return VISFS_BA_ERR_UNSUPPORTED; }
     h->batch_last = true; h->window_ok = false;
@@ -1981,6 +2049,7 @@ int visfs_ba_batch_upload(visfs_ba_handle* h, int32_t n, const visfs_ba_graph* c
 
 int visfs_ba_batch_reset(visfs_ba_handle* h) {
     if (!h) return VISFS_BA_ERR_BAD_ARGUMENT;
+    reset_disarm(h);
     HIP_TRY(h, hipSetDevice(h->device));
     if (h->n_batch > 0) launch_reset_batch(h->scratch.d_all, h->n_batch, h->scratch.all_dims, h->prm.framework == 1 ? h->prm.iterations : h->prm.iterations / 2, h->prm.trust_region == 1, 1, h->ws.stream);
     HIP_TRY(h, hipGetLastError());
@@ -1990,6 +2059,7 @@ int visfs_ba_batch_reset(visfs_ba_handle* h) {
 
 int visfs_ba_batch_optimize(visfs_ba_handle* h, visfs_ba_stats* stats) {
     if (!h) return VISFS_BA_ERR_BAD_ARGUMENT;
+    reset_disarm(h);
     return guarded(h, [&]() -> int {
         const int n = h->n_batch;
         if (n == 0) { h->err = "no batch resident"; return VISFS_BA_ERR_NOT_LOADED; }
@@ -2037,6 +2107,7 @@ int visfs_ba_graph_describe(visfs_ba_handle* h, visfs_ba_graph_info* out) {
     out->fused_path = w.fused ? 1 : 0;
     out->band_blocks = (h->prm.solver != 2 && !w.small_solve) ? w.g.band_B : -1;
     out->graph_replayed = w.last_replayed ? 1 : 0;
+    out->resets_skipped = w.resets_skipped; out->state_mirrored = w.state_mirrored;
     out->unit_form = w.spec_fused ? 2 : w.spec ? 1 : 0;
     out->solver_kernel = w.small_solve ? 5 : h->prm.solver != 2 ? (w.g.band_B >= 0 ? 7 : 6) : w.g.pcg_cu ? 4 : w.g.pcg1_code ? 1 : w.g.Npf > MAX_PCG_ONE_ROW_POSES ? 3 : 2;
     return VISFS_BA_OK;
@@ -2152,6 +2223,7 @@ static int stage_ceres_trial(visfs_ba_handle* h, const double lambda, const doub
 
 int visfs_ba_stage_linearize(visfs_ba_handle* h, double* robust_chi2, double* max_diag) {
     if (!h) return VISFS_BA_ERR_BAD_ARGUMENT;
+    reset_disarm(h);
     Workspace& w = h->ws;
     if (!w.loaded) { h->err = "no graph resident"; return VISFS_BA_ERR_NOT_LOADED; }
     if (w.g.ceres) return guarded(h, [&]() -> int { HIP_TRY(h, hipSetDevice(h->device)); return stage_ceres_linearize(h, robust_chi2, max_diag); });
@@ -2170,6 +2242,7 @@ int visfs_ba_stage_linearize(visfs_ba_handle* h, double* robust_chi2, double* ma
 
 int visfs_ba_stage_trial(visfs_ba_handle* h, double lambda, double* trial_chi2, double* scale, int32_t* pcg_iterations, int32_t* solver_ok) {
     if (!h) return VISFS_BA_ERR_BAD_ARGUMENT;
+    reset_disarm(h);
     Workspace& w = h->ws;
     if (!w.loaded) { h->err = "no graph resident"; return VISFS_BA_ERR_NOT_LOADED; }
     if (w.g.dogleg) { h->err = "visfs_ba_stage_trial steps LEVENBERG_MARQUARDT; a DOGLEG handle (Optimizer/TrustRegion=1 under Framework=1) is stepped with visfs_ba_stage_dogleg_trial"; return VISFS_BA_ERR_UNSUPPORTED; }
@@ -2213,6 +2286,7 @@ int visfs_ba_stage_trial(visfs_ba_handle* h, double lambda, double* trial_chi2, 
 
 int visfs_ba_stage_dogleg_trial(visfs_ba_handle* h, double radius, double mu, double out[12]) {
     if (!h || !out) return VISFS_BA_ERR_BAD_ARGUMENT;
+    reset_disarm(h);
     Workspace& w = h->ws;
     if (!w.loaded) { h->err = "no graph resident"; return VISFS_BA_ERR_NOT_LOADED; }
     if (!w.g.ceres) { h->err = "visfs_ba_stage_dogleg_trial: the g2o branch (Optimizer/Framework=0) has no dogleg strategy"; return VISFS_BA_ERR_UNSUPPORTED; }
@@ -2223,6 +2297,7 @@ int visfs_ba_stage_dogleg_trial(visfs_ba_handle* h, double radius, double mu, do
 
 int visfs_ba_stage_ceres_values(visfs_ba_handle* h, double out[4]) {
     if (!h || !out) return VISFS_BA_ERR_BAD_ARGUMENT;
+    reset_disarm(h);
     Workspace& w = h->ws;
     if (!w.loaded) { h->err = "no graph resident"; return VISFS_BA_ERR_NOT_LOADED; }
     if (!w.g.ceres) { h->err = "visfs_ba_stage_ceres_values: an Optimizer/Framework=1 handle is needed"; return VISFS_BA_ERR_UNSUPPORTED; }
@@ -2313,6 +2388,7 @@ static int stage_fetch_impl(visfs_ba_handle* h, int32_t which, double* dst, size
 // (LinearSolverPCG::init()), run the outlier pass on the committed estimate.
 int visfs_ba_stage_commit(visfs_ba_handle* h) {
     if (!h) return VISFS_BA_ERR_BAD_ARGUMENT;
+    reset_disarm(h);
     return guarded(h, [&]() -> int {
     HIP_TRY(h, hipSetDevice(h->device));          // a process may hold handles on several GPUs
     Workspace& w = h->ws;
@@ -2327,6 +2403,7 @@ int visfs_ba_stage_commit(visfs_ba_handle* h) {
 }
 int visfs_ba_stage_begin_phase(visfs_ba_handle* h) {
     if (!h) return VISFS_BA_ERR_BAD_ARGUMENT;
+    reset_disarm(h);
     return guarded(h, [&]() -> int {
     HIP_TRY(h, hipSetDevice(h->device));          // a process may hold handles on several GPUs
     Workspace& w = h->ws;
@@ -2342,6 +2419,7 @@ int visfs_ba_stage_begin_phase(visfs_ba_handle* h) {
 }
 int visfs_ba_stage_mark_outliers(visfs_ba_handle* h) {
     if (!h) return VISFS_BA_ERR_BAD_ARGUMENT;
+    reset_disarm(h);
     return guarded(h, [&]() -> int {
     HIP_TRY(h, hipSetDevice(h->device));          // a process may hold handles on several GPUs
     Workspace& w = h->ws;
@@ -2390,11 +2468,13 @@ int visfs_ba_hook_dogleg_combine(double s1, double s2, double s3, double jv2, do
 // ---------------------------------------------------------------- marginal covariances (ABI 9)
 int visfs_ba_graph_covariance(visfs_ba_handle* h, double* pose_cov, double* pose_cross, double* point_cov) {
     if (!h || !pose_cov) return VISFS_BA_ERR_BAD_ARGUMENT;
+    reset_disarm(h);
     return guarded(h, [&]() { return ws_covariance(h, h->ws, pose_cov, pose_cross, point_cov); });
 }
 
 int visfs_ba_window_covariance(visfs_ba_handle* h, double* pose_cov_wr, double* point_cov) {
     if (!h || !pose_cov_wr) return VISFS_BA_ERR_BAD_ARGUMENT;
+    reset_disarm(h);
     if (h->prm.framework != 0) { h->err = "covariances are computed for the g2o branch only (Optimizer/Framework=0)"; return VISFS_BA_ERR_UNSUPPORTED; }
     if (h->batch_last) { h->err = "covariances of batched windows are not supported"; return VISFS_BA_ERR_UNSUPPORTED; }
     if (!h->window_ok || !h->ws.loaded) { h->err = "no successful visfs_ba_solve_window on this handle since its last upload"; return VISFS_BA_ERR_NOT_LOADED; }
@@ -2463,6 +2543,7 @@ int visfs_ba_hook_band_selinv(int32_t n, int32_t B, const double* S_band, double
 
 int visfs_ba_stage_fetch(visfs_ba_handle* h, int32_t which, double* dst, size_t n_doubles) {
     if (!h || !dst) return VISFS_BA_ERR_BAD_ARGUMENT;
+    reset_disarm(h);
     return guarded(h, [&]() { return stage_fetch_impl(h, which, dst, n_doubles); });
 }
 

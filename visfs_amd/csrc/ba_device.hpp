@@ -36,7 +36,8 @@ constexpr int SM_MAX_SCH = 1024;      // Schur chunks (<= 64 k co-observation pa
 
 // LM / phase state machine, resident in HBM; every kernel of a "unit" reads its gate from here.
 // Unit gate bits (LmState::mode).  Written ONLY by single-workgroup kernels (k_reset, k_decide, k_phase_end,
-// k_stage_arm), so no multi-workgroup launch ever reads a gate that the same launch modifies.
+// k_stage_arm) or by the ONE deciding workgroup of a launch, after every other workgroup of that launch has read its gate (k_backsub
+// with the LM decision, k_eval with the phase end on board), so no workgroup ever reads a gate that its own launch has modified.
 constexpr int MODE_LIN = 1;     // this unit linearises (first unit of a phase, or the previous trial was accepted)
 constexpr int MODE_TRIAL = 2;   // this unit runs one damped solve
 
@@ -85,6 +86,11 @@ struct LmState {
     int32_t dogleg;
     uint32_t decide_epoch;  // tag of the last k_backsub launch that carried the LM decision; never reset (k_reset leaves it): stale
                             // hand-off words of an earlier launch or solve can then never match the tag a launch waits for
+    uint32_t phase_epoch;   // the same for the phase end on board k_eval (DeviceGraph::eval_gran): advanced only by that launch's decider, at its
+                            //   very end; never reset
+    uint32_t mirror_seq;    // launches that have left this state in the host's pinned copy (phase_decider with a mirror); never reset.  Shares an
+                            //   aligned 8-byte word with phase_epoch: that word is the LAST the decider writes into the host's copy, behind a
+                            //   system-scope fence, so a host that sees the count it waits for sees the whole state
     // stage hooks on an Optimizer/Framework=1 handle (DeviceGraph::debug set, never in a solve): what k_dogleg_mid summed — ||J v||^2, S1, S2,
     // S3 — and what ceres_decide received — sum of rho at the candidate, 2 x model cost change, ||x - candidate||
     double stage_out[8];
@@ -255,6 +261,9 @@ struct DeviceGraph {
     int32_t debug;
     int32_t fault_pcg;      // test hook (VISFS_BA_FAULT_PCG_TIMEOUT=1 at upload): block row 0 of the persistent PCG withholds its first hand-off and every wait
                             // gives up after 2^10 instead of 2^22 polls — the path a GPU kept busy by another process takes (LmState::pcg_timeout)
+    unsigned long long* eval_gran; // [(No + 255) / 256 + 1][4] k_eval's two sums (chi2, outliers marked) per workgroup as {epoch:32 | half:32} hand-off
+                            //   words, for the phase end on board that launch (tag: LmState::phase_epoch + 1); zeroed at upload.  Last member:
+                            //   every offset the unit kernels read stays where it was
 };
 
 // A wave-uniform pointer, pinned to scalar registers (the batched kernels read their graph from HBM with vector loads; without

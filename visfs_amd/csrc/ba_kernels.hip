@@ -695,6 +695,12 @@ __device__ __forceinline__ void publish_trial(const DeviceGraph& g, const int w,
     st_granule(o, e | (unsigned)__double2loint(chi)); st_granule(o + 1, e | (unsigned)__double2hiint(chi));
     st_granule(o + 2, e | (unsigned)__double2loint(sc)); st_granule(o + 3, e | (unsigned)__double2hiint(sc));
 }
+// ... the same four words for any pair of sums (the phase end on board k_eval: DeviceGraph::eval_gran)
+__device__ __forceinline__ void publish_words(unsigned long long* o, const unsigned ep, const double a, const double b) {
+    const unsigned long long e = (unsigned long long)ep << 32;
+    st_granule(o, e | (unsigned)__double2loint(a)); st_granule(o + 1, e | (unsigned)__double2hiint(a));
+    st_granule(o + 2, e | (unsigned)__double2loint(b)); st_granule(o + 3, e | (unsigned)__double2hiint(b));
+}
 // The deciding workgroup (256 threads): fetch the partials of every workgroup of the window — four workgroups' words in flight per
 // thread, fetched again after a pause while a tag is missing — add them in decide_role's order and step the LM state
 // machine.  LmState is written only here, after every workgroup has published, i.e. after every workgroup has read its gate and
@@ -4386,15 +4392,118 @@ __global__ __launch_bounds__(256) void k_decide(const Src src) {
 }
 
 // ================================================================= K10: per-edge chi2, outlier marking
+// One thread: closes a phase (Optimizer.cpp:271-280 after phase 1, :315-318 after phase 2) and arms the next.
+__device__ __noinline__ void phase_end_update(const DeviceGraph& g, LmState* st, const double chi, const double nout, const int phase_just_done, const int next_max_iter) {
+    st->ended = phase_just_done + 1;
+    if (phase_just_done == 0) {
+        st->chi2_phase1 = chi; st->chi2_final = chi;
+        st->pcg_phase1 = st->pcg_total;
+        if (st->max_iter <= 0) st->chi2_initial = chi;        // optimize(0): nothing linearised
+        if (g.ceres) { }                                                  // the Ceres branch has no chi2 guards (Optimizer.cpp:504-540)
+        else if (chi != chi) st->status = 3;                              // VISFS_BA_ERR_NAN_CHI2
+        else if (chi > 1000000000000.0 || !(chi <= DBL_MAX)) st->status = 4; // VISFS_BA_ERR_HUGE_CHI2_1
+        st->n_outliers = (int)nout;
+        // arm phase 2: initializeOptimization(0) + optimize(iterations/2) re-initialise lambda and the PCG residual
+        st->phase = 1; st->phase_iter = 0; st->max_iter = next_max_iter; st->trial_q = 0;
+        st->solver_failed = 0; st->pcg_residual = -1.0;
+        st->done = (st->status != 0 || next_max_iter <= 0 || g.huber_delta <= 0.0) ? 1 : 0;
+        st->mode = st->done ? 0 : (MODE_LIN | MODE_TRIAL); st->lin_b_pending = 0;
+    } else {
+        st->chi2_final = chi;
+        if (!g.ceres && chi > 1000000000000.0) st->status = 5;           // VISFS_BA_ERR_HUGE_CHI2_2
+    }
+}
+
+// The phase end on board k_eval<DEC> (a lone window; 256 threads, the last workgroup of the launch): what k_phase_end does, without its
+// launch.  The working workgroups publish their (chi2, outliers marked) pair as hand-off words {tag:32 | half of a double:32} with
+// write-through stores (publish_words); this workgroup fetches them with sc1 loads until every tag is there — the data is the flag, no
+// fence, no counter, as decide_gather_role — adds them in k_phase_end's order (thread tid: words tid, tid + 256, ..., then the workgroup
+// sums) and steps the state through the same phase_end_update.  The tag, LmState::phase_epoch + 1, is advanced here alone, at the very
+// end, and k_reset leaves it: a stale word of an earlier launch, solve or upload never matches.  Gate off (`open` false: the phase this
+// launch would close is not over, or the solve has stopped): nobody publishes and nobody is waited for.  A wait that runs out (never
+// expected: the workers wait for nothing) ends the solve with VISFS_BA_ERR_DEVICE like every other hand-off.
+// mirror != nullptr (the phase-2 end, the last launch of every enqueued sequence): the state goes to the host's pinned copy from here, gate
+// open or not — the host reads it after every sequence, also to learn that a phase is NOT over — so no copy is enqueued behind the launch.
+__device__ __forceinline__ void phase_decider(const DeviceGraph& g, LmState* st, const bool open, const unsigned ep, const int phase_just_done, const int next_max_iter,
+                                              LmState* mirror, double* red) {
+    typedef unsigned v4u_t __attribute__((ext_vector_type(4)));
+    const int tid = threadIdx.x;
+    if (open) {
+        const int n = (g.No + 255) / 256 + 1;               // the working workgroups of this launch
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)g.eval_gran, 0, (int)(n * 32), 0x00020000);
+        double chi = 0.0, nout = 0.0;
+        int bad = 0;
+        constexpr int U = 2;
+        for (int w0 = tid; w0 < n; w0 += 256 * U) {
+            v4u_t a[U], b[U];
+            for (int spin = 0;; ++spin) {
+                bool ready = true;
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const int w = min(w0 + 256 * u, n - 1);     // (clamped: a surplus slot re-reads the last workgroup's words)
+                    a[u] = __builtin_amdgcn_raw_buffer_load_b128(rs, 32 * w, 0, 16); b[u] = __builtin_amdgcn_raw_buffer_load_b128(rs, 32 * w + 16, 0, 16);
+                }
+#pragma unroll
+                for (int u = 0; u < U; ++u) ready = ready && a[u].y == ep && a[u].w == ep && b[u].y == ep && b[u].w == ep;
+                if (ready) break;
+                if (spin > (1 << 20)) { bad = 1; break; }
+                __builtin_amdgcn_s_sleep(8);
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                if (w0 + 256 * u < n) { chi += __hiloint2double((int)a[u].z, (int)a[u].x); nout += __hiloint2double((int)b[u].z, (int)b[u].x); }
+            }
+        }
+        chi = block_sum_256(chi, red);
+        nout = block_sum_256(nout, red);
+        bad = __syncthreads_or(bad);
+        if (tid == 0) {
+            if (bad) { st->status = 8; st->done = 1; st->mode = 0; }      // VISFS_BA_ERR_DEVICE
+            else phase_end_update(g, st, chi, nout, phase_just_done, next_max_iter);
+            st->phase_epoch = ep;
+        }
+    }
+    if (mirror == nullptr) return;
+    if (open) { if (tid == 0) __threadfence(); __syncthreads(); }      // thread 0's last state store is out before anybody reads the state back
+    static_assert(offsetof(LmState, phase_epoch) % 8 == 0 && offsetof(LmState, mirror_seq) == offsetof(LmState, phase_epoch) + 4 && sizeof(LmState) % 8 == 0, "the tag word of the mirror");
+    constexpr int tag_word = (int)(offsetof(LmState, phase_epoch) / 8);
+    const unsigned long long* from = reinterpret_cast<const unsigned long long*>(st);
+    unsigned long long* to = reinterpret_cast<unsigned long long*>(mirror);
+    for (int t = tid; t < (int)(sizeof(LmState) / 8); t += 256) if (t != tag_word) to[t] = ld_granule(from + t);
+    // the word with the count goes last, once every other word is out at system scope: the host may read the copy as soon as it sees the
+    // count it waits for, without waiting for the launch to retire (ws_read_state)
+    __threadfence_system();
+    __syncthreads();
+    if (tid == 0) {
+        const unsigned seq = st->mirror_seq + 1u;
+        st->mirror_seq = seq;
+        __hip_atomic_store(to + tag_word, ((unsigned long long)seq << 32) | (open ? ep : ep - 1u), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
+
 // Optimizer.cpp:270-303: computeActiveErrors; edges with chi2() > kernel->delta() (UNSQUARED) go to level 1.
-template <class Src, bool STG = true>
-__global__ __launch_bounds__(256) void k_eval(const Src src, const int mark, const int phase_just_done) {
+// DEC (a lone window's gated phase end): the launch has one more workgroup, the LAST of its grid, which closes the phase (phase_decider,
+// above) — every working workgroup also publishes its two sums as hand-off words, and k_phase_end is not launched.
+template <class Src, bool STG = true, bool DEC = false>
+__global__ __launch_bounds__(256) void k_eval(const Src src, const int mark, const int phase_just_done, const int next_max_iter, LmState* const mirror) {
     const DeviceGraph& g = graph_of(src);
     LmState* st = state_of(src, g);
-    if (st->status != 0) return;
-    // the host may enqueue a phase end before it knows that the phase is over (one state read per solve): act only then
-    if (phase_just_done >= 0 && (!st->done || st->ended != phase_just_done)) return;
     extern __shared__ __attribute__((aligned(16))) double smem[];
+    unsigned ep = 0u;
+    if (DEC) {
+        // (the gate words and the tag are read side by side: one round trip.  Nobody but the decider writes LmState in this launch, and
+        // it does so only after every working workgroup has published, i.e. has read these words)
+        const int s_status = st->status, s_done = st->done, s_ended = st->ended;
+        ep = st->phase_epoch + 1u;
+        const bool open = s_status == 0 && s_done && s_ended == phase_just_done;
+        if (blockIdx.x == gridDim.x - 1) { phase_decider(g, st, open, ep, phase_just_done, next_max_iter, mirror, smem); return; }
+        if (!open) return;
+    } else {
+        if (st->status != 0) return;
+        // the host may enqueue a phase end before it knows that the phase is over (one state read per solve): act only then
+        if (phase_just_done >= 0 && (!st->done || st->ended != phase_just_done)) return;
+    }
     double* sRt = smem;
     double* red = smem + (STG ? 12 * g.Np : 0);
     const int sel = st->sel;
@@ -4448,32 +4557,13 @@ __global__ __launch_bounds__(256) void k_eval(const Src src, const int mark, con
     }
     const double chi_tot = block_sum_256(chi_acc, red);
     const double out_tot = block_sum_256((double)n_out, red);
-    if (tid == 0) { g.trial_part[2 * bid] = chi_tot; g.trial_part[2 * bid + 1] = out_tot; }
-}
-
-// One workgroup: closes a phase (Optimizer.cpp:271-280 after phase 1, :315-318 after phase 2) and arms the next.
-// One thread: closes a phase (Optimizer.cpp:271-280 after phase 1, :315-318 after phase 2) and arms the next.
-__device__ __noinline__ void phase_end_update(const DeviceGraph& g, LmState* st, const double chi, const double nout, const int phase_just_done, const int next_max_iter) {
-    st->ended = phase_just_done + 1;
-    if (phase_just_done == 0) {
-        st->chi2_phase1 = chi; st->chi2_final = chi;
-        st->pcg_phase1 = st->pcg_total;
-        if (st->max_iter <= 0) st->chi2_initial = chi;        // optimize(0): nothing linearised
-        if (g.ceres) { }                                                  // the Ceres branch has no chi2 guards (Optimizer.cpp:504-540)
-        else if (chi != chi) st->status = 3;                              // VISFS_BA_ERR_NAN_CHI2
-        else if (chi > 1000000000000.0 || !(chi <= DBL_MAX)) st->status = 4; // VISFS_BA_ERR_HUGE_CHI2_1
-        st->n_outliers = (int)nout;
-        // arm phase 2: initializeOptimization(0) + optimize(iterations/2) re-initialise lambda and the PCG residual
-        st->phase = 1; st->phase_iter = 0; st->max_iter = next_max_iter; st->trial_q = 0;
-        st->solver_failed = 0; st->pcg_residual = -1.0;
-        st->done = (st->status != 0 || next_max_iter <= 0 || g.huber_delta <= 0.0) ? 1 : 0;
-        st->mode = st->done ? 0 : (MODE_LIN | MODE_TRIAL); st->lin_b_pending = 0;
-    } else {
-        st->chi2_final = chi;
-        if (!g.ceres && chi > 1000000000000.0) st->status = 5;           // VISFS_BA_ERR_HUGE_CHI2_2
+    if (tid == 0) {
+        g.trial_part[2 * bid] = chi_tot; g.trial_part[2 * bid + 1] = out_tot;
+        if (DEC) publish_words(g.eval_gran + 4 * (size_t)bid, ep, chi_tot, out_tot);
     }
 }
 
+// One workgroup: closes a phase (Optimizer.cpp:271-280 after phase 1, :315-318 after phase 2) and arms the next (phase_end_update, above k_eval).
 template <class Src>
 __global__ __launch_bounds__(256) void k_phase_end(const Src src, const int phase_just_done, const int next_max_iter) {
     const DeviceGraph& g = graph_of(src);
@@ -5345,9 +5435,17 @@ static void launch_backsub_src(const Src& src, const LaunchDims& d, int B, int o
 }
 template <class Src>
 static void launch_phase_end_src(const Src& src, const LaunchDims& d, int B, int phase_just_done, int mark, int next_max_iter, hipStream_t s) {
-    if (!staged(d)) hipLaunchKernelGGL((k_eval<One, false>), dim3(d.eval_blocks, B), dim3(256), lds_poses(d, 8), s, One{ graph_of_host(src) }, mark, phase_just_done);
-    else { ensure_lds(k_eval<Src>, lds_poses(d, 8)); hipLaunchKernelGGL((k_eval<Src>), dim3(d.eval_blocks, B), dim3(256), lds_poses(d, 8), s, src, mark, phase_just_done); }
+    if (!staged(d)) hipLaunchKernelGGL((k_eval<One, false>), dim3(d.eval_blocks, B), dim3(256), lds_poses(d, 8), s, One{ graph_of_host(src) }, mark, phase_just_done, 0, (LmState*)nullptr);
+    else { ensure_lds(k_eval<Src>, lds_poses(d, 8)); hipLaunchKernelGGL((k_eval<Src>), dim3(d.eval_blocks, B), dim3(256), lds_poses(d, 8), s, src, mark, phase_just_done, 0, (LmState*)nullptr); }
     hipLaunchKernelGGL((k_phase_end<Src>), dim3(1, B), dim3(256), 0, s, src, phase_just_done, next_max_iter);
+}
+// A lone window's phase end in ONE launch: k_eval with the decider workgroup behind its working ones (k_eval<DEC>, phase_decider).
+// mirror: the host's pinned LmState at its device address, or nullptr — the decider leaves the state there at the end of the launch.
+static void launch_phase_end_fused(const DeviceGraph& g, int phase_just_done, int mark, int next_max_iter, LmState* mirror, hipStream_t s) {
+    const LaunchDims d = dims_of(g);
+    const One src{ g };
+    if (!staged(d)) hipLaunchKernelGGL((k_eval<One, false, true>), dim3(d.eval_blocks + 1), dim3(256), lds_poses(d, 8), s, src, mark, phase_just_done, next_max_iter, mirror);
+    else { ensure_lds(k_eval<One, true, true>, lds_poses(d, 8)); hipLaunchKernelGGL((k_eval<One, true, true>), dim3(d.eval_blocks + 1), dim3(256), lds_poses(d, 8), s, src, mark, phase_just_done, next_max_iter, mirror); }
 }
 
 // ---- single window
@@ -5445,14 +5543,15 @@ void launch_backsub_dogleg(const DeviceGraph& g, int pass, hipStream_t s) {
     }
 }
 void launch_dogleg_mid(const DeviceGraph& g, hipStream_t s) { hipLaunchKernelGGL((k_dogleg_mid<One>), dim3(1), dim3(256), 0, s, One{ g }); }
-void launch_phase_end(const DeviceGraph& g, int phase_just_done, int mark, int next_max_iter, hipStream_t s) {
-    launch_phase_end_src(One{ g }, dims_of(g), 1, phase_just_done, mark, next_max_iter, s);
+void launch_phase_end(const DeviceGraph& g, int phase_just_done, int mark, int next_max_iter, hipStream_t s, bool on_board, LmState* mirror) {
+    if (on_board) launch_phase_end_fused(g, phase_just_done, mark, next_max_iter, mirror, s);
+    else launch_phase_end_src(One{ g }, dims_of(g), 1, phase_just_done, mark, next_max_iter, s);
 }
 // stage hook: the outlier pass of Optimizer.cpp:283-303 on the committed estimate, ungated (k_eval alone: marks edges, no phase change)
 void launch_eval_mark(const DeviceGraph& g, hipStream_t s) {
     const LaunchDims d = dims_of(g);
-    if (!staged(d)) hipLaunchKernelGGL((k_eval<One, false>), dim3(d.eval_blocks), dim3(256), lds_poses(d, 8), s, One{ g }, 1, -1);
-    else { ensure_lds(k_eval<One>, lds_poses(d, 8)); hipLaunchKernelGGL((k_eval<One>), dim3(d.eval_blocks), dim3(256), lds_poses(d, 8), s, One{ g }, 1, -1); }
+    if (!staged(d)) hipLaunchKernelGGL((k_eval<One, false>), dim3(d.eval_blocks), dim3(256), lds_poses(d, 8), s, One{ g }, 1, -1, 0, (LmState*)nullptr);
+    else { ensure_lds(k_eval<One>, lds_poses(d, 8)); hipLaunchKernelGGL((k_eval<One>), dim3(d.eval_blocks), dim3(256), lds_poses(d, 8), s, One{ g }, 1, -1, 0, (LmState*)nullptr); }
 }
 void launch_reset(const DeviceGraph& g, int max_iter, int gauss_newton, int restore, hipStream_t s) {
     hipLaunchKernelGGL((k_reset<One>), dim3(dims_of(g).reset_blocks), dim3(256), 0, s, One{ g }, max_iter, gauss_newton, restore);

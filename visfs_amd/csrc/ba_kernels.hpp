@@ -37,7 +37,9 @@ void launch_backsub_decide(const DeviceGraph& g, hipStream_t s);    // gated uni
 void launch_decide(const DeviceGraph& g, hipStream_t s);
 void launch_backsub_dogleg(const DeviceGraph& g, int pass, hipStream_t s);   // Optimizer/Framework=1 + TrustRegion=1: the two landmark passes of the dogleg step
 void launch_dogleg_mid(const DeviceGraph& g, hipStream_t s);                  // ... the combination between them (coefficients, model cost change, trial poses)
-void launch_phase_end(const DeviceGraph& g, int phase_just_done, int mark, int next_max_iter, hipStream_t s);
+// on_board: one launch (k_eval with the phase-end decider behind its workgroups) instead of k_eval + k_phase_end; mirror (on_board only):
+// the host's pinned LmState, where that decider leaves the state at the end of the launch (nullptr: nowhere)
+void launch_phase_end(const DeviceGraph& g, int phase_just_done, int mark, int next_max_iter, hipStream_t s, bool on_board = false, LmState* mirror = nullptr);
 size_t band_lds_bytes(int npf, int B, int rows);                       // dynamic LDS of the banded direct solver (k_band_chol) with `rows` block rows resident
 constexpr int BAND_LDS_BUDGET = 156 * 1024;
 bool band_plan(int npf, int B, int* rows, int* lds_bytes);             // false: the band is too wide for k_band_chol (dense blocked Cholesky instead)
