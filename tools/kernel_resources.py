@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Register / scratch / occupancy table of every kernel in ba_kernels.hip, ba_cov.hip, ba_flow.hip, ba_corners.hip, ba_pnp.hip, ba_fund.hip, ba_clahe.hip, ba_tracker.hip, ba_scan.hip, ba_scan_fast.hip, ba_scan_group.hip, ba_scan_refine.hip, ba_pose_graph.hip, ba_pose_graph_cov.hip, ba_map.hip, ba_scan_filter.hip, ba_mcl.hip, ba_mcl_kld.hip and ba_place.hip (hipcc -Rpass-analysis=kernel-resource-usage,
+"""Register / scratch / occupancy table of every kernel in ba_kernels.hip, ba_cov.hip, ba_flow.hip, ba_corners.hip, ba_pnp.hip, ba_fund.hip, ba_clahe.hip, ba_tracker.hip, ba_scan.hip, ba_scan_fast.hip, ba_scan_group.hip, ba_scan_refine.hip, ba_pose_graph.hip, ba_pose_graph_cov.hip, ba_map.hip, ba_scan_filter.hip, ba_mcl.hip, ba_mcl_kld.hip, ba_place.hip and ba_place_verify.hip (hipcc -Rpass-analysis=kernel-resource-usage,
 device only).
 usage: tools/kernel_resources.py [filter-substring ...]   (extra -D flags through VISFS_BA_EXTRA_FLAGS; KRES_TXT=<file> reuses a saved remark dump;
 VISFS_BA_SRC=<dir>: another checkout's visfs_amd/csrc)"""
@@ -7,7 +7,7 @@ import os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from visfs_amd.build import KERNEL_FLAGS, KERNEL_SOURCES
-srcs = [os.path.join(os.environ.get("VISFS_BA_SRC", os.path.join(ROOT, "visfs_amd", "csrc")), f) for f in ("ba_kernels.hip", "ba_cov.hip", "ba_flow.hip", "ba_corners.hip", "ba_pnp.hip", "ba_fund.hip", "ba_clahe.hip", "ba_tracker.hip", "ba_scan.hip", "ba_scan_fast.hip", "ba_scan_group.hip", "ba_scan_refine.hip", "ba_pose_graph.hip", "ba_pose_graph_cov.hip", "ba_map.hip", "ba_scan_filter.hip", "ba_mcl.hip", "ba_mcl_kld.hip", "ba_place.hip")]
+srcs = [os.path.join(os.environ.get("VISFS_BA_SRC", os.path.join(ROOT, "visfs_amd", "csrc")), f) for f in ("ba_kernels.hip", "ba_cov.hip", "ba_flow.hip", "ba_corners.hip", "ba_pnp.hip", "ba_fund.hip", "ba_clahe.hip", "ba_tracker.hip", "ba_scan.hip", "ba_scan_fast.hip", "ba_scan_group.hip", "ba_scan_refine.hip", "ba_pose_graph.hip", "ba_pose_graph_cov.hip", "ba_map.hip", "ba_scan_filter.hip", "ba_mcl.hip", "ba_mcl_kld.hip", "ba_place.hip", "ba_place_verify.hip")]
 if os.environ.get("KRES_TXT"):
     txt = open(os.environ["KRES_TXT"]).read()
 else:

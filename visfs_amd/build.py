@@ -8,7 +8,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "visfs_amd", "csrc")
 LIB_DIR = os.path.join(ROOT, "visfs_amd", "lib")
 LIB = os.path.join(LIB_DIR, "libvisfs_ba_hip.so")
-SOURCES = ["ba_kernels.hip", "ba_cov.hip", "ba_submap.hip", "ba_flow.hip", "ba_corners.hip", "ba_clahe.hip", "ba_pnp.hip", "ba_fund.hip", "ba_tracker.hip", "ba_scan.hip", "ba_scan_fast.hip", "ba_api.cpp", "ba_scan_group.hip", "ba_scan_refine.hip", "ba_pose_graph.hip", "ba_pose_graph_cov.hip", "ba_map.hip", "ba_scan_filter.hip", "ba_mcl.hip", "ba_mcl_kld.hip", "ba_place.hip"]
+SOURCES = ["ba_kernels.hip", "ba_cov.hip", "ba_submap.hip", "ba_flow.hip", "ba_corners.hip", "ba_clahe.hip", "ba_pnp.hip", "ba_fund.hip", "ba_tracker.hip", "ba_scan.hip", "ba_scan_fast.hip", "ba_api.cpp", "ba_scan_group.hip", "ba_scan_refine.hip", "ba_pose_graph.hip", "ba_pose_graph_cov.hip", "ba_map.hip", "ba_scan_filter.hip", "ba_mcl.hip", "ba_mcl_kld.hip", "ba_place.hip", "ba_place_verify.hip"]
 HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.hpp")) + glob.glob(os.path.join(ROOT, "include", "*.h")))      # every header: a new one cannot be forgotten
 
 

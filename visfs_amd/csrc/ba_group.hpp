@@ -3,6 +3,8 @@
 // extraction).  ba_tracker.hip owns the group, fills one pinned block with every table of a call, sends it up in one copy and hands each
 // function the device address of its records.  The member index of every batched kernel is blockIdx.z.
 #pragma once
+#include <vector>
+
 #include "ba_clahe.hpp"
 #include "ba_corners.hpp"
 #include "ba_flow_object.hpp"
@@ -70,11 +72,13 @@ void cull_host(const CullRec& r, const float* from_xy, const float* to_xy, const
 }  // namespace fund
 
 struct visfs_pnp_params;                       // include/visfs_pnp.h
+struct visfs_pnp;
 struct visfs_pnp_camera;
 
 namespace pnp {
 
 struct PnpRec;                                 // ba_pnp.hpp
+struct RefineFromRec;
 struct PnpShape;
 struct Row;
 struct Result;
@@ -82,6 +86,14 @@ struct Cam;
 // The search and the refinement of the pose guess for the n members of a tracker call (ba_pnp.hip): two
 // launches with grid.z = n behind the rows kernel of ba_tracker.hip.
 int group_pnp(hipStream_t stream, int n, const PnpRec* d_recs, const PnpShape& S, flow::GroupCounts* cnt);
+// The refinement alone for the n members of a call, each from the model its record names (k_pnp_refine_from_g, DESIGN.md section
+// 9x): one launch with grid.z = n.  host_refine_from is its twin on a solver of visfs_pnp_create_host, which then reports the passes
+// through visfs_pnp_download; S.min_inliers is already raised to 4.
+int group_refine_from(hipStream_t stream, int n, const RefineFromRec* d_recs, const PnpShape& S, flow::GroupCounts* cnt);
+int host_refine_from(visfs_pnp* p, const Row* rows, int32_t m, const Cam& K, const PnpShape& S, const double start_tq[7], Result* res,
+                     std::vector<int32_t>* inliers);
+// the model block of the last visfs_pnp_solve or host_refine_from of a solver
+const Result& last_result(const visfs_pnp* p);
 // The parameter check of visfs_pnp_solve; `why` is a string literal.
 int check_params(const visfs_pnp_params& q, const visfs_pnp_camera& c, const char** why);
 // MultiviewGeometry.cpp:147-205 from the model and the inliers (numbers of `rows`), on the host in every flavour: the transform

@@ -13,6 +13,7 @@
 //                         ascending query order by ballot prefix, written straight into the result block
 // Every result is a minimum of integers or a count, so no schedule shows in the bytes.
 #include "ba_place.hpp"
+#include "ba_place_object.hpp"
 #include "ba_flow_object.hpp"
 #include "ba_host.hpp"
 #include "../../include/visfs_place.h"
@@ -26,39 +27,6 @@ using namespace place;
 using namespace host;
 
 namespace place {
-
-// A describe of n key-points writes rows 0 .. n - 1 only, and visfs_place_db_add copies the whole block: rows from n on keep what
-// an earlier, longer describe left, on the device and on the twin alike.  Every reader stops at the slot's count (Payload::n) or the
-// set's n, and no hook shows a row beyond it.
-struct SlotBlock {                         // what a store keeps of a set: the head of SetBlock
-    uint32_t desc[kMaxPoints][kDescWords];
-    uint8_t valid[kMaxPoints];
-};
-struct SetBlock {
-    uint32_t desc[kMaxPoints][kDescWords];
-    uint8_t valid[kMaxPoints];
-    uint8_t bin[kMaxPoints];
-    float xy[kMaxPoints][2];
-};
-struct Payload {                           // a slot's words, uploaded in one copy
-    int32_t id[kMaxPoints];
-    float xyz[kMaxPoints][3];
-    int64_t key;
-    int32_t n, pad;
-};
-static_assert(offsetof(SetBlock, valid) == offsetof(SlotBlock, valid) && sizeof(SlotBlock) == 16896, "a slot is the head of a set");
-static_assert(sizeof(visfs_place_row) == 36 && sizeof(visfs_place_result) % 4 == 0, "the result block is written as words");
-
-struct Counts4 {
-    int32_t uploads = 0, launches = 0, downloads = 0, waits = 0;
-    int read(int32_t* u, int32_t* l, int32_t* d, int32_t* w) const {
-        if (u) *u = uploads;
-        if (l) *l = launches;
-        if (d) *d = downloads;
-        if (w) *w = waits;
-        return VISFS_BA_OK;
-    }
-};
 
 // ---------------------------------------------------------------- kernels
 constexpr int kMatchT = 512, kRankT = 1024;
@@ -227,44 +195,7 @@ const Table& host_table() {
 
 }  // namespace
 
-// ---------------------------------------------------------------- the objects
-struct visfs_place_set {
-    std::string err;
-    visfs_flow* flow = nullptr;
-    bool device = false;
-    int dev = 0;
-    hipStream_t stream = nullptr;
-    int32_t capacity = 0, n = 0;
-    bool described = false;
-    Counts4 counts;
-    SetBlock* host = nullptr;              // the twin's set
-    SetBlock* d_set = nullptr;
-    Table* d_table = nullptr;
-    float* h_xy = nullptr;                 // pinned: a call's key-points
-    hipEvent_t up_done = nullptr;          // behind the copy out of h_xy
-    bool up_pending = false;
-};
-
-struct visfs_place_db {
-    std::string err;
-    bool device = false;
-    int dev = 0;
-    hipStream_t stream = nullptr;
-    int32_t max_keyframes = 0, size = 0;
-    Counts4 counts;
-    std::vector<SlotBlock> hslots;         // the twin's store
-    std::vector<Payload> hpay;
-    SlotBlock* d_slots = nullptr;
-    Payload* d_pay = nullptr;
-    int32_t* d_match = nullptr;            // [max_keyframes][512]
-    int32_t* d_counts = nullptr;
-    Params* d_prm = nullptr;
-    visfs_place_result* d_result = nullptr;
-    char* h_io = nullptr;                  // pinned: a Payload going up, Params going up, the result coming down
-    hipEvent_t up_done = nullptr;          // behind the copy of a Payload out of h_io
-    bool up_pending = false;
-};
-
+// ---------------------------------------------------------------- the objects (ba_place_object.hpp)
 namespace {
 
 constexpr size_t kIoBytes = sizeof(visfs_place_result) > sizeof(Payload) ? sizeof(visfs_place_result) : sizeof(Payload);
@@ -332,20 +263,28 @@ template <class T> int pinned_free(T* o) {
     return VISFS_BA_OK;
 }
 
-int same_flavour(visfs_place_db* db, const visfs_place_set* s) {
-    if (db->device != s->device) return fail(db, VISFS_BA_ERR_BAD_ARGUMENT, "the set and the store are of different flavours");
-    if (db->device && (db->dev != s->dev || db->stream != s->stream))
-        return fail(db, VISFS_BA_ERR_BAD_ARGUMENT, "the set and the store belong to different handles");
-    if (!s->described) return fail(db, VISFS_BA_ERR_NOT_LOADED, "the set was never described");
+int flavour_text(const visfs_place_db* db, const visfs_place_set* s, const char** why) {
+    if (db->device != s->device) { *why = "the set and the store are of different flavours"; return VISFS_BA_ERR_BAD_ARGUMENT; }
+    if (db->device && (db->dev != s->dev || db->stream != s->stream)) {
+        *why = "the set and the store belong to different handles"; return VISFS_BA_ERR_BAD_ARGUMENT;
+    }
+    if (!s->described) { *why = "the set was never described"; return VISFS_BA_ERR_NOT_LOADED; }
     return VISFS_BA_OK;
 }
 
-int check_params(visfs_place_db* db, const visfs_place_params& p) {
-    if (p.first_slot < 0 || p.last_slot < p.first_slot) return fail(db, VISFS_BA_ERR_BAD_ARGUMENT, "the slot range is not 0 <= first_slot <= last_slot");
-    if (p.max_distance < 0 || p.max_distance > 256) return fail(db, VISFS_BA_ERR_BAD_ARGUMENT, "max_distance must lie in 0 .. 256");
-    if (p.ratio_num < 1 || p.ratio_num > 1024 || p.ratio_den < 1 || p.ratio_den > 1024)
-        return fail(db, VISFS_BA_ERR_BAD_ARGUMENT, "ratio_num and ratio_den must lie in 1 .. 1024");
-    if (p.min_matches < 0 || p.min_matches > kMaxPoints) return fail(db, VISFS_BA_ERR_BAD_ARGUMENT, "min_matches must lie in 0 .. 512");
+int same_flavour(visfs_place_db* db, const visfs_place_set* s) {
+    const char* why = "";
+    const int rc = flavour_text(db, s, &why);
+    return rc == VISFS_BA_OK ? rc : fail(db, rc, why);
+}
+
+int check_params(const visfs_place_params& p, const char** why) {
+    if (p.first_slot < 0 || p.last_slot < p.first_slot) { *why = "the slot range is not 0 <= first_slot <= last_slot"; return VISFS_BA_ERR_BAD_ARGUMENT; }
+    if (p.max_distance < 0 || p.max_distance > 256) { *why = "max_distance must lie in 0 .. 256"; return VISFS_BA_ERR_BAD_ARGUMENT; }
+    if (p.ratio_num < 1 || p.ratio_num > 1024 || p.ratio_den < 1 || p.ratio_den > 1024) {
+        *why = "ratio_num and ratio_den must lie in 1 .. 1024"; return VISFS_BA_ERR_BAD_ARGUMENT;
+    }
+    if (p.min_matches < 0 || p.min_matches > kMaxPoints) { *why = "min_matches must lie in 0 .. 512"; return VISFS_BA_ERR_BAD_ARGUMENT; }
     return VISFS_BA_OK;
 }
 
@@ -384,12 +323,10 @@ int device_query(visfs_place_db* db, const visfs_place_set* s, const Params& p, 
     if (rc != VISFS_BA_OK) return rc;
     std::memcpy(db->h_io, &p, sizeof p);
     HIP_TRY(db, hipMemcpyAsync(db->d_prm, db->h_io, sizeof p, hipMemcpyHostToDevice, db->stream));
-    hipLaunchKernelGGL(k_place_match, dim3((unsigned)std::max(p.n_slots, 1)), dim3(kMatchT), 0, db->stream, s->d_set, s->n, db->d_slots,
-                       db->d_pay, db->d_prm, db->d_match, db->d_counts);
-    HIP_TRY(db, hipGetLastError());
-    hipLaunchKernelGGL(k_place_rank, dim3(1), dim3(kRankT), 0, db->stream, s->d_set, s->n, db->d_pay, db->d_prm, db->d_match, db->d_counts,
-                       db->d_result);
-    HIP_TRY(db, hipGetLastError());
+    if (launch_query(db, s, p, db->d_prm, db->d_result) != VISFS_PLACE_QUERY_LAUNCHES) {
+        HIP_TRY(db, hipGetLastError());
+        return fail(db, VISFS_BA_ERR_DEVICE, "a launch of the query was refused");
+    }
     HIP_TRY(db, hipMemcpyAsync(db->h_io, db->d_result, sizeof(visfs_place_result), hipMemcpyDeviceToHost, db->stream));
     HIP_TRY(db, hipStreamSynchronize(db->stream));
     std::memcpy(R, db->h_io, sizeof(*R));
@@ -400,6 +337,31 @@ int device_query(visfs_place_db* db, const visfs_place_set* s, const Params& p, 
 }
 
 }  // namespace
+
+namespace place {
+
+int prepare_query(const visfs_place_db* db, const visfs_place_set* s, const visfs_place_params& p, Params* q, const char** why) {
+    int rc = check_params(p, why);
+    if (rc != VISFS_BA_OK) return rc;
+    rc = flavour_text(db, s, why);
+    if (rc != VISFS_BA_OK) return rc;
+    q->first = std::min(p.first_slot, db->size);
+    q->n_slots = std::min(p.last_slot, db->size) - q->first;
+    q->max_distance = p.max_distance; q->ratio_num = p.ratio_num; q->ratio_den = p.ratio_den; q->min_matches = p.min_matches;
+    q->cross_check = p.cross_check ? 1 : 0;
+    return VISFS_BA_OK;
+}
+
+int launch_query(const visfs_place_db* db, const visfs_place_set* s, const Params& p, const Params* d_prm, visfs_place_result* d_R) {
+    hipLaunchKernelGGL(k_place_match, dim3((unsigned)std::max(p.n_slots, 1)), dim3(kMatchT), 0, db->stream, s->d_set, s->n, db->d_slots,
+                       db->d_pay, d_prm, db->d_match, db->d_counts);
+    if (hipPeekAtLastError() != hipSuccess) return -1;
+    hipLaunchKernelGGL(k_place_rank, dim3(1), dim3(kRankT), 0, db->stream, s->d_set, s->n, db->d_pay, d_prm, db->d_match, db->d_counts, d_R);
+    if (hipPeekAtLastError() != hipSuccess) return -1;
+    return VISFS_PLACE_QUERY_LAUNCHES;
+}
+
+}  // namespace place
 
 // ====================================================================== exported C ABI
 extern "C" {
@@ -605,15 +567,10 @@ int visfs_place_db_size(const visfs_place_db* db, int32_t* n_slots) {
 int visfs_place_query(visfs_place_db* db, const visfs_place_set* s, const visfs_place_params* p, visfs_place_result* result) {
     if (!db || !s || !p || !result) return VISFS_BA_ERR_BAD_ARGUMENT;
     return guarded(db, [&]() -> int {
-        int rc = check_params(db, *p);
-        if (rc != VISFS_BA_OK) return rc;
-        rc = same_flavour(db, s);
-        if (rc != VISFS_BA_OK) return rc;
         Params q;
-        q.first = std::min(p->first_slot, db->size);
-        q.n_slots = std::min(p->last_slot, db->size) - q.first;
-        q.max_distance = p->max_distance; q.ratio_num = p->ratio_num; q.ratio_den = p->ratio_den; q.min_matches = p->min_matches;
-        q.cross_check = p->cross_check ? 1 : 0;
+        const char* why = "";
+        const int rc = prepare_query(db, s, *p, &q, &why);
+        if (rc != VISFS_BA_OK) return fail(db, rc, why);
         if (db->device) return device_query(db, s, q, result);
         host_query(db, s, q, result);
         db->counts = Counts4{};

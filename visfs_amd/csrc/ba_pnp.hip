@@ -211,20 +211,26 @@ struct DevicePolicy {
     }
 };
 
-__device__ __forceinline__ void pnp_refine_body(const RefineArgs& A) {
+// The refinement from a start model: what the winner-reading body below and the refine-only kernel share.
+template <bool Polish>
+__device__ __forceinline__ void pnp_refine_run(const RefineArgs& A, bool have_winner, const Rt& W, Result& res) {
     __shared__ int32_t s_lists[2][kMaxPoints];
     __shared__ float s_errs[kMaxPoints];
     __shared__ double s_red[PN_T / 64][28];
     __shared__ int32_t s_wcount[PN_T / 64];
     __shared__ float s_mv[2];
     DevicePolicy pol{ A, s_lists, s_errs, s_red, s_wcount, s_mv, (int)threadIdx.x, (int)(threadIdx.x >> 6), (int)(threadIdx.x & 63) };
+    refine_all<DevicePolicy, Polish>(pol, A.K, have_winner, W, A.min_inliers, A.refine_iterations, A.thr0, A.sigma, res);
+    if (threadIdx.x == 0) *A.res = res;
+}
+
+__device__ __forceinline__ void pnp_refine_body(const RefineArgs& A) {
     const unsigned long long key = *A.key;
     Result res;
     res.winner = key ? (int32_t)(0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFull)) : -1;
     res.winner_count = (int32_t)(key >> 32);
     Rt W = load_model(A.models + 12 * (size_t)(key ? res.winner : 0));
-    refine_all(pol, A.K, key != 0, W, A.min_inliers, A.refine_iterations, A.thr0, A.sigma, res);
-    if (threadIdx.x == 0) *A.res = res;
+    pnp_refine_run<false>(A, key != 0, W, res);
 }
 
 __global__ __launch_bounds__(PN_T) void k_pnp_refine(RefineArgs A) { pnp_refine_body(A); }
@@ -239,6 +245,33 @@ __global__ __launch_bounds__(PN_T) void k_pnp_refine_g(const PnpRec* __restrict_
     A.thr0 = S.thr; A.sigma = S.sigma; A.key = r->key; A.models = r->models; A.res = r->res; A.inliers = r->inliers;
     A.pass_tq = r->pass_tq; A.pass_thr = r->pass_thr; A.pass_cnt = r->pass_cnt; A.pass_lists = r->pass_lists;
     pnp_refine_body(A);
+}
+
+// Member blockIdx.z of a refine-only call (include/visfs_place_verify.h): no search, the loop of section 9e
+// steps 5 and 6 on the member's rows started from the model another call has left in device memory.
+__global__ __launch_bounds__(PN_T) void k_pnp_refine_from_g(const RefineFromRec* __restrict__ recs, PnpShape S) {
+    const RefineFromRec* r = recs + blockIdx.z;
+    if (!*r->ran) return;
+    const int32_t m = min(*r->m, kMaxPoints);
+    if (m < S.min_inliers) return;
+    RefineArgs A;
+    A.rows = r->rows; A.m = m; A.cap = r->cap; A.K = r->K; A.min_inliers = S.min_inliers; A.refine_iterations = S.refine_iterations;
+    A.thr0 = S.thr; A.sigma = S.sigma; A.key = nullptr; A.models = nullptr; A.res = r->res; A.inliers = r->inliers;
+    A.pass_tq = r->pass_tq; A.pass_thr = r->pass_thr; A.pass_cnt = r->pass_cnt; A.pass_lists = r->pass_lists;
+    Result res;
+    res.winner = -1; res.winner_count = 0;
+    double tq[7];
+#pragma unroll
+    for (int i = 0; i < 7; ++i) tq[i] = r->start->tq[i];
+    const Rt W = tq_to_rt(tq);
+    pnp_refine_run<true>(A, true, W, res);
+}
+
+int group_refine_from(hipStream_t stream, int n, const RefineFromRec* d_recs, const PnpShape& S, flow::GroupCounts* cnt) {
+    hipLaunchKernelGGL(k_pnp_refine_from_g, dim3(1, 1, (unsigned)n), dim3(PN_T), 0, stream, d_recs, S);
+    if (hipGetLastError() != hipSuccess) return VISFS_BA_ERR_DEVICE;
+    ++cnt->launches;
+    return VISFS_BA_OK;
 }
 
 int group_pnp(hipStream_t stream, int n, const PnpRec* d_recs, const PnpShape& S, flow::GroupCounts* cnt) {
@@ -506,6 +539,32 @@ int check_params(const visfs_pnp_params& q, const visfs_pnp_camera& c, const cha
     bool fin = std::isfinite(c.fx) && std::isfinite(c.fy) && std::isfinite(c.cx) && std::isfinite(c.cy) && c.fx != 0.0 && c.fy != 0.0;
     for (int i = 0; i < 12; ++i) fin = fin && std::isfinite(c.Tir[i]);
     if (!fin) { why = "a camera value is not finite or a focal length is zero"; return VISFS_BA_ERR_BAD_ARGUMENT; }
+    return VISFS_BA_OK;
+}
+
+const Result& last_result(const visfs_pnp* p) { return p->res; }
+
+// The twin of k_pnp_refine_from_g on a host solver, which keeps the state visfs_pnp_download reports (no hypotheses, the passes).
+int host_refine_from(visfs_pnp* p, const Row* rows, int32_t m, const Cam& K, const PnpShape& S, const double start_tq[7], Result* res,
+                     std::vector<int32_t>* inliers) {
+    if (!p || p->device || m < 0 || m > p->cap) return VISFS_BA_ERR_BAD_ARGUMENT;
+    p->rows.assign(rows, rows + m);
+    p->samples.clear(); p->vc.clear(); p->models.clear();
+    p->pass_tq.assign(7 * kMaxRefine, 0.0); p->pass_thr.assign(kMaxRefine, 0.0f); p->pass_cnt.assign(kMaxRefine, 0);
+    p->pass_lists.assign((size_t)kMaxRefine * m, 0);
+    p->solved = true; p->last_m = m; p->last_hyp = 0; p->last_passes = 0;
+    p->res = Result{}; p->res.winner = -1;
+    inliers->clear();
+    if (m >= S.min_inliers) {
+        HostPolicy pol;
+        pol.p = p; pol.rows = p->rows.data(); pol.m = m;
+        pol.lists[0].assign(m, 0); pol.lists[1].assign(m, 0); pol.errs.assign(m, 0.0f);
+        const Rt W = tq_to_rt(start_tq);
+        refine_all<HostPolicy, true>(pol, K, true, W, S.min_inliers, S.refine_iterations, S.thr, S.sigma, p->res);
+        *inliers = pol.out;
+        p->last_passes = p->res.n_passes;
+    }
+    *res = p->res;
     return VISFS_BA_OK;
 }
 

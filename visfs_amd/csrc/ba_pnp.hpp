@@ -304,6 +304,31 @@ BA_HD void refit(P& pol, const Cam& K, int list, int n, double tq[7]) {
     }
 }
 
+// The convergence polish of a refit that a refine-only call adds: the refit above accepts a step only when the
+// cost falls and stops at a step below kStepStop, which leaves the pose up to about 1e-10 from the least-squares optimum (near it a
+// step changes the cost by less than a double resolves).  From there undamped Gauss-Newton steps are taken while they stay inside
+// kPolishBasin, where such a step cannot move the pose by more than the basin; a refit that ended further out is left as it is.
+constexpr int kPolishSteps = 3;
+constexpr double kPolishBasin = 1e-6, kPolishStop = 1e-14;
+template <class P>
+BA_HD void polish(P& pol, const Cam& K, int list, int n, double tq[7]) {
+    double acc[28];
+    for (int it = 0; it < kPolishSteps; ++it) {
+        pol.sums(tq_to_rt(tq), K, list, n, acc, true);
+        double d[6];
+        if (!damped_solve(acc, 0.0, d)) break;
+        double step = 0.0;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) if (fabs(d[i]) > step) step = fabs(d[i]);
+        if (!(step < kPolishBasin)) break;
+        double cand[7];
+        visfs_ba::pose_oplus(tq, d, cand);
+#pragma unroll
+        for (int i = 0; i < 7; ++i) tq[i] = cand[i];
+        if (step < kPolishStop) break;
+    }
+}
+
 // ---- steps 5 and 6: from the winner to the returned model and list ---------------------------------------------------------------
 // The policy keeps two row lists (0 and 1) and the float errors of the last selection:
 //   select(T, K, thr, list) -> count : list := rows with error <= thr, ascending; the errors in the same order
@@ -311,7 +336,8 @@ BA_HD void refit(P& pol, const Cam& K, int list, int n, double tq[7]) {
 //   same(n)                          : the first n entries of the two lists are equal
 //   record(pass, tq, thr, list, n)   : test hook
 //   finish(list, n)                  : the returned list
-template <class P>
+//   Polish: every refit is followed by polish() (the refine-only call of section 9x; the pose guess of section 9e runs without it)
+template <class P, bool Polish = false>
 BA_HD void refine_all(P& pol, const Cam& K, bool have_winner, const Rt& W, int min_inliers, int refine_iterations, float thr0, float sigma,
                       Result& res) {
     res.n_passes = 0; res.n_inliers = 0;
@@ -323,6 +349,7 @@ BA_HD void refine_all(P& pol, const Cam& K, bool have_winner, const Rt& W, int m
     double tq[7];
     rt_to_tq(W, tq);
     refit(pol, K, 0, n0, tq);
+    if constexpr (Polish) polish(pol, K, 0, n0, tq);
 #pragma unroll
     for (int i = 0; i < 7; ++i) res.refit0[i] = tq[i];
     int prev = 0, nprev = n0, cur = 1, ncur = 0;
@@ -332,6 +359,7 @@ BA_HD void refine_all(P& pol, const Cam& K, bool have_winner, const Rt& W, int m
     float thr = thr0;
     for (;;) {
         refit(pol, K, prev, nprev, tq);
+        if constexpr (Polish) polish(pol, K, prev, nprev, tq);
         h4 = h3; h3 = h2; h2 = h1; h1 = nprev; ++hist;
         ncur = pol.select(tq_to_rt(tq), K, thr, cur);
         if (res.n_passes < kMaxRefine) pol.record(res.n_passes, tq, thr, cur, ncur);
@@ -375,6 +403,20 @@ struct PnpRec {
     Cam K;
     int32_t cap;                               // row stride of pass_lists
     int32_t skip;                              // the member takes no part in this call
+};
+
+// A member of a refine-only call (include/visfs_place_verify.h): k_pnp_refine_from_g runs the refinement loop
+// on the member's rows from the model `start` holds.  *ran == 0: nothing runs for the member and its result stays what its rows
+// kernel wrote; the same holds with fewer rows than min_inliers.
+struct RefineFromRec {
+    const int32_t* m;
+    const Row* rows;
+    const int32_t* ran;
+    const Result* start;                       // its tq is the start model
+    Result* res; int32_t* inliers;
+    double* pass_tq; float* pass_thr; int32_t* pass_cnt; int32_t* pass_lists;
+    Cam K;
+    int32_t cap, pad;
 };
 
 // what every member of a call shares; min_inliers is already raised to 4
