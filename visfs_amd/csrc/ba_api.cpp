@@ -62,15 +62,15 @@ struct PackedWindow {
 // One resident window: device arena + host mirrors of what the host needs later.
 struct Workspace {
     hipStream_t stream = nullptr;
-    char* d_base = nullptr;  size_t d_cap = 0;
-    char* h_base = nullptr;  size_t h_cap = 0;     // pinned staging: the index section (same layout as on the device), later the outputs of a solve
-    char* d_prim = nullptr;  size_t d_prim_cap = 0;   // the primary section (poses, landmarks, observations, odometry / laser measurements) ...
-    char* h_prim = nullptr;  size_t h_prim_cap = 0;   // ... and its pinned staging arena: the window layer packs straight into it
-    LmState* h_state = nullptr;                    // pinned
+    DeviceBuf<char> d_base;
+    PinnedBuf<char> h_base;                        // pinned staging: the index section (same layout as on the device), later the outputs of a solve
+    DeviceBuf<char> d_prim;                        // the primary section (poses, landmarks, observations, odometry / laser measurements) ...
+    PinnedBuf<char> h_prim;                        // ... and its pinned staging arena: the window layer packs straight into it
+    PinnedBuf<LmState> h_state;                    // pinned
     LmState* h_state_dev = nullptr;                // ... at its device address: the last launch of a lone window's sequence writes the state there itself
-    LmState* d_state = nullptr;                    // the LM state at a FIXED device address (DeviceGraph::st): survives uploads
-    DeviceGraph* d_graph = nullptr;                // the resident window's DeviceGraph at a fixed device address (re-written by every upload) ...
-    DeviceGraph* h_graph = nullptr;                // ... and its pinned source
+    DeviceBuf<LmState> d_state;                    // the LM state at a FIXED device address (DeviceGraph::st): survives uploads
+    DeviceBuf<DeviceGraph> d_graph;                // the resident window's DeviceGraph at a fixed device address (re-written by every upload) ...
+    PinnedBuf<DeviceGraph> h_graph;                // ... and its pinned source
     // per-frame replay (round 4): launch sequences of visfs_ba_solve_window captured per geometry class; they read the graph from d_graph,
     // so a sequence captured for one frame's window serves the next frames' windows of the same class
     struct FrameGraph { LaunchDims d; int n0, n1, half, half2, solver, flags; hipGraphExec_t exec; int seen; uint64_t last_use; };
@@ -131,7 +131,7 @@ struct Workspace {
     int64_t active[VISFS_BA_K_COUNT] = { 0 };
     // marginal covariances (visfs_ba_graph_covariance): device scratch allocated at the first call, never at upload — the factor and
     // the band of Sigma ([Npf][band_B + 1][36] each), the landmark marginals ([Nl][9]) and the pivot flag
-    char* d_cov = nullptr; size_t d_cov_cap = 0;
+    DeviceBuf<char> d_cov;
     int n6() const { return 6 * g.Npf; }
 };
 
@@ -172,10 +172,9 @@ static void prof_harvest(Workspace& w) {
 
 // device / pinned scratch of a batched run: the DeviceGraph array the kernels index with blockIdx.y, and the gathered LM states
 struct BatchScratch {
-    DeviceGraph* d_graphs = nullptr; size_t cap_graphs = 0;
-    size_t cap_states = 0;
-    LmState* d_lm = nullptr; LmState* h_lm = nullptr;      // [cap_states] whole LM states, gathered at the end of a run
-    DeviceGraph* d_all = nullptr; size_t cap_all = 0;      // every graph of a resident batch (visfs_ba_batch_upload), for the one-launch reset
+    DeviceBuf<DeviceGraph> d_graphs;
+    DeviceBuf<LmState> d_lm; PinnedBuf<LmState> h_lm;      // whole LM states, gathered at the end of a run; h_lm is made last, its capacity is the pair's
+    DeviceBuf<DeviceGraph> d_all;                          // every graph of a resident batch (visfs_ba_batch_upload), for the one-launch reset
     std::vector<DeviceGraph> host_graphs;                  // source of the asynchronous H2D copy of d_graphs: must outlive it
     LaunchDims all_dims{};
 };
@@ -223,33 +222,25 @@ WorkerPool* host_pool(visfs_ba_handle* h) {
 }
 
 void ws_release(Workspace& w) {
-    if (w.d_base) (void)hipFree(w.d_base);
-    if (w.h_base) (void)hipHostFree(w.h_base);
-    if (w.d_prim) (void)hipFree(w.d_prim);
-    if (w.h_prim) (void)hipHostFree(w.h_prim);
-    if (w.h_state) (void)hipHostFree(w.h_state);
     for (hipEvent_t e : w.ev_pool) (void)hipEventDestroy(e);
     if (w.graph_exec) (void)hipGraphExecDestroy(w.graph_exec);
     for (auto& fg : w.frame_graphs) if (fg.exec) (void)hipGraphExecDestroy(fg.exec);
-    if (w.d_state) (void)hipFree(w.d_state);
-    if (w.d_graph) (void)hipFree(w.d_graph);
-    if (w.d_cov) (void)hipFree(w.d_cov);
-    if (w.h_graph) (void)hipHostFree(w.h_graph);
-    if (w.stream) (void)hipStreamDestroy(w.stream);
-    w = Workspace{};
+    const hipStream_t stream = w.stream;
+    w = Workspace{};                               // its owners free the buffers, before the stream goes
+    if (stream) (void)hipStreamDestroy(stream);
 }
 
 int ws_init(visfs_ba_handle* h, Workspace& w) {
     if (w.stream) return VISFS_BA_OK;
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking));
-    HIP_TRY(h, hipHostMalloc(reinterpret_cast<void**>(&w.h_state), sizeof(LmState), hipHostMallocDefault));
-    std::memset(w.h_state, 0, sizeof(LmState));
-    HIP_TRY(h, hipHostGetDevicePointer(reinterpret_cast<void**>(&w.h_state_dev), w.h_state, 0));
-    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&w.d_state), sizeof(LmState)));
-    HIP_TRY(h, hipMemset(w.d_state, 0, sizeof(LmState)));                       // (decide_epoch counts on from zero, across uploads)
-    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&w.d_graph), sizeof(DeviceGraph)));
-    HIP_TRY(h, hipHostMalloc(reinterpret_cast<void**>(&w.h_graph), sizeof(DeviceGraph), hipHostMallocDefault));
+    RC_TRY(w.h_state.alloc(h, 1));
+    std::memset(w.h_state.get(), 0, sizeof(LmState));
+    HIP_TRY(h, hipHostGetDevicePointer(reinterpret_cast<void**>(&w.h_state_dev), w.h_state.get(), 0));
+    RC_TRY(w.d_state.alloc(h, 1));
+    HIP_TRY(h, hipMemset(w.d_state.get(), 0, sizeof(LmState)));                       // (decide_epoch counts on from zero, across uploads)
+    RC_TRY(w.d_graph.alloc(h, 1));
+    RC_TRY(w.h_graph.alloc(h, 1));
     return VISFS_BA_OK;
 }
 
@@ -284,22 +275,14 @@ void layout_prim(Arena& A, DeviceGraph& g, const PrimSizes& z) {
 size_t prim_bytes(const PrimSizes& z) { Arena a{ nullptr, 0, 0 }; DeviceGraph g{}; layout_prim(a, g, z); return (a.used + 255) & ~size_t(255); }
 int ensure_prim(visfs_ba_handle* h, Workspace& w, size_t bytes) {
     HIP_TRY(h, hipSetDevice(h->device));
-    if (w.h_prim_cap < bytes) {
+    if (w.h_prim.cap() < bytes) {
         // (the previous upload's host-to-device copy reads the arena that is about to be replaced)
         if (w.stream) HIP_TRY(h, hipStreamSynchronize(w.stream));
-        if (w.h_prim) (void)hipHostFree(w.h_prim);
-        w.h_prim = nullptr; w.h_prim_cap = 0;
-        const size_t want = bytes + bytes / 4;                                                   // a sliding window grows and shrinks by a few observations per frame
-        HIP_TRY(h, hipHostMalloc(reinterpret_cast<void**>(&w.h_prim), want, hipHostMallocDefault));
-        w.h_prim_cap = want;
+        RC_TRY(w.h_prim.alloc(h, bytes + bytes / 4));                                            // a sliding window grows and shrinks by a few observations per frame
     }
-    if (w.d_prim_cap < bytes) {
+    if (w.d_prim.cap() < bytes) {
         if (w.stream) HIP_TRY(h, hipStreamSynchronize(w.stream));
-        if (w.d_prim) (void)hipFree(w.d_prim);
-        w.d_prim = nullptr; w.d_prim_cap = 0;
-        const size_t want = bytes + bytes / 4;
-        HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&w.d_prim), want));
-        w.d_prim_cap = want;
+        RC_TRY(w.d_prim.alloc(h, bytes + bytes / 4));
     }
     return VISFS_BA_OK;
 }
@@ -464,7 +447,7 @@ int stage_primary(visfs_ba_handle* h, Workspace& w, const visfs_ba_graph* gr, co
     if (!opt.in_staging) HIP_TRY(h, hipStreamSynchronize(w.stream));        // the previous upload's H2D copy reads the pinned staging arenas filled below
     const int rc = ensure_prim(h, w, pbytes);
     if (rc != VISFS_BA_OK) return rc;
-    { Arena hp{ w.h_prim, w.h_prim_cap, 0 }; layout_prim(hp, hg, pz); }
+    { Arena hp{ w.h_prim.get(), w.h_prim.cap(), 0 }; layout_prim(hp, hg, pz); }
     if (!opt.in_staging) {
         double* p0 = const_cast<double*>(hg.pose0);
         for (int i = 0; i < Np; ++i) { for (int q = 0; q < 7; ++q) p0[POSE_STRIDE * i + q] = gr->pose_tq[7 * i + q]; p0[POSE_STRIDE * i + 7] = 0.0; }
@@ -490,30 +473,22 @@ int stage_primary(visfs_ba_handle* h, Workspace& w, const visfs_ba_graph* gr, co
     if (P.Npf) std::memcpy(const_cast<int32_t*>(hg.free_pose), P.free_pose.data(), (size_t)P.Npf * 4);
     if (Nz && opt.d_grid) {
         // the grid is the last array of the section: everything before it from the staging arena, the grid from device memory
-        const size_t at = (size_t)(reinterpret_cast<const char*>(hg.grid.cost) - w.h_prim);
-        HIP_TRY(h, hipMemcpyAsync(w.d_prim, w.h_prim, at, hipMemcpyHostToDevice, w.stream));
-        HIP_TRY(h, hipMemcpyAsync(w.d_prim + at, opt.d_grid, grid_cells * 4, hipMemcpyDeviceToDevice, w.stream));
-    } else HIP_TRY(h, hipMemcpyAsync(w.d_prim, w.h_prim, pbytes, hipMemcpyHostToDevice, w.stream));
+        const size_t at = (size_t)(reinterpret_cast<const char*>(hg.grid.cost) - w.h_prim.get());
+        HIP_TRY(h, hipMemcpyAsync(w.d_prim.get(), w.h_prim.get(), at, hipMemcpyHostToDevice, w.stream));
+        HIP_TRY(h, hipMemcpyAsync(w.d_prim.get() + at, opt.d_grid, grid_cells * 4, hipMemcpyDeviceToDevice, w.stream));
+    } else HIP_TRY(h, hipMemcpyAsync(w.d_prim.get(), w.h_prim.get(), pbytes, hipMemcpyHostToDevice, w.stream));
     return VISFS_BA_OK;
 }
 
 // the device arena (index + mutable sections) and the pinned arena, grown when the window needs more
 int ensure_arenas(visfs_ba_handle* h, Workspace& w, const size_t total_bytes, const size_t host_need) {
-    if (w.d_cap < total_bytes) {
+    if (w.d_base.cap() < total_bytes) {
         HIP_TRY(h, hipStreamSynchronize(w.stream));
-        if (w.d_base) (void)hipFree(w.d_base);
-        w.d_base = nullptr; w.d_cap = 0;
-        const size_t want = total_bytes + total_bytes / 8;
-        HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&w.d_base), want));
-        w.d_cap = want;
+        RC_TRY(w.d_base.alloc(h, total_bytes + total_bytes / 8));
     }
-    if (w.h_cap < host_need) {
+    if (w.h_base.cap() < host_need) {
         HIP_TRY(h, hipStreamSynchronize(w.stream));
-        if (w.h_base) (void)hipHostFree(w.h_base);
-        w.h_base = nullptr; w.h_cap = 0;
-        const size_t want = host_need + host_need / 8;
-        HIP_TRY(h, hipHostMalloc(reinterpret_cast<void**>(&w.h_base), want, hipHostMallocDefault));
-        w.h_cap = want;
+        RC_TRY(w.h_base.alloc(h, host_need + host_need / 8));
     }
     return VISFS_BA_OK;
 }
@@ -639,7 +614,7 @@ int ws_upload(visfs_ba_handle* h, Workspace& w, const visfs_ba_graph* gr, const 
 
     // ---- the INDEX section and the mutable section: one device arena, the index part staged in pinned memory with the same layout
     const size_t static_bytes = layout_index(IndexWalk{ Arena{ nullptr, 0, 0 }, false }, hg, P);
-    DynOpts dyo; dyo.raw_refs = pz.raw_refs; dyo.dogleg = ceres && prm.trust_region == 1; dyo.st = w.d_state;
+    DynOpts dyo; dyo.raw_refs = pz.raw_refs; dyo.dogleg = ceres && prm.trust_region == 1; dyo.st = w.d_state.get();
     DeviceGraph dg{};
     int32_t* d_hist = nullptr;
     size_t zero_end = 0;
@@ -650,23 +625,23 @@ int ws_upload(visfs_ba_handle* h, Workspace& w, const visfs_ba_graph* gr, const 
     rc = ensure_arenas(h, w, total_bytes, host_need);
     if (rc != VISFS_BA_OK) return rc;
     lap("alloc");
-    layout_index(IndexWalk{ Arena{ w.h_base, w.h_cap, 0 }, true }, hg, P);          // fill the index staging
+    layout_index(IndexWalk{ Arena{ w.h_base.get(), w.h_base.cap(), 0 }, true }, hg, P);          // fill the index staging
     lap("stage fill");
     // device pointers: same offsets
-    { Arena dp{ w.d_prim, w.d_prim_cap, 0 }; layout_prim(dp, dg, pz); }
-    layout_index(IndexWalk{ Arena{ w.d_base, w.d_cap, 0 }, false }, dg, P);
-    layout_dyn(Arena{ w.d_base, w.d_cap, static_bytes }, dg, P, dyo, &d_hist, &zero_end);
+    { Arena dp{ w.d_prim.get(), w.d_prim.cap(), 0 }; layout_prim(dp, dg, pz); }
+    layout_index(IndexWalk{ Arena{ w.d_base.get(), w.d_base.cap(), 0 }, false }, dg, P);
+    layout_dyn(Arena{ w.d_base.get(), w.d_base.cap(), static_bytes }, dg, P, dyo, &d_hist, &zero_end);
     fill_graph_scalars(dg, gr, prm, P, sw, w.batch_member, opt.baseline);
     w.g = dg;
     // the same graph at its fixed device address (what the launch sequences of the per-frame path read: Many{ d_graph, d_state })
-    *w.h_graph = dg;
-    HIP_TRY(h, hipMemcpyAsync(w.d_graph, w.h_graph, sizeof(DeviceGraph), hipMemcpyHostToDevice, w.stream));
+    *w.h_graph.get() = dg;
+    HIP_TRY(h, hipMemcpyAsync(w.d_graph.get(), w.h_graph.get(), sizeof(DeviceGraph), hipMemcpyHostToDevice, w.stream));
     choose_unit_form(w, prm, P, sw);
     w.n_pairs = P.npairs; w.device_bytes = total_bytes + pbytes;
     w.free_pose = P.free_pose; w.blk_i = P.blk_i; w.blk_j = P.blk_j; w.pose_free = P.pose_free;
     w.odo_i.assign(gr->odo_from, gr->odo_from + G.Ne); w.odo_j.assign(gr->odo_to, gr->odo_to + G.Ne);
-    if (static_bytes) HIP_TRY(h, hipMemcpyAsync(w.d_base, w.h_base, static_bytes, hipMemcpyHostToDevice, w.stream));
-    HIP_TRY(h, hipMemsetAsync(w.d_base + static_bytes, 0, zero_end - static_bytes, w.stream));
+    if (static_bytes) HIP_TRY(h, hipMemcpyAsync(w.d_base.get(), w.h_base.get(), static_bytes, hipMemcpyHostToDevice, w.stream));
+    HIP_TRY(h, hipMemsetAsync(w.d_base.get() + static_bytes, 0, zero_end - static_bytes, w.stream));
     if (configure_kernels(w.g) != 0) { h->err = "hipFuncSetAttribute failed"; return VISFS_BA_ERR_DEVICE; }
     launch_build_index(w.g, d_hist, w.stream);             // lm_ptr, obs_ok, pose_obs / obs_ppos: never exist on the host
     launch_build_pairs(w.g, w.stream);                     // the co-observation pair lists never exist on the host
@@ -713,18 +688,18 @@ int ws_read_state(visfs_ba_handle* h, Workspace& w, const bool mirrored = false)
     if (mirrored && poll_mode != 0 && !w.want_outputs && w.recs.empty()) {
         const auto t0 = std::chrono::steady_clock::now();
         for (int spin = 1;; ++spin) {
-            if (mirror_seq_of(w.h_state) == want_seq) { w.outputs_staged = false; w.mirror_seq = want_seq; w.state_mirrored += 1; return VISFS_BA_OK; }
+            if (mirror_seq_of(w.h_state.get()) == want_seq) { w.outputs_staged = false; w.mirror_seq = want_seq; w.state_mirrored += 1; return VISFS_BA_OK; }
 #if defined(__x86_64__) || defined(__i386__)
             __builtin_ia32_pause();
 #endif
             if ((spin & 1023) == 0 && std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count() > STATE_POLL_US) break;
         }
     }
-    if (!mirrored) HIP_TRY(h, hipMemcpyAsync(w.h_state, w.g.st, sizeof(LmState), hipMemcpyDeviceToHost, w.stream));
+    if (!mirrored) HIP_TRY(h, hipMemcpyAsync(w.h_state.get(), w.g.st, sizeof(LmState), hipMemcpyDeviceToHost, w.stream));
     w.outputs_staged = false;
     const OutputStage os = output_stage_of(w.g);
     // (the arena is also the source of the upload's H2D copy: that copy precedes these on the same stream, so it has read its data)
-    const bool with_outputs = w.want_outputs && w.h_base && os.end <= w.h_cap;
+    const bool with_outputs = w.want_outputs && w.h_base.get() && os.end <= w.h_base.cap();
     if (with_outputs) {
         // which estimate buffer is the final one is only known from the state that is coming back: fetch both (poses are tiny, landmarks
         // 24 bytes each) — the caller's download then needs neither a copy nor a second synchronisation
@@ -735,20 +710,20 @@ int ws_read_state(visfs_ba_handle* h, Workspace& w, const bool mirrored = false)
         if (one_span) {
             // the device arena holds the five arrays in the staging layout (ws_upload): one copy instead of five — each is a few microseconds
             // of copy-engine latency on the tail of every per-frame call
-            HIP_TRY(h, hipMemcpyAsync(w.h_base, d0, os.end, hipMemcpyDeviceToHost, w.stream));
+            HIP_TRY(h, hipMemcpyAsync(w.h_base.get(), d0, os.end, hipMemcpyDeviceToHost, w.stream));
         } else {
             for (int k = 0; k < 2; ++k) {
-                HIP_TRY(h, hipMemcpyAsync(w.h_base + os.pose[k], g.pose[k], (size_t)g.Np * POSE_STRIDE * 8, hipMemcpyDeviceToHost, w.stream));
-                if (g.Nl) HIP_TRY(h, hipMemcpyAsync(w.h_base + os.pt[k], g.pt[k], (size_t)g.Nl * 24, hipMemcpyDeviceToHost, w.stream));
+                HIP_TRY(h, hipMemcpyAsync(w.h_base.get() + os.pose[k], g.pose[k], (size_t)g.Np * POSE_STRIDE * 8, hipMemcpyDeviceToHost, w.stream));
+                if (g.Nl) HIP_TRY(h, hipMemcpyAsync(w.h_base.get() + os.pt[k], g.pt[k], (size_t)g.Nl * 24, hipMemcpyDeviceToHost, w.stream));
             }
-            if (g.No) HIP_TRY(h, hipMemcpyAsync(w.h_base + os.out, g.obs_outlier, (size_t)g.No, hipMemcpyDeviceToHost, w.stream));
+            if (g.No) HIP_TRY(h, hipMemcpyAsync(w.h_base.get() + os.out, g.obs_outlier, (size_t)g.No, hipMemcpyDeviceToHost, w.stream));
         }
     }
     HIP_TRY(h, hipStreamSynchronize(w.stream));
     if (mirrored) {
-        if (mirror_seq_of(w.h_state) == want_seq) w.state_mirrored += 1;
+        if (mirror_seq_of(w.h_state.get()) == want_seq) w.state_mirrored += 1;
         else {                                            // (never expected: the sequence did not end in a mirroring launch after all)
-            HIP_TRY(h, hipMemcpyAsync(w.h_state, w.g.st, sizeof(LmState), hipMemcpyDeviceToHost, w.stream));
+            HIP_TRY(h, hipMemcpyAsync(w.h_state.get(), w.g.st, sizeof(LmState), hipMemcpyDeviceToHost, w.stream));
             HIP_TRY(h, hipStreamSynchronize(w.stream));
         }
     }
@@ -931,7 +906,7 @@ int ws_optimize_run(visfs_ba_handle* h, Workspace& w, visfs_ba_stats* stats, con
     // default is the by-value path.
     const int frame_mode = env_int("VISFS_BA_FRAME_GRAPH", 0);   // 0: by-value path, 1: fixed-address path without capture, 2: with (read per call: tests switch it)
     const bool band_direct = solver != 2 && !w.small_solve && w.g.band_B >= 0;
-    const bool ref_mode = frame_mode != 0 && fresh_upload && w.solves_since_upload == 0 && !fallback_run && !w.prof_mask && !w.batch_member && w.d_graph && w.d_state &&
+    const bool ref_mode = frame_mode != 0 && fresh_upload && w.solves_since_upload == 0 && !fallback_run && !w.prof_mask && !w.batch_member && w.d_graph.get() && w.d_state.get() &&
                           (h->prm.framework == 0 || w.small_solve || band_direct) && (solver == 2 || w.small_solve || band_direct) && !(w.spec && !w.spec_fused) &&
                           w.g.Np <= MAX_STAGED_POSES && w.g.Npf <= MAX_PCG_ONE_ROW_POSES && !w.g.pcg_cu;
     const LaunchDims fd = ref_mode ? dims_class(dims_of(w.g)) : LaunchDims{};
@@ -943,15 +918,15 @@ int ws_optimize_run(visfs_ba_handle* h, Workspace& w, visfs_ba_stats* stats, con
     LmState* const state_mirror = (phase_on_board && !w.prof_mask) ? w.h_state_dev : nullptr;   // (profiling runs keep the copy)
     auto enqueue_units = [&](int n, bool first) {
         for (int u = 0; u < n; ++u) {
-            if (ref_mode) launch_unit_batch(w.d_graph, 1, fd, first, w.small_solve, solver, w.fused_decide, w.spec_fused, w.stream, w.d_state);
+            if (ref_mode) launch_unit_batch(w.d_graph.get(), 1, fd, first, w.small_solve, solver, w.fused_decide, w.spec_fused, w.stream, w.d_state.get());
             else enqueue_unit(h, w, first);
             first = false;
         }
     };
     auto phase_end = [&](int which) {
         if (ref_mode) {
-            if (which == 0) launch_phase_end_batch(w.d_graph, 1, fd, 0, 1, half2, w.stream, w.d_state);
-            else launch_phase_end_batch(w.d_graph, 1, fd, 1, 0, 0, w.stream, w.d_state);
+            if (which == 0) launch_phase_end_batch(w.d_graph.get(), 1, fd, 0, 1, half2, w.stream, w.d_state.get());
+            else launch_phase_end_batch(w.d_graph.get(), 1, fd, 1, 0, 0, w.stream, w.d_state.get());
             return;
         }
         ProfScope p(w, VISFS_BA_K_PHASE_END);
@@ -1085,7 +1060,7 @@ int ws_optimize(visfs_ba_handle* h, Workspace& w, visfs_ba_stats* stats, const b
     w.solver_now = -1;
     int rc = ws_optimize_run(h, w, stats, fresh_upload, false);
     if (stats) stats->solver_fallback = 0;
-    if (rc != VISFS_BA_ERR_DEVICE || !w.loaded || !w.h_state || !w.h_state->pcg_timeout) return rc;
+    if (rc != VISFS_BA_ERR_DEVICE || !w.loaded || !w.h_state.get() || !w.h_state->pcg_timeout) return rc;
     if (!(pristine && w.direct_ready && h->prm.solver == 2)) return rc;
     w.solver_now = 0;
     w.fallbacks += 1;
@@ -1109,10 +1084,10 @@ int ws_download(visfs_ba_handle* h, Workspace& w, double* pose_tq, double* point
     if (state_fresh && w.outputs_staged && !obs_chi2) {
         // the outputs came back with the state (ws_read_state): no copy, no synchronisation
         const OutputStage os = output_stage_of(g);
-        const double* ps = reinterpret_cast<const double*>(w.h_base + os.pose[sel]);
+        const double* ps = reinterpret_cast<const double*>(w.h_base.get() + os.pose[sel]);
         if (pose_tq) for (int i = 0; i < g.Np; ++i) for (int q = 0; q < 7; ++q) pose_tq[7 * i + q] = ps[POSE_STRIDE * i + q];
-        if (point_xyz && g.Nl) std::memcpy(point_xyz, w.h_base + os.pt[sel], (size_t)g.Nl * 24);
-        if (obs_outlier && g.No) std::memcpy(obs_outlier, w.h_base + os.out, (size_t)g.No);
+        if (point_xyz && g.Nl) std::memcpy(point_xyz, w.h_base.get() + os.pt[sel], (size_t)g.Nl * 24);
+        if (obs_outlier && g.No) std::memcpy(obs_outlier, w.h_base.get() + os.out, (size_t)g.No);
         w.outputs_staged = false;
         return VISFS_BA_OK;
     }
@@ -1122,9 +1097,9 @@ int ws_download(visfs_ba_handle* h, Workspace& w, double* pose_tq, double* point
     const size_t b_pose = pose_tq ? (size_t)g.Np * POSE_STRIDE * 8 : 0, b_pt = (point_xyz && g.Nl) ? (size_t)g.Nl * 24 : 0;
     const size_t b_out = (obs_outlier && g.No) ? (size_t)g.No : 0, b_chi = (obs_chi2 && g.No) ? (size_t)g.No * 8 : 0;
     const size_t o_pose = 0, o_pt = (o_pose + b_pose + 255) & ~size_t(255), o_chi = (o_pt + b_pt + 255) & ~size_t(255), o_out = (o_chi + b_chi + 255) & ~size_t(255);
-    const bool staged = w.h_base && o_out + b_out <= w.h_cap;
+    const bool staged = w.h_base.get() && o_out + b_out <= w.h_base.cap();
     std::vector<double> tmp;
-    char* hb = w.h_base;
+    char* hb = w.h_base.get();
     if (!staged && pose_tq) tmp.resize((size_t)g.Np * POSE_STRIDE);
     if (pose_tq) HIP_TRY(h, hipMemcpyAsync(staged ? (void*)(hb + o_pose) : (void*)tmp.data(), g.pose[sel], b_pose, hipMemcpyDeviceToHost, w.stream));
     if (b_pt) HIP_TRY(h, hipMemcpyAsync(staged ? (void*)(hb + o_pt) : (void*)point_xyz, g.pt[sel], b_pt, hipMemcpyDeviceToHost, w.stream));
@@ -1392,7 +1367,7 @@ int prepare_window(visfs_ba_handle* h, Workspace& w, const visfs_ba_window* win,
     rc = ensure_prim(h, w, prim_bytes(opt.cap));
     if (rc != VISFS_BA_OK) { r->status = rc; return 0; }
     DeviceGraph hg{};
-    { Arena hp{ w.h_prim, w.h_prim_cap, 0 }; layout_prim(hp, hg, opt.cap); }
+    { Arena hp{ w.h_prim.get(), w.h_prim.cap(), 0 }; layout_prim(hp, hg, opt.cap); }
     pk.pose_fixed.resize(Np); pk.point_used.resize(std::max(Nl, 1)); pk.obs_ref.resize(std::max(Nr, 1));
     PackOut o;
     o.pose = const_cast<double*>(hg.pose0); o.pose_stride = POSE_STRIDE; o.pose_fixed = pk.pose_fixed.data(); o.point_used = pk.point_used.data();
@@ -1429,9 +1404,9 @@ int finish_window(visfs_ba_handle* h, Workspace& w, const visfs_ba_window* win, 
     if (w.outputs_staged) {
         const OutputStage os = output_stage_of(w.g);
         const int sel = w.h_state->sel;
-        pose = reinterpret_cast<const double*>(w.h_base + os.pose[sel]); pose_stride = POSE_STRIDE;
-        pts = reinterpret_cast<const double*>(w.h_base + os.pt[sel]);
-        outl = reinterpret_cast<const uint8_t*>(w.h_base + os.out);
+        pose = reinterpret_cast<const double*>(w.h_base.get() + os.pose[sel]); pose_stride = POSE_STRIDE;
+        pts = reinterpret_cast<const double*>(w.h_base.get() + os.pt[sel]);
+        outl = reinterpret_cast<const uint8_t*>(w.h_base.get() + os.out);
         w.outputs_staged = false;
     } else {
         pose_v.resize((size_t)Np * 7); pts_v.resize((size_t)std::max(Nl, 1) * 3); outl_v.resize(std::max(pk.g.n_obs, 1));
@@ -1532,19 +1507,12 @@ int batch_optimize(visfs_ba_handle* h, BatchScratch& bs, const std::vector<Works
     const int B = (int)members.size();
     if (B == 0) return VISFS_BA_OK;
     HIP_TRY(h, hipSetDevice(h->device));
-    if (bs.cap_graphs < (size_t)B) {
-        if (bs.d_graphs) (void)hipFree(bs.d_graphs);
-        bs.d_graphs = nullptr; bs.cap_graphs = 0;
-        HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&bs.d_graphs), (size_t)B * sizeof(DeviceGraph)));
-        bs.cap_graphs = B;
-    }
-    if (bs.cap_states < (size_t)B) {
-        if (bs.d_lm) (void)hipFree(bs.d_lm);
-        if (bs.h_lm) (void)hipHostFree(bs.h_lm);
-        bs.d_lm = nullptr; bs.h_lm = nullptr; bs.cap_states = 0;
-        HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&bs.d_lm), (size_t)B * sizeof(LmState)));
-        HIP_TRY(h, hipHostMalloc(reinterpret_cast<void**>(&bs.h_lm), (size_t)B * sizeof(LmState), hipHostMallocDefault));
-        bs.cap_states = B;
+    RC_TRY(bs.d_graphs.grow(h, (size_t)B));
+    if (bs.h_lm.cap() < (size_t)B) {
+        RC_TRY(bs.d_lm.release(h));
+        RC_TRY(bs.h_lm.release(h));
+        RC_TRY(bs.d_lm.alloc(h, (size_t)B));
+        RC_TRY(bs.h_lm.alloc(h, (size_t)B));
     }
     // the members were uploaded on their own streams and the batch runs on `stream`: their copies and index kernels must be done
     for (int b = 0; b < B; ++b) {
@@ -1565,28 +1533,28 @@ int batch_optimize(visfs_ba_handle* h, BatchScratch& bs, const std::vector<Works
     }
     PcgLease pcg_lease;                                                                // persistent PCG: co-residency budget of the device
     if (!fused && !small_solve && !d.pcg_cu && h->prm.solver == 2) pcg_lease.acquire(h->device, pcg_wave_cost(d, B));
-    HIP_TRY(h, hipMemcpyAsync(bs.d_graphs, hg.data(), (size_t)B * sizeof(DeviceGraph), hipMemcpyHostToDevice, stream));
+    HIP_TRY(h, hipMemcpyAsync(bs.d_graphs.get(), hg.data(), (size_t)B * sizeof(DeviceGraph), hipMemcpyHostToDevice, stream));
     // g2o branch: optimize(iterations / 2) twice; Ceres branch: one Solve of <= iterations trust-region iterations, no second pass
     const bool ceres = h->prm.framework == 1;
     const int half = ceres ? h->prm.iterations : h->prm.iterations / 2;
-    launch_reset_batch(bs.d_graphs, B, d, half, h->prm.trust_region == 1, 0, stream);
+    launch_reset_batch(bs.d_graphs.get(), B, d, half, h->prm.trust_region == 1, 0, stream);
     if (fused) {
-        launch_small_optimize_batch(bs.d_graphs, B, h->prm.solver, half, stream);
+        launch_small_optimize_batch(bs.d_graphs.get(), B, h->prm.solver, half, stream);
     }
     // As for a single window (ws_optimize): both phases and their device-gated ends are enqueued up front and the whole LM states
     // come back in ONE copy; windows that rejected trials are topped up from what comes back.  Every launch is gated per window,
     // so the same sequence is safe for windows at different points of the schedule.
     const int half2 = (h->prm.robust_kernel_delta > 0.0 && !ceres) ? half : 0;                      // :310-311
-    auto units = [&](int n, bool first) { for (int u = 0; u < n; ++u) { launch_unit_batch(bs.d_graphs, B, d, first, small_solve, h->prm.solver, fused_decide, spec_fused, stream); first = false; } };
+    auto units = [&](int n, bool first) { for (int u = 0; u < n; ++u) { launch_unit_batch(bs.d_graphs.get(), B, d, first, small_solve, h->prm.solver, fused_decide, spec_fused, stream); first = false; } };
     auto phase_end = [&](int which) {
-        if (which == 0) launch_phase_end_batch(bs.d_graphs, B, d, 0, 1, half2, stream);             // :270-303
-        else launch_phase_end_batch(bs.d_graphs, B, d, 1, 0, 0, stream);                            // :315-318
+        if (which == 0) launch_phase_end_batch(bs.d_graphs.get(), B, d, 0, 1, half2, stream);             // :270-303
+        else launch_phase_end_batch(bs.d_graphs.get(), B, d, 1, 0, 0, stream);                            // :315-318
     };
     if (!fused) { units(half, true); phase_end(0); units(half2, true); phase_end(1); }              // :265
     for (int guard = 0;; ++guard) {
-        launch_gather_lm(bs.d_graphs, B, bs.d_lm, stream);
+        launch_gather_lm(bs.d_graphs.get(), B, bs.d_lm.get(), stream);
         HIP_TRY(h, hipGetLastError());
-        HIP_TRY(h, hipMemcpyAsync(bs.h_lm, bs.d_lm, (size_t)B * sizeof(LmState), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(h, hipMemcpyAsync(bs.h_lm.get(), bs.d_lm.get(), (size_t)B * sizeof(LmState), hipMemcpyDeviceToHost, stream));
         HIP_TRY(h, hipStreamSynchronize(stream));
         if (fused) break;
         bool all_finished = true;
@@ -1711,17 +1679,14 @@ int ws_covariance(visfs_ba_handle* h, Workspace& w, double* pose_cov, double* po
     const size_t nband = Npf > 0 ? (size_t)Npf * W * 36 : 0;
     const size_t off_sig = ((nband * 8 + 255) & ~size_t(255)), off_pt = off_sig + ((nband * 8 + 255) & ~size_t(255));
     const size_t off_flag = off_pt + (((size_t)std::max(Nl, 1) * 72 + 255) & ~size_t(255)), bytes = off_flag + 256;
-    if (w.d_cov_cap < bytes) {
+    if (w.d_cov.cap() < bytes) {
         HIP_TRY(h, hipStreamSynchronize(w.stream));
-        if (w.d_cov) (void)hipFree(w.d_cov);
-        w.d_cov = nullptr; w.d_cov_cap = 0;
-        HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&w.d_cov), bytes));
-        w.d_cov_cap = bytes;
+        RC_TRY(w.d_cov.alloc(h, bytes));
     }
-    double* dF = reinterpret_cast<double*>(w.d_cov);
-    double* dSg = reinterpret_cast<double*>(w.d_cov + off_sig);
-    double* dPt = reinterpret_cast<double*>(w.d_cov + off_pt);
-    int* dFail = reinterpret_cast<int*>(w.d_cov + off_flag);
+    double* dF = reinterpret_cast<double*>(w.d_cov.get());
+    double* dSg = reinterpret_cast<double*>(w.d_cov.get() + off_sig);
+    double* dPt = reinterpret_cast<double*>(w.d_cov.get() + off_pt);
+    int* dFail = reinterpret_cast<int*>(w.d_cov.get() + off_flag);
     int rc = ws_read_state(h, w);
     if (rc != VISFS_BA_OK) return rc;
     const LmState saved = *w.h_state;
@@ -1752,7 +1717,7 @@ int ws_covariance(visfs_ba_handle* h, Workspace& w, double* pose_cov, double* po
     HIP_TRY(h, hipStreamSynchronize(w.stream));
     // the LM state as it was (the arm / trial launches above rewrote its mode, lambda, linearisation set, ...)
     *w.h_state = saved;
-    HIP_TRY(h, hipMemcpyAsync(w.g.st, w.h_state, sizeof(LmState), hipMemcpyHostToDevice, w.stream));
+    HIP_TRY(h, hipMemcpyAsync(w.g.st, w.h_state.get(), sizeof(LmState), hipMemcpyHostToDevice, w.stream));
     HIP_TRY(h, hipStreamSynchronize(w.stream));
     if (fail) { h->err = "the Hessian at the estimate is not positive definite (a pivot of its factorisation)"; return VISFS_BA_ERR_SINGULAR; }
     // (the caller's buffers are written only from here on: an error leaves them as they were)
@@ -1842,15 +1807,8 @@ void visfs_ba_destroy(visfs_ba_handle* h) {
     (void)hipSetDevice(h->device);
     ws_release(h->ws);
     for (Workspace* w : h->batch) { ws_release(*w); delete w; }
-    if (h->scratch.d_graphs) (void)hipFree(h->scratch.d_graphs);
-    if (h->scratch.d_lm) (void)hipFree(h->scratch.d_lm);
-    if (h->scratch.h_lm) (void)hipHostFree(h->scratch.h_lm);
-    if (h->scratch.d_all) (void)hipFree(h->scratch.d_all);
-    for (BatchScratch& b : h->part_scratch) {
-        if (b.d_graphs) (void)hipFree(b.d_graphs);
-        if (b.d_lm) (void)hipFree(b.d_lm);
-        if (b.h_lm) (void)hipHostFree(b.h_lm);
-    }
+    h->scratch = BatchScratch{};                   // the scratch buffers go before the streams they were used on
+    h->part_scratch.clear();
     for (hipStream_t st : h->part_stream) if (st) (void)hipStreamDestroy(st);
     delete h;
 }
@@ -1979,7 +1937,7 @@ int visfs_ba_solve_batch(visfs_ba_handle* h, int32_t n, const visfs_ba_window* c
                 const int rc = batch_optimize_group(h, members);
                 for (int i : members) {
                     if (rc != VISFS_BA_OK) { rcs[i] = rc; worst = VISFS_BA_ERR_DEVICE; continue; }
-                    fill_stats(*h->batch[i]->h_state, &stats[i]);
+                    fill_stats(*h->batch[i]->h_state.get(), &stats[i]);
                     stats[i].solver_fallback = h->batch[i]->fell_back_last ? 1 : 0;
                     rcs[i] = h->batch[i]->h_state->status;
                 }
@@ -2033,15 +1991,10 @@ int visfs_ba_batch_upload(visfs_ba_handle* h, int32_t n, const visfs_ba_graph* c
         for (int i = 0; i < n; ++i) { HIP_TRY(h, hipStreamSynchronize(h->batch[i]->stream)); h->batch[i]->upload_in_flight = false; }
         // every graph once more as one array: visfs_ba_batch_reset is then a single launch
         BatchScratch& bs = h->scratch;
-        if (bs.cap_all < (size_t)n) {
-            if (bs.d_all) (void)hipFree(bs.d_all);
-            bs.d_all = nullptr; bs.cap_all = 0;
-            HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&bs.d_all), (size_t)std::max(n, 1) * sizeof(DeviceGraph)));
-            bs.cap_all = (size_t)std::max(n, 1);
-        }
+        if (bs.d_all.cap() < (size_t)n) RC_TRY(bs.d_all.alloc(h, (size_t)std::max(n, 1)));
         std::vector<DeviceGraph> hg(n);
         for (int i = 0; i < n; ++i) { hg[i] = h->batch[i]->g; bs.all_dims = i ? dims_max(bs.all_dims, dims_of(hg[i])) : dims_of(hg[i]); }
-        if (n) HIP_TRY(h, hipMemcpy(bs.d_all, hg.data(), (size_t)n * sizeof(DeviceGraph), hipMemcpyHostToDevice));
+        if (n) HIP_TRY(h, hipMemcpy(bs.d_all.get(), hg.data(), (size_t)n * sizeof(DeviceGraph), hipMemcpyHostToDevice));
         h->n_batch = n;
         return VISFS_BA_OK;
     });
@@ -2051,7 +2004,7 @@ int visfs_ba_batch_reset(visfs_ba_handle* h) {
     if (!h) return VISFS_BA_ERR_BAD_ARGUMENT;
     reset_disarm(h);
     HIP_TRY(h, hipSetDevice(h->device));
-    if (h->n_batch > 0) launch_reset_batch(h->scratch.d_all, h->n_batch, h->scratch.all_dims, h->prm.framework == 1 ? h->prm.iterations : h->prm.iterations / 2, h->prm.trust_region == 1, 1, h->ws.stream);
+    if (h->n_batch > 0) launch_reset_batch(h->scratch.d_all.get(), h->n_batch, h->scratch.all_dims, h->prm.framework == 1 ? h->prm.iterations : h->prm.iterations / 2, h->prm.trust_region == 1, 1, h->ws.stream);
     HIP_TRY(h, hipGetLastError());
     for (int i = 0; i < h->n_batch; ++i) h->batch[i]->pristine = true;
     return VISFS_BA_OK;
@@ -2081,7 +2034,7 @@ int visfs_ba_batch_optimize(visfs_ba_handle* h, visfs_ba_stats* stats) {
                 const int rc = batch_optimize_group(h, members);
                 if (rc != VISFS_BA_OK) return rc;
                 for (int i : members) {
-                    if (stats) { fill_stats(*h->batch[i]->h_state, &stats[i]); stats[i].solver_fallback = h->batch[i]->fell_back_last ? 1 : 0; }
+                    if (stats) { fill_stats(*h->batch[i]->h_state.get(), &stats[i]); stats[i].solver_fallback = h->batch[i]->fell_back_last ? 1 : 0; }
                     if (h->batch[i]->h_state->status != VISFS_BA_OK) worst = h->batch[i]->h_state->status;
                 }
             }
@@ -2216,7 +2169,7 @@ static int stage_ceres_trial(visfs_ba_handle* h, const double lambda, const doub
     }
     // undo the decision: the resident estimate, the trust region and the counters are what they were; the candidate stays in the trial buffers
     *w.h_state = st0;
-    HIP_TRY(h, hipMemcpyAsync(w.g.st, w.h_state, sizeof(LmState), hipMemcpyHostToDevice, w.stream));
+    HIP_TRY(h, hipMemcpyAsync(w.g.st, w.h_state.get(), sizeof(LmState), hipMemcpyHostToDevice, w.stream));
     HIP_TRY(h, hipStreamSynchronize(w.stream));
     return VISFS_BA_OK;
 }
@@ -2279,7 +2232,7 @@ int visfs_ba_stage_trial(visfs_ba_handle* h, double lambda, double* trial_chi2, 
     LmState st = *w.h_state;
     st.sel = sel0; st.current_chi = chi0; st.done = 0; st.mode = 0;
     *w.h_state = st;
-    HIP_TRY(h, hipMemcpyAsync(w.g.st, w.h_state, sizeof(LmState), hipMemcpyHostToDevice, w.stream));
+    HIP_TRY(h, hipMemcpyAsync(w.g.st, w.h_state.get(), sizeof(LmState), hipMemcpyHostToDevice, w.stream));
     HIP_TRY(h, hipStreamSynchronize(w.stream));
     return VISFS_BA_OK;
 }
@@ -2396,7 +2349,7 @@ int visfs_ba_stage_commit(visfs_ba_handle* h) {
     int rc = ws_read_state(h, w);
     if (rc != VISFS_BA_OK) return rc;
     w.h_state->sel ^= 1;
-    HIP_TRY(h, hipMemcpyAsync(w.g.st, w.h_state, sizeof(LmState), hipMemcpyHostToDevice, w.stream));
+    HIP_TRY(h, hipMemcpyAsync(w.g.st, w.h_state.get(), sizeof(LmState), hipMemcpyHostToDevice, w.stream));
     HIP_TRY(h, hipStreamSynchronize(w.stream));
     return (int)VISFS_BA_OK;
     });
@@ -2412,7 +2365,7 @@ int visfs_ba_stage_begin_phase(visfs_ba_handle* h) {
     if (rc != VISFS_BA_OK) return rc;
     w.h_state->pcg_residual = -1.0; w.h_state->pcg_res_in = -1.0; w.h_state->status = 0;
     w.stage_iter0 = true;                         // Optimizer/Framework=1: the next stage_linearize estimates the Jacobi scaling again
-    HIP_TRY(h, hipMemcpyAsync(w.g.st, w.h_state, sizeof(LmState), hipMemcpyHostToDevice, w.stream));
+    HIP_TRY(h, hipMemcpyAsync(w.g.st, w.h_state.get(), sizeof(LmState), hipMemcpyHostToDevice, w.stream));
     HIP_TRY(h, hipStreamSynchronize(w.stream));
     return (int)VISFS_BA_OK;
     });

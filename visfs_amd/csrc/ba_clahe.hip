@@ -167,9 +167,9 @@ struct ClaheState {
     std::vector<int32_t> hhist[2];
 
     // device: sized for kMaxTiles x kMaxTiles at the first call
-    uint8_t* d_raw = nullptr;      // both raw images of a frame
-    uint8_t* d_lut = nullptr;      // both images' tables
-    int32_t* d_hist = nullptr;     // both images' final histograms
+    DeviceBuf<uint8_t> d_raw;      // both raw images of a frame
+    DeviceBuf<uint8_t> d_lut;      // both images' tables
+    DeviceBuf<int32_t> d_hist;     // both images' final histograms
     size_t raw_stride = 0;         // bytes from the left image to the right one
 };
 
@@ -179,9 +179,6 @@ void clahe_release(visfs_flow* f) {
     if (f->device) {
         (void)hipSetDevice(f->dev);
         if (f->stream) (void)hipStreamSynchronize(f->stream);
-        if (c->d_raw) (void)hipFree(c->d_raw);
-        if (c->d_lut) (void)hipFree(c->d_lut);
-        if (c->d_hist) (void)hipFree(c->d_hist);
     }
     delete c;
     f->clahe = nullptr;
@@ -214,9 +211,9 @@ int ensure_state(visfs_flow* f) {
     c->raw_stride = (n0 + 255) & ~size_t(255);
     const auto alloc = [&]() -> int {
         HIP_TRY(f, hipSetDevice(f->dev));
-        HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&c->d_raw), 2 * c->raw_stride));
-        HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&c->d_lut), 2 * kTableCells));
-        HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&c->d_hist), 2 * kTableCells * sizeof(int32_t)));
+        RC_TRY(c->d_raw.alloc(f, 2 * c->raw_stride));
+        RC_TRY(c->d_lut.alloc(f, 2 * kTableCells));
+        RC_TRY(c->d_hist.alloc(f, 2 * kTableCells));
         return VISFS_BA_OK;
     };
     const int rc = alloc();
@@ -251,7 +248,7 @@ void host_equalise(const Geom& g, const uint8_t* img, int32_t stride, uint8_t* l
 }
 
 int device_equalise(visfs_flow* f, ClaheState* c, const Geom& g, int slot, const uint8_t* left, const uint8_t* right, int32_t stride) {
-    uint8_t* const raw[2] = { c->d_raw, c->d_raw + c->raw_stride };
+    uint8_t* const raw[2] = { c->d_raw.get(), c->d_raw.get() + c->raw_stride };
     const int rc = flow::device_stage(f, raw, left, right, stride);
     if (rc != VISFS_BA_OK) return rc;
     const size_t tile_cells = (size_t)g.tiles_x * g.tiles_y * kBins;
@@ -259,8 +256,8 @@ int device_equalise(visfs_flow* f, ClaheState* c, const Geom& g, int slot, const
     ApplyArgs P;
     for (int i = 0; i < 2; ++i) {
         L.raw[i] = P.raw[i] = raw[i];
-        L.lut[i] = c->d_lut + i * tile_cells; P.lut[i] = L.lut[i];
-        L.hist[i] = c->d_hist + i * tile_cells;
+        L.lut[i] = c->d_lut.get() + i * tile_cells; P.lut[i] = L.lut[i];
+        L.hist[i] = c->d_hist.get() + i * tile_cells;
         P.dst[i] = f->dpx[slot][i];
     }
     hipLaunchKernelGGL(k_clahe_lut, dim3((unsigned)(g.tiles_x * g.tiles_y), 2), dim3(CL_T), 0, f->stream, L, g);
@@ -283,10 +280,10 @@ void group_clahe_fill(visfs_flow* f, const Geom& g, int slot, ClaheRec* r, uint8
     ClaheState* c = f->clahe;
     const size_t tile_cells = (size_t)g.tiles_x * g.tiles_y * kBins;
     for (int i = 0; i < 2; ++i) {
-        raw[i] = c->d_raw + i * c->raw_stride;
+        raw[i] = c->d_raw.get() + i * c->raw_stride;
         r->raw[i] = raw[i];
-        r->lut[i] = c->d_lut + i * tile_cells;
-        r->hist[i] = c->d_hist + i * tile_cells;
+        r->lut[i] = c->d_lut.get() + i * tile_cells;
+        r->hist[i] = c->d_hist.get() + i * tile_cells;
         r->dst[i] = f->dpx[slot][i];
     }
     c->valid = false;
@@ -388,8 +385,8 @@ int visfs_flow_clahe_download(const visfs_flow* cf, int32_t image, uint8_t* lut,
             return (int)VISFS_BA_OK;
         }
         HIP_TRY(f, hipSetDevice(f->dev));
-        if (lut) HIP_TRY(f, hipMemcpyAsync(lut, c->d_lut + image * tile_cells, tile_cells, hipMemcpyDeviceToHost, f->stream));
-        if (hist) HIP_TRY(f, hipMemcpyAsync(hist, c->d_hist + image * tile_cells, tile_cells * sizeof(int32_t), hipMemcpyDeviceToHost, f->stream));
+        if (lut) HIP_TRY(f, hipMemcpyAsync(lut, c->d_lut.get() + image * tile_cells, tile_cells, hipMemcpyDeviceToHost, f->stream));
+        if (hist) HIP_TRY(f, hipMemcpyAsync(hist, c->d_hist.get() + image * tile_cells, tile_cells * sizeof(int32_t), hipMemcpyDeviceToHost, f->stream));
         HIP_TRY(f, hipStreamSynchronize(f->stream));
         return (int)VISFS_BA_OK;
     });

@@ -315,15 +315,13 @@ struct CornerState {
     std::vector<uint8_t> hmask;
 
     // device
-    float* d_eig = nullptr;
-    uint8_t* d_mask = nullptr;
-    uint64_t* d_keys = nullptr;        // appended, then sorted: 2 x (w - 2)(h - 2)
-    uint64_t* d_sorted = nullptr;
-    char* d_out = nullptr;             // CornerDev, xy[kMaxCorners][2]
-    char* h_out = nullptr;             // pinned
-    char* d_disc = nullptr;            // Disc[n], hw[]
-    char* h_disc = nullptr;            // pinned
-    size_t disc_cap = 0;               // bytes
+    DeviceBuf<float> d_eig;
+    DeviceBuf<uint8_t> d_mask;
+    DeviceBuf<uint64_t> d_keys;        // appended, then sorted: 2 x (w - 2)(h - 2)
+    uint64_t* d_sorted = nullptr;      // the second half of d_keys
+    DeviceBuf<char> d_out;             // CornerDev, xy[kMaxCorners][2]
+    PinnedBuf<char> h_out;
+    Staged<char> disc;                 // Disc[n], hw[]; bytes
 };
 
 void corners_release(visfs_flow* f) {
@@ -332,15 +330,8 @@ void corners_release(visfs_flow* f) {
     if (f->device) {
         (void)hipSetDevice(f->dev);
         if (f->stream) (void)hipStreamSynchronize(f->stream);
-        if (c->d_eig) (void)hipFree(c->d_eig);
-        if (c->d_mask) (void)hipFree(c->d_mask);
-        if (c->d_keys) (void)hipFree(c->d_keys);
-        if (c->d_out) (void)hipFree(c->d_out);
-        if (c->h_out) (void)hipHostFree(c->h_out);
-        if (c->d_disc) (void)hipFree(c->d_disc);
-        if (c->h_disc) (void)hipHostFree(c->h_disc);
     }
-    delete c;
+    delete c;                                  // its members free what they own
     f->corners = nullptr;
 }
 
@@ -361,13 +352,12 @@ int ensure_state(visfs_flow* f) {
     const size_t n0 = (size_t)f->w * f->h, nc = std::max<size_t>(max_candidates(f), 1);
     const auto alloc = [&]() -> int {
         HIP_TRY(f, hipSetDevice(f->dev));
-        HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&c->d_eig), n0 * sizeof(float)));
-        HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&c->d_mask), n0));
-        HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&c->d_keys), 2 * nc * sizeof(uint64_t)));
-        c->d_sorted = c->d_keys + nc;
-        HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&c->d_out), kOutBytes));
-        HIP_TRY(f, hipHostMalloc(reinterpret_cast<void**>(&c->h_out), kOutBytes, hipHostMallocDefault));
-        return VISFS_BA_OK;
+        RC_TRY(c->d_eig.alloc(f, n0));
+        RC_TRY(c->d_mask.alloc(f, n0));
+        RC_TRY(c->d_keys.alloc(f, 2 * nc));
+        c->d_sorted = c->d_keys.get() + nc;
+        RC_TRY(c->d_out.alloc(f, kOutBytes));
+        return c->h_out.alloc(f, kOutBytes);
     };
     const int rc = alloc();
     if (rc != VISFS_BA_OK) corners_release(f);
@@ -376,16 +366,9 @@ int ensure_state(visfs_flow* f) {
 
 int disc_reserve(visfs_flow* f, size_t bytes) {
     CornerState* c = f->corners;
-    if (bytes <= c->disc_cap) return VISFS_BA_OK;
+    if (bytes <= c->disc.cap()) return VISFS_BA_OK;
     HIP_TRY(f, hipStreamSynchronize(f->stream));
-    if (c->h_disc) HIP_TRY(f, hipHostFree(c->h_disc));
-    if (c->d_disc) HIP_TRY(f, hipFree(c->d_disc));
-    c->h_disc = nullptr; c->d_disc = nullptr; c->disc_cap = 0;
-    const size_t cap = std::max<size_t>(2 * bytes, 16384);
-    HIP_TRY(f, hipHostMalloc(reinterpret_cast<void**>(&c->h_disc), cap, hipHostMallocDefault));
-    HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&c->d_disc), cap));
-    c->disc_cap = cap;
-    return VISFS_BA_OK;
+    return c->disc.reserve(f, bytes, std::max<size_t>(2 * bytes, 16384));
 }
 
 int check_call(visfs_flow* f, int32_t slot, int32_t image, const visfs_corners_params* p, int32_t n_discs, const visfs_corners_disc* discs,
@@ -499,37 +482,37 @@ int device_corners(visfs_flow* f, CornerState* c, const uint8_t* px, const visfs
         const int rc = disc_reserve(f, disc_bytes + hw_bytes);
         if (rc != VISFS_BA_OK) return rc;
         // the pinned block is free: the call that filled it last ended in a synchronise behind its copy
-        std::memcpy(c->h_disc, c->discs.data(), disc_bytes);
-        std::memcpy(c->h_disc + disc_bytes, c->hw.data(), hw_bytes);
-        HIP_TRY(f, hipMemcpyAsync(c->d_disc, c->h_disc, disc_bytes + hw_bytes, hipMemcpyHostToDevice, f->stream));
-        d_discs = reinterpret_cast<const Disc*>(c->d_disc);
-        d_hw = reinterpret_cast<const int32_t*>(c->d_disc + disc_bytes);
+        std::memcpy(c->disc.h.get(), c->discs.data(), disc_bytes);
+        std::memcpy(c->disc.h.get() + disc_bytes, c->hw.data(), hw_bytes);
+        HIP_TRY(f, hipMemcpyAsync(c->disc.d.get(), c->disc.h.get(), disc_bytes + hw_bytes, hipMemcpyHostToDevice, f->stream));
+        d_discs = reinterpret_cast<const Disc*>(c->disc.d.get());
+        d_hw = reinterpret_cast<const int32_t*>(c->disc.d.get() + disc_bytes);
     }
-    CornerDev* st = reinterpret_cast<CornerDev*>(c->d_out);
-    float* d_xy = reinterpret_cast<float*>(c->d_out + sizeof(CornerDev));
-    HIP_TRY(f, hipMemsetAsync(c->d_out, 0, sizeof(CornerDev), f->stream));
+    CornerDev* st = reinterpret_cast<CornerDev*>(c->d_out.get());
+    float* d_xy = reinterpret_cast<float*>(c->d_out.get() + sizeof(CornerDev));
+    HIP_TRY(f, hipMemsetAsync(c->d_out.get(), 0, sizeof(CornerDev), f->stream));
     hipLaunchKernelGGL(k_corner_response, dim3((w + CT_X - 1) / CT_X, (h + CT_Y - 1) / CT_Y), dim3(CR_T), 0, f->stream, px, w, h, d_discs,
-                       (int)c->discs.size(), d_hw, c->d_eig, c->d_mask, st);
+                       (int)c->discs.size(), d_hw, c->d_eig.get(), c->d_mask.get(), st);
     HIP_TRY(f, hipGetLastError());
-    hipLaunchKernelGGL(k_corner_candidates, dim3((unsigned)(((size_t)w * h + CR_T - 1) / CR_T)), dim3(CR_T), 0, f->stream, c->d_eig, c->d_mask,
-                       w, h, p.quality_level, st, c->d_keys);
+    hipLaunchKernelGGL(k_corner_candidates, dim3((unsigned)(((size_t)w * h + CR_T - 1) / CR_T)), dim3(CR_T), 0, f->stream, c->d_eig.get(), c->d_mask.get(),
+                       w, h, p.quality_level, st, c->d_keys.get());
     HIP_TRY(f, hipGetLastError());
     const size_t chunks = (max_candidates(f) + 63) / 64;
     hipLaunchKernelGGL(k_corner_sort, dim3((unsigned)std::min<size_t>(std::max<size_t>(chunks, 1), kSortGrid)), dim3(CR_T), 0, f->stream,
-                       c->d_keys, st, c->d_sorted);
+                       c->d_keys.get(), st, c->d_sorted);
     HIP_TRY(f, hipGetLastError());
     hipLaunchKernelGGL(k_corner_select, dim3(1), dim3(kSelT), 0, f->stream, c->d_sorted, st, w, distance_gate(p.min_distance), p.max_corners,
                        d_xy);
     HIP_TRY(f, hipGetLastError());
-    HIP_TRY(f, hipMemcpyAsync(c->h_out, c->d_out, sizeof(CornerDev) + sizeof(float) * 2 * (size_t)p.max_corners, hipMemcpyDeviceToHost,
+    HIP_TRY(f, hipMemcpyAsync(c->h_out.get(), c->d_out.get(), sizeof(CornerDev) + sizeof(float) * 2 * (size_t)p.max_corners, hipMemcpyDeviceToHost,
                              f->stream));
     HIP_TRY(f, hipStreamSynchronize(f->stream));
     CornerDev out;
-    std::memcpy(&out, c->h_out, sizeof(out));
+    std::memcpy(&out, c->h_out.get(), sizeof(out));
     if (out.n_out < 0 || out.n_out > p.max_corners) return fail(f, VISFS_BA_ERR_DEVICE, "the selection returned an impossible count");
     c->n_candidates = (int32_t)out.count;
     c->max_val = from_ordered_bits(out.max_bits);
-    std::memcpy(xy, c->h_out + sizeof(CornerDev), sizeof(float) * 2 * (size_t)out.n_out);
+    std::memcpy(xy, c->h_out.get() + sizeof(CornerDev), sizeof(float) * 2 * (size_t)out.n_out);
     *n_out = out.n_out;
     return VISFS_BA_OK;
 }
@@ -545,10 +528,10 @@ void group_corners_fill(visfs_flow* f, const uint8_t* px, const Disc* d_discs, c
                         CornerRec* r, const int32_t** d_n_out, const float** d_xy) {
     CornerState* c = f->corners;
     if (!skip) c->valid = false;               // the download hook reports staged calls only
-    CornerDev* st = reinterpret_cast<CornerDev*>(c->d_out);
+    CornerDev* st = reinterpret_cast<CornerDev*>(c->d_out.get());
     r->px = px; r->discs = d_discs; r->hw = d_hw; r->args = d_args;
-    r->eig = c->d_eig; r->mask = c->d_mask; r->keys = c->d_keys; r->sorted = c->d_sorted;
-    r->st = st; r->xy = reinterpret_cast<float*>(c->d_out + sizeof(CornerDev));
+    r->eig = c->d_eig.get(); r->mask = c->d_mask.get(); r->keys = c->d_keys.get(); r->sorted = c->d_sorted;
+    r->st = st; r->xy = reinterpret_cast<float*>(c->d_out.get() + sizeof(CornerDev));
     r->skip = skip ? 1 : 0; r->pad = 0;
     *d_n_out = &st->n_out;
     *d_xy = r->xy;
@@ -640,8 +623,8 @@ int visfs_flow_corners_download(const visfs_flow* cf, float* eig, uint8_t* mask,
             return (int)VISFS_BA_OK;
         }
         HIP_TRY(f, hipSetDevice(f->dev));
-        if (eig) HIP_TRY(f, hipMemcpyAsync(eig, c->d_eig, n0 * sizeof(float), hipMemcpyDeviceToHost, f->stream));
-        if (mask) HIP_TRY(f, hipMemcpyAsync(mask, c->d_mask, n0, hipMemcpyDeviceToHost, f->stream));
+        if (eig) HIP_TRY(f, hipMemcpyAsync(eig, c->d_eig.get(), n0 * sizeof(float), hipMemcpyDeviceToHost, f->stream));
+        if (mask) HIP_TRY(f, hipMemcpyAsync(mask, c->d_mask.get(), n0, hipMemcpyDeviceToHost, f->stream));
         HIP_TRY(f, hipStreamSynchronize(f->stream));
         return (int)VISFS_BA_OK;
     });

@@ -186,13 +186,10 @@ IoLayout io_layout(size_t n) {
 int io_reserve(visfs_flow* f, int32_t n) {
     if (n <= f->io_cap) return VISFS_BA_OK;
     HIP_TRY(f, hipStreamSynchronize(f->stream));
-    if (f->h_io) HIP_TRY(f, hipHostFree(f->h_io));
-    if (f->d_io) HIP_TRY(f, hipFree(f->d_io));
-    f->h_io = nullptr; f->d_io = nullptr; f->io_cap = 0;
+    f->io_cap = 0;
     const int32_t cap = std::max(n, kInitialPoints);
-    const size_t bytes = io_layout((size_t)cap).bytes;
-    HIP_TRY(f, hipHostMalloc(reinterpret_cast<void**>(&f->h_io), bytes, hipHostMallocDefault));
-    HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&f->d_io), bytes));
+    const size_t bytes = io_layout((size_t)cap).bytes;                     // grows with the points, so the block's bytes are short as well
+    RC_TRY(f->io.reserve(f, bytes, bytes));
     f->io_cap = cap;
     return VISFS_BA_OK;
 }
@@ -200,26 +197,15 @@ int io_reserve(visfs_flow* f, int32_t n) {
 int device_init(visfs_flow* f) {
     HIP_TRY(f, hipSetDevice(f->dev));
     const size_t bpx = up256((size_t)f->lay.cells), bder = up256((size_t)f->lay.cells * 4);
-    HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&f->d_mem), 4 * (bpx + bder)));
-    char* m = f->d_mem;
+    RC_TRY(f->d_mem.alloc(f, 4 * (bpx + bder)));
+    char* m = f->d_mem.get();
     for (int s = 0; s < 2; ++s)
         for (int i = 0; i < 2; ++i) {
             f->dder[s][i] = reinterpret_cast<uint32_t*>(m); m += bder;
             f->dpx[s][i] = reinterpret_cast<uint8_t*>(m); m += bpx;
         }
-    HIP_TRY(f, hipHostMalloc(reinterpret_cast<void**>(&f->h_img), 2 * (size_t)f->w * f->h, hipHostMallocDefault));
+    RC_TRY(f->h_img.alloc(f, 2 * (size_t)f->w * f->h));
     return io_reserve(f, kInitialPoints);
-}
-
-void release(visfs_flow* f) {
-    if (!f->device) return;
-    (void)hipSetDevice(f->dev);
-    if (f->stream) (void)hipStreamSynchronize(f->stream);
-    if (f->d_mem) (void)hipFree(f->d_mem);
-    if (f->d_io) (void)hipFree(f->d_io);
-    if (f->h_io) (void)hipHostFree(f->h_io);
-    if (f->h_img) (void)hipHostFree(f->h_img);
-    f->d_mem = f->d_io = f->h_io = nullptr; f->h_img = nullptr;
 }
 
 }  // namespace
@@ -246,8 +232,8 @@ int group_stage(visfs_flow* f, uint8_t* const dst[2], const uint8_t* left, const
     const size_t n0 = (size_t)f->w * f->h;
     const uint8_t* src[2] = { left, right };
     for (int i = 0; i < 2; ++i) {
-        for (int32_t y = 0; y < f->h; ++y) std::memcpy(f->h_img + i * n0 + (size_t)y * f->w, src[i] + (size_t)y * stride, (size_t)f->w);
-        HIP_TRY(f, hipMemcpyAsync(dst[i], f->h_img + i * n0, n0, hipMemcpyHostToDevice, f->stream));
+        for (int32_t y = 0; y < f->h; ++y) std::memcpy(f->h_img.get() + i * n0 + (size_t)y * f->w, src[i] + (size_t)y * stride, (size_t)f->w);
+        HIP_TRY(f, hipMemcpyAsync(dst[i], f->h_img.get() + i * n0, n0, hipMemcpyHostToDevice, f->stream));
         if (cnt) ++cnt->copies;
     }
     return VISFS_BA_OK;
@@ -341,17 +327,17 @@ int run_pass(visfs_flow* f, int si, int ii, int sj, int ij, int32_t n, const flo
     if (rc != VISFS_BA_OK) return rc;
     HIP_TRY(f, hipStreamSynchronize(f->stream));                        // (the pinned block is free again)
     const IoLayout o = io_layout((size_t)n);
-    std::memcpy(f->h_io + o.pts, pts, 8 * (size_t)n);
-    if (init) std::memcpy(f->h_io + o.init, init, 8 * (size_t)n);
-    HIP_TRY(f, hipMemcpyAsync(f->d_io, f->h_io, init ? o.in_bytes : o.init, hipMemcpyHostToDevice, f->stream));
+    std::memcpy(f->io.h.get() + o.pts, pts, 8 * (size_t)n);
+    if (init) std::memcpy(f->io.h.get() + o.init, init, 8 * (size_t)n);
+    HIP_TRY(f, hipMemcpyAsync(f->io.d.get(), f->io.h.get(), init ? o.in_bytes : o.init, hipMemcpyHostToDevice, f->stream));
     LkArgs A;
     A.I = device_image(f, si, ii); A.J = device_image(f, sj, ij);
-    A.pts = reinterpret_cast<const float*>(f->d_io + o.pts);
-    A.init = init ? reinterpret_cast<const float*>(f->d_io + o.init) : nullptr;
-    A.to = reinterpret_cast<float*>(f->d_io + o.to);
-    A.err = reinterpret_cast<float*>(f->d_io + o.err);
-    A.xyz = reinterpret_cast<float*>(f->d_io + o.xyz);
-    A.status = reinterpret_cast<uint8_t*>(f->d_io + o.status);
+    A.pts = reinterpret_cast<const float*>(f->io.d.get() + o.pts);
+    A.init = init ? reinterpret_cast<const float*>(f->io.d.get() + o.init) : nullptr;
+    A.to = reinterpret_cast<float*>(f->io.d.get() + o.to);
+    A.err = reinterpret_cast<float*>(f->io.d.get() + o.err);
+    A.xyz = reinterpret_cast<float*>(f->io.d.get() + o.xyz);
+    A.status = reinterpret_cast<uint8_t*>(f->io.d.get() + o.status);
     A.n = n; A.gate = gate;
     const Camera c = cam ? *cam : Camera{};
     const dim3 grid((unsigned)n), block(64);
@@ -363,12 +349,12 @@ int run_pass(visfs_flow* f, int si, int ii, int sj, int ij, int32_t n, const flo
         else hipLaunchKernelGGL((k_flow_lk<false, false>), grid, block, 0, f->stream, A, f->lk, f->lay, c);
     }
     HIP_TRY(f, hipGetLastError());
-    HIP_TRY(f, hipMemcpyAsync(f->h_io + o.to, f->d_io + o.to, o.status + (size_t)n - o.to, hipMemcpyDeviceToHost, f->stream));
+    HIP_TRY(f, hipMemcpyAsync(f->io.h.get() + o.to, f->io.d.get() + o.to, o.status + (size_t)n - o.to, hipMemcpyDeviceToHost, f->stream));
     HIP_TRY(f, hipStreamSynchronize(f->stream));
-    std::memcpy(to, f->h_io + o.to, 8 * (size_t)n);
-    std::memcpy(status, f->h_io + o.status, (size_t)n);
-    if (err) std::memcpy(err, f->h_io + o.err, 4 * (size_t)n);
-    if (cam) std::memcpy(xyz, f->h_io + o.xyz, 12 * (size_t)n);
+    std::memcpy(to, f->io.h.get() + o.to, 8 * (size_t)n);
+    std::memcpy(status, f->io.h.get() + o.status, (size_t)n);
+    if (err) std::memcpy(err, f->io.h.get() + o.err, 4 * (size_t)n);
+    if (cam) std::memcpy(xyz, f->io.h.get() + o.xyz, 12 * (size_t)n);
     return VISFS_BA_OK;
 }
 
@@ -410,7 +396,7 @@ int visfs_flow_create(visfs_ba_handle* h, const visfs_flow_params* p, int32_t wi
         init_common(f, p, width, height);
         f->device = true; f->ba = h; f->dev = visfs_internal_device(h); f->stream = visfs_internal_stream(h);
         rc = device_init(f);
-        if (rc != VISFS_BA_OK) { visfs_internal_set_error(h, f->err.c_str()); release(f); delete f; return rc; }
+        if (rc != VISFS_BA_OK) { visfs_internal_set_error(h, f->err.c_str()); delete f; return rc; }
         *out = f;
         return (int)VISFS_BA_OK;
     });
@@ -421,7 +407,6 @@ void visfs_flow_destroy(visfs_flow* f) {
     flow::tracker_release(f);
     flow::corners_release(f);
     flow::clahe_release(f);
-    release(f);
     delete f;
 }
 

@@ -2,6 +2,7 @@
 // ba_corners.hip (corner extraction, include/visfs_corners.h) and ba_clahe.hip (the equalised frame push, include/visfs_clahe.h).
 #pragma once
 #include "ba_flow.hpp"
+#include "ba_host.hpp"
 #include "../../include/visfs_flow.h"
 
 #include <string>
@@ -47,12 +48,11 @@ struct visfs_flow {
     visfs_ba_handle* ba = nullptr;
     int dev = 0;
     hipStream_t stream = nullptr;
-    char* d_mem = nullptr;       // the four images' pixels and derivatives
+    host::DeviceBuf<char> d_mem; // the four images' pixels and derivatives
     uint8_t* dpx[2][2] = {};
     uint32_t* dder[2][2] = {};
-    uint8_t* h_img = nullptr;    // pinned: both level-0 images of a frame
-    char* h_io = nullptr;        // pinned: a call's points in, results out
-    char* d_io = nullptr;
+    host::PinnedBuf<uint8_t> h_img;  // both level-0 images of a frame
+    host::Staged<char> io;       // a call's points in, results out
     int32_t io_cap = 0;          // points
 
     // corner extraction (ba_corners.hip): nothing until the first visfs_flow_corners call
@@ -63,4 +63,10 @@ struct visfs_flow {
 
     // resident front end (ba_tracker.hip): the trackers made on this object, nothing until the first visfs_tracker_create
     flow::TrackerState* trackers = nullptr;
+
+    ~visfs_flow() {              // before the members free what they own; the three states above went in visfs_flow_destroy
+        if (!device) return;
+        (void)hipSetDevice(dev);
+        if (stream) (void)hipStreamSynchronize(stream);
+    }
 };

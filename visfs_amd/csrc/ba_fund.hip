@@ -216,13 +216,19 @@ struct visfs_fund {
     visfs_ba_handle* ba = nullptr;
     int dev = 0;
     hipStream_t stream = nullptr;
-    char* h_in = nullptr;      // pinned: header + rows + status
-    char* h_out = nullptr;     // pinned: Result + mask + status
-    char* d_in = nullptr;
-    char* d_out = nullptr;
-    char* d_state = nullptr;   // hypotheses
+    PinnedBuf<char> h_in;      // pinned: header + rows + status
+    PinnedBuf<char> h_out;     // pinned: Result + mask + status
+    DeviceBuf<char> d_in;
+    DeviceBuf<char> d_out;
+    DeviceBuf<char> d_state;   // hypotheses
     int32_t *d_samples = nullptr, *d_nc = nullptr;
     double* d_models = nullptr;
+
+    ~visfs_fund() {                     // before the members free what they own
+        if (!device) return;
+        (void)hipSetDevice(dev);
+        if (stream) (void)hipStreamSynchronize(stream);
+    }
 };
 
 namespace {
@@ -231,29 +237,17 @@ int device_init(visfs_fund* p) {
     HIP_TRY(p, hipSetDevice(p->dev));
     const size_t cap = (size_t)p->cap;
     const size_t in_bytes = kHeaderBytes + up256(17 * cap), out_bytes = kHeaderBytes + up256(2 * cap);
-    HIP_TRY(p, hipHostMalloc(reinterpret_cast<void**>(&p->h_in), in_bytes, hipHostMallocDefault));
-    HIP_TRY(p, hipHostMalloc(reinterpret_cast<void**>(&p->h_out), out_bytes, hipHostMallocDefault));
-    HIP_TRY(p, hipMalloc(reinterpret_cast<void**>(&p->d_in), in_bytes));
-    HIP_TRY(p, hipMalloc(reinterpret_cast<void**>(&p->d_out), out_bytes));
+    RC_TRY(p->h_in.alloc(p, in_bytes));
+    RC_TRY(p->h_out.alloc(p, out_bytes));
+    RC_TRY(p->d_in.alloc(p, in_bytes));
+    RC_TRY(p->d_out.alloc(p, out_bytes));
     const size_t H = kMaxHypotheses;
     const size_t o_models = 0, o_samples = o_models + up256(216 * H), o_nc = o_samples + up256(28 * H), bytes = o_nc + up256(16 * H);
-    HIP_TRY(p, hipMalloc(reinterpret_cast<void**>(&p->d_state), bytes));
-    p->d_models = reinterpret_cast<double*>(p->d_state + o_models);
-    p->d_samples = reinterpret_cast<int32_t*>(p->d_state + o_samples);
-    p->d_nc = reinterpret_cast<int32_t*>(p->d_state + o_nc);
+    RC_TRY(p->d_state.alloc(p, bytes));
+    p->d_models = reinterpret_cast<double*>(p->d_state.get() + o_models);
+    p->d_samples = reinterpret_cast<int32_t*>(p->d_state.get() + o_samples);
+    p->d_nc = reinterpret_cast<int32_t*>(p->d_state.get() + o_nc);
     return VISFS_BA_OK;
-}
-
-void release(visfs_fund* p) {
-    if (!p->device) return;
-    (void)hipSetDevice(p->dev);
-    if (p->stream) (void)hipStreamSynchronize(p->stream);
-    if (p->d_in) (void)hipFree(p->d_in);
-    if (p->d_out) (void)hipFree(p->d_out);
-    if (p->d_state) (void)hipFree(p->d_state);
-    if (p->h_in) (void)hipHostFree(p->h_in);
-    if (p->h_out) (void)hipHostFree(p->h_out);
-    p->d_in = p->d_out = p->d_state = p->h_in = p->h_out = nullptr;
 }
 
 // The host twin's side of fund::hypothesis: the same functions over the rows in sequence.
@@ -327,29 +321,29 @@ int device_cull(visfs_fund* p, const Call& c) {
     const size_t m = (size_t)c.m;
     Header hd{};
     hd.T1 = c.T1; hd.T2 = c.T2;
-    std::memset(p->h_in, 0, kHeaderBytes);
-    std::memcpy(p->h_in, &hd, sizeof hd);
-    std::memcpy(p->h_in + kHeaderBytes, p->rows.data(), sizeof(Row) * m);
-    std::memcpy(p->h_in + kHeaderBytes + sizeof(Row) * m, p->st.data(), m);
-    HIP_TRY(p, hipMemcpyAsync(p->d_in, p->h_in, kHeaderBytes + 17 * m, hipMemcpyHostToDevice, p->stream));
+    std::memset(p->h_in.get(), 0, kHeaderBytes);
+    std::memcpy(p->h_in.get(), &hd, sizeof hd);
+    std::memcpy(p->h_in.get() + kHeaderBytes, p->rows.data(), sizeof(Row) * m);
+    std::memcpy(p->h_in.get() + kHeaderBytes + sizeof(Row) * m, p->st.data(), m);
+    HIP_TRY(p, hipMemcpyAsync(p->d_in.get(), p->h_in.get(), kHeaderBytes + 17 * m, hipMemcpyHostToDevice, p->stream));
     RansacArgs A;
-    A.head = reinterpret_cast<const Header*>(p->d_in); A.rows = reinterpret_cast<const Row*>(p->d_in + kHeaderBytes);
+    A.head = reinterpret_cast<const Header*>(p->d_in.get()); A.rows = reinterpret_cast<const Row*>(p->d_in.get() + kHeaderBytes);
     A.m = c.m; A.iterations = c.iterations; A.seed = c.seed; A.thr2 = c.thr2;
-    A.samples = p->d_samples; A.nc = p->d_nc; A.models = p->d_models; A.key = reinterpret_cast<unsigned long long*>(p->d_in);
+    A.samples = p->d_samples; A.nc = p->d_nc; A.models = p->d_models; A.key = reinterpret_cast<unsigned long long*>(p->d_in.get());
     hipLaunchKernelGGL(k_fund_ransac, dim3((unsigned)((c.iterations + FD_T / 64 - 1) / (FD_T / 64))), dim3(FD_T), 0, p->stream, A);
     HIP_TRY(p, hipGetLastError());
     MaskArgs B;
-    B.head = A.head; B.rows = A.rows; B.status_in = reinterpret_cast<const uint8_t*>(p->d_in + kHeaderBytes + sizeof(Row) * m);
-    B.m = c.m; B.thr2 = c.thr2; B.models = p->d_models; B.res = reinterpret_cast<Result*>(p->d_out);
-    B.mask = reinterpret_cast<uint8_t*>(p->d_out + kHeaderBytes); B.status = B.mask + m;
+    B.head = A.head; B.rows = A.rows; B.status_in = reinterpret_cast<const uint8_t*>(p->d_in.get() + kHeaderBytes + sizeof(Row) * m);
+    B.m = c.m; B.thr2 = c.thr2; B.models = p->d_models; B.res = reinterpret_cast<Result*>(p->d_out.get());
+    B.mask = reinterpret_cast<uint8_t*>(p->d_out.get() + kHeaderBytes); B.status = B.mask + m;
     hipLaunchKernelGGL(k_fund_mask, dim3((unsigned)((c.m + FD_T - 1) / FD_T)), dim3(FD_T), 0, p->stream, B);
     HIP_TRY(p, hipGetLastError());
-    HIP_TRY(p, hipMemcpyAsync(p->h_out, p->d_out, kHeaderBytes + 2 * m, hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(p, hipMemcpyAsync(p->h_out.get(), p->d_out.get(), kHeaderBytes + 2 * m, hipMemcpyDeviceToHost, p->stream));
     HIP_TRY(p, hipStreamSynchronize(p->stream));
-    std::memcpy(&p->res, p->h_out, sizeof(Result));
+    std::memcpy(&p->res, p->h_out.get(), sizeof(Result));
     if (p->res.count < 0 || p->res.count > c.m) return fail(p, VISFS_BA_ERR_DEVICE, "the device returned an impossible inlier count");
-    std::memcpy(p->mask_k.data(), p->h_out + kHeaderBytes, m);
-    std::memcpy(p->status_k.data(), p->h_out + kHeaderBytes + m, m);
+    std::memcpy(p->mask_k.data(), p->h_out.get() + kHeaderBytes, m);
+    std::memcpy(p->status_k.data(), p->h_out.get() + kHeaderBytes + m, m);
     p->state_on_host = false;
     return VISFS_BA_OK;
 }
@@ -416,7 +410,7 @@ int visfs_fund_create(visfs_ba_handle* h, int32_t capacity_points, visfs_fund** 
         p->cap = capacity_points;
         p->device = true; p->ba = h; p->dev = visfs_internal_device(h); p->stream = visfs_internal_stream(h);
         const int rc = device_init(p);
-        if (rc != VISFS_BA_OK) { visfs_internal_set_error(h, p->err.c_str()); release(p); delete p; return rc; }
+        if (rc != VISFS_BA_OK) { visfs_internal_set_error(h, p->err.c_str()); delete p; return rc; }
         *out = p;
         return (int)VISFS_BA_OK;
     });
@@ -424,7 +418,6 @@ int visfs_fund_create(visfs_ba_handle* h, int32_t capacity_points, visfs_fund** 
 
 void visfs_fund_destroy(visfs_fund* p) {
     if (!p) return;
-    release(p);
     delete p;
 }
 

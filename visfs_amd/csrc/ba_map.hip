@@ -60,24 +60,27 @@ struct visfs_map {
     struct Tile {
         PlanTile p;
         std::vector<uint16_t> h;              // twin
-        uint16_t* d = nullptr;                // device
+        DeviceBuf<uint16_t> d;                // device
     };
     std::vector<Tile> tiles;
     int64_t tile_bytes = 0;
     std::vector<int32_t> L;                   // the log-odds table
-    int32_t* d_L = nullptr;
+    DeviceBuf<int32_t> d_L;
     // the last composed grid
     bool have = false;
     Limits G;
     std::vector<uint16_t> h_cells;
     std::vector<uint8_t> h_count;
-    uint16_t* d_cells = nullptr;
-    uint8_t* d_count = nullptr;
-    size_t out_cap = 0;                       // cells
-    TileRec* h_tab = nullptr;                 // pinned
-    TileRec* d_tab = nullptr;
-    size_t tab_cap = 0;                       // records
+    DeviceBuf<uint16_t> d_cells;
+    DeviceBuf<uint8_t> d_count;               // made behind d_cells: its capacity (cells) stands for both
+    Staged<TileRec> tab;
     host::Counts counts;
+
+    ~visfs_map() {                            // before the members free what they own
+        if (!device) return;
+        (void)hipSetDevice(dev);
+        if (stream) (void)hipStreamSynchronize(stream);
+    }
 };
 
 namespace {
@@ -91,23 +94,8 @@ std::vector<int32_t> odds_table() {
 }
 
 void free_tiles(visfs_map* m) {
-    for (visfs_map::Tile& t : m->tiles) if (t.d) (void)hipFree(t.d);
     m->tiles.clear();
     m->tile_bytes = 0;
-}
-
-void map_free(visfs_map* m) {
-    if (m->device) {
-        (void)hipSetDevice(m->dev);
-        if (m->stream) (void)hipStreamSynchronize(m->stream);
-        free_tiles(m);
-        if (m->d_L) (void)hipFree(m->d_L);
-        if (m->d_cells) (void)hipFree(m->d_cells);
-        if (m->d_count) (void)hipFree(m->d_count);
-        if (m->h_tab) (void)hipHostFree(m->h_tab);
-        if (m->d_tab) (void)hipFree(m->d_tab);
-    }
-    delete m;
 }
 
 bool pose_ok(const double p[3]) { return std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]); }
@@ -136,23 +124,18 @@ int push_tile(visfs_map* m, const Limits& L, const double pose[3], const GridVie
             for (int32_t x = 0; x < L.nx; ++x) t.h[(size_t)y * L.nx + x] = frozen_cell(g, x, y);
     } else {
         HIP_TRY(m, hipSetDevice(m->dev));
-        HIP_TRY(m, hipMalloc(reinterpret_cast<void**>(&t.d), (size_t)n * 2));
-        auto run = [&]() -> int {
-            if (staged) {
-                std::vector<uint16_t> tmp((size_t)n);
-                for (int32_t y = 0; y < L.ny; ++y)
-                    for (int32_t x = 0; x < L.nx; ++x) tmp[(size_t)y * L.nx + x] = frozen_cell(g, x, y);
-                HIP_TRY(m, hipMemcpyAsync(t.d, tmp.data(), (size_t)n * 2, hipMemcpyHostToDevice, m->stream));
-                HIP_TRY(m, hipStreamSynchronize(m->stream));
-                return VISFS_BA_OK;
-            }
-            hipLaunchKernelGGL(k_map_tile, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, m->stream, g, L.nx, n, t.d);
+        RC_TRY(t.d.alloc(m, (size_t)n));
+        if (staged) {
+            std::vector<uint16_t> tmp((size_t)n);
+            for (int32_t y = 0; y < L.ny; ++y)
+                for (int32_t x = 0; x < L.nx; ++x) tmp[(size_t)y * L.nx + x] = frozen_cell(g, x, y);
+            HIP_TRY(m, hipMemcpyAsync(t.d.get(), tmp.data(), (size_t)n * 2, hipMemcpyHostToDevice, m->stream));
+            HIP_TRY(m, hipStreamSynchronize(m->stream));
+        } else {
+            hipLaunchKernelGGL(k_map_tile, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, m->stream, g, L.nx, n, t.d.get());
             HIP_TRY(m, hipGetLastError());
             HIP_TRY(m, hipStreamSynchronize(m->stream));                     // the sub-map may change or go from here on
-            return VISFS_BA_OK;
-        };
-        const int rc = run();
-        if (rc != VISFS_BA_OK) { (void)hipFree(t.d); return rc; }
+        }
     }
     m->tile_bytes += n * 2;
     m->tiles.push_back(std::move(t));
@@ -164,30 +147,21 @@ int device_compose(visfs_map* m, const visfs_map_params& p, Plan& P) {
     const Limits& G = P.G;
     const size_t cells = (size_t)G.nx * G.ny, nt = P.recs.size(), recs = nt ? nt : 1;
     HIP_TRY(m, hipSetDevice(m->dev));
-    if (m->out_cap < cells) {
-        if (m->d_cells) HIP_TRY(m, hipFree(m->d_cells));
-        if (m->d_count) HIP_TRY(m, hipFree(m->d_count));
-        m->d_cells = nullptr; m->d_count = nullptr; m->out_cap = 0; m->have = false;       // the old grid went with its buffers
-        HIP_TRY(m, hipMalloc(reinterpret_cast<void**>(&m->d_cells), cells * 2));
-        HIP_TRY(m, hipMalloc(reinterpret_cast<void**>(&m->d_count), cells));
-        m->out_cap = cells;
+    if (m->d_count.cap() < cells) {
+        m->have = false;                                                   // the old grid goes with its buffers
+        RC_TRY(m->d_cells.release(m));
+        RC_TRY(m->d_count.release(m));
+        RC_TRY(m->d_cells.alloc(m, cells));
+        RC_TRY(m->d_count.alloc(m, cells));
     }
-    if (m->tab_cap < recs) {
-        if (m->h_tab) HIP_TRY(m, hipHostFree(m->h_tab));
-        if (m->d_tab) HIP_TRY(m, hipFree(m->d_tab));
-        m->h_tab = nullptr; m->d_tab = nullptr; m->tab_cap = 0;
-        const size_t cap = recs < 16 ? 16 : recs;
-        HIP_TRY(m, hipHostMalloc(reinterpret_cast<void**>(&m->h_tab), cap * sizeof(TileRec), hipHostMallocDefault));
-        HIP_TRY(m, hipMalloc(reinterpret_cast<void**>(&m->d_tab), cap * sizeof(TileRec)));
-        m->tab_cap = cap;
-    }
-    std::memset(m->h_tab, 0, recs * sizeof(TileRec));
-    for (size_t k = 0; k < nt; ++k) { m->h_tab[k] = P.recs[k]; m->h_tab[k].cells = m->tiles[k].d; }
+    RC_TRY(m->tab.reserve(m, recs, recs < 16 ? 16 : recs));
+    std::memset(m->tab.h.get(), 0, recs * sizeof(TileRec));
+    for (size_t k = 0; k < nt; ++k) { m->tab.h[k] = P.recs[k]; m->tab.h[k].cells = m->tiles[k].d.get(); }
     m->have = false;                                                       // the grid is being overwritten from here on
-    HIP_TRY(m, hipMemcpyAsync(m->d_tab, m->h_tab, recs * sizeof(TileRec), hipMemcpyHostToDevice, m->stream));
+    HIP_TRY(m, hipMemcpyAsync(m->tab.d.get(), m->tab.h.get(), recs * sizeof(TileRec), hipMemcpyHostToDevice, m->stream));
     const int32_t blocks_x = (G.nx + kBlockX - 1) / kBlockX, blocks_y = (G.ny + kBlockY - 1) / kBlockY;
-    hipLaunchKernelGGL(k_map_compose, dim3((unsigned)((int64_t)blocks_x * blocks_y)), dim3(kThreads), 0, m->stream, m->d_tab, (int32_t)nt, m->d_L,
-                       p.combine, G.max_x, G.max_y, G.res, G.nx, G.ny, blocks_x, m->d_cells, m->d_count);
+    hipLaunchKernelGGL(k_map_compose, dim3((unsigned)((int64_t)blocks_x * blocks_y)), dim3(kThreads), 0, m->stream, m->tab.d.get(), (int32_t)nt, m->d_L.get(),
+                       p.combine, G.max_x, G.max_y, G.res, G.nx, G.ny, blocks_x, m->d_cells.get(), m->d_count.get());
     HIP_TRY(m, hipGetLastError());
     HIP_TRY(m, hipStreamSynchronize(m->stream));
     m->counts = { 1, 1, 1 };
@@ -213,7 +187,7 @@ void host_compose(visfs_map* m, const visfs_map_params& p, Plan& P) {
 int visfs_internal_map_access(visfs_map* m, gmap::MapAccess* a) {
     if (!m || !a) return VISFS_BA_ERR_BAD_ARGUMENT;
     a->device = m->device; a->dev = m->dev; a->stream = m->stream; a->have = m->have; a->L = m->G;
-    a->cells = m->device ? m->d_cells : m->h_cells.data();
+    a->cells = m->device ? m->d_cells.get() : m->h_cells.data();
     return VISFS_BA_OK;
 }
 
@@ -240,20 +214,20 @@ int visfs_map_create(visfs_ba_handle* h, visfs_map** out) {
             m->device = true; m->dev = visfs_internal_device(h); m->stream = visfs_internal_stream(h);
             auto run = [&]() -> int {
                 HIP_TRY(m, hipSetDevice(m->dev));
-                HIP_TRY(m, hipMalloc(reinterpret_cast<void**>(&m->d_L), kValues * sizeof(int32_t)));
-                HIP_TRY(m, hipMemcpyAsync(m->d_L, m->L.data(), kValues * sizeof(int32_t), hipMemcpyHostToDevice, m->stream));
+                RC_TRY(m->d_L.alloc(m, kValues));
+                HIP_TRY(m, hipMemcpyAsync(m->d_L.get(), m->L.data(), kValues * sizeof(int32_t), hipMemcpyHostToDevice, m->stream));
                 HIP_TRY(m, hipStreamSynchronize(m->stream));
                 return VISFS_BA_OK;
             };
             const int rc = run();
-            if (rc != VISFS_BA_OK) { visfs_internal_set_error(h, m->err.c_str()); map_free(m); return rc; }
+            if (rc != VISFS_BA_OK) { visfs_internal_set_error(h, m->err.c_str()); delete m; return rc; }
         }
         *out = m;
         return (int)VISFS_BA_OK;
     });
 }
 
-void visfs_map_destroy(visfs_map* m) { if (m) map_free(m); }
+void visfs_map_destroy(visfs_map* m) { delete m; }
 
 const char* visfs_map_last_error(const visfs_map* m) { return m ? m->err.c_str() : "null map"; }
 
@@ -347,8 +321,8 @@ int visfs_map_download(visfs_map* m, uint16_t* cells, uint8_t* count) {
             return (int)VISFS_BA_OK;
         }
         HIP_TRY(m, hipSetDevice(m->dev));
-        if (cells) HIP_TRY(m, hipMemcpyAsync(cells, m->d_cells, n * 2, hipMemcpyDeviceToHost, m->stream));
-        if (count) HIP_TRY(m, hipMemcpyAsync(count, m->d_count, n, hipMemcpyDeviceToHost, m->stream));
+        if (cells) HIP_TRY(m, hipMemcpyAsync(cells, m->d_cells.get(), n * 2, hipMemcpyDeviceToHost, m->stream));
+        if (count) HIP_TRY(m, hipMemcpyAsync(count, m->d_count.get(), n, hipMemcpyDeviceToHost, m->stream));
         HIP_TRY(m, hipStreamSynchronize(m->stream));
         return (int)VISFS_BA_OK;
     });
@@ -361,7 +335,7 @@ int visfs_scan_stack_create_from_map(visfs_map* m, int32_t depth, visfs_scan_sta
         if (depth < 1 || depth > VISFS_SCAN_FAST_MAX_DEPTH) return fail(m, VISFS_BA_ERR_BAD_ARGUMENT, "the depth must lie in [1, 16]");
         if (!m->have) return fail(m, VISFS_BA_ERR_BAD_ARGUMENT, "no composed grid: call visfs_map_compose first");
         GridView g;
-        g.cells = m->device ? m->d_cells : m->h_cells.data(); g.nx = m->G.nx; g.ny = m->G.ny;
+        g.cells = m->device ? m->d_cells.get() : m->h_cells.data(); g.nx = m->G.nx; g.ny = m->G.ny;
         std::string why;
         const int rc = visfs_internal_stack_from_view(m->device, m->dev, m->stream, m->G, g, depth, out, &why);
         if (rc != VISFS_BA_OK) return fail(m, rc, why);

@@ -220,16 +220,6 @@ namespace {
 constexpr size_t kUpBytes = sizeof(Hdr) + (size_t)VISFS_MCL_MAX_BEAMS * 2 * sizeof(double);
 static_assert(sizeof(Hdr) % 8 == 0 && sizeof(InitHdr) <= sizeof(Hdr), "the beams follow the header as doubles");
 
-void field_free(visfs_mcl_field* f) {
-    if (f->device) {
-        (void)hipSetDevice(f->dev);
-        if (f->stream) (void)hipStreamSynchronize(f->stream);
-        if (f->d_t) (void)hipFree(f->d_t);
-        if (f->d_q) (void)hipFree(f->d_q);
-    }
-    delete f;
-}
-
 // The field of `cells` (memory of the given flavour, dense [ny][nx]); the parameters are already planned into f.
 int field_build(visfs_mcl_field* f, const uint16_t* cells) {
     const int32_t nx = f->L.nx, ny = f->L.ny;
@@ -243,24 +233,29 @@ int field_build(visfs_mcl_field* f, const uint16_t* cells) {
             for (int32_t x = 0; x < nx; ++x) f->h_t[(size_t)y * nx + x] = col_min(g.data(), nx, ny, x, y, f->R, f->T);
         return VISFS_BA_OK;
     }
-    uint16_t* g = nullptr;
+    DeviceBuf<uint16_t> g;
     HIP_TRY(nullptr, hipSetDevice(f->dev));
-    HIP_TRY(nullptr, hipMalloc(reinterpret_cast<void**>(&f->d_t), (size_t)total * 2));
-    HIP_TRY(nullptr, hipMalloc(reinterpret_cast<void**>(&f->d_q), f->h_q.size() * sizeof(int64_t)));
-    HIP_TRY(nullptr, hipMalloc(reinterpret_cast<void**>(&g), (size_t)total * 2));
-    auto run = [&]() -> int {
-        HIP_TRY(nullptr, hipMemcpyAsync(f->d_q, f->h_q.data(), f->h_q.size() * sizeof(int64_t), hipMemcpyHostToDevice, f->stream));
-        hipLaunchKernelGGL(k_mcl_rows, dim3(blocks_for(total, kThreads)), dim3(kThreads), 0, f->stream, cells, nx, total, f->v_occ, f->R, g);
-        HIP_TRY(nullptr, hipGetLastError());
-        hipLaunchKernelGGL(k_mcl_cols, dim3(blocks_for(total, kThreads)), dim3(kThreads), 0, f->stream, g, nx, ny, total, f->R, f->T, f->d_t);
-        HIP_TRY(nullptr, hipGetLastError());
-        HIP_TRY(nullptr, hipStreamSynchronize(f->stream));
-        return VISFS_BA_OK;
-    };
-    const int rc = run();
-    (void)hipFree(g);
+    RC_TRY(f->d_t.alloc(nullptr, (size_t)total));
+    RC_TRY(f->d_q.alloc(nullptr, f->h_q.size()));
+    RC_TRY(g.alloc(nullptr, (size_t)total));
     f->counts = { VISFS_MCL_FIELD_LAUNCHES, 1, 1 };
-    return rc;
+    HIP_TRY(nullptr, hipMemcpyAsync(f->d_q.get(), f->h_q.data(), f->h_q.size() * sizeof(int64_t), hipMemcpyHostToDevice, f->stream));
+    hipLaunchKernelGGL(k_mcl_rows, dim3(blocks_for(total, kThreads)), dim3(kThreads), 0, f->stream, cells, nx, total, f->v_occ, f->R, g.get());
+    HIP_TRY(nullptr, hipGetLastError());
+    hipLaunchKernelGGL(k_mcl_cols, dim3(blocks_for(total, kThreads)), dim3(kThreads), 0, f->stream, g.get(), nx, ny, total, f->R, f->T, f->d_t.get());
+    HIP_TRY(nullptr, hipGetLastError());
+    HIP_TRY(nullptr, hipStreamSynchronize(f->stream));
+    return VISFS_BA_OK;
+}
+
+// The field of host `cells` on the device: their copy lives until field_build has waited for the stream.
+int field_build_uploaded(visfs_mcl_field* f, const uint16_t* cells) {
+    const size_t total = (size_t)f->L.nx * f->L.ny;
+    DeviceBuf<uint16_t> d_cells;
+    HIP_TRY(nullptr, hipSetDevice(f->dev));
+    RC_TRY(d_cells.alloc(nullptr, total));
+    HIP_TRY(nullptr, hipMemcpyAsync(d_cells.get(), cells, total * 2, hipMemcpyHostToDevice, f->stream));
+    return field_build(f, d_cells.get());
 }
 
 // Plans the parameters on limits L into a new field object; *out stays null on a refusal.
@@ -277,41 +272,28 @@ int field_new(const Limits& L, const visfs_mcl_field_params& p, visfs_mcl_field*
 
 FieldView view_of(const visfs_mcl_field* f) {
     FieldView F;
-    F.t = f->device ? f->d_t : f->h_t.data();
-    F.q = f->device ? f->d_q : f->h_q.data();
+    F.t = f->device ? f->d_t.get() : f->h_t.data();
+    F.q = f->device ? f->d_q.get() : f->h_q.data();
     F.res = f->L.res; F.max_x = f->L.max_x; F.max_y = f->L.max_y; F.nx = f->L.nx; F.ny = f->L.ny; F.T = f->T;
     return F;
-}
-
-void mcl_free(visfs_mcl* f) {
-    if (f->kld) kld_free(f);
-    if (f->device) {
-        (void)hipSetDevice(f->dev);
-        if (f->stream) (void)hipStreamSynchronize(f->stream);
-        void* dv[] = { f->d_st[0], f->d_st[1], f->d_cs, f->d_Q, f->d_anc, f->d_C, f->d_bsum, f->d_part, f->d_pbw, f->d_pbi, f->d_up, f->d_rec };
-        for (void* p : dv) if (p) (void)hipFree(p);
-        if (f->h_up) (void)hipHostFree(f->h_up);
-        if (f->h_rec) (void)hipHostFree(f->h_rec);
-    }
-    delete f;
 }
 
 int mcl_alloc(visfs_mcl* f) {
     const size_t N = (size_t)f->N;
     HIP_TRY(f, hipSetDevice(f->dev));
-    for (int b = 0; b < 2; ++b) HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&f->d_st[b]), 4 * N * sizeof(double)));
-    HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&f->d_cs), 2 * N * sizeof(double)));
-    HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&f->d_Q), N * sizeof(int64_t)));
-    HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&f->d_anc), N * sizeof(int32_t)));
-    HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&f->d_C), N * sizeof(uint64_t)));
-    HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&f->d_bsum), kMaxBlocks * sizeof(uint64_t)));
-    HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&f->d_part), (size_t)kMaxBlocks * kSums * sizeof(double)));
-    HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&f->d_pbw), kMaxBlocks * sizeof(double)));
-    HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&f->d_pbi), kMaxBlocks * sizeof(int32_t)));
-    HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&f->d_up), kUpBytes));
-    HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&f->d_rec), sizeof(Rec)));
-    HIP_TRY(f, hipHostMalloc(reinterpret_cast<void**>(&f->h_up), kUpBytes, hipHostMallocDefault));
-    HIP_TRY(f, hipHostMalloc(reinterpret_cast<void**>(&f->h_rec), sizeof(Rec), hipHostMallocDefault));
+    for (int b = 0; b < 2; ++b) RC_TRY(f->d_st[b].alloc(f, 4 * N));
+    RC_TRY(f->d_cs.alloc(f, 2 * N));
+    RC_TRY(f->d_Q.alloc(f, N));
+    RC_TRY(f->d_anc.alloc(f, N));
+    RC_TRY(f->d_C.alloc(f, N));
+    RC_TRY(f->d_bsum.alloc(f, kMaxBlocks));
+    RC_TRY(f->d_part.alloc(f, (size_t)kMaxBlocks * kSums));
+    RC_TRY(f->d_pbw.alloc(f, kMaxBlocks));
+    RC_TRY(f->d_pbi.alloc(f, kMaxBlocks));
+    RC_TRY(f->d_up.alloc(f, kUpBytes));
+    RC_TRY(f->d_rec.alloc(f, 1));
+    RC_TRY(f->h_up.alloc(f, kUpBytes));
+    RC_TRY(f->h_rec.alloc(f, 1));
     return VISFS_BA_OK;
 }
 
@@ -325,30 +307,30 @@ int32_t lanes_for(const visfs_mcl* f, int32_t n) {
 int device_update(visfs_mcl* f, const Hdr& H, const std::vector<double>& beams, Rec& rec) {
     const int32_t N = H.N, blocks = (int32_t)blocks_for(N, kThreads);                 // the active count
     HIP_TRY(f, hipSetDevice(f->dev));
-    std::memcpy(f->h_up, &H, sizeof H);
-    if (!beams.empty()) std::memcpy(f->h_up + sizeof H, beams.data(), beams.size() * sizeof(double));
-    HIP_TRY(f, hipMemcpyAsync(f->d_up, f->h_up, sizeof H + beams.size() * sizeof(double), hipMemcpyHostToDevice, f->stream));
-    const Hdr* up = reinterpret_cast<const Hdr*>(f->d_up);
-    double* st = f->d_st[f->cur];
-    hipLaunchKernelGGL(k_mcl_weight, dim3(blocks_for((int64_t)N * H.lanes, kThreads)), dim3(kThreads), 0, f->stream, up, view_of(f->field), st, f->d_cs, f->d_Q);
+    std::memcpy(f->h_up.get(), &H, sizeof H);
+    if (!beams.empty()) std::memcpy(f->h_up.get() + sizeof H, beams.data(), beams.size() * sizeof(double));
+    HIP_TRY(f, hipMemcpyAsync(f->d_up.get(), f->h_up.get(), sizeof H + beams.size() * sizeof(double), hipMemcpyHostToDevice, f->stream));
+    const Hdr* up = reinterpret_cast<const Hdr*>(f->d_up.get());
+    double* st = f->d_st[f->cur].get();
+    hipLaunchKernelGGL(k_mcl_weight, dim3(blocks_for((int64_t)N * H.lanes, kThreads)), dim3(kThreads), 0, f->stream, up, view_of(f->field), st, f->d_cs.get(), f->d_Q.get());
     HIP_TRY(f, hipGetLastError());
-    hipLaunchKernelGGL(k_mcl_sums, dim3((unsigned)blocks), dim3(kThreads), 0, f->stream, up, st, f->d_cs, f->d_part, f->d_pbw, f->d_pbi);
+    hipLaunchKernelGGL(k_mcl_sums, dim3((unsigned)blocks), dim3(kThreads), 0, f->stream, up, st, f->d_cs.get(), f->d_part.get(), f->d_pbw.get(), f->d_pbi.get());
     HIP_TRY(f, hipGetLastError());
-    hipLaunchKernelGGL(k_mcl_finish, dim3((unsigned)blocks), dim3(kThreads), 0, f->stream, up, st, f->d_part, f->d_pbw, f->d_pbi, blocks,
-                       f->kld ? kld_device_rec(f) : f->d_rec, f->d_C, f->d_bsum, f->d_anc);
+    hipLaunchKernelGGL(k_mcl_finish, dim3((unsigned)blocks), dim3(kThreads), 0, f->stream, up, st, f->d_part.get(), f->d_pbw.get(), f->d_pbi.get(), blocks,
+                       f->kld ? kld_device_rec(f) : f->d_rec.get(), f->d_C.get(), f->d_bsum.get(), f->d_anc.get());
     HIP_TRY(f, hipGetLastError());
     if (f->kld) {                                                          // k_mcl_kld_resample takes the fourth launch's place
-        const int rc = kld_device_resample(f, up, st, f->d_st[f->cur ^ 1], blocks, rec);
+        const int rc = kld_device_resample(f, up, st, f->d_st[f->cur ^ 1].get(), blocks, rec);
         if (rc != VISFS_BA_OK) return rc;
         f->counts = { VISFS_MCL_UPDATE_LAUNCHES, 2, 1 };
         return VISFS_BA_OK;
     }
-    hipLaunchKernelGGL(k_mcl_resample, dim3((unsigned)blocks), dim3(kThreads), 0, f->stream, up, f->d_rec, st, f->d_st[f->cur ^ 1], f->d_C,
-                       f->d_bsum, blocks, f->d_anc);
+    hipLaunchKernelGGL(k_mcl_resample, dim3((unsigned)blocks), dim3(kThreads), 0, f->stream, up, f->d_rec.get(), st, f->d_st[f->cur ^ 1].get(), f->d_C.get(),
+                       f->d_bsum.get(), blocks, f->d_anc.get());
     HIP_TRY(f, hipGetLastError());
-    HIP_TRY(f, hipMemcpyAsync(f->h_rec, f->d_rec, sizeof(Rec), hipMemcpyDeviceToHost, f->stream));
+    HIP_TRY(f, hipMemcpyAsync(f->h_rec.get(), f->d_rec.get(), sizeof(Rec), hipMemcpyDeviceToHost, f->stream));
     HIP_TRY(f, hipStreamSynchronize(f->stream));
-    rec = *f->h_rec;
+    rec = *f->h_rec.get();
     f->counts = { VISFS_MCL_UPDATE_LAUNCHES, 2, 1 };
     return VISFS_BA_OK;
 }
@@ -436,7 +418,7 @@ int visfs_mcl_field_create_from_map(visfs_map* m, const visfs_mcl_field_params* 
         const char* why = "";
         if ((rc = field_new(a.L, *p, &f, &why)) != VISFS_BA_OK) return rc;
         f->device = a.device; f->dev = a.dev; f->stream = a.stream;
-        if ((rc = field_build(f, a.cells)) != VISFS_BA_OK) { field_free(f); return rc; }
+        if ((rc = field_build(f, a.cells)) != VISFS_BA_OK) { delete f; return rc; }
         *out = f;
         return (int)VISFS_BA_OK;
     });
@@ -454,28 +436,19 @@ int visfs_mcl_field_create_from_grid(visfs_ba_handle* h, const visfs_submap_info
         int rc = field_new(L, *p, &f, &why);
         if (rc != VISFS_BA_OK) { if (h) visfs_internal_set_error(h, why); return rc; }
         if (!h) {
-            if ((rc = field_build(f, cells)) != VISFS_BA_OK) { field_free(f); return rc; }
+            if ((rc = field_build(f, cells)) != VISFS_BA_OK) { delete f; return rc; }
             *out = f;
             return (int)VISFS_BA_OK;
         }
         f->device = true; f->dev = visfs_internal_device(h); f->stream = visfs_internal_stream(h);
-        const size_t bytes = (size_t)L.nx * L.ny * 2;
-        uint16_t* d_cells = nullptr;
-        auto run = [&]() -> int {
-            HIP_TRY(nullptr, hipSetDevice(f->dev));
-            HIP_TRY(nullptr, hipMalloc(reinterpret_cast<void**>(&d_cells), bytes));
-            HIP_TRY(nullptr, hipMemcpyAsync(d_cells, cells, bytes, hipMemcpyHostToDevice, f->stream));
-            return field_build(f, d_cells);
-        };
-        rc = run();
-        if (d_cells) (void)hipFree(d_cells);                                           // field_build has waited for the stream
-        if (rc != VISFS_BA_OK) { visfs_internal_set_error(h, "the likelihood field could not be built on the device"); field_free(f); return rc; }
+        rc = field_build_uploaded(f, cells);
+        if (rc != VISFS_BA_OK) { visfs_internal_set_error(h, "the likelihood field could not be built on the device"); delete f; return rc; }
         *out = f;
         return (int)VISFS_BA_OK;
     });
 }
 
-void visfs_mcl_field_destroy(visfs_mcl_field* f) { if (f) field_free(f); }
+void visfs_mcl_field_destroy(visfs_mcl_field* f) { delete f; }
 
 int visfs_mcl_field_describe(const visfs_mcl_field* f, visfs_mcl_field_info* info) {
     if (!f || !info) return VISFS_BA_ERR_BAD_ARGUMENT;
@@ -495,7 +468,7 @@ int visfs_mcl_field_download(visfs_mcl_field* f, uint16_t* t, int64_t* q, int32_
             if (!f->device) std::memcpy(t, f->h_t.data(), n * 2);
             else {
                 HIP_TRY(nullptr, hipSetDevice(f->dev));
-                HIP_TRY(nullptr, hipMemcpyAsync(t, f->d_t, n * 2, hipMemcpyDeviceToHost, f->stream));
+                HIP_TRY(nullptr, hipMemcpyAsync(t, f->d_t.get(), n * 2, hipMemcpyDeviceToHost, f->stream));
                 HIP_TRY(nullptr, hipStreamSynchronize(f->stream));
             }
         }
@@ -503,7 +476,7 @@ int visfs_mcl_field_download(visfs_mcl_field* f, uint16_t* t, int64_t* q, int32_
             if (!f->device) std::memcpy(q, f->h_q.data(), f->h_q.size() * sizeof(int64_t));
             else {                                                                     // what the device holds, not the host's copy
                 HIP_TRY(nullptr, hipSetDevice(f->dev));
-                HIP_TRY(nullptr, hipMemcpyAsync(q, f->d_q, f->h_q.size() * sizeof(int64_t), hipMemcpyDeviceToHost, f->stream));
+                HIP_TRY(nullptr, hipMemcpyAsync(q, f->d_q.get(), f->h_q.size() * sizeof(int64_t), hipMemcpyDeviceToHost, f->stream));
                 HIP_TRY(nullptr, hipStreamSynchronize(f->stream));
             }
         }
@@ -528,7 +501,7 @@ int visfs_mcl_create(visfs_mcl_field* field, int32_t n_particles, uint64_t seed,
         const size_t N = (size_t)n_particles;
         if (f->device) {
             const int rc = mcl_alloc(f);
-            if (rc != VISFS_BA_OK) { mcl_free(f); return rc; }
+            if (rc != VISFS_BA_OK) { delete f; return rc; }
         } else {
             for (auto& v : f->h_st) v.assign(4 * N, 0.0);
             f->h_Q.assign(N, 0); f->h_anc.assign(N, 0);
@@ -536,13 +509,13 @@ int visfs_mcl_create(visfs_mcl_field* field, int32_t n_particles, uint64_t seed,
         *out = f;
         const double zero[3] = { 0.0, 0.0, 0.0 };
         const int rc = visfs_mcl_init(f, zero, zero);                                  // a defined state from the start
-        if (rc != VISFS_BA_OK) { *out = nullptr; mcl_free(f); return rc; }
+        if (rc != VISFS_BA_OK) { *out = nullptr; delete f; return rc; }
         f->counts = {};
         return (int)VISFS_BA_OK;
     });
 }
 
-void visfs_mcl_destroy(visfs_mcl* f) { if (f) mcl_free(f); }
+void visfs_mcl_destroy(visfs_mcl* f) { if (f) delete f; }
 
 const char* visfs_mcl_last_error(const visfs_mcl* f) { return f ? f->err.c_str() : "null filter"; }
 
@@ -570,10 +543,10 @@ int visfs_mcl_init(visfs_mcl* f, const double mean[3], const double sigma[3]) {
             f->counts = {};
         } else {
             HIP_TRY(f, hipSetDevice(f->dev));
-            std::memcpy(f->h_up, &I, sizeof I);
-            HIP_TRY(f, hipMemcpyAsync(f->d_up, f->h_up, sizeof I, hipMemcpyHostToDevice, f->stream));
-            hipLaunchKernelGGL(k_mcl_init, dim3(blocks_for(f->N, kThreads)), dim3(kThreads), 0, f->stream, reinterpret_cast<const InitHdr*>(f->d_up), f->d_st[0],
-                               f->d_Q, f->d_anc);
+            std::memcpy(f->h_up.get(), &I, sizeof I);
+            HIP_TRY(f, hipMemcpyAsync(f->d_up.get(), f->h_up.get(), sizeof I, hipMemcpyHostToDevice, f->stream));
+            hipLaunchKernelGGL(k_mcl_init, dim3(blocks_for(f->N, kThreads)), dim3(kThreads), 0, f->stream, reinterpret_cast<const InitHdr*>(f->d_up.get()), f->d_st[0].get(),
+                               f->d_Q.get(), f->d_anc.get());
             HIP_TRY(f, hipGetLastError());
             HIP_TRY(f, hipStreamSynchronize(f->stream));
             f->counts = { VISFS_MCL_INIT_LAUNCHES, 1, 1 };
@@ -644,9 +617,9 @@ int visfs_mcl_download(visfs_mcl* f, double* x, double* y, double* yaw, double* 
         }
         HIP_TRY(f, hipSetDevice(f->dev));
         for (int k = 0; k < 4; ++k)
-            if (dst[k]) HIP_TRY(f, hipMemcpyAsync(dst[k], f->d_st[f->cur] + k * N, N * sizeof(double), hipMemcpyDeviceToHost, f->stream));
-        if (Q) HIP_TRY(f, hipMemcpyAsync(Q, f->d_Q, N * sizeof(int64_t), hipMemcpyDeviceToHost, f->stream));
-        if (ancestors) HIP_TRY(f, hipMemcpyAsync(ancestors, f->d_anc, N * sizeof(int32_t), hipMemcpyDeviceToHost, f->stream));
+            if (dst[k]) HIP_TRY(f, hipMemcpyAsync(dst[k], f->d_st[f->cur].get() + k * N, N * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+        if (Q) HIP_TRY(f, hipMemcpyAsync(Q, f->d_Q.get(), N * sizeof(int64_t), hipMemcpyDeviceToHost, f->stream));
+        if (ancestors) HIP_TRY(f, hipMemcpyAsync(ancestors, f->d_anc.get(), N * sizeof(int32_t), hipMemcpyDeviceToHost, f->stream));
         HIP_TRY(f, hipStreamSynchronize(f->stream));
         return (int)VISFS_BA_OK;
     });
@@ -677,7 +650,7 @@ int mcl::upload_n(visfs_mcl* f, int32_t n, const double* x, const double* y, con
             return (int)VISFS_BA_OK;
         }
         HIP_TRY(f, hipSetDevice(f->dev));
-        for (int k = 0; k < 4; ++k) HIP_TRY(f, hipMemcpyAsync(f->d_st[f->cur] + k * N, src[k], N * sizeof(double), hipMemcpyHostToDevice, f->stream));
+        for (int k = 0; k < 4; ++k) HIP_TRY(f, hipMemcpyAsync(f->d_st[f->cur].get() + k * N, src[k], N * sizeof(double), hipMemcpyHostToDevice, f->stream));
         HIP_TRY(f, hipStreamSynchronize(f->stream));
         f->n = n;
         if (f->kld) kld_particles_replaced(f);

@@ -35,10 +35,10 @@ struct Kld {
     visfs_mcl_kld_params p;
     std::vector<int32_t> h_limit;             // [N + 1], both flavours
     int32_t hash_bits = -1;                   // -1: the table's full width
-    int32_t* d_limit = nullptr;
-    int32_t* d_work = nullptr;                // [5 N]
-    KldRec* d_rec = nullptr;
-    KldRec* h_rec = nullptr;                  // pinned
+    DeviceBuf<int32_t> d_limit;
+    DeviceBuf<int32_t> d_work;                // [5 N]
+    DeviceBuf<KldRec> d_rec;
+    PinnedBuf<KldRec> h_rec;                  // pinned
     int32_t pending[3] = { 0, 0, 0 };         // n_after, bins, limit of the update that is running
     visfs_mcl_kld_result last;
     bool have_last = false;
@@ -47,10 +47,10 @@ struct Kld {
 
 // The hypotheses of section 9v on a KLD filter.
 struct Hyp {
-    int32_t* d_work = nullptr;                // [kHypWorkInts N]
-    double* d_cs = nullptr;                   // [2 N]
-    HypRec* d_rec = nullptr;                  // takes the place of Kld::d_rec
-    HypRec* h_rec = nullptr;                  // pinned
+    DeviceBuf<int32_t> d_work;                // [kHypWorkInts N]
+    DeviceBuf<double> d_cs;                   // [2 N]
+    DeviceBuf<HypRec> d_rec;                  // takes the place of Kld::d_rec
+    PinnedBuf<HypRec> h_rec;                  // pinned
     HypBlock pending;                         // of the update that is running
     std::vector<int32_t> h_label;             // the twin's labels of the last resampling
     visfs_mcl_hyp_result last;                // all zero while there are none
@@ -196,31 +196,15 @@ __global__ __launch_bounds__(kKldThreads) void k_mcl_kld_resample(const Hdr* __r
     }
 }
 
-// Frees what a Hyp holds on the device (the stream is idle) and the object.
-void hyp_free(visfs_mcl* f, Hyp* h) {
-    if (!h) return;
-    if (f->device) {
-        if (h->d_work) (void)hipFree(h->d_work);
-        if (h->d_cs) (void)hipFree(h->d_cs);
-        if (h->d_rec) (void)hipFree(h->d_rec);
-        if (h->h_rec) (void)hipHostFree(h->h_rec);
-    }
-    delete h;
-}
-
+// Waits for the stream, then the members of the Kld and of its Hyp free what they own.
 void kld_free(visfs_mcl* f) {
     Kld* k = f->kld;
     if (!k) return;
     if (f->device) {
         (void)hipSetDevice(f->dev);
         if (f->stream) (void)hipStreamSynchronize(f->stream);
-        hyp_free(f, k->hyp);
-        if (k->d_limit) (void)hipFree(k->d_limit);
-        if (k->d_work) (void)hipFree(k->d_work);
-        if (k->d_rec) (void)hipFree(k->d_rec);
-        if (k->h_rec) (void)hipHostFree(k->h_rec);
     }
-    else hyp_free(f, k->hyp);
+    delete k->hyp;
     delete k;
     f->kld = nullptr;
 }
@@ -239,7 +223,7 @@ int kld_device_resample(visfs_mcl* f, const Hdr* up, const double* st, double* o
     KldArgs A;
     std::memset(&A, 0, sizeof A);
     A.bin_xy = k->p.bin_xy; A.bin_yaw = k->p.bin_yaw;
-    A.limit = k->d_limit; A.work = k->d_work;
+    A.limit = k->d_limit.get(); A.work = k->d_work.get();
     A.cap = f->N; A.slots = kld_slots(f->N);
     int32_t width = 0;
     while ((1 << width) < A.slots) ++width;
@@ -247,11 +231,11 @@ int kld_device_resample(visfs_mcl* f, const Hdr* up, const double* st, double* o
     A.home_mask = (int32_t)((1u << bits) - 1u);
     Hyp* h = k->hyp;                                                       // the same launch with the hypotheses; their block comes down behind KldRec
     HypArgs G = HypArgs();
-    if (h) { G.work = h->d_work; G.cs = h->d_cs; }
+    if (h) { G.work = h->d_work.get(); G.cs = h->d_cs.get(); }
     const auto kernel = h ? k_mcl_kld_resample<true> : k_mcl_kld_resample<false>;
-    KldRec* d_rec = h ? &h->d_rec->k : k->d_rec;
-    KldRec* h_rec = h ? &h->h_rec->k : k->h_rec;
-    hipLaunchKernelGGL(kernel, dim3(1), dim3(kKldThreads), 0, f->stream, up, d_rec, st, out, f->d_C, f->d_bsum, blocks, f->d_anc, A, G);
+    KldRec* d_rec = h ? &h->d_rec->k : k->d_rec.get();
+    KldRec* h_rec = h ? &h->h_rec->k : k->h_rec.get();
+    hipLaunchKernelGGL(kernel, dim3(1), dim3(kKldThreads), 0, f->stream, up, d_rec, st, out, f->d_C.get(), f->d_bsum.get(), blocks, f->d_anc.get(), A, G);
     HIP_TRY(f, hipGetLastError());
     HIP_TRY(f, hipMemcpyAsync(h_rec, d_rec, h ? sizeof(HypRec) : sizeof(KldRec), hipMemcpyDeviceToHost, f->stream));
     HIP_TRY(f, hipStreamSynchronize(f->stream));
@@ -339,12 +323,12 @@ int visfs_mcl_kld_enable(visfs_mcl* f, const visfs_mcl_kld_params* p) {
             const size_t N = (size_t)f->N;
             HIP_TRY(f, hipSetDevice(f->dev));
             if (fresh) {
-                HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&k->d_limit), (N + 1) * sizeof(int32_t)));
-                HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&k->d_work), 5 * N * sizeof(int32_t)));
-                HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&k->d_rec), sizeof(KldRec)));
-                HIP_TRY(f, hipHostMalloc(reinterpret_cast<void**>(&k->h_rec), sizeof(KldRec), hipHostMallocDefault));
+                RC_TRY(k->d_limit.alloc(f, N + 1));
+                RC_TRY(k->d_work.alloc(f, 5 * N));
+                RC_TRY(k->d_rec.alloc(f, 1));
+                RC_TRY(k->h_rec.alloc(f, 1));
             }
-            HIP_TRY(f, hipMemcpyAsync(k->d_limit, limit.data(), (N + 1) * sizeof(int32_t), hipMemcpyHostToDevice, f->stream));
+            HIP_TRY(f, hipMemcpyAsync(k->d_limit.get(), limit.data(), (N + 1) * sizeof(int32_t), hipMemcpyHostToDevice, f->stream));
             HIP_TRY(f, hipStreamSynchronize(f->stream));                               // `limit` is pageable and leaves scope
             return (int)VISFS_BA_OK;
         };
@@ -383,7 +367,7 @@ int visfs_mcl_kld_limits(visfs_mcl* f, int32_t* limit) {
         const size_t bytes = ((size_t)f->N + 1) * sizeof(int32_t);
         if (!f->device) { std::memcpy(limit, f->kld->h_limit.data(), bytes); return (int)VISFS_BA_OK; }
         HIP_TRY(f, hipSetDevice(f->dev));                                              // what the device holds, not the host's copy
-        HIP_TRY(f, hipMemcpyAsync(limit, f->kld->d_limit, bytes, hipMemcpyDeviceToHost, f->stream));
+        HIP_TRY(f, hipMemcpyAsync(limit, f->kld->d_limit.get(), bytes, hipMemcpyDeviceToHost, f->stream));
         HIP_TRY(f, hipStreamSynchronize(f->stream));
         return (int)VISFS_BA_OK;
     });
@@ -412,16 +396,16 @@ int visfs_mcl_hyp_enable(visfs_mcl* f) {
             if (!f->device) return (int)VISFS_BA_OK;
             const size_t N = (size_t)f->N;
             HIP_TRY(f, hipSetDevice(f->dev));
-            HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&h->d_work), (size_t)kHypWorkInts * N * sizeof(int32_t)));
-            HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&h->d_cs), 2 * N * sizeof(double)));
-            HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&h->d_rec), sizeof(HypRec)));
-            HIP_TRY(f, hipHostMalloc(reinterpret_cast<void**>(&h->h_rec), sizeof(HypRec), hipHostMallocDefault));
-            HIP_TRY(f, hipMemsetAsync(h->d_rec, 0, sizeof(HypRec), f->stream));
+            RC_TRY(h->d_work.alloc(f, (size_t)kHypWorkInts * N));
+            RC_TRY(h->d_cs.alloc(f, 2 * N));
+            RC_TRY(h->d_rec.alloc(f, 1));
+            RC_TRY(h->h_rec.alloc(f, 1));
+            HIP_TRY(f, hipMemsetAsync(h->d_rec.get(), 0, sizeof(HypRec), f->stream));
             HIP_TRY(f, hipStreamSynchronize(f->stream));
             return (int)VISFS_BA_OK;
         };
         const int rc = push();
-        if (rc != VISFS_BA_OK) { hyp_free(f, h); return rc; }
+        if (rc != VISFS_BA_OK) { delete h; return rc; }
         f->kld->hyp = h;
         return (int)VISFS_BA_OK;
     });
@@ -443,7 +427,7 @@ int visfs_mcl_hyp_download_labels(visfs_mcl* f, int32_t* label) {
         const size_t bytes = (size_t)h->last.n * sizeof(int32_t);
         if (!f->device) { std::memcpy(label, h->h_label.data(), bytes); return (int)VISFS_BA_OK; }
         HIP_TRY(f, hipSetDevice(f->dev));
-        HIP_TRY(f, hipMemcpyAsync(label, h->d_work, bytes, hipMemcpyDeviceToHost, f->stream));
+        HIP_TRY(f, hipMemcpyAsync(label, h->d_work.get(), bytes, hipMemcpyDeviceToHost, f->stream));
         HIP_TRY(f, hipStreamSynchronize(f->stream));
         return (int)VISFS_BA_OK;
     });

@@ -11,7 +11,11 @@
 #include <string>
 #include <vector>
 
-namespace mcl { struct Kld; }
+struct visfs_mcl;
+namespace mcl {
+struct Kld;
+void kld_free(visfs_mcl* f);                 // ba_mcl_kld.hip, called only when f->kld is set
+}
 
 struct visfs_mcl_field {
     bool device = false;
@@ -21,9 +25,15 @@ struct visfs_mcl_field {
     int32_t R = 0, T = 0, v_occ = 0;
     std::vector<uint16_t> h_t;
     std::vector<int64_t> h_q;                 // both flavours keep the table
-    uint16_t* d_t = nullptr;
-    int64_t* d_q = nullptr;
+    host::DeviceBuf<uint16_t> d_t;
+    host::DeviceBuf<int64_t> d_q;
     host::Counts counts;
+
+    ~visfs_mcl_field() {                      // before the members free what they own
+        if (!device) return;
+        (void)hipSetDevice(dev);
+        if (stream) (void)hipStreamSynchronize(stream);
+    }
 };
 
 struct visfs_mcl {
@@ -41,23 +51,30 @@ struct visfs_mcl {
     std::vector<int64_t> h_Q;
     std::vector<int32_t> h_anc;
     // device
-    double* d_st[2] = { nullptr, nullptr };
-    double* d_cs = nullptr;
-    int64_t* d_Q = nullptr;
-    int32_t* d_anc = nullptr;
-    uint64_t* d_C = nullptr;
-    uint64_t* d_bsum = nullptr;
-    double* d_part = nullptr;
-    double* d_pbw = nullptr;
-    int32_t* d_pbi = nullptr;
-    char* h_up = nullptr;                     // pinned: the header and the beams
-    char* d_up = nullptr;
-    mcl::Rec* h_rec = nullptr;                // pinned
-    mcl::Rec* d_rec = nullptr;
+    host::DeviceBuf<double> d_st[2];
+    host::DeviceBuf<double> d_cs;
+    host::DeviceBuf<int64_t> d_Q;
+    host::DeviceBuf<int32_t> d_anc;
+    host::DeviceBuf<uint64_t> d_C;
+    host::DeviceBuf<uint64_t> d_bsum;
+    host::DeviceBuf<double> d_part;
+    host::DeviceBuf<double> d_pbw;
+    host::DeviceBuf<int32_t> d_pbi;
+    host::PinnedBuf<char> h_up;               // pinned: the header and the beams
+    host::DeviceBuf<char> d_up;
+    host::PinnedBuf<mcl::Rec> h_rec;          // pinned
+    host::DeviceBuf<mcl::Rec> d_rec;
     visfs_mcl_result last;
     bool have_last = false;
     host::Counts counts;
     mcl::Kld* kld = nullptr;                  // null: the plain filter
+
+    ~visfs_mcl() {                            // before the members free what they own
+        if (kld) mcl::kld_free(this);
+        if (!device) return;
+        (void)hipSetDevice(dev);
+        if (stream) (void)hipStreamSynchronize(stream);
+    }
 };
 
 namespace mcl {
@@ -66,8 +83,6 @@ namespace mcl {
 // visfs_mcl_upload with a count: the refusals, the copy at stride n, and n becomes the active count.
 int upload_n(visfs_mcl* f, int32_t n, const double* x, const double* y, const double* yaw, const double* w);
 
-// ---- ba_mcl_kld.hip, called only when f->kld is set
-void kld_free(visfs_mcl* f);
 // Where k_mcl_finish writes the record of a KLD update: the head of the longer record that the update downloads.
 Rec* kld_device_rec(visfs_mcl* f);
 // The fourth launch of a KLD update, its one download and its one wait; `rec` and the pending counts are filled.

@@ -200,43 +200,14 @@ namespace {
 
 constexpr size_t kIoBytes = sizeof(visfs_place_result) > sizeof(Payload) ? sizeof(visfs_place_result) : sizeof(Payload);
 
-void release(visfs_place_set* s) {
-    if (s->device) {
-        (void)hipSetDevice(s->dev);
-        if (s->stream) (void)hipStreamSynchronize(s->stream);
-        if (s->d_set) (void)hipFree(s->d_set);
-        if (s->d_table) (void)hipFree(s->d_table);
-        if (s->h_xy) (void)hipHostFree(s->h_xy);
-        if (s->up_done) (void)hipEventDestroy(s->up_done);
-    }
-    delete s->host;
-    delete s;
-}
-
-void release(visfs_place_db* db) {
-    if (db->device) {
-        (void)hipSetDevice(db->dev);
-        if (db->stream) (void)hipStreamSynchronize(db->stream);
-        if (db->d_slots) (void)hipFree(db->d_slots);
-        if (db->d_pay) (void)hipFree(db->d_pay);
-        if (db->d_match) (void)hipFree(db->d_match);
-        if (db->d_counts) (void)hipFree(db->d_counts);
-        if (db->d_prm) (void)hipFree(db->d_prm);
-        if (db->d_result) (void)hipFree(db->d_result);
-        if (db->h_io) (void)hipHostFree(db->h_io);
-        if (db->up_done) (void)hipEventDestroy(db->up_done);
-    }
-    delete db;
-}
-
 int set_alloc(visfs_place_set* s) {
     HIP_TRY(s, hipSetDevice(s->dev));
-    HIP_TRY(s, hipMalloc(reinterpret_cast<void**>(&s->d_set), sizeof(SetBlock)));
-    HIP_TRY(s, hipMalloc(reinterpret_cast<void**>(&s->d_table), sizeof(Table)));
-    HIP_TRY(s, hipHostMalloc(reinterpret_cast<void**>(&s->h_xy), sizeof(float) * 2 * kMaxPoints, hipHostMallocDefault));
-    HIP_TRY(s, hipEventCreateWithFlags(&s->up_done, hipEventDisableTiming));
-    HIP_TRY(s, hipMemsetAsync(s->d_set, 0, sizeof(SetBlock), s->stream));
-    HIP_TRY(s, hipMemcpyAsync(s->d_table, &host_table(), sizeof(Table), hipMemcpyHostToDevice, s->stream));
+    RC_TRY(s->d_set.alloc(s, 1));
+    RC_TRY(s->d_table.alloc(s, 1));
+    RC_TRY(s->h_xy.alloc(s, 2 * kMaxPoints));
+    RC_TRY(s->up_done.create(s, hipEventDisableTiming));
+    HIP_TRY(s, hipMemsetAsync(s->d_set.get(), 0, sizeof(SetBlock), s->stream));
+    HIP_TRY(s, hipMemcpyAsync(s->d_table.get(), &host_table(), sizeof(Table), hipMemcpyHostToDevice, s->stream));
     HIP_TRY(s, hipStreamSynchronize(s->stream));
     return VISFS_BA_OK;
 }
@@ -244,21 +215,21 @@ int set_alloc(visfs_place_set* s) {
 int db_alloc(visfs_place_db* db) {
     const size_t K = (size_t)db->max_keyframes;
     HIP_TRY(db, hipSetDevice(db->dev));
-    HIP_TRY(db, hipMalloc(reinterpret_cast<void**>(&db->d_slots), K * sizeof(SlotBlock)));
-    HIP_TRY(db, hipMalloc(reinterpret_cast<void**>(&db->d_pay), K * sizeof(Payload)));
-    HIP_TRY(db, hipMalloc(reinterpret_cast<void**>(&db->d_match), K * kMaxPoints * sizeof(int32_t)));
-    HIP_TRY(db, hipMalloc(reinterpret_cast<void**>(&db->d_counts), K * sizeof(int32_t)));
-    HIP_TRY(db, hipMalloc(reinterpret_cast<void**>(&db->d_prm), sizeof(Params)));
-    HIP_TRY(db, hipMalloc(reinterpret_cast<void**>(&db->d_result), sizeof(visfs_place_result)));
-    HIP_TRY(db, hipHostMalloc(reinterpret_cast<void**>(&db->h_io), kIoBytes, hipHostMallocDefault));
-    HIP_TRY(db, hipEventCreateWithFlags(&db->up_done, hipEventDisableTiming));
+    RC_TRY(db->d_slots.alloc(db, K));
+    RC_TRY(db->d_pay.alloc(db, K));
+    RC_TRY(db->d_match.alloc(db, K * kMaxPoints));
+    RC_TRY(db->d_counts.alloc(db, K));
+    RC_TRY(db->d_prm.alloc(db, 1));
+    RC_TRY(db->d_result.alloc(db, 1));
+    RC_TRY(db->h_io.alloc(db, kIoBytes));
+    RC_TRY(db->up_done.create(db, hipEventDisableTiming));
     return VISFS_BA_OK;
 }
 
 // the pinned block is written again only when the copy out of it has finished (the kernels behind it are not waited for)
 template <class T> int pinned_free(T* o) {
     if (!o->up_pending) return VISFS_BA_OK;
-    HIP_TRY(o, hipEventSynchronize(o->up_done));
+    HIP_TRY(o, hipEventSynchronize(o->up_done.get()));
     o->up_pending = false;
     return VISFS_BA_OK;
 }
@@ -321,15 +292,15 @@ int device_query(visfs_place_db* db, const visfs_place_set* s, const Params& p, 
     HIP_TRY(db, hipSetDevice(db->dev));
     const int rc = pinned_free(db);
     if (rc != VISFS_BA_OK) return rc;
-    std::memcpy(db->h_io, &p, sizeof p);
-    HIP_TRY(db, hipMemcpyAsync(db->d_prm, db->h_io, sizeof p, hipMemcpyHostToDevice, db->stream));
-    if (launch_query(db, s, p, db->d_prm, db->d_result) != VISFS_PLACE_QUERY_LAUNCHES) {
+    std::memcpy(db->h_io.get(), &p, sizeof p);
+    HIP_TRY(db, hipMemcpyAsync(db->d_prm.get(), db->h_io.get(), sizeof p, hipMemcpyHostToDevice, db->stream));
+    if (launch_query(db, s, p, db->d_prm.get(), db->d_result.get()) != VISFS_PLACE_QUERY_LAUNCHES) {
         HIP_TRY(db, hipGetLastError());
         return fail(db, VISFS_BA_ERR_DEVICE, "a launch of the query was refused");
     }
-    HIP_TRY(db, hipMemcpyAsync(db->h_io, db->d_result, sizeof(visfs_place_result), hipMemcpyDeviceToHost, db->stream));
+    HIP_TRY(db, hipMemcpyAsync(db->h_io.get(), db->d_result.get(), sizeof(visfs_place_result), hipMemcpyDeviceToHost, db->stream));
     HIP_TRY(db, hipStreamSynchronize(db->stream));
-    std::memcpy(R, db->h_io, sizeof(*R));
+    std::memcpy(R, db->h_io.get(), sizeof(*R));
     if (R->n_slots != p.n_slots || R->n_candidates < 0 || R->n_candidates > kMaxCandidates)
         return fail(db, VISFS_BA_ERR_DEVICE, "the ranking returned an impossible block");
     db->counts = Counts4{ 1, VISFS_PLACE_QUERY_LAUNCHES, 1, 1 };
@@ -353,10 +324,10 @@ int prepare_query(const visfs_place_db* db, const visfs_place_set* s, const visf
 }
 
 int launch_query(const visfs_place_db* db, const visfs_place_set* s, const Params& p, const Params* d_prm, visfs_place_result* d_R) {
-    hipLaunchKernelGGL(k_place_match, dim3((unsigned)std::max(p.n_slots, 1)), dim3(kMatchT), 0, db->stream, s->d_set, s->n, db->d_slots,
-                       db->d_pay, d_prm, db->d_match, db->d_counts);
+    hipLaunchKernelGGL(k_place_match, dim3((unsigned)std::max(p.n_slots, 1)), dim3(kMatchT), 0, db->stream, s->d_set.get(), s->n, db->d_slots.get(),
+                       db->d_pay.get(), d_prm, db->d_match.get(), db->d_counts.get());
     if (hipPeekAtLastError() != hipSuccess) return -1;
-    hipLaunchKernelGGL(k_place_rank, dim3(1), dim3(kRankT), 0, db->stream, s->d_set, s->n, db->d_pay, d_prm, db->d_match, db->d_counts, d_R);
+    hipLaunchKernelGGL(k_place_rank, dim3(1), dim3(kRankT), 0, db->stream, s->d_set.get(), s->n, db->d_pay.get(), d_prm, db->d_match.get(), db->d_counts.get(), d_R);
     if (hipPeekAtLastError() != hipSuccess) return -1;
     return VISFS_PLACE_QUERY_LAUNCHES;
 }
@@ -384,7 +355,7 @@ int visfs_place_set_create(visfs_flow* f, int32_t capacity, visfs_place_set** ou
         s->flow = f; s->capacity = capacity; s->device = f->device; s->dev = f->dev; s->stream = f->stream;
         if (s->device) {
             const int rc = set_alloc(s);
-            if (rc != VISFS_BA_OK) { f->err = s->err; release(s); return rc; }
+            if (rc != VISFS_BA_OK) { f->err = s->err; delete s; return rc; }
         } else {
             s->host = new SetBlock();
             std::memset(s->host, 0, sizeof(SetBlock));
@@ -394,7 +365,7 @@ int visfs_place_set_create(visfs_flow* f, int32_t capacity, visfs_place_set** ou
     });
 }
 
-void visfs_place_set_destroy(visfs_place_set* s) { if (s) release(s); }
+void visfs_place_set_destroy(visfs_place_set* s) { delete s; }
 
 const char* visfs_place_set_last_error(const visfs_place_set* s) { return s ? s->err.c_str() : "null set"; }
 
@@ -423,13 +394,13 @@ int visfs_place_describe(visfs_place_set* s, int32_t slot, int32_t image, int32_
         if (rc != VISFS_BA_OK) return rc;
         s->described = false;
         const size_t bytes = sizeof(float) * 2 * (size_t)std::max(n, 1);
-        if (n > 0) std::memcpy(s->h_xy, xy, sizeof(float) * 2 * (size_t)n);
+        if (n > 0) std::memcpy(s->h_xy.get(), xy, sizeof(float) * 2 * (size_t)n);
         else s->h_xy[0] = s->h_xy[1] = 0.0f;
-        HIP_TRY(s, hipMemcpyAsync(&s->d_set->xy[0][0], s->h_xy, bytes, hipMemcpyHostToDevice, s->stream));
-        HIP_TRY(s, hipEventRecord(s->up_done, s->stream));
+        HIP_TRY(s, hipMemcpyAsync(&s->d_set->xy[0][0], s->h_xy.get(), bytes, hipMemcpyHostToDevice, s->stream));
+        HIP_TRY(s, hipEventRecord(s->up_done.get(), s->stream));
         s->up_pending = true;
-        hipLaunchKernelGGL(k_place_describe, dim3((unsigned)std::max(n, 1)), dim3(64), 0, s->stream, f->dpx[sl][image], f->w, f->h, s->d_table,
-                           s->d_set, n);
+        hipLaunchKernelGGL(k_place_describe, dim3((unsigned)std::max(n, 1)), dim3(64), 0, s->stream, f->dpx[sl][image], f->w, f->h, s->d_table.get(),
+                           s->d_set.get(), n);
         HIP_TRY(s, hipGetLastError());
         s->n = n; s->described = true; s->counts = Counts4{ 1, 1, 0, 0 };
         return (int)VISFS_BA_OK;
@@ -480,7 +451,7 @@ int visfs_place_set_upload(visfs_place_set* s, int32_t n, const float* xy, const
         }
         if (s->device) {
             HIP_TRY(s, hipSetDevice(s->dev));
-            HIP_TRY(s, hipMemcpyAsync(s->d_set, B, sizeof(SetBlock), hipMemcpyHostToDevice, s->stream));
+            HIP_TRY(s, hipMemcpyAsync(s->d_set.get(), B, sizeof(SetBlock), hipMemcpyHostToDevice, s->stream));
             HIP_TRY(s, hipStreamSynchronize(s->stream));
         } else {
             std::memcpy(s->host, B, sizeof(SetBlock));
@@ -502,7 +473,7 @@ int visfs_place_db_create(visfs_ba_handle* h, int32_t max_keyframes, visfs_place
         if (h) {
             db->device = true; db->dev = visfs_internal_device(h); db->stream = visfs_internal_stream(h);
             const int r = db_alloc(db);
-            if (r != VISFS_BA_OK) { why = db->err; release(db); return r; }
+            if (r != VISFS_BA_OK) { why = db->err; delete db; return r; }
         } else {
             db->hslots.resize((size_t)max_keyframes);
             db->hpay.resize((size_t)max_keyframes);
@@ -514,7 +485,7 @@ int visfs_place_db_create(visfs_ba_handle* h, int32_t max_keyframes, visfs_place
     return rc;
 }
 
-void visfs_place_db_destroy(visfs_place_db* db) { if (db) release(db); }
+void visfs_place_db_destroy(visfs_place_db* db) { delete db; }
 
 const char* visfs_place_db_last_error(const visfs_place_db* db) { return db ? db->err.c_str() : "null store"; }
 
@@ -526,7 +497,7 @@ int visfs_place_db_add(visfs_place_db* db, const visfs_place_set* s, const int32
         if (s->n > 0 && (!ids || !xyz)) return fail(db, VISFS_BA_ERR_BAD_ARGUMENT, "ids and xyz are needed for a set that is not empty");
         if (db->size >= db->max_keyframes) return fail(db, VISFS_BA_ERR_UNSUPPORTED, "the store is full");
         const int slot = db->size;
-        Payload* P = db->device ? reinterpret_cast<Payload*>(db->h_io) : &db->hpay[(size_t)slot];
+        Payload* P = db->device ? reinterpret_cast<Payload*>(db->h_io.get()) : &db->hpay[(size_t)slot];
         if (db->device) {
             HIP_TRY(db, hipSetDevice(db->dev));
             rc = pinned_free(db);
@@ -539,9 +510,9 @@ int visfs_place_db_add(visfs_place_db* db, const visfs_place_set* s, const int32
         }
         P->key = key; P->n = s->n;
         if (db->device) {
-            HIP_TRY(db, hipMemcpyAsync(&db->d_slots[slot], s->d_set, sizeof(SlotBlock), hipMemcpyDeviceToDevice, db->stream));
+            HIP_TRY(db, hipMemcpyAsync(&db->d_slots[slot], s->d_set.get(), sizeof(SlotBlock), hipMemcpyDeviceToDevice, db->stream));
             HIP_TRY(db, hipMemcpyAsync(&db->d_pay[slot], P, sizeof(Payload), hipMemcpyHostToDevice, db->stream));
-            HIP_TRY(db, hipEventRecord(db->up_done, db->stream));
+            HIP_TRY(db, hipEventRecord(db->up_done.get(), db->stream));
             db->up_pending = true;
         } else {
             std::memcpy(&db->hslots[(size_t)slot], s->host, sizeof(SlotBlock));

@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 
+#include "ba_host.hpp"
 #include "ba_place.hpp"
 #include "../../include/visfs_place.h"
 
@@ -58,11 +59,19 @@ struct visfs_place_set {
     bool described = false;
     place::Counts4 counts;
     place::SetBlock* host = nullptr;       // the twin's set
-    place::SetBlock* d_set = nullptr;
-    place::Table* d_table = nullptr;
-    float* h_xy = nullptr;                 // pinned: a call's key-points
-    hipEvent_t up_done = nullptr;          // behind the copy out of h_xy
+    ::host::DeviceBuf<place::SetBlock> d_set;
+    ::host::DeviceBuf<place::Table> d_table;
+    ::host::PinnedBuf<float> h_xy;           // pinned: a call's key-points
+    ::host::Event up_done;                   // behind the copy out of h_xy
     bool up_pending = false;
+
+    ~visfs_place_set() {                   // before the members free what they own
+        if (device) {
+            (void)hipSetDevice(dev);
+            if (stream) (void)hipStreamSynchronize(stream);
+        }
+        delete host;
+    }
 };
 
 struct visfs_place_db {
@@ -74,15 +83,21 @@ struct visfs_place_db {
     place::Counts4 counts;
     std::vector<place::SlotBlock> hslots;  // the twin's store
     std::vector<place::Payload> hpay;
-    place::SlotBlock* d_slots = nullptr;
-    place::Payload* d_pay = nullptr;
-    int32_t* d_match = nullptr;            // [max_keyframes][512]
-    int32_t* d_counts = nullptr;
-    place::Params* d_prm = nullptr;
-    visfs_place_result* d_result = nullptr;
-    char* h_io = nullptr;                  // pinned: a Payload going up, Params going up, the result coming down
-    hipEvent_t up_done = nullptr;          // behind the copy of a Payload out of h_io
+    ::host::DeviceBuf<place::SlotBlock> d_slots;
+    ::host::DeviceBuf<place::Payload> d_pay;
+    ::host::DeviceBuf<int32_t> d_match;      // [max_keyframes][512]
+    ::host::DeviceBuf<int32_t> d_counts;
+    ::host::DeviceBuf<place::Params> d_prm;
+    ::host::DeviceBuf<visfs_place_result> d_result;
+    ::host::PinnedBuf<char> h_io;            // pinned: a Payload going up, Params going up, the result coming down
+    ::host::Event up_done;                   // behind the copy of a Payload out of h_io
     bool up_pending = false;
+
+    ~visfs_place_db() {                    // before the members free what they own
+        if (!device) return;
+        (void)hipSetDevice(dev);
+        if (stream) (void)hipStreamSynchronize(stream);
+    }
 };
 
 namespace place {

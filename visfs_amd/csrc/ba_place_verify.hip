@@ -217,13 +217,23 @@ struct visfs_place_verifier {
     // device
     int dev = 0;
     hipStream_t stream = nullptr;
-    UpBlock* h_up = nullptr;               // pinned
-    UpBlock* d_up = nullptr;
-    Arena* h_arena = nullptr;              // pinned
-    char* d_state = nullptr;               // the arena, the row lists, the keys, the hypotheses and the passes of both stages
+    PinnedBuf<UpBlock> h_up;               // pinned
+    DeviceBuf<UpBlock> d_up;
+    PinnedBuf<Arena> h_arena;              // pinned
+    DeviceBuf<char> d_state;               // the arena, the row lists, the keys, the hypotheses and the passes of both stages
     Bufs B{};
     pnp::PnpRec rec1[kC] = {};             // device addresses; K is the call's
     pnp::RefineFromRec rec2[kC] = {};
+
+    ~visfs_place_verifier() {              // before the members free what they own
+        for (int c = 0; c < kC; ++c) {
+            if (solver1[c]) visfs_pnp_destroy(solver1[c]);
+            if (solver2[c]) visfs_pnp_destroy(solver2[c]);
+        }
+        if (!device) return;
+        (void)hipSetDevice(dev);
+        if (stream) (void)hipStreamSynchronize(stream);
+    }
 };
 
 namespace {
@@ -267,32 +277,16 @@ size_t carve(visfs_place_verifier* v, char* base) {
     return k.off;
 }
 
-void release(visfs_place_verifier* v) {
-    for (int c = 0; c < kC; ++c) {
-        if (v->solver1[c]) visfs_pnp_destroy(v->solver1[c]);
-        if (v->solver2[c]) visfs_pnp_destroy(v->solver2[c]);
-    }
-    if (v->device) {
-        (void)hipSetDevice(v->dev);
-        if (v->stream) (void)hipStreamSynchronize(v->stream);
-        if (v->d_state) (void)hipFree(v->d_state);
-        if (v->d_up) (void)hipFree(v->d_up);
-        if (v->h_up) (void)hipHostFree(v->h_up);
-        if (v->h_arena) (void)hipHostFree(v->h_arena);
-    }
-    delete v;
-}
-
 int device_init(visfs_place_verifier* v) {
     HIP_TRY(v, hipSetDevice(v->dev));
     const size_t bytes = carve(v, nullptr);
-    HIP_TRY(v, hipMalloc(reinterpret_cast<void**>(&v->d_state), bytes));
-    HIP_TRY(v, hipMalloc(reinterpret_cast<void**>(&v->d_up), sizeof(UpBlock)));
-    HIP_TRY(v, hipHostMalloc(reinterpret_cast<void**>(&v->h_up), sizeof(UpBlock), hipHostMallocDefault));
-    HIP_TRY(v, hipHostMalloc(reinterpret_cast<void**>(&v->h_arena), sizeof(Arena), hipHostMallocDefault));
-    HIP_TRY(v, hipMemsetAsync(v->d_state, 0, bytes, v->stream));
+    RC_TRY(v->d_state.alloc(v, bytes));
+    RC_TRY(v->d_up.alloc(v, 1));
+    RC_TRY(v->h_up.alloc(v, 1));
+    RC_TRY(v->h_arena.alloc(v, 1));
+    HIP_TRY(v, hipMemsetAsync(v->d_state.get(), 0, bytes, v->stream));
     HIP_TRY(v, hipStreamSynchronize(v->stream));
-    (void)carve(v, v->d_state);
+    (void)carve(v, v->d_state.get());
     return VISFS_BA_OK;
 }
 
@@ -409,7 +403,7 @@ int device_call(visfs_place_verifier* v, const visfs_place_set* s, const place::
     const pnp::Cam K{ vp.camera.fx, vp.camera.fy, vp.camera.cx, vp.camera.cy };
     const int min_inliers = v->shape.min_inliers;
     // (every call ends in a wait behind its download, so the pinned blocks are free)
-    UpBlock& U = *v->h_up;
+    UpBlock& U = *v->h_up.get();
     U.q = q; U.pad = 0;
     U.p = DevParams{ vp.guided ? 1 : 0, vp.guided_max_distance, min_inliers, 0, radius2(vp.guided_radius), K };
     for (int c = 0; c < kC; ++c) {
@@ -417,7 +411,7 @@ int device_call(visfs_place_verifier* v, const visfs_place_set* s, const place::
         U.rec2[c] = v->rec2[c]; U.rec2[c].K = K;
     }
     place::Counts4 n;
-    HIP_TRY(v, hipMemcpyAsync(v->d_up, v->h_up, sizeof(UpBlock), hipMemcpyHostToDevice, v->stream));
+    HIP_TRY(v, hipMemcpyAsync(v->d_up.get(), v->h_up.get(), sizeof(UpBlock), hipMemcpyHostToDevice, v->stream));
     ++n.uploads;
     const int launched = place::launch_query(db, s, q, &v->d_up->q, &v->B.arena->place);
     if (launched < 0) { HIP_TRY(v, hipGetLastError()); return fail(v, VISFS_BA_ERR_DEVICE, "a launch of the query was refused"); }
@@ -427,16 +421,16 @@ int device_call(visfs_place_verifier* v, const visfs_place_set* s, const place::
     ++n.launches;
     flow::GroupCounts g{};
     if (pnp::group_pnp(v->stream, kC, v->d_up->rec1, v->shape, &g) != VISFS_BA_OK) return fail(v, VISFS_BA_ERR_DEVICE, "a launch of stage 1 was refused");
-    hipLaunchKernelGGL(k_place_guided, dim3(1, 1, kC), dim3(kT), 0, v->stream, v->B, &v->d_up->p, s->d_set, s->n, db->d_slots, db->d_pay);
+    hipLaunchKernelGGL(k_place_guided, dim3(1, 1, kC), dim3(kT), 0, v->stream, v->B, &v->d_up->p, s->d_set.get(), s->n, db->d_slots.get(), db->d_pay.get());
     HIP_TRY(v, hipGetLastError());
     ++n.launches;
     if (pnp::group_refine_from(v->stream, kC, v->d_up->rec2, v->shape, &g) != VISFS_BA_OK) return fail(v, VISFS_BA_ERR_DEVICE, "the launch of stage 2 was refused");
     n.launches += g.launches;
-    HIP_TRY(v, hipMemcpyAsync(v->h_arena, v->B.arena, sizeof(Arena), hipMemcpyDeviceToHost, v->stream));
+    HIP_TRY(v, hipMemcpyAsync(v->h_arena.get(), v->B.arena, sizeof(Arena), hipMemcpyDeviceToHost, v->stream));
     ++n.downloads;
     HIP_TRY(v, hipStreamSynchronize(v->stream));
     ++n.waits;
-    const Arena& A = *v->h_arena;
+    const Arena& A = *v->h_arena.get();
     if (A.place.n_slots != q.n_slots || A.place.n_candidates < 0 || A.place.n_candidates > kC)
         return fail(v, VISFS_BA_ERR_DEVICE, "the ranking returned an impossible block");
     std::memcpy(R, &A.place, sizeof(*R));
@@ -526,13 +520,13 @@ int visfs_place_verifier_create(visfs_place_db* db, visfs_place_verifier** out) 
             }
             if (rc != VISFS_BA_OK) v->err = "a host solver could not be made";
         }
-        if (rc != VISFS_BA_OK) { db->err = v->err; release(v); return rc; }
+        if (rc != VISFS_BA_OK) { db->err = v->err; delete v; return rc; }
         *out = v;
         return (int)VISFS_BA_OK;
     });
 }
 
-void visfs_place_verifier_destroy(visfs_place_verifier* v) { if (v) release(v); }
+void visfs_place_verifier_destroy(visfs_place_verifier* v) { delete v; }
 
 const char* visfs_place_verifier_last_error(const visfs_place_verifier* v) { return v ? v->err.c_str() : "null verifier"; }
 

@@ -306,14 +306,20 @@ struct visfs_pnp {
     visfs_ba_handle* ba = nullptr;
     int dev = 0;
     hipStream_t stream = nullptr;
-    char* h_in = nullptr;      // pinned: header + rows
-    char* h_out = nullptr;     // pinned: Result + inlier list
-    char* d_in = nullptr;
-    char* d_out = nullptr;
-    char* d_state = nullptr;   // hypotheses and passes
+    PinnedBuf<char> h_in;      // pinned: header + rows
+    PinnedBuf<char> h_out;     // pinned: Result + inlier list
+    DeviceBuf<char> d_in;
+    DeviceBuf<char> d_out;
+    DeviceBuf<char> d_state;   // hypotheses and passes
     int32_t *d_samples = nullptr, *d_vc = nullptr, *d_pass_cnt = nullptr, *d_pass_lists = nullptr;
     double *d_models = nullptr, *d_pass_tq = nullptr;
     float* d_pass_thr = nullptr;
+
+    ~visfs_pnp() {                     // before the members free what they own
+        if (!device) return;
+        (void)hipSetDevice(dev);
+        if (stream) (void)hipStreamSynchronize(stream);
+    }
 };
 
 namespace {
@@ -323,35 +329,23 @@ int device_init(visfs_pnp* p) {
     const size_t cap = (size_t)p->cap;
     const size_t in_bytes = kHeaderBytes + up256(sizeof(Row) * cap), out_bytes = kHeaderBytes + up256(4 * cap);
     static_assert(sizeof(Result) <= kHeaderBytes, "the result block is one header");
-    HIP_TRY(p, hipHostMalloc(reinterpret_cast<void**>(&p->h_in), in_bytes, hipHostMallocDefault));
-    HIP_TRY(p, hipHostMalloc(reinterpret_cast<void**>(&p->h_out), out_bytes, hipHostMallocDefault));
-    HIP_TRY(p, hipMalloc(reinterpret_cast<void**>(&p->d_in), in_bytes));
-    HIP_TRY(p, hipMalloc(reinterpret_cast<void**>(&p->d_out), out_bytes));
+    RC_TRY(p->h_in.alloc(p, in_bytes));
+    RC_TRY(p->h_out.alloc(p, out_bytes));
+    RC_TRY(p->d_in.alloc(p, in_bytes));
+    RC_TRY(p->d_out.alloc(p, out_bytes));
     const size_t H = kMaxHypotheses, R = kMaxRefine;
     const size_t o_models = 0, o_ptq = o_models + up256(96 * H), o_samples = o_ptq + up256(56 * R), o_vc = o_samples + up256(16 * H),
                  o_pthr = o_vc + up256(8 * H), o_pcnt = o_pthr + up256(4 * R), o_plists = o_pcnt + up256(4 * R),
                  bytes = o_plists + up256(4 * R * cap);
-    HIP_TRY(p, hipMalloc(reinterpret_cast<void**>(&p->d_state), bytes));
-    p->d_models = reinterpret_cast<double*>(p->d_state + o_models);
-    p->d_pass_tq = reinterpret_cast<double*>(p->d_state + o_ptq);
-    p->d_samples = reinterpret_cast<int32_t*>(p->d_state + o_samples);
-    p->d_vc = reinterpret_cast<int32_t*>(p->d_state + o_vc);
-    p->d_pass_thr = reinterpret_cast<float*>(p->d_state + o_pthr);
-    p->d_pass_cnt = reinterpret_cast<int32_t*>(p->d_state + o_pcnt);
-    p->d_pass_lists = reinterpret_cast<int32_t*>(p->d_state + o_plists);
+    RC_TRY(p->d_state.alloc(p, bytes));
+    p->d_models = reinterpret_cast<double*>(p->d_state.get() + o_models);
+    p->d_pass_tq = reinterpret_cast<double*>(p->d_state.get() + o_ptq);
+    p->d_samples = reinterpret_cast<int32_t*>(p->d_state.get() + o_samples);
+    p->d_vc = reinterpret_cast<int32_t*>(p->d_state.get() + o_vc);
+    p->d_pass_thr = reinterpret_cast<float*>(p->d_state.get() + o_pthr);
+    p->d_pass_cnt = reinterpret_cast<int32_t*>(p->d_state.get() + o_pcnt);
+    p->d_pass_lists = reinterpret_cast<int32_t*>(p->d_state.get() + o_plists);
     return VISFS_BA_OK;
-}
-
-void release(visfs_pnp* p) {
-    if (!p->device) return;
-    (void)hipSetDevice(p->dev);
-    if (p->stream) (void)hipStreamSynchronize(p->stream);
-    if (p->d_in) (void)hipFree(p->d_in);
-    if (p->d_out) (void)hipFree(p->d_out);
-    if (p->d_state) (void)hipFree(p->d_state);
-    if (p->h_in) (void)hipHostFree(p->h_in);
-    if (p->h_out) (void)hipHostFree(p->h_out);
-    p->d_in = p->d_out = p->d_state = p->h_in = p->h_out = nullptr;
 }
 
 // The host twin's reductions: the same leaves and the same tree as DevicePolicy, in sequence.
@@ -441,26 +435,26 @@ int host_solve(visfs_pnp* p, const visfs_pnp_params& prm, const Cam& K, int32_t 
 int device_solve(visfs_pnp* p, const visfs_pnp_params& prm, const Cam& K, int32_t m, int min_inliers, std::vector<int32_t>& inliers) {
     HIP_TRY(p, hipSetDevice(p->dev));
     // (the rows were written into h_in behind the header by the caller, after the stream had drained)
-    std::memset(p->h_in, 0, kHeaderBytes);
-    HIP_TRY(p, hipMemcpyAsync(p->d_in, p->h_in, kHeaderBytes + sizeof(Row) * (size_t)m, hipMemcpyHostToDevice, p->stream));
+    std::memset(p->h_in.get(), 0, kHeaderBytes);
+    HIP_TRY(p, hipMemcpyAsync(p->d_in.get(), p->h_in.get(), kHeaderBytes + sizeof(Row) * (size_t)m, hipMemcpyHostToDevice, p->stream));
     RansacArgs A;
-    A.rows = reinterpret_cast<const Row*>(p->d_in + kHeaderBytes); A.m = m; A.iterations = prm.iterations; A.seed = prm.seed; A.K = K;
+    A.rows = reinterpret_cast<const Row*>(p->d_in.get() + kHeaderBytes); A.m = m; A.iterations = prm.iterations; A.seed = prm.seed; A.K = K;
     A.thr = prm.reproj_error; A.samples = p->d_samples; A.vc = p->d_vc; A.models = p->d_models;
-    A.key = reinterpret_cast<unsigned long long*>(p->d_in);
+    A.key = reinterpret_cast<unsigned long long*>(p->d_in.get());
     hipLaunchKernelGGL(k_pnp_ransac, dim3((unsigned)((prm.iterations + PN_T / 64 - 1) / (PN_T / 64))), dim3(PN_T), 0, p->stream, A);
     HIP_TRY(p, hipGetLastError());
     RefineArgs B;
     B.rows = A.rows; B.m = m; B.cap = p->cap; B.K = K; B.min_inliers = min_inliers; B.refine_iterations = prm.refine_iterations;
     B.thr0 = prm.reproj_error; B.sigma = prm.refine_sigma; B.key = A.key; B.models = p->d_models;
-    B.res = reinterpret_cast<Result*>(p->d_out); B.inliers = reinterpret_cast<int32_t*>(p->d_out + kHeaderBytes);
+    B.res = reinterpret_cast<Result*>(p->d_out.get()); B.inliers = reinterpret_cast<int32_t*>(p->d_out.get() + kHeaderBytes);
     B.pass_tq = p->d_pass_tq; B.pass_thr = p->d_pass_thr; B.pass_cnt = p->d_pass_cnt; B.pass_lists = p->d_pass_lists;
     hipLaunchKernelGGL(k_pnp_refine, dim3(1), dim3(PN_T), 0, p->stream, B);
     HIP_TRY(p, hipGetLastError());
-    HIP_TRY(p, hipMemcpyAsync(p->h_out, p->d_out, kHeaderBytes + 4 * (size_t)m, hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(p, hipMemcpyAsync(p->h_out.get(), p->d_out.get(), kHeaderBytes + 4 * (size_t)m, hipMemcpyDeviceToHost, p->stream));
     HIP_TRY(p, hipStreamSynchronize(p->stream));
-    std::memcpy(&p->res, p->h_out, sizeof(Result));
+    std::memcpy(&p->res, p->h_out.get(), sizeof(Result));
     if (p->res.n_inliers < 0 || p->res.n_inliers > m) return fail(p, VISFS_BA_ERR_DEVICE, "the device returned an impossible inlier count");
-    const int32_t* li = reinterpret_cast<const int32_t*>(p->h_out + kHeaderBytes);
+    const int32_t* li = reinterpret_cast<const int32_t*>(p->h_out.get() + kHeaderBytes);
     inliers.assign(li, li + p->res.n_inliers);
     return VISFS_BA_OK;
 }
@@ -603,7 +597,7 @@ int visfs_pnp_create(visfs_ba_handle* h, int32_t capacity_points, visfs_pnp** ou
         p->cap = capacity_points;
         p->device = true; p->ba = h; p->dev = visfs_internal_device(h); p->stream = visfs_internal_stream(h);
         const int rc = device_init(p);
-        if (rc != VISFS_BA_OK) { visfs_internal_set_error(h, p->err.c_str()); release(p); delete p; return rc; }
+        if (rc != VISFS_BA_OK) { visfs_internal_set_error(h, p->err.c_str()); delete p; return rc; }
         *out = p;
         return (int)VISFS_BA_OK;
     });
@@ -611,7 +605,6 @@ int visfs_pnp_create(visfs_ba_handle* h, int32_t capacity_points, visfs_pnp** ou
 
 void visfs_pnp_destroy(visfs_pnp* p) {
     if (!p) return;
-    release(p);
     delete p;
 }
 
@@ -652,7 +645,7 @@ int visfs_pnp_solve(visfs_pnp* p, const visfs_pnp_params* params, const visfs_pn
         std::vector<int32_t> inliers;
         int rc2;
         if (p->device) {
-            std::memcpy(p->h_in + kHeaderBytes, p->rows.data(), sizeof(Row) * (size_t)m);
+            std::memcpy(p->h_in.get() + kHeaderBytes, p->rows.data(), sizeof(Row) * (size_t)m);
             rc2 = device_solve(p, *params, K, m, min_inliers, inliers);
         } else {
             rc2 = host_solve(p, *params, K, m, min_inliers, inliers);

@@ -35,16 +35,6 @@ __global__ __launch_bounds__(kLanes) void k_pose_graph(View v, Prm P) {
 
 namespace {
 
-void release(visfs_pose_graph* pg) {
-    cov_release(pg->cov);
-    pg->cov = nullptr;
-    if (pg->h_up) (void)hipHostFree(pg->h_up);
-    if (pg->d_up) (void)hipFree(pg->d_up);
-    if (pg->d_work) (void)hipFree(pg->d_work);
-    if (pg->h_out) (void)hipHostFree(pg->h_out);
-    pg->h_up = pg->d_up = pg->h_out = nullptr; pg->d_work = nullptr;
-}
-
 // One run of `mode` on the plan: the record, the poses and chi2 land at `out` (out_doubles of them, host memory).
 int run_plan(visfs_pose_graph* pg, const Plan& pl, const Prm& P, const double* hook_r, const double** out) {
     View v;
@@ -60,16 +50,16 @@ int run_plan(visfs_pose_graph* pg, const Plan& pl, const Prm& P, const double* h
         return VISFS_BA_OK;
     }
     HIP_TRY(pg, hipSetDevice(pg->dev));
-    const size_t bytes = pack(pl, hook_r, pg->h_up, pg->d_up, v);
-    double* d_out = carve(v, pg->d_work);
+    const size_t bytes = pack(pl, hook_r, pg->h_up.get(), pg->d_up.get(), v);
+    double* d_out = carve(v, pg->d_work.get());
     const size_t out_bytes = out_doubles(pl.N, pl.E) * sizeof(double);
-    HIP_TRY(pg, hipMemcpyAsync(pg->d_up, pg->h_up, bytes, hipMemcpyHostToDevice, pg->stream));
+    HIP_TRY(pg, hipMemcpyAsync(pg->d_up.get(), pg->h_up.get(), bytes, hipMemcpyHostToDevice, pg->stream));
     hipLaunchKernelGGL(k_pose_graph, dim3(1), dim3(kLanes), 0, pg->stream, v, P);
     HIP_TRY(pg, hipGetLastError());
-    HIP_TRY(pg, hipMemcpyAsync(pg->h_out, d_out, out_bytes, hipMemcpyDeviceToHost, pg->stream));
+    HIP_TRY(pg, hipMemcpyAsync(pg->h_out.get(), d_out, out_bytes, hipMemcpyDeviceToHost, pg->stream));
     HIP_TRY(pg, hipStreamSynchronize(pg->stream));
     pg->view = v;
-    *out = reinterpret_cast<const double*>(pg->h_out);
+    *out = reinterpret_cast<const double*>(pg->h_out.get());
     return VISFS_BA_OK;
 }
 
@@ -121,21 +111,19 @@ int visfs_pose_graph_create(visfs_ba_handle* h, int32_t max_vertices, int32_t ma
         pg->device = true; pg->dev = visfs_internal_device(h); pg->stream = visfs_internal_stream(h);
         const int rc = [&]() -> int {
             HIP_TRY(pg, hipSetDevice(pg->dev));
-            HIP_TRY(pg, hipHostMalloc(reinterpret_cast<void**>(&pg->h_up), pg->up_bytes, hipHostMallocDefault));
-            HIP_TRY(pg, hipMalloc(reinterpret_cast<void**>(&pg->d_up), pg->up_bytes));
-            HIP_TRY(pg, hipMalloc(reinterpret_cast<void**>(&pg->d_work), pg->work_doubles * sizeof(double)));
-            HIP_TRY(pg, hipHostMalloc(reinterpret_cast<void**>(&pg->h_out), out_doubles(max_vertices, max_edges) * sizeof(double), hipHostMallocDefault));
+            RC_TRY(pg->h_up.alloc(pg, pg->up_bytes));
+            RC_TRY(pg->d_up.alloc(pg, pg->up_bytes));
+            RC_TRY(pg->d_work.alloc(pg, pg->work_doubles));
+            RC_TRY(pg->h_out.alloc(pg, out_doubles(max_vertices, max_edges) * sizeof(double)));
             return (int)VISFS_BA_OK;
         }();
-        if (rc != VISFS_BA_OK) { visfs_internal_set_error(h, pg->err.c_str()); release(pg); delete pg; return rc; }
+        if (rc != VISFS_BA_OK) { visfs_internal_set_error(h, pg->err.c_str()); delete pg; return rc; }
         *out = pg;
         return (int)VISFS_BA_OK;
     });
 }
 
 void visfs_pose_graph_destroy(visfs_pose_graph* pg) {
-    if (!pg) return;
-    release(pg);
     delete pg;
 }
 

@@ -31,11 +31,11 @@ constexpr int kGatherLanes = 64;
 
 struct CovObject {
     // device
-    size_t up_bytes = 0, fixed_doubles = 0, arena_doubles = 0;
-    char* h_up = nullptr; char* d_up = nullptr;
-    double* d_work = nullptr;                         // the work arrays of the View, then head, flags, joint, relative
-    double* d_arena = nullptr;
-    char* h_out = nullptr;
+    size_t up_bytes = 0, fixed_doubles = 0;
+    PinnedBuf<char> h_up; DeviceBuf<char> d_up;
+    DeviceBuf<double> d_work;                         // the work arrays of the View, then head, flags, joint, relative
+    DeviceBuf<double> d_arena;
+    PinnedBuf<char> h_out;
     // twin
     std::vector<char> up;
     std::vector<double> work, column, solutions;
@@ -49,12 +49,6 @@ struct CovObject {
 };
 
 void cov_release(CovObject* c) {
-    if (!c) return;
-    if (c->h_up) (void)hipHostFree(c->h_up);
-    if (c->d_up) (void)hipFree(c->d_up);
-    if (c->d_work) (void)hipFree(c->d_work);
-    if (c->d_arena) (void)hipFree(c->d_arena);
-    if (c->h_out) (void)hipHostFree(c->h_out);
     delete c;
 }
 
@@ -138,10 +132,10 @@ int cov_reserve(visfs_pose_graph* pg, int32_t columns, int32_t n) {
             c->work.assign(fixed, 0.0);
         } else {
             HIP_TRY(pg, hipSetDevice(pg->dev));
-            HIP_TRY(pg, hipHostMalloc(reinterpret_cast<void**>(&c->h_up), c->up_bytes, hipHostMallocDefault));
-            HIP_TRY(pg, hipMalloc(reinterpret_cast<void**>(&c->d_up), c->up_bytes));
-            HIP_TRY(pg, hipMalloc(reinterpret_cast<void**>(&c->d_work), fixed * sizeof(double)));
-            HIP_TRY(pg, hipHostMalloc(reinterpret_cast<void**>(&c->h_out), cov_out_doubles(3 * kCovMaxSources, kCovMaxQueries) * sizeof(double), hipHostMallocDefault));
+            RC_TRY(c->h_up.alloc(pg, c->up_bytes));
+            RC_TRY(c->d_up.alloc(pg, c->up_bytes));
+            RC_TRY(c->d_work.alloc(pg, fixed));
+            RC_TRY(c->h_out.alloc(pg, cov_out_doubles(3 * kCovMaxSources, kCovMaxQueries) * sizeof(double)));
         }
         c->fixed_doubles = fixed;
     }
@@ -150,12 +144,10 @@ int cov_reserve(visfs_pose_graph* pg, int32_t columns, int32_t n) {
         return VISFS_BA_OK;
     }
     const size_t need = (size_t)columns * kCovColumnVectors * 3 * (size_t)n;
-    if (need > c->arena_doubles) {
+    if (need > c->d_arena.cap()) {
         HIP_TRY(pg, hipSetDevice(pg->dev));
         c->valid = false;                                                    // the stored columns go with the old arena
-        if (c->d_arena) { (void)hipFree(c->d_arena); c->d_arena = nullptr; c->arena_doubles = 0; }
-        HIP_TRY(pg, hipMalloc(reinterpret_cast<void**>(&c->d_arena), need * sizeof(double)));
-        c->arena_doubles = need;
+        RC_TRY(c->d_arena.alloc(pg, need));
     }
     return VISFS_BA_OK;
 }
@@ -194,17 +186,17 @@ int run_cov(visfs_pose_graph* pg, const Plan& pl, const CovPlan& cp, const Prm& 
         return VISFS_BA_OK;
     }
     HIP_TRY(pg, hipSetDevice(pg->dev));
-    const size_t off = pack(pl, nullptr, c->h_up, c->d_up, v);
-    const size_t bytes = pack_cov(cp, c->h_up, c->d_up, off, q);
-    carve(v, c->d_work);
-    double* d_out = c->d_work + work_capacity(pg->maxN, pg->maxE);
+    const size_t off = pack(pl, nullptr, c->h_up.get(), c->d_up.get(), v);
+    const size_t bytes = pack_cov(cp, c->h_up.get(), c->d_up.get(), off, q);
+    carve(v, c->d_work.get());
+    double* d_out = c->d_work.get() + work_capacity(pg->maxN, pg->maxE);
     carve_cov(q, d_out);
-    q.arena = c->d_arena;
+    q.arena = c->d_arena.get();
     q.sol_stride = kCovColumnVectors * 3 * (int64_t)pl.n;
-    q.sol = c->d_arena + kCovSolutionVector * 3 * (int64_t)pl.n;
+    q.sol = c->d_arena.get() + kCovSolutionVector * 3 * (int64_t)pl.n;
     const size_t out_bytes = cov_out_doubles(columns, cp.Q) * sizeof(double);
     int32_t launches = 0;
-    HIP_TRY(pg, hipMemcpyAsync(c->d_up, c->h_up, bytes, hipMemcpyHostToDevice, pg->stream));
+    HIP_TRY(pg, hipMemcpyAsync(c->d_up.get(), c->h_up.get(), bytes, hipMemcpyHostToDevice, pg->stream));
     hipLaunchKernelGGL(k_pose_graph_cov_setup, dim3(1), dim3(kLanes), 0, pg->stream, v, q, P.precond);
     HIP_TRY(pg, hipGetLastError());
     ++launches;
@@ -216,10 +208,10 @@ int run_cov(visfs_pose_graph* pg, const Plan& pl, const CovPlan& cp, const Prm& 
     hipLaunchKernelGGL(k_pose_graph_cov_gather, dim3((unsigned)((cp.Q + kGatherLanes - 1) / kGatherLanes)), dim3(kGatherLanes), 0, pg->stream, v, q);
     HIP_TRY(pg, hipGetLastError());
     ++launches;
-    HIP_TRY(pg, hipMemcpyAsync(c->h_out, d_out, out_bytes, hipMemcpyDeviceToHost, pg->stream));
+    HIP_TRY(pg, hipMemcpyAsync(c->h_out.get(), d_out, out_bytes, hipMemcpyDeviceToHost, pg->stream));
     HIP_TRY(pg, hipStreamSynchronize(pg->stream));
     c->counts = { launches, 2, 1 };
-    *out = reinterpret_cast<const double*>(c->h_out);
+    *out = reinterpret_cast<const double*>(c->h_out.get());
     return VISFS_BA_OK;
 }
 

@@ -98,14 +98,18 @@ struct visfs_pose_graph {
     int32_t maxN = 0, maxE = 0;
     std::string err;
     size_t up_bytes = 0, work_doubles = 0;
-    char* h_up = nullptr; char* d_up = nullptr;       // the upload: pinned, device
-    double* d_work = nullptr; char* h_out = nullptr;  // the work (its tail is the download), the pinned download
+    host::PinnedBuf<char> h_up; host::DeviceBuf<char> d_up;          // the upload: pinned, device
+    host::DeviceBuf<double> d_work; host::PinnedBuf<char> h_out;     // the work (its tail is the download), the pinned download
     std::vector<char> up;                             // twin
     std::vector<double> work;
     posegraph::View view;                             // of the last run
     int32_t trials = 0;
     host::Counts counts;
     posegraph::CovObject* cov = nullptr;              // made at the first covariance call
+
+    visfs_pose_graph() = default;
+    visfs_pose_graph(const visfs_pose_graph&) = delete;
+    ~visfs_pose_graph() { posegraph::cov_release(cov); }
 };
 
 namespace posegraph {

@@ -134,26 +134,17 @@ struct State {
     std::vector<int32_t> sums;
     std::vector<double> scores;
     // device: one upload buffer (points, rotation table, weight table) with its pinned source, the candidates, the slots, the record
-    char* h_up = nullptr; char* d_up = nullptr; size_t up_cap = 0;
-    int32_t* d_sums = nullptr; size_t sums_cap = 0; double* d_scores = nullptr; size_t scores_cap = 0;
-    Slot* d_slots = nullptr; size_t slot_cap = 0;
-    Record* d_rec = nullptr; Record* h_rec = nullptr;
-    int32_t* d_cells = nullptr; size_t cells_cap = 0;
-    const double* d_pts() const { return reinterpret_cast<const double*>(d_up); }
+    Staged<char> up;
+    DeviceBuf<int32_t> d_sums; DeviceBuf<double> d_scores;
+    DeviceBuf<Slot> d_slots;
+    DeviceBuf<Record> d_rec; PinnedBuf<Record> h_rec;
+    DeviceBuf<int32_t> d_cells;
+    const double* d_pts() const { return reinterpret_cast<const double*>(up.d.get()); }
     const double* d_rot() const { return d_pts() + 2 * (size_t)plan.n; }
 };
 
 void state_destroy(void* v) {
-    State* st = static_cast<State*>(v);
-    if (st->h_up) (void)hipHostFree(st->h_up);
-    if (st->d_up) (void)hipFree(st->d_up);
-    if (st->d_sums) (void)hipFree(st->d_sums);
-    if (st->d_scores) (void)hipFree(st->d_scores);
-    if (st->d_slots) (void)hipFree(st->d_slots);
-    if (st->d_rec) (void)hipFree(st->d_rec);
-    if (st->h_rec) (void)hipHostFree(st->h_rec);
-    if (st->d_cells) (void)hipFree(st->d_cells);
-    delete st;
+    delete static_cast<State*>(v);
 }
 
 State* state_of(visfs_submaps* s) {
@@ -172,48 +163,42 @@ void tiling(int32_t Lsq, int32_t& tc, int32_t& slices, int32_t& tiles) {
 int device_match(visfs_submaps* s, State* st, const submap::ScanAccess& acc, Plan& P, visfs_scan_match_result* out) {
     const size_t npts = 2 * (size_t)P.n, nrot = 2 * (size_t)P.S, nw = P.weight.size();
     const size_t bytes = (npts + nrot + nw) * sizeof(double);
-    if (st->up_cap < bytes) {
-        if (st->h_up) HIP_TRY(s, hipHostFree(st->h_up));
-        if (st->d_up) HIP_TRY(s, hipFree(st->d_up));
-        st->h_up = st->d_up = nullptr; st->up_cap = 0; st->have = false;
-        const size_t cap = bytes + bytes / 2;
-        HIP_TRY(s, hipHostMalloc(reinterpret_cast<void**>(&st->h_up), cap, hipHostMallocDefault));
-        HIP_TRY(s, hipMalloc(reinterpret_cast<void**>(&st->d_up), cap));
-        st->up_cap = cap;
-    }
-    if (!st->d_rec) {
-        HIP_TRY(s, hipMalloc(reinterpret_cast<void**>(&st->d_rec), sizeof(Record)));
-        HIP_TRY(s, hipHostMalloc(reinterpret_cast<void**>(&st->h_rec), sizeof(Record), hipHostMallocDefault));
+    bool grew = false;
+    const int made = st->up.reserve(s, bytes, bytes + bytes / 2, &grew);
+    if (grew) st->have = false;                                            // what the last call left went with the old buffer
+    if (made != VISFS_BA_OK) return made;
+    if (!st->d_rec.get() || !st->h_rec.get()) {
+        RC_TRY(st->d_rec.alloc(s, 1));
+        RC_TRY(st->h_rec.alloc(s, 1));
     }
     int32_t tc, slices, tiles;
     tiling(P.Lw * P.Lw, tc, slices, tiles);
     const size_t ncand = (size_t)P.candidates(), nslots = (size_t)P.S * tiles;
-    int rc;
-    if (st->sums_cap < ncand || st->scores_cap < ncand) st->have = false;
-    if ((rc = grow(s, &st->d_sums, &st->sums_cap, ncand, ncand / 2)) != VISFS_BA_OK) return rc;
-    if ((rc = grow(s, &st->d_scores, &st->scores_cap, ncand, ncand / 2)) != VISFS_BA_OK) return rc;
-    if ((rc = grow(s, &st->d_slots, &st->slot_cap, nslots, nslots / 2)) != VISFS_BA_OK) return rc;
+    if (st->d_sums.cap() < ncand || st->d_scores.cap() < ncand) st->have = false;
+    RC_TRY(st->d_sums.grow(s, ncand, ncand / 2));
+    RC_TRY(st->d_scores.grow(s, ncand, ncand / 2));
+    RC_TRY(st->d_slots.grow(s, nslots, nslots / 2));
     st->have = false;                                                      // the buffers are about to hold this call
-    double* h = reinterpret_cast<double*>(st->h_up);
+    double* h = reinterpret_cast<double*>(st->up.h.get());
     std::memcpy(h, P.pts.data(), npts * sizeof(double));
     std::memcpy(h + npts, P.rot.data(), nrot * sizeof(double));
     std::memcpy(h + npts + nrot, P.weight.data(), nw * sizeof(double));
-    HIP_TRY(s, hipMemcpyAsync(st->d_up, st->h_up, bytes, hipMemcpyHostToDevice, acc.stream));
-    const double* d = reinterpret_cast<const double*>(st->d_up);
+    HIP_TRY(s, hipMemcpyAsync(st->up.d.get(), st->up.h.get(), bytes, hipMemcpyHostToDevice, acc.stream));
+    const double* d = reinterpret_cast<const double*>(st->up.d.get());
     ScoreArgs A{};
     A.pts = d; A.rot = d + npts; A.weight = d + npts + nrot;
     A.grid = acc.grid;
     A.gx = P.gx; A.gy = P.gy; A.res = P.L.res; A.max_x = P.L.max_x; A.max_y = P.L.max_y;
     A.n = P.n; A.na = P.na; A.nl = P.nl; A.Lw = P.Lw; A.Lsq = P.Lw * P.Lw;
     A.tc = tc; A.slices = slices; A.tiles = tiles;
-    A.sums = st->d_sums; A.scores = st->d_scores; A.slots = st->d_slots;
+    A.sums = st->d_sums.get(); A.scores = st->d_scores.get(); A.slots = st->d_slots.get();
     hipLaunchKernelGGL(k_scan_score, dim3(tiles, P.S), dim3(kThreads), 0, acc.stream, A);
     HIP_TRY(s, hipGetLastError());
-    hipLaunchKernelGGL(k_scan_best, dim3(1), dim3(kThreads), 0, acc.stream, st->d_slots, (int32_t)nslots, st->d_sums, st->d_rec);
+    hipLaunchKernelGGL(k_scan_best, dim3(1), dim3(kThreads), 0, acc.stream, st->d_slots.get(), (int32_t)nslots, st->d_sums.get(), st->d_rec.get());
     HIP_TRY(s, hipGetLastError());
-    HIP_TRY(s, hipMemcpyAsync(st->h_rec, st->d_rec, sizeof(Record), hipMemcpyDeviceToHost, acc.stream));
+    HIP_TRY(s, hipMemcpyAsync(st->h_rec.get(), st->d_rec.get(), sizeof(Record), hipMemcpyDeviceToHost, acc.stream));
     HIP_TRY(s, hipStreamSynchronize(acc.stream));
-    const Record r = *st->h_rec;
+    const Record r = *st->h_rec.get();
     if (r.index < 0 || (int64_t)r.index >= P.candidates()) return visfs_internal_scan_fail(s, VISFS_BA_ERR_DEVICE, "the reduction returned no candidate");
     fill_result(P, r.index, r.score, r.sum, *out);
     st->plan = std::move(P);
@@ -317,14 +302,14 @@ int visfs_scan_match_download(visfs_submaps* s, int64_t cap, int32_t* sums, doub
         submap::ScanAccess acc;
         int rc = visfs_internal_scan_access(s, -1, &acc);                  // the device and the stream
         if (rc != VISFS_BA_OK) return rc;
-        if (sums) HIP_TRY(s, hipMemcpyAsync(sums, st->d_sums, (size_t)nc * sizeof(int32_t), hipMemcpyDeviceToHost, acc.stream));
-        if (scores) HIP_TRY(s, hipMemcpyAsync(scores, st->d_scores, (size_t)nc * sizeof(double), hipMemcpyDeviceToHost, acc.stream));
+        if (sums) HIP_TRY(s, hipMemcpyAsync(sums, st->d_sums.get(), (size_t)nc * sizeof(int32_t), hipMemcpyDeviceToHost, acc.stream));
+        if (scores) HIP_TRY(s, hipMemcpyAsync(scores, st->d_scores.get(), (size_t)nc * sizeof(double), hipMemcpyDeviceToHost, acc.stream));
         if (cells_xy) {
-            if ((rc = grow(s, &st->d_cells, &st->cells_cap, 2 * (size_t)ncell, (size_t)ncell)) != VISFS_BA_OK) return rc;
+            RC_TRY(st->d_cells.grow(s, 2 * (size_t)ncell, (size_t)ncell));
             hipLaunchKernelGGL(k_scan_cells, dim3((unsigned)((ncell + kThreads - 1) / kThreads)), dim3(kThreads), 0, acc.stream, st->d_pts(), st->d_rot(),
-                               P.n, ncell, P.gx, P.gy, P.L.res, P.L.max_x, P.L.max_y, st->d_cells);
+                               P.n, ncell, P.gx, P.gy, P.L.res, P.L.max_x, P.L.max_y, st->d_cells.get());
             HIP_TRY(s, hipGetLastError());
-            HIP_TRY(s, hipMemcpyAsync(cells_xy, st->d_cells, 2 * (size_t)ncell * sizeof(int32_t), hipMemcpyDeviceToHost, acc.stream));
+            HIP_TRY(s, hipMemcpyAsync(cells_xy, st->d_cells.get(), 2 * (size_t)ncell * sizeof(int32_t), hipMemcpyDeviceToHost, acc.stream));
         }
         HIP_TRY(s, hipStreamSynchronize(acc.stream));
         return (int)VISFS_BA_OK;

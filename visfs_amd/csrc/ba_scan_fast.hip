@@ -53,16 +53,6 @@ __global__ __launch_bounds__(kThreads) void k_fast_up(LevelView lo, int32_t w, i
 namespace {
 
 
-void stack_free(visfs_scan_stack* st) {
-    if (st->device) {
-        (void)hipSetDevice(st->dev);
-        if (st->stream) (void)hipStreamSynchronize(st->stream);
-        if (st->d_mem) (void)hipFree(st->d_mem);
-        block_free(st->blk);
-    }
-    scanrefine::state_free(st->refine);
-    delete st;
-}
 
 // The levels' sizes and places; VISFS_BA_ERR_UNSUPPORTED beyond 1 GiB.
 int stack_layout(visfs_scan_stack* st) {
@@ -100,20 +90,33 @@ int stack_build(visfs_scan_stack* st, const GridView& g) {
     int cus = 0;
     HIP_TRY(&st->err, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, st->dev));
     st->blocks = std::max(1, cus) * 8;
-    HIP_TRY(&st->err, hipMalloc(reinterpret_cast<void**>(&st->d_mem), items * 2));
-    for (int32_t h = 0; h < st->depth; ++h) st->lv.v[h].p = st->d_mem + st->off[h];
+    RC_TRY(st->d_mem.alloc(&st->err, items));
+    for (int32_t h = 0; h < st->depth; ++h) st->lv.v[h].p = st->d_mem.get() + st->off[h];
     const int64_t n0 = (int64_t)st->L.nx * st->L.ny;
-    hipLaunchKernelGGL(k_fast_base, dim3(blocks_for(n0, kThreads)), dim3(kThreads), 0, st->stream, g, st->L.nx, n0, st->d_mem);
+    hipLaunchKernelGGL(k_fast_base, dim3(blocks_for(n0, kThreads)), dim3(kThreads), 0, st->stream, g, st->L.nx, n0, st->d_mem.get());
     HIP_TRY(&st->err, hipGetLastError());
     for (int32_t h = 1; h < st->depth; ++h) {
         const LevelView& hi = st->lv.v[h];
         const int64_t nh = (int64_t)hi.w * hi.ht;
         hipLaunchKernelGGL(k_fast_up, dim3(blocks_for(nh, kThreads)), dim3(kThreads), 0, st->stream, st->lv.v[h - 1], hi.w, hi.e, 1 << (h - 1), nh,
-                           st->d_mem + st->off[h]);
+                           st->d_mem.get() + st->off[h]);
         HIP_TRY(&st->err, hipGetLastError());
     }
     HIP_TRY(&st->err, hipStreamSynchronize(st->stream));                          // the source grid may change or go from here on
     return VISFS_BA_OK;
+}
+
+// The stack of a grid in host memory: its device copy goes once the stream has been waited for, however the build ended.
+int stack_build_uploaded(visfs_scan_stack* st, GridView g) {
+    struct Wait { hipStream_t stream; ~Wait() { (void)hipStreamSynchronize(stream); } };
+    const size_t n = (size_t)g.nx * g.ny;
+    DeviceBuf<uint16_t> tmp;
+    HIP_TRY(&st->err, hipSetDevice(st->dev));
+    RC_TRY(tmp.alloc(&st->err, n));
+    const Wait before_tmp_goes{ st->stream };
+    HIP_TRY(&st->err, hipMemcpyAsync(tmp.get(), g.cells, n * 2, hipMemcpyHostToDevice, st->stream));
+    g.cells = tmp.get();
+    return stack_build(st, g);
 }
 
 }  // namespace
@@ -246,17 +249,6 @@ int host_search(const Levels& lv, const Search& s, Last& now, std::string& why) 
     return VISFS_BA_OK;
 }
 
-void block_free(CallBlock& b) {
-    if (b.h_up) (void)hipHostFree(b.h_up);
-    if (b.d_up) (void)hipFree(b.d_up);
-    if (b.d_cells) (void)hipFree(b.d_cells);
-    if (b.d_ctrl) (void)hipFree(b.d_ctrl);
-    if (b.h_ctrl) (void)hipHostFree(b.h_ctrl);
-    for (Bounds& x : b.bnd) if (x.p) (void)hipFree(x.p);
-    for (Frontier& f : b.fr) if (f.p) (void)hipFree(f.p);
-    b = CallBlock();
-}
-
 Last device_last(const Search& s, const Ctrl& c) {
     Last l;
     l.have = true; l.S = s.P.S; l.L = s.P.Lw; l.n = s.P.n; l.H = s.H; l.mH = s.mH; l.survivors = c.kept[0]; l.c = c;
@@ -279,8 +271,8 @@ int match_download(bool device, int dev, hipStream_t stream, const CallBlock& b,
         return VISFS_BA_OK;
     }
     HIP_TRY(&why, hipSetDevice(dev));
-    if (bounds) HIP_TRY(&why, hipMemcpyAsync(bounds, b.bnd[1].p + member * b.top, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-    if (survivors) HIP_TRY(&why, hipMemcpyAsync(survivors, b.fr[2].p + member * b.cap, (size_t)l.survivors * sizeof(int2), hipMemcpyDeviceToHost, stream));
+    if (bounds) HIP_TRY(&why, hipMemcpyAsync(bounds, b.bnd[1].get() + member * b.top, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    if (survivors) HIP_TRY(&why, hipMemcpyAsync(survivors, b.fr[2].get() + member * b.cap, (size_t)l.survivors * sizeof(int2), hipMemcpyDeviceToHost, stream));
     HIP_TRY(&why, hipStreamSynchronize(stream));
     if (survivors) {                                                       // the device appends unordered
         int2* sv = reinterpret_cast<int2*>(survivors);
@@ -333,7 +325,7 @@ int visfs_scan_stack_create(visfs_submaps* s, int32_t index, int32_t depth, visf
         st->device = acc.device; st->dev = acc.dev; st->stream = acc.stream;
         st->L = acc.L; st->depth = depth;
         rc = stack_build(st, acc.grid);
-        if (rc != VISFS_BA_OK) { (void)visfs_internal_scan_fail(s, rc, st->err.c_str()); stack_free(st); return rc; }
+        if (rc != VISFS_BA_OK) { (void)visfs_internal_scan_fail(s, rc, st->err.c_str()); delete st; return rc; }
         *out = st;
         return (int)VISFS_BA_OK;
     });
@@ -358,25 +350,15 @@ int visfs_scan_stack_create_from_grid(visfs_ba_handle* h, const visfs_submap_inf
         if (!h) rc = stack_build(st, g);
         else {
             st->device = true; st->dev = visfs_internal_device(h); st->stream = visfs_internal_stream(h);
-            uint16_t* tmp = nullptr;
-            auto run = [&]() -> int {
-                const size_t nb = (size_t)g.nx * g.ny * 2;
-                HIP_TRY(&st->err, hipSetDevice(st->dev));
-                HIP_TRY(&st->err, hipMalloc(reinterpret_cast<void**>(&tmp), nb));
-                HIP_TRY(&st->err, hipMemcpyAsync(tmp, cells, nb, hipMemcpyHostToDevice, st->stream));
-                g.cells = tmp;
-                return stack_build(st, g);                                 // ends with a wait on the stream
-            };
-            rc = run();
-            if (tmp) { (void)hipStreamSynchronize(st->stream); (void)hipFree(tmp); }
+            rc = stack_build_uploaded(st, g);
         }
-        if (rc != VISFS_BA_OK) { (void)bad(rc, st->err.c_str()); stack_free(st); return rc; }
+        if (rc != VISFS_BA_OK) { (void)bad(rc, st->err.c_str()); delete st; return rc; }
         *out = st;
         return (int)VISFS_BA_OK;
     });
 }
 
-void visfs_scan_stack_destroy(visfs_scan_stack* st) { if (st) stack_free(st); }
+void visfs_scan_stack_destroy(visfs_scan_stack* st) { delete st; }
 
 const char* visfs_scan_stack_last_error(const visfs_scan_stack* st) { return st ? st->err.c_str() : "null stack"; }
 
@@ -403,7 +385,7 @@ int visfs_scan_stack_match(visfs_scan_stack* st, const visfs_scan_stack_params* 
         int cur = 0;
         rc = device_run(st->blk, st->dev, st->stream, st->blocks, 1, &st, &s, &cur, st->err);
         if (rc != VISFS_BA_OK) return rc;
-        const Ctrl& c = st->blk.h_ctrl[0];
+        const Ctrl& c = st->blk.ctrl_h()[0];
         if (c.overflow) return fail(st, VISFS_BA_ERR_UNSUPPORTED, overflow_text(c.overflow - 1, s.cap));
         if (c.best_index < 0 || (int64_t)c.best_index >= s.P.candidates()) return fail(st, VISFS_BA_ERR_DEVICE, "the search returned no candidate");
         st->blk.hand_over(cur, s);                                         // only now: a failed call leaves the hook's arenas and `last`
@@ -454,7 +436,7 @@ int visfs_internal_stack_from_view(bool device, int dev, hipStream_t stream, con
             return stack_build(st, g);
         };
         const int rc = run();
-        if (rc != VISFS_BA_OK) { if (err) *err = st->err; stack_free(st); return rc; }
+        if (rc != VISFS_BA_OK) { if (err) *err = st->err; delete st; return rc; }
         *out = st;
         return (int)VISFS_BA_OK;
     });

@@ -371,61 +371,29 @@ struct visfs_scan_filter {
     std::vector<ScanHdr> hdr;
     std::vector<visfs_scan_filter_record> recs;
     std::vector<uint8_t> h_in_v, h_out_v;         // twin
-    uint8_t* h_in = nullptr;                      // device: pinned
-    uint8_t* h_out = nullptr;
-    uint8_t* d_in = nullptr;
-    uint8_t* d_out = nullptr;
-    uint8_t* d_work = nullptr;
-    size_t in_cap = 0, out_cap = 0, work_cap = 0;
+    Staged<uint8_t> in, res;                      // device: a call's scans and its results, bytes
+    DeviceBuf<uint8_t> d_work;
     host::Counts counts;
-    const uint8_t* out() const { return device ? h_out : h_out_v.data(); }
+    const uint8_t* out() const { return device ? res.h.get() : h_out_v.data(); }
+
+    ~visfs_scan_filter() {                        // before the members free what they own
+        if (!device) return;
+        (void)hipSetDevice(dev);
+        if (stream) (void)hipStreamSynchronize(stream);
+    }
 };
 
 namespace {
-
-
-void filter_free(visfs_scan_filter* f) {
-    if (f->device) {
-        (void)hipSetDevice(f->dev);
-        if (f->stream) (void)hipStreamSynchronize(f->stream);
-        if (f->h_in) (void)hipHostFree(f->h_in);
-        if (f->h_out) (void)hipHostFree(f->h_out);
-        if (f->d_in) (void)hipFree(f->d_in);
-        if (f->d_out) (void)hipFree(f->d_out);
-        if (f->d_work) (void)hipFree(f->d_work);
-    }
-    delete f;
-}
 
 size_t pad8(size_t v) { return (v + 7) & ~(size_t)7; }
 
 // Room for the call's three blocks; growing a block drops the results that lay in it.
 int device_room(visfs_scan_filter* f, size_t in_bytes, size_t out_bytes, size_t work_bytes) {
     HIP_TRY(f, hipSetDevice(f->dev));
-    if (f->in_cap < in_bytes) {
-        if (f->h_in) HIP_TRY(f, hipHostFree(f->h_in));
-        if (f->d_in) HIP_TRY(f, hipFree(f->d_in));
-        f->h_in = nullptr; f->d_in = nullptr; f->in_cap = 0;
-        HIP_TRY(f, hipHostMalloc(reinterpret_cast<void**>(&f->h_in), in_bytes, hipHostMallocDefault));
-        HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&f->d_in), in_bytes));
-        f->in_cap = in_bytes;
-    }
-    if (f->out_cap < out_bytes) {
-        f->m = 0;
-        if (f->h_out) HIP_TRY(f, hipHostFree(f->h_out));
-        if (f->d_out) HIP_TRY(f, hipFree(f->d_out));
-        f->h_out = nullptr; f->d_out = nullptr; f->out_cap = 0;
-        HIP_TRY(f, hipHostMalloc(reinterpret_cast<void**>(&f->h_out), out_bytes, hipHostMallocDefault));
-        HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&f->d_out), out_bytes));
-        f->out_cap = out_bytes;
-    }
-    if (f->work_cap < work_bytes) {
-        if (f->d_work) HIP_TRY(f, hipFree(f->d_work));
-        f->d_work = nullptr; f->work_cap = 0;
-        HIP_TRY(f, hipMalloc(reinterpret_cast<void**>(&f->d_work), work_bytes));
-        f->work_cap = work_bytes;
-    }
-    return VISFS_BA_OK;
+    RC_TRY(f->in.reserve(f, in_bytes, in_bytes));
+    if (f->res.cap() < out_bytes) f->m = 0;
+    RC_TRY(f->res.reserve(f, out_bytes, out_bytes));
+    return f->d_work.grow(f, work_bytes);
 }
 
 bool finite_n(const double* v, size_t n) {
@@ -473,7 +441,7 @@ int visfs_scan_filter_create(visfs_ba_handle* h, visfs_scan_filter** out) {
     });
 }
 
-void visfs_scan_filter_destroy(visfs_scan_filter* f) { if (f) filter_free(f); }
+void visfs_scan_filter_destroy(visfs_scan_filter* f) { delete f; }
 
 const char* visfs_scan_filter_last_error(const visfs_scan_filter* f) { return f ? f->err.c_str() : "null filter"; }
 
@@ -523,7 +491,7 @@ int visfs_scan_filter_process(visfs_scan_filter* f, const visfs_scan_filter_para
         uint8_t* out;
         if (f->device) {
             if (m > 0) { const int rc = device_room(f, in_bytes, out_bytes, work_bytes ? work_bytes : 8); if (rc != VISFS_BA_OK) return rc; }
-            in = f->h_in; out = f->h_out;
+            in = f->in.h.get(); out = f->res.h.get();
         } else {
             f->h_in_v.resize(in_bytes); f->h_out_v.resize(out_bytes);
             in = f->h_in_v.data(); out = f->h_out_v.data();
@@ -535,10 +503,10 @@ int visfs_scan_filter_process(visfs_scan_filter* f, const visfs_scan_filter_para
             for (int32_t b = 0; b < m; ++b)
                 if (hdr[(size_t)b].n) std::memcpy(in + hdr[(size_t)b].in_pts, scans[b].points_xyz, 24 * (size_t)hdr[(size_t)b].n);
             if (f->device) {
-                HIP_TRY(f, hipMemcpyAsync(f->d_in, in, in_bytes, hipMemcpyHostToDevice, f->stream));
-                hipLaunchKernelGGL(k_scan_filter, dim3((unsigned)m), dim3(kThreads), 0, f->stream, f->d_in, f->d_out, f->d_work, K);
+                HIP_TRY(f, hipMemcpyAsync(f->in.d.get(), in, in_bytes, hipMemcpyHostToDevice, f->stream));
+                hipLaunchKernelGGL(k_scan_filter, dim3((unsigned)m), dim3(kThreads), 0, f->stream, f->in.d.get(), f->res.d.get(), f->d_work.get(), K);
                 HIP_TRY(f, hipGetLastError());
-                HIP_TRY(f, hipMemcpyAsync(out, f->d_out, out_bytes, hipMemcpyDeviceToHost, f->stream));
+                HIP_TRY(f, hipMemcpyAsync(out, f->res.d.get(), out_bytes, hipMemcpyDeviceToHost, f->stream));
                 HIP_TRY(f, hipStreamSynchronize(f->stream));
                 f->counts = { 1, 2, 1 };
             } else {

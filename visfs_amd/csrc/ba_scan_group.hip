@@ -105,27 +105,23 @@ struct visfs_scan_group {
     CallBlock blk;
     // match_refine: the traces [m][kMaxTrials][kTraceItems] of the call in work ([0]) and of the hook ([1]); the twin's traces; the
     // trials per member of the last call that ran to its end
-    double* d_rtrace[2] = { nullptr, nullptr };
+    DeviceBuf<double> d_rtrace[2];
     std::vector<std::vector<double>> h_rtrace;
     std::vector<int32_t> rtrials;
     // the last call that ran to its end, per member (have = false: its status was not OK)
     std::vector<Last> last;
+
+    ~visfs_scan_group() {                     // before the members free what they own
+        if (!device) return;
+        (void)hipSetDevice(dev);
+        if (stream) (void)hipStreamSynchronize(stream);
+    }
 };
 
 namespace {
 
 thread_local std::string t_create_err;
 
-
-void group_free(visfs_scan_group* g) {
-    if (g->device) {
-        (void)hipSetDevice(g->dev);
-        if (g->stream) (void)hipStreamSynchronize(g->stream);
-        block_free(g->blk);
-        for (double* p : g->d_rtrace) if (p) (void)hipFree(p);
-    }
-    delete g;
-}
 
 std::string member_text(int32_t i, const std::string& why) { return "member " + std::to_string(i) + ": " + why; }
 
@@ -156,25 +152,15 @@ int scanfast::device_run(CallBlock& b, int dev, hipStream_t stream, int32_t bloc
     const size_t npts = 2 * (size_t)n, nrot = 2 * (size_t)S * m;
     const size_t match_bytes = (npts + nrot) * sizeof(double) + (size_t)m * sizeof(Member);
     const size_t bytes = match_bytes + (rp ? (size_t)m * sizeof(scanrefine::Job) : 0);
-    if (b.up_cap < bytes) {
-        if (b.h_up) HIP_TRY(&why, hipHostFree(b.h_up));
-        if (b.d_up) HIP_TRY(&why, hipFree(b.d_up));
-        b.h_up = b.d_up = nullptr; b.up_cap = 0;
-        const size_t want = bytes + bytes / 2;
-        HIP_TRY(&why, hipHostMalloc(reinterpret_cast<void**>(&b.h_up), want, hipHostMallocDefault));
-        HIP_TRY(&why, hipMalloc(reinterpret_cast<void**>(&b.d_up), want));
-        b.up_cap = want;
+    RC_TRY(b.up.reserve(&why, bytes, bytes + bytes / 2));
+    if (!b.ctrl_d() || !b.h_ctrl) {
+        RC_TRY(b.d_ctrl.alloc(&why, ctrl_bytes(m) + record_bytes(m)));
+        RC_TRY(b.h_ctrl.alloc(&why, ctrl_bytes(m) + record_bytes(m)));
     }
-    if (!b.d_ctrl) {
-        HIP_TRY(&why, hipMalloc(reinterpret_cast<void**>(&b.d_ctrl), ctrl_bytes(m) + record_bytes(m)));
-        HIP_TRY(&why, hipHostMalloc(reinterpret_cast<void**>(&b.h_ctrl), ctrl_bytes(m) + record_bytes(m), hipHostMallocDefault));
-    }
-    int rc;
-    if ((rc = grow(&why, &b.d_cells, &b.cells_cap, (size_t)m * (size_t)ncell)) != VISFS_BA_OK) return rc;
-    if ((rc = grow(&why, &b.bnd[0].p, &b.bnd[0].cap, (size_t)m * (size_t)total)) != VISFS_BA_OK) return rc;
-    for (int f = 0; f < 2; ++f)
-        if ((rc = grow(&why, &b.fr[f].p, &b.fr[f].cap, (size_t)m * (size_t)cap)) != VISFS_BA_OK) return rc;
-    double* hup = reinterpret_cast<double*>(b.h_up);
+    RC_TRY(b.d_cells.grow(&why, (size_t)m * (size_t)ncell));
+    RC_TRY(b.bnd[0].grow(&why, (size_t)m * (size_t)total));
+    for (int f = 0; f < 2; ++f) RC_TRY(b.fr[f].grow(&why, (size_t)m * (size_t)cap));
+    double* hup = reinterpret_cast<double*>(b.up.h.get());
     std::memcpy(hup, s0.P.pts.data(), npts * sizeof(double));
     Member* hmt = reinterpret_cast<Member*>(hup + npts + nrot);                // doubles in front of it: aligned to 8
     for (int32_t i = 0; i < m; ++i) {
@@ -185,40 +171,40 @@ int scanfast::device_run(CallBlock& b, int dev, hipStream_t stream, int32_t bloc
         std::memcpy(hmt + i, &M, sizeof M);
     }
     if (rp) {                                                              // the jobs point into the device's copies
-        const double* drot0 = reinterpret_cast<const double*>(b.d_up) + npts;
+        const double* drot0 = reinterpret_cast<const double*>(b.up.d.get()) + npts;
         for (int32_t i = 0; i < m; ++i) {
-            const scanrefine::Job J = match_job(mem[i], ss[i], min_score, b.d_ctrl + i, drot0 + 2 * (size_t)S * i);
-            std::memcpy(b.h_up + match_bytes + (size_t)i * sizeof J, &J, sizeof J);
+            const scanrefine::Job J = match_job(mem[i], ss[i], min_score, b.ctrl_d() + i, drot0 + 2 * (size_t)S * i);
+            std::memcpy(b.up.h.get() + match_bytes + (size_t)i * sizeof J, &J, sizeof J);
         }
     }
-    HIP_TRY(&why, hipMemcpyAsync(b.d_up, b.h_up, bytes, hipMemcpyHostToDevice, stream));
+    HIP_TRY(&why, hipMemcpyAsync(b.up.d.get(), b.up.h.get(), bytes, hipMemcpyHostToDevice, stream));
     ++b.counts.copies;
-    const double* d = reinterpret_cast<const double*>(b.d_up);
+    const double* d = reinterpret_cast<const double*>(b.up.d.get());
     const double* drot = d + npts;
     const Member* dmt = reinterpret_cast<const Member*>(drot + nrot);
     const dim3 fixed((unsigned)std::max(1, blocks / m), (unsigned)m), wg(kThreads);
-    hipLaunchKernelGGL(k_group_cells, dim3(blocks_for(ncell, kThreads), (unsigned)m), wg, 0, stream, d, drot, dmt, n, S, ncell, b.d_cells, b.d_ctrl);
+    hipLaunchKernelGGL(k_group_cells, dim3(blocks_for(ncell, kThreads), (unsigned)m), wg, 0, stream, d, drot, dmt, n, S, ncell, b.d_cells.get(), b.ctrl_d());
     HIP_TRY(&why, hipGetLastError()); ++b.counts.launches;
-    hipLaunchKernelGGL(k_group_bounds, fixed, wg, 0, stream, b.d_cells, ncell, n, dmt, nl, H, mH, total, b.bnd[0].p);
+    hipLaunchKernelGGL(k_group_bounds, fixed, wg, 0, stream, b.d_cells.get(), ncell, n, dmt, nl, H, mH, total, b.bnd[0].get());
     HIP_TRY(&why, hipGetLastError()); ++b.counts.launches;
-    hipLaunchKernelGGL(k_group_seeds, dim3((unsigned)S, (unsigned)m), wg, 0, stream, b.bnd[0].p, total, b.d_cells, ncell, n, dmt, nl, L, H, mH, b.d_ctrl);
+    hipLaunchKernelGGL(k_group_seeds, dim3((unsigned)S, (unsigned)m), wg, 0, stream, b.bnd[0].get(), total, b.d_cells.get(), ncell, n, dmt, nl, L, H, mH, b.ctrl_d());
     HIP_TRY(&why, hipGetLastError()); ++b.counts.launches;
     int cur = 0;                                                           // the frontiers of the level in work: fr[cur]
-    hipLaunchKernelGGL(k_group_keep, fixed, wg, 0, stream, b.bnd[0].p, total, H, b.fr[cur].p, cap, b.d_ctrl);
+    hipLaunchKernelGGL(k_group_keep, fixed, wg, 0, stream, b.bnd[0].get(), total, H, b.fr[cur].get(), cap, b.ctrl_d());
     HIP_TRY(&why, hipGetLastError()); ++b.counts.launches;
     for (int32_t h = H; h >= 1; --h) {
-        hipLaunchKernelGGL(k_group_level, fixed, wg, 0, stream, h, b.fr[cur].p, b.fr[1 - cur].p, cap, b.d_cells, ncell, n, dmt, nl, L, b.d_ctrl);
+        hipLaunchKernelGGL(k_group_level, fixed, wg, 0, stream, h, b.fr[cur].get(), b.fr[1 - cur].get(), cap, b.d_cells.get(), ncell, n, dmt, nl, L, b.ctrl_d());
         HIP_TRY(&why, hipGetLastError()); ++b.counts.launches;
         cur = 1 - cur;
     }
-    hipLaunchKernelGGL(k_group_best, dim3(1, (unsigned)m), wg, 0, stream, b.fr[cur].p, cap, b.d_ctrl);
+    hipLaunchKernelGGL(k_group_best, dim3(1, (unsigned)m), wg, 0, stream, b.fr[cur].get(), cap, b.ctrl_d());
     HIP_TRY(&why, hipGetLastError()); ++b.counts.launches;
     if (rp) {
-        HIP_TRY(&why, (hipError_t)scanrefine::launch_refine(stream, m, reinterpret_cast<const scanrefine::Job*>(b.d_up + match_bytes), *rp, d,
-                                                            records_of(b.d_ctrl, m), rtrace));
+        HIP_TRY(&why, (hipError_t)scanrefine::launch_refine(stream, m, reinterpret_cast<const scanrefine::Job*>(b.up.d.get() + match_bytes), *rp, d,
+                                                            records_of(b.ctrl_d(), m), rtrace));
         ++b.counts.launches;
     }
-    HIP_TRY(&why, hipMemcpyAsync(b.h_ctrl, b.d_ctrl, ctrl_bytes(m) + (rp ? record_bytes(m) : 0), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(&why, hipMemcpyAsync(b.h_ctrl.get(), b.d_ctrl.get(), ctrl_bytes(m) + (rp ? record_bytes(m) : 0), hipMemcpyDeviceToHost, stream));
     ++b.counts.copies;
     HIP_TRY(&why, hipStreamSynchronize(stream));
     ++b.counts.waits;
@@ -269,14 +255,14 @@ int group_match(visfs_scan_group* g, const visfs_scan_stack_params& p, const dou
     if (g->device) {
         if (rp) {
             HIP_TRY(&g->err, hipSetDevice(g->dev));
-            for (double*& t : g->d_rtrace)
-                if (!t) HIP_TRY(&g->err, hipMalloc(reinterpret_cast<void**>(&t), (size_t)m * scanrefine::kMaxTrials * scanrefine::kTraceItems * sizeof(double)));
+            for (DeviceBuf<double>& t : g->d_rtrace)
+                if (!t) RC_TRY(t.alloc(&g->err, (size_t)m * scanrefine::kMaxTrials * scanrefine::kTraceItems));
         }
         if ((rc = device_run(g->blk, g->dev, g->stream, g->blocks, m, g->mem.data(), ss.data(), &cur, g->err, rp ? &RP : nullptr, p.min_score,
-                             g->d_rtrace[0])) != VISFS_BA_OK)
+                             g->d_rtrace[0].get())) != VISFS_BA_OK)
             return rc;
         for (int32_t i = 0; i < m; ++i) {
-            const Ctrl& c = g->blk.h_ctrl[i];
+            const Ctrl& c = g->blk.ctrl_h()[i];
             const Search& s = ss[i];
             if (c.overflow) {
                 if (first_overflow.empty()) first_overflow = member_text(i, overflow_text(c.overflow - 1, s.cap));
@@ -315,7 +301,7 @@ int group_match(visfs_scan_group* g, const visfs_scan_stack_params& p, const dou
             const visfs_scan_match_result& w = results[i].match;
             if (!w.matched) { scanrefine::not_refined(VISFS_BA_OK, w.x, w.y, w.yaw, refined + i); continue; }
             if (g->device) {
-                refined[i] = records_of(g->blk.h_ctrl, m)[i];
+                refined[i] = records_of(g->blk.ctrl_h(), m)[i];
                 if (!refined[i].refined) return fail(g, VISFS_BA_ERR_DEVICE, member_text(i, "the refinement skipped a matched member"));
             } else {
                 const double start[3] = { w.x, w.y, w.yaw };
@@ -366,7 +352,7 @@ int visfs_scan_group_create(int32_t m, visfs_scan_stack* const* members, visfs_s
     });
 }
 
-void visfs_scan_group_destroy(visfs_scan_group* g) { if (g) group_free(g); }
+void visfs_scan_group_destroy(visfs_scan_group* g) { delete g; }
 
 const char* visfs_scan_group_last_error(const visfs_scan_group* g) { return g ? g->err.c_str() : t_create_err.c_str(); }
 
@@ -404,7 +390,7 @@ int visfs_scan_group_refine_download(visfs_scan_group* g, int32_t member, int32_
         const size_t bytes = (size_t)nt * scanrefine::kTraceItems * sizeof(double);
         if (!g->device) { std::memcpy(trace, g->h_rtrace[(size_t)member].data(), bytes); return (int)VISFS_BA_OK; }
         HIP_TRY(&g->err, hipSetDevice(g->dev));
-        HIP_TRY(&g->err, hipMemcpyAsync(trace, g->d_rtrace[1] + (size_t)member * scanrefine::kMaxTrials * scanrefine::kTraceItems, bytes, hipMemcpyDeviceToHost, g->stream));
+        HIP_TRY(&g->err, hipMemcpyAsync(trace, g->d_rtrace[1].get() + (size_t)member * scanrefine::kMaxTrials * scanrefine::kTraceItems, bytes, hipMemcpyDeviceToHost, g->stream));
         HIP_TRY(&g->err, hipStreamSynchronize(g->stream));
         return (int)VISFS_BA_OK;
     });

@@ -127,22 +127,14 @@ void not_refined(int32_t status, double x, double y, double yaw, visfs_scan_refi
 
 // the buffers of the single calls on one object
 struct State {
-    char* h_up = nullptr; char* d_up = nullptr; size_t up_cap = 0;
-    visfs_scan_refine_result* d_out = nullptr; visfs_scan_refine_result* h_out = nullptr;
-    double* d_trace[2] = { nullptr, nullptr };    // [0] of the call in work, [1] the hook's: they change hands after a call that ran to its end
+    Staged<char> up;
+    DeviceBuf<visfs_scan_refine_result> d_out; PinnedBuf<visfs_scan_refine_result> h_out;
+    DeviceBuf<double> d_trace[2];                 // [0] of the call in work, [1] the hook's: they change hands after a call that ran to its end
     std::vector<double> trace;                    // host twin
     int32_t trials = 0;                           // of the last successful call
 };
 
-void state_free(State* s) {
-    if (!s) return;
-    if (s->h_up) (void)hipHostFree(s->h_up);
-    if (s->d_up) (void)hipFree(s->d_up);
-    if (s->d_out) (void)hipFree(s->d_out);
-    if (s->h_out) (void)hipHostFree(s->h_out);
-    for (double* p : s->d_trace) if (p) (void)hipFree(p);
-    delete s;
-}
+void state_free(State* s) { delete s; }
 
 }  // namespace scanrefine
 
@@ -169,28 +161,20 @@ int run_single(State& st, bool device, int dev, hipStream_t stream, const Job& J
     }
     HIP_TRY(&why, hipSetDevice(dev));
     const size_t bytes = sizeof(Job) + pts.size() * sizeof(double);
-    if (st.up_cap < bytes) {
-        if (st.h_up) HIP_TRY(&why, hipHostFree(st.h_up));
-        if (st.d_up) HIP_TRY(&why, hipFree(st.d_up));
-        st.h_up = st.d_up = nullptr; st.up_cap = 0;
-        const size_t cap = bytes + bytes / 2;
-        HIP_TRY(&why, hipHostMalloc(reinterpret_cast<void**>(&st.h_up), cap, hipHostMallocDefault));
-        HIP_TRY(&why, hipMalloc(reinterpret_cast<void**>(&st.d_up), cap));
-        st.up_cap = cap;
+    RC_TRY(st.up.reserve(&why, bytes, bytes + bytes / 2));
+    if (!st.d_out || !st.h_out) {
+        RC_TRY(st.d_out.alloc(&why, 1));
+        RC_TRY(st.h_out.alloc(&why, 1));
     }
-    if (!st.d_out) {
-        HIP_TRY(&why, hipMalloc(reinterpret_cast<void**>(&st.d_out), sizeof(visfs_scan_refine_result)));
-        HIP_TRY(&why, hipHostMalloc(reinterpret_cast<void**>(&st.h_out), sizeof(visfs_scan_refine_result), hipHostMallocDefault));
-    }
-    for (double*& p : st.d_trace) if (!p) HIP_TRY(&why, hipMalloc(reinterpret_cast<void**>(&p), kTraceBytes));
-    std::memcpy(st.h_up, &J, sizeof(Job));
-    std::memcpy(st.h_up + sizeof(Job), pts.data(), pts.size() * sizeof(double));
-    HIP_TRY(&why, hipMemcpyAsync(st.d_up, st.h_up, bytes, hipMemcpyHostToDevice, stream));
-    HIP_TRY(&why, (hipError_t)launch_refine(stream, 1, reinterpret_cast<const Job*>(st.d_up), P, reinterpret_cast<const double*>(st.d_up + sizeof(Job)), st.d_out,
-                                     st.d_trace[0]));
-    HIP_TRY(&why, hipMemcpyAsync(st.h_out, st.d_out, sizeof(visfs_scan_refine_result), hipMemcpyDeviceToHost, stream));
+    for (DeviceBuf<double>& t : st.d_trace) if (!t) RC_TRY(t.alloc(&why, (size_t)kMaxTrials * kTraceItems));
+    std::memcpy(st.up.h.get(), &J, sizeof(Job));
+    std::memcpy(st.up.h.get() + sizeof(Job), pts.data(), pts.size() * sizeof(double));
+    HIP_TRY(&why, hipMemcpyAsync(st.up.d.get(), st.up.h.get(), bytes, hipMemcpyHostToDevice, stream));
+    HIP_TRY(&why, (hipError_t)launch_refine(stream, 1, reinterpret_cast<const Job*>(st.up.d.get()), P, reinterpret_cast<const double*>(st.up.d.get() + sizeof(Job)), st.d_out.get(),
+                                     st.d_trace[0].get()));
+    HIP_TRY(&why, hipMemcpyAsync(st.h_out.get(), st.d_out.get(), sizeof(visfs_scan_refine_result), hipMemcpyDeviceToHost, stream));
     HIP_TRY(&why, hipStreamSynchronize(stream));
-    *out = *st.h_out;
+    *out = *st.h_out.get();
     std::swap(st.d_trace[0], st.d_trace[1]);
     st.trials = out->trials;
     return VISFS_BA_OK;
@@ -204,7 +188,7 @@ int download_trace(State* st, bool device, int dev, hipStream_t stream, int32_t 
     const size_t bytes = (size_t)n * kTraceItems * sizeof(double);
     if (!device) { std::memcpy(trace, st->trace.data(), bytes); return VISFS_BA_OK; }
     HIP_TRY(&why, hipSetDevice(dev));
-    HIP_TRY(&why, hipMemcpyAsync(trace, st->d_trace[1], bytes, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(&why, hipMemcpyAsync(trace, st->d_trace[1].get(), bytes, hipMemcpyDeviceToHost, stream));
     HIP_TRY(&why, hipStreamSynchronize(stream));
     return VISFS_BA_OK;
 }

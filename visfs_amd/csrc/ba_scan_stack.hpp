@@ -16,8 +16,8 @@
 
 namespace scanfast {
 
-struct Frontier { int2* p = nullptr; size_t cap = 0; };
-struct Bounds { int32_t* p = nullptr; size_t cap = 0; };
+using Frontier = host::DeviceBuf<int2>;
+using Bounds = host::DeviceBuf<int32_t>;
 
 // the last successful match, as the hook reports it
 struct Last {
@@ -38,11 +38,13 @@ struct Search {
 // The device buffers of a call over m members, m fixed for the block's life (1: a stack's own, for its single calls): the upload
 // with its pinned source, and every other one an arena of m equal slices: the cells, the records with their pinned copy (behind them
 // room for m refinement records), bounds and frontiers of the call in work (bnd[0], fr[0], fr[1]) and those the hook reads (bnd[1],
-// fr[2]), which change hands in hand_over.  Made by the first call, let go by block_free.
+// fr[2]), which change hands in hand_over.  Made by the first call.
 struct CallBlock {
-    char* h_up = nullptr; char* d_up = nullptr; size_t up_cap = 0;
-    int2* d_cells = nullptr; size_t cells_cap = 0;
-    Ctrl* d_ctrl = nullptr; Ctrl* h_ctrl = nullptr;
+    host::Staged<char> up;
+    host::DeviceBuf<int2> d_cells;
+    host::DeviceBuf<char> d_ctrl; host::PinnedBuf<char> h_ctrl;      // Ctrl[m], then m refinement records
+    Ctrl* ctrl_d() const { return reinterpret_cast<Ctrl*>(d_ctrl.get()); }
+    Ctrl* ctrl_h() const { return reinterpret_cast<Ctrl*>(h_ctrl.get()); }
     Bounds bnd[2];
     Frontier fr[3];
     int64_t top = 0, cap = 0;                 // the strides of the hook's arenas: those of the last call handed over
@@ -75,13 +77,21 @@ struct visfs_scan_stack {
     std::string err;
     size_t off[scanfast::kMaxDepth] = {};     // in uint16 items
     std::vector<uint16_t> h_mem;
-    uint16_t* d_mem = nullptr;
+    host::DeviceBuf<uint16_t> d_mem;
     scanfast::Levels lv;
     // a match on the device: a block for one member, whatever groups the stack is a member of; handed over by successful calls
     // only, so a failed call leaves the hook's arenas and `last`
     scanfast::CallBlock blk;
     scanfast::Last last;
     scanrefine::State* refine = nullptr;
+
+    ~visfs_scan_stack() {                     // before the members free what they own
+        if (device) {
+            (void)hipSetDevice(dev);
+            if (stream) (void)hipStreamSynchronize(stream);
+        }
+        scanrefine::state_free(refine);
+    }
 };
 
 namespace scanfast {
@@ -101,8 +111,6 @@ void no_points(const double g[3], visfs_scan_stack_result* out);
 // on a frontier overflow VISFS_BA_ERR_UNSUPPORTED, on an empty result VISFS_BA_ERR_DEVICE, with `why`.
 int host_search(const Levels& lv, const Search& s, Last& now, std::string& why);
 
-// Every buffer of the block let go; the caller has selected the device and waited for the stream.
-void block_free(CallBlock& b);
 // The searches ss[0..m) of one scan, equal in S, nl, H, m_H and capacity, on the stacks mem[0..m) in one sequence on `stream`: one
 // upload, H + 5 launches, one download and one wait, `blocks` being the fixed grid of the striding kernels shared among the members.
 // Fills b.h_ctrl[0..m) and leaves member i's level-0 frontier in slice i of b.fr[*cur]; the hand-over is the caller's.  With `rp`

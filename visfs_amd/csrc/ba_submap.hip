@@ -271,6 +271,7 @@ struct visfs_submaps {
     visfs_ba_handle* h = nullptr;
     int dev = 0;
     hipStream_t stream = nullptr;
+    DeviceBuf<char> d_tables;                 // one allocation, the four tables below
     uint16_t *d_hit = nullptr, *d_miss = nullptr, *d_crop = nullptr;
     float* d_cost = nullptr;
     struct DSub {
@@ -280,15 +281,15 @@ struct visfs_submaps {
         Box known;                // in L's coordinates
         int count = 0;
         bool finished = false;
-        char* mem = nullptr;
+        DeviceBuf<char> mem;      // one allocation, the four arrays below
         uint16_t* cells = nullptr; float* cost = nullptr; uint32_t* hit = nullptr; uint32_t* miss = nullptr;
     };
     std::deque<DSub> dsubs;
     // the batch being staged: records in the coordinates of the limits in force at their insertion (ox, oy = growth at that point)
     std::vector<MarkRec> recs;
     int batch_n = 0;
-    MarkRec* h_recs = nullptr; size_t h_recs_cap = 0;
-    MarkRec* d_recs = nullptr; size_t d_recs_cap = 0;
+    PinnedBuf<MarkRec> h_recs;
+    DeviceBuf<MarkRec> d_recs;
     bool recs_in_flight = false;
 
     // the scan matcher's state (ba_scan.hip), freed with the sub-maps
@@ -296,38 +297,42 @@ struct visfs_submaps {
     void (*scan_destroy)(void*) = nullptr;
     void* refine_state = nullptr;
     void (*refine_destroy)(void*) = nullptr;
+
+    ~visfs_submaps() {                        // before the members free what they own; the two states went in visfs_submaps_destroy
+        if (!device) return;
+        (void)hipSetDevice(dev);
+        if (stream) (void)hipStreamSynchronize(stream);
+    }
 };
 
 namespace {
 
 
 // one allocation: cells, cost mirror, hit and miss marks
-int dsub_alloc(visfs_submaps* s, visfs_submaps::DSub& d, const Limits& L, char** mem, uint16_t** c, float** f, uint32_t** hm, uint32_t** mm) {
+int dsub_alloc(visfs_submaps* s, const Limits& L, DeviceBuf<char>& mem, uint16_t** c, float** f, uint32_t** hm, uint32_t** mm) {
     const size_t n = (size_t)L.nx * L.ny;
     const size_t b2 = up256(n * 2), b4 = up256(n * 4);
-    (void)d;
-    HIP_TRY(s, hipMalloc(reinterpret_cast<void**>(mem), b2 + 3 * b4));
-    *c = reinterpret_cast<uint16_t*>(*mem);
-    *f = reinterpret_cast<float*>(*mem + b2);
-    *hm = reinterpret_cast<uint32_t*>(*mem + b2 + b4);
-    *mm = reinterpret_cast<uint32_t*>(*mem + b2 + 2 * b4);
+    RC_TRY(mem.alloc(s, b2 + 3 * b4));
+    *c = reinterpret_cast<uint16_t*>(mem.get());
+    *f = reinterpret_cast<float*>(mem.get() + b2);
+    *hm = reinterpret_cast<uint32_t*>(mem.get() + b2 + b4);
+    *mm = reinterpret_cast<uint32_t*>(mem.get() + b2 + 2 * b4);
     return VISFS_BA_OK;
 }
 
 // the allocation follows the limits: a new (grown) allocation with the old cells moved by (gx, gy)
 int dsub_realize(visfs_submaps* s, visfs_submaps::DSub& d) {
     if (d.mem && d.La.nx == d.L.nx && d.La.ny == d.L.ny) return VISFS_BA_OK;
-    char* mem; uint16_t* c; float* f; uint32_t *hm, *mm;
-    int rc = dsub_alloc(s, d, d.L, &mem, &c, &f, &hm, &mm);
-    if (rc != VISFS_BA_OK) return rc;
+    DeviceBuf<char> mem; uint16_t* c; float* f; uint32_t *hm, *mm;
+    RC_TRY(dsub_alloc(s, d.L, mem, &c, &f, &hm, &mm));
     const int64_t n = (int64_t)d.L.nx * d.L.ny;
     hipLaunchKernelGGL(k_submap_grow, dim3(blocks_for(n, SM_T)), dim3(SM_T), 0, s->stream, d.cells, d.cost, d.La.nx, d.La.ny, d.gx, d.gy,
                        c, f, hm, mm, d.L.nx, n, s->tab.cost_f[0]);
     HIP_TRY(s, hipGetLastError());
-    if (d.mem) HIP_TRY(s, hipFree(d.mem));                              // (waits for the copy above)
-    d.mem = mem; d.cells = c; d.cost = f; d.hit = hm; d.miss = mm;
+    const int gone = d.mem.release(s);                                  // (waits for the copy above)
+    d.mem = std::move(mem); d.cells = c; d.cost = f; d.hit = hm; d.miss = mm;       // whatever the free said: nothing points into the old block
     d.La = d.L; d.gx = d.gy = 0;
-    return VISFS_BA_OK;
+    return gone;
 }
 
 int flush_batch(visfs_submaps* s) {
@@ -369,25 +374,15 @@ int flush_batch(visfs_submaps* s) {
     const size_t nrec = s->recs.size();
     if (nrec > 0) {
         if (s->recs_in_flight) { HIP_TRY(s, hipStreamSynchronize(s->stream)); s->recs_in_flight = false; }
-        if (s->h_recs_cap < nrec) {
-            if (s->h_recs) (void)hipHostFree(s->h_recs);
-            s->h_recs = nullptr; s->h_recs_cap = 0;
-            HIP_TRY(s, hipHostMalloc(reinterpret_cast<void**>(&s->h_recs), (nrec + nrec / 2) * sizeof(MarkRec), hipHostMallocDefault));
-            s->h_recs_cap = nrec + nrec / 2;
-        }
-        if (s->d_recs_cap < nrec) {
-            if (s->d_recs) HIP_TRY(s, hipFree(s->d_recs));
-            s->d_recs = nullptr; s->d_recs_cap = 0;
-            HIP_TRY(s, hipMalloc(reinterpret_cast<void**>(&s->d_recs), (nrec + nrec / 2) * sizeof(MarkRec)));
-            s->d_recs_cap = nrec + nrec / 2;
-        }
-        std::memcpy(s->h_recs, s->recs.data(), nrec * sizeof(MarkRec));
-        HIP_TRY(s, hipMemcpyAsync(s->d_recs, s->h_recs, nrec * sizeof(MarkRec), hipMemcpyHostToDevice, s->stream));
+        RC_TRY(s->h_recs.grow(s, nrec, nrec / 2));
+        RC_TRY(s->d_recs.grow(s, nrec, nrec / 2));
+        std::memcpy(s->h_recs.get(), s->recs.data(), nrec * sizeof(MarkRec));
+        HIP_TRY(s, hipMemcpyAsync(s->d_recs.get(), s->h_recs.get(), nrec * sizeof(MarkRec), hipMemcpyHostToDevice, s->stream));
         s->recs_in_flight = true;
         MarkArgs M{};
         for (int k = 0; k < ns; ++k) { M.hit[k] = s->dsubs[k].hit; M.miss[k] = s->dsubs[k].miss; M.nx[k] = s->dsubs[k].L.nx; M.ny[k] = s->dsubs[k].L.ny; }
         if (total > 0) {
-            hipLaunchKernelGGL(k_submap_mark, dim3(blocks_for(total, SM_T)), dim3(SM_T), 0, s->stream, s->d_recs, (int32_t)nrec, (int32_t)total, M);
+            hipLaunchKernelGGL(k_submap_mark, dim3(blocks_for(total, SM_T)), dim3(SM_T), 0, s->stream, s->d_recs.get(), (int32_t)nrec, (int32_t)total, M);
             HIP_TRY(s, hipGetLastError());
         }
         ApplyArgs A{};
@@ -418,20 +413,19 @@ int device_finish(visfs_submaps* s, visfs_submaps::DSub& d) {
     l.max_x = d.L.max_x - l.res * (double)offy;
     l.max_y = d.L.max_y - l.res * (double)offx;
     l.nx = cx; l.ny = cy;
-    char* mem; uint16_t* c; float* f; uint32_t *hm, *mm;
-    int rc = dsub_alloc(s, d, l, &mem, &c, &f, &hm, &mm);
-    if (rc != VISFS_BA_OK) return rc;
+    DeviceBuf<char> mem; uint16_t* c; float* f; uint32_t *hm, *mm;
+    RC_TRY(dsub_alloc(s, l, mem, &c, &f, &hm, &mm));
     const int64_t n = (int64_t)cx * cy;
     hipLaunchKernelGGL(k_submap_crop, dim3(blocks_for(n, SM_T)), dim3(SM_T), 0, s->stream, d.cells, d.L.nx, offx, offy, c, f, hm, mm, cx, n, s->d_crop, s->d_cost);
     HIP_TRY(s, hipGetLastError());
-    HIP_TRY(s, hipFree(d.mem));
-    d.mem = mem; d.cells = c; d.cost = f; d.hit = hm; d.miss = mm;
+    const int gone = d.mem.release(s);
+    d.mem = std::move(mem); d.cells = c; d.cost = f; d.hit = hm; d.miss = mm;
     d.L = d.La = l; d.gx = d.gy = 0;
     Box b;
     if (!d.known.empty()) { b.extend(0, 0); b.extend(cx - 1, cy - 1); }              // every cell of the old known box's border rows is known
     d.known = b;
     d.finished = true;
-    return VISFS_BA_OK;
+    return gone;                                                        // a failed free is reported; the sub-map stands on its new block
 }
 
 // stage one range data into the batch: growth (host-simulated), the insertion's records with the limits in force at it
@@ -475,10 +469,10 @@ int device_insert(visfs_submaps* s, const double T[12], const Transformed& t) {
     int rc;
     if (s->dsubs.empty() || s->dsubs.back().count == limit) {                              // addSubmap (the front, finished, dropped)
         if ((rc = flush_batch(s)) != VISFS_BA_OK) return rc;
-        if (s->dsubs.size() >= 2) { if (s->dsubs.front().mem) HIP_TRY(s, hipFree(s->dsubs.front().mem)); s->dsubs.pop_front(); }
+        if (s->dsubs.size() >= 2) { const int gone = s->dsubs.front().mem.release(s); s->dsubs.pop_front(); RC_TRY(gone); }
         visfs_submaps::DSub d;
         d.L = initial_limits(s->prm.map_resolution, T);
-        s->dsubs.push_back(d);
+        s->dsubs.push_back(std::move(d));
         if ((rc = dsub_realize(s, s->dsubs.back())) != VISFS_BA_OK) return rc;
     }
     for (const visfs_submaps::DSub& d : s->dsubs)
@@ -545,18 +539,6 @@ int check_params(const visfs_submap_params* p, std::string& why) {
     return VISFS_BA_OK;
 }
 
-void release(visfs_submaps* s) {
-    if (!s->device) return;
-    (void)hipSetDevice(s->dev);
-    if (s->stream) (void)hipStreamSynchronize(s->stream);
-    for (auto& d : s->dsubs) if (d.mem) (void)hipFree(d.mem);
-    s->dsubs.clear();
-    if (s->d_hit) (void)hipFree(s->d_hit);
-    if (s->d_recs) (void)hipFree(s->d_recs);
-    if (s->h_recs) (void)hipHostFree(s->h_recs);
-    s->d_hit = nullptr; s->d_recs = nullptr; s->h_recs = nullptr;
-}
-
 }  // namespace
 
 // ====================================================================== exported C ABI
@@ -600,8 +582,8 @@ int visfs_submaps_create(visfs_ba_handle* h, const visfs_submap_params* p, visfs
             HIP_TRY(s, hipSetDevice(s->dev));
             // the tables, one allocation: hit, miss (without the update marker), crop round trip (uint16), cost (float)
             const size_t b2 = up256((size_t)kValueCount * 2), b4 = up256((size_t)kValueCount * 4);
-            char* mem = nullptr;
-            HIP_TRY(s, hipMalloc(reinterpret_cast<void**>(&mem), 3 * b2 + b4));
+            RC_TRY(s->d_tables.alloc(s, 3 * b2 + b4));
+            char* const mem = s->d_tables.get();
             s->d_hit = reinterpret_cast<uint16_t*>(mem); s->d_miss = reinterpret_cast<uint16_t*>(mem + b2);
             s->d_crop = reinterpret_cast<uint16_t*>(mem + 2 * b2); s->d_cost = reinterpret_cast<float*>(mem + 3 * b2);
             std::vector<uint16_t> hit(kValueCount), miss(kValueCount);
@@ -613,7 +595,7 @@ int visfs_submaps_create(visfs_ba_handle* h, const visfs_submap_params* p, visfs
             return VISFS_BA_OK;
         };
         rc = init();
-        if (rc != VISFS_BA_OK) { visfs_internal_set_error(h, s->err.c_str()); release(s); delete s; return rc; }
+        if (rc != VISFS_BA_OK) { visfs_internal_set_error(h, s->err.c_str()); delete s; return rc; }
         *out = s;
         return (int)VISFS_BA_OK;
     });
@@ -631,7 +613,6 @@ void visfs_submaps_destroy(visfs_submaps* s) {
         s->refine_destroy(s->refine_state);
         s->refine_state = nullptr;
     }
-    release(s);
     delete s;
 }
 

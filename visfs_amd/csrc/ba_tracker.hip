@@ -687,10 +687,10 @@ __global__ __launch_bounds__(TK_T) void k_trk_finish_g(const TrkRec* __restrict_
 // [PyrRec n][ClaheRec n][CornerRec n: bootstrap][CornerRec n: top-up][TrkRec n][CullRec n][PnpRec n][InHead n][outlier ids of the
 // members, one behind the other]
 struct CallBlock {
-    char* pinned = nullptr; char* dev = nullptr;
+    PinnedBuf<char> pinned; DeviceBuf<char> dev;
     size_t off_pyr = 0, off_clahe = 0, off_boot = 0, off_top = 0, off_trk = 0, off_cull = 0, off_pnp = 0, off_in = 0, off_ids = 0, bytes = 0;
 
-    hipError_t allocate(size_t n) {            // the caller has selected the device
+    template <class S> int allocate(S sink, size_t n) {       // the caller has selected the device
         size_t off = 0;
         const auto take = [&](size_t b) { const size_t at = off; off = (off + b + 255) & ~size_t(255); return at; };
         off_pyr = take(n * sizeof(PyrRec));
@@ -703,15 +703,10 @@ struct CallBlock {
         off_in = take(n * sizeof(InHead));
         off_ids = take(n * sizeof(uint64_t) * kMaxOutliers);
         bytes = off;
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&dev), bytes);
-        if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&pinned), bytes, hipHostMallocDefault);
-        if (e == hipSuccess) std::memset(pinned, 0, bytes);
-        return e;
-    }
-    void release() {                           // the caller has waited for the stream that read it
-        if (dev) (void)hipFree(dev);
-        if (pinned) (void)hipHostFree(pinned);
-        dev = pinned = nullptr;
+        RC_TRY(dev.alloc(sink, bytes));
+        RC_TRY(pinned.alloc(sink, bytes));
+        std::memset(pinned.get(), 0, bytes);
+        return VISFS_BA_OK;
     }
 };
 
@@ -732,10 +727,13 @@ struct visfs_tracker {
     // host restatement: the same blocks in host memory
     std::vector<char> h_work, h_outblk, h_inblk;
     // device
-    char* d_work = nullptr; char* d_out = nullptr;
-    char* p_out = nullptr;                                                        // pinned
+    struct Owned {                             // gone with the flow object (free_device), which the tracker may outlive
+        DeviceBuf<char> d_work, d_out;
+        PinnedBuf<char> p_out;
+        DeviceBuf<char> d_pnp;                 // the pose guess: rows, winner key, hypotheses, passes
+        CallBlock blk;                         // the tables of a single call: a group of one
+    } own;
     size_t out_bytes = 0;
-    CallBlock blk;                             // the tables of a single call: a group of one
 
     Bufs B{};                                  // where the kernels (or the host steps) work
     Out R{};                                   // where the caller reads: the pinned copy, or the host twin's block itself
@@ -749,7 +747,6 @@ struct visfs_tracker {
     visfs_pnp_camera pnp_cam{};
     pnp::PnpShape pnp_shape{};
     pnp::PnpRec pnp_rec{};                     // device: where the stages work
-    char* d_pnp = nullptr;                     // device: rows, winner key, hypotheses, passes
     size_t out_base_bytes = 0;                 // the output block of a tracker without the pose guess; what a call brings down with it off
     visfs_pnp* pnp_host = nullptr;             // host twin: the staged host solver its steps run on
     visfs_tracker_pnp_result pnp_res{};
@@ -770,6 +767,12 @@ struct visfs_tracker_group {
     int dev = 0;
     hipStream_t stream = nullptr;
     CallBlock blk;                             // the tables of a call of all members
+
+    ~visfs_tracker_group() {                   // before the members free what they own
+        if (!device) return;
+        (void)hipSetDevice(dev);
+        if (stream) (void)hipStreamSynchronize(stream);
+    }
 };
 
 namespace {
@@ -787,12 +790,7 @@ void free_device(visfs_tracker* t) {
     if (!f || !f->device) return;
     (void)hipSetDevice(f->dev);
     if (f->stream) (void)hipStreamSynchronize(f->stream);
-    if (t->d_work) (void)hipFree(t->d_work);
-    if (t->d_out) (void)hipFree(t->d_out);
-    if (t->p_out) (void)hipHostFree(t->p_out);
-    if (t->d_pnp) (void)hipFree(t->d_pnp);
-    t->blk.release();
-    t->d_work = t->d_out = t->p_out = t->d_pnp = nullptr;
+    t->own = visfs_tracker::Owned();
 }
 
 int allocate(visfs_tracker* t) {
@@ -815,16 +813,16 @@ int allocate(visfs_tracker* t) {
         return VISFS_BA_OK;
     }
     HIP_TRY(t, hipSetDevice(f->dev));
-    HIP_TRY(t, hipMalloc(reinterpret_cast<void**>(&t->d_work), work_bytes));
-    HIP_TRY(t, hipMalloc(reinterpret_cast<void**>(&t->d_out), t->out_bytes));
-    HIP_TRY(t, hipHostMalloc(reinterpret_cast<void**>(&t->p_out), t->out_bytes, hipHostMallocDefault));
-    HIP_TRY(t, t->blk.allocate(1));
-    carve_work(t->d_work, M, t->hw.size(), H, B, &hw);
-    carve_out(t->d_out, M, false, B.o);
-    carve_out(t->p_out, M, false, t->R);              // (B.in and B.outliers of a call point into the block the call goes through)
-    std::memset(t->p_out, 0, t->out_bytes);
-    HIP_TRY(t, hipMemsetAsync(t->d_work, 0, work_bytes, f->stream));
-    HIP_TRY(t, hipMemsetAsync(t->d_out, 0, t->out_bytes, f->stream));
+    RC_TRY(t->own.d_work.alloc(t, work_bytes));
+    RC_TRY(t->own.d_out.alloc(t, t->out_bytes));
+    RC_TRY(t->own.p_out.alloc(t, t->out_bytes));
+    RC_TRY(t->own.blk.allocate(t, 1));
+    carve_work(t->own.d_work.get(), M, t->hw.size(), H, B, &hw);
+    carve_out(t->own.d_out.get(), M, false, B.o);
+    carve_out(t->own.p_out.get(), M, false, t->R);              // (B.in and B.outliers of a call point into the block the call goes through)
+    std::memset(t->own.p_out.get(), 0, t->out_bytes);
+    HIP_TRY(t, hipMemsetAsync(t->own.d_work.get(), 0, work_bytes, f->stream));
+    HIP_TRY(t, hipMemsetAsync(t->own.d_out.get(), 0, t->out_bytes, f->stream));
     HIP_TRY(t, hipMemcpyAsync(hw, t->hw.data(), t->hw.size() * sizeof(int32_t), hipMemcpyHostToDevice, f->stream));
     HIP_TRY(t, hipStreamSynchronize(f->stream));                        // t->hw may move; nothing else waits here
     return VISFS_BA_OK;
@@ -1208,15 +1206,15 @@ int run_call(visfs_tracker* const* m, int n, const visfs_tracker_frame* fr, cons
     HIP_TRY(fault, hipSetDevice(device));
     HIP_TRY(fault, hipStreamSynchronize(stream));
     ++cnt.waits;
-    PyrRec* pyr = reinterpret_cast<PyrRec*>(blk.pinned + blk.off_pyr);
-    ClaheRec* clr = reinterpret_cast<ClaheRec*>(blk.pinned + blk.off_clahe);
-    CornerRec* cboot = reinterpret_cast<CornerRec*>(blk.pinned + blk.off_boot);
-    CornerRec* ctop = reinterpret_cast<CornerRec*>(blk.pinned + blk.off_top);
-    TrkRec* trk = reinterpret_cast<TrkRec*>(blk.pinned + blk.off_trk);
-    fund::CullRec* cull = reinterpret_cast<fund::CullRec*>(blk.pinned + blk.off_cull);
-    pnp::PnpRec* pnr = reinterpret_cast<pnp::PnpRec*>(blk.pinned + blk.off_pnp);
-    InHead* inh = reinterpret_cast<InHead*>(blk.pinned + blk.off_in);
-    uint64_t* ids = reinterpret_cast<uint64_t*>(blk.pinned + blk.off_ids);
+    PyrRec* pyr = reinterpret_cast<PyrRec*>(blk.pinned.get() + blk.off_pyr);
+    ClaheRec* clr = reinterpret_cast<ClaheRec*>(blk.pinned.get() + blk.off_clahe);
+    CornerRec* cboot = reinterpret_cast<CornerRec*>(blk.pinned.get() + blk.off_boot);
+    CornerRec* ctop = reinterpret_cast<CornerRec*>(blk.pinned.get() + blk.off_top);
+    TrkRec* trk = reinterpret_cast<TrkRec*>(blk.pinned.get() + blk.off_trk);
+    fund::CullRec* cull = reinterpret_cast<fund::CullRec*>(blk.pinned.get() + blk.off_cull);
+    pnp::PnpRec* pnr = reinterpret_cast<pnp::PnpRec*>(blk.pinned.get() + blk.off_pnp);
+    InHead* inh = reinterpret_cast<InHead*>(blk.pinned.get() + blk.off_in);
+    uint64_t* ids = reinterpret_cast<uint64_t*>(blk.pinned.get() + blk.off_ids);
     size_t n_ids = 0;
     bool any_active = false, any_boot = false;
     int32_t bound = 0;
@@ -1238,8 +1236,8 @@ int run_call(visfs_tracker* const* m, int n, const visfs_tracker_frame* fr, cons
         const bool skip = P.no_previous;
         TrkRec& r = trk[i];
         r.B = t->B;
-        r.B.in = reinterpret_cast<const InHead*>(blk.dev + blk.off_in) + i;
-        r.B.outliers = reinterpret_cast<const uint64_t*>(blk.dev + blk.off_ids) + n_ids;
+        r.B.in = reinterpret_cast<const InHead*>(blk.dev.get() + blk.off_in) + i;
+        r.B.outliers = reinterpret_cast<const uint64_t*>(blk.dev.get() + blk.off_ids) + n_ids;
         inh[i] = InHead{ fr[i].n_outliers, 0 };
         if (fr[i].n_outliers > 0) std::memcpy(ids + n_ids, fr[i].outlier_ids, sizeof(uint64_t) * (size_t)fr[i].n_outliers);
         n_ids += (size_t)fr[i].n_outliers;
@@ -1264,9 +1262,9 @@ int run_call(visfs_tracker* const* m, int n, const visfs_tracker_frame* fr, cons
             t->have_call = false;
         }
     }
-    HIP_TRY(fault, hipMemcpyAsync(blk.dev, blk.pinned, blk.off_ids + sizeof(uint64_t) * n_ids, hipMemcpyHostToDevice, stream));
+    HIP_TRY(fault, hipMemcpyAsync(blk.dev.get(), blk.pinned.get(), blk.off_ids + sizeof(uint64_t) * n_ids, hipMemcpyHostToDevice, stream));
     ++cnt.copies;
-    const auto dev = [&](size_t off) { return blk.dev + off; };
+    const auto dev = [&](size_t off) { return blk.dev.get() + off; };
     int rc;
     if (clahe_on) {
         rc = group_clahe(f0, geom, n, reinterpret_cast<const ClaheRec*>(dev(blk.off_clahe)), &cnt);
@@ -1319,7 +1317,7 @@ int run_call(visfs_tracker* const* m, int n, const visfs_tracker_frame* fr, cons
         for (int i = 0; i < n; ++i) {
             if (plan[i].no_previous) continue;
             visfs_tracker* t = m[i];
-            HIP_TRY(fault, hipMemcpyAsync(t->p_out, t->d_out, pnp_on ? t->out_bytes : t->out_base_bytes, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(fault, hipMemcpyAsync(t->own.p_out.get(), t->own.d_out.get(), pnp_on ? t->out_bytes : t->out_base_bytes, hipMemcpyDeviceToHost, stream));
             ++cnt.copies;
         }
     }
@@ -1435,7 +1433,7 @@ int visfs_tracker_process(visfs_tracker* t, const uint8_t* left, const uint8_t* 
             const visfs_tracker_frame fr{ left, right, stride, delta_guess, n_outliers, outlier_ids };
             GroupCounts counts;
             CallFault fault;
-            const int rc = run_call(&t, 1, &fr, &P, t->blk, f->dev, f->stream, &counts, &fault);
+            const int rc = run_call(&t, 1, &fr, &P, t->own.blk, f->dev, f->stream, &counts, &fault);
             if (rc != VISFS_BA_OK) { t->ids.clear(); return fail(t, rc, fault.why); }
             return commit_member(t, P, result);
         }
@@ -1602,28 +1600,26 @@ int visfs_tracker_enable_pnp(visfs_tracker* t, const visfs_pnp_params* p) {
             const size_t state_bytes = carve(c, q, scratch);
             Out sized{};
             const size_t out_bytes = carve_out(nullptr, M, true, sized);
-            char *d_pnp = nullptr, *d_out = nullptr, *p_out = nullptr;
-            hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_pnp), state_bytes);
-            if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_out), out_bytes);
-            if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&p_out), out_bytes, hipHostMallocDefault);
-            if (e == hipSuccess) e = hipMemsetAsync(d_pnp, 0, state_bytes, f->stream);
-            if (e == hipSuccess) e = hipMemsetAsync(d_out, 0, out_bytes, f->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(f->stream);
-            if (e != hipSuccess) {
-                if (d_pnp) (void)hipFree(d_pnp);
-                if (d_out) (void)hipFree(d_out);
-                if (p_out) (void)hipHostFree(p_out);
-                return fail(t, VISFS_BA_ERR_DEVICE, std::string("the buffers of the pose guess: ") + hipGetErrorString(e));
-            }
-            std::memset(p_out, 0, out_bytes);
-            if (t->d_pnp) (void)hipFree(t->d_pnp);
-            (void)hipFree(t->d_out);
-            (void)hipHostFree(t->p_out);
-            t->d_pnp = d_pnp; t->d_out = d_out; t->p_out = p_out; t->out_bytes = out_bytes;
-            Carver k{ d_pnp };
+            DeviceBuf<char> d_pnp, d_out;
+            PinnedBuf<char> p_out;
+            std::string why;
+            const int made = [&]() -> int {
+                RC_TRY(d_pnp.alloc(&why, state_bytes));
+                RC_TRY(d_out.alloc(&why, out_bytes));
+                RC_TRY(p_out.alloc(&why, out_bytes));
+                hipError_t e = hipMemsetAsync(d_pnp.get(), 0, state_bytes, f->stream);
+                if (e == hipSuccess) e = hipMemsetAsync(d_out.get(), 0, out_bytes, f->stream);
+                if (e == hipSuccess) e = hipStreamSynchronize(f->stream);
+                if (e != hipSuccess) { why = hipGetErrorString(e); return VISFS_BA_ERR_DEVICE; }
+                return VISFS_BA_OK;
+            }();
+            if (made != VISFS_BA_OK) return fail(t, VISFS_BA_ERR_DEVICE, "the buffers of the pose guess: " + why);
+            std::memset(p_out.get(), 0, out_bytes);
+            t->own.d_pnp = std::move(d_pnp); t->own.d_out = std::move(d_out); t->own.p_out = std::move(p_out); t->out_bytes = out_bytes;
+            Carver k{ t->own.d_pnp.get() };
             carve(k, q, t->B);
-            carve_out(d_out, M, true, t->B.o);
-            carve_out(p_out, M, true, t->R);
+            carve_out(t->own.d_out.get(), M, true, t->B.o);
+            carve_out(t->own.p_out.get(), M, true, t->R);
             q.m = &t->B.ctl->pnp_m; q.rows = t->B.pnp_rows; q.key = t->B.pnp_key;
             q.res = t->B.o.p_res; q.inliers = t->B.o.p_inl;
             q.K = pnp::Cam{ cam.fx, cam.fy, cam.cx, cam.cy };
@@ -1747,13 +1743,6 @@ bool same_pnp(const visfs_tracker* a, const visfs_tracker* b) {
            p.refine_iterations == q.refine_iterations && p.refine_sigma == q.refine_sigma && p.seed == q.seed;
 }
 
-void free_group(visfs_tracker_group* g) {
-    if (!g->device) return;
-    (void)hipSetDevice(g->dev);
-    if (g->stream) (void)hipStreamSynchronize(g->stream);
-    g->blk.release();
-}
-
 }  // namespace
 
 extern "C" {
@@ -1788,9 +1777,10 @@ int visfs_tracker_group_create(int32_t n, visfs_tracker* const* members, visfs_t
         if (g->device) {
             g->dev = f0->dev; g->stream = f0->stream;
             int rc = VISFS_BA_OK;
-            hipError_t e = hipSetDevice(g->dev);
-            if (e == hipSuccess) e = g->blk.allocate((size_t)n);
-            if (e != hipSuccess) rc = gfail(g, VISFS_BA_ERR_DEVICE, -1, std::string("the group's call block: ") + hipGetErrorString(e));
+            std::string why;
+            const hipError_t e = hipSetDevice(g->dev);
+            if (e != hipSuccess) why = hipGetErrorString(e);
+            if (e != hipSuccess || g->blk.allocate(&why, (size_t)n) != VISFS_BA_OK) rc = gfail(g, VISFS_BA_ERR_DEVICE, -1, "the group's call block: " + why);
             for (int i = 0; i < n && rc == VISFS_BA_OK; ++i) {
                 visfs_flow* f = members[i]->f;
                 rc = group_corners_prepare(f);
@@ -1799,7 +1789,6 @@ int visfs_tracker_group_create(int32_t n, visfs_tracker* const* members, visfs_t
             }
             if (rc != VISFS_BA_OK) {
                 g_create_err = g->err;
-                free_group(g);
                 delete g;
                 return rc;
             }
@@ -1817,7 +1806,6 @@ void visfs_tracker_group_destroy(visfs_tracker_group* g) {
     if (!g) return;
     for (visfs_tracker* t : g->m)
         if (t) t->group = nullptr;
-    free_group(g);
     delete g;
 }
 
